@@ -1,9 +1,20 @@
 #!/usr/bin/env python3
 """bench.py -- the reference's headline benchmark on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline needs: set up, W warm-up steps, K timed steps, the outputs if
+--dump-outputs is given, one JSON line.  Everything else the benchmark measures or checks runs only with
+--full: at N = 1 the CPU baseline, the read calibration, the other BASELINE configs and the C-level multi-GPU
+step; at N > 1 the allgather and bcast exchanges, the strong-scaling leg, each piece of a step alone (and the
+roofline of the multiply-only pass) and the C-level multi-GPU host.
+
+--dump-outputs DIR: after the timed steps, y of the last step (what a caller of spmv() receives) goes to
+DIR/y.npy (N > 1: DIR/y_rank<r>.npy, this rank's row block) in the value dtype.  A y larger than the share of
+DUMP_BYTES is sampled: the rows are the first entries of np.random.default_rng(DUMP_SEED + rank).permutation(m),
+sorted -- the same rows in every run, like the inputs, so that two builds can be compared output for output.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment: this process -- before it touches any GPU --
 starts N rank processes itself (one per device, LOCAL_RANK = device) and relays rank 0's JSON line; it fails
@@ -17,7 +28,7 @@ Workload at N = 1 = BASELINE config 2: CSR fp64, 1e7 x 1e7, exactly 32 nnz/row, 
 (SURVEY 8d variant (i)), schedule Method_Parallel = CSR-vector.  At N > 1 = config 5 scaled
 weakly: every rank holds a 1e7-row block of the (N*1e7)^2 banded matrix (local int32 RowPtr,
 global columns) and the matching slice of x; each step first exchanges x over RCCL
-(spmv_amd.dist) and then multiplies; y stays distributed.  All three exchanges are run and reported
+(spmv_amd.dist) and then multiplies; y stays distributed.  With --full all three exchanges are run and reported
 in the one JSON line ("exchanges"): "halo" (the library's default: only the referenced entries move,
 point to point; `value` is this one), "allgather" (every rank gathers the whole x each step: the
 solver-style loop) and "bcast" (north_star's literal broadcast of x from rank 0), each with the
@@ -28,7 +39,7 @@ barrier + torch.cuda.synchronize() pairs, MAX over ranks, rank 0 prints ONE JSON
 `value` = 2 * nnz(all ranks) * K / time (FLOPs per SpMV = 2 nnz: test_spmv.c:126).
 
 roofline (the dominant kernel; measured live): HIP events on the stream the kernel is launched on
-bracket the launches (N = 1: the K timed steps themselves; N > 1: a multiply-only pass after them).  Three fractions of the
+bracket the launches (N = 1: the K timed steps themselves; N > 1, --full: a multiply-only pass after them).  Three fractions of the
 8 TB/s HBM peak are reported side by side, over the same mean launch time:
   frac_alg     = SURVEY 8d's ALGORITHMIC bytes B_alg = 4(m+1) + nnz(4+s) + s n + s m ("achieved_alg").  The accounting figure of the
                  metric; an EFFECTIVE rate -- it charges 4 B/nnz of ColIdx, which the staged schedules replace by a 2 B (BYTE tiles: 1 B,
@@ -41,7 +52,7 @@ bracket the launches (N = 1: the K timed steps themselves; N > 1: a multiply-onl
   frac / achieved = frac_counter when there is one, else frac_model ("frac_source" says which): the physical HBM rate.
   traffic      = the counter bytes (or null);  read_calibration = a pure 16 B/lane read of the same byte count, same box, same run
                  (spmv_amd/bin/gbench read): the ceiling the rates sit under.
-`cpu_baseline` (rank 0, N = 1): the real reference's OpenMP path (oracle/_ref, Method_Parallel,
+`cpu_baseline` (rank 0, N = 1, --full): the real reference's OpenMP path (oracle/_ref, Method_Parallel,
 kind "reference") or, if that library is absent, the oracle's OpenMP port, on the first
 --cpu-rows rows of the same matrix, with the GPU result checked against it.
 """
@@ -62,9 +73,11 @@ os.environ.setdefault("OMP_PLACES", "cores")
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md "HBM3E peak BW 8.0 TB/s spec"
+DUMP_BYTES = 60 << 20   # --dump-outputs: all files together stay under 64 MB
+DUMP_SEED = 20250301
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)   # test_spmv.c:103-124: 10 warm + 100 timed
@@ -75,8 +88,12 @@ def parse():
     ap.add_argument("--workload", default="banded", choices=["banded", "random", "powerlaw"],
                     help="headline matrix; powerlaw (N > 1): heavy-tailed rows with R-MAT columns, rows cut into equal-nnz blocks")
     ap.add_argument("--method", type=int, default=1, help="SPMV_METHODS id (1 = Method_Parallel = CSR-vector)")
-    ap.add_argument("--xchg", default="all", choices=["all", "halo", "allgather", "bcast", "none"],
-                    help="N > 1: which x exchange(s) to run; 'all' = halo (headline), allgather, bcast")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: CPU baseline, read calibration, other configs, multi-GPU legs, pieces of a step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write y of the last timed step to DIR/y.npy (sampled above DUMP_BYTES; N > 1: DIR/y_rank<r>.npy)")
+    ap.add_argument("--xchg", default=None, choices=["all", "halo", "allgather", "bcast", "none"],
+                    help="N > 1: which x exchange(s) to run; 'all' = halo (headline), allgather, bcast (default: all with --full, else halo)")
     ap.add_argument("--cpu-rows", type=int, default=1_000_000)
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline: keep timing calls for about this long (at least 100 calls)")
     ap.add_argument("--no-cpu", action="store_true")
@@ -85,13 +102,18 @@ def parse():
     ap.add_argument("--no-overlap", action="store_true", help="halo mode: do not split interior / boundary rows")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI (the judged path); gloo + SPMV_BENCH_ONE_DEVICE=1 rehearses N>1 on a 1-GPU box")
-    ap.add_argument("--scaling", default="both", choices=["weak", "strong", "both"],
+    ap.add_argument("--scaling", default=None, choices=["weak", "strong", "both"],
                     help="N > 1: weak = --rows per GPU (the headline `value`), strong = --rows in total split over the N ranks; both: the strong leg is "
-                         "reported under 'strong' in the same line")
+                         "reported under 'strong' in the same line (default: both with --full, else weak)")
     ap.add_argument("--no-c-leg", action="store_true", help="N > 1: skip the C-level multi-GPU host (one process, N devices) that rank 0 starts as a child after the ranks are done")
     ap.add_argument("--c-leg", action="store_true", help=argparse.SUPPRESS)   # the child process of that leg
     ap.add_argument("--c-leg-timeout", type=float, default=240.0)
-    return ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.xchg is None:
+        args.xchg = "all" if args.full else "halo"
+    if args.scaling is None:
+        args.scaling = "both" if args.full else "weak"
+    return args
 
 
 # ---------------------------------------------------------------------------------------- launcher
@@ -560,6 +582,31 @@ def traffic_from_profiles(kernel_name, m, nnz, dtype, model_bytes):
     return None, None, None
 
 
+# ---------------------------------------------------------------------------------------- --dump-outputs
+def dump_rows(m, itemsize, world=1, rank=0):
+    """The rows of a length-m y that --dump-outputs writes: None = all of them, else a sorted int64 array of the rows of the fixed,
+    seeded sample (this rank's share of DUMP_BYTES)."""
+    import numpy as np
+    keep = (DUMP_BYTES // max(world, 1)) // itemsize
+    if m <= keep:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED + rank).permutation(m)[:keep])
+
+
+def dump_outputs(path, y, world=1, rank=0):
+    """y (a device tensor) of the last timed step -> path/y.npy (N > 1: path/y_rank<r>.npy), sampled by dump_rows.  -> what was written."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    yh = y.cpu().numpy()
+    assert yh.dtype in (np.float32, np.float64), yh.dtype
+    rows = dump_rows(yh.size, yh.itemsize, world, rank)
+    out = yh if rows is None else yh[rows]
+    name = "y" if world == 1 else f"y_rank{rank}"
+    np.save(os.path.join(path, name + ".npy"), out)
+    return {"dir": path, "files": {name: {"dtype": str(out.dtype), "entries": int(out.size), "of_rows": int(yh.size),
+                                           "sampled": rows is not None}}}
+
+
 # ---------------------------------------------------------------------------------------- one rank
 NCCL_FAIL_RC = 3
 
@@ -674,20 +721,23 @@ def run_rank(args):
             for _ in range(args.warmup):
                 sh.step(x_loc, y)
             elapsed, ev_ms = timed(lambda: sh.step(x_loc, y), K)
+            y_last = y.clone() if (head is None and (world == 1 or args.dump_outputs)) else None   # y of the last timed step
             r = {"ms_per_step": elapsed / K * 1e3, "create_s": create_s, "ghost_columns_rank0": sh.n_ghost, "overlap_split": bool(sh.split),
                  "boundary_rows_rank0": int(sh.bnd_rows.numel()) if sh.split else 0}
-            if world > 1:   # the pieces of a step, each alone (same barrier / MAX-over-ranks protocol, a quarter of the steps)
+            if world > 1 and args.full:   # the pieces of a step, each alone (same barrier / MAX-over-ranks protocol, a quarter of the steps)
                 kk = max(5, K // 4)
                 t_x, _ = timed(lambda: sh.exchange_only(x_loc), kk)
                 t_m, mul_ms = timed(lambda: sh.multiply(y), kk)
                 r.update(exchange_only_ms=t_x / kk * 1e3, multiply_only_ms=t_m / kk * 1e3,
                          exposed_comm_ms=max(0.0, (elapsed / K - t_m / kk) * 1e3))
+            elif world > 1:
+                mul_ms = None           # no multiply-only pass without --full: no roofline
             else:
                 mul_ms = ev_ms
             if head is None:
                 nnz_k = int(sh._A_int[1].numel()) if sh.split else nnz_loc
                 head = dict(info=info, mul_ms=mul_ms, nnz_k=nnz_k, n_x=(sh.n_local if sh.split else sh.n_x), xchg=sh.xchg,
-                            x_ext=sh.x_ext.clone() if world == 1 else None, y=y.clone() if world == 1 else None)
+                            x_ext=sh.x_ext.clone() if world == 1 else None, y=y_last)
             results[mode] = r
             sh.close()
             del sh, y
@@ -703,16 +753,17 @@ def run_rank(args):
         return w
 
     modes = ["none"] if world == 1 else (["halo", "allgather", "bcast"] if args.xchg == "all" else [args.xchg])
-    weak = run_workload(args.rows, modes, keep_arrays=(world == 1)) if (world == 1 or args.scaling in ("weak", "both")) else None
+    weak = run_workload(args.rows, modes, keep_arrays=(world == 1 and args.full)) if (world == 1 or args.scaling in ("weak", "both")) else None
     strong = None
     if world > 1 and args.scaling in ("strong", "both"):
         strong = run_workload(max(1024, args.rows // world), modes if args.scaling == "strong" else modes[:1], keep_arrays=False)
     main_w, scaling = (weak, "weak") if weak is not None else (strong, "strong")
+    dumped = dump_outputs(args.dump_outputs, main_w["head"]["y"], world, rank) if args.dump_outputs else None
 
     def exchanges_of(w):
+        pieces = ("exchange_only_ms", "multiply_only_ms", "exposed_comm_ms")
         return {mode: {"gflops": round(2.0 * w["nnz_all"] / (r["ms_per_step"] * 1e-3) / 1e9, 2), "ms_per_step": round(r["ms_per_step"], 5),
-                       "exchange_only_ms": round(r["exchange_only_ms"], 5), "multiply_only_ms": round(r["multiply_only_ms"], 5),
-                       "exposed_comm_ms": round(r["exposed_comm_ms"], 5), "ghost_columns_rank0": r["ghost_columns_rank0"],
+                       **{p: round(r[p], 5) for p in pieces if p in r}, "ghost_columns_rank0": r["ghost_columns_rank0"],
                        "overlap_split": r["overlap_split"]}
                 for mode, r in w["results"].items()}
 
@@ -725,18 +776,20 @@ def run_rank(args):
         gflops = 2.0 * nnz_all / (ms_step * 1e-3) / 1e9
         # the dominant kernel of THIS rank: SURVEY 8d's algorithmic bytes for what it multiplies, the model's bytes and the counters'
         alg_bytes = 4 * (m_loc + 1) + head["nnz_k"] * (4 + s) + s * head["n_x"] + s * m_loc
-        rf = roofline_fields(info, mul_ms, args.dtype, alg_bytes=alg_bytes)
-        rf.update({
-            # the reference's own bytes model, x counted once per non-zero (csr5_avx2/utils.h:10-14, numa.c:247-248): comparability only
-            "reference_model_gbps": round(((m_loc + 1 + head["nnz_k"]) * 4 + (2 * head["nnz_k"] + m_loc) * s) / (mul_ms * 1e-3) / 1e9, 1),
-            "launch_ms_mean": round(mul_ms, 5), "launches_timed": K if world == 1 else max(5, K // 4),
-            "run_nnz": int(info.get("run_nnz", 0)), "byte_nnz": int(info.get("byte_nnz", 0)),
-            "note": "frac = counter bytes / time / 8 TB/s when profiles/ holds a rocprofv3 measurement of exactly this kernel, shape, dtype and source "
-                    "tree (frac_source), else the storage-format model's bytes; frac_alg divides SURVEY 8d's algorithmic bytes by the same time -- an "
-                    "EFFECTIVE rate that charges 4 B/nnz of ColIdx: run_nnz entries sit in tiles whose rows are single runs of consecutive columns and "
-                    "read 2 B per ROW instead (generator-specific: true for this banded matrix, not for config 2 with holes or 2-ii under 'configs'), "
-                    "byte_nnz entries read 1 B, the rest of the staged entries 2 B",
-        })
+        rf = None
+        if mul_ms is not None:      # N > 1 without --full: no multiply-only pass, no roofline
+            rf = roofline_fields(info, mul_ms, args.dtype, alg_bytes=alg_bytes)
+            rf.update({
+                # the reference's own bytes model, x counted once per non-zero (csr5_avx2/utils.h:10-14, numa.c:247-248): comparability only
+                "reference_model_gbps": round(((m_loc + 1 + head["nnz_k"]) * 4 + (2 * head["nnz_k"] + m_loc) * s) / (mul_ms * 1e-3) / 1e9, 1),
+                "launch_ms_mean": round(mul_ms, 5), "launches_timed": K if world == 1 else max(5, K // 4),
+                "run_nnz": int(info.get("run_nnz", 0)), "byte_nnz": int(info.get("byte_nnz", 0)),
+                "note": "frac = counter bytes / time / 8 TB/s when profiles/ holds a rocprofv3 measurement of exactly this kernel, shape, dtype and source "
+                        "tree (frac_source), else the storage-format model's bytes; frac_alg divides SURVEY 8d's algorithmic bytes by the same time -- an "
+                        "EFFECTIVE rate that charges 4 B/nnz of ColIdx: run_nnz entries sit in tiles whose rows are single runs of consecutive columns and "
+                        "read 2 B per ROW instead (generator-specific: true for this banded matrix, not for config 2 with holes or 2-ii under 'configs'), "
+                        "byte_nnz entries read 1 B, the rest of the staged entries 2 B",
+            })
         out = {
             "metric": "SpMV GFLOP/s (fp64 CSR, y = A x through spmv())" if s == 8 else "SpMV GFLOP/s (fp32 CSR)",
             "value": round(gflops, 2), "unit": "GFLOP/s", "n_gpus": world, "steps": K, "warmup": args.warmup,
@@ -755,17 +808,21 @@ def run_rank(args):
                 "nnz_total": nnz_all, "create_seconds": round(first["create_s"], 3), "inspect_ms": round(info["inspect_ms"], 3),
                 "what_was_exchanged": ("nothing: one GPU" if world == 1 else
                                        f"'{head['xchg']}' in the timed steps of `value` ({first['ghost_columns_rank0']} remote x entries on rank 0 per step); "
-                                       "every other exchange and its cost alone: 'exchanges'"),
+                                       + ("every other exchange and its cost alone: 'exchanges'" if args.full else "the other exchanges: --full")),
             },
-            "hbm_gbps": rf["achieved"],
-            "roofline": rf,
         }
-        if world > 1:
+        if rf is not None:
+            out["hbm_gbps"] = rf["achieved"]
+            out["roofline"] = rf
+        if dumped is not None:
+            out["dump_outputs"] = dumped
+        if world > 1 and args.full:
             out["exchanges"] = exchanges_of(main_w)
             out["scaling_claim"] = {"exchange": "halo", "note": "the >= 6x-at-8-GPUs target (north_star) is claimed on the value above = the "
                                     "'halo' exchange (only the referenced x entries move, point to point, overlapped with the interior rows); "
                                     "'bcast' -- north_star's literal broadcast of x from rank 0 -- and 'allgather' are measured in the same run "
                                     "and reported under 'exchanges'"}
+        if world > 1:
             if strong is not None and strong is not main_w:
                 f0 = strong["results"][modes[0]]
                 out["strong"] = {"scaling": "strong", "workload": f"{args.workload} CSR {strong['n_glob']}x{strong['n_glob']} in total, {strong['m_loc']} rows per rank",
@@ -773,9 +830,9 @@ def run_rank(args):
                                  "nnz_total": strong["nnz_all"], "exchanges": exchanges_of(strong),
                                  "note": "total work fixed at --rows rows (SURVEY 8d config 5: strong beside weak); same protocol, same K steps; efficiency is the driver's to compute "
                                          "against the N = 1 line"}
-        if world == 1 and not args.no_cpu:
+        if world == 1 and args.full and not args.no_cpu:
             out["cpu_baseline"] = cpu_baseline(args, weak["rp"], weak["ci"], weak["va"], head["x_ext"], head["y"], head["n_x"])
-        if world == 1 and not args.no_configs:
+        if world == 1 and args.full and not args.no_configs:
             t0 = time.perf_counter()
             out["multi_gpu_c_entry"] = multi_step_leg(args, dev, weak["rp"], weak["ci"], weak["va"], n_glob, weak["x_full"], head["y"])
             for kk in ("rp", "ci", "va", "x_full"):
@@ -783,13 +840,13 @@ def run_rank(args):
             torch.cuda.empty_cache()
             out["configs"] = extra_configs(args, dev)
             out["configs_seconds"] = round(time.perf_counter() - t0, 1)
-        if world == 1:
+        if world == 1 and args.full:
             out["roofline"]["read_calibration"] = read_calibration(rf["bytes_moved_per_launch"])
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        if world > 1 and not args.no_c_leg and args.backend == "nccl":
+        if world > 1 and args.full and not args.no_c_leg and args.backend == "nccl":
             # the C-level host (one process, N devices, RCCL by dlopen): a child process of rank 0, started once the ranks have released RCCL
             for kk in ("rp", "ci", "va", "x_full"):
                 main_w.pop(kk, None)

@@ -1,9 +1,11 @@
 """CPU: the pure helpers of bench.py -- the three roofline fractions, the traffic lookup's keying (kernel, shape, dtype, the model's byte count and the
-source hash), the column-stream accounting and the per-kernel shares.  No GPU, no library call: fake spmv_hip_info dictionaries."""
+source hash), the column-stream accounting, the per-kernel shares, what a plain run leaves to --full and the --dump-outputs sample.  No GPU, no
+library call: fake spmv_hip_info dictionaries."""
 import json
 import os
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -84,3 +86,35 @@ def test_kernel_shares_list_every_launch():
     assert [k["kernel"] for k in out] == ["sell_window_kernel", "csr5_group_pipe_kernel", "csr5_fixup_kernel"]
     assert abs(sum(k["share"] for k in out) - 1.0) < 2e-3 and out[1]["share"] > 0.69
     assert bench.kernel_shares(["nat_kernel", "csr5_fixup_kernel"], None) == [{"kernel": "nat_kernel"}, {"kernel": "csr5_fixup_kernel"}]
+
+
+def test_plain_run_is_lean_and_full_brings_the_rest_back():
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    assert a.xchg == "halo" and a.scaling == "weak"                     # N > 1 plain: the headline exchange and leg only
+    f = bench.parse(["--full"])
+    assert f.full is True and f.xchg == "all" and f.scaling == "both"  # what every run measured before --full existed
+    e = bench.parse(["--xchg", "bcast", "--scaling", "strong", "--dump-outputs", "out"])
+    assert e.xchg == "bcast" and e.scaling == "strong" and e.dump_outputs == "out"
+
+
+def test_dump_rows_is_a_fixed_seeded_sample_within_the_budget():
+    assert bench.dump_rows(1000, 8) is None                              # fits: every row
+    assert bench.dump_rows(10_000_000, 4) is None                        # fp32 config 2: 40 MB, every row
+    rows = bench.dump_rows(10_000_000, 8)                                # fp64 config 2: 80 MB, sampled
+    assert rows.size * 8 <= bench.DUMP_BYTES < 64 << 20
+    assert (np.diff(rows) > 0).all() and rows[0] >= 0 and rows[-1] < 10_000_000
+    assert np.array_equal(rows, bench.dump_rows(10_000_000, 8))          # the same rows in every run
+    r1 = bench.dump_rows(10_000_000, 8, world=2, rank=1)
+    assert r1.size * 8 * 2 <= bench.DUMP_BYTES and not np.array_equal(r1, rows[: r1.size])
+
+
+def test_dump_outputs_writes_y_in_its_dtype(tmp_path):
+    import torch
+    y = torch.arange(5000, dtype=torch.float64) / 7
+    d = bench.dump_outputs(str(tmp_path / "o"), y)
+    got = np.load(tmp_path / "o" / "y.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, y.numpy())
+    assert d["files"]["y"] == {"dtype": "float64", "entries": 5000, "of_rows": 5000, "sampled": False}
+    bench.dump_outputs(str(tmp_path / "o"), y.float(), world=2, rank=1)
+    assert np.load(tmp_path / "o" / "y_rank1.npy").dtype == np.float32

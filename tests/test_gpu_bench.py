@@ -15,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_line_has_the_contract_keys_and_sane_values():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--rows", "200000",
-                        "--cpu-rows", "20000", "--cpu-seconds", "0.2", "--config-iters", "3"], capture_output=True, text=True, env=env, timeout=600)
+                        "--cpu-rows", "20000", "--cpu-seconds", "0.2", "--config-iters", "3", "--full"], capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -47,6 +47,42 @@ def test_bench_line_has_the_contract_keys_and_sane_values():
     assert d["configs"]["3-orkut-style"]["method"] == "Method_Balanced2"
     mg = d["multi_gpu_c_entry"]
     assert mg["gpus"] >= 1 and mg["matches_single_handle"] is True and mg["ms_per_step"] > 0
+
+
+def test_plain_bench_line_is_the_headline_only_and_dumps_y_of_the_last_step(tmp_path):
+    """The run made for every change: set up, warm up, K timed steps, y of the last step under --dump-outputs, the line.  Nothing of --full
+    (CPU baseline, configs, multi-GPU step, read calibration) runs, and the dumped y is the product A x of the bench's own matrix."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    from spmv_amd import synth
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    m = 200000
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--rows", str(m),
+                        "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "roofline"):
+        assert k in d, k
+    assert d["steps"] == 4 and d["warmup"] == 2 and d["dtype"] == "f64" and d["higher_is_better"] is True and d["unit"] == "GFLOP/s"
+    assert d["ms_per_step"] > 0 and abs(d["value"] - 2.0 * d["config"]["nnz_total"] / (d["ms_per_step"] * 1e-3) / 1e9) <= 0.01 * d["value"]
+    for k in ("cpu_baseline", "configs", "multi_gpu_c_entry"):
+        assert k not in d, k
+    assert "read_calibration" not in d["roofline"]
+    assert d["dump_outputs"]["files"]["y"] == {"dtype": "float64", "entries": m, "of_rows": m, "sampled": False}
+    y = np.load(tmp_path / "out" / "y.npy")
+    assert y.dtype == np.float64 and y.shape == (m,)
+    dev = torch.device("cuda:0")
+    _, _, rp, ci, va = synth.banded_device(m, m, 32, "uniform", torch.float64, dev, seed=1, row0=0)
+    g = torch.Generator(device=dev)
+    g.manual_seed(1234)
+    x = torch.rand(m, generator=g, device=dev, dtype=torch.float64) * 2 - 1
+    want, scale_row = bench.definition(rp, ci, va, x)
+    err = np.abs(y - want.cpu().numpy())
+    assert (err <= 1e-6 * scale_row.cpu().numpy() + 1e-300).all(), float(err.max())
 
 
 def test_c_level_leg_of_the_multi_gpu_bench_rehearsed_with_virtual_shards():

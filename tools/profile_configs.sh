@@ -2,7 +2,7 @@
 # rocprofv3 evidence for every BASELINE config's named kernel (run through gpurun from the repo root):
 #   per config: --kernel-trace --stats | --pmc FETCH_SIZE | --pmc WRITE_SIZE | --pmc TCC_HIT_sum TCC_MISS_sum
 # (separate passes: FETCH_SIZE and WRITE_SIZE do not fit the TCC slots together; PMC passes carry --kernel-trace only).
-# Plus the same for `python3 bench.py` (config 2 through the bench itself) and the known-bytes calibration kernels.
+# Plus the same for `python3 bench.py --full` (config 2 and the other configs through the bench itself) and the known-bytes calibration kernels.
 # Raw output: gpurun_out/prof_<tag>/ (scratch); tools/summarize_configs.py condenses it into profiles/ (tracked).
 #   usage: tools/profile_configs.sh r02 "2 2r 3w 3o 4"      (NOBENCH=1: configs only; KEEP=1: add to an existing output directory)
 set -u
@@ -23,7 +23,7 @@ for C in $CONFIGS; do
 done
 if [ -z "${NOBENCH:-}" ]; then
 echo "== bench.py"; date +%T
-timeout -k 10 280 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/bench/stats" -- python3 "$REPO/bench.py" --steps 30 --warmup 5 --no-cpu > "$OUT/bench.stats.log" 2>&1 || echo "bench stats pass failed"
+timeout -k 10 280 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/bench/stats" -- python3 "$REPO/bench.py" --steps 30 --warmup 5 --full --no-cpu > "$OUT/bench.stats.log" 2>&1 || echo "bench stats pass failed"
 if [ -x "$REPO/spmv_amd/bin/gbench" ]; then   # built by spmv_amd/build.py from tools/gbench.hip
   timeout -k 10 280 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$OUT/calib/fetch" -- "$REPO/spmv_amd/bin/gbench" calib > "$OUT/calib.log" 2>&1 || echo "calib pass failed"
 fi
