@@ -61,6 +61,30 @@ void spmv_hip_trim_pool(void);
  * option "reorder".  Returns 0 or an SPMV_HIP_E_* code. */
 int spmv_hip_update_values(spmv_Handle_t handle, const void *Matrix_Val);
 
+/* ---- k right-hand sides: Y = A X ------------------------------------------------------------
+ * Y = A X for k vectors at once: X is n x k, Y is m x k, both ROW-MAJOR with leading dimensions
+ * (X[j*ldx + c], Y[i*ldy + c], ldx >= k, ldy >= k; host or device pointers).  Returns 0 or an SPMV_HIP_E_* code.
+ *   - The CSR arguments follow spmv()'s rules: m and the pointers seen at create -> the resident matrix; others -> that matrix is
+ *     re-inspected; option "check_values", in-place value changes and spmv_hip_update_values apply as for spmv().
+ *   - Only the first k entries of every Y row are written (empty rows: zeros); the padding of Y is never touched, that of X never read.
+ *     Offsets are 64-bit: n*ldx and m*ldy may exceed 2^31 elements.
+ *   - A is read once per panel of up to 16 (fp64) / 32 (fp32) columns.  Every (row, column) is summed in an order fixed by the matrix:
+ *     results are bit-identical run to run and across host / device pointers, ldx / ldy and stream / async settings.
+ *     k = 1 with ldx = ldy = 1 runs the handle's spmv() schedule: bit-identical to spmv().
+ *   - The handle's stream and async setting apply as for spmv(); host X / Y are staged through handle-owned HBM buffers of n*k and m*k
+ *     elements, allocated at first use, freed at destroy / clear / re-inspection and counted in spmv_hip_info.device_bytes.
+ *   - Option "reorder" handles multiply the resident P A P^T: the caller gathers X rows and scatters Y rows by handle->index, as for spmv().
+ *     Split and cache-blocked handles multiply the resident CSR itself.
+ *   - Column indices: with option "keep_columns" = 0 (default) create() may have released the resident ColIdx copy.  The first call
+ *     (k > 1 or ld > 1) then copies it back from the call's ColIdx -- by the pointer rule the create-time array, which must therefore still
+ *     hold the create-time indices (permuted like the matrix on "reorder" handles): device_bytes grows by 4 B per non-zero from then on,
+ *     and spmv() computes exactly what it did before.
+ *   - Errors (SPMV_HIP_E_ARG, Y untouched): k < 1, ldx < k, ldy < k; a NULL X or Y when m > 0; multi-GPU handles (option "gpus",
+ *     spmv_hip_create_handle_from_blocks); host_rows handles.  A cleared or failed handle: SPMV_HIP_E_NOSTATE.  Every failure is also
+ *     reported through spmv_hip_last_error(). */
+int spmv_hip_spmm(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                  const void *Matrix_Val, int k, const void *X, long long ldx, void *Y, long long ldy);
+
 /* ---- options --------------------------------------------------------------------------------
  * Resolved once per handle, at create: process-wide value (spmv_hip_set_option / env), overridden by the
  * calling thread's value (spmv_hip_set_thread_option) -- so two threads can create differently tuned handles

@@ -17,6 +17,11 @@ extern "C" {
 double spmv_hip_time_launches(spmv_Handle_t handle, const void *x, void *y,
                               int warmup, int iters, float *ms_out);
 
+/* The same for spmv_hip_spmm: `warmup` untimed + `iters` timed launches of Y = A X (k columns, leading dimensions ldx / ldy) on the
+ * handle's stream, each bracketed by hipEvents; X and Y must be DEVICE pointers.  Returns the mean in ms, < 0 on error. */
+double spmv_hip_time_spmm_launches(spmv_Handle_t handle, int k, const void *X, long long ldx, void *Y, long long ldy,
+                                   int warmup, int iters, float *ms_out);
+
 #endif /* SPMV_HIP_TOOLS_H */
 #if defined(__cplusplus)
 }

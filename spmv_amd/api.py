@@ -103,6 +103,9 @@ FUNCTIONS = {
                                                   C.c_int, C.c_ulong]),
     "spmv_hip_get_info": (C.c_int, [spmv_Handle_t, C.POINTER(spmv_hip_info)]),
     "spmv_hip_time_launches": (C.c_double, [spmv_Handle_t, _V, _V, C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "spmv_hip_spmm": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, C.c_int, _V, C.c_longlong, _V, C.c_longlong]),
+    "spmv_hip_time_spmm_launches": (C.c_double, [spmv_Handle_t, C.c_int, _V, C.c_longlong, _V, C.c_longlong, C.c_int, C.c_int,
+                                                 C.POINTER(C.c_float)]),
     # include/spmv_io.h (host only)
     "spmv_io_read_mtx": (C.c_int, [C.c_char_p, C.c_size_t, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_V)]),
     "spmv_io_cache_path": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t]),
@@ -273,6 +276,50 @@ def time_launches(handle, x, y, warmup=10, iters=100):
     return mean, np.frombuffer(ms, dtype=np.float32).copy()
 
 
+def _block(a, name):
+    """(address, rows, k, ld) of a 2-D numpy array / torch tensor whose column stride is 1 (the row stride is its leading dimension)."""
+    if a is None:
+        return None, 0, 0, 0
+    if isinstance(a, np.ndarray):
+        if a.ndim == 2 and a.size == 0:
+            return a.ctypes.data, a.shape[0], a.shape[1], max(a.shape[1], 1)
+        if a.ndim != 2 or (a.strides[1] != a.itemsize and a.shape[1] > 1) or a.strides[0] % a.itemsize:
+            raise ValueError(f"{name} must be 2-D with column stride 1")
+        return a.ctypes.data, a.shape[0], a.shape[1], a.strides[0] // a.itemsize
+    if hasattr(a, "data_ptr"):
+        if a.dim() != 2 or (a.stride(1) != 1 and a.shape[1] > 1):
+            raise ValueError(f"{name} must be 2-D with column stride 1")
+        return a.data_ptr(), a.shape[0], a.shape[1], a.stride(0)
+    raise TypeError(type(a))
+
+
+def spmm(handle, m, RowPtr, ColIdx, Matrix_Val, X, Y, check=True):
+    """Y = A X for the k columns of X (spmv_hip_spmm).  X (n x k) and Y (m x k): 2-D numpy arrays or torch tensors with column
+    stride 1; their row strides are passed as ldx / ldy, so views into wider arrays work.  -> the return code (0 on success)."""
+    px, _, k, ldx = _block(X, "X")
+    py, _, ky, ldy = _block(Y, "Y")
+    if X is not None and Y is not None and ky != k:
+        raise ValueError(f"X has {k} columns, Y {ky}")
+    if X is None:
+        k = ky
+    rc = load().spmv_hip_spmm(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), int(k), px, int(max(ldx, 1) if X is not None else k),
+                              py, int(max(ldy, 1) if Y is not None else k))
+    if check and rc != 0:
+        _raise_if_error("spmv_hip_spmm")
+    return rc
+
+
+def time_spmm_launches(handle, X, Y, warmup=10, iters=100):
+    """-> (mean_ms, per-launch ms array) of spmv_hip_spmm on device X / Y (spmv_hip_time_spmm_launches)."""
+    px, _, k, ldx = _block(X, "X")
+    py, _, _, ldy = _block(Y, "Y")
+    ms = (C.c_float * iters)()
+    mean = load().spmv_hip_time_spmm_launches(handle, int(k), px, int(max(ldx, 1)), py, int(max(ldy, 1)), warmup, iters, ms)
+    if mean < 0:
+        _raise_if_error("spmv_hip_time_spmm_launches")
+    return mean, np.frombuffer(ms, dtype=np.float32).copy()
+
+
 def _take_csr(m, n, nnz, rp, ci, va, dtype):
     """Copy malloc'ed C arrays into numpy arrays and free the C side."""
     from .synth import CSR
@@ -353,6 +400,19 @@ class Handle:
         rp, ci, va = self._keep
         spmv(self.h, self.m, rp, ci, va, x, y)
         return y
+
+    def spmm(self, X, Y=None):
+        """Y = A X (spmv_hip_spmm) for a 2-D X of n x k; Y (m x k) is allocated like X -- same kind, dtype and device -- when None."""
+        if Y is None:
+            k = X.shape[1]
+            if isinstance(X, np.ndarray):
+                Y = np.empty((self.m, k), dtype=X.dtype)
+            else:
+                import torch
+                Y = torch.empty((self.m, k), dtype=X.dtype, device=X.device)
+        rp, ci, va = self._keep
+        spmm(self.h, self.m, rp, ci, va, X, Y)
+        return Y
 
     def update_values(self, val):
         """The caller changed the values (in place or in a new array of the same pattern)."""

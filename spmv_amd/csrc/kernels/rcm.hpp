@@ -217,7 +217,7 @@ __global__ __launch_bounds__(kBlock) void rcm_permute_kernel(int m, const int *_
         for (int k = lane; k < len; k += kWave) {
             const int c = colidx[src + k];
             ci2[dst + k] = c < m ? inv[c] : c;
-            va2[dst + k] = val[src + k];
+            if (va2) va2[dst + k] = val[src + k]; // NULL: columns only (spmv_shim_restore_columns)
         }
     }
 }

@@ -262,6 +262,12 @@ struct spmv_dev {
     float near_share = -1.f;                 // sampled share of near entries (-1: not sampled)
     float split_ms[2] = {0, 0};              // measured: schedule as built vs the split pair
     bool accumulate = false;                 // this matrix is the far half of a split: y += A x (blocked executor only)
+    // spmv_hip_spmm (shim/spmm.hpp): equal-nnz row batches and the long-row list over the resident CSR, built at the first call; HBM staging of host X / Y
+    bool spmm_planned = false;
+    int spmm_nb = 0, spmm_nlong = 0;
+    int *spmm_split = nullptr, *spmm_longs = nullptr;
+    void *spmm_x = nullptr, *spmm_y = nullptr;
+    size_t spmm_x_bytes = 0, spmm_y_bytes = 0;
     long long device_bytes = 0;
     double inspect_ms = 0;
     std::vector<std::pair<void *, size_t>> sched_allocs; // (pointer, bytes): freed when the schedule is rebuilt

@@ -525,6 +525,52 @@ void spmv_create_handle_all_in_one(spmv_Handle_t *Handle, BASIC_INT_TYPE m, BASI
     }
 }
 
+/* The prologue of every multiply (spmv, spmv_hip_spmm): the CSR arguments of THIS call against the resident matrix -- re-inspection
+ * for another matrix, refresh of values changed in place (option "check_values").  0, or the code already reported. */
+static int refresh_resident(spmv_Handle_t handle, spmv_hip_state *st, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr,
+                            const BASIC_INT_TYPE *ColIdx, const void *Matrix_Val)
+{
+    int rc;
+    /* The reference re-reads the CSR arguments on every call (common.c:286-298).  Same pointers
+     * and m as at create -> the HBM-resident matrix; anything else -> re-inspect that matrix. */
+    if (st->from_blocks) {
+        /* created from row blocks: there is no monolithic CSR the arguments could name; they are ignored */
+    } else if (m != st->m || RowPtr != handle->RowPtr || ColIdx != handle->ColIdx ||
+               Matrix_Val != handle->Matrix_Val) {
+        if (!st->warned_rebuild && !getenv("SPMV_HIP_QUIET")) {
+            fprintf(stderr, "[spmv_hip] spmv(): CSR arguments differ from create(); re-inspecting "
+                            "(slow path, DESIGN.md \"CSR arguments\")\n");
+            st->warned_rebuild = 1;
+        }
+        if ((rc = state_build(handle, st, m, st->n, RowPtr, ColIdx, Matrix_Val)) != SPMV_HIP_OK) return rc;
+    } else if (st->val_sum_valid) {
+        /* option "check_values": the reference re-reads Matrix_Val on every call, so a caller may change the
+         * values in place between calls (Newton steps, time stepping).  Detect that by checksum and refresh
+         * the resident copies (no re-inspection: the pattern is the same). */
+        unsigned long long sum = 0;
+        int have = 1;
+        if (st->val_sum_valid == 2) sum = sampled_host_checksum(Matrix_Val, st->val_words);
+        else have = spmv_shim_checksum_words(Matrix_Val, st->val_words, &sum) == SPMV_HIP_OK;
+        if (have && sum != st->val_sum) {
+            if (st->multi && !handle->Level_3_opt_used) { /* every shard refreshes its slice of the values in place */
+                rc = spmv_shim_multi_update_values(st->multi, Matrix_Val);
+                if (rc) { spmv_set_error(rc, "spmv/refresh values", spmv_shim_error_text()); return rc; }
+                st->val_sum = sum;
+            } else if (handle->Level_3_opt_used) {
+                /* option "reorder": the resident matrix is P A P^T, whose value order is not the caller's -- the values
+                 * cannot be refreshed in place; upload, reorder and inspect the caller's matrix again (state_build
+                 * takes a new checksum) */
+                if ((rc = state_build(handle, st, m, st->n, RowPtr, ColIdx, Matrix_Val)) != SPMV_HIP_OK) return rc;
+            } else {
+                rc = spmv_shim_update_values(st->dev, Matrix_Val);
+                if (rc) { spmv_set_error(rc, "spmv/refresh values", spmv_shim_error_text()); return rc; }
+                st->val_sum = sum;
+            }
+        }
+    }
+    return SPMV_HIP_OK;
+}
+
 void spmv(const spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr,
           const BASIC_INT_TYPE *ColIdx, const void *Matrix_Val, const void *X, void *Y)
 {
@@ -545,43 +591,7 @@ void spmv(const spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *Ro
         spmv_set_error(SPMV_HIP_E_NOSTATE, "spmv", "handle has no device state (create failed?)");
         return;
     }
-    /* The reference re-reads the CSR arguments on every call (common.c:286-298).  Same pointers
-     * and m as at create -> the HBM-resident matrix; anything else -> re-inspect that matrix. */
-    if (st->from_blocks) {
-        /* created from row blocks: there is no monolithic CSR the arguments could name; they are ignored */
-    } else if (m != st->m || RowPtr != handle->RowPtr || ColIdx != handle->ColIdx ||
-               Matrix_Val != handle->Matrix_Val) {
-        if (!st->warned_rebuild && !getenv("SPMV_HIP_QUIET")) {
-            fprintf(stderr, "[spmv_hip] spmv(): CSR arguments differ from create(); re-inspecting "
-                            "(slow path, DESIGN.md \"CSR arguments\")\n");
-            st->warned_rebuild = 1;
-        }
-        if (state_build(handle, st, m, st->n, RowPtr, ColIdx, Matrix_Val) != SPMV_HIP_OK) return;
-    } else if (st->val_sum_valid) {
-        /* option "check_values": the reference re-reads Matrix_Val on every call, so a caller may change the
-         * values in place between calls (Newton steps, time stepping).  Detect that by checksum and refresh
-         * the resident copies (no re-inspection: the pattern is the same). */
-        unsigned long long sum = 0;
-        int have = 1;
-        if (st->val_sum_valid == 2) sum = sampled_host_checksum(Matrix_Val, st->val_words);
-        else have = spmv_shim_checksum_words(Matrix_Val, st->val_words, &sum) == SPMV_HIP_OK;
-        if (have && sum != st->val_sum) {
-            if (st->multi && !handle->Level_3_opt_used) { /* every shard refreshes its slice of the values in place */
-                rc = spmv_shim_multi_update_values(st->multi, Matrix_Val);
-                if (rc) { spmv_set_error(rc, "spmv/refresh values", spmv_shim_error_text()); return; }
-                st->val_sum = sum;
-            } else if (handle->Level_3_opt_used) {
-                /* option "reorder": the resident matrix is P A P^T, whose value order is not the caller's -- the values
-                 * cannot be refreshed in place; upload, reorder and inspect the caller's matrix again (state_build
-                 * takes a new checksum) */
-                if (state_build(handle, st, m, st->n, RowPtr, ColIdx, Matrix_Val) != SPMV_HIP_OK) return;
-            } else {
-                rc = spmv_shim_update_values(st->dev, Matrix_Val);
-                if (rc) { spmv_set_error(rc, "spmv/refresh values", spmv_shim_error_text()); return; }
-                st->val_sum = sum;
-            }
-        }
-    }
+    if (refresh_resident(handle, st, m, RowPtr, ColIdx, Matrix_Val) != SPMV_HIP_OK) return;
     rc = st->multi ? spmv_shim_multi_run(st->multi, X, Y) : spmv_shim_run(st->dev, X, Y);
     if (rc) spmv_set_error(rc, "spmv", spmv_shim_error_text());
 }
@@ -792,5 +802,56 @@ double spmv_hip_time_launches(spmv_Handle_t h, const void *x, void *y, int warmu
     if (!st) return -1.0;
     r = spmv_shim_time(st->dev, x, y, warmup, iters, ms_out);
     if (r < 0) spmv_set_error(SPMV_HIP_E_RUNTIME, "time_launches", spmv_shim_error_text());
+    return r;
+}
+
+/* ---------------------------------------------------------------- k right-hand sides */
+/* Argument rules and state shared by spmv_hip_spmm and its timing entry point: 0 and *out = the device state with its resident ColIdx
+ * (restored from the create-time array when create() had released it), or the code already reported. */
+static int spmm_state(spmv_Handle_t h, const char *where, int k, const void *X, long long ldx, const void *Y, long long ldy, int m, spmv_hip_state **out)
+{
+    spmv_hip_state *st = h ? (spmv_hip_state *) h->extraHandle : NULL;
+    *out = NULL;
+    if (!h) { spmv_set_error(SPMV_HIP_E_ARG, where, "handle is NULL"); return SPMV_HIP_E_ARG; }
+    if (k < 1 || ldx < k || ldy < k) { spmv_set_error(SPMV_HIP_E_ARG, where, "need k >= 1, ldx >= k and ldy >= k"); return SPMV_HIP_E_ARG; }
+    if (m > 0 && (!X || !Y)) { spmv_set_error(SPMV_HIP_E_ARG, where, "X or Y is NULL"); return SPMV_HIP_E_ARG; }
+    if (st && st->host_rows) { spmv_set_error(SPMV_HIP_E_ARG, where, "not available on a host_rows handle"); return SPMV_HIP_E_ARG; }
+    if (st && st->multi) { spmv_set_error(SPMV_HIP_E_ARG, where, "not available on a multi-GPU handle (option \"gpus\", create_handle_from_blocks)"); return SPMV_HIP_E_ARG; }
+    if (!st || !st->dev) { spmv_set_error(SPMV_HIP_E_NOSTATE, where, "handle has no device state (create failed or handle cleared)"); return SPMV_HIP_E_NOSTATE; }
+    *out = st;
+    return SPMV_HIP_OK;
+}
+
+static int spmm_columns(spmv_Handle_t h, spmv_hip_state *st, const char *where)
+{
+    /* option keep_columns = 0 may have released the resident ColIdx at create; the handle's ColIdx is the create-time array (pointer rule) */
+    int rc = spmv_shim_restore_columns(st->dev, h->RowPtr, h->ColIdx, h->Level_3_opt_used ? h->index : NULL);
+    if (rc) spmv_set_error(rc, where, spmv_shim_error_text());
+    return rc;
+}
+
+int spmv_hip_spmm(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                  const void *Matrix_Val, int k, const void *X, long long ldx, void *Y, long long ldy)
+{
+    spmv_hip_state *st;
+    int rc = spmm_state(handle, "spmm", k, X, ldx, Y, ldy, m, &st);
+    if (rc) return rc;
+    if ((rc = refresh_resident(handle, st, m, RowPtr, ColIdx, Matrix_Val)) != SPMV_HIP_OK) return rc;
+    if (!st->dev) { spmv_set_error(SPMV_HIP_E_NOSTATE, "spmm", "handle has no device state"); return SPMV_HIP_E_NOSTATE; }
+    if (k == 1 && ldx == 1 && ldy == 1) rc = spmv_shim_run(st->dev, X, Y); /* one vector: the handle's own spmv schedule, bit-identical to spmv() */
+    else if ((rc = spmm_columns(handle, st, "spmm")) == SPMV_HIP_OK) rc = spmv_shim_spmm(st->dev, k, X, ldx, Y, ldy);
+    else return rc;
+    if (rc) spmv_set_error(rc, "spmm", spmv_shim_error_text());
+    return rc;
+}
+
+double spmv_hip_time_spmm_launches(spmv_Handle_t h, int k, const void *X, long long ldx, void *Y, long long ldy, int warmup, int iters, float *ms_out)
+{
+    spmv_hip_state *st;
+    double r;
+    if (spmm_state(h, "time_spmm_launches", k, X, ldx, Y, ldy, 1, &st) != SPMV_HIP_OK) return -1.0;
+    if (spmm_columns(h, st, "time_spmm_launches") != SPMV_HIP_OK) return -1.0;
+    r = spmv_shim_time_spmm(st->dev, k, X, ldx, Y, ldy, warmup, iters, ms_out);
+    if (r < 0) spmv_set_error(SPMV_HIP_E_RUNTIME, "time_spmm_launches", spmv_shim_error_text());
     return r;
 }

@@ -96,6 +96,15 @@ int spmv_shim_checksum_words(const void *val, long long words, unsigned long lon
  * (row i of the new matrix = row perm[i] of the old).  Before spmv_shim_build. */
 int spmv_shim_reorder_rcm(spmv_dev *d, int *perm_host);
 
+/* Y = A X for k right-hand sides over the resident CSR (shim/spmm.hpp): X n x k, Y m x k, row-major, leading dimensions ldx, ldy >= k;
+ * host or device pointers.  Needs the resident ColIdx (spmv_shim_restore_columns after spmv_shim_release_columns). */
+int spmv_shim_spmm(spmv_dev *d, int k, const void *x, long long ldx, void *y, long long ldy);
+/* the same, `iters` launches timed with events on the handle's stream (device X / Y); mean ms, < 0 on failure */
+double spmv_shim_time_spmm(spmv_dev *d, int k, const void *x, long long ldx, void *y, long long ldy, int warmup, int iters, float *ms_out);
+/* Give a matrix whose ColIdx copy was released its resident copy back, from the create-time arrays (host or device): as is, or permuted
+ * with perm_host (m ints, the create-time reordering: row i of the resident matrix = row perm_host[i] of the caller's).  No-op when resident. */
+int spmv_shim_restore_columns(spmv_dev *d, const int *rowptr, const int *colidx, const int *perm_host);
+
 /* the resident CSR arrays (device pointers; ColIdx may be NULL after spmv_shim_release_columns) */
 void spmv_shim_matrix_arrays(const spmv_dev *d, const int **rowptr, const int **colidx, const void **val);
 

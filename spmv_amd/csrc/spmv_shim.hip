@@ -33,6 +33,7 @@
 #include "kernels/split.hpp"
 #include "kernels/rcm.hpp"
 #include "kernels/csr_vector_tile.hpp"
+#include "kernels/spmm.hpp"
 
 using namespace spmv;
 
@@ -170,6 +171,7 @@ extern "C" void spmv_shim_matrix_destroy(spmv_dev *d)
     if (d->x_stage) (void) pool_free(d->x_stage);
     if (d->y_stage) (void) pool_free(d->y_stage);
     if (d->scratch8) (void) pool_free(d->scratch8);
+    for (void *p : {(void *) d->spmm_split, (void *) d->spmm_longs, d->spmm_x, d->spmm_y}) if (p) (void) pool_free(p);
     delete d;
 }
 
@@ -529,6 +531,7 @@ extern "C" int spmv_shim_is_device_ptr(const void *p) { return is_device_ptr(p) 
 
 #include "shim/launch.hpp"
 #include "shim/split.hpp"
+#include "shim/spmm.hpp"
 
 extern "C" int spmv_shim_run(spmv_dev *d, const void *x, void *y)
 {
