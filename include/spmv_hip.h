@@ -85,6 +85,34 @@ int spmv_hip_update_values(spmv_Handle_t handle, const void *Matrix_Val);
 int spmv_hip_spmm(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
                   const void *Matrix_Val, int k, const void *X, long long ldx, void *Y, long long ldy);
 
+/* ---- the transpose: y = A^T x ----------------------------------------------------------------
+ * y = A^T x: X has m entries (A's rows), Y has n entries (A's columns, as at create); host or device pointers.  Returns 0 or an SPMV_HIP_E_* code.
+ *   - A^T is built on the device from the resident matrix at the first call (or at spmv_hip_prepare_transpose): row j of A^T lists its
+ *     entries in ascending row of A, so the transpose is a function of the matrix alone.  It is then planned and inspected exactly as create()
+ *     would plan a matrix of that shape, with the handle's requested method and options (spmv_hip_get_transpose_info reports the result).
+ *   - The CSR arguments follow spmv()'s rules: m and the pointers seen at create -> the resident matrix; others -> that matrix is
+ *     re-inspected and the transpose dropped (rebuilt at the next call); option "check_values", in-place value changes and
+ *     spmv_hip_update_values apply as for spmv(): the next transpose call multiplies the new values (gathered again on the device; spmv()
+ *     itself pays nothing for this).
+ *   - Results are bit-identical run to run and across host / device pointers, stream and async settings (unless the handle was created
+ *     with option "deterministic" = 0, as for spmv()).  m = 0 or nnz = 0 writes n zeros; empty columns of A give zero entries of Y.
+ *   - The handle's stream and async setting apply, also when changed later; host X / Y are staged as in spmv().
+ *   - Option "reorder" handles multiply the transpose of the resident P A P^T, i.e. P A^T P^T: the caller gathers X and scatters Y by
+ *     handle->index, as for spmv().  Split and cache-blocked handles transpose the resident CSR itself.
+ *   - Column indices: with option "keep_columns" = 0 create() may have released the resident ColIdx copy.  The build then copies it back
+ *     from the create-time array (which must therefore still hold the create-time indices, permuted like the matrix on "reorder" handles)
+ *     and releases it again afterwards: spmv() computes exactly what it did before.
+ *   - Memory: perm (4 B per non-zero), A^T's CSR arrays and its schedule, counted in spmv_hip_info.device_bytes of the handle and freed at
+ *     destroy / clear / re-inspection.
+ *   - Errors (SPMV_HIP_E_ARG, Y untouched): multi-GPU handles (option "gpus", spmv_hip_create_handle_from_blocks); host_rows handles; a NULL
+ *     X when m > 0 or a NULL Y when n > 0.  A cleared or failed handle: SPMV_HIP_E_NOSTATE.  Every failure is also reported through
+ *     spmv_hip_last_error(). */
+int spmv_hip_spmv_transpose(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                            const void *Matrix_Val, const void *X, void *Y);
+/* build the transposed schedule now instead of at the first call (create-time cost, outside a timed loop) */
+int spmv_hip_prepare_transpose(spmv_Handle_t handle);
+/* spmv_hip_get_transpose_info: below, after spmv_hip_info */
+
 /* ---- options --------------------------------------------------------------------------------
  * Resolved once per handle, at create: process-wide value (spmv_hip_set_option / env), overridden by the
  * calling thread's value (spmv_hip_set_thread_option) -- so two threads can create differently tuned handles
@@ -199,6 +227,8 @@ typedef struct spmv_hip_info {
                                  * handle; 0 only for the wide blocked form under option "deterministic" = 0 */
 } spmv_hip_info;
 int spmv_hip_get_info(spmv_Handle_t handle, spmv_hip_info *out);
+/* the transposed schedule's spmv_hip_info (m, n swapped; schedule, kernels, device_bytes of A^T alone, reproducible); SPMV_HIP_E_NOSTATE until built */
+int spmv_hip_get_transpose_info(spmv_Handle_t handle, spmv_hip_info *out);
 
 /* ---- multi-GPU: row blocks over the GPUs of ONE process (option "gpus"; BASELINE config 5) --------------
  * A handle created while option "gpus" = G > 0 splits the matrix into min(G, visible devices) equal-nnz row blocks, one

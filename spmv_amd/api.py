@@ -106,6 +106,11 @@ FUNCTIONS = {
     "spmv_hip_spmm": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, C.c_int, _V, C.c_longlong, _V, C.c_longlong]),
     "spmv_hip_time_spmm_launches": (C.c_double, [spmv_Handle_t, C.c_int, _V, C.c_longlong, _V, C.c_longlong, C.c_int, C.c_int,
                                                  C.POINTER(C.c_float)]),
+    "spmv_hip_spmv_transpose": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, _V, _V]),
+    "spmv_hip_prepare_transpose": (C.c_int, [spmv_Handle_t]),
+    "spmv_hip_get_transpose_info": (C.c_int, [spmv_Handle_t, C.POINTER(spmv_hip_info)]),
+    "spmv_hip_time_transpose_launches": (C.c_double, [spmv_Handle_t, _V, _V, C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "spmv_hip_transpose_map": (C.c_int, [spmv_Handle_t, _I, _I]),
     # include/spmv_io.h (host only)
     "spmv_io_read_mtx": (C.c_int, [C.c_char_p, C.c_size_t, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_V)]),
     "spmv_io_cache_path": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t]),
@@ -246,10 +251,7 @@ def update_values(handle, Matrix_Val):
         _raise_if_error("spmv_hip_update_values")
 
 
-def get_info(handle):
-    info = spmv_hip_info()
-    if load().spmv_hip_get_info(handle, C.byref(info)) != 0:
-        _raise_if_error("spmv_hip_get_info")
+def _info_dict(info):
     out = {k: getattr(info, k) for k, _ in spmv_hip_info._fields_}
     out["schedule_name"] = (out["schedule_name"] or b"").decode()
     out["kernel_name"] = (out["kernel_name"] or b"").decode()
@@ -258,6 +260,21 @@ def get_info(handle):
     out["route_ms"] = [float(v) for v in out["route_ms"]]
     out["split_ms"] = [float(v) for v in out["split_ms"]]
     return out
+
+
+def get_info(handle):
+    info = spmv_hip_info()
+    if load().spmv_hip_get_info(handle, C.byref(info)) != 0:
+        _raise_if_error("spmv_hip_get_info")
+    return _info_dict(info)
+
+
+def get_transpose_info(handle):
+    """spmv_hip_get_transpose_info as a dict shaped like get_info's: the schedule of A^T (raises until the transpose is built)."""
+    info = spmv_hip_info()
+    if load().spmv_hip_get_transpose_info(handle, C.byref(info)) != 0:
+        _raise_if_error("spmv_hip_get_transpose_info")
+    return _info_dict(info)
 
 
 def set_stream(handle, stream_ptr, async_=True):
@@ -318,6 +335,40 @@ def time_spmm_launches(handle, X, Y, warmup=10, iters=100):
     if mean < 0:
         _raise_if_error("spmv_hip_time_spmm_launches")
     return mean, np.frombuffer(ms, dtype=np.float32).copy()
+
+
+def spmv_transpose(handle, m, RowPtr, ColIdx, Matrix_Val, X, Y, check=True):
+    """y = A^T x (spmv_hip_spmv_transpose): X has m entries, Y n.  -> the return code (0 on success)."""
+    rc = load().spmv_hip_spmv_transpose(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), _ptr(X), _ptr(Y))
+    if check and rc != 0:
+        _raise_if_error("spmv_hip_spmv_transpose")
+    return rc
+
+
+def prepare_transpose(handle, check=True):
+    """Build (and plan) A^T now rather than at the first spmv_transpose (spmv_hip_prepare_transpose)."""
+    rc = load().spmv_hip_prepare_transpose(handle)
+    if check and rc != 0:
+        _raise_if_error("spmv_hip_prepare_transpose")
+    return rc
+
+
+def time_transpose_launches(handle, x, y, warmup=10, iters=100):
+    """-> (mean_ms, per-launch ms array) of y = A^T x on device x / y (spmv_hip_time_transpose_launches)."""
+    ms = (C.c_float * iters)()
+    mean = load().spmv_hip_time_transpose_launches(handle, _ptr(x), _ptr(y), warmup, iters, ms)
+    if mean < 0:
+        _raise_if_error("spmv_hip_time_transpose_launches")
+    return mean, np.frombuffer(ms, dtype=np.float32).copy()
+
+
+def transpose_map(handle, n, nnz):
+    """-> (rowptr_T, perm) of the built transpose as int32 numpy arrays (n + 1 and nnz entries; spmv_hip_transpose_map)."""
+    rp = np.empty(int(n) + 1, dtype=np.int32)
+    perm = np.empty(max(int(nnz), 1), dtype=np.int32)
+    if load().spmv_hip_transpose_map(handle, rp.ctypes.data_as(_I), perm.ctypes.data_as(_I)) != 0:
+        _raise_if_error("spmv_hip_transpose_map")
+    return rp, perm[:int(nnz)]
 
 
 def _take_csr(m, n, nnz, rp, ci, va, dtype):
@@ -413,6 +464,18 @@ class Handle:
         rp, ci, va = self._keep
         spmm(self.h, self.m, rp, ci, va, X, Y)
         return Y
+
+    def spmv_transpose(self, x, y=None):
+        """y = A^T x (spmv_hip_spmv_transpose) for x of m entries; y (n entries) is allocated like x -- same kind, dtype and device -- when None."""
+        if y is None:
+            if isinstance(x, np.ndarray):
+                y = np.empty(self.n, dtype=x.dtype)
+            else:
+                import torch
+                y = torch.empty(self.n, dtype=x.dtype, device=x.device)
+        rp, ci, va = self._keep
+        spmv_transpose(self.h, self.m, rp, ci, va, x, y)
+        return y
 
     def update_values(self, val):
         """The caller changed the values (in place or in a new array of the same pattern)."""

@@ -268,6 +268,12 @@ struct spmv_dev {
     int *spmm_split = nullptr, *spmm_longs = nullptr;
     void *spmm_x = nullptr, *spmm_y = nullptr;
     size_t spmm_x_bytes = 0, spmm_y_bytes = 0;
+    // spmv_hip_spmv_transpose (shim/transpose.hpp): A^T as a matrix of its own (n x m), planned and built like any; perm[p] = our index of its entry p.
+    // val_gen counts spmv_shim_update_values calls; A^T's values are gathered again when tr_gen falls behind it.
+    spmv_dev *tr = nullptr;
+    int *tr_perm = nullptr;
+    size_t tr_perm_bytes = 0;
+    unsigned long long val_gen = 0, tr_gen = 0;
     long long device_bytes = 0;
     double inspect_ms = 0;
     std::vector<std::pair<void *, size_t>> sched_allocs; // (pointer, bytes): freed when the schedule is rebuilt

@@ -323,14 +323,14 @@ void spmv_hip_create_handle_from_blocks(spmv_Handle_t *Handle, int blocks, const
  * A_near + A_far (csrc/kernels/split.hpp), each half planned and inspected like any matrix -- near: the method's tile schedule, every
  * tile staged by construction, never the blocked executor; far: always the blocked executor, accumulating into y -- and the pair is
  * timed against the schedule as built; the faster stays (spmv_hip_info.split_ms, far_nnz). */
-static void try_split(spmv_Handle_t h, spmv_hip_state *st, SPMV_METHODS actual)
+static void try_split(spmv_Handle_t h, spmv_hip_state *st, spmv_dev *dev, SPMV_METHODS actual)
 {
     spmv_dev *halves[2] = {NULL, NULL};
     double t_built, t_split = -1.0;
     int k, ok = 1;
-    if (st->opts.v[SPMV_OPT_SPLIT] != 1 || !spmv_shim_split_candidate(st->dev)) return;
-    t_built = spmv_shim_time_self(st->dev, 5);
-    if (t_built <= 0.0 || spmv_shim_split(st->dev, &halves[0], &halves[1]) != SPMV_HIP_OK) return;
+    if (st->opts.v[SPMV_OPT_SPLIT] != 1 || !spmv_shim_split_candidate(dev)) return;
+    t_built = spmv_shim_time_self(dev, 5);
+    if (t_built <= 0.0 || spmv_shim_split(dev, &halves[0], &halves[1]) != SPMV_HIP_OK) return;
     for (k = 0; k < 2 && ok; ++k) {
         spmv_stats stats;
         spmv_plan plan;
@@ -354,23 +354,87 @@ static void try_split(spmv_Handle_t h, spmv_hip_state *st, SPMV_METHODS actual)
         fprintf(stderr, "[spmv_hip] split: as built %.4f ms; near %lld nnz %s %.4f ms; far %lld nnz %s %.4f ms (inspect %.1f / %.1f ms)\n", t_built, a.nnz, a.kernel_name,
                 tn, b.nnz, b.kernel_name, tf, a.inspect_ms, b.inspect_ms);
     }
-    if (ok && spmv_shim_attach_split(st->dev, halves[0], halves[1], 0) == SPMV_HIP_OK) {
-        t_split = spmv_shim_time_self(st->dev, 5);
-        if (t_split > 0.0 && t_split < 0.9 * t_built) (void) spmv_shim_attach_split(st->dev, halves[0], halves[1], 1); /* keep: drop the unsplit schedule */
-        else (void) spmv_shim_attach_split(st->dev, NULL, NULL, 0);                                                    /* destroys the halves */
+    if (ok && spmv_shim_attach_split(dev, halves[0], halves[1], 0) == SPMV_HIP_OK) {
+        t_split = spmv_shim_time_self(dev, 5);
+        if (t_split > 0.0 && t_split < 0.9 * t_built) (void) spmv_shim_attach_split(dev, halves[0], halves[1], 1); /* keep: drop the unsplit schedule */
+        else (void) spmv_shim_attach_split(dev, NULL, NULL, 0);                                                    /* destroys the halves */
     } else {
         if (halves[0]) spmv_shim_matrix_destroy(halves[0]);
         if (halves[1]) spmv_shim_matrix_destroy(halves[1]);
     }
-    spmv_shim_note_split_ms(st->dev, t_built, t_split);
+    spmv_shim_note_split_ms(dev, t_built, t_split);
     spmv_hip_clear_error();
+}
+
+/* Plan + inspect one uploaded matrix as create() does: row statistics -> spmv_plan_choose -> spmv_shim_build, the measured choice
+ * (auto_method = 2), the near / far split, the release of the column copy, the handle's stream and async setting.  Used for the handle's
+ * matrix (state_build) and for its transpose (transpose_ready), with the handle's requested method and options.  *plan and *actual receive
+ * what was chosen, *nnz the matrix's non-zeros.  A failure is reported; the matrix is the caller's to destroy. */
+static int plan_and_build(spmv_Handle_t h, spmv_hip_state *st, spmv_dev *dev, spmv_plan *plan_out, SPMV_METHODS *actual_out, long long *nnz_out)
+{
+    spmv_stats stats;
+    spmv_plan plan;
+    SPMV_METHODS actual = st->requested;
+    int rc = spmv_shim_matrix_stats(dev, &stats);
+    if (rc) { spmv_set_error(rc, "create/stats", spmv_shim_error_text()); return rc; }
+    spmv_plan_choose(st->requested, &stats, (size_t) h->data_size, &st->opts, &plan, &actual, 1);
+    rc = spmv_shim_build(dev, &plan);
+    if (rc) { spmv_set_error(rc, "create/inspect", spmv_shim_error_text()); return rc; }
+    /* A schedule that could not stage a single x window on a matrix whose x is far larger than an L2 is
+     * switched to the row-block x column-slab executor INSIDE spmv_shim_build (option "cache_block", default
+     * automatic) -- whatever the method, so Method_Parallel / Method_CSR5SPMV requests on matrices without
+     * column locality no longer run the gather-bound tile kernels. */
+    /* automatic choice, measured (auto_method = 2): the rules above pick from row statistics; which schedule is
+     * fastest also depends on the columns and, by a few percent, on the device (DESIGN.md 4).  For matrices
+     * large enough to be worth it, every candidate schedule is built and timed on scratch vectors and the
+     * fastest is kept (the rule-based choice stays on a tie within 2 %). */
+    if (st->opts.v[SPMV_OPT_AUTO_METHOD] == 2 && stats.nnz >= (1ll << 20)) {
+        static const SPMV_METHODS cand[] = {Method_Parallel, Method_CSR5SPMV, Method_SellCSigma, Method_Balanced_Yid, Method_Balanced};
+        spmv_plan best_plan = plan;
+        SPMV_METHODS best_method = actual;
+        double best_ms = spmv_shim_time_self(dev, 5);
+        unsigned k, j, nseen = 1;
+        spmv_plan seen[1 + sizeof cand / sizeof cand[0]]; /* schedules already built and timed: several methods may plan the same one (short heavy-tailed rows) */
+        int current_is_best = best_ms >= 0.0;
+        seen[0] = plan;
+        for (k = 0; k < sizeof cand / sizeof cand[0] && best_ms >= 0.0; ++k) {
+            spmv_plan p;
+            SPMV_METHODS a = cand[k];
+            double ms;
+            int dup = 0;
+            spmv_plan_choose(cand[k], &stats, (size_t) h->data_size, &st->opts, &p, &a, 0);
+            for (j = 0; j < nseen; ++j) /* the same schedule with the same shape is the same multiply whatever the method is called: timing noise must not choose */
+                if (seen[j].sched == p.sched && seen[j].lanes_per_row == p.lanes_per_row && seen[j].long_thr == p.long_thr && seen[j].sell_sigma == p.sell_sigma &&
+                    seen[j].sell_long_thr == p.sell_long_thr && seen[j].csr5_sigma == p.csr5_sigma && seen[j].rowblock_nnz == p.rowblock_nnz) dup = 1;
+            if (dup) continue;
+            seen[nseen++] = p;
+            if (spmv_shim_build(dev, &p) != SPMV_HIP_OK) { current_is_best = 0; continue; }
+            current_is_best = 0;
+            ms = spmv_shim_time_self(dev, 5);
+            if (ms >= 0.0 && ms < 0.98 * best_ms) { best_ms = ms; best_plan = p; best_method = a; current_is_best = 1; }
+        }
+        if (!current_is_best) {
+            rc = spmv_shim_build(dev, &best_plan);
+            if (rc) { spmv_set_error(rc, "create/inspect", spmv_shim_error_text()); return rc; }
+        }
+        plan = best_plan;
+        actual = best_method;
+    }
+    try_split(h, st, dev, actual);
+    if (st->opts.v[SPMV_OPT_KEEP_COLUMNS] == 0) (void) spmv_shim_release_columns(dev); /* the last build of this create is done */
+    if (st->stream_set) spmv_shim_set_stream(dev, st->stream);
+    spmv_shim_set_async(dev, st->async);
+    *plan_out = plan;
+    *actual_out = actual;
+    *nnz_out = stats.nnz;
+    return SPMV_HIP_OK;
 }
 
 /* Upload + plan + inspect.  Used by create and by spmv() when it is handed another matrix. */
 static int state_build(spmv_Handle_t h, spmv_hip_state *st, int m, int n, const int *RowPtr,
                        const int *ColIdx, const void *Val)
 {
-    spmv_stats stats;
+    long long nnz = 0;
     SPMV_METHODS actual = st->requested;
     int rc;
     if (st->opts.v[SPMV_OPT_GPUS] > 0) return state_build_multi(h, st, m, n, RowPtr, ColIdx, Val);
@@ -398,68 +462,15 @@ static int state_build(spmv_Handle_t h, spmv_hip_state *st, int m, int n, const 
             spmv_set_error(SPMV_HIP_E_RUNTIME, "create/reorder", perm ? spmv_shim_error_text() : "malloc(perm)");
         }
     }
-    rc = spmv_shim_matrix_stats(st->dev, &stats);
-    if (rc) { spmv_set_error(rc, "create/stats", spmv_shim_error_text()); return rc; }
-    spmv_plan_choose(st->requested, &stats, (size_t) h->data_size, &st->opts, &st->plan, &actual, 1);
-    rc = spmv_shim_build(st->dev, &st->plan);
+    rc = plan_and_build(h, st, st->dev, &st->plan, &actual, &nnz);
     if (rc) {
-        spmv_set_error(rc, "create/inspect", spmv_shim_error_text());
         spmv_shim_matrix_destroy(st->dev);
         st->dev = NULL;
         return rc;
     }
-    /* A schedule that could not stage a single x window on a matrix whose x is far larger than an L2 is
-     * switched to the row-block x column-slab executor INSIDE spmv_shim_build (option "cache_block", default
-     * automatic) -- whatever the method, so Method_Parallel / Method_CSR5SPMV requests on matrices without
-     * column locality no longer run the gather-bound tile kernels. */
-    /* automatic choice, measured (auto_method = 2): the rules above pick from row statistics; which schedule is
-     * fastest also depends on the columns and, by a few percent, on the device (DESIGN.md 4).  For matrices
-     * large enough to be worth it, every candidate schedule is built and timed on scratch vectors and the
-     * fastest is kept (the rule-based choice stays on a tie within 2 %). */
-    if (st->opts.v[SPMV_OPT_AUTO_METHOD] == 2 && stats.nnz >= (1ll << 20)) {
-        static const SPMV_METHODS cand[] = {Method_Parallel, Method_CSR5SPMV, Method_SellCSigma, Method_Balanced_Yid, Method_Balanced};
-        spmv_plan best_plan = st->plan;
-        SPMV_METHODS best_method = actual;
-        double best_ms = spmv_shim_time_self(st->dev, 5);
-        unsigned k, j, nseen = 1;
-        spmv_plan seen[1 + sizeof cand / sizeof cand[0]]; /* schedules already built and timed: several methods may plan the same one (short heavy-tailed rows) */
-        int current_is_best = best_ms >= 0.0;
-        seen[0] = st->plan;
-        for (k = 0; k < sizeof cand / sizeof cand[0] && best_ms >= 0.0; ++k) {
-            spmv_plan p;
-            SPMV_METHODS a = cand[k];
-            double ms;
-            int dup = 0;
-            spmv_plan_choose(cand[k], &stats, (size_t) h->data_size, &st->opts, &p, &a, 0);
-            for (j = 0; j < nseen; ++j) /* the same schedule with the same shape is the same multiply whatever the method is called: timing noise must not choose */
-                if (seen[j].sched == p.sched && seen[j].lanes_per_row == p.lanes_per_row && seen[j].long_thr == p.long_thr && seen[j].sell_sigma == p.sell_sigma &&
-                    seen[j].sell_long_thr == p.sell_long_thr && seen[j].csr5_sigma == p.csr5_sigma && seen[j].rowblock_nnz == p.rowblock_nnz) dup = 1;
-            if (dup) continue;
-            seen[nseen++] = p;
-            if (spmv_shim_build(st->dev, &p) != SPMV_HIP_OK) { current_is_best = 0; continue; }
-            current_is_best = 0;
-            ms = spmv_shim_time_self(st->dev, 5);
-            if (ms >= 0.0 && ms < 0.98 * best_ms) { best_ms = ms; best_plan = p; best_method = a; current_is_best = 1; }
-        }
-        if (!current_is_best) {
-            rc = spmv_shim_build(st->dev, &best_plan);
-            if (rc) {
-                spmv_set_error(rc, "create/inspect", spmv_shim_error_text());
-                spmv_shim_matrix_destroy(st->dev);
-                st->dev = NULL;
-                return rc;
-            }
-        }
-        st->plan = best_plan;
-        actual = best_method;
-    }
-    try_split(h, st, actual);
-    if (st->opts.v[SPMV_OPT_KEEP_COLUMNS] == 0) (void) spmv_shim_release_columns(st->dev); /* the last build of this create is done */
-    if (st->stream_set) spmv_shim_set_stream(st->dev, st->stream);
-    spmv_shim_set_async(st->dev, st->async);
     st->m = m;
     st->n = n;
-    watch_values(h, st, Val, stats.nnz);
+    watch_values(h, st, Val, nnz);
     h->spmvMethod = actual;
     h->RowPtr = (BASIC_INT_TYPE *) RowPtr;
     h->ColIdx = (BASIC_INT_TYPE *) ColIdx;
@@ -854,4 +865,118 @@ double spmv_hip_time_spmm_launches(spmv_Handle_t h, int k, const void *X, long l
     r = spmv_shim_time_spmm(st->dev, k, X, ldx, Y, ldy, warmup, iters, ms_out);
     if (r < 0) spmv_set_error(SPMV_HIP_E_RUNTIME, "time_spmm_launches", spmv_shim_error_text());
     return r;
+}
+
+/* ---------------------------------------------------------------- y = A^T x */
+/* Handle rules shared by the transpose entry points: 0 and *out = the single-GPU device state, or the code already reported. */
+static int transpose_state(spmv_Handle_t h, const char *where, spmv_hip_state **out)
+{
+    spmv_hip_state *st = h ? (spmv_hip_state *) h->extraHandle : NULL;
+    *out = NULL;
+    if (!h) { spmv_set_error(SPMV_HIP_E_ARG, where, "handle is NULL"); return SPMV_HIP_E_ARG; }
+    if (st && st->host_rows) { spmv_set_error(SPMV_HIP_E_ARG, where, "not available on a host_rows handle"); return SPMV_HIP_E_ARG; }
+    if (st && st->multi) { spmv_set_error(SPMV_HIP_E_ARG, where, "not available on a multi-GPU handle (option \"gpus\", create_handle_from_blocks)"); return SPMV_HIP_E_ARG; }
+    if (!st || !st->dev) { spmv_set_error(SPMV_HIP_E_NOSTATE, where, "handle has no device state (create failed or handle cleared)"); return SPMV_HIP_E_NOSTATE; }
+    *out = st;
+    return SPMV_HIP_OK;
+}
+
+/* A^T of the resident matrix: built on the device once per resident matrix, planned and inspected by the code path of create() with the
+ * handle's requested method and options, attached to the resident matrix; afterwards its values are gathered again whenever A's changed.
+ * When create() released the resident ColIdx, it is restored for the build and released again, so the forward multiply is unchanged. */
+static int transpose_ready(spmv_Handle_t h, spmv_hip_state *st, const char *where)
+{
+    int rc;
+    if (!spmv_shim_transpose_of(st->dev)) {
+        const int *ci = NULL;
+        spmv_dev *child = NULL;
+        int *perm = NULL;
+        long long nnz = 0;
+        SPMV_METHODS actual = st->requested;
+        spmv_plan plan;
+        int released;
+        spmv_shim_matrix_arrays(st->dev, NULL, &ci, NULL);
+        released = ci == NULL;
+        if ((rc = spmm_columns(h, st, where)) != SPMV_HIP_OK) return rc;
+        rc = spmv_shim_transpose(st->dev, &child, &perm);
+        if (released) (void) spmv_shim_release_columns(st->dev);
+        if (rc) { spmv_set_error(rc, where, spmv_shim_error_text()); return rc; }
+        if ((rc = spmv_shim_attach_transpose(st->dev, child, perm)) != SPMV_HIP_OK) {
+            spmv_set_error(rc, where, spmv_shim_error_text());
+            spmv_shim_matrix_destroy(child);
+            return rc;
+        }
+        if ((rc = plan_and_build(h, st, child, &plan, &actual, &nnz)) != SPMV_HIP_OK) {
+            (void) spmv_shim_attach_transpose(st->dev, NULL, NULL); /* destroys child and perm */
+            return rc;
+        }
+        st->tplan = plan;
+        st->tmethod = actual;
+    }
+    rc = spmv_shim_transpose_refresh(st->dev);
+    if (rc) spmv_set_error(rc, where, spmv_shim_error_text());
+    return rc;
+}
+
+int spmv_hip_spmv_transpose(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                            const void *Matrix_Val, const void *X, void *Y)
+{
+    spmv_hip_state *st;
+    int rc = transpose_state(handle, "spmv_transpose", &st);
+    if (rc) return rc;
+    if ((m > 0 && !X) || (st->n > 0 && !Y)) { spmv_set_error(SPMV_HIP_E_ARG, "spmv_transpose", "X or Y is NULL"); return SPMV_HIP_E_ARG; }
+    if ((rc = refresh_resident(handle, st, m, RowPtr, ColIdx, Matrix_Val)) != SPMV_HIP_OK) return rc;
+    if (!st->dev) { spmv_set_error(SPMV_HIP_E_NOSTATE, "spmv_transpose", "handle has no device state"); return SPMV_HIP_E_NOSTATE; }
+    if ((rc = transpose_ready(handle, st, "spmv_transpose")) != SPMV_HIP_OK) return rc;
+    rc = spmv_shim_run(spmv_shim_transpose_of(st->dev), X, Y);
+    if (rc) spmv_set_error(rc, "spmv_transpose", spmv_shim_error_text());
+    return rc;
+}
+
+int spmv_hip_prepare_transpose(spmv_Handle_t handle)
+{
+    spmv_hip_state *st;
+    int rc = transpose_state(handle, "prepare_transpose", &st);
+    if (rc) return rc;
+    return transpose_ready(handle, st, "prepare_transpose");
+}
+
+int spmv_hip_get_transpose_info(spmv_Handle_t handle, spmv_hip_info *out)
+{
+    spmv_hip_state *st;
+    int rc = transpose_state(handle, "get_transpose_info", &st);
+    if (rc) return rc;
+    if (!out) { spmv_set_error(SPMV_HIP_E_ARG, "get_transpose_info", "out is NULL"); return SPMV_HIP_E_ARG; }
+    if (!spmv_shim_transpose_of(st->dev)) {
+        spmv_set_error(SPMV_HIP_E_NOSTATE, "get_transpose_info", "the transpose is not built (spmv_hip_prepare_transpose, or a first spmv_hip_spmv_transpose)");
+        return SPMV_HIP_E_NOSTATE;
+    }
+    rc = spmv_shim_info(spmv_shim_transpose_of(st->dev), out);
+    if (rc) spmv_set_error(rc, "get_transpose_info", spmv_shim_error_text());
+    return rc;
+}
+
+double spmv_hip_time_transpose_launches(spmv_Handle_t h, const void *x, void *y, int warmup, int iters, float *ms_out)
+{
+    spmv_hip_state *st;
+    double r;
+    if (transpose_state(h, "time_transpose_launches", &st) != SPMV_HIP_OK) return -1.0;
+    if (transpose_ready(h, st, "time_transpose_launches") != SPMV_HIP_OK) return -1.0;
+    r = spmv_shim_time(spmv_shim_transpose_of(st->dev), x, y, warmup, iters, ms_out);
+    if (r < 0) spmv_set_error(SPMV_HIP_E_RUNTIME, "time_transpose_launches", spmv_shim_error_text());
+    return r;
+}
+
+int spmv_hip_transpose_map(spmv_Handle_t h, int *rowptr_t, int *perm)
+{
+    spmv_hip_state *st;
+    int rc = transpose_state(h, "transpose_map", &st);
+    if (rc) return rc;
+    if (!spmv_shim_transpose_of(st->dev)) {
+        spmv_set_error(SPMV_HIP_E_NOSTATE, "transpose_map", "the transpose is not built (spmv_hip_prepare_transpose, or a first spmv_hip_spmv_transpose)");
+        return SPMV_HIP_E_NOSTATE;
+    }
+    rc = spmv_shim_transpose_map(st->dev, rowptr_t, perm);
+    if (rc) spmv_set_error(rc, "transpose_map", spmv_shim_error_text());
+    return rc;
 }

@@ -28,6 +28,8 @@ typedef struct spmv_hip_state {
     int host_rows;          /* 1: VECTOR_NONE + option "host_rows": the plain-C row loop (host_rows.c), no device state */
     SPMV_METHODS requested; /* method asked for at create (handle->spmvMethod may be rewritten) */
     spmv_plan plan;
+    spmv_plan tplan;        /* spmv_hip_spmv_transpose: the schedule chosen for A^T (valid once it is built) */
+    SPMV_METHODS tmethod;   /* ... and the method it reports */
     spmv_options opts;      /* the options this handle was created with */
     int m, n;
     void *stream;

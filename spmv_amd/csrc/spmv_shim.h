@@ -105,6 +105,17 @@ double spmv_shim_time_spmm(spmv_dev *d, int k, const void *x, long long ldx, voi
  * with perm_host (m ints, the create-time reordering: row i of the resident matrix = row perm_host[i] of the caller's).  No-op when resident. */
 int spmv_shim_restore_columns(spmv_dev *d, const int *rowptr, const int *colidx, const int *perm_host);
 
+/* ---- A^T as a matrix of its own (shim/transpose.hpp; spmv_hip_spmv_transpose) ----
+ * spmv_shim_transpose: A^T (n x m, rows listing their entries in ascending row of A) built on the device from the resident CSR -- unplanned,
+ * owning its arrays -- and perm (device, nnz ints: perm[p] = the CSR index in A of A^T's entry p).  Needs the resident ColIdx.  The caller
+ * plans + builds the child and attaches it (NULLs: detach + destroy); the parent owns both from then on, counts them in its info's
+ * device_bytes and frees them at destroy.  spmv_shim_transpose_refresh gathers A's values again after spmv_shim_update_values. */
+int spmv_shim_transpose(spmv_dev *d, spmv_dev **out, int **perm_out);
+int spmv_shim_attach_transpose(spmv_dev *d, spmv_dev *child, int *perm);
+spmv_dev *spmv_shim_transpose_of(const spmv_dev *d); /* NULL until attached */
+int spmv_shim_transpose_refresh(spmv_dev *d);
+int spmv_shim_transpose_map(spmv_dev *d, int *rowptr_t, int *perm); /* copies to host; either may be NULL */
+
 /* the resident CSR arrays (device pointers; ColIdx may be NULL after spmv_shim_release_columns) */
 void spmv_shim_matrix_arrays(const spmv_dev *d, const int **rowptr, const int **colidx, const void **val);
 

@@ -34,6 +34,7 @@
 #include "kernels/rcm.hpp"
 #include "kernels/csr_vector_tile.hpp"
 #include "kernels/spmm.hpp"
+#include "kernels/transpose.hpp"
 
 using namespace spmv;
 
@@ -164,6 +165,8 @@ extern "C" void spmv_shim_matrix_destroy(spmv_dev *d)
     if (d->sp_near) { spmv_shim_matrix_destroy(d->sp_near); d->sp_near = nullptr; }
     if (d->sp_far) { spmv_shim_matrix_destroy(d->sp_far); d->sp_far = nullptr; }
     if (d->sp_centre) { (void) pool_free(d->sp_centre); d->sp_centre = nullptr; }
+    if (d->tr) { spmv_shim_matrix_destroy(d->tr); d->tr = nullptr; }
+    if (d->tr_perm) { (void) pool_free(d->tr_perm); d->tr_perm = nullptr; }
     free_schedule(d);
     if (d->rowptr) (void) pool_free(d->rowptr);
     if (d->colidx) (void) pool_free(d->colidx);
@@ -444,13 +447,16 @@ extern "C" int spmv_shim_update_values(spmv_dev *d, const void *val)
     if (!guard.ok) return fail(SPMV_HIP_E_RUNTIME, "hipSetDevice(%d) failed", d->device);
     if (d->sp_near && d->sp_far) { // split handle: the resident values first, then both halves from them (same positions as at create)
         d->sp_near->stream = d->sp_far->stream = d->stream;
-        HIP_TRY(hipMemcpyAsync(d->val, val, d->vsize * (size_t) d->nnz, hipMemcpyDefault, d->stream));
+        if (val != d->val) HIP_TRY(hipMemcpyAsync(d->val, val, d->vsize * (size_t) d->nnz, hipMemcpyDefault, d->stream)); // a transpose refreshes in place
         int rc = d->vsize == sizeof(double) ? split_make<double>(d, nullptr, nullptr, true) : split_make<float>(d, nullptr, nullptr, true);
         if (!rc) rc = spmv_shim_update_values(d->sp_near, d->sp_near->val);
         if (!rc) rc = spmv_shim_update_values(d->sp_far, d->sp_far->val);
+        if (!rc) ++d->val_gen;
         return rc;
     }
-    return d->vsize == sizeof(double) ? update_values<double>(d, val) : update_values<float>(d, val);
+    const int rc = d->vsize == sizeof(double) ? update_values<double>(d, val) : update_values<float>(d, val);
+    if (!rc) ++d->val_gen; // an attached transpose gathers the new values at its next multiply (shim/transpose.hpp)
+    return rc;
 }
 
 // Checksum of the value array (option "check_values"): the sum over the 32-bit words of word * (odd multiplier of its
@@ -532,6 +538,7 @@ extern "C" int spmv_shim_is_device_ptr(const void *p) { return is_device_ptr(p) 
 #include "shim/launch.hpp"
 #include "shim/split.hpp"
 #include "shim/spmm.hpp"
+#include "shim/transpose.hpp"
 
 extern "C" int spmv_shim_run(spmv_dev *d, const void *x, void *y)
 {
@@ -566,6 +573,7 @@ extern "C" int spmv_shim_set_stream(spmv_dev *d, void *stream)
     // the halves of a split handle launch on the parent's stream; a values refresh between set_stream and the next multiply must already see it
     if (d->sp_near) d->sp_near->stream = d->stream;
     if (d->sp_far) d->sp_far->stream = d->stream;
+    if (d->tr) (void) spmv_shim_set_stream(d->tr, stream);
     return SPMV_HIP_OK;
 }
 
@@ -573,6 +581,7 @@ extern "C" int spmv_shim_set_async(spmv_dev *d, int async)
 {
     if (!d) return fail(SPMV_HIP_E_ARG, "set_async: NULL");
     d->async = async;
+    if (d->tr) (void) spmv_shim_set_async(d->tr, async);
     return SPMV_HIP_OK;
 }
 
@@ -675,7 +684,7 @@ extern "C" int spmv_shim_info(const spmv_dev *d, spmv_hip_info *o)
         o->nnz = d->nnz;
         o->stored_nnz += f.stored_nnz;
         o->max_row_len = d->stats.max_row_len; o->min_row_len = d->stats.min_row_len; o->empty_rows = d->stats.empty_rows; o->mean_row_len = d->stats.mean_row_len;
-        o->device_bytes = d->device_bytes + d->sp_near->device_bytes + d->sp_far->device_bytes;
+        o->device_bytes = d->device_bytes + d->sp_near->device_bytes + d->sp_far->device_bytes + transpose_bytes(d);
         o->alg_bytes = 4ll * ((long long) d->m + 1) + d->nnz * (4 + s) + s * d->n + s * d->m;
         o->stream_bytes += f.stream_bytes;
         o->x_bytes += f.x_bytes;
@@ -703,7 +712,7 @@ extern "C" int spmv_shim_info(const spmv_dev *d, spmv_hip_info *o)
     o->min_row_len = d->stats.min_row_len;
     o->empty_rows = d->stats.empty_rows;
     o->mean_row_len = d->stats.mean_row_len;
-    o->device_bytes = d->device_bytes;
+    o->device_bytes = d->device_bytes + transpose_bytes(d);
     const long long s = (long long) d->vsize;
     o->alg_bytes = 4ll * ((long long) d->m + 1) + d->nnz * (4 + s) + s * d->n + s * d->m;
     o->inspect_ms = d->inspect_ms;
