@@ -432,7 +432,7 @@ __device__ __forceinline__ void csr5_tile_compute(int t, int lane, const int (&c
     bool write = started;
     if constexpr (FWD) {
         if (fw.count != 0) { // wave-uniform: the tile's last row goes on behind the tile
-            T fs = fw.v * fx;
+            T fs = lane < fw.count ? fw.v * fx : T(0); // lanes beyond the row add nothing: 0 * x[0] would carry a NaN / Inf of x[0] into it
             for (int k = kWave + lane; k < fw.count; k += kWave) fs = fmadd(fw.val[fw.base + k], x[fw.colidx[fw.base + k]], fs); // more than 64 entries behind the cut: rare
             fs = lane0_value(group_sum_dpp<kWave>(fs));
             if (lane == 63 - __clzll((long long) starts)) { // the lane that holds the row's start
@@ -907,7 +907,7 @@ __device__ __forceinline__ void nat_long_row(int4 row, const int *__restrict__ c
             v[j] = q < e ? val[q] : T(0);
         }
 #pragma unroll
-        for (int j = 0; j < U; ++j) acc = fmadd(v[j], x[c[j]], acc);
+        for (int j = 0; j < U; ++j) acc = fmadd(v[j], k + j * kBlock < e ? x[c[j]] : T(0), acc); // past the row: 0 * 0, never 0 * x[0] (x[0] may be NaN / Inf)
     }
 #pragma unroll
     for (int o = kWave / 2; o > 0; o >>= 1) acc += __shfl_xor(acc, o, kWave);

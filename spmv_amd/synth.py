@@ -10,6 +10,7 @@ Value/x fills
                the same bits and schedules can be compared bitwise.
     "uniform"  uniform(-1, 1)      -- tolerance tests.
     "ones"     1                   -- x of the reference harness.
+The dyadic_* draws (end of this file) are the full-precision, signed counterpart of "eighths".
 
 All generators are deterministic in (shape, seed).
 """
@@ -21,6 +22,7 @@ __all__ = [
     "CSR", "fill_values", "fill_x", "banded", "uniform_k", "powerlaw", "skewed_rows",
     "from_row_lengths", "with_empty_rows", "dense_rows", "banded_device", "uniform_k_device", "rmat_columns_device",
     "from_row_lengths_device", "skewed_lengths_device", "powerlaw_lengths_device",
+    "DyadicPlan", "dyadic_plan", "dyadic_row_bits", "dyadic_values", "dyadic_x", "dyadic_values_device", "dyadic_x_device",
 ]
 
 
@@ -342,3 +344,148 @@ def powerlaw_lengths_device(m, mean_len=3.1, max_len=4700, alpha=1.6, device="cu
     raw = u.pow(-1.0 / alpha)
     lens = torch.floor(raw * mean_len * (alpha - 1.0) / alpha).clamp_(max=max_len)
     return lens.to(torch.int64)
+
+
+# ----------------------------------------------------------------------------- full-precision signed dyadic operands
+# "eighths" proves the indexing, but its operands are exact in fp16 and never negative: it cannot see an fp64 operand rounded through
+# fp32, an fp64 row accumulated in fp32, or a lost sign.  These draws keep every partial sum exact (so schedules still compare bit for
+# bit) while using the whole significand of one operand:
+#     val = vi * 2**ev,  x = xi * 2**ex,  vi / xi signed integers,
+#     bits(|vi|) + bits(|xi|) + ceil(log2(L + 1)) <= p   for a row of length L  (p = 53 fp64, 24 fp32; one less for the subnormal draw)
+# so every partial sum of a row's products is an integer below 2^p times 2^(ev + ex), exact in the value type in any order.
+# The wide operand alternates with `case`: even = wide values (fp64 30 bits, fp32 up to 16), odd = wide x (fp64 30 bits, fp32 up to 12,
+# both capped by the longest row).  A wide integer has its top and bottom bits set: an fp64 one needs more than fp32's 24 bits and an
+# fp32 one of 12 or more bits more than fp16's 11.  ev / ex are drawn from whole-matrix scales that include 2^+-300 (fp64) and
+# 2^+-40 (fp32); the subnormal draw puts the product grid at the smallest subnormal with row sums below the smallest normal.
+_DYADIC = {  # dtype: (p, wide value bits, wide x bits, narrow bits, scales, subnormal (ev, ex))
+    np.dtype(np.float64): (53, 30, 30, 8, (0, 0, 3, -7, 300, -300), (-537, -537)),
+    np.dtype(np.float32): (24, 16, 12, 4, (0, 0, 3, -7, 40, -40), (-75, -74)),
+}
+DYADIC_X_ZEROS = 0.03                           # share of x set to +0.0 / -0.0 (a negative value times +0.0 is a -0.0 product)
+
+
+class DyadicPlan:
+    """The shared part of one draw: the value type, the scales, the width of x and the cap on the width of the values."""
+
+    def __init__(self, dtype, p, ev, ex, xbits, vcap, wide_values):
+        self.dtype, self.p, self.ev, self.ex = np.dtype(dtype), int(p), int(ev), int(ex)
+        self.xbits, self.vcap, self.wide_values = int(xbits), int(vcap), bool(wide_values)
+
+    def __repr__(self):
+        return (f"DyadicPlan({self.dtype.name}, p={self.p}, ev={self.ev}, ex={self.ex}, xbits={self.xbits}, vcap={self.vcap}, "
+                f"wide={'values' if self.wide_values else 'x'})")
+
+
+def bit_length(a):
+    """ceil(log2(a + 1)) = bits of |a| for an int64 numpy array with |a| < 2^53 (0 -> 0)."""
+    return np.frexp(np.abs(np.asarray(a, dtype=np.int64)).astype(np.float64))[1].astype(np.int64)
+
+
+def dyadic_plan(max_len, dtype, case, seed, subnormal=False):
+    """-> DyadicPlan for matrices whose rows (and, for the transpose, columns) hold at most max_len entries."""
+    p, wide_v, wide_x, narrow, scales, sub = _DYADIC[np.dtype(dtype)]
+    p -= 1 if subnormal else 0
+    lg = int(max_len).bit_length()
+    wide_values = case % 2 == 0
+    xbits = narrow if wide_values else min(wide_x, p - 1 - lg)
+    assert xbits >= 1 and p - xbits - lg >= 1, ("rows too long for the bit budget", max_len, dtype)
+    rng = np.random.default_rng(seed + 7919 * case)
+    ev, ex = sub if subnormal else (int(rng.choice(scales)), int(rng.choice(scales)))
+    return DyadicPlan(dtype, p, ev, ex, xbits, wide_v if wide_values else narrow, wide_values)
+
+
+def dyadic_row_bits(lens, plan):
+    """Width of the values of rows of these lengths: the budget left beside x and the row length, capped by the plan."""
+    return np.minimum(plan.p - plan.xbits - bit_length(lens), plan.vcap)
+
+
+def _signed_ints(r, s, b, wide):
+    """Signed integers of at most b bits from random words r and sign bits s; wide ones have bits b-1 and 0 set."""
+    one = np.int64(1)
+    if wide:
+        mag = (r & ((one << (b - 1)) - 1)) | (one << (b - 1)) | 1
+    else:
+        mag = r & ((one << b) - 1)
+    return np.where(s, -mag, mag)
+
+
+def _entry_lens(rowptr, colidx, n):
+    rp = np.asarray(rowptr, dtype=np.int64)
+    lens = np.diff(rp)
+    el = np.repeat(lens, lens)
+    if colidx is not None:                      # the transpose's rows are this matrix's columns: the budget holds for both
+        cl = np.bincount(np.asarray(colidx, dtype=np.int64), minlength=n)
+        el = np.maximum(el, cl[np.asarray(colidx, dtype=np.int64)])
+    return el
+
+
+def dyadic_values(rowptr, plan, seed, colidx=None, n=None):
+    """Values for a matrix with this RowPtr under `plan` (numpy, the plan's dtype).  With colidx / n the bit budget also holds for the
+    columns, so that A^T x is exact too."""
+    el = _entry_lens(rowptr, colidx, n)
+    b = dyadic_row_bits(el, plan)
+    assert el.size == 0 or int(b.min()) >= 1, ("rows too long for the plan", int(el.max()), plan)
+    rng = np.random.default_rng(seed)
+    r = rng.integers(0, 1 << 62, size=el.size, dtype=np.int64)
+    s = rng.integers(0, 2, size=el.size).astype(bool)
+    vi = _signed_ints(r, s, b, plan.wide_values)
+    return np.ldexp(vi.astype(np.float64), plan.ev).astype(plan.dtype)
+
+
+def dyadic_x(n, plan, seed):
+    """x for the plan (numpy): xbits-wide signed integers times 2**ex, DYADIC_X_ZEROS of them +0.0 / -0.0."""
+    rng = np.random.default_rng(seed ^ 0x5BD1E995)
+    r = rng.integers(0, 1 << 62, size=n, dtype=np.int64)
+    s = rng.integers(0, 2, size=n).astype(bool)
+    x = np.ldexp(_signed_ints(r, s, np.full(n, plan.xbits, dtype=np.int64), not plan.wide_values).astype(np.float64), plan.ex)
+    z = rng.random(n) < DYADIC_X_ZEROS
+    x[z] = np.where(s[z], -0.0, 0.0)
+    return x.astype(plan.dtype)
+
+
+def dyadic_values_device(rowptr, plan, seed, colidx=None, n=None):
+    """Device twin of dyadic_values (torch tensors on rowptr's device, value dtype = the plan's)."""
+    torch = _torch()
+    dev = rowptr.device
+    rp = rowptr.to(torch.int64)
+    lens = rp[1:] - rp[:-1]
+    el = torch.repeat_interleave(lens, lens)
+    if colidx is not None:
+        c = colidx.to(torch.int64)
+        el = torch.maximum(el, torch.bincount(c, minlength=n)[c])
+    b = torch.clamp(plan.p - plan.xbits - torch.frexp(el.to(torch.float64))[1].to(torch.int64), max=plan.vcap)
+    assert el.numel() == 0 or int(b.min()) >= 1, ("rows too long for the plan", plan)
+    g = torch.Generator(device=dev)
+    g.manual_seed(seed)
+    r = torch.randint(0, 1 << 62, (el.numel(),), generator=g, device=dev, dtype=torch.int64)
+    one = torch.ones_like(b)
+    if plan.wide_values:
+        mag = (r & ((one << (b - 1)) - 1)) | (one << (b - 1)) | 1
+    else:
+        mag = r & ((one << b) - 1)
+    del r, one, el
+    mag = torch.where(torch.randint(0, 2, mag.shape, generator=g, device=dev, dtype=torch.int64) == 1, -mag, mag)
+    return (mag.to(torch.float64) * 2.0**plan.ev).to(_torch_dtype(plan.dtype))     # a power-of-two scalar: exact (torch.ldexp goes through pow)
+
+
+def dyadic_x_device(n, plan, seed, device="cuda"):
+    """Device twin of dyadic_x."""
+    torch = _torch()
+    g = torch.Generator(device=device)
+    g.manual_seed(seed ^ 0x5BD1E995)
+    r = torch.randint(0, 1 << 62, (n,), generator=g, device=device, dtype=torch.int64)
+    s = torch.randint(0, 2, (n,), generator=g, device=device, dtype=torch.int64) == 1
+    b = plan.xbits
+    if plan.wide_values:
+        mag = r & ((1 << b) - 1)
+    else:
+        mag = (r & ((1 << (b - 1)) - 1)) | (1 << (b - 1)) | 1
+    x = torch.where(s, -mag, mag).to(torch.float64) * 2.0**plan.ex
+    z = torch.rand(n, generator=g, device=device) < DYADIC_X_ZEROS
+    x = torch.where(z, torch.where(s, -0.0, 0.0).to(torch.float64), x)
+    return x.to(_torch_dtype(plan.dtype))
+
+
+def _torch_dtype(dtype):
+    torch = _torch()
+    return torch.float64 if np.dtype(dtype) == np.float64 else torch.float32

@@ -58,8 +58,8 @@ CASES = [  # (rows, columns, row-length kind, column locality, dtype)
 ]
 
 
-@pytest.mark.parametrize("case", range(len(CASES)))
-def test_big_shapes_every_schedule_matches_the_definition(case):
+def _matrix(case):
+    """-> (rp, ci, va, g) of CASES[case] on the device ("eighths" values); g is the case's generator, left where x is drawn from it."""
     m, n, kind, local, dt = CASES[case]
     g = torch.Generator(device=DEV)
     g.manual_seed(100 + case)
@@ -84,6 +84,13 @@ def test_big_shapes_every_schedule_matches_the_definition(case):
         _, _, rp, ci, va = synth.from_row_lengths_device(lens, n, "eighths", dt, DEV, seed=200 + case, cols=local)
     else:
         _, _, rp, ci, va = synth.from_row_lengths_device(lens, n, "eighths", dt, DEV, seed=200 + case, local=local)
+    return rp, ci, va, g
+
+
+@pytest.mark.parametrize("case", range(len(CASES)))
+def test_big_shapes_every_schedule_matches_the_definition(case):
+    m, n, kind, local, dt = CASES[case]
+    rp, ci, va, g = _matrix(case)
     x = (torch.randint(-8, 9, (n,), generator=g, device=DEV).to(dt) * 0.125)
     want = _definition(rp, ci, va, x)
     seen = set()
