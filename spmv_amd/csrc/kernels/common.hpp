@@ -4,6 +4,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+#include <mutex>
+
 namespace spmv {
 
 constexpr int kWave = 64;   // wavefront width (cdna_hip_programming.md 1: hard-code 64)
@@ -155,6 +158,30 @@ __device__ __forceinline__ int upper_bound_dev(const int *a, int n, long long ke
         if ((long long) a[mid] <= key) lo = mid + 1; else hi = mid;
     }
     return lo;
+}
+
+// ---- host: launch helpers of every translation unit that launches kernels ------------------------
+inline int grid_for(long long work_items, int per_block, int cap)
+{
+    long long g = (work_items + per_block - 1) / per_block;
+    if (g < 1) g = 1;
+    if (g > cap) g = cap;
+    return (int) g;
+}
+
+// Dynamic LDS above the 64 KiB default needs hipFuncAttributeMaxDynamicSharedMemorySize raised once per kernel
+// instantiation (and per device): remembered here, so that launches do not pay the call every time.
+template <auto Kernel>
+inline void ensure_lds(int device, size_t bytes, size_t static_bytes = 0)
+{
+    static std::mutex lock;
+    static std::atomic<size_t> granted[64]; // per device ordinal; zero-initialised = the 64 KiB default
+    const int dev = device >= 0 && device < 64 ? device : 0;
+    if (bytes + static_bytes <= 64 * 1024 || bytes <= granted[dev].load(std::memory_order_acquire)) return;
+    std::lock_guard<std::mutex> g(lock); // the attribute only ever grows: a second thread must not set a smaller value after a larger one
+    if (bytes <= granted[dev].load(std::memory_order_relaxed)) return;
+    if (hipFuncSetAttribute((const void *) Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) bytes) == hipSuccess) granted[dev].store(bytes, std::memory_order_release);
+    else (void) hipGetLastError();
 }
 
 } // namespace spmv

@@ -34,18 +34,6 @@ struct TileWindows {
     int runs;            // CSR-vector tiles only: 1 = every row's columns are ONE run of consecutive columns (csr_vector_tile.hpp: no column stream)
 };
 
-// sum of TileWindows::total over `count` tiles: the x elements one launch stages (traffic model, spmv_hip_info.stream_bytes)
-static __global__ __launch_bounds__(kBlock) void wins_total_kernel(int count, const TileWindows *__restrict__ wins, unsigned long long *__restrict__ sum,
-                                                            unsigned long long *__restrict__ staged_tiles)
-{
-    unsigned long long t = 0, c = 0;
-    for (long long i = (long long) blockIdx.x * kBlock + threadIdx.x; i < count; i += (long long) gridDim.x * kBlock)
-        if (wins[i].nwin > 0) { t += (unsigned long long) wins[i].total; c += 1; }
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) { t += __shfl_xor(t, o, kWave); c += __shfl_xor(c, o, kWave); }
-    if ((threadIdx.x & (kWave - 1)) == 0 && c) { atomicAdd(sum, t); atomicAdd(staged_tiles, c); }
-}
-
 // Stage the tile's windows: xs[base_w + i] = x[start_w + i].  NT = threads of the workgroup.  16-byte loads, four in flight per
 // thread, from the first 16-byte boundary of the window on (x is the caller's pointer: any element alignment): a wide window --
 // 10 000 columns of a CSR5 / SELL group whose rows scatter +-4096 around the diagonal -- is three round trips to L2 instead of eleven,
@@ -213,47 +201,6 @@ __device__ __forceinline__ void build_windows(int n, int max_cols, Loop loop, St
         }
         store(pos, slot, total);
     });
-}
-
-// Inspector for tiles that are CONTIGUOUS RANGES of a private column array (CSR5 tile groups,
-// nnz-split tile groups, SELL sigma windows): group g covers cols[b, e) with
-// b = bounds ? bounds[g * bstride] * scale : g * group_len,  e likewise (clipped to total).
-// cols16 == NULL: in place (cols then holds int32 slots for staged groups).  Else cols is left
-// alone (unstaged groups keep reading global columns from it) and the staged groups' slots go to the
-// 16-bit stream cols16, padding entries to the zero slot; pack16 = 0: same positions, pack16 =
-// sigma (CSR5): position t*64*sigma + i*64 + lane -> t*64*sigma + (i/4)*256 + lane*4 + i%4, so a
-// lane fetches four slots with one 8-byte load.
-static __global__ __launch_bounds__(kBlock) void range_windows_kernel(long long total, long long group_len,
-                                                               const long long *__restrict__ bounds, int bstride, int scale,
-                                                               long long nbounds /* bounds has nbounds + 1 entries */,
-                                                               int n, int max_cols, int *__restrict__ cols,
-                                                               unsigned short *__restrict__ cols16, int pack16,
-                                                               TileWindows *__restrict__ wins, int *__restrict__ staged, int rewrite)
-{
-    long long b, e;
-    if (bounds) {
-        long long i0 = (long long) blockIdx.x * bstride, i1 = i0 + bstride;
-        if (i0 > nbounds) i0 = nbounds;
-        if (i1 > nbounds) i1 = nbounds;
-        b = bounds[i0] * scale;
-        e = bounds[i1] * scale;
-    }
-    else { b = (long long) blockIdx.x * group_len; e = b + group_len; }
-    if (e > total) e = total;
-    auto loop = [&](auto body) {
-        for (long long i = b + threadIdx.x; i < e; i += kBlock) body(cols[i], i);
-    };
-    auto store = [&](long long pos, int slot, int tile_total) {
-        if (!cols16) { if (slot >= 0) cols[pos] = slot; return; }
-        long long q = pos;
-        if (pack16) {
-            const long long tn = (long long) kWave * pack16, t = pos / tn;
-            const int o = (int) (pos - t * tn), i = o / kWave, lane = o % kWave;
-            q = t * tn + (i / 4) * (4 * kWave) + lane * 4 + (i % 4);
-        }
-        cols16[q] = (unsigned short) (slot >= 0 ? slot : tile_total);
-    };
-    build_windows(n, max_cols, loop, store, wins[blockIdx.x], staged, rewrite != 0);
 }
 
 } // namespace spmv

@@ -40,7 +40,7 @@ template <typename T>
 static int build_csr5(spmv_dev *d, Csr5Plan &P, int m, long long nnz, const int *rowptr, const int *colidx, const T *val, int empty_rows,
                       double mean_row_len, const int *out_rows, bool natural = false, int sigma_override = 0);
 template <typename T> static int autotune_vector(spmv_dev *d);
-template <typename T> static int autotune_rows(spmv_dev *d, const int *split);
+template <typename T> static int autotune_rows(spmv_dev *d);
 template <typename T> static int autotune_blocked(spmv_dev *d);
 template <typename T> static double time_schedule(spmv_dev *d, int iters);
 template <typename T> static int split_make(spmv_dev *d, spmv_dev **near_out, spmv_dev **far_out, bool values_only);
@@ -555,9 +555,9 @@ static int blocked_fill(spmv_dev *d, bool values_only)
             cleanup();
             return fail(SPMV_HIP_E_ALLOC, "pool_malloc(block inspector scratch)");
         }
-        ensure_lds<blk_rows_kernel>(d, sizeof(int) * ((size_t) S.R + 1));
+        ensure_lds<blk_rows_kernel>(d->device, sizeof(int) * ((size_t) S.R + 1));
         blk_rows_kernel<<<B, kBlkThreads, sizeof(int) * ((size_t) S.R + 1), d->stream>>>(S.row0, d->rowptr, rowin);
-        ensure_lds<blk_count_kernel>(d, sizeof(unsigned) * (size_t) K);
+        ensure_lds<blk_count_kernel>(d->device, sizeof(unsigned) * (size_t) K);
         blk_count_kernel<<<B, kBlkThreads, sizeof(unsigned) * (size_t) K, d->stream>>>(S.row0, K, S.wshift, S.ge, d->rowptr, d->colidx, groups, occupied);
         e = hipGetLastError();
         int rc = dev_alloc(d, (void **) &S.gstart, sizeof(long long) * ((size_t) B + 1), true);
@@ -589,11 +589,11 @@ static int blocked_fill(spmv_dev *d, bool values_only)
             (void) hipGetLastError();
             return fail(SPMV_HIP_E_ALLOC, "pool_malloc(block refresh scratch)");
         }
-        ensure_lds<blk_fill_kernel<T, true>>(d, lds);
+        ensure_lds<blk_fill_kernel<T, true>>(d->device, lds);
         blk_fill_kernel<T, true><<<B, kBlkThreads, lds, d->stream>>>(S.row0, K, S.wshift, S.ge, d->rowptr, d->colidx, (const T *) d->val, nullptr, S.gstart, (T *) S.val, S.meta, S.hdr, S.dir,
                                                                      S.subsort ? 1 : 0, kscr);
     } else {
-        ensure_lds<blk_fill_kernel<T, false>>(d, lds);
+        ensure_lds<blk_fill_kernel<T, false>>(d->device, lds);
         blk_fill_kernel<T, false><<<B, kBlkThreads, lds, d->stream>>>(S.row0, K, S.wshift, S.ge, d->rowptr, d->colidx, (const T *) d->val, rowin, S.gstart, (T *) S.val, S.meta, S.hdr, S.dir,
                                                                       S.subsort ? 1 : 0, nullptr);
     }

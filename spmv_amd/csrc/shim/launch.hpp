@@ -4,15 +4,51 @@
 #pragma once
 
 // ------------------------------------------------------------------------------------ executors
-// The CSR-vector family's launchers (tile / pipe / rows kernels for every lanes-per-row value: the bulk of the library's device
-// code) live in their own translation unit, spmv_vector.hip (shim/launch_vector.hpp), compiled beside this one.
-#include "vector_forms.hpp"
-template <typename T> void launch_vector_any(spmv_dev *d, const T *x, T *y);
-template <typename T> void launch_rows_any(spmv_dev *d, const T *x, T *y, const int *split);
-extern template void launch_vector_any<double>(spmv_dev *, const double *, double *);
-extern template void launch_vector_any<float>(spmv_dev *, const float *, float *);
-extern template void launch_rows_any<double>(spmv_dev *, const double *, double *, const int *);
-extern template void launch_rows_any<float>(spmv_dev *, const float *, float *, const int *);
+// Kernel forms of the CSR-vector schedule.  Which one is fastest differs between MI355X boxes by a
+// few percent, so create() times the applicable ones once on the resident matrix
+// (autotune_vector) and keeps the winner in d->vec_choice; option vector_form forces one (tests, A/B runs).
+enum { VEC_AUTO = 0, VEC_PIPE = 4, VEC_TILE_D2 = 5, VEC_TILE_D8 = 6, VEC_TILE_D4 = 10, VEC_TILE_D4_NOPRE = 11, VEC_TILE_D2_NOPRE = 12 };
+
+// The launch of the CSR-vector family (kernels/csr_vector_tile.hpp) that a built CSR-vector or Balanced schedule makes: the one place that
+// decides the kernel and its form.  launch(), the autotune, spmv_shim_release_columns and spmv_shim_info all read it.
+static VecArgs vector_args(const spmv_dev *d)
+{
+    VecArgs a;
+    const bool f64 = d->vsize == sizeof(double);
+    if (d->plan.sched == SPMV_SCHED_ROWBLOCK || d->vt_wide) {
+        // the rows kernel: Balanced's equal-nnz row blocks (split), or CSR-vector's wide form (uniform blocks).  Steps in flight: what create()
+        // measured (rows_depth, autotune_rows), what option vector_form names (5 / 12: two, 10 / 11: four), else the dtype's default
+        const int v = d->plan.vector_form;
+        a.kernel = kVecRowsKernel;
+        a.depth = d->rows_depth ? d->rows_depth : (f64 ? 4 : 2);
+        if (v == VEC_TILE_D2 || v == VEC_TILE_D2_NOPRE) a.depth = 2;
+        if (v == VEC_TILE_D4 || v == VEC_TILE_D4_NOPRE) a.depth = 4;
+        a.wide = d->vt_wide;
+        a.split = d->plan.sched == SPMV_SCHED_ROWBLOCK ? d->rb_split : nullptr;
+    } else {
+        const int v = d->plan.vector_form ? d->plan.vector_form : d->vec_choice;
+        const bool tile_default = d->vt_staged * 2 >= d->vt_tiles; // most x tiles fit LDS
+        const bool tile_forced = v == VEC_TILE_D2 || v == VEC_TILE_D4 || v == VEC_TILE_D8 || v == VEC_TILE_D4_NOPRE || v == VEC_TILE_D2_NOPRE;
+        if (d->vt_tiles > 0 && v != VEC_PIPE && (tile_default || tile_forced)) { // tile kernel (unstaged tiles gather from L1/L2)
+            a.kernel = kVecTileKernel;
+            a.depth = v == VEC_TILE_D2 || v == VEC_TILE_D2_NOPRE ? 2 : v == VEC_TILE_D8 ? 8 : v == VEC_TILE_D4 || v == VEC_TILE_D4_NOPRE ? 4 : (f64 ? 4 : 2); // else the measured default
+            a.pre = v != VEC_TILE_D4_NOPRE && v != VEC_TILE_D2_NOPRE;
+        }
+    }
+    a.lanes = d->plan.lanes_per_row; a.m = d->m; a.long_thr = d->long_thr; a.tiles = d->vt_tiles; a.maxspan = d->vt_maxspan; a.rows = d->vt_rows;
+    a.rowptr = d->rowptr; a.colidx = d->colidx; a.val = d->val; a.wins = d->vt_wins;
+    a.col = d->vt_col; a.rowslot = d->vt_rowslot; a.tmpl = d->vt_tmpl; a.col8 = d->vt_col8; a.rowtid = d->vt_rowtid;
+    a.device = d->device; a.stream = d->stream;
+    return a;
+}
+
+// One CSR-vector-family launch as vector_args resolves it (spmv_vector.hip).
+template <typename T>
+static hipError_t launch_vector(const spmv_dev *d, const T *x, T *y)
+{
+    const VecArgs a = vector_args(d);
+    return a.kernel == kVecRowsKernel ? rows_launch(a, x, y) : vector_launch(a, x, y);
+}
 
 // Time the applicable CSR-vector forms on the resident matrix (x = 1) and keep the fastest.
 template <typename T>
@@ -38,12 +74,12 @@ static int autotune_vector(spmv_dev *d)
     const int ncand = (long long) d->vt_staged * 100 >= (long long) d->vt_tiles * 99 ? kCand - 1 : kCand;
     float tmin[kCand];
     for (int k = 0; k < kCand; ++k) tmin[k] = 1e30f;
-    for (int k = 0; k < ncand; ++k) { d->vec_choice = cand[k]; launch_vector_any<T>(d, x, y); } // warm every form once
+    for (int k = 0; k < ncand; ++k) { d->vec_choice = cand[k]; (void) launch_vector<T>(d, x, y); } // warm every form once
     for (int round = 0; round < 3; ++round) // interleaved rounds (one process, same clocks): min per form
         for (int k = 0; k < ncand; ++k) {
             d->vec_choice = cand[k];
             (void) hipEventRecord(e0, d->stream);
-            launch_vector_any<T>(d, x, y); // one launch per sample (round 3: two): the forms differ by whole percents where they differ, events resolve a microsecond
+            (void) launch_vector<T>(d, x, y); // one launch per sample (round 3: two): the forms differ by whole percents where they differ, events resolve a microsecond
             (void) hipEventRecord(e1, d->stream);
             (void) hipEventSynchronize(e1);
             float ms = 0;
@@ -88,12 +124,12 @@ static void launch_blocked(spmv_dev *d, const T *x, T *y)
     const size_t lds = blocked_lds_bytes(S);
 #define SPMV_BLK_LAUNCH(UN, DBG)                                                                                                  \
     do {                                                                                                                          \
-        ensure_lds<blk_kernel<T, UN, DBG>>(d, lds);                                                                               \
+        ensure_lds<blk_kernel<T, UN, DBG>>(d->device, lds);                                                                       \
         blk_kernel<T, UN, DBG><<<S.B, kWave, lds, d->stream>>>(S.row0, S.R, S.dir, (const T *) S.val, S.meta, S.hdr, S.order, x, y, d->accumulate ? 1 : 0); \
     } while (0)
 #define SPMV_BLK_WLAUNCH(UN, W, ORD)                                                                                              \
     do {                                                                                                                          \
-        ensure_lds<blk_wide_kernel<T, UN, W, ORD>>(d, lds);                                                                       \
+        ensure_lds<blk_wide_kernel<T, UN, W, ORD>>(d->device, lds);                                                               \
         blk_wide_kernel<T, UN, W, ORD><<<S.B, kWave * W, lds, d->stream>>>(S.row0, S.R, S.dir, (const T *) S.val, S.meta, S.hdr, S.order, x, y, d->accumulate ? 1 : 0); \
     } while (0)
 #define SPMV_BLK_WFORM(UN, W) do { if (S.ordered) SPMV_BLK_WLAUNCH(UN, W, true); else SPMV_BLK_WLAUNCH(UN, W, false); } while (0)
@@ -167,7 +203,7 @@ static int autotune_blocked(spmv_dev *d)
 // The rows kernel (Balanced's row blocks with `split`, CSR-vector's wide form without): two or four steps in flight?  Timed like the tile forms, on matrices of
 // >= 2^24 entries whose blocks mostly stage (27-point stencil under Method_Balanced: 0.55 ms four deep, the fp64 default, 0.47 two deep).
 template <typename T>
-static int autotune_rows(spmv_dev *d, const int *split)
+static int autotune_rows(spmv_dev *d)
 {
     d->rows_depth = 0;
     if (d->nnz < (1ll << 24) || d->plan.forced || d->vt_tiles <= 0 || d->vt_staged * 2 < d->vt_tiles) return SPMV_HIP_OK;
@@ -183,12 +219,12 @@ static int autotune_rows(spmv_dev *d, const int *split)
     (void) hipEventCreate(&e1);
     const int depth[2] = {4, 2};
     float tmin[2] = {1e30f, 1e30f};
-    for (int k = 0; k < 2; ++k) { d->rows_depth = depth[k]; launch_rows_any<T>(d, x, y, split); }
+    for (int k = 0; k < 2; ++k) { d->rows_depth = depth[k]; (void) launch_vector<T>(d, x, y); }
     for (int round = 0; round < 2; ++round)
         for (int k = 0; k < 2; ++k) {
             d->rows_depth = depth[k];
             (void) hipEventRecord(e0, d->stream);
-            launch_rows_any<T>(d, x, y, split);
+            (void) launch_vector<T>(d, x, y);
             (void) hipEventRecord(e1, d->stream);
             (void) hipEventSynchronize(e1);
             float ms = 0;
@@ -230,12 +266,12 @@ static void launch_csr5_form(spmv_dev *d, const Csr5Plan &P, const T *x, T *y)
             constexpr size_t full = (size_t) (kBlock / kWave) * NatLds<T, SIGMA, false>::kBytes;
             const bool half = lds + rmb + full > 76 * 1024; // two workgroups no longer fit a CU's 160 KiB
             if (half) {
-                ensure_lds<nat_group_kernel<T, SIGMA, MAPPED, true>>(d, lds + rmb, (size_t) (kBlock / kWave) * NatLds<T, SIGMA, true>::kBytes);
+                ensure_lds<nat_group_kernel<T, SIGMA, MAPPED, true>>(d->device, lds + rmb, (size_t) (kBlock / kWave) * NatLds<T, SIGMA, true>::kBytes);
                 nat_group_kernel<T, SIGMA, MAPPED, true><<<P.groups, kBlock, lds + rmb, d->stream>>>(P.group_tiles, P.tiles, (int) P.nnz, P.tile_ptr, P.desc, P.col, P.col16,
                                                                                                     (const T *) P.val, P.row_map, P.wins, x, y, (T *) P.carry, P.n_empty, P.empty_list,
                                                                                                     (int) lds, rm_stride);
             } else {
-                ensure_lds<nat_group_kernel<T, SIGMA, MAPPED, false>>(d, lds + rmb, full);
+                ensure_lds<nat_group_kernel<T, SIGMA, MAPPED, false>>(d->device, lds + rmb, full);
                 nat_group_kernel<T, SIGMA, MAPPED, false><<<P.groups, kBlock, lds + rmb, d->stream>>>(P.group_tiles, P.tiles, (int) P.nnz, P.tile_ptr, P.desc, P.col, P.col16,
                                                                                                      (const T *) P.val, P.row_map, P.wins, x, y, (T *) P.carry, P.n_empty, P.empty_list,
                                                                                                      (int) lds, rm_stride);
@@ -243,12 +279,12 @@ static void launch_csr5_form(spmv_dev *d, const Csr5Plan &P, const T *x, T *y)
             return;
         }
         if (csr5_two_deep(d, P)) {
-            ensure_lds<csr5_group_pipe_kernel<T, SIGMA, MAPPED>>(d, lds + rmb);
+            ensure_lds<csr5_group_pipe_kernel<T, SIGMA, MAPPED>>(d->device, lds + rmb);
             csr5_group_pipe_kernel<T, SIGMA, MAPPED><<<P.groups, kBlock, lds + rmb, d->stream>>>(P.group_tiles, P.tiles, P.tile_ptr, P.desc, P.col16, (const T *) P.val, P.row_map, P.wins, P.lane_run,
                                                                                                 x, y, (T *) P.carry, P.n_empty, P.empty_list, (int) lds, rm_stride);
             return;
         }
-        ensure_lds<csr5_group_kernel<T, SIGMA, MAPPED>>(d, lds + rmb);
+        ensure_lds<csr5_group_kernel<T, SIGMA, MAPPED>>(d->device, lds + rmb);
         csr5_group_kernel<T, SIGMA, MAPPED><<<P.groups, kBlock, lds + rmb, d->stream>>>(P.group_tiles, P.tiles, P.tile_ptr, P.desc, P.col, P.col16, (const T *) P.val, P.row_map, P.wins, P.lane_run,
                                                                                        x, y, (T *) P.carry, P.n_empty, P.empty_list, (int) lds, rm_stride);
         return;
@@ -316,8 +352,7 @@ static int launch(spmv_dev *d, const T *x, T *y)
         break;
     case SPMV_SCHED_CSR_VECTOR:
         if (d->blk_on) { launch_blocked<T>(d, x, y); break; } // no x window could be staged (option "cache_block")
-        if (d->vt_wide) launch_rows_any<T>(d, x, y, nullptr); // wide x windows: uniform 1024-row blocks, slot-index stream
-        else launch_vector_any<T>(d, x, y);
+        HIP_TRY(launch_vector<T>(d, x, y)); // the tile or pipe kernel; wide x windows: the rows kernel over uniform 1024-row blocks, slot-index stream
         launch_long_rows<T>(d, x, y);
         break;
     case SPMV_SCHED_NNZ_SPLIT: {
@@ -328,7 +363,7 @@ static int launch(spmv_dev *d, const T *x, T *y)
     }
     case SPMV_SCHED_ROWBLOCK:
         if (d->blk_on) { launch_blocked<T>(d, x, y); break; }
-        launch_rows_any<T>(d, x, y, d->rb_split);
+        HIP_TRY(launch_vector<T>(d, x, y)); // the rows kernel over the equal-nnz row blocks
         launch_long_rows<T>(d, x, y);
         break;
     case SPMV_SCHED_SELL:
@@ -339,7 +374,7 @@ static int launch(spmv_dev *d, const T *x, T *y)
             const int cpw = d->sell_group * (d->plan.sell_sigma / kSellC);
             const size_t xbytes = ((((size_t) d->sell_maxspan + 1) * sizeof(T)) + 1023) & ~(size_t) 1023; // x windows + the zero slot
             const size_t lds = xbytes + sizeof(T) * (size_t) cpw * kSellC;                                  // + the group's row sums
-            ensure_lds<sell_window_kernel<T>>(d, lds);
+            ensure_lds<sell_window_kernel<T>>(d->device, lds);
             sell_window_kernel<T><<<d->sell_nwin, kSellWinThreads, lds, d->stream>>>(cpw, (long long) d->nchunks, d->m, d->chunk_ptr, d->scol, d->scol16, (const T *) d->sval,
                                                                                      d->perm, d->sell_wins, d->sell_run, d->sell_tmpl, d->scol8, x, y, (int) xbytes);
         }

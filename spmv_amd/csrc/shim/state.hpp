@@ -2,7 +2,6 @@
 // error channel, the device-side state of a handle (spmv_dev), allocation bookkeeping and the small
 // utility kernels (row statistics, ColIdx validation, fills).
 #pragma once
-#include <atomic>
 
 // ------------------------------------------------------------------------------------ errors
 static thread_local char t_err[400] = "";
@@ -16,9 +15,7 @@ static int fail(int code, const char *fmt, ...)
     return code;
 }
 
-#ifndef SPMV_TU_SECONDARY
 extern "C" const char *spmv_shim_error_text(void) { return t_err; }
-#endif
 
 #define HIP_TRY(expr)                                                                              \
     do {                                                                                           \
@@ -118,13 +115,11 @@ static hipError_t pool_free(void *p)
     return hipFree(p);
 }
 
-#ifndef SPMV_TU_SECONDARY
 extern "C" void spmv_shim_trim_pool(void)
 {
     std::lock_guard<std::mutex> g(g_pool_lock);
     pool_trim_locked();
 }
-#endif
 
 // Makes `device` current for the life of the guard and restores the caller's device afterwards.
 struct DeviceGuard {
@@ -366,14 +361,12 @@ static bool is_device_ptr(const void *p)
     return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
 }
 
-#ifndef SPMV_TU_SECONDARY
 extern "C" int spmv_shim_device_count(void)
 {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) { (void) hipGetLastError(); return 0; }
     return n;
 }
-#endif
 
 // ------------------------------------------------------------------------------------ stats
 static __global__ __launch_bounds__(kBlock) void stats_kernel(int m, const int *__restrict__ rowptr, DevStats *s)
@@ -457,28 +450,4 @@ __global__ __launch_bounds__(kBlock) void fill_zero_kernel(long long n, T *y)
 {
     const long long stride = (long long) gridDim.x * kBlock;
     for (long long i = (long long) blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) y[i] = T(0);
-}
-
-// Dynamic LDS above the 64 KiB default needs hipFuncAttributeMaxDynamicSharedMemorySize raised once per kernel
-// instantiation (and per device): remembered here, so that launches do not pay the call every time.
-static std::mutex g_lds_attr_lock;
-
-template <auto Kernel>
-static void ensure_lds(const spmv_dev *d, size_t bytes, size_t static_bytes = 0)
-{
-    static std::atomic<size_t> granted[64]; // per device ordinal; zero-initialised = the 64 KiB default
-    const int dev = d->device >= 0 && d->device < 64 ? d->device : 0;
-    if (bytes + static_bytes <= 64 * 1024 || bytes <= granted[dev].load(std::memory_order_acquire)) return;
-    std::lock_guard<std::mutex> g(g_lds_attr_lock); // the attribute only ever grows: a second thread must not set a smaller value after a larger one
-    if (bytes <= granted[dev].load(std::memory_order_relaxed)) return;
-    if (hipFuncSetAttribute((const void *) Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) bytes) == hipSuccess) granted[dev].store(bytes, std::memory_order_release);
-    else (void) hipGetLastError();
-}
-
-static int grid_for(long long work_items, int per_block, int cap)
-{
-    long long g = (work_items + per_block - 1) / per_block;
-    if (g < 1) g = 1;
-    if (g > cap) g = cap;
-    return (int) g;
 }

@@ -51,7 +51,7 @@ static opt_t g_opts[SPMV_N_OPTS] = {
     /* executor-form selectors: what create() would otherwise choose by rule or by timing.  Tests force every form through them; setting any of
      * them switches the create-time timing of alternatives off for that handle. */
     [SPMV_OPT_VECTOR_FORM] = {"vector_form", 0, 0, 12, 0, 0},         /* CSR-vector kernel form: 0 = timed at create; 4 pipe, 5 / 12 tile two steps deep (with / without the
-                                                                       * pre-issued step), 10 / 11 tile four deep, 6 tile eight deep (shim/vector_forms.hpp) */
+                                                                       * pre-issued step), 10 / 11 tile four deep, 6 tile eight deep (shim/launch.hpp) */
     [SPMV_OPT_X_WINDOWS] = {"x_windows", 1, 0, 1, 0, 0},              /* 1: tile schedules stage the x windows of their tile groups in LDS; 0: never (global gathers; the blocked
                                                                        * executor does not take over either) */
     [SPMV_OPT_XCD_ORDER] = {"xcd_order", 1, 0, 1, 0, 0},              /* tile kernels that gather x through L2: 1 = XCD-aware block order, 0 = dispatch order */

@@ -33,13 +33,13 @@
 #include "kernels/split.hpp"
 #include "kernels/rcm.hpp"
 #include "kernels/csr_vector_tile.hpp"
+#include "kernels/xwindows_inspect.hpp"
 #include "kernels/spmm.hpp"
 #include "kernels/transpose.hpp"
 
 using namespace spmv;
 
 #include "shim/state.hpp"
-#include "shim/vector_forms.hpp"
 
 // row statistics of the resident RowPtr (also validates it): d->nnz, d->stats
 static int matrix_row_stats(spmv_dev *d)
@@ -180,33 +180,6 @@ extern "C" void spmv_shim_matrix_destroy(spmv_dev *d)
 
 #include "shim/inspect.hpp"
 
-// The resident int32 ColIdx copy (4 B per non-zero: 1.28 GB on config 2) is read by the inspectors -- and afterwards only by executors that
-// gather through global columns.  Once create() has settled on a schedule whose multiply never touches it (every tile / group staged: the 16-bit
-// slot streams, RUN / BYTE / TEMPLATE data, SELL slabs and CSR5 tiles are copies of their own), it goes back to the pool.  Kept: CSR-scalar, the pipe
-// form, any schedule with unstaged groups, the blocked executor (its values refresh re-derives the cells from the columns), split handles.
-extern "C" int spmv_shim_release_columns(spmv_dev *d)
-{
-    if (!d || !d->built || !d->colidx || d->nnz == 0) return SPMV_HIP_OK;
-    if (d->sp_near || d->sp_far || d->accumulate || d->blk_on) return SPMV_HIP_OK;
-    bool unused = false;
-    switch (d->plan.sched) {
-    case SPMV_SCHED_CSR_VECTOR:
-        unused = d->vt_tiles > 0 && d->vt_staged == d->vt_tiles && d->plan.vector_form != VEC_PIPE && d->vec_choice != VEC_PIPE;
-        break;
-    case SPMV_SCHED_ROWBLOCK: unused = d->vt_tiles > 0 && d->vt_staged == d->vt_tiles; break;
-    case SPMV_SCHED_NNZ_SPLIT: unused = d->ns.groups > 0 && d->ns.staged == d->ns.groups; break; // natural layout: unstaged groups read the matrix's own columns
-    case SPMV_SCHED_SELL:
-    case SPMV_SCHED_CSR5: unused = true; break;                                                    // slabs / transposed tiles are copies
-    default: break;
-    }
-    if (!unused) return SPMV_HIP_OK;
-    quiesce(d);
-    (void) pool_free(d->colidx);
-    d->colidx = nullptr;
-    d->device_bytes -= (long long) (sizeof(int) * ((size_t) d->nnz + kStreamPad));
-    return SPMV_HIP_OK;
-}
-
 extern "C" int spmv_shim_build(spmv_dev *d, const spmv_plan *plan)
 {
     if (!d || !plan) return fail(SPMV_HIP_E_ARG, "build: NULL");
@@ -249,7 +222,7 @@ extern "C" int spmv_shim_build(spmv_dev *d, const spmv_plan *plan)
             staged = d->vt_staged;
             groups = d->vt_tiles;
             if (!rc && plan->autotune && blocked_mode(d, staged, groups) != 1) {
-                if (d->vt_wide) rc = f64 ? autotune_rows<double>(d, nullptr) : autotune_rows<float>(d, nullptr); // wide x windows: the rows kernel over uniform blocks
+                if (d->vt_wide) rc = f64 ? autotune_rows<double>(d) : autotune_rows<float>(d); // wide x windows: the rows kernel over uniform blocks
                 else rc = f64 ? autotune_vector<double>(d) : autotune_vector<float>(d);
             }
             break;
@@ -268,7 +241,7 @@ extern "C" int spmv_shim_build(spmv_dev *d, const spmv_plan *plan)
             if (!rc) rc = f64 ? build_rowblock_tiles<double>(d) : build_rowblock_tiles<float>(d);
             staged = d->vt_staged;
             groups = d->vt_tiles;
-            if (!rc && plan->autotune && blocked_mode(d, staged, groups) != 1) rc = f64 ? autotune_rows<double>(d, d->rb_split) : autotune_rows<float>(d, d->rb_split);
+            if (!rc && plan->autotune && blocked_mode(d, staged, groups) != 1) rc = f64 ? autotune_rows<double>(d) : autotune_rows<float>(d);
             break;
         case SPMV_SCHED_SELL:
             rc = f64 ? build_sell<double>(d) : build_sell<float>(d);
@@ -540,6 +513,31 @@ extern "C" int spmv_shim_is_device_ptr(const void *p) { return is_device_ptr(p) 
 #include "shim/spmm.hpp"
 #include "shim/transpose.hpp"
 
+// The resident int32 ColIdx copy (4 B per non-zero: 1.28 GB on config 2) is read by the inspectors -- and afterwards only by executors that
+// gather through global columns.  Once create() has settled on a schedule whose multiply never touches it (every tile / group staged: the 16-bit
+// slot streams, RUN / BYTE / TEMPLATE data, SELL slabs and CSR5 tiles are copies of their own), it goes back to the pool.  Kept: CSR-scalar, the pipe
+// form, any schedule with unstaged groups, the blocked executor (its values refresh re-derives the cells from the columns), split handles.
+extern "C" int spmv_shim_release_columns(spmv_dev *d)
+{
+    if (!d || !d->built || !d->colidx || d->nnz == 0) return SPMV_HIP_OK;
+    if (d->sp_near || d->sp_far || d->accumulate || d->blk_on) return SPMV_HIP_OK;
+    bool unused = false;
+    switch (d->plan.sched) {
+    case SPMV_SCHED_CSR_VECTOR:
+    case SPMV_SCHED_ROWBLOCK: unused = d->vt_tiles > 0 && d->vt_staged == d->vt_tiles && vector_args(d).kernel != kVecPipeKernel; break;
+    case SPMV_SCHED_NNZ_SPLIT: unused = d->ns.groups > 0 && d->ns.staged == d->ns.groups; break; // natural layout: unstaged groups read the matrix's own columns
+    case SPMV_SCHED_SELL:
+    case SPMV_SCHED_CSR5: unused = true; break;                                                    // slabs / transposed tiles are copies
+    default: break;
+    }
+    if (!unused) return SPMV_HIP_OK;
+    quiesce(d);
+    (void) pool_free(d->colidx);
+    d->colidx = nullptr;
+    d->device_bytes -= (long long) (sizeof(int) * ((size_t) d->nnz + kStreamPad));
+    return SPMV_HIP_OK;
+}
+
 extern "C" int spmv_shim_run(spmv_dev *d, const void *x, void *y)
 {
     if (!d || !d->built) return fail(SPMV_HIP_E_NOSTATE, "run: schedule not built");
@@ -654,6 +652,7 @@ extern "C" double spmv_shim_time_self(spmv_dev *d, int iters)
 static const char *kSchedNames[] = {"csr-scalar", "csr-vector", "row-block", "nnz-split", "sell-c-sigma", "csr5"};
 static const char *kKernelNames[] = {"csr_scalar_kernel", "csr_vector_pipe_kernel", "csr_vector_rows_kernel",
                                      "nat_kernel", "sell_kernel", "csr5_kernel"};
+static const char *kVecKernelNames[] = {"csr_vector_pipe_kernel", "csr_vector_tile_kernel", "csr_vector_rows_kernel"}; // VecArgs::kernel
 
 // kernels of one CSR5 / nnz-split plan's multiply, appended to `buf` ('+'-separated, in launch order)
 static void append_name(char *buf, size_t cap, const char *name)
@@ -721,10 +720,8 @@ extern "C" int spmv_shim_info(const spmv_dev *d, spmv_hip_info *o)
     for (int k = 0; k < 3; ++k) o->tune_ms[k] = d->blk_on ? d->blk.tune_ms[k] : d->tune_ms[k];
     o->schedule_name = kSchedNames[d->plan.sched];
     o->kernel_name = kKernelNames[d->plan.sched];
-    if (d->plan.sched == SPMV_SCHED_CSR_VECTOR && d->vt_tiles > 0 && d->vec_choice != VEC_PIPE &&
-        (d->vt_staged * 2 >= d->vt_tiles || (d->vec_choice != VEC_AUTO && d->vec_choice != VEC_PIPE)))
-        o->kernel_name = "csr_vector_tile_kernel";
-    if (d->plan.sched == SPMV_SCHED_CSR_VECTOR && d->vt_wide) o->kernel_name = "csr_vector_rows_kernel";
+    const int vec_kernel = vector_args(d).kernel; // CSR-vector, Balanced: the kernel launch() makes
+    if (d->plan.sched == SPMV_SCHED_CSR_VECTOR) o->kernel_name = kVecKernelNames[vec_kernel];
     o->cache_blocked = d->blk_on ? 1 : 0;
     o->stream_bytes = d->stream_bytes;
     o->x_bytes = d->x_bytes;
@@ -734,7 +731,7 @@ extern "C" int spmv_shim_info(const spmv_dev *d, spmv_hip_info *o)
     o->split_ms[1] = d->split_ms[1];
     o->far_nnz = d->sp_far ? d->sp_far->nnz : 0;
     {
-        const bool tiles_run = !d->blk_on && ((d->plan.sched == SPMV_SCHED_CSR_VECTOR && d->vt_tiles > 0 && (d->vt_wide || d->vt_staged * 2 >= d->vt_tiles) && d->vec_choice != VEC_PIPE) || d->plan.sched == SPMV_SCHED_ROWBLOCK);
+        const bool tiles_run = !d->blk_on && (d->plan.sched == SPMV_SCHED_CSR_VECTOR || d->plan.sched == SPMV_SCHED_ROWBLOCK) && vec_kernel != kVecPipeKernel;
         o->run_nnz = tiles_run ? d->vt_run_nnz : 0;
         o->byte_nnz = tiles_run ? d->vt_byte_nnz : 0;
         o->tmpl_nnz = tiles_run ? d->vt_tmpl_nnz : 0;

@@ -7,17 +7,9 @@
 
 namespace spmv {
 
-static int tr_grid(long long items, int per_block, int cap)
-{
-    long long g = (items + per_block - 1) / per_block;
-    if (g < 1) g = 1;
-    if (g > cap) g = cap;
-    return (int) g;
-}
-
 hipError_t tr_rows_launch(int m, const int *rowptr, int *row_of, int cus, hipStream_t stream)
 {
-    if (m > 0) tr_rows_kernel<<<tr_grid(m, kBlock / kWave, cus * 32), kBlock, 0, stream>>>(m, rowptr, row_of);
+    if (m > 0) tr_rows_kernel<<<grid_for(m, kBlock / kWave, cus * 32), kBlock, 0, stream>>>(m, rowptr, row_of);
     return hipGetLastError();
 }
 
@@ -35,21 +27,21 @@ hipError_t tr_scatter_launch(long long nnz, int tiles, int shift, const int *key
 
 hipError_t tr_rowptr_launch(int n, long long nnz, const int *sorted, int *rowptr_t, int cus, hipStream_t stream)
 {
-    tr_rowptr_kernel<<<tr_grid((long long) n + 1, kBlock, cus * 8), kBlock, 0, stream>>>(n, nnz, sorted, rowptr_t);
+    tr_rowptr_kernel<<<grid_for((long long) n + 1, kBlock, cus * 8), kBlock, 0, stream>>>(n, nnz, sorted, rowptr_t);
     return hipGetLastError();
 }
 
 hipError_t tr_columns_launch(long long nnz, const int *perm, const int *row_of, int *colidx_t, int cus, hipStream_t stream)
 {
-    if (nnz > 0) tr_columns_kernel<<<tr_grid(nnz, kBlock, cus * 16), kBlock, 0, stream>>>(nnz, perm, row_of, colidx_t);
+    if (nnz > 0) tr_columns_kernel<<<grid_for(nnz, kBlock, cus * 16), kBlock, 0, stream>>>(nnz, perm, row_of, colidx_t);
     return hipGetLastError();
 }
 
 hipError_t tr_gather_launch(long long nnz, const int *perm, const void *val, void *val_t, bool f64, int cus, hipStream_t stream)
 {
     if (nnz > 0) {
-        if (f64) tr_gather_kernel<double><<<tr_grid(nnz, kBlock, cus * 16), kBlock, 0, stream>>>(nnz, perm, (const double *) val, (double *) val_t);
-        else tr_gather_kernel<float><<<tr_grid(nnz, kBlock, cus * 16), kBlock, 0, stream>>>(nnz, perm, (const float *) val, (float *) val_t);
+        if (f64) tr_gather_kernel<double><<<grid_for(nnz, kBlock, cus * 16), kBlock, 0, stream>>>(nnz, perm, (const double *) val, (double *) val_t);
+        else tr_gather_kernel<float><<<grid_for(nnz, kBlock, cus * 16), kBlock, 0, stream>>>(nnz, perm, (const float *) val, (float *) val_t);
     }
     return hipGetLastError();
 }

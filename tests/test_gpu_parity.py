@@ -265,6 +265,34 @@ def test_tuning_options_do_not_change_results(key, values, method, name):
         api.set_option(key, default)
 
 
+def test_forced_vector_form_reports_the_kernel_that_runs():
+    """Option vector_form on a matrix whose x tiles stage: spmv_hip_info names the kernel that launch() makes -- the pipe kernel for form 4 (and no
+    RUN / BYTE / TEMPLATE entries, which only the tile kernels read), the tile kernel for every tile form."""
+    import torch
+    dev = torch.device("cuda:0")
+    csr, x, y_ref = load_golden("banded_f64_eighths")
+    rp, ci, va = (torch.from_numpy(a).to(dev) for a in (csr.rowptr, csr.colidx, csr.val))
+    xd = torch.from_numpy(x).to(dev)
+    for form in (4, 5, 6, 10, 11, 12):
+        api.set_thread_option("vector_form", form)
+        try:
+            h = api.Handle(csr.m, csr.n, rp, ci, va, M.Method_Parallel)
+        finally:
+            api.clear_thread_options()
+        with h:
+            info = h.info()
+            y = torch.full((csr.m,), float("nan"), dtype=va.dtype, device=dev)
+            h.spmv(xd, y)
+            torch.cuda.synchronize()
+        assert np.array_equal(y.cpu().numpy(), y_ref), form
+        assert info["x_groups"] > 0 and 2 * info["x_groups_staged"] >= info["x_groups"], info
+        if form == 4:
+            assert info["kernel_name"] == "csr_vector_pipe_kernel", info
+            assert info["run_nnz"] == info["byte_nnz"] == info["tmpl_nnz"] == 0, info
+        else:
+            assert info["kernel_name"] == "csr_vector_tile_kernel", (form, info)
+
+
 def test_illegal_option_values_are_reported_at_create():
     csr, x, _ = load_golden("tiny_f64_eighths")
     api.set_option("csr5_sigma", 5)
