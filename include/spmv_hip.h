@@ -225,6 +225,11 @@ typedef struct spmv_hip_info {
     char launch_kernels[160];   /* every kernel ONE spmv() launches, in order, '+'-separated (e.g. "sell_window_kernel+csr5_group_pipe_kernel+csr5_fixup_kernel") */
     int reproducible;           /* 1: the executor adds every row's products in an order fixed by the matrix -- identical bits run to run and handle to
                                  * handle; 0 only for the wide blocked form under option "deterministic" = 0 */
+    int x_span_max;             /* elements of the largest x window set the dominant kernel stages for one tile / group (the single window's span, or the
+                                 * sum of the windows of a tile covered by several); 0 when it stages nothing (global-column kernels, cache_blocked) */
+    int lds_bytes;              /* dynamic LDS, in bytes, the dominant kernel's launch requests: (x_span_max + 1 zero slot) elements in whole KiB, plus SELL's
+                                 * row sums of one window group, plus the CSR5 / nnz-split waves' row maps (matrices with empty rows); cache_blocked: one row
+                                 * block's accumulators.  The kernels' static LDS is not included */
 } spmv_hip_info;
 int spmv_hip_get_info(spmv_Handle_t handle, spmv_hip_info *out);
 /* the transposed schedule's spmv_hip_info (m, n swapped; schedule, kernels, device_bytes of A^T alone, reproducible); SPMV_HIP_E_NOSTATE until built */

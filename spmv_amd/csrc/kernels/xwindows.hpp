@@ -34,6 +34,10 @@ struct TileWindows {
     int runs;            // CSR-vector tiles only: 1 = every row's columns are ONE run of consecutive columns (csr_vector_tile.hpp: no column stream)
 };
 
+// host: dynamic LDS of a staged executor's x windows -- the largest staged window of the schedule (maxspan elements of elem bytes) + the
+// zero slot behind it, in whole KiB.  The one copy of the expression: every launcher and spmv_hip_info.lds_bytes go through it.
+inline size_t xwin_lds_bytes(int maxspan, size_t elem) { return ((((size_t) maxspan + 1) * elem) + 1023) & ~(size_t) 1023; }
+
 // Stage the tile's windows: xs[base_w + i] = x[start_w + i].  NT = threads of the workgroup.  16-byte loads, four in flight per
 // thread, from the first 16-byte boundary of the window on (x is the caller's pointer: any element alignment): a wide window --
 // 10 000 columns of a CSR5 / SELL group whose rows scatter +-4096 around the diagonal -- is three round trips to L2 instead of eleven,

@@ -251,15 +251,40 @@ static bool csr5_two_deep(const spmv_dev *d, const Csr5Plan &P)
     return d->vsize == sizeof(float) || d->plan.csr5_two_deep == 2;
 }
 
+// Dynamic LDS of one CSR5 / nnz-split launch: the x windows (when groups are staged) and, behind them, the waves' row maps.
+// MAPPED (matrices with empty rows, long-row sub-matrices: P.row_map): every wave stages its tile's row map in LDS, behind the x
+// windows in the dynamic segment.  A tile of long rows holds few row starts: kWave ints per wave then (csr5.hpp)
+struct Csr5Lds {
+    int rm_stride = 0;
+    size_t x = 0, rm = 0;
+};
+static Csr5Lds csr5_lds(const Csr5Plan &P, size_t elem)
+{
+    Csr5Lds L;
+    const int sigma = P.sigma == 4 || P.sigma == 8 ? P.sigma : 16;
+    L.rm_stride = P.row_map ? (P.max_tile_rows < kWave ? kWave : (sigma + 1) * kWave) : 0;
+    L.rm = (size_t) (kBlock / kWave) * L.rm_stride * sizeof(int);
+    L.x = P.staged > 0 ? xwin_lds_bytes(P.maxspan, elem) : 0; // + the zero slot
+    return L;
+}
+
+// Dynamic LDS of the staged SELL launch: the group's x windows + the zero slot (*xbytes_out), then the group's row sums
+static size_t sell_lds_bytes(const spmv_dev *d, size_t *xbytes_out)
+{
+    const int cpw = d->sell_group * (d->plan.sell_sigma / kSellC);
+    const size_t xbytes = xwin_lds_bytes(d->sell_maxspan, d->vsize);
+    if (xbytes_out) *xbytes_out = xbytes;
+    return xbytes + d->vsize * (size_t) cpw * kSellC;
+}
+
 template <typename T, int SIGMA, bool MAPPED>
 static void launch_csr5_form(spmv_dev *d, const Csr5Plan &P, const T *x, T *y)
 {
-    // MAPPED (matrices with empty rows, long-row sub-matrices): every wave stages its tile's row map in LDS, behind the x
-    // windows in the dynamic segment.  A tile of long rows holds few row starts: kWave ints per wave then (csr5.hpp)
-    const int rm_stride = MAPPED ? (P.max_tile_rows < kWave ? kWave : (SIGMA + 1) * kWave) : 0;
-    const size_t rmb = (size_t) (kBlock / kWave) * rm_stride * sizeof(int);
+    const Csr5Lds L = csr5_lds(P, sizeof(T));
+    const int rm_stride = L.rm_stride;
+    const size_t rmb = L.rm;
     if (P.staged > 0) { // the inspector staged (at least half of) the groups: their column stream is the 16-bit slot array
-        const size_t lds = ((((size_t) P.maxspan + 1) * sizeof(T)) + 1023) & ~(size_t) 1023; // + the zero slot
+        const size_t lds = L.x;
         if (P.natural) {
             // the waves' tile buffers are static LDS next to the x windows: if the full-size buffers would leave
             // one workgroup per CU, hand the tiles over in two halves (half the buffers)
@@ -372,8 +397,8 @@ static int launch(spmv_dev *d, const T *x, T *y)
         // sized by the largest staged span actually present (rounded to 16 KiB) to keep occupancy
         if (d->sell_staged > 0) {
             const int cpw = d->sell_group * (d->plan.sell_sigma / kSellC);
-            const size_t xbytes = ((((size_t) d->sell_maxspan + 1) * sizeof(T)) + 1023) & ~(size_t) 1023; // x windows + the zero slot
-            const size_t lds = xbytes + sizeof(T) * (size_t) cpw * kSellC;                                  // + the group's row sums
+            size_t xbytes = 0;
+            const size_t lds = sell_lds_bytes(d, &xbytes);
             ensure_lds<sell_window_kernel<T>>(d->device, lds);
             sell_window_kernel<T><<<d->sell_nwin, kSellWinThreads, lds, d->stream>>>(cpw, (long long) d->nchunks, d->m, d->chunk_ptr, d->scol, d->scol16, (const T *) d->sval,
                                                                                      d->perm, d->sell_wins, d->sell_run, d->sell_tmpl, d->scol8, x, y, (int) xbytes);

@@ -754,6 +754,26 @@ extern "C" int spmv_shim_info(const spmv_dev *d, spmv_hip_info *o)
         o->kernel_name = d->ns.staged > 0 ? "nat_group_kernel" : "nat_kernel";
     if (d->plan.sched == SPMV_SCHED_CSR5 && d->c5.staged > 0) o->kernel_name = csr5_two_deep(d, d->c5) ? "csr5_group_pipe_kernel" : "csr5_group_kernel";
     if (d->plan.sched == SPMV_SCHED_SELL && d->sell_staged > 0) o->kernel_name = "sell_window_kernel";
+    // the staged x windows of the dominant kernel and the dynamic LDS its launch requests: the launchers' own expressions
+    if (d->blk_on) o->lds_bytes = d->nnz > 0 ? (int) blocked_lds_bytes(d->blk) : 0;
+    else switch (d->nnz > 0 ? d->plan.sched : -1) {
+    case SPMV_SCHED_CSR_VECTOR:
+    case SPMV_SCHED_ROWBLOCK:
+        if (vec_kernel != kVecPipeKernel) { o->x_span_max = d->vt_maxspan; o->lds_bytes = (int) xwin_lds_bytes(d->vt_maxspan, d->vsize); }
+        break;
+    case SPMV_SCHED_SELL:
+        if (d->sell_staged > 0) { o->x_span_max = d->sell_maxspan; o->lds_bytes = (int) sell_lds_bytes(d, nullptr); }
+        break;
+    case SPMV_SCHED_NNZ_SPLIT:
+    case SPMV_SCHED_CSR5: {
+        const Csr5Plan &P = d->plan.sched == SPMV_SCHED_CSR5 ? d->c5 : d->ns;
+        const Csr5Lds L = csr5_lds(P, d->vsize);
+        o->x_span_max = P.staged > 0 ? P.maxspan : 0;
+        o->lds_bytes = P.nnz > 0 ? (int) (L.x + L.rm) : 0;
+        break;
+    }
+    default: break;
+    }
     { // every kernel of one multiply, in launch order
         char *b = o->launch_kernels;
         const size_t cap = sizeof o->launch_kernels;

@@ -18,7 +18,7 @@
 namespace spmv {
 
 // the staged x windows of the largest tile + the zero slot, in whole KiB
-template <typename T> static size_t vec_lds_bytes(const VecArgs &a) { return ((((size_t) a.maxspan + 1) * sizeof(T)) + 1023) & ~(size_t) 1023; }
+template <typename T> static size_t vec_lds_bytes(const VecArgs &a) { return xwin_lds_bytes(a.maxspan, sizeof(T)); }
 
 template <typename F>
 static void with_lanes(int lanes, F f)

@@ -22,7 +22,7 @@ __all__ = [
     "CSR", "fill_values", "fill_x", "banded", "uniform_k", "powerlaw", "skewed_rows",
     "from_row_lengths", "with_empty_rows", "dense_rows", "banded_device", "uniform_k_device", "rmat_columns_device",
     "from_row_lengths_device", "skewed_lengths_device", "powerlaw_lengths_device",
-    "DyadicPlan", "dyadic_plan", "dyadic_row_bits", "dyadic_values", "dyadic_x", "dyadic_values_device", "dyadic_x_device",
+    "span_rows", "DyadicPlan", "dyadic_plan", "dyadic_row_bits", "dyadic_values", "dyadic_x", "dyadic_values_device", "dyadic_x_device",
 ]
 
 
@@ -484,6 +484,50 @@ def dyadic_x_device(n, plan, seed, device="cuda"):
     z = torch.rand(n, generator=g, device=device) < DYADIC_X_ZEROS
     x = torch.where(z, torch.where(s, -0.0, 0.0).to(torch.float64), x)
     return x.to(_torch_dtype(plan.dtype))
+
+
+# ----------------------------------------------------------------------------- rows with an exactly known x-window span
+# The staged x-window kernels size their LDS request from the widest set of columns any tile references (kernels/xwindows.hpp), and
+# every schedule cuts its tiles differently: 256 or 1024 rows, equal-nnz row blocks, sigma windows, ranges of entries.  A matrix whose
+# EVERY tile, however cut, references the same known column set puts that request on a chosen byte.
+def span_rows(m, n, bands, k, fill="spread", empty_every=0, dtype=np.float64):
+    """m rows of (at most) k sorted distinct columns inside `bands`, an ascending list of disjoint (first column, width) ranges.
+
+    Every non-empty row holds the first column of the first band and the last column of the last band, so any tile that contains one
+    whole row has min = bands[0][0] and max = the last band's end - 1: one band (off, S) gives a window span of exactly S.  The
+    other k - 2 columns come from the inner columns of the bands (all but those two):
+        fill = "spread"    evenly spaced over them, shifted from row to row -- the plain span;
+        fill = "segments"  cycling, row after row, through one column of every 64-column segment the bands touch: any
+                           ceil(segments / (k - 2)) + 1 consecutive rows touch them all.  One band wider than a budget then cannot be
+                           rescued by the several-window path (its segments exceed the budget too), and W far-apart bands give W runs
+                           of known length: total = 64 x the touched segments, clipped at n.
+    empty_every = e > 0 leaves rows e - 1, 2e - 1, ... empty.  Values are zeros of `dtype`: callers draw them (dyadic_values)."""
+    bands = [(int(a), int(w)) for a, w in bands]
+    assert bands and all(w >= 1 for _, w in bands) and bands[0][0] >= 0 and bands[-1][0] + bands[-1][1] <= n, (bands, n)
+    assert all(a + w <= b for (a, w), (b, _) in zip(bands, bands[1:])), ("bands must ascend and not overlap", bands)
+    cols = np.concatenate([np.arange(a, a + w, dtype=np.int64) for a, w in bands])
+    lo, hi, inner = cols[0], cols[-1], cols[1:-1]
+    if fill == "segments":
+        inner = inner[np.unique(inner >> 6, return_index=True)[1]]
+    else:
+        assert fill == "spread", fill
+    kk = int(min(max(k - 2, 0), inner.size))
+    r = np.arange(m, dtype=np.int64)[:, None]
+    j = np.arange(kk, dtype=np.int64)[None, :]
+    if fill == "segments":
+        idx = (r * kk + j) % max(inner.size, 1)
+    else:
+        idx = (r * 7919 + j * (inner.size // max(kk, 1))) % max(inner.size, 1)      # j * stride < inner.size: distinct within a row
+    ends = [np.full((m, 1), lo)] + ([np.full((m, 1), hi)] if hi > lo else [])
+    rows = np.sort(np.concatenate(ends + [inner[idx]], axis=1), axis=1)
+    assert (np.diff(rows, axis=1) > 0).all()
+    lens = np.full(m, rows.shape[1], dtype=np.int64)
+    if empty_every > 0:
+        lens[empty_every - 1::empty_every] = 0
+    rowptr = np.zeros(m + 1, dtype=np.int64)
+    np.cumsum(lens, out=rowptr[1:])
+    colidx = rows[lens > 0].reshape(-1).astype(np.int32)
+    return CSR(m, n, rowptr.astype(np.int32), colidx, np.zeros(colidx.size, dtype=dtype))
 
 
 def _torch_dtype(dtype):
