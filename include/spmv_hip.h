@@ -113,6 +113,56 @@ int spmv_hip_spmv_transpose(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_
 int spmv_hip_prepare_transpose(spmv_Handle_t handle);
 /* spmv_hip_get_transpose_info: below, after spmv_hip_info */
 
+/* ---- the transpose for k right-hand sides: Y = A^T X -------------------------------------------
+ * Y = A^T X for k vectors at once: X is m x k (A's rows), Y is n x k (A's columns), both ROW-MAJOR with leading dimensions
+ * (X[i*ldx + c], Y[j*ldy + c], ldx >= k, ldy >= k; host or device pointers).  Returns 0 or an SPMV_HIP_E_* code.
+ *   - The transpose is the one spmv_hip_spmv_transpose builds (at the first call of either, or at spmv_hip_prepare_transpose), and the CSR
+ *     arguments, option "check_values", in-place value changes, spmv_hip_update_values and later stream / async changes are handled as there.
+ *   - The multiply is spmv_hip_spmm's executor on A^T: only the first k entries of every Y row are written (empty columns of A: zeros), Y's
+ *     padding is never touched, X's never read; offsets are 64-bit.  Every column has the bits spmv_hip_spmm gives on a handle created from
+ *     A^T itself (rows of A^T listing their entries in ascending row of A): identical run to run and across ldx / ldy, host / device
+ *     pointers, stream and async settings.  k = 1 with ldx = ldy = 1 runs A^T's own schedule: bit-identical to spmv_hip_spmv_transpose.
+ *   - Column indices: the transposed schedule may have released ITS resident column indices at the end of its build (option "keep_columns"
+ *     = 0).  The first call with k > 1 or ld > 1 then rebuilds them on the device from what the handle keeps (RowPtr and perm; the caller's
+ *     arrays are not read): spmv_hip_info.device_bytes grows by 4 B per non-zero from then on, and spmv() and spmv_hip_spmv_transpose
+ *     compute exactly what they did before.
+ *   - Memory: the batch table, the long-row list and the staging buffers of host X / Y (m*k and n*k elements) belong to the transpose; they
+ *     are counted in the handle's spmv_hip_info.device_bytes and freed with it: destroy / clear / re-inspection.
+ *   - Option "reorder" handles multiply P A^T P^T: the caller gathers X rows and scatters Y rows by handle->index.
+ *   - Errors (SPMV_HIP_E_ARG, Y untouched): k < 1, ldx < k, ldy < k; a NULL X or Y; multi-GPU handles (option "gpus",
+ *     spmv_hip_create_handle_from_blocks); host_rows handles.  A cleared or failed handle: SPMV_HIP_E_NOSTATE.  Every failure is also
+ *     reported through spmv_hip_last_error(). */
+int spmv_hip_spmm_transpose(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                            const void *Matrix_Val, int k, const void *X, long long ldx, void *Y, long long ldy);
+
+/* ---- the sampled dense-dense product: Out = (U V^T) on A's pattern --------------------------------
+ * Out[p] = sum over c < k of U[i*ldu + c] * V[j*ldv + c] for every stored entry p of the resident matrix, i its row and j = ColIdx[p]:
+ * U is m x k, V is n x k, ROW-MAJOR with leading dimensions ldu, ldv >= k; Out has RowPtr[m] elements in CSR order, in the handle's
+ * precision; each of U, V and Out may be a host or a device pointer.  A's VALUES are not used: with U = dL/dY and V = X this is
+ * dL/dMatrix_Val of Y = A X.  Returns 0 or an SPMV_HIP_E_* code.
+ *   - The CSR arguments follow spmv()'s rules (another matrix is re-inspected first).  Split and cache-blocked handles use the resident
+ *     CSR itself.  Option "reorder" handles return SPMV_HIP_E_ARG: the resident matrix is P A P^T, whose entry order is not the caller's
+ *     (as for spmv_hip_update_values).
+ *   - One launch; RowPtr and ColIdx are read once per call whatever k is, the entries are split evenly over the wavefronts (a long row is
+ *     shared by many), nothing is built per matrix.  Exactly the RowPtr[m] elements of Out are written, nothing else; the padding of U and V
+ *     is never read.  nnz = 0 or m = 0 returns 0 and writes nothing.
+ *   - Summation order of an entry: a function of k and the value type alone.  With W = 2 (fp64) / 4 (fp32) columns per lane and L = the
+ *     smallest of 1, 2, 4, 8 with L*W >= k (8 beyond that), lane l of L adds the columns c = l*W + t + q*L*W < k in the order q = 0, 1, ..
+ *     outermost, t = 0 .. W-1 innermost -- the first product a plain multiplication, every further one an fma onto the chain; a lane
+ *     without a column holds -0, the identity of IEEE addition -- and the lanes' sums are added as ((l0 + l1) + (l2 + l3)) + ((l4 + l5) + (l6 + l7)) (L = 8; the left half
+ *     for L = 4; l0 + l1 for L = 2).  Results are therefore bit-identical across ldu / ldv, alignment and load width, host / device
+ *     pointers, stream and async settings, the handle's method and the entry's position.  k = 1: Out[p] is the single correctly rounded
+ *     product U[i] * V[j] (signed zeros, subnormals, infinities and NaN as IEEE 754 has them); for any k a zero result is -0 exactly when
+ *     every one of the k products is -0, as in any sequential IEEE summation.
+ *   - The handle's stream and async setting apply as for spmv(); host U / V / Out are staged through handle-owned HBM buffers (m*k, n*k and
+ *     nnz elements), allocated at first use, freed at destroy / clear / re-inspection and counted in spmv_hip_info.device_bytes.
+ *   - Column indices: as for spmv_hip_spmm -- when create() released the resident ColIdx copy (option "keep_columns" = 0), the first call
+ *     copies it back from the create-time array: device_bytes grows by 4 B per non-zero from then on, spmv() is unchanged.
+ *   - Errors (SPMV_HIP_E_ARG, Out untouched): k < 1, ldu < k, ldv < k; a NULL U, V or Out while nnz > 0; multi-GPU, host_rows and
+ *     "reorder" handles.  A cleared or failed handle: SPMV_HIP_E_NOSTATE.  Every failure is also reported through spmv_hip_last_error(). */
+int spmv_hip_sddmm(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                   const void *Matrix_Val, int k, const void *U, long long ldu, const void *V, long long ldv, void *Out);
+
 /* ---- options --------------------------------------------------------------------------------
  * Resolved once per handle, at create: process-wide value (spmv_hip_set_option / env), overridden by the
  * calling thread's value (spmv_hip_set_thread_option) -- so two threads can create differently tuned handles

@@ -112,6 +112,12 @@ FUNCTIONS = {
     "spmv_hip_get_transpose_info": (C.c_int, [spmv_Handle_t, C.POINTER(spmv_hip_info)]),
     "spmv_hip_time_transpose_launches": (C.c_double, [spmv_Handle_t, _V, _V, C.c_int, C.c_int, C.POINTER(C.c_float)]),
     "spmv_hip_transpose_map": (C.c_int, [spmv_Handle_t, _I, _I]),
+    "spmv_hip_spmm_transpose": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, C.c_int, _V, C.c_longlong, _V, C.c_longlong]),
+    "spmv_hip_time_spmm_transpose_launches": (C.c_double, [spmv_Handle_t, C.c_int, _V, C.c_longlong, _V, C.c_longlong, C.c_int, C.c_int,
+                                                           C.POINTER(C.c_float)]),
+    "spmv_hip_sddmm": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, C.c_int, _V, C.c_longlong, _V, C.c_longlong, _V]),
+    "spmv_hip_time_sddmm_launches": (C.c_double, [spmv_Handle_t, C.c_int, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_int, C.c_int,
+                                                  C.POINTER(C.c_float)]),
     # include/spmv_io.h (host only)
     "spmv_io_read_mtx": (C.c_int, [C.c_char_p, C.c_size_t, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_V)]),
     "spmv_io_cache_path": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t]),
@@ -372,6 +378,60 @@ def transpose_map(handle, n, nnz):
     return rp, perm[:int(nnz)]
 
 
+def spmm_transpose(handle, m, RowPtr, ColIdx, Matrix_Val, X, Y, check=True):
+    """Y = A^T X for the k columns of X (spmv_hip_spmm_transpose).  X (m x k) and Y (n x k): 2-D numpy arrays or torch tensors with column
+    stride 1; their row strides are passed as ldx / ldy.  -> the return code (0 on success)."""
+    px, _, k, ldx = _block(X, "X")
+    py, _, ky, ldy = _block(Y, "Y")
+    if X is not None and Y is not None and ky != k:
+        raise ValueError(f"X has {k} columns, Y {ky}")
+    if X is None:
+        k = ky
+    rc = load().spmv_hip_spmm_transpose(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), int(k), px,
+                                        int(max(ldx, 1) if X is not None else k), py, int(max(ldy, 1) if Y is not None else k))
+    if check and rc != 0:
+        _raise_if_error("spmv_hip_spmm_transpose")
+    return rc
+
+
+def time_spmm_transpose_launches(handle, X, Y, warmup=10, iters=100):
+    """-> (mean_ms, per-launch ms array) of spmv_hip_spmm_transpose on device X / Y (spmv_hip_time_spmm_transpose_launches)."""
+    px, _, k, ldx = _block(X, "X")
+    py, _, _, ldy = _block(Y, "Y")
+    ms = (C.c_float * iters)()
+    mean = load().spmv_hip_time_spmm_transpose_launches(handle, int(k), px, int(max(ldx, 1)), py, int(max(ldy, 1)), warmup, iters, ms)
+    if mean < 0:
+        _raise_if_error("spmv_hip_time_spmm_transpose_launches")
+    return mean, np.frombuffer(ms, dtype=np.float32).copy()
+
+
+def sddmm(handle, m, RowPtr, ColIdx, Matrix_Val, U, V, Out, check=True):
+    """Out[p] = sum_c U[row(p), c] * V[col(p), c] over the handle's pattern (spmv_hip_sddmm).  U (m x k) and V (n x k): 2-D numpy arrays or
+    torch tensors with column stride 1 (row strides are passed as ldu / ldv); Out: nnz contiguous elements.  -> the return code."""
+    pu, _, k, ldu = _block(U, "U")
+    pv, _, kv, ldv = _block(V, "V")
+    if U is not None and V is not None and kv != k:
+        raise ValueError(f"U has {k} columns, V {kv}")
+    if U is None:
+        k = kv
+    rc = load().spmv_hip_sddmm(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), int(k), pu, int(max(ldu, 1) if U is not None else k),
+                               pv, int(max(ldv, 1) if V is not None else k), _ptr(Out))
+    if check and rc != 0:
+        _raise_if_error("spmv_hip_sddmm")
+    return rc
+
+
+def time_sddmm_launches(handle, U, V, Out, warmup=10, iters=100):
+    """-> (mean_ms, per-launch ms array) of spmv_hip_sddmm on device U / V / Out (spmv_hip_time_sddmm_launches)."""
+    pu, _, k, ldu = _block(U, "U")
+    pv, _, _, ldv = _block(V, "V")
+    ms = (C.c_float * iters)()
+    mean = load().spmv_hip_time_sddmm_launches(handle, int(k), pu, int(max(ldu, 1)), pv, int(max(ldv, 1)), _ptr(Out), warmup, iters, ms)
+    if mean < 0:
+        _raise_if_error("spmv_hip_time_sddmm_launches")
+    return mean, np.frombuffer(ms, dtype=np.float32).copy()
+
+
 def _take_csr(m, n, nnz, rp, ci, va, dtype):
     """Copy malloc'ed C arrays into numpy arrays and free the C side."""
     from .synth import CSR
@@ -441,6 +501,13 @@ class Handle:
         return get_info(self.h)
 
     @property
+    def nnz(self):
+        """stored entries of the resident matrix (asked once, then remembered)"""
+        if getattr(self, "_nnz", None) is None:
+            self._nnz = int(self.info()["nnz"])
+        return self._nnz
+
+    @property
     def index(self):
         """handle->index as a numpy array (the RCM permutation when option "reorder" is on), else None."""
         p = self.h.contents.index
@@ -477,6 +544,30 @@ class Handle:
         rp, ci, va = self._keep
         spmv_transpose(self.h, self.m, rp, ci, va, x, y)
         return y
+
+    def _like(self, a, shape):
+        """an uninitialised array of `shape`, of a's kind, dtype and device"""
+        if isinstance(a, np.ndarray):
+            return np.empty(shape, dtype=a.dtype)
+        import torch
+        return torch.empty(shape, dtype=a.dtype, device=a.device)
+
+    def spmm_transpose(self, X, Y=None):
+        """Y = A^T X (spmv_hip_spmm_transpose) for a 2-D X of m x k; Y (n x k) is allocated like X -- same kind, dtype and device -- when None."""
+        if Y is None:
+            Y = self._like(X, (self.n, X.shape[1]))
+        rp, ci, va = self._keep
+        spmm_transpose(self.h, self.m, rp, ci, va, X, Y)
+        return Y
+
+    def sddmm(self, U, V, out=None):
+        """out[p] = <U[row(p)], V[col(p)]> over the pattern (spmv_hip_sddmm) for 2-D U (m x k) and V (n x k); out (nnz elements in CSR order) is
+        allocated like U -- same kind, dtype and device -- when None."""
+        if out is None:
+            out = self._like(U, (self.nnz,))
+        rp, ci, va = self._keep
+        sddmm(self.h, self.m, rp, ci, va, U, V, out)
+        return out
 
     def update_values(self, val):
         """The caller changed the values (in place or in a new array of the same pattern)."""
@@ -532,6 +623,12 @@ class Handle:
 
     def attach_stream(self, stream_ptr, async_=True):
         set_stream(self.h, stream_ptr, async_)
+        self._attached = (int(stream_ptr or 0), bool(async_))
+
+    @property
+    def attached(self):
+        """(stream pointer, async) last given to attach_stream; (0, False) -- the default stream, synchronous -- before any"""
+        return getattr(self, "_attached", (0, False))
 
     def close(self):
         if self.h:

@@ -1,0 +1,121 @@
+"""Y = A X inside a differentiable torch computation, on the library's own kernels.
+
+    Y = spmv_amd.autograd.matmul(handle, X, values=None)
+
+handle   an api.Handle on the current device (single GPU, not created with option "reorder")
+X        (n, k) or (n,) tensor of the handle's dtype on that device; any row stride, a column stride != 1 is made contiguous first
+values   None -- the matrix is a constant, only X receives a gradient -- or an nnz-element tensor of the handle's dtype: the forward pass
+         makes it the handle's values (Handle.update_values; skipped when the handle already holds exactly that tensor state, told by
+         the tensor's address and version counter -- a write behind the version counter, through tensor.data or a raw pointer, is not
+         seen: pass a new tensor or call Handle.update_values)
+
+forward   Handle.spmm                      Y = A X
+backward  Handle.spmm_transpose(G)         dL/dX = A^T G
+          Handle.sddmm(G, X)               dL/dvalues[p] = sum_c G[row(p), c] X[col(p), c]
+
+Every call runs on torch's current stream.  The only module of the package that needs torch; libspmv_hip.so has no torch dependency.
+"""
+from __future__ import annotations
+
+import torch
+from torch.autograd.function import once_differentiable
+
+_DTYPES = {4: torch.float32, 8: torch.float64}
+
+
+def _handle_dtype(handle):
+    return _DTYPES[int(handle.h.contents.data_size)]
+
+
+def _handle_device(handle):
+    if getattr(handle, "_ag_device", None) is None:
+        handle._ag_device = int(handle.info()["device"])
+    return handle._ag_device
+
+
+def _check_tensor(t, name, handle):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor, not {type(t).__name__}")
+    if t.dtype != _handle_dtype(handle):
+        raise TypeError(f"{name} is {t.dtype}, the handle holds {_handle_dtype(handle)}")
+    if t.device.type != "cuda" or t.device.index != _handle_device(handle):
+        raise TypeError(f"{name} is on {t.device}, the handle lives on cuda:{_handle_device(handle)}")
+
+
+def _on_current_stream(handle):
+    """the handle launches on torch's current stream, asynchronously (stream-ordered like every torch op)"""
+    want = (int(torch.cuda.current_stream(_handle_device(handle)).cuda_stream), True)
+    if handle.attached != want:
+        handle.attach_stream(want[0], async_=True)
+
+
+def _token(values):
+    return (values.data_ptr(), values._version)
+
+
+def _apply_values(handle, values, token):
+    """make `values` the handle's values unless it holds exactly that tensor state already"""
+    if getattr(handle, "_values_token", None) == token:
+        return
+    handle.update_values(values.detach().contiguous().view(-1))
+    handle._values_token = token
+    handle._values_ref = values.detach()   # the address in the token stays taken while the token stands
+
+
+def _block(t, k):
+    """2-D operand the C side can address: column stride 1, row stride >= k"""
+    if (k > 1 and t.stride(1) != 1) or t.stride(0) < k:
+        return t.contiguous()
+    return t
+
+
+class _MatMul(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, handle, X, values):
+        one_d = X.dim() == 1
+        X2 = _block(X.detach().unsqueeze(1) if one_d else X.detach(), 1 if one_d else X.shape[1])
+        _on_current_stream(handle)
+        token = None
+        if values is not None:
+            token = _token(values)
+            _apply_values(handle, values, token)
+        Y = handle.spmm(X2)
+        ctx.handle, ctx.token, ctx.one_d = handle, token, one_d
+        ctx.save_for_backward(X2 if values is not None and ctx.needs_input_grad[2] else None, values)
+        return Y[:, 0] if one_d else Y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, G):
+        handle = ctx.handle
+        X2, values = ctx.saved_tensors
+        G2 = G.unsqueeze(1) if ctx.one_d else G
+        G2 = _block(G2, G2.shape[1])
+        _on_current_stream(handle)
+        if values is not None:   # A^T G and the pattern's gradient belong to the forward pass's matrix
+            _apply_values(handle, values, ctx.token)
+        dX = dV = None
+        if ctx.needs_input_grad[1]:
+            dX = handle.spmm_transpose(G2)
+            dX = dX[:, 0] if ctx.one_d else dX
+        if ctx.needs_input_grad[2]:
+            dV = handle.sddmm(G2, X2).view(values.shape)
+        return None, dX, dV
+
+
+def matmul(handle, X, values=None):
+    """A X with gradients for X and, when given, for the matrix values (see the module's docstring)."""
+    if handle.multi_gpus() > 0:
+        raise ValueError("multi-GPU handles (option \"gpus\") are not differentiable")
+    if handle.h.contents.Level_3_opt_used:
+        raise ValueError("handles created with option \"reorder\" are not differentiable: the resident matrix is P A P^T")
+    _check_tensor(X, "X", handle)
+    if X.dim() not in (1, 2) or X.shape[0] != handle.n:
+        raise ValueError(f"X must be ({handle.n}, k) or ({handle.n},), not {tuple(X.shape)}")
+    if X.dim() == 2 and X.shape[1] < 1:
+        raise ValueError("X needs at least one column")
+    if values is not None:
+        _check_tensor(values, "values", handle)
+        if values.numel() != handle.nnz:
+            raise ValueError(f"values has {values.numel()} elements, the matrix {handle.nnz} non-zeros")
+    return _MatMul.apply(handle, X, values)

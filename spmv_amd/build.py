@@ -35,7 +35,8 @@ ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 # forms x two value types) are most of the device code: spmv_vector.hip is compiled four times, a quarter of the instantiations each
 HIP_SOURCES = [("spmv_shim.hip", [], "spmv_shim.hip.o")] + [("spmv_vector.hip", [f"SPMV_VEC_PART={k}"], f"spmv_vector{k}.hip.o") for k in range(4)] + \
               [("spmv_spmm.hip", [], "spmv_spmm.hip.o")] + \
-              [("spmv_transpose.hip", [], "spmv_transpose.hip.o")]   # the k-right-hand-side executors (kernels/spmm.hpp), the transpose builder (kernels/transpose.hpp)
+              [("spmv_transpose.hip", [], "spmv_transpose.hip.o")] + \
+              [("spmv_sddmm.hip", [], "spmv_sddmm.hip.o")]   # the k-right-hand-side executors (kernels/spmm.hpp), the transpose builder (kernels/transpose.hpp), the sampled product (kernels/sddmm.hpp)
 HIP_FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
              "-ffp-contract=fast"]
 C_FLAGS = ["-O2", "-std=c11", "-fPIC", "-fopenmp", "-Wall", "-Wextra", "-D_POSIX_C_SOURCE=200809L"]

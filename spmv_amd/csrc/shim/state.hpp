@@ -263,6 +263,9 @@ struct spmv_dev {
     int *spmm_split = nullptr, *spmm_longs = nullptr;
     void *spmm_x = nullptr, *spmm_y = nullptr;
     size_t spmm_x_bytes = 0, spmm_y_bytes = 0;
+    // spmv_hip_sddmm (shim/sddmm.hpp): HBM staging of host U / V / Out, grown on demand
+    void *sddmm_u = nullptr, *sddmm_v = nullptr, *sddmm_o = nullptr;
+    size_t sddmm_u_bytes = 0, sddmm_v_bytes = 0, sddmm_o_bytes = 0;
     // spmv_hip_spmv_transpose (shim/transpose.hpp): A^T as a matrix of its own (n x m), planned and built like any; perm[p] = our index of its entry p.
     // val_gen counts spmv_shim_update_values calls; A^T's values are gathered again when tr_gen falls behind it.
     spmv_dev *tr = nullptr;

@@ -130,6 +130,38 @@ extern "C" int spmv_shim_transpose_refresh(spmv_dev *d)
     return rc;
 }
 
+// spmv_shim_spmm on the child gathers through the child's global column indices, which the child's own spmv_shim_release_columns may have
+// given back at the end of its build.  No create-time array exists for them: they are rebuilt from what the parent keeps, exactly as
+// spmv_shim_transpose made them -- colidx_T[p] = row of A holding entry perm[p].  Counted in the child's device_bytes (hence the parent's info).
+extern "C" int spmv_shim_transpose_restore_columns(spmv_dev *d)
+{
+    if (!d || !d->tr) return fail(SPMV_HIP_E_NOSTATE, "transpose: not built");
+    spmv_dev *t = d->tr;
+    if (t->colidx || t->nnz == 0) return SPMV_HIP_OK;
+    DeviceGuard guard(d->device);
+    if (!guard.ok) return fail(SPMV_HIP_E_RUNTIME, "hipSetDevice(%d) failed", d->device);
+    const long long nnz = d->nnz;
+    const size_t ci_bytes = sizeof(int) * ((size_t) nnz + kStreamPad);
+    int *ci = nullptr, *row_of = nullptr;
+    int rc = dev_alloc(t, (void **) &ci, ci_bytes, false);
+    if (rc) return rc;
+    auto finish = [&](int code) {
+        (void) hipStreamSynchronize(d->stream);
+        (void) hipGetLastError();
+        if (row_of) (void) pool_free(row_of);
+        if (code) { (void) pool_free(ci); t->device_bytes -= (long long) ci_bytes; }
+        else t->colidx = ci;
+        return code;
+    };
+    if (pool_malloc((void **) &row_of, sizeof(int) * (size_t) nnz) != hipSuccess) { (void) hipGetLastError(); row_of = nullptr; return finish(fail(SPMV_HIP_E_ALLOC, "transpose: row scratch (%lld entries)", nnz)); }
+    hipError_t e = hipMemsetAsync(ci + nnz, 0, sizeof(int) * kStreamPad, d->stream);
+    if (e == hipSuccess) e = tr_rows_launch(d->m, d->rowptr, row_of, d->cus, d->stream);
+    if (e == hipSuccess) e = tr_columns_launch(nnz, d->tr_perm, row_of, ci, d->cus, d->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
+    if (e != hipSuccess) return finish(fail(SPMV_HIP_E_RUNTIME, "transpose: restore columns: %s", hipGetErrorString(e)));
+    return finish(SPMV_HIP_OK);
+}
+
 // tools / tests: the built map on the host (rowptr_T: n + 1 ints, perm: nnz ints; either may be NULL)
 extern "C" int spmv_shim_transpose_map(spmv_dev *d, int *rowptr_t, int *perm)
 {

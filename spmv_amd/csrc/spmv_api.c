@@ -980,3 +980,94 @@ int spmv_hip_transpose_map(spmv_Handle_t h, int *rowptr_t, int *perm)
     if (rc) spmv_set_error(rc, "transpose_map", spmv_shim_error_text());
     return rc;
 }
+
+/* ---------------------------------------------------------------- Y = A^T X for k right-hand sides */
+/* the attached transpose with its own column indices resident: what spmv_shim_spmm on the child gathers through */
+static int transpose_columns(spmv_hip_state *st, const char *where)
+{
+    int rc = spmv_shim_transpose_restore_columns(st->dev);
+    if (rc) spmv_set_error(rc, where, spmv_shim_error_text());
+    return rc;
+}
+
+int spmv_hip_spmm_transpose(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                            const void *Matrix_Val, int k, const void *X, long long ldx, void *Y, long long ldy)
+{
+    spmv_hip_state *st;
+    int rc;
+    if (!handle) { spmv_set_error(SPMV_HIP_E_ARG, "spmm_transpose", "handle is NULL"); return SPMV_HIP_E_ARG; }
+    if (k < 1 || ldx < k || ldy < k) { spmv_set_error(SPMV_HIP_E_ARG, "spmm_transpose", "need k >= 1, ldx >= k and ldy >= k"); return SPMV_HIP_E_ARG; }
+    if ((rc = transpose_state(handle, "spmm_transpose", &st)) != SPMV_HIP_OK) return rc;
+    if ((m > 0 || st->n > 0) && (!X || !Y)) { spmv_set_error(SPMV_HIP_E_ARG, "spmm_transpose", "X or Y is NULL"); return SPMV_HIP_E_ARG; }
+    if ((rc = refresh_resident(handle, st, m, RowPtr, ColIdx, Matrix_Val)) != SPMV_HIP_OK) return rc;
+    if (!st->dev) { spmv_set_error(SPMV_HIP_E_NOSTATE, "spmm_transpose", "handle has no device state"); return SPMV_HIP_E_NOSTATE; }
+    if ((rc = transpose_ready(handle, st, "spmm_transpose")) != SPMV_HIP_OK) return rc;
+    if (k == 1 && ldx == 1 && ldy == 1) rc = spmv_shim_run(spmv_shim_transpose_of(st->dev), X, Y); /* one vector: A^T's own schedule, bit-identical to spmv_hip_spmv_transpose */
+    else if ((rc = transpose_columns(st, "spmm_transpose")) == SPMV_HIP_OK) rc = spmv_shim_spmm(spmv_shim_transpose_of(st->dev), k, X, ldx, Y, ldy);
+    else return rc;
+    if (rc) spmv_set_error(rc, "spmm_transpose", spmv_shim_error_text());
+    return rc;
+}
+
+double spmv_hip_time_spmm_transpose_launches(spmv_Handle_t h, int k, const void *X, long long ldx, void *Y, long long ldy, int warmup, int iters, float *ms_out)
+{
+    spmv_hip_state *st;
+    double r;
+    if (!h) { spmv_set_error(SPMV_HIP_E_ARG, "time_spmm_transpose_launches", "handle is NULL"); return -1.0; }
+    if (k < 1 || ldx < k || ldy < k || !X || !Y) { spmv_set_error(SPMV_HIP_E_ARG, "time_spmm_transpose_launches", "need k >= 1, ldx >= k, ldy >= k, X and Y"); return -1.0; }
+    if (transpose_state(h, "time_spmm_transpose_launches", &st) != SPMV_HIP_OK) return -1.0;
+    if (transpose_ready(h, st, "time_spmm_transpose_launches") != SPMV_HIP_OK) return -1.0;
+    if (transpose_columns(st, "time_spmm_transpose_launches") != SPMV_HIP_OK) return -1.0;
+    r = spmv_shim_time_spmm(spmv_shim_transpose_of(st->dev), k, X, ldx, Y, ldy, warmup, iters, ms_out);
+    if (r < 0) spmv_set_error(SPMV_HIP_E_RUNTIME, "time_spmm_transpose_launches", spmv_shim_error_text());
+    return r;
+}
+
+/* ---------------------------------------------------------------- Out = (U V^T) sampled on A's pattern */
+/* Argument and handle rules shared by spmv_hip_sddmm and its timing entry point: 0 and *out = the single-GPU device state, or the code already reported. */
+static int sddmm_state(spmv_Handle_t h, const char *where, int k, long long ldu, long long ldv, spmv_hip_state **out)
+{
+    spmv_hip_state *st = h ? (spmv_hip_state *) h->extraHandle : NULL;
+    *out = NULL;
+    if (!h) { spmv_set_error(SPMV_HIP_E_ARG, where, "handle is NULL"); return SPMV_HIP_E_ARG; }
+    if (k < 1 || ldu < k || ldv < k) { spmv_set_error(SPMV_HIP_E_ARG, where, "need k >= 1, ldu >= k and ldv >= k"); return SPMV_HIP_E_ARG; }
+    if (st && st->host_rows) { spmv_set_error(SPMV_HIP_E_ARG, where, "not available on a host_rows handle"); return SPMV_HIP_E_ARG; }
+    if (st && st->multi) { spmv_set_error(SPMV_HIP_E_ARG, where, "not available on a multi-GPU handle (option \"gpus\", create_handle_from_blocks)"); return SPMV_HIP_E_ARG; }
+    if (!st || !st->dev) { spmv_set_error(SPMV_HIP_E_NOSTATE, where, "handle has no device state (create failed or handle cleared)"); return SPMV_HIP_E_NOSTATE; }
+    if (h->Level_3_opt_used) { /* the resident matrix is P A P^T: its entry order is not the caller's */
+        spmv_set_error(SPMV_HIP_E_ARG, where, "not available on a reordered handle (option \"reorder\")");
+        return SPMV_HIP_E_ARG;
+    }
+    *out = st;
+    return SPMV_HIP_OK;
+}
+
+int spmv_hip_sddmm(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                   const void *Matrix_Val, int k, const void *U, long long ldu, const void *V, long long ldv, void *Out)
+{
+    spmv_hip_state *st;
+    spmv_hip_info info;
+    int rc = sddmm_state(handle, "sddmm", k, ldu, ldv, &st);
+    if (rc) return rc;
+    if ((rc = refresh_resident(handle, st, m, RowPtr, ColIdx, Matrix_Val)) != SPMV_HIP_OK) return rc;
+    if (!st->dev) { spmv_set_error(SPMV_HIP_E_NOSTATE, "sddmm", "handle has no device state"); return SPMV_HIP_E_NOSTATE; }
+    if (handle->Level_3_opt_used) { spmv_set_error(SPMV_HIP_E_ARG, "sddmm", "not available on a reordered handle (option \"reorder\")"); return SPMV_HIP_E_ARG; }
+    if ((rc = spmv_shim_info(st->dev, &info)) != SPMV_HIP_OK) { spmv_set_error(rc, "sddmm", spmv_shim_error_text()); return rc; }
+    if (info.nnz == 0 || info.m == 0) return SPMV_HIP_OK; /* nothing stored: nothing written */
+    if (!U || !V || !Out) { spmv_set_error(SPMV_HIP_E_ARG, "sddmm", "U, V or Out is NULL"); return SPMV_HIP_E_ARG; }
+    if ((rc = spmm_columns(handle, st, "sddmm")) != SPMV_HIP_OK) return rc;
+    rc = spmv_shim_sddmm(st->dev, k, U, ldu, V, ldv, Out);
+    if (rc) spmv_set_error(rc, "sddmm", spmv_shim_error_text());
+    return rc;
+}
+
+double spmv_hip_time_sddmm_launches(spmv_Handle_t h, int k, const void *U, long long ldu, const void *V, long long ldv, void *Out, int warmup, int iters, float *ms_out)
+{
+    spmv_hip_state *st;
+    double r;
+    if (sddmm_state(h, "time_sddmm_launches", k, ldu, ldv, &st) != SPMV_HIP_OK) return -1.0;
+    if (spmm_columns(h, st, "time_sddmm_launches") != SPMV_HIP_OK) return -1.0;
+    r = spmv_shim_time_sddmm(st->dev, k, U, ldu, V, ldv, Out, warmup, iters, ms_out);
+    if (r < 0) spmv_set_error(SPMV_HIP_E_RUNTIME, "time_sddmm_launches", spmv_shim_error_text());
+    return r;
+}

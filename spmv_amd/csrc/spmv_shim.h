@@ -115,6 +115,16 @@ int spmv_shim_attach_transpose(spmv_dev *d, spmv_dev *child, int *perm);
 spmv_dev *spmv_shim_transpose_of(const spmv_dev *d); /* NULL until attached */
 int spmv_shim_transpose_refresh(spmv_dev *d);
 int spmv_shim_transpose_map(spmv_dev *d, int *rowptr_t, int *perm); /* copies to host; either may be NULL */
+/* The attached transpose's own column indices again in HBM after its spmv_shim_release_columns gave them back (spmv_shim_spmm on the child
+ * gathers through them): colidx_T[p] = row of A of entry perm[p], rebuilt on the device from the parent's RowPtr and perm.  No-op when resident. */
+int spmv_shim_transpose_restore_columns(spmv_dev *d);
+
+/* ---- Out[p] = sum_c U[row(p), c] V[col(p), c] over the resident pattern (shim/sddmm.hpp; spmv_hip_sddmm) ----
+ * U m x k, V n x k, row-major with leading dimensions ldu, ldv >= k; Out nnz elements in CSR order; host or device pointers each.  Needs the
+ * resident ColIdx (spmv_shim_restore_columns after spmv_shim_release_columns). */
+int spmv_shim_sddmm(spmv_dev *d, int k, const void *u, long long ldu, const void *v, long long ldv, void *out);
+/* `iters` launches timed with events on the handle's stream (device U / V / Out); mean ms, < 0 on failure */
+double spmv_shim_time_sddmm(spmv_dev *d, int k, const void *u, long long ldu, const void *v, long long ldv, void *out, int warmup, int iters, float *ms_out);
 
 /* the resident CSR arrays (device pointers; ColIdx may be NULL after spmv_shim_release_columns) */
 void spmv_shim_matrix_arrays(const spmv_dev *d, const int **rowptr, const int **colidx, const void **val);
