@@ -163,6 +163,45 @@ int spmv_hip_spmm_transpose(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_
 int spmv_hip_sddmm(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
                    const void *Matrix_Val, int k, const void *U, long long ldu, const void *V, long long ldv, void *Out);
 
+/* ---- the row softmax over A's pattern, and its backward -------------------------------------------
+ * spmv_hip_row_softmax:          Out[p] = exp(S[p] - M_i) / Z_i,  i = the row of entry p,  M_i = max over row i of S,
+ *                                Z_i = sum over row i of exp(S[q] - M_i)
+ * spmv_hip_row_softmax_backward: Out[p] = P[p] * (G[p] - D_i),  D_i = sum over row i of P[q] * G[q]   (dL/dS from P = softmax(S), G = dL/dP)
+ * S, P, G and Out hold RowPtr[m] elements in CSR order, in the handle's precision; each may be a host or a device pointer.  With
+ * spmv_hip_sddmm before and spmv_hip_spmm (values = P) after, softmax_rows(Q K^T on A's pattern) V runs on this library's kernels, forward
+ * and backward.  Returns 0 or an SPMV_HIP_E_* code.
+ *   - The CSR arguments follow spmv()'s rules (another matrix is re-inspected first).  Split and cache-blocked handles use the resident
+ *     RowPtr itself.  Option "reorder" handles return SPMV_HIP_E_ARG: the entry order of P A P^T is not the caller's.
+ *   - Only the row structure is read: ColIdx and A's values are never touched, and a resident ColIdx copy that create() released (option
+ *     "keep_columns" = 0) stays released -- spmv_hip_info.device_bytes grows by the operation's own tables and staging buffers, never by
+ *     4 B per non-zero.
+ *   - Writes: exactly the RowPtr[m] elements of Out; empty rows write nothing; m = 0 or nnz = 0 returns 0 and writes nothing.  Out may be
+ *     the very same pointer as S (forward) or as G (backward), with the same bits as out of place; any other overlap is undefined.
+ *   - Arithmetic: the maximum is subtracted, so every finite row gives finite results whatever its magnitude; exp / expf of the device math
+ *     library (not the fast intrinsics), one subtraction before it and one division after it.  The backward's map is one subtraction and
+ *     one multiplication.  No operation is contracted that is not written as an fma below.
+ *   - Special values, as torch.softmax has them on the row: a NaN anywhere in a row, a +inf, or a row of only -inf makes that whole row NaN
+ *     (the maximum drops a NaN, the sum restores it) and no other row is affected; a -inf beside finite scores gives an exact +0; a row of
+ *     length 1 gives exactly 1 for a finite S.
+ *   - Summation order of a row (Z_i, D_i): a function of the row's length and the value type alone.  Rows of up to 512 entries: with W = 1
+ *     for a length <= 1, else the smallest power of two >= the length, 64 at the most, lane t of W chains the terms t, t + W, t + 2 W, ..
+ *     in that order -- the first term as it is (forward: exp(S - M); backward: the plain product P * G), every further one added onto the
+ *     chain (forward: a plain addition; backward: fma(P, G, chain)); a lane without a term holds -0, the identity of IEEE addition -- and
+ *     the W chains are added as a balanced tree over neighbours, ((t0 + t1) + (t2 + t3)) + ((t4 + t5) + (t6 + t7)) and so on.  Longer rows:
+ *     thread t of 256 chains the terms t, t + 256, .. the same way, each 64 consecutive chains are added by that tree and the four sums as
+ *     (w0 + w1) + (w2 + w3).  A row's output bits therefore do not depend on where the row sits in the matrix, on its neighbours, the
+ *     handle's method, host or device pointers, stream and async settings: results are identical run to run.  No floating-point atomics;
+ *     no workgroup waits on another.
+ *   - The handle's stream and async setting apply as for spmv(); host arrays are staged through handle-owned HBM buffers (nnz elements
+ *     each) allocated at first use; with the batch table and the long-row list (shared with spmv_hip_spmm, built at the first call of
+ *     either) they are counted in spmv_hip_info.device_bytes and freed at destroy / clear / re-inspection.
+ *   - Errors (SPMV_HIP_E_ARG, Out untouched): a NULL handle; a NULL array while nnz > 0; multi-GPU, host_rows and "reorder" handles.  A
+ *     cleared or failed handle: SPMV_HIP_E_NOSTATE.  Every failure is also reported through spmv_hip_last_error(). */
+int spmv_hip_row_softmax(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                         const void *Matrix_Val, const void *S, void *Out);
+int spmv_hip_row_softmax_backward(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                                  const void *Matrix_Val, const void *P, const void *G, void *Out);
+
 /* ---- options --------------------------------------------------------------------------------
  * Resolved once per handle, at create: process-wide value (spmv_hip_set_option / env), overridden by the
  * calling thread's value (spmv_hip_set_thread_option) -- so two threads can create differently tuned handles

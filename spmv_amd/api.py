@@ -118,6 +118,9 @@ FUNCTIONS = {
     "spmv_hip_sddmm": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, C.c_int, _V, C.c_longlong, _V, C.c_longlong, _V]),
     "spmv_hip_time_sddmm_launches": (C.c_double, [spmv_Handle_t, C.c_int, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_int, C.c_int,
                                                   C.POINTER(C.c_float)]),
+    "spmv_hip_row_softmax": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, _V, _V]),
+    "spmv_hip_row_softmax_backward": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, _V, _V, _V]),
+    "spmv_hip_time_row_softmax_launches": (C.c_double, [spmv_Handle_t, _V, _V, C.c_int, C.c_int, C.POINTER(C.c_float)]),
     # include/spmv_io.h (host only)
     "spmv_io_read_mtx": (C.c_int, [C.c_char_p, C.c_size_t, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_V)]),
     "spmv_io_cache_path": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t]),
@@ -432,6 +435,33 @@ def time_sddmm_launches(handle, U, V, Out, warmup=10, iters=100):
     return mean, np.frombuffer(ms, dtype=np.float32).copy()
 
 
+def row_softmax(handle, m, RowPtr, ColIdx, Matrix_Val, S, Out, check=True):
+    """Out[p] = exp(S[p] - max_row) / sum_row over every row of the handle's pattern (spmv_hip_row_softmax).  S and Out: nnz contiguous elements
+    in CSR order (numpy arrays or torch tensors); Out may be S.  -> the return code."""
+    rc = load().spmv_hip_row_softmax(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), _ptr(S), _ptr(Out))
+    if check and rc != 0:
+        _raise_if_error("spmv_hip_row_softmax")
+    return rc
+
+
+def row_softmax_backward(handle, m, RowPtr, ColIdx, Matrix_Val, P, G, Out, check=True):
+    """Out[p] = P[p] * (G[p] - sum over the row of P * G): dL/dS from P = row_softmax(S) and G = dL/dP (spmv_hip_row_softmax_backward).  Out may
+    be G.  -> the return code."""
+    rc = load().spmv_hip_row_softmax_backward(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), _ptr(P), _ptr(G), _ptr(Out))
+    if check and rc != 0:
+        _raise_if_error("spmv_hip_row_softmax_backward")
+    return rc
+
+
+def time_row_softmax_launches(handle, S, Out, warmup=10, iters=100):
+    """-> (mean_ms, per-launch ms array) of spmv_hip_row_softmax on device S / Out (spmv_hip_time_row_softmax_launches)."""
+    ms = (C.c_float * iters)()
+    mean = load().spmv_hip_time_row_softmax_launches(handle, _ptr(S), _ptr(Out), warmup, iters, ms)
+    if mean < 0:
+        _raise_if_error("spmv_hip_time_row_softmax_launches")
+    return mean, np.frombuffer(ms, dtype=np.float32).copy()
+
+
 def _take_csr(m, n, nnz, rp, ci, va, dtype):
     """Copy malloc'ed C arrays into numpy arrays and free the C side."""
     from .synth import CSR
@@ -567,6 +597,23 @@ class Handle:
             out = self._like(U, (self.nnz,))
         rp, ci, va = self._keep
         sddmm(self.h, self.m, rp, ci, va, U, V, out)
+        return out
+
+    def row_softmax(self, S, out=None):
+        """out[p] = softmax of S over the stored entries of p's row (spmv_hip_row_softmax); S: nnz elements in CSR order; out is allocated like
+        S -- same kind, dtype and device -- when None, and may be S itself."""
+        if out is None:
+            out = self._like(S, (self.nnz,))
+        rp, ci, va = self._keep
+        row_softmax(self.h, self.m, rp, ci, va, S, out)
+        return out
+
+    def row_softmax_backward(self, P, G, out=None):
+        """out = dL/dS from P = row_softmax(S) and G = dL/dP (spmv_hip_row_softmax_backward); out is allocated like P when None, and may be G."""
+        if out is None:
+            out = self._like(P, (self.nnz,))
+        rp, ci, va = self._keep
+        row_softmax_backward(self.h, self.m, rp, ci, va, P, G, out)
         return out
 
     def update_values(self, val):

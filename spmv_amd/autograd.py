@@ -13,6 +13,12 @@ forward   Handle.spmm                      Y = A X
 backward  Handle.spmm_transpose(G)         dL/dX = A^T G
           Handle.sddmm(G, X)               dL/dvalues[p] = sum_c G[row(p), c] X[col(p), c]
 
+    S = spmv_amd.autograd.sddmm(handle, U, V)          S[p] = <U[row(p)], V[col(p)]> over A's pattern, with gradients for U and V
+    P = spmv_amd.autograd.row_softmax(handle, S)       softmax of S over the stored entries of every row, with a gradient for S
+
+With matmul(handle, X, values=P) after them, softmax_rows(Q K^T on A's pattern) X -- graph attention, masked attention -- runs on the
+library's kernels forward and backward (Handle.sddmm / row_softmax / spmm; Handle.row_softmax_backward, spmm, spmm_transpose, sddmm).
+
 Every call runs on torch's current stream.  The only module of the package that needs torch; libspmv_hip.so has no torch dependency.
 """
 from __future__ import annotations
@@ -119,3 +125,92 @@ def matmul(handle, X, values=None):
         if values.numel() != handle.nnz:
             raise ValueError(f"values has {values.numel()} elements, the matrix {handle.nnz} non-zeros")
     return _MatMul.apply(handle, X, values)
+
+
+def _check_handle(handle):
+    if handle.multi_gpus() > 0:
+        raise ValueError("multi-GPU handles (option \"gpus\") are not differentiable")
+    if handle.h.contents.Level_3_opt_used:
+        raise ValueError("handles created with option \"reorder\" are not differentiable: the resident matrix is P A P^T")
+
+
+class _RowSoftmax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, handle, scores):
+        _on_current_stream(handle)
+        P = handle.row_softmax(scores.detach().contiguous().view(-1)).view(scores.shape)
+        ctx.handle = handle
+        ctx.save_for_backward(P)
+        return P
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, G):
+        (P,) = ctx.saved_tensors
+        _on_current_stream(ctx.handle)
+        return None, ctx.handle.row_softmax_backward(P.view(-1), G.contiguous().view(-1)).view(G.shape)
+
+
+def row_softmax(handle, scores):
+    """P[p] = exp(scores[p] - max) / sum over the stored entries of p's row of the handle's pattern (Handle.row_softmax), with the gradient
+    dL/dscores = P * (G - sum over the row of P * G) (Handle.row_softmax_backward).  scores: an nnz-element tensor of the handle's dtype on
+    its device, in CSR order.  A's values and columns play no part."""
+    _check_handle(handle)
+    _check_tensor(scores, "scores", handle)
+    if scores.numel() != handle.nnz:
+        raise ValueError(f"scores has {scores.numel()} elements, the matrix {handle.nnz} non-zeros")
+    return _RowSoftmax.apply(handle, scores)
+
+
+class _Sddmm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, handle, U, V):
+        k = U.shape[1]
+        U2, V2 = _block(U.detach(), k), _block(V.detach(), k)
+        _on_current_stream(handle)
+        S = handle.sddmm(U2, V2)
+        ctx.handle = handle
+        ctx.save_for_backward(U2 if ctx.needs_input_grad[2] else None, V2 if ctx.needs_input_grad[1] else None)
+        return S
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, G):
+        handle = ctx.handle
+        U2, V2 = ctx.saved_tensors
+        dU = dV = None
+        if not (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]):
+            return None, None, None
+        if handle.nnz == 0:   # no stored entry: A_G is the zero matrix
+            return None, (V2.new_zeros((handle.m, V2.shape[1])) if ctx.needs_input_grad[1] else None), \
+                (U2.new_zeros((handle.n, U2.shape[1])) if ctx.needs_input_grad[2] else None)
+        _on_current_stream(handle)
+        # A_G = A's pattern with values G, for the duration: the handle's own values, and what matmul() remembers of them, come back below
+        keep, token, ref = handle._keep[2], getattr(handle, "_values_token", None), getattr(handle, "_values_ref", None)
+        Gv = G.contiguous().view(-1)
+        try:
+            handle.update_values(Gv)
+            if ctx.needs_input_grad[1]:
+                dU = handle.spmm(V2)
+            if ctx.needs_input_grad[2]:
+                dV = handle.spmm_transpose(U2)
+        finally:
+            handle.update_values(keep)
+            handle._values_token, handle._values_ref = token, ref
+        return None, dU, dV
+
+
+def sddmm(handle, U, V):
+    """S[p] = sum_c U[row(p), c] * V[col(p), c] over the handle's pattern (Handle.sddmm), with gradients for U and V: with A_G = A's pattern
+    holding G = dL/dS as values, dL/dU = A_G V (Handle.spmm) and dL/dV = A_G^T U (Handle.spmm_transpose); only the gradients asked for are
+    computed.  U: (m, k), V: (n, k), of the handle's dtype on its device.
+
+    A backward pass costs two Handle.update_values: G becomes the handle's values for the two products, then the previous values are put
+    back -- the array the handle held, and what matmul() remembers about it -- so a later matmul(handle, X), with values=None or with the
+    earlier tensor, and Handle.spmv / spmv_transpose multiply what they did before."""
+    _check_handle(handle)
+    _check_tensor(U, "U", handle)
+    _check_tensor(V, "V", handle)
+    if U.dim() != 2 or V.dim() != 2 or U.shape[0] != handle.m or V.shape[0] != handle.n or U.shape[1] != V.shape[1] or U.shape[1] < 1:
+        raise ValueError(f"U must be ({handle.m}, k) and V ({handle.n}, k) with k >= 1, not {tuple(U.shape)} and {tuple(V.shape)}")
+    return _Sddmm.apply(handle, U, V)

@@ -36,7 +36,8 @@ ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 HIP_SOURCES = [("spmv_shim.hip", [], "spmv_shim.hip.o")] + [("spmv_vector.hip", [f"SPMV_VEC_PART={k}"], f"spmv_vector{k}.hip.o") for k in range(4)] + \
               [("spmv_spmm.hip", [], "spmv_spmm.hip.o")] + \
               [("spmv_transpose.hip", [], "spmv_transpose.hip.o")] + \
-              [("spmv_sddmm.hip", [], "spmv_sddmm.hip.o")]   # the k-right-hand-side executors (kernels/spmm.hpp), the transpose builder (kernels/transpose.hpp), the sampled product (kernels/sddmm.hpp)
+              [("spmv_sddmm.hip", [], "spmv_sddmm.hip.o")] + \
+              [("spmv_softmax.hip", [], "spmv_softmax.hip.o")]   # the k-right-hand-side executors (kernels/spmm.hpp), the transpose builder (kernels/transpose.hpp), the sampled product (kernels/sddmm.hpp), the row reductions (kernels/row_softmax.hpp)
 HIP_FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
              "-ffp-contract=fast"]
 C_FLAGS = ["-O2", "-std=c11", "-fPIC", "-fopenmp", "-Wall", "-Wextra", "-D_POSIX_C_SOURCE=200809L"]

@@ -266,6 +266,9 @@ struct spmv_dev {
     // spmv_hip_sddmm (shim/sddmm.hpp): HBM staging of host U / V / Out, grown on demand
     void *sddmm_u = nullptr, *sddmm_v = nullptr, *sddmm_o = nullptr;
     size_t sddmm_u_bytes = 0, sddmm_v_bytes = 0, sddmm_o_bytes = 0;
+    // spmv_hip_row_softmax / _backward (shim/row_softmax.hpp): HBM staging of host S or P / G / Out, grown on demand (the tables are spmm's)
+    void *rowred_a = nullptr, *rowred_g = nullptr, *rowred_o = nullptr;
+    size_t rowred_a_bytes = 0, rowred_g_bytes = 0, rowred_o_bytes = 0;
     // spmv_hip_spmv_transpose (shim/transpose.hpp): A^T as a matrix of its own (n x m), planned and built like any; perm[p] = our index of its entry p.
     // val_gen counts spmv_shim_update_values calls; A^T's values are gathered again when tr_gen falls behind it.
     spmv_dev *tr = nullptr;

@@ -1071,3 +1071,52 @@ double spmv_hip_time_sddmm_launches(spmv_Handle_t h, int k, const void *U, long 
     if (r < 0) spmv_set_error(SPMV_HIP_E_RUNTIME, "time_sddmm_launches", spmv_shim_error_text());
     return r;
 }
+
+/* ---------------------------------------------------------------- row softmax over A's pattern, and its backward */
+/* Handle rules shared by spmv_hip_row_softmax, its backward and the timing entry point: sddmm's, without the shape arguments. */
+static int row_softmax_state(spmv_Handle_t h, const char *where, spmv_hip_state **out)
+{
+    return sddmm_state(h, where, 1, 1, 1, out);
+}
+
+/* P: S (forward) or P (backward); G: NULL for the forward */
+static int row_softmax_call(spmv_Handle_t handle, const char *where, int backward, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                            const void *Matrix_Val, const void *P, const void *G, void *Out)
+{
+    spmv_hip_state *st;
+    spmv_hip_info info;
+    int rc = row_softmax_state(handle, where, &st);
+    if (rc) return rc;
+    if ((rc = refresh_resident(handle, st, m, RowPtr, ColIdx, Matrix_Val)) != SPMV_HIP_OK) return rc;
+    if (!st->dev) { spmv_set_error(SPMV_HIP_E_NOSTATE, where, "handle has no device state"); return SPMV_HIP_E_NOSTATE; }
+    if (handle->Level_3_opt_used) { spmv_set_error(SPMV_HIP_E_ARG, where, "not available on a reordered handle (option \"reorder\")"); return SPMV_HIP_E_ARG; }
+    if ((rc = spmv_shim_info(st->dev, &info)) != SPMV_HIP_OK) { spmv_set_error(rc, where, spmv_shim_error_text()); return rc; }
+    if (info.nnz == 0 || info.m == 0) return SPMV_HIP_OK; /* nothing stored: nothing written */
+    if (!P || !Out || (backward && !G)) { spmv_set_error(SPMV_HIP_E_ARG, where, "a NULL array"); return SPMV_HIP_E_ARG; }
+    /* RowPtr alone is read: a released resident ColIdx copy stays released */
+    rc = backward ? spmv_shim_row_softmax_backward(st->dev, P, G, Out) : spmv_shim_row_softmax(st->dev, P, Out);
+    if (rc) spmv_set_error(rc, where, spmv_shim_error_text());
+    return rc;
+}
+
+int spmv_hip_row_softmax(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                         const void *Matrix_Val, const void *S, void *Out)
+{
+    return row_softmax_call(handle, "row_softmax", 0, m, RowPtr, ColIdx, Matrix_Val, S, NULL, Out);
+}
+
+int spmv_hip_row_softmax_backward(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                                  const void *Matrix_Val, const void *P, const void *G, void *Out)
+{
+    return row_softmax_call(handle, "row_softmax_backward", 1, m, RowPtr, ColIdx, Matrix_Val, P, G, Out);
+}
+
+double spmv_hip_time_row_softmax_launches(spmv_Handle_t h, const void *S, void *Out, int warmup, int iters, float *ms_out)
+{
+    spmv_hip_state *st;
+    double r;
+    if (row_softmax_state(h, "time_row_softmax_launches", &st) != SPMV_HIP_OK) return -1.0;
+    r = spmv_shim_time_row_softmax(st->dev, S, Out, warmup, iters, ms_out);
+    if (r < 0) spmv_set_error(SPMV_HIP_E_RUNTIME, "time_row_softmax_launches", spmv_shim_error_text());
+    return r;
+}

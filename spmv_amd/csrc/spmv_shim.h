@@ -126,6 +126,14 @@ int spmv_shim_sddmm(spmv_dev *d, int k, const void *u, long long ldu, const void
 /* `iters` launches timed with events on the handle's stream (device U / V / Out); mean ms, < 0 on failure */
 double spmv_shim_time_sddmm(spmv_dev *d, int k, const void *u, long long ldu, const void *v, long long ldv, void *out, int warmup, int iters, float *ms_out);
 
+/* ---- the row softmax over the resident ROW STRUCTURE and its backward (shim/row_softmax.hpp; spmv_hip_row_softmax, _backward) ----
+ * S, P, G, Out: nnz elements in CSR order, host or device pointers each; Out may be S (forward) or G (backward).  Reads RowPtr alone: the
+ * resident ColIdx is not needed.  Builds spmm's batch table and long-row list at the first call. */
+int spmv_shim_row_softmax(spmv_dev *d, const void *s, void *out);
+int spmv_shim_row_softmax_backward(spmv_dev *d, const void *p, const void *g, void *out);
+/* `iters` forward launches timed with events on the handle's stream (device S / Out); mean ms, < 0 on failure */
+double spmv_shim_time_row_softmax(spmv_dev *d, const void *s, void *out, int warmup, int iters, float *ms_out);
+
 /* the resident CSR arrays (device pointers; ColIdx may be NULL after spmv_shim_release_columns) */
 void spmv_shim_matrix_arrays(const spmv_dev *d, const int **rowptr, const int **colidx, const void **val);
 

@@ -37,6 +37,7 @@
 #include "kernels/spmm.hpp"
 #include "kernels/transpose.hpp"
 #include "kernels/sddmm.hpp"
+#include "kernels/row_softmax.hpp"
 
 using namespace spmv;
 
@@ -175,7 +176,7 @@ extern "C" void spmv_shim_matrix_destroy(spmv_dev *d)
     if (d->x_stage) (void) pool_free(d->x_stage);
     if (d->y_stage) (void) pool_free(d->y_stage);
     if (d->scratch8) (void) pool_free(d->scratch8);
-    for (void *p : {(void *) d->spmm_split, (void *) d->spmm_longs, d->spmm_x, d->spmm_y, d->sddmm_u, d->sddmm_v, d->sddmm_o}) if (p) (void) pool_free(p);
+    for (void *p : {(void *) d->spmm_split, (void *) d->spmm_longs, d->spmm_x, d->spmm_y, d->sddmm_u, d->sddmm_v, d->sddmm_o, d->rowred_a, d->rowred_g, d->rowred_o}) if (p) (void) pool_free(p);
     delete d;
 }
 
@@ -514,6 +515,7 @@ extern "C" int spmv_shim_is_device_ptr(const void *p) { return is_device_ptr(p) 
 #include "shim/spmm.hpp"
 #include "shim/transpose.hpp"
 #include "shim/sddmm.hpp"
+#include "shim/row_softmax.hpp"
 
 // The resident int32 ColIdx copy (4 B per non-zero: 1.28 GB on config 2) is read by the inspectors -- and afterwards only by executors that
 // gather through global columns.  Once create() has settled on a schedule whose multiply never touches it (every tile / group staged: the 16-bit

@@ -219,6 +219,18 @@ int main(int argc, char **argv)
         printf("{\"kernel\": \"calib_read\", \"bytes\": %zu, \"launches\": %d, \"ms_min\": %.5f, \"read_gbps\": %.1f}\n", n2 * 16, reps, t, n2 * 16 / t / 1e6);
         return 0;
     }
+    if (argc > 2 && strcmp(argv[1], "copy") == 0) { // same-box floor of read-once / write-once kernels: a 16-byte-per-lane copy of `bytes` (read + written: 2 x bytes)
+        size_t bytes = (size_t) strtoull(argv[2], nullptr, 10);
+        if (bytes < (1u << 20)) bytes = 1u << 20;
+        const size_t n2 = bytes / 16;
+        const int reps = argc > 3 ? atoi(argv[3]) : 10;
+        double *a, *b;
+        CK(hipMalloc(&a, n2 * 16)); CK(hipMalloc(&b, n2 * 16));
+        CK(hipMemset(a, 0, n2 * 16)); CK(hipMemset(b, 0, n2 * 16));
+        const float t = time_ms([&] { stream_rw<<<(int) ((n2 + 1023) / 1024), 256>>>(a, b, n2, 2, 1); }, reps);
+        printf("{\"kernel\": \"stream_rw copy nt\", \"bytes\": %zu, \"launches\": %d, \"ms_min\": %.5f, \"copy_gbps\": %.1f}\n", n2 * 16, reps, t, 2.0 * n2 * 16 / t / 1e6);
+        return 0;
+    }
     if (argc > 1 && strcmp(argv[1], "calib") == 0) { // known-bytes read for the FETCH_SIZE calibration
         const size_t n2 = (size_t) 240 << 20;       // 16-byte elements: 3.75 GiB, far beyond the 256 MiB Infinity Cache
         double *a, *o;
