@@ -181,6 +181,22 @@ def _raise_if_error(where):
         raise SpmvError(f"{where}: [{code}] {text}")
 
 
+def _checked(rc, symbol, check=True):
+    """-> rc, the return code of the C function `symbol`; a failure is raised when `check` is set."""
+    if check and rc != 0:
+        _raise_if_error(symbol)
+    return rc
+
+
+def _timed(symbol, args, warmup, iters):
+    """-> (mean_ms, per-launch ms array) of the timing entry point `symbol`: hipEvents on the handle's stream around each launch."""
+    ms = (C.c_float * iters)()
+    mean = getattr(load(), symbol)(*args, warmup, iters, ms)
+    if mean < 0:
+        _raise_if_error(symbol)
+    return mean, np.frombuffer(ms, dtype=np.float32).copy()
+
+
 def _ptr(a):
     """Raw address of a numpy array / torch tensor / None / int."""
     if a is None:
@@ -257,8 +273,7 @@ def clear_thread_options():
 
 def update_values(handle, Matrix_Val):
     """New values behind the same pattern (spmv_hip_update_values): no re-inspection."""
-    if load().spmv_hip_update_values(handle, _ptr(Matrix_Val)) != 0:
-        _raise_if_error("spmv_hip_update_values")
+    _checked(load().spmv_hip_update_values(handle, _ptr(Matrix_Val)), "spmv_hip_update_values")
 
 
 def _info_dict(info):
@@ -274,16 +289,14 @@ def _info_dict(info):
 
 def get_info(handle):
     info = spmv_hip_info()
-    if load().spmv_hip_get_info(handle, C.byref(info)) != 0:
-        _raise_if_error("spmv_hip_get_info")
+    _checked(load().spmv_hip_get_info(handle, C.byref(info)), "spmv_hip_get_info")
     return _info_dict(info)
 
 
 def get_transpose_info(handle):
     """spmv_hip_get_transpose_info as a dict shaped like get_info's: the schedule of A^T (raises until the transpose is built)."""
     info = spmv_hip_info()
-    if load().spmv_hip_get_transpose_info(handle, C.byref(info)) != 0:
-        _raise_if_error("spmv_hip_get_transpose_info")
+    _checked(load().spmv_hip_get_transpose_info(handle, C.byref(info)), "spmv_hip_get_transpose_info")
     return _info_dict(info)
 
 
@@ -296,11 +309,7 @@ def set_stream(handle, stream_ptr, async_=True):
 
 def time_launches(handle, x, y, warmup=10, iters=100):
     """-> (mean_ms, per-launch ms array): hipEvents on the handle's stream around each launch."""
-    ms = (C.c_float * iters)()
-    mean = load().spmv_hip_time_launches(handle, _ptr(x), _ptr(y), warmup, iters, ms)
-    if mean < 0:
-        _raise_if_error("spmv_hip_time_launches")
-    return mean, np.frombuffer(ms, dtype=np.float32).copy()
+    return _timed("spmv_hip_time_launches", (handle, _ptr(x), _ptr(y)), warmup, iters)
 
 
 def _block(a, name):
@@ -320,146 +329,99 @@ def _block(a, name):
     raise TypeError(type(a))
 
 
+def _blocks(A, a_name, B, b_name):
+    """-> (k, address of A, ld of A, address of B, ld of B) for two 2-D blocks of k columns each (_block); a block that is None has a NULL
+    address, k is the other block's and its ld is k."""
+    pa, _, k, lda = _block(A, a_name)
+    pb, _, kb, ldb = _block(B, b_name)
+    if A is not None and B is not None and kb != k:
+        raise ValueError(f"{a_name} has {k} columns, {b_name} {kb}")
+    if A is None:
+        k = kb
+    return int(k), pa, int(max(lda, 1) if A is not None else k), pb, int(max(ldb, 1) if B is not None else k)
+
+
 def spmm(handle, m, RowPtr, ColIdx, Matrix_Val, X, Y, check=True):
     """Y = A X for the k columns of X (spmv_hip_spmm).  X (n x k) and Y (m x k): 2-D numpy arrays or torch tensors with column
     stride 1; their row strides are passed as ldx / ldy, so views into wider arrays work.  -> the return code (0 on success)."""
-    px, _, k, ldx = _block(X, "X")
-    py, _, ky, ldy = _block(Y, "Y")
-    if X is not None and Y is not None and ky != k:
-        raise ValueError(f"X has {k} columns, Y {ky}")
-    if X is None:
-        k = ky
-    rc = load().spmv_hip_spmm(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), int(k), px, int(max(ldx, 1) if X is not None else k),
-                              py, int(max(ldy, 1) if Y is not None else k))
-    if check and rc != 0:
-        _raise_if_error("spmv_hip_spmm")
-    return rc
+    k, px, ldx, py, ldy = _blocks(X, "X", Y, "Y")
+    return _checked(load().spmv_hip_spmm(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), k, px, ldx, py, ldy), "spmv_hip_spmm", check)
 
 
 def time_spmm_launches(handle, X, Y, warmup=10, iters=100):
     """-> (mean_ms, per-launch ms array) of spmv_hip_spmm on device X / Y (spmv_hip_time_spmm_launches)."""
     px, _, k, ldx = _block(X, "X")
     py, _, _, ldy = _block(Y, "Y")
-    ms = (C.c_float * iters)()
-    mean = load().spmv_hip_time_spmm_launches(handle, int(k), px, int(max(ldx, 1)), py, int(max(ldy, 1)), warmup, iters, ms)
-    if mean < 0:
-        _raise_if_error("spmv_hip_time_spmm_launches")
-    return mean, np.frombuffer(ms, dtype=np.float32).copy()
+    return _timed("spmv_hip_time_spmm_launches", (handle, int(k), px, int(max(ldx, 1)), py, int(max(ldy, 1))), warmup, iters)
 
 
 def spmv_transpose(handle, m, RowPtr, ColIdx, Matrix_Val, X, Y, check=True):
     """y = A^T x (spmv_hip_spmv_transpose): X has m entries, Y n.  -> the return code (0 on success)."""
-    rc = load().spmv_hip_spmv_transpose(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), _ptr(X), _ptr(Y))
-    if check and rc != 0:
-        _raise_if_error("spmv_hip_spmv_transpose")
-    return rc
+    return _checked(load().spmv_hip_spmv_transpose(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), _ptr(X), _ptr(Y)), "spmv_hip_spmv_transpose", check)
 
 
 def prepare_transpose(handle, check=True):
     """Build (and plan) A^T now rather than at the first spmv_transpose (spmv_hip_prepare_transpose)."""
-    rc = load().spmv_hip_prepare_transpose(handle)
-    if check and rc != 0:
-        _raise_if_error("spmv_hip_prepare_transpose")
-    return rc
+    return _checked(load().spmv_hip_prepare_transpose(handle), "spmv_hip_prepare_transpose", check)
 
 
 def time_transpose_launches(handle, x, y, warmup=10, iters=100):
     """-> (mean_ms, per-launch ms array) of y = A^T x on device x / y (spmv_hip_time_transpose_launches)."""
-    ms = (C.c_float * iters)()
-    mean = load().spmv_hip_time_transpose_launches(handle, _ptr(x), _ptr(y), warmup, iters, ms)
-    if mean < 0:
-        _raise_if_error("spmv_hip_time_transpose_launches")
-    return mean, np.frombuffer(ms, dtype=np.float32).copy()
+    return _timed("spmv_hip_time_transpose_launches", (handle, _ptr(x), _ptr(y)), warmup, iters)
 
 
 def transpose_map(handle, n, nnz):
     """-> (rowptr_T, perm) of the built transpose as int32 numpy arrays (n + 1 and nnz entries; spmv_hip_transpose_map)."""
     rp = np.empty(int(n) + 1, dtype=np.int32)
     perm = np.empty(max(int(nnz), 1), dtype=np.int32)
-    if load().spmv_hip_transpose_map(handle, rp.ctypes.data_as(_I), perm.ctypes.data_as(_I)) != 0:
-        _raise_if_error("spmv_hip_transpose_map")
+    _checked(load().spmv_hip_transpose_map(handle, rp.ctypes.data_as(_I), perm.ctypes.data_as(_I)), "spmv_hip_transpose_map")
     return rp, perm[:int(nnz)]
 
 
 def spmm_transpose(handle, m, RowPtr, ColIdx, Matrix_Val, X, Y, check=True):
     """Y = A^T X for the k columns of X (spmv_hip_spmm_transpose).  X (m x k) and Y (n x k): 2-D numpy arrays or torch tensors with column
     stride 1; their row strides are passed as ldx / ldy.  -> the return code (0 on success)."""
-    px, _, k, ldx = _block(X, "X")
-    py, _, ky, ldy = _block(Y, "Y")
-    if X is not None and Y is not None and ky != k:
-        raise ValueError(f"X has {k} columns, Y {ky}")
-    if X is None:
-        k = ky
-    rc = load().spmv_hip_spmm_transpose(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), int(k), px,
-                                        int(max(ldx, 1) if X is not None else k), py, int(max(ldy, 1) if Y is not None else k))
-    if check and rc != 0:
-        _raise_if_error("spmv_hip_spmm_transpose")
-    return rc
+    k, px, ldx, py, ldy = _blocks(X, "X", Y, "Y")
+    return _checked(load().spmv_hip_spmm_transpose(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), k, px, ldx, py, ldy), "spmv_hip_spmm_transpose", check)
 
 
 def time_spmm_transpose_launches(handle, X, Y, warmup=10, iters=100):
     """-> (mean_ms, per-launch ms array) of spmv_hip_spmm_transpose on device X / Y (spmv_hip_time_spmm_transpose_launches)."""
     px, _, k, ldx = _block(X, "X")
     py, _, _, ldy = _block(Y, "Y")
-    ms = (C.c_float * iters)()
-    mean = load().spmv_hip_time_spmm_transpose_launches(handle, int(k), px, int(max(ldx, 1)), py, int(max(ldy, 1)), warmup, iters, ms)
-    if mean < 0:
-        _raise_if_error("spmv_hip_time_spmm_transpose_launches")
-    return mean, np.frombuffer(ms, dtype=np.float32).copy()
+    return _timed("spmv_hip_time_spmm_transpose_launches", (handle, int(k), px, int(max(ldx, 1)), py, int(max(ldy, 1))), warmup, iters)
 
 
 def sddmm(handle, m, RowPtr, ColIdx, Matrix_Val, U, V, Out, check=True):
     """Out[p] = sum_c U[row(p), c] * V[col(p), c] over the handle's pattern (spmv_hip_sddmm).  U (m x k) and V (n x k): 2-D numpy arrays or
     torch tensors with column stride 1 (row strides are passed as ldu / ldv); Out: nnz contiguous elements.  -> the return code."""
-    pu, _, k, ldu = _block(U, "U")
-    pv, _, kv, ldv = _block(V, "V")
-    if U is not None and V is not None and kv != k:
-        raise ValueError(f"U has {k} columns, V {kv}")
-    if U is None:
-        k = kv
-    rc = load().spmv_hip_sddmm(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), int(k), pu, int(max(ldu, 1) if U is not None else k),
-                               pv, int(max(ldv, 1) if V is not None else k), _ptr(Out))
-    if check and rc != 0:
-        _raise_if_error("spmv_hip_sddmm")
-    return rc
+    k, pu, ldu, pv, ldv = _blocks(U, "U", V, "V")
+    return _checked(load().spmv_hip_sddmm(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), k, pu, ldu, pv, ldv, _ptr(Out)), "spmv_hip_sddmm", check)
 
 
 def time_sddmm_launches(handle, U, V, Out, warmup=10, iters=100):
     """-> (mean_ms, per-launch ms array) of spmv_hip_sddmm on device U / V / Out (spmv_hip_time_sddmm_launches)."""
     pu, _, k, ldu = _block(U, "U")
     pv, _, _, ldv = _block(V, "V")
-    ms = (C.c_float * iters)()
-    mean = load().spmv_hip_time_sddmm_launches(handle, int(k), pu, int(max(ldu, 1)), pv, int(max(ldv, 1)), _ptr(Out), warmup, iters, ms)
-    if mean < 0:
-        _raise_if_error("spmv_hip_time_sddmm_launches")
-    return mean, np.frombuffer(ms, dtype=np.float32).copy()
+    return _timed("spmv_hip_time_sddmm_launches", (handle, int(k), pu, int(max(ldu, 1)), pv, int(max(ldv, 1)), _ptr(Out)), warmup, iters)
 
 
 def row_softmax(handle, m, RowPtr, ColIdx, Matrix_Val, S, Out, check=True):
     """Out[p] = exp(S[p] - max_row) / sum_row over every row of the handle's pattern (spmv_hip_row_softmax).  S and Out: nnz contiguous elements
     in CSR order (numpy arrays or torch tensors); Out may be S.  -> the return code."""
-    rc = load().spmv_hip_row_softmax(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), _ptr(S), _ptr(Out))
-    if check and rc != 0:
-        _raise_if_error("spmv_hip_row_softmax")
-    return rc
+    return _checked(load().spmv_hip_row_softmax(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), _ptr(S), _ptr(Out)), "spmv_hip_row_softmax", check)
 
 
 def row_softmax_backward(handle, m, RowPtr, ColIdx, Matrix_Val, P, G, Out, check=True):
     """Out[p] = P[p] * (G[p] - sum over the row of P * G): dL/dS from P = row_softmax(S) and G = dL/dP (spmv_hip_row_softmax_backward).  Out may
     be G.  -> the return code."""
-    rc = load().spmv_hip_row_softmax_backward(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), _ptr(P), _ptr(G), _ptr(Out))
-    if check and rc != 0:
-        _raise_if_error("spmv_hip_row_softmax_backward")
-    return rc
+    return _checked(load().spmv_hip_row_softmax_backward(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), _ptr(P), _ptr(G), _ptr(Out)),
+                    "spmv_hip_row_softmax_backward", check)
 
 
 def time_row_softmax_launches(handle, S, Out, warmup=10, iters=100):
     """-> (mean_ms, per-launch ms array) of spmv_hip_row_softmax on device S / Out (spmv_hip_time_row_softmax_launches)."""
-    ms = (C.c_float * iters)()
-    mean = load().spmv_hip_time_row_softmax_launches(handle, _ptr(S), _ptr(Out), warmup, iters, ms)
-    if mean < 0:
-        _raise_if_error("spmv_hip_time_row_softmax_launches")
-    return mean, np.frombuffer(ms, dtype=np.float32).copy()
+    return _timed("spmv_hip_time_row_softmax_launches", (handle, _ptr(S), _ptr(Out)), warmup, iters)
 
 
 def _take_csr(m, n, nnz, rp, ci, va, dtype):
@@ -632,21 +594,17 @@ class Handle:
         """-> dict(x_ptr, x_first, x_count, y_ptr, y_first, y_count, device) of device `gpu`'s slice of x and block of y."""
         xs, ys = _V(), _V()
         xf, xc, yf, yc, dv = C.c_longlong(), C.c_longlong(), C.c_longlong(), C.c_longlong(), C.c_int()
-        if load().spmv_hip_multi_slices(self.h, gpu, C.byref(xs), C.byref(xf), C.byref(xc), C.byref(ys), C.byref(yf), C.byref(yc), C.byref(dv)) != 0:
-            _raise_if_error("spmv_hip_multi_slices")
+        _checked(load().spmv_hip_multi_slices(self.h, gpu, C.byref(xs), C.byref(xf), C.byref(xc), C.byref(ys), C.byref(yf), C.byref(yc), C.byref(dv)), "spmv_hip_multi_slices")
         return dict(x_ptr=xs.value, x_first=xf.value, x_count=xc.value, y_ptr=ys.value, y_first=yf.value, y_count=yc.value, device=dv.value)
 
     def multi_step(self):
-        if load().spmv_hip_multi_step(self.h) != 0:
-            _raise_if_error("spmv_hip_multi_step")
+        _checked(load().spmv_hip_multi_step(self.h), "spmv_hip_multi_step")
 
     def multi_step_async(self):
-        if load().spmv_hip_multi_step_async(self.h) != 0:
-            _raise_if_error("spmv_hip_multi_step_async")
+        _checked(load().spmv_hip_multi_step_async(self.h), "spmv_hip_multi_step_async")
 
     def multi_synchronize(self):
-        if load().spmv_hip_multi_synchronize(self.h) != 0:
-            _raise_if_error("spmv_hip_multi_synchronize")
+        _checked(load().spmv_hip_multi_synchronize(self.h), "spmv_hip_multi_synchronize")
 
     @classmethod
     def from_blocks(cls, blocks, n, method=SPMV_METHODS.Method_Parallel):

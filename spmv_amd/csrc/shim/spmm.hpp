@@ -1,6 +1,5 @@
 // shim/spmm.hpp -- part of spmv_shim.hip: Y = A X for k right-hand sides over the RESIDENT CSR (spmv_hip_spmm).  The executors are
-// kernels/spmm.hpp, launched from their own translation unit (spmv_spmm.hip, spmm_launch); this side owns the batch table, the long-row list,
-// the HBM staging of host X / Y and the error channel.
+// kernels/spmm.hpp, launched from their own translation unit (spmv_spmm.hip, spmm_launch); this side owns the batch table and the long-row list.
 #pragma once
 
 // equal-nnz row batches (one wave each) and the rows longer than kSpmmLongThr (a workgroup each): built once per resident matrix
@@ -53,22 +52,6 @@ static int spmm_plan(spmv_dev *d)
     return SPMV_HIP_OK;
 }
 
-// handle-owned HBM buffer of at least `bytes` (host X / Y staging); grown when a call needs more
-static int spmm_stage_buffer(spmv_dev *d, void **buf, size_t *have, size_t bytes)
-{
-    if (*buf && *have >= bytes) return SPMV_HIP_OK;
-    if (*buf) {
-        quiesce(d);
-        (void) pool_free(*buf);
-        d->device_bytes -= (long long) *have;
-        *buf = nullptr;
-        *have = 0;
-    }
-    ALLOC_TRY(d, buf, bytes, false);
-    *have = bytes ? bytes : 16;
-    return SPMV_HIP_OK;
-}
-
 extern "C" int spmv_shim_spmm(spmv_dev *d, int k, const void *x, long long ldx, void *y, long long ldy)
 {
     if (!d || !d->built) return fail(SPMV_HIP_E_NOSTATE, "spmm: schedule not built");
@@ -82,21 +65,11 @@ extern "C" int spmv_shim_spmm(spmv_dev *d, int k, const void *x, long long ldx, 
     if (rc) return rc;
     const size_t s = d->vsize;
     const bool f64 = s == sizeof(double);
-    const bool xdev = is_device_ptr(x), ydev = is_device_ptr(y);
+    Stager stg{d};
     const char *xd = (const char *) x;
     char *yd = (char *) y;
     long long lx = ldx, ly = ldy;
-    if (!xdev && d->n > 0) { // host X: its k columns packed into HBM (the padding is not copied)
-        if ((rc = spmm_stage_buffer(d, &d->spmm_x, &d->spmm_x_bytes, s * (size_t) k * (size_t) d->n))) return rc;
-        HIP_TRY(hipMemcpy2DAsync(d->spmm_x, s * (size_t) k, x, s * (size_t) ldx, s * (size_t) k, (size_t) d->n, hipMemcpyHostToDevice, d->stream));
-        xd = (const char *) d->spmm_x;
-        lx = k;
-    }
-    if (!ydev) {
-        if ((rc = spmm_stage_buffer(d, &d->spmm_y, &d->spmm_y_bytes, s * (size_t) k * (size_t) d->m))) return rc;
-        yd = (char *) d->spmm_y;
-        ly = k;
-    }
+    if ((rc = stg.in(d->stage[STAGE_SPMM_X], xd, lx, (size_t) d->n, k)) || (rc = stg.out(d->stage[STAGE_SPMM_Y], yd, ly, (size_t) d->m, k))) return rc;
     const int KP = f64 ? SpmmShape<double>::KP : SpmmShape<float>::KP;
     for (int c = 0; c < k; c += KP) { // one pass over A per panel
         SpmmArgs a;
@@ -114,13 +87,11 @@ extern "C" int spmv_shim_spmm(spmv_dev *d, int k, const void *x, long long ldx, 
         a.y = yd + s * (size_t) c;
         a.ldx = lx;
         a.ldy = ly;
-        a.vec = ((uintptr_t) a.x & 15) == 0 && ((uintptr_t) a.y & 15) == 0 && ((size_t) lx * s) % 16 == 0 && ((size_t) ly * s) % 16 == 0;
+        a.vec = wide_ok(a.x, lx, s) && wide_ok(a.y, ly, s);
         const hipError_t e = spmm_launch(a, f64, d->stream);
         if (e != hipSuccess) return fail(SPMV_HIP_E_RUNTIME, "spmm: launch: %s", hipGetErrorString(e));
     }
-    if (!ydev) HIP_TRY(hipMemcpy2DAsync(y, s * (size_t) ldy, d->spmm_y, s * (size_t) k, s * (size_t) k, (size_t) d->m, hipMemcpyDeviceToHost, d->stream));
-    if (!d->async || !xdev || !ydev) HIP_TRY(hipStreamSynchronize(d->stream));
-    return SPMV_HIP_OK;
+    return stg.finish();
 }
 
 // The create-time ColIdx again in HBM after spmv_shim_release_columns gave the resident copy back: copied as is, or -- perm_host given (option
@@ -194,32 +165,5 @@ extern "C" double spmv_shim_time_spmm(spmv_dev *d, int k, const void *x, long lo
 {
     if (!d || !d->built || iters <= 0) { fail(SPMV_HIP_E_ARG, "time_spmm: bad arguments"); return -1.0; }
     if (!is_device_ptr(x) || !is_device_ptr(y)) { fail(SPMV_HIP_E_ARG, "time_spmm: X and Y must be device pointers"); return -1.0; }
-    const int keep_async = d->async;
-    d->async = 1;
-    std::vector<hipEvent_t> ev((size_t) iters + 1);
-    for (auto &e : ev) if (hipEventCreate(&e) != hipSuccess) { d->async = keep_async; fail(SPMV_HIP_E_RUNTIME, "hipEventCreate"); return -1.0; }
-    int rc = SPMV_HIP_OK;
-    for (int i = 0; i < warmup && !rc; ++i) rc = spmv_shim_spmm(d, k, x, ldx, y, ldy);
-    for (int i = 0; i < iters && !rc; ++i) {
-        (void) hipEventRecord(ev[i], d->stream);
-        rc = spmv_shim_spmm(d, k, x, ldx, y, ldy);
-    }
-    (void) hipEventRecord(ev[iters], d->stream);
-    hipError_t e = hipStreamSynchronize(d->stream);
-    d->async = keep_async;
-    double mean = -1.0;
-    if (!rc && e == hipSuccess) {
-        double tot = 0;
-        for (int i = 0; i < iters; ++i) {
-            float ms = 0;
-            (void) hipEventElapsedTime(&ms, ev[i], ev[i + 1]);
-            if (ms_out) ms_out[i] = ms;
-            tot += ms;
-        }
-        mean = tot / iters;
-    } else if (e != hipSuccess) {
-        fail(SPMV_HIP_E_RUNTIME, "time_spmm: %s", hipGetErrorString(e));
-    }
-    for (auto &v : ev) (void) hipEventDestroy(v);
-    return mean;
+    return time_events(d, "time_spmm", warmup, iters, ms_out, [&] { return spmv_shim_spmm(d, k, x, ldx, y, ldy); });
 }

@@ -1,6 +1,6 @@
 // shim/state.hpp -- part of the single translation unit spmv_shim.hip (included there, in order):
-// error channel, the device-side state of a handle (spmv_dev), allocation bookkeeping and the small
-// utility kernels (row statistics, ColIdx validation, fills).
+// error channel, the device-side state of a handle (spmv_dev), allocation bookkeeping, the stager and the timer every operation on the
+// resident matrix shares, and the small utility kernels (row statistics, ColIdx validation, fills).
 #pragma once
 
 // ------------------------------------------------------------------------------------ errors
@@ -183,6 +183,11 @@ struct BlkSet {
     int *hdr = nullptr;           // per group: first column of its super-slab
 };
 
+// The handle-owned HBM buffer behind one host operand of one operation: allocated at the first call that passes that operand from the host,
+// given back and allocated anew when a later call needs more, counted in device_bytes, freed with the device state.
+struct StageBuf { void *p = nullptr; size_t bytes = 0; };
+enum { STAGE_X, STAGE_Y, STAGE_SPMM_X, STAGE_SPMM_Y, STAGE_SDDMM_U, STAGE_SDDMM_V, STAGE_SDDMM_O, STAGE_ROWRED_A, STAGE_ROWRED_G, STAGE_ROWRED_O, STAGE_COUNT };
+
 struct spmv_dev {
     int device = 0;
     int cus = 256;
@@ -245,8 +250,8 @@ struct spmv_dev {
     int *lsub_rowptr = nullptr, *lsub_colidx = nullptr;
     void *lsub_val = nullptr;
     long long lsub_nnz = 0;
-    // staging for host x / y
-    void *x_stage = nullptr, *y_stage = nullptr, *scratch8 = nullptr;
+    StageBuf stage[STAGE_COUNT]; // HBM behind host operands, one buffer per operand (Stager)
+    void *scratch8 = nullptr;
     long long stream_bytes = 0, x_bytes = 0; // traffic model of one launch (account_stream_bytes)
     int x_groups_seen = 0;                   // tile groups analysed before the blocked executor took over
     float route_ms[2] = {0, 0};              // measured tile schedule vs blocked executor (spmv_shim_build, mode 2)
@@ -257,18 +262,10 @@ struct spmv_dev {
     float near_share = -1.f;                 // sampled share of near entries (-1: not sampled)
     float split_ms[2] = {0, 0};              // measured: schedule as built vs the split pair
     bool accumulate = false;                 // this matrix is the far half of a split: y += A x (blocked executor only)
-    // spmv_hip_spmm (shim/spmm.hpp): equal-nnz row batches and the long-row list over the resident CSR, built at the first call; HBM staging of host X / Y
+    // spmv_hip_spmm (shim/spmm.hpp): equal-nnz row batches and the long-row list over the resident CSR, built at the first call (row_softmax reads them too)
     bool spmm_planned = false;
     int spmm_nb = 0, spmm_nlong = 0;
     int *spmm_split = nullptr, *spmm_longs = nullptr;
-    void *spmm_x = nullptr, *spmm_y = nullptr;
-    size_t spmm_x_bytes = 0, spmm_y_bytes = 0;
-    // spmv_hip_sddmm (shim/sddmm.hpp): HBM staging of host U / V / Out, grown on demand
-    void *sddmm_u = nullptr, *sddmm_v = nullptr, *sddmm_o = nullptr;
-    size_t sddmm_u_bytes = 0, sddmm_v_bytes = 0, sddmm_o_bytes = 0;
-    // spmv_hip_row_softmax / _backward (shim/row_softmax.hpp): HBM staging of host S or P / G / Out, grown on demand (the tables are spmm's)
-    void *rowred_a = nullptr, *rowred_g = nullptr, *rowred_o = nullptr;
-    size_t rowred_a_bytes = 0, rowred_g_bytes = 0, rowred_o_bytes = 0;
     // spmv_hip_spmv_transpose (shim/transpose.hpp): A^T as a matrix of its own (n x m), planned and built like any; perm[p] = our index of its entry p.
     // val_gen counts spmv_shim_update_values calls; A^T's values are gathered again when tr_gen falls behind it.
     spmv_dev *tr = nullptr;
@@ -365,6 +362,112 @@ static bool is_device_ptr(const void *p)
         return false;
     }
     return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
+}
+
+// ------------------------------------------------------------------------------------ host operands, timing
+// One call's operands, rows x k elements each with leading dimension ld (a vector: k = ld = 1).  A device operand is used where it is, with the
+// caller's ld; a host operand goes through its StageBuf -- in(): its k columns packed into HBM on the handle's stream (the padding is not copied);
+// out(): the buffer the kernel writes instead -- and p / ld are redirected there.  finish() copies the host result back and synchronizes, unless
+// the handle is asynchronous and every operand was on the device.  Every operand is asked once whether it is a device pointer.
+struct Stager {
+    spmv_dev *d;
+    bool all_dev = true;
+    const StageBuf *res = nullptr; // the staged result and where it goes
+    void *res_host = nullptr;
+    size_t res_ld = 0, res_rows = 0, res_k = 0;
+
+    int reserve(StageBuf &b, size_t bytes)
+    {
+        if (b.p && b.bytes >= bytes) return SPMV_HIP_OK;
+        if (b.p) {
+            quiesce(d);
+            (void) pool_free(b.p);
+            d->device_bytes -= (long long) b.bytes;
+            b = StageBuf();
+        }
+        ALLOC_TRY(d, &b.p, bytes, false);
+        b.bytes = bytes ? bytes : 16;
+        return SPMV_HIP_OK;
+    }
+    // rows x k elements between a packed device buffer and a host array of leading dimension ld
+    hipError_t copy(void *dst, size_t dst_ld, const void *src, size_t src_ld, size_t rows, size_t k, hipMemcpyKind kind)
+    {
+        const size_t s = d->vsize;
+        if (dst_ld == k && src_ld == k) return hipMemcpyAsync(dst, src, s * k * rows, kind, d->stream);
+        return hipMemcpy2DAsync(dst, s * dst_ld, src, s * src_ld, s * k, rows, kind, d->stream);
+    }
+    template <class P> int in(StageBuf &b, P &p, long long &ld, size_t rows, int k)
+    {
+        const bool dev = is_device_ptr(p);
+        all_dev = all_dev && dev;
+        if (dev || !p || rows == 0) return SPMV_HIP_OK;
+        const int rc = reserve(b, d->vsize * (size_t) k * rows);
+        if (rc) return rc;
+        HIP_TRY(copy(b.p, (size_t) k, p, (size_t) ld, rows, (size_t) k, hipMemcpyHostToDevice));
+        p = (P) b.p;
+        ld = k;
+        return SPMV_HIP_OK;
+    }
+    template <class P> int out(StageBuf &b, P &p, long long &ld, size_t rows, int k)
+    {
+        const bool dev = is_device_ptr(p);
+        all_dev = all_dev && dev;
+        if (dev || rows == 0) return SPMV_HIP_OK;
+        const int rc = reserve(b, d->vsize * (size_t) k * rows);
+        if (rc) return rc;
+        res = &b; res_host = p; res_ld = (size_t) ld; res_rows = rows; res_k = (size_t) k;
+        p = (P) b.p;
+        ld = k;
+        return SPMV_HIP_OK;
+    }
+    int finish()
+    {
+        if (res) HIP_TRY(copy(res_host, res_ld, res->p, res_k, res_rows, res_k, hipMemcpyDeviceToHost));
+        if (!d->async || !all_dev) HIP_TRY(hipStreamSynchronize(d->stream));
+        return SPMV_HIP_OK;
+    }
+};
+
+// true if p and the leading dimension ld (elements of s bytes) allow 16-byte accesses to every row
+static bool wide_ok(const void *p, long long ld, size_t s) { return ((uintptr_t) p & 15) == 0 && ((size_t) ld * s) % 16 == 0; }
+
+// Mean ms of `iters` calls of run() (an operation's own entry point on device operands; 0 on success) after `warmup` untimed ones: hipEvents on
+// the handle's stream around every call, the handle asynchronous for the loop only.  ms_out (iters floats, may be NULL) receives the single
+// times.  < 0 on failure, with the error text set; the events are destroyed on every path.
+template <class Run> static double time_events(spmv_dev *d, const char *what, int warmup, int iters, float *ms_out, Run run)
+{
+    std::vector<hipEvent_t> ev;
+    ev.reserve((size_t) iters + 1);
+    const int keep_async = d->async;
+    auto done = [&](double mean) {
+        d->async = keep_async;
+        for (hipEvent_t e : ev) (void) hipEventDestroy(e);
+        return mean;
+    };
+    for (int i = 0; i <= iters; ++i) {
+        hipEvent_t e;
+        if (hipEventCreate(&e) != hipSuccess) { (void) hipGetLastError(); fail(SPMV_HIP_E_RUNTIME, "hipEventCreate"); return done(-1.0); }
+        ev.push_back(e);
+    }
+    d->async = 1;
+    int rc = SPMV_HIP_OK;
+    for (int i = 0; i < warmup && !rc; ++i) rc = run();
+    for (int i = 0; i < iters && !rc; ++i) {
+        (void) hipEventRecord(ev[i], d->stream);
+        rc = run();
+    }
+    (void) hipEventRecord(ev[iters], d->stream);
+    const hipError_t e = hipStreamSynchronize(d->stream);
+    if (e != hipSuccess) fail(SPMV_HIP_E_RUNTIME, "%s: %s", what, hipGetErrorString(e));
+    if (rc || e != hipSuccess) return done(-1.0);
+    double tot = 0;
+    for (int i = 0; i < iters; ++i) {
+        float ms = 0;
+        (void) hipEventElapsedTime(&ms, ev[i], ev[i + 1]);
+        if (ms_out) ms_out[i] = ms;
+        tot += ms;
+    }
+    return done(tot / iters);
 }
 
 extern "C" int spmv_shim_device_count(void)

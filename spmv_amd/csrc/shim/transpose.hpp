@@ -1,7 +1,6 @@
 // shim/transpose.hpp -- part of spmv_shim.hip: A^T of the resident CSR as a matrix of its own (spmv_hip_spmv_transpose).  The kernels are
-// kernels/transpose.hpp, launched from their own translation unit (spmv_transpose.hip); this side owns the scratch, the scan between the radix
-// passes, the child matrix and its value refresh.  The host C side (spmv_api.c) plans and builds the child exactly as create() plans a matrix,
-// then attaches it -- the protocol of the split halves (shim/split.hpp).
+// kernels/transpose.hpp, launched from their own translation unit (spmv_transpose.hip).  The host C side (spmv_api.c) plans and builds the child
+// exactly as create() plans a matrix, then attaches it -- the protocol of the split halves (shim/split.hpp).
 #pragma once
 
 // Build A^T (n x m): an unplanned matrix that owns rowptr_T / colidx_T / val_T, and perm (device, nnz ints: perm[p] = our CSR index of its

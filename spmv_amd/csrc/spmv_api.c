@@ -60,6 +60,25 @@ void spmv_hip_clear_error(void) { g_err_code = 0; g_err_text[0] = 0; }
 int spmv_hip_device_count(void) { return spmv_shim_device_count(); }
 void spmv_hip_trim_pool(void) { spmv_shim_trim_pool(); }
 
+/* the shim's code goes out with the shim's text; `refuse` is the same for a rule of this file; a timer's failure is a negative time */
+static int report(int rc, const char *where)
+{
+    if (rc) spmv_set_error(rc, where, spmv_shim_error_text());
+    return rc;
+}
+static double report_time(double ms, const char *where)
+{
+    if (ms < 0) spmv_set_error(SPMV_HIP_E_RUNTIME, where, spmv_shim_error_text());
+    return ms;
+}
+static int refuse(int code, const char *where, const char *what)
+{
+    spmv_set_error(code, where, what);
+    return code;
+}
+static size_t value_size(spmv_Handle_t h) { return h->data_size == sizeof(double) ? sizeof(double) : sizeof(float); } /* serial_spmv.c:48-54 */
+static long long alg_bytes(long long m, long long n, long long nnz, long long s) { return 4ll * (m + 1) + nnz * (4 + s) + s * n + s * m; } /* SURVEY 8d */
+
 /* ---------------------------------------------------------------- handle life-cycle */
 static void handle_reset(spmv_Handle_t h) /* common.c:18-29 */
 {
@@ -142,7 +161,7 @@ static void watch_values(spmv_Handle_t h, spmv_hip_state *st, const void *Val, l
 {
     const long mode = st->opts.v[SPMV_OPT_CHECK_VALUES];
     st->val_sum_valid = 0;
-    st->val_words = nnz * (long long) ((h->data_size == sizeof(double) ? sizeof(double) : sizeof(float)) / 4);
+    st->val_words = nnz * (long long) (value_size(h) / 4);
     if (!Val || st->val_words <= 0 || mode == 0) return;
     if (mode == 1) {
         if (spmv_shim_checksum_words(Val, st->val_words, &st->val_sum) == SPMV_HIP_OK) st->val_sum_valid = 1;
@@ -184,7 +203,7 @@ out:
 static int upload_reordered(spmv_Handle_t h, spmv_hip_state *st, int m, int n, const int *RowPtr,
                             const int *ColIdx, const void *Val)
 {
-    const size_t vs = h->data_size == sizeof(double) ? sizeof(double) : sizeof(float);
+    const size_t vs = value_size(h);
     int *rp2 = NULL, *ci2 = NULL, *perm = NULL;
     void *va2 = NULL;
     int rc = 1;
@@ -564,8 +583,7 @@ static int refresh_resident(spmv_Handle_t handle, spmv_hip_state *st, BASIC_INT_
         else have = spmv_shim_checksum_words(Matrix_Val, st->val_words, &sum) == SPMV_HIP_OK;
         if (have && sum != st->val_sum) {
             if (st->multi && !handle->Level_3_opt_used) { /* every shard refreshes its slice of the values in place */
-                rc = spmv_shim_multi_update_values(st->multi, Matrix_Val);
-                if (rc) { spmv_set_error(rc, "spmv/refresh values", spmv_shim_error_text()); return rc; }
+                if ((rc = report(spmv_shim_multi_update_values(st->multi, Matrix_Val), "spmv/refresh values"))) return rc;
                 st->val_sum = sum;
             } else if (handle->Level_3_opt_used) {
                 /* option "reorder": the resident matrix is P A P^T, whose value order is not the caller's -- the values
@@ -573,8 +591,7 @@ static int refresh_resident(spmv_Handle_t handle, spmv_hip_state *st, BASIC_INT_
                  * takes a new checksum) */
                 if ((rc = state_build(handle, st, m, st->n, RowPtr, ColIdx, Matrix_Val)) != SPMV_HIP_OK) return rc;
             } else {
-                rc = spmv_shim_update_values(st->dev, Matrix_Val);
-                if (rc) { spmv_set_error(rc, "spmv/refresh values", spmv_shim_error_text()); return rc; }
+                if ((rc = report(spmv_shim_update_values(st->dev, Matrix_Val), "spmv/refresh values"))) return rc;
                 st->val_sum = sum;
             }
         }
@@ -586,7 +603,6 @@ void spmv(const spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *Ro
           const BASIC_INT_TYPE *ColIdx, const void *Matrix_Val, const void *X, void *Y)
 {
     spmv_hip_state *st;
-    int rc;
     if (handle == NULL) return; /* common.c:285 */
     st = (spmv_hip_state *) handle->extraHandle;
     if (st && st->host_rows) { /* the arguments of THIS call are what is multiplied (common.c:286-298) */
@@ -603,8 +619,7 @@ void spmv(const spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *Ro
         return;
     }
     if (refresh_resident(handle, st, m, RowPtr, ColIdx, Matrix_Val) != SPMV_HIP_OK) return;
-    rc = st->multi ? spmv_shim_multi_run(st->multi, X, Y) : spmv_shim_run(st->dev, X, Y);
-    if (rc) spmv_set_error(rc, "spmv", spmv_shim_error_text());
+    (void) report(st->multi ? spmv_shim_multi_run(st->multi, X, Y) : spmv_shim_run(st->dev, X, Y), "spmv");
 }
 
 /* ---------------------------------------------------------------- extensions */
@@ -645,46 +660,23 @@ int spmv_hip_multi_uses_rccl(spmv_Handle_t h)
     return st && st->multi ? spmv_shim_multi_uses_rccl(st->multi) : 0;
 }
 
+/* one shim call on the multi-GPU state, reported */
+static int multi_call(spmv_Handle_t h, const char *where, int (*call)(spmv_multi *))
+{
+    spmv_multi *mt = multi_of(h, where);
+    return mt ? report(call(mt), where) : SPMV_HIP_E_NOSTATE;
+}
+
 int spmv_hip_multi_slices(spmv_Handle_t h, int gpu, void **x_slice, long long *x_first, long long *x_count,
                           void **y_block, long long *y_first, long long *y_count, int *device)
 {
     spmv_multi *mt = multi_of(h, "multi_slices");
-    int rc;
-    if (!mt) return SPMV_HIP_E_NOSTATE;
-    rc = spmv_shim_multi_slices(mt, gpu, x_slice, x_first, x_count, y_block, y_first, y_count, device);
-    if (rc) spmv_set_error(rc, "multi_slices", spmv_shim_error_text());
-    return rc;
+    return mt ? report(spmv_shim_multi_slices(mt, gpu, x_slice, x_first, x_count, y_block, y_first, y_count, device), "multi_slices") : SPMV_HIP_E_NOSTATE;
 }
 
-int spmv_hip_multi_step(spmv_Handle_t h)
-{
-    spmv_multi *mt = multi_of(h, "multi_step");
-    int rc;
-    if (!mt) return SPMV_HIP_E_NOSTATE;
-    rc = spmv_shim_multi_step(mt);
-    if (rc) spmv_set_error(rc, "multi_step", spmv_shim_error_text());
-    return rc;
-}
-
-int spmv_hip_multi_step_async(spmv_Handle_t h)
-{
-    spmv_multi *mt = multi_of(h, "multi_step_async");
-    int rc;
-    if (!mt) return SPMV_HIP_E_NOSTATE;
-    rc = spmv_shim_multi_step_async(mt);
-    if (rc) spmv_set_error(rc, "multi_step_async", spmv_shim_error_text());
-    return rc;
-}
-
-int spmv_hip_multi_synchronize(spmv_Handle_t h)
-{
-    spmv_multi *mt = multi_of(h, "multi_synchronize");
-    int rc;
-    if (!mt) return SPMV_HIP_E_NOSTATE;
-    rc = spmv_shim_multi_sync(mt);
-    if (rc) spmv_set_error(rc, "multi_synchronize", spmv_shim_error_text());
-    return rc;
-}
+int spmv_hip_multi_step(spmv_Handle_t h) { return multi_call(h, "multi_step", spmv_shim_multi_step); }
+int spmv_hip_multi_step_async(spmv_Handle_t h) { return multi_call(h, "multi_step_async", spmv_shim_multi_step_async); }
+int spmv_hip_multi_synchronize(spmv_Handle_t h) { return multi_call(h, "multi_synchronize", spmv_shim_multi_sync); }
 
 int spmv_hip_set_stream(spmv_Handle_t h, void *stream)
 {
@@ -706,18 +698,13 @@ int spmv_hip_set_async(spmv_Handle_t h, int async)
 int spmv_hip_synchronize(spmv_Handle_t h)
 {
     spmv_hip_state *st = state_of(h, "synchronize");
-    int rc;
-    if (!st) return SPMV_HIP_E_NOSTATE;
-    rc = spmv_shim_sync(st->dev);
-    if (rc) spmv_set_error(rc, "synchronize", spmv_shim_error_text());
-    return rc;
+    return st ? report(spmv_shim_sync(st->dev), "synchronize") : SPMV_HIP_E_NOSTATE;
 }
 
 int spmv_hip_get_info(spmv_Handle_t h, spmv_hip_info *out)
 {
     spmv_hip_state *st = h ? (spmv_hip_state *) h->extraHandle : NULL;
     if (st && st->host_rows && out) { /* no device state: describe the host loop */
-        const long long s = h->data_size == sizeof(double) ? 8 : 4;
         memset(out, 0, sizeof *out);
         out->device = -1;
         out->schedule = SPMV_SCHED_HOST_ROWS;
@@ -725,7 +712,7 @@ int spmv_hip_get_info(spmv_Handle_t h, spmv_hip_info *out)
         out->n = st->n;
         out->nnz = out->stored_nnz = st->m > 0 ? h->RowPtr[st->m] : 0;
         out->mean_row_len = st->m > 0 ? (double) out->nnz / st->m : 0.0;
-        out->alg_bytes = 4ll * ((long long) st->m + 1) + out->nnz * (4 + s) + s * st->n + s * st->m;
+        out->alg_bytes = alg_bytes(st->m, st->n, out->nnz, (long long) value_size(h));
         out->stream_bytes = out->alg_bytes;
         out->schedule_name = "host-rows";
         out->kernel_name = "spmv_host_rows";
@@ -752,10 +739,9 @@ int spmv_hip_get_info(spmv_Handle_t h, spmv_hip_info *out)
             if (o.min_row_len < out->min_row_len) out->min_row_len = o.min_row_len;
         }
         if (rc == SPMV_HIP_OK) {
-            const long long s = h->data_size == sizeof(double) ? 8 : 4;
             out->m = st->m; out->n = st->n; out->nnz = spmv_shim_multi_nnz(st->multi);
             out->mean_row_len = st->m > 0 ? (double) out->nnz / st->m : 0.0;
-            out->alg_bytes = 4ll * ((long long) st->m + 1) + out->nnz * (4 + s) + s * st->n + s * st->m;
+            out->alg_bytes = alg_bytes(st->m, st->n, out->nnz, (long long) value_size(h));
         }
         return rc;
     }
@@ -774,29 +760,13 @@ int spmv_hip_update_values(spmv_Handle_t h, const void *Val)
     spmv_hip_state *st = h ? (spmv_hip_state *) h->extraHandle : NULL;
     int rc;
     if (st && st->host_rows) { h->Matrix_Val = (void *) Val; return SPMV_HIP_OK; } /* borrowed arrays: nothing resident */
-    if (st && st->multi) {
-        if (!Val) { spmv_set_error(SPMV_HIP_E_ARG, "update_values", "Val is NULL"); return SPMV_HIP_E_ARG; }
-        if (h->Level_3_opt_used) {
-            spmv_set_error(SPMV_HIP_E_ARG, "update_values", "not available on a reordered handle (option \"reorder\")");
-            return SPMV_HIP_E_ARG;
-        }
-        rc = spmv_shim_multi_update_values(st->multi, Val);
-        if (rc) { spmv_set_error(rc, "update_values", spmv_shim_error_text()); return rc; }
-        h->Matrix_Val = (void *) Val;
-        watch_values(h, st, Val, spmv_shim_multi_nnz(st->multi));
-        return SPMV_HIP_OK;
-    }
-    st = state_of(h, "update_values");
-    if (!st) return SPMV_HIP_E_NOSTATE;
-    if (!Val) { spmv_set_error(SPMV_HIP_E_ARG, "update_values", "Val is NULL"); return SPMV_HIP_E_ARG; }
-    if (h->Level_3_opt_used) { /* the resident matrix is P A P^T: its value order is not the caller's */
-        spmv_set_error(SPMV_HIP_E_ARG, "update_values", "not available on a reordered handle (option \"reorder\")");
-        return SPMV_HIP_E_ARG;
-    }
-    rc = spmv_shim_update_values(st->dev, Val);
-    if (rc) { spmv_set_error(rc, "update_values", spmv_shim_error_text()); return rc; }
+    if (!(st && st->multi) && !(st = state_of(h, "update_values"))) return SPMV_HIP_E_NOSTATE;
+    if (!Val) return refuse(SPMV_HIP_E_ARG, "update_values", "Val is NULL");
+    if (h->Level_3_opt_used) /* the resident matrix is P A P^T: its value order is not the caller's */
+        return refuse(SPMV_HIP_E_ARG, "update_values", "not available on a reordered handle (option \"reorder\")");
+    if ((rc = report(st->multi ? spmv_shim_multi_update_values(st->multi, Val) : spmv_shim_update_values(st->dev, Val), "update_values"))) return rc;
     h->Matrix_Val = (void *) Val;
-    watch_values(h, st, Val, st->val_words / (long long) ((h->data_size == sizeof(double) ? sizeof(double) : sizeof(float)) / 4));
+    watch_values(h, st, Val, st->multi ? spmv_shim_multi_nnz(st->multi) : st->val_words / (long long) (value_size(h) / 4));
     return SPMV_HIP_OK;
 }
 
@@ -809,78 +779,77 @@ long spmv_hip_get_handle_option(spmv_Handle_t h, const char *key)
 double spmv_hip_time_launches(spmv_Handle_t h, const void *x, void *y, int warmup, int iters, float *ms_out)
 {
     spmv_hip_state *st = state_of(h, "time_launches");
-    double r;
-    if (!st) return -1.0;
-    r = spmv_shim_time(st->dev, x, y, warmup, iters, ms_out);
-    if (r < 0) spmv_set_error(SPMV_HIP_E_RUNTIME, "time_launches", spmv_shim_error_text());
-    return r;
+    return st ? report_time(spmv_shim_time(st->dev, x, y, warmup, iters, ms_out), "time_launches") : -1.0;
 }
 
-/* ---------------------------------------------------------------- k right-hand sides */
-/* Argument rules and state shared by spmv_hip_spmm and its timing entry point: 0 and *out = the device state with its resident ColIdx
- * (restored from the create-time array when create() had released it), or the code already reported. */
-static int spmm_state(spmv_Handle_t h, const char *where, int k, const void *X, long long ldx, const void *Y, long long ldy, int m, spmv_hip_state **out)
+/* ---------------------------------------------------------------- operations on the resident matrix: one gate, one prologue
+ * spmm, the transposed multiplies, sddmm, the row softmax and their timers work on the single-GPU resident matrix.  An entry point is: its own
+ * argument rules -- a NULL handle and a bad k / ld are E_ARG before the handle's state is looked at --, the gate or the prologue, the tables it
+ * needs (columns, transpose), the shim call through report().  Where an entry point checks its operands for NULL is its own business and differs. */
+#define RESIDENT_NOT_REORDERED 1 /* the entries are addressed in the caller's CSR order: the resident P A P^T of option "reorder" has another */
+
+/* The gate: 0 and *out = the single-GPU device state, or the code already reported. */
+static int resident_state(spmv_Handle_t h, const char *where, int flags, spmv_hip_state **out)
 {
     spmv_hip_state *st = h ? (spmv_hip_state *) h->extraHandle : NULL;
     *out = NULL;
-    if (!h) { spmv_set_error(SPMV_HIP_E_ARG, where, "handle is NULL"); return SPMV_HIP_E_ARG; }
-    if (k < 1 || ldx < k || ldy < k) { spmv_set_error(SPMV_HIP_E_ARG, where, "need k >= 1, ldx >= k and ldy >= k"); return SPMV_HIP_E_ARG; }
-    if (m > 0 && (!X || !Y)) { spmv_set_error(SPMV_HIP_E_ARG, where, "X or Y is NULL"); return SPMV_HIP_E_ARG; }
-    if (st && st->host_rows) { spmv_set_error(SPMV_HIP_E_ARG, where, "not available on a host_rows handle"); return SPMV_HIP_E_ARG; }
-    if (st && st->multi) { spmv_set_error(SPMV_HIP_E_ARG, where, "not available on a multi-GPU handle (option \"gpus\", create_handle_from_blocks)"); return SPMV_HIP_E_ARG; }
-    if (!st || !st->dev) { spmv_set_error(SPMV_HIP_E_NOSTATE, where, "handle has no device state (create failed or handle cleared)"); return SPMV_HIP_E_NOSTATE; }
+    if (!h) return refuse(SPMV_HIP_E_ARG, where, "handle is NULL");
+    if (st && st->host_rows) return refuse(SPMV_HIP_E_ARG, where, "not available on a host_rows handle");
+    if (st && st->multi) return refuse(SPMV_HIP_E_ARG, where, "not available on a multi-GPU handle (option \"gpus\", create_handle_from_blocks)");
+    if (!st || !st->dev) return refuse(SPMV_HIP_E_NOSTATE, where, "handle has no device state (create failed or handle cleared)");
+    if ((flags & RESIDENT_NOT_REORDERED) && h->Level_3_opt_used) return refuse(SPMV_HIP_E_ARG, where, "not available on a reordered handle (option \"reorder\")");
     *out = st;
     return SPMV_HIP_OK;
 }
 
+/* The prologue of an operation that takes the CSR arguments like spmv(): the gate, this call's arguments against the resident matrix
+ * (refresh_resident), and what a re-inspection may have changed -- the device state, the reordering -- looked at again. */
+static int resident_prologue(spmv_Handle_t h, const char *where, int flags, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                             const void *Matrix_Val, spmv_hip_state **out)
+{
+    int rc = resident_state(h, where, flags, out);
+    if (rc || (rc = refresh_resident(h, *out, m, RowPtr, ColIdx, Matrix_Val)) != SPMV_HIP_OK) return rc;
+    if (!(*out)->dev) return refuse(SPMV_HIP_E_NOSTATE, where, "handle has no device state");
+    if ((flags & RESIDENT_NOT_REORDERED) && h->Level_3_opt_used) return refuse(SPMV_HIP_E_ARG, where, "not available on a reordered handle (option \"reorder\")");
+    return SPMV_HIP_OK;
+}
+
+/* option keep_columns = 0 may have released the resident ColIdx at create; the handle's ColIdx is the create-time array (pointer rule) */
 static int spmm_columns(spmv_Handle_t h, spmv_hip_state *st, const char *where)
 {
-    /* option keep_columns = 0 may have released the resident ColIdx at create; the handle's ColIdx is the create-time array (pointer rule) */
-    int rc = spmv_shim_restore_columns(st->dev, h->RowPtr, h->ColIdx, h->Level_3_opt_used ? h->index : NULL);
-    if (rc) spmv_set_error(rc, where, spmv_shim_error_text());
-    return rc;
+    return report(spmv_shim_restore_columns(st->dev, h->RowPtr, h->ColIdx, h->Level_3_opt_used ? h->index : NULL), where);
+}
+
+/* ---------------------------------------------------------------- k right-hand sides */
+/* the argument rules ahead of the gate: spmv_hip_spmm; its timer with m = 1 (X and Y are always needed); spmv_hip_spmm_transpose with m = 0 (it checks X and Y behind the gate) */
+static int spmm_args(spmv_Handle_t h, const char *where, int k, const void *X, long long ldx, const void *Y, long long ldy, int m)
+{
+    if (!h) return refuse(SPMV_HIP_E_ARG, where, "handle is NULL");
+    if (k < 1 || ldx < k || ldy < k) return refuse(SPMV_HIP_E_ARG, where, "need k >= 1, ldx >= k and ldy >= k");
+    if (m > 0 && (!X || !Y)) return refuse(SPMV_HIP_E_ARG, where, "X or Y is NULL");
+    return SPMV_HIP_OK;
 }
 
 int spmv_hip_spmm(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
                   const void *Matrix_Val, int k, const void *X, long long ldx, void *Y, long long ldy)
 {
     spmv_hip_state *st;
-    int rc = spmm_state(handle, "spmm", k, X, ldx, Y, ldy, m, &st);
-    if (rc) return rc;
-    if ((rc = refresh_resident(handle, st, m, RowPtr, ColIdx, Matrix_Val)) != SPMV_HIP_OK) return rc;
-    if (!st->dev) { spmv_set_error(SPMV_HIP_E_NOSTATE, "spmm", "handle has no device state"); return SPMV_HIP_E_NOSTATE; }
-    if (k == 1 && ldx == 1 && ldy == 1) rc = spmv_shim_run(st->dev, X, Y); /* one vector: the handle's own spmv schedule, bit-identical to spmv() */
-    else if ((rc = spmm_columns(handle, st, "spmm")) == SPMV_HIP_OK) rc = spmv_shim_spmm(st->dev, k, X, ldx, Y, ldy);
-    else return rc;
-    if (rc) spmv_set_error(rc, "spmm", spmv_shim_error_text());
-    return rc;
+    int rc;
+    if ((rc = spmm_args(handle, "spmm", k, X, ldx, Y, ldy, m)) || (rc = resident_prologue(handle, "spmm", 0, m, RowPtr, ColIdx, Matrix_Val, &st))) return rc;
+    if (k == 1 && ldx == 1 && ldy == 1) return report(spmv_shim_run(st->dev, X, Y), "spmm"); /* one vector: the handle's own spmv schedule, bit-identical to spmv() */
+    if ((rc = spmm_columns(handle, st, "spmm"))) return rc;
+    return report(spmv_shim_spmm(st->dev, k, X, ldx, Y, ldy), "spmm");
 }
 
 double spmv_hip_time_spmm_launches(spmv_Handle_t h, int k, const void *X, long long ldx, void *Y, long long ldy, int warmup, int iters, float *ms_out)
 {
+    const char *where = "time_spmm_launches";
     spmv_hip_state *st;
-    double r;
-    if (spmm_state(h, "time_spmm_launches", k, X, ldx, Y, ldy, 1, &st) != SPMV_HIP_OK) return -1.0;
-    if (spmm_columns(h, st, "time_spmm_launches") != SPMV_HIP_OK) return -1.0;
-    r = spmv_shim_time_spmm(st->dev, k, X, ldx, Y, ldy, warmup, iters, ms_out);
-    if (r < 0) spmv_set_error(SPMV_HIP_E_RUNTIME, "time_spmm_launches", spmv_shim_error_text());
-    return r;
+    if (spmm_args(h, where, k, X, ldx, Y, ldy, 1) || resident_state(h, where, 0, &st) || spmm_columns(h, st, where)) return -1.0;
+    return report_time(spmv_shim_time_spmm(st->dev, k, X, ldx, Y, ldy, warmup, iters, ms_out), where);
 }
 
 /* ---------------------------------------------------------------- y = A^T x */
-/* Handle rules shared by the transpose entry points: 0 and *out = the single-GPU device state, or the code already reported. */
-static int transpose_state(spmv_Handle_t h, const char *where, spmv_hip_state **out)
-{
-    spmv_hip_state *st = h ? (spmv_hip_state *) h->extraHandle : NULL;
-    *out = NULL;
-    if (!h) { spmv_set_error(SPMV_HIP_E_ARG, where, "handle is NULL"); return SPMV_HIP_E_ARG; }
-    if (st && st->host_rows) { spmv_set_error(SPMV_HIP_E_ARG, where, "not available on a host_rows handle"); return SPMV_HIP_E_ARG; }
-    if (st && st->multi) { spmv_set_error(SPMV_HIP_E_ARG, where, "not available on a multi-GPU handle (option \"gpus\", create_handle_from_blocks)"); return SPMV_HIP_E_ARG; }
-    if (!st || !st->dev) { spmv_set_error(SPMV_HIP_E_NOSTATE, where, "handle has no device state (create failed or handle cleared)"); return SPMV_HIP_E_NOSTATE; }
-    *out = st;
-    return SPMV_HIP_OK;
-}
-
 /* A^T of the resident matrix: built on the device once per resident matrix, planned and inspected by the code path of create() with the
  * handle's requested method and options, attached to the resident matrix; afterwards its values are gathered again whenever A's changed.
  * When create() released the resident ColIdx, it is restored for the build and released again, so the forward multiply is unchanged. */
@@ -900,9 +869,8 @@ static int transpose_ready(spmv_Handle_t h, spmv_hip_state *st, const char *wher
         if ((rc = spmm_columns(h, st, where)) != SPMV_HIP_OK) return rc;
         rc = spmv_shim_transpose(st->dev, &child, &perm);
         if (released) (void) spmv_shim_release_columns(st->dev);
-        if (rc) { spmv_set_error(rc, where, spmv_shim_error_text()); return rc; }
-        if ((rc = spmv_shim_attach_transpose(st->dev, child, perm)) != SPMV_HIP_OK) {
-            spmv_set_error(rc, where, spmv_shim_error_text());
+        if (report(rc, where)) return rc;
+        if ((rc = report(spmv_shim_attach_transpose(st->dev, child, perm), where)) != SPMV_HIP_OK) {
             spmv_shim_matrix_destroy(child);
             return rc;
         }
@@ -913,170 +881,114 @@ static int transpose_ready(spmv_Handle_t h, spmv_hip_state *st, const char *wher
         st->tplan = plan;
         st->tmethod = actual;
     }
-    rc = spmv_shim_transpose_refresh(st->dev);
-    if (rc) spmv_set_error(rc, where, spmv_shim_error_text());
-    return rc;
+    return report(spmv_shim_transpose_refresh(st->dev), where);
 }
+
+static const char transpose_not_built[] = "the transpose is not built (spmv_hip_prepare_transpose, or a first spmv_hip_spmv_transpose)";
 
 int spmv_hip_spmv_transpose(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
                             const void *Matrix_Val, const void *X, void *Y)
 {
     spmv_hip_state *st;
-    int rc = transpose_state(handle, "spmv_transpose", &st);
+    int rc = resident_state(handle, "spmv_transpose", 0, &st); /* ahead of the prologue: the operands are checked behind the gate, before the refresh */
     if (rc) return rc;
-    if ((m > 0 && !X) || (st->n > 0 && !Y)) { spmv_set_error(SPMV_HIP_E_ARG, "spmv_transpose", "X or Y is NULL"); return SPMV_HIP_E_ARG; }
-    if ((rc = refresh_resident(handle, st, m, RowPtr, ColIdx, Matrix_Val)) != SPMV_HIP_OK) return rc;
-    if (!st->dev) { spmv_set_error(SPMV_HIP_E_NOSTATE, "spmv_transpose", "handle has no device state"); return SPMV_HIP_E_NOSTATE; }
-    if ((rc = transpose_ready(handle, st, "spmv_transpose")) != SPMV_HIP_OK) return rc;
-    rc = spmv_shim_run(spmv_shim_transpose_of(st->dev), X, Y);
-    if (rc) spmv_set_error(rc, "spmv_transpose", spmv_shim_error_text());
-    return rc;
+    if ((m > 0 && !X) || (st->n > 0 && !Y)) return refuse(SPMV_HIP_E_ARG, "spmv_transpose", "X or Y is NULL");
+    if ((rc = resident_prologue(handle, "spmv_transpose", 0, m, RowPtr, ColIdx, Matrix_Val, &st)) || (rc = transpose_ready(handle, st, "spmv_transpose"))) return rc;
+    return report(spmv_shim_run(spmv_shim_transpose_of(st->dev), X, Y), "spmv_transpose");
 }
 
 int spmv_hip_prepare_transpose(spmv_Handle_t handle)
 {
     spmv_hip_state *st;
-    int rc = transpose_state(handle, "prepare_transpose", &st);
-    if (rc) return rc;
-    return transpose_ready(handle, st, "prepare_transpose");
+    int rc = resident_state(handle, "prepare_transpose", 0, &st);
+    return rc ? rc : transpose_ready(handle, st, "prepare_transpose");
 }
 
 int spmv_hip_get_transpose_info(spmv_Handle_t handle, spmv_hip_info *out)
 {
     spmv_hip_state *st;
-    int rc = transpose_state(handle, "get_transpose_info", &st);
+    int rc = resident_state(handle, "get_transpose_info", 0, &st);
     if (rc) return rc;
-    if (!out) { spmv_set_error(SPMV_HIP_E_ARG, "get_transpose_info", "out is NULL"); return SPMV_HIP_E_ARG; }
-    if (!spmv_shim_transpose_of(st->dev)) {
-        spmv_set_error(SPMV_HIP_E_NOSTATE, "get_transpose_info", "the transpose is not built (spmv_hip_prepare_transpose, or a first spmv_hip_spmv_transpose)");
-        return SPMV_HIP_E_NOSTATE;
-    }
-    rc = spmv_shim_info(spmv_shim_transpose_of(st->dev), out);
-    if (rc) spmv_set_error(rc, "get_transpose_info", spmv_shim_error_text());
-    return rc;
+    if (!out) return refuse(SPMV_HIP_E_ARG, "get_transpose_info", "out is NULL");
+    if (!spmv_shim_transpose_of(st->dev)) return refuse(SPMV_HIP_E_NOSTATE, "get_transpose_info", transpose_not_built);
+    return report(spmv_shim_info(spmv_shim_transpose_of(st->dev), out), "get_transpose_info");
 }
 
 double spmv_hip_time_transpose_launches(spmv_Handle_t h, const void *x, void *y, int warmup, int iters, float *ms_out)
 {
+    const char *where = "time_transpose_launches";
     spmv_hip_state *st;
-    double r;
-    if (transpose_state(h, "time_transpose_launches", &st) != SPMV_HIP_OK) return -1.0;
-    if (transpose_ready(h, st, "time_transpose_launches") != SPMV_HIP_OK) return -1.0;
-    r = spmv_shim_time(spmv_shim_transpose_of(st->dev), x, y, warmup, iters, ms_out);
-    if (r < 0) spmv_set_error(SPMV_HIP_E_RUNTIME, "time_transpose_launches", spmv_shim_error_text());
-    return r;
+    if (resident_state(h, where, 0, &st) || transpose_ready(h, st, where)) return -1.0;
+    return report_time(spmv_shim_time(spmv_shim_transpose_of(st->dev), x, y, warmup, iters, ms_out), where);
 }
 
 int spmv_hip_transpose_map(spmv_Handle_t h, int *rowptr_t, int *perm)
 {
     spmv_hip_state *st;
-    int rc = transpose_state(h, "transpose_map", &st);
+    int rc = resident_state(h, "transpose_map", 0, &st);
     if (rc) return rc;
-    if (!spmv_shim_transpose_of(st->dev)) {
-        spmv_set_error(SPMV_HIP_E_NOSTATE, "transpose_map", "the transpose is not built (spmv_hip_prepare_transpose, or a first spmv_hip_spmv_transpose)");
-        return SPMV_HIP_E_NOSTATE;
-    }
-    rc = spmv_shim_transpose_map(st->dev, rowptr_t, perm);
-    if (rc) spmv_set_error(rc, "transpose_map", spmv_shim_error_text());
-    return rc;
+    if (!spmv_shim_transpose_of(st->dev)) return refuse(SPMV_HIP_E_NOSTATE, "transpose_map", transpose_not_built);
+    return report(spmv_shim_transpose_map(st->dev, rowptr_t, perm), "transpose_map");
 }
 
 /* ---------------------------------------------------------------- Y = A^T X for k right-hand sides */
 /* the attached transpose with its own column indices resident: what spmv_shim_spmm on the child gathers through */
 static int transpose_columns(spmv_hip_state *st, const char *where)
 {
-    int rc = spmv_shim_transpose_restore_columns(st->dev);
-    if (rc) spmv_set_error(rc, where, spmv_shim_error_text());
-    return rc;
+    return report(spmv_shim_transpose_restore_columns(st->dev), where);
 }
 
 int spmv_hip_spmm_transpose(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
                             const void *Matrix_Val, int k, const void *X, long long ldx, void *Y, long long ldy)
 {
+    const char *where = "spmm_transpose";
     spmv_hip_state *st;
     int rc;
-    if (!handle) { spmv_set_error(SPMV_HIP_E_ARG, "spmm_transpose", "handle is NULL"); return SPMV_HIP_E_ARG; }
-    if (k < 1 || ldx < k || ldy < k) { spmv_set_error(SPMV_HIP_E_ARG, "spmm_transpose", "need k >= 1, ldx >= k and ldy >= k"); return SPMV_HIP_E_ARG; }
-    if ((rc = transpose_state(handle, "spmm_transpose", &st)) != SPMV_HIP_OK) return rc;
-    if ((m > 0 || st->n > 0) && (!X || !Y)) { spmv_set_error(SPMV_HIP_E_ARG, "spmm_transpose", "X or Y is NULL"); return SPMV_HIP_E_ARG; }
-    if ((rc = refresh_resident(handle, st, m, RowPtr, ColIdx, Matrix_Val)) != SPMV_HIP_OK) return rc;
-    if (!st->dev) { spmv_set_error(SPMV_HIP_E_NOSTATE, "spmm_transpose", "handle has no device state"); return SPMV_HIP_E_NOSTATE; }
-    if ((rc = transpose_ready(handle, st, "spmm_transpose")) != SPMV_HIP_OK) return rc;
-    if (k == 1 && ldx == 1 && ldy == 1) rc = spmv_shim_run(spmv_shim_transpose_of(st->dev), X, Y); /* one vector: A^T's own schedule, bit-identical to spmv_hip_spmv_transpose */
-    else if ((rc = transpose_columns(st, "spmm_transpose")) == SPMV_HIP_OK) rc = spmv_shim_spmm(spmv_shim_transpose_of(st->dev), k, X, ldx, Y, ldy);
-    else return rc;
-    if (rc) spmv_set_error(rc, "spmm_transpose", spmv_shim_error_text());
-    return rc;
+    if ((rc = spmm_args(handle, where, k, NULL, ldx, NULL, ldy, 0)) || (rc = resident_state(handle, where, 0, &st))) return rc; /* the operands: behind the gate, before the refresh */
+    if ((m > 0 || st->n > 0) && (!X || !Y)) return refuse(SPMV_HIP_E_ARG, where, "X or Y is NULL");
+    if ((rc = resident_prologue(handle, where, 0, m, RowPtr, ColIdx, Matrix_Val, &st)) || (rc = transpose_ready(handle, st, where))) return rc;
+    if (k == 1 && ldx == 1 && ldy == 1) return report(spmv_shim_run(spmv_shim_transpose_of(st->dev), X, Y), where); /* one vector: A^T's own schedule, bit-identical to spmv_hip_spmv_transpose */
+    if ((rc = transpose_columns(st, where))) return rc;
+    return report(spmv_shim_spmm(spmv_shim_transpose_of(st->dev), k, X, ldx, Y, ldy), where);
 }
 
 double spmv_hip_time_spmm_transpose_launches(spmv_Handle_t h, int k, const void *X, long long ldx, void *Y, long long ldy, int warmup, int iters, float *ms_out)
 {
+    const char *where = "time_spmm_transpose_launches";
     spmv_hip_state *st;
-    double r;
-    if (!h) { spmv_set_error(SPMV_HIP_E_ARG, "time_spmm_transpose_launches", "handle is NULL"); return -1.0; }
-    if (k < 1 || ldx < k || ldy < k || !X || !Y) { spmv_set_error(SPMV_HIP_E_ARG, "time_spmm_transpose_launches", "need k >= 1, ldx >= k, ldy >= k, X and Y"); return -1.0; }
-    if (transpose_state(h, "time_spmm_transpose_launches", &st) != SPMV_HIP_OK) return -1.0;
-    if (transpose_ready(h, st, "time_spmm_transpose_launches") != SPMV_HIP_OK) return -1.0;
-    if (transpose_columns(st, "time_spmm_transpose_launches") != SPMV_HIP_OK) return -1.0;
-    r = spmv_shim_time_spmm(spmv_shim_transpose_of(st->dev), k, X, ldx, Y, ldy, warmup, iters, ms_out);
-    if (r < 0) spmv_set_error(SPMV_HIP_E_RUNTIME, "time_spmm_transpose_launches", spmv_shim_error_text());
-    return r;
-}
-
-/* ---------------------------------------------------------------- Out = (U V^T) sampled on A's pattern */
-/* Argument and handle rules shared by spmv_hip_sddmm and its timing entry point: 0 and *out = the single-GPU device state, or the code already reported. */
-static int sddmm_state(spmv_Handle_t h, const char *where, int k, long long ldu, long long ldv, spmv_hip_state **out)
-{
-    spmv_hip_state *st = h ? (spmv_hip_state *) h->extraHandle : NULL;
-    *out = NULL;
-    if (!h) { spmv_set_error(SPMV_HIP_E_ARG, where, "handle is NULL"); return SPMV_HIP_E_ARG; }
-    if (k < 1 || ldu < k || ldv < k) { spmv_set_error(SPMV_HIP_E_ARG, where, "need k >= 1, ldu >= k and ldv >= k"); return SPMV_HIP_E_ARG; }
-    if (st && st->host_rows) { spmv_set_error(SPMV_HIP_E_ARG, where, "not available on a host_rows handle"); return SPMV_HIP_E_ARG; }
-    if (st && st->multi) { spmv_set_error(SPMV_HIP_E_ARG, where, "not available on a multi-GPU handle (option \"gpus\", create_handle_from_blocks)"); return SPMV_HIP_E_ARG; }
-    if (!st || !st->dev) { spmv_set_error(SPMV_HIP_E_NOSTATE, where, "handle has no device state (create failed or handle cleared)"); return SPMV_HIP_E_NOSTATE; }
-    if (h->Level_3_opt_used) { /* the resident matrix is P A P^T: its entry order is not the caller's */
-        spmv_set_error(SPMV_HIP_E_ARG, where, "not available on a reordered handle (option \"reorder\")");
-        return SPMV_HIP_E_ARG;
+    if (!h || k < 1 || ldx < k || ldy < k || !X || !Y) {
+        (void) refuse(SPMV_HIP_E_ARG, where, !h ? "handle is NULL" : "need k >= 1, ldx >= k, ldy >= k, X and Y");
+        return -1.0;
     }
-    *out = st;
-    return SPMV_HIP_OK;
+    if (resident_state(h, where, 0, &st) || transpose_ready(h, st, where) || transpose_columns(st, where)) return -1.0;
+    return report_time(spmv_shim_time_spmm(spmv_shim_transpose_of(st->dev), k, X, ldx, Y, ldy, warmup, iters, ms_out), where);
 }
 
+/* ---------------------------------------------------------------- the operations over A's pattern: sddmm, row softmax and its backward */
 int spmv_hip_sddmm(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
                    const void *Matrix_Val, int k, const void *U, long long ldu, const void *V, long long ldv, void *Out)
 {
     spmv_hip_state *st;
     spmv_hip_info info;
-    int rc = sddmm_state(handle, "sddmm", k, ldu, ldv, &st);
-    if (rc) return rc;
-    if ((rc = refresh_resident(handle, st, m, RowPtr, ColIdx, Matrix_Val)) != SPMV_HIP_OK) return rc;
-    if (!st->dev) { spmv_set_error(SPMV_HIP_E_NOSTATE, "sddmm", "handle has no device state"); return SPMV_HIP_E_NOSTATE; }
-    if (handle->Level_3_opt_used) { spmv_set_error(SPMV_HIP_E_ARG, "sddmm", "not available on a reordered handle (option \"reorder\")"); return SPMV_HIP_E_ARG; }
-    if ((rc = spmv_shim_info(st->dev, &info)) != SPMV_HIP_OK) { spmv_set_error(rc, "sddmm", spmv_shim_error_text()); return rc; }
+    int rc;
+    if (!handle || k < 1 || ldu < k || ldv < k) return refuse(SPMV_HIP_E_ARG, "sddmm", !handle ? "handle is NULL" : "need k >= 1, ldu >= k and ldv >= k");
+    if ((rc = resident_prologue(handle, "sddmm", RESIDENT_NOT_REORDERED, m, RowPtr, ColIdx, Matrix_Val, &st)) || (rc = report(spmv_shim_info(st->dev, &info), "sddmm"))) return rc;
     if (info.nnz == 0 || info.m == 0) return SPMV_HIP_OK; /* nothing stored: nothing written */
-    if (!U || !V || !Out) { spmv_set_error(SPMV_HIP_E_ARG, "sddmm", "U, V or Out is NULL"); return SPMV_HIP_E_ARG; }
-    if ((rc = spmm_columns(handle, st, "sddmm")) != SPMV_HIP_OK) return rc;
-    rc = spmv_shim_sddmm(st->dev, k, U, ldu, V, ldv, Out);
-    if (rc) spmv_set_error(rc, "sddmm", spmv_shim_error_text());
-    return rc;
+    if (!U || !V || !Out) return refuse(SPMV_HIP_E_ARG, "sddmm", "U, V or Out is NULL");
+    if ((rc = spmm_columns(handle, st, "sddmm"))) return rc;
+    return report(spmv_shim_sddmm(st->dev, k, U, ldu, V, ldv, Out), "sddmm");
 }
 
 double spmv_hip_time_sddmm_launches(spmv_Handle_t h, int k, const void *U, long long ldu, const void *V, long long ldv, void *Out, int warmup, int iters, float *ms_out)
 {
+    const char *where = "time_sddmm_launches";
     spmv_hip_state *st;
-    double r;
-    if (sddmm_state(h, "time_sddmm_launches", k, ldu, ldv, &st) != SPMV_HIP_OK) return -1.0;
-    if (spmm_columns(h, st, "time_sddmm_launches") != SPMV_HIP_OK) return -1.0;
-    r = spmv_shim_time_sddmm(st->dev, k, U, ldu, V, ldv, Out, warmup, iters, ms_out);
-    if (r < 0) spmv_set_error(SPMV_HIP_E_RUNTIME, "time_sddmm_launches", spmv_shim_error_text());
-    return r;
-}
-
-/* ---------------------------------------------------------------- row softmax over A's pattern, and its backward */
-/* Handle rules shared by spmv_hip_row_softmax, its backward and the timing entry point: sddmm's, without the shape arguments. */
-static int row_softmax_state(spmv_Handle_t h, const char *where, spmv_hip_state **out)
-{
-    return sddmm_state(h, where, 1, 1, 1, out);
+    if (!h || k < 1 || ldu < k || ldv < k) {
+        (void) refuse(SPMV_HIP_E_ARG, where, !h ? "handle is NULL" : "need k >= 1, ldu >= k and ldv >= k");
+        return -1.0;
+    }
+    if (resident_state(h, where, RESIDENT_NOT_REORDERED, &st) || spmm_columns(h, st, where)) return -1.0;
+    return report_time(spmv_shim_time_sddmm(st->dev, k, U, ldu, V, ldv, Out, warmup, iters, ms_out), where);
 }
 
 /* P: S (forward) or P (backward); G: NULL for the forward */
@@ -1085,18 +997,12 @@ static int row_softmax_call(spmv_Handle_t handle, const char *where, int backwar
 {
     spmv_hip_state *st;
     spmv_hip_info info;
-    int rc = row_softmax_state(handle, where, &st);
-    if (rc) return rc;
-    if ((rc = refresh_resident(handle, st, m, RowPtr, ColIdx, Matrix_Val)) != SPMV_HIP_OK) return rc;
-    if (!st->dev) { spmv_set_error(SPMV_HIP_E_NOSTATE, where, "handle has no device state"); return SPMV_HIP_E_NOSTATE; }
-    if (handle->Level_3_opt_used) { spmv_set_error(SPMV_HIP_E_ARG, where, "not available on a reordered handle (option \"reorder\")"); return SPMV_HIP_E_ARG; }
-    if ((rc = spmv_shim_info(st->dev, &info)) != SPMV_HIP_OK) { spmv_set_error(rc, where, spmv_shim_error_text()); return rc; }
+    int rc;
+    if ((rc = resident_prologue(handle, where, RESIDENT_NOT_REORDERED, m, RowPtr, ColIdx, Matrix_Val, &st)) || (rc = report(spmv_shim_info(st->dev, &info), where))) return rc;
     if (info.nnz == 0 || info.m == 0) return SPMV_HIP_OK; /* nothing stored: nothing written */
-    if (!P || !Out || (backward && !G)) { spmv_set_error(SPMV_HIP_E_ARG, where, "a NULL array"); return SPMV_HIP_E_ARG; }
+    if (!P || !Out || (backward && !G)) return refuse(SPMV_HIP_E_ARG, where, "a NULL array");
     /* RowPtr alone is read: a released resident ColIdx copy stays released */
-    rc = backward ? spmv_shim_row_softmax_backward(st->dev, P, G, Out) : spmv_shim_row_softmax(st->dev, P, Out);
-    if (rc) spmv_set_error(rc, where, spmv_shim_error_text());
-    return rc;
+    return report(backward ? spmv_shim_row_softmax_backward(st->dev, P, G, Out) : spmv_shim_row_softmax(st->dev, P, Out), where);
 }
 
 int spmv_hip_row_softmax(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
@@ -1114,9 +1020,6 @@ int spmv_hip_row_softmax_backward(spmv_Handle_t handle, BASIC_INT_TYPE m, const 
 double spmv_hip_time_row_softmax_launches(spmv_Handle_t h, const void *S, void *Out, int warmup, int iters, float *ms_out)
 {
     spmv_hip_state *st;
-    double r;
-    if (row_softmax_state(h, "time_row_softmax_launches", &st) != SPMV_HIP_OK) return -1.0;
-    r = spmv_shim_time_row_softmax(st->dev, S, Out, warmup, iters, ms_out);
-    if (r < 0) spmv_set_error(SPMV_HIP_E_RUNTIME, "time_row_softmax_launches", spmv_shim_error_text());
-    return r;
+    if (resident_state(h, "time_row_softmax_launches", RESIDENT_NOT_REORDERED, &st)) return -1.0;
+    return report_time(spmv_shim_time_row_softmax(st->dev, S, Out, warmup, iters, ms_out), "time_row_softmax_launches");
 }

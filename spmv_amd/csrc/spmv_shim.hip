@@ -173,10 +173,8 @@ extern "C" void spmv_shim_matrix_destroy(spmv_dev *d)
     if (d->rowptr) (void) pool_free(d->rowptr);
     if (d->colidx) (void) pool_free(d->colidx);
     if (d->val) (void) pool_free(d->val);
-    if (d->x_stage) (void) pool_free(d->x_stage);
-    if (d->y_stage) (void) pool_free(d->y_stage);
-    if (d->scratch8) (void) pool_free(d->scratch8);
-    for (void *p : {(void *) d->spmm_split, (void *) d->spmm_longs, d->spmm_x, d->spmm_y, d->sddmm_u, d->sddmm_v, d->sddmm_o, d->rowred_a, d->rowred_g, d->rowred_o}) if (p) (void) pool_free(p);
+    for (void *p : {d->scratch8, (void *) d->spmm_split, (void *) d->spmm_longs}) if (p) (void) pool_free(p);
+    for (StageBuf &b : d->stage) if (b.p) (void) pool_free(b.p);
     delete d;
 }
 
@@ -548,24 +546,15 @@ extern "C" int spmv_shim_run(spmv_dev *d, const void *x, void *y)
     if ((d->n > 0 && d->nnz > 0 && !x) || (d->m > 0 && !y)) return fail(SPMV_HIP_E_ARG, "run: X or Y is NULL");
     DeviceGuard guard(d->device); // the caller's current device is restored on return
     if (!guard.ok) return fail(SPMV_HIP_E_RUNTIME, "hipSetDevice(%d) failed", d->device);
-    const bool xdev = is_device_ptr(x), ydev = is_device_ptr(y);
+    Stager stg{d}; // host x / y: staged through HBM (correct, PCIe-bound)
     const void *xd = x;
     void *yd = y;
-    if (!xdev && d->n > 0 && x) { // host x: stage through HBM (correct, PCIe-bound)
-        if (!d->x_stage) ALLOC_TRY(d, &d->x_stage, d->vsize * (size_t) d->n, false);
-        HIP_TRY(hipMemcpyAsync(d->x_stage, x, d->vsize * (size_t) d->n, hipMemcpyHostToDevice, d->stream));
-        xd = d->x_stage;
-    }
-    if (!ydev && d->m > 0) {
-        if (!d->y_stage) ALLOC_TRY(d, &d->y_stage, d->vsize * (size_t) d->m, false);
-        yd = d->y_stage;
-    }
-    int rc = d->vsize == sizeof(double) ? launch<double>(d, (const double *) xd, (double *) yd)
-                                        : launch<float>(d, (const float *) xd, (float *) yd);
-    if (rc) return rc;
-    if (!ydev && d->m > 0) HIP_TRY(hipMemcpyAsync(y, d->y_stage, d->vsize * (size_t) d->m, hipMemcpyDeviceToHost, d->stream));
-    if (!d->async || !xdev || !ydev) HIP_TRY(hipStreamSynchronize(d->stream));
-    return SPMV_HIP_OK;
+    long long ld = 1;
+    int rc;
+    if ((rc = stg.in(d->stage[STAGE_X], xd, ld, (size_t) d->n, 1)) || (rc = stg.out(d->stage[STAGE_Y], yd, ld, (size_t) d->m, 1))) return rc;
+    rc = d->vsize == sizeof(double) ? launch<double>(d, (const double *) xd, (double *) yd)
+                                    : launch<float>(d, (const float *) xd, (float *) yd);
+    return rc ? rc : stg.finish();
 }
 
 extern "C" int spmv_shim_set_stream(spmv_dev *d, void *stream)
@@ -598,34 +587,7 @@ extern "C" double spmv_shim_time(spmv_dev *d, const void *x, void *y, int warmup
 {
     if (!d || !d->built || iters <= 0) { fail(SPMV_HIP_E_ARG, "time: bad arguments"); return -1.0; }
     if (!is_device_ptr(x) || !is_device_ptr(y)) { fail(SPMV_HIP_E_ARG, "time: x and y must be device pointers"); return -1.0; }
-    const int keep_async = d->async;
-    d->async = 1;
-    std::vector<hipEvent_t> ev((size_t) iters + 1);
-    for (auto &e : ev) if (hipEventCreate(&e) != hipSuccess) { d->async = keep_async; fail(SPMV_HIP_E_RUNTIME, "hipEventCreate"); return -1.0; }
-    int rc = SPMV_HIP_OK;
-    for (int i = 0; i < warmup && !rc; ++i) rc = spmv_shim_run(d, x, y);
-    for (int i = 0; i < iters && !rc; ++i) {
-        (void) hipEventRecord(ev[i], d->stream);
-        rc = spmv_shim_run(d, x, y);
-    }
-    (void) hipEventRecord(ev[iters], d->stream);
-    hipError_t e = hipStreamSynchronize(d->stream);
-    d->async = keep_async;
-    double mean = -1.0;
-    if (!rc && e == hipSuccess) {
-        double tot = 0;
-        for (int i = 0; i < iters; ++i) {
-            float ms = 0;
-            (void) hipEventElapsedTime(&ms, ev[i], ev[i + 1]);
-            if (ms_out) ms_out[i] = ms;
-            tot += ms;
-        }
-        mean = tot / iters;
-    } else if (e != hipSuccess) {
-        fail(SPMV_HIP_E_RUNTIME, "time: %s", hipGetErrorString(e));
-    }
-    for (auto &v : ev) (void) hipEventDestroy(v);
-    return mean;
+    return time_events(d, "time", warmup, iters, ms_out, [&] { return spmv_shim_run(d, x, y); });
 }
 
 // min over `iters` launches of the built schedule on scratch vectors (x = 1): what the measured automatic
