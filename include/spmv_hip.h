@@ -202,6 +202,44 @@ int spmv_hip_row_softmax(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT
 int spmv_hip_row_softmax_backward(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
                                   const void *Matrix_Val, const void *P, const void *G, void *Out);
 
+/* ---- sparse attention in one pass: O = softmax_rows(scale * Q K^T on A's pattern) V ---------------
+ * O[i*ldo + c] = sum over the stored entries p of row i of P_p * V[j_p*ldv + c] for c < dv, where j_p = ColIdx[p],
+ * P = softmax over row i of t_p = scale * sum over c < k of Q[i*ldq + c] * K[j_p*ldk + c].  Q is m x k, K is n x k, V is n x dv, O is m x dv,
+ * ROW-MAJOR with leading dimensions ldq, ldk >= k and ldv, ldo >= dv, in the handle's precision; each may be a host or a device pointer; K
+ * and V may be the same pointer; O must not overlap an input.  `scale` is converted once to the handle's precision.  A's VALUES are not
+ * read, and the handle's resident values are NOT MODIFIED: spmv() before and after computes the same.  This is the composition
+ * spmv_hip_sddmm, * scale, spmv_hip_row_softmax, spmv_hip_spmm (values = P) without the scores or P ever stored in the caller's memory --
+ * and with the composition's bits.  Returns 0 or an SPMV_HIP_E_* code.
+ *   - The CSR arguments follow spmv()'s rules (another matrix is re-inspected first).  Split and cache-blocked handles use the resident
+ *     CSR itself.  Option "reorder" handles return SPMV_HIP_E_ARG: the resident matrix is P A P^T.
+ *   - Writes: exactly the first dv elements of each of the m rows of O; a row without entries gets dv zeros (+0); the padding of Q, K, V
+ *     and O is never read or written; offsets are 64-bit.  m = 0 writes nothing; nnz = 0 writes the zeros.
+ *   - Arithmetic and order -- the composition's, step by step, so the result is a function of the matrix, k, dv and the value type alone
+ *     (not of ld, alignment, access width, host / device pointers, stream and async settings, the handle's method, run to run):
+ *       1. s_p is the dot in spmv_hip_sddmm's order for this k (above).
+ *       2. t_p = s_p * scale: one plain multiplication.
+ *       3. M_i, Z_i and P_p = exp(t_p - M_i) / Z_i are spmv_hip_row_softmax's: its order by row length, exp / expf of the device math
+ *          library, one subtraction and one division.
+ *       4. O[i, c] is spmv_hip_spmm's chain.  Rows of up to 512 entries: acc = +0, then acc = fma(P_p, V[j_p, c], acc) in CSR order.  Longer
+ *          rows: 64 segments of ceil(len / 64) entries, each chained from +0, the partial sums added left to right.
+ *     No other operation is contracted.  Special values follow from these steps: a NaN, a +inf or only -inf among a row's scores makes that
+ *     row of O NaN, and only that row; a -inf beside finite scores weighs its V row with an exact +0.
+ *   - One launch for the rows of up to 512 entries (a wavefront per batch of whole rows; scores and P live in LDS) and one for the longer
+ *     rows (a workgroup each; their scores are parked in a handle-owned array of sum-of-their-lengths elements).  No floating-point atomics;
+ *     no workgroup waits on another.
+ *   - The handle's stream and async setting apply as for spmv(); host Q / K / V / O are staged through handle-owned HBM buffers (m*k, n*k,
+ *     n*dv and m*dv elements) allocated at first use; with the batch table and the long-row list (shared with spmv_hip_spmm) and the long
+ *     rows' parking space they are counted in spmv_hip_info.device_bytes and freed at destroy / clear / re-inspection.
+ *   - Column indices: as for spmv_hip_spmm -- when create() released the resident ColIdx copy (option "keep_columns" = 0), the first call
+ *     copies it back from the create-time array: device_bytes grows by 4 B per non-zero from then on, spmv() is unchanged.
+ *   - Errors (SPMV_HIP_E_ARG, O untouched): a NULL handle; k < 1, dv < 1, ldq < k, ldk < k, ldv < dv, ldo < dv; a NULL Q, K, V or O while
+ *     m > 0; multi-GPU, host_rows and "reorder" handles.  A cleared or failed handle: SPMV_HIP_E_NOSTATE.  Every failure is also reported
+ *     through spmv_hip_last_error(). */
+int spmv_hip_attention(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                       const void *Matrix_Val, int k, int dv, double scale,
+                       const void *Q, long long ldq, const void *K, long long ldk, const void *V, long long ldv,
+                       void *O, long long ldo);
+
 /* ---- options --------------------------------------------------------------------------------
  * Resolved once per handle, at create: process-wide value (spmv_hip_set_option / env), overridden by the
  * calling thread's value (spmv_hip_set_thread_option) -- so two threads can create differently tuned handles

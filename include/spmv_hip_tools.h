@@ -33,6 +33,9 @@ double spmv_hip_time_sddmm_launches(spmv_Handle_t handle, int k, const void *U, 
                                     int warmup, int iters, float *ms_out);
 /* The same for spmv_hip_row_softmax (S and Out: nnz elements, DEVICE pointers; Out may be S). */
 double spmv_hip_time_row_softmax_launches(spmv_Handle_t handle, const void *S, void *Out, int warmup, int iters, float *ms_out);
+/* The same for spmv_hip_attention (Q: m x k, K: n x k, V: n x dv, O: m x dv; DEVICE pointers). */
+double spmv_hip_time_attention_launches(spmv_Handle_t handle, int k, int dv, double scale, const void *Q, long long ldq, const void *K, long long ldk,
+                                        const void *V, long long ldv, void *O, long long ldo, int warmup, int iters, float *ms_out);
 /* copies the built transpose map to host: rowptr_t (n+1 entries) and perm (nnz entries: perm[p] = CSR index in A of the entry at
    position p of A^T's CSR); either may be NULL.  SPMV_HIP_E_NOSTATE until the transpose is built. */
 int spmv_hip_transpose_map(spmv_Handle_t handle, int *rowptr_t, int *perm);

@@ -121,6 +121,10 @@ FUNCTIONS = {
     "spmv_hip_row_softmax": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, _V, _V]),
     "spmv_hip_row_softmax_backward": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, _V, _V, _V]),
     "spmv_hip_time_row_softmax_launches": (C.c_double, [spmv_Handle_t, _V, _V, C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "spmv_hip_attention": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong,
+                                     _V, C.c_longlong]),
+    "spmv_hip_time_attention_launches": (C.c_double, [spmv_Handle_t, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong,
+                                                      _V, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_float)]),
     # include/spmv_io.h (host only)
     "spmv_io_read_mtx": (C.c_int, [C.c_char_p, C.c_size_t, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_V)]),
     "spmv_io_cache_path": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t]),
@@ -424,6 +428,30 @@ def time_row_softmax_launches(handle, S, Out, warmup=10, iters=100):
     return _timed("spmv_hip_time_row_softmax_launches", (handle, _ptr(S), _ptr(Out)), warmup, iters)
 
 
+def _attention_blocks(Q, K, V, O):
+    """-> (k, dv, pq, ldq, pk, ldk, pv, ldv, po, ldo) of the four 2-D blocks of an attention call (_blocks: Q and K share k, V and O share dv)"""
+    k, pq, ldq, pk, ldk = _blocks(Q, "Q", K, "K")
+    dv, pv, ldv, po, ldo = _blocks(V, "V", O, "O")
+    return k, dv, pq, ldq, pk, ldk, pv, ldv, po, ldo
+
+
+def attention(handle, m, RowPtr, ColIdx, Matrix_Val, Q, K, V, O, scale=None, check=True):
+    """O = softmax_rows(scale * Q K^T on the handle's pattern) V in one pass (spmv_hip_attention).  Q (m x k), K (n x k), V (n x dv) and O
+    (m x dv): 2-D numpy arrays or torch tensors with column stride 1 (row strides are passed as leading dimensions); scale None means
+    1 / sqrt(k).  The handle's values are neither read nor changed.  -> the return code."""
+    k, dv, pq, ldq, pk, ldk, pv, ldv, po, ldo = _attention_blocks(Q, K, V, O)
+    scale = 1.0 / np.sqrt(k) if scale is None and k > 0 else (0.0 if scale is None else scale)
+    return _checked(load().spmv_hip_attention(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), k, dv, float(scale), pq, ldq, pk, ldk, pv, ldv, po, ldo),
+                    "spmv_hip_attention", check)
+
+
+def time_attention_launches(handle, Q, K, V, O, scale=None, warmup=10, iters=100):
+    """-> (mean_ms, per-call ms array) of spmv_hip_attention on device Q / K / V / O (spmv_hip_time_attention_launches)."""
+    k, dv, pq, ldq, pk, ldk, pv, ldv, po, ldo = _attention_blocks(Q, K, V, O)
+    scale = 1.0 / np.sqrt(k) if scale is None else scale
+    return _timed("spmv_hip_time_attention_launches", (handle, k, dv, float(scale), pq, ldq, pk, ldk, pv, ldv, po, ldo), warmup, iters)
+
+
 def _take_csr(m, n, nnz, rp, ci, va, dtype):
     """Copy malloc'ed C arrays into numpy arrays and free the C side."""
     from .synth import CSR
@@ -576,6 +604,16 @@ class Handle:
             out = self._like(P, (self.nnz,))
         rp, ci, va = self._keep
         row_softmax_backward(self.h, self.m, rp, ci, va, P, G, out)
+        return out
+
+    def attention(self, Q, K, V, scale=None, out=None):
+        """out = softmax_rows(scale * Q K^T on the pattern) V in one pass (spmv_hip_attention) for 2-D Q (m x k), K (n x k) and V (n x dv); scale
+        None means 1 / sqrt(k); out (m x dv) is allocated like Q -- same kind, dtype and device -- when None.  The handle's values are not
+        used and not changed."""
+        if out is None:
+            out = self._like(Q, (self.m, V.shape[1]))
+        rp, ci, va = self._keep
+        attention(self.h, self.m, rp, ci, va, Q, K, V, out, scale)
         return out
 
     def update_values(self, val):

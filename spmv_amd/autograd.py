@@ -19,9 +19,14 @@ backward  Handle.spmm_transpose(G)         dL/dX = A^T G
 With matmul(handle, X, values=P) after them, softmax_rows(Q K^T on A's pattern) X -- graph attention, masked attention -- runs on the
 library's kernels forward and backward (Handle.sddmm / row_softmax / spmm; Handle.row_softmax_backward, spmm, spmm_transpose, sddmm).
 
+    O = spmv_amd.autograd.attention(handle, Q, K, V, scale=None)   the same in ONE forward pass (Handle.attention): no nnz-sized array is
+                                                                   written or saved, and the handle's values are not touched
+
 Every call runs on torch's current stream.  The only module of the package that needs torch; libspmv_hip.so has no torch dependency.
 """
 from __future__ import annotations
+
+import math
 
 import torch
 from torch.autograd.function import once_differentiable
@@ -214,3 +219,71 @@ def sddmm(handle, U, V):
     if U.dim() != 2 or V.dim() != 2 or U.shape[0] != handle.m or V.shape[0] != handle.n or U.shape[1] != V.shape[1] or U.shape[1] < 1:
         raise ValueError(f"U must be ({handle.m}, k) and V ({handle.n}, k) with k >= 1, not {tuple(U.shape)} and {tuple(V.shape)}")
     return _Sddmm.apply(handle, U, V)
+
+
+class _Attention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, handle, Q, K, V, scale):
+        Q2, K2, V2 = _block(Q.detach(), Q.shape[1]), _block(K.detach(), K.shape[1]), _block(V.detach(), V.shape[1])
+        _on_current_stream(handle)
+        O = handle.attention(Q2, K2, V2, scale)
+        ctx.handle, ctx.scale = handle, scale
+        ctx.save_for_backward(Q2, K2, V2)   # nothing nnz-sized: the backward pass computes S and P again
+        return O
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, G):
+        handle, scale = ctx.handle, ctx.scale
+        Q2, K2, V2 = ctx.saved_tensors
+        need_q, need_k, need_v = ctx.needs_input_grad[1:4]
+        dQ = dK = dV = None
+        if not (need_q or need_k or need_v):
+            return None, None, None, None, None
+        if handle.nnz == 0:   # no stored entry: O is zero whatever Q, K and V are
+            return None, (torch.zeros_like(Q2) if need_q else None), (torch.zeros_like(K2) if need_k else None), (torch.zeros_like(V2) if need_v else None), None
+        _on_current_stream(handle)
+        G2 = _block(G, G.shape[1])
+        S = handle.sddmm(Q2, K2)
+        S.mul_(scale)
+        P = handle.row_softmax(S, out=S)
+        # A_P, then A_dS = A's pattern with those values, for the duration: the handle's own values, and what matmul() remembers of them, come back below
+        keep, token, ref = handle._keep[2], getattr(handle, "_values_token", None), getattr(handle, "_values_ref", None)
+        try:
+            if need_v:
+                handle.update_values(P)
+                dV = handle.spmm_transpose(G2)
+            if need_q or need_k:
+                dP = handle.sddmm(G2, V2)
+                dS = handle.row_softmax_backward(P, dP, out=dP)
+                dS.mul_(scale)
+                handle.update_values(dS)
+                if need_q:
+                    dQ = handle.spmm(K2)
+                if need_k:
+                    dK = handle.spmm_transpose(Q2)
+        finally:
+            handle.update_values(keep)
+            handle._values_token, handle._values_ref = token, ref
+        return None, dQ, dK, dV, None
+
+
+def attention(handle, Q, K, V, scale=None):
+    """O = softmax_rows(scale * Q K^T on the handle's pattern) V (Handle.attention: one fused pass, the bits of
+    matmul(h, V, values=row_softmax(h, sddmm(h, Q, K) * scale))), with gradients for Q, K and V.  Q: (m, k), K: (n, k), V: (n, dv), of the
+    handle's dtype on its device; scale: a Python number, None means 1 / sqrt(k); it receives no gradient.
+
+    The forward pass saves Q, K and V only -- nothing nnz-sized -- and neither reads nor changes the handle's values.  The backward pass
+    computes S and P again (Handle.sddmm, Handle.row_softmax) and composes the existing operations, only for the gradients asked for:
+    dP = sddmm(G, V), dS = row_softmax_backward(P, dP) * scale, dV = A_P^T G, dQ = A_dS K, dK = A_dS^T Q, where A_X is A's pattern holding
+    X as values.  That costs up to three Handle.update_values per backward pass: one for P when dV is asked for, one for dS when dQ or dK is,
+    and one that puts the previous values back -- the array the handle held, and what matmul() remembers about it -- so a later
+    matmul(handle, X) and Handle.spmv / spmv_transpose multiply what they did before."""
+    _check_handle(handle)
+    for t, name in ((Q, "Q"), (K, "K"), (V, "V")):
+        _check_tensor(t, name, handle)
+    if Q.dim() != 2 or K.dim() != 2 or V.dim() != 2 or Q.shape[0] != handle.m or K.shape[0] != handle.n or V.shape[0] != handle.n or \
+            Q.shape[1] != K.shape[1] or Q.shape[1] < 1 or V.shape[1] < 1:
+        raise ValueError(f"Q must be ({handle.m}, k), K ({handle.n}, k) and V ({handle.n}, dv) with k, dv >= 1, not {tuple(Q.shape)}, {tuple(K.shape)} and {tuple(V.shape)}")
+    scale = 1.0 / math.sqrt(Q.shape[1]) if scale is None else float(scale)   # Handle.attention's default, to the bit
+    return _Attention.apply(handle, Q, K, V, scale)

@@ -1,0 +1,95 @@
+// shim/attention.hpp -- part of spmv_shim.hip: O = softmax_rows(scale * Q K^T on the RESIDENT pattern) V in one pass (spmv_hip_attention).  The
+// kernels are kernels/attention.hpp, launched from their own translation unit (spmv_attention.hip, attention_launch); the tables are spmm's
+// batch table and long-row list (spmm_plan).  This side adds what the long rows need: where each one parks its scores.
+#pragma once
+
+// long_off[i] = first element of long row i of spmm's list in att_park (sum of the long rows' lengths elements): built once per resident matrix
+static int attention_plan(spmv_dev *d)
+{
+    if (d->att_planned) return SPMV_HIP_OK;
+    const int nlong = d->spmm_nlong;
+    if (nlong > 0) {
+        const size_t off_bytes = sizeof(int) * ((size_t) nlong + 1);
+        int *off = nullptr;
+        void *park = nullptr;
+        int rc = dev_alloc(d, (void **) &off, off_bytes, false);
+        if (rc) return rc;
+        auto bail = [&](int code) {
+            quiesce(d);
+            (void) pool_free(off);
+            d->device_bytes -= (long long) off_bytes;
+            return code;
+        };
+        std::vector<int> host((size_t) nlong + 1, 0);
+        attention_long_len_kernel<<<grid_for(nlong, kBlock, d->cus * 8), kBlock, 0, d->stream>>>(nlong, d->spmm_longs, d->rowptr, off);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(host.data(), off, sizeof(int) * (size_t) nlong, hipMemcpyDeviceToHost, d->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
+        if (e != hipSuccess) { (void) hipGetLastError(); return bail(fail(SPMV_HIP_E_RUNTIME, "attention: long-row lengths: %s", hipGetErrorString(e))); }
+        long long total = 0; // at most nnz < INT_MAX
+        for (int i = 0; i <= nlong; ++i) {
+            const int len = host[(size_t) i];
+            host[(size_t) i] = (int) total;
+            total += len;
+        }
+        e = hipMemcpyAsync(off, host.data(), off_bytes, hipMemcpyHostToDevice, d->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
+        if (e != hipSuccess) { (void) hipGetLastError(); return bail(fail(SPMV_HIP_E_RUNTIME, "attention: long-row offsets: %s", hipGetErrorString(e))); }
+        if ((rc = dev_alloc(d, &park, d->vsize * (size_t) total, false))) return bail(rc);
+        d->att_off = off;
+        d->att_park = park;
+    }
+    d->att_planned = true;
+    return SPMV_HIP_OK;
+}
+
+extern "C" int spmv_shim_attention(spmv_dev *d, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v, long long ldv, void *o,
+                                   long long ldo)
+{
+    if (!d || !d->built) return fail(SPMV_HIP_E_NOSTATE, "attention: schedule not built");
+    if (k < 1 || dv < 1 || ldq < k || ldk < k || ldv < dv || ldo < dv)
+        return fail(SPMV_HIP_E_ARG, "attention: need k >= 1, dv >= 1, ldq >= k, ldk >= k, ldv >= dv, ldo >= dv (k = %d, dv = %d, ld = %lld, %lld, %lld, %lld)", k, dv, ldq, ldk, ldv, ldo);
+    if (d->m > 0 && (!q || !kk || !v || !o)) return fail(SPMV_HIP_E_ARG, "attention: Q, K, V or O is NULL");
+    if (d->nnz > 0 && !d->colidx) return fail(SPMV_HIP_E_NOSTATE, "attention: the resident column indices were released (spmv_shim_restore_columns first)");
+    if (d->m == 0) return SPMV_HIP_OK;
+    DeviceGuard guard(d->device);
+    if (!guard.ok) return fail(SPMV_HIP_E_RUNTIME, "hipSetDevice(%d) failed", d->device);
+    int rc;
+    if ((rc = spmm_plan(d)) || (rc = attention_plan(d))) return rc;
+    const size_t s = d->vsize;
+    Stager stg{d};
+    AttentionArgs a;
+    a.m = d->m;
+    a.k = k;
+    a.dv = dv;
+    a.nb = d->spmm_nb;
+    a.nlong = d->spmm_nlong;
+    a.cus = d->cus;
+    a.split = d->spmm_split;
+    a.longs = d->spmm_longs;
+    a.rowptr = d->rowptr;
+    a.colidx = d->colidx;
+    a.long_off = d->att_off;
+    a.park = d->att_park;
+    a.scale = scale;
+    a.q = q; a.ldq = ldq;
+    a.kk = kk; a.ldk = ldk;
+    a.v = v; a.ldv = ldv;
+    a.o = o; a.ldo = ldo;
+    // every row of O gets its dv elements, empty rows their zeros: a staged result is written completely before it is copied back
+    if ((rc = stg.in(d->stage[STAGE_ATT_Q], a.q, a.ldq, (size_t) d->m, k)) || (rc = stg.in(d->stage[STAGE_ATT_K], a.kk, a.ldk, (size_t) d->n, k)) ||
+        (rc = stg.in(d->stage[STAGE_ATT_V], a.v, a.ldv, (size_t) d->n, dv)) || (rc = stg.out(d->stage[STAGE_ATT_O], a.o, a.ldo, (size_t) d->m, dv))) return rc;
+    // the access width changes no bit (kernels/attention.hpp): chosen per call from what the addresses allow
+    a.vec = wide_ok(a.q, a.ldq, s) && wide_ok(a.kk, a.ldk, s) && wide_ok(a.v, a.ldv, s) && wide_ok(a.o, a.ldo, s);
+    const hipError_t e = attention_launch(a, s == sizeof(double), d->stream);
+    if (e != hipSuccess) return fail(SPMV_HIP_E_RUNTIME, "attention: launch: %s", hipGetErrorString(e));
+    return stg.finish();
+}
+
+extern "C" double spmv_shim_time_attention(spmv_dev *d, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v, long long ldv,
+                                           void *o, long long ldo, int warmup, int iters, float *ms_out)
+{
+    if (!d || !d->built || iters <= 0) { fail(SPMV_HIP_E_ARG, "time_attention: bad arguments"); return -1.0; }
+    if (!is_device_ptr(q) || !is_device_ptr(kk) || !is_device_ptr(v) || !is_device_ptr(o)) { fail(SPMV_HIP_E_ARG, "time_attention: Q, K, V and O must be device pointers"); return -1.0; }
+    return time_events(d, "time_attention", warmup, iters, ms_out, [&] { return spmv_shim_attention(d, k, dv, scale, q, ldq, kk, ldk, v, ldv, o, ldo); });
+}

@@ -186,7 +186,8 @@ struct BlkSet {
 // The handle-owned HBM buffer behind one host operand of one operation: allocated at the first call that passes that operand from the host,
 // given back and allocated anew when a later call needs more, counted in device_bytes, freed with the device state.
 struct StageBuf { void *p = nullptr; size_t bytes = 0; };
-enum { STAGE_X, STAGE_Y, STAGE_SPMM_X, STAGE_SPMM_Y, STAGE_SDDMM_U, STAGE_SDDMM_V, STAGE_SDDMM_O, STAGE_ROWRED_A, STAGE_ROWRED_G, STAGE_ROWRED_O, STAGE_COUNT };
+enum { STAGE_X, STAGE_Y, STAGE_SPMM_X, STAGE_SPMM_Y, STAGE_SDDMM_U, STAGE_SDDMM_V, STAGE_SDDMM_O, STAGE_ROWRED_A, STAGE_ROWRED_G, STAGE_ROWRED_O,
+       STAGE_ATT_Q, STAGE_ATT_K, STAGE_ATT_V, STAGE_ATT_O, STAGE_COUNT };
 
 struct spmv_dev {
     int device = 0;
@@ -266,6 +267,10 @@ struct spmv_dev {
     bool spmm_planned = false;
     int spmm_nb = 0, spmm_nlong = 0;
     int *spmm_split = nullptr, *spmm_longs = nullptr;
+    // spmv_hip_attention (shim/attention.hpp): where every long row of spmm's list parks its scores, built at the first call
+    bool att_planned = false;
+    int *att_off = nullptr;   // [spmm_nlong + 1] first element of each long row in att_park
+    void *att_park = nullptr; // sum of the long rows' lengths elements
     // spmv_hip_spmv_transpose (shim/transpose.hpp): A^T as a matrix of its own (n x m), planned and built like any; perm[p] = our index of its entry p.
     // val_gen counts spmv_shim_update_values calls; A^T's values are gathered again when tr_gen falls behind it.
     spmv_dev *tr = nullptr;

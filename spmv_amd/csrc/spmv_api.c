@@ -783,7 +783,7 @@ double spmv_hip_time_launches(spmv_Handle_t h, const void *x, void *y, int warmu
 }
 
 /* ---------------------------------------------------------------- operations on the resident matrix: one gate, one prologue
- * spmm, the transposed multiplies, sddmm, the row softmax and their timers work on the single-GPU resident matrix.  An entry point is: its own
+ * spmm, the transposed multiplies, sddmm, the row softmax, the fused attention and their timers work on the single-GPU resident matrix.  An entry point is: its own
  * argument rules -- a NULL handle and a bad k / ld are E_ARG before the handle's state is looked at --, the gate or the prologue, the tables it
  * needs (columns, transpose), the shim call through report().  Where an entry point checks its operands for NULL is its own business and differs. */
 #define RESIDENT_NOT_REORDERED 1 /* the entries are addressed in the caller's CSR order: the resident P A P^T of option "reorder" has another */
@@ -1022,4 +1022,35 @@ double spmv_hip_time_row_softmax_launches(spmv_Handle_t h, const void *S, void *
     spmv_hip_state *st;
     if (resident_state(h, "time_row_softmax_launches", RESIDENT_NOT_REORDERED, &st)) return -1.0;
     return report_time(spmv_shim_time_row_softmax(st->dev, S, Out, warmup, iters, ms_out), "time_row_softmax_launches");
+}
+
+/* ---------------------------------------------------------------- O = softmax_rows(scale * Q K^T on A's pattern) V in one pass */
+static int attention_args(spmv_Handle_t h, const char *where, int k, int dv, const void *Q, long long ldq, const void *K, long long ldk, const void *V, long long ldv,
+                          const void *O, long long ldo, int m)
+{
+    if (!h) return refuse(SPMV_HIP_E_ARG, where, "handle is NULL");
+    if (k < 1 || dv < 1 || ldq < k || ldk < k || ldv < dv || ldo < dv) return refuse(SPMV_HIP_E_ARG, where, "need k >= 1, dv >= 1, ldq >= k, ldk >= k, ldv >= dv and ldo >= dv");
+    if (m > 0 && (!Q || !K || !V || !O)) return refuse(SPMV_HIP_E_ARG, where, "Q, K, V or O is NULL");
+    return SPMV_HIP_OK;
+}
+
+int spmv_hip_attention(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                       const void *Matrix_Val, int k, int dv, double scale,
+                       const void *Q, long long ldq, const void *K, long long ldk, const void *V, long long ldv,
+                       void *O, long long ldo)
+{
+    spmv_hip_state *st;
+    int rc;
+    if ((rc = attention_args(handle, "attention", k, dv, Q, ldq, K, ldk, V, ldv, O, ldo, m)) ||
+        (rc = resident_prologue(handle, "attention", RESIDENT_NOT_REORDERED, m, RowPtr, ColIdx, Matrix_Val, &st)) || (rc = spmm_columns(handle, st, "attention"))) return rc;
+    return report(spmv_shim_attention(st->dev, k, dv, scale, Q, ldq, K, ldk, V, ldv, O, ldo), "attention");
+}
+
+double spmv_hip_time_attention_launches(spmv_Handle_t h, int k, int dv, double scale, const void *Q, long long ldq, const void *K, long long ldk, const void *V, long long ldv,
+                                        void *O, long long ldo, int warmup, int iters, float *ms_out)
+{
+    const char *where = "time_attention_launches";
+    spmv_hip_state *st;
+    if (attention_args(h, where, k, dv, Q, ldq, K, ldk, V, ldv, O, ldo, 1) || resident_state(h, where, RESIDENT_NOT_REORDERED, &st) || spmm_columns(h, st, where)) return -1.0;
+    return report_time(spmv_shim_time_attention(st->dev, k, dv, scale, Q, ldq, K, ldk, V, ldv, O, ldo, warmup, iters, ms_out), where);
 }

@@ -134,6 +134,15 @@ int spmv_shim_row_softmax_backward(spmv_dev *d, const void *p, const void *g, vo
 /* `iters` forward launches timed with events on the handle's stream (device S / Out); mean ms, < 0 on failure */
 double spmv_shim_time_row_softmax(spmv_dev *d, const void *s, void *out, int warmup, int iters, float *ms_out);
 
+/* ---- O = softmax_rows(scale * Q K^T on the resident pattern) V in one pass (shim/attention.hpp; spmv_hip_attention) ----
+ * Q m x k, K n x k, V n x dv, O m x dv, row-major with leading dimensions; host or device pointers each.  Needs the resident ColIdx; the
+ * resident values are neither read nor written.  Builds spmm's tables and the long rows' parking space at the first call. */
+int spmv_shim_attention(spmv_dev *d, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v, long long ldv, void *o,
+                        long long ldo);
+/* `iters` calls timed with events on the handle's stream (device Q / K / V / O); mean ms, < 0 on failure */
+double spmv_shim_time_attention(spmv_dev *d, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v, long long ldv, void *o,
+                                long long ldo, int warmup, int iters, float *ms_out);
+
 /* the resident CSR arrays (device pointers; ColIdx may be NULL after spmv_shim_release_columns) */
 void spmv_shim_matrix_arrays(const spmv_dev *d, const int **rowptr, const int **colidx, const void **val);
 
