@@ -240,6 +240,54 @@ int spmv_hip_attention(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_T
                        const void *Q, long long ldq, const void *K, long long ldk, const void *V, long long ldv,
                        void *O, long long ldo);
 
+/* ---- the gradients of spmv_hip_attention in two passes over A: dQ, dK, dV -----------------------
+ * With G = dL/dO (m x dv) and t_p, P_p as in spmv_hip_attention:  dP_p = sum over c < dv of G[i*ldg + c] * V[j_p*ldv + c],
+ * D_i = sum over row i of P_q dP_q,  dS_p = P_p (dP_p - D_i) scale,  dQ = A_dS K (m x k),  dK = A_dS^T Q (n x k),  dV = A_P^T G (n x dv), where A_X
+ * is A's pattern holding X as values.  All operands are ROW-MAJOR with leading dimensions (ldq, ldk, lddq, lddk >= k; ldv, ldg, lddv >= dv),
+ * in the handle's precision; each may be a host or a device pointer; K and V may be the same pointer; no output may overlap an input or
+ * another output.  A NULL output means "not wanted": nothing is computed for it; when dK and dV are both NULL the transpose is neither built
+ * nor read; when all three are NULL the call returns 0 after argument checking.  A's VALUES are not read, and the handle's resident values are
+ * NOT MODIFIED: spmv(), spmv_hip_spmv_transpose() and spmv_hip_spmm compute the same before and after.  This is the composition
+ * spmv_hip_sddmm, * scale, spmv_hip_row_softmax, spmv_hip_sddmm(G, V), spmv_hip_row_softmax_backward, * scale, spmv_hip_spmm (values dS),
+ * spmv_hip_spmm_transpose (values P, values dS) without a single update of the handle's values -- and with the composition's bits.
+ * Returns 0 or an SPMV_HIP_E_* code.
+ *   - The CSR arguments follow spmv()'s rules (another matrix is re-inspected first).  Option "reorder" handles return SPMV_HIP_E_ARG.
+ *   - Writes: exactly the first k (dQ, dK) or dv (dV) elements of each row of each requested output; padding is never read or written.  Empty
+ *     rows of A give +0 rows of dQ, empty columns +0 rows of dK and dV; nnz = 0 writes those zeros; m = 0 writes nothing to dQ and n zero rows
+ *     to dK and dV (spmv_hip_spmm_transpose's rule).
+ *   - Arithmetic and order -- the composition's, step by step, so the result is a function of the matrix, k, dv and the value type alone
+ *     (not of ld, alignment, access width, host / device pointers, stream and async settings, the handle's method, which outputs are wanted):
+ *       1. t_p and P_p are exactly spmv_hip_attention's steps 1-3.
+ *       2. dP_p is the dot of G[i, :dv] and V[j_p, :dv] in spmv_hip_sddmm's order for dv columns.
+ *       3. D_i is spmv_hip_row_softmax_backward's sum by row length: the first term a plain product, every further one fma(P, dP, chain), then
+ *          its tree.
+ *       4. dS_p = P_p * (dP_p - D_i): one subtraction and one multiplication; then * scale, one more plain multiplication.
+ *       5. dQ[i, c] is spmv_hip_spmm's chain with values dS and X = K (the k > 1 / ld > 1 executor, also when k = 1): rows of up to 512 entries
+ *          chain from +0 in CSR order, longer rows use 64 segments added left to right.
+ *       6. dV[j, c] and dK[j, c] are spmv_hip_spmm_transpose's chain on the handle's device-built transpose: row j of A^T lists its entries in
+ *          ascending row of A, then CSR order; dV uses values P and X = G, dK values dS and X = Q; the 512 / 64-segment rule applies to the
+ *          column's length.
+ *     No other operation is contracted.
+ *   - Two passes.  Over A's rows: one launch for the rows of up to 512 entries (a wavefront per batch of whole rows; t, P, dP and dS live in
+ *     LDS) and one for the longer rows (a workgroup each); they compute dQ and leave P and dS in two handle-owned arrays of nnz elements
+ *     each.  Over A^T's rows, only when dK or dV is wanted: ceil(max(k, dv) / KP) launches (KP = 16 fp64 / 32 fp32) per length class, each
+ *     gathering P and dS through the transpose's index map for panel r of both outputs.  No floating-point atomics; no workgroup waits on
+ *     another; no scratch memory.
+ *   - Memory: the two nnz-sized arrays are allocated at the first call, the transpose (as for spmv_hip_spmm_transpose; its values are not
+ *     read) at the first call that wants dK or dV; host operands are staged through handle-owned HBM buffers allocated at first use.  All are
+ *     counted in spmv_hip_info.device_bytes and freed at destroy / clear / re-inspection.  The handle's stream and async setting apply as for
+ *     spmv().  Column indices: as for spmv_hip_attention.
+ *   - Errors (SPMV_HIP_E_ARG, every output untouched): a NULL handle; k < 1, dv < 1; a leading dimension below its width (of the requested
+ *     outputs only); a NULL Q, K, V or G while m > 0; multi-GPU, host_rows and "reorder" handles.  A cleared or failed handle:
+ *     SPMV_HIP_E_NOSTATE.  Every failure is also reported through spmv_hip_last_error(). */
+int spmv_hip_attention_backward(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                                const void *Matrix_Val, int k, int dv, double scale,
+                                const void *Q, long long ldq, const void *K, long long ldk, const void *V, long long ldv,
+                                const void *G, long long ldg,            /* dL/dO, m x dv */
+                                void *dQ, long long lddq,                /* m x k,  or NULL: not wanted */
+                                void *dK, long long lddk,                /* n x k,  or NULL */
+                                void *dV, long long lddv);               /* n x dv, or NULL */
+
 /* ---- options --------------------------------------------------------------------------------
  * Resolved once per handle, at create: process-wide value (spmv_hip_set_option / env), overridden by the
  * calling thread's value (spmv_hip_set_thread_option) -- so two threads can create differently tuned handles

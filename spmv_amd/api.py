@@ -125,6 +125,11 @@ FUNCTIONS = {
                                      _V, C.c_longlong]),
     "spmv_hip_time_attention_launches": (C.c_double, [spmv_Handle_t, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong,
                                                       _V, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "spmv_hip_attention_backward": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong,
+                                              _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong]),
+    "spmv_hip_time_attention_backward_launches": (C.c_double, [spmv_Handle_t, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong,
+                                                               _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, C.c_int, C.c_int,
+                                                               C.POINTER(C.c_float)]),
     # include/spmv_io.h (host only)
     "spmv_io_read_mtx": (C.c_int, [C.c_char_p, C.c_size_t, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_V)]),
     "spmv_io_cache_path": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t]),
@@ -452,6 +457,42 @@ def time_attention_launches(handle, Q, K, V, O, scale=None, warmup=10, iters=100
     return _timed("spmv_hip_time_attention_launches", (handle, k, dv, float(scale), pq, ldq, pk, ldk, pv, ldv, po, ldo), warmup, iters)
 
 
+def _attention_backward_blocks(Q, K, V, G, dQ, dK, dV):
+    """-> (k, dv, then address and ld of Q, K, V, G, dQ, dK, dV) of an attention_backward call; an output that is None has a NULL address and its
+    width as ld.  Q, K, dQ and dK share k; V, G and dV share dv."""
+    k, pq, ldq, pk, ldk = _blocks(Q, "Q", K, "K")
+    dv, pv, ldv, pg, ldg = _blocks(V, "V", G, "G")
+    out = [k, dv, pq, ldq, pk, ldk, pv, ldv, pg, ldg]
+    for a, name, width in ((dQ, "dQ", k), (dK, "dK", k), (dV, "dV", dv)):
+        if a is None:
+            out += [None, int(width)]
+            continue
+        p, _, w, ld = _block(a, name)
+        if w != width:
+            raise ValueError(f"{name} has {w} columns, expected {width}")
+        out += [p, int(max(ld, 1))]
+    return out
+
+
+def attention_backward(handle, m, RowPtr, ColIdx, Matrix_Val, Q, K, V, G, dQ=None, dK=None, dV=None, scale=None, check=True):
+    """dQ, dK, dV of O = softmax_rows(scale * Q K^T on the handle's pattern) V from G = dL/dO in two passes over A
+    (spmv_hip_attention_backward).  Q (m x k), K (n x k), V (n x dv), G (m x dv) and the outputs dQ (m x k), dK (n x k), dV (n x dv): 2-D numpy
+    arrays or torch tensors with column stride 1 (row strides are passed as leading dimensions); an output that is None is not computed; scale
+    None means 1 / sqrt(k).  The handle's values are neither read nor changed.  -> the return code."""
+    b = _attention_backward_blocks(Q, K, V, G, dQ, dK, dV)
+    k = b[0]
+    scale = 1.0 / np.sqrt(k) if scale is None and k > 0 else (0.0 if scale is None else scale)
+    return _checked(load().spmv_hip_attention_backward(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), b[0], b[1], float(scale), *b[2:]),
+                    "spmv_hip_attention_backward", check)
+
+
+def time_attention_backward_launches(handle, Q, K, V, G, dQ=None, dK=None, dV=None, scale=None, warmup=10, iters=100):
+    """-> (mean_ms, per-call ms array) of spmv_hip_attention_backward on device operands (spmv_hip_time_attention_backward_launches)."""
+    b = _attention_backward_blocks(Q, K, V, G, dQ, dK, dV)
+    scale = 1.0 / np.sqrt(b[0]) if scale is None else scale
+    return _timed("spmv_hip_time_attention_backward_launches", (handle, b[0], b[1], float(scale), *b[2:]), warmup, iters)
+
+
 def _take_csr(m, n, nnz, rp, ci, va, dtype):
     """Copy malloc'ed C arrays into numpy arrays and free the C side."""
     from .synth import CSR
@@ -615,6 +656,18 @@ class Handle:
         rp, ci, va = self._keep
         attention(self.h, self.m, rp, ci, va, Q, K, V, out, scale)
         return out
+
+    def attention_backward(self, Q, K, V, G, scale=None, need=(True, True, True)):
+        """-> (dQ, dK, dV), the gradients of attention(Q, K, V, scale) for G = dL/dO (m x dv), in two passes over A (spmv_hip_attention_backward);
+        need: which of the three are wanted -- the others are None and nothing is computed for them.  The outputs are allocated like Q -- same
+        kind, dtype and device.  The handle's values are not used and not changed."""
+        k, dv = Q.shape[1], V.shape[1]
+        dQ = self._like(Q, (self.m, k)) if need[0] else None
+        dK = self._like(Q, (self.n, k)) if need[1] else None
+        dV = self._like(Q, (self.n, dv)) if need[2] else None
+        rp, ci, va = self._keep
+        attention_backward(self.h, self.m, rp, ci, va, Q, K, V, G, dQ, dK, dV, scale)
+        return dQ, dK, dV
 
     def update_values(self, val):
         """The caller changed the values (in place or in a new array of the same pattern)."""

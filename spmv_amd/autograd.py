@@ -268,7 +268,31 @@ class _Attention(torch.autograd.Function):
         return None, dQ, dK, dV, None
 
 
-def attention(handle, Q, K, V, scale=None):
+class _AttentionFused(torch.autograd.Function):
+    """_Attention's forward; the backward pass is ONE Handle.attention_backward call: the handle's values are never touched"""
+
+    @staticmethod
+    def forward(ctx, handle, Q, K, V, scale):
+        Q2, K2, V2 = _block(Q.detach(), Q.shape[1]), _block(K.detach(), K.shape[1]), _block(V.detach(), V.shape[1])
+        _on_current_stream(handle)
+        O = handle.attention(Q2, K2, V2, scale)
+        ctx.handle, ctx.scale = handle, scale
+        ctx.save_for_backward(Q2, K2, V2)
+        return O
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, G):
+        Q2, K2, V2 = ctx.saved_tensors
+        need = tuple(bool(x) for x in ctx.needs_input_grad[1:4])
+        if not any(need):
+            return None, None, None, None, None
+        _on_current_stream(ctx.handle)
+        dQ, dK, dV = ctx.handle.attention_backward(Q2, K2, V2, _block(G, G.shape[1]), ctx.scale, need=need)
+        return None, dQ, dK, dV, None
+
+
+def attention(handle, Q, K, V, scale=None, backward="composed"):
     """O = softmax_rows(scale * Q K^T on the handle's pattern) V (Handle.attention: one fused pass, the bits of
     matmul(h, V, values=row_softmax(h, sddmm(h, Q, K) * scale))), with gradients for Q, K and V.  Q: (m, k), K: (n, k), V: (n, dv), of the
     handle's dtype on its device; scale: a Python number, None means 1 / sqrt(k); it receives no gradient.
@@ -278,7 +302,14 @@ def attention(handle, Q, K, V, scale=None):
     dP = sddmm(G, V), dS = row_softmax_backward(P, dP) * scale, dV = A_P^T G, dQ = A_dS K, dK = A_dS^T Q, where A_X is A's pattern holding
     X as values.  That costs up to three Handle.update_values per backward pass: one for P when dV is asked for, one for dS when dQ or dK is,
     and one that puts the previous values back -- the array the handle held, and what matmul() remembers about it -- so a later
-    matmul(handle, X) and Handle.spmv / spmv_transpose multiply what they did before."""
+    matmul(handle, X) and Handle.spmv / spmv_transpose multiply what they did before.
+
+    backward="fused" computes the same gradients with ONE Handle.attention_backward call (spmv_hip_attention_backward: two passes over A, P
+    and dS in handle-owned arrays): no Handle.update_values, the handle multiplies the same matrix throughout.  The gradients have the
+    composition's bits whenever k > 1 and dv > 1 (at width 1 a contiguous tensor sends the composition's products down the spmv schedule,
+    whose summation order is the method's own)."""
+    if backward not in ("composed", "fused"):
+        raise ValueError(f"backward must be 'composed' or 'fused', not {backward!r}")
     _check_handle(handle)
     for t, name in ((Q, "Q"), (K, "K"), (V, "V")):
         _check_tensor(t, name, handle)
@@ -286,4 +317,4 @@ def attention(handle, Q, K, V, scale=None):
             Q.shape[1] != K.shape[1] or Q.shape[1] < 1 or V.shape[1] < 1:
         raise ValueError(f"Q must be ({handle.m}, k), K ({handle.n}, k) and V ({handle.n}, dv) with k, dv >= 1, not {tuple(Q.shape)}, {tuple(K.shape)} and {tuple(V.shape)}")
     scale = 1.0 / math.sqrt(Q.shape[1]) if scale is None else float(scale)   # Handle.attention's default, to the bit
-    return _Attention.apply(handle, Q, K, V, scale)
+    return (_AttentionFused if backward == "fused" else _Attention).apply(handle, Q, K, V, scale)

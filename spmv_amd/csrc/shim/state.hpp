@@ -187,7 +187,8 @@ struct BlkSet {
 // given back and allocated anew when a later call needs more, counted in device_bytes, freed with the device state.
 struct StageBuf { void *p = nullptr; size_t bytes = 0; };
 enum { STAGE_X, STAGE_Y, STAGE_SPMM_X, STAGE_SPMM_Y, STAGE_SDDMM_U, STAGE_SDDMM_V, STAGE_SDDMM_O, STAGE_ROWRED_A, STAGE_ROWRED_G, STAGE_ROWRED_O,
-       STAGE_ATT_Q, STAGE_ATT_K, STAGE_ATT_V, STAGE_ATT_O, STAGE_COUNT };
+       STAGE_ATT_Q, STAGE_ATT_K, STAGE_ATT_V, STAGE_ATT_O,
+       STAGE_ATTB_Q, STAGE_ATTB_K, STAGE_ATTB_V, STAGE_ATTB_G, STAGE_ATTB_DQ, STAGE_ATTB_DK, STAGE_ATTB_DV, STAGE_COUNT };
 
 struct spmv_dev {
     int device = 0;
@@ -271,6 +272,9 @@ struct spmv_dev {
     bool att_planned = false;
     int *att_off = nullptr;   // [spmm_nlong + 1] first element of each long row in att_park
     void *att_park = nullptr; // sum of the long rows' lengths elements
+    // spmv_hip_attention_backward (shim/attention_backward.hpp): P and dS in CSR order, nnz elements each, allocated at the first call -- what the
+    // column pass over A^T gathers through tr_perm, and the long rows' parking space
+    void *attb_p = nullptr, *attb_ds = nullptr;
     // spmv_hip_spmv_transpose (shim/transpose.hpp): A^T as a matrix of its own (n x m), planned and built like any; perm[p] = our index of its entry p.
     // val_gen counts spmv_shim_update_values calls; A^T's values are gathered again when tr_gen falls behind it.
     spmv_dev *tr = nullptr;
@@ -373,13 +377,15 @@ static bool is_device_ptr(const void *p)
 // One call's operands, rows x k elements each with leading dimension ld (a vector: k = ld = 1).  A device operand is used where it is, with the
 // caller's ld; a host operand goes through its StageBuf -- in(): its k columns packed into HBM on the handle's stream (the padding is not copied);
 // out(): the buffer the kernel writes instead -- and p / ld are redirected there.  finish() copies the host result back and synchronizes, unless
-// the handle is asynchronous and every operand was on the device.  Every operand is asked once whether it is a device pointer.
+// the handle is asynchronous and every operand was on the device.  Every operand is asked once whether it is a device pointer.  An operation has
+// at most kMaxRes results (spmv_hip_attention_backward: three).
 struct Stager {
+    static constexpr int kMaxRes = 3;
+    struct Res { const StageBuf *buf; void *host; size_t ld, rows, k; }; // a staged result and where it goes
     spmv_dev *d;
     bool all_dev = true;
-    const StageBuf *res = nullptr; // the staged result and where it goes
-    void *res_host = nullptr;
-    size_t res_ld = 0, res_rows = 0, res_k = 0;
+    Res res[kMaxRes] = {};
+    int nres = 0;
 
     int reserve(StageBuf &b, size_t bytes)
     {
@@ -420,14 +426,15 @@ struct Stager {
         if (dev || rows == 0) return SPMV_HIP_OK;
         const int rc = reserve(b, d->vsize * (size_t) k * rows);
         if (rc) return rc;
-        res = &b; res_host = p; res_ld = (size_t) ld; res_rows = rows; res_k = (size_t) k;
+        if (nres >= kMaxRes) return fail(SPMV_HIP_E_ARG, "staging: more than %d results", kMaxRes);
+        res[nres++] = Res{&b, p, (size_t) ld, rows, (size_t) k};
         p = (P) b.p;
         ld = k;
         return SPMV_HIP_OK;
     }
     int finish()
     {
-        if (res) HIP_TRY(copy(res_host, res_ld, res->p, res_k, res_rows, res_k, hipMemcpyDeviceToHost));
+        for (int i = 0; i < nres; ++i) HIP_TRY(copy(res[i].host, res[i].ld, res[i].buf->p, res[i].k, res[i].rows, res[i].k, hipMemcpyDeviceToHost));
         if (!d->async || !all_dev) HIP_TRY(hipStreamSynchronize(d->stream));
         return SPMV_HIP_OK;
     }

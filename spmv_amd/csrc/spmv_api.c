@@ -853,7 +853,7 @@ double spmv_hip_time_spmm_launches(spmv_Handle_t h, int k, const void *X, long l
 /* A^T of the resident matrix: built on the device once per resident matrix, planned and inspected by the code path of create() with the
  * handle's requested method and options, attached to the resident matrix; afterwards its values are gathered again whenever A's changed.
  * When create() released the resident ColIdx, it is restored for the build and released again, so the forward multiply is unchanged. */
-static int transpose_ready(spmv_Handle_t h, spmv_hip_state *st, const char *where)
+static int transpose_built(spmv_Handle_t h, spmv_hip_state *st, const char *where)
 {
     int rc;
     if (!spmv_shim_transpose_of(st->dev)) {
@@ -881,7 +881,14 @@ static int transpose_ready(spmv_Handle_t h, spmv_hip_state *st, const char *wher
         st->tplan = plan;
         st->tmethod = actual;
     }
-    return report(spmv_shim_transpose_refresh(st->dev), where);
+    return SPMV_HIP_OK;
+}
+
+/* ... and its values those of A as they are now */
+static int transpose_ready(spmv_Handle_t h, spmv_hip_state *st, const char *where)
+{
+    const int rc = transpose_built(h, st, where);
+    return rc ? rc : report(spmv_shim_transpose_refresh(st->dev), where);
 }
 
 static const char transpose_not_built[] = "the transpose is not built (spmv_hip_prepare_transpose, or a first spmv_hip_spmv_transpose)";
@@ -1053,4 +1060,50 @@ double spmv_hip_time_attention_launches(spmv_Handle_t h, int k, int dv, double s
     spmv_hip_state *st;
     if (attention_args(h, where, k, dv, Q, ldq, K, ldk, V, ldv, O, ldo, 1) || resident_state(h, where, RESIDENT_NOT_REORDERED, &st) || spmm_columns(h, st, where)) return -1.0;
     return report_time(spmv_shim_time_attention(st->dev, k, dv, scale, Q, ldq, K, ldk, V, ldv, O, ldo, warmup, iters, ms_out), where);
+}
+
+/* ---------------------------------------------------------------- dQ, dK, dV of the fused attention in two passes over A */
+static int attention_backward_args(spmv_Handle_t h, const char *where, int k, int dv, const void *Q, long long ldq, const void *K, long long ldk, const void *V,
+                                   long long ldv, const void *G, long long ldg, const void *dQ, long long lddq, const void *dK, long long lddk, const void *dV,
+                                   long long lddv, int m)
+{
+    if (!h) return refuse(SPMV_HIP_E_ARG, where, "handle is NULL");
+    if (k < 1 || dv < 1 || ldq < k || ldk < k || ldv < dv || ldg < dv || (dQ && lddq < k) || (dK && lddk < k) || (dV && lddv < dv))
+        return refuse(SPMV_HIP_E_ARG, where, "need k >= 1, dv >= 1, ldq, ldk >= k, ldv, ldg >= dv and, for the requested outputs, lddq, lddk >= k, lddv >= dv");
+    if (m > 0 && (!Q || !K || !V || !G)) return refuse(SPMV_HIP_E_ARG, where, "Q, K, V or G is NULL");
+    return SPMV_HIP_OK;
+}
+
+/* the tables behind the gate: A's columns and, when dK or dV is wanted, the transpose (its values are not read: no refresh) with its columns */
+static int attention_backward_tables(spmv_Handle_t h, spmv_hip_state *st, const char *where, int cols)
+{
+    int rc = spmm_columns(h, st, where);
+    if (!rc && cols && !(rc = transpose_built(h, st, where))) rc = transpose_columns(st, where);
+    return rc;
+}
+
+int spmv_hip_attention_backward(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                                const void *Matrix_Val, int k, int dv, double scale,
+                                const void *Q, long long ldq, const void *K, long long ldk, const void *V, long long ldv,
+                                const void *G, long long ldg, void *dQ, long long lddq, void *dK, long long lddk, void *dV, long long lddv)
+{
+    const char *where = "attention_backward";
+    spmv_hip_state *st;
+    int rc;
+    if ((rc = attention_backward_args(handle, where, k, dv, Q, ldq, K, ldk, V, ldv, G, ldg, dQ, lddq, dK, lddk, dV, lddv, m)) ||
+        (rc = resident_prologue(handle, where, RESIDENT_NOT_REORDERED, m, RowPtr, ColIdx, Matrix_Val, &st))) return rc;
+    if (!dQ && !dK && !dV) return SPMV_HIP_OK;
+    if ((rc = attention_backward_tables(handle, st, where, dK || dV))) return rc;
+    return report(spmv_shim_attention_backward(st->dev, k, dv, scale, Q, ldq, K, ldk, V, ldv, G, ldg, dQ, lddq, dK, lddk, dV, lddv), where);
+}
+
+double spmv_hip_time_attention_backward_launches(spmv_Handle_t h, int k, int dv, double scale, const void *Q, long long ldq, const void *K, long long ldk,
+                                                 const void *V, long long ldv, const void *G, long long ldg, void *dQ, long long lddq, void *dK, long long lddk,
+                                                 void *dV, long long lddv, int warmup, int iters, float *ms_out)
+{
+    const char *where = "time_attention_backward_launches";
+    spmv_hip_state *st;
+    if (attention_backward_args(h, where, k, dv, Q, ldq, K, ldk, V, ldv, G, ldg, dQ, lddq, dK, lddk, dV, lddv, 1) ||
+        resident_state(h, where, RESIDENT_NOT_REORDERED, &st) || attention_backward_tables(h, st, where, dK || dV)) return -1.0;
+    return report_time(spmv_shim_time_attention_backward(st->dev, k, dv, scale, Q, ldq, K, ldk, V, ldv, G, ldg, dQ, lddq, dK, lddk, dV, lddv, warmup, iters, ms_out), where);
 }

@@ -1,0 +1,79 @@
+// spmv_attention_backward.hip -- translation unit of the fused attention backward (kernels/attention_backward.hpp).  Launches only: the
+// tables, the transpose, the two nnz-sized arrays, staging and the error channel stay in spmv_shim.hip (shim/attention_backward.hpp), which
+// calls attention_backward_launch once per call.
+#include <hip/hip_runtime.h>
+
+#include "kernels/common.hpp"
+#include "kernels/attention_backward.hpp"
+
+namespace spmv {
+
+// the row pass over A: P and dS into the handle's arrays, dQ
+template <typename T, int CW, bool VEC>
+static void attention_bwd_rows_cw(const AttentionBwdArgs &a, hipStream_t stream)
+{
+    constexpr int waves = kBlock / kWave, V = SpmmShape<T>::V;
+    // the narrowest lane group that covers a panel's columns (spmm's rule; it changes no bit)
+    const int lgk = a.k <= V ? 0 : (a.k <= 2 * V ? 1 : (a.k <= 4 * V ? 2 : 3));
+    const int cwd = sddmm_group_width(a.dv, SddmmShape<T>::W); // a function of dv and the value type alone: it fixes dP's summation order
+    const T scale = (T) a.scale;
+    const T *q = (const T *) a.q, *kk = (const T *) a.kk, *v = (const T *) a.v, *g = (const T *) a.g;
+    T *dq = (T *) a.dq, *p = (T *) a.p, *ds = (T *) a.ds;
+    if (a.nb > 0)
+        attention_bwd_rows_kernel<T, CW, VEC><<<(a.nb + waves - 1) / waves, kBlock, 0, stream>>>(a.nb, a.split, a.rowptr, a.colidx, a.k, a.dv, cwd, lgk, scale, q, a.ldq, kk,
+                                                                                               a.ldk, v, a.ldv, g, a.ldg, dq, a.lddq, a.dvo ? p : nullptr,
+                                                                                               a.dk ? ds : nullptr);
+    if (a.nlong > 0)
+        attention_bwd_long_kernel<T, CW, VEC><<<a.nlong < a.cus * 8 ? a.nlong : a.cus * 8, kBlock, 0, stream>>>(a.nlong, a.longs, a.rowptr, a.colidx, a.k, a.dv, cwd, lgk, scale,
+                                                                                                              q, a.ldq, kk, a.ldk, v, a.ldv, g, a.ldg, dq, a.lddq, p, ds);
+}
+
+// panel `c` of the column pass over A^T: kcv columns of dV, kck columns of dK
+template <typename T, int CW, bool VEC>
+static void attention_bwd_cols_cw(const AttentionBwdArgs &a, int c, int kcv, int kck, hipStream_t stream)
+{
+    constexpr int waves = kBlock / kWave;
+    const T *pv = (const T *) a.p, *dsv = (const T *) a.ds;
+    const T *g = (const T *) a.g + c, *q = (const T *) a.q + c;
+    T *dvo = a.dvo ? (T *) a.dvo + c : nullptr, *dk = a.dk ? (T *) a.dk + c : nullptr;
+    if (a.t_nb > 0)
+        attention_bwd_cols_kernel<T, CW, VEC><<<(a.t_nb + waves - 1) / waves, kBlock, 0, stream>>>(a.t_nb, a.t_split, a.t_rowptr, a.t_colidx, a.perm, pv, dsv, kcv, g, a.ldg, dvo,
+                                                                                                 a.lddv, kck, q, a.ldq, dk, a.lddk);
+    if (a.t_nlong > 0)
+        attention_bwd_cols_long_kernel<T, CW, VEC><<<a.t_nlong < a.cus * 8 ? a.t_nlong : a.cus * 8, kBlock, 0, stream>>>(a.t_nlong, a.t_longs, a.t_rowptr, a.t_colidx, a.perm, pv,
+                                                                                                                       dsv, kcv, g, a.ldg, dvo, a.lddv, kck, q, a.ldq, dk,
+                                                                                                                       a.lddk);
+}
+
+template <typename T, bool VEC>
+static void attention_bwd_launch_t(const AttentionBwdArgs &a, hipStream_t stream)
+{
+    constexpr int V = SpmmShape<T>::V, KP = SpmmShape<T>::KP;
+    if (a.m > 0)
+        switch (sddmm_group_width(a.k, SddmmShape<T>::W)) { // a function of k and the value type alone: it fixes the scores' summation order
+        case 1: attention_bwd_rows_cw<T, 1, VEC>(a, stream); break;
+        case 2: attention_bwd_rows_cw<T, 2, VEC>(a, stream); break;
+        case 4: attention_bwd_rows_cw<T, 4, VEC>(a, stream); break;
+        default: attention_bwd_rows_cw<T, 8, VEC>(a, stream); break;
+        }
+    if (!a.dk && !a.dvo) return;
+    const int wk = a.dk ? a.k : 0, wv = a.dvo ? a.dv : 0;
+    for (int c = 0; c < wk || c < wv; c += KP) { // panel c / KP of both outputs in one pass over A^T
+        const int kcv = wv - c < KP ? wv - c : KP, kck = wk - c < KP ? wk - c : KP; // <= 0: that output has no such panel
+        const int kc = kcv > kck ? kcv : kck;
+        // the narrowest lane group that covers the wider panel's columns
+        if (kc <= V) attention_bwd_cols_cw<T, 1, VEC>(a, c, kcv, kck, stream);
+        else if (kc <= 2 * V) attention_bwd_cols_cw<T, 2, VEC>(a, c, kcv, kck, stream);
+        else if (kc <= 4 * V) attention_bwd_cols_cw<T, 4, VEC>(a, c, kcv, kck, stream);
+        else attention_bwd_cols_cw<T, 8, VEC>(a, c, kcv, kck, stream);
+    }
+}
+
+hipError_t attention_backward_launch(const AttentionBwdArgs &a, bool f64, hipStream_t stream)
+{
+    if (f64) { if (a.vec) attention_bwd_launch_t<double, true>(a, stream); else attention_bwd_launch_t<double, false>(a, stream); }
+    else { if (a.vec) attention_bwd_launch_t<float, true>(a, stream); else attention_bwd_launch_t<float, false>(a, stream); }
+    return hipGetLastError();
+}
+
+} // namespace spmv

@@ -143,6 +143,18 @@ int spmv_shim_attention(spmv_dev *d, int k, int dv, double scale, const void *q,
 double spmv_shim_time_attention(spmv_dev *d, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v, long long ldv, void *o,
                                 long long ldo, int warmup, int iters, float *ms_out);
 
+/* ---- dQ, dK, dV of the fused attention in two passes (shim/attention_backward.hpp; spmv_hip_attention_backward) ----
+ * Q m x k, K n x k, V n x dv, G m x dv; dq m x k, dk n x k, dv_out n x dv or NULL (not wanted); row-major with leading dimensions; host or
+ * device pointers each.  Needs the resident ColIdx and, when dk or dv_out is wanted, the attached transpose with its column indices resident
+ * (its values are not read).  The resident values are neither read nor written.  Builds spmm's tables (the transpose's too) and the two
+ * nnz-sized arrays at the first call. */
+int spmv_shim_attention_backward(spmv_dev *d, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v, long long ldv,
+                                 const void *g, long long ldg, void *dq, long long lddq, void *dk, long long lddk, void *dv_out, long long lddv);
+/* `iters` calls timed with events on the handle's stream (device operands); mean ms, < 0 on failure */
+double spmv_shim_time_attention_backward(spmv_dev *d, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v, long long ldv,
+                                         const void *g, long long ldg, void *dq, long long lddq, void *dk, long long lddk, void *dv_out, long long lddv, int warmup, int iters,
+                                         float *ms_out);
+
 /* the resident CSR arrays (device pointers; ColIdx may be NULL after spmv_shim_release_columns) */
 void spmv_shim_matrix_arrays(const spmv_dev *d, const int **rowptr, const int **colidx, const void **val);
 
