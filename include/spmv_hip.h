@@ -240,6 +240,35 @@ int spmv_hip_attention(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_T
                        const void *Q, long long ldq, const void *K, long long ldk, const void *V, long long ldv,
                        void *O, long long ldo);
 
+/* ---- sparse attention for H heads over the same pattern, in the same one pass ---------------------
+ * Q is m x heads*k, K is n x heads*k, V is n x heads*dv, O is m x heads*dv, ROW-MAJOR with leading dimensions ldq, ldk >= heads*k and
+ * ldv, ldo >= heads*dv, in the handle's precision -- the (rows, heads, k) layout: head h of a row is its columns [h*k, (h+1)*k) of Q and K
+ * and [h*dv, (h+1)*dv) of V and O.  k, dv and `scale` are ONE head's.  Each operand may be a host or a device pointer; K
+ * and V may be the same pointer; O must not overlap an input.  Returns 0 or an SPMV_HIP_E_* code.
+ *   - Bits: for every h, head h's block of O has exactly the bits that
+ *       spmv_hip_attention(handle, .., k, dv, scale, Q + h*k, ldq, K + h*k, ldk, V + h*dv, ldv, O + h*dv, ldo)
+ *     writes (pointer arithmetic in elements).  heads = 1 IS spmv_hip_attention.  So spmv_hip_attention's arithmetic and order, its
+ *     special-value rules and its invariance (ld, alignment, access width, host / device pointers, stream and async settings, the handle's
+ *     method, run to run) hold head by head; a NaN row in one head does not touch another head of the same row.
+ *   - Writes: exactly the first heads*dv elements of each of the m rows of O; a row without entries gets +0 in all of them; the padding
+ *     of Q, K, V and O is never read or written; offsets are 64-bit.  m = 0 writes nothing; nnz = 0 writes the zeros.
+ *   - A's VALUES are not read, and the handle's resident values are NOT MODIFIED: spmv() before and after computes the same.
+ *   - Still one launch for the rows of up to 512 entries and one for the longer rows, whatever heads is: the head loop is inside the
+ *     kernels.  RowPtr and ColIdx of a chunk of short rows are read once and kept in LDS for every head; the scores' LDS and the long
+ *     rows' parking space are reused head after head, so spmv_hip_info.device_bytes does not depend on heads when the operands are device
+ *     pointers.  16-byte accesses additionally need k and dv to be multiples of 16 bytes when heads > 1 (every head's first column must
+ *     be aligned); element accesses otherwise -- the width changes no bit.  No floating-point atomics; no workgroup waits on another.
+ *   - The CSR arguments, the stream and async setting, the staging of host operands (at widths heads*k and heads*dv, the same four
+ *     buffers), the column indices (option "keep_columns") and the handle kinds: as for spmv_hip_attention.
+ *   - Errors (SPMV_HIP_E_ARG before the handle is looked at, O untouched): a NULL handle; heads < 1, k < 1, dv < 1; heads*k or heads*dv
+ *     not representable in int; ldq, ldk < heads*k; ldv, ldo < heads*dv; a NULL Q, K, V or O while m > 0.  Multi-GPU, host_rows and
+ *     "reorder" handles: SPMV_HIP_E_ARG.  A cleared or failed handle: SPMV_HIP_E_NOSTATE.  Every failure is also reported through
+ *     spmv_hip_last_error(). */
+int spmv_hip_attention_heads(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                             const void *Matrix_Val, int heads, int k, int dv, double scale,
+                             const void *Q, long long ldq, const void *K, long long ldk, const void *V, long long ldv,
+                             void *O, long long ldo);
+
 /* ---- the gradients of spmv_hip_attention in two passes over A: dQ, dK, dV -----------------------
  * With G = dL/dO (m x dv) and t_p, P_p as in spmv_hip_attention:  dP_p = sum over c < dv of G[i*ldg + c] * V[j_p*ldv + c],
  * D_i = sum over row i of P_q dP_q,  dS_p = P_p (dP_p - D_i) scale,  dQ = A_dS K (m x k),  dK = A_dS^T Q (n x k),  dV = A_P^T G (n x dv), where A_X

@@ -36,6 +36,9 @@ double spmv_hip_time_row_softmax_launches(spmv_Handle_t handle, const void *S, v
 /* The same for spmv_hip_attention (Q: m x k, K: n x k, V: n x dv, O: m x dv; DEVICE pointers). */
 double spmv_hip_time_attention_launches(spmv_Handle_t handle, int k, int dv, double scale, const void *Q, long long ldq, const void *K, long long ldk,
                                         const void *V, long long ldv, void *O, long long ldo, int warmup, int iters, float *ms_out);
+/* The same for spmv_hip_attention_heads (Q: m x heads*k, K: n x heads*k, V: n x heads*dv, O: m x heads*dv; DEVICE pointers). */
+double spmv_hip_time_attention_heads_launches(spmv_Handle_t handle, int heads, int k, int dv, double scale, const void *Q, long long ldq, const void *K,
+                                              long long ldk, const void *V, long long ldv, void *O, long long ldo, int warmup, int iters, float *ms_out);
 /* The same for spmv_hip_attention_backward (Q: m x k, K: n x k, V: n x dv, G: m x dv, dQ / dK / dV or NULL; DEVICE pointers); builds the
  * transpose and restores its column indices first when dK or dV is wanted. */
 double spmv_hip_time_attention_backward_launches(spmv_Handle_t handle, int k, int dv, double scale, const void *Q, long long ldq, const void *K, long long ldk,

@@ -125,6 +125,10 @@ FUNCTIONS = {
                                      _V, C.c_longlong]),
     "spmv_hip_time_attention_launches": (C.c_double, [spmv_Handle_t, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong,
                                                       _V, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "spmv_hip_attention_heads": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, C.c_int, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong,
+                                           _V, C.c_longlong, _V, C.c_longlong]),
+    "spmv_hip_time_attention_heads_launches": (C.c_double, [spmv_Handle_t, C.c_int, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong,
+                                                            _V, C.c_longlong, _V, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_float)]),
     "spmv_hip_attention_backward": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong,
                                               _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong]),
     "spmv_hip_time_attention_backward_launches": (C.c_double, [spmv_Handle_t, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong,
@@ -457,6 +461,33 @@ def time_attention_launches(handle, Q, K, V, O, scale=None, warmup=10, iters=100
     return _timed("spmv_hip_time_attention_launches", (handle, k, dv, float(scale), pq, ldq, pk, ldk, pv, ldv, po, ldo), warmup, iters)
 
 
+def _attention_heads_blocks(heads, Q, K, V, O):
+    """-> _attention_blocks with k and dv as ONE head's widths: the column counts of Q / K and of V / O divided by `heads`"""
+    heads = int(heads)
+    wk, wv, *rest = _attention_blocks(Q, K, V, O)
+    if heads < 1 or wk % heads or wv % heads:
+        raise ValueError(f"Q / K have {wk} columns and V / O {wv}: not {heads} heads of equal width")
+    return (wk // heads, wv // heads, *rest)
+
+
+def attention_heads(handle, m, RowPtr, ColIdx, Matrix_Val, heads, Q, K, V, O, scale=None, check=True):
+    """`heads` attention heads over the handle's pattern in one pass (spmv_hip_attention_heads).  Q (m x heads*k), K (n x heads*k),
+    V (n x heads*dv) and O (m x heads*dv) hold the heads side by side -- the (rows, heads, k) layout --: 2-D numpy arrays or torch tensors with
+    column stride 1 (row strides are passed as leading dimensions); head h of O has the bits of attention() on the h-th column slices.  scale
+    None means 1 / sqrt(k) with k ONE head's width.  The handle's values are neither read nor changed.  -> the return code."""
+    k, dv, pq, ldq, pk, ldk, pv, ldv, po, ldo = _attention_heads_blocks(heads, Q, K, V, O)
+    scale = 1.0 / np.sqrt(k) if scale is None and k > 0 else (0.0 if scale is None else scale)
+    return _checked(load().spmv_hip_attention_heads(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), int(heads), k, dv, float(scale),
+                                                    pq, ldq, pk, ldk, pv, ldv, po, ldo), "spmv_hip_attention_heads", check)
+
+
+def time_attention_heads_launches(handle, heads, Q, K, V, O, scale=None, warmup=10, iters=100):
+    """-> (mean_ms, per-call ms array) of spmv_hip_attention_heads on device Q / K / V / O (spmv_hip_time_attention_heads_launches)."""
+    k, dv, pq, ldq, pk, ldk, pv, ldv, po, ldo = _attention_heads_blocks(heads, Q, K, V, O)
+    scale = 1.0 / np.sqrt(k) if scale is None else scale
+    return _timed("spmv_hip_time_attention_heads_launches", (handle, int(heads), k, dv, float(scale), pq, ldq, pk, ldk, pv, ldv, po, ldo), warmup, iters)
+
+
 def _attention_backward_blocks(Q, K, V, G, dQ, dK, dV):
     """-> (k, dv, then address and ld of Q, K, V, G, dQ, dK, dV) of an attention_backward call; an output that is None has a NULL address and its
     width as ld.  Q, K, dQ and dK share k; V, G and dV share dv."""
@@ -655,6 +686,16 @@ class Handle:
             out = self._like(Q, (self.m, V.shape[1]))
         rp, ci, va = self._keep
         attention(self.h, self.m, rp, ci, va, Q, K, V, out, scale)
+        return out
+
+    def attention_heads(self, Q, K, V, heads, scale=None, out=None):
+        """out = `heads` attention heads over the pattern in one pass (spmv_hip_attention_heads) for 2-D Q (m x heads*k), K (n x heads*k) and
+        V (n x heads*dv) holding the heads side by side; scale None means 1 / sqrt(k), k one head's width; out (m x heads*dv) is allocated like
+        Q -- same kind, dtype and device -- when None.  The handle's values are not used and not changed."""
+        if out is None:
+            out = self._like(Q, (self.m, V.shape[1]))
+        rp, ci, va = self._keep
+        attention_heads(self.h, self.m, rp, ci, va, heads, Q, K, V, out, scale)
         return out
 
     def attention_backward(self, Q, K, V, G, scale=None, need=(True, True, True)):

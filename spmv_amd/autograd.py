@@ -21,6 +21,8 @@ library's kernels forward and backward (Handle.sddmm / row_softmax / spmm; Handl
 
     O = spmv_amd.autograd.attention(handle, Q, K, V, scale=None)   the same in ONE forward pass (Handle.attention): no nnz-sized array is
                                                                    written or saved, and the handle's values are not touched
+    O = spmv_amd.autograd.attention_heads(handle, Q, K, V, heads)  the same for `heads` heads side by side in the columns of Q, K and V
+                                                                   (Handle.attention_heads: all heads in that one pass)
 
 Every call runs on torch's current stream.  The only module of the package that needs torch; libspmv_hip.so has no torch dependency.
 """
@@ -290,6 +292,67 @@ class _AttentionFused(torch.autograd.Function):
         _on_current_stream(ctx.handle)
         dQ, dK, dV = ctx.handle.attention_backward(Q2, K2, V2, _block(G, G.shape[1]), ctx.scale, need=need)
         return None, dQ, dK, dV, None
+
+
+class _AttentionHeads(torch.autograd.Function):
+    """Handle.attention_heads forward; the backward pass is one api.attention_backward call per head on column slices, written into the slices
+    of full-width gradients: the handle's values are never touched"""
+
+    @staticmethod
+    def forward(ctx, handle, Q, K, V, heads, scale):
+        Q2, K2, V2 = _block(Q.detach(), Q.shape[1]), _block(K.detach(), K.shape[1]), _block(V.detach(), V.shape[1])
+        _on_current_stream(handle)
+        O = handle.attention_heads(Q2, K2, V2, heads, scale)
+        ctx.handle, ctx.heads, ctx.scale = handle, heads, scale
+        ctx.save_for_backward(Q2, K2, V2)   # nothing nnz-sized
+        return O
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, G):
+        from . import api
+        handle, heads, scale = ctx.handle, ctx.heads, ctx.scale
+        Q2, K2, V2 = ctx.saved_tensors
+        need = tuple(bool(x) for x in ctx.needs_input_grad[1:4])
+        if not any(need):
+            return None, None, None, None, None, None
+        if handle.nnz == 0:   # no stored entry: O is zero whatever Q, K and V are
+            return None, (torch.zeros_like(Q2) if need[0] else None), (torch.zeros_like(K2) if need[1] else None), (torch.zeros_like(V2) if need[2] else None), None, None
+        _on_current_stream(handle)
+        G2 = _block(G, G.shape[1])
+        k, dv = Q2.shape[1] // heads, V2.shape[1] // heads
+        dQ = torch.empty_like(Q2, memory_format=torch.contiguous_format) if need[0] else None
+        dK = torch.empty_like(K2, memory_format=torch.contiguous_format) if need[1] else None
+        dV = torch.empty_like(V2, memory_format=torch.contiguous_format) if need[2] else None
+        rp, ci, va = handle._keep
+        for h in range(heads):
+            ck, cv = slice(h * k, (h + 1) * k), slice(h * dv, (h + 1) * dv)
+            api.attention_backward(handle.h, handle.m, rp, ci, va, Q2[:, ck], K2[:, ck], V2[:, cv], G2[:, cv],
+                                   None if dQ is None else dQ[:, ck], None if dK is None else dK[:, ck], None if dV is None else dV[:, cv], scale)
+        return None, dQ, dK, dV, None, None
+
+
+def attention_heads(handle, Q, K, V, heads, scale=None):
+    """`heads` attention heads over the handle's pattern (Handle.attention_heads: one fused pass for all heads), with gradients for Q, K and
+    V.  Q: (m, heads * k), K: (n, heads * k), V: (n, heads * dv) hold the heads side by side -- a (rows, heads, k) tensor reshaped to two
+    dimensions --, of the handle's dtype on its device; the result is (m, heads * dv).  scale: a Python number, None means 1 / sqrt(k) with k
+    one head's width; it receives no gradient.  Head h is attention() on the h-th column slices, to the bit.
+
+    The forward pass saves Q, K and V only and neither reads nor changes the handle's values.  The backward pass calls
+    spmv_hip_attention_backward once per head on column-slice views of Q, K, V and G; each call writes the matching slices of full-width
+    dQ, dK and dV, only for the gradients asked for -- no Handle.update_values, the handle multiplies the same matrix throughout.  Every head
+    slice of a gradient has the bits of attention(..., backward="fused") on that head's slices."""
+    _check_handle(handle)
+    for t, name in ((Q, "Q"), (K, "K"), (V, "V")):
+        _check_tensor(t, name, handle)
+    heads = int(heads)
+    if Q.dim() != 2 or K.dim() != 2 or V.dim() != 2 or Q.shape[0] != handle.m or K.shape[0] != handle.n or V.shape[0] != handle.n or \
+            Q.shape[1] != K.shape[1] or Q.shape[1] < 1 or V.shape[1] < 1:
+        raise ValueError(f"Q must be ({handle.m}, heads * k), K ({handle.n}, heads * k) and V ({handle.n}, heads * dv) with k, dv >= 1, not {tuple(Q.shape)}, {tuple(K.shape)} and {tuple(V.shape)}")
+    if heads < 1 or Q.shape[1] % heads or V.shape[1] % heads:
+        raise ValueError(f"{Q.shape[1]} columns of Q / K and {V.shape[1]} of V are not {heads} heads of equal width")
+    scale = 1.0 / math.sqrt(Q.shape[1] // heads) if scale is None else float(scale)   # Handle.attention_heads' default, to the bit
+    return _AttentionHeads.apply(handle, Q, K, V, heads, scale)
 
 
 def attention(handle, Q, K, V, scale=None, backward="composed"):

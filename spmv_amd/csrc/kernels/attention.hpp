@@ -3,6 +3,12 @@
 // m x dv, all row-major with leading dimensions.  A's values are neither read nor written; the scores and P never reach HBM for rows of up to
 // kSpmmLongThr entries.
 //
+// Heads (spmv_hip_attention_heads): Q and K are `heads` blocks of k columns side by side, V and O `heads` blocks of dv columns; head hd is the
+// single-head product on the columns from hd * k (Q, K) and hd * dv (V, O).  The head loop is inside both kernels, around the three phases:
+// the pattern of a chunk is fetched once and kept in LDS for every head, the scores' LDS and the long rows' parking space are reused head after
+// head, and each head's arithmetic is the single-head code on offset pointers -- so head hd has the bits of the single-head call on its slices.
+// spmv_hip_attention is heads = 1.
+//
 // Work split: spmm's tables (shim/spmm.hpp) -- equal-nnz batches of whole rows, one wave per batch, and the list of rows longer than
 // kSpmmLongThr, a workgroup each.
 //
@@ -33,7 +39,7 @@ namespace spmv {
 
 // what one call's launches need (device pointers)
 struct AttentionArgs {
-    int m = 0, k = 0, dv = 0, nb = 0, nlong = 0, cus = 256;
+    int m = 0, heads = 1, k = 0, dv = 0, nb = 0, nlong = 0, cus = 256; // k, dv: per head
     const int *split = nullptr, *longs = nullptr, *rowptr = nullptr, *colidx = nullptr;
     const int *long_off = nullptr; // first parked element of long row i of the list
     void *park = nullptr;          // the long rows' scores, then P
@@ -41,7 +47,7 @@ struct AttentionArgs {
     void *o = nullptr;
     long long ldq = 0, ldk = 0, ldv = 0, ldo = 0;
     double scale = 1.0;
-    bool vec = false; // q, kk, v, o and their leading dimensions allow 16-byte accesses
+    bool vec = false; // q, kk, v, o, their leading dimensions and every head's first column allow 16-byte accesses
 };
 
 // spmv_attention.hip: the launches of one call on `stream`
@@ -52,6 +58,14 @@ static __global__ __launch_bounds__(kBlock) void attention_long_len_kernel(int n
 {
     const long long stride = (long long) gridDim.x * kBlock;
     for (long long i = (long long) blockIdx.x * kBlock + threadIdx.x; i < nlong; i += stride) len[i] = rowptr[longs[i] + 1] - rowptr[longs[i]];
+}
+
+// x, as a value the compiler computes with again in every head: what a thread derives from its index (addresses, lane-group coordinates) is
+// cheap to redo and would otherwise be hoisted out of the head loop and kept in registers across all three phases
+__device__ __forceinline__ int att_per_head(int x)
+{
+    asm volatile("" : "+v"(x));
+    return x;
 }
 
 template <typename T>
@@ -82,10 +96,11 @@ __device__ __forceinline__ void att_tile_scores(int i, int j, int lane, int k, c
 }
 
 // One wave per batch [split[b], split[b + 1]) of whole rows; rows longer than kSpmmLongThr are left to attention_long_kernel.
-// CW: sddmm's lane group for k; 1 << lgv: spmm's lane group for min(dv, KP) columns.
+// CW: sddmm's lane group for k; 1 << lgv: spmm's lane group for min(dv, KP) columns.  heads: the chunk's columns stay in s_col while the
+// three phases run once per head over s_p, head hd on the columns from hd * k of Q and K and from hd * dv of V and O.
 template <typename T, int CW, bool VEC>
-__global__ __launch_bounds__(kBlock) void attention_rows_kernel(int nb, const int *__restrict__ split, const int *__restrict__ rowptr, const int *__restrict__ colidx, int k,
-                                                                int dv, int lgv, T scale, const T *__restrict__ q, long long ldq, const T *__restrict__ kk, long long ldk,
+__global__ __launch_bounds__(kBlock) void attention_rows_kernel(int nb, const int *__restrict__ split, const int *__restrict__ rowptr, const int *__restrict__ colidx, int heads,
+                                                                int k, int dv, int lgv, T scale, const T *__restrict__ q, long long ldq, const T *__restrict__ kk, long long ldk,
                                                                 const T *__restrict__ v, long long ldv, T *__restrict__ o, long long ldo)
 {
 #pragma clang fp contract(off)
@@ -95,16 +110,16 @@ __global__ __launch_bounds__(kBlock) void attention_rows_kernel(int nb, const in
     const int w = (int) (threadIdx.x / kWave);
     const int b = blockIdx.x * (kBlock / kWave) + w;
     if (b >= nb) return; // whole waves only; no workgroup barrier follows
-    const int lane = threadIdx.x & (kWave - 1);
-    const int cwv = 1 << lgv, R = kWave >> lgv, subv = lane >> lgv, cv0 = (lane & (cwv - 1)) * V;
+    const int lane0 = threadIdx.x & (kWave - 1);
+    const int cwv = 1 << lgv, R = kWave >> lgv;
     const int r0 = split[b], r1 = split[b + 1];
     const T ninf = -__builtin_huge_val(), nzero = T(-0.0);
     for (int g0 = r0; g0 < r1;) {
         // lane l looks at row g0 + l: the chunk takes the first nr of them
         int sl = 0, ll = -1;
-        if (g0 + lane < r1) {
-            sl = rowptr[g0 + lane];
-            ll = rowptr[g0 + lane + 1] - sl;
+        if (g0 + lane0 < r1) {
+            sl = rowptr[g0 + lane0];
+            ll = rowptr[g0 + lane0 + 1] - sl;
         }
         const int base = __builtin_amdgcn_readfirstlane(sl); // rowptr[g0]
         const bool fits = ll >= 0 && ll <= kSpmmLongThr && sl + ll - base <= CH;
@@ -112,97 +127,105 @@ __global__ __launch_bounds__(kBlock) void attention_rows_kernel(int nb, const in
         const int nr = bad ? __ffsll((long long) bad) - 1 : kWave;
         if (nr == 0) { ++g0; continue; } // a long row: nothing of it here
         const int nq = __shfl(sl + ll, nr - 1, kWave) - base; // entries of the chunk: [base, base + nq) of the matrix
-        const int el = lane < nr ? sl + ll - base : 0x7fffffff;  // where the lane's row ends in the chunk: non-decreasing over the lanes
+        const int el = lane0 < nr ? sl + ll - base : 0x7fffffff;  // where the lane's row ends in the chunk: non-decreasing over the lanes
 
-        // 1. columns and scaled scores into LDS
-        for (int t0 = 0; t0 < nq; t0 += kWave) {
-            const int e = t0 + lane;
-            int pos = 0; // rows of the chunk that end at or before e: the row of entry e
+        for (int hd = 0; hd < heads; ++hd) {
+            const int lane = att_per_head(lane0), subv = lane >> lgv, cv0 = (lane & (cwv - 1)) * V;
+            const T *qh = q + (long long) hd * k, *kh = kk + (long long) hd * k, *vh = v + (long long) hd * dv; // the head's first columns
+            T *oh = o + (long long) hd * dv;
+            // 1. columns (the first head reads them from memory, the others from LDS) and scaled scores into LDS
+            for (int t0 = 0; t0 < nq; t0 += kWave) {
+                const int e = t0 + lane;
+                int pos = 0; // rows of the chunk that end at or before e: the row of entry e
 #pragma unroll
-            for (int s = kWave / 2; s > 0; s >>= 1)
-                if (__shfl(el, pos + s - 1, kWave) <= e) pos += s;
-            int i = -1, j = 0;
-            if (e < nq) {
-                j = ld_stream(colidx + base + e);
-                i = g0 + pos;
-                s_col[w][e] = j;
-            }
-            att_tile_scores<T, CW, VEC>(i, j, lane, k, q, ldq, kk, ldk, scale, s_p[w] + t0);
-        }
-        wave_lds_sync();
-
-        // 2. the row softmax in place in LDS: row_reduce_rows_kernel's passes.  An element is read and written by the same lane.
-        for (int h0 = 0; h0 < nr;) {
-            const int hl = h0 + lane; // lane l looks at chunk row h0 + l
-            const int sh = __shfl(sl, hl & (kWave - 1), kWave) - base, lh0 = __shfl(ll, hl & (kWave - 1), kWave);
-            const int lh = hl < nr ? lh0 : 0;
-            const int wl = row_width(lh);
-            int cw = 1, lg = 0;
-            for (; cw < kWave; cw <<= 1, ++lg)
-                if ((__ballot(wl > cw) & (~0ull >> (kWave - kWave / cw))) == 0) break;
-            const int sub = lane >> lg, t = lane & (cw - 1);
-            const int s = __shfl(sh, sub, kWave), len = __shfl(lh, sub, kWave);
-            const bool wide = cw == kWave; // the only passes in which a lane holds more than one term
-            T *row = s_p[w] + s;
-            T x[kRowChain];
-            x[0] = t < len ? row[t] : ninf;
-            if (wide) {
-#pragma unroll
-                for (int u = 1; u < kRowChain; ++u) x[u] = t + u * kWave < len ? row[t + u * kWave] : ninf;
-            }
-            T mx = x[0];
-            if (wide) {
-#pragma unroll
-                for (int u = 1; u < kRowChain; ++u) mx = row_max(mx, x[u]);
-            }
-            const T M = row_group_reduce<true>(mx, cw);
-            const T e0 = row_exp(x[0] - M);
-            x[0] = t < len ? e0 : nzero;
-            T acc = x[0];
-            if (wide) {
-#pragma unroll
-                for (int u = 1; u < kRowChain; ++u) {
-                    const bool have = t + u * kWave < len;
-                    if (__ballot(have) == 0) break;
-                    x[u] = row_exp(x[u] - M);
-                    acc = have ? acc + x[u] : acc;
+                for (int s = kWave / 2; s > 0; s >>= 1)
+                    if (__shfl(el, pos + s - 1, kWave) <= e) pos += s;
+                int i = -1, j = 0;
+                if (e < nq) {
+                    i = g0 + pos;
+                    if (hd == 0) {
+                        j = ld_stream(colidx + base + e);
+                        s_col[w][e] = j;
+                    } else j = s_col[w][e]; // written by this lane
                 }
+                att_tile_scores<T, CW, VEC>(i, j, lane, k, qh, ldq, kh, ldk, scale, s_p[w] + t0);
             }
-            const T Z = row_group_reduce<false>(acc, cw);
-            if (t < len) row[t] = x[0] / Z;
-            if (wide) {
-#pragma unroll
-                for (int u = 1; u < kRowChain; ++u)
-                    if (t + u * kWave < len) row[t + u * kWave] = x[u] / Z;
-            }
-            h0 += kWave >> lg;
-        }
-        wave_lds_sync();
+            wave_lds_sync();
 
-        // 3. O = P V: R rows side by side, every (row, column) one lane's chain over the row's entries in CSR order; the panels reuse P
-        for (int h0 = 0; h0 < nr; h0 += R) {
-            const int h = h0 + subv;
-            const int s = __shfl(sl, h & (kWave - 1), kWave) - base, len = __shfl(ll, h & (kWave - 1), kWave);
-            if (h < nr)
-                for (int c = 0; c < dv; c += KP) {
-                    const int nc = min(V, min(KP, dv - c) - cv0); // <= 0: a lane beyond the panel's columns
-                    if (nc <= 0) continue;
-                    T acc[V];
+            // 2. the row softmax in place in LDS: row_reduce_rows_kernel's passes.  An element is read and written by the same lane.
+            for (int h0 = 0; h0 < nr;) {
+                const int hl = h0 + lane; // lane l looks at chunk row h0 + l
+                const int sh = __shfl(sl, hl & (kWave - 1), kWave) - base, lh0 = __shfl(ll, hl & (kWave - 1), kWave);
+                const int lh = hl < nr ? lh0 : 0;
+                const int wl = row_width(lh);
+                int cw = 1, lg = 0;
+                for (; cw < kWave; cw <<= 1, ++lg)
+                    if ((__ballot(wl > cw) & (~0ull >> (kWave - kWave / cw))) == 0) break;
+                const int sub = lane >> lg, t = lane & (cw - 1);
+                const int s = __shfl(sh, sub, kWave), len = __shfl(lh, sub, kWave);
+                const bool wide = cw == kWave; // the only passes in which a lane holds more than one term
+                T *row = s_p[w] + s;
+                T x[kRowChain];
+                x[0] = t < len ? row[t] : ninf;
+                if (wide) {
 #pragma unroll
-                    for (int u = 0; u < V; ++u) acc[u] = T(0);
-                    spmm_chain<T, VEC, false>(s, s + len, s_col[w], s_p[w], v + c, ldv, cv0, nc, acc);
-                    spmm_store_y<T, VEC>(o + (long long) (g0 + h) * ldo + c + cv0, nc, acc);
+                    for (int u = 1; u < kRowChain; ++u) x[u] = t + u * kWave < len ? row[t + u * kWave] : ninf;
                 }
+                T mx = x[0];
+                if (wide) {
+#pragma unroll
+                    for (int u = 1; u < kRowChain; ++u) mx = row_max(mx, x[u]);
+                }
+                const T M = row_group_reduce<true>(mx, cw);
+                const T e0 = row_exp(x[0] - M);
+                x[0] = t < len ? e0 : nzero;
+                T acc = x[0];
+                if (wide) {
+#pragma unroll
+                    for (int u = 1; u < kRowChain; ++u) {
+                        const bool have = t + u * kWave < len;
+                        if (__ballot(have) == 0) break;
+                        x[u] = row_exp(x[u] - M);
+                        acc = have ? acc + x[u] : acc;
+                    }
+                }
+                const T Z = row_group_reduce<false>(acc, cw);
+                if (t < len) row[t] = x[0] / Z;
+                if (wide) {
+#pragma unroll
+                    for (int u = 1; u < kRowChain; ++u)
+                        if (t + u * kWave < len) row[t + u * kWave] = x[u] / Z;
+                }
+                h0 += kWave >> lg;
+            }
+            wave_lds_sync();
+
+            // 3. O = P V: R rows side by side, every (row, column) one lane's chain over the row's entries in CSR order; the panels reuse P
+            for (int h0 = 0; h0 < nr; h0 += R) {
+                const int h = h0 + subv;
+                const int s = __shfl(sl, h & (kWave - 1), kWave) - base, len = __shfl(ll, h & (kWave - 1), kWave);
+                if (h < nr)
+                    for (int c = 0; c < dv; c += KP) {
+                        const int nc = min(V, min(KP, dv - c) - cv0); // <= 0: a lane beyond the panel's columns
+                        if (nc <= 0) continue;
+                        T acc[V];
+#pragma unroll
+                        for (int u = 0; u < V; ++u) acc[u] = T(0);
+                        spmm_chain<T, VEC, false>(s, s + len, s_col[w], s_p[w], vh + c, ldv, cv0, nc, acc);
+                        spmm_store_y<T, VEC>(oh + (long long) (g0 + h) * ldo + c + cv0, nc, acc);
+                    }
+            }
+            wave_lds_sync(); // the next head overwrites s_p, the next chunk s_col as well
         }
-        wave_lds_sync(); // the next chunk overwrites s_col / s_p
         g0 += nr;
     }
 }
 
-// one workgroup per long row (len > kSpmmLongThr >= 256: every thread has a first term); park + long_off[i]: len elements of its own
+// one workgroup per long row (len > kSpmmLongThr >= 256: every thread has a first term); park + long_off[i]: len elements of its own, used by
+// one head after the other (the barrier that ends a head's last panel is also the one before the next head parks its scores)
 template <typename T, int CW, bool VEC>
 __global__ __launch_bounds__(kBlock) void attention_long_kernel(int nlong, const int *__restrict__ longs, const int *__restrict__ long_off, const int *__restrict__ rowptr,
-                                                                const int *__restrict__ colidx, int k, int dv, int lgv, T scale, const T *__restrict__ q, long long ldq,
+                                                                const int *__restrict__ colidx, int heads, int k, int dv, int lgv, T scale, const T *__restrict__ q, long long ldq,
                                                                 const T *__restrict__ kk, long long ldk, const T *__restrict__ v, long long ldv, T *__restrict__ o, long long ldo,
                                                                 T *park)
 {
@@ -211,59 +234,64 @@ __global__ __launch_bounds__(kBlock) void attention_long_kernel(int nlong, const
     __shared__ T part[kSpmmSegs][KP];
     __shared__ T s_slot[kBlock / kWave][kWave];
     __shared__ T s_max[kBlock / kWave], s_sum[kBlock / kWave];
-    const int tid = (int) threadIdx.x, w = tid / kWave, lane = tid & (kWave - 1);
-    const int cwv = 1 << lgv, G = kBlock >> lgv, subv = tid >> lgv, cv0 = (tid & (cwv - 1)) * V;
+    const int cwv = 1 << lgv, G = kBlock >> lgv;
     for (int i = blockIdx.x; i < nlong; i += gridDim.x) {
         const int r = longs[i], s = rowptr[r], len = rowptr[r + 1] - s;
         const int *col = colidx + s;
         T *t = park + long_off[i];
-        // 1. the scaled scores, parked: tiles of 64 entries, wave w takes the tiles w, w + 4, .. (entry p is thread p % 256's in every phase)
-        for (int t0 = w * kWave; t0 < len; t0 += kBlock) {
-            const int p = t0 + lane;
-            const bool valid = p < len;
-            const int j = valid ? col[p] : 0;
-            att_tile_scores<T, CW, VEC>(valid ? r : -1, j, lane, k, q, ldq, kk, ldk, scale, s_slot[w]);
-            wave_lds_sync();
-            if (valid) t[p] = s_slot[w][lane];
-            wave_lds_sync();
-        }
-        __syncthreads();
-        // 2. maximum, sum, map: row_reduce_long_kernel's forward over the parked scores, P written in place
-        T mx = t[tid];
-        for (int p = tid + kBlock; p < len; p += kBlock) mx = row_max(mx, t[p]);
-        mx = row_group_reduce<true>(mx, kWave);
-        if (lane == 0) s_max[w] = mx;
-        __syncthreads();
-        const T M = row_max(row_max(s_max[0], s_max[1]), row_max(s_max[2], s_max[3]));
-        T acc = row_exp(t[tid] - M);
-        for (int p = tid + kBlock; p < len; p += kBlock) acc = acc + row_exp(t[p] - M);
-        acc = row_group_reduce<false>(acc, kWave);
-        if (lane == 0) s_sum[w] = acc;
-        __syncthreads();
-        const T Z = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]);
-        for (int p = tid; p < len; p += kBlock) t[p] = row_exp(t[p] - M) / Z;
-        __syncthreads();
-        // 3. O = P V: kSpmmSegs equal segments (lane group g takes g, g + G, ..), partial sums added left to right in LDS, panel by panel
-        const int seg = (len + kSpmmSegs - 1) / kSpmmSegs;
-        for (int c = 0; c < dv; c += KP) {
-            const int kc = min(KP, dv - c), nc = min(V, kc - cv0);
-            if (nc > 0)
-                for (int g = subv; g < kSpmmSegs; g += G) {
-                    T a[V];
-#pragma unroll
-                    for (int u = 0; u < V; ++u) a[u] = T(0);
-                    const int lo = min(len, g * seg), hi = min(len, lo + seg);
-                    spmm_chain<T, VEC, false>(lo, hi, col, t, v + c, ldv, cv0, nc, a);
-#pragma unroll
-                    for (int u = 0; u < V; ++u) part[g][cv0 + u] = a[u];
-                }
-            __syncthreads();
-            if (tid < kc) {
-                T sum = part[0][tid];
-                for (int g = 1; g < kSpmmSegs; ++g) sum += part[g][tid];
-                o[(long long) r * ldo + c + tid] = sum;
+        for (int hd = 0; hd < heads; ++hd) {
+            const T *qh = q + (long long) hd * k, *kh = kk + (long long) hd * k, *vh = v + (long long) hd * dv; // the head's first columns
+            T *oh = o + (long long) hd * dv;
+            const int tid = att_per_head((int) threadIdx.x), w = tid / kWave, lane = tid & (kWave - 1);
+            const int subv = tid >> lgv, cv0 = (tid & (cwv - 1)) * V;
+            // 1. the scaled scores, parked: tiles of 64 entries, wave w takes the tiles w, w + 4, .. (entry p is thread p % 256's in every phase)
+            for (int t0 = w * kWave; t0 < len; t0 += kBlock) {
+                const int p = t0 + lane;
+                const bool valid = p < len;
+                const int j = valid ? col[p] : 0;
+                att_tile_scores<T, CW, VEC>(valid ? r : -1, j, lane, k, qh, ldq, kh, ldk, scale, s_slot[w]);
+                wave_lds_sync();
+                if (valid) t[p] = s_slot[w][lane];
+                wave_lds_sync();
             }
-            __syncthreads(); // the next panel / row writes part, s_max, s_sum again
+            __syncthreads();
+            // 2. maximum, sum, map: row_reduce_long_kernel's forward over the parked scores, P written in place
+            T mx = t[tid];
+            for (int p = tid + kBlock; p < len; p += kBlock) mx = row_max(mx, t[p]);
+            mx = row_group_reduce<true>(mx, kWave);
+            if (lane == 0) s_max[w] = mx;
+            __syncthreads();
+            const T M = row_max(row_max(s_max[0], s_max[1]), row_max(s_max[2], s_max[3]));
+            T acc = row_exp(t[tid] - M);
+            for (int p = tid + kBlock; p < len; p += kBlock) acc = acc + row_exp(t[p] - M);
+            acc = row_group_reduce<false>(acc, kWave);
+            if (lane == 0) s_sum[w] = acc;
+            __syncthreads();
+            const T Z = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]);
+            for (int p = tid; p < len; p += kBlock) t[p] = row_exp(t[p] - M) / Z;
+            __syncthreads();
+            // 3. O = P V: kSpmmSegs equal segments (lane group g takes g, g + G, ..), partial sums added left to right in LDS, panel by panel
+            const int seg = (len + kSpmmSegs - 1) / kSpmmSegs;
+            for (int c = 0; c < dv; c += KP) {
+                const int kc = min(KP, dv - c), nc = min(V, kc - cv0);
+                if (nc > 0)
+                    for (int g = subv; g < kSpmmSegs; g += G) {
+                        T a[V];
+#pragma unroll
+                        for (int u = 0; u < V; ++u) a[u] = T(0);
+                        const int lo = min(len, g * seg), hi = min(len, lo + seg);
+                        spmm_chain<T, VEC, false>(lo, hi, col, t, vh + c, ldv, cv0, nc, a);
+#pragma unroll
+                        for (int u = 0; u < V; ++u) part[g][cv0 + u] = a[u];
+                    }
+                __syncthreads();
+                if (tid < kc) {
+                    T sum = part[0][tid];
+                    for (int g = 1; g < kSpmmSegs; ++g) sum += part[g][tid];
+                    oh[(long long) r * ldo + c + tid] = sum;
+                }
+                __syncthreads(); // the next panel / head / row writes part, s_max, s_sum and the parked scores again
+            }
         }
     }
 }

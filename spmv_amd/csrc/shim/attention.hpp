@@ -1,4 +1,5 @@
-// shim/attention.hpp -- part of spmv_shim.hip: O = softmax_rows(scale * Q K^T on the RESIDENT pattern) V in one pass (spmv_hip_attention).  The
+// shim/attention.hpp -- part of spmv_shim.hip: O = softmax_rows(scale * Q K^T on the RESIDENT pattern) V in one pass, for one head
+// (spmv_hip_attention) or for `heads` heads stored side by side in the rows of Q, K, V and O (spmv_hip_attention_heads).  The
 // kernels are kernels/attention.hpp, launched from their own translation unit (spmv_attention.hip, attention_launch); the tables are spmm's
 // batch table and long-row list (spmm_plan).  This side adds what the long rows need: where each one parks its scores.
 #pragma once
@@ -43,12 +44,15 @@ static int attention_plan(spmv_dev *d)
     return SPMV_HIP_OK;
 }
 
-extern "C" int spmv_shim_attention(spmv_dev *d, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v, long long ldv, void *o,
-                                   long long ldo)
+// k and dv are one head's widths: Q and K are heads * k columns wide, V and O heads * dv
+extern "C" int spmv_shim_attention_heads(spmv_dev *d, int heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v,
+                                         long long ldv, void *o, long long ldo)
 {
     if (!d || !d->built) return fail(SPMV_HIP_E_NOSTATE, "attention: schedule not built");
-    if (k < 1 || dv < 1 || ldq < k || ldk < k || ldv < dv || ldo < dv)
-        return fail(SPMV_HIP_E_ARG, "attention: need k >= 1, dv >= 1, ldq >= k, ldk >= k, ldv >= dv, ldo >= dv (k = %d, dv = %d, ld = %lld, %lld, %lld, %lld)", k, dv, ldq, ldk, ldv, ldo);
+    const long long wk = (long long) heads * k, wv = (long long) heads * dv;
+    if (heads < 1 || k < 1 || dv < 1 || wk > INT_MAX || wv > INT_MAX || ldq < wk || ldk < wk || ldv < wv || ldo < wv)
+        return fail(SPMV_HIP_E_ARG, "attention: need heads, k, dv >= 1, heads * k and heads * dv within int, ldq, ldk >= heads * k, ldv, ldo >= heads * dv (heads = %d, k = %d, dv = %d, ld = %lld, %lld, %lld, %lld)",
+                    heads, k, dv, ldq, ldk, ldv, ldo);
     if (d->m > 0 && (!q || !kk || !v || !o)) return fail(SPMV_HIP_E_ARG, "attention: Q, K, V or O is NULL");
     if (d->nnz > 0 && !d->colidx) return fail(SPMV_HIP_E_NOSTATE, "attention: the resident column indices were released (spmv_shim_restore_columns first)");
     if (d->m == 0) return SPMV_HIP_OK;
@@ -60,6 +64,7 @@ extern "C" int spmv_shim_attention(spmv_dev *d, int k, int dv, double scale, con
     Stager stg{d};
     AttentionArgs a;
     a.m = d->m;
+    a.heads = heads;
     a.k = k;
     a.dv = dv;
     a.nb = d->spmm_nb;
@@ -76,20 +81,34 @@ extern "C" int spmv_shim_attention(spmv_dev *d, int k, int dv, double scale, con
     a.kk = kk; a.ldk = ldk;
     a.v = v; a.ldv = ldv;
     a.o = o; a.ldo = ldo;
-    // every row of O gets its dv elements, empty rows their zeros: a staged result is written completely before it is copied back
-    if ((rc = stg.in(d->stage[STAGE_ATT_Q], a.q, a.ldq, (size_t) d->m, k)) || (rc = stg.in(d->stage[STAGE_ATT_K], a.kk, a.ldk, (size_t) d->n, k)) ||
-        (rc = stg.in(d->stage[STAGE_ATT_V], a.v, a.ldv, (size_t) d->n, dv)) || (rc = stg.out(d->stage[STAGE_ATT_O], a.o, a.ldo, (size_t) d->m, dv))) return rc;
-    // the access width changes no bit (kernels/attention.hpp): chosen per call from what the addresses allow
-    a.vec = wide_ok(a.q, a.ldq, s) && wide_ok(a.kk, a.ldk, s) && wide_ok(a.v, a.ldv, s) && wide_ok(a.o, a.ldo, s);
+    // every row of O gets its heads * dv elements, empty rows their zeros: a staged result is written completely before it is copied back
+    if ((rc = stg.in(d->stage[STAGE_ATT_Q], a.q, a.ldq, (size_t) d->m, (int) wk)) || (rc = stg.in(d->stage[STAGE_ATT_K], a.kk, a.ldk, (size_t) d->n, (int) wk)) ||
+        (rc = stg.in(d->stage[STAGE_ATT_V], a.v, a.ldv, (size_t) d->n, (int) wv)) || (rc = stg.out(d->stage[STAGE_ATT_O], a.o, a.ldo, (size_t) d->m, (int) wv))) return rc;
+    // the access width changes no bit (kernels/attention.hpp): chosen per call from what the addresses allow -- with more than one head, every
+    // head's first column has to be 16-byte aligned as well
+    a.vec = wide_ok(a.q, a.ldq, s) && wide_ok(a.kk, a.ldk, s) && wide_ok(a.v, a.ldv, s) && wide_ok(a.o, a.ldo, s) &&
+            (heads == 1 || (((size_t) k * s) % 16 == 0 && ((size_t) dv * s) % 16 == 0));
     const hipError_t e = attention_launch(a, s == sizeof(double), d->stream);
     if (e != hipSuccess) return fail(SPMV_HIP_E_RUNTIME, "attention: launch: %s", hipGetErrorString(e));
     return stg.finish();
 }
 
-extern "C" double spmv_shim_time_attention(spmv_dev *d, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v, long long ldv,
-                                           void *o, long long ldo, int warmup, int iters, float *ms_out)
+extern "C" int spmv_shim_attention(spmv_dev *d, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v, long long ldv, void *o,
+                                   long long ldo)
+{
+    return spmv_shim_attention_heads(d, 1, k, dv, scale, q, ldq, kk, ldk, v, ldv, o, ldo);
+}
+
+extern "C" double spmv_shim_time_attention_heads(spmv_dev *d, int heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v,
+                                                 long long ldv, void *o, long long ldo, int warmup, int iters, float *ms_out)
 {
     if (!d || !d->built || iters <= 0) { fail(SPMV_HIP_E_ARG, "time_attention: bad arguments"); return -1.0; }
     if (!is_device_ptr(q) || !is_device_ptr(kk) || !is_device_ptr(v) || !is_device_ptr(o)) { fail(SPMV_HIP_E_ARG, "time_attention: Q, K, V and O must be device pointers"); return -1.0; }
-    return time_events(d, "time_attention", warmup, iters, ms_out, [&] { return spmv_shim_attention(d, k, dv, scale, q, ldq, kk, ldk, v, ldv, o, ldo); });
+    return time_events(d, "time_attention", warmup, iters, ms_out, [&] { return spmv_shim_attention_heads(d, heads, k, dv, scale, q, ldq, kk, ldk, v, ldv, o, ldo); });
+}
+
+extern "C" double spmv_shim_time_attention(spmv_dev *d, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v, long long ldv,
+                                           void *o, long long ldo, int warmup, int iters, float *ms_out)
+{
+    return spmv_shim_time_attention_heads(d, 1, k, dv, scale, q, ldq, kk, ldk, v, ldv, o, ldo, warmup, iters, ms_out);
 }

@@ -16,6 +16,7 @@
  * Method_Parallel, BASELINE config 1) runs only when option "host_rows" switches it on -- it is a
  * configuration the caller asks for, never a fallback.
  */
+#include <limits.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -1060,6 +1061,42 @@ double spmv_hip_time_attention_launches(spmv_Handle_t h, int k, int dv, double s
     spmv_hip_state *st;
     if (attention_args(h, where, k, dv, Q, ldq, K, ldk, V, ldv, O, ldo, 1) || resident_state(h, where, RESIDENT_NOT_REORDERED, &st) || spmm_columns(h, st, where)) return -1.0;
     return report_time(spmv_shim_time_attention(st->dev, k, dv, scale, Q, ldq, K, ldk, V, ldv, O, ldo, warmup, iters, ms_out), where);
+}
+
+/* ---------------------------------------------------------------- the same for `heads` heads stored side by side in the rows of Q, K, V and O */
+static int attention_heads_args(spmv_Handle_t h, const char *where, int heads, int k, int dv, const void *Q, long long ldq, const void *K, long long ldk, const void *V,
+                                long long ldv, const void *O, long long ldo, int m)
+{
+    if (!h) return refuse(SPMV_HIP_E_ARG, where, "handle is NULL");
+    if (heads < 1 || k < 1 || dv < 1) return refuse(SPMV_HIP_E_ARG, where, "need heads >= 1, k >= 1 and dv >= 1");
+    if ((long long) heads * k > INT_MAX || (long long) heads * dv > INT_MAX) return refuse(SPMV_HIP_E_ARG, where, "heads * k or heads * dv does not fit an int");
+    if (ldq < (long long) heads * k || ldk < (long long) heads * k || ldv < (long long) heads * dv || ldo < (long long) heads * dv)
+        return refuse(SPMV_HIP_E_ARG, where, "need ldq >= heads * k, ldk >= heads * k, ldv >= heads * dv and ldo >= heads * dv");
+    if (m > 0 && (!Q || !K || !V || !O)) return refuse(SPMV_HIP_E_ARG, where, "Q, K, V or O is NULL");
+    return SPMV_HIP_OK;
+}
+
+int spmv_hip_attention_heads(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                             const void *Matrix_Val, int heads, int k, int dv, double scale,
+                             const void *Q, long long ldq, const void *K, long long ldk, const void *V, long long ldv,
+                             void *O, long long ldo)
+{
+    const char *where = "attention_heads";
+    spmv_hip_state *st;
+    int rc;
+    if ((rc = attention_heads_args(handle, where, heads, k, dv, Q, ldq, K, ldk, V, ldv, O, ldo, m)) ||
+        (rc = resident_prologue(handle, where, RESIDENT_NOT_REORDERED, m, RowPtr, ColIdx, Matrix_Val, &st)) || (rc = spmm_columns(handle, st, where))) return rc;
+    return report(spmv_shim_attention_heads(st->dev, heads, k, dv, scale, Q, ldq, K, ldk, V, ldv, O, ldo), where);
+}
+
+double spmv_hip_time_attention_heads_launches(spmv_Handle_t h, int heads, int k, int dv, double scale, const void *Q, long long ldq, const void *K, long long ldk, const void *V,
+                                              long long ldv, void *O, long long ldo, int warmup, int iters, float *ms_out)
+{
+    const char *where = "time_attention_heads_launches";
+    spmv_hip_state *st;
+    if (attention_heads_args(h, where, heads, k, dv, Q, ldq, K, ldk, V, ldv, O, ldo, 1) || resident_state(h, where, RESIDENT_NOT_REORDERED, &st) || spmm_columns(h, st, where))
+        return -1.0;
+    return report_time(spmv_shim_time_attention_heads(st->dev, heads, k, dv, scale, Q, ldq, K, ldk, V, ldv, O, ldo, warmup, iters, ms_out), where);
 }
 
 /* ---------------------------------------------------------------- dQ, dK, dV of the fused attention in two passes over A */

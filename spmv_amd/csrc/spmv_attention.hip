@@ -11,16 +11,16 @@ template <typename T, int CW, bool VEC>
 static void attention_launch_cw(const AttentionArgs &a, hipStream_t stream)
 {
     constexpr int waves = kBlock / kWave, V = SpmmShape<T>::V;
-    // the narrowest lane group that covers a panel's columns (spmm's rule; it changes no bit)
+    // the narrowest lane group that covers a panel's columns of one head (spmm's rule; it changes no bit)
     const int lgv = a.dv <= V ? 0 : (a.dv <= 2 * V ? 1 : (a.dv <= 4 * V ? 2 : 3));
     const T scale = (T) a.scale;
     const T *q = (const T *) a.q, *kk = (const T *) a.kk, *v = (const T *) a.v;
     T *o = (T *) a.o;
     if (a.nb > 0)
-        attention_rows_kernel<T, CW, VEC><<<(a.nb + waves - 1) / waves, kBlock, 0, stream>>>(a.nb, a.split, a.rowptr, a.colidx, a.k, a.dv, lgv, scale, q, a.ldq, kk, a.ldk, v,
+        attention_rows_kernel<T, CW, VEC><<<(a.nb + waves - 1) / waves, kBlock, 0, stream>>>(a.nb, a.split, a.rowptr, a.colidx, a.heads, a.k, a.dv, lgv, scale, q, a.ldq, kk, a.ldk, v,
                                                                                            a.ldv, o, a.ldo);
     if (a.nlong > 0)
-        attention_long_kernel<T, CW, VEC><<<a.nlong < a.cus * 8 ? a.nlong : a.cus * 8, kBlock, 0, stream>>>(a.nlong, a.longs, a.long_off, a.rowptr, a.colidx, a.k, a.dv, lgv,
+        attention_long_kernel<T, CW, VEC><<<a.nlong < a.cus * 8 ? a.nlong : a.cus * 8, kBlock, 0, stream>>>(a.nlong, a.longs, a.long_off, a.rowptr, a.colidx, a.heads, a.k, a.dv, lgv,
                                                                                                           scale, q, a.ldq, kk, a.ldk, v, a.ldv, o, a.ldo, (T *) a.park);
 }
 

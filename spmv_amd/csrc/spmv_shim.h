@@ -142,6 +142,12 @@ int spmv_shim_attention(spmv_dev *d, int k, int dv, double scale, const void *q,
 /* `iters` calls timed with events on the handle's stream (device Q / K / V / O); mean ms, < 0 on failure */
 double spmv_shim_time_attention(spmv_dev *d, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v, long long ldv, void *o,
                                 long long ldo, int warmup, int iters, float *ms_out);
+/* `heads` heads side by side in the rows (spmv_hip_attention_heads): Q m x heads*k, K n x heads*k, V n x heads*dv, O m x heads*dv; head h is
+ * spmv_shim_attention on the columns from h*k and h*dv, in the same two launches.  heads = 1 is spmv_shim_attention. */
+int spmv_shim_attention_heads(spmv_dev *d, int heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v, long long ldv,
+                              void *o, long long ldo);
+double spmv_shim_time_attention_heads(spmv_dev *d, int heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v,
+                                      long long ldv, void *o, long long ldo, int warmup, int iters, float *ms_out);
 
 /* ---- dQ, dK, dV of the fused attention in two passes (shim/attention_backward.hpp; spmv_hip_attention_backward) ----
  * Q m x k, K n x k, V n x dv, G m x dv; dq m x k, dk n x k, dv_out n x dv or NULL (not wanted); row-major with leading dimensions; host or
