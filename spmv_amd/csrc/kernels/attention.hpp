@@ -12,25 +12,23 @@
 // Work split: spmm's tables (shim/spmm.hpp) -- equal-nnz batches of whole rows, one wave per batch, and the list of rows longer than
 // kSpmmLongThr, a workgroup each.
 //
-// Short rows (attention_rows_kernel).  A wave walks its batch in chunks: the next rows, 64 at the most, none of them long, that hold at most
-// kSpmmChunk entries together -- so every row of a chunk is WHOLE in the wave's LDS, which the softmax needs and spmm's chunks do not give.
-//   1. scores   tiles of 64 entries: lane l loads ColIdx of entry l (coalesced) and finds its row among the chunk's row ends (six shuffles);
-//               sddmm's lane groups (att_tile_scores: sddmm_chain, group_sum_dpp) multiply, scale and leave t_p in LDS beside the column.
-//   2. softmax  row_softmax's passes (CW lanes per row, 64 / CW rows side by side, DPP butterflies), reading and writing LDS instead of HBM.
-//   3. P V      spmm's executor: CWV lanes per row, 64 / CWV rows side by side, spmm_chain from LDS over V; the dv panels of KP columns are
-//               looped here with P still in LDS.
+// Short rows (attention_rows_kernel).  A wave walks its batch in chunks of whole rows (chunk_take) -- so every row of a chunk is WHOLE in
+// the wave's LDS, which the softmax needs and spmm's chunks do not give.
+//   1. scores   tiles of 64 entries: lane l loads ColIdx of entry l (coalesced) and finds its row (chunk_row_of); sddmm's lane groups
+//               (att_tile_scores: sddmm_chain, group_sum_dpp) multiply, scale and leave t_p in LDS beside the column.
+//   2. softmax  the row softmax's passes (row_pass_width, row_softmax_regs), reading and writing LDS instead of HBM.
+//   3. P V      rows_times_panels over V, with P still in LDS.
 // Long rows (attention_long_kernel): the scaled scores are parked in a handle-owned array of (sum of the long rows' lengths) elements --
-// written once, then read by the maximum, the sum and the map exactly like row_reduce_long_kernel reads S, and P is written back in place (every
-// element by the thread that read it) --, then kSpmmSegs segments per panel as in spmm_long_kernel.  The parked row is a few KiB per
-// workgroup: L2 traffic.
+// written once, then long_row_softmax in place --, then long_row_panel per panel of dv.  The parked row is a few KiB per workgroup: L2
+// traffic.
 //
-// Arithmetic and order: the composition's, step by step -- s_p is sddmm's dot for this k (kernels/sddmm.hpp), t_p = s_p * scale one plain
-// multiplication, M_i / Z_i / P_p = exp(t_p - M_i) / Z_i the row softmax's by row length (kernels/row_softmax.hpp), O[i, c] spmm's chain
-// (kernels/spmm.hpp: acc = +0, acc = fma(P_p, V[j_p, c], acc) in CSR order; long rows 64 segments added left to right).  The result is a
-// function of the matrix, k, dv and the value type alone.  Contraction is pinned off: the fmas written out are the only fused operations.
-// No atomics, no waiting between workgroups, no scratch memory.
+// Arithmetic and order: the composition's, because its blocks are the composition's (kernels/row_blocks.hpp) -- s_p is sddmm's dot for this
+// k (kernels/sddmm.hpp), t_p = s_p * scale one plain multiplication, M_i / Z_i / P_p = exp(t_p - M_i) / Z_i the row softmax's by row length,
+// O[i, c] spmm's chain.  The result is a function of the matrix, k, dv and the value type alone.  Contraction is pinned off: the fmas written
+// out are the only fused operations.  No atomics, no waiting between workgroups, no scratch memory.
 #pragma once
 #include "common.hpp"
+#include "row_blocks.hpp"
 #include "row_softmax.hpp"
 #include "sddmm.hpp"
 #include "spmm.hpp"
@@ -104,7 +102,7 @@ __global__ __launch_bounds__(kBlock) void attention_rows_kernel(int nb, const in
                                                                 const T *__restrict__ v, long long ldv, T *__restrict__ o, long long ldo)
 {
 #pragma clang fp contract(off)
-    constexpr int V = SpmmShape<T>::V, KP = SpmmShape<T>::KP, CH = kSpmmChunk;
+    constexpr int V = SpmmShape<T>::V, CH = kSpmmChunk;
     __shared__ int s_col[kBlock / kWave][CH];
     __shared__ T s_p[kBlock / kWave][CH];
     const int w = (int) (threadIdx.x / kWave);
@@ -113,21 +111,11 @@ __global__ __launch_bounds__(kBlock) void attention_rows_kernel(int nb, const in
     const int lane0 = threadIdx.x & (kWave - 1);
     const int cwv = 1 << lgv, R = kWave >> lgv;
     const int r0 = split[b], r1 = split[b + 1];
-    const T ninf = -__builtin_huge_val(), nzero = T(-0.0);
+    const T ninf = -__builtin_huge_val();
     for (int g0 = r0; g0 < r1;) {
-        // lane l looks at row g0 + l: the chunk takes the first nr of them
-        int sl = 0, ll = -1;
-        if (g0 + lane0 < r1) {
-            sl = rowptr[g0 + lane0];
-            ll = rowptr[g0 + lane0 + 1] - sl;
-        }
-        const int base = __builtin_amdgcn_readfirstlane(sl); // rowptr[g0]
-        const bool fits = ll >= 0 && ll <= kSpmmLongThr && sl + ll - base <= CH;
-        const unsigned long long bad = ~__ballot(fits);
-        const int nr = bad ? __ffsll((long long) bad) - 1 : kWave;
-        if (nr == 0) { ++g0; continue; } // a long row: nothing of it here
-        const int nq = __shfl(sl + ll, nr - 1, kWave) - base; // entries of the chunk: [base, base + nq) of the matrix
-        const int el = lane0 < nr ? sl + ll - base : 0x7fffffff;  // where the lane's row ends in the chunk: non-decreasing over the lanes
+        const ChunkRows ch = chunk_take(rowptr, g0, r1, lane0);
+        if (ch.nr == 0) { ++g0; continue; } // a long row: nothing of it here
+        const int sl = ch.sl, ll = ch.ll, base = ch.base, nr = ch.nr, nq = ch.nq;
 
         for (int hd = 0; hd < heads; ++hd) {
             const int lane = att_per_head(lane0), subv = lane >> lgv, cv0 = (lane & (cwv - 1)) * V;
@@ -136,10 +124,7 @@ __global__ __launch_bounds__(kBlock) void attention_rows_kernel(int nb, const in
             // 1. columns (the first head reads them from memory, the others from LDS) and scaled scores into LDS
             for (int t0 = 0; t0 < nq; t0 += kWave) {
                 const int e = t0 + lane;
-                int pos = 0; // rows of the chunk that end at or before e: the row of entry e
-#pragma unroll
-                for (int s = kWave / 2; s > 0; s >>= 1)
-                    if (__shfl(el, pos + s - 1, kWave) <= e) pos += s;
+                const int pos = chunk_row_of(ch.el, e);
                 int i = -1, j = 0;
                 if (e < nq) {
                     i = g0 + pos;
@@ -152,15 +137,13 @@ __global__ __launch_bounds__(kBlock) void attention_rows_kernel(int nb, const in
             }
             wave_lds_sync();
 
-            // 2. the row softmax in place in LDS: row_reduce_rows_kernel's passes.  An element is read and written by the same lane.
+            // 2. the row softmax in place in LDS, in row_reduce_rows_kernel's passes.  An element is read and written by the same lane.
             for (int h0 = 0; h0 < nr;) {
                 const int hl = h0 + lane; // lane l looks at chunk row h0 + l
                 const int sh = __shfl(sl, hl & (kWave - 1), kWave) - base, lh0 = __shfl(ll, hl & (kWave - 1), kWave);
                 const int lh = hl < nr ? lh0 : 0;
-                const int wl = row_width(lh);
-                int cw = 1, lg = 0;
-                for (; cw < kWave; cw <<= 1, ++lg)
-                    if ((__ballot(wl > cw) & (~0ull >> (kWave - kWave / cw))) == 0) break;
+                int cw, lg;
+                row_pass_width(row_width(lh), cw, lg);
                 const int sub = lane >> lg, t = lane & (cw - 1);
                 const int s = __shfl(sh, sub, kWave), len = __shfl(lh, sub, kWave);
                 const bool wide = cw == kWave; // the only passes in which a lane holds more than one term
@@ -171,25 +154,7 @@ __global__ __launch_bounds__(kBlock) void attention_rows_kernel(int nb, const in
 #pragma unroll
                     for (int u = 1; u < kRowChain; ++u) x[u] = t + u * kWave < len ? row[t + u * kWave] : ninf;
                 }
-                T mx = x[0];
-                if (wide) {
-#pragma unroll
-                    for (int u = 1; u < kRowChain; ++u) mx = row_max(mx, x[u]);
-                }
-                const T M = row_group_reduce<true>(mx, cw);
-                const T e0 = row_exp(x[0] - M);
-                x[0] = t < len ? e0 : nzero;
-                T acc = x[0];
-                if (wide) {
-#pragma unroll
-                    for (int u = 1; u < kRowChain; ++u) {
-                        const bool have = t + u * kWave < len;
-                        if (__ballot(have) == 0) break;
-                        x[u] = row_exp(x[u] - M);
-                        acc = have ? acc + x[u] : acc;
-                    }
-                }
-                const T Z = row_group_reduce<false>(acc, cw);
+                const T Z = row_softmax_regs(x, t, len, cw, wide);
                 if (t < len) row[t] = x[0] / Z;
                 if (wide) {
 #pragma unroll
@@ -200,21 +165,8 @@ __global__ __launch_bounds__(kBlock) void attention_rows_kernel(int nb, const in
             }
             wave_lds_sync();
 
-            // 3. O = P V: R rows side by side, every (row, column) one lane's chain over the row's entries in CSR order; the panels reuse P
-            for (int h0 = 0; h0 < nr; h0 += R) {
-                const int h = h0 + subv;
-                const int s = __shfl(sl, h & (kWave - 1), kWave) - base, len = __shfl(ll, h & (kWave - 1), kWave);
-                if (h < nr)
-                    for (int c = 0; c < dv; c += KP) {
-                        const int nc = min(V, min(KP, dv - c) - cv0); // <= 0: a lane beyond the panel's columns
-                        if (nc <= 0) continue;
-                        T acc[V];
-#pragma unroll
-                        for (int u = 0; u < V; ++u) acc[u] = T(0);
-                        spmm_chain<T, VEC, false>(s, s + len, s_col[w], s_p[w], vh + c, ldv, cv0, nc, acc);
-                        spmm_store_y<T, VEC>(oh + (long long) (g0 + h) * ldo + c + cv0, nc, acc);
-                    }
-            }
+            // 3. O = P V; the panels reuse P
+            rows_times_panels<T, VEC>(ch, g0, R, subv, cv0, s_col[w], s_p[w], vh, ldv, dv, oh, ldo);
             wave_lds_sync(); // the next head overwrites s_p, the next chunk s_col as well
         }
         g0 += nr;
@@ -255,43 +207,12 @@ __global__ __launch_bounds__(kBlock) void attention_long_kernel(int nlong, const
                 wave_lds_sync();
             }
             __syncthreads();
-            // 2. maximum, sum, map: row_reduce_long_kernel's forward over the parked scores, P written in place
-            T mx = t[tid];
-            for (int p = tid + kBlock; p < len; p += kBlock) mx = row_max(mx, t[p]);
-            mx = row_group_reduce<true>(mx, kWave);
-            if (lane == 0) s_max[w] = mx;
-            __syncthreads();
-            const T M = row_max(row_max(s_max[0], s_max[1]), row_max(s_max[2], s_max[3]));
-            T acc = row_exp(t[tid] - M);
-            for (int p = tid + kBlock; p < len; p += kBlock) acc = acc + row_exp(t[p] - M);
-            acc = row_group_reduce<false>(acc, kWave);
-            if (lane == 0) s_sum[w] = acc;
-            __syncthreads();
-            const T Z = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]);
-            for (int p = tid; p < len; p += kBlock) t[p] = row_exp(t[p] - M) / Z;
-            __syncthreads();
-            // 3. O = P V: kSpmmSegs equal segments (lane group g takes g, g + G, ..), partial sums added left to right in LDS, panel by panel
-            const int seg = (len + kSpmmSegs - 1) / kSpmmSegs;
-            for (int c = 0; c < dv; c += KP) {
-                const int kc = min(KP, dv - c), nc = min(V, kc - cv0);
-                if (nc > 0)
-                    for (int g = subv; g < kSpmmSegs; g += G) {
-                        T a[V];
-#pragma unroll
-                        for (int u = 0; u < V; ++u) a[u] = T(0);
-                        const int lo = min(len, g * seg), hi = min(len, lo + seg);
-                        spmm_chain<T, VEC, false>(lo, hi, col, t, vh + c, ldv, cv0, nc, a);
-#pragma unroll
-                        for (int u = 0; u < V; ++u) part[g][cv0 + u] = a[u];
-                    }
-                __syncthreads();
-                if (tid < kc) {
-                    T sum = part[0][tid];
-                    for (int g = 1; g < kSpmmSegs; ++g) sum += part[g][tid];
-                    oh[(long long) r * ldo + c + tid] = sum;
-                }
-                __syncthreads(); // the next panel / head / row writes part, s_max, s_sum and the parked scores again
-            }
+            // 2. maximum, sum, map over the parked scores, P written in place
+            long_row_softmax(t, t, 0, len, tid, s_max, s_sum);
+            // 3. O = P V, panel by panel; a panel's last barrier also lets the next panel / head / row write part and the parked scores again
+            for (int c = 0; c < dv; c += KP)
+                long_row_panel<T>(len, min(KP, dv - c), G, subv, cv0, tid, part, oh + (long long) r * ldo + c,
+                                  [&](int lo, int hi, int nc, T (&acc)[V]) { spmm_chain<T, VEC, false>(lo, hi, col, t, vh + c, ldv, cv0, nc, acc); });
         }
     }
 }

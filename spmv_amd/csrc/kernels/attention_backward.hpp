@@ -4,30 +4,33 @@
 // in two passes over the pattern: one over A's rows, one over the rows of the device-built A^T.  A's values are neither read nor written.
 //
 // Row pass (attention_bwd_rows_kernel): attention_rows_kernel's structure -- spmm's batch table, a wave per batch, chunks of whole rows
-// with at most kSpmmChunk entries together -- with a second value array per wave in LDS.  Per chunk:
+// (chunk_take) -- with a second value array per wave in LDS.  Per chunk:
 //   A. dots     tiles of 64 entries: the scaled scores t_p (att_tile_scores, sddmm's lane groups for k) into the first array and dP_p
 //               (the same machinery over G and V rows, sddmm's lane groups for dv) into the second; ColIdx is read once for both.
-//   B. softmax  row_softmax's passes over the two arrays: M_i, Z_i, P from the first; D_i from P (still in registers) and dP; P and
-//               dS = P (dP - D) scale written back, every element by the lane that read it.
+//   B. softmax  the row softmax's passes (row_pass_width) over the two arrays: Z_i and exp(t - M_i) from the first, row_softmax_regs
+//               written out (see there); P and D_i by row_dot_regs from those registers and dP; P and dS = P (dP - D) scale written
+//               back, every element by the lane that read it.
 //   C. stores   P and dS coalesced, in CSR order, into the handle-owned arrays attb_p / attb_ds -- P only when dV is wanted, dS only
 //               when dK is: they are what the column pass gathers.
-//   D. dQ       spmm's executor from LDS: values dS, X = K, the k panels looped here with dS still in LDS.
+//   D. dQ       rows_times_panels over K with values dS, still in LDS.
 // Rows longer than kSpmmLongThr (attention_bwd_long_kernel, a workgroup each): the row's own ranges of attb_p / attb_ds are its
-// parking space -- t becomes P in place, dP becomes dS in place, every element written by the thread that read it --, then kSpmmSegs
-// segments per panel as in spmm_long_kernel.
+// parking space -- t becomes P in place (long_row_softmax), dP becomes dS in place (long_row_dot), every element written by the thread
+// that read it --, then long_row_panel per panel of k.
 //
-// Column pass (attention_bwd_cols_kernel, attention_bwd_cols_long_kernel): spmm's executors on A^T's tables (its rowptr, its colidx = rows of
-// A, its own batch table and long list).  There is no value array: a chunk loads perm[q] (the CSR index in A of A^T's entry q) coalesced
-// and gathers attb_p[perm[q]] and / or attb_ds[perm[q]] into the wave's two LDS arrays.  Two chains run off the one index stream, one
-// after the other: dV's panel against G rows with values P, dK's panel against Q rows with values dS.  One launch does panel r of both.
+// Column pass (attention_bwd_cols_kernel, attention_bwd_cols_long_kernel): spmm's executors (staged_walk, long_row_panel) on A^T's tables
+// (its rowptr, its colidx = rows of A, its own batch table and long list).  There is no value array: a chunk loads perm[q] (the CSR index in
+// A of A^T's entry q) coalesced and gathers attb_p[perm[q]] and / or attb_ds[perm[q]] into the wave's two LDS arrays.  Two chains run off
+// the one index stream, one after the other: dV's panel against G rows with values P, dK's panel against Q rows with values dS.  One launch
+// does panel r of both.
 //
-// Arithmetic and order: the composition's, step by step -- t and P are spmv_hip_attention's; dP is sddmm's dot for dv; D is
-// row_softmax_backward's chain (first term a plain product, every further one fma(P, dP, chain), then the tree) by row length; dS is one
-// subtraction and two plain multiplications; dQ, dK and dV are spmm's chains (rows / columns of up to kSpmmLongThr entries from +0 in
-// stored order, longer ones kSpmmSegs segments added left to right).  Contraction is pinned off: the fmas written out are the only fused
-// operations.  No atomics, no waiting between workgroups, no scratch memory.
+// Arithmetic and order: the composition's, because its blocks are the composition's (kernels/row_blocks.hpp) -- t and P are
+// spmv_hip_attention's; dP is sddmm's dot for dv; D is row_softmax_backward's by row length; dS is one subtraction and two plain
+// multiplications; dQ, dK and dV are spmm's chains.  Contraction is pinned off: the fmas written out are the only fused operations.
+// No atomics, no waiting between workgroups, no scratch memory.
 #pragma once
 #include "attention.hpp"
+#include "dispatch.hpp"
+#include "row_blocks.hpp"
 
 namespace spmv {
 
@@ -54,44 +57,7 @@ hipError_t attention_backward_launch(const AttentionBwdArgs &a, bool f64, hipStr
 template <typename T, bool VEC>
 __device__ __forceinline__ void attb_tile_dots(int cw, int i, int j, int lane, int dv, const T *__restrict__ g, long long ldg, const T *__restrict__ v, long long ldv, T *slot)
 {
-    switch (cw) {
-    case 1: att_tile_scores<T, 1, VEC>(i, j, lane, dv, g, ldg, v, ldv, T(1), slot); break;
-    case 2: att_tile_scores<T, 2, VEC>(i, j, lane, dv, g, ldg, v, ldv, T(1), slot); break;
-    case 4: att_tile_scores<T, 4, VEC>(i, j, lane, dv, g, ldg, v, ldv, T(1), slot); break;
-    default: att_tile_scores<T, 8, VEC>(i, j, lane, dv, g, ldg, v, ldv, T(1), slot); break;
-    }
-}
-
-// spmm_chain over the global streams of A^T with the values gathered through perm: acc[t] += val[perm[j]] * X[col[j]][c0 + t], j = s .. e - 1
-template <typename T, bool VEC>
-__device__ __forceinline__ void attb_chain_gather(int s, int e, const int *__restrict__ colidx, const int *__restrict__ perm, const T *val, const T *__restrict__ x,
-                                                  long long ldx, int c0, int nc, T (&acc)[SpmmShape<T>::V])
-{
-    constexpr int V = SpmmShape<T>::V, U = 4;
-    int j = s;
-    for (; j + U <= e; j += U) {
-        int c[U];
-        T v[U], xv[U][V];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            c[u] = ld_stream(colidx + j + u);
-            v[u] = val[ld_stream(perm + j + u)];
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) spmm_load_x<T, VEC>(x + (long long) c[u] * ldx + c0, nc, xv[u]);
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-#pragma unroll
-            for (int t = 0; t < V; ++t) acc[t] = fmadd(v[u], xv[u][t], acc[t]);
-    }
-    for (; j < e; ++j) {
-        const int c = ld_stream(colidx + j);
-        const T v = val[ld_stream(perm + j)];
-        T xv[V];
-        spmm_load_x<T, VEC>(x + (long long) c * ldx + c0, nc, xv);
-#pragma unroll
-        for (int t = 0; t < V; ++t) acc[t] = fmadd(v, xv[t], acc[t]);
-    }
+    with_width(cw, [&](auto CW) { att_tile_scores<T, decltype(CW)::value, VEC>(i, j, lane, dv, g, ldg, v, ldv, T(1), slot); });
 }
 
 // One wave per batch [split[b], split[b + 1]) of whole rows; rows longer than kSpmmLongThr are left to attention_bwd_long_kernel.
@@ -105,7 +71,7 @@ __global__ __launch_bounds__(kBlock) void attention_bwd_rows_kernel(int nb, cons
                                                                     T *__restrict__ ds_out)
 {
 #pragma clang fp contract(off)
-    constexpr int V = SpmmShape<T>::V, KP = SpmmShape<T>::KP, CH = kSpmmChunk;
+    constexpr int V = SpmmShape<T>::V, CH = kSpmmChunk;
     __shared__ int s_col[kBlock / kWave][CH];
     __shared__ T s_p[kBlock / kWave][CH];
     __shared__ T s_d[kBlock / kWave][CH];
@@ -117,27 +83,14 @@ __global__ __launch_bounds__(kBlock) void attention_bwd_rows_kernel(int nb, cons
     const int r0 = split[b], r1 = split[b + 1];
     const T ninf = -__builtin_huge_val(), nzero = T(-0.0);
     for (int g0 = r0; g0 < r1;) {
-        // lane l looks at row g0 + l: the chunk takes the first nr of them
-        int sl = 0, ll = -1;
-        if (g0 + lane < r1) {
-            sl = rowptr[g0 + lane];
-            ll = rowptr[g0 + lane + 1] - sl;
-        }
-        const int base = __builtin_amdgcn_readfirstlane(sl); // rowptr[g0]
-        const bool fits = ll >= 0 && ll <= kSpmmLongThr && sl + ll - base <= CH;
-        const unsigned long long bad = ~__ballot(fits);
-        const int nr = bad ? __ffsll((long long) bad) - 1 : kWave;
-        if (nr == 0) { ++g0; continue; } // a long row: nothing of it here
-        const int nq = __shfl(sl + ll, nr - 1, kWave) - base; // entries of the chunk: [base, base + nq) of the matrix
-        const int el = lane < nr ? sl + ll - base : 0x7fffffff;  // where the lane's row ends in the chunk: non-decreasing over the lanes
+        const ChunkRows ch = chunk_take(rowptr, g0, r1, lane);
+        if (ch.nr == 0) { ++g0; continue; } // a long row: nothing of it here
+        const int sl = ch.sl, ll = ch.ll, base = ch.base, nr = ch.nr, nq = ch.nq;
 
         // A. columns, scaled scores and dP into LDS
         for (int t0 = 0; t0 < nq; t0 += kWave) {
             const int e = t0 + lane;
-            int pos = 0; // rows of the chunk that end at or before e: the row of entry e
-#pragma unroll
-            for (int s = kWave / 2; s > 0; s >>= 1)
-                if (__shfl(el, pos + s - 1, kWave) <= e) pos += s;
+            const int pos = chunk_row_of(ch.el, e);
             int i = -1, j = 0;
             if (e < nq) {
                 j = ld_stream(colidx + base + e);
@@ -149,15 +102,13 @@ __global__ __launch_bounds__(kBlock) void attention_bwd_rows_kernel(int nb, cons
         }
         wave_lds_sync();
 
-        // B. the row softmax and its backward in place in LDS: row_reduce_rows_kernel's passes.  An element is read and written by the same lane.
+        // B. the row softmax and its backward in place in LDS, in row_reduce_rows_kernel's passes.  An element is read and written by the same lane.
         for (int h0 = 0; h0 < nr;) {
             const int hl = h0 + lane; // lane l looks at chunk row h0 + l
             const int sh = __shfl(sl, hl & (kWave - 1), kWave) - base, lh0 = __shfl(ll, hl & (kWave - 1), kWave);
             const int lh = hl < nr ? lh0 : 0;
-            const int wl = row_width(lh);
-            int cw = 1, lg = 0;
-            for (; cw < kWave; cw <<= 1, ++lg)
-                if ((__ballot(wl > cw) & (~0ull >> (kWave - kWave / cw))) == 0) break;
+            int cw, lg;
+            row_pass_width(row_width(lh), cw, lg);
             const int sub = lane >> lg, t = lane & (cw - 1);
             const int s = __shfl(sh, sub, kWave), len = __shfl(lh, sub, kWave);
             const bool wide = cw == kWave; // the only passes in which a lane holds more than one term
@@ -173,6 +124,8 @@ __global__ __launch_bounds__(kBlock) void attention_bwd_rows_kernel(int nb, cons
                     y[u] = have ? drow[t + u * kWave] : nzero;
                 }
             }
+            // row_softmax_regs, written out: as a call it costs attention_bwd_rows_kernel<float, 4, false> two registers and with them, at
+            // 129, a wave per SIMD.  The one copy of that block: keep the two alike.
             T mx = x[0];
             if (wide) {
 #pragma unroll
@@ -192,19 +145,7 @@ __global__ __launch_bounds__(kBlock) void attention_bwd_rows_kernel(int nb, cons
                 }
             }
             const T Z = row_group_reduce<false>(acc, cw);
-            // P, then D_i: the first term a plain product, every further one an fma onto the chain
-            x[0] = x[0] / Z;
-            T dacc = t < len ? x[0] * y[0] : nzero;
-            if (wide) {
-#pragma unroll
-                for (int u = 1; u < kRowChain; ++u) {
-                    const bool have = t + u * kWave < len;
-                    if (__ballot(have) == 0) break;
-                    x[u] = x[u] / Z;
-                    dacc = have ? fmadd(x[u], y[u], dacc) : dacc;
-                }
-            }
-            const T D = row_group_reduce<false>(dacc, cw);
+            const T D = row_dot_regs<T, true>(x, y, t, len, cw, wide, Z); // x becomes P
             if (t < len) {
                 row[t] = x[0];
                 drow[t] = att_scale(x[0] * (y[0] - D), scale);
@@ -227,22 +168,8 @@ __global__ __launch_bounds__(kBlock) void attention_bwd_rows_kernel(int nb, cons
         if (ds_out)
             for (int e = lane; e < nq; e += kWave) ds_out[base + e] = s_d[w][e];
 
-        // D. dQ = A_dS K: R rows side by side, every (row, column) one lane's chain over the row's entries in CSR order; the panels reuse dS
-        if (dq)
-            for (int h0 = 0; h0 < nr; h0 += R) {
-                const int h = h0 + subk;
-                const int s = __shfl(sl, h & (kWave - 1), kWave) - base, len = __shfl(ll, h & (kWave - 1), kWave);
-                if (h < nr)
-                    for (int c = 0; c < k; c += KP) {
-                        const int nc = min(V, min(KP, k - c) - ck0); // <= 0: a lane beyond the panel's columns
-                        if (nc <= 0) continue;
-                        T acc[V];
-#pragma unroll
-                        for (int u = 0; u < V; ++u) acc[u] = T(0);
-                        spmm_chain<T, VEC, false>(s, s + len, s_col[w], s_d[w], kk + c, ldk, ck0, nc, acc);
-                        spmm_store_y<T, VEC>(dq + (long long) (g0 + h) * lddq + c + ck0, nc, acc);
-                    }
-            }
+        // D. dQ = A_dS K; the panels reuse dS
+        if (dq) rows_times_panels<T, VEC>(ch, g0, R, subk, ck0, s_col[w], s_d[w], kk, ldk, k, dq, lddq);
         wave_lds_sync(); // the next chunk overwrites s_col / s_p / s_d
         g0 += nr;
     }
@@ -282,54 +209,17 @@ __global__ __launch_bounds__(kBlock) void attention_bwd_long_kernel(int nlong, c
             wave_lds_sync();
         }
         __syncthreads();
-        // 2. maximum, sum, map: row_reduce_long_kernel's forward over the parked scores, P written in place
-        T mx = t[tid];
-        for (int p = tid + kBlock; p < len; p += kBlock) mx = row_max(mx, t[p]);
-        mx = row_group_reduce<true>(mx, kWave);
-        if (lane == 0) s_max[w] = mx;
-        __syncthreads();
-        const T M = row_max(row_max(s_max[0], s_max[1]), row_max(s_max[2], s_max[3]));
-        T acc = row_exp(t[tid] - M);
-        for (int p = tid + kBlock; p < len; p += kBlock) acc = acc + row_exp(t[p] - M);
-        acc = row_group_reduce<false>(acc, kWave);
-        if (lane == 0) s_sum[w] = acc;
-        __syncthreads();
-        const T Z = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]);
-        for (int p = tid; p < len; p += kBlock) t[p] = row_exp(t[p] - M) / Z;
-        __syncthreads(); // s_sum is written again below
-        // 3. row_reduce_long_kernel's backward over P and the parked dP, dS written in place
-        T dacc = t[tid] * d[tid];
-        for (int p = tid + kBlock; p < len; p += kBlock) dacc = fmadd(t[p], d[p], dacc);
-        dacc = row_group_reduce<false>(dacc, kWave);
-        if (lane == 0) s_sum[w] = dacc;
-        __syncthreads();
-        const T D = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]);
+        // 2. maximum, sum, map over the parked scores, P written in place
+        long_row_softmax(t, t, 0, len, tid, s_max, s_sum);
+        // 3. D over P and the parked dP, dS written in place
+        const T D = long_row_dot(t, d, 0, len, tid, s_sum);
         for (int p = tid; p < len; p += kBlock) d[p] = att_scale(t[p] * (d[p] - D), scale);
         __syncthreads();
-        // 4. dQ = A_dS K: kSpmmSegs equal segments (lane group g takes g, g + G, ..), partial sums added left to right in LDS, panel by panel
-        if (dq) {
-            const int seg = (len + kSpmmSegs - 1) / kSpmmSegs;
-            for (int c = 0; c < k; c += KP) {
-                const int kc = min(KP, k - c), nc = min(V, kc - ck0);
-                if (nc > 0)
-                    for (int gi = subk; gi < kSpmmSegs; gi += G) {
-                        T a[V];
-#pragma unroll
-                        for (int u = 0; u < V; ++u) a[u] = T(0);
-                        const int lo = min(len, gi * seg), hi = min(len, lo + seg);
-                        spmm_chain<T, VEC, false>(lo, hi, col, d, kk + c, ldk, ck0, nc, a);
-#pragma unroll
-                        for (int u = 0; u < V; ++u) part[gi][ck0 + u] = a[u];
-                    }
-                __syncthreads();
-                if (tid < kc) {
-                    T sum = part[0][tid];
-                    for (int gi = 1; gi < kSpmmSegs; ++gi) sum += part[gi][tid];
-                    dq[(long long) r * lddq + c + tid] = sum;
-                }
-                __syncthreads(); // the next panel / row writes part, s_max, s_sum again
-            }
-        }
+        // 4. dQ = A_dS K, panel by panel; a panel's last barrier also lets the next panel / row write part, s_max, s_sum again
+        if (dq)
+            for (int c = 0; c < k; c += KP)
+                long_row_panel<T>(len, min(KP, k - c), G, subk, ck0, tid, part, dq + (long long) r * lddq + c,
+                                  [&](int lo, int hi, int nc, T (&acc)[V]) { spmm_chain<T, VEC, false>(lo, hi, col, d, kk + c, ldk, ck0, nc, acc); });
     }
 }
 
@@ -361,25 +251,18 @@ __global__ __launch_bounds__(kBlock) void attention_bwd_cols_kernel(int nb, cons
         T accv[V], acck[V];
 #pragma unroll
         for (int t = 0; t < V; ++t) accv[t] = acck[t] = T(0);
-        const int hi = rowptr[g1];
-        for (int p = rowptr[g0]; p < hi;) {
-            const unsigned long long inside = __ballot(longrow && s <= p && e > p);
-            if (inside) { p = __builtin_amdgcn_readlane(e, __ffsll((long long) inside) - 1); continue; } // p is in a long row: past it
-            const unsigned long long next = __ballot(longrow && s > p);
-            const int lim = next ? __builtin_amdgcn_readlane(s, __ffsll((long long) next) - 1) : hi;
-            const int nq = min(CH, lim - p);
-            for (int i = lane; i < nq; i += kWave) {
-                s_col[w][i] = ld_stream(colidx + p + i);
-                const int pp = ld_stream(perm + p + i);
+        staged_walk(
+            rowptr, g0, g1, s, e, longrow, lane,
+            [&](int i, int p) {
+                s_col[w][i] = ld_stream(colidx + p);
+                const int pp = ld_stream(perm + p);
                 if (kcv > 0) s_p[w][i] = pv[pp];
                 if (kck > 0) s_d[w][i] = dsv[pp];
-            }
-            wave_lds_sync();
-            if (!longrow && ncv > 0) spmm_chain<T, VEC, false>(max(s, p) - p, min(e, p + nq) - p, s_col[w], s_p[w], g, ldg, c0, ncv, accv);
-            if (!longrow && nck > 0) spmm_chain<T, VEC, false>(max(s, p) - p, min(e, p + nq) - p, s_col[w], s_d[w], q, ldq, c0, nck, acck);
-            wave_lds_sync();
-            p += nq;
-        }
+            },
+            [&](int lo, int hi) {
+                if (!longrow && ncv > 0) spmm_chain<T, VEC, false>(lo, hi, s_col[w], s_p[w], g, ldg, c0, ncv, accv);
+                if (!longrow && nck > 0) spmm_chain<T, VEC, false>(lo, hi, s_col[w], s_d[w], q, ldq, c0, nck, acck);
+            });
         if (have && !longrow && ncv > 0) spmm_store_y<T, VEC>(dvo + (long long) r * lddv + c0, ncv, accv);
         if (have && !longrow && nck > 0) spmm_store_y<T, VEC>(dk + (long long) r * lddk + c0, nck, acck);
     }
@@ -395,34 +278,19 @@ __global__ __launch_bounds__(kBlock) void attention_bwd_cols_long_kernel(int nlo
 #pragma clang fp contract(off)
     constexpr int V = SpmmShape<T>::V, KP = SpmmShape<T>::KP, G = kBlock / CW;
     __shared__ T part[kSpmmSegs][KP];
-    const int sub = (int) threadIdx.x / CW, c0 = ((int) threadIdx.x % CW) * V;
+    const int tid = (int) threadIdx.x, sub = tid / CW, c0 = (tid % CW) * V;
     for (int i = blockIdx.x; i < nlong; i += gridDim.x) {
         const int r = longs[i], s = rowptr[r], e = rowptr[r + 1];
-        const int seg = (e - s + kSpmmSegs - 1) / kSpmmSegs;
         for (int o = 0; o < 2; ++o) { // 0: dV (values P, X = G); 1: dK (values dS, X = Q)
             const int kc = o ? kck : kcv;
             if (kc <= 0) continue; // uniform over the workgroup
             const T *val = o ? dsv : pv, *x = o ? q : g;
             const long long ldx = o ? ldq : ldg;
-            const int nc = min(V, kc - c0);
-            if (nc > 0)
-                for (int gi = sub; gi < kSpmmSegs; gi += G) {
-                    T acc[V];
-#pragma unroll
-                    for (int t = 0; t < V; ++t) acc[t] = T(0);
-                    const int a = min(e, s + gi * seg), z = min(e, a + seg);
-                    attb_chain_gather<T, VEC>(a, z, colidx, perm, val, x, ldx, c0, nc, acc);
-#pragma unroll
-                    for (int t = 0; t < V; ++t) part[gi][c0 + t] = acc[t];
-                }
-            __syncthreads();
-            if ((int) threadIdx.x < kc) {
-                T sum = part[0][threadIdx.x];
-                for (int gi = 1; gi < kSpmmSegs; ++gi) sum += part[gi][threadIdx.x];
-                if (o) dk[(long long) r * lddk + threadIdx.x] = sum;
-                else dvo[(long long) r * lddv + threadIdx.x] = sum;
-            }
-            __syncthreads();
+            long_row_panel<T>(e - s, kc, G, sub, c0, tid, part, o ? dk + (long long) r * lddk : dvo + (long long) r * lddv, [&](int lo, int hi, int nc, T (&acc)[V]) {
+                // the global streams of A^T, the values gathered through perm
+                spmm_chain_with<T, VEC>(
+                    s + lo, s + hi, [=](int j) { return ld_stream(colidx + j); }, [=](int j) { return val[ld_stream(perm + j)]; }, x, ldx, c0, nc, acc);
+            });
         }
     }
 }

@@ -44,9 +44,6 @@ struct SddmmArgs {
     bool vec = false; // u, v, ldu and ldv allow 16-byte loads
 };
 
-// lanes per entry for k columns of W per lane
-inline int sddmm_group_width(int k, int W) { return k <= W ? 1 : (k <= 2 * W ? 2 : (k <= 4 * W ? 4 : 8)); }
-
 // spmv_sddmm.hip: the one launch of a call on `stream`
 hipError_t sddmm_launch(const SddmmArgs &a, bool f64, hipStream_t stream);
 

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels/common.hpp"
+#include "kernels/dispatch.hpp"
 #include "kernels/attention.hpp"
 
 namespace spmv {
@@ -10,9 +11,8 @@ namespace spmv {
 template <typename T, int CW, bool VEC>
 static void attention_launch_cw(const AttentionArgs &a, hipStream_t stream)
 {
-    constexpr int waves = kBlock / kWave, V = SpmmShape<T>::V;
-    // the narrowest lane group that covers a panel's columns of one head (spmm's rule; it changes no bit)
-    const int lgv = a.dv <= V ? 0 : (a.dv <= 2 * V ? 1 : (a.dv <= 4 * V ? 2 : 3));
+    constexpr int waves = kBlock / kWave;
+    const int lgv = panel_group_lg<T>(a.dv); // the narrowest lane group that covers a panel's columns of one head (spmm's rule; it changes no bit)
     const T scale = (T) a.scale;
     const T *q = (const T *) a.q, *kk = (const T *) a.kk, *v = (const T *) a.v;
     T *o = (T *) a.o;
@@ -24,22 +24,14 @@ static void attention_launch_cw(const AttentionArgs &a, hipStream_t stream)
                                                                                                           scale, q, a.ldq, kk, a.ldk, v, a.ldv, o, a.ldo, (T *) a.park);
 }
 
-template <typename T, bool VEC>
-static void attention_launch_t(const AttentionArgs &a, hipStream_t stream)
-{
-    switch (sddmm_group_width(a.k, SddmmShape<T>::W)) { // a function of k and the value type alone: it fixes the scores' summation order
-    case 1: attention_launch_cw<T, 1, VEC>(a, stream); break;
-    case 2: attention_launch_cw<T, 2, VEC>(a, stream); break;
-    case 4: attention_launch_cw<T, 4, VEC>(a, stream); break;
-    default: attention_launch_cw<T, 8, VEC>(a, stream); break;
-    }
-}
-
 hipError_t attention_launch(const AttentionArgs &a, bool f64, hipStream_t stream)
 {
     if (a.m <= 0) return hipSuccess;
-    if (f64) { if (a.vec) attention_launch_t<double, true>(a, stream); else attention_launch_t<double, false>(a, stream); }
-    else { if (a.vec) attention_launch_t<float, true>(a, stream); else attention_launch_t<float, false>(a, stream); }
+    with_type_vec(f64, a.vec, [&](auto t, auto vec) {
+        using T = decltype(t);
+        // sddmm's lane group for k: a function of k and the value type alone, it fixes the scores' summation order
+        with_width(panel_group_width<T>(a.k), [&](auto CW) { attention_launch_cw<T, decltype(CW)::value, decltype(vec)::value>(a, stream); });
+    });
     return hipGetLastError();
 }
 

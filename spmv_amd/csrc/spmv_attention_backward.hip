@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels/common.hpp"
+#include "kernels/dispatch.hpp"
 #include "kernels/attention_backward.hpp"
 
 namespace spmv {
@@ -12,10 +13,9 @@ namespace spmv {
 template <typename T, int CW, bool VEC>
 static void attention_bwd_rows_cw(const AttentionBwdArgs &a, hipStream_t stream)
 {
-    constexpr int waves = kBlock / kWave, V = SpmmShape<T>::V;
-    // the narrowest lane group that covers a panel's columns (spmm's rule; it changes no bit)
-    const int lgk = a.k <= V ? 0 : (a.k <= 2 * V ? 1 : (a.k <= 4 * V ? 2 : 3));
-    const int cwd = sddmm_group_width(a.dv, SddmmShape<T>::W); // a function of dv and the value type alone: it fixes dP's summation order
+    constexpr int waves = kBlock / kWave;
+    const int lgk = panel_group_lg<T>(a.k);    // the narrowest lane group that covers a panel's columns (spmm's rule; it changes no bit)
+    const int cwd = panel_group_width<T>(a.dv); // a function of dv and the value type alone: it fixes dP's summation order
     const T scale = (T) a.scale;
     const T *q = (const T *) a.q, *kk = (const T *) a.kk, *v = (const T *) a.v, *g = (const T *) a.g;
     T *dq = (T *) a.dq, *p = (T *) a.p, *ds = (T *) a.ds;
@@ -48,31 +48,22 @@ static void attention_bwd_cols_cw(const AttentionBwdArgs &a, int c, int kcv, int
 template <typename T, bool VEC>
 static void attention_bwd_launch_t(const AttentionBwdArgs &a, hipStream_t stream)
 {
-    constexpr int V = SpmmShape<T>::V, KP = SpmmShape<T>::KP;
-    if (a.m > 0)
-        switch (sddmm_group_width(a.k, SddmmShape<T>::W)) { // a function of k and the value type alone: it fixes the scores' summation order
-        case 1: attention_bwd_rows_cw<T, 1, VEC>(a, stream); break;
-        case 2: attention_bwd_rows_cw<T, 2, VEC>(a, stream); break;
-        case 4: attention_bwd_rows_cw<T, 4, VEC>(a, stream); break;
-        default: attention_bwd_rows_cw<T, 8, VEC>(a, stream); break;
-        }
+    constexpr int KP = SpmmShape<T>::KP;
+    // sddmm's lane group for k: a function of k and the value type alone, it fixes the scores' summation order
+    if (a.m > 0) with_width(panel_group_width<T>(a.k), [&](auto CW) { attention_bwd_rows_cw<T, decltype(CW)::value, VEC>(a, stream); });
     if (!a.dk && !a.dvo) return;
     const int wk = a.dk ? a.k : 0, wv = a.dvo ? a.dv : 0;
     for (int c = 0; c < wk || c < wv; c += KP) { // panel c / KP of both outputs in one pass over A^T
         const int kcv = wv - c < KP ? wv - c : KP, kck = wk - c < KP ? wk - c : KP; // <= 0: that output has no such panel
         const int kc = kcv > kck ? kcv : kck;
         // the narrowest lane group that covers the wider panel's columns
-        if (kc <= V) attention_bwd_cols_cw<T, 1, VEC>(a, c, kcv, kck, stream);
-        else if (kc <= 2 * V) attention_bwd_cols_cw<T, 2, VEC>(a, c, kcv, kck, stream);
-        else if (kc <= 4 * V) attention_bwd_cols_cw<T, 4, VEC>(a, c, kcv, kck, stream);
-        else attention_bwd_cols_cw<T, 8, VEC>(a, c, kcv, kck, stream);
+        with_width(panel_group_width<T>(kc), [&](auto CW) { attention_bwd_cols_cw<T, decltype(CW)::value, VEC>(a, c, kcv, kck, stream); });
     }
 }
 
 hipError_t attention_backward_launch(const AttentionBwdArgs &a, bool f64, hipStream_t stream)
 {
-    if (f64) { if (a.vec) attention_bwd_launch_t<double, true>(a, stream); else attention_bwd_launch_t<double, false>(a, stream); }
-    else { if (a.vec) attention_bwd_launch_t<float, true>(a, stream); else attention_bwd_launch_t<float, false>(a, stream); }
+    with_type_vec(f64, a.vec, [&](auto t, auto vec) { attention_bwd_launch_t<decltype(t), decltype(vec)::value>(a, stream); });
     return hipGetLastError();
 }
 

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels/common.hpp"
+#include "kernels/dispatch.hpp"
 #include "kernels/sddmm.hpp"
 
 namespace spmv {
@@ -16,22 +17,14 @@ static void sddmm_launch_cw(const SddmmArgs &a, hipStream_t stream)
                                                                                          (T *) a.out);
 }
 
-template <typename T, bool VEC>
-static void sddmm_launch_t(const SddmmArgs &a, hipStream_t stream)
-{
-    switch (sddmm_group_width(a.k, SddmmShape<T>::W)) { // a function of k and the value type alone: it fixes the summation order
-    case 1: sddmm_launch_cw<T, 1, VEC>(a, stream); break;
-    case 2: sddmm_launch_cw<T, 2, VEC>(a, stream); break;
-    case 4: sddmm_launch_cw<T, 4, VEC>(a, stream); break;
-    default: sddmm_launch_cw<T, 8, VEC>(a, stream); break;
-    }
-}
-
 hipError_t sddmm_launch(const SddmmArgs &a, bool f64, hipStream_t stream)
 {
     if (a.nnz <= 0 || a.m <= 0) return hipSuccess;
-    if (f64) { if (a.vec) sddmm_launch_t<double, true>(a, stream); else sddmm_launch_t<double, false>(a, stream); }
-    else { if (a.vec) sddmm_launch_t<float, true>(a, stream); else sddmm_launch_t<float, false>(a, stream); }
+    with_type_vec(f64, a.vec, [&](auto t, auto vec) {
+        using T = decltype(t);
+        // lanes per entry: a function of k and the value type alone, it fixes the summation order
+        with_width(panel_group_width<T>(a.k), [&](auto CW) { sddmm_launch_cw<T, decltype(CW)::value, decltype(vec)::value>(a, stream); });
+    });
     return hipGetLastError();
 }
 

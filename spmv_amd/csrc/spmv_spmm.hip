@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels/common.hpp"
+#include "kernels/dispatch.hpp"
 #include "kernels/spmm.hpp"
 
 namespace spmv {
@@ -20,21 +21,13 @@ static void spmm_launch_cw(const SpmmArgs &a, hipStream_t stream)
                                                                                                   a.ldx, y, a.ldy);
 }
 
-template <typename T, bool VEC>
-static void spmm_launch_t(const SpmmArgs &a, hipStream_t stream)
-{
-    constexpr int V = SpmmShape<T>::V;
-    // the narrowest lane group that covers the panel's columns
-    if (a.kc <= V) spmm_launch_cw<T, 1, VEC>(a, stream);
-    else if (a.kc <= 2 * V) spmm_launch_cw<T, 2, VEC>(a, stream);
-    else if (a.kc <= 4 * V) spmm_launch_cw<T, 4, VEC>(a, stream);
-    else spmm_launch_cw<T, 8, VEC>(a, stream);
-}
-
 hipError_t spmm_launch(const SpmmArgs &a, bool f64, hipStream_t stream)
 {
-    if (f64) { if (a.vec) spmm_launch_t<double, true>(a, stream); else spmm_launch_t<double, false>(a, stream); }
-    else { if (a.vec) spmm_launch_t<float, true>(a, stream); else spmm_launch_t<float, false>(a, stream); }
+    with_type_vec(f64, a.vec, [&](auto t, auto vec) {
+        using T = decltype(t);
+        // the narrowest lane group that covers the panel's columns
+        with_width(panel_group_width<T>(a.kc), [&](auto CW) { spmm_launch_cw<T, decltype(CW)::value, decltype(vec)::value>(a, stream); });
+    });
     return hipGetLastError();
 }
 
