@@ -317,6 +317,39 @@ int spmv_hip_attention_backward(spmv_Handle_t handle, BASIC_INT_TYPE m, const BA
                                 void *dK, long long lddk,                /* n x k,  or NULL */
                                 void *dV, long long lddv);               /* n x dv, or NULL */
 
+/* ---- the gradients of spmv_hip_attention_heads: all heads in two passes per group of heads -----------
+ * The layout is spmv_hip_attention_heads': Q and dQ are m x heads*k, K and dK n x heads*k, V and dV n x heads*dv, G = dL/dO m x heads*dv, all
+ * row-major with leading dimensions at least the full widths; k, dv and scale are ONE head's; each operand may be a host or a device pointer; a
+ * NULL output means "not wanted", exactly as in spmv_hip_attention_backward.  For every h, head h's block of every wanted output has exactly
+ * the bits spmv_hip_attention_backward writes on the h-th column slices (pointers advanced by h*k and h*dv, the same leading dimensions);
+ * heads = 1 IS spmv_hip_attention_backward.  Everything that section promises -- the order, the special values, the invariance under ld,
+ * alignment, access width, pointer kind, stream, async, method and which outputs are wanted -- therefore holds head by head; a NaN row in one
+ * head touches no other head.  A's VALUES are not read, and the handle's resident values are NOT MODIFIED.  Returns 0 or an SPMV_HIP_E_* code.
+ *   - Writes: exactly the first heads*k (dQ, dK) or heads*dv (dV) elements of each row of each wanted output; padding is never read or
+ *     written.  Empty rows, empty columns, nnz = 0 and m = 0: the single-head call's rules, at the full widths.
+ *   - Groups of heads.  The two handle-owned arrays become HG planes of nnz elements each, plane g one head's P or dS in CSR order, and a call
+ *     runs ceil(heads / HG) rounds: one row pass and one column pass over HG heads, the head loop INSIDE the kernels -- so per round the
+ *     pattern, the chunking and the transpose's index map are paid once and the launch count is that of one single-head call.  HG: option
+ *     "attention_backward_heads" = n > 0 means at most n heads per round; 0 (default) the largest HG <= heads with 2*HG*s*nnz bytes (s = the
+ *     value size) within one eighth of the device's memory -- the device pool's default share, used as a bound on memory, not as a measured
+ *     optimum -- and at least 1.  The option changes NO BIT, only memory and the number of rounds.
+ *   - Memory: the planes are allocated or grown (never shrunk) to what a call needs: a handle that only sees single-head calls holds 2*s*nnz
+ *     bytes, the first call with HG > 1 grows spmv_hip_info.device_bytes to 2*HG*s*nnz, an identical second call grows nothing.  Host operands
+ *     are staged through spmv_hip_attention_backward's seven buffers at the full widths.  Freed at destroy / clear / re-inspection.
+ *   - 16-byte accesses additionally need k and dv to be multiples of 16 bytes when heads > 1; element accesses otherwise -- the width changes
+ *     no bit.  No floating-point atomics; no workgroup waits on another; no scratch memory.
+ *   - Errors (SPMV_HIP_E_ARG before the handle's state is looked at, every output untouched): a NULL handle; heads, k or dv < 1; heads*k or
+ *     heads*dv not representable in int; a leading dimension below its full width (of the requested outputs only); a NULL Q, K, V or G while
+ *     m > 0.  Multi-GPU, host_rows and "reorder" handles: SPMV_HIP_E_ARG.  A cleared or failed handle: SPMV_HIP_E_NOSTATE.  All outputs NULL:
+ *     0 right after argument checking (the handle's state is not looked at).  Every failure is also reported through spmv_hip_last_error(). */
+int spmv_hip_attention_heads_backward(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                                      const void *Matrix_Val, int heads, int k, int dv, double scale,
+                                      const void *Q, long long ldq, const void *K, long long ldk, const void *V, long long ldv,
+                                      const void *G, long long ldg,            /* dL/dO, m x heads*dv */
+                                      void *dQ, long long lddq,                /* m x heads*k,  or NULL: not wanted */
+                                      void *dK, long long lddk,                /* n x heads*k,  or NULL */
+                                      void *dV, long long lddv);               /* n x heads*dv, or NULL */
+
 /* ---- options --------------------------------------------------------------------------------
  * Resolved once per handle, at create: process-wide value (spmv_hip_set_option / env), overridden by the
  * calling thread's value (spmv_hip_set_thread_option) -- so two threads can create differently tuned handles
@@ -361,6 +394,9 @@ int spmv_hip_attention_backward(spmv_Handle_t handle, BASIC_INT_TYPE m, const BA
                        every tile / group staged, SELL slabs, CSR5 tiles -- 4 B per non-zero less (spmv_hip_info.device_bytes); 1 keeps it)
        "deterministic" (0/1, default 1: every executor adds a row's products in an order fixed by the matrix, so results are bit-identical run to
                         run; 0 lets the wide blocked form add in arrival order -- 10-16 % faster on matrices without column locality, equal to rounding)
+ *       "attention_backward_heads" (0..1024, default 0: heads per round of spmv_hip_attention_heads_backward, i.e. planes of the two handle-owned
+ *                      arrays; 0 = as many as fit 2*HG*s*nnz bytes into an eighth of the device's memory.  Changes memory and the number of
+ *                      rounds, never a bit)
  *       "host_rows" (0/1, default 0: 1 = handles created with VECTOR_NONE and Method_Serial / Method_Parallel run
  *                    a plain-C row loop on the HOST over the caller's arrays (BASELINE config 1: the reference's
  *                    plumbing case); never selected automatically -- without it a missing GPU is an error)

@@ -134,6 +134,11 @@ FUNCTIONS = {
     "spmv_hip_time_attention_backward_launches": (C.c_double, [spmv_Handle_t, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong,
                                                                _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, C.c_int, C.c_int,
                                                                C.POINTER(C.c_float)]),
+    "spmv_hip_attention_heads_backward": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, C.c_int, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong,
+                                                    _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong]),
+    "spmv_hip_time_attention_heads_backward_launches": (C.c_double, [spmv_Handle_t, C.c_int, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong,
+                                                                     _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong,
+                                                                     C.c_int, C.c_int, C.POINTER(C.c_float)]),
     # include/spmv_io.h (host only)
     "spmv_io_read_mtx": (C.c_int, [C.c_char_p, C.c_size_t, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_V)]),
     "spmv_io_cache_path": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t]),
@@ -524,6 +529,35 @@ def time_attention_backward_launches(handle, Q, K, V, G, dQ=None, dK=None, dV=No
     return _timed("spmv_hip_time_attention_backward_launches", (handle, b[0], b[1], float(scale), *b[2:]), warmup, iters)
 
 
+def _attention_heads_backward_blocks(heads, Q, K, V, G, dQ, dK, dV):
+    """-> _attention_backward_blocks with k and dv as ONE head's widths: the column counts of Q / K and of V / G divided by `heads`"""
+    heads = int(heads)
+    wk, wv, *rest = _attention_backward_blocks(Q, K, V, G, dQ, dK, dV)
+    if heads < 1 or wk % heads or wv % heads:
+        raise ValueError(f"Q / K have {wk} columns and V / G {wv}: not {heads} heads of equal width")
+    return [wk // heads, wv // heads, *rest]
+
+
+def attention_heads_backward(handle, m, RowPtr, ColIdx, Matrix_Val, heads, Q, K, V, G, dQ=None, dK=None, dV=None, scale=None, check=True):
+    """dQ, dK, dV of attention_heads(Q, K, V) from G = dL/dO, all heads in two passes per group of heads (spmv_hip_attention_heads_backward).
+    Q, dQ (m x heads*k), K, dK (n x heads*k), V, dV (n x heads*dv) and G (m x heads*dv) hold the heads side by side: 2-D numpy arrays or torch
+    tensors with column stride 1 (row strides are passed as leading dimensions); an output that is None is not computed; head h of every output
+    has the bits of attention_backward() on the h-th column slices.  scale None means 1 / sqrt(k) with k ONE head's width.  The handle's
+    values are neither read nor changed.  -> the return code."""
+    b = _attention_heads_backward_blocks(heads, Q, K, V, G, dQ, dK, dV)
+    k = b[0]
+    scale = 1.0 / np.sqrt(k) if scale is None and k > 0 else (0.0 if scale is None else scale)
+    return _checked(load().spmv_hip_attention_heads_backward(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), int(heads), b[0], b[1], float(scale), *b[2:]),
+                    "spmv_hip_attention_heads_backward", check)
+
+
+def time_attention_heads_backward_launches(handle, heads, Q, K, V, G, dQ=None, dK=None, dV=None, scale=None, warmup=10, iters=100):
+    """-> (mean_ms, per-call ms array) of spmv_hip_attention_heads_backward on device operands (spmv_hip_time_attention_heads_backward_launches)."""
+    b = _attention_heads_backward_blocks(heads, Q, K, V, G, dQ, dK, dV)
+    scale = 1.0 / np.sqrt(b[0]) if scale is None else scale
+    return _timed("spmv_hip_time_attention_heads_backward_launches", (handle, int(heads), b[0], b[1], float(scale), *b[2:]), warmup, iters)
+
+
 def _take_csr(m, n, nnz, rp, ci, va, dtype):
     """Copy malloc'ed C arrays into numpy arrays and free the C side."""
     from .synth import CSR
@@ -708,6 +742,19 @@ class Handle:
         dV = self._like(Q, (self.n, dv)) if need[2] else None
         rp, ci, va = self._keep
         attention_backward(self.h, self.m, rp, ci, va, Q, K, V, G, dQ, dK, dV, scale)
+        return dQ, dK, dV
+
+    def attention_heads_backward(self, Q, K, V, G, heads, scale=None, need=(True, True, True)):
+        """-> (dQ, dK, dV), the gradients of attention_heads(Q, K, V, heads, scale) for G = dL/dO (m x heads*dv), all heads in two passes per group
+        of heads (spmv_hip_attention_heads_backward); need: which of the three are wanted -- the others are None and nothing is computed for
+        them.  The outputs are allocated like Q -- same kind, dtype and device -- at the full widths.  The handle's values are not used and
+        not changed."""
+        wk, wv = Q.shape[1], V.shape[1]
+        dQ = self._like(Q, (self.m, wk)) if need[0] else None
+        dK = self._like(Q, (self.n, wk)) if need[1] else None
+        dV = self._like(Q, (self.n, wv)) if need[2] else None
+        rp, ci, va = self._keep
+        attention_heads_backward(self.h, self.m, rp, ci, va, heads, Q, K, V, G, dQ, dK, dV, scale)
         return dQ, dK, dV
 
     def update_values(self, val):

@@ -296,14 +296,14 @@ class _AttentionFused(torch.autograd.Function):
 
 class _AttentionHeads(torch.autograd.Function):
     """Handle.attention_heads forward; the backward pass is one api.attention_backward call per head on column slices, written into the slices
-    of full-width gradients: the handle's values are never touched"""
+    of full-width gradients, or (fused) ONE Handle.attention_heads_backward call: the handle's values are never touched"""
 
     @staticmethod
-    def forward(ctx, handle, Q, K, V, heads, scale):
+    def forward(ctx, handle, Q, K, V, heads, scale, fused=False):
         Q2, K2, V2 = _block(Q.detach(), Q.shape[1]), _block(K.detach(), K.shape[1]), _block(V.detach(), V.shape[1])
         _on_current_stream(handle)
         O = handle.attention_heads(Q2, K2, V2, heads, scale)
-        ctx.handle, ctx.heads, ctx.scale = handle, heads, scale
+        ctx.handle, ctx.heads, ctx.scale, ctx.fused = handle, heads, scale, fused
         ctx.save_for_backward(Q2, K2, V2)   # nothing nnz-sized
         return O
 
@@ -315,11 +315,14 @@ class _AttentionHeads(torch.autograd.Function):
         Q2, K2, V2 = ctx.saved_tensors
         need = tuple(bool(x) for x in ctx.needs_input_grad[1:4])
         if not any(need):
-            return None, None, None, None, None, None
+            return None, None, None, None, None, None, None
         if handle.nnz == 0:   # no stored entry: O is zero whatever Q, K and V are
-            return None, (torch.zeros_like(Q2) if need[0] else None), (torch.zeros_like(K2) if need[1] else None), (torch.zeros_like(V2) if need[2] else None), None, None
+            return None, (torch.zeros_like(Q2) if need[0] else None), (torch.zeros_like(K2) if need[1] else None), (torch.zeros_like(V2) if need[2] else None), None, None, None
         _on_current_stream(handle)
         G2 = _block(G, G.shape[1])
+        if ctx.fused:   # every head in one call
+            dQ, dK, dV = handle.attention_heads_backward(Q2, K2, V2, G2, heads, scale, need=need)
+            return None, dQ, dK, dV, None, None, None
         k, dv = Q2.shape[1] // heads, V2.shape[1] // heads
         dQ = torch.empty_like(Q2, memory_format=torch.contiguous_format) if need[0] else None
         dK = torch.empty_like(K2, memory_format=torch.contiguous_format) if need[1] else None
@@ -329,10 +332,10 @@ class _AttentionHeads(torch.autograd.Function):
             ck, cv = slice(h * k, (h + 1) * k), slice(h * dv, (h + 1) * dv)
             api.attention_backward(handle.h, handle.m, rp, ci, va, Q2[:, ck], K2[:, ck], V2[:, cv], G2[:, cv],
                                    None if dQ is None else dQ[:, ck], None if dK is None else dK[:, ck], None if dV is None else dV[:, cv], scale)
-        return None, dQ, dK, dV, None, None
+        return None, dQ, dK, dV, None, None, None
 
 
-def attention_heads(handle, Q, K, V, heads, scale=None):
+def attention_heads(handle, Q, K, V, heads, scale=None, backward="per_head"):
     """`heads` attention heads over the handle's pattern (Handle.attention_heads: one fused pass for all heads), with gradients for Q, K and
     V.  Q: (m, heads * k), K: (n, heads * k), V: (n, heads * dv) hold the heads side by side -- a (rows, heads, k) tensor reshaped to two
     dimensions --, of the handle's dtype on its device; the result is (m, heads * dv).  scale: a Python number, None means 1 / sqrt(k) with k
@@ -341,7 +344,15 @@ def attention_heads(handle, Q, K, V, heads, scale=None):
     The forward pass saves Q, K and V only and neither reads nor changes the handle's values.  The backward pass calls
     spmv_hip_attention_backward once per head on column-slice views of Q, K, V and G; each call writes the matching slices of full-width
     dQ, dK and dV, only for the gradients asked for -- no Handle.update_values, the handle multiplies the same matrix throughout.  Every head
-    slice of a gradient has the bits of attention(..., backward="fused") on that head's slices."""
+    slice of a gradient has the bits of attention(..., backward="fused") on that head's slices.
+
+    backward="fused" routes the backward pass to ONE Handle.attention_heads_backward call (spmv_hip_attention_heads_backward) instead: two
+    passes over the pattern per group of heads, the head loop inside the kernels, so the pattern, the chunking and the launches are paid per
+    group and not per head.  The group is all heads when 2 * heads * nnz values fit an eighth of the device's memory (option
+    "attention_backward_heads" sets another bound); the handle then holds that many values instead of 2 * nnz.  The gradients have the
+    bits of the default mode."""
+    if backward not in ("per_head", "fused"):
+        raise ValueError(f"backward must be 'per_head' or 'fused', not {backward!r}")
     _check_handle(handle)
     for t, name in ((Q, "Q"), (K, "K"), (V, "V")):
         _check_tensor(t, name, handle)
@@ -352,7 +363,7 @@ def attention_heads(handle, Q, K, V, heads, scale=None):
     if heads < 1 or Q.shape[1] % heads or V.shape[1] % heads:
         raise ValueError(f"{Q.shape[1]} columns of Q / K and {V.shape[1]} of V are not {heads} heads of equal width")
     scale = 1.0 / math.sqrt(Q.shape[1] // heads) if scale is None else float(scale)   # Handle.attention_heads' default, to the bit
-    return _AttentionHeads.apply(handle, Q, K, V, heads, scale)
+    return _AttentionHeads.apply(handle, Q, K, V, heads, scale, backward == "fused")
 
 
 def attention(handle, Q, K, V, scale=None, backward="composed"):

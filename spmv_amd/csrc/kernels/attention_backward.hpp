@@ -23,6 +23,14 @@
 // the one index stream, one after the other: dV's panel against G rows with values P, dK's panel against Q rows with values dS.  One launch
 // does panel r of both.
 //
+// Heads (spmv_hip_attention_heads_backward): Q, K, dQ, dK are `heads` blocks of k columns side by side, V, G, dV `heads` blocks of dv columns,
+// and attb_p / attb_ds are planes of `plane` (= nnz) elements, plane hd holding head hd's P / dS in CSR order.  The head loop is inside all
+// four kernels: the row pass fetches a chunk's pattern once and keeps it in LDS for every head (s_p / s_d and, in long rows, each plane's own
+// range of the row are reused or used head after head); the column pass stages a row group's A^T columns once when the group is one chunk --
+// s_col then serves every head -- and reads perm again per head (L2 has just served it).  Each head's arithmetic is the single-head code on
+// offset pointers, so head hd has the bits of the single-head call on its slices.  spmv_hip_attention_backward is heads = 1.  The launch
+// side offsets the pointers to a round's first head (kernels see heads = the round's count and planes from 0).
+//
 // Arithmetic and order: the composition's, because its blocks are the composition's (kernels/row_blocks.hpp) -- t and P are
 // spmv_hip_attention's; dP is sddmm's dot for dv; D is row_softmax_backward's by row length; dS is one subtraction and two plain
 // multiplications; dQ, dK and dV are spmm's chains.  Contraction is pinned off: the fmas written out are the only fused operations.
@@ -36,20 +44,22 @@ namespace spmv {
 
 // what one call's launches need (device pointers); an output that is not wanted is nullptr
 struct AttentionBwdArgs {
-    int m = 0, k = 0, dv = 0, cus = 256;
+    int m = 0, k = 0, dv = 0, cus = 256; // k, dv: per head
+    int heads = 1, hg = 1;               // heads of the call; heads per round (the planes of p / ds)
+    long long plane = 0;                 // elements per plane of p / ds: nnz
     int nb = 0, nlong = 0; // A: spmm's tables
     const int *split = nullptr, *longs = nullptr, *rowptr = nullptr, *colidx = nullptr;
     int t_rows = 0, t_nb = 0, t_nlong = 0; // A^T (read only when dk or dvo is wanted)
     const int *t_split = nullptr, *t_longs = nullptr, *t_rowptr = nullptr, *t_colidx = nullptr, *perm = nullptr;
-    void *p = nullptr, *ds = nullptr; // attb_p, attb_ds: nnz elements each, CSR order
+    void *p = nullptr, *ds = nullptr; // attb_p, attb_ds: hg planes of nnz elements each, CSR order
     const void *q = nullptr, *kk = nullptr, *v = nullptr, *g = nullptr;
     void *dq = nullptr, *dk = nullptr, *dvo = nullptr;
     long long ldq = 0, ldk = 0, ldv = 0, ldg = 0, lddq = 0, lddk = 0, lddv = 0;
     double scale = 1.0;
-    bool vec = false; // every operand and leading dimension allows 16-byte accesses
+    bool vec = false; // every operand, leading dimension and head's first column allows 16-byte accesses
 };
 
-// spmv_attention_backward.hip: the launches of one call on `stream`
+// spmv_attention_backward.hip: the launches of one call on `stream`, ceil(heads / hg) rounds of a row pass and a column pass
 hipError_t attention_backward_launch(const AttentionBwdArgs &a, bool f64, hipStream_t stream);
 
 // att_tile_scores without the scaling, for a lane group width known at run time (wave-uniform): dP's dots, sddmm's order for dv columns.
@@ -62,13 +72,14 @@ __device__ __forceinline__ void attb_tile_dots(int cw, int i, int j, int lane, i
 
 // One wave per batch [split[b], split[b + 1]) of whole rows; rows longer than kSpmmLongThr are left to attention_bwd_long_kernel.
 // CW: sddmm's lane group for k; cwd: the same for dv; 1 << lgk: spmm's lane group for min(k, KP) columns.
-// p_out / ds_out / dq: nullptr when dV / dK / dQ is not wanted.
+// p_out / ds_out / dq: nullptr when dV / dK / dQ is not wanted.  heads: the chunk's columns stay in s_col while the four phases run once per
+// head over s_p / s_d, head hd on the columns from hd * k (Q, K, dQ) and hd * dv (V, G) and on plane hd of p_out / ds_out.
 template <typename T, int CW, bool VEC>
 __global__ __launch_bounds__(kBlock) void attention_bwd_rows_kernel(int nb, const int *__restrict__ split, const int *__restrict__ rowptr, const int *__restrict__ colidx,
-                                                                    int k, int dv, int cwd, int lgk, T scale, const T *__restrict__ q, long long ldq,
-                                                                    const T *__restrict__ kk, long long ldk, const T *__restrict__ v, long long ldv,
-                                                                    const T *__restrict__ g, long long ldg, T *__restrict__ dq, long long lddq, T *__restrict__ p_out,
-                                                                    T *__restrict__ ds_out)
+                                                                    int heads, long long plane, int k, int dv, int cwd, int lgk, T scale,
+                                                                    const T *__restrict__ q, long long ldq, const T *__restrict__ kk, long long ldk,
+                                                                    const T *__restrict__ v, long long ldv, const T *__restrict__ g, long long ldg, T *__restrict__ dq,
+                                                                    long long lddq, T *__restrict__ p_out, T *__restrict__ ds_out)
 {
 #pragma clang fp contract(off)
     constexpr int V = SpmmShape<T>::V, CH = kSpmmChunk;
@@ -78,159 +89,173 @@ __global__ __launch_bounds__(kBlock) void attention_bwd_rows_kernel(int nb, cons
     const int w = (int) (threadIdx.x / kWave);
     const int b = blockIdx.x * (kBlock / kWave) + w;
     if (b >= nb) return; // whole waves only; no workgroup barrier follows
-    const int lane = threadIdx.x & (kWave - 1);
-    const int cwk = 1 << lgk, R = kWave >> lgk, subk = lane >> lgk, ck0 = (lane & (cwk - 1)) * V;
+    const int lane0 = threadIdx.x & (kWave - 1);
+    const int cwk = 1 << lgk, R = kWave >> lgk;
     const int r0 = split[b], r1 = split[b + 1];
     const T ninf = -__builtin_huge_val(), nzero = T(-0.0);
     for (int g0 = r0; g0 < r1;) {
-        const ChunkRows ch = chunk_take(rowptr, g0, r1, lane);
+        const ChunkRows ch = chunk_take(rowptr, g0, r1, lane0);
         if (ch.nr == 0) { ++g0; continue; } // a long row: nothing of it here
         const int sl = ch.sl, ll = ch.ll, base = ch.base, nr = ch.nr, nq = ch.nq;
 
-        // A. columns, scaled scores and dP into LDS
-        for (int t0 = 0; t0 < nq; t0 += kWave) {
-            const int e = t0 + lane;
-            const int pos = chunk_row_of(ch.el, e);
-            int i = -1, j = 0;
-            if (e < nq) {
-                j = ld_stream(colidx + base + e);
-                i = g0 + pos;
-                s_col[w][e] = j;
+        for (int hd = 0; hd < heads; ++hd) {
+            const int lane = att_per_head(lane0), subk = lane >> lgk, ck0 = (lane & (cwk - 1)) * V;
+            const T *qh = q + (long long) hd * k, *kh = kk + (long long) hd * k, *vh = v + (long long) hd * dv, *gh = g + (long long) hd * dv; // the head's first columns
+            // A. columns (the first head reads them from memory, the others from LDS), scaled scores and dP into LDS
+            for (int t0 = 0; t0 < nq; t0 += kWave) {
+                const int e = t0 + lane;
+                const int pos = chunk_row_of(ch.el, e);
+                int i = -1, j = 0;
+                if (e < nq) {
+                    i = g0 + pos;
+                    if (hd == 0) {
+                        j = ld_stream(colidx + base + e);
+                        s_col[w][e] = j;
+                    } else j = s_col[w][e]; // written by this lane
+                }
+                att_tile_scores<T, CW, VEC>(i, j, lane, k, qh, ldq, kh, ldk, scale, s_p[w] + t0);
+                attb_tile_dots<T, VEC>(cwd, i, j, lane, dv, gh, ldg, vh, ldv, s_d[w] + t0);
             }
-            att_tile_scores<T, CW, VEC>(i, j, lane, k, q, ldq, kk, ldk, scale, s_p[w] + t0);
-            attb_tile_dots<T, VEC>(cwd, i, j, lane, dv, g, ldg, v, ldv, s_d[w] + t0);
-        }
-        wave_lds_sync();
+            wave_lds_sync();
 
-        // B. the row softmax and its backward in place in LDS, in row_reduce_rows_kernel's passes.  An element is read and written by the same lane.
-        for (int h0 = 0; h0 < nr;) {
-            const int hl = h0 + lane; // lane l looks at chunk row h0 + l
-            const int sh = __shfl(sl, hl & (kWave - 1), kWave) - base, lh0 = __shfl(ll, hl & (kWave - 1), kWave);
-            const int lh = hl < nr ? lh0 : 0;
-            int cw, lg;
-            row_pass_width(row_width(lh), cw, lg);
-            const int sub = lane >> lg, t = lane & (cw - 1);
-            const int s = __shfl(sh, sub, kWave), len = __shfl(lh, sub, kWave);
-            const bool wide = cw == kWave; // the only passes in which a lane holds more than one term
-            T *row = s_p[w] + s, *drow = s_d[w] + s;
-            T x[kRowChain], y[kRowChain];
-            x[0] = t < len ? row[t] : ninf;
-            y[0] = t < len ? drow[t] : nzero;
-            if (wide) {
+            // B. the row softmax and its backward in place in LDS, in row_reduce_rows_kernel's passes.  An element is read and written by the same lane.
+            for (int h0 = 0; h0 < nr;) {
+                const int hl = h0 + lane; // lane l looks at chunk row h0 + l
+                const int sh = __shfl(sl, hl & (kWave - 1), kWave) - base, lh0 = __shfl(ll, hl & (kWave - 1), kWave);
+                const int lh = hl < nr ? lh0 : 0;
+                int cw, lg;
+                row_pass_width(row_width(lh), cw, lg);
+                const int sub = lane >> lg, t = lane & (cw - 1);
+                const int s = __shfl(sh, sub, kWave), len = __shfl(lh, sub, kWave);
+                const bool wide = cw == kWave; // the only passes in which a lane holds more than one term
+                T *row = s_p[w] + s, *drow = s_d[w] + s;
+                T x[kRowChain], y[kRowChain];
+                x[0] = t < len ? row[t] : ninf;
+                y[0] = t < len ? drow[t] : nzero;
+                if (wide) {
 #pragma unroll
-                for (int u = 1; u < kRowChain; ++u) {
-                    const bool have = t + u * kWave < len;
-                    x[u] = have ? row[t + u * kWave] : ninf;
-                    y[u] = have ? drow[t + u * kWave] : nzero;
-                }
-            }
-            // row_softmax_regs, written out: as a call it costs attention_bwd_rows_kernel<float, 4, false> two registers and with them, at
-            // 129, a wave per SIMD.  The one copy of that block: keep the two alike.
-            T mx = x[0];
-            if (wide) {
-#pragma unroll
-                for (int u = 1; u < kRowChain; ++u) mx = row_max(mx, x[u]);
-            }
-            const T M = row_group_reduce<true>(mx, cw);
-            const T e0 = row_exp(x[0] - M);
-            x[0] = t < len ? e0 : nzero;
-            T acc = x[0];
-            if (wide) {
-#pragma unroll
-                for (int u = 1; u < kRowChain; ++u) {
-                    const bool have = t + u * kWave < len;
-                    if (__ballot(have) == 0) break;
-                    x[u] = row_exp(x[u] - M);
-                    acc = have ? acc + x[u] : acc;
-                }
-            }
-            const T Z = row_group_reduce<false>(acc, cw);
-            const T D = row_dot_regs<T, true>(x, y, t, len, cw, wide, Z); // x becomes P
-            if (t < len) {
-                row[t] = x[0];
-                drow[t] = att_scale(x[0] * (y[0] - D), scale);
-            }
-            if (wide) {
-#pragma unroll
-                for (int u = 1; u < kRowChain; ++u)
-                    if (t + u * kWave < len) {
-                        row[t + u * kWave] = x[u];
-                        drow[t + u * kWave] = att_scale(x[u] * (y[u] - D), scale);
+                    for (int u = 1; u < kRowChain; ++u) {
+                        const bool have = t + u * kWave < len;
+                        x[u] = have ? row[t + u * kWave] : ninf;
+                        y[u] = have ? drow[t + u * kWave] : nzero;
                     }
+                }
+                // row_softmax_regs, written out: as a call it costs attention_bwd_rows_kernel<float, 4, false> two registers and with them, at
+                // 129, a wave per SIMD.  The one copy of that block: keep the two alike.
+                T mx = x[0];
+                if (wide) {
+#pragma unroll
+                    for (int u = 1; u < kRowChain; ++u) mx = row_max(mx, x[u]);
+                }
+                const T M = row_group_reduce<true>(mx, cw);
+                const T e0 = row_exp(x[0] - M);
+                x[0] = t < len ? e0 : nzero;
+                T acc = x[0];
+                if (wide) {
+#pragma unroll
+                    for (int u = 1; u < kRowChain; ++u) {
+                        const bool have = t + u * kWave < len;
+                        if (__ballot(have) == 0) break;
+                        x[u] = row_exp(x[u] - M);
+                        acc = have ? acc + x[u] : acc;
+                    }
+                }
+                const T Z = row_group_reduce<false>(acc, cw);
+                const T D = row_dot_regs<T, true>(x, y, t, len, cw, wide, Z); // x becomes P
+                if (t < len) {
+                    row[t] = x[0];
+                    drow[t] = att_scale(x[0] * (y[0] - D), scale);
+                }
+                if (wide) {
+#pragma unroll
+                    for (int u = 1; u < kRowChain; ++u)
+                        if (t + u * kWave < len) {
+                            row[t + u * kWave] = x[u];
+                            drow[t + u * kWave] = att_scale(x[u] * (y[u] - D), scale);
+                        }
+                }
+                h0 += kWave >> lg;
             }
-            h0 += kWave >> lg;
+            wave_lds_sync();
+
+            // C. what the column pass gathers: P and dS in CSR order, coalesced
+            if (p_out)
+                for (int e = lane; e < nq; e += kWave) p_out[hd * plane + base + e] = s_p[w][e];
+            if (ds_out)
+                for (int e = lane; e < nq; e += kWave) ds_out[hd * plane + base + e] = s_d[w][e];
+
+            // D. dQ = A_dS K; the panels reuse dS
+            if (dq) rows_times_panels<T, VEC>(ch, g0, R, subk, ck0, s_col[w], s_d[w], kh, ldk, k, dq + (long long) hd * k, lddq);
+            wave_lds_sync(); // the next head overwrites s_p / s_d, the next chunk s_col as well
         }
-        wave_lds_sync();
-
-        // C. what the column pass gathers: P and dS in CSR order, coalesced
-        if (p_out)
-            for (int e = lane; e < nq; e += kWave) p_out[base + e] = s_p[w][e];
-        if (ds_out)
-            for (int e = lane; e < nq; e += kWave) ds_out[base + e] = s_d[w][e];
-
-        // D. dQ = A_dS K; the panels reuse dS
-        if (dq) rows_times_panels<T, VEC>(ch, g0, R, subk, ck0, s_col[w], s_d[w], kk, ldk, k, dq, lddq);
-        wave_lds_sync(); // the next chunk overwrites s_col / s_p / s_d
         g0 += nr;
     }
 }
 
-// one workgroup per long row (len > kSpmmLongThr >= 256: every thread has a first term); the row's ranges of pa (attb_p) and da (attb_ds)
-// are its own: no other workgroup of this launch touches them
+// one workgroup per long row (len > kSpmmLongThr >= 256: every thread has a first term); the row's ranges of every plane of pa (attb_p) and
+// da (attb_ds) are its own: no other workgroup of this launch touches them.  Head hd parks in plane hd's range.
 template <typename T, int CW, bool VEC>
 __global__ __launch_bounds__(kBlock) void attention_bwd_long_kernel(int nlong, const int *__restrict__ longs, const int *__restrict__ rowptr, const int *__restrict__ colidx,
-                                                                    int k, int dv, int cwd, int lgk, T scale, const T *__restrict__ q, long long ldq,
-                                                                    const T *__restrict__ kk, long long ldk, const T *__restrict__ v, long long ldv,
-                                                                    const T *__restrict__ g, long long ldg, T *__restrict__ dq, long long lddq, T *pa, T *da)
+                                                                    int heads, long long plane, int k, int dv, int cwd, int lgk, T scale,
+                                                                    const T *__restrict__ q, long long ldq, const T *__restrict__ kk, long long ldk,
+                                                                    const T *__restrict__ v, long long ldv, const T *__restrict__ g, long long ldg, T *__restrict__ dq,
+                                                                    long long lddq, T *pa, T *da)
 {
 #pragma clang fp contract(off)
     constexpr int V = SpmmShape<T>::V, KP = SpmmShape<T>::KP;
     __shared__ T part[kSpmmSegs][KP];
     __shared__ T s_slot[kBlock / kWave][kWave], s_slot2[kBlock / kWave][kWave];
     __shared__ T s_max[kBlock / kWave], s_sum[kBlock / kWave];
-    const int tid = (int) threadIdx.x, w = tid / kWave, lane = tid & (kWave - 1);
-    const int cwk = 1 << lgk, G = kBlock >> lgk, subk = tid >> lgk, ck0 = (tid & (cwk - 1)) * V;
+    const int cwk = 1 << lgk, G = kBlock >> lgk;
     for (int i = blockIdx.x; i < nlong; i += gridDim.x) {
         const int r = longs[i], s = rowptr[r], len = rowptr[r + 1] - s;
         const int *col = colidx + s;
-        T *t = pa + s, *d = da + s;
-        // 1. the scaled scores and dP, parked: tiles of 64 entries, wave w takes the tiles w, w + 4, .. (entry p is thread p % 256's in every phase)
-        for (int t0 = w * kWave; t0 < len; t0 += kBlock) {
-            const int p = t0 + lane;
-            const bool valid = p < len;
-            const int j = valid ? col[p] : 0;
-            att_tile_scores<T, CW, VEC>(valid ? r : -1, j, lane, k, q, ldq, kk, ldk, scale, s_slot[w]);
-            attb_tile_dots<T, VEC>(cwd, valid ? r : -1, j, lane, dv, g, ldg, v, ldv, s_slot2[w]);
-            wave_lds_sync();
-            if (valid) {
-                t[p] = s_slot[w][lane];
-                d[p] = s_slot2[w][lane];
+        for (int hd = 0; hd < heads; ++hd) {
+            const T *qh = q + (long long) hd * k, *kh = kk + (long long) hd * k, *vh = v + (long long) hd * dv, *gh = g + (long long) hd * dv; // the head's first columns
+            const int tid = att_per_head((int) threadIdx.x), w = tid / kWave, lane = tid & (kWave - 1);
+            const int subk = tid >> lgk, ck0 = (tid & (cwk - 1)) * V;
+            T *t = pa + hd * plane + s, *d = da + hd * plane + s;
+            // 1. the scaled scores and dP, parked: tiles of 64 entries, wave w takes the tiles w, w + 4, .. (entry p is thread p % 256's in every phase)
+            for (int t0 = w * kWave; t0 < len; t0 += kBlock) {
+                const int p = t0 + lane;
+                const bool valid = p < len;
+                const int j = valid ? col[p] : 0;
+                att_tile_scores<T, CW, VEC>(valid ? r : -1, j, lane, k, qh, ldq, kh, ldk, scale, s_slot[w]);
+                attb_tile_dots<T, VEC>(cwd, valid ? r : -1, j, lane, dv, gh, ldg, vh, ldv, s_slot2[w]);
+                wave_lds_sync();
+                if (valid) {
+                    t[p] = s_slot[w][lane];
+                    d[p] = s_slot2[w][lane];
+                }
+                wave_lds_sync();
             }
-            wave_lds_sync();
+            __syncthreads();
+            // 2. maximum, sum, map over the parked scores, P written in place
+            long_row_softmax(t, t, 0, len, tid, s_max, s_sum);
+            // 3. D over P and the parked dP, dS written in place
+            const T D = long_row_dot(t, d, 0, len, tid, s_sum);
+            for (int p = tid; p < len; p += kBlock) d[p] = att_scale(t[p] * (d[p] - D), scale);
+            __syncthreads();
+            // 4. dQ = A_dS K, panel by panel; a panel's last barrier also lets the next panel / head / row write part, s_max, s_sum again
+            if (dq)
+                for (int c = 0; c < k; c += KP)
+                    long_row_panel<T>(len, min(KP, k - c), G, subk, ck0, tid, part, dq + (long long) r * lddq + (long long) hd * k + c,
+                                      [&](int lo, int hi, int nc, T (&acc)[V]) { spmm_chain<T, VEC, false>(lo, hi, col, d, kh + c, ldk, ck0, nc, acc); });
         }
-        __syncthreads();
-        // 2. maximum, sum, map over the parked scores, P written in place
-        long_row_softmax(t, t, 0, len, tid, s_max, s_sum);
-        // 3. D over P and the parked dP, dS written in place
-        const T D = long_row_dot(t, d, 0, len, tid, s_sum);
-        for (int p = tid; p < len; p += kBlock) d[p] = att_scale(t[p] * (d[p] - D), scale);
-        __syncthreads();
-        // 4. dQ = A_dS K, panel by panel; a panel's last barrier also lets the next panel / row write part, s_max, s_sum again
-        if (dq)
-            for (int c = 0; c < k; c += KP)
-                long_row_panel<T>(len, min(KP, k - c), G, subk, ck0, tid, part, dq + (long long) r * lddq + c,
-                                  [&](int lo, int hi, int nc, T (&acc)[V]) { spmm_chain<T, VEC, false>(lo, hi, col, d, kk + c, ldk, ck0, nc, acc); });
     }
 }
 
 // spmm_rows_kernel on A^T's tables, two outputs off one index stream.  One wave per batch of A^T's rows (A's columns); CW lanes per row for
 // the wider of the two panels.  kcv / kck: the columns of this panel of dV / dK (<= 0: not wanted, or no such panel); g, dvo, q, dk are
-// offset to the panel's first column.  pv / dsv: attb_p / attb_ds, gathered through perm.
+// offset to the panel's first column of the first head.  pv / dsv: attb_p / attb_ds, plane hd gathered through perm.
+// The head loop is around a row group's walk (a row's accumulators live across its chunks, so they cannot be kept for every head).  A group of
+// at most kSpmmChunk entries is ONE chunk: its columns are staged by the first head and stay in s_col for the others; a larger group (or one
+// with a long row in it) stages them again.  perm is read again by every head: L2 has just served it.
 template <typename T, int CW, bool VEC>
 __global__ __launch_bounds__(kBlock) void attention_bwd_cols_kernel(int nb, const int *__restrict__ split, const int *__restrict__ rowptr, const int *__restrict__ colidx,
-                                                                    const int *__restrict__ perm, const T *__restrict__ pv, const T *__restrict__ dsv, int kcv,
-                                                                    const T *__restrict__ g, long long ldg, T *__restrict__ dvo, long long lddv, int kck,
-                                                                    const T *__restrict__ q, long long ldq, T *__restrict__ dk, long long lddk)
+                                                                    const int *__restrict__ perm, int heads, long long plane, int k, int dv, const T *__restrict__ pv,
+                                                                    const T *__restrict__ dsv, int kcv, const T *__restrict__ g, long long ldg, T *__restrict__ dvo,
+                                                                    long long lddv, int kck, const T *__restrict__ q, long long ldq, T *__restrict__ dk, long long lddk)
 {
 #pragma clang fp contract(off)
     constexpr int V = SpmmShape<T>::V, R = kWave / CW, CH = kSpmmChunk;
@@ -248,32 +273,38 @@ __global__ __launch_bounds__(kBlock) void attention_bwd_cols_kernel(int nb, cons
         const bool have = r < g1;
         const int s = have ? rowptr[r] : 0, e = have ? rowptr[r + 1] : 0;
         const bool longrow = e - s > kSpmmLongThr;
-        T accv[V], acck[V];
+        const bool one = rowptr[g1] - rowptr[g0] <= CH; // the whole group is one chunk (and holds no long row): wave-uniform
+        for (int hd = 0; hd < heads; ++hd) {
+            const T *ph = pv + hd * plane, *dh = dsv + hd * plane;
+            const T *gh = g + (long long) hd * dv, *qh = q + (long long) hd * k; // the head's panel
+            T accv[V], acck[V];
 #pragma unroll
-        for (int t = 0; t < V; ++t) accv[t] = acck[t] = T(0);
-        staged_walk(
-            rowptr, g0, g1, s, e, longrow, lane,
-            [&](int i, int p) {
-                s_col[w][i] = ld_stream(colidx + p);
-                const int pp = ld_stream(perm + p);
-                if (kcv > 0) s_p[w][i] = pv[pp];
-                if (kck > 0) s_d[w][i] = dsv[pp];
-            },
-            [&](int lo, int hi) {
-                if (!longrow && ncv > 0) spmm_chain<T, VEC, false>(lo, hi, s_col[w], s_p[w], g, ldg, c0, ncv, accv);
-                if (!longrow && nck > 0) spmm_chain<T, VEC, false>(lo, hi, s_col[w], s_d[w], q, ldq, c0, nck, acck);
-            });
-        if (have && !longrow && ncv > 0) spmm_store_y<T, VEC>(dvo + (long long) r * lddv + c0, ncv, accv);
-        if (have && !longrow && nck > 0) spmm_store_y<T, VEC>(dk + (long long) r * lddk + c0, nck, acck);
+            for (int t = 0; t < V; ++t) accv[t] = acck[t] = T(0);
+            staged_walk(
+                rowptr, g0, g1, s, e, longrow, lane,
+                [&](int i, int p) {
+                    if (hd == 0 || !one) s_col[w][i] = ld_stream(colidx + p);
+                    const int pp = ld_stream(perm + p);
+                    if (kcv > 0) s_p[w][i] = ph[pp];
+                    if (kck > 0) s_d[w][i] = dh[pp];
+                },
+                [&](int lo, int hi) {
+                    if (!longrow && ncv > 0) spmm_chain<T, VEC, false>(lo, hi, s_col[w], s_p[w], gh, ldg, c0, ncv, accv);
+                    if (!longrow && nck > 0) spmm_chain<T, VEC, false>(lo, hi, s_col[w], s_d[w], qh, ldq, c0, nck, acck);
+                });
+            if (have && !longrow && ncv > 0) spmm_store_y<T, VEC>(dvo + (long long) r * lddv + (long long) hd * dv + c0, ncv, accv);
+            if (have && !longrow && nck > 0) spmm_store_y<T, VEC>(dk + (long long) r * lddk + (long long) hd * k + c0, nck, acck);
+        }
     }
 }
 
-// spmm_long_kernel on A^T's long rows (columns of A with more than kSpmmLongThr entries), a workgroup each: first dV's panel, then dK's
+// spmm_long_kernel on A^T's long rows (columns of A with more than kSpmmLongThr entries), a workgroup each: per head, first dV's panel, then dK's
 template <typename T, int CW, bool VEC>
 __global__ __launch_bounds__(kBlock) void attention_bwd_cols_long_kernel(int nlong, const int *__restrict__ longs, const int *__restrict__ rowptr,
-                                                                         const int *__restrict__ colidx, const int *__restrict__ perm, const T *__restrict__ pv,
-                                                                         const T *__restrict__ dsv, int kcv, const T *__restrict__ g, long long ldg, T *__restrict__ dvo,
-                                                                         long long lddv, int kck, const T *__restrict__ q, long long ldq, T *__restrict__ dk, long long lddk)
+                                                                         const int *__restrict__ colidx, const int *__restrict__ perm, int heads, long long plane, int k, int dv,
+                                                                         const T *__restrict__ pv, const T *__restrict__ dsv, int kcv, const T *__restrict__ g, long long ldg,
+                                                                         T *__restrict__ dvo, long long lddv, int kck, const T *__restrict__ q, long long ldq, T *__restrict__ dk,
+                                                                         long long lddk)
 {
 #pragma clang fp contract(off)
     constexpr int V = SpmmShape<T>::V, KP = SpmmShape<T>::KP, G = kBlock / CW;
@@ -281,17 +312,19 @@ __global__ __launch_bounds__(kBlock) void attention_bwd_cols_long_kernel(int nlo
     const int tid = (int) threadIdx.x, sub = tid / CW, c0 = (tid % CW) * V;
     for (int i = blockIdx.x; i < nlong; i += gridDim.x) {
         const int r = longs[i], s = rowptr[r], e = rowptr[r + 1];
-        for (int o = 0; o < 2; ++o) { // 0: dV (values P, X = G); 1: dK (values dS, X = Q)
-            const int kc = o ? kck : kcv;
-            if (kc <= 0) continue; // uniform over the workgroup
-            const T *val = o ? dsv : pv, *x = o ? q : g;
-            const long long ldx = o ? ldq : ldg;
-            long_row_panel<T>(e - s, kc, G, sub, c0, tid, part, o ? dk + (long long) r * lddk : dvo + (long long) r * lddv, [&](int lo, int hi, int nc, T (&acc)[V]) {
-                // the global streams of A^T, the values gathered through perm
-                spmm_chain_with<T, VEC>(
-                    s + lo, s + hi, [=](int j) { return ld_stream(colidx + j); }, [=](int j) { return val[ld_stream(perm + j)]; }, x, ldx, c0, nc, acc);
-            });
-        }
+        for (int hd = 0; hd < heads; ++hd)
+            for (int o = 0; o < 2; ++o) { // 0: dV (values P, X = G); 1: dK (values dS, X = Q)
+                const int kc = o ? kck : kcv;
+                if (kc <= 0) continue; // uniform over the workgroup
+                const T *val = (o ? dsv : pv) + hd * plane, *x = o ? q + (long long) hd * k : g + (long long) hd * dv;
+                const long long ldx = o ? ldq : ldg;
+                T *y = o ? dk + (long long) r * lddk + (long long) hd * k : dvo + (long long) r * lddv + (long long) hd * dv;
+                long_row_panel<T>(e - s, kc, G, sub, c0, tid, part, y, [&](int lo, int hi, int nc, T (&acc)[V]) {
+                    // the global streams of A^T, the values gathered through perm
+                    spmm_chain_with<T, VEC>(
+                        s + lo, s + hi, [=](int j) { return ld_stream(colidx + j); }, [=](int j) { return val[ld_stream(perm + j)]; }, x, ldx, c0, nc, acc);
+                });
+            }
     }
 }
 

@@ -1,28 +1,64 @@
-// shim/attention_backward.hpp -- part of spmv_shim.hip: dQ, dK, dV of O = softmax_rows(scale * Q K^T on the RESIDENT pattern) V in two passes
-// (spmv_hip_attention_backward).  The kernels are kernels/attention_backward.hpp, launched from their own translation unit
+// shim/attention_backward.hpp -- part of spmv_shim.hip: dQ, dK, dV of O = softmax_rows(scale * Q K^T on the RESIDENT pattern) V in two passes,
+// for one head (spmv_hip_attention_backward) or for `heads` heads stored side by side in the rows (spmv_hip_attention_heads_backward: two
+// passes per round of up to hg heads).  The kernels are kernels/attention_backward.hpp, launched from their own translation unit
 // (spmv_attention_backward.hip, attention_backward_launch); the tables are spmm's batch table and long-row list of the resident matrix
 // and, when dK or dV is wanted, those of the attached transpose.  This side adds the two nnz-sized arrays the passes share.
 #pragma once
 
-// attb_p / attb_ds: P and dS in CSR order, allocated once per resident matrix
-static int attention_backward_plan(spmv_dev *d)
+// attb_p / attb_ds: `planes` planes of nnz elements each, plane g one head's P / dS in CSR order.  Allocated at the first call that needs them,
+// grown (never shrunk) when a later call needs more planes; nothing in them outlives a call, so growing copies nothing.
+static int attention_backward_plan(spmv_dev *d, int planes)
 {
-    if (d->attb_p && d->attb_ds) return SPMV_HIP_OK;
-    const size_t bytes = d->vsize * (size_t) d->nnz;
+    if (d->attb_p && d->attb_ds && d->attb_planes >= planes) return SPMV_HIP_OK;
+    const size_t bytes = d->vsize * (size_t) d->nnz * (size_t) planes;
+    quiesce(d); // an asynchronous call may still read the arrays that go back to the pool
+    auto drop = [&](void *&p) {
+        if (!p) return;
+        (void) pool_free(p);
+        p = nullptr;
+        d->device_bytes -= (long long) d->attb_bytes; // what dev_alloc counted for it
+    };
+    drop(d->attb_p);
+    drop(d->attb_ds);
+    d->attb_planes = 0;
+    d->attb_bytes = bytes ? bytes : 16;
     int rc;
-    if (!d->attb_p && (rc = dev_alloc(d, &d->attb_p, bytes, false))) return rc;
-    if (!d->attb_ds && (rc = dev_alloc(d, &d->attb_ds, bytes, false))) return rc;
+    if ((rc = dev_alloc(d, &d->attb_p, bytes, false))) return rc;
+    if ((rc = dev_alloc(d, &d->attb_ds, bytes, false))) { drop(d->attb_p); return rc; }
+    d->attb_planes = planes;
     return SPMV_HIP_OK;
 }
 
-// dq / dk / dv: NULL = not wanted.  When dk or dv is wanted the transpose must be attached with its column indices resident
-// (spmv_shim_transpose, spmv_shim_transpose_restore_columns); its values are not read.
-extern "C" int spmv_shim_attention_backward(spmv_dev *d, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v,
-                                            long long ldv, const void *g, long long ldg, void *dq, long long lddq, void *dk, long long lddk, void *dvo, long long lddv)
+// heads per round (the planes a call needs): at most `limit` when limit > 0 (option "attention_backward_heads"); limit = 0: the most for which
+// the two arrays, 2 * hg * s * nnz bytes, stay within an eighth of the device's memory -- the pool's default share (pool_cap), used as a bound
+// on memory, not as a measured optimum; one head at the least.  Changes no bit: only memory and the number of rounds.
+static int attention_backward_group(const spmv_dev *d, int heads, int limit)
+{
+    if (limit > 0) return heads < limit ? heads : limit;
+    static long long eighth = -1; // of the first device asked about: the devices of one process are alike
+    if (eighth < 0) {
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void) hipGetLastError(); total_b = (size_t) 64 << 30; }
+        eighth = (long long) (total_b / 8);
+    }
+    const long long per_head = 2 * (long long) d->vsize * d->nnz;
+    const long long fit = per_head > 0 ? eighth / per_head : heads;
+    return fit >= heads ? heads : (fit < 1 ? 1 : (int) fit);
+}
+
+// k and dv are one head's widths: Q, K, dq, dk are heads * k columns wide, V, G, dvo heads * dv.  dq / dk / dvo: NULL = not wanted.  When dk or
+// dvo is wanted the transpose must be attached with its column indices resident (spmv_shim_transpose, spmv_shim_transpose_restore_columns);
+// its values are not read.  max_heads: option "attention_backward_heads" (0 = by the memory rule).
+extern "C" int spmv_shim_attention_heads_backward(spmv_dev *d, int heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
+                                                  const void *v, long long ldv, const void *g, long long ldg, void *dq, long long lddq, void *dk, long long lddk, void *dvo,
+                                                  long long lddv)
 {
     if (!d || !d->built) return fail(SPMV_HIP_E_NOSTATE, "attention_backward: schedule not built");
-    if (k < 1 || dv < 1 || ldq < k || ldk < k || ldv < dv || ldg < dv || (dq && lddq < k) || (dk && lddk < k) || (dvo && lddv < dv))
-        return fail(SPMV_HIP_E_ARG, "attention_backward: need k >= 1, dv >= 1, ldq, ldk >= k, ldv, ldg >= dv, lddq, lddk >= k, lddv >= dv (k = %d, dv = %d)", k, dv);
+    const long long wk = (long long) heads * k, wv = (long long) heads * dv;
+    if (heads < 1 || k < 1 || dv < 1 || wk > INT_MAX || wv > INT_MAX || max_heads < 0 || ldq < wk || ldk < wk || ldv < wv || ldg < wv || (dq && lddq < wk) || (dk && lddk < wk) ||
+        (dvo && lddv < wv))
+        return fail(SPMV_HIP_E_ARG, "attention_backward: need heads, k, dv >= 1, heads * k and heads * dv within int, ldq, ldk >= heads * k, ldv, ldg >= heads * dv, lddq, lddk >= heads * k, lddv >= heads * dv (heads = %d, k = %d, dv = %d)",
+                    heads, k, dv);
     if (d->m > 0 && (!q || !kk || !v || !g)) return fail(SPMV_HIP_E_ARG, "attention_backward: Q, K, V or G is NULL");
     if (!dq && !dk && !dvo) return SPMV_HIP_OK;
     if (d->nnz > 0 && !d->colidx) return fail(SPMV_HIP_E_NOSTATE, "attention_backward: the resident column indices were released (spmv_shim_restore_columns first)");
@@ -33,11 +69,15 @@ extern "C" int spmv_shim_attention_backward(spmv_dev *d, int k, int dv, double s
     DeviceGuard guard(d->device);
     if (!guard.ok) return fail(SPMV_HIP_E_RUNTIME, "hipSetDevice(%d) failed", d->device);
     int rc;
-    if ((rc = spmm_plan(d)) || (rc = attention_backward_plan(d)) || (cols && (rc = spmm_plan(t)))) return rc;
+    const int hg = attention_backward_group(d, heads, max_heads);
+    if ((rc = spmm_plan(d)) || (rc = attention_backward_plan(d, hg)) || (cols && (rc = spmm_plan(t)))) return rc;
     const size_t s = d->vsize;
     Stager stg{d};
     AttentionBwdArgs a;
     a.m = d->m;
+    a.heads = heads;
+    a.hg = hg;
+    a.plane = d->nnz;
     a.k = k;
     a.dv = dv;
     a.cus = d->cus;
@@ -68,27 +108,42 @@ extern "C" int spmv_shim_attention_backward(spmv_dev *d, int k, int dv, double s
     a.dk = cols ? dk : nullptr; a.lddk = lddk;
     a.dvo = cols ? dvo : nullptr; a.lddv = lddv;
     // every row of a wanted output gets its elements, empty rows and columns their zeros: a staged result is written completely before it is copied back
-    if ((rc = stg.in(d->stage[STAGE_ATTB_Q], a.q, a.ldq, (size_t) d->m, k)) || (rc = stg.in(d->stage[STAGE_ATTB_K], a.kk, a.ldk, (size_t) d->n, k)) ||
-        (rc = stg.in(d->stage[STAGE_ATTB_V], a.v, a.ldv, (size_t) d->n, dv)) || (rc = stg.in(d->stage[STAGE_ATTB_G], a.g, a.ldg, (size_t) d->m, dv)) ||
-        (a.dq && (rc = stg.out(d->stage[STAGE_ATTB_DQ], a.dq, a.lddq, (size_t) d->m, k))) || (a.dk && (rc = stg.out(d->stage[STAGE_ATTB_DK], a.dk, a.lddk, (size_t) d->n, k))) ||
-        (a.dvo && (rc = stg.out(d->stage[STAGE_ATTB_DV], a.dvo, a.lddv, (size_t) d->n, dv)))) return rc;
-    // the access width changes no bit (kernels/attention_backward.hpp): chosen per call from what the addresses allow
+    if ((rc = stg.in(d->stage[STAGE_ATTB_Q], a.q, a.ldq, (size_t) d->m, (int) wk)) || (rc = stg.in(d->stage[STAGE_ATTB_K], a.kk, a.ldk, (size_t) d->n, (int) wk)) ||
+        (rc = stg.in(d->stage[STAGE_ATTB_V], a.v, a.ldv, (size_t) d->n, (int) wv)) || (rc = stg.in(d->stage[STAGE_ATTB_G], a.g, a.ldg, (size_t) d->m, (int) wv)) ||
+        (a.dq && (rc = stg.out(d->stage[STAGE_ATTB_DQ], a.dq, a.lddq, (size_t) d->m, (int) wk))) || (a.dk && (rc = stg.out(d->stage[STAGE_ATTB_DK], a.dk, a.lddk, (size_t) d->n, (int) wk))) ||
+        (a.dvo && (rc = stg.out(d->stage[STAGE_ATTB_DV], a.dvo, a.lddv, (size_t) d->n, (int) wv)))) return rc;
+    // the access width changes no bit (kernels/attention_backward.hpp): chosen per call from what the addresses allow -- with more than one head,
+    // every head's first column has to be 16-byte aligned as well
     a.vec = wide_ok(a.q, a.ldq, s) && wide_ok(a.kk, a.ldk, s) && wide_ok(a.v, a.ldv, s) && wide_ok(a.g, a.ldg, s) && (!a.dq || wide_ok(a.dq, a.lddq, s)) &&
-            (!a.dk || wide_ok(a.dk, a.lddk, s)) && (!a.dvo || wide_ok(a.dvo, a.lddv, s));
+            (!a.dk || wide_ok(a.dk, a.lddk, s)) && (!a.dvo || wide_ok(a.dvo, a.lddv, s)) && (heads == 1 || (((size_t) k * s) % 16 == 0 && ((size_t) dv * s) % 16 == 0));
     const hipError_t e = attention_backward_launch(a, s == sizeof(double), d->stream);
     if (e != hipSuccess) return fail(SPMV_HIP_E_RUNTIME, "attention_backward: launch: %s", hipGetErrorString(e));
     return stg.finish();
 }
 
-extern "C" double spmv_shim_time_attention_backward(spmv_dev *d, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v,
-                                                    long long ldv, const void *g, long long ldg, void *dq, long long lddq, void *dk, long long lddk, void *dvo, long long lddv,
-                                                    int warmup, int iters, float *ms_out)
+extern "C" int spmv_shim_attention_backward(spmv_dev *d, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v,
+                                            long long ldv, const void *g, long long ldg, void *dq, long long lddq, void *dk, long long lddk, void *dvo, long long lddv)
+{
+    return spmv_shim_attention_heads_backward(d, 1, 0, k, dv, scale, q, ldq, kk, ldk, v, ldv, g, ldg, dq, lddq, dk, lddk, dvo, lddv);
+}
+
+extern "C" double spmv_shim_time_attention_heads_backward(spmv_dev *d, int heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk,
+                                                          long long ldk, const void *v, long long ldv, const void *g, long long ldg, void *dq, long long lddq, void *dk,
+                                                          long long lddk, void *dvo, long long lddv, int warmup, int iters, float *ms_out)
 {
     if (!d || !d->built || iters <= 0) { fail(SPMV_HIP_E_ARG, "time_attention_backward: bad arguments"); return -1.0; }
     if (!is_device_ptr(q) || !is_device_ptr(kk) || !is_device_ptr(v) || !is_device_ptr(g) || (dq && !is_device_ptr(dq)) || (dk && !is_device_ptr(dk)) || (dvo && !is_device_ptr(dvo))) {
         fail(SPMV_HIP_E_ARG, "time_attention_backward: Q, K, V, G and the outputs must be device pointers");
         return -1.0;
     }
-    return time_events(d, "time_attention_backward", warmup, iters, ms_out,
-                       [&] { return spmv_shim_attention_backward(d, k, dv, scale, q, ldq, kk, ldk, v, ldv, g, ldg, dq, lddq, dk, lddk, dvo, lddv); });
+    return time_events(d, "time_attention_backward", warmup, iters, ms_out, [&] {
+        return spmv_shim_attention_heads_backward(d, heads, max_heads, k, dv, scale, q, ldq, kk, ldk, v, ldv, g, ldg, dq, lddq, dk, lddk, dvo, lddv);
+    });
+}
+
+extern "C" double spmv_shim_time_attention_backward(spmv_dev *d, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v,
+                                                    long long ldv, const void *g, long long ldg, void *dq, long long lddq, void *dk, long long lddk, void *dvo, long long lddv,
+                                                    int warmup, int iters, float *ms_out)
+{
+    return spmv_shim_time_attention_heads_backward(d, 1, 0, k, dv, scale, q, ldq, kk, ldk, v, ldv, g, ldg, dq, lddq, dk, lddk, dvo, lddv, warmup, iters, ms_out);
 }

@@ -272,9 +272,12 @@ struct spmv_dev {
     bool att_planned = false;
     int *att_off = nullptr;   // [spmm_nlong + 1] first element of each long row in att_park
     void *att_park = nullptr; // sum of the long rows' lengths elements
-    // spmv_hip_attention_backward (shim/attention_backward.hpp): P and dS in CSR order, nnz elements each, allocated at the first call -- what the
-    // column pass over A^T gathers through tr_perm, and the long rows' parking space
+    // spmv_hip_attention_backward / _heads_backward (shim/attention_backward.hpp): P and dS in CSR order, attb_planes planes (one per head of a
+    // round) of nnz elements each, allocated at the first call and grown when a call needs more planes -- what the column pass over A^T gathers
+    // through tr_perm, and the long rows' parking space
     void *attb_p = nullptr, *attb_ds = nullptr;
+    int attb_planes = 0;
+    size_t attb_bytes = 0; // of each of the two, as counted in device_bytes
     // spmv_hip_spmv_transpose (shim/transpose.hpp): A^T as a matrix of its own (n x m), planned and built like any; perm[p] = our index of its entry p.
     // val_gen counts spmv_shim_update_values calls; A^T's values are gathered again when tr_gen falls behind it.
     spmv_dev *tr = nullptr;

@@ -1144,3 +1144,48 @@ double spmv_hip_time_attention_backward_launches(spmv_Handle_t h, int k, int dv,
         resident_state(h, where, RESIDENT_NOT_REORDERED, &st) || attention_backward_tables(h, st, where, dK || dV)) return -1.0;
     return report_time(spmv_shim_time_attention_backward(st->dev, k, dv, scale, Q, ldq, K, ldk, V, ldv, G, ldg, dQ, lddq, dK, lddk, dV, lddv, warmup, iters, ms_out), where);
 }
+
+/* ---------------------------------------------------------------- the same for `heads` heads side by side: two passes per group of heads */
+static int attention_heads_backward_args(spmv_Handle_t h, const char *where, int heads, int k, int dv, const void *Q, long long ldq, const void *K, long long ldk,
+                                         const void *V, long long ldv, const void *G, long long ldg, const void *dQ, long long lddq, const void *dK, long long lddk,
+                                         const void *dV, long long lddv, int m)
+{
+    long long wk, wv;
+    if (!h) return refuse(SPMV_HIP_E_ARG, where, "handle is NULL");
+    if (heads < 1 || k < 1 || dv < 1) return refuse(SPMV_HIP_E_ARG, where, "need heads >= 1, k >= 1 and dv >= 1");
+    wk = (long long) heads * k;
+    wv = (long long) heads * dv;
+    if (wk > INT_MAX || wv > INT_MAX) return refuse(SPMV_HIP_E_ARG, where, "heads * k or heads * dv does not fit an int");
+    if (ldq < wk || ldk < wk || ldv < wv || ldg < wv || (dQ && lddq < wk) || (dK && lddk < wk) || (dV && lddv < wv))
+        return refuse(SPMV_HIP_E_ARG, where, "need ldq, ldk >= heads * k, ldv, ldg >= heads * dv and, for the requested outputs, lddq, lddk >= heads * k, lddv >= heads * dv");
+    if (m > 0 && (!Q || !K || !V || !G)) return refuse(SPMV_HIP_E_ARG, where, "Q, K, V or G is NULL");
+    return SPMV_HIP_OK;
+}
+
+int spmv_hip_attention_heads_backward(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                                      const void *Matrix_Val, int heads, int k, int dv, double scale,
+                                      const void *Q, long long ldq, const void *K, long long ldk, const void *V, long long ldv,
+                                      const void *G, long long ldg, void *dQ, long long lddq, void *dK, long long lddk, void *dV, long long lddv)
+{
+    const char *where = "attention_heads_backward";
+    spmv_hip_state *st;
+    int rc;
+    if ((rc = attention_heads_backward_args(handle, where, heads, k, dv, Q, ldq, K, ldk, V, ldv, G, ldg, dQ, lddq, dK, lddk, dV, lddv, m))) return rc;
+    if (!dQ && !dK && !dV) return SPMV_HIP_OK; /* nothing wanted: no work, the handle's state is not looked at */
+    if ((rc = resident_prologue(handle, where, RESIDENT_NOT_REORDERED, m, RowPtr, ColIdx, Matrix_Val, &st))) return rc;
+    if ((rc = attention_backward_tables(handle, st, where, dK || dV))) return rc;
+    return report(spmv_shim_attention_heads_backward(st->dev, heads, (int) st->opts.v[SPMV_OPT_ATTENTION_BACKWARD_HEADS], k, dv, scale, Q, ldq, K, ldk, V, ldv, G, ldg, dQ, lddq,
+                                                     dK, lddk, dV, lddv), where);
+}
+
+double spmv_hip_time_attention_heads_backward_launches(spmv_Handle_t h, int heads, int k, int dv, double scale, const void *Q, long long ldq, const void *K, long long ldk,
+                                                       const void *V, long long ldv, const void *G, long long ldg, void *dQ, long long lddq, void *dK, long long lddk,
+                                                       void *dV, long long lddv, int warmup, int iters, float *ms_out)
+{
+    const char *where = "time_attention_heads_backward_launches";
+    spmv_hip_state *st;
+    if (attention_heads_backward_args(h, where, heads, k, dv, Q, ldq, K, ldk, V, ldv, G, ldg, dQ, lddq, dK, lddk, dV, lddv, 1) ||
+        resident_state(h, where, RESIDENT_NOT_REORDERED, &st) || attention_backward_tables(h, st, where, dK || dV)) return -1.0;
+    return report_time(spmv_shim_time_attention_heads_backward(st->dev, heads, (int) st->opts.v[SPMV_OPT_ATTENTION_BACKWARD_HEADS], k, dv, scale, Q, ldq, K, ldk, V, ldv, G, ldg,
+                                                               dQ, lddq, dK, lddk, dV, lddv, warmup, iters, ms_out), where);
+}

@@ -1,6 +1,7 @@
 // spmv_attention_backward.hip -- translation unit of the fused attention backward (kernels/attention_backward.hpp).  Launches only: the
 // tables, the transpose, the two nnz-sized arrays, staging and the error channel stay in spmv_shim.hip (shim/attention_backward.hpp), which
-// calls attention_backward_launch once per call.
+// calls attention_backward_launch once per call.  A call is ceil(heads / hg) rounds -- a row pass and a column pass over up to hg heads each,
+// the head loop inside the kernels --, the pointers offset here to the round's first head.
 #include <hip/hip_runtime.h>
 
 #include "kernels/common.hpp"
@@ -20,12 +21,12 @@ static void attention_bwd_rows_cw(const AttentionBwdArgs &a, hipStream_t stream)
     const T *q = (const T *) a.q, *kk = (const T *) a.kk, *v = (const T *) a.v, *g = (const T *) a.g;
     T *dq = (T *) a.dq, *p = (T *) a.p, *ds = (T *) a.ds;
     if (a.nb > 0)
-        attention_bwd_rows_kernel<T, CW, VEC><<<(a.nb + waves - 1) / waves, kBlock, 0, stream>>>(a.nb, a.split, a.rowptr, a.colidx, a.k, a.dv, cwd, lgk, scale, q, a.ldq, kk,
-                                                                                               a.ldk, v, a.ldv, g, a.ldg, dq, a.lddq, a.dvo ? p : nullptr,
+        attention_bwd_rows_kernel<T, CW, VEC><<<(a.nb + waves - 1) / waves, kBlock, 0, stream>>>(a.nb, a.split, a.rowptr, a.colidx, a.heads, a.plane, a.k, a.dv, cwd, lgk, scale,
+                                                                                               q, a.ldq, kk, a.ldk, v, a.ldv, g, a.ldg, dq, a.lddq, a.dvo ? p : nullptr,
                                                                                                a.dk ? ds : nullptr);
     if (a.nlong > 0)
-        attention_bwd_long_kernel<T, CW, VEC><<<a.nlong < a.cus * 8 ? a.nlong : a.cus * 8, kBlock, 0, stream>>>(a.nlong, a.longs, a.rowptr, a.colidx, a.k, a.dv, cwd, lgk, scale,
-                                                                                                              q, a.ldq, kk, a.ldk, v, a.ldv, g, a.ldg, dq, a.lddq, p, ds);
+        attention_bwd_long_kernel<T, CW, VEC><<<a.nlong < a.cus * 8 ? a.nlong : a.cus * 8, kBlock, 0, stream>>>(a.nlong, a.longs, a.rowptr, a.colidx, a.heads, a.plane, a.k, a.dv, cwd, lgk,
+                                                                                                              scale, q, a.ldq, kk, a.ldk, v, a.ldv, g, a.ldg, dq, a.lddq, p, ds);
 }
 
 // panel `c` of the column pass over A^T: kcv columns of dV, kck columns of dK
@@ -37,27 +38,47 @@ static void attention_bwd_cols_cw(const AttentionBwdArgs &a, int c, int kcv, int
     const T *g = (const T *) a.g + c, *q = (const T *) a.q + c;
     T *dvo = a.dvo ? (T *) a.dvo + c : nullptr, *dk = a.dk ? (T *) a.dk + c : nullptr;
     if (a.t_nb > 0)
-        attention_bwd_cols_kernel<T, CW, VEC><<<(a.t_nb + waves - 1) / waves, kBlock, 0, stream>>>(a.t_nb, a.t_split, a.t_rowptr, a.t_colidx, a.perm, pv, dsv, kcv, g, a.ldg, dvo,
-                                                                                                 a.lddv, kck, q, a.ldq, dk, a.lddk);
+        attention_bwd_cols_kernel<T, CW, VEC><<<(a.t_nb + waves - 1) / waves, kBlock, 0, stream>>>(a.t_nb, a.t_split, a.t_rowptr, a.t_colidx, a.perm, a.heads, a.plane, a.k, a.dv,
+                                                                                                 pv, dsv, kcv, g, a.ldg, dvo, a.lddv, kck, q, a.ldq, dk, a.lddk);
     if (a.t_nlong > 0)
-        attention_bwd_cols_long_kernel<T, CW, VEC><<<a.t_nlong < a.cus * 8 ? a.t_nlong : a.cus * 8, kBlock, 0, stream>>>(a.t_nlong, a.t_longs, a.t_rowptr, a.t_colidx, a.perm, pv,
-                                                                                                                       dsv, kcv, g, a.ldg, dvo, a.lddv, kck, q, a.ldq, dk,
-                                                                                                                       a.lddk);
+        attention_bwd_cols_long_kernel<T, CW, VEC><<<a.t_nlong < a.cus * 8 ? a.t_nlong : a.cus * 8, kBlock, 0, stream>>>(a.t_nlong, a.t_longs, a.t_rowptr, a.t_colidx, a.perm,
+                                                                                                                       a.heads, a.plane, a.k, a.dv, pv, dsv, kcv, g, a.ldg, dvo,
+                                                                                                                       a.lddv, kck, q, a.ldq, dk, a.lddk);
 }
 
+// one round: a.heads heads from the pointers' first columns, planes 0 .. a.heads - 1
 template <typename T, bool VEC>
-static void attention_bwd_launch_t(const AttentionBwdArgs &a, hipStream_t stream)
+static void attention_bwd_round(const AttentionBwdArgs &a, hipStream_t stream)
 {
     constexpr int KP = SpmmShape<T>::KP;
     // sddmm's lane group for k: a function of k and the value type alone, it fixes the scores' summation order
     if (a.m > 0) with_width(panel_group_width<T>(a.k), [&](auto CW) { attention_bwd_rows_cw<T, decltype(CW)::value, VEC>(a, stream); });
     if (!a.dk && !a.dvo) return;
     const int wk = a.dk ? a.k : 0, wv = a.dvo ? a.dv : 0;
-    for (int c = 0; c < wk || c < wv; c += KP) { // panel c / KP of both outputs in one pass over A^T
+    for (int c = 0; c < wk || c < wv; c += KP) { // panel c / KP of both outputs, of every head of the round, in one pass over A^T
         const int kcv = wv - c < KP ? wv - c : KP, kck = wk - c < KP ? wk - c : KP; // <= 0: that output has no such panel
         const int kc = kcv > kck ? kcv : kck;
         // the narrowest lane group that covers the wider panel's columns
         with_width(panel_group_width<T>(kc), [&](auto CW) { attention_bwd_cols_cw<T, decltype(CW)::value, VEC>(a, c, kcv, kck, stream); });
+    }
+}
+
+template <typename T, bool VEC>
+static void attention_bwd_launch_t(const AttentionBwdArgs &a, hipStream_t stream)
+{
+    const int hg = a.hg < 1 ? 1 : a.hg;
+    for (int h0 = 0; h0 < a.heads; h0 += hg) { // a round's column pass has read the planes before the next round's row pass writes them: one stream
+        AttentionBwdArgs r = a;
+        r.heads = a.heads - h0 < hg ? a.heads - h0 : hg;
+        const long long ck = (long long) h0 * a.k, cv = (long long) h0 * a.dv; // the round's first columns
+        r.q = (const T *) a.q + ck;
+        r.kk = (const T *) a.kk + ck;
+        r.v = (const T *) a.v + cv;
+        r.g = (const T *) a.g + cv;
+        if (a.dq) r.dq = (T *) a.dq + ck;
+        if (a.dk) r.dk = (T *) a.dk + ck;
+        if (a.dvo) r.dvo = (T *) a.dvo + cv;
+        attention_bwd_round<T, VEC>(r, stream);
     }
 }
 

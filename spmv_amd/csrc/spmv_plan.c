@@ -80,6 +80,8 @@ static opt_t g_opts[SPMV_N_OPTS] = {
     [SPMV_OPT_BLK_SUBSORT] = {"blk_subsort", 1, 0, 1, 0, 0},          /* ... sparse (block, slab) cells stored sorted by column (1) or in CSR order (0: round 3's order, A/B) */
     [SPMV_OPT_DETERMINISTIC] = {"deterministic", 1, 0, 1, 0, 0},      /* 1: results are bit-reproducible run to run and handle to handle (every executor); 0: the wide blocked form may let its
                                                                        * waves add into the shared accumulators in arrival order (faster, correct to rounding, not reproducible) */
+    [SPMV_OPT_ATTENTION_BACKWARD_HEADS] = {"attention_backward_heads", 0, 0, 1024, 0, 0}, /* spmv_hip_attention_heads_backward: heads per round = planes of attb_p / attb_ds; 0 = as many as keep
+                                                                       * 2 * HG * s * nnz bytes within an eighth of the device's memory (shim/attention_backward.hpp).  Changes no bit */
     [SPMV_OPT_X_EXCHANGE] = {"x_exchange", 0, 0, 2, 0, 0},            /* multi-GPU: 0 = allgather of the x slices, 1 = range (each device gets x[min col .. max col] of its block), 2 = broadcast from device 0 */
 };
 

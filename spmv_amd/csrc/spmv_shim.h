@@ -161,6 +161,17 @@ double spmv_shim_time_attention_backward(spmv_dev *d, int k, int dv, double scal
                                          const void *g, long long ldg, void *dq, long long lddq, void *dk, long long lddk, void *dv_out, long long lddv, int warmup, int iters,
                                          float *ms_out);
 
+/* `heads` heads side by side in the rows (spmv_hip_attention_heads_backward): Q, K, dq, dk heads*k columns wide, V, G, dv_out heads*dv; head h
+ * is spmv_shim_attention_backward on the columns from h*k and h*dv.  ceil(heads / hg) rounds of the two passes, the head loop inside the
+ * kernels; hg = min(heads, max_heads) when max_heads > 0 (option "attention_backward_heads"), else what fits an eighth of the device's memory.
+ * The two arrays hold hg planes of nnz elements, grown when a call needs more.  heads = 1 is spmv_shim_attention_backward. */
+int spmv_shim_attention_heads_backward(spmv_dev *d, int heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
+                                       const void *v, long long ldv, const void *g, long long ldg, void *dq, long long lddq, void *dk, long long lddk, void *dv_out,
+                                       long long lddv);
+double spmv_shim_time_attention_heads_backward(spmv_dev *d, int heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
+                                               const void *v, long long ldv, const void *g, long long ldg, void *dq, long long lddq, void *dk, long long lddk, void *dv_out,
+                                               long long lddv, int warmup, int iters, float *ms_out);
+
 /* the resident CSR arrays (device pointers; ColIdx may be NULL after spmv_shim_release_columns) */
 void spmv_shim_matrix_arrays(const spmv_dev *d, const int **rowptr, const int **colidx, const void **val);
 
