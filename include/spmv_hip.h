@@ -350,6 +350,57 @@ int spmv_hip_attention_heads_backward(spmv_Handle_t handle, BASIC_INT_TYPE m, co
                                       void *dK, long long lddk,                /* n x heads*k,  or NULL */
                                       void *dV, long long lddv);               /* n x heads*dv, or NULL */
 
+/* ---- sparse attention with an additive bias per head and stored entry -----------------------------
+ * spmv_hip_attention_heads with  t_p = (s_p * scale) + B_p  in place of its step 2: edge biases of graph transformers, relative-position and
+ * ALiBi biases on a band, additive masks (-inf on an entry) that vary per head or per call without another handle.  Everything else -- the
+ * layout of Q, K, V and O, k, dv and scale as ONE head's, the writes, steps 1, 3 and 4, the launches, the CSR arguments, the stream and async
+ * setting, the column indices, the handle kinds -- is that section's.  A's VALUES are not read and the resident values are NOT MODIFIED.
+ *   - B holds bias PLANES in the handle's precision: B[h*ldb + p] is the bias of head h on entry p of the caller's CSR order (the order of
+ *     ColIdx and Matrix_Val).  ldb >= nnz: one plane per head; ldb == 0: one plane shared by all heads.  Host or device pointer.  B is only
+ *     read, and may be the very array passed as Matrix_Val (edge weights as bias).  Element accesses: B needs no alignment.
+ *   - The one new step: t_p = (s_p * scale) + B_p is one plain multiplication followed by one plain addition, NEVER an fma -- the bits of the
+ *     composition spmv_hip_sddmm, * scale, + B, spmv_hip_row_softmax, spmv_hip_spmm (values = P), head by head.  The result is a function of
+ *     the matrix, k, dv, the value type and B's values alone (not of ldb, shared or per-head planes holding the same values, pointer kind, ..).
+ *   - B == NULL: ldb is ignored and the call IS spmv_hip_attention_heads, to the bit.
+ *   - Special values follow from the steps: a -inf bias beside finite scores gives that entry an exact +0 weight; a row whose biases are all
+ *     -inf, or that holds a NaN or +inf, is NaN in O for that head and that row only.
+ *   - Memory: a host B is staged through one more handle-owned buffer (the planes packed, allocated at first use, counted in
+ *     spmv_hip_info.device_bytes, freed with the others); with device operands device_bytes grows by nothing over spmv_hip_attention_heads.
+ *   - Errors: spmv_hip_attention_heads' (SPMV_HIP_E_ARG before the handle is looked at, O untouched), and ldb < 0 (with a B) with them; once nnz is
+ *     known, 0 < ldb < nnz: SPMV_HIP_E_ARG, O untouched.  Handle kinds and SPMV_HIP_E_NOSTATE as there. */
+int spmv_hip_attention_bias(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                            const void *Matrix_Val, int heads, int k, int dv, double scale,
+                            const void *Q, long long ldq, const void *K, long long ldk, const void *V, long long ldv,
+                            const void *B, long long ldb,            /* bias planes, or NULL: spmv_hip_attention_heads */
+                            void *O, long long ldo);
+
+/* ---- the gradients of spmv_hip_attention_bias: dQ, dK, dV and dB -------------------------------------
+ * spmv_hip_attention_heads_backward with t_p = (s_p * scale) + B_p as in spmv_hip_attention_bias, and one more output:
+ *   dB_p = P_p * (dP_p - D_i)   -- spmv_hip_row_softmax_backward's output: one subtraction and one multiplication --
+ * the value from which dS_p = dB_p * scale is made as before; dQ, dK and dV follow from dS exactly as there.  B is laid out as in
+ * spmv_hip_attention_bias (ldb == 0: shared; else >= nnz).  dB always has `heads` planes, dB[h*lddb + p] with lddb >= nnz, host or device
+ * pointer, NULL = not wanted; a shared bias' gradient is the sum of the planes, which is the caller's to take.
+ *   - B == NULL: ldb is ignored; dQ, dK and dV are spmv_hip_attention_heads_backward's to the bit, and dB is still the formula above.
+ *   - Special values: where B_p = -inf beside finite scores, P_p = +0 and dB_p = +-0.
+ *   - Which passes run: dB is written by the row pass alone.  Only dB wanted: the row pass runs, computes no dQ and stores nothing for the
+ *     column pass, and the transpose is neither built nor read.  All four outputs NULL: 0 right after argument checking.
+ *   - Option "attention_backward_heads" changes no bit of dB either: dB goes straight to the caller's plane of each head, not through the
+ *     handle's planes.  Which outputs are wanted changes no bit of any of them.
+ *   - Writes: exactly the first nnz elements of each of the `heads` planes of dB; the padding between planes is never read or written.
+ *   - Memory: host B / dB are staged through two more handle-owned buffers (shared with spmv_hip_attention_bias); with device operands
+ *     device_bytes grows by nothing over spmv_hip_attention_heads_backward.
+ *   - Errors: spmv_hip_attention_heads_backward's (SPMV_HIP_E_ARG before the handle's state is looked at, every output untouched), and
+ *     ldb < 0 (with a B) or lddb < 0 (with a dB) with them; once nnz is known, 0 < ldb < nnz, or dB != NULL with lddb < nnz: SPMV_HIP_E_ARG, every output untouched. */
+int spmv_hip_attention_bias_backward(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                                     const void *Matrix_Val, int heads, int k, int dv, double scale,
+                                     const void *Q, long long ldq, const void *K, long long ldk, const void *V, long long ldv,
+                                     const void *B, long long ldb,            /* bias planes, or NULL */
+                                     const void *G, long long ldg,            /* dL/dO, m x heads*dv */
+                                     void *dQ, long long lddq,                /* m x heads*k,  or NULL: not wanted */
+                                     void *dK, long long lddk,                /* n x heads*k,  or NULL */
+                                     void *dV, long long lddv,                /* n x heads*dv, or NULL */
+                                     void *dB, long long lddb);               /* heads planes of nnz, or NULL */
+
 /* ---- options --------------------------------------------------------------------------------
  * Resolved once per handle, at create: process-wide value (spmv_hip_set_option / env), overridden by the
  * calling thread's value (spmv_hip_set_thread_option) -- so two threads can create differently tuned handles

@@ -139,6 +139,16 @@ FUNCTIONS = {
     "spmv_hip_time_attention_heads_backward_launches": (C.c_double, [spmv_Handle_t, C.c_int, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong,
                                                                      _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong,
                                                                      C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "spmv_hip_attention_bias": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, C.c_int, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong,
+                                          _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong]),
+    "spmv_hip_time_attention_bias_launches": (C.c_double, [spmv_Handle_t, C.c_int, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong,
+                                                           _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "spmv_hip_attention_bias_backward": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, C.c_int, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong,
+                                                   _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong,
+                                                   _V, C.c_longlong]),
+    "spmv_hip_time_attention_bias_backward_launches": (C.c_double, [spmv_Handle_t, C.c_int, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong,
+                                                                    _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong,
+                                                                    _V, C.c_longlong, _V, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_float)]),
     # include/spmv_io.h (host only)
     "spmv_io_read_mtx": (C.c_int, [C.c_char_p, C.c_size_t, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_V)]),
     "spmv_io_cache_path": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t]),
@@ -558,6 +568,68 @@ def time_attention_heads_backward_launches(handle, heads, Q, K, V, G, dQ=None, d
     return _timed("spmv_hip_time_attention_heads_backward_launches", (handle, int(heads), b[0], b[1], float(scale), *b[2:]), warmup, iters)
 
 
+def _planes(a, name, heads, shared_ok):
+    """-> (address, ld) of bias planes: None -> (None, 0); a 1-D array / tensor of nnz elements is ONE plane for all heads (ld 0, only where
+    `shared_ok`); a 2-D one of (heads, nnz) with column stride 1 has a plane per head, its row stride as ld."""
+    if a is None:
+        return None, 0
+    if len(a.shape) == 1:
+        if not shared_ok and int(heads) != 1:
+            raise ValueError(f"{name} must be 2-D, (heads, nnz)")
+        p, _, _, _ = _block(a.reshape(1, -1), name)
+        return p, (0 if shared_ok else int(a.shape[0]))
+    if len(a.shape) != 2 or a.shape[0] != int(heads):
+        raise ValueError(f"{name} must be (nnz,) or ({int(heads)}, nnz), not {tuple(a.shape)}")
+    p, _, w, ld = _block(a, name)
+    return p, int(max(ld, w, 1))
+
+
+def attention_bias(handle, m, RowPtr, ColIdx, Matrix_Val, heads, Q, K, V, B, O, scale=None, check=True, ldb=None):
+    """attention_heads() with the additive bias B on the scaled scores (spmv_hip_attention_bias): t = (s * scale) + B.  B: None (then this IS
+    attention_heads), an (nnz,) array / tensor -- one plane shared by all heads -- or (heads, nnz) -- a plane per head, any row stride --, in
+    CSR order; ldb overrides the plane stride derived from B (for flat buffers holding padded planes).  -> the return code."""
+    k, dv, pq, ldq, pk, ldk, pv, ldv, po, ldo = _attention_heads_blocks(heads, Q, K, V, O)
+    scale = 1.0 / np.sqrt(k) if scale is None and k > 0 else (0.0 if scale is None else scale)
+    pb, ld = (_ptr(B), int(ldb)) if ldb is not None else _planes(B, "B", heads, True)
+    return _checked(load().spmv_hip_attention_bias(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), int(heads), k, dv, float(scale),
+                                                   pq, ldq, pk, ldk, pv, ldv, pb, ld, po, ldo), "spmv_hip_attention_bias", check)
+
+
+def time_attention_bias_launches(handle, heads, Q, K, V, B, O, scale=None, warmup=10, iters=100):
+    """-> (mean_ms, per-call ms array) of spmv_hip_attention_bias on device operands (spmv_hip_time_attention_bias_launches)."""
+    k, dv, pq, ldq, pk, ldk, pv, ldv, po, ldo = _attention_heads_blocks(heads, Q, K, V, O)
+    scale = 1.0 / np.sqrt(k) if scale is None else scale
+    pb, ld = _planes(B, "B", heads, True)
+    return _timed("spmv_hip_time_attention_bias_launches", (handle, int(heads), k, dv, float(scale), pq, ldq, pk, ldk, pv, ldv, pb, ld, po, ldo), warmup, iters)
+
+
+def _attention_bias_backward_args(heads, Q, K, V, B, G, dQ, dK, dV, dB, ldb, lddb):
+    b = _attention_heads_backward_blocks(heads, Q, K, V, G, dQ, dK, dV)
+    pb, ld = (_ptr(B), int(ldb)) if ldb is not None else _planes(B, "B", heads, True)
+    pdb, ldd = (_ptr(dB), int(lddb)) if lddb is not None else _planes(dB, "dB", heads, False)
+    # k, dv, Q, K, V | B | G, dQ, dK, dV | dB
+    return b[0], b[1], [*b[2:8], pb, ld, *b[8:], pdb, ldd]
+
+
+def attention_bias_backward(handle, m, RowPtr, ColIdx, Matrix_Val, heads, Q, K, V, B, G, dQ=None, dK=None, dV=None, dB=None, scale=None, check=True,
+                            ldb=None, lddb=None):
+    """dQ, dK, dV and dB of attention_bias(Q, K, V, B) from G = dL/dO (spmv_hip_attention_bias_backward).  B as in attention_bias(); dB: None
+    (not wanted) or (heads, nnz) -- always a plane per head, dB[h, p] = P (dP - D) of head h --; the other operands as in
+    attention_heads_backward(); ldb / lddb override the plane strides.  With B None, dQ, dK and dV are attention_heads_backward()'s to the
+    bit.  -> the return code."""
+    k, dv, rest = _attention_bias_backward_args(heads, Q, K, V, B, G, dQ, dK, dV, dB, ldb, lddb)
+    scale = 1.0 / np.sqrt(k) if scale is None and k > 0 else (0.0 if scale is None else scale)
+    return _checked(load().spmv_hip_attention_bias_backward(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), int(heads), k, dv, float(scale), *rest),
+                    "spmv_hip_attention_bias_backward", check)
+
+
+def time_attention_bias_backward_launches(handle, heads, Q, K, V, B, G, dQ=None, dK=None, dV=None, dB=None, scale=None, warmup=10, iters=100):
+    """-> (mean_ms, per-call ms array) of spmv_hip_attention_bias_backward on device operands (spmv_hip_time_attention_bias_backward_launches)."""
+    k, dv, rest = _attention_bias_backward_args(heads, Q, K, V, B, G, dQ, dK, dV, dB, None, None)
+    scale = 1.0 / np.sqrt(k) if scale is None else scale
+    return _timed("spmv_hip_time_attention_bias_backward_launches", (handle, int(heads), k, dv, float(scale), *rest), warmup, iters)
+
+
 def _take_csr(m, n, nnz, rp, ci, va, dtype):
     """Copy malloc'ed C arrays into numpy arrays and free the C side."""
     from .synth import CSR
@@ -756,6 +828,29 @@ class Handle:
         rp, ci, va = self._keep
         attention_heads_backward(self.h, self.m, rp, ci, va, heads, Q, K, V, G, dQ, dK, dV, scale)
         return dQ, dK, dV
+
+    def attention_bias(self, Q, K, V, heads, bias, scale=None, out=None):
+        """out = attention_heads(Q, K, V, heads, scale) with `bias` added to the scaled scores before the softmax (spmv_hip_attention_bias);
+        bias: None, (nnz,) -- one plane for all heads -- or (heads, nnz), in CSR order, of Q's kind.  The handle's values are not used and not
+        changed."""
+        if out is None:
+            out = self._like(Q, (self.m, V.shape[1]))
+        rp, ci, va = self._keep
+        attention_bias(self.h, self.m, rp, ci, va, heads, Q, K, V, bias, out, scale)
+        return out
+
+    def attention_bias_backward(self, Q, K, V, bias, G, heads, scale=None, need=(True, True, True, True)):
+        """-> (dQ, dK, dV, dB), the gradients of attention_bias(Q, K, V, heads, bias, scale) for G = dL/dO (spmv_hip_attention_bias_backward);
+        need: which of the four are wanted -- the others are None and nothing is computed for them.  dB is (heads, nnz), a plane per head also
+        when the bias is one shared plane (its gradient is dB.sum(0)).  The outputs are allocated like Q."""
+        wk, wv = Q.shape[1], V.shape[1]
+        dQ = self._like(Q, (self.m, wk)) if need[0] else None
+        dK = self._like(Q, (self.n, wk)) if need[1] else None
+        dV = self._like(Q, (self.n, wv)) if need[2] else None
+        dB = self._like(Q, (int(heads), self.nnz)) if need[3] else None
+        rp, ci, va = self._keep
+        attention_bias_backward(self.h, self.m, rp, ci, va, heads, Q, K, V, bias, G, dQ, dK, dV, dB, scale)
+        return dQ, dK, dV, dB
 
     def update_values(self, val):
         """The caller changed the values (in place or in a new array of the same pattern)."""

@@ -24,6 +24,9 @@ library's kernels forward and backward (Handle.sddmm / row_softmax / spmm; Handl
     O = spmv_amd.autograd.attention_heads(handle, Q, K, V, heads)  the same for `heads` heads side by side in the columns of Q, K and V
                                                                    (Handle.attention_heads: all heads in that one pass)
 
+Both take a trailing keyword bias=None: a tensor of (nnz,) -- one plane, shared by all heads -- or (heads, nnz), in CSR order, added to the
+scaled scores before the softmax (Handle.attention_bias), which receives a gradient (Handle.attention_bias_backward).
+
 Every call runs on torch's current stream.  The only module of the package that needs torch; libspmv_hip.so has no torch dependency.
 """
 from __future__ import annotations
@@ -223,31 +226,58 @@ def sddmm(handle, U, V):
     return _Sddmm.apply(handle, U, V)
 
 
+def _bias_planes(bias):
+    """the bias as the C side can address it: detached -- a reference, not a copy, unless its layout has to be mended"""
+    if bias is None:
+        return None
+    b = bias.detach()
+    return b.contiguous() if b.dim() == 1 else _block(b, b.shape[1])
+
+
+def _forward(handle, Q2, K2, V2, heads, bias, scale):
+    """the one fused forward pass: Handle.attention / attention_heads, or Handle.attention_bias when there is a bias"""
+    if bias is not None:
+        return handle.attention_bias(Q2, K2, V2, heads, bias, scale)
+    return handle.attention(Q2, K2, V2, scale) if heads is None else handle.attention_heads(Q2, K2, V2, heads, scale)
+
+
+def _bias_grad(dB, bias):
+    """dL/dbias from the per-head planes dB (heads, nnz): a shared plane's is their sum -- torch's sum, whose order is torch's business"""
+    if dB is None:
+        return None
+    return dB.sum(0) if bias.dim() == 1 and dB.shape[0] > 1 else dB.view(bias.shape)
+
+
 class _Attention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, handle, Q, K, V, scale):
+    def forward(ctx, handle, Q, K, V, scale, bias=None):
         Q2, K2, V2 = _block(Q.detach(), Q.shape[1]), _block(K.detach(), K.shape[1]), _block(V.detach(), V.shape[1])
+        B2 = _bias_planes(bias)
         _on_current_stream(handle)
-        O = handle.attention(Q2, K2, V2, scale)
+        O = _forward(handle, Q2, K2, V2, None if B2 is None else 1, B2, scale)
         ctx.handle, ctx.scale = handle, scale
-        ctx.save_for_backward(Q2, K2, V2)   # nothing nnz-sized: the backward pass computes S and P again
+        ctx.save_for_backward(Q2, K2, V2, B2)   # nothing nnz-sized but the caller's own bias: the backward pass computes S and P again
         return O
 
     @staticmethod
     @once_differentiable
     def backward(ctx, G):
         handle, scale = ctx.handle, ctx.scale
-        Q2, K2, V2 = ctx.saved_tensors
+        Q2, K2, V2, B2 = ctx.saved_tensors
         need_q, need_k, need_v = ctx.needs_input_grad[1:4]
-        dQ = dK = dV = None
-        if not (need_q or need_k or need_v):
-            return None, None, None, None, None
+        need_b = B2 is not None and ctx.needs_input_grad[5]
+        dQ = dK = dV = dB = None
+        if not (need_q or need_k or need_v or need_b):
+            return None, None, None, None, None, None
         if handle.nnz == 0:   # no stored entry: O is zero whatever Q, K and V are
-            return None, (torch.zeros_like(Q2) if need_q else None), (torch.zeros_like(K2) if need_k else None), (torch.zeros_like(V2) if need_v else None), None
+            return None, (torch.zeros_like(Q2) if need_q else None), (torch.zeros_like(K2) if need_k else None), (torch.zeros_like(V2) if need_v else None), None, \
+                (torch.zeros_like(B2) if need_b else None)
         _on_current_stream(handle)
         G2 = _block(G, G.shape[1])
         S = handle.sddmm(Q2, K2)
         S.mul_(scale)
+        if B2 is not None:
+            S.add_(B2.view(-1))   # a rounding of its own after the scaling's: the fused kernels' two steps
         P = handle.row_softmax(S, out=S)
         # A_P, then A_dS = A's pattern with those values, for the duration: the handle's own values, and what matmul() remembers of them, come back below
         keep, token, ref = handle._keep[2], getattr(handle, "_values_token", None), getattr(handle, "_values_ref", None)
@@ -255,9 +285,12 @@ class _Attention(torch.autograd.Function):
             if need_v:
                 handle.update_values(P)
                 dV = handle.spmm_transpose(G2)
-            if need_q or need_k:
+            if need_q or need_k or need_b:
                 dP = handle.sddmm(G2, V2)
                 dS = handle.row_softmax_backward(P, dP, out=dP)
+                if need_b:   # the bias enters after the scaling: its gradient is dS before it
+                    dB = dS.clone().view(B2.shape) if need_q or need_k else dS.view(B2.shape)
+            if need_q or need_k:
                 dS.mul_(scale)
                 handle.update_values(dS)
                 if need_q:
@@ -267,31 +300,36 @@ class _Attention(torch.autograd.Function):
         finally:
             handle.update_values(keep)
             handle._values_token, handle._values_ref = token, ref
-        return None, dQ, dK, dV, None
+        return None, dQ, dK, dV, None, dB
 
 
 class _AttentionFused(torch.autograd.Function):
     """_Attention's forward; the backward pass is ONE Handle.attention_backward call: the handle's values are never touched"""
 
     @staticmethod
-    def forward(ctx, handle, Q, K, V, scale):
+    def forward(ctx, handle, Q, K, V, scale, bias=None):
         Q2, K2, V2 = _block(Q.detach(), Q.shape[1]), _block(K.detach(), K.shape[1]), _block(V.detach(), V.shape[1])
+        B2 = _bias_planes(bias)
         _on_current_stream(handle)
-        O = handle.attention(Q2, K2, V2, scale)
+        O = _forward(handle, Q2, K2, V2, None if B2 is None else 1, B2, scale)
         ctx.handle, ctx.scale = handle, scale
-        ctx.save_for_backward(Q2, K2, V2)
+        ctx.save_for_backward(Q2, K2, V2, B2)
         return O
 
     @staticmethod
     @once_differentiable
     def backward(ctx, G):
-        Q2, K2, V2 = ctx.saved_tensors
+        Q2, K2, V2, B2 = ctx.saved_tensors
         need = tuple(bool(x) for x in ctx.needs_input_grad[1:4])
-        if not any(need):
-            return None, None, None, None, None
+        need_b = B2 is not None and bool(ctx.needs_input_grad[5])
+        if not (any(need) or need_b):
+            return None, None, None, None, None, None
         _on_current_stream(ctx.handle)
-        dQ, dK, dV = ctx.handle.attention_backward(Q2, K2, V2, _block(G, G.shape[1]), ctx.scale, need=need)
-        return None, dQ, dK, dV, None
+        if B2 is None:
+            dQ, dK, dV = ctx.handle.attention_backward(Q2, K2, V2, _block(G, G.shape[1]), ctx.scale, need=need)
+            return None, dQ, dK, dV, None, None
+        dQ, dK, dV, dB = ctx.handle.attention_bias_backward(Q2, K2, V2, B2, _block(G, G.shape[1]), 1, ctx.scale, need=(*need, need_b))
+        return None, dQ, dK, dV, None, _bias_grad(dB, B2)
 
 
 class _AttentionHeads(torch.autograd.Function):
@@ -299,12 +337,13 @@ class _AttentionHeads(torch.autograd.Function):
     of full-width gradients, or (fused) ONE Handle.attention_heads_backward call: the handle's values are never touched"""
 
     @staticmethod
-    def forward(ctx, handle, Q, K, V, heads, scale, fused=False):
+    def forward(ctx, handle, Q, K, V, heads, scale, fused=False, bias=None):
         Q2, K2, V2 = _block(Q.detach(), Q.shape[1]), _block(K.detach(), K.shape[1]), _block(V.detach(), V.shape[1])
+        B2 = _bias_planes(bias)
         _on_current_stream(handle)
-        O = handle.attention_heads(Q2, K2, V2, heads, scale)
+        O = _forward(handle, Q2, K2, V2, heads, B2, scale)
         ctx.handle, ctx.heads, ctx.scale, ctx.fused = handle, heads, scale, fused
-        ctx.save_for_backward(Q2, K2, V2)   # nothing nnz-sized
+        ctx.save_for_backward(Q2, K2, V2, B2)   # nothing nnz-sized but the caller's own bias
         return O
 
     @staticmethod
@@ -312,30 +351,49 @@ class _AttentionHeads(torch.autograd.Function):
     def backward(ctx, G):
         from . import api
         handle, heads, scale = ctx.handle, ctx.heads, ctx.scale
-        Q2, K2, V2 = ctx.saved_tensors
+        Q2, K2, V2, B2 = ctx.saved_tensors
         need = tuple(bool(x) for x in ctx.needs_input_grad[1:4])
-        if not any(need):
-            return None, None, None, None, None, None, None
+        need_b = B2 is not None and bool(ctx.needs_input_grad[7])
+        if not (any(need) or need_b):
+            return None, None, None, None, None, None, None, None
         if handle.nnz == 0:   # no stored entry: O is zero whatever Q, K and V are
-            return None, (torch.zeros_like(Q2) if need[0] else None), (torch.zeros_like(K2) if need[1] else None), (torch.zeros_like(V2) if need[2] else None), None, None, None
+            return None, (torch.zeros_like(Q2) if need[0] else None), (torch.zeros_like(K2) if need[1] else None), (torch.zeros_like(V2) if need[2] else None), None, None, None, \
+                (torch.zeros_like(B2) if need_b else None)
         _on_current_stream(handle)
         G2 = _block(G, G.shape[1])
         if ctx.fused:   # every head in one call
-            dQ, dK, dV = handle.attention_heads_backward(Q2, K2, V2, G2, heads, scale, need=need)
-            return None, dQ, dK, dV, None, None, None
+            if B2 is None:
+                dQ, dK, dV = handle.attention_heads_backward(Q2, K2, V2, G2, heads, scale, need=need)
+                return None, dQ, dK, dV, None, None, None, None
+            dQ, dK, dV, dB = handle.attention_bias_backward(Q2, K2, V2, B2, G2, heads, scale, need=(*need, need_b))
+            return None, dQ, dK, dV, None, None, None, _bias_grad(dB, B2)
         k, dv = Q2.shape[1] // heads, V2.shape[1] // heads
         dQ = torch.empty_like(Q2, memory_format=torch.contiguous_format) if need[0] else None
         dK = torch.empty_like(K2, memory_format=torch.contiguous_format) if need[1] else None
         dV = torch.empty_like(V2, memory_format=torch.contiguous_format) if need[2] else None
+        dB = Q2.new_empty((heads, handle.nnz)) if need_b else None
         rp, ci, va = handle._keep
         for h in range(heads):
             ck, cv = slice(h * k, (h + 1) * k), slice(h * dv, (h + 1) * dv)
-            api.attention_backward(handle.h, handle.m, rp, ci, va, Q2[:, ck], K2[:, ck], V2[:, cv], G2[:, cv],
-                                   None if dQ is None else dQ[:, ck], None if dK is None else dK[:, ck], None if dV is None else dV[:, cv], scale)
-        return None, dQ, dK, dV, None, None, None
+            if B2 is None:
+                api.attention_backward(handle.h, handle.m, rp, ci, va, Q2[:, ck], K2[:, ck], V2[:, cv], G2[:, cv],
+                                       None if dQ is None else dQ[:, ck], None if dK is None else dK[:, ck], None if dV is None else dV[:, cv], scale)
+            else:   # one head on its column slices and on its plane of the bias and of dB
+                api.attention_bias_backward(handle.h, handle.m, rp, ci, va, 1, Q2[:, ck], K2[:, ck], V2[:, cv], B2 if B2.dim() == 1 else B2[h], G2[:, cv],
+                                            None if dQ is None else dQ[:, ck], None if dK is None else dK[:, ck], None if dV is None else dV[:, cv],
+                                            None if dB is None else dB[h], scale)
+        return None, dQ, dK, dV, None, None, None, _bias_grad(dB, B2)
 
 
-def attention_heads(handle, Q, K, V, heads, scale=None, backward="per_head"):
+def _check_bias(bias, handle, heads):
+    if bias is None:
+        return
+    _check_tensor(bias, "bias", handle)
+    if tuple(bias.shape) not in ((handle.nnz,), (heads, handle.nnz)):
+        raise ValueError(f"bias must be ({handle.nnz},) or ({heads}, {handle.nnz}), not {tuple(bias.shape)}")
+
+
+def attention_heads(handle, Q, K, V, heads, scale=None, backward="per_head", *, bias=None):
     """`heads` attention heads over the handle's pattern (Handle.attention_heads: one fused pass for all heads), with gradients for Q, K and
     V.  Q: (m, heads * k), K: (n, heads * k), V: (n, heads * dv) hold the heads side by side -- a (rows, heads, k) tensor reshaped to two
     dimensions --, of the handle's dtype on its device; the result is (m, heads * dv).  scale: a Python number, None means 1 / sqrt(k) with k
@@ -350,7 +408,13 @@ def attention_heads(handle, Q, K, V, heads, scale=None, backward="per_head"):
     passes over the pattern per group of heads, the head loop inside the kernels, so the pattern, the chunking and the launches are paid per
     group and not per head.  The group is all heads when 2 * heads * nnz values fit an eighth of the device's memory (option
     "attention_backward_heads" sets another bound); the handle then holds that many values instead of 2 * nnz.  The gradients have the
-    bits of the default mode."""
+    bits of the default mode.
+
+    bias: None, or a tensor of (nnz,) -- one plane shared by all heads -- or (heads, nnz), in CSR order, added to the scaled scores before the
+    softmax (Handle.attention_bias; t = (s * scale) + bias, two roundings).  It receives a gradient: dL/dbias[h, p] = P (dP - D) of head h
+    (Handle.attention_bias_backward, in the same call as dQ, dK, dV; per head in the default mode, on plane h); a shared plane's gradient is the
+    sum of the heads' planes -- torch's sum, whose order is not part of the contract.  A -inf entry masks that entry for that head.  The forward
+    pass saves Q, K, V and a reference to the bias; a bias that needs no gradient gets none computed."""
     if backward not in ("per_head", "fused"):
         raise ValueError(f"backward must be 'per_head' or 'fused', not {backward!r}")
     _check_handle(handle)
@@ -362,11 +426,12 @@ def attention_heads(handle, Q, K, V, heads, scale=None, backward="per_head"):
         raise ValueError(f"Q must be ({handle.m}, heads * k), K ({handle.n}, heads * k) and V ({handle.n}, heads * dv) with k, dv >= 1, not {tuple(Q.shape)}, {tuple(K.shape)} and {tuple(V.shape)}")
     if heads < 1 or Q.shape[1] % heads or V.shape[1] % heads:
         raise ValueError(f"{Q.shape[1]} columns of Q / K and {V.shape[1]} of V are not {heads} heads of equal width")
+    _check_bias(bias, handle, heads)
     scale = 1.0 / math.sqrt(Q.shape[1] // heads) if scale is None else float(scale)   # Handle.attention_heads' default, to the bit
-    return _AttentionHeads.apply(handle, Q, K, V, heads, scale, backward == "fused")
+    return _AttentionHeads.apply(handle, Q, K, V, heads, scale, backward == "fused", bias)
 
 
-def attention(handle, Q, K, V, scale=None, backward="composed"):
+def attention(handle, Q, K, V, scale=None, backward="composed", *, bias=None):
     """O = softmax_rows(scale * Q K^T on the handle's pattern) V (Handle.attention: one fused pass, the bits of
     matmul(h, V, values=row_softmax(h, sddmm(h, Q, K) * scale))), with gradients for Q, K and V.  Q: (m, k), K: (n, k), V: (n, dv), of the
     handle's dtype on its device; scale: a Python number, None means 1 / sqrt(k); it receives no gradient.
@@ -381,7 +446,12 @@ def attention(handle, Q, K, V, scale=None, backward="composed"):
     backward="fused" computes the same gradients with ONE Handle.attention_backward call (spmv_hip_attention_backward: two passes over A, P
     and dS in handle-owned arrays): no Handle.update_values, the handle multiplies the same matrix throughout.  The gradients have the
     composition's bits whenever k > 1 and dv > 1 (at width 1 a contiguous tensor sends the composition's products down the spmv schedule,
-    whose summation order is the method's own)."""
+    whose summation order is the method's own).
+
+    bias: None, or a tensor of (nnz,) or (1, nnz) in CSR order, added to the scaled scores before the softmax (Handle.attention_bias with one
+    head), which receives a gradient.  "composed" adds it in torch between * scale and row_softmax and takes dL/dbias from
+    row_softmax_backward before * scale; "fused" takes it from the one Handle.attention_bias_backward call.  The same bits both ways for
+    k, dv > 1."""
     if backward not in ("composed", "fused"):
         raise ValueError(f"backward must be 'composed' or 'fused', not {backward!r}")
     _check_handle(handle)
@@ -390,5 +460,6 @@ def attention(handle, Q, K, V, scale=None, backward="composed"):
     if Q.dim() != 2 or K.dim() != 2 or V.dim() != 2 or Q.shape[0] != handle.m or K.shape[0] != handle.n or V.shape[0] != handle.n or \
             Q.shape[1] != K.shape[1] or Q.shape[1] < 1 or V.shape[1] < 1:
         raise ValueError(f"Q must be ({handle.m}, k), K ({handle.n}, k) and V ({handle.n}, dv) with k, dv >= 1, not {tuple(Q.shape)}, {tuple(K.shape)} and {tuple(V.shape)}")
+    _check_bias(bias, handle, 1)
     scale = 1.0 / math.sqrt(Q.shape[1]) if scale is None else float(scale)   # Handle.attention's default, to the bit
-    return (_AttentionFused if backward == "fused" else _Attention).apply(handle, Q, K, V, scale)
+    return (_AttentionFused if backward == "fused" else _Attention).apply(handle, Q, K, V, scale, bias)

@@ -22,6 +22,13 @@
 // written once, then long_row_softmax in place --, then long_row_panel per panel of dv.  The parked row is a few KiB per workgroup: L2
 // traffic.
 //
+// Bias (spmv_hip_attention_bias; the BIAS instantiations): t_p = (s_p * scale) + B[hd * ldb + p], a plain multiplication and then a plain addition,
+// B in planes of CSR order -- ldb = 0: one plane for every head.  The product always goes through LDS before the addition (att_add_bias reads it
+// back): the build's -ffp-contract=fast lets the backend fuse a multiplication and an addition that meet in registers whatever the pragma
+// says, and the contract is the two roundings.  Short rows: lane l loads the bias of entry l beside its column (coalesced, streaming) before
+// the dots and, after the tile's scores are in LDS, adds it to its own entry's; long rows: added where the score is parked.  Everything after
+// t_p is unchanged.  The instantiations without BIAS are the code from before the bias existed.
+//
 // Arithmetic and order: the composition's, because its blocks are the composition's (kernels/row_blocks.hpp) -- s_p is sddmm's dot for this
 // k (kernels/sddmm.hpp), t_p = s_p * scale one plain multiplication, M_i / Z_i / P_p = exp(t_p - M_i) / Z_i the row softmax's by row length,
 // O[i, c] spmm's chain.  The result is a function of the matrix, k, dv and the value type alone.  Contraction is pinned off: the fmas written
@@ -46,6 +53,8 @@ struct AttentionArgs {
     long long ldq = 0, ldk = 0, ldv = 0, ldo = 0;
     double scale = 1.0;
     bool vec = false; // q, kk, v, o, their leading dimensions and every head's first column allow 16-byte accesses
+    const void *bias = nullptr; // nullptr: no bias; else planes of nnz elements in CSR order, head hd's at bias + hd * ldb (ldb = 0: one plane shared)
+    long long ldb = 0;
 };
 
 // spmv_attention.hip: the launches of one call on `stream`
@@ -73,6 +82,14 @@ __device__ __forceinline__ T att_scale(T s, T scale)
     return s * scale;
 }
 
+// t_p with a bias, from the scaled score READ BACK FROM LDS (see the header): the composition's second rounding, never an fma
+template <typename T>
+__device__ __forceinline__ T att_add_bias(T t, T b)
+{
+#pragma clang fp contract(off)
+    return t + b;
+}
+
 // The scaled scores of one tile of 64 entries.  Lane l passes its entry's row i (-1: no entry) and column j; the tile's entries are multiplied
 // in CW rounds of 64 / CW, CW adjacent lanes per entry (sddmm_kernel's rounds, the same chain and the same tree), and t of entry e lands in
 // slot[e] (the wave's own LDS; the caller synchronizes).  Every lane of the wave must call.
@@ -95,11 +112,13 @@ __device__ __forceinline__ void att_tile_scores(int i, int j, int lane, int k, c
 
 // One wave per batch [split[b], split[b + 1]) of whole rows; rows longer than kSpmmLongThr are left to attention_long_kernel.
 // CW: sddmm's lane group for k; 1 << lgv: spmm's lane group for min(dv, KP) columns.  heads: the chunk's columns stay in s_col while the
-// three phases run once per head over s_p, head hd on the columns from hd * k of Q and K and from hd * dv of V and O.
-template <typename T, int CW, bool VEC>
+// three phases run once per head over s_p, head hd on the columns from hd * k of Q and K and from hd * dv of V and O.  BIAS: head hd adds
+// bias[hd * ldb + p] to the scaled score of entry p (bias is not nullptr).
+template <typename T, int CW, bool VEC, bool BIAS>
 __global__ __launch_bounds__(kBlock) void attention_rows_kernel(int nb, const int *__restrict__ split, const int *__restrict__ rowptr, const int *__restrict__ colidx, int heads,
                                                                 int k, int dv, int lgv, T scale, const T *__restrict__ q, long long ldq, const T *__restrict__ kk, long long ldk,
-                                                                const T *__restrict__ v, long long ldv, T *__restrict__ o, long long ldo)
+                                                                const T *__restrict__ v, long long ldv, T *__restrict__ o, long long ldo, const T *__restrict__ bias,
+                                                                long long ldb)
 {
 #pragma clang fp contract(off)
     constexpr int V = SpmmShape<T>::V, CH = kSpmmChunk;
@@ -133,7 +152,12 @@ __global__ __launch_bounds__(kBlock) void attention_rows_kernel(int nb, const in
                         s_col[w][e] = j;
                     } else j = s_col[w][e]; // written by this lane
                 }
-                att_tile_scores<T, CW, VEC>(i, j, lane, k, qh, ldq, kh, ldk, scale, s_p[w] + t0);
+                if constexpr (BIAS) {
+                    const T be = e < nq ? ld_stream(bias + (long long) hd * ldb + base + e) : T(0); // in flight during the dots
+                    att_tile_scores<T, CW, VEC>(i, j, lane, k, qh, ldq, kh, ldk, scale, s_p[w] + t0);
+                    wave_lds_sync();
+                    if (e < nq) s_p[w][e] = att_add_bias(s_p[w][e], be); // lane l: its own entry, written by another lane
+                } else att_tile_scores<T, CW, VEC>(i, j, lane, k, qh, ldq, kh, ldk, scale, s_p[w] + t0);
             }
             wave_lds_sync();
 
@@ -174,12 +198,13 @@ __global__ __launch_bounds__(kBlock) void attention_rows_kernel(int nb, const in
 }
 
 // one workgroup per long row (len > kSpmmLongThr >= 256: every thread has a first term); park + long_off[i]: len elements of its own, used by
-// one head after the other (the barrier that ends a head's last panel is also the one before the next head parks its scores)
-template <typename T, int CW, bool VEC>
+// one head after the other (the barrier that ends a head's last panel is also the one before the next head parks its scores).  BIAS: the
+// bias is added where the score is parked.
+template <typename T, int CW, bool VEC, bool BIAS>
 __global__ __launch_bounds__(kBlock) void attention_long_kernel(int nlong, const int *__restrict__ longs, const int *__restrict__ long_off, const int *__restrict__ rowptr,
                                                                 const int *__restrict__ colidx, int heads, int k, int dv, int lgv, T scale, const T *__restrict__ q, long long ldq,
                                                                 const T *__restrict__ kk, long long ldk, const T *__restrict__ v, long long ldv, T *__restrict__ o, long long ldo,
-                                                                T *park)
+                                                                T *park, const T *__restrict__ bias, long long ldb)
 {
 #pragma clang fp contract(off)
     constexpr int V = SpmmShape<T>::V, KP = SpmmShape<T>::KP;
@@ -203,7 +228,11 @@ __global__ __launch_bounds__(kBlock) void attention_long_kernel(int nlong, const
                 const int j = valid ? col[p] : 0;
                 att_tile_scores<T, CW, VEC>(valid ? r : -1, j, lane, k, qh, ldq, kh, ldk, scale, s_slot[w]);
                 wave_lds_sync();
-                if (valid) t[p] = s_slot[w][lane];
+                if constexpr (BIAS) {
+                    if (valid) t[p] = att_add_bias(s_slot[w][lane], bias[(long long) hd * ldb + s + p]);
+                } else {
+                    if (valid) t[p] = s_slot[w][lane];
+                }
                 wave_lds_sync();
             }
             __syncthreads();

@@ -31,6 +31,12 @@
 // offset pointers, so head hd has the bits of the single-head call on its slices.  spmv_hip_attention_backward is heads = 1.  The launch
 // side offsets the pointers to a round's first head (kernels see heads = the round's count and planes from 0).
 //
+// Bias and its gradient (spmv_hip_attention_bias_backward; the BIAS instantiations of the two row kernels): t_p = (s_p * scale) + B_p exactly
+// as in the forward pass (kernels/attention.hpp), and dB_p = P_p (dP_p - D_i) -- the value dS_p is made from by one more multiplication --
+// stored from its register by the lane / thread that owns the entry, straight into the caller's plane of the head (db + hd * lddb, CSR
+// order).  Either of bias and db may be nullptr in a BIAS instantiation (wave-uniform tests); the column pass knows neither.  The
+// instantiations without BIAS are the code from before the bias existed.
+//
 // Arithmetic and order: the composition's, because its blocks are the composition's (kernels/row_blocks.hpp) -- t and P are
 // spmv_hip_attention's; dP is sddmm's dot for dv; D is row_softmax_backward's by row length; dS is one subtraction and two plain
 // multiplications; dQ, dK and dV are spmm's chains.  Contraction is pinned off: the fmas written out are the only fused operations.
@@ -57,6 +63,9 @@ struct AttentionBwdArgs {
     long long ldq = 0, ldk = 0, ldv = 0, ldg = 0, lddq = 0, lddk = 0, lddv = 0;
     double scale = 1.0;
     bool vec = false; // every operand, leading dimension and head's first column allows 16-byte accesses
+    const void *bias = nullptr; // nullptr: no bias; else head hd's plane at bias + hd * ldb (ldb = 0: one plane shared), CSR order
+    void *db = nullptr;         // nullptr: not wanted; else head hd's plane of dL/dB at db + hd * lddb
+    long long ldb = 0, lddb = 0;
 };
 
 // spmv_attention_backward.hip: the launches of one call on `stream`, ceil(heads / hg) rounds of a row pass and a column pass
@@ -74,12 +83,14 @@ __device__ __forceinline__ void attb_tile_dots(int cw, int i, int j, int lane, i
 // CW: sddmm's lane group for k; cwd: the same for dv; 1 << lgk: spmm's lane group for min(k, KP) columns.
 // p_out / ds_out / dq: nullptr when dV / dK / dQ is not wanted.  heads: the chunk's columns stay in s_col while the four phases run once per
 // head over s_p / s_d, head hd on the columns from hd * k (Q, K, dQ) and hd * dv (V, G) and on plane hd of p_out / ds_out.
-template <typename T, int CW, bool VEC>
+// BIAS: bias (added to the scaled scores) and db (P (dP - D), before the scaling) as in the header; either may be nullptr.
+template <typename T, int CW, bool VEC, bool BIAS>
 __global__ __launch_bounds__(kBlock) void attention_bwd_rows_kernel(int nb, const int *__restrict__ split, const int *__restrict__ rowptr, const int *__restrict__ colidx,
                                                                     int heads, long long plane, int k, int dv, int cwd, int lgk, T scale,
                                                                     const T *__restrict__ q, long long ldq, const T *__restrict__ kk, long long ldk,
                                                                     const T *__restrict__ v, long long ldv, const T *__restrict__ g, long long ldg, T *__restrict__ dq,
-                                                                    long long lddq, T *__restrict__ p_out, T *__restrict__ ds_out)
+                                                                    long long lddq, T *__restrict__ p_out, T *__restrict__ ds_out, const T *__restrict__ bias,
+                                                                    long long ldb, T *__restrict__ db, long long lddb)
 {
 #pragma clang fp contract(off)
     constexpr int V = SpmmShape<T>::V, CH = kSpmmChunk;
@@ -113,7 +124,17 @@ __global__ __launch_bounds__(kBlock) void attention_bwd_rows_kernel(int nb, cons
                         s_col[w][e] = j;
                     } else j = s_col[w][e]; // written by this lane
                 }
+                [[maybe_unused]] T be = T(0);
+                if constexpr (BIAS) {
+                    if (bias && e < nq) be = ld_stream(bias + (long long) hd * ldb + base + e); // in flight during the dots
+                }
                 att_tile_scores<T, CW, VEC>(i, j, lane, k, qh, ldq, kh, ldk, scale, s_p[w] + t0);
+                if constexpr (BIAS) {
+                    if (bias) { // wave-uniform
+                        wave_lds_sync();
+                        if (e < nq) s_p[w][e] = att_add_bias(s_p[w][e], be); // the product comes back from LDS: never an fma (kernels/attention.hpp)
+                    }
+                }
                 attb_tile_dots<T, VEC>(cwd, i, j, lane, dv, gh, ldg, vh, ldv, s_d[w] + t0);
             }
             wave_lds_sync();
@@ -162,17 +183,37 @@ __global__ __launch_bounds__(kBlock) void attention_bwd_rows_kernel(int nb, cons
                 }
                 const T Z = row_group_reduce<false>(acc, cw);
                 const T D = row_dot_regs<T, true>(x, y, t, len, cw, wide, Z); // x becomes P
-                if (t < len) {
-                    row[t] = x[0];
-                    drow[t] = att_scale(x[0] * (y[0] - D), scale);
-                }
-                if (wide) {
+                if constexpr (BIAS) {
+                    T *dbr = db ? db + (long long) hd * lddb + base + s : nullptr; // the row's range of the head's plane
+                    if (t < len) {
+                        const T d0 = x[0] * (y[0] - D);
+                        if (dbr) dbr[t] = d0;
+                        row[t] = x[0];
+                        drow[t] = att_scale(d0, scale);
+                    }
+                    if (wide) {
 #pragma unroll
-                    for (int u = 1; u < kRowChain; ++u)
-                        if (t + u * kWave < len) {
-                            row[t + u * kWave] = x[u];
-                            drow[t + u * kWave] = att_scale(x[u] * (y[u] - D), scale);
-                        }
+                        for (int u = 1; u < kRowChain; ++u)
+                            if (t + u * kWave < len) {
+                                const T du = x[u] * (y[u] - D);
+                                if (dbr) dbr[t + u * kWave] = du;
+                                row[t + u * kWave] = x[u];
+                                drow[t + u * kWave] = att_scale(du, scale);
+                            }
+                    }
+                } else {
+                    if (t < len) {
+                        row[t] = x[0];
+                        drow[t] = att_scale(x[0] * (y[0] - D), scale);
+                    }
+                    if (wide) {
+#pragma unroll
+                        for (int u = 1; u < kRowChain; ++u)
+                            if (t + u * kWave < len) {
+                                row[t + u * kWave] = x[u];
+                                drow[t + u * kWave] = att_scale(x[u] * (y[u] - D), scale);
+                            }
+                    }
                 }
                 h0 += kWave >> lg;
             }
@@ -193,13 +234,14 @@ __global__ __launch_bounds__(kBlock) void attention_bwd_rows_kernel(int nb, cons
 }
 
 // one workgroup per long row (len > kSpmmLongThr >= 256: every thread has a first term); the row's ranges of every plane of pa (attb_p) and
-// da (attb_ds) are its own: no other workgroup of this launch touches them.  Head hd parks in plane hd's range.
-template <typename T, int CW, bool VEC>
+// da (attb_ds) are its own: no other workgroup of this launch touches them.  Head hd parks in plane hd's range.  BIAS: as in the rows kernel.
+template <typename T, int CW, bool VEC, bool BIAS>
 __global__ __launch_bounds__(kBlock) void attention_bwd_long_kernel(int nlong, const int *__restrict__ longs, const int *__restrict__ rowptr, const int *__restrict__ colidx,
                                                                     int heads, long long plane, int k, int dv, int cwd, int lgk, T scale,
                                                                     const T *__restrict__ q, long long ldq, const T *__restrict__ kk, long long ldk,
                                                                     const T *__restrict__ v, long long ldv, const T *__restrict__ g, long long ldg, T *__restrict__ dq,
-                                                                    long long lddq, T *pa, T *da)
+                                                                    long long lddq, T *pa, T *da, const T *__restrict__ bias, long long ldb, T *__restrict__ db,
+                                                                    long long lddb)
 {
 #pragma clang fp contract(off)
     constexpr int V = SpmmShape<T>::V, KP = SpmmShape<T>::KP;
@@ -224,7 +266,8 @@ __global__ __launch_bounds__(kBlock) void attention_bwd_long_kernel(int nlong, c
                 attb_tile_dots<T, VEC>(cwd, valid ? r : -1, j, lane, dv, gh, ldg, vh, ldv, s_slot2[w]);
                 wave_lds_sync();
                 if (valid) {
-                    t[p] = s_slot[w][lane];
+                    if constexpr (BIAS) t[p] = bias ? att_add_bias(s_slot[w][lane], bias[(long long) hd * ldb + s + p]) : s_slot[w][lane];
+                    else t[p] = s_slot[w][lane];
                     d[p] = s_slot2[w][lane];
                 }
                 wave_lds_sync();
@@ -234,7 +277,16 @@ __global__ __launch_bounds__(kBlock) void attention_bwd_long_kernel(int nlong, c
             long_row_softmax(t, t, 0, len, tid, s_max, s_sum);
             // 3. D over P and the parked dP, dS written in place
             const T D = long_row_dot(t, d, 0, len, tid, s_sum);
-            for (int p = tid; p < len; p += kBlock) d[p] = att_scale(t[p] * (d[p] - D), scale);
+            if constexpr (BIAS) {
+                T *dbr = db ? db + (long long) hd * lddb + s : nullptr; // the row's range of the head's plane
+                for (int p = tid; p < len; p += kBlock) {
+                    const T dp = t[p] * (d[p] - D);
+                    if (dbr) dbr[p] = dp;
+                    d[p] = att_scale(dp, scale);
+                }
+            } else {
+                for (int p = tid; p < len; p += kBlock) d[p] = att_scale(t[p] * (d[p] - D), scale);
+            }
             __syncthreads();
             // 4. dQ = A_dS K, panel by panel; a panel's last barrier also lets the next panel / head / row write part, s_max, s_sum again
             if (dq)

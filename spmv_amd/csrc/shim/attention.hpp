@@ -1,5 +1,6 @@
 // shim/attention.hpp -- part of spmv_shim.hip: O = softmax_rows(scale * Q K^T on the RESIDENT pattern) V in one pass, for one head
-// (spmv_hip_attention) or for `heads` heads stored side by side in the rows of Q, K, V and O (spmv_hip_attention_heads).  The
+// (spmv_hip_attention) or for `heads` heads stored side by side in the rows of Q, K, V and O (spmv_hip_attention_heads), with an additive
+// bias per head and entry (spmv_hip_attention_bias: the one entry point the others call with no bias).  The
 // kernels are kernels/attention.hpp, launched from their own translation unit (spmv_attention.hip, attention_launch); the tables are spmm's
 // batch table and long-row list (spmm_plan).  This side adds what the long rows need: where each one parks its scores.
 #pragma once
@@ -44,15 +45,30 @@ static int attention_plan(spmv_dev *d)
     return SPMV_HIP_OK;
 }
 
-// k and dv are one head's widths: Q and K are heads * k columns wide, V and O heads * dv
-extern "C" int spmv_shim_attention_heads(spmv_dev *d, int heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v,
-                                         long long ldv, void *o, long long ldo)
+// A host bias: `planes` planes of nnz elements, ld apart, packed into the handle's buffer `b` (Stager::in with a plane as a row); a shared plane
+// (ld = 0) is one row and stays shared.  nnz > 0.
+static int attention_stage_bias(Stager &stg, StageBuf &b, const void *&bias, long long &ldb, int heads)
+{
+    const bool shared = ldb == 0;
+    long long ld = shared ? stg.d->nnz : ldb;
+    const int rc = stg.in(b, bias, ld, shared ? (size_t) 1 : (size_t) heads, (int) stg.d->nnz);
+    if (!shared) ldb = ld;
+    return rc;
+}
+
+// k and dv are one head's widths: Q and K are heads * k columns wide, V and O heads * dv.  bias: NULL, or the planes of spmv_hip_attention_bias
+// (ldb = 0: one plane for all heads; else >= nnz); with NULL, ldb is ignored and the call is spmv_shim_attention_heads.
+extern "C" int spmv_shim_attention_bias(spmv_dev *d, int heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v,
+                                        long long ldv, const void *bias, long long ldb, void *o, long long ldo)
 {
     if (!d || !d->built) return fail(SPMV_HIP_E_NOSTATE, "attention: schedule not built");
     const long long wk = (long long) heads * k, wv = (long long) heads * dv;
     if (heads < 1 || k < 1 || dv < 1 || wk > INT_MAX || wv > INT_MAX || ldq < wk || ldk < wk || ldv < wv || ldo < wv)
         return fail(SPMV_HIP_E_ARG, "attention: need heads, k, dv >= 1, heads * k and heads * dv within int, ldq, ldk >= heads * k, ldv, ldo >= heads * dv (heads = %d, k = %d, dv = %d, ld = %lld, %lld, %lld, %lld)",
                     heads, k, dv, ldq, ldk, ldv, ldo);
+    if (bias && (ldb < 0 || (ldb > 0 && ldb < d->nnz)))
+        return fail(SPMV_HIP_E_ARG, "attention: the bias planes need ldb = 0 (one plane for all heads) or ldb >= nnz (ldb = %lld, nnz = %lld)", ldb, d->nnz);
+    if (d->nnz == 0) bias = nullptr; // no entry: no bias is read
     if (d->m > 0 && (!q || !kk || !v || !o)) return fail(SPMV_HIP_E_ARG, "attention: Q, K, V or O is NULL");
     if (d->nnz > 0 && !d->colidx) return fail(SPMV_HIP_E_NOSTATE, "attention: the resident column indices were released (spmv_shim_restore_columns first)");
     if (d->m == 0) return SPMV_HIP_OK;
@@ -81,9 +97,11 @@ extern "C" int spmv_shim_attention_heads(spmv_dev *d, int heads, int k, int dv, 
     a.kk = kk; a.ldk = ldk;
     a.v = v; a.ldv = ldv;
     a.o = o; a.ldo = ldo;
+    a.bias = bias; a.ldb = bias ? ldb : 0;
     // every row of O gets its heads * dv elements, empty rows their zeros: a staged result is written completely before it is copied back
     if ((rc = stg.in(d->stage[STAGE_ATT_Q], a.q, a.ldq, (size_t) d->m, (int) wk)) || (rc = stg.in(d->stage[STAGE_ATT_K], a.kk, a.ldk, (size_t) d->n, (int) wk)) ||
-        (rc = stg.in(d->stage[STAGE_ATT_V], a.v, a.ldv, (size_t) d->n, (int) wv)) || (rc = stg.out(d->stage[STAGE_ATT_O], a.o, a.ldo, (size_t) d->m, (int) wv))) return rc;
+        (rc = stg.in(d->stage[STAGE_ATT_V], a.v, a.ldv, (size_t) d->n, (int) wv)) || (rc = stg.out(d->stage[STAGE_ATT_O], a.o, a.ldo, (size_t) d->m, (int) wv)) ||
+        (a.bias && (rc = attention_stage_bias(stg, d->stage[STAGE_ATT_B], a.bias, a.ldb, heads)))) return rc;
     // the access width changes no bit (kernels/attention.hpp): chosen per call from what the addresses allow -- with more than one head, every
     // head's first column has to be 16-byte aligned as well
     a.vec = wide_ok(a.q, a.ldq, s) && wide_ok(a.kk, a.ldk, s) && wide_ok(a.v, a.ldv, s) && wide_ok(a.o, a.ldo, s) &&
@@ -93,18 +111,33 @@ extern "C" int spmv_shim_attention_heads(spmv_dev *d, int heads, int k, int dv, 
     return stg.finish();
 }
 
+extern "C" int spmv_shim_attention_heads(spmv_dev *d, int heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v,
+                                         long long ldv, void *o, long long ldo)
+{
+    return spmv_shim_attention_bias(d, heads, k, dv, scale, q, ldq, kk, ldk, v, ldv, nullptr, 0, o, ldo);
+}
+
 extern "C" int spmv_shim_attention(spmv_dev *d, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v, long long ldv, void *o,
                                    long long ldo)
 {
     return spmv_shim_attention_heads(d, 1, k, dv, scale, q, ldq, kk, ldk, v, ldv, o, ldo);
 }
 
+extern "C" double spmv_shim_time_attention_bias(spmv_dev *d, int heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v,
+                                                long long ldv, const void *bias, long long ldb, void *o, long long ldo, int warmup, int iters, float *ms_out)
+{
+    if (!d || !d->built || iters <= 0) { fail(SPMV_HIP_E_ARG, "time_attention: bad arguments"); return -1.0; }
+    if (!is_device_ptr(q) || !is_device_ptr(kk) || !is_device_ptr(v) || !is_device_ptr(o) || (bias && !is_device_ptr(bias))) {
+        fail(SPMV_HIP_E_ARG, "time_attention: Q, K, V, O and the bias must be device pointers");
+        return -1.0;
+    }
+    return time_events(d, "time_attention", warmup, iters, ms_out, [&] { return spmv_shim_attention_bias(d, heads, k, dv, scale, q, ldq, kk, ldk, v, ldv, bias, ldb, o, ldo); });
+}
+
 extern "C" double spmv_shim_time_attention_heads(spmv_dev *d, int heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v,
                                                  long long ldv, void *o, long long ldo, int warmup, int iters, float *ms_out)
 {
-    if (!d || !d->built || iters <= 0) { fail(SPMV_HIP_E_ARG, "time_attention: bad arguments"); return -1.0; }
-    if (!is_device_ptr(q) || !is_device_ptr(kk) || !is_device_ptr(v) || !is_device_ptr(o)) { fail(SPMV_HIP_E_ARG, "time_attention: Q, K, V and O must be device pointers"); return -1.0; }
-    return time_events(d, "time_attention", warmup, iters, ms_out, [&] { return spmv_shim_attention_heads(d, heads, k, dv, scale, q, ldq, kk, ldk, v, ldv, o, ldo); });
+    return spmv_shim_time_attention_bias(d, heads, k, dv, scale, q, ldq, kk, ldk, v, ldv, nullptr, 0, o, ldo, warmup, iters, ms_out);
 }
 
 extern "C" double spmv_shim_time_attention(spmv_dev *d, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v, long long ldv,

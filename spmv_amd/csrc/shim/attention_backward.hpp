@@ -48,10 +48,13 @@ static int attention_backward_group(const spmv_dev *d, int heads, int limit)
 
 // k and dv are one head's widths: Q, K, dq, dk are heads * k columns wide, V, G, dvo heads * dv.  dq / dk / dvo: NULL = not wanted.  When dk or
 // dvo is wanted the transpose must be attached with its column indices resident (spmv_shim_transpose, spmv_shim_transpose_restore_columns);
-// its values are not read.  max_heads: option "attention_backward_heads" (0 = by the memory rule).
-extern "C" int spmv_shim_attention_heads_backward(spmv_dev *d, int heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
-                                                  const void *v, long long ldv, const void *g, long long ldg, void *dq, long long lddq, void *dk, long long lddk, void *dvo,
-                                                  long long lddv)
+// its values are not read.  max_heads: option "attention_backward_heads" (0 = by the memory rule).  bias: NULL or the forward call's planes
+// (ldb = 0: one plane for all heads; else >= nnz); db: NULL = not wanted, else `heads` planes lddb >= nnz apart, written by the row pass alone --
+// with only db wanted the column pass does not run and the transpose is not looked at.  With bias and db NULL this is
+// spmv_shim_attention_heads_backward.
+extern "C" int spmv_shim_attention_bias_backward(spmv_dev *d, int heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
+                                                 const void *v, long long ldv, const void *bias, long long ldb, const void *g, long long ldg, void *dq, long long lddq, void *dk,
+                                                 long long lddk, void *dvo, long long lddv, void *db, long long lddb)
 {
     if (!d || !d->built) return fail(SPMV_HIP_E_NOSTATE, "attention_backward: schedule not built");
     const long long wk = (long long) heads * k, wv = (long long) heads * dv;
@@ -60,12 +63,16 @@ extern "C" int spmv_shim_attention_heads_backward(spmv_dev *d, int heads, int ma
         return fail(SPMV_HIP_E_ARG, "attention_backward: need heads, k, dv >= 1, heads * k and heads * dv within int, ldq, ldk >= heads * k, ldv, ldg >= heads * dv, lddq, lddk >= heads * k, lddv >= heads * dv (heads = %d, k = %d, dv = %d)",
                     heads, k, dv);
     if (d->m > 0 && (!q || !kk || !v || !g)) return fail(SPMV_HIP_E_ARG, "attention_backward: Q, K, V or G is NULL");
-    if (!dq && !dk && !dvo) return SPMV_HIP_OK;
+    if ((bias && (ldb < 0 || (ldb > 0 && ldb < d->nnz))) || (db && lddb < d->nnz))
+        return fail(SPMV_HIP_E_ARG, "attention_backward: the bias planes need ldb = 0 (one plane for all heads) or ldb >= nnz, those of dB lddb >= nnz (ldb = %lld, lddb = %lld, nnz = %lld)",
+                    ldb, lddb, d->nnz);
+    if (!dq && !dk && !dvo && !db) return SPMV_HIP_OK;
+    if (d->nnz == 0) { bias = nullptr; db = nullptr; } // no entry: no bias is read, dB has no element
     if (d->nnz > 0 && !d->colidx) return fail(SPMV_HIP_E_NOSTATE, "attention_backward: the resident column indices were released (spmv_shim_restore_columns first)");
     const bool cols = (dk || dvo) && d->n > 0;
     spmv_dev *t = d->tr;
     if (cols && (!t || !d->tr_perm || (t->nnz > 0 && !t->colidx))) return fail(SPMV_HIP_E_NOSTATE, "attention_backward: the transpose is not attached with its column indices");
-    if (d->m == 0 && !cols) return SPMV_HIP_OK;
+    if ((d->m == 0 || (!dq && !db)) && !cols) return SPMV_HIP_OK;
     DeviceGuard guard(d->device);
     if (!guard.ok) return fail(SPMV_HIP_E_RUNTIME, "hipSetDevice(%d) failed", d->device);
     int rc;
@@ -107,11 +114,15 @@ extern "C" int spmv_shim_attention_heads_backward(spmv_dev *d, int heads, int ma
     a.dq = d->m > 0 ? dq : nullptr; a.lddq = lddq;
     a.dk = cols ? dk : nullptr; a.lddk = lddk;
     a.dvo = cols ? dvo : nullptr; a.lddv = lddv;
+    a.bias = bias; a.ldb = bias ? ldb : 0;
+    a.db = db; a.lddb = lddb;
     // every row of a wanted output gets its elements, empty rows and columns their zeros: a staged result is written completely before it is copied back
     if ((rc = stg.in(d->stage[STAGE_ATTB_Q], a.q, a.ldq, (size_t) d->m, (int) wk)) || (rc = stg.in(d->stage[STAGE_ATTB_K], a.kk, a.ldk, (size_t) d->n, (int) wk)) ||
         (rc = stg.in(d->stage[STAGE_ATTB_V], a.v, a.ldv, (size_t) d->n, (int) wv)) || (rc = stg.in(d->stage[STAGE_ATTB_G], a.g, a.ldg, (size_t) d->m, (int) wv)) ||
         (a.dq && (rc = stg.out(d->stage[STAGE_ATTB_DQ], a.dq, a.lddq, (size_t) d->m, (int) wk))) || (a.dk && (rc = stg.out(d->stage[STAGE_ATTB_DK], a.dk, a.lddk, (size_t) d->n, (int) wk))) ||
-        (a.dvo && (rc = stg.out(d->stage[STAGE_ATTB_DV], a.dvo, a.lddv, (size_t) d->n, (int) wv)))) return rc;
+        (a.dvo && (rc = stg.out(d->stage[STAGE_ATTB_DV], a.dvo, a.lddv, (size_t) d->n, (int) wv))) ||
+        (a.bias && (rc = attention_stage_bias(stg, d->stage[STAGE_ATT_B], a.bias, a.ldb, heads))) ||
+        (a.db && (rc = stg.out(d->stage[STAGE_ATT_DB], a.db, a.lddb, (size_t) heads, (int) d->nnz)))) return rc; // every entry of every plane is written
     // the access width changes no bit (kernels/attention_backward.hpp): chosen per call from what the addresses allow -- with more than one head,
     // every head's first column has to be 16-byte aligned as well
     a.vec = wide_ok(a.q, a.ldq, s) && wide_ok(a.kk, a.ldk, s) && wide_ok(a.v, a.ldv, s) && wide_ok(a.g, a.ldg, s) && (!a.dq || wide_ok(a.dq, a.lddq, s)) &&
@@ -121,24 +132,41 @@ extern "C" int spmv_shim_attention_heads_backward(spmv_dev *d, int heads, int ma
     return stg.finish();
 }
 
+extern "C" int spmv_shim_attention_heads_backward(spmv_dev *d, int heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
+                                                  const void *v, long long ldv, const void *g, long long ldg, void *dq, long long lddq, void *dk, long long lddk, void *dvo,
+                                                  long long lddv)
+{
+    return spmv_shim_attention_bias_backward(d, heads, max_heads, k, dv, scale, q, ldq, kk, ldk, v, ldv, nullptr, 0, g, ldg, dq, lddq, dk, lddk, dvo, lddv, nullptr, 0);
+}
+
 extern "C" int spmv_shim_attention_backward(spmv_dev *d, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v,
                                             long long ldv, const void *g, long long ldg, void *dq, long long lddq, void *dk, long long lddk, void *dvo, long long lddv)
 {
     return spmv_shim_attention_heads_backward(d, 1, 0, k, dv, scale, q, ldq, kk, ldk, v, ldv, g, ldg, dq, lddq, dk, lddk, dvo, lddv);
 }
 
+extern "C" double spmv_shim_time_attention_bias_backward(spmv_dev *d, int heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk,
+                                                         long long ldk, const void *v, long long ldv, const void *bias, long long ldb, const void *g, long long ldg, void *dq,
+                                                         long long lddq, void *dk, long long lddk, void *dvo, long long lddv, void *db, long long lddb, int warmup, int iters,
+                                                         float *ms_out)
+{
+    if (!d || !d->built || iters <= 0) { fail(SPMV_HIP_E_ARG, "time_attention_backward: bad arguments"); return -1.0; }
+    if (!is_device_ptr(q) || !is_device_ptr(kk) || !is_device_ptr(v) || !is_device_ptr(g) || (dq && !is_device_ptr(dq)) || (dk && !is_device_ptr(dk)) || (dvo && !is_device_ptr(dvo)) ||
+        (bias && !is_device_ptr(bias)) || (db && !is_device_ptr(db))) {
+        fail(SPMV_HIP_E_ARG, "time_attention_backward: Q, K, V, G, the bias and the outputs must be device pointers");
+        return -1.0;
+    }
+    return time_events(d, "time_attention_backward", warmup, iters, ms_out, [&] {
+        return spmv_shim_attention_bias_backward(d, heads, max_heads, k, dv, scale, q, ldq, kk, ldk, v, ldv, bias, ldb, g, ldg, dq, lddq, dk, lddk, dvo, lddv, db, lddb);
+    });
+}
+
 extern "C" double spmv_shim_time_attention_heads_backward(spmv_dev *d, int heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk,
                                                           long long ldk, const void *v, long long ldv, const void *g, long long ldg, void *dq, long long lddq, void *dk,
                                                           long long lddk, void *dvo, long long lddv, int warmup, int iters, float *ms_out)
 {
-    if (!d || !d->built || iters <= 0) { fail(SPMV_HIP_E_ARG, "time_attention_backward: bad arguments"); return -1.0; }
-    if (!is_device_ptr(q) || !is_device_ptr(kk) || !is_device_ptr(v) || !is_device_ptr(g) || (dq && !is_device_ptr(dq)) || (dk && !is_device_ptr(dk)) || (dvo && !is_device_ptr(dvo))) {
-        fail(SPMV_HIP_E_ARG, "time_attention_backward: Q, K, V, G and the outputs must be device pointers");
-        return -1.0;
-    }
-    return time_events(d, "time_attention_backward", warmup, iters, ms_out, [&] {
-        return spmv_shim_attention_heads_backward(d, heads, max_heads, k, dv, scale, q, ldq, kk, ldk, v, ldv, g, ldg, dq, lddq, dk, lddk, dvo, lddv);
-    });
+    return spmv_shim_time_attention_bias_backward(d, heads, max_heads, k, dv, scale, q, ldq, kk, ldk, v, ldv, nullptr, 0, g, ldg, dq, lddq, dk, lddk, dvo, lddv, nullptr, 0, warmup,
+                                                  iters, ms_out);
 }
 
 extern "C" double spmv_shim_time_attention_backward(spmv_dev *d, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v,

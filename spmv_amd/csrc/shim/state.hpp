@@ -188,7 +188,9 @@ struct BlkSet {
 struct StageBuf { void *p = nullptr; size_t bytes = 0; };
 enum { STAGE_X, STAGE_Y, STAGE_SPMM_X, STAGE_SPMM_Y, STAGE_SDDMM_U, STAGE_SDDMM_V, STAGE_SDDMM_O, STAGE_ROWRED_A, STAGE_ROWRED_G, STAGE_ROWRED_O,
        STAGE_ATT_Q, STAGE_ATT_K, STAGE_ATT_V, STAGE_ATT_O,
-       STAGE_ATTB_Q, STAGE_ATTB_K, STAGE_ATTB_V, STAGE_ATTB_G, STAGE_ATTB_DQ, STAGE_ATTB_DK, STAGE_ATTB_DV, STAGE_COUNT };
+       STAGE_ATTB_Q, STAGE_ATTB_K, STAGE_ATTB_V, STAGE_ATTB_G, STAGE_ATTB_DQ, STAGE_ATTB_DK, STAGE_ATTB_DV,
+       STAGE_ATT_B, STAGE_ATT_DB, // the bias planes of spmv_hip_attention_bias / _bias_backward, and dB's
+       STAGE_COUNT };
 
 struct spmv_dev {
     int device = 0;
@@ -381,9 +383,9 @@ static bool is_device_ptr(const void *p)
 // caller's ld; a host operand goes through its StageBuf -- in(): its k columns packed into HBM on the handle's stream (the padding is not copied);
 // out(): the buffer the kernel writes instead -- and p / ld are redirected there.  finish() copies the host result back and synchronizes, unless
 // the handle is asynchronous and every operand was on the device.  Every operand is asked once whether it is a device pointer.  An operation has
-// at most kMaxRes results (spmv_hip_attention_backward: three).
+// at most kMaxRes results (spmv_hip_attention_bias_backward: four).
 struct Stager {
-    static constexpr int kMaxRes = 3;
+    static constexpr int kMaxRes = 4;
     struct Res { const StageBuf *buf; void *host; size_t ld, rows, k; }; // a staged result and where it goes
     spmv_dev *d;
     bool all_dev = true;

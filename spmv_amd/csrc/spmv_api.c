@@ -1189,3 +1189,61 @@ double spmv_hip_time_attention_heads_backward_launches(spmv_Handle_t h, int head
     return report_time(spmv_shim_time_attention_heads_backward(st->dev, heads, (int) st->opts.v[SPMV_OPT_ATTENTION_BACKWARD_HEADS], k, dv, scale, Q, ldq, K, ldk, V, ldv, G, ldg,
                                                                dQ, lddq, dK, lddk, dV, lddv, warmup, iters, ms_out), where);
 }
+
+/* ---------------------------------------------------------------- the heads calls with an additive bias per head and entry, and its gradient */
+int spmv_hip_attention_bias(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                            const void *Matrix_Val, int heads, int k, int dv, double scale,
+                            const void *Q, long long ldq, const void *K, long long ldk, const void *V, long long ldv,
+                            const void *B, long long ldb, void *O, long long ldo)
+{
+    const char *where = "attention_bias";
+    spmv_hip_state *st;
+    int rc;
+    if ((rc = attention_heads_args(handle, where, heads, k, dv, Q, ldq, K, ldk, V, ldv, O, ldo, m))) return rc;
+    if (B && ldb < 0) return refuse(SPMV_HIP_E_ARG, where, "need ldb >= 0");
+    if ((rc = resident_prologue(handle, where, RESIDENT_NOT_REORDERED, m, RowPtr, ColIdx, Matrix_Val, &st)) || (rc = spmm_columns(handle, st, where))) return rc;
+    return report(spmv_shim_attention_bias(st->dev, heads, k, dv, scale, Q, ldq, K, ldk, V, ldv, B, ldb, O, ldo), where); /* 0 < ldb < nnz: refused there, nothing written */
+}
+
+double spmv_hip_time_attention_bias_launches(spmv_Handle_t h, int heads, int k, int dv, double scale, const void *Q, long long ldq, const void *K, long long ldk,
+                                             const void *V, long long ldv, const void *B, long long ldb, void *O, long long ldo, int warmup, int iters, float *ms_out)
+{
+    const char *where = "time_attention_bias_launches";
+    spmv_hip_state *st;
+    if (attention_heads_args(h, where, heads, k, dv, Q, ldq, K, ldk, V, ldv, O, ldo, 1)) return -1.0;
+    if (B && ldb < 0) { (void) refuse(SPMV_HIP_E_ARG, where, "need ldb >= 0"); return -1.0; }
+    if (resident_state(h, where, RESIDENT_NOT_REORDERED, &st) || spmm_columns(h, st, where)) return -1.0;
+    return report_time(spmv_shim_time_attention_bias(st->dev, heads, k, dv, scale, Q, ldq, K, ldk, V, ldv, B, ldb, O, ldo, warmup, iters, ms_out), where);
+}
+
+int spmv_hip_attention_bias_backward(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                                     const void *Matrix_Val, int heads, int k, int dv, double scale,
+                                     const void *Q, long long ldq, const void *K, long long ldk, const void *V, long long ldv,
+                                     const void *B, long long ldb, const void *G, long long ldg, void *dQ, long long lddq, void *dK, long long lddk,
+                                     void *dV, long long lddv, void *dB, long long lddb)
+{
+    const char *where = "attention_bias_backward";
+    spmv_hip_state *st;
+    int rc;
+    if ((rc = attention_heads_backward_args(handle, where, heads, k, dv, Q, ldq, K, ldk, V, ldv, G, ldg, dQ, lddq, dK, lddk, dV, lddv, m))) return rc;
+    if ((B && ldb < 0) || (dB && lddb < 0)) return refuse(SPMV_HIP_E_ARG, where, "need ldb >= 0 and lddb >= 0");
+    if (!dQ && !dK && !dV && !dB) return SPMV_HIP_OK; /* nothing wanted: no work, the handle's state is not looked at */
+    if ((rc = resident_prologue(handle, where, RESIDENT_NOT_REORDERED, m, RowPtr, ColIdx, Matrix_Val, &st))) return rc;
+    if ((rc = attention_backward_tables(handle, st, where, dK || dV))) return rc; /* only dB (or dQ) wanted: no transpose */
+    return report(spmv_shim_attention_bias_backward(st->dev, heads, (int) st->opts.v[SPMV_OPT_ATTENTION_BACKWARD_HEADS], k, dv, scale, Q, ldq, K, ldk, V, ldv, B, ldb, G, ldg,
+                                                    dQ, lddq, dK, lddk, dV, lddv, dB, lddb), where); /* a plane stride below nnz: refused there, nothing written */
+}
+
+double spmv_hip_time_attention_bias_backward_launches(spmv_Handle_t h, int heads, int k, int dv, double scale, const void *Q, long long ldq, const void *K,
+                                                      long long ldk, const void *V, long long ldv, const void *B, long long ldb, const void *G, long long ldg, void *dQ,
+                                                      long long lddq, void *dK, long long lddk, void *dV, long long lddv, void *dB, long long lddb, int warmup, int iters,
+                                                      float *ms_out)
+{
+    const char *where = "time_attention_bias_backward_launches";
+    spmv_hip_state *st;
+    if (attention_heads_backward_args(h, where, heads, k, dv, Q, ldq, K, ldk, V, ldv, G, ldg, dQ, lddq, dK, lddk, dV, lddv, 1)) return -1.0;
+    if ((B && ldb < 0) || (dB && lddb < 0)) { (void) refuse(SPMV_HIP_E_ARG, where, "need ldb >= 0 and lddb >= 0"); return -1.0; }
+    if (resident_state(h, where, RESIDENT_NOT_REORDERED, &st) || attention_backward_tables(h, st, where, dK || dV)) return -1.0;
+    return report_time(spmv_shim_time_attention_bias_backward(st->dev, heads, (int) st->opts.v[SPMV_OPT_ATTENTION_BACKWARD_HEADS], k, dv, scale, Q, ldq, K, ldk, V, ldv, B, ldb,
+                                                              G, ldg, dQ, lddq, dK, lddk, dV, lddv, dB, lddb, warmup, iters, ms_out), where);
+}

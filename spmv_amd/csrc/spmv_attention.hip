@@ -8,7 +8,7 @@
 
 namespace spmv {
 
-template <typename T, int CW, bool VEC>
+template <typename T, int CW, bool VEC, bool BIAS>
 static void attention_launch_cw(const AttentionArgs &a, hipStream_t stream)
 {
     constexpr int waves = kBlock / kWave;
@@ -16,12 +16,14 @@ static void attention_launch_cw(const AttentionArgs &a, hipStream_t stream)
     const T scale = (T) a.scale;
     const T *q = (const T *) a.q, *kk = (const T *) a.kk, *v = (const T *) a.v;
     T *o = (T *) a.o;
+    const T *bias = (const T *) a.bias;
     if (a.nb > 0)
-        attention_rows_kernel<T, CW, VEC><<<(a.nb + waves - 1) / waves, kBlock, 0, stream>>>(a.nb, a.split, a.rowptr, a.colidx, a.heads, a.k, a.dv, lgv, scale, q, a.ldq, kk, a.ldk, v,
-                                                                                           a.ldv, o, a.ldo);
+        attention_rows_kernel<T, CW, VEC, BIAS><<<(a.nb + waves - 1) / waves, kBlock, 0, stream>>>(a.nb, a.split, a.rowptr, a.colidx, a.heads, a.k, a.dv, lgv, scale, q, a.ldq, kk, a.ldk,
+                                                                                                 v, a.ldv, o, a.ldo, bias, a.ldb);
     if (a.nlong > 0)
-        attention_long_kernel<T, CW, VEC><<<a.nlong < a.cus * 8 ? a.nlong : a.cus * 8, kBlock, 0, stream>>>(a.nlong, a.longs, a.long_off, a.rowptr, a.colidx, a.heads, a.k, a.dv, lgv,
-                                                                                                          scale, q, a.ldq, kk, a.ldk, v, a.ldv, o, a.ldo, (T *) a.park);
+        attention_long_kernel<T, CW, VEC, BIAS><<<a.nlong < a.cus * 8 ? a.nlong : a.cus * 8, kBlock, 0, stream>>>(a.nlong, a.longs, a.long_off, a.rowptr, a.colidx, a.heads, a.k, a.dv,
+                                                                                                                lgv, scale, q, a.ldq, kk, a.ldk, v, a.ldv, o, a.ldo, (T *) a.park, bias,
+                                                                                                                a.ldb);
 }
 
 hipError_t attention_launch(const AttentionArgs &a, bool f64, hipStream_t stream)
@@ -30,7 +32,11 @@ hipError_t attention_launch(const AttentionArgs &a, bool f64, hipStream_t stream
     with_type_vec(f64, a.vec, [&](auto t, auto vec) {
         using T = decltype(t);
         // sddmm's lane group for k: a function of k and the value type alone, it fixes the scores' summation order
-        with_width(panel_group_width<T>(a.k), [&](auto CW) { attention_launch_cw<T, decltype(CW)::value, decltype(vec)::value>(a, stream); });
+        // a bias has instantiations of its own: without one, the kernels are the code without the bias's loads and addition
+        with_width(panel_group_width<T>(a.k), [&](auto CW) {
+            if (a.bias) attention_launch_cw<T, decltype(CW)::value, decltype(vec)::value, true>(a, stream);
+            else attention_launch_cw<T, decltype(CW)::value, decltype(vec)::value, false>(a, stream);
+        });
     });
     return hipGetLastError();
 }

@@ -10,8 +10,8 @@
 
 namespace spmv {
 
-// the row pass over A: P and dS into the handle's arrays, dQ
-template <typename T, int CW, bool VEC>
+// the row pass over A: P and dS into the handle's arrays, dQ; BIAS: the bias read and dB written as well
+template <typename T, int CW, bool VEC, bool BIAS>
 static void attention_bwd_rows_cw(const AttentionBwdArgs &a, hipStream_t stream)
 {
     constexpr int waves = kBlock / kWave;
@@ -20,13 +20,15 @@ static void attention_bwd_rows_cw(const AttentionBwdArgs &a, hipStream_t stream)
     const T scale = (T) a.scale;
     const T *q = (const T *) a.q, *kk = (const T *) a.kk, *v = (const T *) a.v, *g = (const T *) a.g;
     T *dq = (T *) a.dq, *p = (T *) a.p, *ds = (T *) a.ds;
+    const T *bias = (const T *) a.bias;
+    T *db = (T *) a.db;
     if (a.nb > 0)
-        attention_bwd_rows_kernel<T, CW, VEC><<<(a.nb + waves - 1) / waves, kBlock, 0, stream>>>(a.nb, a.split, a.rowptr, a.colidx, a.heads, a.plane, a.k, a.dv, cwd, lgk, scale,
+        attention_bwd_rows_kernel<T, CW, VEC, BIAS><<<(a.nb + waves - 1) / waves, kBlock, 0, stream>>>(a.nb, a.split, a.rowptr, a.colidx, a.heads, a.plane, a.k, a.dv, cwd, lgk, scale,
                                                                                                q, a.ldq, kk, a.ldk, v, a.ldv, g, a.ldg, dq, a.lddq, a.dvo ? p : nullptr,
-                                                                                               a.dk ? ds : nullptr);
+                                                                                               a.dk ? ds : nullptr, bias, a.ldb, db, a.lddb);
     if (a.nlong > 0)
-        attention_bwd_long_kernel<T, CW, VEC><<<a.nlong < a.cus * 8 ? a.nlong : a.cus * 8, kBlock, 0, stream>>>(a.nlong, a.longs, a.rowptr, a.colidx, a.heads, a.plane, a.k, a.dv, cwd, lgk,
-                                                                                                              scale, q, a.ldq, kk, a.ldk, v, a.ldv, g, a.ldg, dq, a.lddq, p, ds);
+        attention_bwd_long_kernel<T, CW, VEC, BIAS><<<a.nlong < a.cus * 8 ? a.nlong : a.cus * 8, kBlock, 0, stream>>>(a.nlong, a.longs, a.rowptr, a.colidx, a.heads, a.plane, a.k, a.dv, cwd, lgk,
+                                                                                                              scale, q, a.ldq, kk, a.ldk, v, a.ldv, g, a.ldg, dq, a.lddq, p, ds, bias, a.ldb, db, a.lddb);
 }
 
 // panel `c` of the column pass over A^T: kcv columns of dV, kck columns of dK
@@ -52,7 +54,12 @@ static void attention_bwd_round(const AttentionBwdArgs &a, hipStream_t stream)
 {
     constexpr int KP = SpmmShape<T>::KP;
     // sddmm's lane group for k: a function of k and the value type alone, it fixes the scores' summation order
-    if (a.m > 0) with_width(panel_group_width<T>(a.k), [&](auto CW) { attention_bwd_rows_cw<T, decltype(CW)::value, VEC>(a, stream); });
+    // a bias or a wanted dB has instantiations of its own: without them, the row kernels are the code without the bias's loads, addition and store
+    if (a.m > 0)
+        with_width(panel_group_width<T>(a.k), [&](auto CW) {
+            if (a.bias || a.db) attention_bwd_rows_cw<T, decltype(CW)::value, VEC, true>(a, stream);
+            else attention_bwd_rows_cw<T, decltype(CW)::value, VEC, false>(a, stream);
+        });
     if (!a.dk && !a.dvo) return;
     const int wk = a.dk ? a.k : 0, wv = a.dvo ? a.dv : 0;
     for (int c = 0; c < wk || c < wv; c += KP) { // panel c / KP of both outputs, of every head of the round, in one pass over A^T
@@ -78,6 +85,8 @@ static void attention_bwd_launch_t(const AttentionBwdArgs &a, hipStream_t stream
         if (a.dq) r.dq = (T *) a.dq + ck;
         if (a.dk) r.dk = (T *) a.dk + ck;
         if (a.dvo) r.dvo = (T *) a.dvo + cv;
+        if (a.bias) r.bias = (const T *) a.bias + (long long) h0 * a.ldb; // the round's first planes: dB goes straight to the caller's, at head h0 + g
+        if (a.db) r.db = (T *) a.db + (long long) h0 * a.lddb;
         attention_bwd_round<T, VEC>(r, stream);
     }
 }

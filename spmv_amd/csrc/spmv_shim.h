@@ -149,6 +149,13 @@ int spmv_shim_attention_heads(spmv_dev *d, int heads, int k, int dv, double scal
 double spmv_shim_time_attention_heads(spmv_dev *d, int heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v,
                                       long long ldv, void *o, long long ldo, int warmup, int iters, float *ms_out);
 
+/* an additive bias per head and entry (spmv_hip_attention_bias): bias NULL (ldb ignored: spmv_shim_attention_heads) or planes of nnz elements in
+ * CSR order, head h's at bias + h*ldb, ldb = 0 one plane for all heads; host or device pointer.  0 < ldb < nnz or ldb < 0: SPMV_HIP_E_ARG */
+int spmv_shim_attention_bias(spmv_dev *d, int heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v, long long ldv,
+                             const void *bias, long long ldb, void *o, long long ldo);
+double spmv_shim_time_attention_bias(spmv_dev *d, int heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v,
+                                     long long ldv, const void *bias, long long ldb, void *o, long long ldo, int warmup, int iters, float *ms_out);
+
 /* ---- dQ, dK, dV of the fused attention in two passes (shim/attention_backward.hpp; spmv_hip_attention_backward) ----
  * Q m x k, K n x k, V n x dv, G m x dv; dq m x k, dk n x k, dv_out n x dv or NULL (not wanted); row-major with leading dimensions; host or
  * device pointers each.  Needs the resident ColIdx and, when dk or dv_out is wanted, the attached transpose with its column indices resident
@@ -171,6 +178,16 @@ int spmv_shim_attention_heads_backward(spmv_dev *d, int heads, int max_heads, in
 double spmv_shim_time_attention_heads_backward(spmv_dev *d, int heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
                                                const void *v, long long ldv, const void *g, long long ldg, void *dq, long long lddq, void *dk, long long lddk, void *dv_out,
                                                long long lddv, int warmup, int iters, float *ms_out);
+
+/* with the bias of spmv_shim_attention_bias and its gradient (spmv_hip_attention_bias_backward): db NULL (not wanted) or `heads` planes
+ * lddb >= nnz apart, written by the row pass alone (only db wanted: no column pass, the transpose is not looked at).  bias and db NULL is
+ * spmv_shim_attention_heads_backward */
+int spmv_shim_attention_bias_backward(spmv_dev *d, int heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
+                                      const void *v, long long ldv, const void *bias, long long ldb, const void *g, long long ldg, void *dq, long long lddq, void *dk,
+                                      long long lddk, void *dv_out, long long lddv, void *db, long long lddb);
+double spmv_shim_time_attention_bias_backward(spmv_dev *d, int heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
+                                              const void *v, long long ldv, const void *bias, long long ldb, const void *g, long long ldg, void *dq, long long lddq, void *dk,
+                                              long long lddk, void *dv_out, long long lddv, void *db, long long lddb, int warmup, int iters, float *ms_out);
 
 /* the resident CSR arrays (device pointers; ColIdx may be NULL after spmv_shim_release_columns) */
 void spmv_shim_matrix_arrays(const spmv_dev *d, const int **rowptr, const int **colidx, const void **val);
