@@ -401,6 +401,51 @@ int spmv_hip_attention_bias_backward(spmv_Handle_t handle, BASIC_INT_TYPE m, con
                                      void *dV, long long lddv,                /* n x heads*dv, or NULL */
                                      void *dB, long long lddb);               /* heads planes of nnz, or NULL */
 
+/* ---- grouped-query sparse attention: `heads` query heads over `kv_heads` K / V heads (GQA; kv_heads == 1: MQA) --------------
+ * spmv_hip_attention_bias with fewer K / V heads than query heads.  Q and O are `heads` blocks wide as there; K is n x kv_heads*k and V is
+ * n x kv_heads*dv (ldk, ldv are checked against THOSE widths); heads % kv_heads == 0 and, with gs = heads / kv_heads, query head h uses K / V head
+ * h / gs -- the consecutive grouping of repeat_interleave.  B stays a plane per QUERY head (ldb == 0: one shared plane; B == NULL: no bias).
+ *   - Head h's block of O has exactly the bits spmv_hip_attention_bias writes with ONE head on Q + h*k, K + (h/gs)*k, V + (h/gs)*dv, O + h*dv and
+ *     plane h of B.  kv_heads == heads IS spmv_hip_attention_bias, to the bit.  K and V are never expanded: a host K / V is staged at its
+ *     kv_heads width, and device_bytes is spmv_hip_attention_heads'.
+ *   - 16-byte accesses need k and dv to be multiples of 16 bytes when heads > 1, as there; the access width changes no bit.
+ *   - Errors: spmv_hip_attention_bias', and kv_heads < 1, heads % kv_heads != 0, kv_heads*k or kv_heads*dv beyond int, ldk < kv_heads*k,
+ *     ldv < kv_heads*dv: SPMV_HIP_E_ARG before the handle's state is looked at, O untouched.  Handle kinds and SPMV_HIP_E_NOSTATE as there. */
+int spmv_hip_attention_gqa(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                           const void *Matrix_Val, int heads, int kv_heads, int k, int dv, double scale,
+                           const void *Q, long long ldq,            /* m x heads*k */
+                           const void *K, long long ldk,            /* n x kv_heads*k */
+                           const void *V, long long ldv,            /* n x kv_heads*dv */
+                           const void *B, long long ldb,            /* `heads` bias planes, one shared plane, or NULL */
+                           void *O, long long ldo);                 /* m x heads*dv */
+
+/* ---- the gradients of spmv_hip_attention_gqa: dQ, dK, dV and dB -----------------------------------------------
+ * spmv_hip_attention_bias_backward with the layout above: G, dQ `heads` blocks wide, dK n x kv_heads*k, dV n x kv_heads*dv, dB `heads` planes.
+ * Let dK(h), dV(h) be what the single-head backward writes for query head h on Q + h*k, K + (h/gs)*k, V + (h/gs)*dv, G + h*dv and plane h of B.
+ *   - dQ and dB: head h's bits of that single-head call.
+ *   - dK and dV of K / V head g: (((dK(g*gs) + dK(g*gs+1)) + ...) + dK(g*gs+gs-1)), and the same for dV -- plain additions in the handle's
+ *     precision in ascending query head, the first term taken as it is (not added to a zero), nothing contracted; gs == 1: no addition at all,
+ *     and the call IS spmv_hip_attention_bias_backward to the bit.  A caller restates it with the single-head call per head and that loop.
+ *   - No head-wide dK or dV ever exists in memory: the sums are held in registers by the column pass, or in the output element itself, read and
+ *     written by one thread.  The handle's P and dS planes stay per QUERY head; device_bytes is spmv_hip_attention_heads_backward's for `heads`.
+ *   - Option "attention_backward_heads" changes no bit: a round may end inside a group, and the next round's column pass then continues the
+ *     chain from the dK / dV it finds (the thread that stores an element reads back its own earlier store; one stream, in order).  The
+ *     default number of heads per round is a multiple of gs whenever it is at least gs, so the default path never reads back.
+ *   - Which outputs are wanted, pointer kinds, leading dimensions, alignment, method, stream and async change no bit; only dB wanted runs
+ *     no column pass and needs no transpose.  Special values stay in their query head in dQ and dB and reach, in dK and dV, the K / V head
+ *     of their group and no other.  Empty rows and columns, nnz == 0, m == 0: spmv_hip_attention_heads_backward's rules at these widths (+0).
+ *   - Errors: spmv_hip_attention_bias_backward's, and those of spmv_hip_attention_gqa with lddk < kv_heads*k, lddv < kv_heads*dv for WANTED
+ *     outputs: SPMV_HIP_E_ARG before the handle's state is looked at, every output untouched. */
+int spmv_hip_attention_gqa_backward(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                                    const void *Matrix_Val, int heads, int kv_heads, int k, int dv, double scale,
+                                    const void *Q, long long ldq, const void *K, long long ldk, const void *V, long long ldv,
+                                    const void *B, long long ldb,            /* bias planes, or NULL */
+                                    const void *G, long long ldg,            /* dL/dO, m x heads*dv */
+                                    void *dQ, long long lddq,                /* m x heads*k,     or NULL: not wanted */
+                                    void *dK, long long lddk,                /* n x kv_heads*k,  or NULL */
+                                    void *dV, long long lddv,                /* n x kv_heads*dv, or NULL */
+                                    void *dB, long long lddb);               /* heads planes of nnz, or NULL */
+
 /* ---- options --------------------------------------------------------------------------------
  * Resolved once per handle, at create: process-wide value (spmv_hip_set_option / env), overridden by the
  * calling thread's value (spmv_hip_set_thread_option) -- so two threads can create differently tuned handles

@@ -59,6 +59,15 @@ double spmv_hip_time_attention_bias_backward_launches(spmv_Handle_t handle, int 
                                                       long long ldk, const void *V, long long ldv, const void *B, long long ldb, const void *G, long long ldg, void *dQ,
                                                       long long lddq, void *dK, long long lddk, void *dV, long long lddv, void *dB, long long lddb, int warmup, int iters,
                                                       float *ms_out);
+/* The same for spmv_hip_attention_gqa and spmv_hip_attention_gqa_backward: the bias timers' arguments plus kv_heads (K, V, dK, dV kv_heads blocks
+ * wide; DEVICE pointers). */
+double spmv_hip_time_attention_gqa_launches(spmv_Handle_t handle, int heads, int kv_heads, int k, int dv, double scale, const void *Q, long long ldq, const void *K,
+                                            long long ldk, const void *V, long long ldv, const void *B, long long ldb, void *O, long long ldo, int warmup, int iters,
+                                            float *ms_out);
+double spmv_hip_time_attention_gqa_backward_launches(spmv_Handle_t handle, int heads, int kv_heads, int k, int dv, double scale, const void *Q, long long ldq, const void *K,
+                                                     long long ldk, const void *V, long long ldv, const void *B, long long ldb, const void *G, long long ldg, void *dQ,
+                                                     long long lddq, void *dK, long long lddk, void *dV, long long lddv, void *dB, long long lddb, int warmup, int iters,
+                                                     float *ms_out);
 /* copies the built transpose map to host: rowptr_t (n+1 entries) and perm (nnz entries: perm[p] = CSR index in A of the entry at
    position p of A^T's CSR); either may be NULL.  SPMV_HIP_E_NOSTATE until the transpose is built. */
 int spmv_hip_transpose_map(spmv_Handle_t handle, int *rowptr_t, int *perm);

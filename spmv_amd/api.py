@@ -149,6 +149,16 @@ FUNCTIONS = {
     "spmv_hip_time_attention_bias_backward_launches": (C.c_double, [spmv_Handle_t, C.c_int, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong,
                                                                     _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong,
                                                                     _V, C.c_longlong, _V, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "spmv_hip_attention_gqa": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong,
+                                         _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong]),
+    "spmv_hip_time_attention_gqa_launches": (C.c_double, [spmv_Handle_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong,
+                                                          _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "spmv_hip_attention_gqa_backward": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong,
+                                                  _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong,
+                                                  _V, C.c_longlong]),
+    "spmv_hip_time_attention_gqa_backward_launches": (C.c_double, [spmv_Handle_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong,
+                                                                   _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong,
+                                                                   _V, C.c_longlong, _V, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_float)]),
     # include/spmv_io.h (host only)
     "spmv_io_read_mtx": (C.c_int, [C.c_char_p, C.c_size_t, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_V)]),
     "spmv_io_cache_path": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t]),
@@ -630,6 +640,88 @@ def time_attention_bias_backward_launches(handle, heads, Q, K, V, B, G, dQ=None,
     return _timed("spmv_hip_time_attention_bias_backward_launches", (handle, int(heads), k, dv, float(scale), *rest), warmup, iters)
 
 
+def _gqa_widths(heads, kv_heads, wq, wkk, wv, wo, o_name):
+    """-> (k, dv) of ONE head from the column counts of Q, K, V and O / G: Q and O / G hold `heads` blocks, K and V `kv_heads`"""
+    heads, kv_heads = int(heads), int(kv_heads)
+    if heads < 1 or kv_heads < 1 or heads % kv_heads:
+        raise ValueError(f"heads = {heads} is not a multiple of kv_heads = {kv_heads}")
+    if wq % heads or wo % heads or wkk % kv_heads or wv % kv_heads or wq // heads != wkk // kv_heads or wo // heads != wv // kv_heads:
+        raise ValueError(f"Q has {wq} columns, K {wkk}, V {wv} and {o_name} {wo}: not {heads} query heads over {kv_heads} K / V heads of equal widths")
+    return wq // heads, wo // heads
+
+
+def _attention_gqa_blocks(heads, kv_heads, Q, K, V, O):
+    """-> (k, dv, pq, ldq, pk, ldk, pv, ldv, po, ldo) of an attention_gqa call: Q (heads*k) and K (kv_heads*k), V (kv_heads*dv) and O (heads*dv)"""
+    pq, _, wq, ldq = _block(Q, "Q")
+    pk, _, wkk, ldk = _block(K, "K")
+    pv, _, wv, ldv = _block(V, "V")
+    po, _, wo, ldo = _block(O, "O")
+    k, dv = _gqa_widths(heads, kv_heads, wq, wkk, wv, wo, "O")
+    return k, dv, pq, int(max(ldq, 1)), pk, int(max(ldk, 1)), pv, int(max(ldv, 1)), po, int(max(ldo, 1))
+
+
+def attention_gqa(handle, m, RowPtr, ColIdx, Matrix_Val, heads, kv_heads, Q, K, V, B, O, scale=None, check=True, ldb=None):
+    """attention_bias() with `kv_heads` K / V heads for `heads` query heads (spmv_hip_attention_gqa; grouped-query attention, kv_heads = 1:
+    multi-query).  Q (m x heads*k) and O (m x heads*dv) as there; K is (n x kv_heads*k) and V (n x kv_heads*dv); query head h uses K / V head
+    h // (heads // kv_heads), the grouping of repeat_interleave, and has the bits of the single-head call on those slices.  B: None, (nnz,) or
+    (heads, nnz) -- per QUERY head.  kv_heads = heads is attention_bias().  -> the return code."""
+    k, dv, pq, ldq, pk, ldk, pv, ldv, po, ldo = _attention_gqa_blocks(heads, kv_heads, Q, K, V, O)
+    scale = 1.0 / np.sqrt(k) if scale is None and k > 0 else (0.0 if scale is None else scale)
+    pb, ld = (_ptr(B), int(ldb)) if ldb is not None else _planes(B, "B", heads, True)
+    return _checked(load().spmv_hip_attention_gqa(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), int(heads), int(kv_heads), k, dv, float(scale),
+                                                  pq, ldq, pk, ldk, pv, ldv, pb, ld, po, ldo), "spmv_hip_attention_gqa", check)
+
+
+def time_attention_gqa_launches(handle, heads, kv_heads, Q, K, V, B, O, scale=None, warmup=10, iters=100):
+    """-> (mean_ms, per-call ms array) of spmv_hip_attention_gqa on device operands (spmv_hip_time_attention_gqa_launches)."""
+    k, dv, pq, ldq, pk, ldk, pv, ldv, po, ldo = _attention_gqa_blocks(heads, kv_heads, Q, K, V, O)
+    scale = 1.0 / np.sqrt(k) if scale is None else scale
+    pb, ld = _planes(B, "B", heads, True)
+    return _timed("spmv_hip_time_attention_gqa_launches", (handle, int(heads), int(kv_heads), k, dv, float(scale), pq, ldq, pk, ldk, pv, ldv, pb, ld, po, ldo),
+                  warmup, iters)
+
+
+def _attention_gqa_backward_args(heads, kv_heads, Q, K, V, B, G, dQ, dK, dV, dB, ldb, lddb):
+    """-> (k, dv, the C arguments from Q on) of an attention_gqa_backward call; an output that is None has a NULL address and its width as ld"""
+    pq, _, wq, ldq = _block(Q, "Q")
+    pk, _, wkk, ldk = _block(K, "K")
+    pv, _, wv, ldv = _block(V, "V")
+    pg, _, wg, ldg = _block(G, "G")
+    k, dv = _gqa_widths(heads, kv_heads, wq, wkk, wv, wg, "G")
+    args = [pq, int(max(ldq, 1)), pk, int(max(ldk, 1)), pv, int(max(ldv, 1))]
+    pb, ld = (_ptr(B), int(ldb)) if ldb is not None else _planes(B, "B", heads, True)
+    args += [pb, ld, pg, int(max(ldg, 1))]
+    for a, name, width in ((dQ, "dQ", wq), (dK, "dK", wkk), (dV, "dV", wv)):
+        if a is None:
+            args += [None, int(width)]
+            continue
+        p, _, w, ldo = _block(a, name)
+        if w != width:
+            raise ValueError(f"{name} has {w} columns, expected {width}")
+        args += [p, int(max(ldo, 1))]
+    pdb, ldd = (_ptr(dB), int(lddb)) if lddb is not None else _planes(dB, "dB", heads, False)
+    return k, dv, args + [pdb, ldd]
+
+
+def attention_gqa_backward(handle, m, RowPtr, ColIdx, Matrix_Val, heads, kv_heads, Q, K, V, B, G, dQ=None, dK=None, dV=None, dB=None, scale=None, check=True,
+                           ldb=None, lddb=None):
+    """dQ, dK, dV and dB of attention_gqa(Q, K, V, B) from G = dL/dO (spmv_hip_attention_gqa_backward).  Q, G, dQ hold `heads` blocks, K, V, dK, dV
+    `kv_heads`; dB: None or (heads, nnz).  dQ and dB of head h are the single-head backward's bits on its slices; dK / dV of a K / V head are the
+    sums of its query heads' single-head dK / dV, added in ascending head in the handle's precision, the first taken as it is.  kv_heads = heads
+    is attention_bias_backward().  -> the return code."""
+    k, dv, rest = _attention_gqa_backward_args(heads, kv_heads, Q, K, V, B, G, dQ, dK, dV, dB, ldb, lddb)
+    scale = 1.0 / np.sqrt(k) if scale is None and k > 0 else (0.0 if scale is None else scale)
+    return _checked(load().spmv_hip_attention_gqa_backward(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), int(heads), int(kv_heads), k, dv,
+                                                           float(scale), *rest), "spmv_hip_attention_gqa_backward", check)
+
+
+def time_attention_gqa_backward_launches(handle, heads, kv_heads, Q, K, V, B, G, dQ=None, dK=None, dV=None, dB=None, scale=None, warmup=10, iters=100):
+    """-> (mean_ms, per-call ms array) of spmv_hip_attention_gqa_backward on device operands (spmv_hip_time_attention_gqa_backward_launches)."""
+    k, dv, rest = _attention_gqa_backward_args(heads, kv_heads, Q, K, V, B, G, dQ, dK, dV, dB, None, None)
+    scale = 1.0 / np.sqrt(k) if scale is None else scale
+    return _timed("spmv_hip_time_attention_gqa_backward_launches", (handle, int(heads), int(kv_heads), k, dv, float(scale), *rest), warmup, iters)
+
+
 def _take_csr(m, n, nnz, rp, ci, va, dtype):
     """Copy malloc'ed C arrays into numpy arrays and free the C side."""
     from .synth import CSR
@@ -850,6 +942,27 @@ class Handle:
         dB = self._like(Q, (int(heads), self.nnz)) if need[3] else None
         rp, ci, va = self._keep
         attention_bias_backward(self.h, self.m, rp, ci, va, heads, Q, K, V, bias, G, dQ, dK, dV, dB, scale)
+        return dQ, dK, dV, dB
+
+    def attention_gqa(self, Q, K, V, heads, kv_heads, bias=None, scale=None, out=None):
+        """out = attention_bias(Q, K, V, heads, bias, scale) with `kv_heads` K / V heads: K is (n, kv_heads*k), V (n, kv_heads*dv), and query head
+        h uses K / V head h // (heads // kv_heads) (spmv_hip_attention_gqa).  out is (m, heads*dv)."""
+        if out is None:
+            out = self._like(Q, (self.m, (V.shape[1] // int(kv_heads)) * int(heads)))
+        rp, ci, va = self._keep
+        attention_gqa(self.h, self.m, rp, ci, va, heads, kv_heads, Q, K, V, bias, out, scale)
+        return out
+
+    def attention_gqa_backward(self, Q, K, V, bias, G, heads, kv_heads, scale=None, need=(True, True, True, True)):
+        """-> (dQ, dK, dV, dB), the gradients of attention_gqa(Q, K, V, heads, kv_heads, bias, scale) for G = dL/dO
+        (spmv_hip_attention_gqa_backward); need: which of the four are wanted.  dK and dV have K's and V's widths (kv_heads blocks): the sums over
+        each group's query heads in ascending head.  dB is (heads, nnz).  The outputs are allocated like Q."""
+        dQ = self._like(Q, (self.m, Q.shape[1])) if need[0] else None
+        dK = self._like(Q, (self.n, K.shape[1])) if need[1] else None
+        dV = self._like(Q, (self.n, V.shape[1])) if need[2] else None
+        dB = self._like(Q, (int(heads), self.nnz)) if need[3] else None
+        rp, ci, va = self._keep
+        attention_gqa_backward(self.h, self.m, rp, ci, va, heads, kv_heads, Q, K, V, bias, G, dQ, dK, dV, dB, scale)
         return dQ, dK, dV, dB
 
     def update_values(self, val):

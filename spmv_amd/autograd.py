@@ -385,6 +385,63 @@ class _AttentionHeads(torch.autograd.Function):
         return None, dQ, dK, dV, None, None, None, _bias_grad(dB, B2)
 
 
+class _AttentionGqa(torch.autograd.Function):
+    """Handle.attention_gqa forward (kv_heads K / V heads for `heads` query heads); the backward pass is ONE Handle.attention_gqa_backward call
+    (fused), or one single-head backward per query head on its group's K / V slices, dK and dV of a group accumulated in torch in ascending
+    head -- the first head assigned, the others added: the fused call's chain, so both modes give the same bits.  K and V are saved at their
+    own (narrow) width; the handle's values are never touched"""
+
+    @staticmethod
+    def forward(ctx, handle, Q, K, V, heads, kv_heads, scale, fused=False, bias=None):
+        Q2, K2, V2 = _block(Q.detach(), Q.shape[1]), _block(K.detach(), K.shape[1]), _block(V.detach(), V.shape[1])
+        B2 = _bias_planes(bias)
+        _on_current_stream(handle)
+        O = handle.attention_gqa(Q2, K2, V2, heads, kv_heads, B2, scale)
+        ctx.handle, ctx.heads, ctx.kv_heads, ctx.scale, ctx.fused = handle, heads, kv_heads, scale, fused
+        ctx.save_for_backward(Q2, K2, V2, B2)   # nothing nnz-sized but the caller's own bias
+        return O
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, G):
+        from . import api
+        handle, heads, kv_heads, scale = ctx.handle, ctx.heads, ctx.kv_heads, ctx.scale
+        Q2, K2, V2, B2 = ctx.saved_tensors
+        need = tuple(bool(x) for x in ctx.needs_input_grad[1:4])
+        need_b = B2 is not None and bool(ctx.needs_input_grad[8])
+        if not (any(need) or need_b):
+            return (None,) * 9
+        if handle.nnz == 0:   # no stored entry: O is zero whatever Q, K and V are
+            return None, (torch.zeros_like(Q2) if need[0] else None), (torch.zeros_like(K2) if need[1] else None), (torch.zeros_like(V2) if need[2] else None), None, None, None, \
+                None, (torch.zeros_like(B2) if need_b else None)
+        _on_current_stream(handle)
+        G2 = _block(G, G.shape[1])
+        if ctx.fused:   # every head in one call
+            dQ, dK, dV, dB = handle.attention_gqa_backward(Q2, K2, V2, B2, G2, heads, kv_heads, scale, need=(*need, need_b))
+            return None, dQ, dK, dV, None, None, None, None, _bias_grad(dB, B2)
+        gs, k, dv = heads // kv_heads, Q2.shape[1] // heads, V2.shape[1] // kv_heads
+        dQ = torch.empty_like(Q2, memory_format=torch.contiguous_format) if need[0] else None
+        dK = torch.empty_like(K2, memory_format=torch.contiguous_format) if need[1] else None
+        dV = torch.empty_like(V2, memory_format=torch.contiguous_format) if need[2] else None
+        dB = Q2.new_empty((heads, handle.nnz)) if need_b else None
+        tK = Q2.new_empty((handle.n, k)) if need[1] and gs > 1 else None   # one head's term of dK / dV: what the group's later heads add
+        tV = Q2.new_empty((handle.n, dv)) if need[2] and gs > 1 else None
+        rp, ci, va = handle._keep
+        for h in range(heads):
+            g, first = h // gs, h % gs == 0
+            cq, co, ck, cv = slice(h * k, (h + 1) * k), slice(h * dv, (h + 1) * dv), slice(g * k, (g + 1) * k), slice(g * dv, (g + 1) * dv)
+            oK = None if dK is None else (dK[:, ck] if first else tK)
+            oV = None if dV is None else (dV[:, cv] if first else tV)
+            api.attention_bias_backward(handle.h, handle.m, rp, ci, va, 1, Q2[:, cq], K2[:, ck], V2[:, cv], None if B2 is None else (B2 if B2.dim() == 1 else B2[h]),
+                                        G2[:, co], None if dQ is None else dQ[:, cq], oK, oV, None if dB is None else dB[h], scale)
+            if not first:   # (..(first + second) + ..) + this one: plain additions in ascending head
+                if dK is not None:
+                    dK[:, ck] += tK
+                if dV is not None:
+                    dV[:, cv] += tV
+        return None, dQ, dK, dV, None, None, None, None, _bias_grad(dB, B2)
+
+
 def _check_bias(bias, handle, heads):
     if bias is None:
         return
@@ -393,7 +450,7 @@ def _check_bias(bias, handle, heads):
         raise ValueError(f"bias must be ({handle.nnz},) or ({heads}, {handle.nnz}), not {tuple(bias.shape)}")
 
 
-def attention_heads(handle, Q, K, V, heads, scale=None, backward="per_head", *, bias=None):
+def attention_heads(handle, Q, K, V, heads, scale=None, backward="per_head", *, bias=None, kv_heads=None):
     """`heads` attention heads over the handle's pattern (Handle.attention_heads: one fused pass for all heads), with gradients for Q, K and
     V.  Q: (m, heads * k), K: (n, heads * k), V: (n, heads * dv) hold the heads side by side -- a (rows, heads, k) tensor reshaped to two
     dimensions --, of the handle's dtype on its device; the result is (m, heads * dv).  scale: a Python number, None means 1 / sqrt(k) with k
@@ -414,13 +471,30 @@ def attention_heads(handle, Q, K, V, heads, scale=None, backward="per_head", *, 
     softmax (Handle.attention_bias; t = (s * scale) + bias, two roundings).  It receives a gradient: dL/dbias[h, p] = P (dP - D) of head h
     (Handle.attention_bias_backward, in the same call as dQ, dK, dV; per head in the default mode, on plane h); a shared plane's gradient is the
     sum of the heads' planes -- torch's sum, whose order is not part of the contract.  A -inf entry masks that entry for that head.  The forward
-    pass saves Q, K, V and a reference to the bias; a bias that needs no gradient gets none computed."""
+    pass saves Q, K, V and a reference to the bias; a bias that needs no gradient gets none computed.
+
+    kv_heads: None means `heads` -- everything above, untouched.  Otherwise grouped-query attention (Handle.attention_gqa): K is
+    (n, kv_heads * k) and V (n, kv_heads * dv), heads a multiple of kv_heads, and query head h uses K / V head h // (heads // kv_heads) -- K and V
+    are never expanded and are saved at their narrow width.  backward="fused" is one Handle.attention_gqa_backward call; the default mode calls
+    the single-head backward per query head on its group's K / V slices and accumulates dK and dV of a group in torch in ascending head (the first
+    head assigned, the others +=), which is the fused call's chain: both modes give the same bits.  The bias stays per QUERY head."""
     if backward not in ("per_head", "fused"):
         raise ValueError(f"backward must be 'per_head' or 'fused', not {backward!r}")
     _check_handle(handle)
     for t, name in ((Q, "Q"), (K, "K"), (V, "V")):
         _check_tensor(t, name, handle)
     heads = int(heads)
+    if kv_heads is not None:
+        kv_heads = int(kv_heads)
+        if heads < 1 or kv_heads < 1 or heads % kv_heads:
+            raise ValueError(f"heads = {heads} is not a multiple of kv_heads = {kv_heads}")
+        if Q.dim() != 2 or K.dim() != 2 or V.dim() != 2 or Q.shape[0] != handle.m or K.shape[0] != handle.n or V.shape[0] != handle.n or Q.shape[1] < 1 or V.shape[1] < 1:
+            raise ValueError(f"Q must be ({handle.m}, heads * k), K ({handle.n}, kv_heads * k) and V ({handle.n}, kv_heads * dv) with k, dv >= 1, not {tuple(Q.shape)}, {tuple(K.shape)} and {tuple(V.shape)}")
+        if Q.shape[1] % heads or K.shape[1] % kv_heads or V.shape[1] % kv_heads or Q.shape[1] // heads != K.shape[1] // kv_heads:
+            raise ValueError(f"{Q.shape[1]} columns of Q, {K.shape[1]} of K and {V.shape[1]} of V are not {heads} query heads over {kv_heads} K / V heads of equal width")
+        _check_bias(bias, handle, heads)
+        scale = 1.0 / math.sqrt(Q.shape[1] // heads) if scale is None else float(scale)
+        return _AttentionGqa.apply(handle, Q, K, V, heads, kv_heads, scale, backward == "fused", bias)
     if Q.dim() != 2 or K.dim() != 2 or V.dim() != 2 or Q.shape[0] != handle.m or K.shape[0] != handle.n or V.shape[0] != handle.n or \
             Q.shape[1] != K.shape[1] or Q.shape[1] < 1 or V.shape[1] < 1:
         raise ValueError(f"Q must be ({handle.m}, heads * k), K ({handle.n}, heads * k) and V ({handle.n}, heads * dv) with k, dv >= 1, not {tuple(Q.shape)}, {tuple(K.shape)} and {tuple(V.shape)}")

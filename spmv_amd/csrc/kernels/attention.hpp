@@ -29,6 +29,12 @@
 // the dots and, after the tile's scores are in LDS, adds it to its own entry's; long rows: added where the score is parked.  Everything after
 // t_p is unchanged.  The instantiations without BIAS are the code from before the bias existed.
 //
+// Grouped heads (spmv_hip_attention_gqa; the GROUPED instantiations, launched when gs > 1): K and V hold heads / gs blocks only and head hd
+// reads block hd / gs of them -- a wave-uniform integer kept by a counter beside hd, outside the per-entry code; nothing else differs, so
+// head hd has the bits of the single-head call on Q's block hd and K's and V's block hd / gs.  Consecutive heads of a group gather the same
+// K and V rows: that reuse is left to the caches.  The instantiations without GROUPED do not look at gs and are the code
+// from before the groups existed (as a runtime argument alone gs moved the register allocation of every instantiation: DESIGN.md 3.21).
+//
 // Arithmetic and order: the composition's, because its blocks are the composition's (kernels/row_blocks.hpp) -- s_p is sddmm's dot for this
 // k (kernels/sddmm.hpp), t_p = s_p * scale one plain multiplication, M_i / Z_i / P_p = exp(t_p - M_i) / Z_i the row softmax's by row length,
 // O[i, c] spmm's chain.  The result is a function of the matrix, k, dv and the value type alone.  Contraction is pinned off: the fmas written
@@ -45,6 +51,7 @@ namespace spmv {
 // what one call's launches need (device pointers)
 struct AttentionArgs {
     int m = 0, heads = 1, k = 0, dv = 0, nb = 0, nlong = 0, cus = 256; // k, dv: per head
+    int gs = 1; // query heads per K / V head: kk and v are heads / gs blocks wide, head hd reads block hd / gs
     const int *split = nullptr, *longs = nullptr, *rowptr = nullptr, *colidx = nullptr;
     const int *long_off = nullptr; // first parked element of long row i of the list
     void *park = nullptr;          // the long rows' scores, then P
@@ -113,12 +120,12 @@ __device__ __forceinline__ void att_tile_scores(int i, int j, int lane, int k, c
 // One wave per batch [split[b], split[b + 1]) of whole rows; rows longer than kSpmmLongThr are left to attention_long_kernel.
 // CW: sddmm's lane group for k; 1 << lgv: spmm's lane group for min(dv, KP) columns.  heads: the chunk's columns stay in s_col while the
 // three phases run once per head over s_p, head hd on the columns from hd * k of Q and K and from hd * dv of V and O.  BIAS: head hd adds
-// bias[hd * ldb + p] to the scaled score of entry p (bias is not nullptr).
-template <typename T, int CW, bool VEC, bool BIAS>
+// bias[hd * ldb + p] to the scaled score of entry p (bias is not nullptr).  GROUPED: gs > 1 heads per K / V block.
+template <typename T, int CW, bool VEC, bool BIAS, bool GROUPED>
 __global__ __launch_bounds__(kBlock) void attention_rows_kernel(int nb, const int *__restrict__ split, const int *__restrict__ rowptr, const int *__restrict__ colidx, int heads,
                                                                 int k, int dv, int lgv, T scale, const T *__restrict__ q, long long ldq, const T *__restrict__ kk, long long ldk,
                                                                 const T *__restrict__ v, long long ldv, T *__restrict__ o, long long ldo, const T *__restrict__ bias,
-                                                                long long ldb)
+                                                                long long ldb, int gs)
 {
 #pragma clang fp contract(off)
     constexpr int V = SpmmShape<T>::V, CH = kSpmmChunk;
@@ -136,9 +143,14 @@ __global__ __launch_bounds__(kBlock) void attention_rows_kernel(int nb, const in
         if (ch.nr == 0) { ++g0; continue; } // a long row: nothing of it here
         const int sl = ch.sl, ll = ch.ll, base = ch.base, nr = ch.nr, nq = ch.nq;
 
+        [[maybe_unused]] int kvh = 0, gc = 0; // GROUPED: kvh = hd / gs, kept by counting -- wave-uniform, in scalar registers
         for (int hd = 0; hd < heads; ++hd) {
             const int lane = att_per_head(lane0), subv = lane >> lgv, cv0 = (lane & (cwv - 1)) * V;
-            const T *qh = q + (long long) hd * k, *kh = kk + (long long) hd * k, *vh = v + (long long) hd * dv; // the head's first columns
+            const int hkv = GROUPED ? kvh : hd;
+            const T *qh = q + (long long) hd * k, *kh = kk + (long long) hkv * k, *vh = v + (long long) hkv * dv; // the head's first columns; K and V: its group's
+            if constexpr (GROUPED) {
+                if (++gc == gs) { gc = 0; ++kvh; }
+            }
             T *oh = o + (long long) hd * dv;
             // 1. columns (the first head reads them from memory, the others from LDS) and scaled scores into LDS
             for (int t0 = 0; t0 < nq; t0 += kWave) {
@@ -200,11 +212,11 @@ __global__ __launch_bounds__(kBlock) void attention_rows_kernel(int nb, const in
 // one workgroup per long row (len > kSpmmLongThr >= 256: every thread has a first term); park + long_off[i]: len elements of its own, used by
 // one head after the other (the barrier that ends a head's last panel is also the one before the next head parks its scores).  BIAS: the
 // bias is added where the score is parked.
-template <typename T, int CW, bool VEC, bool BIAS>
+template <typename T, int CW, bool VEC, bool BIAS, bool GROUPED>
 __global__ __launch_bounds__(kBlock) void attention_long_kernel(int nlong, const int *__restrict__ longs, const int *__restrict__ long_off, const int *__restrict__ rowptr,
                                                                 const int *__restrict__ colidx, int heads, int k, int dv, int lgv, T scale, const T *__restrict__ q, long long ldq,
                                                                 const T *__restrict__ kk, long long ldk, const T *__restrict__ v, long long ldv, T *__restrict__ o, long long ldo,
-                                                                T *park, const T *__restrict__ bias, long long ldb)
+                                                                T *park, const T *__restrict__ bias, long long ldb, int gs)
 {
 #pragma clang fp contract(off)
     constexpr int V = SpmmShape<T>::V, KP = SpmmShape<T>::KP;
@@ -216,9 +228,14 @@ __global__ __launch_bounds__(kBlock) void attention_long_kernel(int nlong, const
         const int r = longs[i], s = rowptr[r], len = rowptr[r + 1] - s;
         const int *col = colidx + s;
         T *t = park + long_off[i];
+        [[maybe_unused]] int kvh = 0, gc = 0; // GROUPED: kvh = hd / gs, kept by counting
         for (int hd = 0; hd < heads; ++hd) {
-            const T *qh = q + (long long) hd * k, *kh = kk + (long long) hd * k, *vh = v + (long long) hd * dv; // the head's first columns
+            const int hkv = GROUPED ? kvh : hd;
+            const T *qh = q + (long long) hd * k, *kh = kk + (long long) hkv * k, *vh = v + (long long) hkv * dv; // the head's first columns; K and V: its group's
             T *oh = o + (long long) hd * dv;
+            if constexpr (GROUPED) {
+                if (++gc == gs) { gc = 0; ++kvh; }
+            }
             const int tid = att_per_head((int) threadIdx.x), w = tid / kWave, lane = tid & (kWave - 1);
             const int subv = tid >> lgv, cv0 = (tid & (cwv - 1)) * V;
             // 1. the scaled scores, parked: tiles of 64 entries, wave w takes the tiles w, w + 4, .. (entry p is thread p % 256's in every phase)

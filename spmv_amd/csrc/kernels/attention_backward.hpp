@@ -37,6 +37,14 @@
 // order).  Either of bias and db may be nullptr in a BIAS instantiation (wave-uniform tests); the column pass knows neither.  The
 // instantiations without BIAS are the code from before the bias existed.
 //
+// Grouped heads (spmv_hip_attention_gqa_backward): K, V, dK and dV hold heads / gs blocks and query head hd belongs to block hd / gs.  The
+// row pass only addresses K and V differently (a counter beside hd, outside the per-entry code); P, dS and dB stay per QUERY head.  All four
+// kernels have GROUPED instantiations for it, launched when gs > 1; the others do not look at gs and gpos and are the code from before.  The
+// column pass computes each head's dK / dV term as before and adds the terms of a group in ascending head: the first is taken as it is,
+// every other one is one plain addition, nothing is contracted -- (((t0 + t1) + t2) + ..), the chain a caller can restate.  No head-wide
+// dK or dV exists in memory: the running sums are registers (short columns) or the output element itself, read and written by one thread
+// (long columns; and wherever a round ends inside a group, the next round continuing from what it finds).
+//
 // Arithmetic and order: the composition's, because its blocks are the composition's (kernels/row_blocks.hpp) -- t and P are
 // spmv_hip_attention's; dP is sddmm's dot for dv; D is row_softmax_backward's by row length; dS is one subtraction and two plain
 // multiplications; dQ, dK and dV are spmm's chains.  Contraction is pinned off: the fmas written out are the only fused operations.
@@ -52,6 +60,7 @@ namespace spmv {
 struct AttentionBwdArgs {
     int m = 0, k = 0, dv = 0, cus = 256; // k, dv: per head
     int heads = 1, hg = 1;               // heads of the call; heads per round (the planes of p / ds)
+    int gs = 1, gpos = 0;                // query heads per K / V head (kk, v, dk, dvo are heads / gs blocks wide); a round: its first head's place in its group
     long long plane = 0;                 // elements per plane of p / ds: nnz
     int nb = 0, nlong = 0; // A: spmm's tables
     const int *split = nullptr, *longs = nullptr, *rowptr = nullptr, *colidx = nullptr;
@@ -84,13 +93,13 @@ __device__ __forceinline__ void attb_tile_dots(int cw, int i, int j, int lane, i
 // p_out / ds_out / dq: nullptr when dV / dK / dQ is not wanted.  heads: the chunk's columns stay in s_col while the four phases run once per
 // head over s_p / s_d, head hd on the columns from hd * k (Q, K, dQ) and hd * dv (V, G) and on plane hd of p_out / ds_out.
 // BIAS: bias (added to the scaled scores) and db (P (dP - D), before the scaling) as in the header; either may be nullptr.
-template <typename T, int CW, bool VEC, bool BIAS>
+template <typename T, int CW, bool VEC, bool BIAS, bool GROUPED>
 __global__ __launch_bounds__(kBlock) void attention_bwd_rows_kernel(int nb, const int *__restrict__ split, const int *__restrict__ rowptr, const int *__restrict__ colidx,
                                                                     int heads, long long plane, int k, int dv, int cwd, int lgk, T scale,
                                                                     const T *__restrict__ q, long long ldq, const T *__restrict__ kk, long long ldk,
                                                                     const T *__restrict__ v, long long ldv, const T *__restrict__ g, long long ldg, T *__restrict__ dq,
                                                                     long long lddq, T *__restrict__ p_out, T *__restrict__ ds_out, const T *__restrict__ bias,
-                                                                    long long ldb, T *__restrict__ db, long long lddb)
+                                                                    long long ldb, T *__restrict__ db, long long lddb, int gs, int gpos)
 {
 #pragma clang fp contract(off)
     constexpr int V = SpmmShape<T>::V, CH = kSpmmChunk;
@@ -109,9 +118,14 @@ __global__ __launch_bounds__(kBlock) void attention_bwd_rows_kernel(int nb, cons
         if (ch.nr == 0) { ++g0; continue; } // a long row: nothing of it here
         const int sl = ch.sl, ll = ch.ll, base = ch.base, nr = ch.nr, nq = ch.nq;
 
+        [[maybe_unused]] int kvh = 0, gc = gpos; // GROUPED: the head's K / V block, kept by counting -- wave-uniform, in scalar registers
         for (int hd = 0; hd < heads; ++hd) {
             const int lane = att_per_head(lane0), subk = lane >> lgk, ck0 = (lane & (cwk - 1)) * V;
-            const T *qh = q + (long long) hd * k, *kh = kk + (long long) hd * k, *vh = v + (long long) hd * dv, *gh = g + (long long) hd * dv; // the head's first columns
+            const int hkv = GROUPED ? kvh : hd;
+            const T *qh = q + (long long) hd * k, *kh = kk + (long long) hkv * k, *vh = v + (long long) hkv * dv, *gh = g + (long long) hd * dv; // the head's first columns; K and V: its group's
+            if constexpr (GROUPED) {
+                if (++gc == gs) { gc = 0; ++kvh; }
+            }
             // A. columns (the first head reads them from memory, the others from LDS), scaled scores and dP into LDS
             for (int t0 = 0; t0 < nq; t0 += kWave) {
                 const int e = t0 + lane;
@@ -235,13 +249,13 @@ __global__ __launch_bounds__(kBlock) void attention_bwd_rows_kernel(int nb, cons
 
 // one workgroup per long row (len > kSpmmLongThr >= 256: every thread has a first term); the row's ranges of every plane of pa (attb_p) and
 // da (attb_ds) are its own: no other workgroup of this launch touches them.  Head hd parks in plane hd's range.  BIAS: as in the rows kernel.
-template <typename T, int CW, bool VEC, bool BIAS>
+template <typename T, int CW, bool VEC, bool BIAS, bool GROUPED>
 __global__ __launch_bounds__(kBlock) void attention_bwd_long_kernel(int nlong, const int *__restrict__ longs, const int *__restrict__ rowptr, const int *__restrict__ colidx,
                                                                     int heads, long long plane, int k, int dv, int cwd, int lgk, T scale,
                                                                     const T *__restrict__ q, long long ldq, const T *__restrict__ kk, long long ldk,
                                                                     const T *__restrict__ v, long long ldv, const T *__restrict__ g, long long ldg, T *__restrict__ dq,
                                                                     long long lddq, T *pa, T *da, const T *__restrict__ bias, long long ldb, T *__restrict__ db,
-                                                                    long long lddb)
+                                                                    long long lddb, int gs, int gpos)
 {
 #pragma clang fp contract(off)
     constexpr int V = SpmmShape<T>::V, KP = SpmmShape<T>::KP;
@@ -252,8 +266,13 @@ __global__ __launch_bounds__(kBlock) void attention_bwd_long_kernel(int nlong, c
     for (int i = blockIdx.x; i < nlong; i += gridDim.x) {
         const int r = longs[i], s = rowptr[r], len = rowptr[r + 1] - s;
         const int *col = colidx + s;
+        [[maybe_unused]] int kvh = 0, gc = gpos; // GROUPED: the head's K / V block, kept by counting
         for (int hd = 0; hd < heads; ++hd) {
-            const T *qh = q + (long long) hd * k, *kh = kk + (long long) hd * k, *vh = v + (long long) hd * dv, *gh = g + (long long) hd * dv; // the head's first columns
+            const int hkv = GROUPED ? kvh : hd;
+            const T *qh = q + (long long) hd * k, *kh = kk + (long long) hkv * k, *vh = v + (long long) hkv * dv, *gh = g + (long long) hd * dv; // the head's first columns; K and V: its group's
+            if constexpr (GROUPED) {
+                if (++gc == gs) { gc = 0; ++kvh; }
+            }
             const int tid = att_per_head((int) threadIdx.x), w = tid / kWave, lane = tid & (kWave - 1);
             const int subk = tid >> lgk, ck0 = (tid & (cwk - 1)) * V;
             T *t = pa + hd * plane + s, *d = da + hd * plane + s;
@@ -303,11 +322,17 @@ __global__ __launch_bounds__(kBlock) void attention_bwd_long_kernel(int nlong, c
 // The head loop is around a row group's walk (a row's accumulators live across its chunks, so they cannot be kept for every head).  A group of
 // at most kSpmmChunk entries is ONE chunk: its columns are staged by the first head and stay in s_col for the others; a larger group (or one
 // with a long row in it) stages them again.  perm is read again by every head: L2 has just served it.
-template <typename T, int CW, bool VEC>
+// GROUPED (spmv_hip_attention_gqa_backward with gs > 1): dvo and dk are heads / gs blocks wide, offset to the block of the round's first head,
+// whose place in its group is gpos.  A lane's accv / acck of the heads of a group are added, in ascending head, into a running pair in
+// registers -- the group's first head is taken as it is, every other one is one plain addition -- and stored once per K / V block; a round
+// that starts inside a group (gpos > 0) first reads back what the lane itself stored in the round before, one that ends inside one stores
+// what it has.  Without GROUPED gs and gpos are not looked at and the kernel is the code from before the groups existed.
+template <typename T, int CW, bool VEC, bool GROUPED>
 __global__ __launch_bounds__(kBlock) void attention_bwd_cols_kernel(int nb, const int *__restrict__ split, const int *__restrict__ rowptr, const int *__restrict__ colidx,
                                                                     const int *__restrict__ perm, int heads, long long plane, int k, int dv, const T *__restrict__ pv,
                                                                     const T *__restrict__ dsv, int kcv, const T *__restrict__ g, long long ldg, T *__restrict__ dvo,
-                                                                    long long lddv, int kck, const T *__restrict__ q, long long ldq, T *__restrict__ dk, long long lddk)
+                                                                    long long lddv, int kck, const T *__restrict__ q, long long ldq, T *__restrict__ dk, long long lddk,
+                                                                    int gs, int gpos)
 {
 #pragma clang fp contract(off)
     constexpr int V = SpmmShape<T>::V, R = kWave / CW, CH = kSpmmChunk;
@@ -326,6 +351,8 @@ __global__ __launch_bounds__(kBlock) void attention_bwd_cols_kernel(int nb, cons
         const int s = have ? rowptr[r] : 0, e = have ? rowptr[r + 1] : 0;
         const bool longrow = e - s > kSpmmLongThr;
         const bool one = rowptr[g1] - rowptr[g0] <= CH; // the whole group is one chunk (and holds no long row): wave-uniform
+        [[maybe_unused]] T runv[V], runk[V]; // GROUPED: the sums over the group's heads so far
+        [[maybe_unused]] int kvh = 0, gc = gpos;
         for (int hd = 0; hd < heads; ++hd) {
             const T *ph = pv + hd * plane, *dh = dsv + hd * plane;
             const T *gh = g + (long long) hd * dv, *qh = q + (long long) hd * k; // the head's panel
@@ -344,19 +371,40 @@ __global__ __launch_bounds__(kBlock) void attention_bwd_cols_kernel(int nb, cons
                     if (!longrow && ncv > 0) spmm_chain<T, VEC, false>(lo, hi, s_col[w], s_p[w], gh, ldg, c0, ncv, accv);
                     if (!longrow && nck > 0) spmm_chain<T, VEC, false>(lo, hi, s_col[w], s_d[w], qh, ldq, c0, nck, acck);
                 });
-            if (have && !longrow && ncv > 0) spmm_store_y<T, VEC>(dvo + (long long) r * lddv + (long long) hd * dv + c0, ncv, accv);
-            if (have && !longrow && nck > 0) spmm_store_y<T, VEC>(dk + (long long) r * lddk + (long long) hd * k + c0, nck, acck);
+            if constexpr (!GROUPED) {
+                if (have && !longrow && ncv > 0) spmm_store_y<T, VEC>(dvo + (long long) r * lddv + (long long) hd * dv + c0, ncv, accv);
+                if (have && !longrow && nck > 0) spmm_store_y<T, VEC>(dk + (long long) r * lddk + (long long) hd * k + c0, nck, acck);
+            } else {
+                const bool first = gc == 0, back = hd == 0 && gc > 0, last = gc + 1 == gs || hd + 1 == heads; // wave-uniform
+                if (have && !longrow && ncv > 0) {
+                    T *y = dvo + (long long) r * lddv + (long long) kvh * dv + c0;
+                    if (back) spmm_load_x<T, VEC>(y, ncv, runv); // this lane's own store of the round before
+#pragma unroll
+                    for (int t = 0; t < V; ++t) runv[t] = first ? accv[t] : runv[t] + accv[t];
+                    if (last) spmm_store_y<T, VEC>(y, ncv, runv);
+                }
+                if (have && !longrow && nck > 0) {
+                    T *y = dk + (long long) r * lddk + (long long) kvh * k + c0;
+                    if (back) spmm_load_x<T, VEC>(y, nck, runk);
+#pragma unroll
+                    for (int t = 0; t < V; ++t) runk[t] = first ? acck[t] : runk[t] + acck[t];
+                    if (last) spmm_store_y<T, VEC>(y, nck, runk);
+                }
+                if (++gc == gs) { gc = 0; ++kvh; }
+            }
         }
     }
 }
 
 // spmm_long_kernel on A^T's long rows (columns of A with more than kSpmmLongThr entries), a workgroup each: per head, first dV's panel, then dK's
-template <typename T, int CW, bool VEC>
+// GROUPED: head hd's panel goes to its K / V block of dvo / dk, stored by the group's first head and added to what the same thread stored there
+// by every other one (long_row_panel's add) -- also across rounds (gpos: the round's first head's place in its group).  Else every head stores.
+template <typename T, int CW, bool VEC, bool GROUPED>
 __global__ __launch_bounds__(kBlock) void attention_bwd_cols_long_kernel(int nlong, const int *__restrict__ longs, const int *__restrict__ rowptr,
                                                                          const int *__restrict__ colidx, const int *__restrict__ perm, int heads, long long plane, int k, int dv,
                                                                          const T *__restrict__ pv, const T *__restrict__ dsv, int kcv, const T *__restrict__ g, long long ldg,
                                                                          T *__restrict__ dvo, long long lddv, int kck, const T *__restrict__ q, long long ldq, T *__restrict__ dk,
-                                                                         long long lddk)
+                                                                         long long lddk, int gs, int gpos)
 {
 #pragma clang fp contract(off)
     constexpr int V = SpmmShape<T>::V, KP = SpmmShape<T>::KP, G = kBlock / CW;
@@ -364,19 +412,28 @@ __global__ __launch_bounds__(kBlock) void attention_bwd_cols_long_kernel(int nlo
     const int tid = (int) threadIdx.x, sub = tid / CW, c0 = (tid % CW) * V;
     for (int i = blockIdx.x; i < nlong; i += gridDim.x) {
         const int r = longs[i], s = rowptr[r], e = rowptr[r + 1];
-        for (int hd = 0; hd < heads; ++hd)
+        [[maybe_unused]] int kvh = 0, gc = gpos;
+        for (int hd = 0; hd < heads; ++hd) {
+            const int hkv = GROUPED ? kvh : hd;
             for (int o = 0; o < 2; ++o) { // 0: dV (values P, X = G); 1: dK (values dS, X = Q)
                 const int kc = o ? kck : kcv;
                 if (kc <= 0) continue; // uniform over the workgroup
                 const T *val = (o ? dsv : pv) + hd * plane, *x = o ? q + (long long) hd * k : g + (long long) hd * dv;
                 const long long ldx = o ? ldq : ldg;
-                T *y = o ? dk + (long long) r * lddk + (long long) hd * k : dvo + (long long) r * lddv + (long long) hd * dv;
-                long_row_panel<T>(e - s, kc, G, sub, c0, tid, part, y, [&](int lo, int hi, int nc, T (&acc)[V]) {
-                    // the global streams of A^T, the values gathered through perm
-                    spmm_chain_with<T, VEC>(
-                        s + lo, s + hi, [=](int j) { return ld_stream(colidx + j); }, [=](int j) { return val[ld_stream(perm + j)]; }, x, ldx, c0, nc, acc);
-                });
+                T *y = o ? dk + (long long) r * lddk + (long long) hkv * k : dvo + (long long) r * lddv + (long long) hkv * dv;
+                long_row_panel<T>(
+                    e - s, kc, G, sub, c0, tid, part, y,
+                    [&](int lo, int hi, int nc, T (&acc)[V]) {
+                        // the global streams of A^T, the values gathered through perm
+                        spmm_chain_with<T, VEC>(
+                            s + lo, s + hi, [=](int j) { return ld_stream(colidx + j); }, [=](int j) { return val[ld_stream(perm + j)]; }, x, ldx, c0, nc, acc);
+                    },
+                    GROUPED && gc > 0);
             }
+            if constexpr (GROUPED) {
+                if (++gc == gs) { gc = 0; ++kvh; }
+            }
+        }
     }
 }
 

@@ -236,9 +236,10 @@ __device__ __forceinline__ T long_row_dot(const T *x, const T *y, int s, int e, 
 // One panel of kc columns of a long row's product: y[c] = sum over the row's len entries of val * X[col][c], c < kc.  The row is cut into
 // kSpmmSegs equal segments; lane group sub (of G groups, its lanes' columns from c0) takes the segments sub, sub + G, .., each one chain from
 // +0 -- chain(lo, hi, nc, acc) runs it over the entries [lo, hi) of the row --, and the partial sums are added left to right through part.
-// Ends with the barrier after which part may be written again.
+// Ends with the barrier after which part may be written again.  add: y[c] = y[c] + sum instead -- one plain addition to what the same thread
+// of an earlier panel call (or launch of the stream) stored there (the grouped column pass: kernels/attention_backward.hpp).
 template <typename T, typename Chain>
-__device__ __forceinline__ void long_row_panel(int len, int kc, int G, int sub, int c0, int tid, T (*part)[SpmmShape<T>::KP], T *y, Chain chain)
+__device__ __forceinline__ void long_row_panel(int len, int kc, int G, int sub, int c0, int tid, T (*part)[SpmmShape<T>::KP], T *y, Chain chain, bool add = false)
 {
 #pragma clang fp contract(off)
     constexpr int V = SpmmShape<T>::V;
@@ -257,7 +258,7 @@ __device__ __forceinline__ void long_row_panel(int len, int kc, int G, int sub, 
     if (tid < kc) {
         T sum = part[0][tid];
         for (int g = 1; g < kSpmmSegs; ++g) sum += part[g][tid];
-        y[tid] = sum;
+        y[tid] = add ? y[tid] + sum : sum;
     }
     __syncthreads();
 }

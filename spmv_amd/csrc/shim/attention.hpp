@@ -1,6 +1,7 @@
 // shim/attention.hpp -- part of spmv_shim.hip: O = softmax_rows(scale * Q K^T on the RESIDENT pattern) V in one pass, for one head
 // (spmv_hip_attention) or for `heads` heads stored side by side in the rows of Q, K, V and O (spmv_hip_attention_heads), with an additive
-// bias per head and entry (spmv_hip_attention_bias: the one entry point the others call with no bias).  The
+// bias per head and entry (spmv_hip_attention_bias) and with fewer K / V heads than query heads (spmv_hip_attention_gqa: the one entry point
+// the others call, with a K / V head per query head and, where they have none, no bias).  The
 // kernels are kernels/attention.hpp, launched from their own translation unit (spmv_attention.hip, attention_launch); the tables are spmm's
 // batch table and long-row list (spmm_plan).  This side adds what the long rows need: where each one parks its scores.
 #pragma once
@@ -56,16 +57,19 @@ static int attention_stage_bias(Stager &stg, StageBuf &b, const void *&bias, lon
     return rc;
 }
 
-// k and dv are one head's widths: Q and K are heads * k columns wide, V and O heads * dv.  bias: NULL, or the planes of spmv_hip_attention_bias
-// (ldb = 0: one plane for all heads; else >= nnz); with NULL, ldb is ignored and the call is spmv_shim_attention_heads.
-extern "C" int spmv_shim_attention_bias(spmv_dev *d, int heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v,
-                                        long long ldv, const void *bias, long long ldb, void *o, long long ldo)
+// k and dv are one head's widths: Q is heads * k columns wide and O heads * dv; K is kv_heads * k and V kv_heads * dv wide, heads a multiple of
+// kv_heads, and query head h reads K / V block h / (heads / kv_heads) (spmv_hip_attention_gqa; kv_heads = heads: a block per head).  bias: NULL,
+// or the planes of spmv_hip_attention_bias, one per QUERY head (ldb = 0: one plane for all heads; else >= nnz); with NULL, ldb is ignored.
+extern "C" int spmv_shim_attention_gqa(spmv_dev *d, int heads, int kv_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
+                                       const void *v, long long ldv, const void *bias, long long ldb, void *o, long long ldo)
 {
     if (!d || !d->built) return fail(SPMV_HIP_E_NOSTATE, "attention: schedule not built");
+    if (kv_heads < 1 || heads < 1 || heads % kv_heads != 0) return fail(SPMV_HIP_E_ARG, "attention: need kv_heads >= 1 and heads a multiple of it (heads = %d, kv_heads = %d)", heads, kv_heads);
     const long long wk = (long long) heads * k, wv = (long long) heads * dv;
-    if (heads < 1 || k < 1 || dv < 1 || wk > INT_MAX || wv > INT_MAX || ldq < wk || ldk < wk || ldv < wv || ldo < wv)
-        return fail(SPMV_HIP_E_ARG, "attention: need heads, k, dv >= 1, heads * k and heads * dv within int, ldq, ldk >= heads * k, ldv, ldo >= heads * dv (heads = %d, k = %d, dv = %d, ld = %lld, %lld, %lld, %lld)",
-                    heads, k, dv, ldq, ldk, ldv, ldo);
+    const long long gk = (long long) kv_heads * k, gv = (long long) kv_heads * dv; // K's and V's widths
+    if (heads < 1 || k < 1 || dv < 1 || wk > INT_MAX || wv > INT_MAX || ldq < wk || ldk < gk || ldv < gv || ldo < wv)
+        return fail(SPMV_HIP_E_ARG, "attention: need heads, k, dv >= 1, heads * k and heads * dv within int, ldq >= heads * k, ldk >= kv_heads * k, ldv >= kv_heads * dv, ldo >= heads * dv (heads = %d, kv_heads = %d, k = %d, dv = %d, ld = %lld, %lld, %lld, %lld)",
+                    heads, kv_heads, k, dv, ldq, ldk, ldv, ldo);
     if (bias && (ldb < 0 || (ldb > 0 && ldb < d->nnz)))
         return fail(SPMV_HIP_E_ARG, "attention: the bias planes need ldb = 0 (one plane for all heads) or ldb >= nnz (ldb = %lld, nnz = %lld)", ldb, d->nnz);
     if (d->nnz == 0) bias = nullptr; // no entry: no bias is read
@@ -81,6 +85,7 @@ extern "C" int spmv_shim_attention_bias(spmv_dev *d, int heads, int k, int dv, d
     AttentionArgs a;
     a.m = d->m;
     a.heads = heads;
+    a.gs = heads / kv_heads;
     a.k = k;
     a.dv = dv;
     a.nb = d->spmm_nb;
@@ -99,8 +104,8 @@ extern "C" int spmv_shim_attention_bias(spmv_dev *d, int heads, int k, int dv, d
     a.o = o; a.ldo = ldo;
     a.bias = bias; a.ldb = bias ? ldb : 0;
     // every row of O gets its heads * dv elements, empty rows their zeros: a staged result is written completely before it is copied back
-    if ((rc = stg.in(d->stage[STAGE_ATT_Q], a.q, a.ldq, (size_t) d->m, (int) wk)) || (rc = stg.in(d->stage[STAGE_ATT_K], a.kk, a.ldk, (size_t) d->n, (int) wk)) ||
-        (rc = stg.in(d->stage[STAGE_ATT_V], a.v, a.ldv, (size_t) d->n, (int) wv)) || (rc = stg.out(d->stage[STAGE_ATT_O], a.o, a.ldo, (size_t) d->m, (int) wv)) ||
+    if ((rc = stg.in(d->stage[STAGE_ATT_Q], a.q, a.ldq, (size_t) d->m, (int) wk)) || (rc = stg.in(d->stage[STAGE_ATT_K], a.kk, a.ldk, (size_t) d->n, (int) gk)) ||
+        (rc = stg.in(d->stage[STAGE_ATT_V], a.v, a.ldv, (size_t) d->n, (int) gv)) || (rc = stg.out(d->stage[STAGE_ATT_O], a.o, a.ldo, (size_t) d->m, (int) wv)) ||
         (a.bias && (rc = attention_stage_bias(stg, d->stage[STAGE_ATT_B], a.bias, a.ldb, heads)))) return rc;
     // the access width changes no bit (kernels/attention.hpp): chosen per call from what the addresses allow -- with more than one head, every
     // head's first column has to be 16-byte aligned as well
@@ -109,6 +114,12 @@ extern "C" int spmv_shim_attention_bias(spmv_dev *d, int heads, int k, int dv, d
     const hipError_t e = attention_launch(a, s == sizeof(double), d->stream);
     if (e != hipSuccess) return fail(SPMV_HIP_E_RUNTIME, "attention: launch: %s", hipGetErrorString(e));
     return stg.finish();
+}
+
+extern "C" int spmv_shim_attention_bias(spmv_dev *d, int heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v,
+                                        long long ldv, const void *bias, long long ldb, void *o, long long ldo)
+{
+    return spmv_shim_attention_gqa(d, heads, heads, k, dv, scale, q, ldq, kk, ldk, v, ldv, bias, ldb, o, ldo);
 }
 
 extern "C" int spmv_shim_attention_heads(spmv_dev *d, int heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v,
@@ -123,15 +134,21 @@ extern "C" int spmv_shim_attention(spmv_dev *d, int k, int dv, double scale, con
     return spmv_shim_attention_heads(d, 1, k, dv, scale, q, ldq, kk, ldk, v, ldv, o, ldo);
 }
 
-extern "C" double spmv_shim_time_attention_bias(spmv_dev *d, int heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v,
-                                                long long ldv, const void *bias, long long ldb, void *o, long long ldo, int warmup, int iters, float *ms_out)
+extern "C" double spmv_shim_time_attention_gqa(spmv_dev *d, int heads, int kv_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
+                                               const void *v, long long ldv, const void *bias, long long ldb, void *o, long long ldo, int warmup, int iters, float *ms_out)
 {
     if (!d || !d->built || iters <= 0) { fail(SPMV_HIP_E_ARG, "time_attention: bad arguments"); return -1.0; }
     if (!is_device_ptr(q) || !is_device_ptr(kk) || !is_device_ptr(v) || !is_device_ptr(o) || (bias && !is_device_ptr(bias))) {
         fail(SPMV_HIP_E_ARG, "time_attention: Q, K, V, O and the bias must be device pointers");
         return -1.0;
     }
-    return time_events(d, "time_attention", warmup, iters, ms_out, [&] { return spmv_shim_attention_bias(d, heads, k, dv, scale, q, ldq, kk, ldk, v, ldv, bias, ldb, o, ldo); });
+    return time_events(d, "time_attention", warmup, iters, ms_out, [&] { return spmv_shim_attention_gqa(d, heads, kv_heads, k, dv, scale, q, ldq, kk, ldk, v, ldv, bias, ldb, o, ldo); });
+}
+
+extern "C" double spmv_shim_time_attention_bias(spmv_dev *d, int heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v,
+                                                long long ldv, const void *bias, long long ldb, void *o, long long ldo, int warmup, int iters, float *ms_out)
+{
+    return spmv_shim_time_attention_gqa(d, heads, heads, k, dv, scale, q, ldq, kk, ldk, v, ldv, bias, ldb, o, ldo, warmup, iters, ms_out);
 }
 
 extern "C" double spmv_shim_time_attention_heads(spmv_dev *d, int heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v,

@@ -32,7 +32,9 @@ static int attention_backward_plan(spmv_dev *d, int planes)
 // heads per round (the planes a call needs): at most `limit` when limit > 0 (option "attention_backward_heads"); limit = 0: the most for which
 // the two arrays, 2 * hg * s * nnz bytes, stay within an eighth of the device's memory -- the pool's default share (pool_cap), used as a bound
 // on memory, not as a measured optimum; one head at the least.  Changes no bit: only memory and the number of rounds.
-static int attention_backward_group(const spmv_dev *d, int heads, int limit)
+// gs (query heads per K / V head): the default is rounded down to a multiple of gs when it is at least gs, so that no round of the default path
+// starts inside a group (the column pass then never reads dK / dV back); an explicit limit is taken as it is.
+static int attention_backward_group(const spmv_dev *d, int heads, int limit, int gs = 1)
 {
     if (limit > 0) return heads < limit ? heads : limit;
     static long long eighth = -1; // of the first device asked about: the devices of one process are alike
@@ -43,7 +45,8 @@ static int attention_backward_group(const spmv_dev *d, int heads, int limit)
     }
     const long long per_head = 2 * (long long) d->vsize * d->nnz;
     const long long fit = per_head > 0 ? eighth / per_head : heads;
-    return fit >= heads ? heads : (fit < 1 ? 1 : (int) fit);
+    const int hg = fit >= heads ? heads : (fit < 1 ? 1 : (int) fit);
+    return hg >= gs ? hg - hg % gs : hg;
 }
 
 // k and dv are one head's widths: Q, K, dq, dk are heads * k columns wide, V, G, dvo heads * dv.  dq / dk / dvo: NULL = not wanted.  When dk or
@@ -51,17 +54,22 @@ static int attention_backward_group(const spmv_dev *d, int heads, int limit)
 // its values are not read.  max_heads: option "attention_backward_heads" (0 = by the memory rule).  bias: NULL or the forward call's planes
 // (ldb = 0: one plane for all heads; else >= nnz); db: NULL = not wanted, else `heads` planes lddb >= nnz apart, written by the row pass alone --
 // with only db wanted the column pass does not run and the transpose is not looked at.  With bias and db NULL this is
-// spmv_shim_attention_heads_backward.
-extern "C" int spmv_shim_attention_bias_backward(spmv_dev *d, int heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
+// spmv_shim_attention_heads_backward.  kv_heads: K, V, dk and dvo are kv_heads * k / kv_heads * dv wide, heads a multiple of kv_heads, query head
+// h belongs to block h / (heads / kv_heads), and dk / dvo of a block are the sums of its heads' terms in ascending head
+// (spmv_hip_attention_gqa_backward); the planes, bias and db stay per QUERY head.  kv_heads = heads is spmv_hip_attention_bias_backward.
+extern "C" int spmv_shim_attention_gqa_backward(spmv_dev *d, int heads, int kv_heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
                                                  const void *v, long long ldv, const void *bias, long long ldb, const void *g, long long ldg, void *dq, long long lddq, void *dk,
                                                  long long lddk, void *dvo, long long lddv, void *db, long long lddb)
 {
     if (!d || !d->built) return fail(SPMV_HIP_E_NOSTATE, "attention_backward: schedule not built");
+    if (kv_heads < 1 || heads < 1 || heads % kv_heads != 0)
+        return fail(SPMV_HIP_E_ARG, "attention_backward: need kv_heads >= 1 and heads a multiple of it (heads = %d, kv_heads = %d)", heads, kv_heads);
     const long long wk = (long long) heads * k, wv = (long long) heads * dv;
-    if (heads < 1 || k < 1 || dv < 1 || wk > INT_MAX || wv > INT_MAX || max_heads < 0 || ldq < wk || ldk < wk || ldv < wv || ldg < wv || (dq && lddq < wk) || (dk && lddk < wk) ||
-        (dvo && lddv < wv))
-        return fail(SPMV_HIP_E_ARG, "attention_backward: need heads, k, dv >= 1, heads * k and heads * dv within int, ldq, ldk >= heads * k, ldv, ldg >= heads * dv, lddq, lddk >= heads * k, lddv >= heads * dv (heads = %d, k = %d, dv = %d)",
-                    heads, k, dv);
+    const long long gk = (long long) kv_heads * k, gv = (long long) kv_heads * dv; // the widths of K and dK, of V and dV
+    if (heads < 1 || k < 1 || dv < 1 || wk > INT_MAX || wv > INT_MAX || max_heads < 0 || ldq < wk || ldk < gk || ldv < gv || ldg < wv || (dq && lddq < wk) || (dk && lddk < gk) ||
+        (dvo && lddv < gv))
+        return fail(SPMV_HIP_E_ARG, "attention_backward: need heads, k, dv >= 1, heads * k and heads * dv within int, ldq >= heads * k, ldk >= kv_heads * k, ldv >= kv_heads * dv, ldg >= heads * dv, lddq >= heads * k, lddk >= kv_heads * k, lddv >= kv_heads * dv (heads = %d, kv_heads = %d, k = %d, dv = %d)",
+                    heads, kv_heads, k, dv);
     if (d->m > 0 && (!q || !kk || !v || !g)) return fail(SPMV_HIP_E_ARG, "attention_backward: Q, K, V or G is NULL");
     if ((bias && (ldb < 0 || (ldb > 0 && ldb < d->nnz))) || (db && lddb < d->nnz))
         return fail(SPMV_HIP_E_ARG, "attention_backward: the bias planes need ldb = 0 (one plane for all heads) or ldb >= nnz, those of dB lddb >= nnz (ldb = %lld, lddb = %lld, nnz = %lld)",
@@ -76,7 +84,7 @@ extern "C" int spmv_shim_attention_bias_backward(spmv_dev *d, int heads, int max
     DeviceGuard guard(d->device);
     if (!guard.ok) return fail(SPMV_HIP_E_RUNTIME, "hipSetDevice(%d) failed", d->device);
     int rc;
-    const int hg = attention_backward_group(d, heads, max_heads);
+    const int hg = attention_backward_group(d, heads, max_heads, heads / kv_heads);
     if ((rc = spmm_plan(d)) || (rc = attention_backward_plan(d, hg)) || (cols && (rc = spmm_plan(t)))) return rc;
     const size_t s = d->vsize;
     Stager stg{d};
@@ -84,6 +92,7 @@ extern "C" int spmv_shim_attention_bias_backward(spmv_dev *d, int heads, int max
     a.m = d->m;
     a.heads = heads;
     a.hg = hg;
+    a.gs = heads / kv_heads;
     a.plane = d->nnz;
     a.k = k;
     a.dv = dv;
@@ -117,10 +126,10 @@ extern "C" int spmv_shim_attention_bias_backward(spmv_dev *d, int heads, int max
     a.bias = bias; a.ldb = bias ? ldb : 0;
     a.db = db; a.lddb = lddb;
     // every row of a wanted output gets its elements, empty rows and columns their zeros: a staged result is written completely before it is copied back
-    if ((rc = stg.in(d->stage[STAGE_ATTB_Q], a.q, a.ldq, (size_t) d->m, (int) wk)) || (rc = stg.in(d->stage[STAGE_ATTB_K], a.kk, a.ldk, (size_t) d->n, (int) wk)) ||
-        (rc = stg.in(d->stage[STAGE_ATTB_V], a.v, a.ldv, (size_t) d->n, (int) wv)) || (rc = stg.in(d->stage[STAGE_ATTB_G], a.g, a.ldg, (size_t) d->m, (int) wv)) ||
-        (a.dq && (rc = stg.out(d->stage[STAGE_ATTB_DQ], a.dq, a.lddq, (size_t) d->m, (int) wk))) || (a.dk && (rc = stg.out(d->stage[STAGE_ATTB_DK], a.dk, a.lddk, (size_t) d->n, (int) wk))) ||
-        (a.dvo && (rc = stg.out(d->stage[STAGE_ATTB_DV], a.dvo, a.lddv, (size_t) d->n, (int) wv))) ||
+    if ((rc = stg.in(d->stage[STAGE_ATTB_Q], a.q, a.ldq, (size_t) d->m, (int) wk)) || (rc = stg.in(d->stage[STAGE_ATTB_K], a.kk, a.ldk, (size_t) d->n, (int) gk)) ||
+        (rc = stg.in(d->stage[STAGE_ATTB_V], a.v, a.ldv, (size_t) d->n, (int) gv)) || (rc = stg.in(d->stage[STAGE_ATTB_G], a.g, a.ldg, (size_t) d->m, (int) wv)) ||
+        (a.dq && (rc = stg.out(d->stage[STAGE_ATTB_DQ], a.dq, a.lddq, (size_t) d->m, (int) wk))) || (a.dk && (rc = stg.out(d->stage[STAGE_ATTB_DK], a.dk, a.lddk, (size_t) d->n, (int) gk))) ||
+        (a.dvo && (rc = stg.out(d->stage[STAGE_ATTB_DV], a.dvo, a.lddv, (size_t) d->n, (int) gv))) ||
         (a.bias && (rc = attention_stage_bias(stg, d->stage[STAGE_ATT_B], a.bias, a.ldb, heads))) ||
         (a.db && (rc = stg.out(d->stage[STAGE_ATT_DB], a.db, a.lddb, (size_t) heads, (int) d->nnz)))) return rc; // every entry of every plane is written
     // the access width changes no bit (kernels/attention_backward.hpp): chosen per call from what the addresses allow -- with more than one head,
@@ -130,6 +139,13 @@ extern "C" int spmv_shim_attention_bias_backward(spmv_dev *d, int heads, int max
     const hipError_t e = attention_backward_launch(a, s == sizeof(double), d->stream);
     if (e != hipSuccess) return fail(SPMV_HIP_E_RUNTIME, "attention_backward: launch: %s", hipGetErrorString(e));
     return stg.finish();
+}
+
+extern "C" int spmv_shim_attention_bias_backward(spmv_dev *d, int heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
+                                                 const void *v, long long ldv, const void *bias, long long ldb, const void *g, long long ldg, void *dq, long long lddq, void *dk,
+                                                 long long lddk, void *dvo, long long lddv, void *db, long long lddb)
+{
+    return spmv_shim_attention_gqa_backward(d, heads, heads, max_heads, k, dv, scale, q, ldq, kk, ldk, v, ldv, bias, ldb, g, ldg, dq, lddq, dk, lddk, dvo, lddv, db, lddb);
 }
 
 extern "C" int spmv_shim_attention_heads_backward(spmv_dev *d, int heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
@@ -145,7 +161,7 @@ extern "C" int spmv_shim_attention_backward(spmv_dev *d, int k, int dv, double s
     return spmv_shim_attention_heads_backward(d, 1, 0, k, dv, scale, q, ldq, kk, ldk, v, ldv, g, ldg, dq, lddq, dk, lddk, dvo, lddv);
 }
 
-extern "C" double spmv_shim_time_attention_bias_backward(spmv_dev *d, int heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk,
+extern "C" double spmv_shim_time_attention_gqa_backward(spmv_dev *d, int heads, int kv_heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk,
                                                          long long ldk, const void *v, long long ldv, const void *bias, long long ldb, const void *g, long long ldg, void *dq,
                                                          long long lddq, void *dk, long long lddk, void *dvo, long long lddv, void *db, long long lddb, int warmup, int iters,
                                                          float *ms_out)
@@ -157,8 +173,17 @@ extern "C" double spmv_shim_time_attention_bias_backward(spmv_dev *d, int heads,
         return -1.0;
     }
     return time_events(d, "time_attention_backward", warmup, iters, ms_out, [&] {
-        return spmv_shim_attention_bias_backward(d, heads, max_heads, k, dv, scale, q, ldq, kk, ldk, v, ldv, bias, ldb, g, ldg, dq, lddq, dk, lddk, dvo, lddv, db, lddb);
+        return spmv_shim_attention_gqa_backward(d, heads, kv_heads, max_heads, k, dv, scale, q, ldq, kk, ldk, v, ldv, bias, ldb, g, ldg, dq, lddq, dk, lddk, dvo, lddv, db, lddb);
     });
+}
+
+extern "C" double spmv_shim_time_attention_bias_backward(spmv_dev *d, int heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk,
+                                                         long long ldk, const void *v, long long ldv, const void *bias, long long ldb, const void *g, long long ldg, void *dq,
+                                                         long long lddq, void *dk, long long lddk, void *dvo, long long lddv, void *db, long long lddb, int warmup, int iters,
+                                                         float *ms_out)
+{
+    return spmv_shim_time_attention_gqa_backward(d, heads, heads, max_heads, k, dv, scale, q, ldq, kk, ldk, v, ldv, bias, ldb, g, ldg, dq, lddq, dk, lddk, dvo, lddv, db, lddb,
+                                                 warmup, iters, ms_out);
 }
 
 extern "C" double spmv_shim_time_attention_heads_backward(spmv_dev *d, int heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk,

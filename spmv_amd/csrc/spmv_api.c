@@ -1247,3 +1247,94 @@ double spmv_hip_time_attention_bias_backward_launches(spmv_Handle_t h, int heads
     return report_time(spmv_shim_time_attention_bias_backward(st->dev, heads, (int) st->opts.v[SPMV_OPT_ATTENTION_BACKWARD_HEADS], k, dv, scale, Q, ldq, K, ldk, V, ldv, B, ldb,
                                                               G, ldg, dQ, lddq, dK, lddk, dV, lddv, dB, lddb, warmup, iters, ms_out), where);
 }
+
+/* ---------------------------------------------------------------- the bias calls with kv_heads K / V heads for heads query heads (GQA, MQA) */
+static int attention_gqa_args(spmv_Handle_t h, const char *where, int heads, int kv_heads, int k, int dv, const void *Q, long long ldq, const void *K, long long ldk,
+                              const void *V, long long ldv, const void *O, long long ldo, int m)
+{
+    if (!h) return refuse(SPMV_HIP_E_ARG, where, "handle is NULL");
+    if (heads < 1 || kv_heads < 1 || k < 1 || dv < 1) return refuse(SPMV_HIP_E_ARG, where, "need heads >= 1, kv_heads >= 1, k >= 1 and dv >= 1");
+    if (heads % kv_heads != 0) return refuse(SPMV_HIP_E_ARG, where, "heads must be a multiple of kv_heads");
+    if ((long long) heads * k > INT_MAX || (long long) heads * dv > INT_MAX || (long long) kv_heads * k > INT_MAX || (long long) kv_heads * dv > INT_MAX)
+        return refuse(SPMV_HIP_E_ARG, where, "heads * k, heads * dv, kv_heads * k or kv_heads * dv does not fit an int");
+    if (ldq < (long long) heads * k || ldk < (long long) kv_heads * k || ldv < (long long) kv_heads * dv || ldo < (long long) heads * dv)
+        return refuse(SPMV_HIP_E_ARG, where, "need ldq >= heads * k, ldk >= kv_heads * k, ldv >= kv_heads * dv and ldo >= heads * dv");
+    if (m > 0 && (!Q || !K || !V || !O)) return refuse(SPMV_HIP_E_ARG, where, "Q, K, V or O is NULL");
+    return SPMV_HIP_OK;
+}
+
+int spmv_hip_attention_gqa(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                           const void *Matrix_Val, int heads, int kv_heads, int k, int dv, double scale,
+                           const void *Q, long long ldq, const void *K, long long ldk, const void *V, long long ldv,
+                           const void *B, long long ldb, void *O, long long ldo)
+{
+    const char *where = "attention_gqa";
+    spmv_hip_state *st;
+    int rc;
+    if ((rc = attention_gqa_args(handle, where, heads, kv_heads, k, dv, Q, ldq, K, ldk, V, ldv, O, ldo, m))) return rc;
+    if (B && ldb < 0) return refuse(SPMV_HIP_E_ARG, where, "need ldb >= 0");
+    if ((rc = resident_prologue(handle, where, RESIDENT_NOT_REORDERED, m, RowPtr, ColIdx, Matrix_Val, &st)) || (rc = spmm_columns(handle, st, where))) return rc;
+    return report(spmv_shim_attention_gqa(st->dev, heads, kv_heads, k, dv, scale, Q, ldq, K, ldk, V, ldv, B, ldb, O, ldo), where); /* 0 < ldb < nnz: refused there, nothing written */
+}
+
+double spmv_hip_time_attention_gqa_launches(spmv_Handle_t h, int heads, int kv_heads, int k, int dv, double scale, const void *Q, long long ldq, const void *K, long long ldk,
+                                            const void *V, long long ldv, const void *B, long long ldb, void *O, long long ldo, int warmup, int iters, float *ms_out)
+{
+    const char *where = "time_attention_gqa_launches";
+    spmv_hip_state *st;
+    if (attention_gqa_args(h, where, heads, kv_heads, k, dv, Q, ldq, K, ldk, V, ldv, O, ldo, 1)) return -1.0;
+    if (B && ldb < 0) { (void) refuse(SPMV_HIP_E_ARG, where, "need ldb >= 0"); return -1.0; }
+    if (resident_state(h, where, RESIDENT_NOT_REORDERED, &st) || spmm_columns(h, st, where)) return -1.0;
+    return report_time(spmv_shim_time_attention_gqa(st->dev, heads, kv_heads, k, dv, scale, Q, ldq, K, ldk, V, ldv, B, ldb, O, ldo, warmup, iters, ms_out), where);
+}
+
+static int attention_gqa_backward_args(spmv_Handle_t h, const char *where, int heads, int kv_heads, int k, int dv, const void *Q, long long ldq, const void *K, long long ldk,
+                                       const void *V, long long ldv, const void *G, long long ldg, const void *dQ, long long lddq, const void *dK, long long lddk,
+                                       const void *dV, long long lddv, int m)
+{
+    long long wk, wv, gk, gv;
+    if (!h) return refuse(SPMV_HIP_E_ARG, where, "handle is NULL");
+    if (heads < 1 || kv_heads < 1 || k < 1 || dv < 1) return refuse(SPMV_HIP_E_ARG, where, "need heads >= 1, kv_heads >= 1, k >= 1 and dv >= 1");
+    if (heads % kv_heads != 0) return refuse(SPMV_HIP_E_ARG, where, "heads must be a multiple of kv_heads");
+    wk = (long long) heads * k;
+    wv = (long long) heads * dv;
+    gk = (long long) kv_heads * k;
+    gv = (long long) kv_heads * dv;
+    if (wk > INT_MAX || wv > INT_MAX || gk > INT_MAX || gv > INT_MAX) return refuse(SPMV_HIP_E_ARG, where, "heads * k, heads * dv, kv_heads * k or kv_heads * dv does not fit an int");
+    if (ldq < wk || ldk < gk || ldv < gv || ldg < wv || (dQ && lddq < wk) || (dK && lddk < gk) || (dV && lddv < gv))
+        return refuse(SPMV_HIP_E_ARG, where, "need ldq >= heads * k, ldk >= kv_heads * k, ldv >= kv_heads * dv, ldg >= heads * dv and, for the requested outputs, lddq >= heads * k, lddk >= kv_heads * k, lddv >= kv_heads * dv");
+    if (m > 0 && (!Q || !K || !V || !G)) return refuse(SPMV_HIP_E_ARG, where, "Q, K, V or G is NULL");
+    return SPMV_HIP_OK;
+}
+
+int spmv_hip_attention_gqa_backward(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                                    const void *Matrix_Val, int heads, int kv_heads, int k, int dv, double scale,
+                                    const void *Q, long long ldq, const void *K, long long ldk, const void *V, long long ldv,
+                                    const void *B, long long ldb, const void *G, long long ldg, void *dQ, long long lddq, void *dK, long long lddk,
+                                    void *dV, long long lddv, void *dB, long long lddb)
+{
+    const char *where = "attention_gqa_backward";
+    spmv_hip_state *st;
+    int rc;
+    if ((rc = attention_gqa_backward_args(handle, where, heads, kv_heads, k, dv, Q, ldq, K, ldk, V, ldv, G, ldg, dQ, lddq, dK, lddk, dV, lddv, m))) return rc;
+    if ((B && ldb < 0) || (dB && lddb < 0)) return refuse(SPMV_HIP_E_ARG, where, "need ldb >= 0 and lddb >= 0");
+    if (!dQ && !dK && !dV && !dB) return SPMV_HIP_OK; /* nothing wanted: no work, the handle's state is not looked at */
+    if ((rc = resident_prologue(handle, where, RESIDENT_NOT_REORDERED, m, RowPtr, ColIdx, Matrix_Val, &st))) return rc;
+    if ((rc = attention_backward_tables(handle, st, where, dK || dV))) return rc; /* only dB (or dQ) wanted: no transpose */
+    return report(spmv_shim_attention_gqa_backward(st->dev, heads, kv_heads, (int) st->opts.v[SPMV_OPT_ATTENTION_BACKWARD_HEADS], k, dv, scale, Q, ldq, K, ldk, V, ldv, B, ldb, G,
+                                                   ldg, dQ, lddq, dK, lddk, dV, lddv, dB, lddb), where); /* a plane stride below nnz: refused there, nothing written */
+}
+
+double spmv_hip_time_attention_gqa_backward_launches(spmv_Handle_t h, int heads, int kv_heads, int k, int dv, double scale, const void *Q, long long ldq, const void *K,
+                                                     long long ldk, const void *V, long long ldv, const void *B, long long ldb, const void *G, long long ldg, void *dQ,
+                                                     long long lddq, void *dK, long long lddk, void *dV, long long lddv, void *dB, long long lddb, int warmup, int iters,
+                                                     float *ms_out)
+{
+    const char *where = "time_attention_gqa_backward_launches";
+    spmv_hip_state *st;
+    if (attention_gqa_backward_args(h, where, heads, kv_heads, k, dv, Q, ldq, K, ldk, V, ldv, G, ldg, dQ, lddq, dK, lddk, dV, lddv, 1)) return -1.0;
+    if ((B && ldb < 0) || (dB && lddb < 0)) { (void) refuse(SPMV_HIP_E_ARG, where, "need ldb >= 0 and lddb >= 0"); return -1.0; }
+    if (resident_state(h, where, RESIDENT_NOT_REORDERED, &st) || attention_backward_tables(h, st, where, dK || dV)) return -1.0;
+    return report_time(spmv_shim_time_attention_gqa_backward(st->dev, heads, kv_heads, (int) st->opts.v[SPMV_OPT_ATTENTION_BACKWARD_HEADS], k, dv, scale, Q, ldq, K, ldk, V, ldv, B,
+                                                             ldb, G, ldg, dQ, lddq, dK, lddk, dV, lddv, dB, lddb, warmup, iters, ms_out), where);
+}

@@ -8,22 +8,23 @@
 
 namespace spmv {
 
-template <typename T, int CW, bool VEC, bool BIAS>
+template <typename T, int CW, bool VEC, bool BIAS, bool GROUPED>
 static void attention_launch_cw(const AttentionArgs &a, hipStream_t stream)
 {
     constexpr int waves = kBlock / kWave;
     const int lgv = panel_group_lg<T>(a.dv); // the narrowest lane group that covers a panel's columns of one head (spmm's rule; it changes no bit)
     const T scale = (T) a.scale;
+    const int gs = a.gs < 1 ? 1 : a.gs;
     const T *q = (const T *) a.q, *kk = (const T *) a.kk, *v = (const T *) a.v;
     T *o = (T *) a.o;
     const T *bias = (const T *) a.bias;
     if (a.nb > 0)
-        attention_rows_kernel<T, CW, VEC, BIAS><<<(a.nb + waves - 1) / waves, kBlock, 0, stream>>>(a.nb, a.split, a.rowptr, a.colidx, a.heads, a.k, a.dv, lgv, scale, q, a.ldq, kk, a.ldk,
-                                                                                                 v, a.ldv, o, a.ldo, bias, a.ldb);
+        attention_rows_kernel<T, CW, VEC, BIAS, GROUPED><<<(a.nb + waves - 1) / waves, kBlock, 0, stream>>>(a.nb, a.split, a.rowptr, a.colidx, a.heads, a.k, a.dv, lgv, scale, q, a.ldq, kk, a.ldk,
+                                                                                                 v, a.ldv, o, a.ldo, bias, a.ldb, gs);
     if (a.nlong > 0)
-        attention_long_kernel<T, CW, VEC, BIAS><<<a.nlong < a.cus * 8 ? a.nlong : a.cus * 8, kBlock, 0, stream>>>(a.nlong, a.longs, a.long_off, a.rowptr, a.colidx, a.heads, a.k, a.dv,
+        attention_long_kernel<T, CW, VEC, BIAS, GROUPED><<<a.nlong < a.cus * 8 ? a.nlong : a.cus * 8, kBlock, 0, stream>>>(a.nlong, a.longs, a.long_off, a.rowptr, a.colidx, a.heads, a.k, a.dv,
                                                                                                                 lgv, scale, q, a.ldq, kk, a.ldk, v, a.ldv, o, a.ldo, (T *) a.park, bias,
-                                                                                                                a.ldb);
+                                                                                                                a.ldb, gs);
 }
 
 hipError_t attention_launch(const AttentionArgs &a, bool f64, hipStream_t stream)
@@ -34,8 +35,16 @@ hipError_t attention_launch(const AttentionArgs &a, bool f64, hipStream_t stream
         // sddmm's lane group for k: a function of k and the value type alone, it fixes the scores' summation order
         // a bias has instantiations of its own: without one, the kernels are the code without the bias's loads and addition
         with_width(panel_group_width<T>(a.k), [&](auto CW) {
-            if (a.bias) attention_launch_cw<T, decltype(CW)::value, decltype(vec)::value, true>(a, stream);
-            else attention_launch_cw<T, decltype(CW)::value, decltype(vec)::value, false>(a, stream);
+            // so have grouped heads (gs > 1): without them, the kernels do not know the groups' counter either
+            constexpr int cw = decltype(CW)::value;
+            constexpr bool vc = decltype(vec)::value;
+            if (a.gs > 1) {
+                if (a.bias) attention_launch_cw<T, cw, vc, true, true>(a, stream);
+                else attention_launch_cw<T, cw, vc, false, true>(a, stream);
+            } else {
+                if (a.bias) attention_launch_cw<T, cw, vc, true, false>(a, stream);
+                else attention_launch_cw<T, cw, vc, false, false>(a, stream);
+            }
         });
     });
     return hipGetLastError();

@@ -156,6 +156,13 @@ int spmv_shim_attention_bias(spmv_dev *d, int heads, int k, int dv, double scale
 double spmv_shim_time_attention_bias(spmv_dev *d, int heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v,
                                      long long ldv, const void *bias, long long ldb, void *o, long long ldo, int warmup, int iters, float *ms_out);
 
+/* fewer K / V heads than query heads (spmv_hip_attention_gqa): K is kv_heads * k and V kv_heads * dv wide, heads % kv_heads == 0, query head h reads
+ * block h / (heads / kv_heads); bias as above, a plane per QUERY head.  kv_heads = heads is spmv_shim_attention_bias */
+int spmv_shim_attention_gqa(spmv_dev *d, int heads, int kv_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v,
+                            long long ldv, const void *bias, long long ldb, void *o, long long ldo);
+double spmv_shim_time_attention_gqa(spmv_dev *d, int heads, int kv_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
+                                    const void *v, long long ldv, const void *bias, long long ldb, void *o, long long ldo, int warmup, int iters, float *ms_out);
+
 /* ---- dQ, dK, dV of the fused attention in two passes (shim/attention_backward.hpp; spmv_hip_attention_backward) ----
  * Q m x k, K n x k, V n x dv, G m x dv; dq m x k, dk n x k, dv_out n x dv or NULL (not wanted); row-major with leading dimensions; host or
  * device pointers each.  Needs the resident ColIdx and, when dk or dv_out is wanted, the attached transpose with its column indices resident
@@ -188,6 +195,16 @@ int spmv_shim_attention_bias_backward(spmv_dev *d, int heads, int max_heads, int
 double spmv_shim_time_attention_bias_backward(spmv_dev *d, int heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
                                               const void *v, long long ldv, const void *bias, long long ldb, const void *g, long long ldg, void *dq, long long lddq, void *dk,
                                               long long lddk, void *dv_out, long long lddv, void *db, long long lddb, int warmup, int iters, float *ms_out);
+
+/* with kv_heads K / V heads (spmv_hip_attention_gqa_backward): K, V, dk and dv_out are kv_heads blocks wide, dk / dv_out of a block the sum of its
+ * query heads' terms in ascending head; bias and db a plane per QUERY head.  kv_heads = heads is spmv_shim_attention_bias_backward */
+int spmv_shim_attention_gqa_backward(spmv_dev *d, int heads, int kv_heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk,
+                                     long long ldk, const void *v, long long ldv, const void *bias, long long ldb, const void *g, long long ldg, void *dq, long long lddq,
+                                     void *dk, long long lddk, void *dv_out, long long lddv, void *db, long long lddb);
+double spmv_shim_time_attention_gqa_backward(spmv_dev *d, int heads, int kv_heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk,
+                                             long long ldk, const void *v, long long ldv, const void *bias, long long ldb, const void *g, long long ldg, void *dq,
+                                             long long lddq, void *dk, long long lddk, void *dv_out, long long lddv, void *db, long long lddb, int warmup, int iters,
+                                             float *ms_out);
 
 /* the resident CSR arrays (device pointers; ColIdx may be NULL after spmv_shim_release_columns) */
 void spmv_shim_matrix_arrays(const spmv_dev *d, const int **rowptr, const int **colidx, const void **val);
