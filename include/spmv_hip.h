@@ -446,6 +446,81 @@ int spmv_hip_attention_gqa_backward(spmv_Handle_t handle, BASIC_INT_TYPE m, cons
                                     void *dV, long long lddv,                /* n x kv_heads*dv, or NULL */
                                     void *dB, long long lddb);               /* heads planes of nnz, or NULL */
 
+/* ---- the row log-sum-exp out of the forward: attention over a key / value set behind SEVERAL handles ------------------------
+ * spmv_hip_attention_gqa with one more output: L holds `heads` planes, L[h*ldl + i] = M_i + log(Z_i) of query head h on row i, ldl >= m, in the
+ * handle's precision, host or device pointer.  With L, partial results over disjoint parts of a key / value set (a local-window handle plus a
+ * global-token handle, a context cut into key blocks, a pattern too large for one int CSR, a cache that grows between calls) are merged by
+ * spmv_hip_attention_merge, and the gradients of each part come from spmv_hip_attention_gqa_backward_lse.
+ *   - M_i and Z_i are EXACTLY the values the row softmax of step 3 computes, in its order; log / logf is the device math library's (not a fast
+ *     intrinsic) and the addition is one plain addition; nothing is contracted.  O has exactly the bits spmv_hip_attention_gqa writes.
+ *   - A row without entries: L = -inf (its O row is +0 as before).  A row that is NaN in O (a NaN or +inf in its scores, all scores -inf) is NaN in
+ *     L, for that head and row only.
+ *   - L == NULL: ldl is ignored and the call IS spmv_hip_attention_gqa, to the bit and to the launch.
+ *   - Writes: exactly the first m elements of each of the `heads` planes; the padding between planes is never read or written.  nnz == 0
+ *     writes the -inf values; m == 0 writes nothing.
+ *   - L is a function of the matrix, k, the value type, the inputs and B alone: not of leading dimensions, alignment, access width, pointer kind,
+ *     method, stream or async.  Head h of an H-head call has the bits of the one-head call on its slices.
+ *   - Memory: a host L is staged through one more handle-owned buffer (counted in spmv_hip_info.device_bytes, freed with the others); with device
+ *     operands device_bytes is spmv_hip_attention_gqa's.
+ *   - Errors: spmv_hip_attention_gqa's, and L != NULL with ldl < m with them (SPMV_HIP_E_ARG before the handle's state is looked at, O and L
+ *     untouched).  Handle kinds and SPMV_HIP_E_NOSTATE as there. */
+int spmv_hip_attention_gqa_lse(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                               const void *Matrix_Val, int heads, int kv_heads, int k, int dv, double scale,
+                               const void *Q, long long ldq, const void *K, long long ldk, const void *V, long long ldv,
+                               const void *B, long long ldb,            /* `heads` bias planes, one shared plane, or NULL */
+                               void *O, long long ldo,                  /* m x heads*dv */
+                               void *L, long long ldl);                 /* heads planes of m, or NULL: spmv_hip_attention_gqa */
+
+/* ---- two partial attention results combined by their log-sum-exps ---------------------------------------
+ * m is the handle's; the matrix is NOT read (the handle gives m, the precision, the stream and async setting, the pointer rule and the staging).
+ * O1, O2 and O are m x heads*dv, L1, L2 and L `heads` planes of m.  Per row i and head h, in the handle's precision, nothing contracted but the
+ * one fma written here, exp and log the device library's:
+ *     Lm  = max(L1, L2)                      (fmax: drops a NaN; the exp restores it)
+ *     w1  = exp(L1 - Lm),  w2 = exp(L2 - Lm),  W = w1 + w2
+ *     O_c = fma(w2, O2_c, w1 * O1_c) / W,   c < dv
+ *     L   = Lm + log(W)
+ *   - Lm == -inf (both parts empty on that row): O = +0 and L = -inf.  A part that is empty on a row (L = -inf, O = 0) leaves the other part's
+ *     O values and L bits.  A NaN in either L makes that head's row NaN in O and L, and no other.
+ *   - O may be the very pointer O1 and L the very pointer L1: a running accumulator that parts are folded into from left to right (every element
+ *     is read and written by the same thread).  Any other overlap is undefined.  L == NULL: the merged log-sum-exp is not wanted.
+ *   - One grid-stride launch, bandwidth-bound; 16-byte accesses when O1, O2 and O allow them (and dv is a multiple of 16 bytes when heads > 1);
+ *     the width, the pointer kinds and the leading dimensions change no bit.  Exactly m x heads*dv elements of O and m per plane of L are written.
+ *   - Memory: host operands go through six more handle-owned buffers (counted in device_bytes, freed with the others); device operands: nothing.
+ *   - Errors (SPMV_HIP_E_ARG before the handle's state is looked at, outputs untouched): a NULL handle; heads or dv < 1; heads*dv beyond int; ldo1,
+ *     ldo2 or ldo < heads*dv; a negative ldl*.  Once m is known (outputs untouched): ldl1, ldl2 or (with an L) ldl < m; a NULL O1, L1, O2, L2 or O
+ *     while m > 0.  Multi-GPU, host_rows and "reorder" handles: SPMV_HIP_E_ARG.  A cleared or failed handle: SPMV_HIP_E_NOSTATE. */
+int spmv_hip_attention_merge(spmv_Handle_t handle, int heads, int dv,
+                             const void *O1, long long ldo1, const void *L1, long long ldl1,
+                             const void *O2, long long ldo2, const void *L2, long long ldl2,
+                             void *O, long long ldo,                    /* m x heads*dv; may be O1 */
+                             void *L, long long ldl);                   /* heads planes of m; may be L1; or NULL */
+
+/* ---- the gradients of one part, driven by the FINAL output and log-sum-exp ----------------------------------
+ * spmv_hip_attention_gqa_backward with four more inputs: O (m x heads*dv, ldo) and L (`heads` planes of m, ldl >= m) hold the final output and
+ * log-sum-exp of the attention this handle's entries are a part of -- for a single handle its own spmv_hip_attention_gqa_lse results, for parts
+ * the merged ones.  The steps that differ:
+ *     t_p as in the forward, bias included;   P_p = exp(t_p - L_i)   -- one subtraction and one exp: no maximum, no sum, no division --
+ *     D_i = <G[i, h*dv .. +dv), O[i, h*dv .. +dv)>   in spmv_hip_sddmm's order for dv columns, once per row and head;
+ * dP_p, dB_p = P_p * (dP_p - D_i), dS_p = dB_p * scale, dQ, dK, dV and the group sums of dK / dV are exactly spmv_hip_attention_gqa_backward's,
+ * and so are the NULL-output rules, "only dB wanted runs no column pass", option "attention_backward_heads" changing no bit, and the column
+ * pass with its transpose.  The parts' dQ are the caller's to add; dK, dV and dB are each part's own.
+ *   - A row whose L_i is NaN gives NaN in its head's dQ row and dB entries and in the dK / dV rows it reaches (the K / V head of its group only).
+ *   - An L inconsistent with the scores (smaller than the row's true log-sum-exp) gives meaningless values, never a fault.
+ *   - Memory: a host O / L is staged through two more handle-owned buffers; with device operands device_bytes is spmv_hip_attention_gqa_backward's.
+ *   - Errors: spmv_hip_attention_gqa_backward's, and ldo < heads*dv, ldl < m, a NULL O or L while m > 0 with them (SPMV_HIP_E_ARG before the
+ *     handle's state is looked at, every output untouched). */
+int spmv_hip_attention_gqa_backward_lse(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                                        const void *Matrix_Val, int heads, int kv_heads, int k, int dv, double scale,
+                                        const void *Q, long long ldq, const void *K, long long ldk, const void *V, long long ldv,
+                                        const void *B, long long ldb,            /* bias planes, or NULL */
+                                        const void *G, long long ldg,            /* dL/dO, m x heads*dv */
+                                        const void *O, long long ldo,            /* the final output, m x heads*dv */
+                                        const void *L, long long ldl,            /* the final log-sum-exp, heads planes of m */
+                                        void *dQ, long long lddq,                /* m x heads*k,     or NULL: not wanted */
+                                        void *dK, long long lddk,                /* n x kv_heads*k,  or NULL */
+                                        void *dV, long long lddv,                /* n x kv_heads*dv, or NULL */
+                                        void *dB, long long lddb);               /* heads planes of nnz, or NULL */
+
 /* ---- options --------------------------------------------------------------------------------
  * Resolved once per handle, at create: process-wide value (spmv_hip_set_option / env), overridden by the
  * calling thread's value (spmv_hip_set_thread_option) -- so two threads can create differently tuned handles

@@ -68,6 +68,18 @@ double spmv_hip_time_attention_gqa_backward_launches(spmv_Handle_t handle, int h
                                                      long long ldk, const void *V, long long ldv, const void *B, long long ldb, const void *G, long long ldg, void *dQ,
                                                      long long lddq, void *dK, long long lddk, void *dV, long long lddv, void *dB, long long lddb, int warmup, int iters,
                                                      float *ms_out);
+/* The same for spmv_hip_attention_gqa_lse, spmv_hip_attention_merge and spmv_hip_attention_gqa_backward_lse: the calls' own arguments (device
+   pointers; the CSR arguments left out), then the timers' warmup, iters and ms_out. */
+double spmv_hip_time_attention_gqa_lse_launches(spmv_Handle_t handle, int heads, int kv_heads, int k, int dv, double scale, const void *Q, long long ldq, const void *K,
+                                                long long ldk, const void *V, long long ldv, const void *B, long long ldb, void *O, long long ldo, void *L, long long ldl,
+                                                int warmup, int iters, float *ms_out);
+double spmv_hip_time_attention_merge_launches(spmv_Handle_t handle, int heads, int dv, const void *O1, long long ldo1, const void *L1, long long ldl1, const void *O2,
+                                              long long ldo2, const void *L2, long long ldl2, void *O, long long ldo, void *L, long long ldl, int warmup, int iters,
+                                              float *ms_out);
+double spmv_hip_time_attention_gqa_backward_lse_launches(spmv_Handle_t handle, int heads, int kv_heads, int k, int dv, double scale, const void *Q, long long ldq, const void *K,
+                                                         long long ldk, const void *V, long long ldv, const void *B, long long ldb, const void *G, long long ldg, const void *O,
+                                                         long long ldo, const void *L, long long ldl, void *dQ, long long lddq, void *dK, long long lddk, void *dV,
+                                                         long long lddv, void *dB, long long lddb, int warmup, int iters, float *ms_out);
 /* copies the built transpose map to host: rowptr_t (n+1 entries) and perm (nnz entries: perm[p] = CSR index in A of the entry at
    position p of A^T's CSR); either may be NULL.  SPMV_HIP_E_NOSTATE until the transpose is built. */
 int spmv_hip_transpose_map(spmv_Handle_t handle, int *rowptr_t, int *perm);

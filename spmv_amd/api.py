@@ -159,6 +159,22 @@ FUNCTIONS = {
     "spmv_hip_time_attention_gqa_backward_launches": (C.c_double, [spmv_Handle_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong,
                                                                    _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong,
                                                                    _V, C.c_longlong, _V, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "spmv_hip_attention_gqa_lse": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong,
+                                             _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong]),
+    "spmv_hip_time_attention_gqa_lse_launches": (C.c_double, [spmv_Handle_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong,
+                                                              _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, C.c_int, C.c_int,
+                                                              C.POINTER(C.c_float)]),
+    "spmv_hip_attention_merge": (C.c_int, [spmv_Handle_t, C.c_int, C.c_int, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong,
+                                           _V, C.c_longlong, _V, C.c_longlong]),
+    "spmv_hip_time_attention_merge_launches": (C.c_double, [spmv_Handle_t, C.c_int, C.c_int, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong,
+                                                            _V, C.c_longlong, _V, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "spmv_hip_attention_gqa_backward_lse": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong,
+                                                      _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong,
+                                                      _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong]),
+    "spmv_hip_time_attention_gqa_backward_lse_launches": (C.c_double, [spmv_Handle_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong,
+                                                                       _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong,
+                                                                       _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, C.c_int, C.c_int,
+                                                                       C.POINTER(C.c_float)]),
     # include/spmv_io.h (host only)
     "spmv_io_read_mtx": (C.c_int, [C.c_char_p, C.c_size_t, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_V)]),
     "spmv_io_cache_path": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t]),
@@ -722,6 +738,99 @@ def time_attention_gqa_backward_launches(handle, heads, kv_heads, Q, K, V, B, G,
     return _timed("spmv_hip_time_attention_gqa_backward_launches", (handle, int(heads), int(kv_heads), k, dv, float(scale), *rest), warmup, iters)
 
 
+def _lse_planes(a, name, heads):
+    """-> (address, ld) of log-sum-exp planes: None -> (None, 0); a 2-D array / tensor of (heads, >= m) with column stride 1, its row stride as ld
+    (a 1-D one is the one plane of heads = 1)"""
+    if a is None:
+        return None, 0
+    if len(a.shape) == 1:
+        a = a.reshape(1, -1)
+    if len(a.shape) != 2 or a.shape[0] != int(heads):
+        raise ValueError(f"{name} must be ({int(heads)}, m), not {tuple(a.shape)}")
+    p, _, w, ld = _block(a, name)
+    return p, int(max(ld, w, 1))
+
+
+def attention_gqa_lse(handle, m, RowPtr, ColIdx, Matrix_Val, heads, kv_heads, Q, K, V, B, O, L, scale=None, check=True, ldb=None, ldl=None):
+    """attention_gqa() that also writes the rows' log-sum-exps (spmv_hip_attention_gqa_lse): L is (heads, m) -- any row stride; ldl overrides it for
+    flat buffers holding padded planes --, L[h, i] = M_i + log Z_i of query head h, -inf on a row without entries.  O has attention_gqa()'s bits;
+    L None IS attention_gqa().  -> the return code."""
+    k, dv, pq, ldq, pk, ldk, pv, ldv, po, ldo = _attention_gqa_blocks(heads, kv_heads, Q, K, V, O)
+    scale = 1.0 / np.sqrt(k) if scale is None and k > 0 else (0.0 if scale is None else scale)
+    pb, ld = (_ptr(B), int(ldb)) if ldb is not None else _planes(B, "B", heads, True)
+    pl, ll = (_ptr(L), int(ldl)) if ldl is not None else _lse_planes(L, "L", heads)
+    return _checked(load().spmv_hip_attention_gqa_lse(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), int(heads), int(kv_heads), k, dv, float(scale),
+                                                      pq, ldq, pk, ldk, pv, ldv, pb, ld, po, ldo, pl, ll), "spmv_hip_attention_gqa_lse", check)
+
+
+def time_attention_gqa_lse_launches(handle, heads, kv_heads, Q, K, V, B, O, L, scale=None, warmup=10, iters=100):
+    """-> (mean_ms, per-call ms array) of spmv_hip_attention_gqa_lse on device operands (spmv_hip_time_attention_gqa_lse_launches)."""
+    k, dv, pq, ldq, pk, ldk, pv, ldv, po, ldo = _attention_gqa_blocks(heads, kv_heads, Q, K, V, O)
+    scale = 1.0 / np.sqrt(k) if scale is None else scale
+    pb, ld = _planes(B, "B", heads, True)
+    pl, ll = _lse_planes(L, "L", heads)
+    return _timed("spmv_hip_time_attention_gqa_lse_launches", (handle, int(heads), int(kv_heads), k, dv, float(scale), pq, ldq, pk, ldk, pv, ldv, pb, ld, po, ldo,
+                                                               pl, ll), warmup, iters)
+
+
+def _attention_merge_args(heads, O1, L1, O2, L2, O, L, ldl):
+    """-> (dv, the C arguments from O1 on) of an attention_merge call; ldl: None, or the plane strides (ldl1, ldl2, ldl) of flat L buffers"""
+    heads = int(heads)
+    args, width = [], None
+    for o, l, no, nl, i in ((O1, L1, "O1", "L1", 0), (O2, L2, "O2", "L2", 1), (O, L, "O", "L", 2)):
+        p, _, w, ld = _block(o, no)
+        if heads < 1 or w % heads or (width is not None and w != width):
+            raise ValueError(f"{no} has {w} columns: not {heads} heads of the other operands' width")
+        width = w
+        pl, ll = (_ptr(l), int(ldl[i])) if ldl is not None else _lse_planes(l, nl, heads)
+        args += [p, int(max(ld, 1)), pl, ll]
+    return width // heads, args
+
+
+def attention_merge(handle, heads, O1, L1, O2, L2, O, L=None, check=True, ldl=None):
+    """O, L = two partial attention results over disjoint parts of a key / value set, combined by their log-sum-exps
+    (spmv_hip_attention_merge): the O operands are (m, heads*dv), the L operands (heads, m).  O may be O1 and L may be L1 (a running
+    accumulator); L None: the merged log-sum-exp is not wanted.  The handle gives m, the precision and the stream; its matrix is not read.
+    -> the return code."""
+    dv, args = _attention_merge_args(heads, O1, L1, O2, L2, O, L, ldl)
+    return _checked(load().spmv_hip_attention_merge(handle, int(heads), dv, *args), "spmv_hip_attention_merge", check)
+
+
+def time_attention_merge_launches(handle, heads, O1, L1, O2, L2, O, L=None, warmup=10, iters=100):
+    """-> (mean_ms, per-call ms array) of spmv_hip_attention_merge on device operands (spmv_hip_time_attention_merge_launches)."""
+    dv, args = _attention_merge_args(heads, O1, L1, O2, L2, O, L, None)
+    return _timed("spmv_hip_time_attention_merge_launches", (handle, int(heads), dv, *args), warmup, iters)
+
+
+def _attention_gqa_backward_lse_args(heads, kv_heads, Q, K, V, B, G, O, L, dQ, dK, dV, dB, ldb, lddb, ldl):
+    """-> (k, dv, the C arguments from Q on) of an attention_gqa_backward_lse call: attention_gqa_backward's with O and L after G"""
+    k, dv, rest = _attention_gqa_backward_args(heads, kv_heads, Q, K, V, B, G, dQ, dK, dV, dB, ldb, lddb)
+    po, _, wo, ldo = _block(O, "O")
+    if wo != int(heads) * dv:
+        raise ValueError(f"O has {wo} columns, expected {int(heads) * dv}")
+    pl, ll = (_ptr(L), int(ldl)) if ldl is not None else _lse_planes(L, "L", heads)
+    # Q, K, V | B | G | O, L | dQ, dK, dV | dB
+    return k, dv, [*rest[:10], po, int(max(ldo, 1)), pl, ll, *rest[10:]]
+
+
+def attention_gqa_backward_lse(handle, m, RowPtr, ColIdx, Matrix_Val, heads, kv_heads, Q, K, V, B, G, O, L, dQ=None, dK=None, dV=None, dB=None, scale=None,
+                               check=True, ldb=None, lddb=None, ldl=None):
+    """attention_gqa_backward() driven by the FINAL output O (m x heads*dv) and log-sum-exp L (heads, m) of the attention this handle's entries are
+    a part of (spmv_hip_attention_gqa_backward_lse): P = exp(t - L), D = <G row, O row>; for one handle, its own attention_gqa_lse() results; for
+    parts, the merged ones -- then the parts' dQ are the caller's to add, dK, dV and dB are each part's own.  -> the return code."""
+    k, dv, rest = _attention_gqa_backward_lse_args(heads, kv_heads, Q, K, V, B, G, O, L, dQ, dK, dV, dB, ldb, lddb, ldl)
+    scale = 1.0 / np.sqrt(k) if scale is None and k > 0 else (0.0 if scale is None else scale)
+    return _checked(load().spmv_hip_attention_gqa_backward_lse(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), int(heads), int(kv_heads), k, dv,
+                                                               float(scale), *rest), "spmv_hip_attention_gqa_backward_lse", check)
+
+
+def time_attention_gqa_backward_lse_launches(handle, heads, kv_heads, Q, K, V, B, G, O, L, dQ=None, dK=None, dV=None, dB=None, scale=None, warmup=10, iters=100):
+    """-> (mean_ms, per-call ms array) of spmv_hip_attention_gqa_backward_lse on device operands (spmv_hip_time_attention_gqa_backward_lse_launches)."""
+    k, dv, rest = _attention_gqa_backward_lse_args(heads, kv_heads, Q, K, V, B, G, O, L, dQ, dK, dV, dB, None, None, None)
+    scale = 1.0 / np.sqrt(k) if scale is None else scale
+    return _timed("spmv_hip_time_attention_gqa_backward_lse_launches", (handle, int(heads), int(kv_heads), k, dv, float(scale), *rest), warmup, iters)
+
+
 def _take_csr(m, n, nnz, rp, ci, va, dtype):
     """Copy malloc'ed C arrays into numpy arrays and free the C side."""
     from .synth import CSR
@@ -963,6 +1072,38 @@ class Handle:
         dB = self._like(Q, (int(heads), self.nnz)) if need[3] else None
         rp, ci, va = self._keep
         attention_gqa_backward(self.h, self.m, rp, ci, va, heads, kv_heads, Q, K, V, bias, G, dQ, dK, dV, dB, scale)
+        return dQ, dK, dV, dB
+
+    def attention_gqa_lse(self, Q, K, V, heads, kv_heads, bias=None, scale=None, out=None, lse=None):
+        """-> (out, lse): attention_gqa(Q, K, V, heads, kv_heads, bias, scale) and the rows' log-sum-exps, lse (heads, m), -inf on a row without
+        entries (spmv_hip_attention_gqa_lse).  out has attention_gqa()'s bits."""
+        if out is None:
+            out = self._like(Q, (self.m, (V.shape[1] // int(kv_heads)) * int(heads)))
+        if lse is None:
+            lse = self._like(Q, (int(heads), self.m))
+        rp, ci, va = self._keep
+        attention_gqa_lse(self.h, self.m, rp, ci, va, heads, kv_heads, Q, K, V, bias, out, lse, scale)
+        return out, lse
+
+    def attention_merge(self, O1, L1, O2, L2, heads, out=None, lse=None, want_lse=True):
+        """-> (out, lse): two partial results over disjoint parts of a key / value set combined by their log-sum-exps (spmv_hip_attention_merge).
+        out may be O1 and lse may be L1 (a running accumulator); want_lse False: lse is not computed (None).  The matrix is not read."""
+        if out is None:
+            out = self._like(O1, tuple(O1.shape))
+        if lse is None and want_lse:
+            lse = self._like(O1, (int(heads), self.m))
+        attention_merge(self.h, heads, O1, L1, O2, L2, out, lse)
+        return out, lse
+
+    def attention_gqa_backward_lse(self, Q, K, V, bias, G, O, L, heads, kv_heads, scale=None, need=(True, True, True, True)):
+        """-> (dQ, dK, dV, dB) like attention_gqa_backward(), driven by the FINAL output O and log-sum-exp L of the attention this handle's entries
+        are a part of (spmv_hip_attention_gqa_backward_lse)."""
+        dQ = self._like(Q, (self.m, Q.shape[1])) if need[0] else None
+        dK = self._like(Q, (self.n, K.shape[1])) if need[1] else None
+        dV = self._like(Q, (self.n, V.shape[1])) if need[2] else None
+        dB = self._like(Q, (int(heads), self.nnz)) if need[3] else None
+        rp, ci, va = self._keep
+        attention_gqa_backward_lse(self.h, self.m, rp, ci, va, heads, kv_heads, Q, K, V, bias, G, O, L, dQ, dK, dV, dB, scale)
         return dQ, dK, dV, dB
 
     def update_values(self, val):

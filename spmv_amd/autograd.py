@@ -537,3 +537,108 @@ def attention(handle, Q, K, V, scale=None, backward="composed", *, bias=None):
     _check_bias(bias, handle, 1)
     scale = 1.0 / math.sqrt(Q.shape[1]) if scale is None else float(scale)   # Handle.attention's default, to the bit
     return (_AttentionFused if backward == "fused" else _Attention).apply(handle, Q, K, V, scale, bias)
+
+
+class _AttentionParts(torch.autograd.Function):
+    """One Handle.attention_gqa_lse per part, folded left to right with Handle.attention_merge into one accumulator; the backward pass is one
+    Handle.attention_gqa_backward_lse per part with the merged O and L.  The flat arguments after `scale`: Q, the parts' K, their V, their
+    biases (None where a part has none)"""
+
+    @staticmethod
+    def forward(ctx, handles, heads, kv_heads, scale, Q, *rest):
+        n = len(handles)
+        Q2 = _block(Q.detach(), Q.shape[1])
+        Ks = [_block(t.detach(), t.shape[1]) for t in rest[:n]]
+        Vs = [_block(t.detach(), t.shape[1]) for t in rest[n:2 * n]]
+        Bs = [_bias_planes(b) for b in rest[2 * n:3 * n]]
+        O = L = None
+        for r, h in enumerate(handles):
+            _on_current_stream(h)
+            Or, Lr = h.attention_gqa_lse(Q2, Ks[r], Vs[r], heads, kv_heads, Bs[r], scale)   # a part without entries: zeros and -inf
+            if r == 0:
+                O, L = Or, Lr
+            else:
+                handles[0].attention_merge(O, L, Or, Lr, heads, out=O, lse=L)   # the accumulator, in place
+        ctx.handles, ctx.heads, ctx.kv_heads, ctx.scale = handles, heads, kv_heads, scale
+        ctx.save_for_backward(Q2, *Ks, *Vs, *Bs, O, L)   # nothing nnz-sized but the caller's own biases
+        ctx.mark_non_differentiable(L)
+        return O, L
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, G, _GL):
+        handles, heads, kv_heads, scale = ctx.handles, ctx.heads, ctx.kv_heads, ctx.scale
+        n = len(handles)
+        saved = ctx.saved_tensors
+        Q2, Ks, Vs, Bs, O, L = saved[0], saved[1:1 + n], saved[1 + n:1 + 2 * n], saved[1 + 2 * n:1 + 3 * n], saved[-2], saved[-1]
+        need = ctx.needs_input_grad[4:]
+        need_q, need_k, need_v = bool(need[0]), [bool(x) for x in need[1:1 + n]], [bool(x) for x in need[1 + n:1 + 2 * n]]
+        need_b = [Bs[r] is not None and bool(need[1 + 2 * n + r]) for r in range(n)]
+        G2 = _block(G, G.shape[1])
+        dQ, dKs, dVs, dBs = None, [None] * n, [None] * n, [None] * n
+        for r, h in enumerate(handles):
+            if not (need_q or need_k[r] or need_v[r] or need_b[r]):
+                continue
+            if h.nnz == 0:   # no stored entry: the part contributes nothing, whatever its K and V are
+                dKs[r] = torch.zeros_like(Ks[r]) if need_k[r] else None
+                dVs[r] = torch.zeros_like(Vs[r]) if need_v[r] else None
+                dBs[r] = torch.zeros_like(Bs[r]) if need_b[r] else None
+                continue
+            _on_current_stream(h)
+            dq, dKs[r], dVs[r], dB = h.attention_gqa_backward_lse(Q2, Ks[r], Vs[r], Bs[r], G2, O, L, heads, kv_heads, scale,
+                                                                   need=(need_q, need_k[r], need_v[r], need_b[r]))
+            dBs[r] = _bias_grad(dB, Bs[r])
+            if need_q:   # the first part's, every later one added in part order
+                if dQ is None:
+                    dQ = dq
+                else:
+                    dQ += dq
+        if need_q and dQ is None:
+            dQ = torch.zeros_like(Q2)
+        return (None, None, None, None, dQ, *dKs, *dVs, *dBs)
+
+
+def attention_parts(handles, Q, Ks, Vs, heads, scale=None, *, kv_heads=None, biases=None, return_lse=False):
+    """Attention of the m query rows over a key / value set cut into PARTS, one handle per part, with gradients for Q, every K_r, V_r and bias:
+    the softmax runs over the union of the parts' stored entries.  handles: a sequence of handles with the same m, dtype and device; part r is
+    a handle of m x n_r with Ks[r] (n_r, kv_heads * k) and Vs[r] (n_r, kv_heads * dv) and an optional bias biases[r] ((nnz_r,) or
+    (heads, nnz_r)); Q is (m, heads * k); kv_heads None means `heads`.  The result is (m, heads * dv); return_lse=True returns (O, L) with the
+    merged row log-sum-exps L (heads, m), which receive no gradient.
+
+    Forward: one Handle.attention_gqa_lse per part, folded left to right with Handle.attention_merge into one accumulator (the merge runs on
+    the first handle; its matrix is not read).  It saves Q, the K_r / V_r, the merged O and L and references to the biases.  Backward: one
+    Handle.attention_gqa_backward_lse per part with the merged O and L: dQ is the first part's, with every later part's added with += in part
+    order; dK_r, dV_r and dB_r are each part's own (a shared bias plane's gradient is the sum of the heads' planes).  With one handle this is
+    the log-sum-exp-driven backward of ordinary attention: the forward's O has Handle.attention_gqa's bits.  A part without stored entries
+    contributes nothing.  No handle's values are read or changed."""
+    handles = list(handles)
+    Ks, Vs = list(Ks), list(Vs)
+    biases = [None] * len(handles) if biases is None else list(biases)
+    if not handles or not (len(handles) == len(Ks) == len(Vs) == len(biases)):
+        raise ValueError(f"need one K, one V and (with biases) one bias or None per handle: {len(handles)} handles, {len(Ks)} K, {len(Vs)} V, {len(biases)} biases")
+    heads = int(heads)
+    kv_heads = heads if kv_heads is None else int(kv_heads)
+    if heads < 1 or kv_heads < 1 or heads % kv_heads:
+        raise ValueError(f"heads = {heads} is not a multiple of kv_heads = {kv_heads}")
+    first = handles[0]
+    for h in handles:
+        _check_handle(h)
+        if h.m != first.m or _handle_dtype(h) != _handle_dtype(first) or _handle_device(h) != _handle_device(first):
+            raise ValueError("the parts' handles must have the same number of rows, dtype and device")
+    _check_tensor(Q, "Q", first)
+    if Q.dim() != 2 or Q.shape[0] != first.m or Q.shape[1] < 1 or Q.shape[1] % heads:
+        raise ValueError(f"Q must be ({first.m}, heads * k) with k >= 1, not {tuple(Q.shape)}")
+    k = Q.shape[1] // heads
+    dv = None
+    for r, (h, K, V, b) in enumerate(zip(handles, Ks, Vs, biases)):
+        _check_tensor(K, f"Ks[{r}]", h)
+        _check_tensor(V, f"Vs[{r}]", h)
+        if K.dim() != 2 or V.dim() != 2 or tuple(K.shape) != (h.n, kv_heads * k) or V.shape[0] != h.n or V.shape[1] < 1 or V.shape[1] % kv_heads:
+            raise ValueError(f"part {r}: K must be ({h.n}, {kv_heads * k}) and V ({h.n}, kv_heads * dv) with dv >= 1, not {tuple(K.shape)} and {tuple(V.shape)}")
+        if dv is not None and V.shape[1] // kv_heads != dv:
+            raise ValueError(f"part {r}: V has heads of width {V.shape[1] // kv_heads}, the parts before it {dv}")
+        dv = V.shape[1] // kv_heads
+        _check_bias(b, h, heads)
+    scale = 1.0 / math.sqrt(k) if scale is None else float(scale)
+    O, L = _AttentionParts.apply(tuple(handles), heads, kv_heads, scale, Q, *Ks, *Vs, *biases)
+    return (O, L) if return_lse else O

@@ -35,6 +35,12 @@
 // K and V rows: that reuse is left to the caches.  The instantiations without GROUPED do not look at gs and are the code
 // from before the groups existed (as a runtime argument alone gs moved the register allocation of every instantiation: DESIGN.md 3.21).
 //
+// Log-sum-exp (spmv_hip_attention_gqa_lse; the LSE instantiations, launched when L is wanted): L[hd * ldl + i] = M_i + log(Z_i), M_i and Z_i the
+// very registers the row softmax divides by (row_softmax_regs_m, long_row_softmax_mz), log the device library's, one plain addition -- stored
+// by lane 0 of the row's group (short rows; a row without entries gets -inf there) or thread 0 of the workgroup (long rows).  O's arithmetic is
+// untouched.  LSE implies BIAS, with bias == nullptr allowed there (a wave-uniform test); the instantiations without LSE do not look at lse and
+// ldl and are the code from before.
+//
 // Arithmetic and order: the composition's, because its blocks are the composition's (kernels/row_blocks.hpp) -- s_p is sddmm's dot for this
 // k (kernels/sddmm.hpp), t_p = s_p * scale one plain multiplication, M_i / Z_i / P_p = exp(t_p - M_i) / Z_i the row softmax's by row length,
 // O[i, c] spmm's chain.  The result is a function of the matrix, k, dv and the value type alone.  Contraction is pinned off: the fmas written
@@ -62,6 +68,8 @@ struct AttentionArgs {
     bool vec = false; // q, kk, v, o, their leading dimensions and every head's first column allow 16-byte accesses
     const void *bias = nullptr; // nullptr: no bias; else planes of nnz elements in CSR order, head hd's at bias + hd * ldb (ldb = 0: one plane shared)
     long long ldb = 0;
+    void *lse = nullptr; // nullptr: not wanted; else `heads` planes of m elements, head hd's row i at lse + hd * ldl + i
+    long long ldl = 0;
 };
 
 // spmv_attention.hip: the launches of one call on `stream`
@@ -120,14 +128,16 @@ __device__ __forceinline__ void att_tile_scores(int i, int j, int lane, int k, c
 // One wave per batch [split[b], split[b + 1]) of whole rows; rows longer than kSpmmLongThr are left to attention_long_kernel.
 // CW: sddmm's lane group for k; 1 << lgv: spmm's lane group for min(dv, KP) columns.  heads: the chunk's columns stay in s_col while the
 // three phases run once per head over s_p, head hd on the columns from hd * k of Q and K and from hd * dv of V and O.  BIAS: head hd adds
-// bias[hd * ldb + p] to the scaled score of entry p (bias is not nullptr).  GROUPED: gs > 1 heads per K / V block.
-template <typename T, int CW, bool VEC, bool BIAS, bool GROUPED>
+// bias[hd * ldb + p] to the scaled score of entry p (bias is not nullptr, except with LSE).  GROUPED: gs > 1 heads per K / V block.
+// LSE (with BIAS): lse is not nullptr and gets every row's M + log(Z) of every head; bias may be nullptr.
+template <typename T, int CW, bool VEC, bool BIAS, bool GROUPED, bool LSE = false>
 __global__ __launch_bounds__(kBlock) void attention_rows_kernel(int nb, const int *__restrict__ split, const int *__restrict__ rowptr, const int *__restrict__ colidx, int heads,
                                                                 int k, int dv, int lgv, T scale, const T *__restrict__ q, long long ldq, const T *__restrict__ kk, long long ldk,
                                                                 const T *__restrict__ v, long long ldv, T *__restrict__ o, long long ldo, const T *__restrict__ bias,
-                                                                long long ldb, int gs)
+                                                                long long ldb, int gs, T *__restrict__ lse = nullptr, long long ldl = 0)
 {
 #pragma clang fp contract(off)
+    static_assert(!LSE || BIAS, "the LSE instantiations are BIAS ones");
     constexpr int V = SpmmShape<T>::V, CH = kSpmmChunk;
     __shared__ int s_col[kBlock / kWave][CH];
     __shared__ T s_p[kBlock / kWave][CH];
@@ -165,10 +175,13 @@ __global__ __launch_bounds__(kBlock) void attention_rows_kernel(int nb, const in
                     } else j = s_col[w][e]; // written by this lane
                 }
                 if constexpr (BIAS) {
-                    const T be = e < nq ? ld_stream(bias + (long long) hd * ldb + base + e) : T(0); // in flight during the dots
+                    const bool hb = !LSE || bias != nullptr; // wave-uniform; without LSE: true at compile time
+                    const T be = hb && e < nq ? ld_stream(bias + (long long) hd * ldb + base + e) : T(0); // in flight during the dots
                     att_tile_scores<T, CW, VEC>(i, j, lane, k, qh, ldq, kh, ldk, scale, s_p[w] + t0);
-                    wave_lds_sync();
-                    if (e < nq) s_p[w][e] = att_add_bias(s_p[w][e], be); // lane l: its own entry, written by another lane
+                    if (hb) {
+                        wave_lds_sync();
+                        if (e < nq) s_p[w][e] = att_add_bias(s_p[w][e], be); // lane l: its own entry, written by another lane
+                    }
                 } else att_tile_scores<T, CW, VEC>(i, j, lane, k, qh, ldq, kh, ldk, scale, s_p[w] + t0);
             }
             wave_lds_sync();
@@ -190,7 +203,13 @@ __global__ __launch_bounds__(kBlock) void attention_rows_kernel(int nb, const in
 #pragma unroll
                     for (int u = 1; u < kRowChain; ++u) x[u] = t + u * kWave < len ? row[t + u * kWave] : ninf;
                 }
-                const T Z = row_softmax_regs(x, t, len, cw, wide);
+                T Z;
+                if constexpr (LSE) {
+                    T M;
+                    Z = row_softmax_regs_m(x, t, len, cw, wide, M);
+                    // one lane per served row; a row without entries: -inf
+                    if (t == 0 && h0 + sub < nr) lse[(long long) hd * ldl + g0 + h0 + sub] = len > 0 ? row_lse(M, Z) : ninf;
+                } else Z = row_softmax_regs(x, t, len, cw, wide);
                 if (t < len) row[t] = x[0] / Z;
                 if (wide) {
 #pragma unroll
@@ -211,14 +230,16 @@ __global__ __launch_bounds__(kBlock) void attention_rows_kernel(int nb, const in
 
 // one workgroup per long row (len > kSpmmLongThr >= 256: every thread has a first term); park + long_off[i]: len elements of its own, used by
 // one head after the other (the barrier that ends a head's last panel is also the one before the next head parks its scores).  BIAS: the
-// bias is added where the score is parked.
-template <typename T, int CW, bool VEC, bool BIAS, bool GROUPED>
+// bias is added where the score is parked.  LSE: as in the rows kernel, thread 0 stores.
+template <typename T, int CW, bool VEC, bool BIAS, bool GROUPED, bool LSE = false>
 __global__ __launch_bounds__(kBlock) void attention_long_kernel(int nlong, const int *__restrict__ longs, const int *__restrict__ long_off, const int *__restrict__ rowptr,
                                                                 const int *__restrict__ colidx, int heads, int k, int dv, int lgv, T scale, const T *__restrict__ q, long long ldq,
                                                                 const T *__restrict__ kk, long long ldk, const T *__restrict__ v, long long ldv, T *__restrict__ o, long long ldo,
-                                                                T *park, const T *__restrict__ bias, long long ldb, int gs)
+                                                                T *park, const T *__restrict__ bias, long long ldb, int gs, T *__restrict__ lse = nullptr,
+                                                                long long ldl = 0)
 {
 #pragma clang fp contract(off)
+    static_assert(!LSE || BIAS, "the LSE instantiations are BIAS ones");
     constexpr int V = SpmmShape<T>::V, KP = SpmmShape<T>::KP;
     __shared__ T part[kSpmmSegs][KP];
     __shared__ T s_slot[kBlock / kWave][kWave];
@@ -246,7 +267,11 @@ __global__ __launch_bounds__(kBlock) void attention_long_kernel(int nlong, const
                 att_tile_scores<T, CW, VEC>(valid ? r : -1, j, lane, k, qh, ldq, kh, ldk, scale, s_slot[w]);
                 wave_lds_sync();
                 if constexpr (BIAS) {
-                    if (valid) t[p] = att_add_bias(s_slot[w][lane], bias[(long long) hd * ldb + s + p]);
+                    if constexpr (LSE) {
+                        if (valid) t[p] = bias ? att_add_bias(s_slot[w][lane], bias[(long long) hd * ldb + s + p]) : s_slot[w][lane];
+                    } else {
+                        if (valid) t[p] = att_add_bias(s_slot[w][lane], bias[(long long) hd * ldb + s + p]);
+                    }
                 } else {
                     if (valid) t[p] = s_slot[w][lane];
                 }
@@ -254,7 +279,11 @@ __global__ __launch_bounds__(kBlock) void attention_long_kernel(int nlong, const
             }
             __syncthreads();
             // 2. maximum, sum, map over the parked scores, P written in place
-            long_row_softmax(t, t, 0, len, tid, s_max, s_sum);
+            if constexpr (LSE) {
+                T M, Z;
+                long_row_softmax_mz(t, t, 0, len, tid, s_max, s_sum, M, Z);
+                if (tid == 0) lse[(long long) hd * ldl + r] = row_lse(M, Z);
+            } else long_row_softmax(t, t, 0, len, tid, s_max, s_sum);
             // 3. O = P V, panel by panel; a panel's last barrier also lets the next panel / head / row write part and the parked scores again
             for (int c = 0; c < dv; c += KP)
                 long_row_panel<T>(len, min(KP, dv - c), G, subv, cv0, tid, part, oh + (long long) r * ldo + c,

@@ -45,6 +45,13 @@
 // dK or dV exists in memory: the running sums are registers (short columns) or the output element itself, read and written by one thread
 // (long columns; and wherever a round ends inside a group, the next round continuing from what it finds).
 //
+// Driven by the final log-sum-exp (spmv_hip_attention_gqa_backward_lse; the STATS instantiations of the two row kernels, which are BIAS ones):
+// the caller hands in O (m x heads * dv) and L (`heads` planes of m), the FINAL output and row log-sum-exp of the attention these entries are
+// a part of.  Phase B is then a map: P_p = exp(t_p - L_i) -- one subtraction, one exp; no maximum, no sum, no division -- and
+// D_i = <G[i, hd * dv ..], O[i, hd * dv ..]>, sddmm's dot for dv columns made by the block that makes dP (attb_tile_dots with "entry" = chunk
+// row, q = G, kk = O; one dot per long row), left in LDS with the rows' L beside it.  dB, dS, the stores for the column pass and dQ are as
+// before; the column kernels are not touched.  The instantiations without STATS do not look at o and lse and are the code from before.
+//
 // Arithmetic and order: the composition's, because its blocks are the composition's (kernels/row_blocks.hpp) -- t and P are
 // spmv_hip_attention's; dP is sddmm's dot for dv; D is row_softmax_backward's by row length; dS is one subtraction and two plain
 // multiplications; dQ, dK and dV are spmm's chains.  Contraction is pinned off: the fmas written out are the only fused operations.
@@ -75,6 +82,8 @@ struct AttentionBwdArgs {
     const void *bias = nullptr; // nullptr: no bias; else head hd's plane at bias + hd * ldb (ldb = 0: one plane shared), CSR order
     void *db = nullptr;         // nullptr: not wanted; else head hd's plane of dL/dB at db + hd * lddb
     long long ldb = 0, lddb = 0;
+    const void *o = nullptr, *lse = nullptr; // both set: the STATS row pass from the final O (m x heads * dv) and L (head hd's row i at lse + hd * ldl + i)
+    long long ldo = 0, ldl = 0;
 };
 
 // spmv_attention_backward.hip: the launches of one call on `stream`, ceil(heads / hg) rounds of a row pass and a column pass
@@ -93,19 +102,24 @@ __device__ __forceinline__ void attb_tile_dots(int cw, int i, int j, int lane, i
 // p_out / ds_out / dq: nullptr when dV / dK / dQ is not wanted.  heads: the chunk's columns stay in s_col while the four phases run once per
 // head over s_p / s_d, head hd on the columns from hd * k (Q, K, dQ) and hd * dv (V, G) and on plane hd of p_out / ds_out.
 // BIAS: bias (added to the scaled scores) and db (P (dP - D), before the scaling) as in the header; either may be nullptr.
-template <typename T, int CW, bool VEC, bool BIAS, bool GROUPED>
+// STATS (with BIAS): P and D from the final o and lse (see the header) instead of the row's own reductions.
+template <typename T, int CW, bool VEC, bool BIAS, bool GROUPED, bool STATS = false>
 __global__ __launch_bounds__(kBlock) void attention_bwd_rows_kernel(int nb, const int *__restrict__ split, const int *__restrict__ rowptr, const int *__restrict__ colidx,
                                                                     int heads, long long plane, int k, int dv, int cwd, int lgk, T scale,
                                                                     const T *__restrict__ q, long long ldq, const T *__restrict__ kk, long long ldk,
                                                                     const T *__restrict__ v, long long ldv, const T *__restrict__ g, long long ldg, T *__restrict__ dq,
                                                                     long long lddq, T *__restrict__ p_out, T *__restrict__ ds_out, const T *__restrict__ bias,
-                                                                    long long ldb, T *__restrict__ db, long long lddb, int gs, int gpos)
+                                                                    long long ldb, T *__restrict__ db, long long lddb, int gs, int gpos,
+                                                                    const T *__restrict__ o = nullptr, long long ldo = 0, const T *__restrict__ lse = nullptr,
+                                                                    long long ldl = 0)
 {
 #pragma clang fp contract(off)
+    static_assert(!STATS || BIAS, "the STATS instantiations are BIAS ones");
     constexpr int V = SpmmShape<T>::V, CH = kSpmmChunk;
     __shared__ int s_col[kBlock / kWave][CH];
     __shared__ T s_p[kBlock / kWave][CH];
     __shared__ T s_d[kBlock / kWave][CH];
+    [[maybe_unused]] __shared__ T s_D[kBlock / kWave][STATS ? kWave : 1], s_L[kBlock / kWave][STATS ? kWave : 1]; // STATS: D and L of the chunk's rows
     const int w = (int) (threadIdx.x / kWave);
     const int b = blockIdx.x * (kBlock / kWave) + w;
     if (b >= nb) return; // whole waves only; no workgroup barrier follows
@@ -151,10 +165,30 @@ __global__ __launch_bounds__(kBlock) void attention_bwd_rows_kernel(int nb, cons
                 }
                 attb_tile_dots<T, VEC>(cwd, i, j, lane, dv, gh, ldg, vh, ldv, s_d[w] + t0);
             }
+            if constexpr (STATS) { // D of chunk row l = <G row, O row> of the head, by lane l's "entry" (row g0 + l of G, row g0 + l of O); its L beside it
+                const int ir = lane < nr ? g0 + lane : -1;
+                attb_tile_dots<T, VEC>(cwd, ir, g0 + lane, lane, dv, gh, ldg, o + (long long) hd * dv, ldo, s_D[w]);
+                if (lane < nr) s_L[w][lane] = lse[(long long) hd * ldl + g0 + lane];
+            }
             wave_lds_sync();
 
+            // B (STATS). a map over the chunk's entries, lane l on the entries l, l + 64, ..: an element is read and written by the same lane
+            if constexpr (STATS) {
+                T *dbc = db ? db + (long long) hd * lddb + base : nullptr; // the chunk's range of the head's plane
+                for (int t0 = 0; t0 < nq; t0 += kWave) {
+                    const int e = t0 + lane;
+                    const int pos = chunk_row_of(ch.el, e); // every lane shuffles
+                    if (e < nq) {
+                        const T pe = row_exp(s_p[w][e] - s_L[w][pos]);
+                        const T d0 = pe * (s_d[w][e] - s_D[w][pos]);
+                        if (dbc) dbc[e] = d0;
+                        s_p[w][e] = pe;
+                        s_d[w][e] = att_scale(d0, scale);
+                    }
+                }
+            }
             // B. the row softmax and its backward in place in LDS, in row_reduce_rows_kernel's passes.  An element is read and written by the same lane.
-            for (int h0 = 0; h0 < nr;) {
+            for (int h0 = 0; !STATS && h0 < nr;) {
                 const int hl = h0 + lane; // lane l looks at chunk row h0 + l
                 const int sh = __shfl(sl, hl & (kWave - 1), kWave) - base, lh0 = __shfl(ll, hl & (kWave - 1), kWave);
                 const int lh = hl < nr ? lh0 : 0;
@@ -248,16 +282,18 @@ __global__ __launch_bounds__(kBlock) void attention_bwd_rows_kernel(int nb, cons
 }
 
 // one workgroup per long row (len > kSpmmLongThr >= 256: every thread has a first term); the row's ranges of every plane of pa (attb_p) and
-// da (attb_ds) are its own: no other workgroup of this launch touches them.  Head hd parks in plane hd's range.  BIAS: as in the rows kernel.
-template <typename T, int CW, bool VEC, bool BIAS, bool GROUPED>
+// da (attb_ds) are its own: no other workgroup of this launch touches them.  Head hd parks in plane hd's range.  BIAS, STATS: as in the rows kernel.
+template <typename T, int CW, bool VEC, bool BIAS, bool GROUPED, bool STATS = false>
 __global__ __launch_bounds__(kBlock) void attention_bwd_long_kernel(int nlong, const int *__restrict__ longs, const int *__restrict__ rowptr, const int *__restrict__ colidx,
                                                                     int heads, long long plane, int k, int dv, int cwd, int lgk, T scale,
                                                                     const T *__restrict__ q, long long ldq, const T *__restrict__ kk, long long ldk,
                                                                     const T *__restrict__ v, long long ldv, const T *__restrict__ g, long long ldg, T *__restrict__ dq,
                                                                     long long lddq, T *pa, T *da, const T *__restrict__ bias, long long ldb, T *__restrict__ db,
-                                                                    long long lddb, int gs, int gpos)
+                                                                    long long lddb, int gs, int gpos, const T *__restrict__ o = nullptr, long long ldo = 0,
+                                                                    const T *__restrict__ lse = nullptr, long long ldl = 0)
 {
 #pragma clang fp contract(off)
+    static_assert(!STATS || BIAS, "the STATS instantiations are BIAS ones");
     constexpr int V = SpmmShape<T>::V, KP = SpmmShape<T>::KP;
     __shared__ T part[kSpmmSegs][KP];
     __shared__ T s_slot[kBlock / kWave][kWave], s_slot2[kBlock / kWave][kWave];
@@ -292,6 +328,21 @@ __global__ __launch_bounds__(kBlock) void attention_bwd_long_kernel(int nlong, c
                 wave_lds_sync();
             }
             __syncthreads();
+            if constexpr (STATS) {
+                // 2 + 3 (STATS). one dot <G row, O row> by the first wave (lane 0's "entry"), then the map over the parked range: P and dS in
+                // place, every element by the thread that parked it
+                if (w == 0) attb_tile_dots<T, VEC>(cwd, lane == 0 ? r : -1, r, lane, dv, gh, ldg, o + (long long) hd * dv, ldo, s_slot[0]);
+                __syncthreads();
+                const T D = s_slot[0][0], lr = lse[(long long) hd * ldl + r];
+                T *dbr = db ? db + (long long) hd * lddb + s : nullptr; // the row's range of the head's plane
+                for (int p = tid; p < len; p += kBlock) {
+                    const T pe = row_exp(t[p] - lr);
+                    const T dp = pe * (d[p] - D);
+                    if (dbr) dbr[p] = dp;
+                    t[p] = pe;
+                    d[p] = att_scale(dp, scale);
+                }
+            } else {
             // 2. maximum, sum, map over the parked scores, P written in place
             long_row_softmax(t, t, 0, len, tid, s_max, s_sum);
             // 3. D over P and the parked dP, dS written in place
@@ -305,6 +356,7 @@ __global__ __launch_bounds__(kBlock) void attention_bwd_long_kernel(int nlong, c
                 }
             } else {
                 for (int p = tid; p < len; p += kBlock) d[p] = att_scale(t[p] * (d[p] - D), scale);
+            }
             }
             __syncthreads();
             // 4. dQ = A_dS K, panel by panel; a panel's last barrier also lets the next panel / head / row write part, s_max, s_sum again

@@ -5,8 +5,8 @@
 //
 //   shapes           SpmmShape, kSpmmLongThr / kSpmmSegs / kSpmmChunk, kRowChain
 //   X rows, chains   spmm_load_x, spmm_store_y, spmm_chain_with / spmm_chain
-//   a row in regs    row_width, row_group_reduce, row_pass_width, row_softmax_regs, row_dot_regs
-//   a long row       long_row_softmax, long_row_dot, long_row_panel
+//   a row in regs    row_width, row_group_reduce, row_pass_width, row_softmax_regs_m / row_softmax_regs, row_lse, row_dot_regs
+//   a long row       long_row_softmax_mz / long_row_softmax, long_row_dot, long_row_panel
 //   chunks of rows   chunk_take, chunk_row_of, rows_times_panels, staged_walk
 #pragma once
 #include "common.hpp"
@@ -108,6 +108,16 @@ __device__ __forceinline__ float row_exp(float x) { return expf(x); }
 __device__ __forceinline__ double row_exp(double x) { return exp(x); }
 __device__ __forceinline__ float row_max(float a, float b) { return __builtin_fmaxf(a, b); }
 __device__ __forceinline__ double row_max(double a, double b) { return __builtin_fmax(a, b); }
+__device__ __forceinline__ float row_log(float x) { return logf(x); }
+__device__ __forceinline__ double row_log(double x) { return log(x); }
+
+// the row's log-sum-exp from the softmax's own M and Z: the device library's log and one plain addition
+template <typename T>
+__device__ __forceinline__ T row_lse(T M, T Z)
+{
+#pragma clang fp contract(off)
+    return M + row_log(Z);
+}
 
 // lanes a row of len entries needs: W = 1 for len <= 1, else the smallest power of two >= len, 64 at the most
 __device__ __forceinline__ int row_width(int len) { return len <= 1 ? 1 : (len >= kWave ? kWave : 1 << (32 - __builtin_clz(len - 1))); }
@@ -144,8 +154,9 @@ __device__ __forceinline__ void row_pass_width(int wl, int &cw, int &lg)
 // in that order, the first as it is and every further one a plain addition onto the chain; a lane without a term holds -0, the identity of
 // IEEE addition; the W chains are added by row_group_reduce's tree.  A group wider than W only adds further -0 lanes: x + (-0) = x for every
 // x, the bits are those of width W.  The maximum is exact in any order (fmax drops a NaN; the sum then restores it: exp(NaN - M) is NaN).
+// row_softmax_regs_m also hands out M (for the row's log-sum-exp, row_lse); row_softmax_regs is the same code without it.
 template <typename T>
-__device__ __forceinline__ T row_softmax_regs(T (&x)[kRowChain], const int t, const int len, const int cw, const bool wide)
+__device__ __forceinline__ T row_softmax_regs_m(T (&x)[kRowChain], const int t, const int len, const int cw, const bool wide, T &M)
 {
 #pragma clang fp contract(off)
     T mx = x[0];
@@ -153,7 +164,7 @@ __device__ __forceinline__ T row_softmax_regs(T (&x)[kRowChain], const int t, co
 #pragma unroll
         for (int j = 1; j < kRowChain; ++j) mx = row_max(mx, x[j]);
     }
-    const T M = row_group_reduce<true>(mx, cw);
+    M = row_group_reduce<true>(mx, cw);
     const T e0 = row_exp(x[0] - M), nzero = T(-0.0);
     x[0] = t < len ? e0 : nzero;
     T acc = x[0];
@@ -167,6 +178,13 @@ __device__ __forceinline__ T row_softmax_regs(T (&x)[kRowChain], const int t, co
         }
     }
     return row_group_reduce<false>(acc, cw);
+}
+
+template <typename T>
+__device__ __forceinline__ T row_softmax_regs(T (&x)[kRowChain], const int t, const int len, const int cw, const bool wide)
+{
+    T M;
+    return row_softmax_regs_m(x, t, len, cw, wide, M);
 }
 
 // D = sum over the row of x * y, the row held like row_softmax_regs' (what a lane holds where it has no term is not read).  Order: virtual
@@ -196,9 +214,9 @@ __device__ __forceinline__ T row_dot_regs(T (&x)[kRowChain], const T (&y)[kRowCh
 // (the first as it is, every further one a plain addition), the 64 chains of a wave are added by row_group_reduce's tree, and the four
 // waves' results as (w0 + w1) + (w2 + w3) through s_max / s_sum.  The row is read again for each phase (max, sum, map); every element is
 // read and written by the same thread in every phase.  Ends with the barrier after which out is every thread's to read and s_max / s_sum
-// may be written again.
+// may be written again.  long_row_softmax_mz also hands out M and Z (every thread holds them); long_row_softmax is the same code without them.
 template <typename T>
-__device__ __forceinline__ void long_row_softmax(const T *in, T *out, int s, int e, int tid, T *s_max, T *s_sum)
+__device__ __forceinline__ void long_row_softmax_mz(const T *in, T *out, int s, int e, int tid, T *s_max, T *s_sum, T &M, T &Z)
 {
 #pragma clang fp contract(off)
     const int w = tid / kWave, lane = tid & (kWave - 1);
@@ -207,15 +225,22 @@ __device__ __forceinline__ void long_row_softmax(const T *in, T *out, int s, int
     mx = row_group_reduce<true>(mx, kWave);
     if (lane == 0) s_max[w] = mx;
     __syncthreads();
-    const T M = row_max(row_max(s_max[0], s_max[1]), row_max(s_max[2], s_max[3]));
+    M = row_max(row_max(s_max[0], s_max[1]), row_max(s_max[2], s_max[3]));
     T acc = row_exp(in[s + tid] - M);
     for (int p = s + tid + kBlock; p < e; p += kBlock) acc = acc + row_exp(in[p] - M);
     acc = row_group_reduce<false>(acc, kWave);
     if (lane == 0) s_sum[w] = acc;
     __syncthreads();
-    const T Z = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]);
+    Z = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]);
     for (int p = s + tid; p < e; p += kBlock) out[p] = row_exp(in[p] - M) / Z;
     __syncthreads();
+}
+
+template <typename T>
+__device__ __forceinline__ void long_row_softmax(const T *in, T *out, int s, int e, int tid, T *s_max, T *s_sum)
+{
+    T M, Z;
+    long_row_softmax_mz(in, out, s, e, tid, s_max, s_sum, M, Z);
 }
 
 // D = sum over p in [s, e) of x[p] * y[p], in long_row_softmax's order with the first term a plain product and every further one

@@ -60,8 +60,10 @@ static int attention_stage_bias(Stager &stg, StageBuf &b, const void *&bias, lon
 // k and dv are one head's widths: Q is heads * k columns wide and O heads * dv; K is kv_heads * k and V kv_heads * dv wide, heads a multiple of
 // kv_heads, and query head h reads K / V block h / (heads / kv_heads) (spmv_hip_attention_gqa; kv_heads = heads: a block per head).  bias: NULL,
 // or the planes of spmv_hip_attention_bias, one per QUERY head (ldb = 0: one plane for all heads; else >= nnz); with NULL, ldb is ignored.
-extern "C" int spmv_shim_attention_gqa(spmv_dev *d, int heads, int kv_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
-                                       const void *v, long long ldv, const void *bias, long long ldb, void *o, long long ldo)
+// lse: NULL, or `heads` planes ldl >= m apart that get the rows' log-sum-exps (spmv_hip_attention_gqa_lse); with NULL, ldl is ignored and the
+// launches are those of spmv_hip_attention_gqa.
+extern "C" int spmv_shim_attention_gqa_lse(spmv_dev *d, int heads, int kv_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
+                                           const void *v, long long ldv, const void *bias, long long ldb, void *o, long long ldo, void *lse, long long ldl)
 {
     if (!d || !d->built) return fail(SPMV_HIP_E_NOSTATE, "attention: schedule not built");
     if (kv_heads < 1 || heads < 1 || heads % kv_heads != 0) return fail(SPMV_HIP_E_ARG, "attention: need kv_heads >= 1 and heads a multiple of it (heads = %d, kv_heads = %d)", heads, kv_heads);
@@ -72,6 +74,7 @@ extern "C" int spmv_shim_attention_gqa(spmv_dev *d, int heads, int kv_heads, int
                     heads, kv_heads, k, dv, ldq, ldk, ldv, ldo);
     if (bias && (ldb < 0 || (ldb > 0 && ldb < d->nnz)))
         return fail(SPMV_HIP_E_ARG, "attention: the bias planes need ldb = 0 (one plane for all heads) or ldb >= nnz (ldb = %lld, nnz = %lld)", ldb, d->nnz);
+    if (lse && ldl < d->m) return fail(SPMV_HIP_E_ARG, "attention: the log-sum-exp planes need ldl >= m (ldl = %lld, m = %d)", ldl, d->m);
     if (d->nnz == 0) bias = nullptr; // no entry: no bias is read
     if (d->m > 0 && (!q || !kk || !v || !o)) return fail(SPMV_HIP_E_ARG, "attention: Q, K, V or O is NULL");
     if (d->nnz > 0 && !d->colidx) return fail(SPMV_HIP_E_NOSTATE, "attention: the resident column indices were released (spmv_shim_restore_columns first)");
@@ -103,16 +106,65 @@ extern "C" int spmv_shim_attention_gqa(spmv_dev *d, int heads, int kv_heads, int
     a.v = v; a.ldv = ldv;
     a.o = o; a.ldo = ldo;
     a.bias = bias; a.ldb = bias ? ldb : 0;
+    a.lse = lse; a.ldl = lse ? ldl : 0;
     // every row of O gets its heads * dv elements, empty rows their zeros: a staged result is written completely before it is copied back
     if ((rc = stg.in(d->stage[STAGE_ATT_Q], a.q, a.ldq, (size_t) d->m, (int) wk)) || (rc = stg.in(d->stage[STAGE_ATT_K], a.kk, a.ldk, (size_t) d->n, (int) gk)) ||
         (rc = stg.in(d->stage[STAGE_ATT_V], a.v, a.ldv, (size_t) d->n, (int) gv)) || (rc = stg.out(d->stage[STAGE_ATT_O], a.o, a.ldo, (size_t) d->m, (int) wv)) ||
-        (a.bias && (rc = attention_stage_bias(stg, d->stage[STAGE_ATT_B], a.bias, a.ldb, heads)))) return rc;
+        (a.bias && (rc = attention_stage_bias(stg, d->stage[STAGE_ATT_B], a.bias, a.ldb, heads))) ||
+        (a.lse && (rc = stg.out(d->stage[STAGE_ATT_L], a.lse, a.ldl, (size_t) heads, d->m)))) return rc; // every row of every plane is written
     // the access width changes no bit (kernels/attention.hpp): chosen per call from what the addresses allow -- with more than one head, every
     // head's first column has to be 16-byte aligned as well
     a.vec = wide_ok(a.q, a.ldq, s) && wide_ok(a.kk, a.ldk, s) && wide_ok(a.v, a.ldv, s) && wide_ok(a.o, a.ldo, s) &&
             (heads == 1 || (((size_t) k * s) % 16 == 0 && ((size_t) dv * s) % 16 == 0));
     const hipError_t e = attention_launch(a, s == sizeof(double), d->stream);
     if (e != hipSuccess) return fail(SPMV_HIP_E_RUNTIME, "attention: launch: %s", hipGetErrorString(e));
+    return stg.finish();
+}
+
+extern "C" int spmv_shim_attention_gqa(spmv_dev *d, int heads, int kv_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
+                                       const void *v, long long ldv, const void *bias, long long ldb, void *o, long long ldo)
+{
+    return spmv_shim_attention_gqa_lse(d, heads, kv_heads, k, dv, scale, q, ldq, kk, ldk, v, ldv, bias, ldb, o, ldo, nullptr, 0);
+}
+
+// O and L of two partial results merged by their log-sum-exps (spmv_hip_attention_merge; kernels/attention_merge.hpp): the matrix is not read,
+// only the handle's m, precision, stream and staging.  o may be o1 and l may be l1; l NULL: the merged log-sum-exp is not wanted.
+extern "C" int spmv_shim_attention_merge(spmv_dev *d, int heads, int dv, const void *o1, long long ldo1, const void *l1, long long ldl1, const void *o2, long long ldo2,
+                                         const void *l2, long long ldl2, void *o, long long ldo, void *l, long long ldl)
+{
+    if (!d || !d->built) return fail(SPMV_HIP_E_NOSTATE, "attention_merge: schedule not built");
+    const long long wv = (long long) heads * dv;
+    if (heads < 1 || dv < 1 || wv > INT_MAX || ldo1 < wv || ldo2 < wv || ldo < wv)
+        return fail(SPMV_HIP_E_ARG, "attention_merge: need heads, dv >= 1, heads * dv within int and ldo1, ldo2, ldo >= heads * dv (heads = %d, dv = %d, ld = %lld, %lld, %lld)", heads,
+                    dv, ldo1, ldo2, ldo);
+    if (ldl1 < d->m || ldl2 < d->m || (l && ldl < d->m))
+        return fail(SPMV_HIP_E_ARG, "attention_merge: the log-sum-exp planes need ldl1, ldl2, ldl >= m (ld = %lld, %lld, %lld, m = %d)", ldl1, ldl2, ldl, d->m);
+    if (d->m > 0 && (!o1 || !l1 || !o2 || !l2 || !o)) return fail(SPMV_HIP_E_ARG, "attention_merge: O1, L1, O2, L2 or O is NULL");
+    if (d->m == 0) return SPMV_HIP_OK;
+    DeviceGuard guard(d->device);
+    if (!guard.ok) return fail(SPMV_HIP_E_RUNTIME, "hipSetDevice(%d) failed", d->device);
+    const size_t s = d->vsize;
+    Stager stg{d};
+    AttentionMergeArgs a;
+    a.m = d->m;
+    a.heads = heads;
+    a.dv = dv;
+    a.cus = d->cus;
+    a.o1 = o1; a.ldo1 = ldo1;
+    a.l1 = l1; a.ldl1 = ldl1;
+    a.o2 = o2; a.ldo2 = ldo2;
+    a.l2 = l2; a.ldl2 = ldl2;
+    a.o = o; a.ldo = ldo;
+    a.l = l; a.ldl = l ? ldl : 0;
+    int rc;
+    // a host accumulator (o == o1, l == l1) is read through one buffer and written through another: the copies keep the in-place rule
+    if ((rc = stg.in(d->stage[STAGE_MRG_O1], a.o1, a.ldo1, (size_t) d->m, (int) wv)) || (rc = stg.in(d->stage[STAGE_MRG_L1], a.l1, a.ldl1, (size_t) heads, d->m)) ||
+        (rc = stg.in(d->stage[STAGE_MRG_O2], a.o2, a.ldo2, (size_t) d->m, (int) wv)) || (rc = stg.in(d->stage[STAGE_MRG_L2], a.l2, a.ldl2, (size_t) heads, d->m)) ||
+        (rc = stg.out(d->stage[STAGE_MRG_O], a.o, a.ldo, (size_t) d->m, (int) wv)) || (a.l && (rc = stg.out(d->stage[STAGE_MRG_L], a.l, a.ldl, (size_t) heads, d->m)))) return rc;
+    // the access width changes no bit (kernels/attention_merge.hpp): with more than one head, every head's first column has to be 16-byte aligned as well
+    a.vec = wide_ok(a.o1, a.ldo1, s) && wide_ok(a.o2, a.ldo2, s) && wide_ok(a.o, a.ldo, s) && (heads == 1 || ((size_t) dv * s) % 16 == 0);
+    const hipError_t e = attention_merge_launch(a, s == sizeof(double), d->stream);
+    if (e != hipSuccess) return fail(SPMV_HIP_E_RUNTIME, "attention_merge: launch: %s", hipGetErrorString(e));
     return stg.finish();
 }
 
@@ -143,6 +195,31 @@ extern "C" double spmv_shim_time_attention_gqa(spmv_dev *d, int heads, int kv_he
         return -1.0;
     }
     return time_events(d, "time_attention", warmup, iters, ms_out, [&] { return spmv_shim_attention_gqa(d, heads, kv_heads, k, dv, scale, q, ldq, kk, ldk, v, ldv, bias, ldb, o, ldo); });
+}
+
+extern "C" double spmv_shim_time_attention_gqa_lse(spmv_dev *d, int heads, int kv_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
+                                                   const void *v, long long ldv, const void *bias, long long ldb, void *o, long long ldo, void *lse, long long ldl, int warmup,
+                                                   int iters, float *ms_out)
+{
+    if (!d || !d->built || iters <= 0) { fail(SPMV_HIP_E_ARG, "time_attention: bad arguments"); return -1.0; }
+    if (!is_device_ptr(q) || !is_device_ptr(kk) || !is_device_ptr(v) || !is_device_ptr(o) || (bias && !is_device_ptr(bias)) || (lse && !is_device_ptr(lse))) {
+        fail(SPMV_HIP_E_ARG, "time_attention: Q, K, V, O, the bias and L must be device pointers");
+        return -1.0;
+    }
+    return time_events(d, "time_attention", warmup, iters, ms_out,
+                       [&] { return spmv_shim_attention_gqa_lse(d, heads, kv_heads, k, dv, scale, q, ldq, kk, ldk, v, ldv, bias, ldb, o, ldo, lse, ldl); });
+}
+
+extern "C" double spmv_shim_time_attention_merge(spmv_dev *d, int heads, int dv, const void *o1, long long ldo1, const void *l1, long long ldl1, const void *o2, long long ldo2,
+                                                 const void *l2, long long ldl2, void *o, long long ldo, void *l, long long ldl, int warmup, int iters, float *ms_out)
+{
+    if (!d || !d->built || iters <= 0) { fail(SPMV_HIP_E_ARG, "time_attention_merge: bad arguments"); return -1.0; }
+    if (!is_device_ptr(o1) || !is_device_ptr(l1) || !is_device_ptr(o2) || !is_device_ptr(l2) || !is_device_ptr(o) || (l && !is_device_ptr(l))) {
+        fail(SPMV_HIP_E_ARG, "time_attention_merge: the operands must be device pointers");
+        return -1.0;
+    }
+    return time_events(d, "time_attention_merge", warmup, iters, ms_out,
+                       [&] { return spmv_shim_attention_merge(d, heads, dv, o1, ldo1, l1, ldl1, o2, ldo2, l2, ldl2, o, ldo, l, ldl); });
 }
 
 extern "C" double spmv_shim_time_attention_bias(spmv_dev *d, int heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v,

@@ -57,9 +57,12 @@ static int attention_backward_group(const spmv_dev *d, int heads, int limit, int
 // spmv_shim_attention_heads_backward.  kv_heads: K, V, dk and dvo are kv_heads * k / kv_heads * dv wide, heads a multiple of kv_heads, query head
 // h belongs to block h / (heads / kv_heads), and dk / dvo of a block are the sums of its heads' terms in ascending head
 // (spmv_hip_attention_gqa_backward); the planes, bias and db stay per QUERY head.  kv_heads = heads is spmv_hip_attention_bias_backward.
-extern "C" int spmv_shim_attention_gqa_backward(spmv_dev *d, int heads, int kv_heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
-                                                 const void *v, long long ldv, const void *bias, long long ldb, const void *g, long long ldg, void *dq, long long lddq, void *dk,
-                                                 long long lddk, void *dvo, long long lddv, void *db, long long lddb)
+// stats (spmv_hip_attention_gqa_backward_lse): o (m x heads * dv, ldo) and lse (`heads` planes ldl >= m apart) are the FINAL output and
+// log-sum-exp of the attention this handle's entries are a part of, and the row pass takes P and D from them; else they are not looked at.
+static int attention_gqa_backward_impl(spmv_dev *d, int heads, int kv_heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
+                                       const void *v, long long ldv, const void *bias, long long ldb, const void *g, long long ldg, void *dq, long long lddq, void *dk,
+                                       long long lddk, void *dvo, long long lddv, void *db, long long lddb, bool stats, const void *o, long long ldo, const void *lse,
+                                       long long ldl)
 {
     if (!d || !d->built) return fail(SPMV_HIP_E_NOSTATE, "attention_backward: schedule not built");
     if (kv_heads < 1 || heads < 1 || heads % kv_heads != 0)
@@ -71,6 +74,8 @@ extern "C" int spmv_shim_attention_gqa_backward(spmv_dev *d, int heads, int kv_h
         return fail(SPMV_HIP_E_ARG, "attention_backward: need heads, k, dv >= 1, heads * k and heads * dv within int, ldq >= heads * k, ldk >= kv_heads * k, ldv >= kv_heads * dv, ldg >= heads * dv, lddq >= heads * k, lddk >= kv_heads * k, lddv >= kv_heads * dv (heads = %d, kv_heads = %d, k = %d, dv = %d)",
                     heads, kv_heads, k, dv);
     if (d->m > 0 && (!q || !kk || !v || !g)) return fail(SPMV_HIP_E_ARG, "attention_backward: Q, K, V or G is NULL");
+    if (stats && ((d->m > 0 && (!o || !lse)) || ldo < wv || ldl < d->m))
+        return fail(SPMV_HIP_E_ARG, "attention_backward: the final O and L are needed, with ldo >= heads * dv and ldl >= m (ldo = %lld, ldl = %lld, m = %d)", ldo, ldl, d->m);
     if ((bias && (ldb < 0 || (ldb > 0 && ldb < d->nnz))) || (db && lddb < d->nnz))
         return fail(SPMV_HIP_E_ARG, "attention_backward: the bias planes need ldb = 0 (one plane for all heads) or ldb >= nnz, those of dB lddb >= nnz (ldb = %lld, lddb = %lld, nnz = %lld)",
                     ldb, lddb, d->nnz);
@@ -125,20 +130,56 @@ extern "C" int spmv_shim_attention_gqa_backward(spmv_dev *d, int heads, int kv_h
     a.dvo = cols ? dvo : nullptr; a.lddv = lddv;
     a.bias = bias; a.ldb = bias ? ldb : 0;
     a.db = db; a.lddb = lddb;
+    if (stats && d->m > 0) { a.o = o; a.ldo = ldo; a.lse = lse; a.ldl = ldl; }
     // every row of a wanted output gets its elements, empty rows and columns their zeros: a staged result is written completely before it is copied back
     if ((rc = stg.in(d->stage[STAGE_ATTB_Q], a.q, a.ldq, (size_t) d->m, (int) wk)) || (rc = stg.in(d->stage[STAGE_ATTB_K], a.kk, a.ldk, (size_t) d->n, (int) gk)) ||
         (rc = stg.in(d->stage[STAGE_ATTB_V], a.v, a.ldv, (size_t) d->n, (int) gv)) || (rc = stg.in(d->stage[STAGE_ATTB_G], a.g, a.ldg, (size_t) d->m, (int) wv)) ||
         (a.dq && (rc = stg.out(d->stage[STAGE_ATTB_DQ], a.dq, a.lddq, (size_t) d->m, (int) wk))) || (a.dk && (rc = stg.out(d->stage[STAGE_ATTB_DK], a.dk, a.lddk, (size_t) d->n, (int) gk))) ||
         (a.dvo && (rc = stg.out(d->stage[STAGE_ATTB_DV], a.dvo, a.lddv, (size_t) d->n, (int) gv))) ||
         (a.bias && (rc = attention_stage_bias(stg, d->stage[STAGE_ATT_B], a.bias, a.ldb, heads))) ||
-        (a.db && (rc = stg.out(d->stage[STAGE_ATT_DB], a.db, a.lddb, (size_t) heads, (int) d->nnz)))) return rc; // every entry of every plane is written
+        (a.db && (rc = stg.out(d->stage[STAGE_ATT_DB], a.db, a.lddb, (size_t) heads, (int) d->nnz))) || // every entry of every plane is written
+        (a.o && ((rc = stg.in(d->stage[STAGE_ATTB_O], a.o, a.ldo, (size_t) d->m, (int) wv)) || (rc = stg.in(d->stage[STAGE_ATTB_L], a.lse, a.ldl, (size_t) heads, d->m))))) return rc;
     // the access width changes no bit (kernels/attention_backward.hpp): chosen per call from what the addresses allow -- with more than one head,
     // every head's first column has to be 16-byte aligned as well
     a.vec = wide_ok(a.q, a.ldq, s) && wide_ok(a.kk, a.ldk, s) && wide_ok(a.v, a.ldv, s) && wide_ok(a.g, a.ldg, s) && (!a.dq || wide_ok(a.dq, a.lddq, s)) &&
-            (!a.dk || wide_ok(a.dk, a.lddk, s)) && (!a.dvo || wide_ok(a.dvo, a.lddv, s)) && (heads == 1 || (((size_t) k * s) % 16 == 0 && ((size_t) dv * s) % 16 == 0));
+            (!a.dk || wide_ok(a.dk, a.lddk, s)) && (!a.dvo || wide_ok(a.dvo, a.lddv, s)) && (!a.o || wide_ok(a.o, a.ldo, s)) && (heads == 1 || (((size_t) k * s) % 16 == 0 && ((size_t) dv * s) % 16 == 0));
     const hipError_t e = attention_backward_launch(a, s == sizeof(double), d->stream);
     if (e != hipSuccess) return fail(SPMV_HIP_E_RUNTIME, "attention_backward: launch: %s", hipGetErrorString(e));
     return stg.finish();
+}
+
+extern "C" int spmv_shim_attention_gqa_backward(spmv_dev *d, int heads, int kv_heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
+                                                 const void *v, long long ldv, const void *bias, long long ldb, const void *g, long long ldg, void *dq, long long lddq, void *dk,
+                                                 long long lddk, void *dvo, long long lddv, void *db, long long lddb)
+{
+    return attention_gqa_backward_impl(d, heads, kv_heads, max_heads, k, dv, scale, q, ldq, kk, ldk, v, ldv, bias, ldb, g, ldg, dq, lddq, dk, lddk, dvo, lddv, db, lddb, false, nullptr,
+                                       0, nullptr, 0);
+}
+
+extern "C" int spmv_shim_attention_gqa_backward_lse(spmv_dev *d, int heads, int kv_heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk,
+                                                     long long ldk, const void *v, long long ldv, const void *bias, long long ldb, const void *g, long long ldg, const void *o,
+                                                     long long ldo, const void *lse, long long ldl, void *dq, long long lddq, void *dk, long long lddk, void *dvo, long long lddv,
+                                                     void *db, long long lddb)
+{
+    return attention_gqa_backward_impl(d, heads, kv_heads, max_heads, k, dv, scale, q, ldq, kk, ldk, v, ldv, bias, ldb, g, ldg, dq, lddq, dk, lddk, dvo, lddv, db, lddb, true, o, ldo, lse,
+                                       ldl);
+}
+
+extern "C" double spmv_shim_time_attention_gqa_backward_lse(spmv_dev *d, int heads, int kv_heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq,
+                                                             const void *kk, long long ldk, const void *v, long long ldv, const void *bias, long long ldb, const void *g, long long ldg,
+                                                             const void *o, long long ldo, const void *lse, long long ldl, void *dq, long long lddq, void *dk, long long lddk,
+                                                             void *dvo, long long lddv, void *db, long long lddb, int warmup, int iters, float *ms_out)
+{
+    if (!d || !d->built || iters <= 0) { fail(SPMV_HIP_E_ARG, "time_attention_backward: bad arguments"); return -1.0; }
+    if (!is_device_ptr(q) || !is_device_ptr(kk) || !is_device_ptr(v) || !is_device_ptr(g) || !is_device_ptr(o) || !is_device_ptr(lse) || (dq && !is_device_ptr(dq)) ||
+        (dk && !is_device_ptr(dk)) || (dvo && !is_device_ptr(dvo)) || (bias && !is_device_ptr(bias)) || (db && !is_device_ptr(db))) {
+        fail(SPMV_HIP_E_ARG, "time_attention_backward: Q, K, V, G, O, L, the bias and the outputs must be device pointers");
+        return -1.0;
+    }
+    return time_events(d, "time_attention_backward", warmup, iters, ms_out, [&] {
+        return spmv_shim_attention_gqa_backward_lse(d, heads, kv_heads, max_heads, k, dv, scale, q, ldq, kk, ldk, v, ldv, bias, ldb, g, ldg, o, ldo, lse, ldl, dq, lddq, dk, lddk, dvo,
+                                                    lddv, db, lddb);
+    });
 }
 
 extern "C" int spmv_shim_attention_bias_backward(spmv_dev *d, int heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,

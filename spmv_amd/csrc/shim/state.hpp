@@ -190,6 +190,9 @@ enum { STAGE_X, STAGE_Y, STAGE_SPMM_X, STAGE_SPMM_Y, STAGE_SDDMM_U, STAGE_SDDMM_
        STAGE_ATT_Q, STAGE_ATT_K, STAGE_ATT_V, STAGE_ATT_O,
        STAGE_ATTB_Q, STAGE_ATTB_K, STAGE_ATTB_V, STAGE_ATTB_G, STAGE_ATTB_DQ, STAGE_ATTB_DK, STAGE_ATTB_DV,
        STAGE_ATT_B, STAGE_ATT_DB, // the bias planes of spmv_hip_attention_bias / _bias_backward, and dB's
+       STAGE_ATT_L,                // the log-sum-exp planes spmv_hip_attention_gqa_lse writes
+       STAGE_ATTB_O, STAGE_ATTB_L, // the final O and L spmv_hip_attention_gqa_backward_lse reads
+       STAGE_MRG_O1, STAGE_MRG_L1, STAGE_MRG_O2, STAGE_MRG_L2, STAGE_MRG_O, STAGE_MRG_L, // spmv_hip_attention_merge's operands
        STAGE_COUNT };
 
 struct spmv_dev {

@@ -1288,6 +1288,67 @@ double spmv_hip_time_attention_gqa_launches(spmv_Handle_t h, int heads, int kv_h
     return report_time(spmv_shim_time_attention_gqa(st->dev, heads, kv_heads, k, dv, scale, Q, ldq, K, ldk, V, ldv, B, ldb, O, ldo, warmup, iters, ms_out), where);
 }
 
+/* ---------------------------------------------------------------- the row log-sum-exp out of the forward, and two partial results merged by it */
+int spmv_hip_attention_gqa_lse(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                               const void *Matrix_Val, int heads, int kv_heads, int k, int dv, double scale,
+                               const void *Q, long long ldq, const void *K, long long ldk, const void *V, long long ldv,
+                               const void *B, long long ldb, void *O, long long ldo, void *L, long long ldl)
+{
+    const char *where = "attention_gqa_lse";
+    spmv_hip_state *st;
+    int rc;
+    if ((rc = attention_gqa_args(handle, where, heads, kv_heads, k, dv, Q, ldq, K, ldk, V, ldv, O, ldo, m))) return rc;
+    if (B && ldb < 0) return refuse(SPMV_HIP_E_ARG, where, "need ldb >= 0");
+    if (L && ldl < (long long) m) return refuse(SPMV_HIP_E_ARG, where, "need ldl >= m");
+    if ((rc = resident_prologue(handle, where, RESIDENT_NOT_REORDERED, m, RowPtr, ColIdx, Matrix_Val, &st)) || (rc = spmm_columns(handle, st, where))) return rc;
+    return report(spmv_shim_attention_gqa_lse(st->dev, heads, kv_heads, k, dv, scale, Q, ldq, K, ldk, V, ldv, B, ldb, O, ldo, L, ldl), where); /* 0 < ldb < nnz: refused there, nothing written */
+}
+
+double spmv_hip_time_attention_gqa_lse_launches(spmv_Handle_t h, int heads, int kv_heads, int k, int dv, double scale, const void *Q, long long ldq, const void *K, long long ldk,
+                                                const void *V, long long ldv, const void *B, long long ldb, void *O, long long ldo, void *L, long long ldl, int warmup, int iters,
+                                                float *ms_out)
+{
+    const char *where = "time_attention_gqa_lse_launches";
+    spmv_hip_state *st;
+    if (attention_gqa_args(h, where, heads, kv_heads, k, dv, Q, ldq, K, ldk, V, ldv, O, ldo, 1)) return -1.0;
+    if (B && ldb < 0) { (void) refuse(SPMV_HIP_E_ARG, where, "need ldb >= 0"); return -1.0; }
+    if (resident_state(h, where, RESIDENT_NOT_REORDERED, &st) || spmm_columns(h, st, where)) return -1.0;
+    return report_time(spmv_shim_time_attention_gqa_lse(st->dev, heads, kv_heads, k, dv, scale, Q, ldq, K, ldk, V, ldv, B, ldb, O, ldo, L, ldl, warmup, iters, ms_out), where);
+}
+
+/* m is the handle's: whether an operand is NULL while m > 0, and the plane strides against m, are looked at behind the gate (nothing written) */
+static int attention_merge_args(spmv_Handle_t h, const char *where, int heads, int dv, long long ldo1, long long ldo2, long long ldo)
+{
+    long long wv;
+    if (!h) return refuse(SPMV_HIP_E_ARG, where, "handle is NULL");
+    if (heads < 1 || dv < 1) return refuse(SPMV_HIP_E_ARG, where, "need heads >= 1 and dv >= 1");
+    wv = (long long) heads * dv;
+    if (wv > INT_MAX) return refuse(SPMV_HIP_E_ARG, where, "heads * dv does not fit an int");
+    if (ldo1 < wv || ldo2 < wv || ldo < wv) return refuse(SPMV_HIP_E_ARG, where, "need ldo1, ldo2 and ldo >= heads * dv");
+    return SPMV_HIP_OK;
+}
+
+int spmv_hip_attention_merge(spmv_Handle_t handle, int heads, int dv, const void *O1, long long ldo1, const void *L1, long long ldl1,
+                             const void *O2, long long ldo2, const void *L2, long long ldl2, void *O, long long ldo, void *L, long long ldl)
+{
+    const char *where = "attention_merge";
+    spmv_hip_state *st;
+    int rc;
+    if ((rc = attention_merge_args(handle, where, heads, dv, ldo1, ldo2, ldo))) return rc;
+    if (ldl1 < 0 || ldl2 < 0 || (L && ldl < 0)) return refuse(SPMV_HIP_E_ARG, where, "need ldl1, ldl2 and ldl >= m");
+    if ((rc = resident_state(handle, where, RESIDENT_NOT_REORDERED, &st))) return rc;
+    return report(spmv_shim_attention_merge(st->dev, heads, dv, O1, ldo1, L1, ldl1, O2, ldo2, L2, ldl2, O, ldo, L, ldl), where);
+}
+
+double spmv_hip_time_attention_merge_launches(spmv_Handle_t h, int heads, int dv, const void *O1, long long ldo1, const void *L1, long long ldl1, const void *O2, long long ldo2,
+                                              const void *L2, long long ldl2, void *O, long long ldo, void *L, long long ldl, int warmup, int iters, float *ms_out)
+{
+    const char *where = "time_attention_merge_launches";
+    spmv_hip_state *st;
+    if (attention_merge_args(h, where, heads, dv, ldo1, ldo2, ldo) || resident_state(h, where, RESIDENT_NOT_REORDERED, &st)) return -1.0;
+    return report_time(spmv_shim_time_attention_merge(st->dev, heads, dv, O1, ldo1, L1, ldl1, O2, ldo2, L2, ldl2, O, ldo, L, ldl, warmup, iters, ms_out), where);
+}
+
 static int attention_gqa_backward_args(spmv_Handle_t h, const char *where, int heads, int kv_heads, int k, int dv, const void *Q, long long ldq, const void *K, long long ldk,
                                        const void *V, long long ldv, const void *G, long long ldg, const void *dQ, long long lddq, const void *dK, long long lddk,
                                        const void *dV, long long lddv, int m)
@@ -1337,4 +1398,47 @@ double spmv_hip_time_attention_gqa_backward_launches(spmv_Handle_t h, int heads,
     if (resident_state(h, where, RESIDENT_NOT_REORDERED, &st) || attention_backward_tables(h, st, where, dK || dV)) return -1.0;
     return report_time(spmv_shim_time_attention_gqa_backward(st->dev, heads, kv_heads, (int) st->opts.v[SPMV_OPT_ATTENTION_BACKWARD_HEADS], k, dv, scale, Q, ldq, K, ldk, V, ldv, B,
                                                              ldb, G, ldg, dQ, lddq, dK, lddk, dV, lddv, dB, lddb, warmup, iters, ms_out), where);
+}
+
+/* ---------------------------------------------------------------- the GQA backward driven by the final O and log-sum-exp */
+static int attention_lse_inputs(const char *where, int heads, int dv, const void *O, long long ldo, const void *L, long long ldl, int m)
+{
+    if (ldo < (long long) heads * dv) return refuse(SPMV_HIP_E_ARG, where, "need ldo >= heads * dv");
+    if (ldl < (long long) m) return refuse(SPMV_HIP_E_ARG, where, "need ldl >= m");
+    if (m > 0 && (!O || !L)) return refuse(SPMV_HIP_E_ARG, where, "O or L is NULL");
+    return SPMV_HIP_OK;
+}
+
+int spmv_hip_attention_gqa_backward_lse(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                                        const void *Matrix_Val, int heads, int kv_heads, int k, int dv, double scale,
+                                        const void *Q, long long ldq, const void *K, long long ldk, const void *V, long long ldv,
+                                        const void *B, long long ldb, const void *G, long long ldg, const void *O, long long ldo, const void *L, long long ldl,
+                                        void *dQ, long long lddq, void *dK, long long lddk, void *dV, long long lddv, void *dB, long long lddb)
+{
+    const char *where = "attention_gqa_backward_lse";
+    spmv_hip_state *st;
+    int rc;
+    if ((rc = attention_gqa_backward_args(handle, where, heads, kv_heads, k, dv, Q, ldq, K, ldk, V, ldv, G, ldg, dQ, lddq, dK, lddk, dV, lddv, m)) ||
+        (rc = attention_lse_inputs(where, heads, dv, O, ldo, L, ldl, m))) return rc;
+    if ((B && ldb < 0) || (dB && lddb < 0)) return refuse(SPMV_HIP_E_ARG, where, "need ldb >= 0 and lddb >= 0");
+    if (!dQ && !dK && !dV && !dB) return SPMV_HIP_OK; /* nothing wanted: no work, the handle's state is not looked at */
+    if ((rc = resident_prologue(handle, where, RESIDENT_NOT_REORDERED, m, RowPtr, ColIdx, Matrix_Val, &st))) return rc;
+    if ((rc = attention_backward_tables(handle, st, where, dK || dV))) return rc; /* only dB (or dQ) wanted: no transpose */
+    return report(spmv_shim_attention_gqa_backward_lse(st->dev, heads, kv_heads, (int) st->opts.v[SPMV_OPT_ATTENTION_BACKWARD_HEADS], k, dv, scale, Q, ldq, K, ldk, V, ldv, B, ldb,
+                                                       G, ldg, O, ldo, L, ldl, dQ, lddq, dK, lddk, dV, lddv, dB, lddb), where); /* a plane stride below nnz: refused there, nothing written */
+}
+
+double spmv_hip_time_attention_gqa_backward_lse_launches(spmv_Handle_t h, int heads, int kv_heads, int k, int dv, double scale, const void *Q, long long ldq, const void *K,
+                                                         long long ldk, const void *V, long long ldv, const void *B, long long ldb, const void *G, long long ldg, const void *O,
+                                                         long long ldo, const void *L, long long ldl, void *dQ, long long lddq, void *dK, long long lddk, void *dV, long long lddv,
+                                                         void *dB, long long lddb, int warmup, int iters, float *ms_out)
+{
+    const char *where = "time_attention_gqa_backward_lse_launches";
+    spmv_hip_state *st;
+    if (attention_gqa_backward_args(h, where, heads, kv_heads, k, dv, Q, ldq, K, ldk, V, ldv, G, ldg, dQ, lddq, dK, lddk, dV, lddv, 1) ||
+        attention_lse_inputs(where, heads, dv, O, ldo, L, ldl, 1)) return -1.0;
+    if ((B && ldb < 0) || (dB && lddb < 0)) { (void) refuse(SPMV_HIP_E_ARG, where, "need ldb >= 0 and lddb >= 0"); return -1.0; }
+    if (resident_state(h, where, RESIDENT_NOT_REORDERED, &st) || attention_backward_tables(h, st, where, dK || dV)) return -1.0;
+    return report_time(spmv_shim_time_attention_gqa_backward_lse(st->dev, heads, kv_heads, (int) st->opts.v[SPMV_OPT_ATTENTION_BACKWARD_HEADS], k, dv, scale, Q, ldq, K, ldk, V,
+                                                                 ldv, B, ldb, G, ldg, O, ldo, L, ldl, dQ, lddq, dK, lddk, dV, lddv, dB, lddb, warmup, iters, ms_out), where);
 }

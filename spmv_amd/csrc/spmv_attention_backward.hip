@@ -11,7 +11,7 @@
 namespace spmv {
 
 // the row pass over A: P and dS into the handle's arrays, dQ; BIAS: the bias read and dB written as well
-template <typename T, int CW, bool VEC, bool BIAS, bool GROUPED>
+template <typename T, int CW, bool VEC, bool BIAS, bool GROUPED, bool STATS = false>
 static void attention_bwd_rows_cw(const AttentionBwdArgs &a, hipStream_t stream)
 {
     constexpr int waves = kBlock / kWave;
@@ -22,13 +22,14 @@ static void attention_bwd_rows_cw(const AttentionBwdArgs &a, hipStream_t stream)
     T *dq = (T *) a.dq, *p = (T *) a.p, *ds = (T *) a.ds;
     const T *bias = (const T *) a.bias;
     T *db = (T *) a.db;
+    const T *o = STATS ? (const T *) a.o : nullptr, *lse = STATS ? (const T *) a.lse : nullptr;
     if (a.nb > 0)
-        attention_bwd_rows_kernel<T, CW, VEC, BIAS, GROUPED><<<(a.nb + waves - 1) / waves, kBlock, 0, stream>>>(a.nb, a.split, a.rowptr, a.colidx, a.heads, a.plane, a.k, a.dv, cwd, lgk, scale,
+        attention_bwd_rows_kernel<T, CW, VEC, BIAS, GROUPED, STATS><<<(a.nb + waves - 1) / waves, kBlock, 0, stream>>>(a.nb, a.split, a.rowptr, a.colidx, a.heads, a.plane, a.k, a.dv, cwd, lgk, scale,
                                                                                                q, a.ldq, kk, a.ldk, v, a.ldv, g, a.ldg, dq, a.lddq, a.dvo ? p : nullptr,
-                                                                                               a.dk ? ds : nullptr, bias, a.ldb, db, a.lddb, a.gs, a.gpos);
+                                                                                               a.dk ? ds : nullptr, bias, a.ldb, db, a.lddb, a.gs, a.gpos, o, a.ldo, lse, a.ldl);
     if (a.nlong > 0)
-        attention_bwd_long_kernel<T, CW, VEC, BIAS, GROUPED><<<a.nlong < a.cus * 8 ? a.nlong : a.cus * 8, kBlock, 0, stream>>>(a.nlong, a.longs, a.rowptr, a.colidx, a.heads, a.plane, a.k, a.dv, cwd, lgk,
-                                                                                                              scale, q, a.ldq, kk, a.ldk, v, a.ldv, g, a.ldg, dq, a.lddq, p, ds, bias, a.ldb, db, a.lddb, a.gs, a.gpos);
+        attention_bwd_long_kernel<T, CW, VEC, BIAS, GROUPED, STATS><<<a.nlong < a.cus * 8 ? a.nlong : a.cus * 8, kBlock, 0, stream>>>(a.nlong, a.longs, a.rowptr, a.colidx, a.heads, a.plane, a.k, a.dv, cwd, lgk,
+                                                                                                              scale, q, a.ldq, kk, a.ldk, v, a.ldv, g, a.ldg, dq, a.lddq, p, ds, bias, a.ldb, db, a.lddb, a.gs, a.gpos, o, a.ldo, lse, a.ldl);
 }
 
 // panel `c` of the column pass over A^T: kcv columns of dV, kck columns of dK
@@ -61,7 +62,9 @@ static void attention_bwd_round(const AttentionBwdArgs &a, hipStream_t stream)
     // a bias or a wanted dB has instantiations of its own: without them, the row kernels are the code without the bias's loads, addition and store
     if (a.m > 0)
         with_width(panel_group_width<T>(a.k), [&](auto CW) {
-            if (a.bias || a.db) attention_bwd_rows_cw<T, decltype(CW)::value, VEC, true, GROUPED>(a, stream);
+            // the final O and L given: the STATS instantiations (BIAS ones, a bias and a wanted dB or not)
+            if (a.o && a.lse) attention_bwd_rows_cw<T, decltype(CW)::value, VEC, true, GROUPED, true>(a, stream);
+            else if (a.bias || a.db) attention_bwd_rows_cw<T, decltype(CW)::value, VEC, true, GROUPED>(a, stream);
             else attention_bwd_rows_cw<T, decltype(CW)::value, VEC, false, GROUPED>(a, stream);
         });
     if (!a.dk && !a.dvo) return;
@@ -94,6 +97,8 @@ static void attention_bwd_launch_t(const AttentionBwdArgs &a, hipStream_t stream
         if (a.dvo) r.dvo = (T *) a.dvo + gv;
         if (a.bias) r.bias = (const T *) a.bias + (long long) h0 * a.ldb; // the round's first planes: dB goes straight to the caller's, at head h0 + g
         if (a.db) r.db = (T *) a.db + (long long) h0 * a.lddb;
+        if (a.o) r.o = (const T *) a.o + cv;
+        if (a.lse) r.lse = (const T *) a.lse + (long long) h0 * a.ldl;
         if (gs > 1) attention_bwd_round<T, VEC, true>(r, stream);
         else attention_bwd_round<T, VEC, false>(r, stream);
     }

@@ -163,6 +163,20 @@ int spmv_shim_attention_gqa(spmv_dev *d, int heads, int kv_heads, int k, int dv,
 double spmv_shim_time_attention_gqa(spmv_dev *d, int heads, int kv_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
                                     const void *v, long long ldv, const void *bias, long long ldb, void *o, long long ldo, int warmup, int iters, float *ms_out);
 
+/* with the rows' log-sum-exps (spmv_hip_attention_gqa_lse): lse NULL (ldl ignored: spmv_shim_attention_gqa) or `heads` planes ldl >= m apart, head h's
+ * row i at lse + h*ldl + i; host or device pointer.  ldl < m: SPMV_HIP_E_ARG, nothing written */
+int spmv_shim_attention_gqa_lse(spmv_dev *d, int heads, int kv_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v,
+                                long long ldv, const void *bias, long long ldb, void *o, long long ldo, void *lse, long long ldl);
+double spmv_shim_time_attention_gqa_lse(spmv_dev *d, int heads, int kv_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
+                                        const void *v, long long ldv, const void *bias, long long ldb, void *o, long long ldo, void *lse, long long ldl, int warmup, int iters,
+                                        float *ms_out);
+/* two partial results merged by their log-sum-exps (spmv_hip_attention_merge): the O operands m x heads*dv, the L operands `heads` planes of m; o may
+ * be o1 and l may be l1; l NULL: not wanted.  The matrix is not read.  A plane stride below m: SPMV_HIP_E_ARG, nothing written */
+int spmv_shim_attention_merge(spmv_dev *d, int heads, int dv, const void *o1, long long ldo1, const void *l1, long long ldl1, const void *o2, long long ldo2, const void *l2,
+                              long long ldl2, void *o, long long ldo, void *l, long long ldl);
+double spmv_shim_time_attention_merge(spmv_dev *d, int heads, int dv, const void *o1, long long ldo1, const void *l1, long long ldl1, const void *o2, long long ldo2,
+                                      const void *l2, long long ldl2, void *o, long long ldo, void *l, long long ldl, int warmup, int iters, float *ms_out);
+
 /* ---- dQ, dK, dV of the fused attention in two passes (shim/attention_backward.hpp; spmv_hip_attention_backward) ----
  * Q m x k, K n x k, V n x dv, G m x dv; dq m x k, dk n x k, dv_out n x dv or NULL (not wanted); row-major with leading dimensions; host or
  * device pointers each.  Needs the resident ColIdx and, when dk or dv_out is wanted, the attached transpose with its column indices resident
@@ -205,6 +219,16 @@ double spmv_shim_time_attention_gqa_backward(spmv_dev *d, int heads, int kv_head
                                              long long ldk, const void *v, long long ldv, const void *bias, long long ldb, const void *g, long long ldg, void *dq,
                                              long long lddq, void *dk, long long lddk, void *dv_out, long long lddv, void *db, long long lddb, int warmup, int iters,
                                              float *ms_out);
+
+/* driven by the final output o (m x heads*dv) and log-sum-exp lse (`heads` planes ldl >= m apart) of the attention this handle's entries are a part
+ * of (spmv_hip_attention_gqa_backward_lse): P = exp(t - L), D = <G row, O row>; everything else as above */
+int spmv_shim_attention_gqa_backward_lse(spmv_dev *d, int heads, int kv_heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk,
+                                         long long ldk, const void *v, long long ldv, const void *bias, long long ldb, const void *g, long long ldg, const void *o, long long ldo,
+                                         const void *lse, long long ldl, void *dq, long long lddq, void *dk, long long lddk, void *dv_out, long long lddv, void *db, long long lddb);
+double spmv_shim_time_attention_gqa_backward_lse(spmv_dev *d, int heads, int kv_heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk,
+                                                 long long ldk, const void *v, long long ldv, const void *bias, long long ldb, const void *g, long long ldg, const void *o,
+                                                 long long ldo, const void *lse, long long ldl, void *dq, long long lddq, void *dk, long long lddk, void *dv_out, long long lddv,
+                                                 void *db, long long lddb, int warmup, int iters, float *ms_out);
 
 /* the resident CSR arrays (device pointers; ColIdx may be NULL after spmv_shim_release_columns) */
 void spmv_shim_matrix_arrays(const spmv_dev *d, const int **rowptr, const int **colidx, const void **val);

@@ -39,6 +39,7 @@
 #include "kernels/sddmm.hpp"
 #include "kernels/row_softmax.hpp"
 #include "kernels/attention.hpp"
+#include "kernels/attention_merge.hpp"
 #include "kernels/attention_backward.hpp"
 
 using namespace spmv;
