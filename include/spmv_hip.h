@@ -521,6 +521,39 @@ int spmv_hip_attention_gqa_backward_lse(spmv_Handle_t handle, BASIC_INT_TYPE m, 
                                         void *dV, long long lddv,                /* n x kv_heads*dv, or NULL */
                                         void *dB, long long lddb);               /* heads planes of nnz, or NULL */
 
+/* ---- the forward on 16-bit Q, K and V (fp16 / bf16), with O in that type or in fp32 ------------------------------------------
+ * spmv_hip_attention_gqa_lse for callers that keep Q, K and V in a 16-bit type: the kernels load the 16-bit elements, widen them in registers and
+ * run the fp32 arithmetic unchanged, so nothing is widened in memory and the gathers of K and V rows move two bytes per element.
+ *   - Handle and types: the handle is an fp32 handle (data_size == 4; an fp64 handle: SPMV_HIP_E_ARG).  io_type is SPMV_HIP_T_F16 (IEEE binary16) or
+ *     SPMV_HIP_T_BF16, the element type of Q, K and V; o_type is SPMV_HIP_T_HANDLE (O is fp32) or equal to io_type (O in that type); anything else is
+ *     SPMV_HIP_E_ARG.  Leading dimensions count elements of the operand's own type: ldq, ldk and ldv 16-bit elements, ldo elements of O's type.  B and L
+ *     are fp32, exactly as in spmv_hip_attention_gqa_lse (ldb == 0: one shared plane; B == NULL: no bias; L == NULL: no L is stored).
+ *   - Bits, o_type == SPMV_HIP_T_HANDLE: O and L have exactly the bits spmv_hip_attention_gqa_lse writes when called with Q, K and V converted
+ *     element by element to fp32.  That conversion is exact -- fp16 subnormals keep their values, infinities and NaN stay what they are --, and the
+ *     lane mapping is the fp32 kernels' (4 columns per lane), so everything promised there holds unchanged: the order, the special values, head h
+ *     equal to the one-head call on its slices, and invariance under leading dimensions, alignment, access width, pointer kind, method, stream
+ *     and async.
+ *   - Bits, o_type == io_type: each element of O is that fp32 value rounded ONCE to the 16-bit type, to nearest, ties to even: fp16 overflow gives
+ *     +-inf, NaN stays NaN, the sign of zero is kept, small results become subnormals (what torch.Tensor.to(dtype) does to the fp32 result).  Rows
+ *     without entries get +0.  L has the same bits in both modes.
+ *   - Access width: a lane's segment of 4 columns is 8 bytes of a 16-bit operand; 8-byte accesses are used when pointer and ld * 2 are multiples
+ *     of 8 for Q, K, V and a 16-bit O (16 for an fp32 O), and with heads > 1 also k * 2 and dv * 2; 2-byte accesses otherwise.  The width changes no bit.
+ *   - Writes: exactly heads*dv elements of each of the m rows of O, in O's type, and exactly m elements per plane of L; padding is never read or
+ *     written.  m == 0 writes nothing.
+ *   - Memory: host or device pointers per operand.  A host Q, K, V or 16-bit O is staged through the handle-owned buffers of
+ *     spmv_hip_attention_gqa_lse at two bytes per element; with device operands device_bytes is spmv_hip_attention_gqa_lse's.
+ *   - Errors: the type rules above and every argument rule of spmv_hip_attention_gqa_lse are SPMV_HIP_E_ARG before the handle's state is looked at,
+ *     every output untouched.  Handle kinds and SPMV_HIP_E_NOSTATE as there.  The gradients are spmv_hip_attention_gqa_backward's on fp32 copies. */
+enum { SPMV_HIP_T_HANDLE = 0, SPMV_HIP_T_F16 = 1, SPMV_HIP_T_BF16 = 2 };
+
+int spmv_hip_attention_gqa_lse_16(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                                  const void *Matrix_Val, int heads, int kv_heads, int k, int dv, double scale,
+                                  int io_type,                             /* SPMV_HIP_T_F16 or SPMV_HIP_T_BF16: the element type of Q, K and V */
+                                  const void *Q, long long ldq, const void *K, long long ldk, const void *V, long long ldv,
+                                  const void *B, long long ldb,            /* bias planes in the HANDLE's precision (fp32), one shared plane, or NULL */
+                                  void *O, long long ldo, int o_type,      /* SPMV_HIP_T_HANDLE: fp32 O; or == io_type: O in that 16-bit type */
+                                  void *L, long long ldl);                 /* fp32 planes, or NULL */
+
 /* ---- options --------------------------------------------------------------------------------
  * Resolved once per handle, at create: process-wide value (spmv_hip_set_option / env), overridden by the
  * calling thread's value (spmv_hip_set_thread_option) -- so two threads can create differently tuned handles

@@ -73,6 +73,10 @@ double spmv_hip_time_attention_gqa_backward_launches(spmv_Handle_t handle, int h
 double spmv_hip_time_attention_gqa_lse_launches(spmv_Handle_t handle, int heads, int kv_heads, int k, int dv, double scale, const void *Q, long long ldq, const void *K,
                                                 long long ldk, const void *V, long long ldv, const void *B, long long ldb, void *O, long long ldo, void *L, long long ldl,
                                                 int warmup, int iters, float *ms_out);
+/* The same for spmv_hip_attention_gqa_lse_16 (io_type ahead of Q, o_type behind ldo, as there; DEVICE pointers). */
+double spmv_hip_time_attention_gqa_lse_16_launches(spmv_Handle_t handle, int heads, int kv_heads, int k, int dv, double scale, int io_type, const void *Q, long long ldq,
+                                                   const void *K, long long ldk, const void *V, long long ldv, const void *B, long long ldb, void *O, long long ldo, int o_type,
+                                                   void *L, long long ldl, int warmup, int iters, float *ms_out);
 double spmv_hip_time_attention_merge_launches(spmv_Handle_t handle, int heads, int dv, const void *O1, long long ldo1, const void *L1, long long ldl1, const void *O2,
                                               long long ldo2, const void *L2, long long ldl2, void *O, long long ldo, void *L, long long ldl, int warmup, int iters,
                                               float *ms_out);

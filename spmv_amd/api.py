@@ -164,6 +164,11 @@ FUNCTIONS = {
     "spmv_hip_time_attention_gqa_lse_launches": (C.c_double, [spmv_Handle_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong,
                                                               _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, C.c_int, C.c_int,
                                                               C.POINTER(C.c_float)]),
+    "spmv_hip_attention_gqa_lse_16": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _V, C.c_longlong, _V, C.c_longlong,
+                                                _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, C.c_int, _V, C.c_longlong]),
+    "spmv_hip_time_attention_gqa_lse_16_launches": (C.c_double, [spmv_Handle_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _V, C.c_longlong, _V, C.c_longlong,
+                                                                 _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, C.c_int, _V, C.c_longlong, C.c_int, C.c_int,
+                                                                 C.POINTER(C.c_float)]),
     "spmv_hip_attention_merge": (C.c_int, [spmv_Handle_t, C.c_int, C.c_int, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong,
                                            _V, C.c_longlong, _V, C.c_longlong]),
     "spmv_hip_time_attention_merge_launches": (C.c_double, [spmv_Handle_t, C.c_int, C.c_int, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong,
@@ -773,6 +778,49 @@ def time_attention_gqa_lse_launches(handle, heads, kv_heads, Q, K, V, B, O, L, s
                                                                pl, ll), warmup, iters)
 
 
+T_HANDLE, T_F16, T_BF16 = 0, 1, 2   # include/spmv_hip.h: SPMV_HIP_T_*
+
+
+def _types_16(Q, K, V, O):
+    """-> (io_type, o_type) of an attention_gqa_lse_16 call from the operands' dtypes: Q, K and V torch tensors (CPU or device) that are all
+    torch.float16 or all torch.bfloat16; O of that dtype or torch.float32"""
+    import torch
+    codes = {torch.float16: T_F16, torch.bfloat16: T_BF16}
+    for t, name in ((Q, "Q"), (K, "K"), (V, "V"), (O, "O")):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor (numpy has no bfloat16), not {type(t).__name__}")
+    if Q.dtype not in codes or K.dtype != Q.dtype or V.dtype != Q.dtype:
+        raise TypeError(f"Q, K and V must all be torch.float16 or all torch.bfloat16, not {Q.dtype}, {K.dtype} and {V.dtype}")
+    if O.dtype != Q.dtype and O.dtype != torch.float32:
+        raise TypeError(f"O must be {Q.dtype} or torch.float32, not {O.dtype}")
+    return codes[Q.dtype], (T_HANDLE if O.dtype == torch.float32 else codes[Q.dtype])
+
+
+def attention_gqa_lse_16(handle, m, RowPtr, ColIdx, Matrix_Val, heads, kv_heads, Q, K, V, B, O, L=None, scale=None, check=True, ldb=None, ldl=None):
+    """attention_gqa_lse() on 16-bit Q, K and V over an fp32 handle (spmv_hip_attention_gqa_lse_16): Q, K and V are torch tensors, all
+    torch.float16 or all torch.bfloat16, on the CPU or the device; O is a tensor of that dtype or of torch.float32; B (None, (nnz,) or (heads, nnz))
+    and L (None or (heads, m)) are fp32.  An fp32 O and L have the bits of attention_gqa_lse() on Q.float(), K.float(), V.float(); a 16-bit O is that
+    result rounded once, O32.to(dtype).  Row strides are passed as leading dimensions in elements of each tensor's own dtype.  -> the return code."""
+    io_type, o_type = _types_16(Q, K, V, O)
+    k, dv, pq, ldq, pk, ldk, pv, ldv, po, ldo = _attention_gqa_blocks(heads, kv_heads, Q, K, V, O)
+    scale = 1.0 / np.sqrt(k) if scale is None and k > 0 else (0.0 if scale is None else scale)
+    pb, ld = (_ptr(B), int(ldb)) if ldb is not None else _planes(B, "B", heads, True)
+    pl, ll = (_ptr(L), int(ldl)) if ldl is not None else _lse_planes(L, "L", heads)
+    return _checked(load().spmv_hip_attention_gqa_lse_16(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), int(heads), int(kv_heads), k, dv, float(scale),
+                                                         io_type, pq, ldq, pk, ldk, pv, ldv, pb, ld, po, ldo, o_type, pl, ll), "spmv_hip_attention_gqa_lse_16", check)
+
+
+def time_attention_gqa_lse_16_launches(handle, heads, kv_heads, Q, K, V, B, O, L=None, scale=None, warmup=10, iters=100):
+    """-> (mean_ms, per-call ms array) of spmv_hip_attention_gqa_lse_16 on device operands (spmv_hip_time_attention_gqa_lse_16_launches)."""
+    io_type, o_type = _types_16(Q, K, V, O)
+    k, dv, pq, ldq, pk, ldk, pv, ldv, po, ldo = _attention_gqa_blocks(heads, kv_heads, Q, K, V, O)
+    scale = 1.0 / np.sqrt(k) if scale is None else scale
+    pb, ld = _planes(B, "B", heads, True)
+    pl, ll = _lse_planes(L, "L", heads)
+    return _timed("spmv_hip_time_attention_gqa_lse_16_launches", (handle, int(heads), int(kv_heads), k, dv, float(scale), io_type, pq, ldq, pk, ldk, pv, ldv, pb, ld,
+                                                                  po, ldo, o_type, pl, ll), warmup, iters)
+
+
 def _attention_merge_args(heads, O1, L1, O2, L2, O, L, ldl):
     """-> (dv, the C arguments from O1 on) of an attention_merge call; ldl: None, or the plane strides (ldl1, ldl2, ldl) of flat L buffers"""
     heads = int(heads)
@@ -1083,6 +1131,20 @@ class Handle:
             lse = self._like(Q, (int(heads), self.m))
         rp, ci, va = self._keep
         attention_gqa_lse(self.h, self.m, rp, ci, va, heads, kv_heads, Q, K, V, bias, out, lse, scale)
+        return out, lse
+
+    def attention_gqa_lse_16(self, Q, K, V, heads, kv_heads, B=None, scale=None, out_dtype=None, want_l=True):
+        """-> (out, lse): attention_gqa_lse() on torch.float16 or torch.bfloat16 Q, K and V over this fp32 handle (spmv_hip_attention_gqa_lse_16).
+        out is (m, heads*dv) of out_dtype -- None: Q's dtype; or torch.float32 --, allocated on Q's device; lse is (heads, m) fp32, None when
+        want_l is False; B is fp32.  An fp32 out and lse have the bits of attention_gqa_lse() on the .float() copies; a 16-bit out is that result
+        rounded once."""
+        import torch
+        if not isinstance(Q, torch.Tensor) or not isinstance(V, torch.Tensor):
+            raise TypeError("Q, K and V must be torch tensors")
+        out = torch.empty((self.m, (V.shape[1] // int(kv_heads)) * int(heads)), dtype=Q.dtype if out_dtype is None else out_dtype, device=Q.device)
+        lse = torch.empty((int(heads), self.m), dtype=torch.float32, device=Q.device) if want_l else None
+        rp, ci, va = self._keep
+        attention_gqa_lse_16(self.h, self.m, rp, ci, va, heads, kv_heads, Q, K, V, B, out, lse, scale)
         return out, lse
 
     def attention_merge(self, O1, L1, O2, L2, heads, out=None, lse=None, want_lse=True):

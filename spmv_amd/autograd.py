@@ -27,6 +27,11 @@ library's kernels forward and backward (Handle.sddmm / row_softmax / spmm; Handl
 Both take a trailing keyword bias=None: a tensor of (nnz,) -- one plane, shared by all heads -- or (heads, nnz), in CSR order, added to the
 scaled scores before the softmax (Handle.attention_bias), which receives a gradient (Handle.attention_bias_backward).
 
+attention, attention_heads and attention_parts also take Q, K and V that are all torch.float16 or all torch.bfloat16 on a float32 handle
+(Handle.attention_gqa_lse_16: the kernels read the 16-bit elements and compute in float32): the result and the gradients of Q, K and V have
+that dtype and are the float32 results of the same function on .float() copies, each rounded once with .to(dtype); the bias and its gradient
+stay float32.
+
 Every call runs on torch's current stream.  The only module of the package that needs torch; libspmv_hip.so has no torch dependency.
 """
 from __future__ import annotations
@@ -49,10 +54,21 @@ def _handle_device(handle):
     return handle._ag_device
 
 
-def _check_tensor(t, name, handle):
+_HALF = (torch.float16, torch.bfloat16)
+
+
+def _io_dtype(handle, *tensors):
+    """the dtype Q, K and V must have: the handle's, or -- on a float32 handle, when every one of them is float16 or every one bfloat16 -- that type"""
+    hd = _handle_dtype(handle)
+    if hd == torch.float32 and all(isinstance(t, torch.Tensor) for t in tensors) and tensors[0].dtype in _HALF and all(t.dtype == tensors[0].dtype for t in tensors):
+        return tensors[0].dtype
+    return hd
+
+
+def _check_tensor(t, name, handle, dtype=None):
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{name} must be a torch.Tensor, not {type(t).__name__}")
-    if t.dtype != _handle_dtype(handle):
+    if t.dtype != (_handle_dtype(handle) if dtype is None else dtype):
         raise TypeError(f"{name} is {t.dtype}, the handle holds {_handle_dtype(handle)}")
     if t.device.type != "cuda" or t.device.index != _handle_device(handle):
         raise TypeError(f"{name} is on {t.device}, the handle lives on cuda:{_handle_device(handle)}")
@@ -262,45 +278,55 @@ class _Attention(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, G):
-        handle, scale = ctx.handle, ctx.scale
         Q2, K2, V2, B2 = ctx.saved_tensors
-        need_q, need_k, need_v = ctx.needs_input_grad[1:4]
-        need_b = B2 is not None and ctx.needs_input_grad[5]
-        dQ = dK = dV = dB = None
-        if not (need_q or need_k or need_v or need_b):
-            return None, None, None, None, None, None
-        if handle.nnz == 0:   # no stored entry: O is zero whatever Q, K and V are
-            return None, (torch.zeros_like(Q2) if need_q else None), (torch.zeros_like(K2) if need_k else None), (torch.zeros_like(V2) if need_v else None), None, \
-                (torch.zeros_like(B2) if need_b else None)
-        _on_current_stream(handle)
-        G2 = _block(G, G.shape[1])
-        S = handle.sddmm(Q2, K2)
-        S.mul_(scale)
-        if B2 is not None:
-            S.add_(B2.view(-1))   # a rounding of its own after the scaling's: the fused kernels' two steps
-        P = handle.row_softmax(S, out=S)
-        # A_P, then A_dS = A's pattern with those values, for the duration: the handle's own values, and what matmul() remembers of them, come back below
-        keep, token, ref = handle._keep[2], getattr(handle, "_values_token", None), getattr(handle, "_values_ref", None)
-        try:
-            if need_v:
-                handle.update_values(P)
-                dV = handle.spmm_transpose(G2)
-            if need_q or need_k or need_b:
-                dP = handle.sddmm(G2, V2)
-                dS = handle.row_softmax_backward(P, dP, out=dP)
-                if need_b:   # the bias enters after the scaling: its gradient is dS before it
-                    dB = dS.clone().view(B2.shape) if need_q or need_k else dS.view(B2.shape)
-            if need_q or need_k:
-                dS.mul_(scale)
-                handle.update_values(dS)
-                if need_q:
-                    dQ = handle.spmm(K2)
-                if need_k:
-                    dK = handle.spmm_transpose(Q2)
-        finally:
-            handle.update_values(keep)
-            handle._values_token, handle._values_ref = token, ref
+        need = tuple(bool(x) for x in ctx.needs_input_grad[1:4])
+        dQ, dK, dV, dB = _attention_backward_composed(ctx.handle, ctx.scale, Q2, K2, V2, B2, G, need, B2 is not None and bool(ctx.needs_input_grad[5]))
         return None, dQ, dK, dV, None, dB
+
+
+def _zero_grads(Q2, K2, V2, B2, need, need_b):
+    """no stored entry: O is zero whatever Q, K and V are"""
+    return (torch.zeros_like(Q2) if need[0] else None), (torch.zeros_like(K2) if need[1] else None), (torch.zeros_like(V2) if need[2] else None), \
+        (torch.zeros_like(B2) if need_b else None)
+
+
+def _attention_backward_composed(handle, scale, Q2, K2, V2, B2, G, need, need_b):
+    """-> (dQ, dK, dV, dB) of attention(): S and P computed again and the existing operations composed, only for the gradients asked for"""
+    need_q, need_k, need_v = need
+    dQ = dK = dV = dB = None
+    if not (need_q or need_k or need_v or need_b):
+        return None, None, None, None
+    if handle.nnz == 0:
+        return _zero_grads(Q2, K2, V2, B2, need, need_b)
+    _on_current_stream(handle)
+    G2 = _block(G, G.shape[1])
+    S = handle.sddmm(Q2, K2)
+    S.mul_(scale)
+    if B2 is not None:
+        S.add_(B2.view(-1))   # a rounding of its own after the scaling's: the fused kernels' two steps
+    P = handle.row_softmax(S, out=S)
+    # A_P, then A_dS = A's pattern with those values, for the duration: the handle's own values, and what matmul() remembers of them, come back below
+    keep, token, ref = handle._keep[2], getattr(handle, "_values_token", None), getattr(handle, "_values_ref", None)
+    try:
+        if need_v:
+            handle.update_values(P)
+            dV = handle.spmm_transpose(G2)
+        if need_q or need_k or need_b:
+            dP = handle.sddmm(G2, V2)
+            dS = handle.row_softmax_backward(P, dP, out=dP)
+            if need_b:   # the bias enters after the scaling: its gradient is dS before it
+                dB = dS.clone().view(B2.shape) if need_q or need_k else dS.view(B2.shape)
+        if need_q or need_k:
+            dS.mul_(scale)
+            handle.update_values(dS)
+            if need_q:
+                dQ = handle.spmm(K2)
+            if need_k:
+                dK = handle.spmm_transpose(Q2)
+    finally:
+        handle.update_values(keep)
+        handle._values_token, handle._values_ref = token, ref
+    return dQ, dK, dV, dB
 
 
 class _AttentionFused(torch.autograd.Function):
@@ -321,15 +347,19 @@ class _AttentionFused(torch.autograd.Function):
     def backward(ctx, G):
         Q2, K2, V2, B2 = ctx.saved_tensors
         need = tuple(bool(x) for x in ctx.needs_input_grad[1:4])
-        need_b = B2 is not None and bool(ctx.needs_input_grad[5])
-        if not (any(need) or need_b):
-            return None, None, None, None, None, None
-        _on_current_stream(ctx.handle)
-        if B2 is None:
-            dQ, dK, dV = ctx.handle.attention_backward(Q2, K2, V2, _block(G, G.shape[1]), ctx.scale, need=need)
-            return None, dQ, dK, dV, None, None
-        dQ, dK, dV, dB = ctx.handle.attention_bias_backward(Q2, K2, V2, B2, _block(G, G.shape[1]), 1, ctx.scale, need=(*need, need_b))
-        return None, dQ, dK, dV, None, _bias_grad(dB, B2)
+        dQ, dK, dV, dB = _attention_backward_fused(ctx.handle, ctx.scale, Q2, K2, V2, B2, G, need, B2 is not None and bool(ctx.needs_input_grad[5]))
+        return None, dQ, dK, dV, None, dB
+
+
+def _attention_backward_fused(handle, scale, Q2, K2, V2, B2, G, need, need_b):
+    """-> (dQ, dK, dV, dB) of attention() from ONE Handle.attention_backward / attention_bias_backward call"""
+    if not (any(need) or need_b):
+        return None, None, None, None
+    _on_current_stream(handle)
+    if B2 is None:
+        return (*handle.attention_backward(Q2, K2, V2, _block(G, G.shape[1]), scale, need=need), None)
+    dQ, dK, dV, dB = handle.attention_bias_backward(Q2, K2, V2, B2, _block(G, G.shape[1]), 1, scale, need=(*need, need_b))
+    return dQ, dK, dV, _bias_grad(dB, B2)
 
 
 class _AttentionHeads(torch.autograd.Function):
@@ -349,40 +379,42 @@ class _AttentionHeads(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, G):
-        from . import api
-        handle, heads, scale = ctx.handle, ctx.heads, ctx.scale
         Q2, K2, V2, B2 = ctx.saved_tensors
         need = tuple(bool(x) for x in ctx.needs_input_grad[1:4])
-        need_b = B2 is not None and bool(ctx.needs_input_grad[7])
-        if not (any(need) or need_b):
-            return None, None, None, None, None, None, None, None
-        if handle.nnz == 0:   # no stored entry: O is zero whatever Q, K and V are
-            return None, (torch.zeros_like(Q2) if need[0] else None), (torch.zeros_like(K2) if need[1] else None), (torch.zeros_like(V2) if need[2] else None), None, None, None, \
-                (torch.zeros_like(B2) if need_b else None)
-        _on_current_stream(handle)
-        G2 = _block(G, G.shape[1])
-        if ctx.fused:   # every head in one call
-            if B2 is None:
-                dQ, dK, dV = handle.attention_heads_backward(Q2, K2, V2, G2, heads, scale, need=need)
-                return None, dQ, dK, dV, None, None, None, None
-            dQ, dK, dV, dB = handle.attention_bias_backward(Q2, K2, V2, B2, G2, heads, scale, need=(*need, need_b))
-            return None, dQ, dK, dV, None, None, None, _bias_grad(dB, B2)
-        k, dv = Q2.shape[1] // heads, V2.shape[1] // heads
-        dQ = torch.empty_like(Q2, memory_format=torch.contiguous_format) if need[0] else None
-        dK = torch.empty_like(K2, memory_format=torch.contiguous_format) if need[1] else None
-        dV = torch.empty_like(V2, memory_format=torch.contiguous_format) if need[2] else None
-        dB = Q2.new_empty((heads, handle.nnz)) if need_b else None
-        rp, ci, va = handle._keep
-        for h in range(heads):
-            ck, cv = slice(h * k, (h + 1) * k), slice(h * dv, (h + 1) * dv)
-            if B2 is None:
-                api.attention_backward(handle.h, handle.m, rp, ci, va, Q2[:, ck], K2[:, ck], V2[:, cv], G2[:, cv],
-                                       None if dQ is None else dQ[:, ck], None if dK is None else dK[:, ck], None if dV is None else dV[:, cv], scale)
-            else:   # one head on its column slices and on its plane of the bias and of dB
-                api.attention_bias_backward(handle.h, handle.m, rp, ci, va, 1, Q2[:, ck], K2[:, ck], V2[:, cv], B2 if B2.dim() == 1 else B2[h], G2[:, cv],
-                                            None if dQ is None else dQ[:, ck], None if dK is None else dK[:, ck], None if dV is None else dV[:, cv],
-                                            None if dB is None else dB[h], scale)
-        return None, dQ, dK, dV, None, None, None, _bias_grad(dB, B2)
+        dQ, dK, dV, dB = _attention_heads_backward(ctx.handle, ctx.heads, ctx.scale, ctx.fused, Q2, K2, V2, B2, G, need, B2 is not None and bool(ctx.needs_input_grad[7]))
+        return None, dQ, dK, dV, None, None, None, dB
+
+
+def _attention_heads_backward(handle, heads, scale, fused, Q2, K2, V2, B2, G, need, need_b):
+    """-> (dQ, dK, dV, dB) of attention_heads() without kv_heads: one call for all heads (fused) or one single-head call per head on column slices"""
+    from . import api
+    if not (any(need) or need_b):
+        return None, None, None, None
+    if handle.nnz == 0:
+        return _zero_grads(Q2, K2, V2, B2, need, need_b)
+    _on_current_stream(handle)
+    G2 = _block(G, G.shape[1])
+    if fused:   # every head in one call
+        if B2 is None:
+            return (*handle.attention_heads_backward(Q2, K2, V2, G2, heads, scale, need=need), None)
+        dQ, dK, dV, dB = handle.attention_bias_backward(Q2, K2, V2, B2, G2, heads, scale, need=(*need, need_b))
+        return dQ, dK, dV, _bias_grad(dB, B2)
+    k, dv = Q2.shape[1] // heads, V2.shape[1] // heads
+    dQ = torch.empty_like(Q2, memory_format=torch.contiguous_format) if need[0] else None
+    dK = torch.empty_like(K2, memory_format=torch.contiguous_format) if need[1] else None
+    dV = torch.empty_like(V2, memory_format=torch.contiguous_format) if need[2] else None
+    dB = Q2.new_empty((heads, handle.nnz)) if need_b else None
+    rp, ci, va = handle._keep
+    for h in range(heads):
+        ck, cv = slice(h * k, (h + 1) * k), slice(h * dv, (h + 1) * dv)
+        if B2 is None:
+            api.attention_backward(handle.h, handle.m, rp, ci, va, Q2[:, ck], K2[:, ck], V2[:, cv], G2[:, cv],
+                                   None if dQ is None else dQ[:, ck], None if dK is None else dK[:, ck], None if dV is None else dV[:, cv], scale)
+        else:   # one head on its column slices and on its plane of the bias and of dB
+            api.attention_bias_backward(handle.h, handle.m, rp, ci, va, 1, Q2[:, ck], K2[:, ck], V2[:, cv], B2 if B2.dim() == 1 else B2[h], G2[:, cv],
+                                        None if dQ is None else dQ[:, ck], None if dK is None else dK[:, ck], None if dV is None else dV[:, cv],
+                                        None if dB is None else dB[h], scale)
+    return dQ, dK, dV, _bias_grad(dB, B2)
 
 
 class _AttentionGqa(torch.autograd.Function):
@@ -404,42 +436,85 @@ class _AttentionGqa(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, G):
-        from . import api
-        handle, heads, kv_heads, scale = ctx.handle, ctx.heads, ctx.kv_heads, ctx.scale
+        Q2, K2, V2, B2 = ctx.saved_tensors
+        need = tuple(bool(x) for x in ctx.needs_input_grad[1:4])
+        dQ, dK, dV, dB = _attention_gqa_backward(ctx.handle, ctx.heads, ctx.kv_heads, ctx.scale, ctx.fused, Q2, K2, V2, B2, G, need,
+                                                 B2 is not None and bool(ctx.needs_input_grad[8]))
+        return None, dQ, dK, dV, None, None, None, None, dB
+
+
+def _attention_gqa_backward(handle, heads, kv_heads, scale, fused, Q2, K2, V2, B2, G, need, need_b):
+    """-> (dQ, dK, dV, dB) of attention_heads() with kv_heads: one Handle.attention_gqa_backward call (fused), or one single-head backward per query
+    head on its group's K / V slices, dK and dV of a group accumulated in torch in ascending head"""
+    from . import api
+    if not (any(need) or need_b):
+        return None, None, None, None
+    if handle.nnz == 0:
+        return _zero_grads(Q2, K2, V2, B2, need, need_b)
+    _on_current_stream(handle)
+    G2 = _block(G, G.shape[1])
+    if fused:   # every head in one call
+        dQ, dK, dV, dB = handle.attention_gqa_backward(Q2, K2, V2, B2, G2, heads, kv_heads, scale, need=(*need, need_b))
+        return dQ, dK, dV, _bias_grad(dB, B2)
+    gs, k, dv = heads // kv_heads, Q2.shape[1] // heads, V2.shape[1] // kv_heads
+    dQ = torch.empty_like(Q2, memory_format=torch.contiguous_format) if need[0] else None
+    dK = torch.empty_like(K2, memory_format=torch.contiguous_format) if need[1] else None
+    dV = torch.empty_like(V2, memory_format=torch.contiguous_format) if need[2] else None
+    dB = Q2.new_empty((heads, handle.nnz)) if need_b else None
+    tK = Q2.new_empty((handle.n, k)) if need[1] and gs > 1 else None   # one head's term of dK / dV: what the group's later heads add
+    tV = Q2.new_empty((handle.n, dv)) if need[2] and gs > 1 else None
+    rp, ci, va = handle._keep
+    for h in range(heads):
+        g, first = h // gs, h % gs == 0
+        cq, co, ck, cv = slice(h * k, (h + 1) * k), slice(h * dv, (h + 1) * dv), slice(g * k, (g + 1) * k), slice(g * dv, (g + 1) * dv)
+        oK = None if dK is None else (dK[:, ck] if first else tK)
+        oV = None if dV is None else (dV[:, cv] if first else tV)
+        api.attention_bias_backward(handle.h, handle.m, rp, ci, va, 1, Q2[:, cq], K2[:, ck], V2[:, cv], None if B2 is None else (B2 if B2.dim() == 1 else B2[h]),
+                                    G2[:, co], None if dQ is None else dQ[:, cq], oK, oV, None if dB is None else dB[h], scale)
+        if not first:   # (..(first + second) + ..) + this one: plain additions in ascending head
+            if dK is not None:
+                dK[:, ck] += tK
+            if dV is not None:
+                dV[:, cv] += tV
+    return dQ, dK, dV, _bias_grad(dB, B2)
+
+
+class _Attention16(torch.autograd.Function):
+    """float16 / bfloat16 Q, K and V on a float32 handle.  Forward: ONE Handle.attention_gqa_lse_16 call with O in that dtype (no L).  Backward: Q, K,
+    V and G widened to float32 and handed to the backward the float32 Function of the same arguments runs (_attention_backward_composed / _fused,
+    _attention_heads_backward or _attention_gqa_backward, in the `backward=` mode asked for); every gradient is its float32 gradient .to(dtype), the
+    bias gradient stays float32.  heads None: attention(); kv_heads None: as many K / V heads as query heads"""
+
+    @staticmethod
+    def forward(ctx, handle, Q, K, V, heads, kv_heads, scale, mode, bias=None):
+        Q2, K2, V2 = _block(Q.detach(), Q.shape[1]), _block(K.detach(), K.shape[1]), _block(V.detach(), V.shape[1])
+        B2 = _bias_planes(bias)
+        _on_current_stream(handle)
+        h = 1 if heads is None else heads
+        O, _ = handle.attention_gqa_lse_16(Q2, K2, V2, h, h if kv_heads is None else kv_heads, B2, scale, want_l=False)
+        ctx.handle, ctx.heads, ctx.kv_heads, ctx.scale, ctx.mode = handle, heads, kv_heads, scale, mode
+        ctx.save_for_backward(Q2, K2, V2, B2)
+        return O
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, G):
+        handle, heads, kv_heads, scale, mode = ctx.handle, ctx.heads, ctx.kv_heads, ctx.scale, ctx.mode
         Q2, K2, V2, B2 = ctx.saved_tensors
         need = tuple(bool(x) for x in ctx.needs_input_grad[1:4])
         need_b = B2 is not None and bool(ctx.needs_input_grad[8])
         if not (any(need) or need_b):
             return (None,) * 9
-        if handle.nnz == 0:   # no stored entry: O is zero whatever Q, K and V are
-            return None, (torch.zeros_like(Q2) if need[0] else None), (torch.zeros_like(K2) if need[1] else None), (torch.zeros_like(V2) if need[2] else None), None, None, None, \
-                None, (torch.zeros_like(B2) if need_b else None)
-        _on_current_stream(handle)
-        G2 = _block(G, G.shape[1])
-        if ctx.fused:   # every head in one call
-            dQ, dK, dV, dB = handle.attention_gqa_backward(Q2, K2, V2, B2, G2, heads, kv_heads, scale, need=(*need, need_b))
-            return None, dQ, dK, dV, None, None, None, None, _bias_grad(dB, B2)
-        gs, k, dv = heads // kv_heads, Q2.shape[1] // heads, V2.shape[1] // kv_heads
-        dQ = torch.empty_like(Q2, memory_format=torch.contiguous_format) if need[0] else None
-        dK = torch.empty_like(K2, memory_format=torch.contiguous_format) if need[1] else None
-        dV = torch.empty_like(V2, memory_format=torch.contiguous_format) if need[2] else None
-        dB = Q2.new_empty((heads, handle.nnz)) if need_b else None
-        tK = Q2.new_empty((handle.n, k)) if need[1] and gs > 1 else None   # one head's term of dK / dV: what the group's later heads add
-        tV = Q2.new_empty((handle.n, dv)) if need[2] and gs > 1 else None
-        rp, ci, va = handle._keep
-        for h in range(heads):
-            g, first = h // gs, h % gs == 0
-            cq, co, ck, cv = slice(h * k, (h + 1) * k), slice(h * dv, (h + 1) * dv), slice(g * k, (g + 1) * k), slice(g * dv, (g + 1) * dv)
-            oK = None if dK is None else (dK[:, ck] if first else tK)
-            oV = None if dV is None else (dV[:, cv] if first else tV)
-            api.attention_bias_backward(handle.h, handle.m, rp, ci, va, 1, Q2[:, cq], K2[:, ck], V2[:, cv], None if B2 is None else (B2 if B2.dim() == 1 else B2[h]),
-                                        G2[:, co], None if dQ is None else dQ[:, cq], oK, oV, None if dB is None else dB[h], scale)
-            if not first:   # (..(first + second) + ..) + this one: plain additions in ascending head
-                if dK is not None:
-                    dK[:, ck] += tK
-                if dV is not None:
-                    dV[:, cv] += tV
-        return None, dQ, dK, dV, None, None, None, None, _bias_grad(dB, B2)
+        wide, Gf = (Q2.float(), K2.float(), V2.float(), B2), G.float()
+        if heads is None:
+            out = (_attention_backward_fused if mode == "fused" else _attention_backward_composed)(handle, scale, *wide, Gf, need, need_b)
+        elif kv_heads is None:
+            out = _attention_heads_backward(handle, heads, scale, mode == "fused", *wide, Gf, need, need_b)
+        else:
+            out = _attention_gqa_backward(handle, heads, kv_heads, scale, mode == "fused", *wide, Gf, need, need_b)
+        dB = out[3]
+        dQ, dK, dV = (None if g is None else g.to(Q2.dtype) for g in out[:3])
+        return None, dQ, dK, dV, None, None, None, None, dB
 
 
 def _check_bias(bias, handle, heads):
@@ -477,12 +552,20 @@ def attention_heads(handle, Q, K, V, heads, scale=None, backward="per_head", *, 
     (n, kv_heads * k) and V (n, kv_heads * dv), heads a multiple of kv_heads, and query head h uses K / V head h // (heads // kv_heads) -- K and V
     are never expanded and are saved at their narrow width.  backward="fused" is one Handle.attention_gqa_backward call; the default mode calls
     the single-head backward per query head on its group's K / V slices and accumulates dK and dV of a group in torch in ascending head (the first
-    head assigned, the others +=), which is the fused call's chain: both modes give the same bits.  The bias stays per QUERY head."""
+    head assigned, the others +=), which is the fused call's chain: both modes give the same bits.  The bias stays per QUERY head.
+
+    16-bit tensors: on a float32 handle Q, K and V may all be torch.float16 or all torch.bfloat16 (mixed dtypes, or 16-bit tensors on a float64
+    handle, are a TypeError).  The forward is then ONE Handle.attention_gqa_lse_16 call -- the kernels read the 16-bit elements, compute in float32
+    and round O once -- and the backward widens Q, K, V and dL/dO to float32 and runs the float32 backward in the mode asked for (a 16-bit backward
+    kernel does not exist yet).  The contract: O is fp32_result.to(dtype) and every gradient of Q, K and V is fp32_gradient.to(dtype), where the
+    float32 results are those of this same function on Q.float(), K.float(), V.float() with dL/dO.float(); the bias and its gradient stay float32,
+    and the bias gradient has the float32 run's bits."""
     if backward not in ("per_head", "fused"):
         raise ValueError(f"backward must be 'per_head' or 'fused', not {backward!r}")
     _check_handle(handle)
+    dtype = _io_dtype(handle, Q, K, V)
     for t, name in ((Q, "Q"), (K, "K"), (V, "V")):
-        _check_tensor(t, name, handle)
+        _check_tensor(t, name, handle, dtype)
     heads = int(heads)
     if kv_heads is not None:
         kv_heads = int(kv_heads)
@@ -494,6 +577,8 @@ def attention_heads(handle, Q, K, V, heads, scale=None, backward="per_head", *, 
             raise ValueError(f"{Q.shape[1]} columns of Q, {K.shape[1]} of K and {V.shape[1]} of V are not {heads} query heads over {kv_heads} K / V heads of equal width")
         _check_bias(bias, handle, heads)
         scale = 1.0 / math.sqrt(Q.shape[1] // heads) if scale is None else float(scale)
+        if dtype in _HALF:
+            return _Attention16.apply(handle, Q, K, V, heads, kv_heads, scale, backward, bias)
         return _AttentionGqa.apply(handle, Q, K, V, heads, kv_heads, scale, backward == "fused", bias)
     if Q.dim() != 2 or K.dim() != 2 or V.dim() != 2 or Q.shape[0] != handle.m or K.shape[0] != handle.n or V.shape[0] != handle.n or \
             Q.shape[1] != K.shape[1] or Q.shape[1] < 1 or V.shape[1] < 1:
@@ -502,6 +587,8 @@ def attention_heads(handle, Q, K, V, heads, scale=None, backward="per_head", *, 
         raise ValueError(f"{Q.shape[1]} columns of Q / K and {V.shape[1]} of V are not {heads} heads of equal width")
     _check_bias(bias, handle, heads)
     scale = 1.0 / math.sqrt(Q.shape[1] // heads) if scale is None else float(scale)   # Handle.attention_heads' default, to the bit
+    if dtype in _HALF:
+        return _Attention16.apply(handle, Q, K, V, heads, None, scale, backward, bias)
     return _AttentionHeads.apply(handle, Q, K, V, heads, scale, backward == "fused", bias)
 
 
@@ -525,17 +612,26 @@ def attention(handle, Q, K, V, scale=None, backward="composed", *, bias=None):
     bias: None, or a tensor of (nnz,) or (1, nnz) in CSR order, added to the scaled scores before the softmax (Handle.attention_bias with one
     head), which receives a gradient.  "composed" adds it in torch between * scale and row_softmax and takes dL/dbias from
     row_softmax_backward before * scale; "fused" takes it from the one Handle.attention_bias_backward call.  The same bits both ways for
-    k, dv > 1."""
+    k, dv > 1.
+
+    16-bit tensors: on a float32 handle Q, K and V may all be torch.float16 or all torch.bfloat16, as in attention_heads(): the forward is one
+    Handle.attention_gqa_lse_16 call, the backward the float32 backward (in the mode asked for) on widened copies; O is fp32_result.to(dtype) and
+    every gradient fp32_gradient.to(dtype), the float32 results being those of this function on .float() copies -- for k, dv > 1: the 16-bit
+    forward is always the fused kernel, and at width 1 the float32 results meant are those of backward="fused" (the composed float32 backward may
+    take the spmv schedule there, whose order is the method's own); the bias and its gradient stay float32."""
     if backward not in ("composed", "fused"):
         raise ValueError(f"backward must be 'composed' or 'fused', not {backward!r}")
     _check_handle(handle)
+    dtype = _io_dtype(handle, Q, K, V)
     for t, name in ((Q, "Q"), (K, "K"), (V, "V")):
-        _check_tensor(t, name, handle)
+        _check_tensor(t, name, handle, dtype)
     if Q.dim() != 2 or K.dim() != 2 or V.dim() != 2 or Q.shape[0] != handle.m or K.shape[0] != handle.n or V.shape[0] != handle.n or \
             Q.shape[1] != K.shape[1] or Q.shape[1] < 1 or V.shape[1] < 1:
         raise ValueError(f"Q must be ({handle.m}, k), K ({handle.n}, k) and V ({handle.n}, dv) with k, dv >= 1, not {tuple(Q.shape)}, {tuple(K.shape)} and {tuple(V.shape)}")
     _check_bias(bias, handle, 1)
     scale = 1.0 / math.sqrt(Q.shape[1]) if scale is None else float(scale)   # Handle.attention's default, to the bit
+    if dtype in _HALF:
+        return _Attention16.apply(handle, Q, K, V, None, None, scale, backward, bias)
     return (_AttentionFused if backward == "fused" else _Attention).apply(handle, Q, K, V, scale, bias)
 
 
@@ -551,18 +647,22 @@ class _AttentionParts(torch.autograd.Function):
         Ks = [_block(t.detach(), t.shape[1]) for t in rest[:n]]
         Vs = [_block(t.detach(), t.shape[1]) for t in rest[n:2 * n]]
         Bs = [_bias_planes(b) for b in rest[2 * n:3 * n]]
+        half = Q2.dtype in _HALF   # 16-bit Q, K, V: every part's O and L in float32, the fold in float32, the merged O rounded once at the end
         O = L = None
         for r, h in enumerate(handles):
             _on_current_stream(h)
-            Or, Lr = h.attention_gqa_lse(Q2, Ks[r], Vs[r], heads, kv_heads, Bs[r], scale)   # a part without entries: zeros and -inf
+            if half:
+                Or, Lr = h.attention_gqa_lse_16(Q2, Ks[r], Vs[r], heads, kv_heads, Bs[r], scale, out_dtype=torch.float32)
+            else:
+                Or, Lr = h.attention_gqa_lse(Q2, Ks[r], Vs[r], heads, kv_heads, Bs[r], scale)   # a part without entries: zeros and -inf
             if r == 0:
                 O, L = Or, Lr
             else:
                 handles[0].attention_merge(O, L, Or, Lr, heads, out=O, lse=L)   # the accumulator, in place
         ctx.handles, ctx.heads, ctx.kv_heads, ctx.scale = handles, heads, kv_heads, scale
-        ctx.save_for_backward(Q2, *Ks, *Vs, *Bs, O, L)   # nothing nnz-sized but the caller's own biases
+        ctx.save_for_backward(Q2, *Ks, *Vs, *Bs, O, L)   # nothing nnz-sized but the caller's own biases; O and L in float32 also for 16-bit Q, K, V
         ctx.mark_non_differentiable(L)
-        return O, L
+        return (O.to(Q2.dtype) if half else O), L
 
     @staticmethod
     @once_differentiable
@@ -574,6 +674,9 @@ class _AttentionParts(torch.autograd.Function):
         need = ctx.needs_input_grad[4:]
         need_q, need_k, need_v = bool(need[0]), [bool(x) for x in need[1:1 + n]], [bool(x) for x in need[1 + n:1 + 2 * n]]
         need_b = [Bs[r] is not None and bool(need[1 + 2 * n + r]) for r in range(n)]
+        half = Q2.dtype if Q2.dtype in _HALF else None
+        if half is not None:   # widened: the float32 backward below, its gradients rounded once at the end
+            Q2, Ks, Vs, G = Q2.float(), [t.float() for t in Ks], [t.float() for t in Vs], G.float()
         G2 = _block(G, G.shape[1])
         dQ, dKs, dVs, dBs = None, [None] * n, [None] * n, [None] * n
         for r, h in enumerate(handles):
@@ -595,6 +698,8 @@ class _AttentionParts(torch.autograd.Function):
                     dQ += dq
         if need_q and dQ is None:
             dQ = torch.zeros_like(Q2)
+        if half is not None:
+            dQ, dKs, dVs = (None if dQ is None else dQ.to(half)), [None if g is None else g.to(half) for g in dKs], [None if g is None else g.to(half) for g in dVs]
         return (None, None, None, None, dQ, *dKs, *dVs, *dBs)
 
 
@@ -610,7 +715,13 @@ def attention_parts(handles, Q, Ks, Vs, heads, scale=None, *, kv_heads=None, bia
     Handle.attention_gqa_backward_lse per part with the merged O and L: dQ is the first part's, with every later part's added with += in part
     order; dK_r, dV_r and dB_r are each part's own (a shared bias plane's gradient is the sum of the heads' planes).  With one handle this is
     the log-sum-exp-driven backward of ordinary attention: the forward's O has Handle.attention_gqa's bits.  A part without stored entries
-    contributes nothing.  No handle's values are read or changed."""
+    contributes nothing.  No handle's values are read or changed.
+
+    16-bit tensors: on float32 handles Q and every K_r and V_r may all be torch.float16 or all torch.bfloat16.  Each part is then one
+    Handle.attention_gqa_lse_16 call with float32 O and L; the fold through Handle.attention_merge stays float32 and the merged O is rounded once at
+    the end (the float32 merged O and L are what is saved).  The backward widens Q, the K_r, V_r and dL/dO and runs the float32 backward above.  O is
+    fp32_result.to(dtype) and every gradient of Q, K_r and V_r fp32_gradient.to(dtype), the float32 results being those of this function on .float()
+    copies; L, the biases and their gradients stay float32."""
     handles = list(handles)
     Ks, Vs = list(Ks), list(Vs)
     biases = [None] * len(handles) if biases is None else list(biases)
@@ -625,14 +736,15 @@ def attention_parts(handles, Q, Ks, Vs, heads, scale=None, *, kv_heads=None, bia
         _check_handle(h)
         if h.m != first.m or _handle_dtype(h) != _handle_dtype(first) or _handle_device(h) != _handle_device(first):
             raise ValueError("the parts' handles must have the same number of rows, dtype and device")
-    _check_tensor(Q, "Q", first)
+    dtype = _io_dtype(first, Q, *Ks, *Vs)   # the handles' dtype, or the one 16-bit type of Q and every K and V on float32 handles
+    _check_tensor(Q, "Q", first, dtype)
     if Q.dim() != 2 or Q.shape[0] != first.m or Q.shape[1] < 1 or Q.shape[1] % heads:
         raise ValueError(f"Q must be ({first.m}, heads * k) with k >= 1, not {tuple(Q.shape)}")
     k = Q.shape[1] // heads
     dv = None
     for r, (h, K, V, b) in enumerate(zip(handles, Ks, Vs, biases)):
-        _check_tensor(K, f"Ks[{r}]", h)
-        _check_tensor(V, f"Vs[{r}]", h)
+        _check_tensor(K, f"Ks[{r}]", h, dtype)
+        _check_tensor(V, f"Vs[{r}]", h, dtype)
         if K.dim() != 2 or V.dim() != 2 or tuple(K.shape) != (h.n, kv_heads * k) or V.shape[0] != h.n or V.shape[1] < 1 or V.shape[1] % kv_heads:
             raise ValueError(f"part {r}: K must be ({h.n}, {kv_heads * k}) and V ({h.n}, kv_heads * dv) with dv >= 1, not {tuple(K.shape)} and {tuple(V.shape)}")
         if dv is not None and V.shape[1] // kv_heads != dv:

@@ -41,6 +41,14 @@
 // untouched.  LSE implies BIAS, with bias == nullptr allowed there (a wave-uniform test); the instantiations without LSE do not look at lse and
 // ldl and are the code from before.
 //
+// 16-bit operands (spmv_hip_attention_gqa_lse_16; the instantiations with SI or SO other than T, launched from spmv_attention_16.hip): Q, K and V
+// are fp16 or bf16 in memory (SI) and O is float or that type (SO) -- kernels/storage16.hpp.  The blocks widen what they load and round what they
+// store; the parked scores, s_p, the bias, L, scale and every arithmetic step stay float, and the lane mapping stays float's -- W = V = 4 columns
+// per lane, CW = panel_group_width<float>(k), lgv = panel_group_lg<float>(dv) --, because it fixes the summation order: O (before the one
+// rounding of a 16-bit O) and L have the bits of the float kernels on the widened operands.  A lane's segment is 8 bytes: VEC is one 8-byte
+// access there.  These instantiations are always the BIAS + LSE family and also test lse for nullptr (wave-uniform); with SI = SO = T (the
+// defaults) that test is true at compile time and the kernels are the code from before.
+//
 // Arithmetic and order: the composition's, because its blocks are the composition's (kernels/row_blocks.hpp) -- s_p is sddmm's dot for this
 // k (kernels/sddmm.hpp), t_p = s_p * scale one plain multiplication, M_i / Z_i / P_p = exp(t_p - M_i) / Z_i the row softmax's by row length,
 // O[i, c] spmm's chain.  The result is a function of the matrix, k, dv and the value type alone.  Contraction is pinned off: the fmas written
@@ -65,7 +73,8 @@ struct AttentionArgs {
     void *o = nullptr;
     long long ldq = 0, ldk = 0, ldv = 0, ldo = 0;
     double scale = 1.0;
-    bool vec = false; // q, kk, v, o, their leading dimensions and every head's first column allow 16-byte accesses
+    bool vec = false; // q, kk, v, o, their leading dimensions and every head's first column allow 16-byte accesses (16-bit operands: 8-byte)
+    int io_type = 0, o_type = 0; // SPMV_HIP_T_*: the element type of q, kk, v and of o; 0 = the handle's (attention_launch), else attention_16_launch
     const void *bias = nullptr; // nullptr: no bias; else planes of nnz elements in CSR order, head hd's at bias + hd * ldb (ldb = 0: one plane shared)
     long long ldb = 0;
     void *lse = nullptr; // nullptr: not wanted; else `heads` planes of m elements, head hd's row i at lse + hd * ldl + i
@@ -74,6 +83,8 @@ struct AttentionArgs {
 
 // spmv_attention.hip: the launches of one call on `stream`
 hipError_t attention_launch(const AttentionArgs &a, bool f64, hipStream_t stream);
+// spmv_attention_16.hip: the same with io_type = F16 or BF16 (float arithmetic; o_type 0 or io_type)
+hipError_t attention_16_launch(const AttentionArgs &a, hipStream_t stream);
 
 // lengths of the listed long rows (the shim turns them into long_off)
 static __global__ __launch_bounds__(kBlock) void attention_long_len_kernel(int nlong, const int *__restrict__ longs, const int *__restrict__ rowptr, int *__restrict__ len)
@@ -108,8 +119,8 @@ __device__ __forceinline__ T att_add_bias(T t, T b)
 // The scaled scores of one tile of 64 entries.  Lane l passes its entry's row i (-1: no entry) and column j; the tile's entries are multiplied
 // in CW rounds of 64 / CW, CW adjacent lanes per entry (sddmm_kernel's rounds, the same chain and the same tree), and t of entry e lands in
 // slot[e] (the wave's own LDS; the caller synchronizes).  Every lane of the wave must call.
-template <typename T, int CW, bool VEC>
-__device__ __forceinline__ void att_tile_scores(int i, int j, int lane, int k, const T *__restrict__ q, long long ldq, const T *__restrict__ kk, long long ldk, T scale,
+template <typename T, int CW, bool VEC, typename S = T>
+__device__ __forceinline__ void att_tile_scores(int i, int j, int lane, int k, const S *__restrict__ q, long long ldq, const S *__restrict__ kk, long long ldk, T scale,
                                                 T *slot)
 {
     constexpr int W = SddmmShape<T>::W, G = kWave / CW;
@@ -129,15 +140,18 @@ __device__ __forceinline__ void att_tile_scores(int i, int j, int lane, int k, c
 // CW: sddmm's lane group for k; 1 << lgv: spmm's lane group for min(dv, KP) columns.  heads: the chunk's columns stay in s_col while the
 // three phases run once per head over s_p, head hd on the columns from hd * k of Q and K and from hd * dv of V and O.  BIAS: head hd adds
 // bias[hd * ldb + p] to the scaled score of entry p (bias is not nullptr, except with LSE).  GROUPED: gs > 1 heads per K / V block.
-// LSE (with BIAS): lse is not nullptr and gets every row's M + log(Z) of every head; bias may be nullptr.
-template <typename T, int CW, bool VEC, bool BIAS, bool GROUPED, bool LSE = false>
+// LSE (with BIAS): lse is not nullptr and gets every row's M + log(Z) of every head; bias may be nullptr.  SI, SO: the storage types of
+// Q / K / V and of O; other than T (16-bit operands): an LSE instantiation in which lse may be nullptr as well.
+template <typename T, int CW, bool VEC, bool BIAS, bool GROUPED, bool LSE = false, typename SI = T, typename SO = T>
 __global__ __launch_bounds__(kBlock) void attention_rows_kernel(int nb, const int *__restrict__ split, const int *__restrict__ rowptr, const int *__restrict__ colidx, int heads,
-                                                                int k, int dv, int lgv, T scale, const T *__restrict__ q, long long ldq, const T *__restrict__ kk, long long ldk,
-                                                                const T *__restrict__ v, long long ldv, T *__restrict__ o, long long ldo, const T *__restrict__ bias,
+                                                                int k, int dv, int lgv, T scale, const SI *__restrict__ q, long long ldq, const SI *__restrict__ kk, long long ldk,
+                                                                const SI *__restrict__ v, long long ldv, SO *__restrict__ o, long long ldo, const T *__restrict__ bias,
                                                                 long long ldb, int gs, T *__restrict__ lse = nullptr, long long ldl = 0)
 {
 #pragma clang fp contract(off)
     static_assert(!LSE || BIAS, "the LSE instantiations are BIAS ones");
+    constexpr bool LOPT = !std::is_same_v<SI, T> || !std::is_same_v<SO, T>; // lse may be nullptr
+    static_assert(!LOPT || LSE, "the 16-bit instantiations are LSE ones");
     constexpr int V = SpmmShape<T>::V, CH = kSpmmChunk;
     __shared__ int s_col[kBlock / kWave][CH];
     __shared__ T s_p[kBlock / kWave][CH];
@@ -157,11 +171,11 @@ __global__ __launch_bounds__(kBlock) void attention_rows_kernel(int nb, const in
         for (int hd = 0; hd < heads; ++hd) {
             const int lane = att_per_head(lane0), subv = lane >> lgv, cv0 = (lane & (cwv - 1)) * V;
             const int hkv = GROUPED ? kvh : hd;
-            const T *qh = q + (long long) hd * k, *kh = kk + (long long) hkv * k, *vh = v + (long long) hkv * dv; // the head's first columns; K and V: its group's
+            const SI *qh = q + (long long) hd * k, *kh = kk + (long long) hkv * k, *vh = v + (long long) hkv * dv; // the head's first columns; K and V: its group's
             if constexpr (GROUPED) {
                 if (++gc == gs) { gc = 0; ++kvh; }
             }
-            T *oh = o + (long long) hd * dv;
+            SO *oh = o + (long long) hd * dv;
             // 1. columns (the first head reads them from memory, the others from LDS) and scaled scores into LDS
             for (int t0 = 0; t0 < nq; t0 += kWave) {
                 const int e = t0 + lane;
@@ -208,7 +222,7 @@ __global__ __launch_bounds__(kBlock) void attention_rows_kernel(int nb, const in
                     T M;
                     Z = row_softmax_regs_m(x, t, len, cw, wide, M);
                     // one lane per served row; a row without entries: -inf
-                    if (t == 0 && h0 + sub < nr) lse[(long long) hd * ldl + g0 + h0 + sub] = len > 0 ? row_lse(M, Z) : ninf;
+                    if ((!LOPT || lse != nullptr) && t == 0 && h0 + sub < nr) lse[(long long) hd * ldl + g0 + h0 + sub] = len > 0 ? row_lse(M, Z) : ninf;
                 } else Z = row_softmax_regs(x, t, len, cw, wide);
                 if (t < len) row[t] = x[0] / Z;
                 if (wide) {
@@ -231,15 +245,17 @@ __global__ __launch_bounds__(kBlock) void attention_rows_kernel(int nb, const in
 // one workgroup per long row (len > kSpmmLongThr >= 256: every thread has a first term); park + long_off[i]: len elements of its own, used by
 // one head after the other (the barrier that ends a head's last panel is also the one before the next head parks its scores).  BIAS: the
 // bias is added where the score is parked.  LSE: as in the rows kernel, thread 0 stores.
-template <typename T, int CW, bool VEC, bool BIAS, bool GROUPED, bool LSE = false>
+template <typename T, int CW, bool VEC, bool BIAS, bool GROUPED, bool LSE = false, typename SI = T, typename SO = T>
 __global__ __launch_bounds__(kBlock) void attention_long_kernel(int nlong, const int *__restrict__ longs, const int *__restrict__ long_off, const int *__restrict__ rowptr,
-                                                                const int *__restrict__ colidx, int heads, int k, int dv, int lgv, T scale, const T *__restrict__ q, long long ldq,
-                                                                const T *__restrict__ kk, long long ldk, const T *__restrict__ v, long long ldv, T *__restrict__ o, long long ldo,
+                                                                const int *__restrict__ colidx, int heads, int k, int dv, int lgv, T scale, const SI *__restrict__ q, long long ldq,
+                                                                const SI *__restrict__ kk, long long ldk, const SI *__restrict__ v, long long ldv, SO *__restrict__ o, long long ldo,
                                                                 T *park, const T *__restrict__ bias, long long ldb, int gs, T *__restrict__ lse = nullptr,
                                                                 long long ldl = 0)
 {
 #pragma clang fp contract(off)
     static_assert(!LSE || BIAS, "the LSE instantiations are BIAS ones");
+    constexpr bool LOPT = !std::is_same_v<SI, T> || !std::is_same_v<SO, T>; // lse may be nullptr
+    static_assert(!LOPT || LSE, "the 16-bit instantiations are LSE ones");
     constexpr int V = SpmmShape<T>::V, KP = SpmmShape<T>::KP;
     __shared__ T part[kSpmmSegs][KP];
     __shared__ T s_slot[kBlock / kWave][kWave];
@@ -252,8 +268,8 @@ __global__ __launch_bounds__(kBlock) void attention_long_kernel(int nlong, const
         [[maybe_unused]] int kvh = 0, gc = 0; // GROUPED: kvh = hd / gs, kept by counting
         for (int hd = 0; hd < heads; ++hd) {
             const int hkv = GROUPED ? kvh : hd;
-            const T *qh = q + (long long) hd * k, *kh = kk + (long long) hkv * k, *vh = v + (long long) hkv * dv; // the head's first columns; K and V: its group's
-            T *oh = o + (long long) hd * dv;
+            const SI *qh = q + (long long) hd * k, *kh = kk + (long long) hkv * k, *vh = v + (long long) hkv * dv; // the head's first columns; K and V: its group's
+            SO *oh = o + (long long) hd * dv;
             if constexpr (GROUPED) {
                 if (++gc == gs) { gc = 0; ++kvh; }
             }
@@ -282,7 +298,7 @@ __global__ __launch_bounds__(kBlock) void attention_long_kernel(int nlong, const
             if constexpr (LSE) {
                 T M, Z;
                 long_row_softmax_mz(t, t, 0, len, tid, s_max, s_sum, M, Z);
-                if (tid == 0) lse[(long long) hd * ldl + r] = row_lse(M, Z);
+                if ((!LOPT || lse != nullptr) && tid == 0) lse[(long long) hd * ldl + r] = row_lse(M, Z);
             } else long_row_softmax(t, t, 0, len, tid, s_max, s_sum);
             // 3. O = P V, panel by panel; a panel's last barrier also lets the next panel / head / row write part and the parked scores again
             for (int c = 0; c < dv; c += KP)

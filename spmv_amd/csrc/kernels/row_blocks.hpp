@@ -10,6 +10,7 @@
 //   chunks of rows   chunk_take, chunk_row_of, rows_times_panels, staged_walk
 #pragma once
 #include "common.hpp"
+#include "storage16.hpp"
 
 namespace spmv {
 
@@ -27,12 +28,20 @@ template <typename T> struct SpmmShape {
 
 // ---- X row segments and the chain over a row's entries --------------------------------------------------------------------------------
 
-// X row segment of one lane: nc (<= V) columns from p; a 16-byte load when allowed and the segment is whole
-template <typename T, bool VEC>
-__device__ __forceinline__ void spmm_load_x(const T *p, int nc, T (&o)[SpmmShape<T>::V])
+// X row segment of one lane: nc (<= V) columns from p; a 16-byte load when allowed and the segment is whole.  S: what X is in memory
+// (kernels/storage16.hpp) -- T itself, or a 16-bit type widened here: the same V columns per lane, an 8-byte segment, one 8-byte load when allowed
+template <typename T, bool VEC, typename S = T>
+__device__ __forceinline__ void spmm_load_x(const S *p, int nc, T (&o)[SpmmShape<T>::V])
 {
     constexpr int V = SpmmShape<T>::V;
-    if (VEC && nc == V) {
+    if constexpr (!std::is_same_v<S, T>) {
+        static_assert(std::is_same_v<T, float> && is_storage16<S>, "16-bit storage is for float arithmetic");
+        if (VEC && nc == V) st16_load4(p, o);
+        else {
+#pragma unroll
+            for (int t = 0; t < V; ++t) o[t] = t < nc ? st16_widen(p[t]) : T(0);
+        }
+    } else if (VEC && nc == V) {
         if constexpr (sizeof(T) == 8) {
             const f64x2 v = *reinterpret_cast<const f64x2 *>(p);
             o[0] = v.x; o[1] = v.y;
@@ -46,11 +55,21 @@ __device__ __forceinline__ void spmm_load_x(const T *p, int nc, T (&o)[SpmmShape
     }
 }
 
-template <typename T, bool VEC>
-__device__ __forceinline__ void spmm_store_y(T *p, int nc, const T (&a)[SpmmShape<T>::V])
+// Y row segment of one lane.  S: what Y is in memory -- T itself, or a 16-bit type: every element rounded once (st16_narrow), an 8-byte store
+// when allowed and the segment is whole
+template <typename T, bool VEC, typename S = T>
+__device__ __forceinline__ void spmm_store_y(S *p, int nc, const T (&a)[SpmmShape<T>::V])
 {
     constexpr int V = SpmmShape<T>::V;
-    if (VEC && nc == V) {
+    if constexpr (!std::is_same_v<S, T>) {
+        static_assert(std::is_same_v<T, float> && is_storage16<S>, "16-bit storage is for float arithmetic");
+        if (VEC && nc == V) st16_store4(p, a);
+        else {
+#pragma unroll
+            for (int t = 0; t < V; ++t)
+                if (t < nc) p[t] = st16_narrow<S>(a[t]);
+        }
+    } else if (VEC && nc == V) {
         if constexpr (sizeof(T) == 8) *reinterpret_cast<f64x2 *>(p) = f64x2{a[0], a[1]};
         else *reinterpret_cast<f32x4 *>(p) = f32x4{a[0], a[1], a[2], a[3]};
     } else {
@@ -62,9 +81,9 @@ __device__ __forceinline__ void spmm_store_y(T *p, int nc, const T (&a)[SpmmShap
 
 // acc[t] = fma(val_of(j), X[col_of(j)][c0 + t], acc[t]) for j = s .. e - 1, strictly in that order: ONE lane's sequential chain per (row,
 // column).  Where the column and the value of entry j come from (a global stream, the wave's LDS copy of a chunk, a gather through a
-// permutation) is the caller's: the same values in the same order give identical bits.
-template <typename T, bool VEC, typename ColOf, typename ValOf>
-__device__ __forceinline__ void spmm_chain_with(int s, int e, ColOf col_of, ValOf val_of, const T *__restrict__ x, long long ldx, int c0, int nc, T (&acc)[SpmmShape<T>::V])
+// permutation) is the caller's: the same values in the same order give identical bits.  S: X's storage type (spmm_load_x), told by x.
+template <typename T, bool VEC, typename ColOf, typename ValOf, typename S = T>
+__device__ __forceinline__ void spmm_chain_with(int s, int e, ColOf col_of, ValOf val_of, const S *__restrict__ x, long long ldx, int c0, int nc, T (&acc)[SpmmShape<T>::V])
 {
     constexpr int V = SpmmShape<T>::V, U = 4;
     int j = s;
@@ -94,8 +113,8 @@ __device__ __forceinline__ void spmm_chain_with(int s, int e, ColOf col_of, ValO
 }
 
 // the chain over colidx[j], val[j].  NT: the two are global streams read once; else the wave's LDS copy of a chunk, or a parked row
-template <typename T, bool VEC, bool NT>
-__device__ __forceinline__ void spmm_chain(int s, int e, const int *__restrict__ colidx, const T *__restrict__ val, const T *__restrict__ x, long long ldx,
+template <typename T, bool VEC, bool NT, typename S = T>
+__device__ __forceinline__ void spmm_chain(int s, int e, const int *__restrict__ colidx, const T *__restrict__ val, const S *__restrict__ x, long long ldx,
                                            int c0, int nc, T (&acc)[SpmmShape<T>::V])
 {
     spmm_chain_with<T, VEC>(
@@ -262,9 +281,10 @@ __device__ __forceinline__ T long_row_dot(const T *x, const T *y, int s, int e, 
 // kSpmmSegs equal segments; lane group sub (of G groups, its lanes' columns from c0) takes the segments sub, sub + G, .., each one chain from
 // +0 -- chain(lo, hi, nc, acc) runs it over the entries [lo, hi) of the row --, and the partial sums are added left to right through part.
 // Ends with the barrier after which part may be written again.  add: y[c] = y[c] + sum instead -- one plain addition to what the same thread
-// of an earlier panel call (or launch of the stream) stored there (the grouped column pass: kernels/attention_backward.hpp).
-template <typename T, typename Chain>
-__device__ __forceinline__ void long_row_panel(int len, int kc, int G, int sub, int c0, int tid, T (*part)[SpmmShape<T>::KP], T *y, Chain chain, bool add = false)
+// of an earlier panel call (or launch of the stream) stored there (the grouped column pass: kernels/attention_backward.hpp).  S: y's storage
+// type, told by y -- T itself, or a 16-bit type: the sum rounded once where it is stored (no add there).
+template <typename T, typename Chain, typename S = T>
+__device__ __forceinline__ void long_row_panel(int len, int kc, int G, int sub, int c0, int tid, T (*part)[SpmmShape<T>::KP], S *y, Chain chain, bool add = false)
 {
 #pragma clang fp contract(off)
     constexpr int V = SpmmShape<T>::V;
@@ -283,7 +303,8 @@ __device__ __forceinline__ void long_row_panel(int len, int kc, int G, int sub, 
     if (tid < kc) {
         T sum = part[0][tid];
         for (int g = 1; g < kSpmmSegs; ++g) sum += part[g][tid];
-        y[tid] = add ? y[tid] + sum : sum;
+        if constexpr (std::is_same_v<S, T>) y[tid] = add ? y[tid] + sum : sum;
+        else y[tid] = st16_narrow<S>(sum);
     }
     __syncthreads();
 }
@@ -327,10 +348,11 @@ __device__ __forceinline__ int chunk_row_of(int el, int e)
 
 // Y[g0 + h, :k] = sum over the entries of chunk row h of val * X[col, :], h < nr, with col / val the wave's LDS copy of the chunk: R rows
 // side by side (lane group sub, its lanes' columns from c0 within a panel), every (row, column) one lane's spmm_chain from +0 over the row's
-// entries in CSR order; the panels of KP columns are looped here, with the chunk still in LDS.
-template <typename T, bool VEC>
-__device__ __forceinline__ void rows_times_panels(const ChunkRows ch, int g0, int R, int sub, int c0, const int *col, const T *val, const T *__restrict__ x, long long ldx,
-                                                  int k, T *__restrict__ y, long long ldy)
+// entries in CSR order; the panels of KP columns are looped here, with the chunk still in LDS.  SX, SY: the storage types of X and Y, told by x
+// and y (spmm_load_x, spmm_store_y).
+template <typename T, bool VEC, typename SX = T, typename SY = T>
+__device__ __forceinline__ void rows_times_panels(const ChunkRows ch, int g0, int R, int sub, int c0, const int *col, const T *val, const SX *__restrict__ x, long long ldx,
+                                                  int k, SY *__restrict__ y, long long ldy)
 {
     constexpr int V = SpmmShape<T>::V, KP = SpmmShape<T>::KP;
     for (int h0 = 0; h0 < ch.nr; h0 += R) {

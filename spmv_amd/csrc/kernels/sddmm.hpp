@@ -22,6 +22,7 @@
 // between workgroups, no scratch.
 #pragma once
 #include "common.hpp"
+#include "storage16.hpp"
 
 namespace spmv {
 
@@ -47,12 +48,20 @@ struct SddmmArgs {
 // spmv_sddmm.hip: the one launch of a call on `stream`
 hipError_t sddmm_launch(const SddmmArgs &a, bool f64, hipStream_t stream);
 
-// nc (1 .. W) columns from p; a 16-byte load when allowed and the segment is whole
-template <typename T, bool VEC>
-__device__ __forceinline__ void sddmm_load(const T *p, int nc, T (&o)[SddmmShape<T>::W])
+// nc (1 .. W) columns from p; a 16-byte load when allowed and the segment is whole.  S: what the operand is in memory (kernels/storage16.hpp) --
+// T itself, or a 16-bit type widened here: the same W columns per lane, so the segment is 8 bytes and the wide form one 8-byte load
+template <typename T, bool VEC, typename S = T>
+__device__ __forceinline__ void sddmm_load(const S *p, int nc, T (&o)[SddmmShape<T>::W])
 {
     constexpr int W = SddmmShape<T>::W;
-    if (VEC && nc == W) {
+    if constexpr (!std::is_same_v<S, T>) {
+        static_assert(std::is_same_v<T, float> && is_storage16<S>, "16-bit storage is for float arithmetic");
+        if (VEC && nc == W) st16_load4(p, o);
+        else {
+#pragma unroll
+            for (int t = 0; t < W; ++t) o[t] = t < nc ? st16_widen(p[t]) : T(0);
+        }
+    } else if (VEC && nc == W) {
         if constexpr (sizeof(T) == 8) {
             const f64x2 v = *reinterpret_cast<const f64x2 *>(p);
             o[0] = v.x; o[1] = v.y;
@@ -66,9 +75,9 @@ __device__ __forceinline__ void sddmm_load(const T *p, int nc, T (&o)[SddmmShape
     }
 }
 
-// one lane's chain over its columns c0, c0 + 1, .., then c0 + step, .. (c0 < k)
-template <typename T, bool VEC>
-__device__ __forceinline__ T sddmm_chain(const T *__restrict__ u, const T *__restrict__ v, int c0, int step, int k)
+// one lane's chain over its columns c0, c0 + 1, .., then c0 + step, .. (c0 < k); S: the operands' storage type (sddmm_load)
+template <typename T, bool VEC, typename S = T>
+__device__ __forceinline__ T sddmm_chain(const S *__restrict__ u, const S *__restrict__ v, int c0, int step, int k)
 {
 #pragma clang fp contract(off) // the explicit fmas below are the only fused operations
     constexpr int W = SddmmShape<T>::W;

@@ -62,8 +62,12 @@ static int attention_stage_bias(Stager &stg, StageBuf &b, const void *&bias, lon
 // or the planes of spmv_hip_attention_bias, one per QUERY head (ldb = 0: one plane for all heads; else >= nnz); with NULL, ldb is ignored.
 // lse: NULL, or `heads` planes ldl >= m apart that get the rows' log-sum-exps (spmv_hip_attention_gqa_lse); with NULL, ldl is ignored and the
 // launches are those of spmv_hip_attention_gqa.
-extern "C" int spmv_shim_attention_gqa_lse(spmv_dev *d, int heads, int kv_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
-                                           const void *v, long long ldv, const void *bias, long long ldb, void *o, long long ldo, void *lse, long long ldl)
+// io_type / o_type (SPMV_HIP_T_*): 0, 0 -- every operand in the handle's precision, the kernels of spmv_attention.hip.  io_type F16 or BF16
+// (spmv_hip_attention_gqa_lse_16; a float handle): q, kk and v hold that type and o holds it too (o_type = io_type) or float (o_type = 0); ldq, ldk,
+// ldv and ldo count elements of the operand's own type, a host operand is staged at its own element size, bias and lse stay float, and the
+// kernels are those of spmv_attention_16.hip.  The types are the entry points' to check (spmv_shim_attention_gqa_lse_16); here they are taken as they come.
+static int attention_gqa_lse_any(spmv_dev *d, int heads, int kv_heads, int k, int dv, double scale, int io_type, const void *q, long long ldq, const void *kk, long long ldk,
+                                 const void *v, long long ldv, const void *bias, long long ldb, void *o, long long ldo, int o_type, void *lse, long long ldl)
 {
     if (!d || !d->built) return fail(SPMV_HIP_E_NOSTATE, "attention: schedule not built");
     if (kv_heads < 1 || heads < 1 || heads % kv_heads != 0) return fail(SPMV_HIP_E_ARG, "attention: need kv_heads >= 1 and heads a multiple of it (heads = %d, kv_heads = %d)", heads, kv_heads);
@@ -84,10 +88,13 @@ extern "C" int spmv_shim_attention_gqa_lse(spmv_dev *d, int heads, int kv_heads,
     int rc;
     if ((rc = spmm_plan(d)) || (rc = attention_plan(d))) return rc;
     const size_t s = d->vsize;
+    const size_t si = io_type ? 2 : s, so = o_type ? 2 : s; // element sizes of Q / K / V and of O
     Stager stg{d};
     AttentionArgs a;
     a.m = d->m;
     a.heads = heads;
+    a.io_type = io_type;
+    a.o_type = o_type;
     a.gs = heads / kv_heads;
     a.k = k;
     a.dv = dv;
@@ -108,17 +115,39 @@ extern "C" int spmv_shim_attention_gqa_lse(spmv_dev *d, int heads, int kv_heads,
     a.bias = bias; a.ldb = bias ? ldb : 0;
     a.lse = lse; a.ldl = lse ? ldl : 0;
     // every row of O gets its heads * dv elements, empty rows their zeros: a staged result is written completely before it is copied back
-    if ((rc = stg.in(d->stage[STAGE_ATT_Q], a.q, a.ldq, (size_t) d->m, (int) wk)) || (rc = stg.in(d->stage[STAGE_ATT_K], a.kk, a.ldk, (size_t) d->n, (int) gk)) ||
-        (rc = stg.in(d->stage[STAGE_ATT_V], a.v, a.ldv, (size_t) d->n, (int) gv)) || (rc = stg.out(d->stage[STAGE_ATT_O], a.o, a.ldo, (size_t) d->m, (int) wv)) ||
+    if ((rc = stg.in(d->stage[STAGE_ATT_Q], a.q, a.ldq, (size_t) d->m, (int) wk, si)) || (rc = stg.in(d->stage[STAGE_ATT_K], a.kk, a.ldk, (size_t) d->n, (int) gk, si)) ||
+        (rc = stg.in(d->stage[STAGE_ATT_V], a.v, a.ldv, (size_t) d->n, (int) gv, si)) || (rc = stg.out(d->stage[STAGE_ATT_O], a.o, a.ldo, (size_t) d->m, (int) wv, so)) ||
         (a.bias && (rc = attention_stage_bias(stg, d->stage[STAGE_ATT_B], a.bias, a.ldb, heads))) ||
         (a.lse && (rc = stg.out(d->stage[STAGE_ATT_L], a.lse, a.ldl, (size_t) heads, d->m)))) return rc; // every row of every plane is written
     // the access width changes no bit (kernels/attention.hpp): chosen per call from what the addresses allow -- with more than one head, every
-    // head's first column has to be 16-byte aligned as well
-    a.vec = wide_ok(a.q, a.ldq, s) && wide_ok(a.kk, a.ldk, s) && wide_ok(a.v, a.ldv, s) && wide_ok(a.o, a.ldo, s) &&
-            (heads == 1 || (((size_t) k * s) % 16 == 0 && ((size_t) dv * s) % 16 == 0));
-    const hipError_t e = attention_launch(a, s == sizeof(double), d->stream);
+    // head's first column has to be 16-byte aligned as well.  A lane's segment of a 16-bit operand is 8 bytes: 8-byte accesses there
+    if (io_type == SPMV_HIP_T_HANDLE)
+        a.vec = wide_ok(a.q, a.ldq, s) && wide_ok(a.kk, a.ldk, s) && wide_ok(a.v, a.ldv, s) && wide_ok(a.o, a.ldo, s) &&
+                (heads == 1 || (((size_t) k * s) % 16 == 0 && ((size_t) dv * s) % 16 == 0));
+    else {
+        const size_t wo = 4 * so; // O's segment: 4 elements of its own type
+        a.vec = wide_ok_bytes(a.q, a.ldq, si, 8) && wide_ok_bytes(a.kk, a.ldk, si, 8) && wide_ok_bytes(a.v, a.ldv, si, 8) && wide_ok_bytes(a.o, a.ldo, so, wo) &&
+                (heads == 1 || (((size_t) k * si) % 8 == 0 && ((size_t) dv * si) % 8 == 0 && ((size_t) dv * so) % wo == 0));
+    }
+    const hipError_t e = io_type == SPMV_HIP_T_HANDLE ? attention_launch(a, s == sizeof(double), d->stream) : attention_16_launch(a, d->stream);
     if (e != hipSuccess) return fail(SPMV_HIP_E_RUNTIME, "attention: launch: %s", hipGetErrorString(e));
     return stg.finish();
+}
+
+extern "C" int spmv_shim_attention_gqa_lse(spmv_dev *d, int heads, int kv_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
+                                           const void *v, long long ldv, const void *bias, long long ldb, void *o, long long ldo, void *lse, long long ldl)
+{
+    return attention_gqa_lse_any(d, heads, kv_heads, k, dv, scale, SPMV_HIP_T_HANDLE, q, ldq, kk, ldk, v, ldv, bias, ldb, o, ldo, SPMV_HIP_T_HANDLE, lse, ldl);
+}
+
+extern "C" int spmv_shim_attention_gqa_lse_16(spmv_dev *d, int heads, int kv_heads, int k, int dv, double scale, int io_type, const void *q, long long ldq, const void *kk,
+                                              long long ldk, const void *v, long long ldv, const void *bias, long long ldb, void *o, long long ldo, int o_type, void *lse,
+                                              long long ldl)
+{
+    // the one place of the type rules on this side (spmv_api.c states them ahead of its gate from the public handle's data_size)
+    if ((io_type != SPMV_HIP_T_F16 && io_type != SPMV_HIP_T_BF16) || (o_type != SPMV_HIP_T_HANDLE && o_type != io_type) || (d && d->vsize != sizeof(float)))
+        return fail(SPMV_HIP_E_ARG, "attention: 16-bit operands need a float handle, io_type F16 or BF16 and o_type HANDLE or io_type (io_type = %d, o_type = %d)", io_type, o_type);
+    return attention_gqa_lse_any(d, heads, kv_heads, k, dv, scale, io_type, q, ldq, kk, ldk, v, ldv, bias, ldb, o, ldo, o_type, lse, ldl);
 }
 
 extern "C" int spmv_shim_attention_gqa(spmv_dev *d, int heads, int kv_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
@@ -208,6 +237,19 @@ extern "C" double spmv_shim_time_attention_gqa_lse(spmv_dev *d, int heads, int k
     }
     return time_events(d, "time_attention", warmup, iters, ms_out,
                        [&] { return spmv_shim_attention_gqa_lse(d, heads, kv_heads, k, dv, scale, q, ldq, kk, ldk, v, ldv, bias, ldb, o, ldo, lse, ldl); });
+}
+
+extern "C" double spmv_shim_time_attention_gqa_lse_16(spmv_dev *d, int heads, int kv_heads, int k, int dv, double scale, int io_type, const void *q, long long ldq, const void *kk,
+                                                      long long ldk, const void *v, long long ldv, const void *bias, long long ldb, void *o, long long ldo, int o_type,
+                                                      void *lse, long long ldl, int warmup, int iters, float *ms_out)
+{
+    if (!d || !d->built || iters <= 0) { fail(SPMV_HIP_E_ARG, "time_attention: bad arguments"); return -1.0; }
+    if (!is_device_ptr(q) || !is_device_ptr(kk) || !is_device_ptr(v) || !is_device_ptr(o) || (bias && !is_device_ptr(bias)) || (lse && !is_device_ptr(lse))) {
+        fail(SPMV_HIP_E_ARG, "time_attention: Q, K, V, O, the bias and L must be device pointers");
+        return -1.0;
+    }
+    return time_events(d, "time_attention", warmup, iters, ms_out,
+                       [&] { return spmv_shim_attention_gqa_lse_16(d, heads, kv_heads, k, dv, scale, io_type, q, ldq, kk, ldk, v, ldv, bias, ldb, o, ldo, o_type, lse, ldl); });
 }
 
 extern "C" double spmv_shim_time_attention_merge(spmv_dev *d, int heads, int dv, const void *o1, long long ldo1, const void *l1, long long ldl1, const void *o2, long long ldo2,

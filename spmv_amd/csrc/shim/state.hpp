@@ -386,10 +386,11 @@ static bool is_device_ptr(const void *p)
 // caller's ld; a host operand goes through its StageBuf -- in(): its k columns packed into HBM on the handle's stream (the padding is not copied);
 // out(): the buffer the kernel writes instead -- and p / ld are redirected there.  finish() copies the host result back and synchronizes, unless
 // the handle is asynchronous and every operand was on the device.  Every operand is asked once whether it is a device pointer.  An operation has
-// at most kMaxRes results (spmv_hip_attention_bias_backward: four).
+// at most kMaxRes results (spmv_hip_attention_bias_backward: four).  Elements are of the handle's value type unless in() / out() is given an
+// element size `es` (the 16-bit operands of spmv_hip_attention_gqa_lse_16: 2); ld and k count elements of that size.
 struct Stager {
     static constexpr int kMaxRes = 4;
-    struct Res { const StageBuf *buf; void *host; size_t ld, rows, k; }; // a staged result and where it goes
+    struct Res { const StageBuf *buf; void *host; size_t ld, rows, k, es; }; // a staged result and where it goes
     spmv_dev *d;
     bool all_dev = true;
     Res res[kMaxRes] = {};
@@ -408,41 +409,42 @@ struct Stager {
         b.bytes = bytes ? bytes : 16;
         return SPMV_HIP_OK;
     }
-    // rows x k elements between a packed device buffer and a host array of leading dimension ld
-    hipError_t copy(void *dst, size_t dst_ld, const void *src, size_t src_ld, size_t rows, size_t k, hipMemcpyKind kind)
+    // rows x k elements of s bytes between a packed device buffer and a host array of leading dimension ld
+    hipError_t copy(void *dst, size_t dst_ld, const void *src, size_t src_ld, size_t rows, size_t k, hipMemcpyKind kind, size_t s)
     {
-        const size_t s = d->vsize;
         if (dst_ld == k && src_ld == k) return hipMemcpyAsync(dst, src, s * k * rows, kind, d->stream);
         return hipMemcpy2DAsync(dst, s * dst_ld, src, s * src_ld, s * k, rows, kind, d->stream);
     }
-    template <class P> int in(StageBuf &b, P &p, long long &ld, size_t rows, int k)
+    template <class P> int in(StageBuf &b, P &p, long long &ld, size_t rows, int k, size_t es = 0)
     {
         const bool dev = is_device_ptr(p);
         all_dev = all_dev && dev;
         if (dev || !p || rows == 0) return SPMV_HIP_OK;
-        const int rc = reserve(b, d->vsize * (size_t) k * rows);
+        if (es == 0) es = d->vsize;
+        const int rc = reserve(b, es * (size_t) k * rows);
         if (rc) return rc;
-        HIP_TRY(copy(b.p, (size_t) k, p, (size_t) ld, rows, (size_t) k, hipMemcpyHostToDevice));
+        HIP_TRY(copy(b.p, (size_t) k, p, (size_t) ld, rows, (size_t) k, hipMemcpyHostToDevice, es));
         p = (P) b.p;
         ld = k;
         return SPMV_HIP_OK;
     }
-    template <class P> int out(StageBuf &b, P &p, long long &ld, size_t rows, int k)
+    template <class P> int out(StageBuf &b, P &p, long long &ld, size_t rows, int k, size_t es = 0)
     {
         const bool dev = is_device_ptr(p);
         all_dev = all_dev && dev;
         if (dev || rows == 0) return SPMV_HIP_OK;
-        const int rc = reserve(b, d->vsize * (size_t) k * rows);
+        if (es == 0) es = d->vsize;
+        const int rc = reserve(b, es * (size_t) k * rows);
         if (rc) return rc;
         if (nres >= kMaxRes) return fail(SPMV_HIP_E_ARG, "staging: more than %d results", kMaxRes);
-        res[nres++] = Res{&b, p, (size_t) ld, rows, (size_t) k};
+        res[nres++] = Res{&b, p, (size_t) ld, rows, (size_t) k, es};
         p = (P) b.p;
         ld = k;
         return SPMV_HIP_OK;
     }
     int finish()
     {
-        for (int i = 0; i < nres; ++i) HIP_TRY(copy(res[i].host, res[i].ld, res[i].buf->p, res[i].k, res[i].rows, res[i].k, hipMemcpyDeviceToHost));
+        for (int i = 0; i < nres; ++i) HIP_TRY(copy(res[i].host, res[i].ld, res[i].buf->p, res[i].k, res[i].rows, res[i].k, hipMemcpyDeviceToHost, res[i].es));
         if (!d->async || !all_dev) HIP_TRY(hipStreamSynchronize(d->stream));
         return SPMV_HIP_OK;
     }
@@ -450,6 +452,8 @@ struct Stager {
 
 // true if p and the leading dimension ld (elements of s bytes) allow 16-byte accesses to every row
 static bool wide_ok(const void *p, long long ld, size_t s) { return ((uintptr_t) p & 15) == 0 && ((size_t) ld * s) % 16 == 0; }
+// the same for accesses of `bytes` bytes (a power of two): the 8-byte segments of 16-bit operands
+static bool wide_ok_bytes(const void *p, long long ld, size_t s, size_t bytes) { return ((uintptr_t) p & (bytes - 1)) == 0 && ((size_t) ld * s) % bytes == 0; }
 
 // Mean ms of `iters` calls of run() (an operation's own entry point on device operands; 0 on success) after `warmup` untimed ones: hipEvents on
 // the handle's stream around every call, the handle asynchronous for the loop only.  ms_out (iters floats, may be NULL) receives the single

@@ -1316,6 +1316,47 @@ double spmv_hip_time_attention_gqa_lse_launches(spmv_Handle_t h, int heads, int 
     return report_time(spmv_shim_time_attention_gqa_lse(st->dev, heads, kv_heads, k, dv, scale, Q, ldq, K, ldk, V, ldv, B, ldb, O, ldo, L, ldl, warmup, iters, ms_out), where);
 }
 
+/* ---------------------------------------------------------------- the forward on 16-bit Q, K and V */
+/* the type rules ahead of the gate: data_size is in the public handle, so a handle whose create failed answers them too (a cleared handle holds
+ * no precision any more, data_size 0: it gets as far as the gate and is SPMV_HIP_E_NOSTATE there, like in every other call) */
+static int attention_16_types(spmv_Handle_t h, const char *where, int io_type, int o_type)
+{
+    if (h->data_size != sizeof(float) && h->data_size != 0) return refuse(SPMV_HIP_E_ARG, where, "16-bit operands need an fp32 handle");
+    if (io_type != SPMV_HIP_T_F16 && io_type != SPMV_HIP_T_BF16) return refuse(SPMV_HIP_E_ARG, where, "io_type must be SPMV_HIP_T_F16 or SPMV_HIP_T_BF16");
+    if (o_type != SPMV_HIP_T_HANDLE && o_type != io_type) return refuse(SPMV_HIP_E_ARG, where, "o_type must be SPMV_HIP_T_HANDLE or equal to io_type");
+    return SPMV_HIP_OK;
+}
+
+int spmv_hip_attention_gqa_lse_16(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                                  const void *Matrix_Val, int heads, int kv_heads, int k, int dv, double scale, int io_type,
+                                  const void *Q, long long ldq, const void *K, long long ldk, const void *V, long long ldv,
+                                  const void *B, long long ldb, void *O, long long ldo, int o_type, void *L, long long ldl)
+{
+    const char *where = "attention_gqa_lse_16";
+    spmv_hip_state *st;
+    int rc;
+    if ((rc = attention_gqa_args(handle, where, heads, kv_heads, k, dv, Q, ldq, K, ldk, V, ldv, O, ldo, m))) return rc;
+    if (B && ldb < 0) return refuse(SPMV_HIP_E_ARG, where, "need ldb >= 0");
+    if (L && ldl < (long long) m) return refuse(SPMV_HIP_E_ARG, where, "need ldl >= m");
+    if ((rc = attention_16_types(handle, where, io_type, o_type))) return rc;
+    if ((rc = resident_prologue(handle, where, RESIDENT_NOT_REORDERED, m, RowPtr, ColIdx, Matrix_Val, &st)) || (rc = spmm_columns(handle, st, where))) return rc;
+    return report(spmv_shim_attention_gqa_lse_16(st->dev, heads, kv_heads, k, dv, scale, io_type, Q, ldq, K, ldk, V, ldv, B, ldb, O, ldo, o_type, L, ldl), where);
+}
+
+double spmv_hip_time_attention_gqa_lse_16_launches(spmv_Handle_t h, int heads, int kv_heads, int k, int dv, double scale, int io_type, const void *Q, long long ldq,
+                                                   const void *K, long long ldk, const void *V, long long ldv, const void *B, long long ldb, void *O, long long ldo, int o_type,
+                                                   void *L, long long ldl, int warmup, int iters, float *ms_out)
+{
+    const char *where = "time_attention_gqa_lse_16_launches";
+    spmv_hip_state *st;
+    if (attention_gqa_args(h, where, heads, kv_heads, k, dv, Q, ldq, K, ldk, V, ldv, O, ldo, 1)) return -1.0;
+    if (B && ldb < 0) { (void) refuse(SPMV_HIP_E_ARG, where, "need ldb >= 0"); return -1.0; }
+    if (attention_16_types(h, where, io_type, o_type)) return -1.0;
+    if (resident_state(h, where, RESIDENT_NOT_REORDERED, &st) || spmm_columns(h, st, where)) return -1.0;
+    return report_time(spmv_shim_time_attention_gqa_lse_16(st->dev, heads, kv_heads, k, dv, scale, io_type, Q, ldq, K, ldk, V, ldv, B, ldb, O, ldo, o_type, L, ldl, warmup,
+                                                           iters, ms_out), where);
+}
+
 /* m is the handle's: whether an operand is NULL while m > 0, and the plane strides against m, are looked at behind the gate (nothing written) */
 static int attention_merge_args(spmv_Handle_t h, const char *where, int heads, int dv, long long ldo1, long long ldo2, long long ldo)
 {

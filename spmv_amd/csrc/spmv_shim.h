@@ -170,6 +170,14 @@ int spmv_shim_attention_gqa_lse(spmv_dev *d, int heads, int kv_heads, int k, int
 double spmv_shim_time_attention_gqa_lse(spmv_dev *d, int heads, int kv_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
                                         const void *v, long long ldv, const void *bias, long long ldb, void *o, long long ldo, void *lse, long long ldl, int warmup, int iters,
                                         float *ms_out);
+/* on 16-bit Q, K and V (spmv_hip_attention_gqa_lse_16; a float handle): io_type SPMV_HIP_T_F16 or _BF16 is the element type of q, kk and v, o_type
+ * SPMV_HIP_T_HANDLE (o is float) or io_type; leading dimensions in elements of the operand's own type; bias and lse float.  A bad type or a double
+ * handle: SPMV_HIP_E_ARG, nothing written */
+int spmv_shim_attention_gqa_lse_16(spmv_dev *d, int heads, int kv_heads, int k, int dv, double scale, int io_type, const void *q, long long ldq, const void *kk, long long ldk,
+                                   const void *v, long long ldv, const void *bias, long long ldb, void *o, long long ldo, int o_type, void *lse, long long ldl);
+double spmv_shim_time_attention_gqa_lse_16(spmv_dev *d, int heads, int kv_heads, int k, int dv, double scale, int io_type, const void *q, long long ldq, const void *kk,
+                                           long long ldk, const void *v, long long ldv, const void *bias, long long ldb, void *o, long long ldo, int o_type, void *lse,
+                                           long long ldl, int warmup, int iters, float *ms_out);
 /* two partial results merged by their log-sum-exps (spmv_hip_attention_merge): the O operands m x heads*dv, the L operands `heads` planes of m; o may
  * be o1 and l may be l1; l NULL: not wanted.  The matrix is not read.  A plane stride below m: SPMV_HIP_E_ARG, nothing written */
 int spmv_shim_attention_merge(spmv_dev *d, int heads, int dv, const void *o1, long long ldo1, const void *l1, long long ldl1, const void *o2, long long ldo2, const void *l2,
