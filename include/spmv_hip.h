@@ -554,6 +554,45 @@ int spmv_hip_attention_gqa_lse_16(spmv_Handle_t handle, BASIC_INT_TYPE m, const 
                                   void *O, long long ldo, int o_type,      /* SPMV_HIP_T_HANDLE: fp32 O; or == io_type: O in that 16-bit type */
                                   void *L, long long ldl);                 /* fp32 planes, or NULL */
 
+/* ---- the backward on 16-bit Q, K, V and G (fp16 / bf16), each gradient in that type or in fp32 ------------------------------
+ * spmv_hip_attention_gqa_backward and spmv_hip_attention_gqa_backward_lse for callers that keep Q, K, V and dL/dO in a 16-bit type: the four
+ * kernels load the 16-bit elements, widen them in registers and run the fp32 arithmetic unchanged; nothing is widened in memory, and a 16-bit
+ * gradient is stored already rounded.
+ *   - Handle and types: an fp32 handle (an fp64 handle: SPMV_HIP_E_ARG).  io_type is SPMV_HIP_T_F16 or SPMV_HIP_T_BF16, the element type of Q, K, V
+ *     and G.  dq_type is the type of dQ and dkv_type that of dK and dV: SPMV_HIP_T_HANDLE (fp32) or equal to io_type; anything else is
+ *     SPMV_HIP_E_ARG.  B, dB, O and L are fp32, exactly as in the fp32 calls.  Leading dimensions count elements of the operand's own type.
+ *   - O and L: both NULL -- the self-normalising row pass of spmv_hip_attention_gqa_backward; both given -- the row pass of
+ *     spmv_hip_attention_gqa_backward_lse, driven by them.  Exactly one of them NULL while m > 0: SPMV_HIP_E_ARG.
+ *   - Bits, fp32 outputs and dB: exactly those of spmv_hip_attention_gqa_backward (O = L = NULL) or spmv_hip_attention_gqa_backward_lse (O and L
+ *     given) on Q, K, V and G converted element by element to fp32.  The conversion is exact and the lane mapping is the fp32 kernels' (4 columns
+ *     per lane), so everything promised there carries over: the order, the group sums of dK / dV in ascending head, the special values, head h
+ *     equal to the one-head call on its slices.
+ *   - Bits, 16-bit outputs: each element is that fp32 value rounded ONCE, to nearest, ties to even (what fp32_gradient.to(dtype) gives in torch):
+ *     fp16 overflow gives +-inf -- reachable here: a dV element is a sum over a column --, NaN stays NaN, the sign of zero is kept.  No 16-bit
+ *     element is ever read back as a partial sum: with kv_heads < heads a 16-bit dK / dV is summed over its group's heads in two handle-owned
+ *     fp32 arrays (n x kv_heads*k and n x kv_heads*dv, counted in device_bytes, freed with the handle) and rounded by one bandwidth-bound launch
+ *     at the end of the call, whatever the rounds and however long the columns.
+ *   - These change no bit: access width (8-byte accesses to a 16-bit operand and 16-byte ones to an fp32 operand when pointer and ld allow them
+ *     for every operand and, with heads > 1, k and dv are multiples of 4; element accesses otherwise), leading dimensions, alignment, pointer
+ *     kind, method, stream, async and option "attention_backward_heads".  The two output types are independent: the row kernels see only dQ's,
+ *     the column kernels only dK's and dV's.
+ *   - Memory: host or device pointers per operand; a host operand is staged through the buffers of the fp32 calls at its own element size.
+ *   - Errors: the rules above and every argument rule of spmv_hip_attention_gqa_backward(_lse) are SPMV_HIP_E_ARG before the handle's state is
+ *     looked at, every output untouched; the NULL-output rules (nothing wanted: no work; only dB wanted: no column pass, no transpose), the
+ *     handle kinds and SPMV_HIP_E_NOSTATE are those calls'. */
+int spmv_hip_attention_gqa_backward_16(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                                       const void *Matrix_Val, int heads, int kv_heads, int k, int dv, double scale,
+                                       int io_type,                             /* SPMV_HIP_T_F16 or SPMV_HIP_T_BF16: the element type of Q, K, V and G */
+                                       const void *Q, long long ldq, const void *K, long long ldk, const void *V, long long ldv,
+                                       const void *B, long long ldb,            /* fp32 bias planes, or NULL */
+                                       const void *G, long long ldg,            /* dL/dO, m x heads*dv */
+                                       const void *O, long long ldo,            /* fp32; O and L both NULL: the self-normalising row pass */
+                                       const void *L, long long ldl,            /* fp32; both given: driven by the final output and log-sum-exp */
+                                       int dq_type, void *dQ, long long lddq,   /* SPMV_HIP_T_HANDLE (fp32) or == io_type; dQ NULL: not wanted */
+                                       int dkv_type, void *dK, long long lddk,  /* the type of dK and dV; n x kv_heads*k, or NULL */
+                                       void *dV, long long lddv,                /* n x kv_heads*dv, or NULL */
+                                       void *dB, long long lddb);               /* fp32, heads planes of nnz, or NULL */
+
 /* ---- options --------------------------------------------------------------------------------
  * Resolved once per handle, at create: process-wide value (spmv_hip_set_option / env), overridden by the
  * calling thread's value (spmv_hip_set_thread_option) -- so two threads can create differently tuned handles

@@ -84,6 +84,12 @@ double spmv_hip_time_attention_gqa_backward_lse_launches(spmv_Handle_t handle, i
                                                          long long ldk, const void *V, long long ldv, const void *B, long long ldb, const void *G, long long ldg, const void *O,
                                                          long long ldo, const void *L, long long ldl, void *dQ, long long lddq, void *dK, long long lddk, void *dV,
                                                          long long lddv, void *dB, long long lddb, int warmup, int iters, float *ms_out);
+/* The same for spmv_hip_attention_gqa_backward_16 (io_type ahead of Q, dq_type and dkv_type ahead of dQ and dK, as there; DEVICE pointers; O and L
+   both NULL or both given). */
+double spmv_hip_time_attention_gqa_backward_16_launches(spmv_Handle_t handle, int heads, int kv_heads, int k, int dv, double scale, int io_type, const void *Q, long long ldq,
+                                                        const void *K, long long ldk, const void *V, long long ldv, const void *B, long long ldb, const void *G, long long ldg,
+                                                        const void *O, long long ldo, const void *L, long long ldl, int dq_type, void *dQ, long long lddq, int dkv_type, void *dK,
+                                                        long long lddk, void *dV, long long lddv, void *dB, long long lddb, int warmup, int iters, float *ms_out);
 /* copies the built transpose map to host: rowptr_t (n+1 entries) and perm (nnz entries: perm[p] = CSR index in A of the entry at
    position p of A^T's CSR); either may be NULL.  SPMV_HIP_E_NOSTATE until the transpose is built. */
 int spmv_hip_transpose_map(spmv_Handle_t handle, int *rowptr_t, int *perm);

@@ -180,6 +180,13 @@ FUNCTIONS = {
                                                                        _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong,
                                                                        _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, C.c_int, C.c_int,
                                                                        C.POINTER(C.c_float)]),
+    "spmv_hip_attention_gqa_backward_16": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _V, C.c_longlong, _V, C.c_longlong,
+                                                     _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, C.c_int, _V, C.c_longlong,
+                                                     C.c_int, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong]),
+    "spmv_hip_time_attention_gqa_backward_16_launches": (C.c_double, [spmv_Handle_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _V, C.c_longlong, _V, C.c_longlong,
+                                                                      _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, C.c_int, _V,
+                                                                      C.c_longlong, C.c_int, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, C.c_int, C.c_int,
+                                                                      C.POINTER(C.c_float)]),
     # include/spmv_io.h (host only)
     "spmv_io_read_mtx": (C.c_int, [C.c_char_p, C.c_size_t, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_V)]),
     "spmv_io_cache_path": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t]),
@@ -879,6 +886,67 @@ def time_attention_gqa_backward_lse_launches(handle, heads, kv_heads, Q, K, V, B
     return _timed("spmv_hip_time_attention_gqa_backward_lse_launches", (handle, int(heads), int(kv_heads), k, dv, float(scale), *rest), warmup, iters)
 
 
+def _attention_gqa_backward_16_args(handle, heads, kv_heads, Q, K, V, B, G, O, L, dQ, dK, dV, dB, ldb, lddb, ldl):
+    """-> (k, dv, the C arguments from io_type on) of an attention_gqa_backward_16 call.  The types come from the tensors' dtypes: Q, K, V and G
+    torch tensors that are all torch.float16 or all torch.bfloat16; dQ of that dtype or torch.float32; dK and dV, where both are given, of one such
+    dtype; O and L given together or not at all.  Everything is checked here, before any device call."""
+    import torch
+    codes = {torch.float16: T_F16, torch.bfloat16: T_BF16}
+    for t, name in ((Q, "Q"), (K, "K"), (V, "V"), (G, "G")):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor (numpy has no bfloat16), not {type(t).__name__}")
+    if Q.dtype not in codes or K.dtype != Q.dtype or V.dtype != Q.dtype or G.dtype != Q.dtype:
+        raise TypeError(f"Q, K, V and G must all be torch.float16 or all torch.bfloat16, not {Q.dtype}, {K.dtype}, {V.dtype} and {G.dtype}")
+    if handle and handle.contents.data_size == 8:   # the public handle's own field: no device call
+        raise TypeError("16-bit Q, K, V and G need a float32 handle, not a float64 one")
+    for t, name in ((dQ, "dQ"), (dK, "dK"), (dV, "dV")):
+        if t is not None and (not isinstance(t, torch.Tensor) or (t.dtype != Q.dtype and t.dtype != torch.float32)):
+            raise TypeError(f"{name} must be a torch.Tensor of {Q.dtype} or torch.float32")
+    if dK is not None and dV is not None and dK.dtype != dV.dtype:
+        raise TypeError(f"dK and dV share one type, not {dK.dtype} and {dV.dtype}")
+    for t, name in ((B, "B"), (dB, "dB"), (O, "O"), (L, "L")):
+        if isinstance(t, torch.Tensor) and t.dtype != torch.float32:
+            raise TypeError(f"{name} must be torch.float32, not {t.dtype}")
+    if (O is None) != (L is None):
+        raise ValueError("O and L are given together (the backward driven by them) or not at all")
+    dkv = dK if dK is not None else dV
+    io_type = codes[Q.dtype]
+    dq_type = T_HANDLE if dQ is not None and dQ.dtype == torch.float32 else io_type
+    dkv_type = T_HANDLE if dkv is not None and dkv.dtype == torch.float32 else io_type
+    k, dv, rest = _attention_gqa_backward_args(heads, kv_heads, Q, K, V, B, G, dQ, dK, dV, dB, ldb, lddb)
+    if O is None:
+        po, ldo, pl, ll = None, int(heads) * dv, None, 0
+    else:
+        po, _, wo, ldo = _block(O, "O")
+        if wo != int(heads) * dv:
+            raise ValueError(f"O has {wo} columns, expected {int(heads) * dv}")
+        ldo = int(max(ldo, 1))
+        pl, ll = (_ptr(L), int(ldl)) if ldl is not None else _lse_planes(L, "L", heads)
+    # io_type | Q, K, V | B | G | O, L | dq_type, dQ | dkv_type, dK, dV | dB
+    return k, dv, [io_type, *rest[:10], po, ldo, pl, ll, dq_type, *rest[10:12], dkv_type, *rest[12:]]
+
+
+def attention_gqa_backward_16(handle, m, RowPtr, ColIdx, Matrix_Val, heads, kv_heads, Q, K, V, B, G, O=None, L=None, dQ=None, dK=None, dV=None, dB=None, scale=None,
+                              check=True, ldb=None, lddb=None, ldl=None):
+    """attention_gqa_backward() (O and L None) or attention_gqa_backward_lse() (both given, torch.float32) on 16-bit Q, K, V and G over an fp32 handle
+    (spmv_hip_attention_gqa_backward_16): Q, K, V and G are torch tensors, all torch.float16 or all torch.bfloat16, on the CPU or the device; dQ, and
+    dK / dV together, are tensors of that dtype or of torch.float32 (None: not wanted); B and dB are fp32.  An fp32 output and dB have the bits of the
+    fp32 call on Q.float(), K.float(), V.float(), G.float(); a 16-bit output is that result rounded once, g32.to(dtype) -- also over groups of heads
+    (kv_heads < heads), whose sums are made in fp32 whatever option "attention_backward_heads" says.  Mixed dtypes or a float64 handle: TypeError.
+    On a band the call is no faster than widening first; what it saves is the fp32 copies.  -> the return code."""
+    k, dv, rest = _attention_gqa_backward_16_args(handle, heads, kv_heads, Q, K, V, B, G, O, L, dQ, dK, dV, dB, ldb, lddb, ldl)
+    scale = 1.0 / np.sqrt(k) if scale is None and k > 0 else (0.0 if scale is None else scale)
+    return _checked(load().spmv_hip_attention_gqa_backward_16(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), int(heads), int(kv_heads), k, dv,
+                                                              float(scale), *rest), "spmv_hip_attention_gqa_backward_16", check)
+
+
+def time_attention_gqa_backward_16_launches(handle, heads, kv_heads, Q, K, V, B, G, O=None, L=None, dQ=None, dK=None, dV=None, dB=None, scale=None, warmup=10, iters=100):
+    """-> (mean_ms, per-call ms array) of spmv_hip_attention_gqa_backward_16 on device operands (spmv_hip_time_attention_gqa_backward_16_launches)."""
+    k, dv, rest = _attention_gqa_backward_16_args(handle, heads, kv_heads, Q, K, V, B, G, O, L, dQ, dK, dV, dB, None, None, None)
+    scale = 1.0 / np.sqrt(k) if scale is None else scale
+    return _timed("spmv_hip_time_attention_gqa_backward_16_launches", (handle, int(heads), int(kv_heads), k, dv, float(scale), *rest), warmup, iters)
+
+
 def _take_csr(m, n, nnz, rp, ci, va, dtype):
     """Copy malloc'ed C arrays into numpy arrays and free the C side."""
     from .synth import CSR
@@ -1166,6 +1234,25 @@ class Handle:
         dB = self._like(Q, (int(heads), self.nnz)) if need[3] else None
         rp, ci, va = self._keep
         attention_gqa_backward_lse(self.h, self.m, rp, ci, va, heads, kv_heads, Q, K, V, bias, G, O, L, dQ, dK, dV, dB, scale)
+        return dQ, dK, dV, dB
+
+    def attention_gqa_backward_16(self, Q, K, V, B, G, heads, kv_heads, scale=None, O=None, L=None, need=(True, True, True, True), dq_dtype=None, dkv_dtype=None):
+        """-> (dQ, dK, dV, dB): attention_gqa_backward() -- O and L None -- or attention_gqa_backward_lse() -- the final fp32 O and L given -- on
+        torch.float16 or torch.bfloat16 Q, K, V and G over this fp32 handle (spmv_hip_attention_gqa_backward_16), nothing widened in memory.  dQ is of
+        dq_dtype and dK and dV of dkv_dtype -- None: Q's dtype; or torch.float32 --, allocated on Q's device; dB is (heads, nnz) fp32; need: which
+        of the four are wanted.  An fp32 gradient and dB have the bits of the fp32 call on the .float() copies; a 16-bit gradient is that result
+        rounded once."""
+        import torch
+        if not all(isinstance(t, torch.Tensor) for t in (Q, K, V, G)):
+            raise TypeError("Q, K, V and G must be torch tensors")
+        dq_dtype = Q.dtype if dq_dtype is None else dq_dtype
+        dkv_dtype = Q.dtype if dkv_dtype is None else dkv_dtype
+        dQ = torch.empty((self.m, Q.shape[1]), dtype=dq_dtype, device=Q.device) if need[0] else None
+        dK = torch.empty((self.n, K.shape[1]), dtype=dkv_dtype, device=Q.device) if need[1] else None
+        dV = torch.empty((self.n, V.shape[1]), dtype=dkv_dtype, device=Q.device) if need[2] else None
+        dB = torch.empty((int(heads), self.nnz), dtype=torch.float32, device=Q.device) if need[3] else None
+        rp, ci, va = self._keep
+        attention_gqa_backward_16(self.h, self.m, rp, ci, va, heads, kv_heads, Q, K, V, B, G, O, L, dQ, dK, dV, dB, scale)
         return dQ, dK, dV, dB
 
     def update_values(self, val):

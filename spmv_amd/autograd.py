@@ -28,7 +28,7 @@ Both take a trailing keyword bias=None: a tensor of (nnz,) -- one plane, shared 
 scaled scores before the softmax (Handle.attention_bias), which receives a gradient (Handle.attention_bias_backward).
 
 attention, attention_heads and attention_parts also take Q, K and V that are all torch.float16 or all torch.bfloat16 on a float32 handle
-(Handle.attention_gqa_lse_16: the kernels read the 16-bit elements and compute in float32): the result and the gradients of Q, K and V have
+(Handle.attention_gqa_lse_16, Handle.attention_gqa_backward_16: the kernels read the 16-bit elements and compute in float32): the result and the gradients of Q, K and V have
 that dtype and are the float32 results of the same function on .float() copies, each rounded once with .to(dtype); the bias and its gradient
 stay float32.
 
@@ -479,11 +479,53 @@ def _attention_gqa_backward(handle, heads, kv_heads, scale, fused, Q2, K2, V2, B
     return dQ, dK, dV, _bias_grad(dB, B2)
 
 
+def _attention_backward_16(handle, heads, kv_heads, scale, fused, Q2, K2, V2, B2, G, need, need_b):
+    """-> (dQ, dK, dV, dB) on float16 / bfloat16 Q2, K2, V2 and G without a float32 copy of any of them (Handle.attention_gqa_backward_16): ONE
+    call with 16-bit gradients (fused), or one call per query head on 16-bit column slices.  Per head, a group's dK and dV (kv_heads < heads) are
+    that head's float32 terms added in torch in ascending head -- the first assigned, the others += -- and rounded once at the end: the fused
+    call's chain and its one rounding, so both modes give float32_gradient.to(dtype) bit for bit.  dB is float32."""
+    from . import api
+    if not (any(need) or need_b):
+        return None, None, None, None
+    if handle.nnz == 0:
+        return _zero_grads(Q2, K2, V2, B2, need, need_b)
+    _on_current_stream(handle)
+    G2 = _block(G.to(Q2.dtype), G.shape[1])
+    if fused:   # every head in one call
+        dQ, dK, dV, dB = handle.attention_gqa_backward_16(Q2, K2, V2, B2, G2, heads, kv_heads, scale, need=(*need, need_b))
+        return dQ, dK, dV, _bias_grad(dB, B2)
+    gs, k, dv = heads // kv_heads, Q2.shape[1] // heads, V2.shape[1] // kv_heads
+    acc = Q2.dtype if gs == 1 else torch.float32   # a group's sums are made in float32 and rounded once
+    dQ = torch.empty_like(Q2, memory_format=torch.contiguous_format) if need[0] else None
+    dK = torch.empty(K2.shape, dtype=acc, device=K2.device) if need[1] else None
+    dV = torch.empty(V2.shape, dtype=acc, device=V2.device) if need[2] else None
+    dB = torch.empty((heads, handle.nnz), dtype=torch.float32, device=Q2.device) if need_b else None
+    tK = torch.empty((handle.n, k), dtype=acc, device=K2.device) if need[1] and gs > 1 else None   # one head's term of dK / dV: what the group's later heads add
+    tV = torch.empty((handle.n, dv), dtype=acc, device=V2.device) if need[2] and gs > 1 else None
+    rp, ci, va = handle._keep
+    for h in range(heads):
+        g, first = h // gs, h % gs == 0
+        cq, co, ck, cv = slice(h * k, (h + 1) * k), slice(h * dv, (h + 1) * dv), slice(g * k, (g + 1) * k), slice(g * dv, (g + 1) * dv)
+        oK = None if dK is None else (dK[:, ck] if first else tK)
+        oV = None if dV is None else (dV[:, cv] if first else tV)
+        api.attention_gqa_backward_16(handle.h, handle.m, rp, ci, va, 1, 1, Q2[:, cq], K2[:, ck], V2[:, cv], None if B2 is None else (B2 if B2.dim() == 1 else B2[h]),
+                                      G2[:, co], None, None, None if dQ is None else dQ[:, cq], oK, oV, None if dB is None else dB[h], scale)
+        if not first:   # (..(first + second) + ..) + this one: plain float32 additions in ascending head
+            if dK is not None:
+                dK[:, ck] += tK
+            if dV is not None:
+                dV[:, cv] += tV
+    if gs > 1:
+        dK, dV = (None if dK is None else dK.to(Q2.dtype)), (None if dV is None else dV.to(Q2.dtype))
+    return dQ, dK, dV, _bias_grad(dB, B2)
+
+
 class _Attention16(torch.autograd.Function):
-    """float16 / bfloat16 Q, K and V on a float32 handle.  Forward: ONE Handle.attention_gqa_lse_16 call with O in that dtype (no L).  Backward: Q, K,
-    V and G widened to float32 and handed to the backward the float32 Function of the same arguments runs (_attention_backward_composed / _fused,
-    _attention_heads_backward or _attention_gqa_backward, in the `backward=` mode asked for); every gradient is its float32 gradient .to(dtype), the
-    bias gradient stays float32.  heads None: attention(); kv_heads None: as many K / V heads as query heads"""
+    """float16 / bfloat16 Q, K and V on a float32 handle.  Forward: ONE Handle.attention_gqa_lse_16 call with O in that dtype (no L).  Backward, in
+    the `backward=` mode asked for: "fused" is ONE Handle.attention_gqa_backward_16 call with 16-bit gradients and "per_head" one such call per head
+    on 16-bit column slices (_attention_backward_16) -- no float32 copy of Q, K, V or G is made; "composed" (attention() only) widens Q, K, V and G
+    and runs _attention_backward_composed, its gradients rounded with .to(dtype).  Every gradient is the float32 gradient .to(dtype), the bias
+    gradient stays float32.  heads None: attention(); kv_heads None: as many K / V heads as query heads"""
 
     @staticmethod
     def forward(ctx, handle, Q, K, V, heads, kv_heads, scale, mode, bias=None):
@@ -505,15 +547,12 @@ class _Attention16(torch.autograd.Function):
         need_b = B2 is not None and bool(ctx.needs_input_grad[8])
         if not (any(need) or need_b):
             return (None,) * 9
-        wide, Gf = (Q2.float(), K2.float(), V2.float(), B2), G.float()
-        if heads is None:
-            out = (_attention_backward_fused if mode == "fused" else _attention_backward_composed)(handle, scale, *wide, Gf, need, need_b)
-        elif kv_heads is None:
-            out = _attention_heads_backward(handle, heads, scale, mode == "fused", *wide, Gf, need, need_b)
-        else:
-            out = _attention_gqa_backward(handle, heads, kv_heads, scale, mode == "fused", *wide, Gf, need, need_b)
-        dB = out[3]
-        dQ, dK, dV = (None if g is None else g.to(Q2.dtype) for g in out[:3])
+        if mode == "composed":   # attention() only: the composition runs in float32, on widened copies
+            out = _attention_backward_composed(handle, scale, Q2.float(), K2.float(), V2.float(), B2, G.float(), need, need_b)
+            dQ, dK, dV = (None if g is None else g.to(Q2.dtype) for g in out[:3])
+            return None, dQ, dK, dV, None, None, None, None, out[3]
+        h = 1 if heads is None else heads
+        dQ, dK, dV, dB = _attention_backward_16(handle, h, h if kv_heads is None else kv_heads, scale, mode == "fused", Q2, K2, V2, B2, G, need, need_b)
         return None, dQ, dK, dV, None, None, None, None, dB
 
 
@@ -556,8 +595,11 @@ def attention_heads(handle, Q, K, V, heads, scale=None, backward="per_head", *, 
 
     16-bit tensors: on a float32 handle Q, K and V may all be torch.float16 or all torch.bfloat16 (mixed dtypes, or 16-bit tensors on a float64
     handle, are a TypeError).  The forward is then ONE Handle.attention_gqa_lse_16 call -- the kernels read the 16-bit elements, compute in float32
-    and round O once -- and the backward widens Q, K, V and dL/dO to float32 and runs the float32 backward in the mode asked for (a 16-bit backward
-    kernel does not exist yet).  The contract: O is fp32_result.to(dtype) and every gradient of Q, K and V is fp32_gradient.to(dtype), where the
+    and round O once -- and the backward reads them as they are too (Handle.attention_gqa_backward_16; no float32 copy of Q, K, V or dL/dO):
+    backward="fused" is ONE such call with 16-bit gradients, the default mode one call per head on 16-bit column slices (a group's dK and dV added
+    in float32 in ascending head and rounded once).  On a banded pattern the 16-bit backward is no faster than widening first (DESIGN.md 3.25);
+    what it saves is the float32 twins of every operand.
+    The contract: O is fp32_result.to(dtype) and every gradient of Q, K and V is fp32_gradient.to(dtype), where the
     float32 results are those of this same function on Q.float(), K.float(), V.float() with dL/dO.float(); the bias and its gradient stay float32,
     and the bias gradient has the float32 run's bits."""
     if backward not in ("per_head", "fused"):
@@ -615,7 +657,8 @@ def attention(handle, Q, K, V, scale=None, backward="composed", *, bias=None):
     k, dv > 1.
 
     16-bit tensors: on a float32 handle Q, K and V may all be torch.float16 or all torch.bfloat16, as in attention_heads(): the forward is one
-    Handle.attention_gqa_lse_16 call, the backward the float32 backward (in the mode asked for) on widened copies; O is fp32_result.to(dtype) and
+    Handle.attention_gqa_lse_16 call; backward="fused" is one Handle.attention_gqa_backward_16 call on the 16-bit tensors, "composed" the float32
+    composition on widened copies; O is fp32_result.to(dtype) and
     every gradient fp32_gradient.to(dtype), the float32 results being those of this function on .float() copies -- for k, dv > 1: the 16-bit
     forward is always the fused kernel, and at width 1 the float32 results meant are those of backward="fused" (the composed float32 backward may
     take the spmv schedule there, whose order is the method's own); the bias and its gradient stay float32."""
@@ -674,10 +717,10 @@ class _AttentionParts(torch.autograd.Function):
         need = ctx.needs_input_grad[4:]
         need_q, need_k, need_v = bool(need[0]), [bool(x) for x in need[1:1 + n]], [bool(x) for x in need[1 + n:1 + 2 * n]]
         need_b = [Bs[r] is not None and bool(need[1 + 2 * n + r]) for r in range(n)]
-        half = Q2.dtype if Q2.dtype in _HALF else None
-        if half is not None:   # widened: the float32 backward below, its gradients rounded once at the end
-            Q2, Ks, Vs, G = Q2.float(), [t.float() for t in Ks], [t.float() for t in Vs], G.float()
-        G2 = _block(G, G.shape[1])
+        half = Q2.dtype if Q2.dtype in _HALF else None   # 16-bit: one Handle.attention_gqa_backward_16 per part on the tensors as they are
+        G2 = _block(G if half is None else G.to(half), G.shape[1])
+        live = sum(1 for r, h in enumerate(handles) if h.nnz > 0 and (need_q or need_k[r] or need_v[r] or need_b[r]))
+        dq_dtype = torch.float32 if live > 1 else half   # more than one part adds to dQ: summed in float32 in part order, rounded once below
         dQ, dKs, dVs, dBs = None, [None] * n, [None] * n, [None] * n
         for r, h in enumerate(handles):
             if not (need_q or need_k[r] or need_v[r] or need_b[r]):
@@ -688,8 +731,12 @@ class _AttentionParts(torch.autograd.Function):
                 dBs[r] = torch.zeros_like(Bs[r]) if need_b[r] else None
                 continue
             _on_current_stream(h)
-            dq, dKs[r], dVs[r], dB = h.attention_gqa_backward_lse(Q2, Ks[r], Vs[r], Bs[r], G2, O, L, heads, kv_heads, scale,
-                                                                   need=(need_q, need_k[r], need_v[r], need_b[r]))
+            if half is not None:
+                dq, dKs[r], dVs[r], dB = h.attention_gqa_backward_16(Q2, Ks[r], Vs[r], Bs[r], G2, heads, kv_heads, scale, O=O, L=L,
+                                                                      need=(need_q, need_k[r], need_v[r], need_b[r]), dq_dtype=dq_dtype)
+            else:
+                dq, dKs[r], dVs[r], dB = h.attention_gqa_backward_lse(Q2, Ks[r], Vs[r], Bs[r], G2, O, L, heads, kv_heads, scale,
+                                                                       need=(need_q, need_k[r], need_v[r], need_b[r]))
             dBs[r] = _bias_grad(dB, Bs[r])
             if need_q:   # the first part's, every later one added in part order
                 if dQ is None:
@@ -698,8 +745,8 @@ class _AttentionParts(torch.autograd.Function):
                     dQ += dq
         if need_q and dQ is None:
             dQ = torch.zeros_like(Q2)
-        if half is not None:
-            dQ, dKs, dVs = (None if dQ is None else dQ.to(half)), [None if g is None else g.to(half) for g in dKs], [None if g is None else g.to(half) for g in dVs]
+        if half is not None and dQ is not None:
+            dQ = dQ.to(half)   # the one rounding of a dQ summed over parts; a no-op on the 16-bit dQ of a single part
         return (None, None, None, None, dQ, *dKs, *dVs, *dBs)
 
 
@@ -719,7 +766,9 @@ def attention_parts(handles, Q, Ks, Vs, heads, scale=None, *, kv_heads=None, bia
 
     16-bit tensors: on float32 handles Q and every K_r and V_r may all be torch.float16 or all torch.bfloat16.  Each part is then one
     Handle.attention_gqa_lse_16 call with float32 O and L; the fold through Handle.attention_merge stays float32 and the merged O is rounded once at
-    the end (the float32 merged O and L are what is saved).  The backward widens Q, the K_r, V_r and dL/dO and runs the float32 backward above.  O is
+    the end (the float32 merged O and L are what is saved).  The backward is one Handle.attention_gqa_backward_16 call per part on the 16-bit
+    tensors with the saved float32 O and L: dK_r and dV_r come back in the 16-bit type; with more than one part dQ is float32 per part, summed in
+    part order and rounded once, with one part it is 16-bit.  O is
     fp32_result.to(dtype) and every gradient of Q, K_r and V_r fp32_gradient.to(dtype), the float32 results being those of this function on .float()
     copies; L, the biases and their gradients stay float32."""
     handles = list(handles)

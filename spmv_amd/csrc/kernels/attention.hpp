@@ -118,9 +118,9 @@ __device__ __forceinline__ T att_add_bias(T t, T b)
 
 // The scaled scores of one tile of 64 entries.  Lane l passes its entry's row i (-1: no entry) and column j; the tile's entries are multiplied
 // in CW rounds of 64 / CW, CW adjacent lanes per entry (sddmm_kernel's rounds, the same chain and the same tree), and t of entry e lands in
-// slot[e] (the wave's own LDS; the caller synchronizes).  Every lane of the wave must call.
-template <typename T, int CW, bool VEC, typename S = T>
-__device__ __forceinline__ void att_tile_scores(int i, int j, int lane, int k, const S *__restrict__ q, long long ldq, const S *__restrict__ kk, long long ldk, T scale,
+// slot[e] (the wave's own LDS; the caller synchronizes).  Every lane of the wave must call.  S, S2: the storage types of q and of kk (sddmm_chain).
+template <typename T, int CW, bool VEC, typename S = T, typename S2 = S>
+__device__ __forceinline__ void att_tile_scores(int i, int j, int lane, int k, const S *__restrict__ q, long long ldq, const S2 *__restrict__ kk, long long ldk, T scale,
                                                 T *slot)
 {
     constexpr int W = SddmmShape<T>::W, G = kWave / CW;

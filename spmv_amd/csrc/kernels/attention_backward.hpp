@@ -52,6 +52,17 @@
 // row, q = G, kk = O; one dot per long row), left in LDS with the rows' L beside it.  dB, dS, the stores for the column pass and dQ are as
 // before; the column kernels are not touched.  The instantiations without STATS do not look at o and lse and are the code from before.
 //
+// 16-bit operands (spmv_hip_attention_gqa_backward_16; the instantiations with a storage type other than T, launched from
+// spmv_attention_backward_16.hip): Q, K, V and G are fp16 or bf16 in memory (SI), dQ is float or that type (SQ, the row kernels) and dK / dV are
+// float or that type (SO, the column kernels) -- kernels/storage16.hpp.  The blocks widen what they load and round what they store; attb_p /
+// attb_ds, s_p / s_d, the bias, dB, O, L, scale and every arithmetic step stay float, and the lane mapping stays float's (4 columns per lane, an
+// 8-byte segment of a 16-bit operand), so a float output has the bits of the float kernels on the widened operands and a 16-bit one is that value
+// rounded ONCE.  The STATS dot <G row, O row> meets a 16-bit row and a float one (att_tile_scores' second storage type).  A 16-bit dK / dV is
+// never read back as a partial sum: the GROUPED column kernels exist with float outputs only (static_assert) -- with gs > 1 the launch side
+// hands them two handle-owned float arrays (n x kv_heads * k, n x kv_heads * dv), in which the rounds and the long columns add as before, and
+// attention_bwd_narrow_kernel rounds every element once into the caller's arrays at the end.  With the defaults (SI = SQ = SO = T) the kernels
+// are the code from before.
+//
 // Arithmetic and order: the composition's, because its blocks are the composition's (kernels/row_blocks.hpp) -- t and P are
 // spmv_hip_attention's; dP is sddmm's dot for dv; D is row_softmax_backward's by row length; dS is one subtraction and two plain
 // multiplications; dQ, dK and dV are spmm's chains.  Contraction is pinned off: the fmas written out are the only fused operations.
@@ -84,15 +95,24 @@ struct AttentionBwdArgs {
     long long ldb = 0, lddb = 0;
     const void *o = nullptr, *lse = nullptr; // both set: the STATS row pass from the final O (m x heads * dv) and L (head hd's row i at lse + hd * ldl + i)
     long long ldo = 0, ldl = 0;
+    // attention_backward_16_launch only.  io_type (SPMV_HIP_T_F16 / _BF16): the element type of q, kk, v, g; dq_type / dkv_type: 0 -- dq / dk and
+    // dvo are float --, or io_type.  gs > 1 with 16-bit dK / dV: dk and dvo are the handle's float arrays (dkv_type 0, lddk = kv_heads * k,
+    // lddv = kv_heads * dv) and nar_dk / nar_dv the caller's 16-bit ones, rounded into after the last round (nullptr: not wanted)
+    int io_type = 0, dq_type = 0, dkv_type = 0;
+    void *nar_dk = nullptr, *nar_dv = nullptr;
+    long long nar_lddk = 0, nar_lddv = 0;
+    int n = 0, kv_heads = 1; // the rows and K / V heads of dk / dvo (the narrowing)
 };
 
 // spmv_attention_backward.hip: the launches of one call on `stream`, ceil(heads / hg) rounds of a row pass and a column pass
 hipError_t attention_backward_launch(const AttentionBwdArgs &a, bool f64, hipStream_t stream);
+// spmv_attention_backward_16.hip: the same with io_type = F16 or BF16 (float arithmetic), and the narrowing of grouped 16-bit dK / dV
+hipError_t attention_backward_16_launch(const AttentionBwdArgs &a, hipStream_t stream);
 
 // att_tile_scores without the scaling, for a lane group width known at run time (wave-uniform): dP's dots, sddmm's order for dv columns.
-// The multiplication by one changes no bit.
-template <typename T, bool VEC>
-__device__ __forceinline__ void attb_tile_dots(int cw, int i, int j, int lane, int dv, const T *__restrict__ g, long long ldg, const T *__restrict__ v, long long ldv, T *slot)
+// The multiplication by one changes no bit.  S, S2: the storage types of g and of v (att_tile_scores).
+template <typename T, bool VEC, typename S = T, typename S2 = S>
+__device__ __forceinline__ void attb_tile_dots(int cw, int i, int j, int lane, int dv, const S *__restrict__ g, long long ldg, const S2 *__restrict__ v, long long ldv, T *slot)
 {
     with_width(cw, [&](auto CW) { att_tile_scores<T, decltype(CW)::value, VEC>(i, j, lane, dv, g, ldg, v, ldv, T(1), slot); });
 }
@@ -103,11 +123,12 @@ __device__ __forceinline__ void attb_tile_dots(int cw, int i, int j, int lane, i
 // head over s_p / s_d, head hd on the columns from hd * k (Q, K, dQ) and hd * dv (V, G) and on plane hd of p_out / ds_out.
 // BIAS: bias (added to the scaled scores) and db (P (dP - D), before the scaling) as in the header; either may be nullptr.
 // STATS (with BIAS): P and D from the final o and lse (see the header) instead of the row's own reductions.
-template <typename T, int CW, bool VEC, bool BIAS, bool GROUPED, bool STATS = false>
+// SI, SQ: the storage types of Q / K / V / G and of dQ; other than T: 16-bit operands (see the header).
+template <typename T, int CW, bool VEC, bool BIAS, bool GROUPED, bool STATS = false, typename SI = T, typename SQ = T>
 __global__ __launch_bounds__(kBlock) void attention_bwd_rows_kernel(int nb, const int *__restrict__ split, const int *__restrict__ rowptr, const int *__restrict__ colidx,
                                                                     int heads, long long plane, int k, int dv, int cwd, int lgk, T scale,
-                                                                    const T *__restrict__ q, long long ldq, const T *__restrict__ kk, long long ldk,
-                                                                    const T *__restrict__ v, long long ldv, const T *__restrict__ g, long long ldg, T *__restrict__ dq,
+                                                                    const SI *__restrict__ q, long long ldq, const SI *__restrict__ kk, long long ldk,
+                                                                    const SI *__restrict__ v, long long ldv, const SI *__restrict__ g, long long ldg, SQ *__restrict__ dq,
                                                                     long long lddq, T *__restrict__ p_out, T *__restrict__ ds_out, const T *__restrict__ bias,
                                                                     long long ldb, T *__restrict__ db, long long lddb, int gs, int gpos,
                                                                     const T *__restrict__ o = nullptr, long long ldo = 0, const T *__restrict__ lse = nullptr,
@@ -136,7 +157,7 @@ __global__ __launch_bounds__(kBlock) void attention_bwd_rows_kernel(int nb, cons
         for (int hd = 0; hd < heads; ++hd) {
             const int lane = att_per_head(lane0), subk = lane >> lgk, ck0 = (lane & (cwk - 1)) * V;
             const int hkv = GROUPED ? kvh : hd;
-            const T *qh = q + (long long) hd * k, *kh = kk + (long long) hkv * k, *vh = v + (long long) hkv * dv, *gh = g + (long long) hd * dv; // the head's first columns; K and V: its group's
+            const SI *qh = q + (long long) hd * k, *kh = kk + (long long) hkv * k, *vh = v + (long long) hkv * dv, *gh = g + (long long) hd * dv; // the head's first columns; K and V: its group's
             if constexpr (GROUPED) {
                 if (++gc == gs) { gc = 0; ++kvh; }
             }
@@ -283,11 +304,11 @@ __global__ __launch_bounds__(kBlock) void attention_bwd_rows_kernel(int nb, cons
 
 // one workgroup per long row (len > kSpmmLongThr >= 256: every thread has a first term); the row's ranges of every plane of pa (attb_p) and
 // da (attb_ds) are its own: no other workgroup of this launch touches them.  Head hd parks in plane hd's range.  BIAS, STATS: as in the rows kernel.
-template <typename T, int CW, bool VEC, bool BIAS, bool GROUPED, bool STATS = false>
+template <typename T, int CW, bool VEC, bool BIAS, bool GROUPED, bool STATS = false, typename SI = T, typename SQ = T>
 __global__ __launch_bounds__(kBlock) void attention_bwd_long_kernel(int nlong, const int *__restrict__ longs, const int *__restrict__ rowptr, const int *__restrict__ colidx,
                                                                     int heads, long long plane, int k, int dv, int cwd, int lgk, T scale,
-                                                                    const T *__restrict__ q, long long ldq, const T *__restrict__ kk, long long ldk,
-                                                                    const T *__restrict__ v, long long ldv, const T *__restrict__ g, long long ldg, T *__restrict__ dq,
+                                                                    const SI *__restrict__ q, long long ldq, const SI *__restrict__ kk, long long ldk,
+                                                                    const SI *__restrict__ v, long long ldv, const SI *__restrict__ g, long long ldg, SQ *__restrict__ dq,
                                                                     long long lddq, T *pa, T *da, const T *__restrict__ bias, long long ldb, T *__restrict__ db,
                                                                     long long lddb, int gs, int gpos, const T *__restrict__ o = nullptr, long long ldo = 0,
                                                                     const T *__restrict__ lse = nullptr, long long ldl = 0)
@@ -305,7 +326,7 @@ __global__ __launch_bounds__(kBlock) void attention_bwd_long_kernel(int nlong, c
         [[maybe_unused]] int kvh = 0, gc = gpos; // GROUPED: the head's K / V block, kept by counting
         for (int hd = 0; hd < heads; ++hd) {
             const int hkv = GROUPED ? kvh : hd;
-            const T *qh = q + (long long) hd * k, *kh = kk + (long long) hkv * k, *vh = v + (long long) hkv * dv, *gh = g + (long long) hd * dv; // the head's first columns; K and V: its group's
+            const SI *qh = q + (long long) hd * k, *kh = kk + (long long) hkv * k, *vh = v + (long long) hkv * dv, *gh = g + (long long) hd * dv; // the head's first columns; K and V: its group's
             if constexpr (GROUPED) {
                 if (++gc == gs) { gc = 0; ++kvh; }
             }
@@ -379,14 +400,16 @@ __global__ __launch_bounds__(kBlock) void attention_bwd_long_kernel(int nlong, c
 // registers -- the group's first head is taken as it is, every other one is one plain addition -- and stored once per K / V block; a round
 // that starts inside a group (gpos > 0) first reads back what the lane itself stored in the round before, one that ends inside one stores
 // what it has.  Without GROUPED gs and gpos are not looked at and the kernel is the code from before the groups existed.
-template <typename T, int CW, bool VEC, bool GROUPED>
+// SI, SO: the storage types of G / Q and of dV / dK.  A 16-bit output is stored once per element and never read: no GROUPED instantiation has one.
+template <typename T, int CW, bool VEC, bool GROUPED, typename SI = T, typename SO = T>
 __global__ __launch_bounds__(kBlock) void attention_bwd_cols_kernel(int nb, const int *__restrict__ split, const int *__restrict__ rowptr, const int *__restrict__ colidx,
                                                                     const int *__restrict__ perm, int heads, long long plane, int k, int dv, const T *__restrict__ pv,
-                                                                    const T *__restrict__ dsv, int kcv, const T *__restrict__ g, long long ldg, T *__restrict__ dvo,
-                                                                    long long lddv, int kck, const T *__restrict__ q, long long ldq, T *__restrict__ dk, long long lddk,
+                                                                    const T *__restrict__ dsv, int kcv, const SI *__restrict__ g, long long ldg, SO *__restrict__ dvo,
+                                                                    long long lddv, int kck, const SI *__restrict__ q, long long ldq, SO *__restrict__ dk, long long lddk,
                                                                     int gs, int gpos)
 {
 #pragma clang fp contract(off)
+    static_assert(!GROUPED || std::is_same_v<SO, T>, "a 16-bit dK / dV is never read back: the grouped sums are made in float");
     constexpr int V = SpmmShape<T>::V, R = kWave / CW, CH = kSpmmChunk;
     __shared__ int s_col[kBlock / kWave][CH];
     __shared__ T s_p[kBlock / kWave][CH];
@@ -407,7 +430,7 @@ __global__ __launch_bounds__(kBlock) void attention_bwd_cols_kernel(int nb, cons
         [[maybe_unused]] int kvh = 0, gc = gpos;
         for (int hd = 0; hd < heads; ++hd) {
             const T *ph = pv + hd * plane, *dh = dsv + hd * plane;
-            const T *gh = g + (long long) hd * dv, *qh = q + (long long) hd * k; // the head's panel
+            const SI *gh = g + (long long) hd * dv, *qh = q + (long long) hd * k; // the head's panel
             T accv[V], acck[V];
 #pragma unroll
             for (int t = 0; t < V; ++t) accv[t] = acck[t] = T(0);
@@ -429,14 +452,14 @@ __global__ __launch_bounds__(kBlock) void attention_bwd_cols_kernel(int nb, cons
             } else {
                 const bool first = gc == 0, back = hd == 0 && gc > 0, last = gc + 1 == gs || hd + 1 == heads; // wave-uniform
                 if (have && !longrow && ncv > 0) {
-                    T *y = dvo + (long long) r * lddv + (long long) kvh * dv + c0;
+                    SO *y = dvo + (long long) r * lddv + (long long) kvh * dv + c0;
                     if (back) spmm_load_x<T, VEC>(y, ncv, runv); // this lane's own store of the round before
 #pragma unroll
                     for (int t = 0; t < V; ++t) runv[t] = first ? accv[t] : runv[t] + accv[t];
                     if (last) spmm_store_y<T, VEC>(y, ncv, runv);
                 }
                 if (have && !longrow && nck > 0) {
-                    T *y = dk + (long long) r * lddk + (long long) kvh * k + c0;
+                    SO *y = dk + (long long) r * lddk + (long long) kvh * k + c0;
                     if (back) spmm_load_x<T, VEC>(y, nck, runk);
 #pragma unroll
                     for (int t = 0; t < V; ++t) runk[t] = first ? acck[t] : runk[t] + acck[t];
@@ -451,14 +474,15 @@ __global__ __launch_bounds__(kBlock) void attention_bwd_cols_kernel(int nb, cons
 // spmm_long_kernel on A^T's long rows (columns of A with more than kSpmmLongThr entries), a workgroup each: per head, first dV's panel, then dK's
 // GROUPED: head hd's panel goes to its K / V block of dvo / dk, stored by the group's first head and added to what the same thread stored there
 // by every other one (long_row_panel's add) -- also across rounds (gpos: the round's first head's place in its group).  Else every head stores.
-template <typename T, int CW, bool VEC, bool GROUPED>
+template <typename T, int CW, bool VEC, bool GROUPED, typename SI = T, typename SO = T>
 __global__ __launch_bounds__(kBlock) void attention_bwd_cols_long_kernel(int nlong, const int *__restrict__ longs, const int *__restrict__ rowptr,
                                                                          const int *__restrict__ colidx, const int *__restrict__ perm, int heads, long long plane, int k, int dv,
-                                                                         const T *__restrict__ pv, const T *__restrict__ dsv, int kcv, const T *__restrict__ g, long long ldg,
-                                                                         T *__restrict__ dvo, long long lddv, int kck, const T *__restrict__ q, long long ldq, T *__restrict__ dk,
+                                                                         const T *__restrict__ pv, const T *__restrict__ dsv, int kcv, const SI *__restrict__ g, long long ldg,
+                                                                         SO *__restrict__ dvo, long long lddv, int kck, const SI *__restrict__ q, long long ldq, SO *__restrict__ dk,
                                                                          long long lddk, int gs, int gpos)
 {
 #pragma clang fp contract(off)
+    static_assert(!GROUPED || std::is_same_v<SO, T>, "a 16-bit dK / dV is never added to: the grouped sums are made in float");
     constexpr int V = SpmmShape<T>::V, KP = SpmmShape<T>::KP, G = kBlock / CW;
     __shared__ T part[kSpmmSegs][KP];
     const int tid = (int) threadIdx.x, sub = tid / CW, c0 = (tid % CW) * V;
@@ -470,9 +494,10 @@ __global__ __launch_bounds__(kBlock) void attention_bwd_cols_long_kernel(int nlo
             for (int o = 0; o < 2; ++o) { // 0: dV (values P, X = G); 1: dK (values dS, X = Q)
                 const int kc = o ? kck : kcv;
                 if (kc <= 0) continue; // uniform over the workgroup
-                const T *val = (o ? dsv : pv) + hd * plane, *x = o ? q + (long long) hd * k : g + (long long) hd * dv;
+                const T *val = (o ? dsv : pv) + hd * plane;
+                const SI *x = o ? q + (long long) hd * k : g + (long long) hd * dv;
                 const long long ldx = o ? ldq : ldg;
-                T *y = o ? dk + (long long) r * lddk + (long long) hkv * k : dvo + (long long) r * lddv + (long long) hkv * dv;
+                SO *y = o ? dk + (long long) r * lddk + (long long) hkv * k : dvo + (long long) r * lddv + (long long) hkv * dv;
                 long_row_panel<T>(
                     e - s, kc, G, sub, c0, tid, part, y,
                     [&](int lo, int hi, int nc, T (&acc)[V]) {
@@ -486,6 +511,23 @@ __global__ __launch_bounds__(kBlock) void attention_bwd_cols_long_kernel(int nlo
                 if (++gc == gs) { gc = 0; ++kvh; }
             }
         }
+    }
+}
+
+// dst[r, c] = src[r, c] rounded once to the 16-bit type S, r < rows, c < w: src float with leading dimension w (the handle's arrays of the grouped
+// column pass), dst with leading dimension ldd.  A thread takes one segment of 4 columns (spmm_load_x / spmm_store_y: VEC -- w a multiple of 4 and
+// dst's rows 8-byte aligned -- one 16-byte load and one 8-byte store).  Every element of dst's rows x w block is written, by one thread.
+template <typename S, bool VEC>
+__global__ __launch_bounds__(kBlock) void attention_bwd_narrow_kernel(long long rows, int w, const float *__restrict__ src, S *__restrict__ dst, long long ldd)
+{
+    const int segs = (w + 3) / 4;
+    const long long total = rows * segs, stride = (long long) gridDim.x * kBlock;
+    for (long long i = (long long) blockIdx.x * kBlock + threadIdx.x; i < total; i += stride) {
+        const long long r = i / segs;
+        const int c0 = (int) (i - r * segs) * 4, nc = min(4, w - c0);
+        float x[4];
+        spmm_load_x<float, VEC>(src + r * w + c0, nc, x);
+        spmm_store_y<float, VEC>(dst + r * ldd + c0, nc, x);
     }
 }
 

@@ -75,9 +75,10 @@ __device__ __forceinline__ void sddmm_load(const S *p, int nc, T (&o)[SddmmShape
     }
 }
 
-// one lane's chain over its columns c0, c0 + 1, .., then c0 + step, .. (c0 < k); S: the operands' storage type (sddmm_load)
-template <typename T, bool VEC, typename S = T>
-__device__ __forceinline__ T sddmm_chain(const S *__restrict__ u, const S *__restrict__ v, int c0, int step, int k)
+// one lane's chain over its columns c0, c0 + 1, .., then c0 + step, .. (c0 < k); S, S2: the storage types of u and of v (sddmm_load), told by the
+// pointers -- they differ where a 16-bit row meets a float one (the backward's <G row, O row>)
+template <typename T, bool VEC, typename S = T, typename S2 = S>
+__device__ __forceinline__ T sddmm_chain(const S *__restrict__ u, const S2 *__restrict__ v, int c0, int step, int k)
 {
 #pragma clang fp contract(off) // the explicit fmas below are the only fused operations
     constexpr int W = SddmmShape<T>::W;

@@ -59,10 +59,17 @@ static int attention_backward_group(const spmv_dev *d, int heads, int limit, int
 // (spmv_hip_attention_gqa_backward); the planes, bias and db stay per QUERY head.  kv_heads = heads is spmv_hip_attention_bias_backward.
 // stats (spmv_hip_attention_gqa_backward_lse): o (m x heads * dv, ldo) and lse (`heads` planes ldl >= m apart) are the FINAL output and
 // log-sum-exp of the attention this handle's entries are a part of, and the row pass takes P and D from them; else they are not looked at.
+// io_type / dq_type / dkv_type (SPMV_HIP_T_*): 0, 0, 0 -- every operand in the handle's precision, the kernels of spmv_attention_backward.hip.
+// io_type F16 or BF16 (spmv_hip_attention_gqa_backward_16; a float handle): q, kk, v and g hold that type, dq holds it too (dq_type = io_type) or
+// float (0), dk and dvo likewise by dkv_type; leading dimensions count elements of the operand's own type, a host operand is staged at its own
+// element size; bias, db, o and lse stay float, and the kernels are those of spmv_attention_backward_16.hip.  With kv_heads < heads a 16-bit dk /
+// dvo is summed in the handle's float arrays attb_nk / attb_nv (n x kv_heads * k, n x kv_heads * dv; allocated at the first such call, grown when
+// a call needs more, counted in device_bytes) and rounded once into the caller's arrays by the call's last launch.  The types are the entry
+// point's to check (spmv_shim_attention_gqa_backward_16); here they are taken as they come.
 static int attention_gqa_backward_impl(spmv_dev *d, int heads, int kv_heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
                                        const void *v, long long ldv, const void *bias, long long ldb, const void *g, long long ldg, void *dq, long long lddq, void *dk,
                                        long long lddk, void *dvo, long long lddv, void *db, long long lddb, bool stats, const void *o, long long ldo, const void *lse,
-                                       long long ldl)
+                                       long long ldl, int io_type = SPMV_HIP_T_HANDLE, int dq_type = SPMV_HIP_T_HANDLE, int dkv_type = SPMV_HIP_T_HANDLE)
 {
     if (!d || !d->built) return fail(SPMV_HIP_E_NOSTATE, "attention_backward: schedule not built");
     if (kv_heads < 1 || heads < 1 || heads % kv_heads != 0)
@@ -92,9 +99,15 @@ static int attention_gqa_backward_impl(spmv_dev *d, int heads, int kv_heads, int
     const int hg = attention_backward_group(d, heads, max_heads, heads / kv_heads);
     if ((rc = spmm_plan(d)) || (rc = attention_backward_plan(d, hg)) || (cols && (rc = spmm_plan(t)))) return rc;
     const size_t s = d->vsize;
+    const size_t si = io_type ? 2 : s, sq = dq_type ? 2 : s, so = dkv_type ? 2 : s; // element sizes of Q / K / V / G, of dQ and of dK / dV
     Stager stg{d};
     AttentionBwdArgs a;
     a.m = d->m;
+    a.n = d->n;
+    a.kv_heads = kv_heads;
+    a.io_type = io_type;
+    a.dq_type = dq_type;
+    a.dkv_type = dkv_type;
     a.heads = heads;
     a.hg = hg;
     a.gs = heads / kv_heads;
@@ -132,18 +145,43 @@ static int attention_gqa_backward_impl(spmv_dev *d, int heads, int kv_heads, int
     a.db = db; a.lddb = lddb;
     if (stats && d->m > 0) { a.o = o; a.ldo = ldo; a.lse = lse; a.ldl = ldl; }
     // every row of a wanted output gets its elements, empty rows and columns their zeros: a staged result is written completely before it is copied back
-    if ((rc = stg.in(d->stage[STAGE_ATTB_Q], a.q, a.ldq, (size_t) d->m, (int) wk)) || (rc = stg.in(d->stage[STAGE_ATTB_K], a.kk, a.ldk, (size_t) d->n, (int) gk)) ||
-        (rc = stg.in(d->stage[STAGE_ATTB_V], a.v, a.ldv, (size_t) d->n, (int) gv)) || (rc = stg.in(d->stage[STAGE_ATTB_G], a.g, a.ldg, (size_t) d->m, (int) wv)) ||
-        (a.dq && (rc = stg.out(d->stage[STAGE_ATTB_DQ], a.dq, a.lddq, (size_t) d->m, (int) wk))) || (a.dk && (rc = stg.out(d->stage[STAGE_ATTB_DK], a.dk, a.lddk, (size_t) d->n, (int) gk))) ||
-        (a.dvo && (rc = stg.out(d->stage[STAGE_ATTB_DV], a.dvo, a.lddv, (size_t) d->n, (int) gv))) ||
+    if ((rc = stg.in(d->stage[STAGE_ATTB_Q], a.q, a.ldq, (size_t) d->m, (int) wk, si)) || (rc = stg.in(d->stage[STAGE_ATTB_K], a.kk, a.ldk, (size_t) d->n, (int) gk, si)) ||
+        (rc = stg.in(d->stage[STAGE_ATTB_V], a.v, a.ldv, (size_t) d->n, (int) gv, si)) || (rc = stg.in(d->stage[STAGE_ATTB_G], a.g, a.ldg, (size_t) d->m, (int) wv, si)) ||
+        (a.dq && (rc = stg.out(d->stage[STAGE_ATTB_DQ], a.dq, a.lddq, (size_t) d->m, (int) wk, sq))) ||
+        (a.dk && (rc = stg.out(d->stage[STAGE_ATTB_DK], a.dk, a.lddk, (size_t) d->n, (int) gk, so))) ||
+        (a.dvo && (rc = stg.out(d->stage[STAGE_ATTB_DV], a.dvo, a.lddv, (size_t) d->n, (int) gv, so))) ||
         (a.bias && (rc = attention_stage_bias(stg, d->stage[STAGE_ATT_B], a.bias, a.ldb, heads))) ||
         (a.db && (rc = stg.out(d->stage[STAGE_ATT_DB], a.db, a.lddb, (size_t) heads, (int) d->nnz))) || // every entry of every plane is written
         (a.o && ((rc = stg.in(d->stage[STAGE_ATTB_O], a.o, a.ldo, (size_t) d->m, (int) wv)) || (rc = stg.in(d->stage[STAGE_ATTB_L], a.lse, a.ldl, (size_t) heads, d->m))))) return rc;
     // the access width changes no bit (kernels/attention_backward.hpp): chosen per call from what the addresses allow -- with more than one head,
     // every head's first column has to be 16-byte aligned as well
-    a.vec = wide_ok(a.q, a.ldq, s) && wide_ok(a.kk, a.ldk, s) && wide_ok(a.v, a.ldv, s) && wide_ok(a.g, a.ldg, s) && (!a.dq || wide_ok(a.dq, a.lddq, s)) &&
-            (!a.dk || wide_ok(a.dk, a.lddk, s)) && (!a.dvo || wide_ok(a.dvo, a.lddv, s)) && (!a.o || wide_ok(a.o, a.ldo, s)) && (heads == 1 || (((size_t) k * s) % 16 == 0 && ((size_t) dv * s) % 16 == 0));
-    const hipError_t e = attention_backward_launch(a, s == sizeof(double), d->stream);
+    if (io_type == SPMV_HIP_T_HANDLE)
+        a.vec = wide_ok(a.q, a.ldq, s) && wide_ok(a.kk, a.ldk, s) && wide_ok(a.v, a.ldv, s) && wide_ok(a.g, a.ldg, s) && (!a.dq || wide_ok(a.dq, a.lddq, s)) &&
+                (!a.dk || wide_ok(a.dk, a.lddk, s)) && (!a.dvo || wide_ok(a.dvo, a.lddv, s)) && (!a.o || wide_ok(a.o, a.ldo, s)) &&
+                (heads == 1 || (((size_t) k * s) % 16 == 0 && ((size_t) dv * s) % 16 == 0));
+    else {
+        // a 16-bit dK / dV over groups of heads is never a partial sum: the column pass adds in the handle's float arrays, the narrowing rounds once
+        if (a.gs > 1 && dkv_type != SPMV_HIP_T_HANDLE && (a.dk || a.dvo)) {
+            if (a.dk) {
+                if ((rc = stg.reserve(d->attb_nk, sizeof(float) * (size_t) d->n * (size_t) gk))) return rc;
+                a.nar_dk = a.dk; a.nar_lddk = a.lddk;
+                a.dk = d->attb_nk.p; a.lddk = gk;
+            }
+            if (a.dvo) {
+                if ((rc = stg.reserve(d->attb_nv, sizeof(float) * (size_t) d->n * (size_t) gv))) return rc;
+                a.nar_dv = a.dvo; a.nar_lddv = a.lddv;
+                a.dvo = d->attb_nv.p; a.lddv = gv;
+            }
+            a.dkv_type = SPMV_HIP_T_HANDLE;
+        }
+        // a lane's segment is 4 elements of the operand's own type: 8 bytes of a 16-bit operand, 16 of a float one; with more than one head every
+        // head's first column has to allow it as well (k and dv multiples of 4 serve both sizes)
+        auto seg_ok = [](const void *p, long long ld, size_t es) { return wide_ok_bytes(p, ld, es, 4 * es); };
+        const size_t sk = a.dkv_type ? 2 : s;
+        a.vec = seg_ok(a.q, a.ldq, si) && seg_ok(a.kk, a.ldk, si) && seg_ok(a.v, a.ldv, si) && seg_ok(a.g, a.ldg, si) && (!a.dq || seg_ok(a.dq, a.lddq, sq)) &&
+                (!a.dk || seg_ok(a.dk, a.lddk, sk)) && (!a.dvo || seg_ok(a.dvo, a.lddv, sk)) && (!a.o || wide_ok(a.o, a.ldo, s)) && (heads == 1 || (k % 4 == 0 && dv % 4 == 0));
+    }
+    const hipError_t e = io_type == SPMV_HIP_T_HANDLE ? attention_backward_launch(a, s == sizeof(double), d->stream) : attention_backward_16_launch(a, d->stream);
     if (e != hipSuccess) return fail(SPMV_HIP_E_RUNTIME, "attention_backward: launch: %s", hipGetErrorString(e));
     return stg.finish();
 }
@@ -163,6 +201,41 @@ extern "C" int spmv_shim_attention_gqa_backward_lse(spmv_dev *d, int heads, int 
 {
     return attention_gqa_backward_impl(d, heads, kv_heads, max_heads, k, dv, scale, q, ldq, kk, ldk, v, ldv, bias, ldb, g, ldg, dq, lddq, dk, lddk, dvo, lddv, db, lddb, true, o, ldo, lse,
                                        ldl);
+}
+
+// the one place of the type rules on this side (spmv_api.c states them ahead of its gate from the public handle's data_size).  o and lse both NULL:
+// the self-normalising row pass; both given: the one driven by them; one of the two while m > 0: SPMV_HIP_E_ARG
+extern "C" int spmv_shim_attention_gqa_backward_16(spmv_dev *d, int heads, int kv_heads, int max_heads, int k, int dv, double scale, int io_type, const void *q, long long ldq,
+                                                    const void *kk, long long ldk, const void *v, long long ldv, const void *bias, long long ldb, const void *g, long long ldg,
+                                                    const void *o, long long ldo, const void *lse, long long ldl, int dq_type, void *dq, long long lddq, int dkv_type, void *dk,
+                                                    long long lddk, void *dvo, long long lddv, void *db, long long lddb)
+{
+    if ((io_type != SPMV_HIP_T_F16 && io_type != SPMV_HIP_T_BF16) || (dq_type != SPMV_HIP_T_HANDLE && dq_type != io_type) ||
+        (dkv_type != SPMV_HIP_T_HANDLE && dkv_type != io_type) || (d && d->vsize != sizeof(float)))
+        return fail(SPMV_HIP_E_ARG, "attention_backward: 16-bit operands need a float handle, io_type F16 or BF16 and dq_type, dkv_type HANDLE or io_type (io_type = %d, dq_type = %d, dkv_type = %d)",
+                    io_type, dq_type, dkv_type);
+    if (d && d->m > 0 && (o == nullptr) != (lse == nullptr)) return fail(SPMV_HIP_E_ARG, "attention_backward: O and L are given together or not at all");
+    const bool stats = o != nullptr && lse != nullptr;
+    return attention_gqa_backward_impl(d, heads, kv_heads, max_heads, k, dv, scale, q, ldq, kk, ldk, v, ldv, bias, ldb, g, ldg, dq, lddq, dk, lddk, dvo, lddv, db, lddb, stats,
+                                       stats ? o : nullptr, ldo, stats ? lse : nullptr, ldl, io_type, dq_type, dkv_type);
+}
+
+extern "C" double spmv_shim_time_attention_gqa_backward_16(spmv_dev *d, int heads, int kv_heads, int max_heads, int k, int dv, double scale, int io_type, const void *q, long long ldq,
+                                                            const void *kk, long long ldk, const void *v, long long ldv, const void *bias, long long ldb, const void *g,
+                                                            long long ldg, const void *o, long long ldo, const void *lse, long long ldl, int dq_type, void *dq, long long lddq,
+                                                            int dkv_type, void *dk, long long lddk, void *dvo, long long lddv, void *db, long long lddb, int warmup, int iters,
+                                                            float *ms_out)
+{
+    if (!d || !d->built || iters <= 0) { fail(SPMV_HIP_E_ARG, "time_attention_backward: bad arguments"); return -1.0; }
+    if (!is_device_ptr(q) || !is_device_ptr(kk) || !is_device_ptr(v) || !is_device_ptr(g) || (o && !is_device_ptr(o)) || (lse && !is_device_ptr(lse)) || (dq && !is_device_ptr(dq)) ||
+        (dk && !is_device_ptr(dk)) || (dvo && !is_device_ptr(dvo)) || (bias && !is_device_ptr(bias)) || (db && !is_device_ptr(db))) {
+        fail(SPMV_HIP_E_ARG, "time_attention_backward: Q, K, V, G, O, L, the bias and the outputs must be device pointers");
+        return -1.0;
+    }
+    return time_events(d, "time_attention_backward", warmup, iters, ms_out, [&] {
+        return spmv_shim_attention_gqa_backward_16(d, heads, kv_heads, max_heads, k, dv, scale, io_type, q, ldq, kk, ldk, v, ldv, bias, ldb, g, ldg, o, ldo, lse, ldl, dq_type, dq, lddq,
+                                                   dkv_type, dk, lddk, dvo, lddv, db, lddb);
+    });
 }
 
 extern "C" double spmv_shim_time_attention_gqa_backward_lse(spmv_dev *d, int heads, int kv_heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq,

@@ -283,6 +283,9 @@ struct spmv_dev {
     void *attb_p = nullptr, *attb_ds = nullptr;
     int attb_planes = 0;
     size_t attb_bytes = 0; // of each of the two, as counted in device_bytes
+    // spmv_hip_attention_gqa_backward_16 with kv_heads < heads and 16-bit dK / dV: the float sums over each group's heads (n x kv_heads * k,
+    // n x kv_heads * dv), rounded once into the caller's arrays; allocated at the first such call, grown when a later one needs more
+    StageBuf attb_nk, attb_nv;
     // spmv_hip_spmv_transpose (shim/transpose.hpp): A^T as a matrix of its own (n x m), planned and built like any; perm[p] = our index of its entry p.
     // val_gen counts spmv_shim_update_values calls; A^T's values are gathered again when tr_gen falls behind it.
     spmv_dev *tr = nullptr;
@@ -387,7 +390,7 @@ static bool is_device_ptr(const void *p)
 // out(): the buffer the kernel writes instead -- and p / ld are redirected there.  finish() copies the host result back and synchronizes, unless
 // the handle is asynchronous and every operand was on the device.  Every operand is asked once whether it is a device pointer.  An operation has
 // at most kMaxRes results (spmv_hip_attention_bias_backward: four).  Elements are of the handle's value type unless in() / out() is given an
-// element size `es` (the 16-bit operands of spmv_hip_attention_gqa_lse_16: 2); ld and k count elements of that size.
+// element size `es` (the 16-bit operands of spmv_hip_attention_gqa_lse_16 and _gqa_backward_16: 2); ld and k count elements of that size.
 struct Stager {
     static constexpr int kMaxRes = 4;
     struct Res { const StageBuf *buf; void *host; size_t ld, rows, k, es; }; // a staged result and where it goes

@@ -1483,3 +1483,52 @@ double spmv_hip_time_attention_gqa_backward_lse_launches(spmv_Handle_t h, int he
     return report_time(spmv_shim_time_attention_gqa_backward_lse(st->dev, heads, kv_heads, (int) st->opts.v[SPMV_OPT_ATTENTION_BACKWARD_HEADS], k, dv, scale, Q, ldq, K, ldk, V,
                                                                  ldv, B, ldb, G, ldg, O, ldo, L, ldl, dQ, lddq, dK, lddk, dV, lddv, dB, lddb, warmup, iters, ms_out), where);
 }
+
+/* ---------------------------------------------------------------- the backward on 16-bit Q, K, V and G */
+/* the type rules ahead of the gate, like attention_16_types; O and L: both or neither */
+static int attention_backward_16_rules(spmv_Handle_t h, const char *where, int io_type, int dq_type, int dkv_type, int heads, int dv, const void *O, long long ldo, const void *L,
+                                       long long ldl, int m)
+{
+    if (h->data_size != sizeof(float) && h->data_size != 0) return refuse(SPMV_HIP_E_ARG, where, "16-bit operands need an fp32 handle");
+    if (io_type != SPMV_HIP_T_F16 && io_type != SPMV_HIP_T_BF16) return refuse(SPMV_HIP_E_ARG, where, "io_type must be SPMV_HIP_T_F16 or SPMV_HIP_T_BF16");
+    if (dq_type != SPMV_HIP_T_HANDLE && dq_type != io_type) return refuse(SPMV_HIP_E_ARG, where, "dq_type must be SPMV_HIP_T_HANDLE or equal to io_type");
+    if (dkv_type != SPMV_HIP_T_HANDLE && dkv_type != io_type) return refuse(SPMV_HIP_E_ARG, where, "dkv_type must be SPMV_HIP_T_HANDLE or equal to io_type");
+    if (m > 0 && (O == NULL) != (L == NULL)) return refuse(SPMV_HIP_E_ARG, where, "O and L are given together or not at all");
+    if (O && L) return attention_lse_inputs(where, heads, dv, O, ldo, L, ldl, m);
+    return SPMV_HIP_OK;
+}
+
+int spmv_hip_attention_gqa_backward_16(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                                       const void *Matrix_Val, int heads, int kv_heads, int k, int dv, double scale, int io_type,
+                                       const void *Q, long long ldq, const void *K, long long ldk, const void *V, long long ldv,
+                                       const void *B, long long ldb, const void *G, long long ldg, const void *O, long long ldo, const void *L, long long ldl,
+                                       int dq_type, void *dQ, long long lddq, int dkv_type, void *dK, long long lddk, void *dV, long long lddv, void *dB, long long lddb)
+{
+    const char *where = "attention_gqa_backward_16";
+    spmv_hip_state *st;
+    int rc;
+    if ((rc = attention_gqa_backward_args(handle, where, heads, kv_heads, k, dv, Q, ldq, K, ldk, V, ldv, G, ldg, dQ, lddq, dK, lddk, dV, lddv, m)) ||
+        (rc = attention_backward_16_rules(handle, where, io_type, dq_type, dkv_type, heads, dv, O, ldo, L, ldl, m))) return rc;
+    if ((B && ldb < 0) || (dB && lddb < 0)) return refuse(SPMV_HIP_E_ARG, where, "need ldb >= 0 and lddb >= 0");
+    if (!dQ && !dK && !dV && !dB) return SPMV_HIP_OK; /* nothing wanted: no work, the handle's state is not looked at */
+    if ((rc = resident_prologue(handle, where, RESIDENT_NOT_REORDERED, m, RowPtr, ColIdx, Matrix_Val, &st))) return rc;
+    if ((rc = attention_backward_tables(handle, st, where, dK || dV))) return rc; /* only dB (or dQ) wanted: no transpose */
+    return report(spmv_shim_attention_gqa_backward_16(st->dev, heads, kv_heads, (int) st->opts.v[SPMV_OPT_ATTENTION_BACKWARD_HEADS], k, dv, scale, io_type, Q, ldq, K, ldk, V, ldv,
+                                                      B, ldb, G, ldg, O, ldo, L, ldl, dq_type, dQ, lddq, dkv_type, dK, lddk, dV, lddv, dB, lddb), where);
+}
+
+double spmv_hip_time_attention_gqa_backward_16_launches(spmv_Handle_t h, int heads, int kv_heads, int k, int dv, double scale, int io_type, const void *Q, long long ldq,
+                                                        const void *K, long long ldk, const void *V, long long ldv, const void *B, long long ldb, const void *G, long long ldg,
+                                                        const void *O, long long ldo, const void *L, long long ldl, int dq_type, void *dQ, long long lddq, int dkv_type, void *dK,
+                                                        long long lddk, void *dV, long long lddv, void *dB, long long lddb, int warmup, int iters, float *ms_out)
+{
+    const char *where = "time_attention_gqa_backward_16_launches";
+    spmv_hip_state *st;
+    if (attention_gqa_backward_args(h, where, heads, kv_heads, k, dv, Q, ldq, K, ldk, V, ldv, G, ldg, dQ, lddq, dK, lddk, dV, lddv, 1) ||
+        attention_backward_16_rules(h, where, io_type, dq_type, dkv_type, heads, dv, O, ldo, L, ldl, 1)) return -1.0;
+    if ((B && ldb < 0) || (dB && lddb < 0)) { (void) refuse(SPMV_HIP_E_ARG, where, "need ldb >= 0 and lddb >= 0"); return -1.0; }
+    if (resident_state(h, where, RESIDENT_NOT_REORDERED, &st) || attention_backward_tables(h, st, where, dK || dV)) return -1.0;
+    return report_time(spmv_shim_time_attention_gqa_backward_16(st->dev, heads, kv_heads, (int) st->opts.v[SPMV_OPT_ATTENTION_BACKWARD_HEADS], k, dv, scale, io_type, Q, ldq, K, ldk,
+                                                                V, ldv, B, ldb, G, ldg, O, ldo, L, ldl, dq_type, dQ, lddq, dkv_type, dK, lddk, dV, lddv, dB, lddb, warmup, iters,
+                                                                ms_out), where);
+}

@@ -238,6 +238,19 @@ double spmv_shim_time_attention_gqa_backward_lse(spmv_dev *d, int heads, int kv_
                                                  long long ldo, const void *lse, long long ldl, void *dq, long long lddq, void *dk, long long lddk, void *dv_out, long long lddv,
                                                  void *db, long long lddb, int warmup, int iters, float *ms_out);
 
+/* on 16-bit Q, K, V and G (spmv_hip_attention_gqa_backward_16; a float handle): io_type SPMV_HIP_T_F16 or _BF16 is their element type, dq_type that of
+ * dq and dkv_type that of dk and dv_out, each SPMV_HIP_T_HANDLE (float) or io_type; leading dimensions in elements of the operand's own type; bias,
+ * db, o and lse float.  o and lse both NULL: spmv_shim_attention_gqa_backward's row pass; both given: spmv_shim_attention_gqa_backward_lse's.  A bad
+ * type, a double handle, or one of o and lse alone while m > 0: SPMV_HIP_E_ARG, nothing written */
+int spmv_shim_attention_gqa_backward_16(spmv_dev *d, int heads, int kv_heads, int max_heads, int k, int dv, double scale, int io_type, const void *q, long long ldq, const void *kk,
+                                        long long ldk, const void *v, long long ldv, const void *bias, long long ldb, const void *g, long long ldg, const void *o, long long ldo,
+                                        const void *lse, long long ldl, int dq_type, void *dq, long long lddq, int dkv_type, void *dk, long long lddk, void *dv_out, long long lddv,
+                                        void *db, long long lddb);
+double spmv_shim_time_attention_gqa_backward_16(spmv_dev *d, int heads, int kv_heads, int max_heads, int k, int dv, double scale, int io_type, const void *q, long long ldq,
+                                                const void *kk, long long ldk, const void *v, long long ldv, const void *bias, long long ldb, const void *g, long long ldg,
+                                                const void *o, long long ldo, const void *lse, long long ldl, int dq_type, void *dq, long long lddq, int dkv_type, void *dk,
+                                                long long lddk, void *dv_out, long long lddv, void *db, long long lddb, int warmup, int iters, float *ms_out);
+
 /* the resident CSR arrays (device pointers; ColIdx may be NULL after spmv_shim_release_columns) */
 void spmv_shim_matrix_arrays(const spmv_dev *d, const int **rowptr, const int **colidx, const void **val);
 
