@@ -607,6 +607,14 @@ int spmv_hip_attention_gqa_backward_16(spmv_Handle_t handle, BASIC_INT_TYPE m, c
  *       "x_windows" (0/1, default 1: stage the tile groups' x windows in LDS)   "xcd_order" (0/1, default 1)   "csr5_two_deep" (0 auto / 1 never / 2 always)
  *       "run_tiles" (0/1, default 1: RUN / BYTE tiles -- spmv_hip_info.run_nnz, byte_nnz)
  *       "row_forward" (0/1, default 1: nnz-split tiles that gather through L2 finish the rows they start -- one launch, no carry fix-up; spmv_hip_info.launch_kernels)
+ *       "pack_values" (0/1/2, default 2: fp64 CSR-vector tiles whose values are all k * 2^e -- one e per 256-row tile, integers |k| < 2^55, finite, no -0.0 --
+ *                      and whose rows are whole aligned blocks of 4 x lanes_per_row entries read their values as 7 bytes instead of 8, from two planes
+ *                      the library keeps beside the value array (7 B per non-zero more in device_bytes), decoded exactly: y is bit-identical.  Integer,
+ *                      0/1, quantised or short-mantissa values qualify, e.g. uniform random doubles in [-1, 1); a tile that does not keeps its 8-byte
+ *                      stream, in the same launch; spmv_hip_update_values gates and packs again.  0: never.  1: every qualifying tile, untimed (tests,
+ *                      A/B).  2: only where create() times the tile forms (nnz >= 2^24, nothing forced) and at least half of the tiles qualify; the
+ *                      packed kernel is timed next to the plain winner and kept only below 0.95 x its time, else the planes are freed --
+ *                      spmv_hip_info.packed_nnz, pack_ms)
  *       "autotune" (0/1, default 1: for matrices above 2^24 nnz create() times the applicable CSR-vector
  *                   kernel forms once on the resident matrix and keeps the fastest, ~10 ms)
  *       "reorder" (0/1/2, default 0; 1: reverse Cuthill-McKee on the device (kernels/rcm.hpp), 2: the host BFS of round 1.  For matrices whose band was lost to
@@ -713,6 +721,12 @@ typedef struct spmv_hip_info {
     int lds_bytes;              /* dynamic LDS, in bytes, the dominant kernel's launch requests: (x_span_max + 1 zero slot) elements in whole KiB, plus SELL's
                                  * row sums of one window group, plus the CSR5 / nnz-split waves' row maps (matrices with empty rows); cache_blocked: one row
                                  * block's accumulators.  The kernels' static LDS is not included */
+    long long packed_nnz;       /* CSR-vector tile kernel, fp64: entries in PACKED tiles -- tiles whose values are all k * 2^e with one exponent e per tile and
+                                 * integers |k| < 2^55, finite, no -0.0, every row a whole number of aligned 4L-entry blocks: their values are streamed as
+                                 * 7 bytes (32 low bits + 24 high bits of k) from planes kept beside the value array and decoded exactly -- the same bits
+                                 * in y as from the 8-byte stream.  0 when the planes are not in use (option "pack_values") */
+    float pack_ms[2];           /* option pack_values = 2 where create() timed it: [0] the best plain tile form, [1] the best packed form (four or two steps
+                                 * in flight), ms; the packed form stays only below 0.95 x [0].  0, 0: not timed */
 } spmv_hip_info;
 int spmv_hip_get_info(spmv_Handle_t handle, spmv_hip_info *out);
 /* the transposed schedule's spmv_hip_info (m, n swapped; schedule, kernels, device_bytes of A^T alone, reproducible); SPMV_HIP_E_NOSTATE until built */

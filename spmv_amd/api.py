@@ -69,7 +69,8 @@ class spmv_hip_info(C.Structure):
                 ("x_groups", C.c_int), ("x_groups_staged", C.c_int), ("cache_blocked", C.c_int),
                 ("stream_bytes", C.c_longlong), ("x_bytes", C.c_longlong), ("route_ms", C.c_float * 2), ("split_ms", C.c_float * 2), ("far_nnz", C.c_longlong), ("run_nnz", C.c_longlong), ("byte_nnz", C.c_longlong), ("tmpl_nnz", C.c_longlong),
                 ("blk_waves", C.c_int), ("launch_kernels", C.c_char * 160), ("reproducible", C.c_int),
-                ("x_span_max", C.c_int), ("lds_bytes", C.c_int)]
+                ("x_span_max", C.c_int), ("lds_bytes", C.c_int),
+                ("packed_nnz", C.c_longlong), ("pack_ms", C.c_float * 2)]
 
 
 # Every symbol include/*.h declares: functions with their prototypes, then data symbols.
@@ -350,6 +351,7 @@ def _info_dict(info):
     out["tune_ms"] = [float(v) for v in out["tune_ms"]]
     out["route_ms"] = [float(v) for v in out["route_ms"]]
     out["split_ms"] = [float(v) for v in out["split_ms"]]
+    out["pack_ms"] = [float(v) for v in out["pack_ms"]]
     return out
 
 

@@ -32,8 +32,8 @@ HIP_TOOLS = {"gbench": os.path.join(ROOT, "tools", "gbench.hip")}          # mea
 BINDIR = os.path.join(PKG, "bin")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 # (source, extra defines, object name): compiled side by side.  The CSR-vector family's executors (seven lanes-per-row values x five
-# forms x two value types) are most of the device code: spmv_vector.hip is compiled four times, a quarter of the instantiations each
-HIP_SOURCES = [("spmv_shim.hip", [], "spmv_shim.hip.o")] + [("spmv_vector.hip", [f"SPMV_VEC_PART={k}"], f"spmv_vector{k}.hip.o") for k in range(4)] + \
+# forms x two value types) are most of the device code: spmv_vector.hip is compiled five times, a part of the instantiations each (the fifth: the fp64 tile kernel over packed values)
+HIP_SOURCES = [("spmv_shim.hip", [], "spmv_shim.hip.o")] + [("spmv_vector.hip", [f"SPMV_VEC_PART={k}"], f"spmv_vector{k}.hip.o") for k in range(5)] + \
               [("spmv_spmm.hip", [], "spmv_spmm.hip.o")] + \
               [("spmv_transpose.hip", [], "spmv_transpose.hip.o")] + \
               [("spmv_sddmm.hip", [], "spmv_sddmm.hip.o")] + \

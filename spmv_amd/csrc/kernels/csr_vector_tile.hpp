@@ -105,18 +105,63 @@ struct Lane4 {
     }
 };
 
+// PACKED tiles (fp64): the values of a tile that are all k * 2^e with ONE exponent e and integers |k| < 2^55 are streamed as 7 bytes instead of
+// 8 -- the low 32 bits of k in one plane (lo), the high 24 bits, signed, in another (hi) -- from a copy the library keeps beside val.  The copy is
+// permuted inside every aligned block of C = 4L entries so that the four entries Lane4 hands lane l (chunk-local q = (k / 2) * 2L + 2l + k % 2)
+// sit side by side at slots 4l + k: ONE 16 B load from lo and ONE 12 B load from hi per lane and step, each contiguous over the L lanes of a row
+// and over consecutive rows.  Valid where every row's chunks are aligned C-blocks inside the row (the gate, pack_tiles_kernel, checks it).
+constexpr int kPackNone = INT_MIN; // per-tile exponent: the tile keeps its 8-byte stream
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+struct __attribute__((aligned(4))) PackHi3 { unsigned w0, w1, w2; }; // four 24-bit fields; 12 B apart, so only 4 B-aligned
+struct PackArgs {
+    const unsigned *lo = nullptr;
+    const unsigned char *hi = nullptr;
+    int e = 0;
+};
+// slot of absolute position p (C = 4L a power of two)
+__host__ __device__ __forceinline__ long long pack_slot(long long p, int L)
+{
+    const int q = (int) (p & (4 * L - 1)), kh = q / (2 * L), rem = q % (2 * L);
+    return p - q + 4 * (rem / 2) + 2 * kh + (rem & 1);
+}
+// the raw words of one lane's four entries, kept in registers while the loads are in flight; decoded when the step is consumed
+struct PackRaw {
+    unsigned lo[4] = {0, 0, 0, 0}, hi[3] = {0, 0, 0};
+    __device__ __forceinline__ void load(const PackArgs &pk, int base, int l)
+    {
+        const u32x4 a = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(pk.lo + base + 4 * l));
+        const PackHi3 *h = reinterpret_cast<const PackHi3 *>(pk.hi + 3 * (size_t) (base + 4 * l));
+        lo[0] = a.x; lo[1] = a.y; lo[2] = a.z; lo[3] = a.w;
+        hi[0] = __builtin_nontemporal_load(&h->w0); hi[1] = __builtin_nontemporal_load(&h->w1); hi[2] = __builtin_nontemporal_load(&h->w2);
+    }
+    // v = ldexp(hi * 2^32 + lo, e).  Exact at every step for a value that passed the gate: hi * 2^32 + lo = k is the value scaled by a power of two,
+    // so it has at most 53 significant bits and the ONE rounding of the fused multiply-add returns it unchanged ((double) of a 32-bit integer is
+    // exact, and so is the product inside the fma); ldexp by e then restores the value itself, which is a double (subnormals included), so nothing is
+    // rounded there either.  k = 0 decodes to +0.0: a tile with a -0.0 is not packed.
+    __device__ __forceinline__ void decode(int e, double (&v)[4]) const
+    {
+        const int h0 = (int) (hi[0] << 8) >> 8, h1 = (int) (((hi[0] >> 24) | (hi[1] << 8)) << 8) >> 8,
+                  h2 = (int) (((hi[1] >> 16) | (hi[2] << 16)) << 8) >> 8, h3 = (int) hi[2] >> 8;
+        v[0] = ldexp(fma((double) h0, 0x1p32, (double) lo[0]), e);
+        v[1] = ldexp(fma((double) h1, 0x1p32, (double) lo[1]), e);
+        v[2] = ldexp(fma((double) h2, 0x1p32, (double) lo[2]), e);
+        v[3] = ldexp(fma((double) h3, 0x1p32, (double) lo[3]), e);
+    }
+    __device__ __forceinline__ void decode(int, float (&)[4]) const {} // fp32 is never packed
+};
+
 // One step of one lane group: lane l of the L lanes of row [p0, p1) multiplies its four entries
 // (c, v: already loaded by Lane4 from the chunk starting at the 16 B-aligned position p0 & ~3) and, for
 // rows longer than that chunk, walks on in chunks of 4L.  Returns the lane's partial sum (not yet reduced over the group).
 // MODE 0: unstaged (global columns), 1: staged (16-bit slots from the column stream), 2: staged RUN tile (slots = rs + position in the row;
 // cc0 unused), 3: staged BYTE tile (slots = rs + the entry's byte of the 8-bit column stream, packed in cc0), 4: staged TEMPLATE tile (slots = rs +
 // tm[position in the row], tm = the tile's offset list in LDS; cc0 unused)
-template <typename T, int L, int MODE, int SHIFT = 0>
+template <typename T, int L, int MODE, int SHIFT = 0, bool PACK = false>
 __device__ __forceinline__ T csr_vector_step(int p0, int p1, int l, const int (&cc0)[4], const T (&vv0)[4],
                                              const int *__restrict__ colidx, const unsigned short *__restrict__ col_local,
                                              const T *__restrict__ val, const T *__restrict__ x,
                                              const unsigned char *__restrict__ xb, unsigned zoff, unsigned rs = 0, const unsigned char *__restrict__ col8 = nullptr,
-                                             const unsigned short *__restrict__ tm = nullptr)
+                                             const unsigned short *__restrict__ tm = nullptr, PackArgs pk = PackArgs() /* PACK: the tile's planes and exponent */)
 {
     constexpr bool STAGED = MODE != 0;
     constexpr unsigned INC = SHIFT ? 1u : (unsigned) sizeof(T); // slot unit of the stream: indices (wide form) or bytes
@@ -177,7 +222,8 @@ __device__ __forceinline__ T csr_vector_step(int p0, int p1, int l, const int (&
                 if (MODE == 1) LM::load_col16(col_local, bb, l, cc);
                 else if (MODE == 0) LM::load_col32(colidx, bb, l, cc);
                 else if (MODE == 3) LM::load_col8(col8, bb, l, cc);
-                LM::load_val(val, bb, l, v2);
+                if constexpr (PACK) { PackRaw r2; r2.load(pk, bb, l); r2.decode(pk.e, v2); }
+                else LM::load_val(val, bb, l, v2);
                 if (MODE == 4) {
 #pragma unroll
                     for (int k = 0; k < 4; ++k)
@@ -212,7 +258,8 @@ __device__ __forceinline__ T csr_vector_step(int p0, int p1, int l, const int (&
 // zoff is the byte offset of a slot that holds 0 (masked entries read it: 0 * 0, never x's NaN/Inf).
 // A step whose lanes all hold four entries of their row, or none (regular matrices: every step),
 // takes the unmasked path.  The order of the fused multiply-adds is the same on both paths.
-template <typename T, int L, int MODE, int DEPTH, bool PRE = true, int SHIFT = 0>
+// PACK: the tile's values come from the packed planes (pk; r0 = step 0's raw words when PRE); everything after the decode is the same code.
+template <typename T, int L, int MODE, int DEPTH, bool PRE = true, int SHIFT = 0, bool PACK = false>
 __device__ __forceinline__ void csr_vector_tile_wave(long long row_end, int long_thr, long long rw0, int lane,
                                                      const int *__restrict__ rp_lds, const unsigned *__restrict__ rs_lds /* MODE >= 2: slot of each row's first column (MODE 4: | list number * kTmplMax << 16) */,
                                                      T *__restrict__ y_lds,
@@ -220,7 +267,7 @@ __device__ __forceinline__ void csr_vector_tile_wave(long long row_end, int long
                                                      const T *__restrict__ val,
                                                      const T *__restrict__ x, const T *__restrict__ xs, unsigned zoff,
                                                      T *__restrict__ y, const int (&c0)[4], const T (&v0)[4], const unsigned char *__restrict__ col8 = nullptr,
-                                                     const unsigned short *__restrict__ tm = nullptr)
+                                                     const unsigned short *__restrict__ tm = nullptr, PackArgs pk = PackArgs(), PackRaw r0 = PackRaw())
 {
     constexpr int RW = kWave / L; // rows per step
     constexpr int D = DEPTH < L ? DEPTH : L; // steps of matrix stream in flight per wave
@@ -228,6 +275,8 @@ __device__ __forceinline__ void csr_vector_tile_wave(long long row_end, int long
     const unsigned char *xb = reinterpret_cast<const unsigned char *>(xs);
     int c[D][4];
     T v[D][4];
+    PackRaw pr[PACK ? D : 1]; // PACK: the raw words instead of v
+    pr[0] = r0;
     int pp0[D], pp1[D];
     unsigned rs[D];
 #pragma unroll
@@ -245,7 +294,8 @@ __device__ __forceinline__ void csr_vector_tile_wave(long long row_end, int long
             if (MODE == 1) Lane4<T, L>::load_col16(col_local, an, l, c[slot]);
             else if (MODE == 0) Lane4<T, L>::load_col32(colidx, an, l, c[slot]);
             else if (MODE == 3) Lane4<T, L>::load_col8(col8, an, l, c[slot]);
-            Lane4<T, L>::load_val(val, an, l, v[slot]);
+            if constexpr (PACK) pr[slot].load(pk, an, l);
+            else Lane4<T, L>::load_val(val, an, l, v[slot]);
         }
     };
 #pragma unroll
@@ -254,7 +304,8 @@ __device__ __forceinline__ void csr_vector_tile_wave(long long row_end, int long
     for (int s = 0; s < L; ++s) {
         const int cur = s % D;
         const int p0 = pp0[cur], p1 = pp1[cur];
-        T sum = csr_vector_step<T, L, MODE, SHIFT>(p0, p1, l, c[cur], v[cur], colidx, col_local, val, x, xb, zoff, rs[cur], col8, tm);
+        if constexpr (PACK) pr[cur].decode(pk.e, v[cur]);
+        T sum = csr_vector_step<T, L, MODE, SHIFT, PACK>(p0, p1, l, c[cur], v[cur], colidx, col_local, val, x, xb, zoff, rs[cur], col8, tm, pk);
         sum = group_sum_dpp<L>(sum);
         if (l == 0) y_lds[s * RW + sub] = sum;
         if (s + D < L) issue(s + D); // refill the slot just consumed
@@ -265,7 +316,8 @@ __device__ __forceinline__ void csr_vector_tile_wave(long long row_end, int long
     if (row < row_end && len <= long_thr) y[row] = y_lds[lane]; // one coalesced 64-row store per wave
 }
 
-template <typename T, int L, int DEPTH = 4, bool PRE = true>
+// PACK (fp64): tiles whose entry of tile_e is not kPackNone read their values from the packed planes pk_lo / pk_hi; the others run the 8-byte path.
+template <typename T, int L, int DEPTH = 4, bool PRE = true, bool PACK = false>
 __global__ __launch_bounds__(kVecTileThreads) void csr_vector_tile_kernel(int m, int long_thr, const int *__restrict__ rowptr,
                                                                           const int *__restrict__ colidx,
                                                                           const unsigned short *__restrict__ col_local,
@@ -274,7 +326,9 @@ __global__ __launch_bounds__(kVecTileThreads) void csr_vector_tile_kernel(int m,
                                                                           const unsigned short *__restrict__ row_slot,
                                                                           const unsigned char *__restrict__ col8,
                                                                           const unsigned short *__restrict__ tmpl, const unsigned char *__restrict__ row_tid,
-                                                                          const T *__restrict__ x, T *__restrict__ y)
+                                                                          const T *__restrict__ x, T *__restrict__ y,
+                                                                          const unsigned *__restrict__ pk_lo = nullptr, const unsigned char *__restrict__ pk_hi = nullptr,
+                                                                          const int *__restrict__ tile_e = nullptr)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char vec_x_lds[]; // the tile's staged x
     __shared__ unsigned short tm_lds[kTmplCount * kTmplMax];
@@ -296,6 +350,13 @@ __global__ __launch_bounds__(kVecTileThreads) void csr_vector_tile_kernel(int m,
     // shuffles), BEFORE the x staging and the barrier, so neither sits in front of the first loads
     int c0[4] = {0, 0, 0, 0};
     T v0[4] = {T(0), T(0), T(0), T(0)};
+    PackArgs pk;
+    PackRaw r0;
+    bool packed = false;
+    if constexpr (PACK) {
+        pk.lo = pk_lo; pk.hi = pk_hi; pk.e = tile_e[blockIdx.x]; // workgroup-uniform
+        packed = pk.e != kPackNone;
+    }
     if (PRE) {
         const int sub = lane / L, l = lane % L;
         const int q0 = __shfl(rp, sub, kWave);
@@ -304,7 +365,8 @@ __global__ __launch_bounds__(kVecTileThreads) void csr_vector_tile_kernel(int m,
         else if (bytes) Lane4<T, L>::load_col8(col8, a, l, c0);
         else if (staged) Lane4<T, L>::load_col16(col_local, a, l, c0);
         else Lane4<T, L>::load_col32(colidx, a, l, c0);
-        Lane4<T, L>::load_val(val, a, l, v0);
+        if (PACK && packed) r0.load(pk, a, l);
+        else Lane4<T, L>::load_val(val, a, l, v0);
     }
     rp_lds[wave][lane] = rp;
     if (lane == 0) rp_lds[wave][kWave] = rpe;
@@ -318,11 +380,18 @@ __global__ __launch_bounds__(kVecTileThreads) void csr_vector_tile_kernel(int m,
     __syncthreads();
     if (rw0 >= m) return;
     const unsigned zoff = (unsigned) tw.total * (unsigned) sizeof(T);
-    if (runs) csr_vector_tile_wave<T, L, 2, DEPTH, PRE>((long long) m, long_thr, rw0, lane, rp_lds[wave], rs_lds[wave], y_lds[wave], colidx, col_local, val, x, xs, zoff, y, c0, v0);
-    else if (bytes) csr_vector_tile_wave<T, L, 3, DEPTH, PRE>((long long) m, long_thr, rw0, lane, rp_lds[wave], rs_lds[wave], y_lds[wave], colidx, col_local, val, x, xs, zoff, y, c0, v0, col8);
-    else if (templ) csr_vector_tile_wave<T, L, 4, DEPTH, PRE>((long long) m, long_thr, rw0, lane, rp_lds[wave], rs_lds[wave], y_lds[wave], colidx, col_local, val, x, xs, zoff, y, c0, v0, col8, tm_lds);
-    else if (staged) csr_vector_tile_wave<T, L, 1, DEPTH, PRE>((long long) m, long_thr, rw0, lane, rp_lds[wave], rs_lds[wave], y_lds[wave], colidx, col_local, val, x, xs, zoff, y, c0, v0);
-    else csr_vector_tile_wave<T, L, 0, DEPTH, PRE>((long long) m, long_thr, rw0, lane, rp_lds[wave], rs_lds[wave], y_lds[wave], colidx, col_local, val, x, xs, zoff, y, c0, v0);
+    // one wave program per tile form, from the 8-byte stream or (PACK, packed tiles) from the packed planes
+#define SPMV_TILE_WAVE(MODE, ...)                                                                                                                                   \
+    do {                                                                                                                                                            \
+        if (PACK && packed) csr_vector_tile_wave<T, L, MODE, DEPTH, PRE, 0, PACK>((long long) m, long_thr, rw0, lane, rp_lds[wave], rs_lds[wave], y_lds[wave], colidx, col_local, val, x, xs, zoff, y, c0, v0, __VA_ARGS__, pk, r0); \
+        else csr_vector_tile_wave<T, L, MODE, DEPTH, PRE>((long long) m, long_thr, rw0, lane, rp_lds[wave], rs_lds[wave], y_lds[wave], colidx, col_local, val, x, xs, zoff, y, c0, v0, __VA_ARGS__); \
+    } while (0)
+    if (runs) SPMV_TILE_WAVE(2, col8, nullptr);
+    else if (bytes) SPMV_TILE_WAVE(3, col8, nullptr);
+    else if (templ) SPMV_TILE_WAVE(4, col8, tm_lds);
+    else if (staged) SPMV_TILE_WAVE(1, col8, nullptr);
+    else SPMV_TILE_WAVE(0, col8, nullptr);
+#undef SPMV_TILE_WAVE
 }
 
 // Balanced form (Method_Balanced): the same wave program over EQUAL-NNZ row blocks.  Block b owns
@@ -395,12 +464,17 @@ struct VecArgs {
     const unsigned short *col = nullptr, *rowslot = nullptr, *tmpl = nullptr;
     const unsigned char *col8 = nullptr, *rowtid = nullptr;
     const TileWindows *wins = nullptr;
+    // tile kernel, fp64: the packed value planes and the per-tile exponents (NULL: every tile reads val)
+    const unsigned *pk_lo = nullptr;
+    const unsigned char *pk_hi = nullptr;
+    const int *pk_e = nullptr;
     int device = 0;
     hipStream_t stream = nullptr;
 };
 // spmv_vector.hip: the tile and pipe kernels, the rows kernel
 hipError_t vector_launch(const VecArgs &a, const double *x, double *y);
 hipError_t vector_launch(const VecArgs &a, const float *x, float *y);
+hipError_t vector_launch_packed(const VecArgs &a, const double *x, double *y); // the tile kernel with VecArgs::pk_e set, two or four steps in flight
 hipError_t rows_launch(const VecArgs &a, const double *x, double *y);
 hipError_t rows_launch(const VecArgs &a, const float *x, float *y);
 

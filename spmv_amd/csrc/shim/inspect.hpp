@@ -41,6 +41,7 @@ static int build_csr5(spmv_dev *d, Csr5Plan &P, int m, long long nnz, const int 
                       double mean_row_len, const int *out_rows, bool natural = false, int sigma_override = 0);
 template <typename T> static int autotune_vector(spmv_dev *d);
 template <typename T> static int autotune_rows(spmv_dev *d);
+static int build_packed_values(spmv_dev *d);
 template <typename T> static int autotune_blocked(spmv_dev *d);
 template <typename T> static double time_schedule(spmv_dev *d, int iters);
 template <typename T> static int split_make(spmv_dev *d, spmv_dev **near_out, spmv_dev **far_out, bool values_only);
@@ -232,6 +233,98 @@ static int build_vector_tiles(spmv_dev *d)
     if (rc) return rc;
     if (d->vt_staged * 2 >= d->vt_tiles) return SPMV_HIP_OK;
     return build_tile_windows<T>(d, (int) (((long long) d->m + rows - 1) / rows), nullptr, rows); // no: back to the narrow tiles (unstaged -> pipe form)
+}
+
+// ------------------------------------------------------------------------------------ packed values (kernels/csr_vector_tile.hpp "PACKED tiles")
+// Gate and pack, one workgroup per 256-row tile.  A tile is packed iff no row of it is longer than long_thr, every row starts at a multiple of
+// C = 4L and is a whole number of C-blocks long (empty rows are fine), every value is finite and not -0.0, and ONE exponent e writes every value
+// as k * 2^e with an integer |k| < 2^55: e = the smallest position of a lowest set mantissa bit over the non-zero values (subnormals with their true
+// exponent), and the largest position of a leading bit is at most e + 54.  An all-zero tile packs with e = 0.  tile_e[tile] = e or kPackNone;
+// cnt[0] += 1, cnt[1] += entries for a packed tile.  lo == NULL: the gate alone.
+static __global__ __launch_bounds__(kVecTileThreads) void pack_tiles_kernel(int m, int L, int long_thr, const int *__restrict__ rowptr, const double *__restrict__ val,
+                                                                            unsigned *__restrict__ lo, unsigned char *__restrict__ hi, int *__restrict__ tile_e,
+                                                                            unsigned long long *__restrict__ cnt)
+{
+    __shared__ int s_bad, s_top, s_low;
+    const int C = 4 * L;
+    const long long r0 = (long long) blockIdx.x * kVecTileRows, r1 = r0 + kVecTileRows < m ? r0 + kVecTileRows : m;
+    if (threadIdx.x == 0) { s_bad = 0; s_top = INT_MIN; s_low = INT_MAX; }
+    __syncthreads();
+    const int p_begin = rowptr[r0], p_end = rowptr[r1];
+    int bad = 0, top = INT_MIN, low = INT_MAX;
+    if (r0 + threadIdx.x < r1) {
+        const int a = rowptr[r0 + threadIdx.x], len = rowptr[r0 + threadIdx.x + 1] - a;
+        bad = (a & (C - 1)) != 0 || (len & (C - 1)) != 0 || len > long_thr;
+    }
+    for (int p = p_begin + (int) threadIdx.x; p < p_end; p += kVecTileThreads) {
+        const unsigned long long b = (unsigned long long) __double_as_longlong(val[p]);
+        const int E = (int) ((b >> 52) & 0x7ff);
+        const unsigned long long frac = b & 0xfffffffffffffull;
+        if (E == 0x7ff || b == 0x8000000000000000ull) bad = 1; // Inf, NaN, -0.0
+        else if (E | (frac != 0)) {
+            const unsigned long long mant = E ? frac | (1ull << 52) : frac;
+            const int base = (E ? E : 1) - 1075; // exponent of mant's bit 0
+            top = max(top, base + 63 - __clzll((long long) mant));
+            low = min(low, base + __ffsll((long long) mant) - 1);
+        }
+    }
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) {
+        bad |= __shfl_xor(bad, o, kWave);
+        top = max(top, __shfl_xor(top, o, kWave));
+        low = min(low, __shfl_xor(low, o, kWave));
+    }
+    if ((threadIdx.x & (kWave - 1)) == 0) {
+        if (bad) atomicOr(&s_bad, 1);
+        atomicMax(&s_top, top);
+        atomicMin(&s_low, low);
+    }
+    __syncthreads();
+    const bool zero = s_top == INT_MIN; // no non-zero value
+    const bool ok = !s_bad && (zero || s_top - s_low <= 54);
+    const int e = zero ? 0 : s_low;
+    if (threadIdx.x == 0) {
+        tile_e[blockIdx.x] = ok ? e : kPackNone;
+        if (ok) { atomicAdd(cnt, 1ull); atomicAdd(cnt + 1, (unsigned long long) (p_end - p_begin)); }
+    }
+    if (!ok || !lo) return;
+    // a thread per lane quad: slots s .. s + 3 = the four entries Lane4 hands lane l = (s % C) / 4 of the block
+    for (int s = p_begin + 4 * (int) threadIdx.x; s < p_end; s += 4 * kVecTileThreads) {
+        const int q = s & (C - 1), blk = s - q, l = q >> 2;
+        unsigned w[4], h[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const unsigned long long b = (unsigned long long) __double_as_longlong(val[blk + (k >> 1) * 2 * L + 2 * l + (k & 1)]);
+            const int E = (int) ((b >> 52) & 0x7ff);
+            const unsigned long long frac = b & 0xfffffffffffffull;
+            const unsigned long long mant = E ? frac | (1ull << 52) : frac;
+            const int sh = (E ? E : 1) - 1075 - e; // mant * 2^sh = k: the gate left at least -sh trailing zeros and at most 55 bits
+            long long kk = sh >= 0 ? (long long) (mant << sh) : (long long) (mant >> -sh);
+            if (b >> 63) kk = -kk;
+            w[k] = (unsigned) kk;
+            h[k] = (unsigned) (kk >> 32) & 0xffffffu;
+        }
+        *reinterpret_cast<uint4 *>(lo + s) = make_uint4(w[0], w[1], w[2], w[3]);
+        unsigned *hp = reinterpret_cast<unsigned *>(hi + 3 * (size_t) s); // 3 s is a multiple of 12
+        hp[0] = h[0] | h[1] << 24;
+        hp[1] = h[1] >> 8 | h[2] << 16;
+        hp[2] = h[2] >> 16 | h[3] << 8;
+    }
+}
+
+// run the gate (pack = false) or the gate and the pack over the resident values; d->pk_tiles / pk_nnz receive the counts.  Synchronizes the stream.
+static int pack_tiles_run(spmv_dev *d, bool pack)
+{
+    unsigned long long h[2] = {0, 0};
+    HIP_TRY(hipMemsetAsync(d->pk_cnt, 0, sizeof h, d->stream));
+    pack_tiles_kernel<<<d->vt_tiles, kVecTileThreads, 0, d->stream>>>(d->m, d->plan.lanes_per_row, d->long_thr, d->rowptr, (const double *) d->val, pack ? d->pk_lo : nullptr,
+                                                                      pack ? d->pk_hi : nullptr, d->pk_e, d->pk_cnt);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h, d->pk_cnt, sizeof h, hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(hipStreamSynchronize(d->stream));
+    d->pk_tiles = (long long) h[0];
+    d->pk_nnz = (long long) h[1];
+    return SPMV_HIP_OK;
 }
 
 template <typename T> static int launch_csr5(spmv_dev *d, const Csr5Plan &P, const T *x, T *y);
@@ -890,6 +983,7 @@ static int account_stream_bytes(spmv_dev *d)
             if (tile_form) t.bytes += 2ll * d->vt_run_rows - 2ll * d->vt_run_nnz; // RUN tiles: a 16-bit slot per row instead of one per entry
             if (tile_form) t.bytes += 3ll * d->vt_tmpl_rows + 2ll * kTmplCount * kTmplMax * d->vt_tmpl_tiles - 2ll * d->vt_tmpl_nnz; // TEMPLATE tiles: a 16-bit slot and a list number per row, the lists once per tile
             if (tile_form) t.bytes += 2ll * d->vt_byte_rows - 1ll * d->vt_byte_nnz; // BYTE tiles: a byte per entry and a 16-bit slot per row instead of 16 bits per entry
+            if (tile_form && d->pk_use) t.bytes += 4ll * d->vt_tiles - d->pk_nnz; // PACKED tiles: 7 B instead of 8 per entry, an exponent per tile
             if (d->plan.sched == SPMV_SCHED_ROWBLOCK) t.bytes += 4ll * (d->nblocks + 1);
             if (!tile_form || wtiles < d->vt_tiles) t.gathers_global = true;
             rc = csr5_traffic(d, d->c5_long, t);

@@ -39,6 +39,10 @@ static VecArgs vector_args(const spmv_dev *d)
     a.rowptr = d->rowptr; a.colidx = d->colidx; a.val = d->val; a.wins = d->vt_wins;
     a.col = d->vt_col; a.rowslot = d->vt_rowslot; a.tmpl = d->vt_tmpl; a.col8 = d->vt_col8; a.rowtid = d->vt_rowtid;
     a.device = d->device; a.stream = d->stream;
+    if (d->pk_use && a.kernel == kVecTileKernel && a.depth != 8) { // packed planes: the same kernel, PACK flag (two or four steps in flight)
+        a.pk_lo = d->pk_lo; a.pk_hi = d->pk_hi; a.pk_e = d->pk_e;
+        if (d->pk_depth) a.depth = d->pk_depth;
+    }
     return a;
 }
 
@@ -103,6 +107,90 @@ static int autotune_vector(spmv_dev *d)
     (void) pool_free(x);
     (void) pool_free(y);
     if (hipGetLastError() != hipSuccess) d->vec_choice = VEC_AUTO;
+    return SPMV_HIP_OK;
+}
+
+// PACKED tiles (option pack_values; kernels/csr_vector_tile.hpp): fp64 values of the narrow tile form streamed as 7 bytes from planes the library
+// keeps beside val.  1: every qualifying tile is packed and the planes are used, no timing (tests, A/B).  2 (default): only where autotune_vector
+// has just timed the plain forms and at least half of the tiles qualify (otherwise nothing is allocated); the packed kernel is timed at the
+// winner's PRE setting with 4 and 2 steps in flight, interleaved with the plain winner, min of three, and stays only below 0.95 x the plain best --
+// the guard the pipe form has in autotune_vector, for the same reason: a noisy sample must not decide.  A loser's planes are freed.
+static void free_packed_values(spmv_dev *d)
+{
+    quiesce(d);
+    for (void *p : {(void *) d->pk_lo, (void *) d->pk_hi, (void *) d->pk_e, (void *) d->pk_cnt}) if (p) sched_free(d, p);
+    d->pk_lo = nullptr; d->pk_hi = nullptr; d->pk_e = nullptr; d->pk_cnt = nullptr;
+    d->pk_tiles = d->pk_nnz = 0; d->pk_use = false; d->pk_depth = 0;
+}
+
+static int build_packed_values(spmv_dev *d)
+{
+    const int mode = d->plan.pack_values;
+    d->pack_ms[0] = d->pack_ms[1] = 0;
+    if (mode == 0 || d->vsize != sizeof(double) || d->plan.sched != SPMV_SCHED_CSR_VECTOR || d->vt_wide || d->vt_tiles <= 0 || d->nnz == 0) return SPMV_HIP_OK;
+    const VecArgs plain = vector_args(d);
+    if (plain.kernel != kVecTileKernel || plain.depth == 8) return SPMV_HIP_OK; // pipe form, or a forced form the packed kernel does not have
+    const bool timed = d->vec_choice != VEC_AUTO; // autotune_vector ran (nnz >= 2^24, nothing forced)
+    if (mode == 2 && !timed) return SPMV_HIP_OK;
+    int rc = SPMV_HIP_OK;
+    ALLOC_TRY(d, &d->pk_e, sizeof(int) * (size_t) d->vt_tiles, true);
+    ALLOC_TRY(d, &d->pk_cnt, 2 * sizeof(unsigned long long), true);
+    if (mode == 2) { // the gate alone first: nothing large is allocated for a matrix that does not qualify
+        rc = pack_tiles_run(d, false);
+        if (rc || d->pk_tiles * 2 < d->vt_tiles) { free_packed_values(d); return rc; }
+    }
+    // planes padded like val: a lane's tail read behind the last row stays inside
+    if ((rc = dev_alloc(d, (void **) &d->pk_lo, sizeof(unsigned) * ((size_t) d->nnz + kStreamPad), true)) ||
+        (rc = dev_alloc(d, (void **) &d->pk_hi, 3 * ((size_t) d->nnz + kStreamPad) + 4, true))) {
+        (void) hipGetLastError();
+        free_packed_values(d);
+        return mode == 2 ? SPMV_HIP_OK : rc; // no room: the 8-byte stream stays
+    }
+    HIP_TRY(hipMemsetAsync(d->pk_lo + d->nnz, 0, sizeof(unsigned) * kStreamPad, d->stream));
+    HIP_TRY(hipMemsetAsync(d->pk_hi + 3 * (size_t) d->nnz, 0, 3 * (size_t) kStreamPad + 4, d->stream));
+    rc = pack_tiles_run(d, true);
+    if (rc || d->pk_tiles == 0) { free_packed_values(d); return rc; }
+    if (mode == 1) { d->pk_use = true; return SPMV_HIP_OK; }
+    double *x = nullptr, *y = nullptr;
+    if (pool_malloc((void **) &x, sizeof(double) * (size_t) d->n) != hipSuccess || pool_malloc((void **) &y, sizeof(double) * (size_t) d->m) != hipSuccess) {
+        (void) hipGetLastError();
+        if (x) (void) pool_free(x);
+        free_packed_values(d);
+        return SPMV_HIP_OK; // no room to time: the 8-byte stream stays
+    }
+    fill_value_kernel<double><<<grid_for(d->n, kBlock, d->cus * 8), kBlock, 0, d->stream>>>(d->n, x, 1.0);
+    hipEvent_t e0, e1;
+    (void) hipEventCreate(&e0);
+    (void) hipEventCreate(&e1);
+    constexpr int kCand = 3; // plain winner, packed four deep, packed two deep
+    const int depth[kCand] = {0, 4, 2};
+    float tmin[kCand] = {1e30f, 1e30f, 1e30f};
+    auto set = [&](int k) { d->pk_use = k > 0; d->pk_depth = depth[k]; };
+    for (int k = 0; k < kCand; ++k) { set(k); (void) launch_vector<double>(d, x, y); } // warm every form once
+    for (int round = 0; round < 3; ++round)
+        for (int k = 0; k < kCand; ++k) {
+            set(k);
+            (void) hipEventRecord(e0, d->stream);
+            (void) launch_vector<double>(d, x, y);
+            (void) hipEventRecord(e1, d->stream);
+            (void) hipEventSynchronize(e1);
+            float ms = 0;
+            (void) hipEventElapsedTime(&ms, e0, e1);
+            if (ms < tmin[k]) tmin[k] = ms;
+        }
+    (void) hipEventDestroy(e0);
+    (void) hipEventDestroy(e1);
+    (void) pool_free(x);
+    (void) pool_free(y);
+    // the plain best: this run's sample or autotune_vector's own, whichever is lower
+    float plain_best = tmin[0];
+    for (int k = 0; k < 2; ++k) if (d->tune_ms[k] > 0 && d->tune_ms[k] < plain_best) plain_best = d->tune_ms[k];
+    const int best = tmin[2] < tmin[1] ? 2 : 1;
+    d->pack_ms[0] = plain_best;
+    d->pack_ms[1] = tmin[best];
+    if (hipGetLastError() != hipSuccess || !(tmin[best] < 0.95f * plain_best)) { free_packed_values(d); return SPMV_HIP_OK; }
+    d->pk_use = true;
+    d->pk_depth = depth[best];
     return SPMV_HIP_OK;
 }
 

@@ -228,6 +228,15 @@ struct spmv_dev {
     unsigned char *vt_rowtid = nullptr;   // ... and the list number of every row
     int vt_tmpl_tiles = 0, vt_tmpl_nnz = 0, vt_tmpl_rows = 0;
     TileWindows *vt_wins = nullptr; // x windows of every tile
+    // PACKED tiles of the narrow tile form, fp64 (kernels/csr_vector_tile.hpp; option pack_values): the values as k * 2^e, 7 bytes per entry, beside val
+    unsigned *pk_lo = nullptr;       // low 32 bits of k, by slot (nnz + kStreamPad)
+    unsigned char *pk_hi = nullptr;  // high 24 bits of k, signed, 3 bytes per slot
+    int *pk_e = nullptr;             // per tile: e, or kPackNone
+    unsigned long long *pk_cnt = nullptr; // packed tiles, packed entries (written by the gate)
+    long long pk_tiles = 0, pk_nnz = 0;
+    bool pk_use = false;             // the multiply reads the planes
+    int pk_depth = 0;                // steps in flight of the packed kernel (0: the plain form's)
+    float pack_ms[2] = {0, 0};       // measured at create: plain best, packed best (0, 0: not timed)
     // long rows (csr-vector, sell)
     int nlong = 0, long_thr = INT_MAX;
     int *long_rows = nullptr;
@@ -335,6 +344,7 @@ static void reset_tile_fields(spmv_dev *d)
     d->vt_rowslot = nullptr; d->vt_run_tiles = d->vt_run_nnz = d->vt_run_rows = 0; d->rows_depth = 0;
     d->vt_col8 = nullptr; d->vt_byte_tiles = d->vt_byte_nnz = d->vt_byte_rows = 0;
     d->vt_tmpl = nullptr; d->vt_rowtid = nullptr; d->vt_tmpl_tiles = d->vt_tmpl_nnz = d->vt_tmpl_rows = 0;
+    d->pk_lo = nullptr; d->pk_hi = nullptr; d->pk_e = nullptr; d->pk_cnt = nullptr; d->pk_tiles = d->pk_nnz = 0; d->pk_use = false; d->pk_depth = 0; d->pack_ms[0] = d->pack_ms[1] = 0;
     d->c5 = Csr5Plan();
     d->c5_long = Csr5Plan();
     d->ns = Csr5Plan();

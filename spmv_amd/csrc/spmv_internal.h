@@ -12,7 +12,7 @@ enum {
     SPMV_OPT_VECTOR_FORM, SPMV_OPT_X_WINDOWS, SPMV_OPT_XCD_ORDER, SPMV_OPT_CSR5_TWO_DEEP, SPMV_OPT_RUN_TILES, SPMV_OPT_ROW_FORWARD, SPMV_OPT_AUTO_METHOD, SPMV_OPT_AUTOTUNE, SPMV_OPT_REORDER, SPMV_OPT_HOST_ROWS,
     SPMV_OPT_CHECK_VALUES, SPMV_OPT_GPUS, SPMV_OPT_X_EXCHANGE, SPMV_OPT_SPLIT,
     SPMV_OPT_KEEP_COLUMNS, SPMV_OPT_BLK_WAVES, SPMV_OPT_BLK_GROUPS, SPMV_OPT_BLK_SUBSORT, SPMV_OPT_DETERMINISTIC,
-    SPMV_OPT_ATTENTION_BACKWARD_HEADS,
+    SPMV_OPT_ATTENTION_BACKWARD_HEADS, SPMV_OPT_PACK_VALUES,
     SPMV_N_OPTS
 };
 typedef struct spmv_options { long v[SPMV_N_OPTS]; } spmv_options;

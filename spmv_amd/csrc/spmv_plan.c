@@ -82,6 +82,10 @@ static opt_t g_opts[SPMV_N_OPTS] = {
                                                                        * waves add into the shared accumulators in arrival order (faster, correct to rounding, not reproducible) */
     [SPMV_OPT_ATTENTION_BACKWARD_HEADS] = {"attention_backward_heads", 0, 0, 1024, 0, 0}, /* spmv_hip_attention_heads_backward: heads per round = planes of attb_p / attb_ds; 0 = as many as keep
                                                                        * 2 * HG * s * nnz bytes within an eighth of the device's memory (shim/attention_backward.hpp).  Changes no bit */
+    [SPMV_OPT_PACK_VALUES] = {"pack_values", 2, 0, 2, 0, 0},         /* CSR-vector tile kernel, fp64: values of tiles that are all k * 2^e (one e per tile, |k| < 2^55, rows in aligned 4L-blocks) streamed as
+                                                                       * 7 bytes from planes kept beside the value array, bit-identical results: 0 = never, 1 = every qualifying tile, no timing
+                                                                       * (tests, A/B), 2 = where create() times the tile forms and at least half of the tiles qualify, kept only below 0.95 x the
+                                                                       * plain form's time (spmv_hip_info.packed_nnz, pack_ms) */
     [SPMV_OPT_X_EXCHANGE] = {"x_exchange", 0, 0, 2, 0, 0},            /* multi-GPU: 0 = allgather of the x slices, 1 = range (each device gets x[min col .. max col] of its block), 2 = broadcast from device 0 */
 };
 
@@ -309,6 +313,7 @@ void spmv_plan_choose(SPMV_METHODS requested, const spmv_stats *st, size_t value
     plan->csr5_two_deep = (int) opt->v[SPMV_OPT_CSR5_TWO_DEEP];
     plan->run_tiles = (int) opt->v[SPMV_OPT_RUN_TILES];
     plan->row_forward = (int) opt->v[SPMV_OPT_ROW_FORWARD];
+    plan->pack_values = (int) opt->v[SPMV_OPT_PACK_VALUES];
     plan->forced = plan->vector_form != 0 || plan->x_windows != 1 || plan->xcd_order != 1 || plan->csr5_two_deep != 0 || plan->run_tiles != 1 || plan->row_forward != 1;
     plan->autotune = (int) opt->v[SPMV_OPT_AUTOTUNE];
     plan->sell_c = (int) opt->v[SPMV_OPT_SELL_C];

@@ -51,7 +51,8 @@ typedef struct spmv_plan {
     int cache_block;    /* nnz-split family: 0 never, 1 automatic, 2 always use the row-block x column-slab executor */
     int rowblock_nnz;
     int vector_form, x_windows, xcd_order, csr5_two_deep, run_tiles, row_forward; /* executor-form selectors (spmv_plan.c option table) */
-    int forced;         /* any of them differs from its default: create() does not time alternatives */
+    int pack_values;    /* csr-vector, fp64: 7-byte packed value planes for the tiles that qualify: 0 never, 1 always (no timing), 2 timed and guarded (default) */
+    int forced;         /* any of the selectors differs from its default: create() does not time alternatives */
     int autotune;       /* csr-vector: time the applicable kernel forms at create and keep the fastest */
 } spmv_plan;
 

@@ -228,6 +228,7 @@ extern "C" int spmv_shim_build(spmv_dev *d, const spmv_plan *plan)
                 if (d->vt_wide) rc = f64 ? autotune_rows<double>(d) : autotune_rows<float>(d); // wide x windows: the rows kernel over uniform blocks
                 else rc = f64 ? autotune_vector<double>(d) : autotune_vector<float>(d);
             }
+            if (!rc && f64 && plan->pack_values && blocked_mode(d, staged, groups) != 1) rc = build_packed_values(d); // 7-byte value planes for the tiles that qualify
             break;
         }
         case SPMV_SCHED_NNZ_SPLIT:
@@ -408,7 +409,15 @@ static int update_values(spmv_dev *d, const void *val)
             HIP_TRY(hipGetLastError());
         }
         if (!rc && d->plan.sched == SPMV_SCHED_CSR5) rc = refresh_csr5_values<T>(d, d->c5, v);
-        // CSR-scalar, CSR-vector, Balanced and nnz-split read d->val itself
+        // CSR-scalar, CSR-vector, Balanced and nnz-split read d->val itself -- and CSR-vector's packed tiles the planes beside it: gate and pack again
+        // (a tile may gain or lose the packed state with its new values; the alignment part cannot change)
+        if (!rc && d->pk_lo) {
+            if constexpr (sizeof(T) == sizeof(double)) {
+                const long long before = d->pk_nnz;
+                rc = pack_tiles_run(d, true);
+                if (!rc && d->pk_use) d->stream_bytes += before - d->pk_nnz; // account_stream_bytes: 7 B per packed entry
+            }
+        }
     }
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(d->stream)); // the caller may overwrite `val` again at once
@@ -662,6 +671,7 @@ extern "C" int spmv_shim_info(const spmv_dev *d, spmv_hip_info *o)
         o->route_ms[0] = d->route_ms[0]; o->route_ms[1] = d->route_ms[1];
         o->split_ms[0] = d->split_ms[0]; o->split_ms[1] = d->split_ms[1];
         o->far_nnz = d->sp_far->nnz;
+        o->packed_nnz += f.packed_nnz;
         o->blk_waves = f.blk_waves;
         o->reproducible = o->reproducible && f.reproducible;
         append_name(o->launch_kernels, sizeof o->launch_kernels, f.launch_kernels);
@@ -701,11 +711,14 @@ extern "C" int spmv_shim_info(const spmv_dev *d, spmv_hip_info *o)
     o->split_ms[0] = d->split_ms[0];
     o->split_ms[1] = d->split_ms[1];
     o->far_nnz = d->sp_far ? d->sp_far->nnz : 0;
+    o->pack_ms[0] = d->pack_ms[0];
+    o->pack_ms[1] = d->pack_ms[1];
     {
         const bool tiles_run = !d->blk_on && (d->plan.sched == SPMV_SCHED_CSR_VECTOR || d->plan.sched == SPMV_SCHED_ROWBLOCK) && vec_kernel != kVecPipeKernel;
         o->run_nnz = tiles_run ? d->vt_run_nnz : 0;
         o->byte_nnz = tiles_run ? d->vt_byte_nnz : 0;
         o->tmpl_nnz = tiles_run ? d->vt_tmpl_nnz : 0;
+        o->packed_nnz = tiles_run && d->pk_use ? d->pk_nnz : 0;
         if (!d->blk_on && d->plan.sched == SPMV_SCHED_SELL && d->sell_staged > 0) { o->run_nnz = d->sell_run_nnz - d->sell_tmpl_nnz; o->tmpl_nnz = d->sell_tmpl_nnz; o->byte_nnz = d->sell_byte_nnz; }
         if (!d->blk_on && d->plan.sched == SPMV_SCHED_CSR5) o->run_nnz = d->c5.run_tiles * kWave * d->c5.sigma;
     }

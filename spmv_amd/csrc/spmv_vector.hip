@@ -3,7 +3,8 @@
 // spmv_shim.hip (shim/launch.hpp: vector_args), which calls vector_launch / rows_launch with the resolved VecArgs.  They return the launch's
 // error without clearing it: the shim's launch() and autotune check hipGetLastError() after their launches, as for every other kernel.
 // Seven lanes-per-row values x the forms x two value types are most of the library's device code: build.py compiles this file four
-// times, SPMV_VEC_PART = 0 / 1 the tile and pipe kernels in fp64 / fp32, 2 / 3 the rows kernel in fp64 / fp32, side by side.
+// times, SPMV_VEC_PART = 0 / 1 the tile and pipe kernels in fp64 / fp32, 2 / 3 the rows kernel in fp64 / fp32, side by side -- and a fifth time,
+// SPMV_VEC_PART = 4, for the fp64 tile kernel over packed value planes (as much device code again as the fp64 tile kernel itself).
 #include <hip/hip_runtime.h>
 
 #include "kernels/common.hpp"
@@ -12,7 +13,7 @@
 #include "kernels/csr_vector_tile.hpp"
 
 #ifndef SPMV_VEC_PART
-#error "spmv_vector.hip is compiled with -DSPMV_VEC_PART=0..3"
+#error "spmv_vector.hip is compiled with -DSPMV_VEC_PART=0..4"
 #endif
 
 namespace spmv {
@@ -34,11 +35,32 @@ static void with_lanes(int lanes, F f)
     }
 }
 
-#if SPMV_VEC_PART < 2
+#if SPMV_VEC_PART < 2 || SPMV_VEC_PART == 4
 // One workgroup per kVecNB * (256/L) consecutive rows, dispatched in row order: measured on the
 // config-2 shape a plain in-order grid beats a persistent grid-stride loop by ~10 %.
 constexpr int kVecNB = 4;
 
+#if SPMV_VEC_PART == 4
+// fp64 tiles with packed value planes (VecArgs::pk_e): the same kernel with the PACK flag, two or four steps in flight
+template <int L, int DEPTH, bool PRE>
+static void launch_tile_packed(const VecArgs &a, const double *x, double *y)
+{
+    const size_t lds = vec_lds_bytes<double>(a);
+    ensure_lds<csr_vector_tile_kernel<double, L, DEPTH, PRE, true>>(a.device, lds);
+    csr_vector_tile_kernel<double, L, DEPTH, PRE, true><<<a.tiles, kVecTileThreads, lds, a.stream>>>(a.m, a.long_thr, a.rowptr, a.colidx, a.col, (const double *) a.val, a.wins,
+                                                                                                    a.rowslot, a.col8, a.tmpl, a.rowtid, x, y, a.pk_lo, a.pk_hi, a.pk_e);
+}
+
+hipError_t vector_launch_packed(const VecArgs &a, const double *x, double *y)
+{
+    with_lanes(a.lanes, [&](auto L) {
+        constexpr int LL = decltype(L)::value;
+        if (a.depth == 4) { if (a.pre) launch_tile_packed<LL, 4, true>(a, x, y); else launch_tile_packed<LL, 4, false>(a, x, y); }
+        else { if (a.pre) launch_tile_packed<LL, 2, true>(a, x, y); else launch_tile_packed<LL, 2, false>(a, x, y); }
+    });
+    return hipPeekAtLastError();
+}
+#else
 template <typename T, int L, int DEPTH, bool PRE>
 static void launch_tile(const VecArgs &a, const T *x, T *y)
 {
@@ -64,9 +86,13 @@ static void launch_vector(const VecArgs &a, const T *x, T *y)
 using Val = std::conditional<SPMV_VEC_PART == 0, double, float>::type;
 hipError_t vector_launch(const VecArgs &a, const Val *x, Val *y)
 {
+#if SPMV_VEC_PART == 0
+    if (a.kernel == kVecTileKernel && a.pk_e && a.depth != 8) return vector_launch_packed(a, x, y);
+#endif
     with_lanes(a.lanes, [&](auto L) { launch_vector<Val, decltype(L)::value>(a, x, y); });
     return hipPeekAtLastError();
 }
+#endif
 #else
 template <typename T, int L, int DEPTH, bool WIDE>
 static void launch_rows(const VecArgs &a, const T *x, T *y)
