@@ -327,6 +327,10 @@ static int pack_tiles_run(spmv_dev *d, bool pack)
     return SPMV_HIP_OK;
 }
 
+// what the packed planes change in one multiply's matrix stream while they are in use: 7 B instead of 8 per packed entry, an exponent per tile
+// (account_stream_bytes at create, update_values when the packed tiles change)
+static long long packed_stream_bytes(const spmv_dev *d) { return d->pk_use ? 4ll * d->vt_tiles - d->pk_nnz : 0; }
+
 template <typename T> static int launch_csr5(spmv_dev *d, const Csr5Plan &P, const T *x, T *y);
 
 template <typename T>
@@ -983,7 +987,7 @@ static int account_stream_bytes(spmv_dev *d)
             if (tile_form) t.bytes += 2ll * d->vt_run_rows - 2ll * d->vt_run_nnz; // RUN tiles: a 16-bit slot per row instead of one per entry
             if (tile_form) t.bytes += 3ll * d->vt_tmpl_rows + 2ll * kTmplCount * kTmplMax * d->vt_tmpl_tiles - 2ll * d->vt_tmpl_nnz; // TEMPLATE tiles: a 16-bit slot and a list number per row, the lists once per tile
             if (tile_form) t.bytes += 2ll * d->vt_byte_rows - 1ll * d->vt_byte_nnz; // BYTE tiles: a byte per entry and a 16-bit slot per row instead of 16 bits per entry
-            if (tile_form && d->pk_use) t.bytes += 4ll * d->vt_tiles - d->pk_nnz; // PACKED tiles: 7 B instead of 8 per entry, an exponent per tile
+            t.bytes += packed_stream_bytes(d); // PACKED tiles (the tile kernel, also where option vector_form forces it on unstaged tiles)
             if (d->plan.sched == SPMV_SCHED_ROWBLOCK) t.bytes += 4ll * (d->nblocks + 1);
             if (!tile_form || wtiles < d->vt_tiles) t.gathers_global = true;
             rc = csr5_traffic(d, d->c5_long, t);

@@ -410,12 +410,13 @@ static int update_values(spmv_dev *d, const void *val)
         }
         if (!rc && d->plan.sched == SPMV_SCHED_CSR5) rc = refresh_csr5_values<T>(d, d->c5, v);
         // CSR-scalar, CSR-vector, Balanced and nnz-split read d->val itself -- and CSR-vector's packed tiles the planes beside it: gate and pack again
-        // (a tile may gain or lose the packed state with its new values; the alignment part cannot change)
+        // (a tile may gain or lose the packed state with its new values; the alignment part cannot change).  The planes are in use while any tile is
+        // packed: with none the launch is the 8-byte kernel's and stream_bytes is what create() reports for such values (no planes, no exponents)
         if (!rc && d->pk_lo) {
             if constexpr (sizeof(T) == sizeof(double)) {
-                const long long before = d->pk_nnz;
+                const long long before = packed_stream_bytes(d);
                 rc = pack_tiles_run(d, true);
-                if (!rc && d->pk_use) d->stream_bytes += before - d->pk_nnz; // account_stream_bytes: 7 B per packed entry
+                if (!rc) { d->pk_use = d->pk_tiles > 0; d->stream_bytes += packed_stream_bytes(d) - before; }
             }
         }
     }

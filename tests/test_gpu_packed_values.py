@@ -2,7 +2,7 @@
 
 Every case is a 1000 .. 2304-row banded matrix (row i holds len_i consecutive columns around the diagonal, wrapping at the edges) with
 full-precision x.  Unless stated otherwise a case multiplies through a pack_values = 1 handle and through a pack_values = 0 handle and compares y
-BIT FOR BIT, and it compares spmv_hip_info.packed_nnz with a host model of the gate (`model_packed`): a 256-row tile packs iff every row of it
+BIT FOR BIT, and it compares spmv_hip_info.packed_nnz with a host model of the gate (`model_packed`, tests/packed_cases.py): a 256-row tile packs iff every row of it
 starts at a multiple of C = 4L and is a whole number of C-blocks long, every value is finite and not -0.0, and the non-zero values' bit
 positions span at most 55 (largest leading-bit position - smallest lowest-set-bit position <= 54).  L is read from the handle's info.
 
@@ -18,98 +18,9 @@ import numpy as np
 import pytest
 
 from spmv_amd import api
+from packed_cases import METHOD, TILE, Pair, banded, x_of
 
 pytestmark = pytest.mark.gpu
-
-TILE = 256
-METHOD = int(api.SPMV_METHODS.Method_Parallel)
-
-
-# ------------------------------------------------------------------------------------------------ matrices and the host model
-def banded(lens, seed=1):
-    """m = len(lens) rows, n = m columns; row i holds columns (i - len_i // 2 + j) mod n, j = 0 .. len_i - 1; values uniform in [-1, 1)."""
-    lens = np.asarray(lens, dtype=np.int64)
-    m = lens.size
-    rp = np.zeros(m + 1, dtype=np.int64)
-    np.cumsum(lens, out=rp[1:])
-    row = np.repeat(np.arange(m, dtype=np.int64), lens)
-    j = np.arange(int(rp[-1]), dtype=np.int64) - rp[row]
-    ci = ((row - lens[row] // 2 + j) % m).astype(np.int32)
-    va = np.random.default_rng(seed).uniform(-1.0, 1.0, size=int(rp[-1]))
-    return m, rp.astype(np.int32), ci, va
-
-
-def x_of(n, seed=7):
-    return np.random.default_rng(seed).uniform(-1.0, 1.0, size=n)
-
-
-def bit_span(v):
-    """(top, low) over the non-zero finite values of v: largest leading-bit position, smallest lowest-set-bit position; None if all are zero."""
-    b = np.ascontiguousarray(v).view(np.uint64)
-    E = ((b >> np.uint64(52)) & np.uint64(0x7FF)).astype(np.int64)
-    frac = b & np.uint64((1 << 52) - 1)
-    mant = (frac | ((E > 0).astype(np.uint64) << np.uint64(52))).astype(np.int64)
-    nz = mant != 0
-    if not nz.any():
-        return None
-    mant, base = mant[nz], np.maximum(E[nz], 1) - 1075
-    top = base + np.frexp(mant.astype(np.float64))[1] - 1          # mant < 2^53: exact in a double
-    low = base + np.frexp((mant & -mant).astype(np.float64))[1] - 1
-    return int(top.max()), int(low.min())
-
-
-def model_packed(rp, va, L):
-    """-> (packed entries, [tile packs?]) by the gate's definition."""
-    C, m = 4 * L, rp.size - 1
-    total, flags = 0, []
-    for r0 in range(0, m, TILE):
-        r1 = min(m, r0 + TILE)
-        starts, lens = rp[r0:r1].astype(np.int64), np.diff(rp[r0:r1 + 1].astype(np.int64))
-        v = va[rp[r0]:rp[r1]]
-        ok = bool((starts % C == 0).all() and (lens % C == 0).all())
-        ok = ok and bool(np.isfinite(v).all()) and not bool(((v == 0) & np.signbit(v)).any())
-        if ok:
-            span = bit_span(v)
-            ok = span is None or span[0] - span[1] <= 54
-        flags.append(ok)
-        total += int(rp[r1] - rp[r0]) if ok else 0
-    return total, flags
-
-
-class Pair:
-    """The same matrix under pack_values = 1 and pack_values = 0 (optionally with lanes_per_row forced)."""
-
-    def __init__(self, m, rp, ci, va, lanes=0):
-        self.m, self.rp, self.ci = m, rp, ci
-        self.h = {}
-        for pack in (1, 0):
-            api.set_thread_option("pack_values", pack)
-            if lanes:
-                api.set_thread_option("lanes_per_row", lanes)
-            try:
-                self.h[pack] = api.Handle(m, m, rp, ci, va.copy(), METHOD)
-            finally:
-                api.clear_thread_options()
-        self.L = self.h[1].info()["lanes_per_row"]
-        assert self.h[1].info()["kernel_name"] == "csr_vector_tile_kernel" == self.h[0].info()["kernel_name"]
-        assert self.h[0].info()["packed_nnz"] == 0
-
-    def close(self):
-        for h in self.h.values():
-            h.close()
-
-    def same_bits(self, x):
-        y1 = self.h[1].spmv(x, np.full(self.m, np.nan))
-        y0 = self.h[0].spmv(x, np.full(self.m, np.nan))
-        assert y1.tobytes() == y0.tobytes(), f"{int((y1.view(np.uint64) != y0.view(np.uint64)).sum())} rows differ in their bits"
-        return y1
-
-    def check(self, va, x):
-        """bits equal, packed_nnz = the model's; -> the model's per-tile flags"""
-        want, flags = model_packed(self.rp, va, self.L)
-        self.same_bits(x)
-        assert self.h[1].info()["packed_nnz"] == want, (self.h[1].info()["packed_nnz"], want, flags)
-        return want, flags
 
 
 def run_case(lens, edit=None, lanes=0, seed=1):
