@@ -773,6 +773,63 @@ void spmv_hip_create_handle_from_blocks(spmv_Handle_t *Handle, int blocks, const
                                         BASIC_INT_TYPE *const *RowPtr, BASIC_INT_TYPE *const *ColIdx, void *const *Matrix_Val,
                                         SPMV_METHODS Function, BASIC_SIZE_TYPE size);
 
+/* ---- conjugate gradients on the device: A x = b ------------------------------------------------
+ * Preconditioned conjugate gradients for a SYMMETRIC POSITIVE DEFINITE A (m = n) in the standard two-dot form, with an optional diagonal
+ * (Jacobi) preconditioner: per iteration the handle's own multiply q = A p -- spmv()'s schedule and bits -- and three vector kernels.  alpha,
+ * beta and the stop test are formed on the device; the host enqueues check_every iterations, then looks at a small state word once.
+ *   - Returns SPMV_HIP_OK whenever the solve RAN: not converging is a `status`, not an error.  The call is synchronous: it returns with X
+ *     complete, on the handle's stream, whatever spmv_hip_set_async says.
+ *   - The CSR arguments follow spmv()'s rules: m and the pointers seen at create -> the resident matrix; others -> that matrix is
+ *     re-inspected; option "check_values", in-place value changes and spmv_hip_update_values apply as for spmv().
+ *   - B, X and Dinv: m elements of the handle's type each, host or device pointers (host ones are staged through handle-owned HBM buffers);
+ *     B and X must not overlap.  use_x0 = 0: the solve starts from x = 0 and X is only written; otherwise X holds the initial guess.
+ *   - Stop: rr <= max(rtol^2 * bb, atol^2), with rr = <r,r> of the recurrence's residual and bb = <b,b>, both in fp64; rtol = atol = 0
+ *     runs max_iterations iterations (unless rr reaches 0).  m = 0: converged, 0 iterations.  bb = 0: X is set to zeros, converged, 0 iterations.
+ *   - status: SPMV_HIP_CG_CONVERGED; _MAX_ITERATIONS; _BREAKDOWN: <p,Ap> <= 0 or <r,z> <= 0 while rr > 0 -- A or Dinv is not positive
+ *     definite; X is the last iterate before it; _NONFINITE: a NaN or infinity in <b,b>, <r,r>, <r,z>, <p,Ap>, alpha or beta.  `iterations`
+ *     counts the updates of x that were applied, rr and bb belong to the returned X.  history (a HOST array of max_iterations + 1 doubles, or
+ *     NULL) receives rr after iteration 0 (the initial residual), 1, ..., iterations.
+ *   - Workspace: r, p, q (m elements each), the partial sums and the state in one block -- and the history's device copy when one is
+ *     wanted -- allocated at the first solve, freed at destroy / clear / re-inspection, counted in spmv_hip_info.device_bytes.
+ *   - Option "reorder" handles solve with the resident P A P^T: the caller permutes B, X and Dinv by handle->index (XX[i] = X[index[i]]),
+ *     as for spmv().
+ *   - Errors (SPMV_HIP_E_ARG, X untouched): a matrix with m != n at create; NULL opt or res; NULL B or X when m > 0; max_iterations < 0,
+ *     check_every < 0, a negative or NaN rtol or atol; multi-GPU handles (option "gpus", spmv_hip_create_handle_from_blocks); host_rows
+ *     handles.  A cleared or failed handle: SPMV_HIP_E_NOSTATE.  Every failure is also reported through spmv_hip_last_error().
+ *
+ * The arithmetic contract -- bits, not a tolerance; tests/cg_cases.py restates it in numpy:
+ *   Elements are of the handle's type T.  Every dot widens both elements to fp64, multiplies and adds in fp64, separately (no fma; for float
+ *   the product of two widened elements is exact).  alpha = <r,z> / <p,q> and beta = <r,z>_new / <r,z>_old are formed in fp64 and rounded to T
+ *   ONCE.  The vector updates are in T, a multiply and then an add, never an fma, in this order per iteration:
+ *       x = x + alpha*p;  r = r - alpha*q;  z = Dinv*r (z = r without Dinv);  p = z + beta*p.
+ *   At the start r = B (or r = B - A*x0), p = z.  The stop test reads the rr of the update just applied.
+ *   Order of a dot over m elements: P = min(1024, ceil(m / 1024)) workgroups, L = 1024 * ceil(m / (1024 * P)); workgroup j owns elements
+ *   [j*L, min(m, (j + 1)*L)).  Inside a workgroup the element at offset o goes to thread (o / 4) mod 256, slot o mod 4, step o / 1024; each
+ *   (thread, slot) accumulator starts at +0.0 and adds its products by ascending step; absent elements add +0.0.  A thread's sum is
+ *   (a0 + a1) + (a2 + a3); the 64 lanes of a wave are combined by the adjacent-pair binary tree; the four waves as (w0 + w1) + (w2 + w3).  For
+ *   the final sum the P partials are padded with +0.0 to 1024, thread t takes partials 4t .. 4t + 3 as (a + b) + (c + d), then the same wave
+ *   and workgroup trees.  The order depends on m alone: not on the value type, the alignment of a pointer, the access width, or whether a
+ *   pointer is a host or a device one.
+ *   Consequences: Dinv = all ones gives exactly the bits of Dinv = NULL; X, iterations, rr and history are bit-identical run to run and for
+ *   every check_every (unless the handle was created with option "deterministic" = 0, whose spmv() is not reproducible either). */
+enum { SPMV_HIP_CG_CONVERGED = 0, SPMV_HIP_CG_MAX_ITERATIONS = 1, SPMV_HIP_CG_BREAKDOWN = 2, SPMV_HIP_CG_NONFINITE = 3 };
+typedef struct spmv_hip_cg_options {
+    double rtol, atol;        /* stop when rr <= max(rtol^2 * bb, atol^2); rr = <r,r>, bb = <b,b>, both in fp64 */
+    int max_iterations;       /* >= 0 */
+    int check_every;          /* iterations enqueued between two looks at the device's state word; 0 = default */
+    int use_x0;               /* 0: start from x = 0 (X is only written); != 0: X holds the initial guess */
+    const void *Dinv;         /* NULL, or m elements of the handle's type (host or device): z = Dinv .* r (Jacobi: 1 / diag(A)) */
+    double *history;          /* NULL, or HOST array of max_iterations + 1 doubles: rr after iteration 0, 1, ... */
+} spmv_hip_cg_options;
+typedef struct spmv_hip_cg_result {
+    int status;               /* SPMV_HIP_CG_CONVERGED 0, _MAX_ITERATIONS 1, _BREAKDOWN 2, _NONFINITE 3 */
+    int iterations;           /* updates of x that were applied */
+    double rr, bb;            /* of the returned x (the recurrence's r) */
+} spmv_hip_cg_result;
+int spmv_hip_cg(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                const void *Matrix_Val, const void *B, void *X,
+                const spmv_hip_cg_options *opt, spmv_hip_cg_result *res);
+
 #endif /* SPMV_HIP_EXT_H */
 
 #if defined(__cplusplus)

@@ -90,6 +90,13 @@ double spmv_hip_time_attention_gqa_backward_16_launches(spmv_Handle_t handle, in
                                                         const void *K, long long ldk, const void *V, long long ldv, const void *B, long long ldb, const void *G, long long ldg,
                                                         const void *O, long long ldo, const void *L, long long ldl, int dq_type, void *dQ, long long lddq, int dkv_type, void *dK,
                                                         long long lddk, void *dV, long long lddv, void *dB, long long lddb, int warmup, int iters, float *ms_out);
+/* spmv_hip_cg's iterations (include spmv_hip.h first: spmv_hip_cg_options): `warmup` untimed + `iters` timed RUNS of opt->max_iterations (>= 1)
+   iterations each, with the stop tests disabled.  Every run starts again from B (and X when use_x0); its iterations -- multiply, cg_dot,
+   cg_update, cg_direction -- are enqueued back to back on the handle's stream and bracketed by two hipEvents, the start outside them; ms_out[i]
+   (may be NULL) receives run i.  B, X and opt->Dinv must be DEVICE pointers; rtol, atol, check_every and history are not used.  Returns the mean
+   ms per run, < 0 on error. */
+struct spmv_hip_cg_options;
+double spmv_hip_time_cg_iterations(spmv_Handle_t handle, const void *B, void *X, const struct spmv_hip_cg_options *opt, int warmup, int iters, float *ms_out);
 /* copies the built transpose map to host: rowptr_t (n+1 entries) and perm (nnz entries: perm[p] = CSR index in A of the entry at
    position p of A^T's CSR); either may be NULL.  SPMV_HIP_E_NOSTATE until the transpose is built. */
 int spmv_hip_transpose_map(spmv_Handle_t handle, int *rowptr_t, int *perm);

@@ -73,6 +73,17 @@ class spmv_hip_info(C.Structure):
                 ("packed_nnz", C.c_longlong), ("pack_ms", C.c_float * 2)]
 
 
+class spmv_hip_cg_options(C.Structure):  # include/spmv_hip.h
+    _fields_ = [("rtol", C.c_double), ("atol", C.c_double), ("max_iterations", C.c_int), ("check_every", C.c_int), ("use_x0", C.c_int),
+                ("Dinv", C.c_void_p), ("history", C.POINTER(C.c_double))]
+
+
+class spmv_hip_cg_result(C.Structure):  # include/spmv_hip.h
+    _fields_ = [("status", C.c_int), ("iterations", C.c_int), ("rr", C.c_double), ("bb", C.c_double)]
+
+
+CG_STATUS = ("converged", "max_iterations", "breakdown", "nonfinite")  # SPMV_HIP_CG_*
+
 # Every symbol include/*.h declares: functions with their prototypes, then data symbols.
 FUNCTIONS = {
     "spmv_create_handle_all_in_one": (None, [C.POINTER(spmv_Handle_t), C.c_int, C.c_int, _V, _V, _V,
@@ -188,6 +199,8 @@ FUNCTIONS = {
                                                                       _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, C.c_int, _V,
                                                                       C.c_longlong, C.c_int, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, C.c_int, C.c_int,
                                                                       C.POINTER(C.c_float)]),
+    "spmv_hip_cg": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, _V, _V, C.POINTER(spmv_hip_cg_options), C.POINTER(spmv_hip_cg_result)]),
+    "spmv_hip_time_cg_iterations": (C.c_double, [spmv_Handle_t, _V, _V, C.POINTER(spmv_hip_cg_options), C.c_int, C.c_int, C.POINTER(C.c_float)]),
     # include/spmv_io.h (host only)
     "spmv_io_read_mtx": (C.c_int, [C.c_char_p, C.c_size_t, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_V)]),
     "spmv_io_cache_path": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t]),
@@ -949,6 +962,34 @@ def time_attention_gqa_backward_16_launches(handle, heads, kv_heads, Q, K, V, B,
     return _timed("spmv_hip_time_attention_gqa_backward_16_launches", (handle, int(heads), int(kv_heads), k, dv, float(scale), *rest), warmup, iters)
 
 
+def _cg_options(rtol, atol, max_iterations, check_every, x0, dinv, history):
+    """-> (spmv_hip_cg_options, the history array or None)"""
+    hist = np.zeros(int(max_iterations) + 1, dtype=np.float64) if history and max_iterations >= 0 else None
+    opt = spmv_hip_cg_options(float(rtol), float(atol), int(max_iterations), int(check_every), 1 if x0 else 0, _ptr(dinv),
+                              hist.ctypes.data_as(C.POINTER(C.c_double)) if hist is not None else None)
+    return opt, hist
+
+
+def cg(handle, m, RowPtr, ColIdx, Matrix_Val, B, X, rtol=1e-8, atol=0.0, max_iterations=1000, check_every=0, x0=False, dinv=None, history=False,
+       check=True):
+    """Solve A x = B by preconditioned conjugate gradients on the device (spmv_hip_cg): B, X, dinv of m elements, host or device; x0: X holds the
+    initial guess.  -> (rc, result dict: status, status_name, iterations, rr, bb[, history: rr after iteration 0 .. iterations])."""
+    opt, hist = _cg_options(rtol, atol, max_iterations, check_every, x0, dinv, history)
+    res = spmv_hip_cg_result()
+    rc = _checked(load().spmv_hip_cg(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), _ptr(B), _ptr(X), C.byref(opt), C.byref(res)), "spmv_hip_cg", check)
+    out = {"status": res.status, "status_name": CG_STATUS[res.status] if 0 <= res.status < len(CG_STATUS) else "?", "iterations": res.iterations, "rr": res.rr, "bb": res.bb}
+    if hist is not None:
+        out["history"] = hist[:res.iterations + 1].copy() if rc == 0 else hist[:0].copy()
+    return rc, out
+
+
+def time_cg_iterations(handle, B, X, iterations, x0=False, dinv=None, warmup=2, iters=20):
+    """-> (mean ms per run, per-run ms array) of `iters` runs of `iterations` CG iterations each, stop tests off, on device B / X / dinv
+    (spmv_hip_time_cg_iterations)."""
+    opt, _ = _cg_options(0.0, 0.0, iterations, 0, x0, dinv, False)
+    return _timed("spmv_hip_time_cg_iterations", (handle, _ptr(B), _ptr(X), C.byref(opt)), warmup, iters)
+
+
 def _take_csr(m, n, nnz, rp, ci, va, dtype):
     """Copy malloc'ed C arrays into numpy arrays and free the C side."""
     from .synth import CSR
@@ -1102,6 +1143,20 @@ class Handle:
         rp, ci, va = self._keep
         row_softmax_backward(self.h, self.m, rp, ci, va, P, G, out)
         return out
+
+    def cg(self, b, x=None, x0=False, rtol=1e-8, atol=0.0, max_iterations=1000, check_every=0, dinv=None, history=False):
+        """Solve A x = b by preconditioned conjugate gradients that stay on the device (spmv_hip_cg; A symmetric positive definite).  x is
+        allocated like b when None (then x0 must be off); x0: x holds the initial guess; dinv: None or 1 / diag(A) (Jacobi).
+        -> (x, result dict) or (x, result dict, history) when history is set: rr after iteration 0 .. iterations."""
+        if x is None:
+            if x0:
+                raise ValueError("x0 needs an x that holds the initial guess")
+            x = self._like(b, (self.m,))
+        rp, ci, va = self._keep
+        _, res = cg(self.h, self.m, rp, ci, va, b, x, rtol, atol, max_iterations, check_every, x0, dinv, history)
+        if history:
+            return x, res, res.pop("history")
+        return x, res
 
     def attention(self, Q, K, V, scale=None, out=None):
         """out = softmax_rows(scale * Q K^T on the pattern) V in one pass (spmv_hip_attention) for 2-D Q (m x k), K (n x k) and V (n x dv); scale

@@ -41,9 +41,13 @@ HIP_SOURCES = [("spmv_shim.hip", [], "spmv_shim.hip.o")] + [("spmv_vector.hip", 
               [("spmv_attention.hip", [], "spmv_attention.hip.o")] + \
               [("spmv_attention_16.hip", [f"SPMV_ATT16_TYPE={t}"], f"spmv_attention_16_{t}.hip.o") for t in (1, 2)] + \
               [("spmv_attention_backward.hip", [], "spmv_attention_backward.hip.o")] + \
-              [("spmv_attention_backward_16.hip", [f"SPMV_ATTB16_TYPE={t}"], f"spmv_attention_backward_16_{t}.hip.o") for t in (1, 2)]   # the k-right-hand-side executors (kernels/spmm.hpp), the transpose builder (kernels/transpose.hpp), the sampled product (kernels/sddmm.hpp), the row reductions (kernels/row_softmax.hpp), the fused attention (kernels/attention.hpp; on 16-bit operands once per storage type, fp16 and bf16) and its backward (kernels/attention_backward.hpp; on 16-bit operands likewise once per storage type)
+              [("spmv_attention_backward_16.hip", [f"SPMV_ATTB16_TYPE={t}"], f"spmv_attention_backward_16_{t}.hip.o") for t in (1, 2)] + \
+              [("spmv_cg.hip", [], "spmv_cg.hip.o")]   # the conjugate-gradient vector kernels (kernels/cg.hpp); before it: the k-right-hand-side executors (kernels/spmm.hpp), the transpose builder (kernels/transpose.hpp), the sampled product (kernels/sddmm.hpp), the row reductions (kernels/row_softmax.hpp), the fused attention (kernels/attention.hpp; on 16-bit operands once per storage type, fp16 and bf16) and its backward (kernels/attention_backward.hpp; on 16-bit operands likewise once per storage type)
 HIP_FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
              "-ffp-contract=fast"]
+# flags of single sources, behind HIP_FLAGS.  spmv_cg.hip promises the bits of separate multiplies and adds (include/spmv_hip.h, "the arithmetic
+# contract"): under -ffp-contract=fast the back end fuses a multiply and an add whatever `#pragma clang fp contract(off)` says in the source
+HIP_SOURCE_FLAGS = {"spmv_cg.hip": ["-ffp-contract=off"]}
 C_FLAGS = ["-O2", "-std=c11", "-fPIC", "-fopenmp", "-Wall", "-Wextra", "-D_POSIX_C_SOURCE=200809L"]
 
 
@@ -93,7 +97,7 @@ def build_debug(defines, name="libspmv_hip_dbg.so", verbose=False):
     cmds = []
     for src, defs, oname in HIP_SOURCES:
         obj = os.path.join(OBJDIR, "dbg_" + oname)
-        cmds.append([HIPCC, *HIP_FLAGS, *[f"-D{d}" for d in list(defines) + defs], f"-I{INC}", f"-I{CSRC}", "-c", os.path.join(CSRC, src), "-o", obj])
+        cmds.append([HIPCC, *HIP_FLAGS, *HIP_SOURCE_FLAGS.get(src, []), *[f"-D{d}" for d in list(defines) + defs], f"-I{INC}", f"-I{CSRC}", "-c", os.path.join(CSRC, src), "-o", obj])
         objs.append(obj)
     _run_all(cmds)
     gomp = subprocess.run([CC, "-print-file-name=libgomp.so"], capture_output=True, text=True).stdout.strip()
@@ -122,7 +126,7 @@ def build(force=False, verbose=False):
     cmds = []
     for src, defs, oname in HIP_SOURCES:
         obj = os.path.join(OBJDIR, oname)
-        cmd = [HIPCC, *HIP_FLAGS, *[f"-D{d}" for d in defs], f"-I{INC}", f"-I{CSRC}", "-c", os.path.join(CSRC, src), "-o", obj]
+        cmd = [HIPCC, *HIP_FLAGS, *HIP_SOURCE_FLAGS.get(src, []), *[f"-D{d}" for d in defs], f"-I{INC}", f"-I{CSRC}", "-c", os.path.join(CSRC, src), "-o", obj]
         if verbose:
             print(" ".join(cmd))
         cmds.append(cmd)

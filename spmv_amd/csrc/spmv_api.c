@@ -1532,3 +1532,35 @@ double spmv_hip_time_attention_gqa_backward_16_launches(spmv_Handle_t h, int hea
                                                                 V, ldv, B, ldb, G, ldg, O, ldo, L, ldl, dq_type, dQ, lddq, dkv_type, dK, lddk, dV, lddv, dB, lddb, warmup, iters,
                                                                 ms_out), where);
 }
+
+/* ---------------------------------------------------------------- conjugate gradients on the device */
+/* the argument rules ahead of the gate: spmv_hip_cg; its timer with m = 1 (B and X are always needed) */
+static int cg_args(spmv_Handle_t h, const char *where, const void *B, const void *X, const spmv_hip_cg_options *opt, const void *res, int m)
+{
+    if (!h) return refuse(SPMV_HIP_E_ARG, where, "handle is NULL");
+    if (!opt || !res) return refuse(SPMV_HIP_E_ARG, where, "opt or res is NULL");
+    if (m > 0 && (!B || !X)) return refuse(SPMV_HIP_E_ARG, where, "B or X is NULL");
+    if (opt->max_iterations < 0 || opt->check_every < 0) return refuse(SPMV_HIP_E_ARG, where, "need max_iterations >= 0 and check_every >= 0");
+    if (!(opt->rtol >= 0) || !(opt->atol >= 0)) return refuse(SPMV_HIP_E_ARG, where, "rtol and atol must be >= 0 (and not NaN)");
+    return SPMV_HIP_OK;
+}
+
+int spmv_hip_cg(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                const void *Matrix_Val, const void *B, void *X, const spmv_hip_cg_options *opt, spmv_hip_cg_result *res)
+{
+    const char *where = "cg";
+    spmv_hip_state *st;
+    int rc;
+    if ((rc = cg_args(handle, where, B, X, opt, res, m)) || (rc = resident_prologue(handle, where, 0, m, RowPtr, ColIdx, Matrix_Val, &st))) return rc;
+    if (st->m != st->n) return refuse(SPMV_HIP_E_ARG, where, "the matrix is not square (m != n at create)");
+    return report(spmv_shim_cg(st->dev, B, X, opt, res), where);
+}
+
+double spmv_hip_time_cg_iterations(spmv_Handle_t h, const void *B, void *X, const spmv_hip_cg_options *opt, int warmup, int iters, float *ms_out)
+{
+    const char *where = "time_cg_iterations";
+    spmv_hip_state *st;
+    if (cg_args(h, where, B, X, opt, opt, 1) || resident_state(h, where, 0, &st)) return -1.0;
+    if (st->m != st->n) { (void) refuse(SPMV_HIP_E_ARG, where, "the matrix is not square (m != n at create)"); return -1.0; }
+    return report_time(spmv_shim_time_cg(st->dev, B, X, opt, warmup, iters, ms_out), where);
+}

@@ -252,6 +252,13 @@ double spmv_shim_time_attention_gqa_backward_16(spmv_dev *d, int heads, int kv_h
                                                 const void *o, long long ldo, const void *lse, long long ldl, int dq_type, void *dq, long long lddq, int dkv_type, void *dk,
                                                 long long lddk, void *dv_out, long long lddv, void *db, long long lddb, int warmup, int iters, float *ms_out);
 
+/* ---- preconditioned conjugate gradients on the resident matrix (shim/cg.hpp; spmv_hip_cg) ----
+ * B, X, opt->Dinv: m elements, host or device pointers each.  The multiply is the built schedule's own launch.  Builds the workspace at the first call.
+ * SPMV_HIP_OK whenever the solve ran (res->status says how it ended); synchronous */
+int spmv_shim_cg(spmv_dev *d, const void *b, void *x, const spmv_hip_cg_options *opt, spmv_hip_cg_result *res);
+/* `iters` runs of opt->max_iterations iterations each, the stop tests off, timed with events on the handle's stream (device B / X / Dinv); mean ms per run, < 0 on failure */
+double spmv_shim_time_cg(spmv_dev *d, const void *b, void *x, const spmv_hip_cg_options *opt, int warmup, int iters, float *ms_out);
+
 /* the resident CSR arrays (device pointers; ColIdx may be NULL after spmv_shim_release_columns) */
 void spmv_shim_matrix_arrays(const spmv_dev *d, const int **rowptr, const int **colidx, const void **val);
 
