@@ -84,6 +84,23 @@ class spmv_hip_cg_result(C.Structure):  # include/spmv_hip.h
 
 CG_STATUS = ("converged", "max_iterations", "breakdown", "nonfinite")  # SPMV_HIP_CG_*
 
+# The fragments the attention prototypes of include/spmv_hip.h and spmv_hip_tools.h are made of
+_CSR = [spmv_Handle_t, C.c_int, _V, _V, _V]          # handle, m, RowPtr, ColIdx, Matrix_Val: a call
+_TIMED = [spmv_Handle_t]                               # ... a timer takes the handle alone
+_TAIL = [C.c_int, C.c_int, C.POINTER(C.c_float)]       # ... and ends with warmup, iters, ms_out
+_ONE = [C.c_int, C.c_int, C.c_double]                  # k, dv, scale
+_HEADS = [C.c_int] + _ONE                              # heads, k, dv, scale
+_GQA = [C.c_int] + _HEADS                              # heads, kv_heads, k, dv, scale
+_TYPE = [C.c_int]                                      # a SPMV_HIP_T_* code: io_type, o_type, dq_type, dkv_type where the prototype has them
+_Q = _K = _VV = _B = _O = _L = _G = _DQ = _DK = _DV = _DB = [_V, C.c_longlong]   # an operand and its leading dimension or plane stride
+_QKV = _Q + _K + _VV
+
+
+def _attention(stem, sizes, operands):
+    """-> the FUNCTIONS entries of the call spmv_hip_<stem> and of its timer spmv_hip_time_<stem>_launches"""
+    return {f"spmv_hip_{stem}": (C.c_int, _CSR + sizes + operands), f"spmv_hip_time_{stem}_launches": (C.c_double, _TIMED + sizes + operands + _TAIL)}
+
+
 # Every symbol include/*.h declares: functions with their prototypes, then data symbols.
 FUNCTIONS = {
     "spmv_create_handle_all_in_one": (None, [C.POINTER(spmv_Handle_t), C.c_int, C.c_int, _V, _V, _V,
@@ -133,72 +150,23 @@ FUNCTIONS = {
     "spmv_hip_row_softmax": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, _V, _V]),
     "spmv_hip_row_softmax_backward": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, _V, _V, _V]),
     "spmv_hip_time_row_softmax_launches": (C.c_double, [spmv_Handle_t, _V, _V, C.c_int, C.c_int, C.POINTER(C.c_float)]),
-    "spmv_hip_attention": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong,
-                                     _V, C.c_longlong]),
-    "spmv_hip_time_attention_launches": (C.c_double, [spmv_Handle_t, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong,
-                                                      _V, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_float)]),
-    "spmv_hip_attention_heads": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, C.c_int, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong,
-                                           _V, C.c_longlong, _V, C.c_longlong]),
-    "spmv_hip_time_attention_heads_launches": (C.c_double, [spmv_Handle_t, C.c_int, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong,
-                                                            _V, C.c_longlong, _V, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_float)]),
-    "spmv_hip_attention_backward": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong,
-                                              _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong]),
-    "spmv_hip_time_attention_backward_launches": (C.c_double, [spmv_Handle_t, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong,
-                                                               _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, C.c_int, C.c_int,
-                                                               C.POINTER(C.c_float)]),
-    "spmv_hip_attention_heads_backward": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, C.c_int, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong,
-                                                    _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong]),
-    "spmv_hip_time_attention_heads_backward_launches": (C.c_double, [spmv_Handle_t, C.c_int, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong,
-                                                                     _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong,
-                                                                     C.c_int, C.c_int, C.POINTER(C.c_float)]),
-    "spmv_hip_attention_bias": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, C.c_int, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong,
-                                          _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong]),
-    "spmv_hip_time_attention_bias_launches": (C.c_double, [spmv_Handle_t, C.c_int, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong,
-                                                           _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_float)]),
-    "spmv_hip_attention_bias_backward": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, C.c_int, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong,
-                                                   _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong,
-                                                   _V, C.c_longlong]),
-    "spmv_hip_time_attention_bias_backward_launches": (C.c_double, [spmv_Handle_t, C.c_int, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong,
-                                                                    _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong,
-                                                                    _V, C.c_longlong, _V, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_float)]),
-    "spmv_hip_attention_gqa": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong,
-                                         _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong]),
-    "spmv_hip_time_attention_gqa_launches": (C.c_double, [spmv_Handle_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong,
-                                                          _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_float)]),
-    "spmv_hip_attention_gqa_backward": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong,
-                                                  _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong,
-                                                  _V, C.c_longlong]),
-    "spmv_hip_time_attention_gqa_backward_launches": (C.c_double, [spmv_Handle_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong,
-                                                                   _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong,
-                                                                   _V, C.c_longlong, _V, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_float)]),
-    "spmv_hip_attention_gqa_lse": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong,
-                                             _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong]),
-    "spmv_hip_time_attention_gqa_lse_launches": (C.c_double, [spmv_Handle_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong,
-                                                              _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, C.c_int, C.c_int,
-                                                              C.POINTER(C.c_float)]),
-    "spmv_hip_attention_gqa_lse_16": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _V, C.c_longlong, _V, C.c_longlong,
-                                                _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, C.c_int, _V, C.c_longlong]),
-    "spmv_hip_time_attention_gqa_lse_16_launches": (C.c_double, [spmv_Handle_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _V, C.c_longlong, _V, C.c_longlong,
-                                                                 _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, C.c_int, _V, C.c_longlong, C.c_int, C.c_int,
-                                                                 C.POINTER(C.c_float)]),
+    # the fused attention: a call and its timer per line, the operands in the prototype's order (a name: the operand and its ld)
+    **_attention("attention", _ONE, _QKV + _O),
+    **_attention("attention_heads", _HEADS, _QKV + _O),
+    **_attention("attention_backward", _ONE, _QKV + _G + _DQ + _DK + _DV),
+    **_attention("attention_heads_backward", _HEADS, _QKV + _G + _DQ + _DK + _DV),
+    **_attention("attention_bias", _HEADS, _QKV + _B + _O),
+    **_attention("attention_bias_backward", _HEADS, _QKV + _B + _G + _DQ + _DK + _DV + _DB),
+    **_attention("attention_gqa", _GQA, _QKV + _B + _O),
+    **_attention("attention_gqa_backward", _GQA, _QKV + _B + _G + _DQ + _DK + _DV + _DB),
+    **_attention("attention_gqa_lse", _GQA, _QKV + _B + _O + _L),
+    **_attention("attention_gqa_lse_16", _GQA + _TYPE, _QKV + _B + _O + _TYPE + _L),
     "spmv_hip_attention_merge": (C.c_int, [spmv_Handle_t, C.c_int, C.c_int, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong,
                                            _V, C.c_longlong, _V, C.c_longlong]),
     "spmv_hip_time_attention_merge_launches": (C.c_double, [spmv_Handle_t, C.c_int, C.c_int, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong,
                                                             _V, C.c_longlong, _V, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_float)]),
-    "spmv_hip_attention_gqa_backward_lse": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong,
-                                                      _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong,
-                                                      _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong]),
-    "spmv_hip_time_attention_gqa_backward_lse_launches": (C.c_double, [spmv_Handle_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _V, C.c_longlong, _V, C.c_longlong,
-                                                                       _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong,
-                                                                       _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, C.c_int, C.c_int,
-                                                                       C.POINTER(C.c_float)]),
-    "spmv_hip_attention_gqa_backward_16": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _V, C.c_longlong, _V, C.c_longlong,
-                                                     _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, C.c_int, _V, C.c_longlong,
-                                                     C.c_int, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong]),
-    "spmv_hip_time_attention_gqa_backward_16_launches": (C.c_double, [spmv_Handle_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _V, C.c_longlong, _V, C.c_longlong,
-                                                                      _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, C.c_int, _V,
-                                                                      C.c_longlong, C.c_int, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, C.c_int, C.c_int,
-                                                                      C.POINTER(C.c_float)]),
+    **_attention("attention_gqa_backward_lse", _GQA, _QKV + _B + _G + _O + _L + _DQ + _DK + _DV + _DB),
+    **_attention("attention_gqa_backward_16", _GQA + _TYPE, _QKV + _B + _G + _O + _L + _TYPE + _DQ + _TYPE + _DK + _DV + _DB),
     "spmv_hip_cg": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, _V, _V, C.POINTER(spmv_hip_cg_options), C.POINTER(spmv_hip_cg_result)]),
     "spmv_hip_time_cg_iterations": (C.c_double, [spmv_Handle_t, _V, _V, C.POINTER(spmv_hip_cg_options), C.c_int, C.c_int, C.POINTER(C.c_float)]),
     # include/spmv_io.h (host only)

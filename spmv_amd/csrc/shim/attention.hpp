@@ -1,9 +1,9 @@
-// shim/attention.hpp -- part of spmv_shim.hip: O = softmax_rows(scale * Q K^T on the RESIDENT pattern) V in one pass, for one head
-// (spmv_hip_attention) or for `heads` heads stored side by side in the rows of Q, K, V and O (spmv_hip_attention_heads), with an additive
-// bias per head and entry (spmv_hip_attention_bias) and with fewer K / V heads than query heads (spmv_hip_attention_gqa: the one entry point
-// the others call, with a K / V head per query head and, where they have none, no bias).  The
-// kernels are kernels/attention.hpp, launched from their own translation unit (spmv_attention.hip, attention_launch); the tables are spmm's
-// batch table and long-row list (spmm_plan).  This side adds what the long rows need: where each one parks its scores.
+// shim/attention.hpp -- part of spmv_shim.hip: O = softmax_rows(scale * Q K^T on the RESIDENT pattern) V in one pass.  One entry point,
+// spmv_shim_attention, and its timer serve every public variant -- one head, `heads` heads side by side in the rows, an additive bias per head and
+// entry, fewer K / V heads than query heads, the rows' log-sum-exps, 16-bit operands: spmv_api.c passes them all as one spmv_attention_call
+// (spmv_shim.h), a variant without a feature with that feature's neutral value.  The merge of two partial results is here too.  The
+// kernels are kernels/attention.hpp, launched from their own translation units (spmv_attention.hip, attention_launch; spmv_attention_16.hip); the
+// tables are spmm's batch table and long-row list (spmm_plan).  This side adds what the long rows need: where each one parks its scores.
 #pragma once
 
 // long_off[i] = first element of long row i of spmm's list in att_park (sum of the long rows' lengths elements): built once per resident matrix
@@ -57,30 +57,34 @@ static int attention_stage_bias(Stager &stg, StageBuf &b, const void *&bias, lon
     return rc;
 }
 
-// k and dv are one head's widths: Q is heads * k columns wide and O heads * dv; K is kv_heads * k and V kv_heads * dv wide, heads a multiple of
-// kv_heads, and query head h reads K / V block h / (heads / kv_heads) (spmv_hip_attention_gqa; kv_heads = heads: a block per head).  bias: NULL,
-// or the planes of spmv_hip_attention_bias, one per QUERY head (ldb = 0: one plane for all heads; else >= nnz); with NULL, ldb is ignored.
-// lse: NULL, or `heads` planes ldl >= m apart that get the rows' log-sum-exps (spmv_hip_attention_gqa_lse); with NULL, ldl is ignored and the
-// launches are those of spmv_hip_attention_gqa.
-// io_type / o_type (SPMV_HIP_T_*): 0, 0 -- every operand in the handle's precision, the kernels of spmv_attention.hip.  io_type F16 or BF16
-// (spmv_hip_attention_gqa_lse_16; a float handle): q, kk and v hold that type and o holds it too (o_type = io_type) or float (o_type = 0); ldq, ldk,
-// ldv and ldo count elements of the operand's own type, a host operand is staged at its own element size, bias and lse stay float, and the
-// kernels are those of spmv_attention_16.hip.  The types are the entry points' to check (spmv_shim_attention_gqa_lse_16); here they are taken as they come.
-static int attention_gqa_lse_any(spmv_dev *d, int heads, int kv_heads, int k, int dv, double scale, int io_type, const void *q, long long ldq, const void *kk, long long ldk,
-                                 const void *v, long long ldv, const void *bias, long long ldb, void *o, long long ldo, int o_type, void *lse, long long ldl)
+// The one place of the type rules on this side (spmv_api.c states them ahead of its gate from the public handle's data_size), for the forward (one
+// output type, out2 = out1) and the backward: io_type HANDLE is the handle-precision path and has no other output type; F16 or BF16 needs a float
+// handle and output types HANDLE or io_type.
+static bool attention_types_ok(const spmv_dev *d, int io_type, int out1, int out2)
 {
+    if (io_type == SPMV_HIP_T_HANDLE) return out1 == SPMV_HIP_T_HANDLE && out2 == SPMV_HIP_T_HANDLE;
+    return (io_type == SPMV_HIP_T_F16 || io_type == SPMV_HIP_T_BF16) && (out1 == SPMV_HIP_T_HANDLE || out1 == io_type) && (out2 == SPMV_HIP_T_HANDLE || out2 == io_type) &&
+           (!d || d->vsize == sizeof(float));
+}
+
+// The operands: spmv_attention_call (spmv_shim.h).  With lse NULL the launches are those without a log-sum-exp.  io_type HANDLE: the kernels of
+// spmv_attention.hip; F16 or BF16: a host operand is staged at its own element size, and the kernels are those of spmv_attention_16.hip.
+extern "C" int spmv_shim_attention(spmv_dev *d, const spmv_attention_call *c)
+{
+    const int heads = c->heads, kv_heads = c->kv_heads, k = c->k, dv = c->dv, io_type = c->io_type, o_type = c->o_type;
+    if (!attention_types_ok(d, io_type, o_type, o_type))
+        return fail(SPMV_HIP_E_ARG, "attention: 16-bit operands need a float handle, io_type F16 or BF16 and o_type HANDLE or io_type (io_type = %d, o_type = %d)", io_type, o_type);
     if (!d || !d->built) return fail(SPMV_HIP_E_NOSTATE, "attention: schedule not built");
     if (kv_heads < 1 || heads < 1 || heads % kv_heads != 0) return fail(SPMV_HIP_E_ARG, "attention: need kv_heads >= 1 and heads a multiple of it (heads = %d, kv_heads = %d)", heads, kv_heads);
     const long long wk = (long long) heads * k, wv = (long long) heads * dv;
     const long long gk = (long long) kv_heads * k, gv = (long long) kv_heads * dv; // K's and V's widths
-    if (heads < 1 || k < 1 || dv < 1 || wk > INT_MAX || wv > INT_MAX || ldq < wk || ldk < gk || ldv < gv || ldo < wv)
+    if (heads < 1 || k < 1 || dv < 1 || wk > INT_MAX || wv > INT_MAX || c->ldq < wk || c->ldk < gk || c->ldv < gv || c->ldo < wv)
         return fail(SPMV_HIP_E_ARG, "attention: need heads, k, dv >= 1, heads * k and heads * dv within int, ldq >= heads * k, ldk >= kv_heads * k, ldv >= kv_heads * dv, ldo >= heads * dv (heads = %d, kv_heads = %d, k = %d, dv = %d, ld = %lld, %lld, %lld, %lld)",
-                    heads, kv_heads, k, dv, ldq, ldk, ldv, ldo);
-    if (bias && (ldb < 0 || (ldb > 0 && ldb < d->nnz)))
-        return fail(SPMV_HIP_E_ARG, "attention: the bias planes need ldb = 0 (one plane for all heads) or ldb >= nnz (ldb = %lld, nnz = %lld)", ldb, d->nnz);
-    if (lse && ldl < d->m) return fail(SPMV_HIP_E_ARG, "attention: the log-sum-exp planes need ldl >= m (ldl = %lld, m = %d)", ldl, d->m);
-    if (d->nnz == 0) bias = nullptr; // no entry: no bias is read
-    if (d->m > 0 && (!q || !kk || !v || !o)) return fail(SPMV_HIP_E_ARG, "attention: Q, K, V or O is NULL");
+                    heads, kv_heads, k, dv, c->ldq, c->ldk, c->ldv, c->ldo);
+    if (c->bias && (c->ldb < 0 || (c->ldb > 0 && c->ldb < d->nnz)))
+        return fail(SPMV_HIP_E_ARG, "attention: the bias planes need ldb = 0 (one plane for all heads) or ldb >= nnz (ldb = %lld, nnz = %lld)", c->ldb, d->nnz);
+    if (c->lse && c->ldl < d->m) return fail(SPMV_HIP_E_ARG, "attention: the log-sum-exp planes need ldl >= m (ldl = %lld, m = %d)", c->ldl, d->m);
+    if (d->m > 0 && (!c->q || !c->kk || !c->v || !c->o)) return fail(SPMV_HIP_E_ARG, "attention: Q, K, V or O is NULL");
     if (d->nnz > 0 && !d->colidx) return fail(SPMV_HIP_E_NOSTATE, "attention: the resident column indices were released (spmv_shim_restore_columns first)");
     if (d->m == 0) return SPMV_HIP_OK;
     DeviceGuard guard(d->device);
@@ -107,13 +111,13 @@ static int attention_gqa_lse_any(spmv_dev *d, int heads, int kv_heads, int k, in
     a.colidx = d->colidx;
     a.long_off = d->att_off;
     a.park = d->att_park;
-    a.scale = scale;
-    a.q = q; a.ldq = ldq;
-    a.kk = kk; a.ldk = ldk;
-    a.v = v; a.ldv = ldv;
-    a.o = o; a.ldo = ldo;
-    a.bias = bias; a.ldb = bias ? ldb : 0;
-    a.lse = lse; a.ldl = lse ? ldl : 0;
+    a.scale = c->scale;
+    a.q = c->q; a.ldq = c->ldq;
+    a.kk = c->kk; a.ldk = c->ldk;
+    a.v = c->v; a.ldv = c->ldv;
+    a.o = c->o; a.ldo = c->ldo;
+    a.bias = d->nnz > 0 ? c->bias : nullptr; a.ldb = a.bias ? c->ldb : 0; // no entry: no bias is read
+    a.lse = c->lse; a.ldl = a.lse ? c->ldl : 0;
     // every row of O gets its heads * dv elements, empty rows their zeros: a staged result is written completely before it is copied back
     if ((rc = stg.in(d->stage[STAGE_ATT_Q], a.q, a.ldq, (size_t) d->m, (int) wk, si)) || (rc = stg.in(d->stage[STAGE_ATT_K], a.kk, a.ldk, (size_t) d->n, (int) gk, si)) ||
         (rc = stg.in(d->stage[STAGE_ATT_V], a.v, a.ldv, (size_t) d->n, (int) gv, si)) || (rc = stg.out(d->stage[STAGE_ATT_O], a.o, a.ldo, (size_t) d->m, (int) wv, so)) ||
@@ -134,26 +138,15 @@ static int attention_gqa_lse_any(spmv_dev *d, int heads, int kv_heads, int k, in
     return stg.finish();
 }
 
-extern "C" int spmv_shim_attention_gqa_lse(spmv_dev *d, int heads, int kv_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
-                                           const void *v, long long ldv, const void *bias, long long ldb, void *o, long long ldo, void *lse, long long ldl)
+// one timer preamble: what is given must be a device pointer, and Q, K, V and O must be given (is_device_ptr(NULL) is false)
+extern "C" double spmv_shim_time_attention(spmv_dev *d, const spmv_attention_call *c, int warmup, int iters, float *ms_out)
 {
-    return attention_gqa_lse_any(d, heads, kv_heads, k, dv, scale, SPMV_HIP_T_HANDLE, q, ldq, kk, ldk, v, ldv, bias, ldb, o, ldo, SPMV_HIP_T_HANDLE, lse, ldl);
-}
-
-extern "C" int spmv_shim_attention_gqa_lse_16(spmv_dev *d, int heads, int kv_heads, int k, int dv, double scale, int io_type, const void *q, long long ldq, const void *kk,
-                                              long long ldk, const void *v, long long ldv, const void *bias, long long ldb, void *o, long long ldo, int o_type, void *lse,
-                                              long long ldl)
-{
-    // the one place of the type rules on this side (spmv_api.c states them ahead of its gate from the public handle's data_size)
-    if ((io_type != SPMV_HIP_T_F16 && io_type != SPMV_HIP_T_BF16) || (o_type != SPMV_HIP_T_HANDLE && o_type != io_type) || (d && d->vsize != sizeof(float)))
-        return fail(SPMV_HIP_E_ARG, "attention: 16-bit operands need a float handle, io_type F16 or BF16 and o_type HANDLE or io_type (io_type = %d, o_type = %d)", io_type, o_type);
-    return attention_gqa_lse_any(d, heads, kv_heads, k, dv, scale, io_type, q, ldq, kk, ldk, v, ldv, bias, ldb, o, ldo, o_type, lse, ldl);
-}
-
-extern "C" int spmv_shim_attention_gqa(spmv_dev *d, int heads, int kv_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
-                                       const void *v, long long ldv, const void *bias, long long ldb, void *o, long long ldo)
-{
-    return spmv_shim_attention_gqa_lse(d, heads, kv_heads, k, dv, scale, q, ldq, kk, ldk, v, ldv, bias, ldb, o, ldo, nullptr, 0);
+    if (!d || !d->built || iters <= 0) { fail(SPMV_HIP_E_ARG, "time_attention: bad arguments"); return -1.0; }
+    if (!is_device_ptr(c->q) || !is_device_ptr(c->kk) || !is_device_ptr(c->v) || !is_device_ptr(c->o) || (c->bias && !is_device_ptr(c->bias)) || (c->lse && !is_device_ptr(c->lse))) {
+        fail(SPMV_HIP_E_ARG, "time_attention: Q, K, V, O, the bias and L must be device pointers");
+        return -1.0;
+    }
+    return time_events(d, "time_attention", warmup, iters, ms_out, [&] { return spmv_shim_attention(d, c); });
 }
 
 // O and L of two partial results merged by their log-sum-exps (spmv_hip_attention_merge; kernels/attention_merge.hpp): the matrix is not read,
@@ -197,61 +190,6 @@ extern "C" int spmv_shim_attention_merge(spmv_dev *d, int heads, int dv, const v
     return stg.finish();
 }
 
-extern "C" int spmv_shim_attention_bias(spmv_dev *d, int heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v,
-                                        long long ldv, const void *bias, long long ldb, void *o, long long ldo)
-{
-    return spmv_shim_attention_gqa(d, heads, heads, k, dv, scale, q, ldq, kk, ldk, v, ldv, bias, ldb, o, ldo);
-}
-
-extern "C" int spmv_shim_attention_heads(spmv_dev *d, int heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v,
-                                         long long ldv, void *o, long long ldo)
-{
-    return spmv_shim_attention_bias(d, heads, k, dv, scale, q, ldq, kk, ldk, v, ldv, nullptr, 0, o, ldo);
-}
-
-extern "C" int spmv_shim_attention(spmv_dev *d, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v, long long ldv, void *o,
-                                   long long ldo)
-{
-    return spmv_shim_attention_heads(d, 1, k, dv, scale, q, ldq, kk, ldk, v, ldv, o, ldo);
-}
-
-extern "C" double spmv_shim_time_attention_gqa(spmv_dev *d, int heads, int kv_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
-                                               const void *v, long long ldv, const void *bias, long long ldb, void *o, long long ldo, int warmup, int iters, float *ms_out)
-{
-    if (!d || !d->built || iters <= 0) { fail(SPMV_HIP_E_ARG, "time_attention: bad arguments"); return -1.0; }
-    if (!is_device_ptr(q) || !is_device_ptr(kk) || !is_device_ptr(v) || !is_device_ptr(o) || (bias && !is_device_ptr(bias))) {
-        fail(SPMV_HIP_E_ARG, "time_attention: Q, K, V, O and the bias must be device pointers");
-        return -1.0;
-    }
-    return time_events(d, "time_attention", warmup, iters, ms_out, [&] { return spmv_shim_attention_gqa(d, heads, kv_heads, k, dv, scale, q, ldq, kk, ldk, v, ldv, bias, ldb, o, ldo); });
-}
-
-extern "C" double spmv_shim_time_attention_gqa_lse(spmv_dev *d, int heads, int kv_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
-                                                   const void *v, long long ldv, const void *bias, long long ldb, void *o, long long ldo, void *lse, long long ldl, int warmup,
-                                                   int iters, float *ms_out)
-{
-    if (!d || !d->built || iters <= 0) { fail(SPMV_HIP_E_ARG, "time_attention: bad arguments"); return -1.0; }
-    if (!is_device_ptr(q) || !is_device_ptr(kk) || !is_device_ptr(v) || !is_device_ptr(o) || (bias && !is_device_ptr(bias)) || (lse && !is_device_ptr(lse))) {
-        fail(SPMV_HIP_E_ARG, "time_attention: Q, K, V, O, the bias and L must be device pointers");
-        return -1.0;
-    }
-    return time_events(d, "time_attention", warmup, iters, ms_out,
-                       [&] { return spmv_shim_attention_gqa_lse(d, heads, kv_heads, k, dv, scale, q, ldq, kk, ldk, v, ldv, bias, ldb, o, ldo, lse, ldl); });
-}
-
-extern "C" double spmv_shim_time_attention_gqa_lse_16(spmv_dev *d, int heads, int kv_heads, int k, int dv, double scale, int io_type, const void *q, long long ldq, const void *kk,
-                                                      long long ldk, const void *v, long long ldv, const void *bias, long long ldb, void *o, long long ldo, int o_type,
-                                                      void *lse, long long ldl, int warmup, int iters, float *ms_out)
-{
-    if (!d || !d->built || iters <= 0) { fail(SPMV_HIP_E_ARG, "time_attention: bad arguments"); return -1.0; }
-    if (!is_device_ptr(q) || !is_device_ptr(kk) || !is_device_ptr(v) || !is_device_ptr(o) || (bias && !is_device_ptr(bias)) || (lse && !is_device_ptr(lse))) {
-        fail(SPMV_HIP_E_ARG, "time_attention: Q, K, V, O, the bias and L must be device pointers");
-        return -1.0;
-    }
-    return time_events(d, "time_attention", warmup, iters, ms_out,
-                       [&] { return spmv_shim_attention_gqa_lse_16(d, heads, kv_heads, k, dv, scale, io_type, q, ldq, kk, ldk, v, ldv, bias, ldb, o, ldo, o_type, lse, ldl); });
-}
-
 extern "C" double spmv_shim_time_attention_merge(spmv_dev *d, int heads, int dv, const void *o1, long long ldo1, const void *l1, long long ldl1, const void *o2, long long ldo2,
                                                  const void *l2, long long ldl2, void *o, long long ldo, void *l, long long ldl, int warmup, int iters, float *ms_out)
 {
@@ -264,20 +202,3 @@ extern "C" double spmv_shim_time_attention_merge(spmv_dev *d, int heads, int dv,
                        [&] { return spmv_shim_attention_merge(d, heads, dv, o1, ldo1, l1, ldl1, o2, ldo2, l2, ldl2, o, ldo, l, ldl); });
 }
 
-extern "C" double spmv_shim_time_attention_bias(spmv_dev *d, int heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v,
-                                                long long ldv, const void *bias, long long ldb, void *o, long long ldo, int warmup, int iters, float *ms_out)
-{
-    return spmv_shim_time_attention_gqa(d, heads, heads, k, dv, scale, q, ldq, kk, ldk, v, ldv, bias, ldb, o, ldo, warmup, iters, ms_out);
-}
-
-extern "C" double spmv_shim_time_attention_heads(spmv_dev *d, int heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v,
-                                                 long long ldv, void *o, long long ldo, int warmup, int iters, float *ms_out)
-{
-    return spmv_shim_time_attention_bias(d, heads, k, dv, scale, q, ldq, kk, ldk, v, ldv, nullptr, 0, o, ldo, warmup, iters, ms_out);
-}
-
-extern "C" double spmv_shim_time_attention(spmv_dev *d, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v, long long ldv,
-                                           void *o, long long ldo, int warmup, int iters, float *ms_out)
-{
-    return spmv_shim_time_attention_heads(d, 1, k, dv, scale, q, ldq, kk, ldk, v, ldv, o, ldo, warmup, iters, ms_out);
-}

@@ -1,7 +1,8 @@
-// shim/attention_backward.hpp -- part of spmv_shim.hip: dQ, dK, dV of O = softmax_rows(scale * Q K^T on the RESIDENT pattern) V in two passes,
-// for one head (spmv_hip_attention_backward) or for `heads` heads stored side by side in the rows (spmv_hip_attention_heads_backward: two
-// passes per round of up to hg heads).  The kernels are kernels/attention_backward.hpp, launched from their own translation unit
-// (spmv_attention_backward.hip, attention_backward_launch); the tables are spmm's batch table and long-row list of the resident matrix
+// shim/attention_backward.hpp -- part of spmv_shim.hip: dQ, dK, dV and dB of O = softmax_rows(scale * Q K^T on the RESIDENT pattern) V in two
+// passes per round of up to hg heads.  One entry point, spmv_shim_attention_backward, and its timer serve every public variant (one head, heads,
+// bias, GQA, driven by the final O and log-sum-exp, 16-bit operands): spmv_api.c passes them all as one spmv_attention_backward_call (spmv_shim.h).
+// The kernels are kernels/attention_backward.hpp, launched from their own translation units (spmv_attention_backward.hip,
+// attention_backward_launch; spmv_attention_backward_16.hip); the tables are spmm's batch table and long-row list of the resident matrix
 // and, when dK or dV is wanted, those of the attached transpose.  This side adds the two nnz-sized arrays the passes share.
 #pragma once
 
@@ -49,54 +50,49 @@ static int attention_backward_group(const spmv_dev *d, int heads, int limit, int
     return hg >= gs ? hg - hg % gs : hg;
 }
 
-// k and dv are one head's widths: Q, K, dq, dk are heads * k columns wide, V, G, dvo heads * dv.  dq / dk / dvo: NULL = not wanted.  When dk or
-// dvo is wanted the transpose must be attached with its column indices resident (spmv_shim_transpose, spmv_shim_transpose_restore_columns);
-// its values are not read.  max_heads: option "attention_backward_heads" (0 = by the memory rule).  bias: NULL or the forward call's planes
-// (ldb = 0: one plane for all heads; else >= nnz); db: NULL = not wanted, else `heads` planes lddb >= nnz apart, written by the row pass alone --
-// with only db wanted the column pass does not run and the transpose is not looked at.  With bias and db NULL this is
-// spmv_shim_attention_heads_backward.  kv_heads: K, V, dk and dvo are kv_heads * k / kv_heads * dv wide, heads a multiple of kv_heads, query head
-// h belongs to block h / (heads / kv_heads), and dk / dvo of a block are the sums of its heads' terms in ascending head
-// (spmv_hip_attention_gqa_backward); the planes, bias and db stay per QUERY head.  kv_heads = heads is spmv_hip_attention_bias_backward.
-// stats (spmv_hip_attention_gqa_backward_lse): o (m x heads * dv, ldo) and lse (`heads` planes ldl >= m apart) are the FINAL output and
-// log-sum-exp of the attention this handle's entries are a part of, and the row pass takes P and D from them; else they are not looked at.
-// io_type / dq_type / dkv_type (SPMV_HIP_T_*): 0, 0, 0 -- every operand in the handle's precision, the kernels of spmv_attention_backward.hip.
-// io_type F16 or BF16 (spmv_hip_attention_gqa_backward_16; a float handle): q, kk, v and g hold that type, dq holds it too (dq_type = io_type) or
-// float (0), dk and dvo likewise by dkv_type; leading dimensions count elements of the operand's own type, a host operand is staged at its own
-// element size; bias, db, o and lse stay float, and the kernels are those of spmv_attention_backward_16.hip.  With kv_heads < heads a 16-bit dk /
-// dvo is summed in the handle's float arrays attb_nk / attb_nv (n x kv_heads * k, n x kv_heads * dv; allocated at the first such call, grown when
-// a call needs more, counted in device_bytes) and rounded once into the caller's arrays by the call's last launch.  The types are the entry
-// point's to check (spmv_shim_attention_gqa_backward_16); here they are taken as they come.
-static int attention_gqa_backward_impl(spmv_dev *d, int heads, int kv_heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
-                                       const void *v, long long ldv, const void *bias, long long ldb, const void *g, long long ldg, void *dq, long long lddq, void *dk,
-                                       long long lddk, void *dvo, long long lddv, void *db, long long lddb, bool stats, const void *o, long long ldo, const void *lse,
-                                       long long ldl, int io_type = SPMV_HIP_T_HANDLE, int dq_type = SPMV_HIP_T_HANDLE, int dkv_type = SPMV_HIP_T_HANDLE)
+// The operands: spmv_attention_backward_call (spmv_shim.h).  When dk or dvo is wanted the transpose must be attached with its column indices
+// resident (spmv_shim_transpose, spmv_shim_transpose_restore_columns); its values are not read.  db is written by the row pass alone: with only db
+// wanted the column pass does not run and the transpose is not looked at.  The planes, bias and db are per QUERY head.
+// io_type HANDLE: the kernels of spmv_attention_backward.hip.  F16 or BF16: a host operand is staged at its own element size and the kernels are
+// those of spmv_attention_backward_16.hip; with kv_heads < heads a 16-bit dk / dvo is summed in the handle's float arrays attb_nk / attb_nv
+// (n x kv_heads * k, n x kv_heads * dv; allocated at the first such call, grown when a call needs more, counted in device_bytes) and rounded once
+// into the caller's arrays by the call's last launch.
+extern "C" int spmv_shim_attention_backward(spmv_dev *d, const spmv_attention_backward_call *c)
 {
+    const int heads = c->heads, kv_heads = c->kv_heads, k = c->k, dv = c->dv, io_type = c->io_type, dq_type = c->dq_type, dkv_type = c->dkv_type;
+    if (!attention_types_ok(d, io_type, dq_type, dkv_type))
+        return fail(SPMV_HIP_E_ARG, "attention_backward: 16-bit operands need a float handle, io_type F16 or BF16 and dq_type, dkv_type HANDLE or io_type (io_type = %d, dq_type = %d, dkv_type = %d)",
+                    io_type, dq_type, dkv_type);
+    if (io_type != SPMV_HIP_T_HANDLE && d && d->m > 0 && (c->o == nullptr) != (c->lse == nullptr))
+        return fail(SPMV_HIP_E_ARG, "attention_backward: O and L are given together or not at all");
+    const bool stats = c->stats != 0; // else o and lse are not looked at
+    const void *o = stats ? c->o : nullptr, *lse = stats ? c->lse : nullptr;
     if (!d || !d->built) return fail(SPMV_HIP_E_NOSTATE, "attention_backward: schedule not built");
     if (kv_heads < 1 || heads < 1 || heads % kv_heads != 0)
         return fail(SPMV_HIP_E_ARG, "attention_backward: need kv_heads >= 1 and heads a multiple of it (heads = %d, kv_heads = %d)", heads, kv_heads);
     const long long wk = (long long) heads * k, wv = (long long) heads * dv;
     const long long gk = (long long) kv_heads * k, gv = (long long) kv_heads * dv; // the widths of K and dK, of V and dV
-    if (heads < 1 || k < 1 || dv < 1 || wk > INT_MAX || wv > INT_MAX || max_heads < 0 || ldq < wk || ldk < gk || ldv < gv || ldg < wv || (dq && lddq < wk) || (dk && lddk < gk) ||
-        (dvo && lddv < gv))
+    if (heads < 1 || k < 1 || dv < 1 || wk > INT_MAX || wv > INT_MAX || c->max_heads < 0 || c->ldq < wk || c->ldk < gk || c->ldv < gv || c->ldg < wv || (c->dq && c->lddq < wk) ||
+        (c->dk && c->lddk < gk) || (c->dvo && c->lddv < gv))
         return fail(SPMV_HIP_E_ARG, "attention_backward: need heads, k, dv >= 1, heads * k and heads * dv within int, ldq >= heads * k, ldk >= kv_heads * k, ldv >= kv_heads * dv, ldg >= heads * dv, lddq >= heads * k, lddk >= kv_heads * k, lddv >= kv_heads * dv (heads = %d, kv_heads = %d, k = %d, dv = %d)",
                     heads, kv_heads, k, dv);
-    if (d->m > 0 && (!q || !kk || !v || !g)) return fail(SPMV_HIP_E_ARG, "attention_backward: Q, K, V or G is NULL");
-    if (stats && ((d->m > 0 && (!o || !lse)) || ldo < wv || ldl < d->m))
-        return fail(SPMV_HIP_E_ARG, "attention_backward: the final O and L are needed, with ldo >= heads * dv and ldl >= m (ldo = %lld, ldl = %lld, m = %d)", ldo, ldl, d->m);
-    if ((bias && (ldb < 0 || (ldb > 0 && ldb < d->nnz))) || (db && lddb < d->nnz))
+    if (d->m > 0 && (!c->q || !c->kk || !c->v || !c->g)) return fail(SPMV_HIP_E_ARG, "attention_backward: Q, K, V or G is NULL");
+    if (stats && ((d->m > 0 && (!o || !lse)) || c->ldo < wv || c->ldl < d->m))
+        return fail(SPMV_HIP_E_ARG, "attention_backward: the final O and L are needed, with ldo >= heads * dv and ldl >= m (ldo = %lld, ldl = %lld, m = %d)", c->ldo, c->ldl, d->m);
+    if ((c->bias && (c->ldb < 0 || (c->ldb > 0 && c->ldb < d->nnz))) || (c->db && c->lddb < d->nnz))
         return fail(SPMV_HIP_E_ARG, "attention_backward: the bias planes need ldb = 0 (one plane for all heads) or ldb >= nnz, those of dB lddb >= nnz (ldb = %lld, lddb = %lld, nnz = %lld)",
-                    ldb, lddb, d->nnz);
-    if (!dq && !dk && !dvo && !db) return SPMV_HIP_OK;
-    if (d->nnz == 0) { bias = nullptr; db = nullptr; } // no entry: no bias is read, dB has no element
+                    c->ldb, c->lddb, d->nnz);
+    if (!c->dq && !c->dk && !c->dvo && !c->db) return SPMV_HIP_OK;
     if (d->nnz > 0 && !d->colidx) return fail(SPMV_HIP_E_NOSTATE, "attention_backward: the resident column indices were released (spmv_shim_restore_columns first)");
-    const bool cols = (dk || dvo) && d->n > 0;
+    void *const db = d->nnz > 0 ? c->db : nullptr; // no entry: dB has no element
+    const bool cols = (c->dk || c->dvo) && d->n > 0;
     spmv_dev *t = d->tr;
     if (cols && (!t || !d->tr_perm || (t->nnz > 0 && !t->colidx))) return fail(SPMV_HIP_E_NOSTATE, "attention_backward: the transpose is not attached with its column indices");
-    if ((d->m == 0 || (!dq && !db)) && !cols) return SPMV_HIP_OK;
+    if ((d->m == 0 || (!c->dq && !db)) && !cols) return SPMV_HIP_OK;
     DeviceGuard guard(d->device);
     if (!guard.ok) return fail(SPMV_HIP_E_RUNTIME, "hipSetDevice(%d) failed", d->device);
     int rc;
-    const int hg = attention_backward_group(d, heads, max_heads, heads / kv_heads);
+    const int hg = attention_backward_group(d, heads, c->max_heads, heads / kv_heads);
     if ((rc = spmm_plan(d)) || (rc = attention_backward_plan(d, hg)) || (cols && (rc = spmm_plan(t)))) return rc;
     const size_t s = d->vsize;
     const size_t si = io_type ? 2 : s, sq = dq_type ? 2 : s, so = dkv_type ? 2 : s; // element sizes of Q / K / V / G, of dQ and of dK / dV
@@ -133,17 +129,17 @@ static int attention_gqa_backward_impl(spmv_dev *d, int heads, int kv_heads, int
     }
     a.p = d->attb_p;
     a.ds = d->attb_ds;
-    a.scale = scale;
-    a.q = q; a.ldq = ldq;
-    a.kk = kk; a.ldk = ldk;
-    a.v = v; a.ldv = ldv;
-    a.g = g; a.ldg = ldg;
-    a.dq = d->m > 0 ? dq : nullptr; a.lddq = lddq;
-    a.dk = cols ? dk : nullptr; a.lddk = lddk;
-    a.dvo = cols ? dvo : nullptr; a.lddv = lddv;
-    a.bias = bias; a.ldb = bias ? ldb : 0;
-    a.db = db; a.lddb = lddb;
-    if (stats && d->m > 0) { a.o = o; a.ldo = ldo; a.lse = lse; a.ldl = ldl; }
+    a.scale = c->scale;
+    a.q = c->q; a.ldq = c->ldq;
+    a.kk = c->kk; a.ldk = c->ldk;
+    a.v = c->v; a.ldv = c->ldv;
+    a.g = c->g; a.ldg = c->ldg;
+    a.dq = d->m > 0 ? c->dq : nullptr; a.lddq = c->lddq;
+    a.dk = cols ? c->dk : nullptr; a.lddk = c->lddk;
+    a.dvo = cols ? c->dvo : nullptr; a.lddv = c->lddv;
+    a.bias = d->nnz > 0 ? c->bias : nullptr; a.ldb = a.bias ? c->ldb : 0; // no entry: no bias is read
+    a.db = db; a.lddb = c->lddb;
+    if (stats && d->m > 0) { a.o = o; a.ldo = c->ldo; a.lse = lse; a.ldl = c->ldl; }
     // every row of a wanted output gets its elements, empty rows and columns their zeros: a staged result is written completely before it is copied back
     if ((rc = stg.in(d->stage[STAGE_ATTB_Q], a.q, a.ldq, (size_t) d->m, (int) wk, si)) || (rc = stg.in(d->stage[STAGE_ATTB_K], a.kk, a.ldk, (size_t) d->n, (int) gk, si)) ||
         (rc = stg.in(d->stage[STAGE_ATTB_V], a.v, a.ldv, (size_t) d->n, (int) gv, si)) || (rc = stg.in(d->stage[STAGE_ATTB_G], a.g, a.ldg, (size_t) d->m, (int) wv, si)) ||
@@ -186,131 +182,16 @@ static int attention_gqa_backward_impl(spmv_dev *d, int heads, int kv_heads, int
     return stg.finish();
 }
 
-extern "C" int spmv_shim_attention_gqa_backward(spmv_dev *d, int heads, int kv_heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
-                                                 const void *v, long long ldv, const void *bias, long long ldb, const void *g, long long ldg, void *dq, long long lddq, void *dk,
-                                                 long long lddk, void *dvo, long long lddv, void *db, long long lddb)
-{
-    return attention_gqa_backward_impl(d, heads, kv_heads, max_heads, k, dv, scale, q, ldq, kk, ldk, v, ldv, bias, ldb, g, ldg, dq, lddq, dk, lddk, dvo, lddv, db, lddb, false, nullptr,
-                                       0, nullptr, 0);
-}
-
-extern "C" int spmv_shim_attention_gqa_backward_lse(spmv_dev *d, int heads, int kv_heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk,
-                                                     long long ldk, const void *v, long long ldv, const void *bias, long long ldb, const void *g, long long ldg, const void *o,
-                                                     long long ldo, const void *lse, long long ldl, void *dq, long long lddq, void *dk, long long lddk, void *dvo, long long lddv,
-                                                     void *db, long long lddb)
-{
-    return attention_gqa_backward_impl(d, heads, kv_heads, max_heads, k, dv, scale, q, ldq, kk, ldk, v, ldv, bias, ldb, g, ldg, dq, lddq, dk, lddk, dvo, lddv, db, lddb, true, o, ldo, lse,
-                                       ldl);
-}
-
-// the one place of the type rules on this side (spmv_api.c states them ahead of its gate from the public handle's data_size).  o and lse both NULL:
-// the self-normalising row pass; both given: the one driven by them; one of the two while m > 0: SPMV_HIP_E_ARG
-extern "C" int spmv_shim_attention_gqa_backward_16(spmv_dev *d, int heads, int kv_heads, int max_heads, int k, int dv, double scale, int io_type, const void *q, long long ldq,
-                                                    const void *kk, long long ldk, const void *v, long long ldv, const void *bias, long long ldb, const void *g, long long ldg,
-                                                    const void *o, long long ldo, const void *lse, long long ldl, int dq_type, void *dq, long long lddq, int dkv_type, void *dk,
-                                                    long long lddk, void *dvo, long long lddv, void *db, long long lddb)
-{
-    if ((io_type != SPMV_HIP_T_F16 && io_type != SPMV_HIP_T_BF16) || (dq_type != SPMV_HIP_T_HANDLE && dq_type != io_type) ||
-        (dkv_type != SPMV_HIP_T_HANDLE && dkv_type != io_type) || (d && d->vsize != sizeof(float)))
-        return fail(SPMV_HIP_E_ARG, "attention_backward: 16-bit operands need a float handle, io_type F16 or BF16 and dq_type, dkv_type HANDLE or io_type (io_type = %d, dq_type = %d, dkv_type = %d)",
-                    io_type, dq_type, dkv_type);
-    if (d && d->m > 0 && (o == nullptr) != (lse == nullptr)) return fail(SPMV_HIP_E_ARG, "attention_backward: O and L are given together or not at all");
-    const bool stats = o != nullptr && lse != nullptr;
-    return attention_gqa_backward_impl(d, heads, kv_heads, max_heads, k, dv, scale, q, ldq, kk, ldk, v, ldv, bias, ldb, g, ldg, dq, lddq, dk, lddk, dvo, lddv, db, lddb, stats,
-                                       stats ? o : nullptr, ldo, stats ? lse : nullptr, ldl, io_type, dq_type, dkv_type);
-}
-
-extern "C" double spmv_shim_time_attention_gqa_backward_16(spmv_dev *d, int heads, int kv_heads, int max_heads, int k, int dv, double scale, int io_type, const void *q, long long ldq,
-                                                            const void *kk, long long ldk, const void *v, long long ldv, const void *bias, long long ldb, const void *g,
-                                                            long long ldg, const void *o, long long ldo, const void *lse, long long ldl, int dq_type, void *dq, long long lddq,
-                                                            int dkv_type, void *dk, long long lddk, void *dvo, long long lddv, void *db, long long lddb, int warmup, int iters,
-                                                            float *ms_out)
+// one timer preamble: what is given must be a device pointer, and Q, K, V, G and -- when they drive the row pass -- O and L must be given
+// (is_device_ptr(NULL) is false)
+extern "C" double spmv_shim_time_attention_backward(spmv_dev *d, const spmv_attention_backward_call *c, int warmup, int iters, float *ms_out)
 {
     if (!d || !d->built || iters <= 0) { fail(SPMV_HIP_E_ARG, "time_attention_backward: bad arguments"); return -1.0; }
-    if (!is_device_ptr(q) || !is_device_ptr(kk) || !is_device_ptr(v) || !is_device_ptr(g) || (o && !is_device_ptr(o)) || (lse && !is_device_ptr(lse)) || (dq && !is_device_ptr(dq)) ||
-        (dk && !is_device_ptr(dk)) || (dvo && !is_device_ptr(dvo)) || (bias && !is_device_ptr(bias)) || (db && !is_device_ptr(db))) {
+    auto dev_or_null = [](const void *p) { return !p || is_device_ptr(p); };
+    if (!is_device_ptr(c->q) || !is_device_ptr(c->kk) || !is_device_ptr(c->v) || !is_device_ptr(c->g) || (c->stats && (!c->o || !c->lse)) || !dev_or_null(c->o) || !dev_or_null(c->lse) ||
+        !dev_or_null(c->bias) || !dev_or_null(c->dq) || !dev_or_null(c->dk) || !dev_or_null(c->dvo) || !dev_or_null(c->db)) {
         fail(SPMV_HIP_E_ARG, "time_attention_backward: Q, K, V, G, O, L, the bias and the outputs must be device pointers");
         return -1.0;
     }
-    return time_events(d, "time_attention_backward", warmup, iters, ms_out, [&] {
-        return spmv_shim_attention_gqa_backward_16(d, heads, kv_heads, max_heads, k, dv, scale, io_type, q, ldq, kk, ldk, v, ldv, bias, ldb, g, ldg, o, ldo, lse, ldl, dq_type, dq, lddq,
-                                                   dkv_type, dk, lddk, dvo, lddv, db, lddb);
-    });
-}
-
-extern "C" double spmv_shim_time_attention_gqa_backward_lse(spmv_dev *d, int heads, int kv_heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq,
-                                                             const void *kk, long long ldk, const void *v, long long ldv, const void *bias, long long ldb, const void *g, long long ldg,
-                                                             const void *o, long long ldo, const void *lse, long long ldl, void *dq, long long lddq, void *dk, long long lddk,
-                                                             void *dvo, long long lddv, void *db, long long lddb, int warmup, int iters, float *ms_out)
-{
-    if (!d || !d->built || iters <= 0) { fail(SPMV_HIP_E_ARG, "time_attention_backward: bad arguments"); return -1.0; }
-    if (!is_device_ptr(q) || !is_device_ptr(kk) || !is_device_ptr(v) || !is_device_ptr(g) || !is_device_ptr(o) || !is_device_ptr(lse) || (dq && !is_device_ptr(dq)) ||
-        (dk && !is_device_ptr(dk)) || (dvo && !is_device_ptr(dvo)) || (bias && !is_device_ptr(bias)) || (db && !is_device_ptr(db))) {
-        fail(SPMV_HIP_E_ARG, "time_attention_backward: Q, K, V, G, O, L, the bias and the outputs must be device pointers");
-        return -1.0;
-    }
-    return time_events(d, "time_attention_backward", warmup, iters, ms_out, [&] {
-        return spmv_shim_attention_gqa_backward_lse(d, heads, kv_heads, max_heads, k, dv, scale, q, ldq, kk, ldk, v, ldv, bias, ldb, g, ldg, o, ldo, lse, ldl, dq, lddq, dk, lddk, dvo,
-                                                    lddv, db, lddb);
-    });
-}
-
-extern "C" int spmv_shim_attention_bias_backward(spmv_dev *d, int heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
-                                                 const void *v, long long ldv, const void *bias, long long ldb, const void *g, long long ldg, void *dq, long long lddq, void *dk,
-                                                 long long lddk, void *dvo, long long lddv, void *db, long long lddb)
-{
-    return spmv_shim_attention_gqa_backward(d, heads, heads, max_heads, k, dv, scale, q, ldq, kk, ldk, v, ldv, bias, ldb, g, ldg, dq, lddq, dk, lddk, dvo, lddv, db, lddb);
-}
-
-extern "C" int spmv_shim_attention_heads_backward(spmv_dev *d, int heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
-                                                  const void *v, long long ldv, const void *g, long long ldg, void *dq, long long lddq, void *dk, long long lddk, void *dvo,
-                                                  long long lddv)
-{
-    return spmv_shim_attention_bias_backward(d, heads, max_heads, k, dv, scale, q, ldq, kk, ldk, v, ldv, nullptr, 0, g, ldg, dq, lddq, dk, lddk, dvo, lddv, nullptr, 0);
-}
-
-extern "C" int spmv_shim_attention_backward(spmv_dev *d, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v,
-                                            long long ldv, const void *g, long long ldg, void *dq, long long lddq, void *dk, long long lddk, void *dvo, long long lddv)
-{
-    return spmv_shim_attention_heads_backward(d, 1, 0, k, dv, scale, q, ldq, kk, ldk, v, ldv, g, ldg, dq, lddq, dk, lddk, dvo, lddv);
-}
-
-extern "C" double spmv_shim_time_attention_gqa_backward(spmv_dev *d, int heads, int kv_heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk,
-                                                         long long ldk, const void *v, long long ldv, const void *bias, long long ldb, const void *g, long long ldg, void *dq,
-                                                         long long lddq, void *dk, long long lddk, void *dvo, long long lddv, void *db, long long lddb, int warmup, int iters,
-                                                         float *ms_out)
-{
-    if (!d || !d->built || iters <= 0) { fail(SPMV_HIP_E_ARG, "time_attention_backward: bad arguments"); return -1.0; }
-    if (!is_device_ptr(q) || !is_device_ptr(kk) || !is_device_ptr(v) || !is_device_ptr(g) || (dq && !is_device_ptr(dq)) || (dk && !is_device_ptr(dk)) || (dvo && !is_device_ptr(dvo)) ||
-        (bias && !is_device_ptr(bias)) || (db && !is_device_ptr(db))) {
-        fail(SPMV_HIP_E_ARG, "time_attention_backward: Q, K, V, G, the bias and the outputs must be device pointers");
-        return -1.0;
-    }
-    return time_events(d, "time_attention_backward", warmup, iters, ms_out, [&] {
-        return spmv_shim_attention_gqa_backward(d, heads, kv_heads, max_heads, k, dv, scale, q, ldq, kk, ldk, v, ldv, bias, ldb, g, ldg, dq, lddq, dk, lddk, dvo, lddv, db, lddb);
-    });
-}
-
-extern "C" double spmv_shim_time_attention_bias_backward(spmv_dev *d, int heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk,
-                                                         long long ldk, const void *v, long long ldv, const void *bias, long long ldb, const void *g, long long ldg, void *dq,
-                                                         long long lddq, void *dk, long long lddk, void *dvo, long long lddv, void *db, long long lddb, int warmup, int iters,
-                                                         float *ms_out)
-{
-    return spmv_shim_time_attention_gqa_backward(d, heads, heads, max_heads, k, dv, scale, q, ldq, kk, ldk, v, ldv, bias, ldb, g, ldg, dq, lddq, dk, lddk, dvo, lddv, db, lddb,
-                                                 warmup, iters, ms_out);
-}
-
-extern "C" double spmv_shim_time_attention_heads_backward(spmv_dev *d, int heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk,
-                                                          long long ldk, const void *v, long long ldv, const void *g, long long ldg, void *dq, long long lddq, void *dk,
-                                                          long long lddk, void *dvo, long long lddv, int warmup, int iters, float *ms_out)
-{
-    return spmv_shim_time_attention_bias_backward(d, heads, max_heads, k, dv, scale, q, ldq, kk, ldk, v, ldv, nullptr, 0, g, ldg, dq, lddq, dk, lddk, dvo, lddv, nullptr, 0, warmup,
-                                                  iters, ms_out);
-}
-
-extern "C" double spmv_shim_time_attention_backward(spmv_dev *d, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v,
-                                                    long long ldv, const void *g, long long ldg, void *dq, long long lddq, void *dk, long long lddk, void *dvo, long long lddv,
-                                                    int warmup, int iters, float *ms_out)
-{
-    return spmv_shim_time_attention_heads_backward(d, 1, 0, k, dv, scale, q, ldq, kk, ldk, v, ldv, g, ldg, dq, lddq, dk, lddk, dvo, lddv, warmup, iters, ms_out);
+    return time_events(d, "time_attention_backward", warmup, iters, ms_out, [&] { return spmv_shim_attention_backward(d, c); });
 }

@@ -1032,14 +1032,51 @@ double spmv_hip_time_row_softmax_launches(spmv_Handle_t h, const void *S, void *
     return report_time(spmv_shim_time_row_softmax(st->dev, S, Out, warmup, iters, ms_out), "time_row_softmax_launches");
 }
 
-/* ---------------------------------------------------------------- O = softmax_rows(scale * Q K^T on A's pattern) V in one pass */
-static int attention_args(spmv_Handle_t h, const char *where, int k, int dv, const void *Q, long long ldq, const void *K, long long ldk, const void *V, long long ldv,
-                          const void *O, long long ldo, int m)
+/* ---------------------------------------------------------------- O = softmax_rows(scale * Q K^T on A's pattern) V in one pass: one path for every variant
+ * An entry point -- one head, `heads` heads side by side, with a bias, with fewer K / V heads (GQA, MQA), with the rows' log-sum-exps, on 16-bit
+ * operands -- fills a spmv_attention_call (spmv_shim.h; what it has no argument for: heads = kv_heads = 1, no bias, no L, the handle's types), names
+ * itself and takes the one path of calls or the one of timers. */
+#define ATTENTION_16 1    /* an entry point with type arguments: the type rules are stated here, from the public handle's data_size */
+#define ATTENTION_TIMER 2 /* a timer: ldl is left to the shim, which knows the handle's m */
+
+/* the argument rules ahead of the gate, in this order: the calls with their m, the timers with m = 1 (the operands are always needed) */
+static int attention_rules(spmv_Handle_t h, const char *where, int flags, const spmv_attention_call *c, BASIC_INT_TYPE m)
 {
+    const long long wk = (long long) c->heads * c->k, wv = (long long) c->heads * c->dv, gk = (long long) c->kv_heads * c->k, gv = (long long) c->kv_heads * c->dv;
     if (!h) return refuse(SPMV_HIP_E_ARG, where, "handle is NULL");
-    if (k < 1 || dv < 1 || ldq < k || ldk < k || ldv < dv || ldo < dv) return refuse(SPMV_HIP_E_ARG, where, "need k >= 1, dv >= 1, ldq >= k, ldk >= k, ldv >= dv and ldo >= dv");
-    if (m > 0 && (!Q || !K || !V || !O)) return refuse(SPMV_HIP_E_ARG, where, "Q, K, V or O is NULL");
+    if (c->heads < 1 || c->kv_heads < 1 || c->k < 1 || c->dv < 1) return refuse(SPMV_HIP_E_ARG, where, "need heads >= 1, kv_heads >= 1, k >= 1 and dv >= 1");
+    if (c->heads % c->kv_heads != 0) return refuse(SPMV_HIP_E_ARG, where, "heads must be a multiple of kv_heads");
+    if (wk > INT_MAX || wv > INT_MAX || gk > INT_MAX || gv > INT_MAX) return refuse(SPMV_HIP_E_ARG, where, "heads * k, heads * dv, kv_heads * k or kv_heads * dv does not fit an int");
+    if (c->ldq < wk || c->ldk < gk || c->ldv < gv || c->ldo < wv)
+        return refuse(SPMV_HIP_E_ARG, where, "need ldq >= heads * k, ldk >= kv_heads * k, ldv >= kv_heads * dv and ldo >= heads * dv");
+    if (m > 0 && (!c->q || !c->kk || !c->v || !c->o)) return refuse(SPMV_HIP_E_ARG, where, "Q, K, V or O is NULL");
+    if (c->bias && c->ldb < 0) return refuse(SPMV_HIP_E_ARG, where, "need ldb >= 0"); /* 0 < ldb < nnz: refused by the shim, nothing written */
+    if (!(flags & ATTENTION_TIMER) && c->lse && c->ldl < (long long) m) return refuse(SPMV_HIP_E_ARG, where, "need ldl >= m");
+    if (flags & ATTENTION_16) {
+        /* data_size is in the public handle, so a handle whose create failed answers the type rules too (a cleared handle holds no precision any
+         * more, data_size 0: it gets as far as the gate and is SPMV_HIP_E_NOSTATE there, like in every other call) */
+        if (h->data_size != sizeof(float) && h->data_size != 0) return refuse(SPMV_HIP_E_ARG, where, "16-bit operands need an fp32 handle");
+        if (c->io_type != SPMV_HIP_T_F16 && c->io_type != SPMV_HIP_T_BF16) return refuse(SPMV_HIP_E_ARG, where, "io_type must be SPMV_HIP_T_F16 or SPMV_HIP_T_BF16");
+        if (c->o_type != SPMV_HIP_T_HANDLE && c->o_type != c->io_type) return refuse(SPMV_HIP_E_ARG, where, "o_type must be SPMV_HIP_T_HANDLE or equal to io_type");
+    }
     return SPMV_HIP_OK;
+}
+
+static int attention_call(spmv_Handle_t h, const char *where, int flags, const spmv_attention_call *c, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr,
+                          const BASIC_INT_TYPE *ColIdx, const void *Matrix_Val)
+{
+    spmv_hip_state *st;
+    int rc;
+    if ((rc = attention_rules(h, where, flags, c, m)) || (rc = resident_prologue(h, where, RESIDENT_NOT_REORDERED, m, RowPtr, ColIdx, Matrix_Val, &st)) ||
+        (rc = spmm_columns(h, st, where))) return rc;
+    return report(spmv_shim_attention(st->dev, c), where);
+}
+
+static double attention_time(spmv_Handle_t h, const char *where, int flags, const spmv_attention_call *c, int warmup, int iters, float *ms_out)
+{
+    spmv_hip_state *st;
+    if (attention_rules(h, where, flags | ATTENTION_TIMER, c, 1) || resident_state(h, where, RESIDENT_NOT_REORDERED, &st) || spmm_columns(h, st, where)) return -1.0;
+    return report_time(spmv_shim_time_attention(st->dev, c, warmup, iters, ms_out), where);
 }
 
 int spmv_hip_attention(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
@@ -1047,33 +1084,15 @@ int spmv_hip_attention(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_T
                        const void *Q, long long ldq, const void *K, long long ldk, const void *V, long long ldv,
                        void *O, long long ldo)
 {
-    spmv_hip_state *st;
-    int rc;
-    if ((rc = attention_args(handle, "attention", k, dv, Q, ldq, K, ldk, V, ldv, O, ldo, m)) ||
-        (rc = resident_prologue(handle, "attention", RESIDENT_NOT_REORDERED, m, RowPtr, ColIdx, Matrix_Val, &st)) || (rc = spmm_columns(handle, st, "attention"))) return rc;
-    return report(spmv_shim_attention(st->dev, k, dv, scale, Q, ldq, K, ldk, V, ldv, O, ldo), "attention");
+    const spmv_attention_call c = {.heads = 1, .kv_heads = 1, .k = k, .dv = dv, .scale = scale, .q = Q, .ldq = ldq, .kk = K, .ldk = ldk, .v = V, .ldv = ldv, .o = O, .ldo = ldo};
+    return attention_call(handle, "attention", 0, &c, m, RowPtr, ColIdx, Matrix_Val);
 }
 
 double spmv_hip_time_attention_launches(spmv_Handle_t h, int k, int dv, double scale, const void *Q, long long ldq, const void *K, long long ldk, const void *V, long long ldv,
                                         void *O, long long ldo, int warmup, int iters, float *ms_out)
 {
-    const char *where = "time_attention_launches";
-    spmv_hip_state *st;
-    if (attention_args(h, where, k, dv, Q, ldq, K, ldk, V, ldv, O, ldo, 1) || resident_state(h, where, RESIDENT_NOT_REORDERED, &st) || spmm_columns(h, st, where)) return -1.0;
-    return report_time(spmv_shim_time_attention(st->dev, k, dv, scale, Q, ldq, K, ldk, V, ldv, O, ldo, warmup, iters, ms_out), where);
-}
-
-/* ---------------------------------------------------------------- the same for `heads` heads stored side by side in the rows of Q, K, V and O */
-static int attention_heads_args(spmv_Handle_t h, const char *where, int heads, int k, int dv, const void *Q, long long ldq, const void *K, long long ldk, const void *V,
-                                long long ldv, const void *O, long long ldo, int m)
-{
-    if (!h) return refuse(SPMV_HIP_E_ARG, where, "handle is NULL");
-    if (heads < 1 || k < 1 || dv < 1) return refuse(SPMV_HIP_E_ARG, where, "need heads >= 1, k >= 1 and dv >= 1");
-    if ((long long) heads * k > INT_MAX || (long long) heads * dv > INT_MAX) return refuse(SPMV_HIP_E_ARG, where, "heads * k or heads * dv does not fit an int");
-    if (ldq < (long long) heads * k || ldk < (long long) heads * k || ldv < (long long) heads * dv || ldo < (long long) heads * dv)
-        return refuse(SPMV_HIP_E_ARG, where, "need ldq >= heads * k, ldk >= heads * k, ldv >= heads * dv and ldo >= heads * dv");
-    if (m > 0 && (!Q || !K || !V || !O)) return refuse(SPMV_HIP_E_ARG, where, "Q, K, V or O is NULL");
-    return SPMV_HIP_OK;
+    const spmv_attention_call c = {.heads = 1, .kv_heads = 1, .k = k, .dv = dv, .scale = scale, .q = Q, .ldq = ldq, .kk = K, .ldk = ldk, .v = V, .ldv = ldv, .o = O, .ldo = ldo};
+    return attention_time(h, "time_attention_launches", 0, &c, warmup, iters, ms_out);
 }
 
 int spmv_hip_attention_heads(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
@@ -1081,186 +1100,35 @@ int spmv_hip_attention_heads(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC
                              const void *Q, long long ldq, const void *K, long long ldk, const void *V, long long ldv,
                              void *O, long long ldo)
 {
-    const char *where = "attention_heads";
-    spmv_hip_state *st;
-    int rc;
-    if ((rc = attention_heads_args(handle, where, heads, k, dv, Q, ldq, K, ldk, V, ldv, O, ldo, m)) ||
-        (rc = resident_prologue(handle, where, RESIDENT_NOT_REORDERED, m, RowPtr, ColIdx, Matrix_Val, &st)) || (rc = spmm_columns(handle, st, where))) return rc;
-    return report(spmv_shim_attention_heads(st->dev, heads, k, dv, scale, Q, ldq, K, ldk, V, ldv, O, ldo), where);
+    const spmv_attention_call c = {.heads = heads, .kv_heads = heads, .k = k, .dv = dv, .scale = scale, .q = Q, .ldq = ldq, .kk = K, .ldk = ldk, .v = V, .ldv = ldv,
+                                   .o = O, .ldo = ldo};
+    return attention_call(handle, "attention_heads", 0, &c, m, RowPtr, ColIdx, Matrix_Val);
 }
 
 double spmv_hip_time_attention_heads_launches(spmv_Handle_t h, int heads, int k, int dv, double scale, const void *Q, long long ldq, const void *K, long long ldk, const void *V,
                                               long long ldv, void *O, long long ldo, int warmup, int iters, float *ms_out)
 {
-    const char *where = "time_attention_heads_launches";
-    spmv_hip_state *st;
-    if (attention_heads_args(h, where, heads, k, dv, Q, ldq, K, ldk, V, ldv, O, ldo, 1) || resident_state(h, where, RESIDENT_NOT_REORDERED, &st) || spmm_columns(h, st, where))
-        return -1.0;
-    return report_time(spmv_shim_time_attention_heads(st->dev, heads, k, dv, scale, Q, ldq, K, ldk, V, ldv, O, ldo, warmup, iters, ms_out), where);
+    const spmv_attention_call c = {.heads = heads, .kv_heads = heads, .k = k, .dv = dv, .scale = scale, .q = Q, .ldq = ldq, .kk = K, .ldk = ldk, .v = V, .ldv = ldv,
+                                   .o = O, .ldo = ldo};
+    return attention_time(h, "time_attention_heads_launches", 0, &c, warmup, iters, ms_out);
 }
 
-/* ---------------------------------------------------------------- dQ, dK, dV of the fused attention in two passes over A */
-static int attention_backward_args(spmv_Handle_t h, const char *where, int k, int dv, const void *Q, long long ldq, const void *K, long long ldk, const void *V,
-                                   long long ldv, const void *G, long long ldg, const void *dQ, long long lddq, const void *dK, long long lddk, const void *dV,
-                                   long long lddv, int m)
-{
-    if (!h) return refuse(SPMV_HIP_E_ARG, where, "handle is NULL");
-    if (k < 1 || dv < 1 || ldq < k || ldk < k || ldv < dv || ldg < dv || (dQ && lddq < k) || (dK && lddk < k) || (dV && lddv < dv))
-        return refuse(SPMV_HIP_E_ARG, where, "need k >= 1, dv >= 1, ldq, ldk >= k, ldv, ldg >= dv and, for the requested outputs, lddq, lddk >= k, lddv >= dv");
-    if (m > 0 && (!Q || !K || !V || !G)) return refuse(SPMV_HIP_E_ARG, where, "Q, K, V or G is NULL");
-    return SPMV_HIP_OK;
-}
-
-/* the tables behind the gate: A's columns and, when dK or dV is wanted, the transpose (its values are not read: no refresh) with its columns */
-static int attention_backward_tables(spmv_Handle_t h, spmv_hip_state *st, const char *where, int cols)
-{
-    int rc = spmm_columns(h, st, where);
-    if (!rc && cols && !(rc = transpose_built(h, st, where))) rc = transpose_columns(st, where);
-    return rc;
-}
-
-int spmv_hip_attention_backward(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
-                                const void *Matrix_Val, int k, int dv, double scale,
-                                const void *Q, long long ldq, const void *K, long long ldk, const void *V, long long ldv,
-                                const void *G, long long ldg, void *dQ, long long lddq, void *dK, long long lddk, void *dV, long long lddv)
-{
-    const char *where = "attention_backward";
-    spmv_hip_state *st;
-    int rc;
-    if ((rc = attention_backward_args(handle, where, k, dv, Q, ldq, K, ldk, V, ldv, G, ldg, dQ, lddq, dK, lddk, dV, lddv, m)) ||
-        (rc = resident_prologue(handle, where, RESIDENT_NOT_REORDERED, m, RowPtr, ColIdx, Matrix_Val, &st))) return rc;
-    if (!dQ && !dK && !dV) return SPMV_HIP_OK;
-    if ((rc = attention_backward_tables(handle, st, where, dK || dV))) return rc;
-    return report(spmv_shim_attention_backward(st->dev, k, dv, scale, Q, ldq, K, ldk, V, ldv, G, ldg, dQ, lddq, dK, lddk, dV, lddv), where);
-}
-
-double spmv_hip_time_attention_backward_launches(spmv_Handle_t h, int k, int dv, double scale, const void *Q, long long ldq, const void *K, long long ldk,
-                                                 const void *V, long long ldv, const void *G, long long ldg, void *dQ, long long lddq, void *dK, long long lddk,
-                                                 void *dV, long long lddv, int warmup, int iters, float *ms_out)
-{
-    const char *where = "time_attention_backward_launches";
-    spmv_hip_state *st;
-    if (attention_backward_args(h, where, k, dv, Q, ldq, K, ldk, V, ldv, G, ldg, dQ, lddq, dK, lddk, dV, lddv, 1) ||
-        resident_state(h, where, RESIDENT_NOT_REORDERED, &st) || attention_backward_tables(h, st, where, dK || dV)) return -1.0;
-    return report_time(spmv_shim_time_attention_backward(st->dev, k, dv, scale, Q, ldq, K, ldk, V, ldv, G, ldg, dQ, lddq, dK, lddk, dV, lddv, warmup, iters, ms_out), where);
-}
-
-/* ---------------------------------------------------------------- the same for `heads` heads side by side: two passes per group of heads */
-static int attention_heads_backward_args(spmv_Handle_t h, const char *where, int heads, int k, int dv, const void *Q, long long ldq, const void *K, long long ldk,
-                                         const void *V, long long ldv, const void *G, long long ldg, const void *dQ, long long lddq, const void *dK, long long lddk,
-                                         const void *dV, long long lddv, int m)
-{
-    long long wk, wv;
-    if (!h) return refuse(SPMV_HIP_E_ARG, where, "handle is NULL");
-    if (heads < 1 || k < 1 || dv < 1) return refuse(SPMV_HIP_E_ARG, where, "need heads >= 1, k >= 1 and dv >= 1");
-    wk = (long long) heads * k;
-    wv = (long long) heads * dv;
-    if (wk > INT_MAX || wv > INT_MAX) return refuse(SPMV_HIP_E_ARG, where, "heads * k or heads * dv does not fit an int");
-    if (ldq < wk || ldk < wk || ldv < wv || ldg < wv || (dQ && lddq < wk) || (dK && lddk < wk) || (dV && lddv < wv))
-        return refuse(SPMV_HIP_E_ARG, where, "need ldq, ldk >= heads * k, ldv, ldg >= heads * dv and, for the requested outputs, lddq, lddk >= heads * k, lddv >= heads * dv");
-    if (m > 0 && (!Q || !K || !V || !G)) return refuse(SPMV_HIP_E_ARG, where, "Q, K, V or G is NULL");
-    return SPMV_HIP_OK;
-}
-
-int spmv_hip_attention_heads_backward(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
-                                      const void *Matrix_Val, int heads, int k, int dv, double scale,
-                                      const void *Q, long long ldq, const void *K, long long ldk, const void *V, long long ldv,
-                                      const void *G, long long ldg, void *dQ, long long lddq, void *dK, long long lddk, void *dV, long long lddv)
-{
-    const char *where = "attention_heads_backward";
-    spmv_hip_state *st;
-    int rc;
-    if ((rc = attention_heads_backward_args(handle, where, heads, k, dv, Q, ldq, K, ldk, V, ldv, G, ldg, dQ, lddq, dK, lddk, dV, lddv, m))) return rc;
-    if (!dQ && !dK && !dV) return SPMV_HIP_OK; /* nothing wanted: no work, the handle's state is not looked at */
-    if ((rc = resident_prologue(handle, where, RESIDENT_NOT_REORDERED, m, RowPtr, ColIdx, Matrix_Val, &st))) return rc;
-    if ((rc = attention_backward_tables(handle, st, where, dK || dV))) return rc;
-    return report(spmv_shim_attention_heads_backward(st->dev, heads, (int) st->opts.v[SPMV_OPT_ATTENTION_BACKWARD_HEADS], k, dv, scale, Q, ldq, K, ldk, V, ldv, G, ldg, dQ, lddq,
-                                                     dK, lddk, dV, lddv), where);
-}
-
-double spmv_hip_time_attention_heads_backward_launches(spmv_Handle_t h, int heads, int k, int dv, double scale, const void *Q, long long ldq, const void *K, long long ldk,
-                                                       const void *V, long long ldv, const void *G, long long ldg, void *dQ, long long lddq, void *dK, long long lddk,
-                                                       void *dV, long long lddv, int warmup, int iters, float *ms_out)
-{
-    const char *where = "time_attention_heads_backward_launches";
-    spmv_hip_state *st;
-    if (attention_heads_backward_args(h, where, heads, k, dv, Q, ldq, K, ldk, V, ldv, G, ldg, dQ, lddq, dK, lddk, dV, lddv, 1) ||
-        resident_state(h, where, RESIDENT_NOT_REORDERED, &st) || attention_backward_tables(h, st, where, dK || dV)) return -1.0;
-    return report_time(spmv_shim_time_attention_heads_backward(st->dev, heads, (int) st->opts.v[SPMV_OPT_ATTENTION_BACKWARD_HEADS], k, dv, scale, Q, ldq, K, ldk, V, ldv, G, ldg,
-                                                               dQ, lddq, dK, lddk, dV, lddv, warmup, iters, ms_out), where);
-}
-
-/* ---------------------------------------------------------------- the heads calls with an additive bias per head and entry, and its gradient */
 int spmv_hip_attention_bias(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
                             const void *Matrix_Val, int heads, int k, int dv, double scale,
                             const void *Q, long long ldq, const void *K, long long ldk, const void *V, long long ldv,
                             const void *B, long long ldb, void *O, long long ldo)
 {
-    const char *where = "attention_bias";
-    spmv_hip_state *st;
-    int rc;
-    if ((rc = attention_heads_args(handle, where, heads, k, dv, Q, ldq, K, ldk, V, ldv, O, ldo, m))) return rc;
-    if (B && ldb < 0) return refuse(SPMV_HIP_E_ARG, where, "need ldb >= 0");
-    if ((rc = resident_prologue(handle, where, RESIDENT_NOT_REORDERED, m, RowPtr, ColIdx, Matrix_Val, &st)) || (rc = spmm_columns(handle, st, where))) return rc;
-    return report(spmv_shim_attention_bias(st->dev, heads, k, dv, scale, Q, ldq, K, ldk, V, ldv, B, ldb, O, ldo), where); /* 0 < ldb < nnz: refused there, nothing written */
+    const spmv_attention_call c = {.heads = heads, .kv_heads = heads, .k = k, .dv = dv, .scale = scale, .q = Q, .ldq = ldq, .kk = K, .ldk = ldk, .v = V, .ldv = ldv,
+                                   .bias = B, .ldb = ldb, .o = O, .ldo = ldo};
+    return attention_call(handle, "attention_bias", 0, &c, m, RowPtr, ColIdx, Matrix_Val);
 }
 
 double spmv_hip_time_attention_bias_launches(spmv_Handle_t h, int heads, int k, int dv, double scale, const void *Q, long long ldq, const void *K, long long ldk,
                                              const void *V, long long ldv, const void *B, long long ldb, void *O, long long ldo, int warmup, int iters, float *ms_out)
 {
-    const char *where = "time_attention_bias_launches";
-    spmv_hip_state *st;
-    if (attention_heads_args(h, where, heads, k, dv, Q, ldq, K, ldk, V, ldv, O, ldo, 1)) return -1.0;
-    if (B && ldb < 0) { (void) refuse(SPMV_HIP_E_ARG, where, "need ldb >= 0"); return -1.0; }
-    if (resident_state(h, where, RESIDENT_NOT_REORDERED, &st) || spmm_columns(h, st, where)) return -1.0;
-    return report_time(spmv_shim_time_attention_bias(st->dev, heads, k, dv, scale, Q, ldq, K, ldk, V, ldv, B, ldb, O, ldo, warmup, iters, ms_out), where);
-}
-
-int spmv_hip_attention_bias_backward(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
-                                     const void *Matrix_Val, int heads, int k, int dv, double scale,
-                                     const void *Q, long long ldq, const void *K, long long ldk, const void *V, long long ldv,
-                                     const void *B, long long ldb, const void *G, long long ldg, void *dQ, long long lddq, void *dK, long long lddk,
-                                     void *dV, long long lddv, void *dB, long long lddb)
-{
-    const char *where = "attention_bias_backward";
-    spmv_hip_state *st;
-    int rc;
-    if ((rc = attention_heads_backward_args(handle, where, heads, k, dv, Q, ldq, K, ldk, V, ldv, G, ldg, dQ, lddq, dK, lddk, dV, lddv, m))) return rc;
-    if ((B && ldb < 0) || (dB && lddb < 0)) return refuse(SPMV_HIP_E_ARG, where, "need ldb >= 0 and lddb >= 0");
-    if (!dQ && !dK && !dV && !dB) return SPMV_HIP_OK; /* nothing wanted: no work, the handle's state is not looked at */
-    if ((rc = resident_prologue(handle, where, RESIDENT_NOT_REORDERED, m, RowPtr, ColIdx, Matrix_Val, &st))) return rc;
-    if ((rc = attention_backward_tables(handle, st, where, dK || dV))) return rc; /* only dB (or dQ) wanted: no transpose */
-    return report(spmv_shim_attention_bias_backward(st->dev, heads, (int) st->opts.v[SPMV_OPT_ATTENTION_BACKWARD_HEADS], k, dv, scale, Q, ldq, K, ldk, V, ldv, B, ldb, G, ldg,
-                                                    dQ, lddq, dK, lddk, dV, lddv, dB, lddb), where); /* a plane stride below nnz: refused there, nothing written */
-}
-
-double spmv_hip_time_attention_bias_backward_launches(spmv_Handle_t h, int heads, int k, int dv, double scale, const void *Q, long long ldq, const void *K,
-                                                      long long ldk, const void *V, long long ldv, const void *B, long long ldb, const void *G, long long ldg, void *dQ,
-                                                      long long lddq, void *dK, long long lddk, void *dV, long long lddv, void *dB, long long lddb, int warmup, int iters,
-                                                      float *ms_out)
-{
-    const char *where = "time_attention_bias_backward_launches";
-    spmv_hip_state *st;
-    if (attention_heads_backward_args(h, where, heads, k, dv, Q, ldq, K, ldk, V, ldv, G, ldg, dQ, lddq, dK, lddk, dV, lddv, 1)) return -1.0;
-    if ((B && ldb < 0) || (dB && lddb < 0)) { (void) refuse(SPMV_HIP_E_ARG, where, "need ldb >= 0 and lddb >= 0"); return -1.0; }
-    if (resident_state(h, where, RESIDENT_NOT_REORDERED, &st) || attention_backward_tables(h, st, where, dK || dV)) return -1.0;
-    return report_time(spmv_shim_time_attention_bias_backward(st->dev, heads, (int) st->opts.v[SPMV_OPT_ATTENTION_BACKWARD_HEADS], k, dv, scale, Q, ldq, K, ldk, V, ldv, B, ldb,
-                                                              G, ldg, dQ, lddq, dK, lddk, dV, lddv, dB, lddb, warmup, iters, ms_out), where);
-}
-
-/* ---------------------------------------------------------------- the bias calls with kv_heads K / V heads for heads query heads (GQA, MQA) */
-static int attention_gqa_args(spmv_Handle_t h, const char *where, int heads, int kv_heads, int k, int dv, const void *Q, long long ldq, const void *K, long long ldk,
-                              const void *V, long long ldv, const void *O, long long ldo, int m)
-{
-    if (!h) return refuse(SPMV_HIP_E_ARG, where, "handle is NULL");
-    if (heads < 1 || kv_heads < 1 || k < 1 || dv < 1) return refuse(SPMV_HIP_E_ARG, where, "need heads >= 1, kv_heads >= 1, k >= 1 and dv >= 1");
-    if (heads % kv_heads != 0) return refuse(SPMV_HIP_E_ARG, where, "heads must be a multiple of kv_heads");
-    if ((long long) heads * k > INT_MAX || (long long) heads * dv > INT_MAX || (long long) kv_heads * k > INT_MAX || (long long) kv_heads * dv > INT_MAX)
-        return refuse(SPMV_HIP_E_ARG, where, "heads * k, heads * dv, kv_heads * k or kv_heads * dv does not fit an int");
-    if (ldq < (long long) heads * k || ldk < (long long) kv_heads * k || ldv < (long long) kv_heads * dv || ldo < (long long) heads * dv)
-        return refuse(SPMV_HIP_E_ARG, where, "need ldq >= heads * k, ldk >= kv_heads * k, ldv >= kv_heads * dv and ldo >= heads * dv");
-    if (m > 0 && (!Q || !K || !V || !O)) return refuse(SPMV_HIP_E_ARG, where, "Q, K, V or O is NULL");
-    return SPMV_HIP_OK;
+    const spmv_attention_call c = {.heads = heads, .kv_heads = heads, .k = k, .dv = dv, .scale = scale, .q = Q, .ldq = ldq, .kk = K, .ldk = ldk, .v = V, .ldv = ldv,
+                                   .bias = B, .ldb = ldb, .o = O, .ldo = ldo};
+    return attention_time(h, "time_attention_bias_launches", 0, &c, warmup, iters, ms_out);
 }
 
 int spmv_hip_attention_gqa(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
@@ -1268,63 +1136,36 @@ int spmv_hip_attention_gqa(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_I
                            const void *Q, long long ldq, const void *K, long long ldk, const void *V, long long ldv,
                            const void *B, long long ldb, void *O, long long ldo)
 {
-    const char *where = "attention_gqa";
-    spmv_hip_state *st;
-    int rc;
-    if ((rc = attention_gqa_args(handle, where, heads, kv_heads, k, dv, Q, ldq, K, ldk, V, ldv, O, ldo, m))) return rc;
-    if (B && ldb < 0) return refuse(SPMV_HIP_E_ARG, where, "need ldb >= 0");
-    if ((rc = resident_prologue(handle, where, RESIDENT_NOT_REORDERED, m, RowPtr, ColIdx, Matrix_Val, &st)) || (rc = spmm_columns(handle, st, where))) return rc;
-    return report(spmv_shim_attention_gqa(st->dev, heads, kv_heads, k, dv, scale, Q, ldq, K, ldk, V, ldv, B, ldb, O, ldo), where); /* 0 < ldb < nnz: refused there, nothing written */
+    const spmv_attention_call c = {.heads = heads, .kv_heads = kv_heads, .k = k, .dv = dv, .scale = scale, .q = Q, .ldq = ldq, .kk = K, .ldk = ldk, .v = V, .ldv = ldv,
+                                   .bias = B, .ldb = ldb, .o = O, .ldo = ldo};
+    return attention_call(handle, "attention_gqa", 0, &c, m, RowPtr, ColIdx, Matrix_Val);
 }
 
 double spmv_hip_time_attention_gqa_launches(spmv_Handle_t h, int heads, int kv_heads, int k, int dv, double scale, const void *Q, long long ldq, const void *K, long long ldk,
                                             const void *V, long long ldv, const void *B, long long ldb, void *O, long long ldo, int warmup, int iters, float *ms_out)
 {
-    const char *where = "time_attention_gqa_launches";
-    spmv_hip_state *st;
-    if (attention_gqa_args(h, where, heads, kv_heads, k, dv, Q, ldq, K, ldk, V, ldv, O, ldo, 1)) return -1.0;
-    if (B && ldb < 0) { (void) refuse(SPMV_HIP_E_ARG, where, "need ldb >= 0"); return -1.0; }
-    if (resident_state(h, where, RESIDENT_NOT_REORDERED, &st) || spmm_columns(h, st, where)) return -1.0;
-    return report_time(spmv_shim_time_attention_gqa(st->dev, heads, kv_heads, k, dv, scale, Q, ldq, K, ldk, V, ldv, B, ldb, O, ldo, warmup, iters, ms_out), where);
+    const spmv_attention_call c = {.heads = heads, .kv_heads = kv_heads, .k = k, .dv = dv, .scale = scale, .q = Q, .ldq = ldq, .kk = K, .ldk = ldk, .v = V, .ldv = ldv,
+                                   .bias = B, .ldb = ldb, .o = O, .ldo = ldo};
+    return attention_time(h, "time_attention_gqa_launches", 0, &c, warmup, iters, ms_out);
 }
 
-/* ---------------------------------------------------------------- the row log-sum-exp out of the forward, and two partial results merged by it */
 int spmv_hip_attention_gqa_lse(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
                                const void *Matrix_Val, int heads, int kv_heads, int k, int dv, double scale,
                                const void *Q, long long ldq, const void *K, long long ldk, const void *V, long long ldv,
                                const void *B, long long ldb, void *O, long long ldo, void *L, long long ldl)
 {
-    const char *where = "attention_gqa_lse";
-    spmv_hip_state *st;
-    int rc;
-    if ((rc = attention_gqa_args(handle, where, heads, kv_heads, k, dv, Q, ldq, K, ldk, V, ldv, O, ldo, m))) return rc;
-    if (B && ldb < 0) return refuse(SPMV_HIP_E_ARG, where, "need ldb >= 0");
-    if (L && ldl < (long long) m) return refuse(SPMV_HIP_E_ARG, where, "need ldl >= m");
-    if ((rc = resident_prologue(handle, where, RESIDENT_NOT_REORDERED, m, RowPtr, ColIdx, Matrix_Val, &st)) || (rc = spmm_columns(handle, st, where))) return rc;
-    return report(spmv_shim_attention_gqa_lse(st->dev, heads, kv_heads, k, dv, scale, Q, ldq, K, ldk, V, ldv, B, ldb, O, ldo, L, ldl), where); /* 0 < ldb < nnz: refused there, nothing written */
+    const spmv_attention_call c = {.heads = heads, .kv_heads = kv_heads, .k = k, .dv = dv, .scale = scale, .q = Q, .ldq = ldq, .kk = K, .ldk = ldk, .v = V, .ldv = ldv,
+                                   .bias = B, .ldb = ldb, .o = O, .ldo = ldo, .lse = L, .ldl = ldl};
+    return attention_call(handle, "attention_gqa_lse", 0, &c, m, RowPtr, ColIdx, Matrix_Val);
 }
 
 double spmv_hip_time_attention_gqa_lse_launches(spmv_Handle_t h, int heads, int kv_heads, int k, int dv, double scale, const void *Q, long long ldq, const void *K, long long ldk,
                                                 const void *V, long long ldv, const void *B, long long ldb, void *O, long long ldo, void *L, long long ldl, int warmup, int iters,
                                                 float *ms_out)
 {
-    const char *where = "time_attention_gqa_lse_launches";
-    spmv_hip_state *st;
-    if (attention_gqa_args(h, where, heads, kv_heads, k, dv, Q, ldq, K, ldk, V, ldv, O, ldo, 1)) return -1.0;
-    if (B && ldb < 0) { (void) refuse(SPMV_HIP_E_ARG, where, "need ldb >= 0"); return -1.0; }
-    if (resident_state(h, where, RESIDENT_NOT_REORDERED, &st) || spmm_columns(h, st, where)) return -1.0;
-    return report_time(spmv_shim_time_attention_gqa_lse(st->dev, heads, kv_heads, k, dv, scale, Q, ldq, K, ldk, V, ldv, B, ldb, O, ldo, L, ldl, warmup, iters, ms_out), where);
-}
-
-/* ---------------------------------------------------------------- the forward on 16-bit Q, K and V */
-/* the type rules ahead of the gate: data_size is in the public handle, so a handle whose create failed answers them too (a cleared handle holds
- * no precision any more, data_size 0: it gets as far as the gate and is SPMV_HIP_E_NOSTATE there, like in every other call) */
-static int attention_16_types(spmv_Handle_t h, const char *where, int io_type, int o_type)
-{
-    if (h->data_size != sizeof(float) && h->data_size != 0) return refuse(SPMV_HIP_E_ARG, where, "16-bit operands need an fp32 handle");
-    if (io_type != SPMV_HIP_T_F16 && io_type != SPMV_HIP_T_BF16) return refuse(SPMV_HIP_E_ARG, where, "io_type must be SPMV_HIP_T_F16 or SPMV_HIP_T_BF16");
-    if (o_type != SPMV_HIP_T_HANDLE && o_type != io_type) return refuse(SPMV_HIP_E_ARG, where, "o_type must be SPMV_HIP_T_HANDLE or equal to io_type");
-    return SPMV_HIP_OK;
+    const spmv_attention_call c = {.heads = heads, .kv_heads = kv_heads, .k = k, .dv = dv, .scale = scale, .q = Q, .ldq = ldq, .kk = K, .ldk = ldk, .v = V, .ldv = ldv,
+                                   .bias = B, .ldb = ldb, .o = O, .ldo = ldo, .lse = L, .ldl = ldl};
+    return attention_time(h, "time_attention_gqa_lse_launches", 0, &c, warmup, iters, ms_out);
 }
 
 int spmv_hip_attention_gqa_lse_16(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
@@ -1332,30 +1173,21 @@ int spmv_hip_attention_gqa_lse_16(spmv_Handle_t handle, BASIC_INT_TYPE m, const 
                                   const void *Q, long long ldq, const void *K, long long ldk, const void *V, long long ldv,
                                   const void *B, long long ldb, void *O, long long ldo, int o_type, void *L, long long ldl)
 {
-    const char *where = "attention_gqa_lse_16";
-    spmv_hip_state *st;
-    int rc;
-    if ((rc = attention_gqa_args(handle, where, heads, kv_heads, k, dv, Q, ldq, K, ldk, V, ldv, O, ldo, m))) return rc;
-    if (B && ldb < 0) return refuse(SPMV_HIP_E_ARG, where, "need ldb >= 0");
-    if (L && ldl < (long long) m) return refuse(SPMV_HIP_E_ARG, where, "need ldl >= m");
-    if ((rc = attention_16_types(handle, where, io_type, o_type))) return rc;
-    if ((rc = resident_prologue(handle, where, RESIDENT_NOT_REORDERED, m, RowPtr, ColIdx, Matrix_Val, &st)) || (rc = spmm_columns(handle, st, where))) return rc;
-    return report(spmv_shim_attention_gqa_lse_16(st->dev, heads, kv_heads, k, dv, scale, io_type, Q, ldq, K, ldk, V, ldv, B, ldb, O, ldo, o_type, L, ldl), where);
+    const spmv_attention_call c = {.heads = heads, .kv_heads = kv_heads, .k = k, .dv = dv, .scale = scale, .io_type = io_type, .o_type = o_type, .q = Q, .ldq = ldq,
+                                   .kk = K, .ldk = ldk, .v = V, .ldv = ldv, .bias = B, .ldb = ldb, .o = O, .ldo = ldo, .lse = L, .ldl = ldl};
+    return attention_call(handle, "attention_gqa_lse_16", ATTENTION_16, &c, m, RowPtr, ColIdx, Matrix_Val);
 }
 
 double spmv_hip_time_attention_gqa_lse_16_launches(spmv_Handle_t h, int heads, int kv_heads, int k, int dv, double scale, int io_type, const void *Q, long long ldq,
                                                    const void *K, long long ldk, const void *V, long long ldv, const void *B, long long ldb, void *O, long long ldo, int o_type,
                                                    void *L, long long ldl, int warmup, int iters, float *ms_out)
 {
-    const char *where = "time_attention_gqa_lse_16_launches";
-    spmv_hip_state *st;
-    if (attention_gqa_args(h, where, heads, kv_heads, k, dv, Q, ldq, K, ldk, V, ldv, O, ldo, 1)) return -1.0;
-    if (B && ldb < 0) { (void) refuse(SPMV_HIP_E_ARG, where, "need ldb >= 0"); return -1.0; }
-    if (attention_16_types(h, where, io_type, o_type)) return -1.0;
-    if (resident_state(h, where, RESIDENT_NOT_REORDERED, &st) || spmm_columns(h, st, where)) return -1.0;
-    return report_time(spmv_shim_time_attention_gqa_lse_16(st->dev, heads, kv_heads, k, dv, scale, io_type, Q, ldq, K, ldk, V, ldv, B, ldb, O, ldo, o_type, L, ldl, warmup,
-                                                           iters, ms_out), where);
+    const spmv_attention_call c = {.heads = heads, .kv_heads = kv_heads, .k = k, .dv = dv, .scale = scale, .io_type = io_type, .o_type = o_type, .q = Q, .ldq = ldq,
+                                   .kk = K, .ldk = ldk, .v = V, .ldv = ldv, .bias = B, .ldb = ldb, .o = O, .ldo = ldo, .lse = L, .ldl = ldl};
+    return attention_time(h, "time_attention_gqa_lse_16_launches", ATTENTION_16, &c, warmup, iters, ms_out);
 }
+
+/* ---------------------------------------------------------------- two partial results merged by their log-sum-exps */
 
 /* m is the handle's: whether an operand is NULL while m > 0, and the plane strides against m, are looked at behind the gate (nothing written) */
 static int attention_merge_args(spmv_Handle_t h, const char *where, int heads, int dv, long long ldo1, long long ldo2, long long ldo)
@@ -1390,23 +1222,126 @@ double spmv_hip_time_attention_merge_launches(spmv_Handle_t h, int heads, int dv
     return report_time(spmv_shim_time_attention_merge(st->dev, heads, dv, O1, ldo1, L1, ldl1, O2, ldo2, L2, ldl2, O, ldo, L, ldl, warmup, iters, ms_out), where);
 }
 
-static int attention_gqa_backward_args(spmv_Handle_t h, const char *where, int heads, int kv_heads, int k, int dv, const void *Q, long long ldq, const void *K, long long ldk,
-                                       const void *V, long long ldv, const void *G, long long ldg, const void *dQ, long long lddq, const void *dK, long long lddk,
-                                       const void *dV, long long lddv, int m)
+/* ---------------------------------------------------------------- dQ, dK, dV and dB of the fused attention in two passes over A: one path for every variant
+ * Like the forward: an entry point fills a spmv_attention_backward_call, names itself and takes the path of calls or that of timers. */
+#define ATTENTION_GATE_FIRST 4 /* spmv_hip_attention_backward alone: with nothing wanted it still runs the prologue, so a handle without state is
+                                * SPMV_HIP_E_NOSTATE there, where every later entry point returns 0 before the handle's state is looked at */
+
+/* the argument rules ahead of the gate, in this order: the calls with their m, the timers with m = 1.  The strides of outputs that are not wanted
+ * are not looked at. */
+static int attention_backward_rules(spmv_Handle_t h, const char *where, int flags, const spmv_attention_backward_call *c, BASIC_INT_TYPE m)
 {
-    long long wk, wv, gk, gv;
+    const long long wk = (long long) c->heads * c->k, wv = (long long) c->heads * c->dv, gk = (long long) c->kv_heads * c->k, gv = (long long) c->kv_heads * c->dv;
     if (!h) return refuse(SPMV_HIP_E_ARG, where, "handle is NULL");
-    if (heads < 1 || kv_heads < 1 || k < 1 || dv < 1) return refuse(SPMV_HIP_E_ARG, where, "need heads >= 1, kv_heads >= 1, k >= 1 and dv >= 1");
-    if (heads % kv_heads != 0) return refuse(SPMV_HIP_E_ARG, where, "heads must be a multiple of kv_heads");
-    wk = (long long) heads * k;
-    wv = (long long) heads * dv;
-    gk = (long long) kv_heads * k;
-    gv = (long long) kv_heads * dv;
+    if (c->heads < 1 || c->kv_heads < 1 || c->k < 1 || c->dv < 1) return refuse(SPMV_HIP_E_ARG, where, "need heads >= 1, kv_heads >= 1, k >= 1 and dv >= 1");
+    if (c->heads % c->kv_heads != 0) return refuse(SPMV_HIP_E_ARG, where, "heads must be a multiple of kv_heads");
     if (wk > INT_MAX || wv > INT_MAX || gk > INT_MAX || gv > INT_MAX) return refuse(SPMV_HIP_E_ARG, where, "heads * k, heads * dv, kv_heads * k or kv_heads * dv does not fit an int");
-    if (ldq < wk || ldk < gk || ldv < gv || ldg < wv || (dQ && lddq < wk) || (dK && lddk < gk) || (dV && lddv < gv))
+    if (c->ldq < wk || c->ldk < gk || c->ldv < gv || c->ldg < wv || (c->dq && c->lddq < wk) || (c->dk && c->lddk < gk) || (c->dvo && c->lddv < gv))
         return refuse(SPMV_HIP_E_ARG, where, "need ldq >= heads * k, ldk >= kv_heads * k, ldv >= kv_heads * dv, ldg >= heads * dv and, for the requested outputs, lddq >= heads * k, lddk >= kv_heads * k, lddv >= kv_heads * dv");
-    if (m > 0 && (!Q || !K || !V || !G)) return refuse(SPMV_HIP_E_ARG, where, "Q, K, V or G is NULL");
+    if (m > 0 && (!c->q || !c->kk || !c->v || !c->g)) return refuse(SPMV_HIP_E_ARG, where, "Q, K, V or G is NULL");
+    if ((c->bias && c->ldb < 0) || (c->db && c->lddb < 0)) return refuse(SPMV_HIP_E_ARG, where, "need ldb >= 0 and lddb >= 0"); /* a plane stride below nnz: refused by the shim, nothing written */
+    if ((flags & ATTENTION_16) && m > 0 && (c->o == NULL) != (c->lse == NULL)) return refuse(SPMV_HIP_E_ARG, where, "O and L are given together or not at all");
+    if (c->stats) {
+        if (c->ldo < wv) return refuse(SPMV_HIP_E_ARG, where, "need ldo >= heads * dv");
+        if (c->ldl < (long long) m) return refuse(SPMV_HIP_E_ARG, where, "need ldl >= m");
+        if (m > 0 && (!c->o || !c->lse)) return refuse(SPMV_HIP_E_ARG, where, "O or L is NULL");
+    }
+    if (flags & ATTENTION_16) { /* from the public handle's data_size, like the forward's */
+        if (h->data_size != sizeof(float) && h->data_size != 0) return refuse(SPMV_HIP_E_ARG, where, "16-bit operands need an fp32 handle");
+        if (c->io_type != SPMV_HIP_T_F16 && c->io_type != SPMV_HIP_T_BF16) return refuse(SPMV_HIP_E_ARG, where, "io_type must be SPMV_HIP_T_F16 or SPMV_HIP_T_BF16");
+        if (c->dq_type != SPMV_HIP_T_HANDLE && c->dq_type != c->io_type) return refuse(SPMV_HIP_E_ARG, where, "dq_type must be SPMV_HIP_T_HANDLE or equal to io_type");
+        if (c->dkv_type != SPMV_HIP_T_HANDLE && c->dkv_type != c->io_type) return refuse(SPMV_HIP_E_ARG, where, "dkv_type must be SPMV_HIP_T_HANDLE or equal to io_type");
+    }
     return SPMV_HIP_OK;
+}
+
+/* behind the gate: A's columns and, when dK or dV is wanted, the transpose (its values are not read: no refresh) with its columns; the heads per round */
+static int attention_backward_tables(spmv_Handle_t h, spmv_hip_state *st, const char *where, spmv_attention_backward_call *c)
+{
+    int rc = spmm_columns(h, st, where);
+    if (!rc && (c->dk || c->dvo) && !(rc = transpose_built(h, st, where))) rc = transpose_columns(st, where); /* only dB (or dQ) wanted: no transpose */
+    c->max_heads = (int) st->opts.v[SPMV_OPT_ATTENTION_BACKWARD_HEADS];
+    return rc;
+}
+
+static int attention_backward_call(spmv_Handle_t h, const char *where, int flags, spmv_attention_backward_call *c, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr,
+                                   const BASIC_INT_TYPE *ColIdx, const void *Matrix_Val)
+{
+    const int wanted = c->dq || c->dk || c->dvo || c->db;
+    spmv_hip_state *st;
+    int rc;
+    if ((rc = attention_backward_rules(h, where, flags, c, m))) return rc;
+    if (!wanted && !(flags & ATTENTION_GATE_FIRST)) return SPMV_HIP_OK; /* nothing wanted: no work, the handle's state is not looked at */
+    if ((rc = resident_prologue(h, where, RESIDENT_NOT_REORDERED, m, RowPtr, ColIdx, Matrix_Val, &st))) return rc;
+    if (!wanted) return SPMV_HIP_OK;
+    if ((rc = attention_backward_tables(h, st, where, c))) return rc;
+    return report(spmv_shim_attention_backward(st->dev, c), where);
+}
+
+static double attention_backward_time(spmv_Handle_t h, const char *where, int flags, spmv_attention_backward_call *c, int warmup, int iters, float *ms_out)
+{
+    spmv_hip_state *st;
+    if (attention_backward_rules(h, where, flags, c, 1) || resident_state(h, where, RESIDENT_NOT_REORDERED, &st) || attention_backward_tables(h, st, where, c)) return -1.0;
+    return report_time(spmv_shim_time_attention_backward(st->dev, c, warmup, iters, ms_out), where);
+}
+
+int spmv_hip_attention_backward(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                                const void *Matrix_Val, int k, int dv, double scale,
+                                const void *Q, long long ldq, const void *K, long long ldk, const void *V, long long ldv,
+                                const void *G, long long ldg, void *dQ, long long lddq, void *dK, long long lddk, void *dV, long long lddv)
+{
+    spmv_attention_backward_call c = {.heads = 1, .kv_heads = 1, .k = k, .dv = dv, .scale = scale, .q = Q, .ldq = ldq, .kk = K, .ldk = ldk, .v = V, .ldv = ldv, .g = G, .ldg = ldg,
+                                      .dq = dQ, .lddq = lddq, .dk = dK, .lddk = lddk, .dvo = dV, .lddv = lddv};
+    return attention_backward_call(handle, "attention_backward", ATTENTION_GATE_FIRST, &c, m, RowPtr, ColIdx, Matrix_Val);
+}
+
+double spmv_hip_time_attention_backward_launches(spmv_Handle_t h, int k, int dv, double scale, const void *Q, long long ldq, const void *K, long long ldk,
+                                                 const void *V, long long ldv, const void *G, long long ldg, void *dQ, long long lddq, void *dK, long long lddk,
+                                                 void *dV, long long lddv, int warmup, int iters, float *ms_out)
+{
+    spmv_attention_backward_call c = {.heads = 1, .kv_heads = 1, .k = k, .dv = dv, .scale = scale, .q = Q, .ldq = ldq, .kk = K, .ldk = ldk, .v = V, .ldv = ldv, .g = G, .ldg = ldg,
+                                      .dq = dQ, .lddq = lddq, .dk = dK, .lddk = lddk, .dvo = dV, .lddv = lddv};
+    return attention_backward_time(h, "time_attention_backward_launches", 0, &c, warmup, iters, ms_out);
+}
+
+int spmv_hip_attention_heads_backward(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                                      const void *Matrix_Val, int heads, int k, int dv, double scale,
+                                      const void *Q, long long ldq, const void *K, long long ldk, const void *V, long long ldv,
+                                      const void *G, long long ldg, void *dQ, long long lddq, void *dK, long long lddk, void *dV, long long lddv)
+{
+    spmv_attention_backward_call c = {.heads = heads, .kv_heads = heads, .k = k, .dv = dv, .scale = scale, .q = Q, .ldq = ldq, .kk = K, .ldk = ldk, .v = V, .ldv = ldv,
+                                      .g = G, .ldg = ldg, .dq = dQ, .lddq = lddq, .dk = dK, .lddk = lddk, .dvo = dV, .lddv = lddv};
+    return attention_backward_call(handle, "attention_heads_backward", 0, &c, m, RowPtr, ColIdx, Matrix_Val);
+}
+
+double spmv_hip_time_attention_heads_backward_launches(spmv_Handle_t h, int heads, int k, int dv, double scale, const void *Q, long long ldq, const void *K, long long ldk,
+                                                       const void *V, long long ldv, const void *G, long long ldg, void *dQ, long long lddq, void *dK, long long lddk,
+                                                       void *dV, long long lddv, int warmup, int iters, float *ms_out)
+{
+    spmv_attention_backward_call c = {.heads = heads, .kv_heads = heads, .k = k, .dv = dv, .scale = scale, .q = Q, .ldq = ldq, .kk = K, .ldk = ldk, .v = V, .ldv = ldv,
+                                      .g = G, .ldg = ldg, .dq = dQ, .lddq = lddq, .dk = dK, .lddk = lddk, .dvo = dV, .lddv = lddv};
+    return attention_backward_time(h, "time_attention_heads_backward_launches", 0, &c, warmup, iters, ms_out);
+}
+
+int spmv_hip_attention_bias_backward(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                                     const void *Matrix_Val, int heads, int k, int dv, double scale,
+                                     const void *Q, long long ldq, const void *K, long long ldk, const void *V, long long ldv,
+                                     const void *B, long long ldb, const void *G, long long ldg, void *dQ, long long lddq, void *dK, long long lddk,
+                                     void *dV, long long lddv, void *dB, long long lddb)
+{
+    spmv_attention_backward_call c = {.heads = heads, .kv_heads = heads, .k = k, .dv = dv, .scale = scale, .q = Q, .ldq = ldq, .kk = K, .ldk = ldk, .v = V, .ldv = ldv,
+                                      .bias = B, .ldb = ldb, .g = G, .ldg = ldg, .dq = dQ, .lddq = lddq, .dk = dK, .lddk = lddk, .dvo = dV, .lddv = lddv, .db = dB, .lddb = lddb};
+    return attention_backward_call(handle, "attention_bias_backward", 0, &c, m, RowPtr, ColIdx, Matrix_Val);
+}
+
+double spmv_hip_time_attention_bias_backward_launches(spmv_Handle_t h, int heads, int k, int dv, double scale, const void *Q, long long ldq, const void *K,
+                                                      long long ldk, const void *V, long long ldv, const void *B, long long ldb, const void *G, long long ldg, void *dQ,
+                                                      long long lddq, void *dK, long long lddk, void *dV, long long lddv, void *dB, long long lddb, int warmup, int iters,
+                                                      float *ms_out)
+{
+    spmv_attention_backward_call c = {.heads = heads, .kv_heads = heads, .k = k, .dv = dv, .scale = scale, .q = Q, .ldq = ldq, .kk = K, .ldk = ldk, .v = V, .ldv = ldv,
+                                      .bias = B, .ldb = ldb, .g = G, .ldg = ldg, .dq = dQ, .lddq = lddq, .dk = dK, .lddk = lddk, .dvo = dV, .lddv = lddv, .db = dB, .lddb = lddb};
+    return attention_backward_time(h, "time_attention_bias_backward_launches", 0, &c, warmup, iters, ms_out);
 }
 
 int spmv_hip_attention_gqa_backward(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
@@ -1415,16 +1350,9 @@ int spmv_hip_attention_gqa_backward(spmv_Handle_t handle, BASIC_INT_TYPE m, cons
                                     const void *B, long long ldb, const void *G, long long ldg, void *dQ, long long lddq, void *dK, long long lddk,
                                     void *dV, long long lddv, void *dB, long long lddb)
 {
-    const char *where = "attention_gqa_backward";
-    spmv_hip_state *st;
-    int rc;
-    if ((rc = attention_gqa_backward_args(handle, where, heads, kv_heads, k, dv, Q, ldq, K, ldk, V, ldv, G, ldg, dQ, lddq, dK, lddk, dV, lddv, m))) return rc;
-    if ((B && ldb < 0) || (dB && lddb < 0)) return refuse(SPMV_HIP_E_ARG, where, "need ldb >= 0 and lddb >= 0");
-    if (!dQ && !dK && !dV && !dB) return SPMV_HIP_OK; /* nothing wanted: no work, the handle's state is not looked at */
-    if ((rc = resident_prologue(handle, where, RESIDENT_NOT_REORDERED, m, RowPtr, ColIdx, Matrix_Val, &st))) return rc;
-    if ((rc = attention_backward_tables(handle, st, where, dK || dV))) return rc; /* only dB (or dQ) wanted: no transpose */
-    return report(spmv_shim_attention_gqa_backward(st->dev, heads, kv_heads, (int) st->opts.v[SPMV_OPT_ATTENTION_BACKWARD_HEADS], k, dv, scale, Q, ldq, K, ldk, V, ldv, B, ldb, G,
-                                                   ldg, dQ, lddq, dK, lddk, dV, lddv, dB, lddb), where); /* a plane stride below nnz: refused there, nothing written */
+    spmv_attention_backward_call c = {.heads = heads, .kv_heads = kv_heads, .k = k, .dv = dv, .scale = scale, .q = Q, .ldq = ldq, .kk = K, .ldk = ldk, .v = V, .ldv = ldv,
+                                      .bias = B, .ldb = ldb, .g = G, .ldg = ldg, .dq = dQ, .lddq = lddq, .dk = dK, .lddk = lddk, .dvo = dV, .lddv = lddv, .db = dB, .lddb = lddb};
+    return attention_backward_call(handle, "attention_gqa_backward", 0, &c, m, RowPtr, ColIdx, Matrix_Val);
 }
 
 double spmv_hip_time_attention_gqa_backward_launches(spmv_Handle_t h, int heads, int kv_heads, int k, int dv, double scale, const void *Q, long long ldq, const void *K,
@@ -1432,22 +1360,9 @@ double spmv_hip_time_attention_gqa_backward_launches(spmv_Handle_t h, int heads,
                                                      long long lddq, void *dK, long long lddk, void *dV, long long lddv, void *dB, long long lddb, int warmup, int iters,
                                                      float *ms_out)
 {
-    const char *where = "time_attention_gqa_backward_launches";
-    spmv_hip_state *st;
-    if (attention_gqa_backward_args(h, where, heads, kv_heads, k, dv, Q, ldq, K, ldk, V, ldv, G, ldg, dQ, lddq, dK, lddk, dV, lddv, 1)) return -1.0;
-    if ((B && ldb < 0) || (dB && lddb < 0)) { (void) refuse(SPMV_HIP_E_ARG, where, "need ldb >= 0 and lddb >= 0"); return -1.0; }
-    if (resident_state(h, where, RESIDENT_NOT_REORDERED, &st) || attention_backward_tables(h, st, where, dK || dV)) return -1.0;
-    return report_time(spmv_shim_time_attention_gqa_backward(st->dev, heads, kv_heads, (int) st->opts.v[SPMV_OPT_ATTENTION_BACKWARD_HEADS], k, dv, scale, Q, ldq, K, ldk, V, ldv, B,
-                                                             ldb, G, ldg, dQ, lddq, dK, lddk, dV, lddv, dB, lddb, warmup, iters, ms_out), where);
-}
-
-/* ---------------------------------------------------------------- the GQA backward driven by the final O and log-sum-exp */
-static int attention_lse_inputs(const char *where, int heads, int dv, const void *O, long long ldo, const void *L, long long ldl, int m)
-{
-    if (ldo < (long long) heads * dv) return refuse(SPMV_HIP_E_ARG, where, "need ldo >= heads * dv");
-    if (ldl < (long long) m) return refuse(SPMV_HIP_E_ARG, where, "need ldl >= m");
-    if (m > 0 && (!O || !L)) return refuse(SPMV_HIP_E_ARG, where, "O or L is NULL");
-    return SPMV_HIP_OK;
+    spmv_attention_backward_call c = {.heads = heads, .kv_heads = kv_heads, .k = k, .dv = dv, .scale = scale, .q = Q, .ldq = ldq, .kk = K, .ldk = ldk, .v = V, .ldv = ldv,
+                                      .bias = B, .ldb = ldb, .g = G, .ldg = ldg, .dq = dQ, .lddq = lddq, .dk = dK, .lddk = lddk, .dvo = dV, .lddv = lddv, .db = dB, .lddb = lddb};
+    return attention_backward_time(h, "time_attention_gqa_backward_launches", 0, &c, warmup, iters, ms_out);
 }
 
 int spmv_hip_attention_gqa_backward_lse(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
@@ -1456,17 +1371,10 @@ int spmv_hip_attention_gqa_backward_lse(spmv_Handle_t handle, BASIC_INT_TYPE m, 
                                         const void *B, long long ldb, const void *G, long long ldg, const void *O, long long ldo, const void *L, long long ldl,
                                         void *dQ, long long lddq, void *dK, long long lddk, void *dV, long long lddv, void *dB, long long lddb)
 {
-    const char *where = "attention_gqa_backward_lse";
-    spmv_hip_state *st;
-    int rc;
-    if ((rc = attention_gqa_backward_args(handle, where, heads, kv_heads, k, dv, Q, ldq, K, ldk, V, ldv, G, ldg, dQ, lddq, dK, lddk, dV, lddv, m)) ||
-        (rc = attention_lse_inputs(where, heads, dv, O, ldo, L, ldl, m))) return rc;
-    if ((B && ldb < 0) || (dB && lddb < 0)) return refuse(SPMV_HIP_E_ARG, where, "need ldb >= 0 and lddb >= 0");
-    if (!dQ && !dK && !dV && !dB) return SPMV_HIP_OK; /* nothing wanted: no work, the handle's state is not looked at */
-    if ((rc = resident_prologue(handle, where, RESIDENT_NOT_REORDERED, m, RowPtr, ColIdx, Matrix_Val, &st))) return rc;
-    if ((rc = attention_backward_tables(handle, st, where, dK || dV))) return rc; /* only dB (or dQ) wanted: no transpose */
-    return report(spmv_shim_attention_gqa_backward_lse(st->dev, heads, kv_heads, (int) st->opts.v[SPMV_OPT_ATTENTION_BACKWARD_HEADS], k, dv, scale, Q, ldq, K, ldk, V, ldv, B, ldb,
-                                                       G, ldg, O, ldo, L, ldl, dQ, lddq, dK, lddk, dV, lddv, dB, lddb), where); /* a plane stride below nnz: refused there, nothing written */
+    spmv_attention_backward_call c = {.heads = heads, .kv_heads = kv_heads, .k = k, .dv = dv, .scale = scale, .q = Q, .ldq = ldq, .kk = K, .ldk = ldk, .v = V, .ldv = ldv,
+                                      .bias = B, .ldb = ldb, .g = G, .ldg = ldg, .stats = 1, .o = O, .ldo = ldo, .lse = L, .ldl = ldl,
+                                      .dq = dQ, .lddq = lddq, .dk = dK, .lddk = lddk, .dvo = dV, .lddv = lddv, .db = dB, .lddb = lddb};
+    return attention_backward_call(handle, "attention_gqa_backward_lse", 0, &c, m, RowPtr, ColIdx, Matrix_Val);
 }
 
 double spmv_hip_time_attention_gqa_backward_lse_launches(spmv_Handle_t h, int heads, int kv_heads, int k, int dv, double scale, const void *Q, long long ldq, const void *K,
@@ -1474,47 +1382,24 @@ double spmv_hip_time_attention_gqa_backward_lse_launches(spmv_Handle_t h, int he
                                                          long long ldo, const void *L, long long ldl, void *dQ, long long lddq, void *dK, long long lddk, void *dV, long long lddv,
                                                          void *dB, long long lddb, int warmup, int iters, float *ms_out)
 {
-    const char *where = "time_attention_gqa_backward_lse_launches";
-    spmv_hip_state *st;
-    if (attention_gqa_backward_args(h, where, heads, kv_heads, k, dv, Q, ldq, K, ldk, V, ldv, G, ldg, dQ, lddq, dK, lddk, dV, lddv, 1) ||
-        attention_lse_inputs(where, heads, dv, O, ldo, L, ldl, 1)) return -1.0;
-    if ((B && ldb < 0) || (dB && lddb < 0)) { (void) refuse(SPMV_HIP_E_ARG, where, "need ldb >= 0 and lddb >= 0"); return -1.0; }
-    if (resident_state(h, where, RESIDENT_NOT_REORDERED, &st) || attention_backward_tables(h, st, where, dK || dV)) return -1.0;
-    return report_time(spmv_shim_time_attention_gqa_backward_lse(st->dev, heads, kv_heads, (int) st->opts.v[SPMV_OPT_ATTENTION_BACKWARD_HEADS], k, dv, scale, Q, ldq, K, ldk, V,
-                                                                 ldv, B, ldb, G, ldg, O, ldo, L, ldl, dQ, lddq, dK, lddk, dV, lddv, dB, lddb, warmup, iters, ms_out), where);
+    spmv_attention_backward_call c = {.heads = heads, .kv_heads = kv_heads, .k = k, .dv = dv, .scale = scale, .q = Q, .ldq = ldq, .kk = K, .ldk = ldk, .v = V, .ldv = ldv,
+                                      .bias = B, .ldb = ldb, .g = G, .ldg = ldg, .stats = 1, .o = O, .ldo = ldo, .lse = L, .ldl = ldl,
+                                      .dq = dQ, .lddq = lddq, .dk = dK, .lddk = lddk, .dvo = dV, .lddv = lddv, .db = dB, .lddb = lddb};
+    return attention_backward_time(h, "time_attention_gqa_backward_lse_launches", 0, &c, warmup, iters, ms_out);
 }
 
-/* ---------------------------------------------------------------- the backward on 16-bit Q, K, V and G */
-/* the type rules ahead of the gate, like attention_16_types; O and L: both or neither */
-static int attention_backward_16_rules(spmv_Handle_t h, const char *where, int io_type, int dq_type, int dkv_type, int heads, int dv, const void *O, long long ldo, const void *L,
-                                       long long ldl, int m)
-{
-    if (h->data_size != sizeof(float) && h->data_size != 0) return refuse(SPMV_HIP_E_ARG, where, "16-bit operands need an fp32 handle");
-    if (io_type != SPMV_HIP_T_F16 && io_type != SPMV_HIP_T_BF16) return refuse(SPMV_HIP_E_ARG, where, "io_type must be SPMV_HIP_T_F16 or SPMV_HIP_T_BF16");
-    if (dq_type != SPMV_HIP_T_HANDLE && dq_type != io_type) return refuse(SPMV_HIP_E_ARG, where, "dq_type must be SPMV_HIP_T_HANDLE or equal to io_type");
-    if (dkv_type != SPMV_HIP_T_HANDLE && dkv_type != io_type) return refuse(SPMV_HIP_E_ARG, where, "dkv_type must be SPMV_HIP_T_HANDLE or equal to io_type");
-    if (m > 0 && (O == NULL) != (L == NULL)) return refuse(SPMV_HIP_E_ARG, where, "O and L are given together or not at all");
-    if (O && L) return attention_lse_inputs(where, heads, dv, O, ldo, L, ldl, m);
-    return SPMV_HIP_OK;
-}
-
+/* O and L: both given, the row pass is driven by them; both NULL, it normalises by itself; one of the two while m > 0 is refused by the rules */
 int spmv_hip_attention_gqa_backward_16(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
                                        const void *Matrix_Val, int heads, int kv_heads, int k, int dv, double scale, int io_type,
                                        const void *Q, long long ldq, const void *K, long long ldk, const void *V, long long ldv,
                                        const void *B, long long ldb, const void *G, long long ldg, const void *O, long long ldo, const void *L, long long ldl,
                                        int dq_type, void *dQ, long long lddq, int dkv_type, void *dK, long long lddk, void *dV, long long lddv, void *dB, long long lddb)
 {
-    const char *where = "attention_gqa_backward_16";
-    spmv_hip_state *st;
-    int rc;
-    if ((rc = attention_gqa_backward_args(handle, where, heads, kv_heads, k, dv, Q, ldq, K, ldk, V, ldv, G, ldg, dQ, lddq, dK, lddk, dV, lddv, m)) ||
-        (rc = attention_backward_16_rules(handle, where, io_type, dq_type, dkv_type, heads, dv, O, ldo, L, ldl, m))) return rc;
-    if ((B && ldb < 0) || (dB && lddb < 0)) return refuse(SPMV_HIP_E_ARG, where, "need ldb >= 0 and lddb >= 0");
-    if (!dQ && !dK && !dV && !dB) return SPMV_HIP_OK; /* nothing wanted: no work, the handle's state is not looked at */
-    if ((rc = resident_prologue(handle, where, RESIDENT_NOT_REORDERED, m, RowPtr, ColIdx, Matrix_Val, &st))) return rc;
-    if ((rc = attention_backward_tables(handle, st, where, dK || dV))) return rc; /* only dB (or dQ) wanted: no transpose */
-    return report(spmv_shim_attention_gqa_backward_16(st->dev, heads, kv_heads, (int) st->opts.v[SPMV_OPT_ATTENTION_BACKWARD_HEADS], k, dv, scale, io_type, Q, ldq, K, ldk, V, ldv,
-                                                      B, ldb, G, ldg, O, ldo, L, ldl, dq_type, dQ, lddq, dkv_type, dK, lddk, dV, lddv, dB, lddb), where);
+    spmv_attention_backward_call c = {.heads = heads, .kv_heads = kv_heads, .k = k, .dv = dv, .scale = scale, .io_type = io_type, .dq_type = dq_type, .dkv_type = dkv_type,
+                                      .q = Q, .ldq = ldq, .kk = K, .ldk = ldk, .v = V, .ldv = ldv, .bias = B, .ldb = ldb, .g = G, .ldg = ldg,
+                                      .stats = O && L, .o = O, .ldo = ldo, .lse = L, .ldl = ldl,
+                                      .dq = dQ, .lddq = lddq, .dk = dK, .lddk = lddk, .dvo = dV, .lddv = lddv, .db = dB, .lddb = lddb};
+    return attention_backward_call(handle, "attention_gqa_backward_16", ATTENTION_16, &c, m, RowPtr, ColIdx, Matrix_Val);
 }
 
 double spmv_hip_time_attention_gqa_backward_16_launches(spmv_Handle_t h, int heads, int kv_heads, int k, int dv, double scale, int io_type, const void *Q, long long ldq,
@@ -1522,15 +1407,11 @@ double spmv_hip_time_attention_gqa_backward_16_launches(spmv_Handle_t h, int hea
                                                         const void *O, long long ldo, const void *L, long long ldl, int dq_type, void *dQ, long long lddq, int dkv_type, void *dK,
                                                         long long lddk, void *dV, long long lddv, void *dB, long long lddb, int warmup, int iters, float *ms_out)
 {
-    const char *where = "time_attention_gqa_backward_16_launches";
-    spmv_hip_state *st;
-    if (attention_gqa_backward_args(h, where, heads, kv_heads, k, dv, Q, ldq, K, ldk, V, ldv, G, ldg, dQ, lddq, dK, lddk, dV, lddv, 1) ||
-        attention_backward_16_rules(h, where, io_type, dq_type, dkv_type, heads, dv, O, ldo, L, ldl, 1)) return -1.0;
-    if ((B && ldb < 0) || (dB && lddb < 0)) { (void) refuse(SPMV_HIP_E_ARG, where, "need ldb >= 0 and lddb >= 0"); return -1.0; }
-    if (resident_state(h, where, RESIDENT_NOT_REORDERED, &st) || attention_backward_tables(h, st, where, dK || dV)) return -1.0;
-    return report_time(spmv_shim_time_attention_gqa_backward_16(st->dev, heads, kv_heads, (int) st->opts.v[SPMV_OPT_ATTENTION_BACKWARD_HEADS], k, dv, scale, io_type, Q, ldq, K, ldk,
-                                                                V, ldv, B, ldb, G, ldg, O, ldo, L, ldl, dq_type, dQ, lddq, dkv_type, dK, lddk, dV, lddv, dB, lddb, warmup, iters,
-                                                                ms_out), where);
+    spmv_attention_backward_call c = {.heads = heads, .kv_heads = kv_heads, .k = k, .dv = dv, .scale = scale, .io_type = io_type, .dq_type = dq_type, .dkv_type = dkv_type,
+                                      .q = Q, .ldq = ldq, .kk = K, .ldk = ldk, .v = V, .ldv = ldv, .bias = B, .ldb = ldb, .g = G, .ldg = ldg,
+                                      .stats = O && L, .o = O, .ldo = ldo, .lse = L, .ldl = ldl,
+                                      .dq = dQ, .lddq = lddq, .dk = dK, .lddk = lddk, .dvo = dV, .lddv = lddv, .db = dB, .lddb = lddb};
+    return attention_backward_time(h, "time_attention_gqa_backward_16_launches", ATTENTION_16, &c, warmup, iters, ms_out);
 }
 
 /* ---------------------------------------------------------------- conjugate gradients on the device */

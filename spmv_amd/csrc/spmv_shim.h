@@ -135,50 +135,61 @@ int spmv_shim_row_softmax_backward(spmv_dev *d, const void *p, const void *g, vo
 /* `iters` forward launches timed with events on the handle's stream (device S / Out); mean ms, < 0 on failure */
 double spmv_shim_time_row_softmax(spmv_dev *d, const void *s, void *out, int warmup, int iters, float *ms_out);
 
-/* ---- O = softmax_rows(scale * Q K^T on the resident pattern) V in one pass (shim/attention.hpp; spmv_hip_attention) ----
- * Q m x k, K n x k, V n x dv, O m x dv, row-major with leading dimensions; host or device pointers each.  Needs the resident ColIdx; the
- * resident values are neither read nor written.  Builds spmm's tables and the long rows' parking space at the first call. */
-int spmv_shim_attention(spmv_dev *d, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v, long long ldv, void *o,
-                        long long ldo);
-/* `iters` calls timed with events on the handle's stream (device Q / K / V / O); mean ms, < 0 on failure */
-double spmv_shim_time_attention(spmv_dev *d, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v, long long ldv, void *o,
-                                long long ldo, int warmup, int iters, float *ms_out);
-/* `heads` heads side by side in the rows (spmv_hip_attention_heads): Q m x heads*k, K n x heads*k, V n x heads*dv, O m x heads*dv; head h is
- * spmv_shim_attention on the columns from h*k and h*dv, in the same two launches.  heads = 1 is spmv_shim_attention. */
-int spmv_shim_attention_heads(spmv_dev *d, int heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v, long long ldv,
-                              void *o, long long ldo);
-double spmv_shim_time_attention_heads(spmv_dev *d, int heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v,
-                                      long long ldv, void *o, long long ldo, int warmup, int iters, float *ms_out);
+/* ---- the fused attention over the resident pattern and its backward: one argument struct each (shim/attention.hpp, shim/attention_backward.hpp) ----
+ * What every spmv_hip_attention* entry point passes down; an entry point without a feature fills it as heads = kv_heads = 1, bias = NULL,
+ * lse = NULL, the types SPMV_HIP_T_HANDLE.  The operand conventions, once:
+ *   - k and dv are ONE head's widths.  Q, G, O, dQ are `heads` blocks wide (heads * k, heads * dv columns), K, V, dK, dV `kv_heads` blocks
+ *     (kv_heads * k, kv_heads * dv); heads is a multiple of kv_heads and query head h reads block h / (heads / kv_heads).  Row-major, every
+ *     leading dimension at least the operand's width and counted in elements of the operand's own type; host or device pointers each.
+ *   - bias: NULL (ldb ignored) or planes of nnz elements in CSR order, QUERY head h's at bias + h * ldb; ldb = 0: one plane for all heads, else
+ *     ldb >= nnz.  lse: `heads` planes ldl >= m apart, head h's row i at lse + h * ldl + i.  db: `heads` planes lddb >= nnz apart.  bias, db, lse
+ *     and the backward's o are in the handle's precision whatever the types say.
+ *   - io_type SPMV_HIP_T_HANDLE: every operand in the handle's precision, and the output types are SPMV_HIP_T_HANDLE too.  io_type SPMV_HIP_T_F16 or
+ *     _BF16 (a float handle): the element type of Q, K, V and G; an output type (o_type of O, dq_type of dQ, dkv_type of dK and dV) is
+ *     SPMV_HIP_T_HANDLE (float) or io_type.  Anything else, or a double handle with a 16-bit io_type: SPMV_HIP_E_ARG.
+ *   - An output pointer that is NULL is not wanted and its leading dimension is not looked at (the forward's O is always wanted).
+ *   - A refusal (SPMV_HIP_E_ARG: a bad size, stride or type, a NULL operand while m > 0) writes nothing.
+ * The resident values are neither read nor written; the resident ColIdx is needed (spmv_shim_restore_columns). */
+typedef struct spmv_attention_call {
+    int heads, kv_heads, k, dv;
+    double scale;
+    int io_type, o_type;
+    const void *q;    long long ldq;  /* m x heads * k */
+    const void *kk;   long long ldk;  /* n x kv_heads * k */
+    const void *v;    long long ldv;  /* n x kv_heads * dv */
+    const void *bias; long long ldb;
+    void *o;          long long ldo;  /* m x heads * dv */
+    void *lse;        long long ldl;  /* NULL: the rows' log-sum-exps are not wanted */
+} spmv_attention_call;
 
-/* an additive bias per head and entry (spmv_hip_attention_bias): bias NULL (ldb ignored: spmv_shim_attention_heads) or planes of nnz elements in
- * CSR order, head h's at bias + h*ldb, ldb = 0 one plane for all heads; host or device pointer.  0 < ldb < nnz or ldb < 0: SPMV_HIP_E_ARG */
-int spmv_shim_attention_bias(spmv_dev *d, int heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v, long long ldv,
-                             const void *bias, long long ldb, void *o, long long ldo);
-double spmv_shim_time_attention_bias(spmv_dev *d, int heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v,
-                                     long long ldv, const void *bias, long long ldb, void *o, long long ldo, int warmup, int iters, float *ms_out);
+typedef struct spmv_attention_backward_call {
+    int heads, kv_heads, k, dv;
+    int max_heads; /* heads per round of the two passes: option "attention_backward_heads"; 0: what fits an eighth of the device's memory */
+    double scale;
+    int io_type, dq_type, dkv_type;
+    const void *q;    long long ldq;
+    const void *kk;   long long ldk;
+    const void *v;    long long ldv;
+    const void *bias; long long ldb;
+    const void *g;    long long ldg;  /* dL/dO, m x heads * dv */
+    /* stats != 0: the row pass is driven by o and lse, the FINAL output and log-sum-exp of the attention this handle's entries are a part of
+     * (P = exp(t - L), D = <G row, O row>).  stats == 0: it normalises by itself and o and lse are not read -- but with a 16-bit io_type one of
+     * the two alone while m > 0 is SPMV_HIP_E_ARG (spmv_hip_attention_gqa_backward_16: both or neither, stats = both) */
+    int stats;
+    const void *o;    long long ldo;
+    const void *lse;  long long ldl;
+    void *dq;         long long lddq;
+    void *dk;         long long lddk; /* dk or dvo wanted: the attached transpose with its column indices resident is needed (its values are not read) */
+    void *dvo;        long long lddv;
+    void *db;         long long lddb; /* written by the row pass alone: with only db (or dq) wanted the transpose is not looked at */
+} spmv_attention_backward_call;
 
-/* fewer K / V heads than query heads (spmv_hip_attention_gqa): K is kv_heads * k and V kv_heads * dv wide, heads % kv_heads == 0, query head h reads
- * block h / (heads / kv_heads); bias as above, a plane per QUERY head.  kv_heads = heads is spmv_shim_attention_bias */
-int spmv_shim_attention_gqa(spmv_dev *d, int heads, int kv_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v,
-                            long long ldv, const void *bias, long long ldb, void *o, long long ldo);
-double spmv_shim_time_attention_gqa(spmv_dev *d, int heads, int kv_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
-                                    const void *v, long long ldv, const void *bias, long long ldb, void *o, long long ldo, int warmup, int iters, float *ms_out);
-
-/* with the rows' log-sum-exps (spmv_hip_attention_gqa_lse): lse NULL (ldl ignored: spmv_shim_attention_gqa) or `heads` planes ldl >= m apart, head h's
- * row i at lse + h*ldl + i; host or device pointer.  ldl < m: SPMV_HIP_E_ARG, nothing written */
-int spmv_shim_attention_gqa_lse(spmv_dev *d, int heads, int kv_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v,
-                                long long ldv, const void *bias, long long ldb, void *o, long long ldo, void *lse, long long ldl);
-double spmv_shim_time_attention_gqa_lse(spmv_dev *d, int heads, int kv_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
-                                        const void *v, long long ldv, const void *bias, long long ldb, void *o, long long ldo, void *lse, long long ldl, int warmup, int iters,
-                                        float *ms_out);
-/* on 16-bit Q, K and V (spmv_hip_attention_gqa_lse_16; a float handle): io_type SPMV_HIP_T_F16 or _BF16 is the element type of q, kk and v, o_type
- * SPMV_HIP_T_HANDLE (o is float) or io_type; leading dimensions in elements of the operand's own type; bias and lse float.  A bad type or a double
- * handle: SPMV_HIP_E_ARG, nothing written */
-int spmv_shim_attention_gqa_lse_16(spmv_dev *d, int heads, int kv_heads, int k, int dv, double scale, int io_type, const void *q, long long ldq, const void *kk, long long ldk,
-                                   const void *v, long long ldv, const void *bias, long long ldb, void *o, long long ldo, int o_type, void *lse, long long ldl);
-double spmv_shim_time_attention_gqa_lse_16(spmv_dev *d, int heads, int kv_heads, int k, int dv, double scale, int io_type, const void *q, long long ldq, const void *kk,
-                                           long long ldk, const void *v, long long ldv, const void *bias, long long ldb, void *o, long long ldo, int o_type, void *lse,
-                                           long long ldl, int warmup, int iters, float *ms_out);
+/* O = softmax_rows(scale * Q K^T + bias on the resident pattern) V in one pass, and the log-sum-exps.  Builds spmm's tables and the long rows'
+ * parking space at the first call. */
+int spmv_shim_attention(spmv_dev *d, const spmv_attention_call *c);
+/* `iters` calls timed with events on the handle's stream; mean ms, < 0 on failure.  Every operand that is given must be a device pointer, and
+ * Q, K, V and O must be given. */
+double spmv_shim_time_attention(spmv_dev *d, const spmv_attention_call *c, int warmup, int iters, float *ms_out);
 /* two partial results merged by their log-sum-exps (spmv_hip_attention_merge): the O operands m x heads*dv, the L operands `heads` planes of m; o may
  * be o1 and l may be l1; l NULL: not wanted.  The matrix is not read.  A plane stride below m: SPMV_HIP_E_ARG, nothing written */
 int spmv_shim_attention_merge(spmv_dev *d, int heads, int dv, const void *o1, long long ldo1, const void *l1, long long ldl1, const void *o2, long long ldo2, const void *l2,
@@ -186,71 +197,13 @@ int spmv_shim_attention_merge(spmv_dev *d, int heads, int dv, const void *o1, lo
 double spmv_shim_time_attention_merge(spmv_dev *d, int heads, int dv, const void *o1, long long ldo1, const void *l1, long long ldl1, const void *o2, long long ldo2,
                                       const void *l2, long long ldl2, void *o, long long ldo, void *l, long long ldl, int warmup, int iters, float *ms_out);
 
-/* ---- dQ, dK, dV of the fused attention in two passes (shim/attention_backward.hpp; spmv_hip_attention_backward) ----
- * Q m x k, K n x k, V n x dv, G m x dv; dq m x k, dk n x k, dv_out n x dv or NULL (not wanted); row-major with leading dimensions; host or
- * device pointers each.  Needs the resident ColIdx and, when dk or dv_out is wanted, the attached transpose with its column indices resident
- * (its values are not read).  The resident values are neither read nor written.  Builds spmm's tables (the transpose's too) and the two
- * nnz-sized arrays at the first call. */
-int spmv_shim_attention_backward(spmv_dev *d, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v, long long ldv,
-                                 const void *g, long long ldg, void *dq, long long lddq, void *dk, long long lddk, void *dv_out, long long lddv);
-/* `iters` calls timed with events on the handle's stream (device operands); mean ms, < 0 on failure */
-double spmv_shim_time_attention_backward(spmv_dev *d, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk, const void *v, long long ldv,
-                                         const void *g, long long ldg, void *dq, long long lddq, void *dk, long long lddk, void *dv_out, long long lddv, int warmup, int iters,
-                                         float *ms_out);
-
-/* `heads` heads side by side in the rows (spmv_hip_attention_heads_backward): Q, K, dq, dk heads*k columns wide, V, G, dv_out heads*dv; head h
- * is spmv_shim_attention_backward on the columns from h*k and h*dv.  ceil(heads / hg) rounds of the two passes, the head loop inside the
- * kernels; hg = min(heads, max_heads) when max_heads > 0 (option "attention_backward_heads"), else what fits an eighth of the device's memory.
- * The two arrays hold hg planes of nnz elements, grown when a call needs more.  heads = 1 is spmv_shim_attention_backward. */
-int spmv_shim_attention_heads_backward(spmv_dev *d, int heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
-                                       const void *v, long long ldv, const void *g, long long ldg, void *dq, long long lddq, void *dk, long long lddk, void *dv_out,
-                                       long long lddv);
-double spmv_shim_time_attention_heads_backward(spmv_dev *d, int heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
-                                               const void *v, long long ldv, const void *g, long long ldg, void *dq, long long lddq, void *dk, long long lddk, void *dv_out,
-                                               long long lddv, int warmup, int iters, float *ms_out);
-
-/* with the bias of spmv_shim_attention_bias and its gradient (spmv_hip_attention_bias_backward): db NULL (not wanted) or `heads` planes
- * lddb >= nnz apart, written by the row pass alone (only db wanted: no column pass, the transpose is not looked at).  bias and db NULL is
- * spmv_shim_attention_heads_backward */
-int spmv_shim_attention_bias_backward(spmv_dev *d, int heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
-                                      const void *v, long long ldv, const void *bias, long long ldb, const void *g, long long ldg, void *dq, long long lddq, void *dk,
-                                      long long lddk, void *dv_out, long long lddv, void *db, long long lddb);
-double spmv_shim_time_attention_bias_backward(spmv_dev *d, int heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk, long long ldk,
-                                              const void *v, long long ldv, const void *bias, long long ldb, const void *g, long long ldg, void *dq, long long lddq, void *dk,
-                                              long long lddk, void *dv_out, long long lddv, void *db, long long lddb, int warmup, int iters, float *ms_out);
-
-/* with kv_heads K / V heads (spmv_hip_attention_gqa_backward): K, V, dk and dv_out are kv_heads blocks wide, dk / dv_out of a block the sum of its
- * query heads' terms in ascending head; bias and db a plane per QUERY head.  kv_heads = heads is spmv_shim_attention_bias_backward */
-int spmv_shim_attention_gqa_backward(spmv_dev *d, int heads, int kv_heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk,
-                                     long long ldk, const void *v, long long ldv, const void *bias, long long ldb, const void *g, long long ldg, void *dq, long long lddq,
-                                     void *dk, long long lddk, void *dv_out, long long lddv, void *db, long long lddb);
-double spmv_shim_time_attention_gqa_backward(spmv_dev *d, int heads, int kv_heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk,
-                                             long long ldk, const void *v, long long ldv, const void *bias, long long ldb, const void *g, long long ldg, void *dq,
-                                             long long lddq, void *dk, long long lddk, void *dv_out, long long lddv, void *db, long long lddb, int warmup, int iters,
-                                             float *ms_out);
-
-/* driven by the final output o (m x heads*dv) and log-sum-exp lse (`heads` planes ldl >= m apart) of the attention this handle's entries are a part
- * of (spmv_hip_attention_gqa_backward_lse): P = exp(t - L), D = <G row, O row>; everything else as above */
-int spmv_shim_attention_gqa_backward_lse(spmv_dev *d, int heads, int kv_heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk,
-                                         long long ldk, const void *v, long long ldv, const void *bias, long long ldb, const void *g, long long ldg, const void *o, long long ldo,
-                                         const void *lse, long long ldl, void *dq, long long lddq, void *dk, long long lddk, void *dv_out, long long lddv, void *db, long long lddb);
-double spmv_shim_time_attention_gqa_backward_lse(spmv_dev *d, int heads, int kv_heads, int max_heads, int k, int dv, double scale, const void *q, long long ldq, const void *kk,
-                                                 long long ldk, const void *v, long long ldv, const void *bias, long long ldb, const void *g, long long ldg, const void *o,
-                                                 long long ldo, const void *lse, long long ldl, void *dq, long long lddq, void *dk, long long lddk, void *dv_out, long long lddv,
-                                                 void *db, long long lddb, int warmup, int iters, float *ms_out);
-
-/* on 16-bit Q, K, V and G (spmv_hip_attention_gqa_backward_16; a float handle): io_type SPMV_HIP_T_F16 or _BF16 is their element type, dq_type that of
- * dq and dkv_type that of dk and dv_out, each SPMV_HIP_T_HANDLE (float) or io_type; leading dimensions in elements of the operand's own type; bias,
- * db, o and lse float.  o and lse both NULL: spmv_shim_attention_gqa_backward's row pass; both given: spmv_shim_attention_gqa_backward_lse's.  A bad
- * type, a double handle, or one of o and lse alone while m > 0: SPMV_HIP_E_ARG, nothing written */
-int spmv_shim_attention_gqa_backward_16(spmv_dev *d, int heads, int kv_heads, int max_heads, int k, int dv, double scale, int io_type, const void *q, long long ldq, const void *kk,
-                                        long long ldk, const void *v, long long ldv, const void *bias, long long ldb, const void *g, long long ldg, const void *o, long long ldo,
-                                        const void *lse, long long ldl, int dq_type, void *dq, long long lddq, int dkv_type, void *dk, long long lddk, void *dv_out, long long lddv,
-                                        void *db, long long lddb);
-double spmv_shim_time_attention_gqa_backward_16(spmv_dev *d, int heads, int kv_heads, int max_heads, int k, int dv, double scale, int io_type, const void *q, long long ldq,
-                                                const void *kk, long long ldk, const void *v, long long ldv, const void *bias, long long ldb, const void *g, long long ldg,
-                                                const void *o, long long ldo, const void *lse, long long ldl, int dq_type, void *dq, long long lddq, int dkv_type, void *dk,
-                                                long long lddk, void *dv_out, long long lddv, void *db, long long lddb, int warmup, int iters, float *ms_out);
+/* dQ, dK, dV and dB of spmv_shim_attention in two passes per round of up to hg heads (hg = min(heads, max_heads) when max_heads > 0, else by the
+ * memory rule); dK / dV of a K / V block are the sums of its query heads' terms in ascending head.  Builds spmm's tables (the transpose's too)
+ * and the two arrays of hg planes of nnz elements at the first call, grown when a call needs more. */
+int spmv_shim_attention_backward(spmv_dev *d, const spmv_attention_backward_call *c);
+/* `iters` calls timed with events on the handle's stream; mean ms, < 0 on failure.  Every operand that is given must be a device pointer, and
+ * Q, K, V, G and, with stats, O and L must be given. */
+double spmv_shim_time_attention_backward(spmv_dev *d, const spmv_attention_backward_call *c, int warmup, int iters, float *ms_out);
 
 /* ---- preconditioned conjugate gradients on the resident matrix (shim/cg.hpp; spmv_hip_cg) ----
  * B, X, opt->Dinv: m elements, host or device pointers each.  The multiply is the built schedule's own launch.  Builds the workspace at the first call.
