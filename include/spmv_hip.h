@@ -830,6 +830,48 @@ int spmv_hip_cg(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *Ro
                 const void *Matrix_Val, const void *B, void *X,
                 const spmv_hip_cg_options *opt, spmv_hip_cg_result *res);
 
+/* ---- BiCGStab on the device: A x = b for a matrix that need not be symmetric --------------------
+ * Right-preconditioned BiCGStab for a square A (m = n) with an optional diagonal preconditioner: per iteration two of the handle's own
+ * multiplies -- spmv()'s schedule and bits -- and five vector kernels.  alpha, omega, beta and the stop tests are formed on the device; the
+ * host enqueues check_every iterations, then looks at a small state once.
+ * The options, the result, the status values and EVERY rule of spmv_hip_cg above hold word for word: the return value, the synchronous call,
+ * the CSR arguments, host or device B / X / Dinv, use_x0, history (max_iterations + 1 doubles), m = 0, bb = 0, option "reorder", the errors.
+ * What differs:
+ *   - Dinv is a RIGHT preconditioner: the iteration runs on A diag(Dinv) and x = diag(Dinv) y is accumulated directly, so X solves the
+ *     original system and r, rr, history and the stop test rr <= max(rtol^2 * bb, atol^2) belong to the original system whatever Dinv is.
+ *   - status: _BREAKDOWN: <rhat,v> = 0 or rho = 0 (nothing of the iteration is applied), or <t,t> = 0, <t,s> = 0 or omega = 0 (X keeps the half
+ *     step x + alpha ph); _NONFINITE: a NaN or infinity in any dot, alpha, omega or beta.  An iteration counts from its half step on.
+ *   - Workspace: r, rhat, p, v, t and y (m elements each, y only used with Dinv), eight partial arrays and the state in one block of the
+ *     solver's own, and the history's device copy in another: allocated at the first BiCGStab solve, freed at destroy / clear /
+ *     re-inspection, counted in spmv_hip_info.device_bytes.  spmv_hip_cg's workspace is neither shared nor grown.
+ *
+ * The arithmetic contract -- bits, not a tolerance; tests/bicgstab_cases.py restates it in numpy.  Elements are of the handle's type T.  Every
+ * dot is spmv_hip_cg's dot exactly (the same P, L, slot, step, wave and workgroup trees; fp64 products and sums, no fma).  alpha, omega and
+ * beta are formed in fp64 and rounded to T ONCE.  The vector updates are in T, every multiply and every add a separate operation.
+ *   start:  x = 0, r = B  (or r = B - A*x0);  rhat = r;  p = r
+ *           rho = <rhat,r>, rr = <r,r>, bb = <B,B>;  history[0] = rr
+ *           nonfinite(bb, rr, rho) -> NONFINITE;  bb == 0 -> x = 0, rr = 0, CONVERGED;  rr <= thresh -> CONVERGED          (0 iterations)
+ *   iteration k = 1, 2, ...:
+ *           ph = Dinv*p (ph = p without Dinv);  v = A*ph                          -- the handle's multiply, spmv()'s bits
+ *           rv = <rhat,v>;  nonfinite(rv, rho) -> NONFINITE;  rv == 0 or rho == 0 -> BREAKDOWN   (nothing applied, iterations = k - 1)
+ *           alpha = T(rho / rv);  nonfinite(alpha) -> NONFINITE                                    (the same)
+ *           x = x + alpha*ph;  s = r - alpha*v;  ss = <s,s>                       -- from here on iterations = k
+ *           nonfinite(ss) -> NONFINITE;  ss <= thresh -> CONVERGED                (the half step: rr = history[k] = ss)
+ *           sh = Dinv*s (sh = s);  t = A*sh
+ *           ts = <t,s>, tt = <t,t>;  nonfinite -> NONFINITE;  tt == 0 or ts == 0 -> BREAKDOWN    (rr = history[k] = ss, x keeps the half step)
+ *           omega = T(ts / tt);  nonfinite(omega) -> NONFINITE;  omega == 0 -> BREAKDOWN          (the same)
+ *           x = x + omega*sh;  r = s - omega*t;  rho_new = <rhat,r>, rr = <r,r>;  history[k] = rr
+ *           nonfinite(rr, rho_new) -> NONFINITE;  rr <= thresh -> CONVERGED
+ *           beta = T((rho_new / rho) * (double(alpha) / double(omega)));  nonfinite(beta) -> NONFINITE
+ *           p = r + beta*(p - omega*v)                                            -- in T: omega*v, p - that, beta * that, r + that
+ *           rho = rho_new
+ *   k == max_iterations without a status -> MAX_ITERATIONS.  thresh = max(rtol^2 * bb, atol^2).
+ *   Consequences: res.rr and res.bb belong to the returned X; Dinv = all ones gives exactly the bits of Dinv = NULL; X, iterations, rr and
+ *   history are bit-identical run to run and for every check_every (unless the handle was created with option "deterministic" = 0). */
+int spmv_hip_bicgstab(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                      const void *Matrix_Val, const void *B, void *X,
+                      const spmv_hip_cg_options *opt, spmv_hip_cg_result *res);
+
 #endif /* SPMV_HIP_EXT_H */
 
 #if defined(__cplusplus)

@@ -169,6 +169,8 @@ FUNCTIONS = {
     **_attention("attention_gqa_backward_16", _GQA + _TYPE, _QKV + _B + _G + _O + _L + _TYPE + _DQ + _TYPE + _DK + _DV + _DB),
     "spmv_hip_cg": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, _V, _V, C.POINTER(spmv_hip_cg_options), C.POINTER(spmv_hip_cg_result)]),
     "spmv_hip_time_cg_iterations": (C.c_double, [spmv_Handle_t, _V, _V, C.POINTER(spmv_hip_cg_options), C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "spmv_hip_bicgstab": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, _V, _V, C.POINTER(spmv_hip_cg_options), C.POINTER(spmv_hip_cg_result)]),
+    "spmv_hip_time_bicgstab_iterations": (C.c_double, [spmv_Handle_t, _V, _V, C.POINTER(spmv_hip_cg_options), C.c_int, C.c_int, C.POINTER(C.c_float)]),
     # include/spmv_io.h (host only)
     "spmv_io_read_mtx": (C.c_int, [C.c_char_p, C.c_size_t, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_V)]),
     "spmv_io_cache_path": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t]),
@@ -958,6 +960,27 @@ def time_cg_iterations(handle, B, X, iterations, x0=False, dinv=None, warmup=2, 
     return _timed("spmv_hip_time_cg_iterations", (handle, _ptr(B), _ptr(X), C.byref(opt)), warmup, iters)
 
 
+def bicgstab(handle, m, RowPtr, ColIdx, Matrix_Val, B, X, rtol=1e-8, atol=0.0, max_iterations=1000, check_every=0, x0=False, dinv=None, history=False,
+             check=True):
+    """Solve A x = B by right-preconditioned BiCGStab on the device (spmv_hip_bicgstab; A need not be symmetric): B, X, dinv of m elements, host
+    or device; x0: X holds the initial guess.  -> (rc, result dict: status, status_name, iterations, rr, bb[, history: rr after iteration
+    0 .. iterations]), as cg()."""
+    opt, hist = _cg_options(rtol, atol, max_iterations, check_every, x0, dinv, history)
+    res = spmv_hip_cg_result()
+    rc = _checked(load().spmv_hip_bicgstab(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), _ptr(B), _ptr(X), C.byref(opt), C.byref(res)), "spmv_hip_bicgstab", check)
+    out = {"status": res.status, "status_name": CG_STATUS[res.status] if 0 <= res.status < len(CG_STATUS) else "?", "iterations": res.iterations, "rr": res.rr, "bb": res.bb}
+    if hist is not None:
+        out["history"] = hist[:res.iterations + 1].copy() if rc == 0 else hist[:0].copy()
+    return rc, out
+
+
+def time_bicgstab_iterations(handle, B, X, iterations, x0=False, dinv=None, warmup=2, iters=20):
+    """-> (mean ms per run, per-run ms array) of `iters` runs of `iterations` BiCGStab iterations each, stop tests off, on device B / X / dinv
+    (spmv_hip_time_bicgstab_iterations)."""
+    opt, _ = _cg_options(0.0, 0.0, iterations, 0, x0, dinv, False)
+    return _timed("spmv_hip_time_bicgstab_iterations", (handle, _ptr(B), _ptr(X), C.byref(opt)), warmup, iters)
+
+
 def _take_csr(m, n, nnz, rp, ci, va, dtype):
     """Copy malloc'ed C arrays into numpy arrays and free the C side."""
     from .synth import CSR
@@ -1122,6 +1145,21 @@ class Handle:
             x = self._like(b, (self.m,))
         rp, ci, va = self._keep
         _, res = cg(self.h, self.m, rp, ci, va, b, x, rtol, atol, max_iterations, check_every, x0, dinv, history)
+        if history:
+            return x, res, res.pop("history")
+        return x, res
+
+    def bicgstab(self, b, x=None, x0=False, rtol=1e-8, atol=0.0, max_iterations=1000, check_every=0, dinv=None, history=False):
+        """Solve A x = b by right-preconditioned BiCGStab that stays on the device (spmv_hip_bicgstab; A square, not necessarily symmetric).
+        The arguments and the return value are cg()'s: x is allocated like b when None (then x0 must be off); x0: x holds the initial guess;
+        dinv: None or 1 / diag(A) (Jacobi, applied from the right: x solves the original system).
+        -> (x, result dict) or (x, result dict, history) when history is set: rr after iteration 0 .. iterations."""
+        if x is None:
+            if x0:
+                raise ValueError("x0 needs an x that holds the initial guess")
+            x = self._like(b, (self.m,))
+        rp, ci, va = self._keep
+        _, res = bicgstab(self.h, self.m, rp, ci, va, b, x, rtol, atol, max_iterations, check_every, x0, dinv, history)
         if history:
             return x, res, res.pop("history")
         return x, res

@@ -193,7 +193,7 @@ enum { STAGE_X, STAGE_Y, STAGE_SPMM_X, STAGE_SPMM_Y, STAGE_SDDMM_U, STAGE_SDDMM_
        STAGE_ATT_L,                // the log-sum-exp planes spmv_hip_attention_gqa_lse writes
        STAGE_ATTB_O, STAGE_ATTB_L, // the final O and L spmv_hip_attention_gqa_backward_lse reads
        STAGE_MRG_O1, STAGE_MRG_L1, STAGE_MRG_O2, STAGE_MRG_L2, STAGE_MRG_O, STAGE_MRG_L, // spmv_hip_attention_merge's operands
-       STAGE_CG_B, STAGE_CG_X, STAGE_CG_DINV, // spmv_hip_cg's right-hand side, solution and diagonal preconditioner
+       STAGE_CG_B, STAGE_CG_X, STAGE_CG_DINV, // spmv_hip_cg's and spmv_hip_bicgstab's right-hand side, solution and diagonal preconditioner
        STAGE_COUNT };
 
 struct spmv_dev {
@@ -300,6 +300,10 @@ struct spmv_dev {
     // history (doubles, one per iteration + 1) in a block of its own, allocated when a solve wants one and grown when a later one needs more
     void *cg_ws = nullptr;
     StageBuf cg_hist;
+    // spmv_hip_bicgstab (shim/bicgstab.hpp): r, rhat, p, v, t, y (m elements each), the partial arrays and the state in ONE block of the solver's
+    // own, allocated at the first BiCGStab solve; its history likewise in a block of its own
+    void *bicg_ws = nullptr;
+    StageBuf bicg_hist;
     // spmv_hip_spmv_transpose (shim/transpose.hpp): A^T as a matrix of its own (n x m), planned and built like any; perm[p] = our index of its entry p.
     // val_gen counts spmv_shim_update_values calls; A^T's values are gathered again when tr_gen falls behind it.
     spmv_dev *tr = nullptr;

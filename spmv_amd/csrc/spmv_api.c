@@ -1445,3 +1445,24 @@ double spmv_hip_time_cg_iterations(spmv_Handle_t h, const void *B, void *X, cons
     if (st->m != st->n) { (void) refuse(SPMV_HIP_E_ARG, where, "the matrix is not square (m != n at create)"); return -1.0; }
     return report_time(spmv_shim_time_cg(st->dev, B, X, opt, warmup, iters, ms_out), where);
 }
+
+/* ---------------------------------------------------------------- BiCGStab on the device: spmv_hip_cg's rules, a matrix that need not be symmetric */
+int spmv_hip_bicgstab(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                      const void *Matrix_Val, const void *B, void *X, const spmv_hip_cg_options *opt, spmv_hip_cg_result *res)
+{
+    const char *where = "bicgstab";
+    spmv_hip_state *st;
+    int rc;
+    if ((rc = cg_args(handle, where, B, X, opt, res, m)) || (rc = resident_prologue(handle, where, 0, m, RowPtr, ColIdx, Matrix_Val, &st))) return rc;
+    if (st->m != st->n) return refuse(SPMV_HIP_E_ARG, where, "the matrix is not square (m != n at create)");
+    return report(spmv_shim_bicgstab(st->dev, B, X, opt, res), where);
+}
+
+double spmv_hip_time_bicgstab_iterations(spmv_Handle_t h, const void *B, void *X, const spmv_hip_cg_options *opt, int warmup, int iters, float *ms_out)
+{
+    const char *where = "time_bicgstab_iterations";
+    spmv_hip_state *st;
+    if (cg_args(h, where, B, X, opt, opt, 1) || resident_state(h, where, 0, &st)) return -1.0;
+    if (st->m != st->n) { (void) refuse(SPMV_HIP_E_ARG, where, "the matrix is not square (m != n at create)"); return -1.0; }
+    return report_time(spmv_shim_time_bicgstab(st->dev, B, X, opt, warmup, iters, ms_out), where);
+}

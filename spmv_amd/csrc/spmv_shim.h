@@ -212,6 +212,12 @@ int spmv_shim_cg(spmv_dev *d, const void *b, void *x, const spmv_hip_cg_options 
 /* `iters` runs of opt->max_iterations iterations each, the stop tests off, timed with events on the handle's stream (device B / X / Dinv); mean ms per run, < 0 on failure */
 double spmv_shim_time_cg(spmv_dev *d, const void *b, void *x, const spmv_hip_cg_options *opt, int warmup, int iters, float *ms_out);
 
+/* ---- right-preconditioned BiCGStab on the resident matrix (shim/bicgstab.hpp; spmv_hip_bicgstab) ----
+ * The operands, the options, the result and the return value are spmv_shim_cg's; the matrix need not be symmetric.  Builds a workspace of its own at the first call. */
+int spmv_shim_bicgstab(spmv_dev *d, const void *b, void *x, const spmv_hip_cg_options *opt, spmv_hip_cg_result *res);
+/* as spmv_shim_time_cg */
+double spmv_shim_time_bicgstab(spmv_dev *d, const void *b, void *x, const spmv_hip_cg_options *opt, int warmup, int iters, float *ms_out);
+
 /* the resident CSR arrays (device pointers; ColIdx may be NULL after spmv_shim_release_columns) */
 void spmv_shim_matrix_arrays(const spmv_dev *d, const int **rowptr, const int **colidx, const void **val);
 

@@ -42,6 +42,7 @@
 #include "kernels/attention_merge.hpp"
 #include "kernels/attention_backward.hpp"
 #include "kernels/cg.hpp"
+#include "kernels/bicgstab.hpp"
 
 using namespace spmv;
 
@@ -177,7 +178,7 @@ extern "C" void spmv_shim_matrix_destroy(spmv_dev *d)
     if (d->rowptr) (void) pool_free(d->rowptr);
     if (d->colidx) (void) pool_free(d->colidx);
     if (d->val) (void) pool_free(d->val);
-    for (void *p : {d->scratch8, (void *) d->spmm_split, (void *) d->spmm_longs, (void *) d->att_off, d->att_park, d->attb_p, d->attb_ds, d->attb_nk.p, d->attb_nv.p, d->cg_ws, d->cg_hist.p}) if (p) (void) pool_free(p);
+    for (void *p : {d->scratch8, (void *) d->spmm_split, (void *) d->spmm_longs, (void *) d->att_off, d->att_park, d->attb_p, d->attb_ds, d->attb_nk.p, d->attb_nv.p, d->cg_ws, d->cg_hist.p, d->bicg_ws, d->bicg_hist.p}) if (p) (void) pool_free(p);
     for (StageBuf &b : d->stage) if (b.p) (void) pool_free(b.p);
     delete d;
 }
@@ -531,6 +532,7 @@ extern "C" int spmv_shim_is_device_ptr(const void *p) { return is_device_ptr(p) 
 #include "shim/attention.hpp"
 #include "shim/attention_backward.hpp"
 #include "shim/cg.hpp"
+#include "shim/bicgstab.hpp"
 
 // The resident int32 ColIdx copy (4 B per non-zero: 1.28 GB on config 2) is read by the inspectors -- and afterwards only by executors that
 // gather through global columns.  Once create() has settled on a schedule whose multiply never touches it (every tile / group staged: the 16-bit
