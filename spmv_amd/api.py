@@ -940,24 +940,33 @@ def _cg_options(rtol, atol, max_iterations, check_every, x0, dinv, history):
     return opt, hist
 
 
-def cg(handle, m, RowPtr, ColIdx, Matrix_Val, B, X, rtol=1e-8, atol=0.0, max_iterations=1000, check_every=0, x0=False, dinv=None, history=False,
-       check=True):
-    """Solve A x = B by preconditioned conjugate gradients on the device (spmv_hip_cg): B, X, dinv of m elements, host or device; x0: X holds the
-    initial guess.  -> (rc, result dict: status, status_name, iterations, rr, bb[, history: rr after iteration 0 .. iterations])."""
+def _solve(name, handle, m, RowPtr, ColIdx, Matrix_Val, B, X, rtol, atol, max_iterations, check_every, x0, dinv, history, check):
+    """cg() and bicgstab(): one call of the entry point `name`"""
     opt, hist = _cg_options(rtol, atol, max_iterations, check_every, x0, dinv, history)
     res = spmv_hip_cg_result()
-    rc = _checked(load().spmv_hip_cg(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), _ptr(B), _ptr(X), C.byref(opt), C.byref(res)), "spmv_hip_cg", check)
+    rc = _checked(getattr(load(), name)(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), _ptr(B), _ptr(X), C.byref(opt), C.byref(res)), name, check)
     out = {"status": res.status, "status_name": CG_STATUS[res.status] if 0 <= res.status < len(CG_STATUS) else "?", "iterations": res.iterations, "rr": res.rr, "bb": res.bb}
     if hist is not None:
         out["history"] = hist[:res.iterations + 1].copy() if rc == 0 else hist[:0].copy()
     return rc, out
 
 
+def _time_solve(name, handle, B, X, iterations, x0, dinv, warmup, iters):
+    opt, _ = _cg_options(0.0, 0.0, iterations, 0, x0, dinv, False)
+    return _timed(name, (handle, _ptr(B), _ptr(X), C.byref(opt)), warmup, iters)
+
+
+def cg(handle, m, RowPtr, ColIdx, Matrix_Val, B, X, rtol=1e-8, atol=0.0, max_iterations=1000, check_every=0, x0=False, dinv=None, history=False,
+       check=True):
+    """Solve A x = B by preconditioned conjugate gradients on the device (spmv_hip_cg): B, X, dinv of m elements, host or device; x0: X holds the
+    initial guess.  -> (rc, result dict: status, status_name, iterations, rr, bb[, history: rr after iteration 0 .. iterations])."""
+    return _solve("spmv_hip_cg", handle, m, RowPtr, ColIdx, Matrix_Val, B, X, rtol, atol, max_iterations, check_every, x0, dinv, history, check)
+
+
 def time_cg_iterations(handle, B, X, iterations, x0=False, dinv=None, warmup=2, iters=20):
     """-> (mean ms per run, per-run ms array) of `iters` runs of `iterations` CG iterations each, stop tests off, on device B / X / dinv
     (spmv_hip_time_cg_iterations)."""
-    opt, _ = _cg_options(0.0, 0.0, iterations, 0, x0, dinv, False)
-    return _timed("spmv_hip_time_cg_iterations", (handle, _ptr(B), _ptr(X), C.byref(opt)), warmup, iters)
+    return _time_solve("spmv_hip_time_cg_iterations", handle, B, X, iterations, x0, dinv, warmup, iters)
 
 
 def bicgstab(handle, m, RowPtr, ColIdx, Matrix_Val, B, X, rtol=1e-8, atol=0.0, max_iterations=1000, check_every=0, x0=False, dinv=None, history=False,
@@ -965,20 +974,13 @@ def bicgstab(handle, m, RowPtr, ColIdx, Matrix_Val, B, X, rtol=1e-8, atol=0.0, m
     """Solve A x = B by right-preconditioned BiCGStab on the device (spmv_hip_bicgstab; A need not be symmetric): B, X, dinv of m elements, host
     or device; x0: X holds the initial guess.  -> (rc, result dict: status, status_name, iterations, rr, bb[, history: rr after iteration
     0 .. iterations]), as cg()."""
-    opt, hist = _cg_options(rtol, atol, max_iterations, check_every, x0, dinv, history)
-    res = spmv_hip_cg_result()
-    rc = _checked(load().spmv_hip_bicgstab(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), _ptr(B), _ptr(X), C.byref(opt), C.byref(res)), "spmv_hip_bicgstab", check)
-    out = {"status": res.status, "status_name": CG_STATUS[res.status] if 0 <= res.status < len(CG_STATUS) else "?", "iterations": res.iterations, "rr": res.rr, "bb": res.bb}
-    if hist is not None:
-        out["history"] = hist[:res.iterations + 1].copy() if rc == 0 else hist[:0].copy()
-    return rc, out
+    return _solve("spmv_hip_bicgstab", handle, m, RowPtr, ColIdx, Matrix_Val, B, X, rtol, atol, max_iterations, check_every, x0, dinv, history, check)
 
 
 def time_bicgstab_iterations(handle, B, X, iterations, x0=False, dinv=None, warmup=2, iters=20):
     """-> (mean ms per run, per-run ms array) of `iters` runs of `iterations` BiCGStab iterations each, stop tests off, on device B / X / dinv
     (spmv_hip_time_bicgstab_iterations)."""
-    opt, _ = _cg_options(0.0, 0.0, iterations, 0, x0, dinv, False)
-    return _timed("spmv_hip_time_bicgstab_iterations", (handle, _ptr(B), _ptr(X), C.byref(opt)), warmup, iters)
+    return _time_solve("spmv_hip_time_bicgstab_iterations", handle, B, X, iterations, x0, dinv, warmup, iters)
 
 
 def _take_csr(m, n, nnz, rp, ci, va, dtype):
@@ -1135,34 +1137,29 @@ class Handle:
         row_softmax_backward(self.h, self.m, rp, ci, va, P, G, out)
         return out
 
-    def cg(self, b, x=None, x0=False, rtol=1e-8, atol=0.0, max_iterations=1000, check_every=0, dinv=None, history=False):
-        """Solve A x = b by preconditioned conjugate gradients that stay on the device (spmv_hip_cg; A symmetric positive definite).  x is
-        allocated like b when None (then x0 must be off); x0: x holds the initial guess; dinv: None or 1 / diag(A) (Jacobi).
-        -> (x, result dict) or (x, result dict, history) when history is set: rr after iteration 0 .. iterations."""
+    def _solve(self, solve, b, x, x0, rtol, atol, max_iterations, check_every, dinv, history):
         if x is None:
             if x0:
                 raise ValueError("x0 needs an x that holds the initial guess")
             x = self._like(b, (self.m,))
         rp, ci, va = self._keep
-        _, res = cg(self.h, self.m, rp, ci, va, b, x, rtol, atol, max_iterations, check_every, x0, dinv, history)
+        _, res = solve(self.h, self.m, rp, ci, va, b, x, rtol, atol, max_iterations, check_every, x0, dinv, history)
         if history:
             return x, res, res.pop("history")
         return x, res
+
+    def cg(self, b, x=None, x0=False, rtol=1e-8, atol=0.0, max_iterations=1000, check_every=0, dinv=None, history=False):
+        """Solve A x = b by preconditioned conjugate gradients that stay on the device (spmv_hip_cg; A symmetric positive definite).  x is
+        allocated like b when None (then x0 must be off); x0: x holds the initial guess; dinv: None or 1 / diag(A) (Jacobi).
+        -> (x, result dict) or (x, result dict, history) when history is set: rr after iteration 0 .. iterations."""
+        return self._solve(cg, b, x, x0, rtol, atol, max_iterations, check_every, dinv, history)
 
     def bicgstab(self, b, x=None, x0=False, rtol=1e-8, atol=0.0, max_iterations=1000, check_every=0, dinv=None, history=False):
         """Solve A x = b by right-preconditioned BiCGStab that stays on the device (spmv_hip_bicgstab; A square, not necessarily symmetric).
         The arguments and the return value are cg()'s: x is allocated like b when None (then x0 must be off); x0: x holds the initial guess;
         dinv: None or 1 / diag(A) (Jacobi, applied from the right: x solves the original system).
         -> (x, result dict) or (x, result dict, history) when history is set: rr after iteration 0 .. iterations."""
-        if x is None:
-            if x0:
-                raise ValueError("x0 needs an x that holds the initial guess")
-            x = self._like(b, (self.m,))
-        rp, ci, va = self._keep
-        _, res = bicgstab(self.h, self.m, rp, ci, va, b, x, rtol, atol, max_iterations, check_every, x0, dinv, history)
-        if history:
-            return x, res, res.pop("history")
-        return x, res
+        return self._solve(bicgstab, b, x, x0, rtol, atol, max_iterations, check_every, dinv, history)
 
     def attention(self, Q, K, V, scale=None, out=None):
         """out = softmax_rows(scale * Q K^T on the pattern) V in one pass (spmv_hip_attention) for 2-D Q (m x k), K (n x k) and V (n x dv); scale

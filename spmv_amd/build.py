@@ -42,12 +42,12 @@ HIP_SOURCES = [("spmv_shim.hip", [], "spmv_shim.hip.o")] + [("spmv_vector.hip", 
               [("spmv_attention_16.hip", [f"SPMV_ATT16_TYPE={t}"], f"spmv_attention_16_{t}.hip.o") for t in (1, 2)] + \
               [("spmv_attention_backward.hip", [], "spmv_attention_backward.hip.o")] + \
               [("spmv_attention_backward_16.hip", [f"SPMV_ATTB16_TYPE={t}"], f"spmv_attention_backward_16_{t}.hip.o") for t in (1, 2)] + \
-              [("spmv_cg.hip", [], "spmv_cg.hip.o"), ("spmv_bicgstab.hip", [], "spmv_bicgstab.hip.o")]   # the conjugate-gradient and the BiCGStab vector kernels (kernels/cg.hpp, kernels/bicgstab.hpp); before them: the k-right-hand-side executors (kernels/spmm.hpp), the transpose builder (kernels/transpose.hpp), the sampled product (kernels/sddmm.hpp), the row reductions (kernels/row_softmax.hpp), the fused attention (kernels/attention.hpp; on 16-bit operands once per storage type, fp16 and bf16) and its backward (kernels/attention_backward.hpp; on 16-bit operands likewise once per storage type)
+              [("spmv_solve.hip", [], "spmv_solve.hip.o")]   # the conjugate-gradient and the BiCGStab vector kernels (kernels/cg.hpp, kernels/bicgstab.hpp); before them: the k-right-hand-side executors (kernels/spmm.hpp), the transpose builder (kernels/transpose.hpp), the sampled product (kernels/sddmm.hpp), the row reductions (kernels/row_softmax.hpp), the fused attention (kernels/attention.hpp; on 16-bit operands once per storage type, fp16 and bf16) and its backward (kernels/attention_backward.hpp; on 16-bit operands likewise once per storage type)
 HIP_FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
              "-ffp-contract=fast"]
-# flags of single sources, behind HIP_FLAGS.  spmv_cg.hip and spmv_bicgstab.hip promise the bits of separate multiplies and adds (include/spmv_hip.h, "the arithmetic
+# flags of single sources, behind HIP_FLAGS.  spmv_solve.hip promises the bits of separate multiplies and adds (include/spmv_hip.h, "the arithmetic
 # contract"): under -ffp-contract=fast the back end fuses a multiply and an add whatever `#pragma clang fp contract(off)` says in the source
-HIP_SOURCE_FLAGS = {"spmv_cg.hip": ["-ffp-contract=off"], "spmv_bicgstab.hip": ["-ffp-contract=off"]}
+HIP_SOURCE_FLAGS = {"spmv_solve.hip": ["-ffp-contract=off"]}
 C_FLAGS = ["-O2", "-std=c11", "-fPIC", "-fopenmp", "-Wall", "-Wextra", "-D_POSIX_C_SOURCE=200809L"]
 
 

@@ -9,13 +9,13 @@
 //   bicg_direction  reads r, p, v, (Dinv)            the stop test; beta; p = r + beta (p - omega v); y <- Dinv .* p; block 0 writes the state
 //
 // s lives in r.  y exists only with Dinv: it holds ph from bicg_direction (bicg_init) to bicg_half, which overwrites it element by element
-// with sh.  Everything that crosses workgroups is cg.hpp's: ONE fp64 partial per workgroup and dot, every workgroup of a later kernel adds the
+// with sh.  Everything that crosses workgroups is solve_common.hpp's: ONE fp64 partial per workgroup and dot, every workgroup of a later kernel adds the
 // partials again itself in the fixed order (cg_final_sums) and derives alpha / omega / beta and the stop tests from the sums, with the same
 // bits everywhere.  The partial arrays of an iteration stay in place until the next one overwrites them, so bicg_direction forms alpha
 // and omega again from <rhat,v>, <t,s> and <t,t>; rho has two arrays, iteration k reads (k - 1) & 1 and writes k & 1.  Hand-off between
 // workgroups is the kernel boundary and nothing else: no atomics, no in-launch flags, no fences, no spinning, no cooperative launch.
 //
-// The state (BicgState): no kernel reads a word that its own launch writes, so every wave of a launch sees the same state and takes the same
+// The state (SolveState): no kernel reads a word that its own launch writes, so every wave of a launch sees the same state and takes the same
 // early return.  Three kernels of an iteration can end the loop, hence three words:
 //   end_half       written by bicg_half                      read by bicg_ts and bicg_update
 //   end_update     written by bicg_update                    read by bicg_direction
@@ -23,43 +23,24 @@
 // A kernel that finds the word it reads set passes the end on in the word it writes (block 0) and returns, so from the launch that ends the
 // loop on every later kernel of the batch returns at once.  bb is written by bicg_begin alone.
 //
-// The order of a dot is cg.hpp's (include/spmv_hip.h, "the arithmetic contract"); every product and every sum is a separate operation:
-// contraction is off in every function of this file AND spmv_bicgstab.hip is compiled with -ffp-contract=off (build.py, HIP_SOURCE_FLAGS).
+// The order of a dot is solve_common.hpp's (include/spmv_hip.h, "the arithmetic contract"); every product and every sum is a separate operation:
+// contraction is off in every function of this file AND spmv_solve.hip is compiled with -ffp-contract=off (build.py, HIP_SOURCE_FLAGS).
+// bicg_begin and bicg_rv are solve_common.hpp's cg_begin_kernel (without CG's <r,z> <= 0 test) and cg_dot_kernel.
 #pragma once
-#include "common.hpp"
-#include "cg.hpp"
+#include "solve_common.hpp"
 
 namespace spmv {
 
-// device copy of what spmv_hip_bicgstab reports (status: the SPMV_HIP_CG_* values)
-struct BicgState {
-    int end_half, end_update, end_direction; // the host reads all three
-    int status, iterations;
-    double rr, bb;
-};
+// the workspace vectors: SolveArgs::vec
+enum { kBicgVecR, kBicgVecRhat, kBicgVecP, kBicgVecV, kBicgVecT, kBicgVecY, kBicgVectors };
 
 // the partial arrays, kCgMaxParts doubles each; entries behind the P in use stay +0.0 from the allocation on
 enum { kBicgPartRV, kBicgPartSS, kBicgPartTS, kBicgPartTT, kBicgPartRho0, kBicgPartRho1, kBicgPartRR, kBicgPartBB, kBicgPartArrays };
 
-// what one solve's launches need (device pointers)
-struct BicgArgs {
-    int m = 0, parts = 0;
-    long long span = 0;            // L
-    void *r = nullptr, *rhat = nullptr, *p = nullptr, *v = nullptr, *t = nullptr, *y = nullptr, *x = nullptr;
-    const void *b = nullptr, *dinv = nullptr;
-    double *part = nullptr;        // kBicgPartArrays arrays
-    BicgState *state = nullptr;
-    double *hist = nullptr;        // NULL: not wanted
-    double rtol2 = 0, atol2 = 0;   // rtol^2, atol^2
-    int nostop = 0;                // the timer: no test ever ends the loop
-    bool wide = false;             // b, x and dinv allow 16-byte accesses (the workspace vectors always do)
-    bool f64 = true;
-};
-
-// spmv_bicgstab.hip
-hipError_t bicg_start_launch(const BicgArgs &a, bool use_x0, hipStream_t stream); // bicg_init + bicg_begin; v holds A x0 when use_x0
-hipError_t bicg_first_launch(const BicgArgs &a, int k, hipStream_t stream);       // bicg_rv + bicg_half of iteration k >= 1; v holds A ph
-hipError_t bicg_second_launch(const BicgArgs &a, int k, hipStream_t stream);      // bicg_ts + bicg_update + bicg_direction; t holds A sh
+// spmv_solve.hip
+hipError_t bicg_start_launch(const SolveArgs &a, bool use_x0, hipStream_t stream); // bicg_init + bicg_begin; v holds A x0 when use_x0
+hipError_t bicg_first_launch(const SolveArgs &a, int k, hipStream_t stream);       // bicg_rv + bicg_half of iteration k >= 1; v holds A ph
+hipError_t bicg_second_launch(const SolveArgs &a, int k, hipStream_t stream);      // bicg_ts + bicg_update + bicg_direction; t holds A sh
 
 // r = b (x = 0 is written) or r = b - v with v = A x0; rhat = p = r; y = Dinv .* p; the partials of <rhat,r>, <r,r> and <b,b>
 template <typename T, bool WIDE, bool DINV, bool X0>
@@ -68,7 +49,7 @@ __global__ __launch_bounds__(kBlock) void bicg_init_kernel(int m, long long span
 {
 #pragma clang fp contract(off)
     __shared__ double s_own[3][kBlock / kWave];
-    const long long begin = (long long) blockIdx.x * span, end = begin + span < m ? begin + span : (long long) m;
+    const auto [begin, end] = cg_range(m, span);
     double rho[4] = {0, 0, 0, 0}, rr[4] = {0, 0, 0, 0}, bb[4] = {0, 0, 0, 0};
     for (long long o = begin + 4 * threadIdx.x; o < end; o += kCgChunk) {
         T vb[4], vr[4];
@@ -110,58 +91,12 @@ __global__ __launch_bounds__(kBlock) void bicg_init_kernel(int m, long long span
     }
 }
 
-// one workgroup: the state of iteration 0 (the host has zeroed it)
-template <bool HIST>
-__global__ __launch_bounds__(kBlock) void bicg_begin_kernel(const double *__restrict__ part, BicgState *st, double *__restrict__ hist, double rtol2, double atol2, int nostop)
-{
-#pragma clang fp contract(off)
-    __shared__ double s_fin[3][kBlock / kWave];
-    const int ids[3] = {kBicgPartRho0, kBicgPartRR, kBicgPartBB};
-    double v[3];
-    cg_final_sums<3>(part, ids, v, s_fin);
-    if (threadIdx.x != 0) return;
-    double rr = v[1];
-    const double rho = v[0], bb = v[2];
-    int status = -1;
-    if (!nostop) {
-        if (!cg_finite(bb) || !cg_finite(rr) || !cg_finite(rho)) status = 3;
-        else if (bb == 0) { status = 0; rr = 0; } // the solution is x = 0: the host zeroes X
-        else if (rr <= __builtin_fmax(rtol2 * bb, atol2)) status = 0;
-    }
-    st->iterations = 0;
-    st->rr = rr;
-    st->bb = bb;
-    if (HIST) hist[0] = rr;
-    if (status >= 0) { st->status = status; st->end_direction = 1; }
-}
-
-template <typename T>
-__global__ __launch_bounds__(kBlock) void bicg_rv_kernel(int m, long long span, const T *__restrict__ rhat, const T *__restrict__ v, double *__restrict__ part, const BicgState *st)
-{
-#pragma clang fp contract(off)
-    __shared__ double s_own[1][kBlock / kWave];
-    if (st->end_direction) return;
-    const long long begin = (long long) blockIdx.x * span, end = begin + span < m ? begin + span : (long long) m;
-    double rv[4] = {0, 0, 0, 0};
-#pragma unroll 2
-    for (long long o = begin + 4 * threadIdx.x; o < end; o += kCgChunk) {
-        T va[4], vv[4];
-        cg_load4<T, true>(rhat, o, end, va);
-        cg_load4<T, true>(v, o, end, vv);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) rv[i] += (double) va[i] * (double) vv[i];
-    }
-    double own[1] = {cg_thread_sum(rv)};
-    cg_block_tree<1>(own, s_own);
-    if (threadIdx.x == 0) part[(size_t) kBicgPartRV * kCgMaxParts + blockIdx.x] = own[0];
-}
-
 // iteration k: alpha = rho / <rhat,v> rounded to T once; x = x + alpha ph, s = r - alpha v (into r) in T, a multiply and then an add; y = Dinv .* s;
 // the partials of <s,s>.  ph is y with Dinv (read before this element's sh is written over it) and p without.  <rhat,v> = 0 or rho = 0
 // (breakdown) or a non-finite scalar: block 0 records it and NO workgroup applies the half step.
 template <typename T, bool WIDE, bool DINV>
 __global__ __launch_bounds__(kBlock) void bicg_half_kernel(int m, long long span, int k, const T *__restrict__ p, const T *__restrict__ v, T *__restrict__ x, T *__restrict__ r,
-                                                           const T *__restrict__ dinv, T *__restrict__ y, double *__restrict__ part, BicgState *st, int nostop)
+                                                           const T *__restrict__ dinv, T *__restrict__ y, double *__restrict__ part, SolveState *st, int nostop)
 {
 #pragma clang fp contract(off)
     __shared__ double s_fin[2][kBlock / kWave], s_own[1][kBlock / kWave];
@@ -183,7 +118,7 @@ __global__ __launch_bounds__(kBlock) void bicg_half_kernel(int m, long long span
             return;
         }
     }
-    const long long begin = (long long) blockIdx.x * span, end = begin + span < m ? begin + span : (long long) m;
+    const auto [begin, end] = cg_range(m, span);
     double ss[4] = {0, 0, 0, 0};
     for (long long o = begin + 4 * threadIdx.x; o < end; o += kCgChunk) {
         T vp[4], vv[4], vx[4], vr[4];
@@ -215,12 +150,12 @@ __global__ __launch_bounds__(kBlock) void bicg_half_kernel(int m, long long span
 }
 
 template <typename T>
-__global__ __launch_bounds__(kBlock) void bicg_ts_kernel(int m, long long span, const T *__restrict__ t, const T *__restrict__ s, double *__restrict__ part, const BicgState *st)
+__global__ __launch_bounds__(kBlock) void bicg_ts_kernel(int m, long long span, const T *__restrict__ t, const T *__restrict__ s, double *__restrict__ part, const SolveState *st)
 {
 #pragma clang fp contract(off)
     __shared__ double s_own[2][kBlock / kWave];
     if (st->end_half) return;
-    const long long begin = (long long) blockIdx.x * span, end = begin + span < m ? begin + span : (long long) m;
+    const auto [begin, end] = cg_range(m, span);
     double ts[4] = {0, 0, 0, 0}, tt[4] = {0, 0, 0, 0};
 #pragma unroll 2
     for (long long o = begin + 4 * threadIdx.x; o < end; o += kCgChunk) {
@@ -247,7 +182,7 @@ __global__ __launch_bounds__(kBlock) void bicg_ts_kernel(int m, long long span, 
 // workgroup applies the second half: x keeps the half step.
 template <typename T, bool WIDE, bool DINV>
 __global__ __launch_bounds__(kBlock) void bicg_update_kernel(int m, long long span, int k, const T *__restrict__ t, T *__restrict__ r, const T *__restrict__ y, T *__restrict__ x,
-                                                             const T *__restrict__ rhat, double *__restrict__ part, BicgState *st, double *__restrict__ hist, double rtol2,
+                                                             const T *__restrict__ rhat, double *__restrict__ part, SolveState *st, double *__restrict__ hist, double rtol2,
                                                              double atol2, int nostop)
 {
 #pragma clang fp contract(off)
@@ -281,7 +216,7 @@ __global__ __launch_bounds__(kBlock) void bicg_update_kernel(int m, long long sp
         }
     }
     const int rho_new = k & 1 ? kBicgPartRho1 : kBicgPartRho0;
-    const long long begin = (long long) blockIdx.x * span, end = begin + span < m ? begin + span : (long long) m;
+    const auto [begin, end] = cg_range(m, span);
     double rho[4] = {0, 0, 0, 0}, rr[4] = {0, 0, 0, 0};
     for (long long o = begin + 4 * threadIdx.x; o < end; o += kCgChunk) {
         T vt[4], vs[4], vh[4], vx[4], va[4];
@@ -318,7 +253,7 @@ __global__ __launch_bounds__(kBlock) void bicg_update_kernel(int m, long long sp
 // workgroup touches p.
 template <typename T, bool WIDE, bool DINV>
 __global__ __launch_bounds__(kBlock) void bicg_direction_kernel(int m, long long span, int k, const T *__restrict__ r, T *__restrict__ p, const T *__restrict__ v,
-                                                                const T *__restrict__ dinv, T *__restrict__ y, const double *__restrict__ part, BicgState *st,
+                                                                const T *__restrict__ dinv, T *__restrict__ y, const double *__restrict__ part, SolveState *st,
                                                                 double *__restrict__ hist, double rtol2, double atol2, int nostop)
 {
 #pragma clang fp contract(off)
@@ -347,7 +282,7 @@ __global__ __launch_bounds__(kBlock) void bicg_direction_kernel(int m, long long
         if (status >= 0) { st->status = status; st->end_direction = 1; }
     }
     if (status >= 0) return;
-    const long long begin = (long long) blockIdx.x * span, end = begin + span < m ? begin + span : (long long) m;
+    const auto [begin, end] = cg_range(m, span);
 #pragma unroll 2
     for (long long o = begin + 4 * threadIdx.x; o < end; o += kCgChunk) {
         T vr[4], vp[4], vv[4];

@@ -296,11 +296,11 @@ struct spmv_dev {
     // spmv_hip_attention_gqa_backward_16 with kv_heads < heads and 16-bit dK / dV: the float sums over each group's heads (n x kv_heads * k,
     // n x kv_heads * dv), rounded once into the caller's arrays; allocated at the first such call, grown when a later one needs more
     StageBuf attb_nk, attb_nv;
-    // spmv_hip_cg (shim/cg.hpp): r, p, q (m elements each), the partial arrays and the state in ONE block allocated at the first solve; the
+    // spmv_hip_cg (shim/solve.hpp): r, p, q (m elements each), the partial arrays and the state in ONE block allocated at the first solve; the
     // history (doubles, one per iteration + 1) in a block of its own, allocated when a solve wants one and grown when a later one needs more
     void *cg_ws = nullptr;
     StageBuf cg_hist;
-    // spmv_hip_bicgstab (shim/bicgstab.hpp): r, rhat, p, v, t, y (m elements each), the partial arrays and the state in ONE block of the solver's
+    // spmv_hip_bicgstab (shim/solve.hpp): r, rhat, p, v, t, y (m elements each), the partial arrays and the state in ONE block of the solver's
     // own, allocated at the first BiCGStab solve; its history likewise in a block of its own
     void *bicg_ws = nullptr;
     StageBuf bicg_hist;

@@ -1414,8 +1414,8 @@ double spmv_hip_time_attention_gqa_backward_16_launches(spmv_Handle_t h, int hea
     return attention_backward_time(h, "time_attention_gqa_backward_16_launches", ATTENTION_16, &c, warmup, iters, ms_out);
 }
 
-/* ---------------------------------------------------------------- conjugate gradients on the device */
-/* the argument rules ahead of the gate: spmv_hip_cg; its timer with m = 1 (B and X are always needed) */
+/* ---------------------------------------------------------------- conjugate gradients and BiCGStab (a matrix that need not be symmetric) on the device */
+/* the argument rules ahead of the gate, the same for both: a solve; its timer with m = 1 (B and X are always needed) */
 static int cg_args(spmv_Handle_t h, const char *where, const void *B, const void *X, const spmv_hip_cg_options *opt, const void *res, int m)
 {
     if (!h) return refuse(SPMV_HIP_E_ARG, where, "handle is NULL");
@@ -1426,43 +1426,42 @@ static int cg_args(spmv_Handle_t h, const char *where, const void *B, const void
     return SPMV_HIP_OK;
 }
 
-int spmv_hip_cg(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
-                const void *Matrix_Val, const void *B, void *X, const spmv_hip_cg_options *opt, spmv_hip_cg_result *res)
+static int solve_call(spmv_Handle_t handle, const char *where, int solver, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                      const void *Matrix_Val, const void *B, void *X, const spmv_hip_cg_options *opt, spmv_hip_cg_result *res)
 {
-    const char *where = "cg";
     spmv_hip_state *st;
     int rc;
     if ((rc = cg_args(handle, where, B, X, opt, res, m)) || (rc = resident_prologue(handle, where, 0, m, RowPtr, ColIdx, Matrix_Val, &st))) return rc;
     if (st->m != st->n) return refuse(SPMV_HIP_E_ARG, where, "the matrix is not square (m != n at create)");
-    return report(spmv_shim_cg(st->dev, B, X, opt, res), where);
+    return report(spmv_shim_solve(solver, st->dev, B, X, opt, res), where);
+}
+
+static double solve_time(spmv_Handle_t h, const char *where, int solver, const void *B, void *X, const spmv_hip_cg_options *opt, int warmup, int iters, float *ms_out)
+{
+    spmv_hip_state *st;
+    if (cg_args(h, where, B, X, opt, opt, 1) || resident_state(h, where, 0, &st)) return -1.0;
+    if (st->m != st->n) { (void) refuse(SPMV_HIP_E_ARG, where, "the matrix is not square (m != n at create)"); return -1.0; }
+    return report_time(spmv_shim_time_solve(solver, st->dev, B, X, opt, warmup, iters, ms_out), where);
+}
+
+int spmv_hip_cg(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                const void *Matrix_Val, const void *B, void *X, const spmv_hip_cg_options *opt, spmv_hip_cg_result *res)
+{
+    return solve_call(handle, "cg", SPMV_SHIM_SOLVE_CG, m, RowPtr, ColIdx, Matrix_Val, B, X, opt, res);
+}
+
+int spmv_hip_bicgstab(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                      const void *Matrix_Val, const void *B, void *X, const spmv_hip_cg_options *opt, spmv_hip_cg_result *res)
+{
+    return solve_call(handle, "bicgstab", SPMV_SHIM_SOLVE_BICGSTAB, m, RowPtr, ColIdx, Matrix_Val, B, X, opt, res);
 }
 
 double spmv_hip_time_cg_iterations(spmv_Handle_t h, const void *B, void *X, const spmv_hip_cg_options *opt, int warmup, int iters, float *ms_out)
 {
-    const char *where = "time_cg_iterations";
-    spmv_hip_state *st;
-    if (cg_args(h, where, B, X, opt, opt, 1) || resident_state(h, where, 0, &st)) return -1.0;
-    if (st->m != st->n) { (void) refuse(SPMV_HIP_E_ARG, where, "the matrix is not square (m != n at create)"); return -1.0; }
-    return report_time(spmv_shim_time_cg(st->dev, B, X, opt, warmup, iters, ms_out), where);
-}
-
-/* ---------------------------------------------------------------- BiCGStab on the device: spmv_hip_cg's rules, a matrix that need not be symmetric */
-int spmv_hip_bicgstab(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
-                      const void *Matrix_Val, const void *B, void *X, const spmv_hip_cg_options *opt, spmv_hip_cg_result *res)
-{
-    const char *where = "bicgstab";
-    spmv_hip_state *st;
-    int rc;
-    if ((rc = cg_args(handle, where, B, X, opt, res, m)) || (rc = resident_prologue(handle, where, 0, m, RowPtr, ColIdx, Matrix_Val, &st))) return rc;
-    if (st->m != st->n) return refuse(SPMV_HIP_E_ARG, where, "the matrix is not square (m != n at create)");
-    return report(spmv_shim_bicgstab(st->dev, B, X, opt, res), where);
+    return solve_time(h, "time_cg_iterations", SPMV_SHIM_SOLVE_CG, B, X, opt, warmup, iters, ms_out);
 }
 
 double spmv_hip_time_bicgstab_iterations(spmv_Handle_t h, const void *B, void *X, const spmv_hip_cg_options *opt, int warmup, int iters, float *ms_out)
 {
-    const char *where = "time_bicgstab_iterations";
-    spmv_hip_state *st;
-    if (cg_args(h, where, B, X, opt, opt, 1) || resident_state(h, where, 0, &st)) return -1.0;
-    if (st->m != st->n) { (void) refuse(SPMV_HIP_E_ARG, where, "the matrix is not square (m != n at create)"); return -1.0; }
-    return report_time(spmv_shim_time_bicgstab(st->dev, B, X, opt, warmup, iters, ms_out), where);
+    return solve_time(h, "time_bicgstab_iterations", SPMV_SHIM_SOLVE_BICGSTAB, B, X, opt, warmup, iters, ms_out);
 }

@@ -205,18 +205,14 @@ int spmv_shim_attention_backward(spmv_dev *d, const spmv_attention_backward_call
  * Q, K, V, G and, with stats, O and L must be given. */
 double spmv_shim_time_attention_backward(spmv_dev *d, const spmv_attention_backward_call *c, int warmup, int iters, float *ms_out);
 
-/* ---- preconditioned conjugate gradients on the resident matrix (shim/cg.hpp; spmv_hip_cg) ----
- * B, X, opt->Dinv: m elements, host or device pointers each.  The multiply is the built schedule's own launch.  Builds the workspace at the first call.
- * SPMV_HIP_OK whenever the solve ran (res->status says how it ended); synchronous */
-int spmv_shim_cg(spmv_dev *d, const void *b, void *x, const spmv_hip_cg_options *opt, spmv_hip_cg_result *res);
+/* ---- the solves on the resident matrix that stay on the device (shim/solve.hpp): preconditioned conjugate gradients (spmv_hip_cg) and
+ * right-preconditioned BiCGStab (spmv_hip_bicgstab; the matrix need not be symmetric) ----
+ * B, X, opt->Dinv: m elements, host or device pointers each.  The multiply is the built schedule's own launch.  Each solver builds a workspace of its
+ * own at its first call.  SPMV_HIP_OK whenever the solve ran (res->status says how it ended); synchronous */
+enum { SPMV_SHIM_SOLVE_CG, SPMV_SHIM_SOLVE_BICGSTAB };
+int spmv_shim_solve(int solver, spmv_dev *d, const void *b, void *x, const spmv_hip_cg_options *opt, spmv_hip_cg_result *res);
 /* `iters` runs of opt->max_iterations iterations each, the stop tests off, timed with events on the handle's stream (device B / X / Dinv); mean ms per run, < 0 on failure */
-double spmv_shim_time_cg(spmv_dev *d, const void *b, void *x, const spmv_hip_cg_options *opt, int warmup, int iters, float *ms_out);
-
-/* ---- right-preconditioned BiCGStab on the resident matrix (shim/bicgstab.hpp; spmv_hip_bicgstab) ----
- * The operands, the options, the result and the return value are spmv_shim_cg's; the matrix need not be symmetric.  Builds a workspace of its own at the first call. */
-int spmv_shim_bicgstab(spmv_dev *d, const void *b, void *x, const spmv_hip_cg_options *opt, spmv_hip_cg_result *res);
-/* as spmv_shim_time_cg */
-double spmv_shim_time_bicgstab(spmv_dev *d, const void *b, void *x, const spmv_hip_cg_options *opt, int warmup, int iters, float *ms_out);
+double spmv_shim_time_solve(int solver, spmv_dev *d, const void *b, void *x, const spmv_hip_cg_options *opt, int warmup, int iters, float *ms_out);
 
 /* the resident CSR arrays (device pointers; ColIdx may be NULL after spmv_shim_release_columns) */
 void spmv_shim_matrix_arrays(const spmv_dev *d, const int **rowptr, const int **colidx, const void **val);

@@ -531,8 +531,7 @@ extern "C" int spmv_shim_is_device_ptr(const void *p) { return is_device_ptr(p) 
 #include "shim/row_softmax.hpp"
 #include "shim/attention.hpp"
 #include "shim/attention_backward.hpp"
-#include "shim/cg.hpp"
-#include "shim/bicgstab.hpp"
+#include "shim/solve.hpp"
 
 // The resident int32 ColIdx copy (4 B per non-zero: 1.28 GB on config 2) is read by the inspectors -- and afterwards only by executors that
 // gather through global columns.  Once create() has settled on a schedule whose multiply never touches it (every tile / group staged: the 16-bit

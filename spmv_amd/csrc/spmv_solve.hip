@@ -1,0 +1,95 @@
+// spmv_solve.hip -- translation unit of the vector kernels of the device-resident solvers (kernels/cg.hpp, kernels/bicgstab.hpp, what they
+// share in kernels/solve_common.hpp).  Launches only: the workspace, staging, the multiplies, the host's looks at the state and the error channel
+// stay in spmv_shim.hip (shim/solve.hpp).  Per solve it calls cg_start_launch or bicg_start_launch once; per iteration cg_iteration_launch
+// behind q = A p, or bicg_first_launch behind v = A ph and bicg_second_launch behind t = A sh.
+#include <hip/hip_runtime.h>
+
+#include "kernels/common.hpp"
+#include "kernels/cg.hpp"
+#include "kernels/bicgstab.hpp"
+
+namespace spmv {
+
+// cg_begin on the partial arrays rz / rr / bb; SPD: CG's <r,z> <= 0 test
+template <bool SPD>
+static void solve_begin(const SolveArgs &a, int rz, int rr, int bb, hipStream_t stream)
+{
+    if (a.hist) cg_begin_kernel<true, SPD><<<1, kBlock, 0, stream>>>(a.part, rz, rr, bb, a.state, a.hist, a.rtol2, a.atol2, a.nostop);
+    else cg_begin_kernel<false, SPD><<<1, kBlock, 0, stream>>>(a.part, rz, rr, bb, a.state, a.hist, a.rtol2, a.atol2, a.nostop);
+}
+
+template <typename T, bool WIDE, bool DINV>
+static void cg_start_t(const SolveArgs &a, bool use_x0, hipStream_t stream)
+{
+    const T *b = (const T *) a.b, *q = (const T *) a.vec[kCgVecQ], *dinv = (const T *) a.dinv;
+    T *r = (T *) a.vec[kCgVecR], *p = (T *) a.vec[kCgVecP];
+    if (use_x0) cg_init_kernel<T, WIDE, DINV, true><<<(unsigned) a.parts, kBlock, 0, stream>>>(a.m, a.span, b, (T *) a.x, q, dinv, r, p, a.part);
+    else cg_init_kernel<T, WIDE, DINV, false><<<(unsigned) a.parts, kBlock, 0, stream>>>(a.m, a.span, b, (T *) a.x, q, dinv, r, p, a.part);
+    solve_begin<true>(a, kCgPartRZ0, kCgPartRR, kCgPartBB, stream);
+}
+
+template <typename T, bool WIDE, bool DINV>
+static void cg_iteration_t(const SolveArgs &a, int k, hipStream_t stream)
+{
+    const unsigned grid = (unsigned) a.parts;
+    const T *dinv = (const T *) a.dinv;
+    T *r = (T *) a.vec[kCgVecR], *p = (T *) a.vec[kCgVecP], *q = (T *) a.vec[kCgVecQ];
+    cg_dot_kernel<T><<<grid, kBlock, 0, stream>>>(a.m, a.span, p, q, a.part + (size_t) kCgPartPQ * kCgMaxParts, &a.state->end_direction);
+    cg_update_kernel<T, WIDE, DINV><<<grid, kBlock, 0, stream>>>(a.m, a.span, k, p, q, (T *) a.x, r, dinv, a.part, a.state, a.nostop);
+    cg_direction_kernel<T, WIDE, DINV><<<grid, kBlock, 0, stream>>>(a.m, a.span, k, r, dinv, p, a.part, a.state, a.hist, a.rtol2, a.atol2, a.nostop);
+}
+
+template <typename T, bool WIDE, bool DINV>
+static void bicg_start_t(const SolveArgs &a, bool use_x0, hipStream_t stream)
+{
+    const T *b = (const T *) a.b, *v = (const T *) a.vec[kBicgVecV], *dinv = (const T *) a.dinv;
+    T *r = (T *) a.vec[kBicgVecR], *rhat = (T *) a.vec[kBicgVecRhat], *p = (T *) a.vec[kBicgVecP], *y = (T *) a.vec[kBicgVecY];
+    if (use_x0) bicg_init_kernel<T, WIDE, DINV, true><<<(unsigned) a.parts, kBlock, 0, stream>>>(a.m, a.span, b, (T *) a.x, v, dinv, r, rhat, p, y, a.part);
+    else bicg_init_kernel<T, WIDE, DINV, false><<<(unsigned) a.parts, kBlock, 0, stream>>>(a.m, a.span, b, (T *) a.x, v, dinv, r, rhat, p, y, a.part);
+    solve_begin<false>(a, kBicgPartRho0, kBicgPartRR, kBicgPartBB, stream);
+}
+
+template <typename T, bool WIDE, bool DINV>
+static void bicg_first_t(const SolveArgs &a, int k, hipStream_t stream)
+{
+    const unsigned grid = (unsigned) a.parts;
+    const T *rhat = (const T *) a.vec[kBicgVecRhat], *p = (const T *) a.vec[kBicgVecP], *v = (const T *) a.vec[kBicgVecV];
+    cg_dot_kernel<T><<<grid, kBlock, 0, stream>>>(a.m, a.span, rhat, v, a.part + (size_t) kBicgPartRV * kCgMaxParts, &a.state->end_direction);
+    bicg_half_kernel<T, WIDE, DINV><<<grid, kBlock, 0, stream>>>(a.m, a.span, k, p, v, (T *) a.x, (T *) a.vec[kBicgVecR], (const T *) a.dinv, (T *) a.vec[kBicgVecY], a.part, a.state, a.nostop);
+}
+
+template <typename T, bool WIDE, bool DINV>
+static void bicg_second_t(const SolveArgs &a, int k, hipStream_t stream)
+{
+    const unsigned grid = (unsigned) a.parts;
+    const T *rhat = (const T *) a.vec[kBicgVecRhat], *v = (const T *) a.vec[kBicgVecV], *t = (const T *) a.vec[kBicgVecT], *dinv = (const T *) a.dinv;
+    T *r = (T *) a.vec[kBicgVecR], *p = (T *) a.vec[kBicgVecP], *y = (T *) a.vec[kBicgVecY];
+    bicg_ts_kernel<T><<<grid, kBlock, 0, stream>>>(a.m, a.span, t, r, a.part, a.state);
+    bicg_update_kernel<T, WIDE, DINV><<<grid, kBlock, 0, stream>>>(a.m, a.span, k, t, r, y, (T *) a.x, rhat, a.part, a.state, a.hist, a.rtol2, a.atol2, a.nostop);
+    bicg_direction_kernel<T, WIDE, DINV><<<grid, kBlock, 0, stream>>>(a.m, a.span, k, r, p, v, dinv, y, a.part, a.state, a.hist, a.rtol2, a.atol2, a.nostop);
+}
+
+static bool args_ok(const SolveArgs &a) { return a.m > 0 && a.parts >= 1 && a.parts <= kCgMaxParts && a.span * a.parts >= a.m; }
+
+// the checked launch of the instantiation of F that a.f64 / a.wide / a.dinv select; `ok`: what the call needs beyond args_ok
+#define SOLVE_LAUNCH(F, ok, ...)                                                                                             \
+    do {                                                                                                                     \
+        if (!args_ok(a) || !(ok)) return hipErrorInvalidValue;                                                               \
+        const bool dinv__ = a.dinv != nullptr;                                                                               \
+        if (a.f64) {                                                                                                         \
+            if (a.wide) { if (dinv__) F<double, true, true>(__VA_ARGS__); else F<double, true, false>(__VA_ARGS__); }        \
+            else { if (dinv__) F<double, false, true>(__VA_ARGS__); else F<double, false, false>(__VA_ARGS__); }             \
+        } else {                                                                                                             \
+            if (a.wide) { if (dinv__) F<float, true, true>(__VA_ARGS__); else F<float, true, false>(__VA_ARGS__); }          \
+            else { if (dinv__) F<float, false, true>(__VA_ARGS__); else F<float, false, false>(__VA_ARGS__); }               \
+        }                                                                                                                    \
+        return hipGetLastError();                                                                                            \
+    } while (0)
+
+hipError_t cg_start_launch(const SolveArgs &a, bool use_x0, hipStream_t stream) { SOLVE_LAUNCH(cg_start_t, true, a, use_x0, stream); }
+hipError_t cg_iteration_launch(const SolveArgs &a, int k, hipStream_t stream) { SOLVE_LAUNCH(cg_iteration_t, k >= 1, a, k, stream); }
+hipError_t bicg_start_launch(const SolveArgs &a, bool use_x0, hipStream_t stream) { SOLVE_LAUNCH(bicg_start_t, true, a, use_x0, stream); }
+hipError_t bicg_first_launch(const SolveArgs &a, int k, hipStream_t stream) { SOLVE_LAUNCH(bicg_first_t, k >= 1, a, k, stream); }
+hipError_t bicg_second_launch(const SolveArgs &a, int k, hipStream_t stream) { SOLVE_LAUNCH(bicg_second_t, k >= 1, a, k, stream); }
+
+} // namespace spmv
