@@ -91,10 +91,13 @@ double spmv_hip_time_attention_gqa_backward_16_launches(spmv_Handle_t handle, in
                                                         const void *O, long long ldo, const void *L, long long ldl, int dq_type, void *dQ, long long lddq, int dkv_type, void *dK,
                                                         long long lddk, void *dV, long long lddv, void *dB, long long lddb, int warmup, int iters, float *ms_out);
 /* spmv_hip_cg's iterations (include spmv_hip.h first: spmv_hip_cg_options): `warmup` untimed + `iters` timed RUNS of opt->max_iterations (>= 1)
-   iterations each, with the stop tests disabled.  Every run starts again from B (and X when use_x0); its iterations -- multiply, cg_dot,
-   cg_update, cg_direction -- are enqueued back to back on the handle's stream and bracketed by two hipEvents, the start outside them; ms_out[i]
-   (may be NULL) receives run i.  B, X and opt->Dinv must be DEVICE pointers; rtol, atol, check_every and history are not used.  Returns the mean
-   ms per run, < 0 on error. */
+   iterations each, with the stop tests disabled.  Every run starts again from B; its iterations -- multiply, cg_dot, cg_update, cg_direction --
+   are enqueued back to back on the handle's stream and bracketed by two hipEvents, the start outside them; ms_out[i] (may be NULL) receives
+   run i.  What X holds: without use_x0 every run starts from x = 0, so every run computes the same and the call leaves in X the bits that
+   spmv_hip_cg returns for rtol = atol = 0 and the same max_iterations when none of its tests ends that solve early.  With use_x0 the FIRST run
+   (a warm-up run, if there is one) starts from the guess the caller put into X; X is not put back between runs, so every later run starts from
+   the X that the run before it left: only warmup = 0, iters = 1 equals the solve from that guess.  B, X and opt->Dinv must be DEVICE pointers;
+   rtol, atol, check_every and history are not used.  Returns the mean ms per run, < 0 on error. */
 struct spmv_hip_cg_options;
 double spmv_hip_time_cg_iterations(spmv_Handle_t handle, const void *B, void *X, const struct spmv_hip_cg_options *opt, int warmup, int iters, float *ms_out);
 /* spmv_hip_bicgstab's iterations, timed as spmv_hip_time_cg_iterations times spmv_hip_cg's: an iteration is multiply, bicg_rv, bicg_half,

@@ -11,16 +11,19 @@ from spmv_amd import synth
 
 
 # ----------------------------------------------------------------------------- the loop
-def bicgstab(multiply, b, x0=None, dinv=None, rtol=0.0, atol=0.0, max_iterations=0):
+def bicgstab(multiply, b, x0=None, dinv=None, rtol=0.0, atol=0.0, max_iterations=0, watch=None):
     """Right-preconditioned BiCGStab as spmv_hip_bicgstab runs it.  multiply(p) -> A p in b's dtype.  -> dict: x, status, iterations, rr, bb,
-    history (rr after iteration 0 .. iterations) and iterates (x after iteration 0 .. iterations: what a run with a smaller max_iterations
-    returns)."""
+    history (rr after iteration 0 .. iterations), iterates (x after iteration 0 .. iterations: what a run with a smaller max_iterations
+    returns), halves (<s,s> of the half step of iteration 1 .. iterations, behind rr of iteration 0) and end: the kernel and the test that ended
+    the loop ("update:tt_zero", ...; "budget" when none did).  watch(*values), when given, sees every vector and every scalar of type T as it
+    is formed."""
     T = b.dtype.type
     f64 = np.float64
     m = b.size
     if m == 0:
-        return dict(x=b.copy(), status=CONVERGED, iterations=0, rr=0.0, bb=0.0, history=np.zeros(0), iterates=[])
+        return dict(x=b.copy(), status=CONVERGED, iterations=0, rr=0.0, bb=0.0, history=np.zeros(0), iterates=[], end="begin:empty", halves=np.zeros(0))
     fin = np.isfinite
+    see = watch if watch is not None else (lambda *values: None)
     with np.errstate(all="ignore"):
         if x0 is None:
             x, r = np.zeros_like(b), b.copy()
@@ -28,79 +31,89 @@ def bicgstab(multiply, b, x0=None, dinv=None, rtol=0.0, atol=0.0, max_iterations
             x = x0.copy()
             r = b - multiply(x)
         rhat, p = r.copy(), r.copy()
+        see(b, x, r) if dinv is None else see(b, x, r, dinv)
         rho, rr, bb = dot(rhat, r), dot(r, r), dot(b, b)
         thresh = max(rtol * rtol * bb, atol * atol)
-        status = None
+        status, end = None, "budget"
         if not (fin(bb) and fin(rr) and fin(rho)):
-            status = NONFINITE
+            status, end = NONFINITE, "begin:nonfinite"
         elif bb == 0:
-            status, rr, x = CONVERGED, 0.0, np.zeros_like(b)
+            status, rr, x, end = CONVERGED, 0.0, np.zeros_like(b), "begin:bb_zero"
         elif rr <= thresh:
-            status = CONVERGED
-        history, iterates, k = [rr], [x.copy()], 0
+            status, end = CONVERGED, "begin:converged"
+        history, iterates, halves, k = [rr], [x.copy()], [rr], 0
         while status is None and k < max_iterations:
             ph = dinv * p if dinv is not None else p
             v = multiply(ph)
             rv = dot(rhat, v)
             if not (fin(rv) and fin(rho)):
-                status = NONFINITE
+                status, end = NONFINITE, "half:dot_nonfinite"
                 break
             if rv == 0 or rho == 0:
-                status = BREAKDOWN
+                status, end = BREAKDOWN, "half:rv_zero" if rv == 0 else "half:rho_zero"
                 break
+            see(ph, v)
             alpha = T(f64(rho) / f64(rv))                  # fp64 quotient, rounded to T once
             if not fin(alpha):
-                status = NONFINITE
+                status, end = NONFINITE, "half:alpha_nonfinite"
                 break
-            x = x + alpha * ph                              # a multiply, then an add, in T
-            s = r - alpha * v
+            ap, av = alpha * ph, alpha * v
+            x = x + ap                                      # a multiply, then an add, in T
+            s = r - av
+            see(alpha, ap, av, x, s)
             ss = dot(s, s)
             k += 1
+            halves.append(ss)
             if not fin(ss) or ss <= thresh:                 # the half step ends the loop
-                status = CONVERGED if fin(ss) else NONFINITE
+                status, end = (CONVERGED, "update:ss_converged") if fin(ss) else (NONFINITE, "update:ss_nonfinite")
                 rr = ss
                 history.append(rr)
                 iterates.append(x.copy())
                 break
             sh = dinv * s if dinv is not None else s
             t = multiply(sh)
+            see(sh, t)
             ts, tt = dot(t, s), dot(t, t)
             omega = T(f64(ts) / f64(tt))
             half = None
             if not (fin(ts) and fin(tt)):
-                half = NONFINITE
+                half, end = NONFINITE, "update:ts_tt_nonfinite"
             elif tt == 0 or ts == 0:
-                half = BREAKDOWN
+                half, end = BREAKDOWN, "update:tt_zero" if tt == 0 else "update:ts_zero"
             elif not fin(omega):
-                half = NONFINITE
+                half, end = NONFINITE, "update:omega_nonfinite"
             elif omega == 0:
-                half = BREAKDOWN
+                half, end = BREAKDOWN, "update:omega_zero"
             if half is not None:                            # x keeps the half step
                 status, rr = half, ss
                 history.append(rr)
                 iterates.append(x.copy())
                 break
-            x = x + omega * sh
-            r = s - omega * t
+            osh, ot = omega * sh, omega * t
+            x = x + osh
+            r = s - ot
+            see(omega, osh, ot, x, r)
             rho_new, rr = dot(rhat, r), dot(r, r)
             history.append(rr)
             iterates.append(x.copy())
             if not (fin(rr) and fin(rho_new)):
-                status = NONFINITE
+                status, end = NONFINITE, "direction:nonfinite"
                 break
             if rr <= thresh:
-                status = CONVERGED
+                status, end = CONVERGED, "direction:converged"
                 break
             beta = T((f64(rho_new) / f64(rho)) * (f64(alpha) / f64(omega)))
             if not fin(beta):
-                status = NONFINITE
+                status, end = NONFINITE, "direction:beta_nonfinite"
                 break
             ov = omega * v                                  # four separate operations in T
             d = p - ov
             bd = beta * d
             p = r + bd
+            see(beta, ov, d, bd, p)
             rho = rho_new
-    return dict(x=x, status=MAX_ITERATIONS if status is None else status, iterations=k, rr=rr, bb=bb, history=np.array(history), iterates=iterates)
+    return dict(x=x, status=MAX_ITERATIONS if status is None else status, iterations=k, rr=rr, bb=bb, history=np.array(history), iterates=iterates,
+                end=end, halves=np.array(halves))
 
 
 # ----------------------------------------------------------------------------- matrices

@@ -54,14 +54,17 @@ def dot(a, b):
 
 
 # ----------------------------------------------------------------------------- the loop
-def cg(multiply, b, x0=None, dinv=None, rtol=0.0, atol=0.0, max_iterations=0):
+def cg(multiply, b, x0=None, dinv=None, rtol=0.0, atol=0.0, max_iterations=0, watch=None):
     """Preconditioned CG as spmv_hip_cg runs it.  multiply(p) -> A p in b's dtype.  -> dict: x, status, iterations, rr, bb, history (rr after
-    iteration 0 .. iterations) and iterates (x after iteration 0 .. iterations: what a run with a smaller max_iterations returns)."""
+    iteration 0 .. iterations), iterates (x after iteration 0 .. iterations: what a run with a smaller max_iterations returns) and end: the
+    kernel and the test that ended the loop ("direction:converged", ...; "budget" when none did).  watch(*values), when given, sees every
+    vector and every scalar of type T as it is formed."""
     T = b.dtype.type
     m = b.size
     if m == 0:
-        return dict(x=b.copy(), status=CONVERGED, iterations=0, rr=0.0, bb=0.0, history=np.zeros(0), iterates=[])
+        return dict(x=b.copy(), status=CONVERGED, iterations=0, rr=0.0, bb=0.0, history=np.zeros(0), iterates=[], end="begin:empty")
     fin = np.isfinite
+    see = watch if watch is not None else (lambda *values: None)
     with np.errstate(all="ignore"):
         if x0 is None:
             x, r = np.zeros_like(b), b.copy()
@@ -70,51 +73,58 @@ def cg(multiply, b, x0=None, dinv=None, rtol=0.0, atol=0.0, max_iterations=0):
             r = b - multiply(x)
         z = dinv * r if dinv is not None else r.copy()
         p = z.copy()
+        see(b, x, r, z) if dinv is None else see(b, x, r, z, dinv)
         rz, rr, bb = dot(r, z), dot(r, r), dot(b, b)
         thresh = max(rtol * rtol * bb, atol * atol)
-        status = None
+        status, end = None, "budget"
         if not (fin(bb) and fin(rr) and fin(rz)):
-            status = NONFINITE
+            status, end = NONFINITE, "begin:nonfinite"
         elif bb == 0:
-            status, rr, x = CONVERGED, 0.0, np.zeros_like(b)
+            status, rr, x, end = CONVERGED, 0.0, np.zeros_like(b), "begin:bb_zero"
         elif rr <= thresh:
-            status = CONVERGED
+            status, end = CONVERGED, "begin:converged"
         elif rz <= 0:
-            status = BREAKDOWN
+            status, end = BREAKDOWN, "begin:rz_breakdown"
         history, iterates, k = [rr], [x.copy()], 0
         while status is None and k < max_iterations:
             q = multiply(p)
             pq = dot(p, q)
             if not (fin(pq) and fin(rz)):
-                status = NONFINITE
+                status, end = NONFINITE, "update:dot_nonfinite"
                 break
             if pq <= 0:
-                status = BREAKDOWN
+                status, end = BREAKDOWN, "update:pq_breakdown"
                 break
+            see(q)
             alpha = T(np.float64(rz) / np.float64(pq))     # fp64 quotient, rounded to T once
             if not fin(alpha):
-                status = NONFINITE
+                status, end = NONFINITE, "update:alpha_nonfinite"
                 break
-            x = x + alpha * p                               # a multiply, then an add, in T
-            r = r - alpha * q
+            ap, aq = alpha * p, alpha * q
+            x = x + ap                                      # a multiply, then an add, in T
+            r = r - aq
             z = dinv * r if dinv is not None else r
+            see(alpha, ap, aq, x, r, z)
             rz_new, rr = dot(r, z), dot(r, r)
             k += 1
             history.append(rr)
             iterates.append(x.copy())
             beta = T(np.float64(rz_new) / np.float64(rz))
             if not (fin(rr) and fin(rz_new)):
-                status = NONFINITE
+                status, end = NONFINITE, "direction:nonfinite"
             elif rr <= thresh:
-                status = CONVERGED
+                status, end = CONVERGED, "direction:converged"
             elif rz_new <= 0:
-                status = BREAKDOWN
+                status, end = BREAKDOWN, "direction:rz_breakdown"
             elif not fin(beta):
-                status = NONFINITE
+                status, end = NONFINITE, "direction:beta_nonfinite"
             else:
-                p = z + beta * p
+                bp = beta * p
+                p = z + bp
+                see(beta, bp, p)
                 rz = rz_new
-    return dict(x=x, status=MAX_ITERATIONS if status is None else status, iterations=k, rr=rr, bb=bb, history=np.array(history), iterates=iterates)
+    return dict(x=x, status=MAX_ITERATIONS if status is None else status, iterations=k, rr=rr, bb=bb, history=np.array(history), iterates=iterates,
+                end=end)
 
 
 # ----------------------------------------------------------------------------- matrices
