@@ -872,6 +872,47 @@ int spmv_hip_bicgstab(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TY
                       const void *Matrix_Val, const void *B, void *X,
                       const spmv_hip_cg_options *opt, spmv_hip_cg_result *res);
 
+/* ---- conjugate gradients for k right-hand sides: A X = B, one pass over A per iteration ----------
+ * k INDEPENDENT conjugate-gradient recurrences (1 <= k <= SPMV_HIP_CG_COLUMNS_MAX) that share the matrix stream: per iteration ONE multiply
+ * Q = A P for all columns -- spmv_hip_spmm's executor, one panel, A read once -- and five vector kernels.  Every column has its own alpha,
+ * beta, stop test, status and iteration count.  This is not block CG: no Krylov space is shared, a column knows nothing of the others.
+ * spmv_hip_cg's rules hold word for word -- the return value, the synchronous call, the CSR arguments, use_x0, the stop test, m = 0, bb = 0,
+ * the status values, option "reorder", the errors -- with these differences:
+ *   - B and X are m x k, row-major with leading dimensions ldb, ldx >= k (spmv_hip_spmm's layout), host or device pointers; B's padding is
+ *     never read and X's never written; B and X must not overlap.  More than SPMV_HIP_CG_COLUMNS_MAX columns: call again.
+ *   - opt->Dinv is ONE vector of m elements for all columns (the preconditioner belongs to A).  rtol, atol, max_iterations, check_every and
+ *     use_x0 apply to every column alike.  opt->history, when given, is a HOST array of (max_iterations + 1) * k doubles: entry [it * k + j] is
+ *     column j's rr after iteration it, written for it <= res[j].iterations; the entries behind that are left as they were.
+ *   - res has k entries; res[j] is column j's status, iterations, rr and bb.  The call ends when every column has ended or at max_iterations.
+ *   - A column that has ended -- converged, breakdown, non-finite, or bb = 0 (its X column is set to zeros) -- is FROZEN: its X column, rr and
+ *     iterations are not touched again while the others go on (it is still multiplied; that is cheaper than re-packing).
+ *   - The resident ColIdx is needed as for spmv_hip_spmm with k > 1 (option keep_columns = 0: restored from the create-time arrays).
+ *   - Workspace, the solver's own: r, p, q (m x k elements each, compact), 4 k partial arrays of 1024 doubles and the per-column state in one
+ *     block of 3 * roundup(m * k * sizeof(T), 256) + 4 * k * 8192 + 1024 bytes, allocated at the first call and allocated anew when a later
+ *     call has a larger k; the history's device copy in another; freed and counted as spmv_hip_cg's.  spmv_hip_cg's and spmv_hip_bicgstab's
+ *     workspaces are neither shared nor grown.
+ *   - Errors (SPMV_HIP_E_ARG, X untouched): spmv_hip_cg's, and k < 1, k > SPMV_HIP_CG_COLUMNS_MAX, ldb < k, ldx < k, NULL res.
+ *   - k = 1 with ldb = ldx = 1 IS spmv_hip_cg: the same code path, workspace and bits (the handle's own multiply).  Every other form -- k = 1
+ *     with a leading dimension above 1 included -- runs the k-column kernels around spmv_hip_spmm's executor.
+ *
+ * The per-column contract -- bits, not a tolerance; tests/cg_columns_cases.py restates it in numpy.  Column j of a call is spmv_hip_cg's
+ * recurrence above, word for word: the start, the order of the updates x += alpha p; r -= alpha q; z = Dinv r; p = z + beta p (each a multiply
+ * and then an add in T), alpha and beta fp64 quotients rounded to T once, every test that ends the loop and their order.  Two differences:
+ *   1. The multiply is column j of spmv_hip_spmm's result: for rows of up to 512 entries ONE sequential fma chain per (row, column) in CSR
+ *      order; longer rows in the 64-segment form (see spmv_hip_spmm).
+ *   2. Every dot of column j is spmv_hip_cg's dot over that column's m elements by ROW index: the same P and L; the row at offset o of its
+ *      workgroup has position o mod 1024 and step o / 1024 (position = 4 * thread + slot of the single solve); one accumulator per (position,
+ *      column) starts at +0.0 and adds by ascending step; then the perfect adjacent-pair binary tree over the 1024 positions (slots, lanes,
+ *      waves), and the same tree over the <= 1024 partials.  tests/cg_cases.dot applied to a column is the model, unchanged.  The order does
+ *      not depend on k, ldb, ldx, alignment, access width, host or device pointers, or the contents or fate of another column.
+ *   Consequences: X[:, j], res[j] and column j's history are bit-identical for every k in 2 .. 16, every position j, every leading dimension,
+ *   every check_every and every method the handle was created with (for k > 1 the multiply does not depend on the method); a NaN or a breakdown
+ *   in one column changes no bit of any other; a frozen column's X, rr and iterations stay what they were when it ended. */
+#define SPMV_HIP_CG_COLUMNS_MAX 16
+int spmv_hip_cg_columns(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                        const void *Matrix_Val, int k, const void *B, long long ldb, void *X, long long ldx,
+                        const spmv_hip_cg_options *opt, spmv_hip_cg_result *res /* k entries */);
+
 #endif /* SPMV_HIP_EXT_H */
 
 #if defined(__cplusplus)

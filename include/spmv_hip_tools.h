@@ -103,6 +103,12 @@ double spmv_hip_time_cg_iterations(spmv_Handle_t handle, const void *B, void *X,
 /* spmv_hip_bicgstab's iterations, timed as spmv_hip_time_cg_iterations times spmv_hip_cg's: an iteration is multiply, bicg_rv, bicg_half,
    multiply, bicg_ts, bicg_update, bicg_direction.  The same arguments, the same rules, the same return value. */
 double spmv_hip_time_bicgstab_iterations(spmv_Handle_t handle, const void *B, void *X, const struct spmv_hip_cg_options *opt, int warmup, int iters, float *ms_out);
+/* spmv_hip_cg_columns' iterations, timed as spmv_hip_time_cg_iterations times spmv_hip_cg's: an iteration is the k-column multiply, ccg_dot,
+   ccg_alpha, ccg_update, ccg_beta, ccg_direction.  B and X: m x k DEVICE arrays with leading dimensions ldb, ldx >= k, opt->Dinv a DEVICE vector
+   of m elements or NULL; 1 <= k <= SPMV_HIP_CG_COLUMNS_MAX; k = 1 with ldb = ldx = 1 times spmv_hip_cg itself.  The same rules about what X
+   holds, the same return value. */
+double spmv_hip_time_cg_columns_iterations(spmv_Handle_t handle, int k, const void *B, long long ldb, void *X, long long ldx, const struct spmv_hip_cg_options *opt, int warmup,
+                                           int iters, float *ms_out);
 /* copies the built transpose map to host: rowptr_t (n+1 entries) and perm (nnz entries: perm[p] = CSR index in A of the entry at
    position p of A^T's CSR); either may be NULL.  SPMV_HIP_E_NOSTATE until the transpose is built. */
 int spmv_hip_transpose_map(spmv_Handle_t handle, int *rowptr_t, int *perm);

@@ -28,19 +28,24 @@ struct SolveState {
     double rr, bb;
 };
 
+struct ColsState; // cg_columns.hpp: the per-column state of spmv_hip_cg_columns
+
 // what one solve's launches need (device pointers)
 struct SolveArgs {
     int m = 0, parts = 0;
+    int k = 1;                     // right-hand sides: 1 but for spmv_hip_cg_columns, whose workspace vectors are m x k with ld = k
+    long long ldb = 1, ldx = 1;    // leading dimensions of b and x
     long long span = 0;            // L
     void *vec[6] = {};             // the workspace vectors: the solver's own enum names the slots (kCgVec*, kBicgVec*)
     void *x = nullptr;
     const void *b = nullptr, *dinv = nullptr;
     double *part = nullptr;        // the solver's partial arrays, kCgMaxParts doubles each
     SolveState *state = nullptr;
+    ColsState *cols = nullptr;     // spmv_hip_cg_columns: in the place of `state`
     double *hist = nullptr;        // NULL: not wanted
     double rtol2 = 0, atol2 = 0;   // rtol^2, atol^2
     int nostop = 0;                // the timer: no test ever ends the loop
-    bool wide = false;             // b, x and dinv allow 16-byte accesses (the workspace vectors always do)
+    bool wide = false;             // b, x and dinv allow 16-byte accesses (the workspace vectors always do); k columns: b and x are compact and aligned
     bool f64 = true;
 };
 

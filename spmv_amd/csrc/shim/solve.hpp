@@ -1,24 +1,39 @@
-// shim/solve.hpp -- part of spmv_shim.hip: the solves on the RESIDENT matrix that stay on the device, conjugate gradients (spmv_hip_cg) and
-// BiCGStab (spmv_hip_bicgstab), and their timers.  The vector kernels are kernels/cg.hpp and kernels/bicgstab.hpp, launched from their own
-// translation unit (spmv_solve.hip); the multiplies -- q = A p, or v = A ph and t = A sh -- are launch<T>() on workspace vectors: the launch
-// spmv_shim_run makes, without its staging: the handle's own schedule, spmv()'s bits.
+// shim/solve.hpp -- part of spmv_shim.hip: the solves on the RESIDENT matrix that stay on the device, conjugate gradients (spmv_hip_cg),
+// BiCGStab (spmv_hip_bicgstab) and conjugate gradients for k right-hand sides at once (spmv_hip_cg_columns), and their timers.  The vector
+// kernels are kernels/cg.hpp, kernels/bicgstab.hpp and kernels/cg_columns.hpp, launched from their own translation unit (spmv_solve.hip); the
+// multiplies -- q = A p, or v = A ph and t = A sh -- are launch<T>() on workspace vectors: the launch spmv_shim_run makes, without its staging:
+// the handle's own schedule, spmv()'s bits.  For k columns the multiply is spmm_panels() on the compact workspace vectors: the launches
+// spmv_shim_spmm makes, without its staging: spmv_hip_spmm's bits.
 //
 // The host enqueues `check_every` iterations, copies the state back and synchronises ONCE; inside a batch nothing waits for the host: alpha,
-// (omega,) beta and the stop tests are derived on the device by every workgroup (kernels/cg.hpp), and once the state says that the loop has ended
-// every later kernel of the batch returns at once -- what is wasted is at most check_every - 1 multiplies into the scratch vector q (BiCGStab:
-// 2 check_every - 1 into v and t).  The returned x, iterations and history therefore do not depend on check_every.
+// (omega,) beta and the stop tests are derived on the device (kernels/cg.hpp), and once the state says that the loop has ended every later
+// kernel of the batch returns at once -- what is wasted is at most check_every - 1 multiplies into the scratch vector q (BiCGStab:
+// 2 check_every - 1 into v and t).  The returned x, iterations and history therefore do not depend on check_every.  With k columns the state
+// holds k of everything; the loop ends when every column has ended.
 //
-// Everything here is written once; a solver is a Solver: its sizes, its workspace and what its start and one iteration enqueue.
+// Everything here is written once; a solver is a Solver: its sizes, its workspace, what its start and one iteration enqueue and how its
+// state reads.  k, ldb and ldx are 1 for the two single solves.
 #pragma once
+
+// what the host reads out of a solver's state, per column
+struct SolveLook {
+    bool done[kCcgMaxK];
+    int status[kCcgMaxK], iterations[kCcgMaxK];
+    double rr[kCcgMaxK], bb[kCcgMaxK];
+};
 
 struct Solver {
     const char *name;                 // in error texts
-    int vectors, part_arrays;         // workspace vectors of m elements; partial arrays of kCgMaxParts doubles
+    int vectors, part_arrays;         // workspace vectors of m k elements; partial arrays of kCgMaxParts doubles PER COLUMN
     int check_every;                  // iterations between two looks at the state when the caller leaves check_every at 0
+    size_t state_bytes, state_room;   // the device state: what is zeroed and copied, and the bytes behind the partial arrays that hold it
     void *spmv_dev::*ws;              // the workspace: the vectors, the partial arrays, the state
+    int spmv_dev::*ws_k;              // the columns that workspace holds; nullptr: the solver has one column
     StageBuf spmv_dev::*hist;         // the history block
+    int stage_b, stage_x;             // the stage buffers of host B and X
     int (*start)(const Solver &s, spmv_dev *d, const SolveArgs &a, bool use_x0); // behind the zeroed state: (A x0,) the init and begin kernels
     int (*iteration)(const Solver &s, spmv_dev *d, const SolveArgs &a, int k);   // iteration k >= 1: the multiplies and the vector kernels
+    void (*look)(const void *state, int k, SolveLook &l);                         // a host copy of the state -> what it says
 };
 
 static int solve_multiply(spmv_dev *d, const void *x, void *y)
@@ -63,44 +78,104 @@ static int bicg_iteration(const Solver &s, spmv_dev *d, const SolveArgs &a, int 
     return solve_launched(s, bicg_second_launch(a, k, d->stream));
 }
 
+// (q = A X0 for all columns,) ccg_init + ccg_begin
+static int ccg_start(const Solver &s, spmv_dev *d, const SolveArgs &a, bool use_x0)
+{
+    int rc;
+    if (use_x0 && (rc = spmm_panels(d, a.k, (const char *) a.x, a.ldx, (char *) a.vec[kCcgVecQ], a.k))) return rc;
+    return solve_launched(s, ccg_start_launch(a, use_x0, d->stream));
+}
+
+// q = A p for all columns in one pass over A, then the five vector kernels
+static int ccg_iteration(const Solver &s, spmv_dev *d, const SolveArgs &a, int it)
+{
+    const int rc = spmm_panels(d, a.k, (const char *) a.vec[kCcgVecP], a.k, (char *) a.vec[kCcgVecQ], a.k);
+    return rc ? rc : solve_launched(s, ccg_iteration_launch(a, it, d->stream));
+}
+
+static void single_look(const void *state, int, SolveLook &l)
+{
+    const SolveState &hs = *(const SolveState *) state;
+    l.done[0] = hs.end_half || hs.end_update || hs.end_direction;
+    l.status[0] = hs.status;
+    l.iterations[0] = hs.iterations;
+    l.rr[0] = hs.rr;
+    l.bb[0] = hs.bb;
+}
+
+static void cols_look(const void *state, int k, SolveLook &l)
+{
+    const ColsState &hs = *(const ColsState *) state;
+    for (int j = 0; j < k; ++j) {
+        l.done[j] = hs.end_update[j] || hs.end_direction[j];
+        l.status[j] = hs.status[j];
+        l.iterations[j] = hs.iterations[j];
+        l.rr[j] = hs.rr[j];
+        l.bb[j] = hs.bb[j];
+    }
+}
+
 // indexed by the solver ids of spmv_shim.h.  check_every: DESIGN 3.26 for CG.  BiCGStab's is from the sweep of tools/bicgstab_bench.py (DESIGN
 // 3.27): a look costs 23-31 us; at 8 an iteration is within 3 % of the best figure of the sweep (32) on the 1e6-row case and within 0.3 % on the
-// 1e7-row band, and what a larger value saves per iteration it loses again behind convergence, where on average check_every - 1 multiplies are wasted
+// 1e7-row band, and what a larger value saves per iteration it loses again behind convergence, where on average check_every - 1 multiplies are wasted.
+// The k-column solve keeps CG's 8
 static const Solver kSolvers[] = {
-    {"cg", kCgVectors, kCgPartArrays, 8, &spmv_dev::cg_ws, &spmv_dev::cg_hist, cg_start, cg_iteration},
-    {"bicgstab", kBicgVectors, kBicgPartArrays, 8, &spmv_dev::bicg_ws, &spmv_dev::bicg_hist, bicg_start, bicg_iteration},
+    {"cg", kCgVectors, kCgPartArrays, 8, sizeof(SolveState), 256, &spmv_dev::cg_ws, nullptr, &spmv_dev::cg_hist, STAGE_CG_B, STAGE_CG_X, cg_start, cg_iteration, single_look},
+    {"bicgstab", kBicgVectors, kBicgPartArrays, 8, sizeof(SolveState), 256, &spmv_dev::bicg_ws, nullptr, &spmv_dev::bicg_hist, STAGE_CG_B, STAGE_CG_X, bicg_start, bicg_iteration,
+     single_look},
+    {"cg_columns", kCcgVectors, kCcgPartArrays, 8, sizeof(ColsState), 1024, &spmv_dev::cgc_ws, &spmv_dev::cgc_k, &spmv_dev::cgc_hist, STAGE_CGC_B, STAGE_CGC_X, ccg_start,
+     ccg_iteration, cols_look},
 };
 static const Solver *solver_of(int id) { return id == SPMV_SHIM_SOLVE_CG || id == SPMV_SHIM_SOLVE_BICGSTAB ? &kSolvers[id] : nullptr; }
 
-static size_t solve_vec_bytes(const spmv_dev *d) { return (d->vsize * (size_t) d->m + 255) & ~(size_t) 255; }
+// bytes of one workspace vector of m x k elements
+static size_t solve_vec_bytes(const spmv_dev *d, int k) { return (d->vsize * (size_t) d->m * (size_t) k + 255) & ~(size_t) 255; }
+static size_t solve_tail_bytes(const Solver &s, int k) { return sizeof(double) * s.part_arrays * (size_t) k * kCgMaxParts + s.state_room; }
+// the columns the solver's workspace holds (0: none yet)
+static int solve_ws_columns(const Solver &s, const spmv_dev *d) { return !(d->*s.ws) ? 0 : s.ws_k ? d->*s.ws_k : 1; }
 
-// the vectors, the partial arrays (zeroed once: the entries behind the P in use stay +0.0) and the state: allocated at the solver's first solve
-static int solve_workspace(const Solver &s, spmv_dev *d)
+// the vectors, the partial arrays (zeroed once: the entries behind the P in use stay +0.0) and the state: allocated at the solver's first solve --
+// s.vectors * solve_vec_bytes(k) + 8 * s.part_arrays * k * 1024 + s.state_room bytes -- and, for a solver with columns, given back and
+// allocated anew when a call has more columns than it holds
+static int solve_workspace(const Solver &s, spmv_dev *d, int k)
 {
-    static_assert(sizeof(SolveState) <= 256, "the state has 256 bytes behind the partial arrays");
-    if (d->*s.ws) return SPMV_HIP_OK;
-    const size_t vec = solve_vec_bytes(d), tail = sizeof(double) * s.part_arrays * kCgMaxParts + 256;
+    static_assert(sizeof(SolveState) <= 256 && sizeof(ColsState) <= 1024, "the state's room behind the partial arrays");
+    const int have = solve_ws_columns(s, d);
+    if (have >= k) return SPMV_HIP_OK;
+    if (have) {
+        quiesce(d);
+        (void) pool_free(d->*s.ws);
+        d->device_bytes -= (long long) (s.vectors * solve_vec_bytes(d, have) + solve_tail_bytes(s, have));
+        d->*s.ws = nullptr;
+    }
+    const size_t vec = solve_vec_bytes(d, k), tail = solve_tail_bytes(s, k);
     ALLOC_TRY(d, &(d->*s.ws), s.vectors * vec + tail, false);
+    if (s.ws_k) d->*s.ws_k = k;
     HIP_TRY(hipMemsetAsync((char *) (d->*s.ws) + s.vectors * vec, 0, tail, d->stream));
     return SPMV_HIP_OK;
 }
 
-// One solve's device operands: the workspace carved up, host B / X / Dinv staged (X's copy-back registered with the stager; the initial
-// guess copied in when it is wanted; the solvers share the stage buffers: both calls are synchronous, so they never hold them at the same
-// time), the history block, the geometry of the dots.  m > 0.
-static int solve_prepare(const Solver &s, spmv_dev *d, Stager &stg, const void *b, void *x, const spmv_hip_cg_options *opt, size_t hist_entries, int nostop, SolveArgs &a)
+// One solve's device operands: the workspace carved up (by the columns it HOLDS, so that a partial array never lies where a vector did), host
+// B / X / Dinv staged (X's copy-back registered with the stager; the initial guess copied in when it is wanted; the single solves share their
+// stage buffers, and all three Dinv's: the calls are synchronous, so they never hold them at the same time), the history block, the geometry
+// of the dots.  m > 0.
+static int solve_prepare(const Solver &s, spmv_dev *d, Stager &stg, int k, const void *b, long long ldb, void *x, long long ldx, const spmv_hip_cg_options *opt,
+                         size_t hist_entries, int nostop, SolveArgs &a)
 {
-    int rc = solve_workspace(s, d);
+    int rc = solve_workspace(s, d, k);
     if (rc) return rc;
-    const size_t vec = solve_vec_bytes(d), m = (size_t) d->m;
+    const size_t vec = solve_vec_bytes(d, solve_ws_columns(s, d)), m = (size_t) d->m;
     char *ws = (char *) (d->*s.ws);
     a.m = d->m;
+    a.k = k;
     const long long chunks = ((long long) d->m + kCgChunk - 1) / kCgChunk;
     a.parts = (int) (chunks < kCgMaxParts ? chunks : kCgMaxParts);
     a.span = (long long) kCgChunk * (((long long) d->m + (long long) kCgChunk * a.parts - 1) / ((long long) kCgChunk * a.parts));
     for (int i = 0; i < s.vectors; ++i) a.vec[i] = ws + i * vec;
     a.part = (double *) (ws + s.vectors * vec);
-    a.state = (SolveState *) (ws + s.vectors * vec + sizeof(double) * s.part_arrays * kCgMaxParts);
+    void *state = ws + s.vectors * vec + sizeof(double) * s.part_arrays * (size_t) solve_ws_columns(s, d) * kCgMaxParts;
+    if (s.ws_k) a.cols = (ColsState *) state;
+    else a.state = (SolveState *) state;
     a.rtol2 = opt->rtol * opt->rtol;
     a.atol2 = opt->atol * opt->atol;
     a.nostop = nostop;
@@ -108,10 +183,13 @@ static int solve_prepare(const Solver &s, spmv_dev *d, Stager &stg, const void *
     a.b = b;
     a.dinv = opt->Dinv;
     a.x = x;
+    a.ldb = ldb;
+    a.ldx = ldx;
     long long ld = 1;
-    if ((rc = stg.in(d->stage[STAGE_CG_B], a.b, ld, m, 1)) || (rc = stg.in(d->stage[STAGE_CG_DINV], a.dinv, ld, m, 1)) || (rc = stg.out(d->stage[STAGE_CG_X], a.x, ld, m, 1))) return rc;
-    if (a.x != x && opt->use_x0) HIP_TRY(hipMemcpyAsync(a.x, x, d->vsize * m, hipMemcpyHostToDevice, d->stream));
-    a.wide = wide_ok(a.b, 1, 16) && wide_ok(a.x, 1, 16) && (!a.dinv || wide_ok(a.dinv, 1, 16));
+    if ((rc = stg.in(d->stage[s.stage_b], a.b, a.ldb, m, k)) || (rc = stg.in(d->stage[STAGE_CG_DINV], a.dinv, ld, m, 1)) || (rc = stg.out(d->stage[s.stage_x], a.x, a.ldx, m, k))) return rc;
+    if (a.x != x && opt->use_x0) HIP_TRY(stg.copy(a.x, (size_t) k, x, (size_t) ldx, m, (size_t) k, hipMemcpyHostToDevice, d->vsize));
+    // 16-byte accesses: B and X compact and aligned; the single solves' kernels read Dinv that way too, the k-column ones by element
+    a.wide = a.ldb == k && a.ldx == k && wide_ok(a.b, 1, 16) && wide_ok(a.x, 1, 16) && (s.ws_k || !a.dinv || wide_ok(a.dinv, 1, 16));
     a.hist = nullptr;
     if (hist_entries > 0) {
         if ((rc = stg.reserve(d->*s.hist, sizeof(double) * hist_entries))) return rc;
@@ -120,64 +198,95 @@ static int solve_prepare(const Solver &s, spmv_dev *d, Stager &stg, const void *
     return SPMV_HIP_OK;
 }
 
+static void *solve_state(const Solver &s, const SolveArgs &a) { return s.ws_k ? (void *) a.cols : (void *) a.state; }
+
 // the state zeroed, then the solver's start
 static int solve_start(const Solver &s, spmv_dev *d, const SolveArgs &a, bool use_x0)
 {
-    HIP_TRY(hipMemsetAsync(a.state, 0, sizeof(SolveState), d->stream));
+    HIP_TRY(hipMemsetAsync(solve_state(s, a), 0, s.state_bytes, d->stream));
     return s.start(s, d, a, use_x0);
 }
 
-static int solve_run(const Solver &s, spmv_dev *d, const void *b, void *x, const spmv_hip_cg_options *opt, spmv_hip_cg_result *res)
+// res: k entries.  history (k > 1): entry [it * k + j] is column j's rr after iteration it, written for it <= that column's iterations
+static int solve_run(const Solver &s, spmv_dev *d, int k, const void *b, long long ldb, void *x, long long ldx, const spmv_hip_cg_options *opt, spmv_hip_cg_result *res)
 {
     if (!d || !d->built) return fail(SPMV_HIP_E_NOSTATE, "%s: schedule not built", s.name);
     if (!opt || !res) return fail(SPMV_HIP_E_ARG, "%s: opt or res is NULL", s.name);
+    if (k < 1 || k > (s.ws_k ? kCcgMaxK : 1) || ldb < k || ldx < k) return fail(SPMV_HIP_E_ARG, "%s: need 1 <= k <= %d, ldb >= k, ldx >= k", s.name, s.ws_k ? kCcgMaxK : 1);
     if (d->m != d->n) return fail(SPMV_HIP_E_ARG, "%s: the matrix is %d x %d, not square", s.name, d->m, d->n);
     if (d->m > 0 && (!b || !x)) return fail(SPMV_HIP_E_ARG, "%s: B or X is NULL", s.name);
-    res->status = SPMV_HIP_CG_CONVERGED;
-    res->iterations = 0;
-    res->rr = res->bb = 0;
+    if (s.ws_k && d->nnz > 0 && !d->colidx) return fail(SPMV_HIP_E_NOSTATE, "%s: the resident column indices were released (spmv_shim_restore_columns first)", s.name);
+    for (int j = 0; j < k; ++j) {
+        res[j].status = SPMV_HIP_CG_CONVERGED;
+        res[j].iterations = 0;
+        res[j].rr = res[j].bb = 0;
+    }
     if (d->m == 0) return SPMV_HIP_OK;
     DeviceGuard guard(d->device);
     if (!guard.ok) return fail(SPMV_HIP_E_RUNTIME, "hipSetDevice(%d) failed", d->device);
+    int rc;
+    if (s.ws_k && (rc = spmm_plan(d))) return rc;
     Stager stg{d};
     SolveArgs a;
-    int rc = solve_prepare(s, d, stg, b, x, opt, opt->history ? (size_t) opt->max_iterations + 1 : 0, 0, a);
+    rc = solve_prepare(s, d, stg, k, b, ldb, x, ldx, opt, opt->history ? ((size_t) opt->max_iterations + 1) * (size_t) k : 0, 0, a);
     if (rc || (rc = solve_start(s, d, a, opt->use_x0 != 0))) return rc;
     const int every = opt->check_every > 0 ? opt->check_every : s.check_every;
-    SolveState hs;
-    bool done = false;
-    for (int k = 0;;) {
-        HIP_TRY(hipMemcpyAsync(&hs, a.state, sizeof hs, hipMemcpyDeviceToHost, d->stream));
+    alignas(8) unsigned char hs[sizeof(ColsState) > sizeof(SolveState) ? sizeof(ColsState) : sizeof(SolveState)];
+    SolveLook l;
+    for (int it = 0;;) {
+        HIP_TRY(hipMemcpyAsync(hs, solve_state(s, a), s.state_bytes, hipMemcpyDeviceToHost, d->stream));
         HIP_TRY(hipStreamSynchronize(d->stream));
-        done = hs.end_half || hs.end_update || hs.end_direction;
-        if (done || k >= opt->max_iterations) break;
-        const int stop = opt->max_iterations - k < every ? opt->max_iterations : k + every;
-        while (k < stop)
-            if ((rc = s.iteration(s, d, a, ++k))) return rc;
+        s.look(hs, k, l);
+        bool done = true;
+        for (int j = 0; j < k; ++j) done = done && l.done[j];
+        if (done || it >= opt->max_iterations) break;
+        const int stop = opt->max_iterations - it < every ? opt->max_iterations : it + every;
+        while (it < stop)
+            if ((rc = s.iteration(s, d, a, ++it))) return rc;
     }
-    res->status = done ? hs.status : SPMV_HIP_CG_MAX_ITERATIONS;
-    res->iterations = hs.iterations;
-    res->rr = hs.rr;
-    res->bb = hs.bb;
-    if (done && hs.status == SPMV_HIP_CG_CONVERGED && hs.bb == 0) HIP_TRY(hipMemsetAsync(a.x, 0, d->vsize * (size_t) d->m, d->stream)); // B = 0: x = 0
-    if (opt->history) HIP_TRY(hipMemcpyAsync(opt->history, a.hist, sizeof(double) * ((size_t) hs.iterations + 1), hipMemcpyDeviceToHost, d->stream));
+    int longest = 0;
+    for (int j = 0; j < k; ++j) {
+        res[j].status = l.done[j] ? l.status[j] : SPMV_HIP_CG_MAX_ITERATIONS;
+        res[j].iterations = l.iterations[j];
+        res[j].rr = l.rr[j];
+        res[j].bb = l.bb[j];
+        if (l.iterations[j] > longest) longest = l.iterations[j];
+        if (!(l.done[j] && l.status[j] == SPMV_HIP_CG_CONVERGED && l.bb[j] == 0)) continue;
+        // B = 0: x = 0
+        if (k == 1 && a.ldx == 1) HIP_TRY(hipMemsetAsync(a.x, 0, d->vsize * (size_t) d->m, d->stream));
+        else HIP_TRY(hipMemset2DAsync((char *) a.x + d->vsize * (size_t) j, d->vsize * (size_t) a.ldx, 0, d->vsize, (size_t) d->m, d->stream));
+    }
+    std::vector<double> hist;
+    if (opt->history && k == 1) HIP_TRY(hipMemcpyAsync(opt->history, a.hist, sizeof(double) * ((size_t) longest + 1), hipMemcpyDeviceToHost, d->stream));
+    if (opt->history && k > 1) {
+        hist.resize(((size_t) longest + 1) * (size_t) k);
+        HIP_TRY(hipMemcpyAsync(hist.data(), a.hist, sizeof(double) * hist.size(), hipMemcpyDeviceToHost, d->stream));
+    }
     if ((rc = stg.finish())) return rc;
     HIP_TRY(hipStreamSynchronize(d->stream)); // the call is synchronous whatever the handle's async setting
+    for (size_t i = 0; i < hist.size(); ++i) // the entries behind a column's end stay the caller's
+        if ((int) (i / (size_t) k) <= l.iterations[i % (size_t) k]) opt->history[i] = hist[i];
     return SPMV_HIP_OK;
 }
 
 // `warmup` untimed + `iters` timed RUNS of opt->max_iterations iterations each, the stop tests disabled: every run starts again from B (and
 // X when use_x0), its iterations are enqueued back to back and bracketed by two events on the handle's stream (the start is outside them:
 // not state.hpp's time_events, which brackets a whole call).  ms_out[i] (may be NULL): run i.  Mean ms per run, < 0 on failure.  Device pointers only.
-static double solve_time(const Solver &s, spmv_dev *d, const void *b, void *x, const spmv_hip_cg_options *opt, int warmup, int iters, float *ms_out)
+static double solve_time(const Solver &s, spmv_dev *d, int k, const void *b, long long ldb, void *x, long long ldx, const spmv_hip_cg_options *opt, int warmup, int iters,
+                         float *ms_out)
 {
-    if (!d || !d->built || !opt || iters <= 0 || warmup < 0 || opt->max_iterations < 1 || d->m != d->n || d->m <= 0) { fail(SPMV_HIP_E_ARG, "time_%s: bad arguments", s.name); return -1.0; }
+    if (!d || !d->built || !opt || iters <= 0 || warmup < 0 || opt->max_iterations < 1 || d->m != d->n || d->m <= 0 || k < 1 || k > (s.ws_k ? kCcgMaxK : 1) || ldb < k || ldx < k) {
+        fail(SPMV_HIP_E_ARG, "time_%s: bad arguments", s.name);
+        return -1.0;
+    }
     if (!is_device_ptr(b) || !is_device_ptr(x) || (opt->Dinv && !is_device_ptr(opt->Dinv))) { fail(SPMV_HIP_E_ARG, "time_%s: B, X and Dinv must be device pointers", s.name); return -1.0; }
+    if (s.ws_k && d->nnz > 0 && !d->colidx) { fail(SPMV_HIP_E_NOSTATE, "time_%s: the resident column indices were released", s.name); return -1.0; }
     DeviceGuard guard(d->device);
     if (!guard.ok) { fail(SPMV_HIP_E_RUNTIME, "hipSetDevice(%d) failed", d->device); return -1.0; }
+    if (s.ws_k && spmm_plan(d)) return -1.0;
     Stager stg{d};
     SolveArgs a;
-    if (solve_prepare(s, d, stg, b, x, opt, 0, 1, a)) return -1.0;
+    if (solve_prepare(s, d, stg, k, b, ldb, x, ldx, opt, 0, 1, a)) return -1.0;
     std::vector<hipEvent_t> ev;
     auto done = [&](double mean) {
         for (hipEvent_t e : ev) (void) hipEventDestroy(e);
@@ -192,7 +301,7 @@ static double solve_time(const Solver &s, spmv_dev *d, const void *b, void *x, c
     for (int run = -warmup; run < iters && !rc; ++run) {
         rc = solve_start(s, d, a, opt->use_x0 != 0);
         if (run >= 0) (void) hipEventRecord(ev[2 * run], d->stream);
-        for (int k = 1; k <= opt->max_iterations && !rc; ++k) rc = s.iteration(s, d, a, k);
+        for (int it = 1; it <= opt->max_iterations && !rc; ++it) rc = s.iteration(s, d, a, it);
         if (run >= 0) (void) hipEventRecord(ev[2 * run + 1], d->stream);
     }
     const hipError_t e = hipStreamSynchronize(d->stream);
@@ -211,12 +320,23 @@ static double solve_time(const Solver &s, spmv_dev *d, const void *b, void *x, c
 extern "C" int spmv_shim_solve(int solver, spmv_dev *d, const void *b, void *x, const spmv_hip_cg_options *opt, spmv_hip_cg_result *res)
 {
     const Solver *s = solver_of(solver);
-    return s ? solve_run(*s, d, b, x, opt, res) : fail(SPMV_HIP_E_ARG, "solve: no solver %d", solver);
+    return s ? solve_run(*s, d, 1, b, 1, x, 1, opt, res) : fail(SPMV_HIP_E_ARG, "solve: no solver %d", solver);
 }
 
 extern "C" double spmv_shim_time_solve(int solver, spmv_dev *d, const void *b, void *x, const spmv_hip_cg_options *opt, int warmup, int iters, float *ms_out)
 {
     const Solver *s = solver_of(solver);
     if (!s) { fail(SPMV_HIP_E_ARG, "time_solve: no solver %d", solver); return -1.0; }
-    return solve_time(*s, d, b, x, opt, warmup, iters, ms_out);
+    return solve_time(*s, d, 1, b, 1, x, 1, opt, warmup, iters, ms_out);
+}
+
+extern "C" int spmv_shim_solve_columns(spmv_dev *d, int k, const void *b, long long ldb, void *x, long long ldx, const spmv_hip_cg_options *opt, spmv_hip_cg_result *res)
+{
+    return solve_run(kSolvers[SPMV_SHIM_SOLVE_CG_COLUMNS], d, k, b, ldb, x, ldx, opt, res);
+}
+
+extern "C" double spmv_shim_time_solve_columns(spmv_dev *d, int k, const void *b, long long ldb, void *x, long long ldx, const spmv_hip_cg_options *opt, int warmup, int iters,
+                                               float *ms_out)
+{
+    return solve_time(kSolvers[SPMV_SHIM_SOLVE_CG_COLUMNS], d, k, b, ldb, x, ldx, opt, warmup, iters, ms_out);
 }

@@ -52,24 +52,12 @@ static int spmm_plan(spmv_dev *d)
     return SPMV_HIP_OK;
 }
 
-extern "C" int spmv_shim_spmm(spmv_dev *d, int k, const void *x, long long ldx, void *y, long long ldy)
+// Y = A X on DEVICE operands, one pass over A per panel of KP columns; the batch table and the long-row list are built (spmm_plan).  What
+// spmv_shim_spmm launches behind its staging, and what spmv_hip_cg_columns multiplies its workspace vectors with (shim/solve.hpp)
+static int spmm_panels(spmv_dev *d, int k, const char *xd, long long lx, char *yd, long long ly)
 {
-    if (!d || !d->built) return fail(SPMV_HIP_E_NOSTATE, "spmm: schedule not built");
-    if (k < 1 || ldx < k || ldy < k) return fail(SPMV_HIP_E_ARG, "spmm: need k >= 1, ldx >= k, ldy >= k (k = %d, ldx = %lld, ldy = %lld)", k, ldx, ldy);
-    if (d->m > 0 && (!x || !y)) return fail(SPMV_HIP_E_ARG, "spmm: X or Y is NULL");
-    if (d->nnz > 0 && !d->colidx) return fail(SPMV_HIP_E_NOSTATE, "spmm: the resident column indices were released (spmv_shim_restore_columns first)");
-    if (d->m == 0) return SPMV_HIP_OK;
-    DeviceGuard guard(d->device);
-    if (!guard.ok) return fail(SPMV_HIP_E_RUNTIME, "hipSetDevice(%d) failed", d->device);
-    int rc = spmm_plan(d);
-    if (rc) return rc;
     const size_t s = d->vsize;
     const bool f64 = s == sizeof(double);
-    Stager stg{d};
-    const char *xd = (const char *) x;
-    char *yd = (char *) y;
-    long long lx = ldx, ly = ldy;
-    if ((rc = stg.in(d->stage[STAGE_SPMM_X], xd, lx, (size_t) d->n, k)) || (rc = stg.out(d->stage[STAGE_SPMM_Y], yd, ly, (size_t) d->m, k))) return rc;
     const int KP = f64 ? SpmmShape<double>::KP : SpmmShape<float>::KP;
     for (int c = 0; c < k; c += KP) { // one pass over A per panel
         SpmmArgs a;
@@ -91,6 +79,26 @@ extern "C" int spmv_shim_spmm(spmv_dev *d, int k, const void *x, long long ldx, 
         const hipError_t e = spmm_launch(a, f64, d->stream);
         if (e != hipSuccess) return fail(SPMV_HIP_E_RUNTIME, "spmm: launch: %s", hipGetErrorString(e));
     }
+    return SPMV_HIP_OK;
+}
+
+extern "C" int spmv_shim_spmm(spmv_dev *d, int k, const void *x, long long ldx, void *y, long long ldy)
+{
+    if (!d || !d->built) return fail(SPMV_HIP_E_NOSTATE, "spmm: schedule not built");
+    if (k < 1 || ldx < k || ldy < k) return fail(SPMV_HIP_E_ARG, "spmm: need k >= 1, ldx >= k, ldy >= k (k = %d, ldx = %lld, ldy = %lld)", k, ldx, ldy);
+    if (d->m > 0 && (!x || !y)) return fail(SPMV_HIP_E_ARG, "spmm: X or Y is NULL");
+    if (d->nnz > 0 && !d->colidx) return fail(SPMV_HIP_E_NOSTATE, "spmm: the resident column indices were released (spmv_shim_restore_columns first)");
+    if (d->m == 0) return SPMV_HIP_OK;
+    DeviceGuard guard(d->device);
+    if (!guard.ok) return fail(SPMV_HIP_E_RUNTIME, "hipSetDevice(%d) failed", d->device);
+    int rc = spmm_plan(d);
+    if (rc) return rc;
+    Stager stg{d};
+    const char *xd = (const char *) x;
+    char *yd = (char *) y;
+    long long lx = ldx, ly = ldy;
+    if ((rc = stg.in(d->stage[STAGE_SPMM_X], xd, lx, (size_t) d->n, k)) || (rc = stg.out(d->stage[STAGE_SPMM_Y], yd, ly, (size_t) d->m, k))) return rc;
+    if ((rc = spmm_panels(d, k, xd, lx, yd, ly))) return rc;
     return stg.finish();
 }
 

@@ -194,6 +194,7 @@ enum { STAGE_X, STAGE_Y, STAGE_SPMM_X, STAGE_SPMM_Y, STAGE_SDDMM_U, STAGE_SDDMM_
        STAGE_ATTB_O, STAGE_ATTB_L, // the final O and L spmv_hip_attention_gqa_backward_lse reads
        STAGE_MRG_O1, STAGE_MRG_L1, STAGE_MRG_O2, STAGE_MRG_L2, STAGE_MRG_O, STAGE_MRG_L, // spmv_hip_attention_merge's operands
        STAGE_CG_B, STAGE_CG_X, STAGE_CG_DINV, // spmv_hip_cg's and spmv_hip_bicgstab's right-hand side, solution and diagonal preconditioner
+       STAGE_CGC_B, STAGE_CGC_X,              // spmv_hip_cg_columns' m x k right-hand sides and solutions (its Dinv is one vector: STAGE_CG_DINV)
        STAGE_COUNT };
 
 struct spmv_dev {
@@ -304,6 +305,11 @@ struct spmv_dev {
     // own, allocated at the first BiCGStab solve; its history likewise in a block of its own
     void *bicg_ws = nullptr;
     StageBuf bicg_hist;
+    // spmv_hip_cg_columns (shim/solve.hpp): r, p, q (m x cgc_k elements each, compact), 4 cgc_k partial arrays and the per-column state in ONE
+    // block of the solver's own, allocated at the first call and allocated anew when a later call has more columns; its history likewise
+    void *cgc_ws = nullptr;
+    int cgc_k = 0;
+    StageBuf cgc_hist;
     // spmv_hip_spmv_transpose (shim/transpose.hpp): A^T as a matrix of its own (n x m), planned and built like any; perm[p] = our index of its entry p.
     // val_gen counts spmv_shim_update_values calls; A^T's values are gathered again when tr_gen falls behind it.
     spmv_dev *tr = nullptr;

@@ -1465,3 +1465,39 @@ double spmv_hip_time_bicgstab_iterations(spmv_Handle_t h, const void *B, void *X
 {
     return solve_time(h, "time_bicgstab_iterations", SPMV_SHIM_SOLVE_BICGSTAB, B, X, opt, warmup, iters, ms_out);
 }
+
+/* ---------------------------------------------------------------- conjugate gradients for k right-hand sides in one pass over A per iteration */
+/* cg_args' rules and the columns' own; the timer with m = 1 */
+static int cg_columns_args(spmv_Handle_t h, const char *where, int k, const void *B, long long ldb, const void *X, long long ldx, const spmv_hip_cg_options *opt, const void *res,
+                           int m)
+{
+    const int rc = cg_args(h, where, B, X, opt, res, m);
+    if (rc) return rc;
+    if (k < 1 || k > SPMV_HIP_CG_COLUMNS_MAX || ldb < k || ldx < k) return refuse(SPMV_HIP_E_ARG, where, "need 1 <= k <= SPMV_HIP_CG_COLUMNS_MAX, ldb >= k and ldx >= k");
+    return SPMV_HIP_OK;
+}
+
+int spmv_hip_cg_columns(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx, const void *Matrix_Val, int k, const void *B,
+                        long long ldb, void *X, long long ldx, const spmv_hip_cg_options *opt, spmv_hip_cg_result *res)
+{
+    const char *where = "cg_columns";
+    spmv_hip_state *st;
+    int rc;
+    if ((rc = cg_columns_args(handle, where, k, B, ldb, X, ldx, opt, res, m)) || (rc = resident_prologue(handle, where, 0, m, RowPtr, ColIdx, Matrix_Val, &st))) return rc;
+    if (st->m != st->n) return refuse(SPMV_HIP_E_ARG, where, "the matrix is not square (m != n at create)");
+    if (k == 1 && ldb == 1 && ldx == 1) return report(spmv_shim_solve(SPMV_SHIM_SOLVE_CG, st->dev, B, X, opt, res), where); /* one vector: spmv_hip_cg, its workspace and bits */
+    if ((rc = spmm_columns(handle, st, where))) return rc;
+    return report(spmv_shim_solve_columns(st->dev, k, B, ldb, X, ldx, opt, res), where);
+}
+
+double spmv_hip_time_cg_columns_iterations(spmv_Handle_t h, int k, const void *B, long long ldb, void *X, long long ldx, const spmv_hip_cg_options *opt, int warmup, int iters,
+                                           float *ms_out)
+{
+    const char *where = "time_cg_columns_iterations";
+    spmv_hip_state *st;
+    if (cg_columns_args(h, where, k, B, ldb, X, ldx, opt, opt, 1) || resident_state(h, where, 0, &st)) return -1.0;
+    if (st->m != st->n) { (void) refuse(SPMV_HIP_E_ARG, where, "the matrix is not square (m != n at create)"); return -1.0; }
+    if (k == 1 && ldb == 1 && ldx == 1) return report_time(spmv_shim_time_solve(SPMV_SHIM_SOLVE_CG, st->dev, B, X, opt, warmup, iters, ms_out), where);
+    if (spmm_columns(h, st, where)) return -1.0;
+    return report_time(spmv_shim_time_solve_columns(st->dev, k, B, ldb, X, ldx, opt, warmup, iters, ms_out), where);
+}

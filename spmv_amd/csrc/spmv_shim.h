@@ -209,10 +209,17 @@ double spmv_shim_time_attention_backward(spmv_dev *d, const spmv_attention_backw
  * right-preconditioned BiCGStab (spmv_hip_bicgstab; the matrix need not be symmetric) ----
  * B, X, opt->Dinv: m elements, host or device pointers each.  The multiply is the built schedule's own launch.  Each solver builds a workspace of its
  * own at its first call.  SPMV_HIP_OK whenever the solve ran (res->status says how it ended); synchronous */
-enum { SPMV_SHIM_SOLVE_CG, SPMV_SHIM_SOLVE_BICGSTAB };
+enum { SPMV_SHIM_SOLVE_CG, SPMV_SHIM_SOLVE_BICGSTAB, SPMV_SHIM_SOLVE_CG_COLUMNS /* spmv_shim_solve_columns alone */ };
 int spmv_shim_solve(int solver, spmv_dev *d, const void *b, void *x, const spmv_hip_cg_options *opt, spmv_hip_cg_result *res);
 /* `iters` runs of opt->max_iterations iterations each, the stop tests off, timed with events on the handle's stream (device B / X / Dinv); mean ms per run, < 0 on failure */
 double spmv_shim_time_solve(int solver, spmv_dev *d, const void *b, void *x, const spmv_hip_cg_options *opt, int warmup, int iters, float *ms_out);
+/* conjugate gradients for k independent right-hand sides (spmv_hip_cg_columns), 1 <= k <= SPMV_HIP_CG_COLUMNS_MAX: B and X m x k, row-major, leading
+ * dimensions ldb, ldx >= k, host or device pointers; opt->Dinv one vector of m elements; res k entries; opt->history (max_iterations + 1) * k doubles.
+ * The multiply is spmv_shim_spmm's executor on the solver's own compact workspace vectors, one pass over A per iteration: the resident ColIdx
+ * is needed (spmv_shim_restore_columns).  The same loop, workspace rules and return value as spmv_shim_solve */
+int spmv_shim_solve_columns(spmv_dev *d, int k, const void *b, long long ldb, void *x, long long ldx, const spmv_hip_cg_options *opt, spmv_hip_cg_result *res);
+double spmv_shim_time_solve_columns(spmv_dev *d, int k, const void *b, long long ldb, void *x, long long ldx, const spmv_hip_cg_options *opt, int warmup, int iters,
+                                    float *ms_out);
 
 /* the resident CSR arrays (device pointers; ColIdx may be NULL after spmv_shim_release_columns) */
 void spmv_shim_matrix_arrays(const spmv_dev *d, const int **rowptr, const int **colidx, const void **val);

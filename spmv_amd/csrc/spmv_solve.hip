@@ -1,12 +1,14 @@
-// spmv_solve.hip -- translation unit of the vector kernels of the device-resident solvers (kernels/cg.hpp, kernels/bicgstab.hpp, what they
-// share in kernels/solve_common.hpp).  Launches only: the workspace, staging, the multiplies, the host's looks at the state and the error channel
-// stay in spmv_shim.hip (shim/solve.hpp).  Per solve it calls cg_start_launch or bicg_start_launch once; per iteration cg_iteration_launch
-// behind q = A p, or bicg_first_launch behind v = A ph and bicg_second_launch behind t = A sh.
+// spmv_solve.hip -- translation unit of the vector kernels of the device-resident solvers (kernels/cg.hpp, kernels/bicgstab.hpp,
+// kernels/cg_columns.hpp, what they share in kernels/solve_common.hpp).  Launches only: the workspace, staging, the multiplies, the host's
+// looks at the state and the error channel stay in spmv_shim.hip (shim/solve.hpp).  Per solve it calls cg_start_launch or bicg_start_launch
+// once; per iteration cg_iteration_launch behind q = A p, or bicg_first_launch behind v = A ph and bicg_second_launch behind t = A sh;
+// spmv_hip_cg_columns: ccg_start_launch, and ccg_iteration_launch behind q = A p for all k columns.
 #include <hip/hip_runtime.h>
 
 #include "kernels/common.hpp"
 #include "kernels/cg.hpp"
 #include "kernels/bicgstab.hpp"
+#include "kernels/cg_columns.hpp"
 
 namespace spmv {
 
@@ -86,6 +88,34 @@ static bool args_ok(const SolveArgs &a) { return a.m > 0 && a.parts >= 1 && a.pa
         return hipGetLastError();                                                                                            \
     } while (0)
 
+template <typename T, bool WIDE, bool DINV>
+static void ccg_start_t(const SolveArgs &a, bool use_x0, hipStream_t stream)
+{
+    const T *b = (const T *) a.b, *q = (const T *) a.vec[kCcgVecQ], *dinv = (const T *) a.dinv;
+    T *r = (T *) a.vec[kCcgVecR], *p = (T *) a.vec[kCcgVecP];
+    if (use_x0) ccg_init_kernel<T, WIDE, DINV, true><<<(unsigned) a.parts, kBlock, 0, stream>>>(a.m, a.span, a.k, b, a.ldb, (T *) a.x, a.ldx, q, dinv, r, p, a.part);
+    else ccg_init_kernel<T, WIDE, DINV, false><<<(unsigned) a.parts, kBlock, 0, stream>>>(a.m, a.span, a.k, b, a.ldb, (T *) a.x, a.ldx, q, dinv, r, p, a.part);
+    if (a.hist) ccg_begin_kernel<true><<<(unsigned) a.k, kBlock, 0, stream>>>(a.part, a.k, a.cols, a.hist, a.rtol2, a.atol2, a.nostop);
+    else ccg_begin_kernel<false><<<(unsigned) a.k, kBlock, 0, stream>>>(a.part, a.k, a.cols, a.hist, a.rtol2, a.atol2, a.nostop);
+}
+
+template <typename T, bool WIDE, bool DINV>
+static void ccg_iteration_t(const SolveArgs &a, int it, hipStream_t stream)
+{
+    const unsigned grid = (unsigned) a.parts, cols = (unsigned) a.k;
+    const T *dinv = (const T *) a.dinv;
+    T *r = (T *) a.vec[kCcgVecR], *p = (T *) a.vec[kCcgVecP], *q = (T *) a.vec[kCcgVecQ];
+    ccg_dot_kernel<T><<<grid, kBlock, 0, stream>>>(a.m, a.span, a.k, p, q, a.part, a.cols);
+    ccg_alpha_kernel<T><<<cols, kBlock, 0, stream>>>(a.part, a.k, it, a.cols, a.nostop);
+    ccg_update_kernel<T, WIDE, DINV><<<grid, kBlock, 0, stream>>>(a.m, a.span, a.k, p, q, (T *) a.x, a.ldx, r, dinv, a.part, a.cols);
+    ccg_beta_kernel<T><<<cols, kBlock, 0, stream>>>(a.part, a.k, it, a.cols, a.hist, a.rtol2, a.atol2, a.nostop);
+    ccg_direction_kernel<T, DINV><<<grid, kBlock, 0, stream>>>(a.m, a.span, a.k, r, dinv, p, a.cols);
+}
+
+static bool cols_ok(const SolveArgs &a) { return a.k >= 1 && a.k <= kCcgMaxK && a.ldb >= a.k && a.ldx >= a.k && a.cols != nullptr && (!a.wide || (a.ldb == a.k && a.ldx == a.k)); }
+
+hipError_t ccg_start_launch(const SolveArgs &a, bool use_x0, hipStream_t stream) { SOLVE_LAUNCH(ccg_start_t, cols_ok(a), a, use_x0, stream); }
+hipError_t ccg_iteration_launch(const SolveArgs &a, int it, hipStream_t stream) { SOLVE_LAUNCH(ccg_iteration_t, cols_ok(a) && it >= 1, a, it, stream); }
 hipError_t cg_start_launch(const SolveArgs &a, bool use_x0, hipStream_t stream) { SOLVE_LAUNCH(cg_start_t, true, a, use_x0, stream); }
 hipError_t cg_iteration_launch(const SolveArgs &a, int k, hipStream_t stream) { SOLVE_LAUNCH(cg_iteration_t, k >= 1, a, k, stream); }
 hipError_t bicg_start_launch(const SolveArgs &a, bool use_x0, hipStream_t stream) { SOLVE_LAUNCH(bicg_start_t, true, a, use_x0, stream); }
