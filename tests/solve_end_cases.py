@@ -1,4 +1,5 @@
-"""A catalogue of the ways spmv_hip_cg and spmv_hip_bicgstab can end (tests/test_solve_ends_host.py, tests/test_gpu_solve_ends.py).
+"""A catalogue of the ways spmv_hip_cg and spmv_hip_bicgstab can end (tests/test_solve_ends_host.py, tests/test_gpu_solve_ends.py), and its CG
+cases as the columns of one spmv_hip_cg_columns call (columns_system; tests/test_cg_column_ends_host.py, tests/test_gpu_cg_column_ends.py).
 
 A case is a 2 x 2 block, a right-hand side of two elements and, optionally, a Dinv of two: `system` repeats them `reps` times along the
 diagonal, so every row, every workgroup and every size runs the same small recurrence and the loop ends where the block's own ends.  The
@@ -266,6 +267,97 @@ def mixed(cases, reps, dtype, tail):
             x0[own] = np.tile(cx, reps)
         return b, None if cd is None else dinv, None if cx is None else x0
     return whole, select
+
+
+# ----------------------------------------------------------------------------- the CG catalogue as the columns of one call
+# spmv_hip_cg_columns (tests/test_cg_column_ends_host.py, tests/test_gpu_cg_column_ends.py): every CG case of a type is one column of a call
+# on `mixed`, and behind them one ordinary column on the tridiagonal tail that is still running at BUDGET, so that every case ends -- and is
+# frozen -- in company that runs on.  One call has one Dinv, so the cases are grouped by whether they carry one.
+GROUPS = ("plain", "plain_nox0", "pre")
+BIG_GROUP = ("c_rr_2", "c_pq_1x", "c_begin_zero")        # the group of the run at BIG: three ends at three iteration counts, one of them B = 0
+
+
+def column_groups(dtype):
+    """-> {"plain": the CG cases of `dtype` without a Dinv (they run with Dinv = NULL or all ones), "plain_nox0": those of them without a guess,
+    "pre": the cases with a Dinv (they share one)}, in the catalogue's order"""
+    mine = [c for c in CASES if c.solver == "cg" and dtype in c.dtypes]
+    plain = [c for c in mine if c.dinv is None]
+    return {"plain": plain, "plain_nox0": [c for c in plain if c.x0 is None], "pre": [c for c in mine if c.dinv is not None]}
+
+
+def columns_shape(n, m):
+    """-> (reps, tail) of `mixed` for n cases at the size m of SIZES or BIG; the smallest size is one copy of every block and four tail rows"""
+    if m == SIZES[0]:
+        return 1, 4
+    reps = (m - 4) // (2 * n)
+    return reps, m - 2 * n * reps
+
+
+def columns_system(group, m, dtype):
+    """group: a name of GROUPS or a list of CG cases.  -> (CSR, B, X0 or None, Dinv or None, cases): `mixed` over the cases with column j of B
+    (and of X0) case j's right-hand side (guess) and, last, the ordinary column select(None, 1) on the tail.  X0: None when no case has a
+    guess, zero in the columns of the cases without one.  Dinv: None when no case has one; every case's own on its own blocks -- the blocks
+    do not touch, so no column's recurrence sees another's entries -- and 1 everywhere else."""
+    cases = column_groups(dtype)[group] if isinstance(group, str) else list(group)
+    n = len(cases)
+    assert 1 <= n <= 15 and all(c.solver == "cg" and dtype in c.dtypes for c in cases)
+    reps, tail = columns_shape(n, m)
+    csr, select = mixed(cases, reps, dtype, tail)
+    return (csr,) + columns_batch(csr, select, range(n), dtype) + (cases,)
+
+
+def columns_batch(csr, select, picked, dtype):
+    """-> (B, X0 or None, Dinv or None) of columns_system for the cases `picked` (indices into the cases `mixed` was built over) and the tail"""
+    picks = [select(j) for j in picked]
+    zero = np.zeros(csr.m, dtype=dtype)
+    B = np.stack([p[0] for p in picks] + [select(None, 1)[0]], axis=1)
+    X0 = None
+    if any(p[2] is not None for p in picks):
+        X0 = np.ascontiguousarray(np.stack([zero if p[2] is None else p[2] for p in picks] + [zero], axis=1))
+    Dinv = None
+    if any(p[1] is not None for p in picks):
+        Dinv = np.ones(csr.m, dtype=dtype)
+        for p in picks:
+            if p[1] is not None:
+                own = p[1] != 1
+                assert (Dinv[own] == 1).all()                  # nobody else's rows
+                Dinv[own] = p[1][own]
+    return np.ascontiguousarray(B), X0, Dinv
+
+
+def columns_state_system(dtype, m=1026):
+    """the matrix of the test of state between calls: `mixed` over ALL CG cases of the type (more than one call holds), so that one handle runs
+    the `plain` group, the `pre` group and ordinary columns on the tail.  -> (CSR, {group: (B, X0, Dinv, cases)}, tail_columns(k, seed) -> m x k
+    generic right-hand sides on the tail rows, zero on the blocks)"""
+    groups = column_groups(dtype)
+    every = groups["plain"] + groups["pre"]
+    reps, tail = columns_shape(len(every), m)
+    csr, select = mixed(every, reps, dtype, tail)
+    out = {g: columns_batch(csr, select, [every.index(c) for c in groups[g]], dtype) + (groups[g],) for g in ("plain", "pre")}
+
+    def tail_columns(k, seed):
+        return np.ascontiguousarray(np.stack([select(None, 1000 * seed + j)[0] for j in range(k)], axis=1))
+    return csr, out, tail_columns
+
+
+def column_runs(group, B, X0):
+    """the (X0 or None, Dinv-is-all-ones) combinations a group is run with: `plain` with its guesses, also under an all-ones Dinv; `plain_nox0`
+    from x = 0; `pre` from x = 0 and from all-zero guesses.  -> [(name, X0 of the call or None, ones: bool)]"""
+    if group == "plain":
+        return [("x0", X0, False), ("x0-ones", X0, True)]
+    if group == "plain_nox0":
+        return [("nox0", None, False)]
+    return [("nox0", None, False), ("x0", np.zeros_like(B), False)]
+
+
+def declared_columns(cases, budget=BUDGET):
+    """-> what every column of columns_system reports under `budget`: (status, iterations, end) per case and the tail's (MAX_ITERATIONS, budget,
+    "budget").  An end that ccg_alpha finds (first_kernel) is found while starting iteration `iterations` + 1: not with a budget of `iterations`"""
+    out = []
+    for c in cases:
+        short = budget < c.iterations or (budget == c.iterations and first_kernel(c))
+        out.append((M, budget, "budget") if short else (c.status, c.iterations, c.end))
+    return out + [(M, budget, "budget")]
 
 
 def state_cases(solver, dtype):
