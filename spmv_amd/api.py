@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import ctypes as C
 import enum
+import math
 import os
 
 import numpy as np
@@ -84,21 +85,41 @@ class spmv_hip_cg_result(C.Structure):  # include/spmv_hip.h
 
 CG_STATUS = ("converged", "max_iterations", "breakdown", "nonfinite")  # SPMV_HIP_CG_*
 
-# The fragments the attention prototypes of include/spmv_hip.h and spmv_hip_tools.h are made of
-_CSR = [spmv_Handle_t, C.c_int, _V, _V, _V]          # handle, m, RowPtr, ColIdx, Matrix_Val: a call
+# The fused attention's entry points (include/spmv_hip.h, spmv_hip_tools.h), a row each: the stem, then the size arguments and the operands in
+# the prototype's order.  A size is an int -- scale a double --, an operand a void * followed by its leading dimension or plane stride, a
+# long long; a *_type is a SPMV_HIP_T_* code, an int.  Both the prototypes in FUNCTIONS (the call's and its timer's) and the arguments that
+# are passed (_attention_args, which looks every name up in a record) come from the row: a new rung is a new row, and nothing else lists
+# C arguments.
+_GQA = "heads kv_heads k dv scale"
+_ATTENTION = {stem: tuple((sizes + " " + operands).split()) for stem, sizes, operands in (
+    ("attention", "k dv scale", "Q K V O"),
+    ("attention_heads", "heads k dv scale", "Q K V O"),
+    ("attention_backward", "k dv scale", "Q K V G dQ dK dV"),
+    ("attention_heads_backward", "heads k dv scale", "Q K V G dQ dK dV"),
+    ("attention_bias", "heads k dv scale", "Q K V B O"),
+    ("attention_bias_backward", "heads k dv scale", "Q K V B G dQ dK dV dB"),
+    ("attention_gqa", _GQA, "Q K V B O"),
+    ("attention_gqa_backward", _GQA, "Q K V B G dQ dK dV dB"),
+    ("attention_gqa_lse", _GQA, "Q K V B O L"),
+    ("attention_gqa_lse_16", _GQA + " io_type", "Q K V B O o_type L"),
+    ("attention_gqa_backward_lse", _GQA, "Q K V B G O L dQ dK dV dB"),
+    ("attention_gqa_backward_16", _GQA + " io_type", "Q K V B G O L dq_type dQ dkv_type dK dV dB"),
+)}
+_CSR = [spmv_Handle_t, C.c_int, _V, _V, _V]          # handle, m, RowPtr, ColIdx, Matrix_Val: what a call begins with
 _TIMED = [spmv_Handle_t]                               # ... a timer takes the handle alone
 _TAIL = [C.c_int, C.c_int, C.POINTER(C.c_float)]       # ... and ends with warmup, iters, ms_out
-_ONE = [C.c_int, C.c_int, C.c_double]                  # k, dv, scale
-_HEADS = [C.c_int] + _ONE                              # heads, k, dv, scale
-_GQA = [C.c_int] + _HEADS                              # heads, kv_heads, k, dv, scale
-_TYPE = [C.c_int]                                      # a SPMV_HIP_T_* code: io_type, o_type, dq_type, dkv_type where the prototype has them
-_Q = _K = _VV = _B = _O = _L = _G = _DQ = _DK = _DV = _DB = [_V, C.c_longlong]   # an operand and its leading dimension or plane stride
-_QKV = _Q + _K + _VV
 
 
-def _attention(stem, sizes, operands):
-    """-> the FUNCTIONS entries of the call spmv_hip_<stem> and of its timer spmv_hip_time_<stem>_launches"""
-    return {f"spmv_hip_{stem}": (C.c_int, _CSR + sizes + operands), f"spmv_hip_time_{stem}_launches": (C.c_double, _TIMED + sizes + operands + _TAIL)}
+def _attention_prototypes():
+    """-> the FUNCTIONS entries of every row's call spmv_hip_<stem> and timer spmv_hip_time_<stem>_launches"""
+    out = {}
+    for stem, row in _ATTENTION.items():
+        args = []
+        for name in row:
+            args += [C.c_double] if name == "scale" else [C.c_int] if name.islower() else [_V, C.c_longlong]   # only an operand has a capital
+        out[f"spmv_hip_{stem}"] = (C.c_int, _CSR + args)
+        out[f"spmv_hip_time_{stem}_launches"] = (C.c_double, _TIMED + args + _TAIL)
+    return out
 
 
 # Every symbol include/*.h declares: functions with their prototypes, then data symbols.
@@ -150,23 +171,11 @@ FUNCTIONS = {
     "spmv_hip_row_softmax": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, _V, _V]),
     "spmv_hip_row_softmax_backward": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, _V, _V, _V]),
     "spmv_hip_time_row_softmax_launches": (C.c_double, [spmv_Handle_t, _V, _V, C.c_int, C.c_int, C.POINTER(C.c_float)]),
-    # the fused attention: a call and its timer per line, the operands in the prototype's order (a name: the operand and its ld)
-    **_attention("attention", _ONE, _QKV + _O),
-    **_attention("attention_heads", _HEADS, _QKV + _O),
-    **_attention("attention_backward", _ONE, _QKV + _G + _DQ + _DK + _DV),
-    **_attention("attention_heads_backward", _HEADS, _QKV + _G + _DQ + _DK + _DV),
-    **_attention("attention_bias", _HEADS, _QKV + _B + _O),
-    **_attention("attention_bias_backward", _HEADS, _QKV + _B + _G + _DQ + _DK + _DV + _DB),
-    **_attention("attention_gqa", _GQA, _QKV + _B + _O),
-    **_attention("attention_gqa_backward", _GQA, _QKV + _B + _G + _DQ + _DK + _DV + _DB),
-    **_attention("attention_gqa_lse", _GQA, _QKV + _B + _O + _L),
-    **_attention("attention_gqa_lse_16", _GQA + _TYPE, _QKV + _B + _O + _TYPE + _L),
+    **_attention_prototypes(),   # the fused attention: a call and its timer per row of _ATTENTION
     "spmv_hip_attention_merge": (C.c_int, [spmv_Handle_t, C.c_int, C.c_int, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong,
                                            _V, C.c_longlong, _V, C.c_longlong]),
     "spmv_hip_time_attention_merge_launches": (C.c_double, [spmv_Handle_t, C.c_int, C.c_int, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong, _V, C.c_longlong,
                                                             _V, C.c_longlong, _V, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_float)]),
-    **_attention("attention_gqa_backward_lse", _GQA, _QKV + _B + _G + _O + _L + _DQ + _DK + _DV + _DB),
-    **_attention("attention_gqa_backward_16", _GQA + _TYPE, _QKV + _B + _G + _O + _L + _TYPE + _DQ + _TYPE + _DK + _DV + _DB),
     "spmv_hip_cg": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, _V, _V, C.POINTER(spmv_hip_cg_options), C.POINTER(spmv_hip_cg_result)]),
     "spmv_hip_time_cg_iterations": (C.c_double, [spmv_Handle_t, _V, _V, C.POINTER(spmv_hip_cg_options), C.c_int, C.c_int, C.POINTER(C.c_float)]),
     "spmv_hip_bicgstab": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, _V, _V, C.POINTER(spmv_hip_cg_options), C.POINTER(spmv_hip_cg_result)]),
@@ -479,122 +488,6 @@ def time_row_softmax_launches(handle, S, Out, warmup=10, iters=100):
     return _timed("spmv_hip_time_row_softmax_launches", (handle, _ptr(S), _ptr(Out)), warmup, iters)
 
 
-def _attention_blocks(Q, K, V, O):
-    """-> (k, dv, pq, ldq, pk, ldk, pv, ldv, po, ldo) of the four 2-D blocks of an attention call (_blocks: Q and K share k, V and O share dv)"""
-    k, pq, ldq, pk, ldk = _blocks(Q, "Q", K, "K")
-    dv, pv, ldv, po, ldo = _blocks(V, "V", O, "O")
-    return k, dv, pq, ldq, pk, ldk, pv, ldv, po, ldo
-
-
-def attention(handle, m, RowPtr, ColIdx, Matrix_Val, Q, K, V, O, scale=None, check=True):
-    """O = softmax_rows(scale * Q K^T on the handle's pattern) V in one pass (spmv_hip_attention).  Q (m x k), K (n x k), V (n x dv) and O
-    (m x dv): 2-D numpy arrays or torch tensors with column stride 1 (row strides are passed as leading dimensions); scale None means
-    1 / sqrt(k).  The handle's values are neither read nor changed.  -> the return code."""
-    k, dv, pq, ldq, pk, ldk, pv, ldv, po, ldo = _attention_blocks(Q, K, V, O)
-    scale = 1.0 / np.sqrt(k) if scale is None and k > 0 else (0.0 if scale is None else scale)
-    return _checked(load().spmv_hip_attention(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), k, dv, float(scale), pq, ldq, pk, ldk, pv, ldv, po, ldo),
-                    "spmv_hip_attention", check)
-
-
-def time_attention_launches(handle, Q, K, V, O, scale=None, warmup=10, iters=100):
-    """-> (mean_ms, per-call ms array) of spmv_hip_attention on device Q / K / V / O (spmv_hip_time_attention_launches)."""
-    k, dv, pq, ldq, pk, ldk, pv, ldv, po, ldo = _attention_blocks(Q, K, V, O)
-    scale = 1.0 / np.sqrt(k) if scale is None else scale
-    return _timed("spmv_hip_time_attention_launches", (handle, k, dv, float(scale), pq, ldq, pk, ldk, pv, ldv, po, ldo), warmup, iters)
-
-
-def _attention_heads_blocks(heads, Q, K, V, O):
-    """-> _attention_blocks with k and dv as ONE head's widths: the column counts of Q / K and of V / O divided by `heads`"""
-    heads = int(heads)
-    wk, wv, *rest = _attention_blocks(Q, K, V, O)
-    if heads < 1 or wk % heads or wv % heads:
-        raise ValueError(f"Q / K have {wk} columns and V / O {wv}: not {heads} heads of equal width")
-    return (wk // heads, wv // heads, *rest)
-
-
-def attention_heads(handle, m, RowPtr, ColIdx, Matrix_Val, heads, Q, K, V, O, scale=None, check=True):
-    """`heads` attention heads over the handle's pattern in one pass (spmv_hip_attention_heads).  Q (m x heads*k), K (n x heads*k),
-    V (n x heads*dv) and O (m x heads*dv) hold the heads side by side -- the (rows, heads, k) layout --: 2-D numpy arrays or torch tensors with
-    column stride 1 (row strides are passed as leading dimensions); head h of O has the bits of attention() on the h-th column slices.  scale
-    None means 1 / sqrt(k) with k ONE head's width.  The handle's values are neither read nor changed.  -> the return code."""
-    k, dv, pq, ldq, pk, ldk, pv, ldv, po, ldo = _attention_heads_blocks(heads, Q, K, V, O)
-    scale = 1.0 / np.sqrt(k) if scale is None and k > 0 else (0.0 if scale is None else scale)
-    return _checked(load().spmv_hip_attention_heads(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), int(heads), k, dv, float(scale),
-                                                    pq, ldq, pk, ldk, pv, ldv, po, ldo), "spmv_hip_attention_heads", check)
-
-
-def time_attention_heads_launches(handle, heads, Q, K, V, O, scale=None, warmup=10, iters=100):
-    """-> (mean_ms, per-call ms array) of spmv_hip_attention_heads on device Q / K / V / O (spmv_hip_time_attention_heads_launches)."""
-    k, dv, pq, ldq, pk, ldk, pv, ldv, po, ldo = _attention_heads_blocks(heads, Q, K, V, O)
-    scale = 1.0 / np.sqrt(k) if scale is None else scale
-    return _timed("spmv_hip_time_attention_heads_launches", (handle, int(heads), k, dv, float(scale), pq, ldq, pk, ldk, pv, ldv, po, ldo), warmup, iters)
-
-
-def _attention_backward_blocks(Q, K, V, G, dQ, dK, dV):
-    """-> (k, dv, then address and ld of Q, K, V, G, dQ, dK, dV) of an attention_backward call; an output that is None has a NULL address and its
-    width as ld.  Q, K, dQ and dK share k; V, G and dV share dv."""
-    k, pq, ldq, pk, ldk = _blocks(Q, "Q", K, "K")
-    dv, pv, ldv, pg, ldg = _blocks(V, "V", G, "G")
-    out = [k, dv, pq, ldq, pk, ldk, pv, ldv, pg, ldg]
-    for a, name, width in ((dQ, "dQ", k), (dK, "dK", k), (dV, "dV", dv)):
-        if a is None:
-            out += [None, int(width)]
-            continue
-        p, _, w, ld = _block(a, name)
-        if w != width:
-            raise ValueError(f"{name} has {w} columns, expected {width}")
-        out += [p, int(max(ld, 1))]
-    return out
-
-
-def attention_backward(handle, m, RowPtr, ColIdx, Matrix_Val, Q, K, V, G, dQ=None, dK=None, dV=None, scale=None, check=True):
-    """dQ, dK, dV of O = softmax_rows(scale * Q K^T on the handle's pattern) V from G = dL/dO in two passes over A
-    (spmv_hip_attention_backward).  Q (m x k), K (n x k), V (n x dv), G (m x dv) and the outputs dQ (m x k), dK (n x k), dV (n x dv): 2-D numpy
-    arrays or torch tensors with column stride 1 (row strides are passed as leading dimensions); an output that is None is not computed; scale
-    None means 1 / sqrt(k).  The handle's values are neither read nor changed.  -> the return code."""
-    b = _attention_backward_blocks(Q, K, V, G, dQ, dK, dV)
-    k = b[0]
-    scale = 1.0 / np.sqrt(k) if scale is None and k > 0 else (0.0 if scale is None else scale)
-    return _checked(load().spmv_hip_attention_backward(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), b[0], b[1], float(scale), *b[2:]),
-                    "spmv_hip_attention_backward", check)
-
-
-def time_attention_backward_launches(handle, Q, K, V, G, dQ=None, dK=None, dV=None, scale=None, warmup=10, iters=100):
-    """-> (mean_ms, per-call ms array) of spmv_hip_attention_backward on device operands (spmv_hip_time_attention_backward_launches)."""
-    b = _attention_backward_blocks(Q, K, V, G, dQ, dK, dV)
-    scale = 1.0 / np.sqrt(b[0]) if scale is None else scale
-    return _timed("spmv_hip_time_attention_backward_launches", (handle, b[0], b[1], float(scale), *b[2:]), warmup, iters)
-
-
-def _attention_heads_backward_blocks(heads, Q, K, V, G, dQ, dK, dV):
-    """-> _attention_backward_blocks with k and dv as ONE head's widths: the column counts of Q / K and of V / G divided by `heads`"""
-    heads = int(heads)
-    wk, wv, *rest = _attention_backward_blocks(Q, K, V, G, dQ, dK, dV)
-    if heads < 1 or wk % heads or wv % heads:
-        raise ValueError(f"Q / K have {wk} columns and V / G {wv}: not {heads} heads of equal width")
-    return [wk // heads, wv // heads, *rest]
-
-
-def attention_heads_backward(handle, m, RowPtr, ColIdx, Matrix_Val, heads, Q, K, V, G, dQ=None, dK=None, dV=None, scale=None, check=True):
-    """dQ, dK, dV of attention_heads(Q, K, V) from G = dL/dO, all heads in two passes per group of heads (spmv_hip_attention_heads_backward).
-    Q, dQ (m x heads*k), K, dK (n x heads*k), V, dV (n x heads*dv) and G (m x heads*dv) hold the heads side by side: 2-D numpy arrays or torch
-    tensors with column stride 1 (row strides are passed as leading dimensions); an output that is None is not computed; head h of every output
-    has the bits of attention_backward() on the h-th column slices.  scale None means 1 / sqrt(k) with k ONE head's width.  The handle's
-    values are neither read nor changed.  -> the return code."""
-    b = _attention_heads_backward_blocks(heads, Q, K, V, G, dQ, dK, dV)
-    k = b[0]
-    scale = 1.0 / np.sqrt(k) if scale is None and k > 0 else (0.0 if scale is None else scale)
-    return _checked(load().spmv_hip_attention_heads_backward(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), int(heads), b[0], b[1], float(scale), *b[2:]),
-                    "spmv_hip_attention_heads_backward", check)
-
-
-def time_attention_heads_backward_launches(handle, heads, Q, K, V, G, dQ=None, dK=None, dV=None, scale=None, warmup=10, iters=100):
-    """-> (mean_ms, per-call ms array) of spmv_hip_attention_heads_backward on device operands (spmv_hip_time_attention_heads_backward_launches)."""
-    b = _attention_heads_backward_blocks(heads, Q, K, V, G, dQ, dK, dV)
-    scale = 1.0 / np.sqrt(b[0]) if scale is None else scale
-    return _timed("spmv_hip_time_attention_heads_backward_launches", (handle, int(heads), b[0], b[1], float(scale), *b[2:]), warmup, iters)
-
-
 def _planes(a, name, heads, shared_ok):
     """-> (address, ld) of bias planes: None -> (None, 0); a 1-D array / tensor of nnz elements is ONE plane for all heads (ld 0, only where
     `shared_ok`); a 2-D one of (heads, nnz) with column stride 1 has a plane per head, its row stride as ld."""
@@ -611,134 +504,6 @@ def _planes(a, name, heads, shared_ok):
     return p, int(max(ld, w, 1))
 
 
-def attention_bias(handle, m, RowPtr, ColIdx, Matrix_Val, heads, Q, K, V, B, O, scale=None, check=True, ldb=None):
-    """attention_heads() with the additive bias B on the scaled scores (spmv_hip_attention_bias): t = (s * scale) + B.  B: None (then this IS
-    attention_heads), an (nnz,) array / tensor -- one plane shared by all heads -- or (heads, nnz) -- a plane per head, any row stride --, in
-    CSR order; ldb overrides the plane stride derived from B (for flat buffers holding padded planes).  -> the return code."""
-    k, dv, pq, ldq, pk, ldk, pv, ldv, po, ldo = _attention_heads_blocks(heads, Q, K, V, O)
-    scale = 1.0 / np.sqrt(k) if scale is None and k > 0 else (0.0 if scale is None else scale)
-    pb, ld = (_ptr(B), int(ldb)) if ldb is not None else _planes(B, "B", heads, True)
-    return _checked(load().spmv_hip_attention_bias(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), int(heads), k, dv, float(scale),
-                                                   pq, ldq, pk, ldk, pv, ldv, pb, ld, po, ldo), "spmv_hip_attention_bias", check)
-
-
-def time_attention_bias_launches(handle, heads, Q, K, V, B, O, scale=None, warmup=10, iters=100):
-    """-> (mean_ms, per-call ms array) of spmv_hip_attention_bias on device operands (spmv_hip_time_attention_bias_launches)."""
-    k, dv, pq, ldq, pk, ldk, pv, ldv, po, ldo = _attention_heads_blocks(heads, Q, K, V, O)
-    scale = 1.0 / np.sqrt(k) if scale is None else scale
-    pb, ld = _planes(B, "B", heads, True)
-    return _timed("spmv_hip_time_attention_bias_launches", (handle, int(heads), k, dv, float(scale), pq, ldq, pk, ldk, pv, ldv, pb, ld, po, ldo), warmup, iters)
-
-
-def _attention_bias_backward_args(heads, Q, K, V, B, G, dQ, dK, dV, dB, ldb, lddb):
-    b = _attention_heads_backward_blocks(heads, Q, K, V, G, dQ, dK, dV)
-    pb, ld = (_ptr(B), int(ldb)) if ldb is not None else _planes(B, "B", heads, True)
-    pdb, ldd = (_ptr(dB), int(lddb)) if lddb is not None else _planes(dB, "dB", heads, False)
-    # k, dv, Q, K, V | B | G, dQ, dK, dV | dB
-    return b[0], b[1], [*b[2:8], pb, ld, *b[8:], pdb, ldd]
-
-
-def attention_bias_backward(handle, m, RowPtr, ColIdx, Matrix_Val, heads, Q, K, V, B, G, dQ=None, dK=None, dV=None, dB=None, scale=None, check=True,
-                            ldb=None, lddb=None):
-    """dQ, dK, dV and dB of attention_bias(Q, K, V, B) from G = dL/dO (spmv_hip_attention_bias_backward).  B as in attention_bias(); dB: None
-    (not wanted) or (heads, nnz) -- always a plane per head, dB[h, p] = P (dP - D) of head h --; the other operands as in
-    attention_heads_backward(); ldb / lddb override the plane strides.  With B None, dQ, dK and dV are attention_heads_backward()'s to the
-    bit.  -> the return code."""
-    k, dv, rest = _attention_bias_backward_args(heads, Q, K, V, B, G, dQ, dK, dV, dB, ldb, lddb)
-    scale = 1.0 / np.sqrt(k) if scale is None and k > 0 else (0.0 if scale is None else scale)
-    return _checked(load().spmv_hip_attention_bias_backward(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), int(heads), k, dv, float(scale), *rest),
-                    "spmv_hip_attention_bias_backward", check)
-
-
-def time_attention_bias_backward_launches(handle, heads, Q, K, V, B, G, dQ=None, dK=None, dV=None, dB=None, scale=None, warmup=10, iters=100):
-    """-> (mean_ms, per-call ms array) of spmv_hip_attention_bias_backward on device operands (spmv_hip_time_attention_bias_backward_launches)."""
-    k, dv, rest = _attention_bias_backward_args(heads, Q, K, V, B, G, dQ, dK, dV, dB, None, None)
-    scale = 1.0 / np.sqrt(k) if scale is None else scale
-    return _timed("spmv_hip_time_attention_bias_backward_launches", (handle, int(heads), k, dv, float(scale), *rest), warmup, iters)
-
-
-def _gqa_widths(heads, kv_heads, wq, wkk, wv, wo, o_name):
-    """-> (k, dv) of ONE head from the column counts of Q, K, V and O / G: Q and O / G hold `heads` blocks, K and V `kv_heads`"""
-    heads, kv_heads = int(heads), int(kv_heads)
-    if heads < 1 or kv_heads < 1 or heads % kv_heads:
-        raise ValueError(f"heads = {heads} is not a multiple of kv_heads = {kv_heads}")
-    if wq % heads or wo % heads or wkk % kv_heads or wv % kv_heads or wq // heads != wkk // kv_heads or wo // heads != wv // kv_heads:
-        raise ValueError(f"Q has {wq} columns, K {wkk}, V {wv} and {o_name} {wo}: not {heads} query heads over {kv_heads} K / V heads of equal widths")
-    return wq // heads, wo // heads
-
-
-def _attention_gqa_blocks(heads, kv_heads, Q, K, V, O):
-    """-> (k, dv, pq, ldq, pk, ldk, pv, ldv, po, ldo) of an attention_gqa call: Q (heads*k) and K (kv_heads*k), V (kv_heads*dv) and O (heads*dv)"""
-    pq, _, wq, ldq = _block(Q, "Q")
-    pk, _, wkk, ldk = _block(K, "K")
-    pv, _, wv, ldv = _block(V, "V")
-    po, _, wo, ldo = _block(O, "O")
-    k, dv = _gqa_widths(heads, kv_heads, wq, wkk, wv, wo, "O")
-    return k, dv, pq, int(max(ldq, 1)), pk, int(max(ldk, 1)), pv, int(max(ldv, 1)), po, int(max(ldo, 1))
-
-
-def attention_gqa(handle, m, RowPtr, ColIdx, Matrix_Val, heads, kv_heads, Q, K, V, B, O, scale=None, check=True, ldb=None):
-    """attention_bias() with `kv_heads` K / V heads for `heads` query heads (spmv_hip_attention_gqa; grouped-query attention, kv_heads = 1:
-    multi-query).  Q (m x heads*k) and O (m x heads*dv) as there; K is (n x kv_heads*k) and V (n x kv_heads*dv); query head h uses K / V head
-    h // (heads // kv_heads), the grouping of repeat_interleave, and has the bits of the single-head call on those slices.  B: None, (nnz,) or
-    (heads, nnz) -- per QUERY head.  kv_heads = heads is attention_bias().  -> the return code."""
-    k, dv, pq, ldq, pk, ldk, pv, ldv, po, ldo = _attention_gqa_blocks(heads, kv_heads, Q, K, V, O)
-    scale = 1.0 / np.sqrt(k) if scale is None and k > 0 else (0.0 if scale is None else scale)
-    pb, ld = (_ptr(B), int(ldb)) if ldb is not None else _planes(B, "B", heads, True)
-    return _checked(load().spmv_hip_attention_gqa(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), int(heads), int(kv_heads), k, dv, float(scale),
-                                                  pq, ldq, pk, ldk, pv, ldv, pb, ld, po, ldo), "spmv_hip_attention_gqa", check)
-
-
-def time_attention_gqa_launches(handle, heads, kv_heads, Q, K, V, B, O, scale=None, warmup=10, iters=100):
-    """-> (mean_ms, per-call ms array) of spmv_hip_attention_gqa on device operands (spmv_hip_time_attention_gqa_launches)."""
-    k, dv, pq, ldq, pk, ldk, pv, ldv, po, ldo = _attention_gqa_blocks(heads, kv_heads, Q, K, V, O)
-    scale = 1.0 / np.sqrt(k) if scale is None else scale
-    pb, ld = _planes(B, "B", heads, True)
-    return _timed("spmv_hip_time_attention_gqa_launches", (handle, int(heads), int(kv_heads), k, dv, float(scale), pq, ldq, pk, ldk, pv, ldv, pb, ld, po, ldo),
-                  warmup, iters)
-
-
-def _attention_gqa_backward_args(heads, kv_heads, Q, K, V, B, G, dQ, dK, dV, dB, ldb, lddb):
-    """-> (k, dv, the C arguments from Q on) of an attention_gqa_backward call; an output that is None has a NULL address and its width as ld"""
-    pq, _, wq, ldq = _block(Q, "Q")
-    pk, _, wkk, ldk = _block(K, "K")
-    pv, _, wv, ldv = _block(V, "V")
-    pg, _, wg, ldg = _block(G, "G")
-    k, dv = _gqa_widths(heads, kv_heads, wq, wkk, wv, wg, "G")
-    args = [pq, int(max(ldq, 1)), pk, int(max(ldk, 1)), pv, int(max(ldv, 1))]
-    pb, ld = (_ptr(B), int(ldb)) if ldb is not None else _planes(B, "B", heads, True)
-    args += [pb, ld, pg, int(max(ldg, 1))]
-    for a, name, width in ((dQ, "dQ", wq), (dK, "dK", wkk), (dV, "dV", wv)):
-        if a is None:
-            args += [None, int(width)]
-            continue
-        p, _, w, ldo = _block(a, name)
-        if w != width:
-            raise ValueError(f"{name} has {w} columns, expected {width}")
-        args += [p, int(max(ldo, 1))]
-    pdb, ldd = (_ptr(dB), int(lddb)) if lddb is not None else _planes(dB, "dB", heads, False)
-    return k, dv, args + [pdb, ldd]
-
-
-def attention_gqa_backward(handle, m, RowPtr, ColIdx, Matrix_Val, heads, kv_heads, Q, K, V, B, G, dQ=None, dK=None, dV=None, dB=None, scale=None, check=True,
-                           ldb=None, lddb=None):
-    """dQ, dK, dV and dB of attention_gqa(Q, K, V, B) from G = dL/dO (spmv_hip_attention_gqa_backward).  Q, G, dQ hold `heads` blocks, K, V, dK, dV
-    `kv_heads`; dB: None or (heads, nnz).  dQ and dB of head h are the single-head backward's bits on its slices; dK / dV of a K / V head are the
-    sums of its query heads' single-head dK / dV, added in ascending head in the handle's precision, the first taken as it is.  kv_heads = heads
-    is attention_bias_backward().  -> the return code."""
-    k, dv, rest = _attention_gqa_backward_args(heads, kv_heads, Q, K, V, B, G, dQ, dK, dV, dB, ldb, lddb)
-    scale = 1.0 / np.sqrt(k) if scale is None and k > 0 else (0.0 if scale is None else scale)
-    return _checked(load().spmv_hip_attention_gqa_backward(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), int(heads), int(kv_heads), k, dv,
-                                                           float(scale), *rest), "spmv_hip_attention_gqa_backward", check)
-
-
-def time_attention_gqa_backward_launches(handle, heads, kv_heads, Q, K, V, B, G, dQ=None, dK=None, dV=None, dB=None, scale=None, warmup=10, iters=100):
-    """-> (mean_ms, per-call ms array) of spmv_hip_attention_gqa_backward on device operands (spmv_hip_time_attention_gqa_backward_launches)."""
-    k, dv, rest = _attention_gqa_backward_args(heads, kv_heads, Q, K, V, B, G, dQ, dK, dV, dB, None, None)
-    scale = 1.0 / np.sqrt(k) if scale is None else scale
-    return _timed("spmv_hip_time_attention_gqa_backward_launches", (handle, int(heads), int(kv_heads), k, dv, float(scale), *rest), warmup, iters)
-
-
 def _lse_planes(a, name, heads):
     """-> (address, ld) of log-sum-exp planes: None -> (None, 0); a 2-D array / tensor of (heads, >= m) with column stride 1, its row stride as ld
     (a 1-D one is the one plane of heads = 1)"""
@@ -752,44 +517,235 @@ def _lse_planes(a, name, heads):
     return p, int(max(ld, w, 1))
 
 
-def attention_gqa_lse(handle, m, RowPtr, ColIdx, Matrix_Val, heads, kv_heads, Q, K, V, B, O, L, scale=None, check=True, ldb=None, ldl=None):
-    """attention_gqa() that also writes the rows' log-sum-exps (spmv_hip_attention_gqa_lse): L is (heads, m) -- any row stride; ldl overrides it for
-    flat buffers holding padded planes --, L[h, i] = M_i + log Z_i of query head h, -inf on a row without entries.  O has attention_gqa()'s bits;
-    L None IS attention_gqa().  -> the return code."""
-    k, dv, pq, ldq, pk, ldk, pv, ldv, po, ldo = _attention_gqa_blocks(heads, kv_heads, Q, K, V, O)
-    scale = 1.0 / np.sqrt(k) if scale is None and k > 0 else (0.0 if scale is None else scale)
-    pb, ld = (_ptr(B), int(ldb)) if ldb is not None else _planes(B, "B", heads, True)
-    pl, ll = (_ptr(L), int(ldl)) if ldl is not None else _lse_planes(L, "L", heads)
-    return _checked(load().spmv_hip_attention_gqa_lse(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), int(heads), int(kv_heads), k, dv, float(scale),
-                                                      pq, ldq, pk, ldk, pv, ldv, pb, ld, po, ldo, pl, ll), "spmv_hip_attention_gqa_lse", check)
+def _gqa_widths(heads, kv_heads, wq, wkk, wv, wo, o_name):
+    """-> (k, dv) of ONE head from the column counts of Q, K, V and O / G: Q and O / G hold `heads` blocks, K and V `kv_heads`"""
+    if heads < 1 or kv_heads < 1 or heads % kv_heads:
+        raise ValueError(f"heads = {heads} is not a multiple of kv_heads = {kv_heads}")
+    if wq % heads or wo % heads or wkk % kv_heads or wv % kv_heads or wq // heads != wkk // kv_heads or wo // heads != wv // kv_heads:
+        raise ValueError(f"Q has {wq} columns, K {wkk}, V {wv} and {o_name} {wo}: not {heads} query heads over {kv_heads} K / V heads of equal widths")
+    return wq // heads, wo // heads
 
 
-def time_attention_gqa_lse_launches(handle, heads, kv_heads, Q, K, V, B, O, L, scale=None, warmup=10, iters=100):
-    """-> (mean_ms, per-call ms array) of spmv_hip_attention_gqa_lse on device operands (spmv_hip_time_attention_gqa_lse_launches)."""
-    k, dv, pq, ldq, pk, ldk, pv, ldv, po, ldo = _attention_gqa_blocks(heads, kv_heads, Q, K, V, O)
-    scale = 1.0 / np.sqrt(k) if scale is None else scale
-    pb, ld = _planes(B, "B", heads, True)
-    pl, ll = _lse_planes(L, "L", heads)
-    return _timed("spmv_hip_time_attention_gqa_lse_launches", (handle, int(heads), int(kv_heads), k, dv, float(scale), pq, ldq, pk, ldk, pv, ldv, pb, ld, po, ldo,
-                                                               pl, ll), warmup, iters)
+def _operand(a, name, width, optional=True):
+    """-> (address, ld) of a 2-D block that must have `width` columns; None -- an output that is not wanted, or an input the call can do
+    without -- is a NULL address with the width as ld"""
+    if a is None:
+        if width and not optional:
+            raise ValueError(f"{name} has 0 columns, expected {width}")
+        return None, int(width)
+    p, _, w, ld = _block(a, name)
+    if w != width:
+        raise ValueError(f"{name} has {w} columns, expected {width}")
+    return p, int(max(ld, 1))
 
 
 T_HANDLE, T_F16, T_BF16 = 0, 1, 2   # include/spmv_hip.h: SPMV_HIP_T_*
 
 
-def _types_16(Q, K, V, O):
-    """-> (io_type, o_type) of an attention_gqa_lse_16 call from the operands' dtypes: Q, K and V torch tensors (CPU or device) that are all
-    torch.float16 or all torch.bfloat16; O of that dtype or torch.float32"""
+def _types_16(handle, ops):
+    """-> the SPMV_HIP_T_* codes of a 16-bit call, by their names in the prototype, from the operands' dtypes.  Q, K and V -- and G, where
+    there is one -- are torch tensors (CPU or device), all torch.float16 or all torch.bfloat16; an output -- O of the forward, dQ, dK and dV --
+    has that dtype or torch.float32, the handle's; dK and dV, where both are given, share one.  The backward also wants a float32 handle (the
+    forward leaves a float64 one to the library, which answers E_ARG), float32 B, dB, O and L, and O and L together or not at all."""
     import torch
     codes = {torch.float16: T_F16, torch.bfloat16: T_BF16}
-    for t, name in ((Q, "Q"), (K, "K"), (V, "V"), (O, "O")):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{name} must be a torch.Tensor (numpy has no bfloat16), not {type(t).__name__}")
-    if Q.dtype not in codes or K.dtype != Q.dtype or V.dtype != Q.dtype:
-        raise TypeError(f"Q, K and V must all be torch.float16 or all torch.bfloat16, not {Q.dtype}, {K.dtype} and {V.dtype}")
-    if O.dtype != Q.dtype and O.dtype != torch.float32:
-        raise TypeError(f"O must be {Q.dtype} or torch.float32, not {O.dtype}")
-    return codes[Q.dtype], (T_HANDLE if O.dtype == torch.float32 else codes[Q.dtype])
+    backward = "G" in ops
+    ins = ("Q", "K", "V", "G") if backward else ("Q", "K", "V")
+    for name in ins if backward else (*ins, "O"):
+        if not isinstance(ops[name], torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor (numpy has no bfloat16), not {type(ops[name]).__name__}")
+    dtype = ops["Q"].dtype
+    if dtype not in codes or any(ops[name].dtype != dtype for name in ins):
+        raise TypeError(f"{', '.join(ins)} must all be torch.float16 or all torch.bfloat16, not {', '.join(str(ops[name].dtype) for name in ins)}")
+
+    def code(name):   # of an output; one that is not wanted (None) gets the inputs' code, which is never looked at
+        t = ops[name]
+        if t is not None and (not isinstance(t, torch.Tensor) or (t.dtype != dtype and t.dtype != torch.float32)):
+            raise TypeError(f"{name} must be a torch.Tensor of {dtype} or torch.float32")
+        return (T_HANDLE,) if t is not None and t.dtype == torch.float32 else (codes[dtype],)
+    if not backward:
+        return {"io_type": (codes[dtype],), "o_type": code("O")}
+    if handle and handle.contents.data_size == 8:   # the public handle's own field: no device call
+        raise TypeError("16-bit Q, K, V and G need a float32 handle, not a float64 one")
+    dq, dk, dv = code("dQ"), code("dK"), code("dV")
+    if ops["dK"] is not None and ops["dV"] is not None and ops["dK"].dtype != ops["dV"].dtype:
+        raise TypeError(f"dK and dV share one type, not {ops['dK'].dtype} and {ops['dV'].dtype}")
+    for name in ("B", "dB", "O", "L"):
+        if isinstance(ops[name], torch.Tensor) and ops[name].dtype != torch.float32:
+            raise TypeError(f"{name} must be torch.float32, not {ops[name].dtype}")
+    if (ops["O"] is None) != (ops["L"] is None):
+        raise ValueError("O and L are given together (the backward driven by them) or not at all")
+    return {"io_type": (codes[dtype],), "dq_type": dq, "dkv_type": dv if ops["dK"] is None else dk}
+
+
+def _attention_args(stem, handle, heads, kv_heads, scale, ops, ldb=None, lddb=None, ldl=None):
+    """-> the arguments of spmv_hip_<stem> and of its timer from the sizes on, in the order of the row _ATTENTION[stem]: the one marshaller of
+    the family, every rule of which is written once, here.  ops: the row's operands by name -- numpy arrays, torch tensors or None --; heads: 1
+    on the rungs that have none; kv_heads: None on the rungs that have none, where it is `heads`; ldb / lddb / ldl: plane strides that replace
+    what B, dB and L give (flat buffers holding padded planes).  Everything is checked here, before any device call."""
+    row = _ATTENTION[stem]
+    heads, grouped = int(heads), kv_heads is not None
+    kv_heads = int(kv_heads) if grouped else heads
+    rec = {"heads": (heads,), "kv_heads": (kv_heads,)}   # name -> what the prototype has under that name, as a tuple
+    if "io_type" in row:
+        rec.update(_types_16(handle, ops))
+    # the four blocks of every rung: Q holds `heads` heads of k columns and K `kv_heads`; V holds `kv_heads` heads of dv columns and the query
+    # side -- O of a forward, G of a backward -- `heads`
+    side = "G" if "G" in ops else "O"
+    Q, K, V, S = ops["Q"], ops["K"], ops["V"], ops[side]
+    (pq, _, wq, ldq), (pk, _, wk, ldk), (pv, _, wv, ldv), (ps, _, ws, lds) = _block(Q, "Q"), _block(K, "K"), _block(V, "V"), _block(S, side)
+    if not grouped:   # before kv_heads, a block that is None has its partner's width and the NULL is the library's to refuse (as in _blocks)
+        wq, wk = (wk if Q is None else wq), (wq if K is None else wk)
+        wv, ws = (ws if V is None else wv), (wv if S is None else ws)
+    k, dv = _gqa_widths(heads, kv_heads, wq, wk, wv, ws, side)
+    rec["Q"], rec["K"] = (pq, wq if Q is None else max(ldq, 1)), (pk, wk if K is None else max(ldk, 1))   # None: NULL with its width as ld
+    rec["V"], rec[side] = (pv, wv if V is None else max(ldv, 1)), (ps, ws if S is None else max(lds, 1))
+    rec["k"], rec["dv"] = (k,), (dv,)
+    # scale None is 1 / sqrt(k) in double: math.sqrt and numpy's sqrt are both the correctly rounded root, so the bits are those of either; 0
+    # stands beside a k that the library refuses before it reads scale
+    rec["scale"] = ((1.0 / math.sqrt(k) if k > 0 else 0.0) if scale is None else float(scale),)
+    for name, width in (("dQ", wq), ("dK", wk), ("dV", wv)):
+        if name in ops:
+            rec[name] = _operand(ops[name], name, width)
+    if side == "G" and "O" in ops:   # the final output that drives a backward: only the 16-bit call can do without it (and without L, _types_16)
+        rec["O"] = _operand(ops["O"], "O", heads * dv, optional="io_type" in row)
+    if "B" in ops:
+        rec["B"] = (_ptr(ops["B"]), int(ldb)) if ldb is not None else _planes(ops["B"], "B", heads, True)
+    if "dB" in ops:
+        rec["dB"] = (_ptr(ops["dB"]), int(lddb)) if lddb is not None else _planes(ops["dB"], "dB", heads, False)
+    if "L" in ops:
+        rec["L"] = (_ptr(ops["L"]), int(ldl)) if ldl is not None else _lse_planes(ops["L"], "L", heads)
+    return [x for name in row for x in rec[name]]
+
+
+def _attention_call(stem, handle, m, RowPtr, ColIdx, Matrix_Val, heads, kv_heads, scale, check, ops, **ld):
+    """spmv_hip_<stem> on the named operands `ops` (_attention_args) -> the return code; a failure is raised when `check` is set"""
+    args = _attention_args(stem, handle, heads, kv_heads, scale, ops, **ld)
+    return _checked(getattr(load(), "spmv_hip_" + stem)(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), *args), "spmv_hip_" + stem, check)
+
+
+def _attention_time(stem, handle, heads, kv_heads, scale, warmup, iters, ops):
+    """-> (mean_ms, per-call ms array) of spmv_hip_<stem> on the named device operands `ops`: spmv_hip_time_<stem>_launches"""
+    return _timed(f"spmv_hip_time_{stem}_launches", (handle, *_attention_args(stem, handle, heads, kv_heads, scale, ops)), warmup, iters)
+
+
+def attention(handle, m, RowPtr, ColIdx, Matrix_Val, Q, K, V, O, scale=None, check=True):
+    """O = softmax_rows(scale * Q K^T on the handle's pattern) V in one pass (spmv_hip_attention).  Q (m x k), K (n x k), V (n x dv) and O
+    (m x dv): 2-D numpy arrays or torch tensors with column stride 1 (row strides are passed as leading dimensions); scale None means
+    1 / sqrt(k).  The handle's values are neither read nor changed.  -> the return code."""
+    return _attention_call("attention", handle, m, RowPtr, ColIdx, Matrix_Val, 1, None, scale, check, dict(Q=Q, K=K, V=V, O=O))
+
+
+def time_attention_launches(handle, Q, K, V, O, scale=None, warmup=10, iters=100):
+    """-> (mean_ms, per-call ms array) of spmv_hip_attention on device Q / K / V / O (spmv_hip_time_attention_launches)."""
+    return _attention_time("attention", handle, 1, None, scale, warmup, iters, dict(Q=Q, K=K, V=V, O=O))
+
+
+def attention_heads(handle, m, RowPtr, ColIdx, Matrix_Val, heads, Q, K, V, O, scale=None, check=True):
+    """`heads` attention heads over the handle's pattern in one pass (spmv_hip_attention_heads).  Q (m x heads*k), K (n x heads*k),
+    V (n x heads*dv) and O (m x heads*dv) hold the heads side by side -- the (rows, heads, k) layout --: 2-D numpy arrays or torch tensors with
+    column stride 1 (row strides are passed as leading dimensions); head h of O has the bits of attention() on the h-th column slices.  scale
+    None means 1 / sqrt(k) with k ONE head's width.  The handle's values are neither read nor changed.  -> the return code."""
+    return _attention_call("attention_heads", handle, m, RowPtr, ColIdx, Matrix_Val, heads, None, scale, check, dict(Q=Q, K=K, V=V, O=O))
+
+
+def time_attention_heads_launches(handle, heads, Q, K, V, O, scale=None, warmup=10, iters=100):
+    """-> (mean_ms, per-call ms array) of spmv_hip_attention_heads on device Q / K / V / O (spmv_hip_time_attention_heads_launches)."""
+    return _attention_time("attention_heads", handle, heads, None, scale, warmup, iters, dict(Q=Q, K=K, V=V, O=O))
+
+
+def attention_backward(handle, m, RowPtr, ColIdx, Matrix_Val, Q, K, V, G, dQ=None, dK=None, dV=None, scale=None, check=True):
+    """dQ, dK, dV of O = softmax_rows(scale * Q K^T on the handle's pattern) V from G = dL/dO in two passes over A
+    (spmv_hip_attention_backward).  Q (m x k), K (n x k), V (n x dv), G (m x dv) and the outputs dQ (m x k), dK (n x k), dV (n x dv): 2-D numpy
+    arrays or torch tensors with column stride 1 (row strides are passed as leading dimensions); an output that is None is not computed; scale
+    None means 1 / sqrt(k).  The handle's values are neither read nor changed.  -> the return code."""
+    return _attention_call("attention_backward", handle, m, RowPtr, ColIdx, Matrix_Val, 1, None, scale, check, dict(Q=Q, K=K, V=V, G=G, dQ=dQ, dK=dK, dV=dV))
+
+
+def time_attention_backward_launches(handle, Q, K, V, G, dQ=None, dK=None, dV=None, scale=None, warmup=10, iters=100):
+    """-> (mean_ms, per-call ms array) of spmv_hip_attention_backward on device operands (spmv_hip_time_attention_backward_launches)."""
+    return _attention_time("attention_backward", handle, 1, None, scale, warmup, iters, dict(Q=Q, K=K, V=V, G=G, dQ=dQ, dK=dK, dV=dV))
+
+
+def attention_heads_backward(handle, m, RowPtr, ColIdx, Matrix_Val, heads, Q, K, V, G, dQ=None, dK=None, dV=None, scale=None, check=True):
+    """dQ, dK, dV of attention_heads(Q, K, V) from G = dL/dO, all heads in two passes per group of heads (spmv_hip_attention_heads_backward).
+    Q, dQ (m x heads*k), K, dK (n x heads*k), V, dV (n x heads*dv) and G (m x heads*dv) hold the heads side by side: 2-D numpy arrays or torch
+    tensors with column stride 1 (row strides are passed as leading dimensions); an output that is None is not computed; head h of every output
+    has the bits of attention_backward() on the h-th column slices.  scale None means 1 / sqrt(k) with k ONE head's width.  The handle's
+    values are neither read nor changed.  -> the return code."""
+    return _attention_call("attention_heads_backward", handle, m, RowPtr, ColIdx, Matrix_Val, heads, None, scale, check, dict(Q=Q, K=K, V=V, G=G, dQ=dQ, dK=dK, dV=dV))
+
+
+def time_attention_heads_backward_launches(handle, heads, Q, K, V, G, dQ=None, dK=None, dV=None, scale=None, warmup=10, iters=100):
+    """-> (mean_ms, per-call ms array) of spmv_hip_attention_heads_backward on device operands (spmv_hip_time_attention_heads_backward_launches)."""
+    return _attention_time("attention_heads_backward", handle, heads, None, scale, warmup, iters, dict(Q=Q, K=K, V=V, G=G, dQ=dQ, dK=dK, dV=dV))
+
+
+def attention_bias(handle, m, RowPtr, ColIdx, Matrix_Val, heads, Q, K, V, B, O, scale=None, check=True, ldb=None):
+    """attention_heads() with the additive bias B on the scaled scores (spmv_hip_attention_bias): t = (s * scale) + B.  B: None (then this IS
+    attention_heads), an (nnz,) array / tensor -- one plane shared by all heads -- or (heads, nnz) -- a plane per head, any row stride --, in
+    CSR order; ldb overrides the plane stride derived from B (for flat buffers holding padded planes).  -> the return code."""
+    return _attention_call("attention_bias", handle, m, RowPtr, ColIdx, Matrix_Val, heads, None, scale, check, dict(Q=Q, K=K, V=V, B=B, O=O), ldb=ldb)
+
+
+def time_attention_bias_launches(handle, heads, Q, K, V, B, O, scale=None, warmup=10, iters=100):
+    """-> (mean_ms, per-call ms array) of spmv_hip_attention_bias on device operands (spmv_hip_time_attention_bias_launches)."""
+    return _attention_time("attention_bias", handle, heads, None, scale, warmup, iters, dict(Q=Q, K=K, V=V, B=B, O=O))
+
+
+def attention_bias_backward(handle, m, RowPtr, ColIdx, Matrix_Val, heads, Q, K, V, B, G, dQ=None, dK=None, dV=None, dB=None, scale=None, check=True,
+                            ldb=None, lddb=None):
+    """dQ, dK, dV and dB of attention_bias(Q, K, V, B) from G = dL/dO (spmv_hip_attention_bias_backward).  B as in attention_bias(); dB: None
+    (not wanted) or (heads, nnz) -- always a plane per head, dB[h, p] = P (dP - D) of head h --; the other operands as in
+    attention_heads_backward(); ldb / lddb override the plane strides.  With B None, dQ, dK and dV are attention_heads_backward()'s to the
+    bit.  -> the return code."""
+    return _attention_call("attention_bias_backward", handle, m, RowPtr, ColIdx, Matrix_Val, heads, None, scale, check,
+                           dict(Q=Q, K=K, V=V, B=B, G=G, dQ=dQ, dK=dK, dV=dV, dB=dB), ldb=ldb, lddb=lddb)
+
+
+def time_attention_bias_backward_launches(handle, heads, Q, K, V, B, G, dQ=None, dK=None, dV=None, dB=None, scale=None, warmup=10, iters=100):
+    """-> (mean_ms, per-call ms array) of spmv_hip_attention_bias_backward on device operands (spmv_hip_time_attention_bias_backward_launches)."""
+    return _attention_time("attention_bias_backward", handle, heads, None, scale, warmup, iters, dict(Q=Q, K=K, V=V, B=B, G=G, dQ=dQ, dK=dK, dV=dV, dB=dB))
+
+
+def attention_gqa(handle, m, RowPtr, ColIdx, Matrix_Val, heads, kv_heads, Q, K, V, B, O, scale=None, check=True, ldb=None):
+    """attention_bias() with `kv_heads` K / V heads for `heads` query heads (spmv_hip_attention_gqa; grouped-query attention, kv_heads = 1:
+    multi-query).  Q (m x heads*k) and O (m x heads*dv) as there; K is (n x kv_heads*k) and V (n x kv_heads*dv); query head h uses K / V head
+    h // (heads // kv_heads), the grouping of repeat_interleave, and has the bits of the single-head call on those slices.  B: None, (nnz,) or
+    (heads, nnz) -- per QUERY head.  kv_heads = heads is attention_bias().  -> the return code."""
+    return _attention_call("attention_gqa", handle, m, RowPtr, ColIdx, Matrix_Val, heads, kv_heads, scale, check, dict(Q=Q, K=K, V=V, B=B, O=O), ldb=ldb)
+
+
+def time_attention_gqa_launches(handle, heads, kv_heads, Q, K, V, B, O, scale=None, warmup=10, iters=100):
+    """-> (mean_ms, per-call ms array) of spmv_hip_attention_gqa on device operands (spmv_hip_time_attention_gqa_launches)."""
+    return _attention_time("attention_gqa", handle, heads, kv_heads, scale, warmup, iters, dict(Q=Q, K=K, V=V, B=B, O=O))
+
+
+def attention_gqa_backward(handle, m, RowPtr, ColIdx, Matrix_Val, heads, kv_heads, Q, K, V, B, G, dQ=None, dK=None, dV=None, dB=None, scale=None, check=True,
+                           ldb=None, lddb=None):
+    """dQ, dK, dV and dB of attention_gqa(Q, K, V, B) from G = dL/dO (spmv_hip_attention_gqa_backward).  Q, G, dQ hold `heads` blocks, K, V, dK, dV
+    `kv_heads`; dB: None or (heads, nnz).  dQ and dB of head h are the single-head backward's bits on its slices; dK / dV of a K / V head are the
+    sums of its query heads' single-head dK / dV, added in ascending head in the handle's precision, the first taken as it is.  kv_heads = heads
+    is attention_bias_backward().  -> the return code."""
+    return _attention_call("attention_gqa_backward", handle, m, RowPtr, ColIdx, Matrix_Val, heads, kv_heads, scale, check,
+                           dict(Q=Q, K=K, V=V, B=B, G=G, dQ=dQ, dK=dK, dV=dV, dB=dB), ldb=ldb, lddb=lddb)
+
+
+def time_attention_gqa_backward_launches(handle, heads, kv_heads, Q, K, V, B, G, dQ=None, dK=None, dV=None, dB=None, scale=None, warmup=10, iters=100):
+    """-> (mean_ms, per-call ms array) of spmv_hip_attention_gqa_backward on device operands (spmv_hip_time_attention_gqa_backward_launches)."""
+    return _attention_time("attention_gqa_backward", handle, heads, kv_heads, scale, warmup, iters, dict(Q=Q, K=K, V=V, B=B, G=G, dQ=dQ, dK=dK, dV=dV, dB=dB))
+
+
+def attention_gqa_lse(handle, m, RowPtr, ColIdx, Matrix_Val, heads, kv_heads, Q, K, V, B, O, L, scale=None, check=True, ldb=None, ldl=None):
+    """attention_gqa() that also writes the rows' log-sum-exps (spmv_hip_attention_gqa_lse): L is (heads, m) -- any row stride; ldl overrides it for
+    flat buffers holding padded planes --, L[h, i] = M_i + log Z_i of query head h, -inf on a row without entries.  O has attention_gqa()'s bits;
+    L None IS attention_gqa().  -> the return code."""
+    return _attention_call("attention_gqa_lse", handle, m, RowPtr, ColIdx, Matrix_Val, heads, kv_heads, scale, check, dict(Q=Q, K=K, V=V, B=B, O=O, L=L), ldb=ldb, ldl=ldl)
+
+
+def time_attention_gqa_lse_launches(handle, heads, kv_heads, Q, K, V, B, O, L, scale=None, warmup=10, iters=100):
+    """-> (mean_ms, per-call ms array) of spmv_hip_attention_gqa_lse on device operands (spmv_hip_time_attention_gqa_lse_launches)."""
+    return _attention_time("attention_gqa_lse", handle, heads, kv_heads, scale, warmup, iters, dict(Q=Q, K=K, V=V, B=B, O=O, L=L))
 
 
 def attention_gqa_lse_16(handle, m, RowPtr, ColIdx, Matrix_Val, heads, kv_heads, Q, K, V, B, O, L=None, scale=None, check=True, ldb=None, ldl=None):
@@ -797,24 +753,12 @@ def attention_gqa_lse_16(handle, m, RowPtr, ColIdx, Matrix_Val, heads, kv_heads,
     torch.float16 or all torch.bfloat16, on the CPU or the device; O is a tensor of that dtype or of torch.float32; B (None, (nnz,) or (heads, nnz))
     and L (None or (heads, m)) are fp32.  An fp32 O and L have the bits of attention_gqa_lse() on Q.float(), K.float(), V.float(); a 16-bit O is that
     result rounded once, O32.to(dtype).  Row strides are passed as leading dimensions in elements of each tensor's own dtype.  -> the return code."""
-    io_type, o_type = _types_16(Q, K, V, O)
-    k, dv, pq, ldq, pk, ldk, pv, ldv, po, ldo = _attention_gqa_blocks(heads, kv_heads, Q, K, V, O)
-    scale = 1.0 / np.sqrt(k) if scale is None and k > 0 else (0.0 if scale is None else scale)
-    pb, ld = (_ptr(B), int(ldb)) if ldb is not None else _planes(B, "B", heads, True)
-    pl, ll = (_ptr(L), int(ldl)) if ldl is not None else _lse_planes(L, "L", heads)
-    return _checked(load().spmv_hip_attention_gqa_lse_16(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), int(heads), int(kv_heads), k, dv, float(scale),
-                                                         io_type, pq, ldq, pk, ldk, pv, ldv, pb, ld, po, ldo, o_type, pl, ll), "spmv_hip_attention_gqa_lse_16", check)
+    return _attention_call("attention_gqa_lse_16", handle, m, RowPtr, ColIdx, Matrix_Val, heads, kv_heads, scale, check, dict(Q=Q, K=K, V=V, B=B, O=O, L=L), ldb=ldb, ldl=ldl)
 
 
 def time_attention_gqa_lse_16_launches(handle, heads, kv_heads, Q, K, V, B, O, L=None, scale=None, warmup=10, iters=100):
     """-> (mean_ms, per-call ms array) of spmv_hip_attention_gqa_lse_16 on device operands (spmv_hip_time_attention_gqa_lse_16_launches)."""
-    io_type, o_type = _types_16(Q, K, V, O)
-    k, dv, pq, ldq, pk, ldk, pv, ldv, po, ldo = _attention_gqa_blocks(heads, kv_heads, Q, K, V, O)
-    scale = 1.0 / np.sqrt(k) if scale is None else scale
-    pb, ld = _planes(B, "B", heads, True)
-    pl, ll = _lse_planes(L, "L", heads)
-    return _timed("spmv_hip_time_attention_gqa_lse_16_launches", (handle, int(heads), int(kv_heads), k, dv, float(scale), io_type, pq, ldq, pk, ldk, pv, ldv, pb, ld,
-                                                                  po, ldo, o_type, pl, ll), warmup, iters)
+    return _attention_time("attention_gqa_lse_16", handle, heads, kv_heads, scale, warmup, iters, dict(Q=Q, K=K, V=V, B=B, O=O, L=L))
 
 
 def _attention_merge_args(heads, O1, L1, O2, L2, O, L, ldl):
@@ -846,73 +790,19 @@ def time_attention_merge_launches(handle, heads, O1, L1, O2, L2, O, L=None, warm
     return _timed("spmv_hip_time_attention_merge_launches", (handle, int(heads), dv, *args), warmup, iters)
 
 
-def _attention_gqa_backward_lse_args(heads, kv_heads, Q, K, V, B, G, O, L, dQ, dK, dV, dB, ldb, lddb, ldl):
-    """-> (k, dv, the C arguments from Q on) of an attention_gqa_backward_lse call: attention_gqa_backward's with O and L after G"""
-    k, dv, rest = _attention_gqa_backward_args(heads, kv_heads, Q, K, V, B, G, dQ, dK, dV, dB, ldb, lddb)
-    po, _, wo, ldo = _block(O, "O")
-    if wo != int(heads) * dv:
-        raise ValueError(f"O has {wo} columns, expected {int(heads) * dv}")
-    pl, ll = (_ptr(L), int(ldl)) if ldl is not None else _lse_planes(L, "L", heads)
-    # Q, K, V | B | G | O, L | dQ, dK, dV | dB
-    return k, dv, [*rest[:10], po, int(max(ldo, 1)), pl, ll, *rest[10:]]
-
-
 def attention_gqa_backward_lse(handle, m, RowPtr, ColIdx, Matrix_Val, heads, kv_heads, Q, K, V, B, G, O, L, dQ=None, dK=None, dV=None, dB=None, scale=None,
                                check=True, ldb=None, lddb=None, ldl=None):
     """attention_gqa_backward() driven by the FINAL output O (m x heads*dv) and log-sum-exp L (heads, m) of the attention this handle's entries are
     a part of (spmv_hip_attention_gqa_backward_lse): P = exp(t - L), D = <G row, O row>; for one handle, its own attention_gqa_lse() results; for
     parts, the merged ones -- then the parts' dQ are the caller's to add, dK, dV and dB are each part's own.  -> the return code."""
-    k, dv, rest = _attention_gqa_backward_lse_args(heads, kv_heads, Q, K, V, B, G, O, L, dQ, dK, dV, dB, ldb, lddb, ldl)
-    scale = 1.0 / np.sqrt(k) if scale is None and k > 0 else (0.0 if scale is None else scale)
-    return _checked(load().spmv_hip_attention_gqa_backward_lse(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), int(heads), int(kv_heads), k, dv,
-                                                               float(scale), *rest), "spmv_hip_attention_gqa_backward_lse", check)
+    return _attention_call("attention_gqa_backward_lse", handle, m, RowPtr, ColIdx, Matrix_Val, heads, kv_heads, scale, check,
+                           dict(Q=Q, K=K, V=V, B=B, G=G, O=O, L=L, dQ=dQ, dK=dK, dV=dV, dB=dB), ldb=ldb, lddb=lddb, ldl=ldl)
 
 
 def time_attention_gqa_backward_lse_launches(handle, heads, kv_heads, Q, K, V, B, G, O, L, dQ=None, dK=None, dV=None, dB=None, scale=None, warmup=10, iters=100):
     """-> (mean_ms, per-call ms array) of spmv_hip_attention_gqa_backward_lse on device operands (spmv_hip_time_attention_gqa_backward_lse_launches)."""
-    k, dv, rest = _attention_gqa_backward_lse_args(heads, kv_heads, Q, K, V, B, G, O, L, dQ, dK, dV, dB, None, None, None)
-    scale = 1.0 / np.sqrt(k) if scale is None else scale
-    return _timed("spmv_hip_time_attention_gqa_backward_lse_launches", (handle, int(heads), int(kv_heads), k, dv, float(scale), *rest), warmup, iters)
-
-
-def _attention_gqa_backward_16_args(handle, heads, kv_heads, Q, K, V, B, G, O, L, dQ, dK, dV, dB, ldb, lddb, ldl):
-    """-> (k, dv, the C arguments from io_type on) of an attention_gqa_backward_16 call.  The types come from the tensors' dtypes: Q, K, V and G
-    torch tensors that are all torch.float16 or all torch.bfloat16; dQ of that dtype or torch.float32; dK and dV, where both are given, of one such
-    dtype; O and L given together or not at all.  Everything is checked here, before any device call."""
-    import torch
-    codes = {torch.float16: T_F16, torch.bfloat16: T_BF16}
-    for t, name in ((Q, "Q"), (K, "K"), (V, "V"), (G, "G")):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{name} must be a torch.Tensor (numpy has no bfloat16), not {type(t).__name__}")
-    if Q.dtype not in codes or K.dtype != Q.dtype or V.dtype != Q.dtype or G.dtype != Q.dtype:
-        raise TypeError(f"Q, K, V and G must all be torch.float16 or all torch.bfloat16, not {Q.dtype}, {K.dtype}, {V.dtype} and {G.dtype}")
-    if handle and handle.contents.data_size == 8:   # the public handle's own field: no device call
-        raise TypeError("16-bit Q, K, V and G need a float32 handle, not a float64 one")
-    for t, name in ((dQ, "dQ"), (dK, "dK"), (dV, "dV")):
-        if t is not None and (not isinstance(t, torch.Tensor) or (t.dtype != Q.dtype and t.dtype != torch.float32)):
-            raise TypeError(f"{name} must be a torch.Tensor of {Q.dtype} or torch.float32")
-    if dK is not None and dV is not None and dK.dtype != dV.dtype:
-        raise TypeError(f"dK and dV share one type, not {dK.dtype} and {dV.dtype}")
-    for t, name in ((B, "B"), (dB, "dB"), (O, "O"), (L, "L")):
-        if isinstance(t, torch.Tensor) and t.dtype != torch.float32:
-            raise TypeError(f"{name} must be torch.float32, not {t.dtype}")
-    if (O is None) != (L is None):
-        raise ValueError("O and L are given together (the backward driven by them) or not at all")
-    dkv = dK if dK is not None else dV
-    io_type = codes[Q.dtype]
-    dq_type = T_HANDLE if dQ is not None and dQ.dtype == torch.float32 else io_type
-    dkv_type = T_HANDLE if dkv is not None and dkv.dtype == torch.float32 else io_type
-    k, dv, rest = _attention_gqa_backward_args(heads, kv_heads, Q, K, V, B, G, dQ, dK, dV, dB, ldb, lddb)
-    if O is None:
-        po, ldo, pl, ll = None, int(heads) * dv, None, 0
-    else:
-        po, _, wo, ldo = _block(O, "O")
-        if wo != int(heads) * dv:
-            raise ValueError(f"O has {wo} columns, expected {int(heads) * dv}")
-        ldo = int(max(ldo, 1))
-        pl, ll = (_ptr(L), int(ldl)) if ldl is not None else _lse_planes(L, "L", heads)
-    # io_type | Q, K, V | B | G | O, L | dq_type, dQ | dkv_type, dK, dV | dB
-    return k, dv, [io_type, *rest[:10], po, ldo, pl, ll, dq_type, *rest[10:12], dkv_type, *rest[12:]]
+    return _attention_time("attention_gqa_backward_lse", handle, heads, kv_heads, scale, warmup, iters,
+                           dict(Q=Q, K=K, V=V, B=B, G=G, O=O, L=L, dQ=dQ, dK=dK, dV=dV, dB=dB))
 
 
 def attention_gqa_backward_16(handle, m, RowPtr, ColIdx, Matrix_Val, heads, kv_heads, Q, K, V, B, G, O=None, L=None, dQ=None, dK=None, dV=None, dB=None, scale=None,
@@ -923,17 +813,14 @@ def attention_gqa_backward_16(handle, m, RowPtr, ColIdx, Matrix_Val, heads, kv_h
     fp32 call on Q.float(), K.float(), V.float(), G.float(); a 16-bit output is that result rounded once, g32.to(dtype) -- also over groups of heads
     (kv_heads < heads), whose sums are made in fp32 whatever option "attention_backward_heads" says.  Mixed dtypes or a float64 handle: TypeError.
     On a band the call is no faster than widening first; what it saves is the fp32 copies.  -> the return code."""
-    k, dv, rest = _attention_gqa_backward_16_args(handle, heads, kv_heads, Q, K, V, B, G, O, L, dQ, dK, dV, dB, ldb, lddb, ldl)
-    scale = 1.0 / np.sqrt(k) if scale is None and k > 0 else (0.0 if scale is None else scale)
-    return _checked(load().spmv_hip_attention_gqa_backward_16(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), int(heads), int(kv_heads), k, dv,
-                                                              float(scale), *rest), "spmv_hip_attention_gqa_backward_16", check)
+    return _attention_call("attention_gqa_backward_16", handle, m, RowPtr, ColIdx, Matrix_Val, heads, kv_heads, scale, check,
+                           dict(Q=Q, K=K, V=V, B=B, G=G, O=O, L=L, dQ=dQ, dK=dK, dV=dV, dB=dB), ldb=ldb, lddb=lddb, ldl=ldl)
 
 
 def time_attention_gqa_backward_16_launches(handle, heads, kv_heads, Q, K, V, B, G, O=None, L=None, dQ=None, dK=None, dV=None, dB=None, scale=None, warmup=10, iters=100):
     """-> (mean_ms, per-call ms array) of spmv_hip_attention_gqa_backward_16 on device operands (spmv_hip_time_attention_gqa_backward_16_launches)."""
-    k, dv, rest = _attention_gqa_backward_16_args(handle, heads, kv_heads, Q, K, V, B, G, O, L, dQ, dK, dV, dB, None, None, None)
-    scale = 1.0 / np.sqrt(k) if scale is None else scale
-    return _timed("spmv_hip_time_attention_gqa_backward_16_launches", (handle, int(heads), int(kv_heads), k, dv, float(scale), *rest), warmup, iters)
+    return _attention_time("attention_gqa_backward_16", handle, heads, kv_heads, scale, warmup, iters,
+                           dict(Q=Q, K=K, V=V, B=B, G=G, O=O, L=L, dQ=dQ, dK=dK, dV=dV, dB=dB))
 
 
 def _cg_options(rtol, atol, max_iterations, check_every, x0, dinv, history):
@@ -1139,12 +1026,12 @@ class Handle:
         spmv_transpose(self.h, self.m, rp, ci, va, x, y)
         return y
 
-    def _like(self, a, shape):
-        """an uninitialised array of `shape`, of a's kind, dtype and device"""
+    def _like(self, a, shape, dtype=None):
+        """an uninitialised array of `shape`, of a's kind, dtype -- or `dtype` -- and device"""
         if isinstance(a, np.ndarray):
-            return np.empty(shape, dtype=a.dtype)
+            return np.empty(shape, dtype=dtype or a.dtype)
         import torch
-        return torch.empty(shape, dtype=a.dtype, device=a.device)
+        return torch.empty(shape, dtype=dtype or a.dtype, device=a.device)
 
     def spmm_transpose(self, X, Y=None):
         """Y = A^T X (spmv_hip_spmm_transpose) for a 2-D X of m x k; Y (n x k) is allocated like X -- same kind, dtype and device -- when None."""
@@ -1228,104 +1115,92 @@ class Handle:
         -> (x, result dict) or (x, result dict, history) when history is set: rr after iteration 0 .. iterations."""
         return self._solve(bicgstab, b, x, x0, rtol, atol, max_iterations, check_every, dinv, history)
 
+    def _attention_out(self, Q, V, heads, kv_heads, out, dtype=None):
+        """-> `out`, or when that is None the uninitialised output of an attention forward: (m, heads * dv) like Q -- of `dtype` where one is
+        given --, dv the width of one of V's kv_heads heads (kv_heads None: as wide as V, a head of V for every head of out)"""
+        if out is None:
+            out = self._like(Q, (self.m, V.shape[1] if kv_heads is None else (V.shape[1] // int(kv_heads)) * int(heads)), dtype)
+        return out
+
+    def _attention_grads(self, Q, K, V, heads, need, dtypes=(None, None, None, None)):
+        """-> the outputs of an attention backward that `need` asks for, None for the others: dQ, dK and dV as wide as Q, K and V and, where
+        `need` has a fourth entry, dB (heads, nnz); uninitialised, like Q, of `dtypes` where those are given"""
+        shapes = [(self.m, Q.shape[1]), (self.n, K.shape[1]), (self.n, V.shape[1])]
+        if len(need) > 3:
+            shapes.append((int(heads), self.nnz) if need[3] else None)
+        return tuple(self._like(Q, shape, dtype) if want else None for shape, want, dtype in zip(shapes, need, dtypes))
+
     def attention(self, Q, K, V, scale=None, out=None):
         """out = softmax_rows(scale * Q K^T on the pattern) V in one pass (spmv_hip_attention) for 2-D Q (m x k), K (n x k) and V (n x dv); scale
         None means 1 / sqrt(k); out (m x dv) is allocated like Q -- same kind, dtype and device -- when None.  The handle's values are not
         used and not changed."""
-        if out is None:
-            out = self._like(Q, (self.m, V.shape[1]))
-        rp, ci, va = self._keep
-        attention(self.h, self.m, rp, ci, va, Q, K, V, out, scale)
+        out = self._attention_out(Q, V, 1, None, out)
+        attention(self.h, self.m, *self._keep, Q, K, V, out, scale)
         return out
 
     def attention_heads(self, Q, K, V, heads, scale=None, out=None):
         """out = `heads` attention heads over the pattern in one pass (spmv_hip_attention_heads) for 2-D Q (m x heads*k), K (n x heads*k) and
         V (n x heads*dv) holding the heads side by side; scale None means 1 / sqrt(k), k one head's width; out (m x heads*dv) is allocated like
         Q -- same kind, dtype and device -- when None.  The handle's values are not used and not changed."""
-        if out is None:
-            out = self._like(Q, (self.m, V.shape[1]))
-        rp, ci, va = self._keep
-        attention_heads(self.h, self.m, rp, ci, va, heads, Q, K, V, out, scale)
+        out = self._attention_out(Q, V, heads, None, out)
+        attention_heads(self.h, self.m, *self._keep, heads, Q, K, V, out, scale)
         return out
 
     def attention_backward(self, Q, K, V, G, scale=None, need=(True, True, True)):
         """-> (dQ, dK, dV), the gradients of attention(Q, K, V, scale) for G = dL/dO (m x dv), in two passes over A (spmv_hip_attention_backward);
         need: which of the three are wanted -- the others are None and nothing is computed for them.  The outputs are allocated like Q -- same
         kind, dtype and device.  The handle's values are not used and not changed."""
-        k, dv = Q.shape[1], V.shape[1]
-        dQ = self._like(Q, (self.m, k)) if need[0] else None
-        dK = self._like(Q, (self.n, k)) if need[1] else None
-        dV = self._like(Q, (self.n, dv)) if need[2] else None
-        rp, ci, va = self._keep
-        attention_backward(self.h, self.m, rp, ci, va, Q, K, V, G, dQ, dK, dV, scale)
-        return dQ, dK, dV
+        grads = self._attention_grads(Q, K, V, 1, need)
+        attention_backward(self.h, self.m, *self._keep, Q, K, V, G, *grads, scale)
+        return grads
 
     def attention_heads_backward(self, Q, K, V, G, heads, scale=None, need=(True, True, True)):
         """-> (dQ, dK, dV), the gradients of attention_heads(Q, K, V, heads, scale) for G = dL/dO (m x heads*dv), all heads in two passes per group
         of heads (spmv_hip_attention_heads_backward); need: which of the three are wanted -- the others are None and nothing is computed for
         them.  The outputs are allocated like Q -- same kind, dtype and device -- at the full widths.  The handle's values are not used and
         not changed."""
-        wk, wv = Q.shape[1], V.shape[1]
-        dQ = self._like(Q, (self.m, wk)) if need[0] else None
-        dK = self._like(Q, (self.n, wk)) if need[1] else None
-        dV = self._like(Q, (self.n, wv)) if need[2] else None
-        rp, ci, va = self._keep
-        attention_heads_backward(self.h, self.m, rp, ci, va, heads, Q, K, V, G, dQ, dK, dV, scale)
-        return dQ, dK, dV
+        grads = self._attention_grads(Q, K, V, heads, need)
+        attention_heads_backward(self.h, self.m, *self._keep, heads, Q, K, V, G, *grads, scale)
+        return grads
 
     def attention_bias(self, Q, K, V, heads, bias, scale=None, out=None):
         """out = attention_heads(Q, K, V, heads, scale) with `bias` added to the scaled scores before the softmax (spmv_hip_attention_bias);
         bias: None, (nnz,) -- one plane for all heads -- or (heads, nnz), in CSR order, of Q's kind.  The handle's values are not used and not
         changed."""
-        if out is None:
-            out = self._like(Q, (self.m, V.shape[1]))
-        rp, ci, va = self._keep
-        attention_bias(self.h, self.m, rp, ci, va, heads, Q, K, V, bias, out, scale)
+        out = self._attention_out(Q, V, heads, None, out)
+        attention_bias(self.h, self.m, *self._keep, heads, Q, K, V, bias, out, scale)
         return out
 
     def attention_bias_backward(self, Q, K, V, bias, G, heads, scale=None, need=(True, True, True, True)):
         """-> (dQ, dK, dV, dB), the gradients of attention_bias(Q, K, V, heads, bias, scale) for G = dL/dO (spmv_hip_attention_bias_backward);
         need: which of the four are wanted -- the others are None and nothing is computed for them.  dB is (heads, nnz), a plane per head also
         when the bias is one shared plane (its gradient is dB.sum(0)).  The outputs are allocated like Q."""
-        wk, wv = Q.shape[1], V.shape[1]
-        dQ = self._like(Q, (self.m, wk)) if need[0] else None
-        dK = self._like(Q, (self.n, wk)) if need[1] else None
-        dV = self._like(Q, (self.n, wv)) if need[2] else None
-        dB = self._like(Q, (int(heads), self.nnz)) if need[3] else None
-        rp, ci, va = self._keep
-        attention_bias_backward(self.h, self.m, rp, ci, va, heads, Q, K, V, bias, G, dQ, dK, dV, dB, scale)
-        return dQ, dK, dV, dB
+        grads = self._attention_grads(Q, K, V, heads, need)
+        attention_bias_backward(self.h, self.m, *self._keep, heads, Q, K, V, bias, G, *grads, scale)
+        return grads
 
     def attention_gqa(self, Q, K, V, heads, kv_heads, bias=None, scale=None, out=None):
         """out = attention_bias(Q, K, V, heads, bias, scale) with `kv_heads` K / V heads: K is (n, kv_heads*k), V (n, kv_heads*dv), and query head
         h uses K / V head h // (heads // kv_heads) (spmv_hip_attention_gqa).  out is (m, heads*dv)."""
-        if out is None:
-            out = self._like(Q, (self.m, (V.shape[1] // int(kv_heads)) * int(heads)))
-        rp, ci, va = self._keep
-        attention_gqa(self.h, self.m, rp, ci, va, heads, kv_heads, Q, K, V, bias, out, scale)
+        out = self._attention_out(Q, V, heads, kv_heads, out)
+        attention_gqa(self.h, self.m, *self._keep, heads, kv_heads, Q, K, V, bias, out, scale)
         return out
 
     def attention_gqa_backward(self, Q, K, V, bias, G, heads, kv_heads, scale=None, need=(True, True, True, True)):
         """-> (dQ, dK, dV, dB), the gradients of attention_gqa(Q, K, V, heads, kv_heads, bias, scale) for G = dL/dO
         (spmv_hip_attention_gqa_backward); need: which of the four are wanted.  dK and dV have K's and V's widths (kv_heads blocks): the sums over
         each group's query heads in ascending head.  dB is (heads, nnz).  The outputs are allocated like Q."""
-        dQ = self._like(Q, (self.m, Q.shape[1])) if need[0] else None
-        dK = self._like(Q, (self.n, K.shape[1])) if need[1] else None
-        dV = self._like(Q, (self.n, V.shape[1])) if need[2] else None
-        dB = self._like(Q, (int(heads), self.nnz)) if need[3] else None
-        rp, ci, va = self._keep
-        attention_gqa_backward(self.h, self.m, rp, ci, va, heads, kv_heads, Q, K, V, bias, G, dQ, dK, dV, dB, scale)
-        return dQ, dK, dV, dB
+        grads = self._attention_grads(Q, K, V, heads, need)
+        attention_gqa_backward(self.h, self.m, *self._keep, heads, kv_heads, Q, K, V, bias, G, *grads, scale)
+        return grads
 
     def attention_gqa_lse(self, Q, K, V, heads, kv_heads, bias=None, scale=None, out=None, lse=None):
         """-> (out, lse): attention_gqa(Q, K, V, heads, kv_heads, bias, scale) and the rows' log-sum-exps, lse (heads, m), -inf on a row without
         entries (spmv_hip_attention_gqa_lse).  out has attention_gqa()'s bits."""
-        if out is None:
-            out = self._like(Q, (self.m, (V.shape[1] // int(kv_heads)) * int(heads)))
+        out = self._attention_out(Q, V, heads, kv_heads, out)
         if lse is None:
             lse = self._like(Q, (int(heads), self.m))
-        rp, ci, va = self._keep
-        attention_gqa_lse(self.h, self.m, rp, ci, va, heads, kv_heads, Q, K, V, bias, out, lse, scale)
+        attention_gqa_lse(self.h, self.m, *self._keep, heads, kv_heads, Q, K, V, bias, out, lse, scale)
         return out, lse
 
     def attention_gqa_lse_16(self, Q, K, V, heads, kv_heads, B=None, scale=None, out_dtype=None, want_l=True):
@@ -1336,10 +1211,9 @@ class Handle:
         import torch
         if not isinstance(Q, torch.Tensor) or not isinstance(V, torch.Tensor):
             raise TypeError("Q, K and V must be torch tensors")
-        out = torch.empty((self.m, (V.shape[1] // int(kv_heads)) * int(heads)), dtype=Q.dtype if out_dtype is None else out_dtype, device=Q.device)
-        lse = torch.empty((int(heads), self.m), dtype=torch.float32, device=Q.device) if want_l else None
-        rp, ci, va = self._keep
-        attention_gqa_lse_16(self.h, self.m, rp, ci, va, heads, kv_heads, Q, K, V, B, out, lse, scale)
+        out = self._attention_out(Q, V, heads, kv_heads, None, out_dtype)
+        lse = self._like(Q, (int(heads), self.m), torch.float32) if want_l else None
+        attention_gqa_lse_16(self.h, self.m, *self._keep, heads, kv_heads, Q, K, V, B, out, lse, scale)
         return out, lse
 
     def attention_merge(self, O1, L1, O2, L2, heads, out=None, lse=None, want_lse=True):
@@ -1355,13 +1229,9 @@ class Handle:
     def attention_gqa_backward_lse(self, Q, K, V, bias, G, O, L, heads, kv_heads, scale=None, need=(True, True, True, True)):
         """-> (dQ, dK, dV, dB) like attention_gqa_backward(), driven by the FINAL output O and log-sum-exp L of the attention this handle's entries
         are a part of (spmv_hip_attention_gqa_backward_lse)."""
-        dQ = self._like(Q, (self.m, Q.shape[1])) if need[0] else None
-        dK = self._like(Q, (self.n, K.shape[1])) if need[1] else None
-        dV = self._like(Q, (self.n, V.shape[1])) if need[2] else None
-        dB = self._like(Q, (int(heads), self.nnz)) if need[3] else None
-        rp, ci, va = self._keep
-        attention_gqa_backward_lse(self.h, self.m, rp, ci, va, heads, kv_heads, Q, K, V, bias, G, O, L, dQ, dK, dV, dB, scale)
-        return dQ, dK, dV, dB
+        grads = self._attention_grads(Q, K, V, heads, need)
+        attention_gqa_backward_lse(self.h, self.m, *self._keep, heads, kv_heads, Q, K, V, bias, G, O, L, *grads, scale)
+        return grads
 
     def attention_gqa_backward_16(self, Q, K, V, B, G, heads, kv_heads, scale=None, O=None, L=None, need=(True, True, True, True), dq_dtype=None, dkv_dtype=None):
         """-> (dQ, dK, dV, dB): attention_gqa_backward() -- O and L None -- or attention_gqa_backward_lse() -- the final fp32 O and L given -- on
@@ -1372,15 +1242,10 @@ class Handle:
         import torch
         if not all(isinstance(t, torch.Tensor) for t in (Q, K, V, G)):
             raise TypeError("Q, K, V and G must be torch tensors")
-        dq_dtype = Q.dtype if dq_dtype is None else dq_dtype
-        dkv_dtype = Q.dtype if dkv_dtype is None else dkv_dtype
-        dQ = torch.empty((self.m, Q.shape[1]), dtype=dq_dtype, device=Q.device) if need[0] else None
-        dK = torch.empty((self.n, K.shape[1]), dtype=dkv_dtype, device=Q.device) if need[1] else None
-        dV = torch.empty((self.n, V.shape[1]), dtype=dkv_dtype, device=Q.device) if need[2] else None
-        dB = torch.empty((int(heads), self.nnz), dtype=torch.float32, device=Q.device) if need[3] else None
-        rp, ci, va = self._keep
-        attention_gqa_backward_16(self.h, self.m, rp, ci, va, heads, kv_heads, Q, K, V, B, G, O, L, dQ, dK, dV, dB, scale)
-        return dQ, dK, dV, dB
+        grads = self._attention_grads(Q, K, V, heads, need, (dq_dtype, dkv_dtype, dkv_dtype, torch.float32))
+        attention_gqa_backward_16(self.h, self.m, *self._keep, heads, kv_heads, Q, K, V, B, G, O, L, *grads, scale)
+        return grads
+
 
     def update_values(self, val):
         """The caller changed the values (in place or in a new array of the same pattern)."""

@@ -250,38 +250,11 @@ def _bias_planes(bias):
     return b.contiguous() if b.dim() == 1 else _block(b, b.shape[1])
 
 
-def _forward(handle, Q2, K2, V2, heads, bias, scale):
-    """the one fused forward pass: Handle.attention / attention_heads, or Handle.attention_bias when there is a bias"""
-    if bias is not None:
-        return handle.attention_bias(Q2, K2, V2, heads, bias, scale)
-    return handle.attention(Q2, K2, V2, scale) if heads is None else handle.attention_heads(Q2, K2, V2, heads, scale)
-
-
 def _bias_grad(dB, bias):
     """dL/dbias from the per-head planes dB (heads, nnz): a shared plane's is their sum -- torch's sum, whose order is torch's business"""
     if dB is None:
         return None
     return dB.sum(0) if bias.dim() == 1 and dB.shape[0] > 1 else dB.view(bias.shape)
-
-
-class _Attention(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, handle, Q, K, V, scale, bias=None):
-        Q2, K2, V2 = _block(Q.detach(), Q.shape[1]), _block(K.detach(), K.shape[1]), _block(V.detach(), V.shape[1])
-        B2 = _bias_planes(bias)
-        _on_current_stream(handle)
-        O = _forward(handle, Q2, K2, V2, None if B2 is None else 1, B2, scale)
-        ctx.handle, ctx.scale = handle, scale
-        ctx.save_for_backward(Q2, K2, V2, B2)   # nothing nnz-sized but the caller's own bias: the backward pass computes S and P again
-        return O
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, G):
-        Q2, K2, V2, B2 = ctx.saved_tensors
-        need = tuple(bool(x) for x in ctx.needs_input_grad[1:4])
-        dQ, dK, dV, dB = _attention_backward_composed(ctx.handle, ctx.scale, Q2, K2, V2, B2, G, need, B2 is not None and bool(ctx.needs_input_grad[5]))
-        return None, dQ, dK, dV, None, dB
 
 
 def _zero_grads(Q2, K2, V2, B2, need, need_b):
@@ -329,203 +302,85 @@ def _attention_backward_composed(handle, scale, Q2, K2, V2, B2, G, need, need_b)
     return dQ, dK, dV, dB
 
 
-class _AttentionFused(torch.autograd.Function):
-    """_Attention's forward; the backward pass is ONE Handle.attention_backward call: the handle's values are never touched"""
-
-    @staticmethod
-    def forward(ctx, handle, Q, K, V, scale, bias=None):
-        Q2, K2, V2 = _block(Q.detach(), Q.shape[1]), _block(K.detach(), K.shape[1]), _block(V.detach(), V.shape[1])
-        B2 = _bias_planes(bias)
-        _on_current_stream(handle)
-        O = _forward(handle, Q2, K2, V2, None if B2 is None else 1, B2, scale)
-        ctx.handle, ctx.scale = handle, scale
-        ctx.save_for_backward(Q2, K2, V2, B2)
-        return O
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, G):
-        Q2, K2, V2, B2 = ctx.saved_tensors
-        need = tuple(bool(x) for x in ctx.needs_input_grad[1:4])
-        dQ, dK, dV, dB = _attention_backward_fused(ctx.handle, ctx.scale, Q2, K2, V2, B2, G, need, B2 is not None and bool(ctx.needs_input_grad[5]))
-        return None, dQ, dK, dV, None, dB
-
-
-def _attention_backward_fused(handle, scale, Q2, K2, V2, B2, G, need, need_b):
-    """-> (dQ, dK, dV, dB) of attention() from ONE Handle.attention_backward / attention_bias_backward call"""
-    if not (any(need) or need_b):
-        return None, None, None, None
-    _on_current_stream(handle)
-    if B2 is None:
-        return (*handle.attention_backward(Q2, K2, V2, _block(G, G.shape[1]), scale, need=need), None)
-    dQ, dK, dV, dB = handle.attention_bias_backward(Q2, K2, V2, B2, _block(G, G.shape[1]), 1, scale, need=(*need, need_b))
-    return dQ, dK, dV, _bias_grad(dB, B2)
-
-
-class _AttentionHeads(torch.autograd.Function):
-    """Handle.attention_heads forward; the backward pass is one api.attention_backward call per head on column slices, written into the slices
-    of full-width gradients, or (fused) ONE Handle.attention_heads_backward call: the handle's values are never touched"""
-
-    @staticmethod
-    def forward(ctx, handle, Q, K, V, heads, scale, fused=False, bias=None):
-        Q2, K2, V2 = _block(Q.detach(), Q.shape[1]), _block(K.detach(), K.shape[1]), _block(V.detach(), V.shape[1])
-        B2 = _bias_planes(bias)
-        _on_current_stream(handle)
-        O = _forward(handle, Q2, K2, V2, heads, B2, scale)
-        ctx.handle, ctx.heads, ctx.scale, ctx.fused = handle, heads, scale, fused
-        ctx.save_for_backward(Q2, K2, V2, B2)   # nothing nnz-sized but the caller's own bias
-        return O
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, G):
-        Q2, K2, V2, B2 = ctx.saved_tensors
-        need = tuple(bool(x) for x in ctx.needs_input_grad[1:4])
-        dQ, dK, dV, dB = _attention_heads_backward(ctx.handle, ctx.heads, ctx.scale, ctx.fused, Q2, K2, V2, B2, G, need, B2 is not None and bool(ctx.needs_input_grad[7]))
-        return None, dQ, dK, dV, None, None, None, dB
-
-
-def _attention_heads_backward(handle, heads, scale, fused, Q2, K2, V2, B2, G, need, need_b):
-    """-> (dQ, dK, dV, dB) of attention_heads() without kv_heads: one call for all heads (fused) or one single-head call per head on column slices"""
-    from . import api
-    if not (any(need) or need_b):
-        return None, None, None, None
-    if handle.nnz == 0:
-        return _zero_grads(Q2, K2, V2, B2, need, need_b)
-    _on_current_stream(handle)
-    G2 = _block(G, G.shape[1])
-    if fused:   # every head in one call
-        if B2 is None:
-            return (*handle.attention_heads_backward(Q2, K2, V2, G2, heads, scale, need=need), None)
-        dQ, dK, dV, dB = handle.attention_bias_backward(Q2, K2, V2, B2, G2, heads, scale, need=(*need, need_b))
-        return dQ, dK, dV, _bias_grad(dB, B2)
-    k, dv = Q2.shape[1] // heads, V2.shape[1] // heads
-    dQ = torch.empty_like(Q2, memory_format=torch.contiguous_format) if need[0] else None
-    dK = torch.empty_like(K2, memory_format=torch.contiguous_format) if need[1] else None
-    dV = torch.empty_like(V2, memory_format=torch.contiguous_format) if need[2] else None
-    dB = Q2.new_empty((heads, handle.nnz)) if need_b else None
-    rp, ci, va = handle._keep
-    for h in range(heads):
-        ck, cv = slice(h * k, (h + 1) * k), slice(h * dv, (h + 1) * dv)
-        if B2 is None:
-            api.attention_backward(handle.h, handle.m, rp, ci, va, Q2[:, ck], K2[:, ck], V2[:, cv], G2[:, cv],
-                                   None if dQ is None else dQ[:, ck], None if dK is None else dK[:, ck], None if dV is None else dV[:, cv], scale)
-        else:   # one head on its column slices and on its plane of the bias and of dB
-            api.attention_bias_backward(handle.h, handle.m, rp, ci, va, 1, Q2[:, ck], K2[:, ck], V2[:, cv], B2 if B2.dim() == 1 else B2[h], G2[:, cv],
-                                        None if dQ is None else dQ[:, ck], None if dK is None else dK[:, ck], None if dV is None else dV[:, cv],
-                                        None if dB is None else dB[h], scale)
-    return dQ, dK, dV, _bias_grad(dB, B2)
-
-
-class _AttentionGqa(torch.autograd.Function):
-    """Handle.attention_gqa forward (kv_heads K / V heads for `heads` query heads); the backward pass is ONE Handle.attention_gqa_backward call
-    (fused), or one single-head backward per query head on its group's K / V slices, dK and dV of a group accumulated in torch in ascending
-    head -- the first head assigned, the others added: the fused call's chain, so both modes give the same bits.  K and V are saved at their
-    own (narrow) width; the handle's values are never touched"""
-
-    @staticmethod
-    def forward(ctx, handle, Q, K, V, heads, kv_heads, scale, fused=False, bias=None):
-        Q2, K2, V2 = _block(Q.detach(), Q.shape[1]), _block(K.detach(), K.shape[1]), _block(V.detach(), V.shape[1])
-        B2 = _bias_planes(bias)
-        _on_current_stream(handle)
-        O = handle.attention_gqa(Q2, K2, V2, heads, kv_heads, B2, scale)
-        ctx.handle, ctx.heads, ctx.kv_heads, ctx.scale, ctx.fused = handle, heads, kv_heads, scale, fused
-        ctx.save_for_backward(Q2, K2, V2, B2)   # nothing nnz-sized but the caller's own bias
-        return O
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, G):
-        Q2, K2, V2, B2 = ctx.saved_tensors
-        need = tuple(bool(x) for x in ctx.needs_input_grad[1:4])
-        dQ, dK, dV, dB = _attention_gqa_backward(ctx.handle, ctx.heads, ctx.kv_heads, ctx.scale, ctx.fused, Q2, K2, V2, B2, G, need,
-                                                 B2 is not None and bool(ctx.needs_input_grad[8]))
-        return None, dQ, dK, dV, None, None, None, None, dB
-
-
-def _attention_gqa_backward(handle, heads, kv_heads, scale, fused, Q2, K2, V2, B2, G, need, need_b):
-    """-> (dQ, dK, dV, dB) of attention_heads() with kv_heads: one Handle.attention_gqa_backward call (fused), or one single-head backward per query
-    head on its group's K / V slices, dK and dV of a group accumulated in torch in ascending head"""
-    from . import api
-    if not (any(need) or need_b):
-        return None, None, None, None
-    if handle.nnz == 0:
-        return _zero_grads(Q2, K2, V2, B2, need, need_b)
-    _on_current_stream(handle)
-    G2 = _block(G, G.shape[1])
-    if fused:   # every head in one call
-        dQ, dK, dV, dB = handle.attention_gqa_backward(Q2, K2, V2, B2, G2, heads, kv_heads, scale, need=(*need, need_b))
-        return dQ, dK, dV, _bias_grad(dB, B2)
+def _per_head_backward(handle, heads, kv_heads, acc, call, Q2, K2, V2, B2, G2, need, need_b):
+    """-> (dQ, dK, dV, dB) from one single-head backward per query head: call(Q, K, V, B, G, dQ, dK, dV, dB) on head h's column slices -- K and V
+    those of its group, h // (heads // kv_heads) -- and on its plane of the bias and of dB, written into the slices of full-width gradients.
+    dK and dV of a group are its heads' terms added in torch in ascending head, in the dtype `acc` -- the first assigned, the others += -- and
+    brought to Q2's dtype once at the end: the fused calls' chain and their one rounding, so both modes give the same bits."""
     gs, k, dv = heads // kv_heads, Q2.shape[1] // heads, V2.shape[1] // kv_heads
     dQ = torch.empty_like(Q2, memory_format=torch.contiguous_format) if need[0] else None
-    dK = torch.empty_like(K2, memory_format=torch.contiguous_format) if need[1] else None
-    dV = torch.empty_like(V2, memory_format=torch.contiguous_format) if need[2] else None
-    dB = Q2.new_empty((heads, handle.nnz)) if need_b else None
-    tK = Q2.new_empty((handle.n, k)) if need[1] and gs > 1 else None   # one head's term of dK / dV: what the group's later heads add
-    tV = Q2.new_empty((handle.n, dv)) if need[2] and gs > 1 else None
-    rp, ci, va = handle._keep
+    dK = torch.empty(K2.shape, dtype=acc, device=K2.device) if need[1] else None
+    dV = torch.empty(V2.shape, dtype=acc, device=V2.device) if need[2] else None
+    dB = B2.new_empty((heads, handle.nnz)) if need_b else None   # of the bias' dtype: the handle's
+    tK = torch.empty((handle.n, k), dtype=acc, device=K2.device) if need[1] and gs > 1 else None   # one head's term of dK / dV: what the group's later heads add
+    tV = torch.empty((handle.n, dv), dtype=acc, device=V2.device) if need[2] and gs > 1 else None
     for h in range(heads):
         g, first = h // gs, h % gs == 0
         cq, co, ck, cv = slice(h * k, (h + 1) * k), slice(h * dv, (h + 1) * dv), slice(g * k, (g + 1) * k), slice(g * dv, (g + 1) * dv)
         oK = None if dK is None else (dK[:, ck] if first else tK)
         oV = None if dV is None else (dV[:, cv] if first else tV)
-        api.attention_bias_backward(handle.h, handle.m, rp, ci, va, 1, Q2[:, cq], K2[:, ck], V2[:, cv], None if B2 is None else (B2 if B2.dim() == 1 else B2[h]),
-                                    G2[:, co], None if dQ is None else dQ[:, cq], oK, oV, None if dB is None else dB[h], scale)
+        call(Q2[:, cq], K2[:, ck], V2[:, cv], None if B2 is None else (B2 if B2.dim() == 1 else B2[h]), G2[:, co],
+             None if dQ is None else dQ[:, cq], oK, oV, None if dB is None else dB[h])
         if not first:   # (..(first + second) + ..) + this one: plain additions in ascending head
             if dK is not None:
                 dK[:, ck] += tK
             if dV is not None:
                 dV[:, cv] += tV
-    return dQ, dK, dV, _bias_grad(dB, B2)
-
-
-def _attention_backward_16(handle, heads, kv_heads, scale, fused, Q2, K2, V2, B2, G, need, need_b):
-    """-> (dQ, dK, dV, dB) on float16 / bfloat16 Q2, K2, V2 and G without a float32 copy of any of them (Handle.attention_gqa_backward_16): ONE
-    call with 16-bit gradients (fused), or one call per query head on 16-bit column slices.  Per head, a group's dK and dV (kv_heads < heads) are
-    that head's float32 terms added in torch in ascending head -- the first assigned, the others += -- and rounded once at the end: the fused
-    call's chain and its one rounding, so both modes give float32_gradient.to(dtype) bit for bit.  dB is float32."""
-    from . import api
-    if not (any(need) or need_b):
-        return None, None, None, None
-    if handle.nnz == 0:
-        return _zero_grads(Q2, K2, V2, B2, need, need_b)
-    _on_current_stream(handle)
-    G2 = _block(G.to(Q2.dtype), G.shape[1])
-    if fused:   # every head in one call
-        dQ, dK, dV, dB = handle.attention_gqa_backward_16(Q2, K2, V2, B2, G2, heads, kv_heads, scale, need=(*need, need_b))
-        return dQ, dK, dV, _bias_grad(dB, B2)
-    gs, k, dv = heads // kv_heads, Q2.shape[1] // heads, V2.shape[1] // kv_heads
-    acc = Q2.dtype if gs == 1 else torch.float32   # a group's sums are made in float32 and rounded once
-    dQ = torch.empty_like(Q2, memory_format=torch.contiguous_format) if need[0] else None
-    dK = torch.empty(K2.shape, dtype=acc, device=K2.device) if need[1] else None
-    dV = torch.empty(V2.shape, dtype=acc, device=V2.device) if need[2] else None
-    dB = torch.empty((heads, handle.nnz), dtype=torch.float32, device=Q2.device) if need_b else None
-    tK = torch.empty((handle.n, k), dtype=acc, device=K2.device) if need[1] and gs > 1 else None   # one head's term of dK / dV: what the group's later heads add
-    tV = torch.empty((handle.n, dv), dtype=acc, device=V2.device) if need[2] and gs > 1 else None
-    rp, ci, va = handle._keep
-    for h in range(heads):
-        g, first = h // gs, h % gs == 0
-        cq, co, ck, cv = slice(h * k, (h + 1) * k), slice(h * dv, (h + 1) * dv), slice(g * k, (g + 1) * k), slice(g * dv, (g + 1) * dv)
-        oK = None if dK is None else (dK[:, ck] if first else tK)
-        oV = None if dV is None else (dV[:, cv] if first else tV)
-        api.attention_gqa_backward_16(handle.h, handle.m, rp, ci, va, 1, 1, Q2[:, cq], K2[:, ck], V2[:, cv], None if B2 is None else (B2 if B2.dim() == 1 else B2[h]),
-                                      G2[:, co], None, None, None if dQ is None else dQ[:, cq], oK, oV, None if dB is None else dB[h], scale)
-        if not first:   # (..(first + second) + ..) + this one: plain float32 additions in ascending head
-            if dK is not None:
-                dK[:, ck] += tK
-            if dV is not None:
-                dV[:, cv] += tV
-    if gs > 1:
+    if acc != Q2.dtype:
         dK, dV = (None if dK is None else dK.to(Q2.dtype)), (None if dV is None else dV.to(Q2.dtype))
     return dQ, dK, dV, _bias_grad(dB, B2)
 
 
-class _Attention16(torch.autograd.Function):
-    """float16 / bfloat16 Q, K and V on a float32 handle.  Forward: ONE Handle.attention_gqa_lse_16 call with O in that dtype (no L).  Backward, in
-    the `backward=` mode asked for: "fused" is ONE Handle.attention_gqa_backward_16 call with 16-bit gradients and "per_head" one such call per head
-    on 16-bit column slices (_attention_backward_16) -- no float32 copy of Q, K, V or G is made; "composed" (attention() only) widens Q, K, V and G
-    and runs _attention_backward_composed, its gradients rounded with .to(dtype).  Every gradient is the float32 gradient .to(dtype), the bias
-    gradient stays float32.  heads None: attention(); kv_heads None: as many K / V heads as query heads"""
+def _attention_backward(handle, heads, kv_heads, scale, mode, Q2, K2, V2, B2, G, need, need_b):
+    """-> (dQ, dK, dV, dB) of attention() (heads None) and attention_heads() in the `backward=` mode asked for, only for the gradients asked for.
+    "composed": the existing operations composed (_attention_backward_composed), in float32 on widened copies of 16-bit tensors, the gradients
+    rounded with .to(dtype).  "fused": ONE call of the Handle method of the forward's rung.  "per_head": one single-head call per head
+    (_per_head_backward) -- spmv_hip_attention_backward without a bias or kv_heads, else spmv_hip_attention_bias_backward with heads = 1; on
+    16-bit tensors spmv_hip_attention_gqa_backward_16 with 1, 1, a group's terms asked for in float32.  No mode touches the handle's values but
+    "composed", which puts them back; 16-bit tensors are read as they are, the bias gradient stays float32."""
+    from . import api
+    if not (any(need) or need_b):
+        return None, None, None, None
+    half = Q2.dtype in _HALF
+    if mode == "composed":
+        if not half:
+            return _attention_backward_composed(handle, scale, Q2, K2, V2, B2, G, need, need_b)
+        out = _attention_backward_composed(handle, scale, Q2.float(), K2.float(), V2.float(), B2, G.float(), need, need_b)
+        return (*(None if g is None else g.to(Q2.dtype) for g in out[:3]), out[3])
+    if (half or heads is not None) and handle.nnz == 0:   # attention(backward="fused") in the handle's dtype has the library write its zeros
+        return _zero_grads(Q2, K2, V2, B2, need, need_b)
+    _on_current_stream(handle)
+    G2 = _block(G.to(Q2.dtype), G.shape[1])   # dL/dO arrives in O's dtype, which is Q's: a cast only where someone changed it
+    h = 1 if heads is None else heads
+    kv = h if kv_heads is None else kv_heads
+    if mode == "fused":   # every head in one call
+        if half:
+            grads = handle.attention_gqa_backward_16(Q2, K2, V2, B2, G2, h, kv, scale, need=(*need, need_b))
+        elif kv_heads is not None:
+            grads = handle.attention_gqa_backward(Q2, K2, V2, B2, G2, h, kv, scale, need=(*need, need_b))
+        elif B2 is not None:
+            grads = handle.attention_bias_backward(Q2, K2, V2, B2, G2, h, scale, need=(*need, need_b))
+        elif heads is None:
+            grads = (*handle.attention_backward(Q2, K2, V2, G2, scale, need=need), None)
+        else:
+            grads = (*handle.attention_heads_backward(Q2, K2, V2, G2, h, scale, need=need), None)
+        return (*grads[:3], _bias_grad(grads[3], B2))
+    csr = (handle.h, handle.m, *handle._keep)
+    if half:   # a group's sums are made in float32 and rounded once
+        return _per_head_backward(handle, h, kv, Q2.dtype if h == kv else torch.float32, lambda q, k, v, b, g, dq, dk, dv, db: api.attention_gqa_backward_16(
+            *csr, 1, 1, q, k, v, b, g, None, None, dq, dk, dv, db, scale), Q2, K2, V2, B2, G2, need, need_b)
+    if kv_heads is None and B2 is None:
+        return _per_head_backward(handle, h, kv, Q2.dtype, lambda q, k, v, b, g, dq, dk, dv, db: api.attention_backward(
+            *csr, q, k, v, g, dq, dk, dv, scale), Q2, K2, V2, B2, G2, need, need_b)
+    return _per_head_backward(handle, h, kv, Q2.dtype, lambda q, k, v, b, g, dq, dk, dv, db: api.attention_bias_backward(
+        *csr, 1, q, k, v, b, g, dq, dk, dv, db, scale), Q2, K2, V2, B2, G2, need, need_b)
+
+
+class _Attention(torch.autograd.Function):
+    """attention() (heads None) and attention_heads() in every `backward=` mode, in the handle's dtype and on float16 / bfloat16 Q, K and V.
+    Forward: ONE call of the narrowest rung that serves -- Handle.attention, attention_heads, attention_bias with a bias, attention_gqa with
+    kv_heads; Handle.attention_gqa_lse_16 with O in their dtype (no L) for 16-bit tensors.  It saves Q, K and V -- K and V at their own, narrow,
+    width -- and a reference to the bias: nothing nnz-sized but the caller's own.  Backward: _attention_backward"""
 
     @staticmethod
     def forward(ctx, handle, Q, K, V, heads, kv_heads, scale, mode, bias=None):
@@ -533,7 +388,14 @@ class _Attention16(torch.autograd.Function):
         B2 = _bias_planes(bias)
         _on_current_stream(handle)
         h = 1 if heads is None else heads
-        O, _ = handle.attention_gqa_lse_16(Q2, K2, V2, h, h if kv_heads is None else kv_heads, B2, scale, want_l=False)
+        if Q2.dtype in _HALF:
+            O, _ = handle.attention_gqa_lse_16(Q2, K2, V2, h, h if kv_heads is None else kv_heads, B2, scale, want_l=False)
+        elif kv_heads is not None:
+            O = handle.attention_gqa(Q2, K2, V2, heads, kv_heads, B2, scale)
+        elif B2 is not None:
+            O = handle.attention_bias(Q2, K2, V2, h, B2, scale)
+        else:
+            O = handle.attention(Q2, K2, V2, scale) if heads is None else handle.attention_heads(Q2, K2, V2, heads, scale)
         ctx.handle, ctx.heads, ctx.kv_heads, ctx.scale, ctx.mode = handle, heads, kv_heads, scale, mode
         ctx.save_for_backward(Q2, K2, V2, B2)
         return O
@@ -541,19 +403,15 @@ class _Attention16(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, G):
-        handle, heads, kv_heads, scale, mode = ctx.handle, ctx.heads, ctx.kv_heads, ctx.scale, ctx.mode
         Q2, K2, V2, B2 = ctx.saved_tensors
         need = tuple(bool(x) for x in ctx.needs_input_grad[1:4])
-        need_b = B2 is not None and bool(ctx.needs_input_grad[8])
-        if not (any(need) or need_b):
-            return (None,) * 9
-        if mode == "composed":   # attention() only: the composition runs in float32, on widened copies
-            out = _attention_backward_composed(handle, scale, Q2.float(), K2.float(), V2.float(), B2, G.float(), need, need_b)
-            dQ, dK, dV = (None if g is None else g.to(Q2.dtype) for g in out[:3])
-            return None, dQ, dK, dV, None, None, None, None, out[3]
-        h = 1 if heads is None else heads
-        dQ, dK, dV, dB = _attention_backward_16(handle, h, h if kv_heads is None else kv_heads, scale, mode == "fused", Q2, K2, V2, B2, G, need, need_b)
+        dQ, dK, dV, dB = _attention_backward(ctx.handle, ctx.heads, ctx.kv_heads, ctx.scale, ctx.mode, Q2, K2, V2, B2, G, need,
+                                             B2 is not None and bool(ctx.needs_input_grad[8]))
         return None, dQ, dK, dV, None, None, None, None, dB
+
+
+class _AttentionHeads(_Attention):
+    """_Attention under the name that attention_heads() without kv_heads has in a graph: its grad_fn tells that kv_heads=None took no new path"""
 
 
 def _check_bias(bias, handle, heads):
@@ -619,9 +477,7 @@ def attention_heads(handle, Q, K, V, heads, scale=None, backward="per_head", *, 
             raise ValueError(f"{Q.shape[1]} columns of Q, {K.shape[1]} of K and {V.shape[1]} of V are not {heads} query heads over {kv_heads} K / V heads of equal width")
         _check_bias(bias, handle, heads)
         scale = 1.0 / math.sqrt(Q.shape[1] // heads) if scale is None else float(scale)
-        if dtype in _HALF:
-            return _Attention16.apply(handle, Q, K, V, heads, kv_heads, scale, backward, bias)
-        return _AttentionGqa.apply(handle, Q, K, V, heads, kv_heads, scale, backward == "fused", bias)
+        return _Attention.apply(handle, Q, K, V, heads, kv_heads, scale, backward, bias)
     if Q.dim() != 2 or K.dim() != 2 or V.dim() != 2 or Q.shape[0] != handle.m or K.shape[0] != handle.n or V.shape[0] != handle.n or \
             Q.shape[1] != K.shape[1] or Q.shape[1] < 1 or V.shape[1] < 1:
         raise ValueError(f"Q must be ({handle.m}, heads * k), K ({handle.n}, heads * k) and V ({handle.n}, heads * dv) with k, dv >= 1, not {tuple(Q.shape)}, {tuple(K.shape)} and {tuple(V.shape)}")
@@ -629,9 +485,7 @@ def attention_heads(handle, Q, K, V, heads, scale=None, backward="per_head", *, 
         raise ValueError(f"{Q.shape[1]} columns of Q / K and {V.shape[1]} of V are not {heads} heads of equal width")
     _check_bias(bias, handle, heads)
     scale = 1.0 / math.sqrt(Q.shape[1] // heads) if scale is None else float(scale)   # Handle.attention_heads' default, to the bit
-    if dtype in _HALF:
-        return _Attention16.apply(handle, Q, K, V, heads, None, scale, backward, bias)
-    return _AttentionHeads.apply(handle, Q, K, V, heads, scale, backward == "fused", bias)
+    return _AttentionHeads.apply(handle, Q, K, V, heads, None, scale, backward, bias)
 
 
 def attention(handle, Q, K, V, scale=None, backward="composed", *, bias=None):
@@ -673,9 +527,7 @@ def attention(handle, Q, K, V, scale=None, backward="composed", *, bias=None):
         raise ValueError(f"Q must be ({handle.m}, k), K ({handle.n}, k) and V ({handle.n}, dv) with k, dv >= 1, not {tuple(Q.shape)}, {tuple(K.shape)} and {tuple(V.shape)}")
     _check_bias(bias, handle, 1)
     scale = 1.0 / math.sqrt(Q.shape[1]) if scale is None else float(scale)   # Handle.attention's default, to the bit
-    if dtype in _HALF:
-        return _Attention16.apply(handle, Q, K, V, None, None, scale, backward, bias)
-    return (_AttentionFused if backward == "fused" else _Attention).apply(handle, Q, K, V, scale, bias)
+    return _Attention.apply(handle, Q, K, V, None, None, scale, backward, bias)
 
 
 class _AttentionParts(torch.autograd.Function):
