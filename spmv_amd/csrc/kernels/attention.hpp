@@ -41,7 +41,7 @@
 // untouched.  LSE implies BIAS, with bias == nullptr allowed there (a wave-uniform test); the instantiations without LSE do not look at lse and
 // ldl and are the code from before.
 //
-// 16-bit operands (spmv_hip_attention_gqa_lse_16; the instantiations with SI or SO other than T, launched from spmv_attention_16.hip): Q, K and V
+// 16-bit operands (spmv_hip_attention_gqa_lse_16; the instantiations with SI or SO other than T, launched from spmv_attention.hip's 16-bit parts): Q, K and V
 // are fp16 or bf16 in memory (SI) and O is float or that type (SO) -- kernels/storage16.hpp.  The blocks widen what they load and round what they
 // store; the parked scores, s_p, the bias, L, scale and every arithmetic step stay float, and the lane mapping stays float's -- W = V = 4 columns
 // per lane, CW = panel_group_width<float>(k), lgv = panel_group_lg<float>(dv) --, because it fixes the summation order: O (before the one
@@ -74,17 +74,20 @@ struct AttentionArgs {
     long long ldq = 0, ldk = 0, ldv = 0, ldo = 0;
     double scale = 1.0;
     bool vec = false; // q, kk, v, o, their leading dimensions and every head's first column allow 16-byte accesses (16-bit operands: 8-byte)
-    int io_type = 0, o_type = 0; // SPMV_HIP_T_*: the element type of q, kk, v and of o; 0 = the handle's (attention_launch), else attention_16_launch
+    int io_type = 0, o_type = 0; // SPMV_HIP_T_*: the element type of q, kk, v and of o; 0 = the handle's, else F16 or BF16 (float arithmetic; o_type 0 or io_type)
     const void *bias = nullptr; // nullptr: no bias; else planes of nnz elements in CSR order, head hd's at bias + hd * ldb (ldb = 0: one plane shared)
     long long ldb = 0;
     void *lse = nullptr; // nullptr: not wanted; else `heads` planes of m elements, head hd's row i at lse + hd * ldl + i
     long long ldl = 0;
 };
 
-// spmv_attention.hip: the launches of one call on `stream`
+// spmv_attention.hip: the launches of one call on `stream`.  It routes on io_type to the part of that file -- one per element type of Q, K and V,
+// compiled side by side -- that holds the instantiations
 hipError_t attention_launch(const AttentionArgs &a, bool f64, hipStream_t stream);
-// spmv_attention_16.hip: the same with io_type = F16 or BF16 (float arithmetic; o_type 0 or io_type)
-hipError_t attention_16_launch(const AttentionArgs &a, hipStream_t stream);
+template <int IO> hipError_t attention_launch_part(const AttentionArgs &a, bool f64, hipStream_t stream);
+template <> hipError_t attention_launch_part<0>(const AttentionArgs &a, bool f64, hipStream_t stream);
+template <> hipError_t attention_launch_part<1>(const AttentionArgs &a, bool f64, hipStream_t stream);
+template <> hipError_t attention_launch_part<2>(const AttentionArgs &a, bool f64, hipStream_t stream);
 
 // lengths of the listed long rows (the shim turns them into long_off)
 static __global__ __launch_bounds__(kBlock) void attention_long_len_kernel(int nlong, const int *__restrict__ longs, const int *__restrict__ rowptr, int *__restrict__ len)

@@ -53,7 +53,7 @@
 // before; the column kernels are not touched.  The instantiations without STATS do not look at o and lse and are the code from before.
 //
 // 16-bit operands (spmv_hip_attention_gqa_backward_16; the instantiations with a storage type other than T, launched from
-// spmv_attention_backward_16.hip): Q, K, V and G are fp16 or bf16 in memory (SI), dQ is float or that type (SQ, the row kernels) and dK / dV are
+// spmv_attention_backward.hip's 16-bit parts): Q, K, V and G are fp16 or bf16 in memory (SI), dQ is float or that type (SQ, the row kernels) and dK / dV are
 // float or that type (SO, the column kernels) -- kernels/storage16.hpp.  The blocks widen what they load and round what they store; attb_p /
 // attb_ds, s_p / s_d, the bias, dB, O, L, scale and every arithmetic step stay float, and the lane mapping stays float's (4 columns per lane, an
 // 8-byte segment of a 16-bit operand), so a float output has the bits of the float kernels on the widened operands and a 16-bit one is that value
@@ -95,7 +95,7 @@ struct AttentionBwdArgs {
     long long ldb = 0, lddb = 0;
     const void *o = nullptr, *lse = nullptr; // both set: the STATS row pass from the final O (m x heads * dv) and L (head hd's row i at lse + hd * ldl + i)
     long long ldo = 0, ldl = 0;
-    // attention_backward_16_launch only.  io_type (SPMV_HIP_T_F16 / _BF16): the element type of q, kk, v, g; dq_type / dkv_type: 0 -- dq / dk and
+    // 16-bit operands only (else all 0 and nullptr).  io_type (SPMV_HIP_T_F16 / _BF16): the element type of q, kk, v, g; dq_type / dkv_type: 0 -- dq / dk and
     // dvo are float --, or io_type.  gs > 1 with 16-bit dK / dV: dk and dvo are the handle's float arrays (dkv_type 0, lddk = kv_heads * k,
     // lddv = kv_heads * dv) and nar_dk / nar_dv the caller's 16-bit ones, rounded into after the last round (nullptr: not wanted)
     int io_type = 0, dq_type = 0, dkv_type = 0;
@@ -104,10 +104,13 @@ struct AttentionBwdArgs {
     int n = 0, kv_heads = 1; // the rows and K / V heads of dk / dvo (the narrowing)
 };
 
-// spmv_attention_backward.hip: the launches of one call on `stream`, ceil(heads / hg) rounds of a row pass and a column pass
+// spmv_attention_backward.hip: the launches of one call on `stream`, ceil(heads / hg) rounds of a row pass and a column pass, and with 16-bit
+// operands the narrowing of grouped 16-bit dK / dV.  It routes on io_type to the part of that file that holds the instantiations
 hipError_t attention_backward_launch(const AttentionBwdArgs &a, bool f64, hipStream_t stream);
-// spmv_attention_backward_16.hip: the same with io_type = F16 or BF16 (float arithmetic), and the narrowing of grouped 16-bit dK / dV
-hipError_t attention_backward_16_launch(const AttentionBwdArgs &a, hipStream_t stream);
+template <int IO> hipError_t attention_backward_launch_part(const AttentionBwdArgs &a, bool f64, hipStream_t stream);
+template <> hipError_t attention_backward_launch_part<0>(const AttentionBwdArgs &a, bool f64, hipStream_t stream);
+template <> hipError_t attention_backward_launch_part<1>(const AttentionBwdArgs &a, bool f64, hipStream_t stream);
+template <> hipError_t attention_backward_launch_part<2>(const AttentionBwdArgs &a, bool f64, hipStream_t stream);
 
 // att_tile_scores without the scaling, for a lane group width known at run time (wave-uniform): dP's dots, sddmm's order for dv columns.
 // The multiplication by one changes no bit.  S, S2: the storage types of g and of v (att_tile_scores).

@@ -2,8 +2,9 @@
 // spmv_shim_attention, and its timer serve every public variant -- one head, `heads` heads side by side in the rows, an additive bias per head and
 // entry, fewer K / V heads than query heads, the rows' log-sum-exps, 16-bit operands: spmv_api.c passes them all as one spmv_attention_call
 // (spmv_shim.h), a variant without a feature with that feature's neutral value.  The merge of two partial results is here too.  The
-// kernels are kernels/attention.hpp, launched from their own translation units (spmv_attention.hip, attention_launch; spmv_attention_16.hip); the
-// tables are spmm's batch table and long-row list (spmm_plan).  This side adds what the long rows need: where each one parks its scores.
+// kernels are kernels/attention.hpp, launched from their own translation unit (spmv_attention.hip, attention_launch: compiled in one part per
+// element type of Q, K and V); the tables are spmm's batch table and long-row list (spmm_plan).  This side adds what the long rows need: where
+// each one parks its scores.
 #pragma once
 
 // long_off[i] = first element of long row i of spmm's list in att_park (sum of the long rows' lengths elements): built once per resident matrix
@@ -67,8 +68,8 @@ static bool attention_types_ok(const spmv_dev *d, int io_type, int out1, int out
            (!d || d->vsize == sizeof(float));
 }
 
-// The operands: spmv_attention_call (spmv_shim.h).  With lse NULL the launches are those without a log-sum-exp.  io_type HANDLE: the kernels of
-// spmv_attention.hip; F16 or BF16: a host operand is staged at its own element size, and the kernels are those of spmv_attention_16.hip.
+// The operands: spmv_attention_call (spmv_shim.h).  With lse NULL the launches are those without a log-sum-exp.  io_type F16 or BF16: a host
+// operand is staged at its own element size; attention_launch finds the kernels of every io_type.
 extern "C" int spmv_shim_attention(spmv_dev *d, const spmv_attention_call *c)
 {
     const int heads = c->heads, kv_heads = c->kv_heads, k = c->k, dv = c->dv, io_type = c->io_type, o_type = c->o_type;
@@ -124,16 +125,10 @@ extern "C" int spmv_shim_attention(spmv_dev *d, const spmv_attention_call *c)
         (a.bias && (rc = attention_stage_bias(stg, d->stage[STAGE_ATT_B], a.bias, a.ldb, heads))) ||
         (a.lse && (rc = stg.out(d->stage[STAGE_ATT_L], a.lse, a.ldl, (size_t) heads, d->m)))) return rc; // every row of every plane is written
     // the access width changes no bit (kernels/attention.hpp): chosen per call from what the addresses allow -- with more than one head, every
-    // head's first column has to be 16-byte aligned as well.  A lane's segment of a 16-bit operand is 8 bytes: 8-byte accesses there
-    if (io_type == SPMV_HIP_T_HANDLE)
-        a.vec = wide_ok(a.q, a.ldq, s) && wide_ok(a.kk, a.ldk, s) && wide_ok(a.v, a.ldv, s) && wide_ok(a.o, a.ldo, s) &&
-                (heads == 1 || (((size_t) k * s) % 16 == 0 && ((size_t) dv * s) % 16 == 0));
-    else {
-        const size_t wo = 4 * so; // O's segment: 4 elements of its own type
-        a.vec = wide_ok_bytes(a.q, a.ldq, si, 8) && wide_ok_bytes(a.kk, a.ldk, si, 8) && wide_ok_bytes(a.v, a.ldv, si, 8) && wide_ok_bytes(a.o, a.ldo, so, wo) &&
-                (heads == 1 || (((size_t) k * si) % 8 == 0 && ((size_t) dv * si) % 8 == 0 && ((size_t) dv * so) % wo == 0));
-    }
-    const hipError_t e = io_type == SPMV_HIP_T_HANDLE ? attention_launch(a, s == sizeof(double), d->stream) : attention_16_launch(a, d->stream);
+    // head's first column has to allow whole segments as well (seg_ok, state.hpp: 16 bytes, 8 of a 16-bit operand)
+    a.vec = seg_ok(a.q, a.ldq, si) && seg_ok(a.kk, a.ldk, si) && seg_ok(a.v, a.ldv, si) && seg_ok(a.o, a.ldo, so) &&
+            (heads == 1 || (seg_cols_ok(k, si) && seg_cols_ok(dv, si) && seg_cols_ok(dv, so)));
+    const hipError_t e = attention_launch(a, s == sizeof(double), d->stream);
     if (e != hipSuccess) return fail(SPMV_HIP_E_RUNTIME, "attention: launch: %s", hipGetErrorString(e));
     return stg.finish();
 }

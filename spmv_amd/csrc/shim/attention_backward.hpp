@@ -1,9 +1,9 @@
 // shim/attention_backward.hpp -- part of spmv_shim.hip: dQ, dK, dV and dB of O = softmax_rows(scale * Q K^T on the RESIDENT pattern) V in two
 // passes per round of up to hg heads.  One entry point, spmv_shim_attention_backward, and its timer serve every public variant (one head, heads,
 // bias, GQA, driven by the final O and log-sum-exp, 16-bit operands): spmv_api.c passes them all as one spmv_attention_backward_call (spmv_shim.h).
-// The kernels are kernels/attention_backward.hpp, launched from their own translation units (spmv_attention_backward.hip,
-// attention_backward_launch; spmv_attention_backward_16.hip); the tables are spmm's batch table and long-row list of the resident matrix
-// and, when dK or dV is wanted, those of the attached transpose.  This side adds the two nnz-sized arrays the passes share.
+// The kernels are kernels/attention_backward.hpp, launched from their own translation unit (spmv_attention_backward.hip,
+// attention_backward_launch: compiled in one part per element type of Q, K, V and G); the tables are spmm's batch table and long-row list of the
+// resident matrix and, when dK or dV is wanted, those of the attached transpose.  This side adds the two nnz-sized arrays the passes share.
 #pragma once
 
 // attb_p / attb_ds: `planes` planes of nnz elements each, plane g one head's P / dS in CSR order.  Allocated at the first call that needs them,
@@ -53,10 +53,9 @@ static int attention_backward_group(const spmv_dev *d, int heads, int limit, int
 // The operands: spmv_attention_backward_call (spmv_shim.h).  When dk or dvo is wanted the transpose must be attached with its column indices
 // resident (spmv_shim_transpose, spmv_shim_transpose_restore_columns); its values are not read.  db is written by the row pass alone: with only db
 // wanted the column pass does not run and the transpose is not looked at.  The planes, bias and db are per QUERY head.
-// io_type HANDLE: the kernels of spmv_attention_backward.hip.  F16 or BF16: a host operand is staged at its own element size and the kernels are
-// those of spmv_attention_backward_16.hip; with kv_heads < heads a 16-bit dk / dvo is summed in the handle's float arrays attb_nk / attb_nv
-// (n x kv_heads * k, n x kv_heads * dv; allocated at the first such call, grown when a call needs more, counted in device_bytes) and rounded once
-// into the caller's arrays by the call's last launch.
+// io_type F16 or BF16: a host operand is staged at its own element size (attention_backward_launch finds the kernels of every io_type); with
+// kv_heads < heads a 16-bit dk / dvo is summed in the handle's float arrays attb_nk / attb_nv (n x kv_heads * k, n x kv_heads * dv; allocated at
+// the first such call, grown when a call needs more, counted in device_bytes) and rounded once into the caller's arrays by the call's last launch.
 extern "C" int spmv_shim_attention_backward(spmv_dev *d, const spmv_attention_backward_call *c)
 {
     const int heads = c->heads, kv_heads = c->kv_heads, k = c->k, dv = c->dv, io_type = c->io_type, dq_type = c->dq_type, dkv_type = c->dkv_type;
@@ -149,35 +148,28 @@ extern "C" int spmv_shim_attention_backward(spmv_dev *d, const spmv_attention_ba
         (a.bias && (rc = attention_stage_bias(stg, d->stage[STAGE_ATT_B], a.bias, a.ldb, heads))) ||
         (a.db && (rc = stg.out(d->stage[STAGE_ATT_DB], a.db, a.lddb, (size_t) heads, (int) d->nnz))) || // every entry of every plane is written
         (a.o && ((rc = stg.in(d->stage[STAGE_ATTB_O], a.o, a.ldo, (size_t) d->m, (int) wv)) || (rc = stg.in(d->stage[STAGE_ATTB_L], a.lse, a.ldl, (size_t) heads, d->m))))) return rc;
-    // the access width changes no bit (kernels/attention_backward.hpp): chosen per call from what the addresses allow -- with more than one head,
-    // every head's first column has to be 16-byte aligned as well
-    if (io_type == SPMV_HIP_T_HANDLE)
-        a.vec = wide_ok(a.q, a.ldq, s) && wide_ok(a.kk, a.ldk, s) && wide_ok(a.v, a.ldv, s) && wide_ok(a.g, a.ldg, s) && (!a.dq || wide_ok(a.dq, a.lddq, s)) &&
-                (!a.dk || wide_ok(a.dk, a.lddk, s)) && (!a.dvo || wide_ok(a.dvo, a.lddv, s)) && (!a.o || wide_ok(a.o, a.ldo, s)) &&
-                (heads == 1 || (((size_t) k * s) % 16 == 0 && ((size_t) dv * s) % 16 == 0));
-    else {
-        // a 16-bit dK / dV over groups of heads is never a partial sum: the column pass adds in the handle's float arrays, the narrowing rounds once
-        if (a.gs > 1 && dkv_type != SPMV_HIP_T_HANDLE && (a.dk || a.dvo)) {
-            if (a.dk) {
-                if ((rc = stg.reserve(d->attb_nk, sizeof(float) * (size_t) d->n * (size_t) gk))) return rc;
-                a.nar_dk = a.dk; a.nar_lddk = a.lddk;
-                a.dk = d->attb_nk.p; a.lddk = gk;
-            }
-            if (a.dvo) {
-                if ((rc = stg.reserve(d->attb_nv, sizeof(float) * (size_t) d->n * (size_t) gv))) return rc;
-                a.nar_dv = a.dvo; a.nar_lddv = a.lddv;
-                a.dvo = d->attb_nv.p; a.lddv = gv;
-            }
-            a.dkv_type = SPMV_HIP_T_HANDLE;
+    // a 16-bit dK / dV over groups of heads is never a partial sum: the column pass adds in the handle's float arrays, the narrowing rounds once
+    if (a.gs > 1 && dkv_type != SPMV_HIP_T_HANDLE && (a.dk || a.dvo)) {
+        if (a.dk) {
+            if ((rc = stg.reserve(d->attb_nk, sizeof(float) * (size_t) d->n * (size_t) gk))) return rc;
+            a.nar_dk = a.dk; a.nar_lddk = a.lddk;
+            a.dk = d->attb_nk.p; a.lddk = gk;
         }
-        // a lane's segment is 4 elements of the operand's own type: 8 bytes of a 16-bit operand, 16 of a float one; with more than one head every
-        // head's first column has to allow it as well (k and dv multiples of 4 serve both sizes)
-        auto seg_ok = [](const void *p, long long ld, size_t es) { return wide_ok_bytes(p, ld, es, 4 * es); };
-        const size_t sk = a.dkv_type ? 2 : s;
-        a.vec = seg_ok(a.q, a.ldq, si) && seg_ok(a.kk, a.ldk, si) && seg_ok(a.v, a.ldv, si) && seg_ok(a.g, a.ldg, si) && (!a.dq || seg_ok(a.dq, a.lddq, sq)) &&
-                (!a.dk || seg_ok(a.dk, a.lddk, sk)) && (!a.dvo || seg_ok(a.dvo, a.lddv, sk)) && (!a.o || wide_ok(a.o, a.ldo, s)) && (heads == 1 || (k % 4 == 0 && dv % 4 == 0));
+        if (a.dvo) {
+            if ((rc = stg.reserve(d->attb_nv, sizeof(float) * (size_t) d->n * (size_t) gv))) return rc;
+            a.nar_dv = a.dvo; a.nar_lddv = a.lddv;
+            a.dvo = d->attb_nv.p; a.lddv = gv;
+        }
+        a.dkv_type = SPMV_HIP_T_HANDLE;
     }
-    const hipError_t e = io_type == SPMV_HIP_T_HANDLE ? attention_backward_launch(a, s == sizeof(double), d->stream) : attention_backward_16_launch(a, d->stream);
+    // the access width changes no bit (kernels/attention_backward.hpp): chosen per call from what the addresses allow -- with more than one head,
+    // every head's first column has to allow whole segments as well (seg_ok, state.hpp: 16 bytes, 8 of a 16-bit operand).  A call's element sizes
+    // are s alone, or 2 and 4, which ask the same of a head's width (a multiple of 4): Q's size stands for every operand's there
+    const size_t sk = a.dkv_type ? 2 : s; // dK's and dV's as the kernels write them
+    a.vec = seg_ok(a.q, a.ldq, si) && seg_ok(a.kk, a.ldk, si) && seg_ok(a.v, a.ldv, si) && seg_ok(a.g, a.ldg, si) && (!a.dq || seg_ok(a.dq, a.lddq, sq)) &&
+            (!a.dk || seg_ok(a.dk, a.lddk, sk)) && (!a.dvo || seg_ok(a.dvo, a.lddv, sk)) && (!a.o || seg_ok(a.o, a.ldo, s)) &&
+            (heads == 1 || (seg_cols_ok(k, si) && seg_cols_ok(dv, si)));
+    const hipError_t e = attention_backward_launch(a, s == sizeof(double), d->stream);
     if (e != hipSuccess) return fail(SPMV_HIP_E_RUNTIME, "attention_backward: launch: %s", hipGetErrorString(e));
     return stg.finish();
 }

@@ -480,8 +480,12 @@ struct Stager {
 
 // true if p and the leading dimension ld (elements of s bytes) allow 16-byte accesses to every row
 static bool wide_ok(const void *p, long long ld, size_t s) { return ((uintptr_t) p & 15) == 0 && ((size_t) ld * s) % 16 == 0; }
-// the same for accesses of `bytes` bytes (a power of two): the 8-byte segments of 16-bit operands
-static bool wide_ok_bytes(const void *p, long long ld, size_t s, size_t bytes) { return ((uintptr_t) p & (bytes - 1)) == 0 && ((size_t) ld * s) % bytes == 0; }
+// The attention's operands, whose element size es differs within a call: a lane's segment is 8 bytes of a 2-byte type (4 elements) and 16 bytes
+// otherwise.  seg_ok: p and the leading dimension ld allow whole segments in every row; seg_cols_ok: so does a head's first column, w columns
+// further on
+static size_t seg_bytes(size_t es) { return es == 2 ? 8 : 16; }
+static bool seg_ok(const void *p, long long ld, size_t es) { return ((uintptr_t) p & (seg_bytes(es) - 1)) == 0 && ((size_t) ld * es) % seg_bytes(es) == 0; }
+static bool seg_cols_ok(int w, size_t es) { return ((size_t) w * es) % seg_bytes(es) == 0; }
 
 // Mean ms of `iters` calls of run() (an operation's own entry point on device operands; 0 on success) after `warmup` untimed ones: hipEvents on
 // the handle's stream around every call, the handle asynchronous for the loop only.  ms_out (iters floats, may be NULL) receives the single
