@@ -913,6 +913,65 @@ int spmv_hip_cg_columns(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_
                         const void *Matrix_Val, int k, const void *B, long long ldb, void *X, long long ldx,
                         const spmv_hip_cg_options *opt, spmv_hip_cg_result *res /* k entries */);
 
+/* ---- restarted GMRES on the device: A x = b for a matrix that need not be symmetric -------------
+ * Right-preconditioned GMRES(restart) for a square A (m = n) with an optional diagonal preconditioner; the new Krylov vector is made orthogonal
+ * by classical Gram-Schmidt applied TWICE, unconditionally.  An ITERATION is one inner step: one of the handle's own multiplies -- spmv()'s
+ * schedule and bits -- one new basis vector, seven vector kernels.  Within a cycle the residual estimate never rises, and the only breakdown is
+ * a singular A diag(Dinv).  The coefficients, the rotations and the stop tests are formed on the device; the host enqueues check_every
+ * iterations, then looks at a small state once.
+ * The options, the result, the status values and EVERY rule of spmv_hip_cg above hold word for word: the return value, the synchronous call,
+ * the CSR arguments, host or device B / X / Dinv, use_x0, history (max_iterations + 1 doubles), m = 0, bb = 0, option "reorder", the errors.
+ * What differs:
+ *   - restart < 1 or restart > SPMV_HIP_GMRES_RESTART_MAX is SPMV_HIP_E_ARG as well.
+ *   - Dinv is a RIGHT preconditioner, as for spmv_hip_bicgstab: the residual, rr, the history and the stop test belong to the original system.
+ *   - `iterations` counts the steps whose column is in the returned X.  rr is the recurrence's residual ESTIMATE g_(j+1)^2 of the last step
+ *     applied (the initial <r,r> at 0 iterations), and so is history[k]: within a cycle no residual vector exists.  At every restart the true
+ *     r = B - A x is formed and the next cycle starts from its norm; rr and the history do not show it.
+ *   - status: _BREAKDOWN: the diagonal entry d of the rotated Hessenberg column is exactly 0 -- A diag(Dinv) is singular on the space built so
+ *     far; X is the iterate of the last step before it -- or h_(j+1,j) = 0 (the space is exhausted) while the estimate is above the threshold:
+ *     that step IS applied.  h_(j+1,j) = 0 with the estimate at or below the threshold is _CONVERGED (the lucky case).  _NONFINITE: a NaN or
+ *     infinity in any dot, norm, rotation or coefficient; X is the iterate of the last step before it.  _MAX_ITERATIONS in the middle of a
+ *     cycle: X includes the columns of the unfinished cycle.
+ *   - Workspace, the solver's own: w, z and restart + 1 basis vectors (m elements each), 35 partial arrays of 1024 doubles and the state
+ *     (the Hessenberg columns, the rotations, g, y) in one block of (restart + 3) * roundup(m * sizeof(T), 256) + 35 * 8192 + 10240 bytes,
+ *     allocated at the first call and allocated anew when a later call has a larger restart; the history's device copy in another; freed
+ *     and counted as spmv_hip_cg's.  The other solvers' workspaces are neither shared nor grown.
+ *
+ * The arithmetic contract -- bits, not a tolerance; tests/gmres_cases.py restates it in numpy.  Elements are of the handle's type T.  Every dot
+ * is spmv_hip_cg's dot exactly.  Every scalar is fp64, with every product, sum, quotient and square root a separate operation; the square root
+ * is the correctly rounded one (IEEE 754).  A scalar that multiplies a vector is rounded to T once.  The vector updates are in T, a multiply and
+ * then an add or a subtraction, never an fma.  thresh = max(rtol^2 * bb, atol^2).
+ *   start:   x = 0, r = B (or r = B - A*x0);  rr = <r,r>, bb = <B,B>;  history[0] = rr
+ *            nonfinite(bb, rr) -> NONFINITE;  bb == 0 -> x = 0, rr = 0, CONVERGED;  rr <= thresh -> CONVERGED                    (0 iterations)
+ *   cycle:   beta = sqrt(rr_cycle) (rr_cycle = rr at the start);  g_1 = beta;  v_1 = r * T(1 / beta)
+ *   step j = 1 .. restart of the cycle, iteration k = 1, 2, ... of the call:
+ *            z = Dinv*v_j (z = v_j without Dinv);  w = A*z                         -- the handle's multiply, spmv()'s bits
+ *            c_i = <v_i,w>, i = 1..j (all of the same w);  a_i = T(c_i);  w = w - a_i*v_i by ascending i
+ *            d_i = <v_i,w>, i = 1..j (all of the same w);  e_i = T(d_i);  w = w - e_i*v_i by ascending i;  ww = <w,w>
+ *            h_i = double(a_i) + double(e_i);  hn = sqrt(ww)
+ *            the rotations i = 1..j-1 by ascending i:  (h_i, h_(i+1)) = (c_i*h_i + s_i*h_(i+1),  c_i*h_(i+1) - s_i*h_i), of the old h_i and h_(i+1)
+ *            d = sqrt(h_j*h_j + hn*hn)
+ *            nonfinite(ww, any h_i before or after a rotation, d) -> NONFINITE;  d == 0 -> BREAKDOWN      (step not applied: iterations = k - 1)
+ *            c_j = h_j / d;  s_j = hn / d;  g_(j+1) = -(s_j*g_j);  g_j = c_j*g_j (of the old g_j);  est = g_(j+1)*g_(j+1)
+ *            nonfinite(c_j, s_j, g_j, est) -> NONFINITE                                                    (the same)
+ *            h_j = d;  iterations = k;  rr = history[k] = est                      -- from here on the step is applied
+ *            est <= thresh -> CONVERGED;  hn == 0 -> BREAKDOWN
+ *            v_(j+1) = w * T(1 / hn)
+ *   cycle end, behind step j = restart and when the loop has ended or k = max_iterations, over the n steps of the cycle that were applied:
+ *            R y = g in fp64 with R the rotated columns: rows n .. 1; row i: sum = +0.0, then sum = sum + R_(i,c)*y_c by ascending c > i;
+ *            y_i = (g_i - sum) / R_(i,i) (the unrounded y_c enter the later rows)
+ *            u = T(y_1)*v_1, then u = u + T(y_i)*v_i by ascending i;  x = x + Dinv*u (x = x + u without Dinv)
+ *   restart, behind every FULL cycle (also when k = max_iterations falls on it):
+ *            r = B - A*x (the multiply, then a subtraction in T);  rr_cycle = <r,r>;  nonfinite -> NONFINITE;  rr_cycle == 0 -> CONVERGED
+ *   k == max_iterations without a status -> MAX_ITERATIONS.
+ *   Consequences: a run with max_iterations = k returns the iterate k of a longer run, restart boundaries included; Dinv = all ones gives
+ *   exactly the bits of Dinv = NULL; X, iterations, rr and history are bit-identical run to run, for every check_every, for host or device
+ *   pointers and every pointer alignment (unless the handle was created with option "deterministic" = 0). */
+#define SPMV_HIP_GMRES_RESTART_MAX 32
+int spmv_hip_gmres(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                   const void *Matrix_Val, const void *B, void *X, int restart,
+                   const spmv_hip_cg_options *opt, spmv_hip_cg_result *res);
+
 #endif /* SPMV_HIP_EXT_H */
 
 #if defined(__cplusplus)

@@ -109,6 +109,16 @@ double spmv_hip_time_bicgstab_iterations(spmv_Handle_t handle, const void *B, vo
    holds, the same return value. */
 double spmv_hip_time_cg_columns_iterations(spmv_Handle_t handle, int k, const void *B, long long ldb, void *X, long long ldx, const struct spmv_hip_cg_options *opt, int warmup,
                                            int iters, float *ms_out);
+/* spmv_hip_gmres's iterations, timed as spmv_hip_time_cg_iterations times spmv_hip_cg's: iteration k is step (k - 1) mod restart + 1 of its
+   cycle -- multiply, gmres_dots, gmres_coeffs, gmres_sub_dots, gmres_coeffs, gmres_sub_norm, gmres_rotate, gmres_scale -- and every restart-th
+   one also the cycle's end and the restart (gmres_solve, gmres_update_x, multiply, gmres_residual, gmres_cycle, gmres_scale).  1 <= restart <=
+   SPMV_HIP_GMRES_RESTART_MAX.  The same arguments otherwise, the same rules, the same return value; X holds the iterate of the last FINISHED
+   cycle. */
+double spmv_hip_time_gmres_iterations(spmv_Handle_t handle, const void *B, void *X, int restart, const struct spmv_hip_cg_options *opt, int warmup, int iters, float *ms_out);
+/* out[i] = the fp64 square root of in[i] exactly as spmv_hip_gmres's kernels take it (a kernel of the same translation unit, the same
+   compiler flags): n doubles each, DEVICE pointers on the current device; synchronous.  For the test that holds it against a correctly
+   rounded square root; SPMV_HIP_E_ARG for n < 0, NULL or host pointers. */
+int spmv_hip_gmres_device_sqrt(const double *in, double *out, long long n);
 /* copies the built transpose map to host: rowptr_t (n+1 entries) and perm (nnz entries: perm[p] = CSR index in A of the entry at
    position p of A^T's CSR); either may be NULL.  SPMV_HIP_E_NOSTATE until the transpose is built. */
 int spmv_hip_transpose_map(spmv_Handle_t handle, int *rowptr_t, int *perm);

@@ -180,6 +180,9 @@ FUNCTIONS = {
     "spmv_hip_time_cg_iterations": (C.c_double, [spmv_Handle_t, _V, _V, C.POINTER(spmv_hip_cg_options), C.c_int, C.c_int, C.POINTER(C.c_float)]),
     "spmv_hip_bicgstab": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, _V, _V, C.POINTER(spmv_hip_cg_options), C.POINTER(spmv_hip_cg_result)]),
     "spmv_hip_time_bicgstab_iterations": (C.c_double, [spmv_Handle_t, _V, _V, C.POINTER(spmv_hip_cg_options), C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "spmv_hip_gmres": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, _V, _V, C.c_int, C.POINTER(spmv_hip_cg_options), C.POINTER(spmv_hip_cg_result)]),
+    "spmv_hip_time_gmres_iterations": (C.c_double, [spmv_Handle_t, _V, _V, C.c_int, C.POINTER(spmv_hip_cg_options), C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "spmv_hip_gmres_device_sqrt": (C.c_int, [_V, _V, C.c_longlong]),
     "spmv_hip_cg_columns": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, C.c_int, _V, C.c_longlong, _V, C.c_longlong, C.POINTER(spmv_hip_cg_options),
                                       C.POINTER(spmv_hip_cg_result)]),
     "spmv_hip_time_cg_columns_iterations": (C.c_double, [spmv_Handle_t, C.c_int, _V, C.c_longlong, _V, C.c_longlong, C.POINTER(spmv_hip_cg_options), C.c_int, C.c_int,
@@ -831,20 +834,20 @@ def _cg_options(rtol, atol, max_iterations, check_every, x0, dinv, history):
     return opt, hist
 
 
-def _solve(name, handle, m, RowPtr, ColIdx, Matrix_Val, B, X, rtol, atol, max_iterations, check_every, x0, dinv, history, check):
-    """cg() and bicgstab(): one call of the entry point `name`"""
+def _solve(name, handle, m, RowPtr, ColIdx, Matrix_Val, B, X, rtol, atol, max_iterations, check_every, x0, dinv, history, check, extra=()):
+    """cg(), bicgstab() and gmres(): one call of the entry point `name`; extra: what it takes between X and the options"""
     opt, hist = _cg_options(rtol, atol, max_iterations, check_every, x0, dinv, history)
     res = spmv_hip_cg_result()
-    rc = _checked(getattr(load(), name)(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), _ptr(B), _ptr(X), C.byref(opt), C.byref(res)), name, check)
+    rc = _checked(getattr(load(), name)(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), _ptr(B), _ptr(X), *extra, C.byref(opt), C.byref(res)), name, check)
     out = {"status": res.status, "status_name": CG_STATUS[res.status] if 0 <= res.status < len(CG_STATUS) else "?", "iterations": res.iterations, "rr": res.rr, "bb": res.bb}
     if hist is not None:
         out["history"] = hist[:res.iterations + 1].copy() if rc == 0 else hist[:0].copy()
     return rc, out
 
 
-def _time_solve(name, handle, B, X, iterations, x0, dinv, warmup, iters):
+def _time_solve(name, handle, B, X, iterations, x0, dinv, warmup, iters, extra=()):
     opt, _ = _cg_options(0.0, 0.0, iterations, 0, x0, dinv, False)
-    return _timed(name, (handle, _ptr(B), _ptr(X), C.byref(opt)), warmup, iters)
+    return _timed(name, (handle, _ptr(B), _ptr(X), *extra, C.byref(opt)), warmup, iters)
 
 
 def cg(handle, m, RowPtr, ColIdx, Matrix_Val, B, X, rtol=1e-8, atol=0.0, max_iterations=1000, check_every=0, x0=False, dinv=None, history=False,
@@ -872,6 +875,29 @@ def time_bicgstab_iterations(handle, B, X, iterations, x0=False, dinv=None, warm
     """-> (mean ms per run, per-run ms array) of `iters` runs of `iterations` BiCGStab iterations each, stop tests off, on device B / X / dinv
     (spmv_hip_time_bicgstab_iterations)."""
     return _time_solve("spmv_hip_time_bicgstab_iterations", handle, B, X, iterations, x0, dinv, warmup, iters)
+
+
+GMRES_RESTART_MAX = 32  # SPMV_HIP_GMRES_RESTART_MAX
+
+
+def gmres(handle, m, RowPtr, ColIdx, Matrix_Val, B, X, restart=30, rtol=1e-8, atol=0.0, max_iterations=1000, check_every=0, x0=False, dinv=None,
+          history=False, check=True):
+    """Solve A x = B by right-preconditioned restarted GMRES(restart) on the device (spmv_hip_gmres; A need not be symmetric; 1 <= restart <=
+    32): B, X, dinv of m elements, host or device; x0: X holds the initial guess.  An iteration is one inner step.  -> (rc, result dict:
+    status, status_name, iterations, rr, bb[, history: the residual estimate after iteration 0 .. iterations]), as cg()."""
+    return _solve("spmv_hip_gmres", handle, m, RowPtr, ColIdx, Matrix_Val, B, X, rtol, atol, max_iterations, check_every, x0, dinv, history, check, (int(restart),))
+
+
+def time_gmres_iterations(handle, B, X, iterations, restart=30, x0=False, dinv=None, warmup=2, iters=20):
+    """-> (mean ms per run, per-run ms array) of `iters` runs of `iterations` GMRES(restart) steps each, the cycle ends and restarts among
+    them included, stop tests off, on device B / X / dinv (spmv_hip_time_gmres_iterations)."""
+    return _time_solve("spmv_hip_time_gmres_iterations", handle, B, X, iterations, x0, dinv, warmup, iters, (int(restart),))
+
+
+def gmres_device_sqrt(values, out):
+    """out[i] = the fp64 square root of values[i] as spmv_hip_gmres's kernels take it (spmv_hip_gmres_device_sqrt): device fp64 tensors."""
+    _checked(load().spmv_hip_gmres_device_sqrt(_ptr(values), _ptr(out), int(values.numel())), "spmv_hip_gmres_device_sqrt", True)
+    return out
 
 
 CG_COLUMNS_MAX = 16  # SPMV_HIP_CG_COLUMNS_MAX
@@ -1114,6 +1140,15 @@ class Handle:
         dinv: None or 1 / diag(A) (Jacobi, applied from the right: x solves the original system).
         -> (x, result dict) or (x, result dict, history) when history is set: rr after iteration 0 .. iterations."""
         return self._solve(bicgstab, b, x, x0, rtol, atol, max_iterations, check_every, dinv, history)
+
+    def gmres(self, b, x=None, restart=30, x0=False, rtol=1e-8, atol=0.0, max_iterations=1000, check_every=0, dinv=None, history=False):
+        """Solve A x = b by right-preconditioned restarted GMRES(restart) that stays on the device (spmv_hip_gmres; A square, not necessarily
+        symmetric; 1 <= restart <= 32).  An iteration is one inner step: one multiply and one new basis vector.  The other arguments and the
+        return value are bicgstab()'s; rr and the history are the recurrence's residual estimate, which never rises inside a cycle.
+        -> (x, result dict) or (x, result dict, history) when history is set."""
+        def solve(h, m, rp, ci, va, b, x, rtol, atol, max_iterations, check_every, x0, dinv, history):
+            return gmres(h, m, rp, ci, va, b, x, restart, rtol, atol, max_iterations, check_every, x0, dinv, history)
+        return self._solve(solve, b, x, x0, rtol, atol, max_iterations, check_every, dinv, history)
 
     def _attention_out(self, Q, V, heads, kv_heads, out, dtype=None):
         """-> `out`, or when that is None the uninitialised output of an attention forward: (m, heads * dv) like Q -- of `dtype` where one is

@@ -37,6 +37,9 @@ struct SolveArgs {
     long long ldb = 1, ldx = 1;    // leading dimensions of b and x
     long long span = 0;            // L
     void *vec[6] = {};             // the workspace vectors: the solver's own enum names the slots (kCgVec*, kBicgVec*)
+    char *base = nullptr;          // spmv_hip_gmres, which has more than six: workspace vector i is base + i * stride
+    size_t stride = 0;
+    int restart = 0;               // spmv_hip_gmres: steps per cycle
     void *x = nullptr;
     const void *b = nullptr, *dinv = nullptr;
     double *part = nullptr;        // the solver's partial arrays, kCgMaxParts doubles each

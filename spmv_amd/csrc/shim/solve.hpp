@@ -12,7 +12,8 @@
 // holds k of everything; the loop ends when every column has ended.
 //
 // Everything here is written once; a solver is a Solver: its sizes, its workspace, what its start and one iteration enqueue and how its
-// state reads.  k, ldb and ldx are 1 for the two single solves.
+// state reads.  k, ldb and ldx are 1 for the single solves.  spmv_hip_gmres (kernels/gmres.hpp) is the fourth: its workspace has `restart`
+// vectors more than its fixed three, and it alone has a `finish`: the columns of an unfinished cycle are applied to x behind the last look.
 #pragma once
 
 // what the host reads out of a solver's state, per column
@@ -25,6 +26,7 @@ struct SolveLook {
 struct Solver {
     const char *name;                 // in error texts
     int vectors, part_arrays;         // workspace vectors of m k elements; partial arrays of kCgMaxParts doubles PER COLUMN
+    int vectors_per_step;             // spmv_hip_gmres: further vectors per step of a cycle; its workspace is sized by `restart`, not by k (0: by k)
     int check_every;                  // iterations between two looks at the state when the caller leaves check_every at 0
     size_t state_bytes, state_room;   // the device state: what is zeroed and copied, and the bytes behind the partial arrays that hold it
     void *spmv_dev::*ws;              // the workspace: the vectors, the partial arrays, the state
@@ -34,6 +36,7 @@ struct Solver {
     int (*start)(const Solver &s, spmv_dev *d, const SolveArgs &a, bool use_x0); // behind the zeroed state: (A x0,) the init and begin kernels
     int (*iteration)(const Solver &s, spmv_dev *d, const SolveArgs &a, int k);   // iteration k >= 1: the multiplies and the vector kernels
     void (*look)(const void *state, int k, SolveLook &l);                         // a host copy of the state -> what it says
+    int (*finish)(const Solver &s, spmv_dev *d, const SolveArgs &a, const void *state); // nullptr, or what the last look's state still asks for
 };
 
 static int solve_multiply(spmv_dev *d, const void *x, void *y)
@@ -93,6 +96,32 @@ static int ccg_iteration(const Solver &s, spmv_dev *d, const SolveArgs &a, int i
     return rc ? rc : solve_launched(s, ccg_iteration_launch(a, it, d->stream));
 }
 
+// (w = A x0,) gmres_init + cg_begin + gmres_cycle + gmres_scale
+static int gmres_start(const Solver &s, spmv_dev *d, const SolveArgs &a, bool use_x0)
+{
+    int rc;
+    if (use_x0 && (rc = solve_multiply(d, a.x, a.base + kGmresVecW * a.stride))) return rc;
+    return solve_launched(s, gmres_start_launch(a, use_x0, d->stream));
+}
+
+// step j = (k - 1) mod restart + 1 of its cycle: w = A z (z is v_j without Dinv), then the seven vector kernels, sized by j; at j = restart
+// the cycle's end (gmres_solve + gmres_update_x) and the restart (w = A x, gmres_residual + gmres_cycle + gmres_scale) as well
+static int gmres_iteration(const Solver &s, spmv_dev *d, const SolveArgs &a, int k)
+{
+    const int j = (k - 1) % a.restart + 1;
+    int rc;
+    if ((rc = solve_multiply(d, a.base + (a.dinv ? (size_t) kGmresVecZ : (size_t) (kGmresVecV + j - 1)) * a.stride, a.base + kGmresVecW * a.stride))) return rc;
+    if ((rc = solve_launched(s, gmres_step_launch(a, k, j, d->stream))) || j < a.restart) return rc;
+    if ((rc = solve_launched(s, gmres_apply_launch(a, 0, d->stream))) || (rc = solve_multiply(d, a.x, a.base + kGmresVecW * a.stride))) return rc;
+    return solve_launched(s, gmres_restart_launch(a, d->stream));
+}
+
+// the loop ended, or the budget ran out, in the middle of a cycle: the columns the state names go into x
+static int gmres_finish(const Solver &s, spmv_dev *d, const SolveArgs &a, const void *state)
+{
+    return ((const GmresState *) state)->pending > 0 ? solve_launched(s, gmres_apply_launch(a, 1, d->stream)) : SPMV_HIP_OK;
+}
+
 static void single_look(const void *state, int, SolveLook &l)
 {
     const SolveState &hs = *(const SolveState *) state;
@@ -120,38 +149,45 @@ static void cols_look(const void *state, int k, SolveLook &l)
 // 1e7-row band, and what a larger value saves per iteration it loses again behind convergence, where on average check_every - 1 multiplies are wasted.
 // The k-column solve keeps CG's 8
 static const Solver kSolvers[] = {
-    {"cg", kCgVectors, kCgPartArrays, 8, sizeof(SolveState), 256, &spmv_dev::cg_ws, nullptr, &spmv_dev::cg_hist, STAGE_CG_B, STAGE_CG_X, cg_start, cg_iteration, single_look},
-    {"bicgstab", kBicgVectors, kBicgPartArrays, 8, sizeof(SolveState), 256, &spmv_dev::bicg_ws, nullptr, &spmv_dev::bicg_hist, STAGE_CG_B, STAGE_CG_X, bicg_start, bicg_iteration,
-     single_look},
-    {"cg_columns", kCcgVectors, kCcgPartArrays, 8, sizeof(ColsState), 1024, &spmv_dev::cgc_ws, &spmv_dev::cgc_k, &spmv_dev::cgc_hist, STAGE_CGC_B, STAGE_CGC_X, ccg_start,
-     ccg_iteration, cols_look},
+    {"cg", kCgVectors, kCgPartArrays, 0, 8, sizeof(SolveState), 256, &spmv_dev::cg_ws, nullptr, &spmv_dev::cg_hist, STAGE_CG_B, STAGE_CG_X, cg_start, cg_iteration, single_look, nullptr},
+    {"bicgstab", kBicgVectors, kBicgPartArrays, 0, 8, sizeof(SolveState), 256, &spmv_dev::bicg_ws, nullptr, &spmv_dev::bicg_hist, STAGE_CG_B, STAGE_CG_X, bicg_start, bicg_iteration,
+     single_look, nullptr},
+    {"cg_columns", kCcgVectors, kCcgPartArrays, 0, 8, sizeof(ColsState), 1024, &spmv_dev::cgc_ws, &spmv_dev::cgc_k, &spmv_dev::cgc_hist, STAGE_CGC_B, STAGE_CGC_X, ccg_start,
+     ccg_iteration, cols_look, nullptr},
+    {"gmres", kGmresVectors, kGmresPartArrays, 1, 8, sizeof(GmresState), kGmresStateRoom, &spmv_dev::gmres_ws, &spmv_dev::gmres_restart, &spmv_dev::gmres_hist, STAGE_CG_B,
+     STAGE_CG_X, gmres_start, gmres_iteration, single_look, gmres_finish},
 };
 static const Solver *solver_of(int id) { return id == SPMV_SHIM_SOLVE_CG || id == SPMV_SHIM_SOLVE_BICGSTAB ? &kSolvers[id] : nullptr; }
+// a solver with k columns (its workspace is sized by k; spmv_hip_gmres's by restart)
+static bool solve_has_columns(const Solver &s) { return s.ws_k && !s.vectors_per_step; }
 
 // bytes of one workspace vector of m x k elements
 static size_t solve_vec_bytes(const spmv_dev *d, int k) { return (d->vsize * (size_t) d->m * (size_t) k + 255) & ~(size_t) 255; }
-static size_t solve_tail_bytes(const Solver &s, int k) { return sizeof(double) * s.part_arrays * (size_t) k * kCgMaxParts + s.state_room; }
-// the columns the solver's workspace holds (0: none yet)
+// what a workspace sized by n (k columns; spmv_hip_gmres: restart n) holds: the columns of a vector, the vectors, the bytes behind them
+static int solve_cols(const Solver &s, int n) { return s.vectors_per_step ? 1 : n; }
+static int solve_vectors(const Solver &s, int n) { return s.vectors + s.vectors_per_step * n; }
+static size_t solve_tail_bytes(const Solver &s, int n) { return sizeof(double) * s.part_arrays * (size_t) solve_cols(s, n) * kCgMaxParts + s.state_room; }
+// the size n the solver's workspace was built for (0: none yet)
 static int solve_ws_columns(const Solver &s, const spmv_dev *d) { return !(d->*s.ws) ? 0 : s.ws_k ? d->*s.ws_k : 1; }
 
 // the vectors, the partial arrays (zeroed once: the entries behind the P in use stay +0.0) and the state: allocated at the solver's first solve --
 // s.vectors * solve_vec_bytes(k) + 8 * s.part_arrays * k * 1024 + s.state_room bytes -- and, for a solver with columns, given back and
-// allocated anew when a call has more columns than it holds
+// allocated anew when a call has more columns than it holds (spmv_hip_gmres: a larger restart; its vectors are restart + 3 of m elements)
 static int solve_workspace(const Solver &s, spmv_dev *d, int k)
 {
-    static_assert(sizeof(SolveState) <= 256 && sizeof(ColsState) <= 1024, "the state's room behind the partial arrays");
+    static_assert(sizeof(SolveState) <= 256 && sizeof(ColsState) <= 1024 && sizeof(GmresState) <= kGmresStateRoom, "the state's room behind the partial arrays");
     const int have = solve_ws_columns(s, d);
     if (have >= k) return SPMV_HIP_OK;
     if (have) {
         quiesce(d);
         (void) pool_free(d->*s.ws);
-        d->device_bytes -= (long long) (s.vectors * solve_vec_bytes(d, have) + solve_tail_bytes(s, have));
+        d->device_bytes -= (long long) (solve_vectors(s, have) * solve_vec_bytes(d, solve_cols(s, have)) + solve_tail_bytes(s, have));
         d->*s.ws = nullptr;
     }
-    const size_t vec = solve_vec_bytes(d, k), tail = solve_tail_bytes(s, k);
-    ALLOC_TRY(d, &(d->*s.ws), s.vectors * vec + tail, false);
+    const size_t vec = solve_vec_bytes(d, solve_cols(s, k)), tail = solve_tail_bytes(s, k);
+    ALLOC_TRY(d, &(d->*s.ws), solve_vectors(s, k) * vec + tail, false);
     if (s.ws_k) d->*s.ws_k = k;
-    HIP_TRY(hipMemsetAsync((char *) (d->*s.ws) + s.vectors * vec, 0, tail, d->stream));
+    HIP_TRY(hipMemsetAsync((char *) (d->*s.ws) + solve_vectors(s, k) * vec, 0, tail, d->stream));
     return SPMV_HIP_OK;
 }
 
@@ -159,22 +195,26 @@ static int solve_workspace(const Solver &s, spmv_dev *d, int k)
 // B / X / Dinv staged (X's copy-back registered with the stager; the initial guess copied in when it is wanted; the single solves share their
 // stage buffers, and all three Dinv's: the calls are synchronous, so they never hold them at the same time), the history block, the geometry
 // of the dots.  m > 0.
-static int solve_prepare(const Solver &s, spmv_dev *d, Stager &stg, int k, const void *b, long long ldb, void *x, long long ldx, const spmv_hip_cg_options *opt,
+static int solve_prepare(const Solver &s, spmv_dev *d, Stager &stg, int k, int restart, const void *b, long long ldb, void *x, long long ldx, const spmv_hip_cg_options *opt,
                          size_t hist_entries, int nostop, SolveArgs &a)
 {
-    int rc = solve_workspace(s, d, k);
+    int rc = solve_workspace(s, d, s.vectors_per_step ? restart : k);
     if (rc) return rc;
-    const size_t vec = solve_vec_bytes(d, solve_ws_columns(s, d)), m = (size_t) d->m;
+    const int held = solve_ws_columns(s, d), vectors = solve_vectors(s, held);
+    const size_t vec = solve_vec_bytes(d, solve_cols(s, held)), m = (size_t) d->m;
     char *ws = (char *) (d->*s.ws);
     a.m = d->m;
     a.k = k;
+    a.restart = restart;
+    a.base = ws;
+    a.stride = vec;
     const long long chunks = ((long long) d->m + kCgChunk - 1) / kCgChunk;
     a.parts = (int) (chunks < kCgMaxParts ? chunks : kCgMaxParts);
     a.span = (long long) kCgChunk * (((long long) d->m + (long long) kCgChunk * a.parts - 1) / ((long long) kCgChunk * a.parts));
-    for (int i = 0; i < s.vectors; ++i) a.vec[i] = ws + i * vec;
-    a.part = (double *) (ws + s.vectors * vec);
-    void *state = ws + s.vectors * vec + sizeof(double) * s.part_arrays * (size_t) solve_ws_columns(s, d) * kCgMaxParts;
-    if (s.ws_k) a.cols = (ColsState *) state;
+    for (int i = 0; i < vectors && i < (int) (sizeof(a.vec) / sizeof(a.vec[0])); ++i) a.vec[i] = ws + i * vec;
+    a.part = (double *) (ws + vectors * vec);
+    void *state = ws + vectors * vec + sizeof(double) * s.part_arrays * (size_t) solve_cols(s, held) * kCgMaxParts;
+    if (solve_has_columns(s)) a.cols = (ColsState *) state;
     else a.state = (SolveState *) state;
     a.rtol2 = opt->rtol * opt->rtol;
     a.atol2 = opt->atol * opt->atol;
@@ -189,7 +229,7 @@ static int solve_prepare(const Solver &s, spmv_dev *d, Stager &stg, int k, const
     if ((rc = stg.in(d->stage[s.stage_b], a.b, a.ldb, m, k)) || (rc = stg.in(d->stage[STAGE_CG_DINV], a.dinv, ld, m, 1)) || (rc = stg.out(d->stage[s.stage_x], a.x, a.ldx, m, k))) return rc;
     if (a.x != x && opt->use_x0) HIP_TRY(stg.copy(a.x, (size_t) k, x, (size_t) ldx, m, (size_t) k, hipMemcpyHostToDevice, d->vsize));
     // 16-byte accesses: B and X compact and aligned; the single solves' kernels read Dinv that way too, the k-column ones by element
-    a.wide = a.ldb == k && a.ldx == k && wide_ok(a.b, 1, 16) && wide_ok(a.x, 1, 16) && (s.ws_k || !a.dinv || wide_ok(a.dinv, 1, 16));
+    a.wide = a.ldb == k && a.ldx == k && wide_ok(a.b, 1, 16) && wide_ok(a.x, 1, 16) && (solve_has_columns(s) || !a.dinv || wide_ok(a.dinv, 1, 16));
     a.hist = nullptr;
     if (hist_entries > 0) {
         if ((rc = stg.reserve(d->*s.hist, sizeof(double) * hist_entries))) return rc;
@@ -198,7 +238,7 @@ static int solve_prepare(const Solver &s, spmv_dev *d, Stager &stg, int k, const
     return SPMV_HIP_OK;
 }
 
-static void *solve_state(const Solver &s, const SolveArgs &a) { return s.ws_k ? (void *) a.cols : (void *) a.state; }
+static void *solve_state(const Solver &s, const SolveArgs &a) { return solve_has_columns(s) ? (void *) a.cols : (void *) a.state; }
 
 // the state zeroed, then the solver's start
 static int solve_start(const Solver &s, spmv_dev *d, const SolveArgs &a, bool use_x0)
@@ -208,14 +248,16 @@ static int solve_start(const Solver &s, spmv_dev *d, const SolveArgs &a, bool us
 }
 
 // res: k entries.  history (k > 1): entry [it * k + j] is column j's rr after iteration it, written for it <= that column's iterations
-static int solve_run(const Solver &s, spmv_dev *d, int k, const void *b, long long ldb, void *x, long long ldx, const spmv_hip_cg_options *opt, spmv_hip_cg_result *res)
+static int solve_run(const Solver &s, spmv_dev *d, int k, int restart, const void *b, long long ldb, void *x, long long ldx, const spmv_hip_cg_options *opt, spmv_hip_cg_result *res)
 {
     if (!d || !d->built) return fail(SPMV_HIP_E_NOSTATE, "%s: schedule not built", s.name);
     if (!opt || !res) return fail(SPMV_HIP_E_ARG, "%s: opt or res is NULL", s.name);
-    if (k < 1 || k > (s.ws_k ? kCcgMaxK : 1) || ldb < k || ldx < k) return fail(SPMV_HIP_E_ARG, "%s: need 1 <= k <= %d, ldb >= k, ldx >= k", s.name, s.ws_k ? kCcgMaxK : 1);
+    const bool cols = solve_has_columns(s);
+    if (k < 1 || k > (cols ? kCcgMaxK : 1) || ldb < k || ldx < k) return fail(SPMV_HIP_E_ARG, "%s: need 1 <= k <= %d, ldb >= k, ldx >= k", s.name, cols ? kCcgMaxK : 1);
+    if (s.vectors_per_step && (restart < 1 || restart > kGmresMaxRestart)) return fail(SPMV_HIP_E_ARG, "%s: need 1 <= restart <= %d", s.name, kGmresMaxRestart);
     if (d->m != d->n) return fail(SPMV_HIP_E_ARG, "%s: the matrix is %d x %d, not square", s.name, d->m, d->n);
     if (d->m > 0 && (!b || !x)) return fail(SPMV_HIP_E_ARG, "%s: B or X is NULL", s.name);
-    if (s.ws_k && d->nnz > 0 && !d->colidx) return fail(SPMV_HIP_E_NOSTATE, "%s: the resident column indices were released (spmv_shim_restore_columns first)", s.name);
+    if (cols && d->nnz > 0 && !d->colidx) return fail(SPMV_HIP_E_NOSTATE, "%s: the resident column indices were released (spmv_shim_restore_columns first)", s.name);
     for (int j = 0; j < k; ++j) {
         res[j].status = SPMV_HIP_CG_CONVERGED;
         res[j].iterations = 0;
@@ -225,13 +267,14 @@ static int solve_run(const Solver &s, spmv_dev *d, int k, const void *b, long lo
     DeviceGuard guard(d->device);
     if (!guard.ok) return fail(SPMV_HIP_E_RUNTIME, "hipSetDevice(%d) failed", d->device);
     int rc;
-    if (s.ws_k && (rc = spmm_plan(d))) return rc;
+    if (cols && (rc = spmm_plan(d))) return rc;
     Stager stg{d};
     SolveArgs a;
-    rc = solve_prepare(s, d, stg, k, b, ldb, x, ldx, opt, opt->history ? ((size_t) opt->max_iterations + 1) * (size_t) k : 0, 0, a);
+    rc = solve_prepare(s, d, stg, k, restart, b, ldb, x, ldx, opt, opt->history ? ((size_t) opt->max_iterations + 1) * (size_t) k : 0, 0, a);
     if (rc || (rc = solve_start(s, d, a, opt->use_x0 != 0))) return rc;
     const int every = opt->check_every > 0 ? opt->check_every : s.check_every;
-    alignas(8) unsigned char hs[sizeof(ColsState) > sizeof(SolveState) ? sizeof(ColsState) : sizeof(SolveState)];
+    alignas(8) unsigned char hs[sizeof(GmresState) > sizeof(ColsState) ? sizeof(GmresState) : sizeof(ColsState)];
+    static_assert(sizeof(hs) >= sizeof(SolveState), "the largest state");
     SolveLook l;
     for (int it = 0;;) {
         HIP_TRY(hipMemcpyAsync(hs, solve_state(s, a), s.state_bytes, hipMemcpyDeviceToHost, d->stream));
@@ -244,6 +287,7 @@ static int solve_run(const Solver &s, spmv_dev *d, int k, const void *b, long lo
         while (it < stop)
             if ((rc = s.iteration(s, d, a, ++it))) return rc;
     }
+    if (s.finish && (rc = s.finish(s, d, a, hs))) return rc;
     int longest = 0;
     for (int j = 0; j < k; ++j) {
         res[j].status = l.done[j] ? l.status[j] : SPMV_HIP_CG_MAX_ITERATIONS;
@@ -272,21 +316,22 @@ static int solve_run(const Solver &s, spmv_dev *d, int k, const void *b, long lo
 // `warmup` untimed + `iters` timed RUNS of opt->max_iterations iterations each, the stop tests disabled: every run starts again from B (and
 // X when use_x0), its iterations are enqueued back to back and bracketed by two events on the handle's stream (the start is outside them:
 // not state.hpp's time_events, which brackets a whole call).  ms_out[i] (may be NULL): run i.  Mean ms per run, < 0 on failure.  Device pointers only.
-static double solve_time(const Solver &s, spmv_dev *d, int k, const void *b, long long ldb, void *x, long long ldx, const spmv_hip_cg_options *opt, int warmup, int iters,
+static double solve_time(const Solver &s, spmv_dev *d, int k, int restart, const void *b, long long ldb, void *x, long long ldx, const spmv_hip_cg_options *opt, int warmup, int iters,
                          float *ms_out)
 {
-    if (!d || !d->built || !opt || iters <= 0 || warmup < 0 || opt->max_iterations < 1 || d->m != d->n || d->m <= 0 || k < 1 || k > (s.ws_k ? kCcgMaxK : 1) || ldb < k || ldx < k) {
+    if (!d || !d->built || !opt || iters <= 0 || warmup < 0 || opt->max_iterations < 1 || d->m != d->n || d->m <= 0 || k < 1 || k > (solve_has_columns(s) ? kCcgMaxK : 1) || ldb < k || ldx < k ||
+        (s.vectors_per_step && (restart < 1 || restart > kGmresMaxRestart))) {
         fail(SPMV_HIP_E_ARG, "time_%s: bad arguments", s.name);
         return -1.0;
     }
     if (!is_device_ptr(b) || !is_device_ptr(x) || (opt->Dinv && !is_device_ptr(opt->Dinv))) { fail(SPMV_HIP_E_ARG, "time_%s: B, X and Dinv must be device pointers", s.name); return -1.0; }
-    if (s.ws_k && d->nnz > 0 && !d->colidx) { fail(SPMV_HIP_E_NOSTATE, "time_%s: the resident column indices were released", s.name); return -1.0; }
+    if (solve_has_columns(s) && d->nnz > 0 && !d->colidx) { fail(SPMV_HIP_E_NOSTATE, "time_%s: the resident column indices were released", s.name); return -1.0; }
     DeviceGuard guard(d->device);
     if (!guard.ok) { fail(SPMV_HIP_E_RUNTIME, "hipSetDevice(%d) failed", d->device); return -1.0; }
-    if (s.ws_k && spmm_plan(d)) return -1.0;
+    if (solve_has_columns(s) && spmm_plan(d)) return -1.0;
     Stager stg{d};
     SolveArgs a;
-    if (solve_prepare(s, d, stg, k, b, ldb, x, ldx, opt, 0, 1, a)) return -1.0;
+    if (solve_prepare(s, d, stg, k, restart, b, ldb, x, ldx, opt, 0, 1, a)) return -1.0;
     std::vector<hipEvent_t> ev;
     auto done = [&](double mean) {
         for (hipEvent_t e : ev) (void) hipEventDestroy(e);
@@ -320,23 +365,44 @@ static double solve_time(const Solver &s, spmv_dev *d, int k, const void *b, lon
 extern "C" int spmv_shim_solve(int solver, spmv_dev *d, const void *b, void *x, const spmv_hip_cg_options *opt, spmv_hip_cg_result *res)
 {
     const Solver *s = solver_of(solver);
-    return s ? solve_run(*s, d, 1, b, 1, x, 1, opt, res) : fail(SPMV_HIP_E_ARG, "solve: no solver %d", solver);
+    return s ? solve_run(*s, d, 1, 0, b, 1, x, 1, opt, res) : fail(SPMV_HIP_E_ARG, "solve: no solver %d", solver);
 }
 
 extern "C" double spmv_shim_time_solve(int solver, spmv_dev *d, const void *b, void *x, const spmv_hip_cg_options *opt, int warmup, int iters, float *ms_out)
 {
     const Solver *s = solver_of(solver);
     if (!s) { fail(SPMV_HIP_E_ARG, "time_solve: no solver %d", solver); return -1.0; }
-    return solve_time(*s, d, 1, b, 1, x, 1, opt, warmup, iters, ms_out);
+    return solve_time(*s, d, 1, 0, b, 1, x, 1, opt, warmup, iters, ms_out);
 }
 
 extern "C" int spmv_shim_solve_columns(spmv_dev *d, int k, const void *b, long long ldb, void *x, long long ldx, const spmv_hip_cg_options *opt, spmv_hip_cg_result *res)
 {
-    return solve_run(kSolvers[SPMV_SHIM_SOLVE_CG_COLUMNS], d, k, b, ldb, x, ldx, opt, res);
+    return solve_run(kSolvers[SPMV_SHIM_SOLVE_CG_COLUMNS], d, k, 0, b, ldb, x, ldx, opt, res);
 }
 
 extern "C" double spmv_shim_time_solve_columns(spmv_dev *d, int k, const void *b, long long ldb, void *x, long long ldx, const spmv_hip_cg_options *opt, int warmup, int iters,
                                                float *ms_out)
 {
-    return solve_time(kSolvers[SPMV_SHIM_SOLVE_CG_COLUMNS], d, k, b, ldb, x, ldx, opt, warmup, iters, ms_out);
+    return solve_time(kSolvers[SPMV_SHIM_SOLVE_CG_COLUMNS], d, k, 0, b, ldb, x, ldx, opt, warmup, iters, ms_out);
+}
+
+extern "C" int spmv_shim_solve_gmres(spmv_dev *d, int restart, const void *b, void *x, const spmv_hip_cg_options *opt, spmv_hip_cg_result *res)
+{
+    return solve_run(kSolvers[SPMV_SHIM_SOLVE_GMRES], d, 1, restart, b, 1, x, 1, opt, res);
+}
+
+extern "C" double spmv_shim_time_solve_gmres(spmv_dev *d, int restart, const void *b, void *x, const spmv_hip_cg_options *opt, int warmup, int iters, float *ms_out)
+{
+    return solve_time(kSolvers[SPMV_SHIM_SOLVE_GMRES], d, 1, restart, b, 1, x, 1, opt, warmup, iters, ms_out);
+}
+
+// out[i] = the square root spmv_hip_gmres's kernels take of in[i]; n doubles each, device pointers; synchronous, on the null stream
+extern "C" int spmv_shim_gmres_sqrt(const double *in, double *out, long long n)
+{
+    if (n == 0) return SPMV_HIP_OK;
+    if (n < 0 || !in || !out || !is_device_ptr(in) || !is_device_ptr(out)) return fail(SPMV_HIP_E_ARG, "gmres_sqrt: need n >= 0 and device pointers");
+    const hipError_t e = gmres_sqrt_launch(in, out, n, nullptr);
+    if (e != hipSuccess) return fail(SPMV_HIP_E_RUNTIME, "gmres_sqrt: launch: %s", hipGetErrorString(e));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return SPMV_HIP_OK;
 }

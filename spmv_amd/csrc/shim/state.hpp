@@ -310,6 +310,11 @@ struct spmv_dev {
     void *cgc_ws = nullptr;
     int cgc_k = 0;
     StageBuf cgc_hist;
+    // spmv_hip_gmres (shim/solve.hpp): w, z and gmres_restart + 1 basis vectors (m elements each), 35 partial arrays and the state in ONE block
+    // of the solver's own, allocated at the first call and allocated anew when a later call has a larger restart; its history likewise
+    void *gmres_ws = nullptr;
+    int gmres_restart = 0;
+    StageBuf gmres_hist;
     // spmv_hip_spmv_transpose (shim/transpose.hpp): A^T as a matrix of its own (n x m), planned and built like any; perm[p] = our index of its entry p.
     // val_gen counts spmv_shim_update_values calls; A^T's values are gathered again when tr_gen falls behind it.
     spmv_dev *tr = nullptr;

@@ -1466,6 +1466,36 @@ double spmv_hip_time_bicgstab_iterations(spmv_Handle_t h, const void *B, void *X
     return solve_time(h, "time_bicgstab_iterations", SPMV_SHIM_SOLVE_BICGSTAB, B, X, opt, warmup, iters, ms_out);
 }
 
+/* ---------------------------------------------------------------- restarted GMRES on the device */
+int spmv_hip_gmres(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx, const void *Matrix_Val, const void *B, void *X, int restart,
+                   const spmv_hip_cg_options *opt, spmv_hip_cg_result *res)
+{
+    const char *where = "gmres";
+    spmv_hip_state *st;
+    int rc;
+    if ((rc = cg_args(handle, where, B, X, opt, res, m))) return rc;
+    if (restart < 1 || restart > SPMV_HIP_GMRES_RESTART_MAX) return refuse(SPMV_HIP_E_ARG, where, "need 1 <= restart <= SPMV_HIP_GMRES_RESTART_MAX");
+    if ((rc = resident_prologue(handle, where, 0, m, RowPtr, ColIdx, Matrix_Val, &st))) return rc;
+    if (st->m != st->n) return refuse(SPMV_HIP_E_ARG, where, "the matrix is not square (m != n at create)");
+    return report(spmv_shim_solve_gmres(st->dev, restart, B, X, opt, res), where);
+}
+
+double spmv_hip_time_gmres_iterations(spmv_Handle_t h, const void *B, void *X, int restart, const spmv_hip_cg_options *opt, int warmup, int iters, float *ms_out)
+{
+    const char *where = "time_gmres_iterations";
+    spmv_hip_state *st;
+    if (cg_args(h, where, B, X, opt, opt, 1)) return -1.0;
+    if (restart < 1 || restart > SPMV_HIP_GMRES_RESTART_MAX) { (void) refuse(SPMV_HIP_E_ARG, where, "need 1 <= restart <= SPMV_HIP_GMRES_RESTART_MAX"); return -1.0; }
+    if (resident_state(h, where, 0, &st)) return -1.0;
+    if (st->m != st->n) { (void) refuse(SPMV_HIP_E_ARG, where, "the matrix is not square (m != n at create)"); return -1.0; }
+    return report_time(spmv_shim_time_solve_gmres(st->dev, restart, B, X, opt, warmup, iters, ms_out), where);
+}
+
+int spmv_hip_gmres_device_sqrt(const double *in, double *out, long long n)
+{
+    return report(spmv_shim_gmres_sqrt(in, out, n), "gmres_device_sqrt");
+}
+
 /* ---------------------------------------------------------------- conjugate gradients for k right-hand sides in one pass over A per iteration */
 /* cg_args' rules and the columns' own; the timer with m = 1 */
 static int cg_columns_args(spmv_Handle_t h, const char *where, int k, const void *B, long long ldb, const void *X, long long ldx, const spmv_hip_cg_options *opt, const void *res,

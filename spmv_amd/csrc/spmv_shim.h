@@ -209,7 +209,7 @@ double spmv_shim_time_attention_backward(spmv_dev *d, const spmv_attention_backw
  * right-preconditioned BiCGStab (spmv_hip_bicgstab; the matrix need not be symmetric) ----
  * B, X, opt->Dinv: m elements, host or device pointers each.  The multiply is the built schedule's own launch.  Each solver builds a workspace of its
  * own at its first call.  SPMV_HIP_OK whenever the solve ran (res->status says how it ended); synchronous */
-enum { SPMV_SHIM_SOLVE_CG, SPMV_SHIM_SOLVE_BICGSTAB, SPMV_SHIM_SOLVE_CG_COLUMNS /* spmv_shim_solve_columns alone */ };
+enum { SPMV_SHIM_SOLVE_CG, SPMV_SHIM_SOLVE_BICGSTAB, SPMV_SHIM_SOLVE_CG_COLUMNS /* spmv_shim_solve_columns alone */, SPMV_SHIM_SOLVE_GMRES /* spmv_shim_solve_gmres alone */ };
 int spmv_shim_solve(int solver, spmv_dev *d, const void *b, void *x, const spmv_hip_cg_options *opt, spmv_hip_cg_result *res);
 /* `iters` runs of opt->max_iterations iterations each, the stop tests off, timed with events on the handle's stream (device B / X / Dinv); mean ms per run, < 0 on failure */
 double spmv_shim_time_solve(int solver, spmv_dev *d, const void *b, void *x, const spmv_hip_cg_options *opt, int warmup, int iters, float *ms_out);
@@ -217,6 +217,12 @@ double spmv_shim_time_solve(int solver, spmv_dev *d, const void *b, void *x, con
  * dimensions ldb, ldx >= k, host or device pointers; opt->Dinv one vector of m elements; res k entries; opt->history (max_iterations + 1) * k doubles.
  * The multiply is spmv_shim_spmm's executor on the solver's own compact workspace vectors, one pass over A per iteration: the resident ColIdx
  * is needed (spmv_shim_restore_columns).  The same loop, workspace rules and return value as spmv_shim_solve */
+/* spmv_hip_gmres: restarted GMRES(restart), 1 <= restart <= SPMV_HIP_GMRES_RESTART_MAX, through the same loop; its workspace holds restart + 3 vectors and is
+ * allocated anew when a later call has a larger restart.  The timer's iterations include the cycle ends and restarts that fall among them */
+int spmv_shim_solve_gmres(spmv_dev *d, int restart, const void *b, void *x, const spmv_hip_cg_options *opt, spmv_hip_cg_result *res);
+double spmv_shim_time_solve_gmres(spmv_dev *d, int restart, const void *b, void *x, const spmv_hip_cg_options *opt, int warmup, int iters, float *ms_out);
+/* out[i] = the fp64 square root of in[i] as spmv_hip_gmres's kernels take it: n doubles each, device pointers; synchronous */
+int spmv_shim_gmres_sqrt(const double *in, double *out, long long n);
 int spmv_shim_solve_columns(spmv_dev *d, int k, const void *b, long long ldb, void *x, long long ldx, const spmv_hip_cg_options *opt, spmv_hip_cg_result *res);
 double spmv_shim_time_solve_columns(spmv_dev *d, int k, const void *b, long long ldb, void *x, long long ldx, const spmv_hip_cg_options *opt, int warmup, int iters,
                                     float *ms_out);

@@ -2,13 +2,15 @@
 // kernels/cg_columns.hpp, what they share in kernels/solve_common.hpp).  Launches only: the workspace, staging, the multiplies, the host's
 // looks at the state and the error channel stay in spmv_shim.hip (shim/solve.hpp).  Per solve it calls cg_start_launch or bicg_start_launch
 // once; per iteration cg_iteration_launch behind q = A p, or bicg_first_launch behind v = A ph and bicg_second_launch behind t = A sh;
-// spmv_hip_cg_columns: ccg_start_launch, and ccg_iteration_launch behind q = A p for all k columns.
+// spmv_hip_cg_columns: ccg_start_launch, and ccg_iteration_launch behind q = A p for all k columns.  spmv_hip_gmres (kernels/gmres.hpp):
+// gmres_start_launch, gmres_step_launch behind w = A z, and at a cycle's end gmres_apply_launch, then gmres_restart_launch behind w = A x.
 #include <hip/hip_runtime.h>
 
 #include "kernels/common.hpp"
 #include "kernels/cg.hpp"
 #include "kernels/bicgstab.hpp"
 #include "kernels/cg_columns.hpp"
+#include "kernels/gmres.hpp"
 
 namespace spmv {
 
@@ -121,5 +123,72 @@ hipError_t cg_iteration_launch(const SolveArgs &a, int k, hipStream_t stream) { 
 hipError_t bicg_start_launch(const SolveArgs &a, bool use_x0, hipStream_t stream) { SOLVE_LAUNCH(bicg_start_t, true, a, use_x0, stream); }
 hipError_t bicg_first_launch(const SolveArgs &a, int k, hipStream_t stream) { SOLVE_LAUNCH(bicg_first_t, k >= 1, a, k, stream); }
 hipError_t bicg_second_launch(const SolveArgs &a, int k, hipStream_t stream) { SOLVE_LAUNCH(bicg_second_t, k >= 1, a, k, stream); }
+
+// ---- spmv_hip_gmres
+static GmresState *gmres_state(const SolveArgs &a) { return reinterpret_cast<GmresState *>(a.state); }
+template <typename T> static T *gmres_vec(const SolveArgs &a, int i) { return (T *) (a.base + (size_t) i * a.stride); }
+
+// v_i = w * T(scale) (i >= 1), z = Dinv .* v_i
+template <typename T, bool WIDE, bool DINV>
+static void gmres_scale_t(const SolveArgs &a, int i, hipStream_t stream)
+{
+    gmres_scale_kernel<T, WIDE, DINV><<<(unsigned) a.parts, kBlock, 0, stream>>>(a.m, a.span, gmres_vec<T>(a, kGmresVecW), gmres_vec<T>(a, kGmresVecV + i - 1), (const T *) a.dinv,
+                                                                                  gmres_vec<T>(a, kGmresVecZ), gmres_state(a));
+}
+
+template <typename T, bool WIDE, bool DINV>
+static void gmres_start_t(const SolveArgs &a, bool use_x0, hipStream_t stream)
+{
+    T *w = gmres_vec<T>(a, kGmresVecW);
+    if (use_x0) gmres_init_kernel<T, WIDE, true><<<(unsigned) a.parts, kBlock, 0, stream>>>(a.m, a.span, (const T *) a.b, (T *) a.x, w, a.part);
+    else gmres_init_kernel<T, WIDE, false><<<(unsigned) a.parts, kBlock, 0, stream>>>(a.m, a.span, (const T *) a.b, (T *) a.x, w, a.part);
+    solve_begin<false>(a, kGmresPartRR, kGmresPartRR, kGmresPartBB, stream);
+    gmres_cycle_kernel<false><<<1, kBlock, 0, stream>>>(a.part, gmres_state(a), a.nostop);
+    gmres_scale_t<T, WIDE, DINV>(a, 1, stream);
+}
+
+template <typename T, bool WIDE, bool DINV>
+static void gmres_step_t(const SolveArgs &a, int k, int j, hipStream_t stream)
+{
+    const unsigned grid = (unsigned) a.parts;
+    GmresState *st = gmres_state(a);
+    gmres_dots_kernel<T, kGmresGroup><<<grid, kBlock, 0, stream>>>(a.m, a.span, a.base, a.stride, j, a.part, st);
+    gmres_coeffs_kernel<T><<<(unsigned) j, kBlock, 0, stream>>>(a.part, st, 0);
+    gmres_sub_dots_kernel<T, kGmresGroup><<<grid, kBlock, 0, stream>>>(a.m, a.span, a.base, a.stride, j, a.part, st);
+    gmres_coeffs_kernel<T><<<(unsigned) j, kBlock, 0, stream>>>(a.part, st, 1);
+    gmres_sub_norm_kernel<T><<<grid, kBlock, 0, stream>>>(a.m, a.span, a.base, a.stride, j, a.part, st);
+    if (a.hist) gmres_rotate_kernel<true><<<1, kBlock, 0, stream>>>(a.part, st, k, j, a.hist, a.rtol2, a.atol2, a.nostop);
+    else gmres_rotate_kernel<false><<<1, kBlock, 0, stream>>>(a.part, st, k, j, a.hist, a.rtol2, a.atol2, a.nostop);
+    if (j < a.restart) gmres_scale_t<T, WIDE, DINV>(a, j + 1, stream);
+}
+
+template <typename T, bool WIDE, bool DINV>
+static void gmres_apply_t(const SolveArgs &a, int force, hipStream_t stream)
+{
+    gmres_solve_kernel<T><<<1, kWave, 0, stream>>>(gmres_state(a), force);
+    gmres_update_x_kernel<T, WIDE, DINV><<<(unsigned) a.parts, kBlock, 0, stream>>>(a.m, a.span, a.base, a.stride, (T *) a.x, (const T *) a.dinv, gmres_state(a), force);
+}
+
+template <typename T, bool WIDE, bool DINV>
+static void gmres_restart_t(const SolveArgs &a, hipStream_t stream)
+{
+    gmres_residual_kernel<T, WIDE><<<(unsigned) a.parts, kBlock, 0, stream>>>(a.m, a.span, (const T *) a.b, gmres_vec<T>(a, kGmresVecW), a.part, gmres_state(a));
+    gmres_cycle_kernel<true><<<1, kBlock, 0, stream>>>(a.part, gmres_state(a), a.nostop);
+    gmres_scale_t<T, WIDE, DINV>(a, 1, stream);
+}
+
+static bool gmres_ok(const SolveArgs &a) { return a.restart >= 1 && a.restart <= kGmresMaxRestart && a.base != nullptr && a.stride >= sizeof(double) && a.state != nullptr; }
+
+hipError_t gmres_start_launch(const SolveArgs &a, bool use_x0, hipStream_t stream) { SOLVE_LAUNCH(gmres_start_t, gmres_ok(a), a, use_x0, stream); }
+hipError_t gmres_step_launch(const SolveArgs &a, int k, int j, hipStream_t stream) { SOLVE_LAUNCH(gmres_step_t, gmres_ok(a) && k >= 1 && j >= 1 && j <= a.restart, a, k, j, stream); }
+hipError_t gmres_apply_launch(const SolveArgs &a, int force, hipStream_t stream) { SOLVE_LAUNCH(gmres_apply_t, gmres_ok(a), a, force, stream); }
+hipError_t gmres_restart_launch(const SolveArgs &a, hipStream_t stream) { SOLVE_LAUNCH(gmres_restart_t, gmres_ok(a), a, stream); }
+
+hipError_t gmres_sqrt_launch(const double *in, double *out, long long n, hipStream_t stream)
+{
+    if (n <= 0 || !in || !out || (n + kBlock - 1) / kBlock > 0x7fffffffLL) return hipErrorInvalidValue;
+    gmres_sqrt_kernel<double><<<(unsigned) ((n + kBlock - 1) / kBlock), kBlock, 0, stream>>>(in, out, n);
+    return hipGetLastError();
+}
 
 } // namespace spmv
