@@ -1,39 +1,32 @@
 // shim/launch.hpp -- part of the single translation unit spmv_shim.hip: the EXECUTORS' launchers (which
 // kernel form, which template arguments, grid and LDS size per schedule), the create-time autotune of the
 // CSR-vector forms, and launch<T>() = one y = A x on the handle's stream.
+//
+// The create-time choices.  Which form of a kernel is fastest differs between MI355X boxes by a few percent, so create() times the applicable
+// ones once on the resident matrix and the handle launches the winner from then on.  autotune_vector, build_packed_values, autotune_blocked, autotune_rows
+// and time_schedule are each a gate in front of ONE race, race_forms: it ends with no room for its scratch vectors (the default stays, nothing is wrong),
+// failed (the choice goes back to the default) or timed.  What a form's code means, the candidates, the round counts, the 0.95 guard and what is done with
+// the times are shim/tune.hpp: a table and pure functions that a host program runs without a device.  Option vector_form forces a form (tests, A/B runs).
 #pragma once
 
 // ------------------------------------------------------------------------------------ executors
-// Kernel forms of the CSR-vector schedule.  Which one is fastest differs between MI355X boxes by a
-// few percent, so create() times the applicable ones once on the resident matrix
-// (autotune_vector) and keeps the winner in d->vec_choice; option vector_form forces one (tests, A/B runs).
-enum { VEC_AUTO = 0, VEC_PIPE = 4, VEC_TILE_D2 = 5, VEC_TILE_D8 = 6, VEC_TILE_D4 = 10, VEC_TILE_D4_NOPRE = 11, VEC_TILE_D2_NOPRE = 12 };
-
 // The launch of the CSR-vector family (kernels/csr_vector_tile.hpp) that a built CSR-vector or Balanced schedule makes: the one place that
-// decides the kernel and its form.  launch(), the autotune, spmv_shim_release_columns and spmv_shim_info all read it.
+// decides the kernel and its form (from tune.hpp's table).  launch(), the autotune, spmv_shim_release_columns and spmv_shim_info all read it.
 static VecArgs vector_args(const spmv_dev *d)
 {
     VecArgs a;
     const bool f64 = d->vsize == sizeof(double);
     if (d->plan.sched == SPMV_SCHED_ROWBLOCK || d->vt_wide) {
-        // the rows kernel: Balanced's equal-nnz row blocks (split), or CSR-vector's wide form (uniform blocks).  Steps in flight: what create()
-        // measured (rows_depth, autotune_rows), what option vector_form names (5 / 12: two, 10 / 11: four), else the dtype's default
-        const int v = d->plan.vector_form;
+        // the rows kernel: Balanced's equal-nnz row blocks (split), or CSR-vector's wide form (uniform blocks).  Steps in flight: what option
+        // vector_form names (5 / 12: two, 10 / 11: four), what create() measured (rows_depth, autotune_rows), else the dtype's default
         a.kernel = kVecRowsKernel;
-        a.depth = d->rows_depth ? d->rows_depth : (f64 ? 4 : 2);
-        if (v == VEC_TILE_D2 || v == VEC_TILE_D2_NOPRE) a.depth = 2;
-        if (v == VEC_TILE_D4 || v == VEC_TILE_D4_NOPRE) a.depth = 4;
+        a.depth = rows_depth_of(d->plan.vector_form, d->rows_depth, f64);
         a.wide = d->vt_wide;
         a.split = d->plan.sched == SPMV_SCHED_ROWBLOCK ? d->rb_split : nullptr;
     } else {
-        const int v = d->plan.vector_form ? d->plan.vector_form : d->vec_choice;
-        const bool tile_default = d->vt_staged * 2 >= d->vt_tiles; // most x tiles fit LDS
-        const bool tile_forced = v == VEC_TILE_D2 || v == VEC_TILE_D4 || v == VEC_TILE_D8 || v == VEC_TILE_D4_NOPRE || v == VEC_TILE_D2_NOPRE;
-        if (d->vt_tiles > 0 && v != VEC_PIPE && (tile_default || tile_forced)) { // tile kernel (unstaged tiles gather from L1/L2)
-            a.kernel = kVecTileKernel;
-            a.depth = v == VEC_TILE_D2 || v == VEC_TILE_D2_NOPRE ? 2 : v == VEC_TILE_D8 ? 8 : v == VEC_TILE_D4 || v == VEC_TILE_D4_NOPRE ? 4 : (f64 ? 4 : 2); // else the measured default
-            a.pre = v != VEC_TILE_D4_NOPRE && v != VEC_TILE_D2_NOPRE;
-        }
+        // tile kernel where most x tiles fit LDS or a tile form is named (unstaged tiles gather from L1/L2), else the pipe kernel
+        const VecForm f = vector_form_of(d->plan.vector_form ? d->plan.vector_form : d->vec_choice, f64, d->vt_tiles > 0, d->vt_staged * 2 >= d->vt_tiles);
+        if (f.tile) { a.kernel = kVecTileKernel; a.depth = f.depth; a.pre = f.pre; }
     }
     a.lanes = d->plan.lanes_per_row; a.m = d->m; a.long_thr = d->long_thr; a.tiles = d->vt_tiles; a.maxspan = d->vt_maxspan; a.rows = d->vt_rows;
     a.rowptr = d->rowptr; a.colidx = d->colidx; a.val = d->val; a.wins = d->vt_wins;
@@ -54,59 +47,62 @@ static hipError_t launch_vector(const spmv_dev *d, const T *x, T *y)
     return a.kernel == kVecRowsKernel ? rows_launch(a, x, y) : vector_launch(a, x, y);
 }
 
-// Time the applicable CSR-vector forms on the resident matrix (x = 1) and keep the fastest.
+// The race of every create-time choice: scratch x = 1 and y from the pool, two events, set(k); launch(x, y) once per candidate to warm it, then `rounds`
+// interleaved rounds (one process, same clocks) of one launch per sample -- the forms differ by whole percents where they differ, events resolve a
+// microsecond -- and tmin[k] = the minimum.  kRaceFailed: hipEventCreate or a launch returned an error (the race ends there), or the runtime holds one at the end.
+enum RaceEnd { kRaceNoRoom, kRaceFailed, kRaceTimed };
+template <typename T, class Set, class Launch>
+static RaceEnd race_forms(spmv_dev *d, int ncand, int rounds, float *tmin, Set set, Launch launch)
+{
+    for (int k = 0; k < ncand; ++k) tmin[k] = kNotTimed;
+    T *x = nullptr, *y = nullptr;
+    if (pool_malloc((void **) &x, sizeof(T) * (size_t) (d->n > 0 ? d->n : 1)) != hipSuccess || pool_malloc((void **) &y, sizeof(T) * (size_t) (d->m > 0 ? d->m : 1)) != hipSuccess) {
+        (void) hipGetLastError();
+        if (x) (void) pool_free(x);
+        return kRaceNoRoom;
+    }
+    fill_value_kernel<T><<<grid_for(d->n, kBlock, d->cus * 8), kBlock, 0, d->stream>>>(d->n, x, T(1));
+    int rc = 0;
+    {
+        Events ev(2);
+        rc = ev.ok ? 0 : 1;
+        for (int k = 0; k < ncand && !rc; ++k) { set(k); rc = launch(x, y); } // warm every form once
+        for (int round = 0; round < rounds && !rc; ++round)
+            for (int k = 0; k < ncand && !rc; ++k) {
+                set(k);
+                (void) hipEventRecord(ev[0], d->stream);
+                rc = launch(x, y);
+                (void) hipEventRecord(ev[1], d->stream);
+                (void) hipEventSynchronize(ev[1]);
+                float ms = 0;
+                (void) hipEventElapsedTime(&ms, ev[0], ev[1]);
+                if (ms < tmin[k]) tmin[k] = ms;
+            }
+    }
+    (void) pool_free(x);
+    (void) pool_free(y);
+    const bool clean = hipGetLastError() == hipSuccess;
+    return rc || !clean ? kRaceFailed : kRaceTimed;
+}
+
+// Time the applicable CSR-vector forms on the resident matrix and keep the fastest (tune.hpp: vector_rule).
 template <typename T>
 static int autotune_vector(spmv_dev *d)
 {
     d->vec_choice = VEC_AUTO;
     if (d->nnz < (1ll << 24) || d->plan.forced || d->vt_tiles <= 0) return SPMV_HIP_OK;
     if (d->vt_wide || d->vt_staged * 2 < d->vt_tiles) return SPMV_HIP_OK; // wide form: one kernel form; x windows not staged: the pipe form runs, nothing to choose (and 45 gather-bound launches would cost ~0.3 s)
-    T *x = nullptr, *y = nullptr;
-    if (pool_malloc((void **) &x, sizeof(T) * (size_t) d->n) != hipSuccess || pool_malloc((void **) &y, sizeof(T) * (size_t) d->m) != hipSuccess) {
-        (void) hipGetLastError();
-        if (x) (void) pool_free(x);
-        return SPMV_HIP_OK; // no room to tune: keep the default
-    }
-    fill_value_kernel<T><<<grid_for(d->n, kBlock, d->cus * 8), kBlock, 0, d->stream>>>(d->n, x, T(1));
-    hipEvent_t e0, e1;
-    (void) hipEventCreate(&e0);
-    (void) hipEventCreate(&e1);
-    constexpr int kCand = 5;
-    const int cand[kCand] = {VEC_TILE_D4, VEC_TILE_D4_NOPRE, VEC_TILE_D2, VEC_TILE_D2_NOPRE, VEC_PIPE};
     // (nearly) every tile staged: the pipe form (4-byte columns, gathers through L1 / L2) has nothing to win and is not timed -- on config 2 its nine
     // launches were a quarter of the inspector's 26 ms
-    const int ncand = (long long) d->vt_staged * 100 >= (long long) d->vt_tiles * 99 ? kCand - 1 : kCand;
-    float tmin[kCand];
-    for (int k = 0; k < kCand; ++k) tmin[k] = 1e30f;
-    for (int k = 0; k < ncand; ++k) { d->vec_choice = cand[k]; (void) launch_vector<T>(d, x, y); } // warm every form once
-    for (int round = 0; round < 3; ++round) // interleaved rounds (one process, same clocks): min per form
-        for (int k = 0; k < ncand; ++k) {
-            d->vec_choice = cand[k];
-            (void) hipEventRecord(e0, d->stream);
-            (void) launch_vector<T>(d, x, y); // one launch per sample (round 3: two): the forms differ by whole percents where they differ, events resolve a microsecond
-            (void) hipEventRecord(e1, d->stream);
-            (void) hipEventSynchronize(e1);
-            float ms = 0;
-            (void) hipEventElapsedTime(&ms, e0, e1);
-            if (ms < tmin[k]) tmin[k] = ms;
-        }
-    float best = 1e30f;
-    int best_c = VEC_AUTO;
-    for (int k = 0; k < kCand - 1; ++k) {
-        if (tmin[k] < best) { best = tmin[k]; best_c = cand[k]; }
-    }
-    // the pipe form (int32 columns, global gathers) only on a clear win: a noisy sample -- e.g. another
-    // process on the device during create -- must not cost 30 % on every later launch
-    if (ncand == kCand && tmin[kCand - 1] < 0.95f * best) { best = tmin[kCand - 1]; best_c = VEC_PIPE; }
-    d->tune_ms[0] = tmin[0] < tmin[1] ? tmin[0] : tmin[1]; // tile, 4 steps in flight (best of the two issue orders)
-    d->tune_ms[1] = tmin[2] < tmin[3] ? tmin[2] : tmin[3]; // tile, 2 steps in flight
-    d->tune_ms[2] = ncand == kCand ? tmin[4] : 0.f;        // pipe (0: not timed)
-    d->vec_choice = best_c;
-    (void) hipEventDestroy(e0);
-    (void) hipEventDestroy(e1);
-    (void) pool_free(x);
-    (void) pool_free(y);
-    if (hipGetLastError() != hipSuccess) d->vec_choice = VEC_AUTO;
+    const int ncand = (long long) d->vt_staged * 100 >= (long long) d->vt_tiles * 99 ? kVectorCands - 1 : kVectorCands;
+    float tmin[kVectorCands] = {};
+    const RaceEnd end = race_forms<T>(d, ncand, kVectorRounds, tmin, [&](int k) { d->vec_choice = kVectorCand[k]; }, [&](const T *x, T *y) { return (int) launch_vector<T>(d, x, y); });
+    d->vec_choice = VEC_AUTO;
+    if (end == kRaceNoRoom) return SPMV_HIP_OK; // no room to tune: keep the default
+    // the pipe form (int32 columns, global gathers) only on a clear win: a noisy sample -- e.g. another process on the device during create -- must not
+    // cost 30 % on every later launch
+    const int best = vector_rule(tmin, ncand, d->tune_ms);
+    if (end == kRaceTimed) d->vec_choice = best;
     return SPMV_HIP_OK;
 }
 
@@ -151,46 +147,15 @@ static int build_packed_values(spmv_dev *d)
     rc = pack_tiles_run(d, true);
     if (rc || d->pk_tiles == 0) { free_packed_values(d); return rc; }
     if (mode == 1) { d->pk_use = true; return SPMV_HIP_OK; }
-    double *x = nullptr, *y = nullptr;
-    if (pool_malloc((void **) &x, sizeof(double) * (size_t) d->n) != hipSuccess || pool_malloc((void **) &y, sizeof(double) * (size_t) d->m) != hipSuccess) {
-        (void) hipGetLastError();
-        if (x) (void) pool_free(x);
-        free_packed_values(d);
-        return SPMV_HIP_OK; // no room to time: the 8-byte stream stays
-    }
-    fill_value_kernel<double><<<grid_for(d->n, kBlock, d->cus * 8), kBlock, 0, d->stream>>>(d->n, x, 1.0);
-    hipEvent_t e0, e1;
-    (void) hipEventCreate(&e0);
-    (void) hipEventCreate(&e1);
-    constexpr int kCand = 3; // plain winner, packed four deep, packed two deep
-    const int depth[kCand] = {0, 4, 2};
-    float tmin[kCand] = {1e30f, 1e30f, 1e30f};
-    auto set = [&](int k) { d->pk_use = k > 0; d->pk_depth = depth[k]; };
-    for (int k = 0; k < kCand; ++k) { set(k); (void) launch_vector<double>(d, x, y); } // warm every form once
-    for (int round = 0; round < 3; ++round)
-        for (int k = 0; k < kCand; ++k) {
-            set(k);
-            (void) hipEventRecord(e0, d->stream);
-            (void) launch_vector<double>(d, x, y);
-            (void) hipEventRecord(e1, d->stream);
-            (void) hipEventSynchronize(e1);
-            float ms = 0;
-            (void) hipEventElapsedTime(&ms, e0, e1);
-            if (ms < tmin[k]) tmin[k] = ms;
-        }
-    (void) hipEventDestroy(e0);
-    (void) hipEventDestroy(e1);
-    (void) pool_free(x);
-    (void) pool_free(y);
-    // the plain best: this run's sample or autotune_vector's own, whichever is lower
-    float plain_best = tmin[0];
-    for (int k = 0; k < 2; ++k) if (d->tune_ms[k] > 0 && d->tune_ms[k] < plain_best) plain_best = d->tune_ms[k];
-    const int best = tmin[2] < tmin[1] ? 2 : 1;
-    d->pack_ms[0] = plain_best;
-    d->pack_ms[1] = tmin[best];
-    if (hipGetLastError() != hipSuccess || !(tmin[best] < 0.95f * plain_best)) { free_packed_values(d); return SPMV_HIP_OK; }
+    auto depth = [](int k) { return k > 0 ? vec_form(kPackedCand[k])->depth : 0; }; // candidate 0: the plain winner
+    float tmin[kPackedCands];
+    const RaceEnd end = race_forms<double>(d, kPackedCands, kPackedRounds, tmin, [&](int k) { d->pk_use = k > 0; d->pk_depth = depth(k); },
+                                           [&](const double *x, double *y) { return (int) launch_vector<double>(d, x, y); });
+    if (end == kRaceNoRoom) { free_packed_values(d); return SPMV_HIP_OK; } // no room to time: the 8-byte stream stays
+    const int best = packed_rule(tmin, d->tune_ms, d->pack_ms);
+    if (end != kRaceTimed || !best) { free_packed_values(d); return SPMV_HIP_OK; }
     d->pk_use = true;
-    d->pk_depth = depth[best];
+    d->pk_depth = depth(best);
     return SPMV_HIP_OK;
 }
 
@@ -253,38 +218,12 @@ static int autotune_blocked(spmv_dev *d)
     d->blk.form = 0;
     d->blk.tune_ms[0] = d->blk.tune_ms[1] = d->blk.tune_ms[2] = 0;
     if (!d->blk_on || !d->plan.autotune || d->plan.blk_groups != 0) return SPMV_HIP_OK;
-    T *x = nullptr, *y = nullptr;
-    if (pool_malloc((void **) &x, sizeof(T) * (size_t) d->n) != hipSuccess || pool_malloc((void **) &y, sizeof(T) * (size_t) d->m) != hipSuccess) {
-        (void) hipGetLastError();
-        if (x) (void) pool_free(x);
-        return SPMV_HIP_OK; // no room to tune: keep the default
-    }
-    fill_value_kernel<T><<<grid_for(d->n, kBlock, d->cus * 8), kBlock, 0, d->stream>>>(d->n, x, T(1));
-    hipEvent_t e0, e1;
-    (void) hipEventCreate(&e0);
-    (void) hipEventCreate(&e1);
-    constexpr int kForms = 2;
-    float tmin[kForms] = {1e30f, 1e30f};
-    for (int f = 0; f < kForms; ++f) { d->blk.form = f; launch_blocked<T>(d, x, y); } // warm every form once
-    for (int round = 0; round < 4; ++round) // interleaved rounds: min per form
-        for (int f = 0; f < kForms; ++f) {
-            d->blk.form = f;
-            (void) hipEventRecord(e0, d->stream);
-            launch_blocked<T>(d, x, y);
-            (void) hipEventRecord(e1, d->stream);
-            (void) hipEventSynchronize(e1);
-            float ms = 0;
-            (void) hipEventElapsedTime(&ms, e0, e1);
-            if (ms < tmin[f]) tmin[f] = ms;
-        }
-    int best = 0;
-    for (int f = 0; f < kForms; ++f) { d->blk.tune_ms[f] = tmin[f]; if (tmin[f] < tmin[best]) best = f; }
-    d->blk.form = best;
-    (void) hipEventDestroy(e0);
-    (void) hipEventDestroy(e1);
-    (void) pool_free(x);
-    (void) pool_free(y);
-    if (hipGetLastError() != hipSuccess) d->blk.form = 0;
+    float tmin[kBlockedForms];
+    const RaceEnd end = race_forms<T>(d, kBlockedForms, kBlockedRounds, tmin, [&](int f) { d->blk.form = f; }, [&](const T *x, T *y) { launch_blocked<T>(d, x, y); return 0; });
+    d->blk.form = 0;
+    if (end == kRaceNoRoom) return SPMV_HIP_OK; // no room to tune: keep the default
+    const int best = blocked_rule(tmin, d->blk.tune_ms);
+    if (end == kRaceTimed) d->blk.form = best;
     return SPMV_HIP_OK;
 }
 
@@ -295,38 +234,14 @@ static int autotune_rows(spmv_dev *d)
 {
     d->rows_depth = 0;
     if (d->nnz < (1ll << 24) || d->plan.forced || d->vt_tiles <= 0 || d->vt_staged * 2 < d->vt_tiles) return SPMV_HIP_OK;
-    T *x = nullptr, *y = nullptr;
-    if (pool_malloc((void **) &x, sizeof(T) * (size_t) d->n) != hipSuccess || pool_malloc((void **) &y, sizeof(T) * (size_t) d->m) != hipSuccess) {
-        (void) hipGetLastError();
-        if (x) (void) pool_free(x);
-        return SPMV_HIP_OK;
-    }
-    fill_value_kernel<T><<<grid_for(d->n, kBlock, d->cus * 8), kBlock, 0, d->stream>>>(d->n, x, T(1));
-    hipEvent_t e0, e1;
-    (void) hipEventCreate(&e0);
-    (void) hipEventCreate(&e1);
-    const int depth[2] = {4, 2};
-    float tmin[2] = {1e30f, 1e30f};
-    for (int k = 0; k < 2; ++k) { d->rows_depth = depth[k]; (void) launch_vector<T>(d, x, y); }
-    for (int round = 0; round < 2; ++round)
-        for (int k = 0; k < 2; ++k) {
-            d->rows_depth = depth[k];
-            (void) hipEventRecord(e0, d->stream);
-            (void) launch_vector<T>(d, x, y);
-            (void) hipEventRecord(e1, d->stream);
-            (void) hipEventSynchronize(e1);
-            float ms = 0;
-            (void) hipEventElapsedTime(&ms, e0, e1);
-            if (ms < tmin[k]) tmin[k] = ms;
-        }
+    auto depth = [](int k) { return vec_form(kRowsCand[k])->depth; };
+    float tmin[kRowsCands];
+    const RaceEnd end = race_forms<T>(d, kRowsCands, kRowsRounds, tmin, [&](int k) { d->rows_depth = depth(k); }, [&](const T *x, T *y) { return (int) launch_vector<T>(d, x, y); });
+    d->rows_depth = 0;
+    if (end == kRaceNoRoom) return SPMV_HIP_OK;
     d->tune_ms[0] = tmin[0];
     d->tune_ms[1] = tmin[1];
-    d->rows_depth = tmin[1] < tmin[0] ? 2 : 4;
-    (void) hipEventDestroy(e0);
-    (void) hipEventDestroy(e1);
-    (void) pool_free(x);
-    (void) pool_free(y);
-    if (hipGetLastError() != hipSuccess) d->rows_depth = 0;
+    if (end == kRaceTimed) d->rows_depth = depth(rows_rule(tmin));
     return SPMV_HIP_OK;
 }
 
@@ -512,31 +427,7 @@ static int launch(spmv_dev *d, const T *x, T *y)
 template <typename T>
 static double time_schedule(spmv_dev *d, int iters)
 {
-    T *x = nullptr, *y = nullptr;
-    if (pool_malloc((void **) &x, sizeof(T) * (size_t) (d->n > 0 ? d->n : 1)) != hipSuccess || pool_malloc((void **) &y, sizeof(T) * (size_t) (d->m > 0 ? d->m : 1)) != hipSuccess) {
-        (void) hipGetLastError();
-        if (x) (void) pool_free(x);
-        return -1.0;
-    }
-    fill_value_kernel<T><<<grid_for(d->n, kBlock, d->cus * 8), kBlock, 0, d->stream>>>(d->n, x, T(1));
-    hipEvent_t e0, e1;
-    (void) hipEventCreate(&e0);
-    (void) hipEventCreate(&e1);
-    float best = 1e30f;
-    int rc = launch<T>(d, x, y); // warm
-    for (int i = 0; i < iters && !rc; ++i) {
-        (void) hipEventRecord(e0, d->stream);
-        rc = launch<T>(d, x, y);
-        (void) hipEventRecord(e1, d->stream);
-        (void) hipEventSynchronize(e1);
-        float ms = 0;
-        (void) hipEventElapsedTime(&ms, e0, e1);
-        best = ms < best ? ms : best;
-    }
-    (void) hipEventDestroy(e0);
-    (void) hipEventDestroy(e1);
-    (void) pool_free(x);
-    (void) pool_free(y);
-    if (rc || hipGetLastError() != hipSuccess) return -1.0;
-    return (double) best;
+    float best;
+    const RaceEnd end = race_forms<T>(d, 1, iters, &best, [](int) {}, [&](const T *x, T *y) { return launch<T>(d, x, y); });
+    return end == kRaceTimed ? (double) best : -1.0;
 }

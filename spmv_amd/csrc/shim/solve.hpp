@@ -332,16 +332,8 @@ static double solve_time(const Solver &s, spmv_dev *d, int k, int restart, const
     Stager stg{d};
     SolveArgs a;
     if (solve_prepare(s, d, stg, k, restart, b, ldb, x, ldx, opt, 0, 1, a)) return -1.0;
-    std::vector<hipEvent_t> ev;
-    auto done = [&](double mean) {
-        for (hipEvent_t e : ev) (void) hipEventDestroy(e);
-        return mean;
-    };
-    for (int i = 0; i < 2 * iters; ++i) {
-        hipEvent_t e;
-        if (hipEventCreate(&e) != hipSuccess) { (void) hipGetLastError(); fail(SPMV_HIP_E_RUNTIME, "hipEventCreate"); return done(-1.0); }
-        ev.push_back(e);
-    }
+    Events ev(2 * iters);
+    if (!ev.ok) { fail(SPMV_HIP_E_RUNTIME, "hipEventCreate"); return -1.0; }
     int rc = SPMV_HIP_OK;
     for (int run = -warmup; run < iters && !rc; ++run) {
         rc = solve_start(s, d, a, opt->use_x0 != 0);
@@ -351,7 +343,7 @@ static double solve_time(const Solver &s, spmv_dev *d, int k, int restart, const
     }
     const hipError_t e = hipStreamSynchronize(d->stream);
     if (e != hipSuccess) fail(SPMV_HIP_E_RUNTIME, "time_%s: %s", s.name, hipGetErrorString(e));
-    if (rc || e != hipSuccess) return done(-1.0);
+    if (rc || e != hipSuccess) return -1.0;
     double tot = 0;
     for (int i = 0; i < iters; ++i) {
         float ms = 0;
@@ -359,7 +351,7 @@ static double solve_time(const Solver &s, spmv_dev *d, int k, int restart, const
         if (ms_out) ms_out[i] = ms;
         tot += ms;
     }
-    return done(tot / iters);
+    return tot / iters;
 }
 
 extern "C" int spmv_shim_solve(int solver, spmv_dev *d, const void *b, void *x, const spmv_hip_cg_options *opt, spmv_hip_cg_result *res)

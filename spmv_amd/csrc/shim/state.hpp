@@ -492,24 +492,33 @@ static size_t seg_bytes(size_t es) { return es == 2 ? 8 : 16; }
 static bool seg_ok(const void *p, long long ld, size_t es) { return ((uintptr_t) p & (seg_bytes(es) - 1)) == 0 && ((size_t) ld * es) % seg_bytes(es) == 0; }
 static bool seg_cols_ok(int w, size_t es) { return ((size_t) w * es) % seg_bytes(es) == 0; }
 
+// The n hipEvents of one timing (time_events, shim/solve.hpp: solve_time, shim/launch.hpp: race_forms).  ok = all n exist (a failed hipEventCreate is
+// cleared from the runtime's error state).  Destroyed with the owner.
+struct Events {
+    std::vector<hipEvent_t> ev;
+    bool ok = true;
+    explicit Events(int n)
+    {
+        for (hipEvent_t e; ok && (int) ev.size() < n;) {
+            ok = hipEventCreate(&e) == hipSuccess;
+            if (ok) ev.push_back(e);
+            else (void) hipGetLastError();
+        }
+    }
+    ~Events() { for (hipEvent_t e : ev) (void) hipEventDestroy(e); }
+    Events(const Events &) = delete;
+    Events &operator=(const Events &) = delete;
+    hipEvent_t operator[](int i) const { return ev[(size_t) i]; }
+};
+
 // Mean ms of `iters` calls of run() (an operation's own entry point on device operands; 0 on success) after `warmup` untimed ones: hipEvents on
 // the handle's stream around every call, the handle asynchronous for the loop only.  ms_out (iters floats, may be NULL) receives the single
 // times.  < 0 on failure, with the error text set; the events are destroyed on every path.
 template <class Run> static double time_events(spmv_dev *d, const char *what, int warmup, int iters, float *ms_out, Run run)
 {
-    std::vector<hipEvent_t> ev;
-    ev.reserve((size_t) iters + 1);
+    Events ev(iters + 1);
+    if (!ev.ok) { fail(SPMV_HIP_E_RUNTIME, "hipEventCreate"); return -1.0; }
     const int keep_async = d->async;
-    auto done = [&](double mean) {
-        d->async = keep_async;
-        for (hipEvent_t e : ev) (void) hipEventDestroy(e);
-        return mean;
-    };
-    for (int i = 0; i <= iters; ++i) {
-        hipEvent_t e;
-        if (hipEventCreate(&e) != hipSuccess) { (void) hipGetLastError(); fail(SPMV_HIP_E_RUNTIME, "hipEventCreate"); return done(-1.0); }
-        ev.push_back(e);
-    }
     d->async = 1;
     int rc = SPMV_HIP_OK;
     for (int i = 0; i < warmup && !rc; ++i) rc = run();
@@ -519,8 +528,9 @@ template <class Run> static double time_events(spmv_dev *d, const char *what, in
     }
     (void) hipEventRecord(ev[iters], d->stream);
     const hipError_t e = hipStreamSynchronize(d->stream);
+    d->async = keep_async;
     if (e != hipSuccess) fail(SPMV_HIP_E_RUNTIME, "%s: %s", what, hipGetErrorString(e));
-    if (rc || e != hipSuccess) return done(-1.0);
+    if (rc || e != hipSuccess) return -1.0;
     double tot = 0;
     for (int i = 0; i < iters; ++i) {
         float ms = 0;
@@ -528,7 +538,7 @@ template <class Run> static double time_events(spmv_dev *d, const char *what, in
         if (ms_out) ms_out[i] = ms;
         tot += ms;
     }
-    return done(tot / iters);
+    return tot / iters;
 }
 
 extern "C" int spmv_shim_device_count(void)
