@@ -972,6 +972,82 @@ int spmv_hip_gmres(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE 
                    const void *Matrix_Val, const void *B, void *X, int restart,
                    const spmv_hip_cg_options *opt, spmv_hip_cg_result *res);
 
+/* ---- mixed-precision conjugate gradients: an fp64 solution from fp32 iterations ------------------
+ * Conjugate gradients with reliable updates (Clark et al., "Solving lattice QCD systems of equations using mixed precision solvers on GPUs",
+ * 2010) on a PAIR of handles: `high` holds the matrix in fp64, `low` the same pattern with the values rounded to float; the caller created
+ * both and keeps them in step (spmv_hip_update_values on each).  Every iteration is spmv_hip_cg's in float on `low`'s multiply and gathers a
+ * partial solution y; when a SEGMENT of iterations ends, x + y goes through `high`'s fp64 multiply once, the true residual b - A (x + y)
+ * replaces the recurrence's, and the search direction p is KEPT -- restarting it at every update (iterative refinement around an fp32 solve)
+ * costs about twice the iterations.  B and X are fp64; every return carries the TRUE fp64 rr of the X it returns.
+ *   - There are no CSR arguments: the call solves with the two RESIDENT matrices as they are.
+ *   - B and X: m doubles; Dinv: m FLOATS; host or device pointers, staged through `high`'s buffers as spmv_hip_cg stages them; B and X must
+ *     not overlap.  The call is synchronous and returns SPMV_HIP_OK whenever the solve ran.  rtol, atol, max_iterations, check_every, use_x0
+ *     and history have spmv_hip_cg's meaning and validation; m = 0 and bb = 0 behave as there.
+ *   - update_drop: a segment ends when the recurrence's rr has fallen to update_drop^2 times its value at the segment's start; 0 means
+ *     SPMV_HIP_CG_MIXED_UPDATE_DROP.  update_every: a segment also ends after that many iterations; 0: no such cap.
+ *   - status: spmv_hip_cg's four and SPMV_HIP_CG_STAGNATED: the narrowed residual is all zeros while rr is above the threshold, or an update
+ *     that the recurrence called progress did not lower the true rr -- fp32 iterations cannot improve this x further (`low` may not be
+ *     `high`'s matrix, or rtol is below what the fp64 multiply resolves).  `updates` counts the committed updates.
+ *   - Workspace: xn, q64 (m doubles each), r, p, q, y (m floats each), six arrays of 1024 partial sums and the state in ONE block of
+ *     2 * up256(8 m) + 4 * up256(4 m) + 6 * 8192 + 256 bytes (up256: rounded up to a multiple of 256), owned by `high`: allocated at the
+ *     first call, freed at `high`'s destroy / clear / re-inspection, counted in `high`'s device_bytes; the history's device copy likewise.
+ *     The other solvers' workspaces are not shared or grown.  `low` is not changed; its own spmv_hip_cg workspace is not used.
+ *   - Errors (SPMV_HIP_E_ARG, X untouched): `high` not fp64 or `low` not fp32; m, n or nnz that differ between the handles, or m != n;
+ *     handles on different devices or streams; either handle multi-GPU, host_rows or created with option "reorder"; NULL opt or res; NULL B
+ *     or X when m > 0; spmv_hip_cg's option errors; update_drop outside [0, 1) or NaN; update_every < 0.  A cleared or failed handle on
+ *     either side: SPMV_HIP_E_NOSTATE.
+ *   - The narrowed residual is not scaled: elements of r64 below 2^-126 lose bits on narrowing, and one above FLT_MAX becomes an infinity
+ *     (NONFINITE).
+ *
+ * The arithmetic contract -- bits, not a tolerance; tests/cg_mixed_cases.py restates it in numpy.  "dot" is spmv_hip_cg's dot over m fp64
+ * elements, or over fp32 elements widened.  All scalars are fp64.  Every product, sum and quotient is separate (no fma).  "narrow" is
+ * round-to-nearest-even to float; widening is exact.  thr = max(rtol^2 * bb, atol^2).
+ *   start:     x = X (use_x0) or 0;  q64 = A_high*x through `high`'s own multiply (only with use_x0);  r64 = b - q64, or b;
+ *              bb = dot(b,b);  rr = dot(r64,r64);  non-finite bb or rr -> NONFINITE;  bb == 0 -> X = 0, CONVERGED;  rr <= thr -> CONVERGED;
+ *              max_iterations == 0 -> MAX_ITERATIONS;  else the first segment starts.
+ *   segment start:  r = narrow(r64);  y = 0;  z = Dinv*r (an fp32 multiply; z = r without Dinv);  rz = dot(r,z);  rs = dot(r,r);  seg = rs;  n = 0;
+ *              non-finite rs or rz -> NONFINITE;  rs == 0 -> STAGNATED;  rz <= 0 -> BREAKDOWN;
+ *              p = z in the first segment and behind a segment that ended "exact"; otherwise p is KEPT as the last iteration left it.
+ *   iteration (spmv_hip_cg's with T = float, on y in the place of x):
+ *              q = A_low*p through `low`'s own multiply;  pq = dot(p,q);  non-finite pq or rz -> NONFINITE;  pq <= 0 -> BREAKDOWN;
+ *              alpha = float(rz / pq), non-finite -> NONFINITE;  y = y + alpha*p;  r = r - alpha*q;  z as above;
+ *              rzn = dot(r,z);  rs = dot(r,r);  iterations and n each increase by one;  then, in this order:
+ *              1. non-finite rs or rzn -> NONFINITE;  2. rs == 0 ends the segment "exact", p untouched;  3. rzn <= 0 -> BREAKDOWN;
+ *              4. beta = float(rzn / rz), non-finite -> NONFINITE;  5. p = z + beta*p;  rz = rzn;
+ *              6. the segment ends on the first that holds: "estimate": rs <= thr;  "drop": rs <= (update_drop*update_drop)*seg;
+ *                 "every": n == update_every;  "budget": iterations == max_iterations.
+ *              BREAKDOWN or NONFINITE inside a segment ends the solve with X = x of the last committed update, y discarded, and rr that x's.
+ *   update:    xn = x + widen(y), an fp64 add;  q64 = A_high*xn;  r64n = b - q64;  rrn = dot(r64n,r64n);
+ *              non-finite rrn -> NONFINITE, x kept;  rrn >= rr behind a segment that ended "exact", "estimate" or "drop" -> STAGNATED, x and rr
+ *              kept;  otherwise commit: x = xn, r64 = r64n, rr = rrn, updates + 1;  then rr <= thr -> CONVERGED;  else iterations ==
+ *              max_iterations -> MAX_ITERATIONS;  else a new segment starts.
+ *   history:   history[0] is the initial rr;  history[k] is rs after iteration k;  where a committed update follows iteration k, the
+ *              committed rr overwrites history[k].
+ *   Consequences: X, status, iterations, updates, rr and history are bit-identical run to run, for every check_every, for host or device
+ *   pointers and every pointer alignment; Dinv = all ones gives the bits of Dinv = NULL; a run with max_iterations = k returns what a longer
+ *   run held after iteration k plus one update (unless the handles were created with option "deterministic" = 0). */
+enum { SPMV_HIP_CG_STAGNATED = 4 };   /* returned by spmv_hip_cg_mixed alone */
+/* the default update_drop: tools/cg_mixed_bench.py's sweep over {0.5, 0.1, 0.01} */
+#define SPMV_HIP_CG_MIXED_UPDATE_DROP 0.01
+typedef struct spmv_hip_cg_mixed_options {
+    double rtol, atol;        /* stop when the TRUE rr <= max(rtol^2 * bb, atol^2) */
+    int max_iterations;       /* >= 0 */
+    int check_every;          /* iterations enqueued between two looks at the device's state; 0 = default */
+    int use_x0;               /* 0: start from x = 0 (X is only written); != 0: X holds the initial guess */
+    const float *Dinv;        /* NULL, or m floats, host or device: z = Dinv .* r in the fp32 recurrence */
+    double *history;          /* NULL, or HOST array of max_iterations + 1 doubles */
+    double update_drop;       /* 0 = default; else 0 < update_drop < 1 */
+    int update_every;         /* >= 0; 0 = no cap on a segment's length */
+} spmv_hip_cg_mixed_options;
+typedef struct spmv_hip_cg_mixed_result {
+    int status;               /* SPMV_HIP_CG_CONVERGED 0, _MAX_ITERATIONS 1, _BREAKDOWN 2, _NONFINITE 3, _STAGNATED 4 */
+    int iterations;           /* fp32 iterations applied */
+    int updates;              /* fp64 updates committed */
+    double rr, bb;            /* the TRUE <b - A x, b - A x> of the returned x, and <b,b> */
+} spmv_hip_cg_mixed_result;
+int spmv_hip_cg_mixed(spmv_Handle_t high, spmv_Handle_t low, const double *B, double *X,
+                      const spmv_hip_cg_mixed_options *opt, spmv_hip_cg_mixed_result *res);
+
 #endif /* SPMV_HIP_EXT_H */
 
 #if defined(__cplusplus)

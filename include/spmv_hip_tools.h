@@ -115,6 +115,14 @@ double spmv_hip_time_cg_columns_iterations(spmv_Handle_t handle, int k, const vo
    SPMV_HIP_GMRES_RESTART_MAX.  The same arguments otherwise, the same rules, the same return value; X holds the iterate of the last FINISHED
    cycle. */
 double spmv_hip_time_gmres_iterations(spmv_Handle_t handle, const void *B, void *X, int restart, const struct spmv_hip_cg_options *opt, int warmup, int iters, float *ms_out);
+/* spmv_hip_cg_mixed's iterations, timed as spmv_hip_time_cg_iterations times spmv_hip_cg's: an iteration is `low`'s multiply, cg_dot,
+   cg_update, mix_direction, and behind every opt->update_every-th one (never when that is 0) the update: mix_try, `high`'s multiply,
+   mix_residual, mix_resume.  The stop tests are off and every update is committed, so what is enqueued does not depend on the data.  B and
+   X: DEVICE arrays of m doubles, opt->Dinv a DEVICE array of m floats or NULL; X holds the x of the last update.  The pair rules of
+   spmv_hip_cg_mixed; rtol, atol, check_every, update_drop and history are not used.  Returns the mean ms per run, < 0 on error. */
+struct spmv_hip_cg_mixed_options;
+double spmv_hip_time_cg_mixed_iterations(spmv_Handle_t high, spmv_Handle_t low, const double *B, double *X, const struct spmv_hip_cg_mixed_options *opt, int warmup, int iters,
+                                         float *ms_out);
 /* out[i] = the fp64 square root of in[i] exactly as spmv_hip_gmres's kernels take it (a kernel of the same translation unit, the same
    compiler flags): n doubles each, DEVICE pointers on the current device; synchronous.  For the test that holds it against a correctly
    rounded square root; SPMV_HIP_E_ARG for n < 0, NULL or host pointers. */

@@ -14,6 +14,7 @@
 // Everything here is written once; a solver is a Solver: its sizes, its workspace, what its start and one iteration enqueue and how its
 // state reads.  k, ldb and ldx are 1 for the single solves.  spmv_hip_gmres (kernels/gmres.hpp) is the fourth: its workspace has `restart`
 // vectors more than its fixed three, and it alone has a `finish`: the columns of an unfinished cycle are applied to x behind the last look.
+// spmv_hip_cg_mixed (kernels/cg_mixed.hpp), at the end of this file, is not a Solver: it solves on a pair of handles with vectors of two types.
 #pragma once
 
 // what the host reads out of a solver's state, per column
@@ -397,4 +398,182 @@ extern "C" int spmv_shim_gmres_sqrt(const double *in, double *out, long long n)
     if (e != hipSuccess) return fail(SPMV_HIP_E_RUNTIME, "gmres_sqrt: launch: %s", hipGetErrorString(e));
     HIP_TRY(hipStreamSynchronize(nullptr));
     return SPMV_HIP_OK;
+}
+
+// ------------------------------------------------------------------------------------ spmv_hip_cg_mixed
+// Conjugate gradients with reliable updates on a PAIR of handles (kernels/cg_mixed.hpp): the iterations are spmv_hip_cg's in float, on `lo`'s
+// multiply and on the partial solution y; when a segment ends, x + y goes through `hi`'s fp64 multiply and the TRUE residual replaces the
+// recurrence's.  The loop is solve_run's -- check_every iterations, one look -- with one thing more: a look that finds a segment's end enqueues
+// the update (mix_try, hi's multiply, mix_residual, mix_resume) and the next batch behind it with no look in between; mix_resume re-arms the
+// loop on the device, or ends the solve, in which case that batch's kernels return at once.  The iterations are numbered from the APPLIED
+// count of the look (the arrays of <r,z> alternate by it), and so is the budget.  The workspace is hi's, of this solver's own; lo is only
+// multiplied with.
+
+// bytes of the workspace: two vectors of m doubles, four of m floats, the partial arrays, the state
+static size_t mix_vec_bytes(const spmv_dev *d, size_t elem) { return (elem * (size_t) d->m + 255) & ~(size_t) 255; }
+static size_t mix_tail_bytes() { return sizeof(double) * kMixPartArrays * kCgMaxParts + 256; }
+
+static const char *mix_pair_error(const spmv_dev *hi, const spmv_dev *lo)
+{
+    if (hi->vsize != sizeof(double) || lo->vsize != sizeof(float)) return "`high` must be an fp64 handle and `low` an fp32 one";
+    if (hi->m != lo->m || hi->n != lo->n || hi->nnz != lo->nnz) return "m, n or nnz differ between the two handles";
+    if (hi->m != hi->n) return "the matrix is not square";
+    if (hi->device != lo->device) return "the two handles are on different devices";
+    if (hi->stream != lo->stream) return "the two handles are on different streams";
+    return nullptr;
+}
+
+static int mix_prepare(spmv_dev *hi, Stager &stg, const double *b, double *x, const spmv_hip_cg_mixed_options *opt, size_t hist_entries, int nostop, MixArgs &a)
+{
+    static_assert(sizeof(MixState) <= 256, "the state's room behind the partial arrays");
+    const size_t v64 = mix_vec_bytes(hi, sizeof(double)), v32 = mix_vec_bytes(hi, sizeof(float)), m = (size_t) hi->m;
+    if (!hi->mix_ws) {
+        ALLOC_TRY(hi, &hi->mix_ws, kMixVectors64 * v64 + kMixVectors32 * v32 + mix_tail_bytes(), false);
+        HIP_TRY(hipMemsetAsync((char *) hi->mix_ws + kMixVectors64 * v64 + kMixVectors32 * v32, 0, mix_tail_bytes(), hi->stream));
+    }
+    char *ws = (char *) hi->mix_ws, *w32 = ws + kMixVectors64 * v64;
+    a.m = hi->m;
+    const long long chunks = ((long long) hi->m + kCgChunk - 1) / kCgChunk;
+    a.parts = (int) (chunks < kCgMaxParts ? chunks : kCgMaxParts);
+    a.span = (long long) kCgChunk * (((long long) hi->m + (long long) kCgChunk * a.parts - 1) / ((long long) kCgChunk * a.parts));
+    a.xn = (double *) (ws + kMixVecXn * v64);
+    a.q64 = (double *) (ws + kMixVecQ64 * v64);
+    a.r = (float *) (w32 + kMixVecR * v32);
+    a.p = (float *) (w32 + kMixVecP * v32);
+    a.q = (float *) (w32 + kMixVecQ * v32);
+    a.y = (float *) (w32 + kMixVecY * v32);
+    a.part = (double *) (w32 + kMixVectors32 * v32);
+    a.state = (MixState *) (a.part + (size_t) kMixPartArrays * kCgMaxParts);
+    a.rtol2 = opt->rtol * opt->rtol;
+    a.atol2 = opt->atol * opt->atol;
+    const double drop = opt->update_drop > 0 ? opt->update_drop : SPMV_HIP_CG_MIXED_UPDATE_DROP;
+    a.drop2 = drop * drop;
+    a.every = opt->update_every;
+    a.budget = opt->max_iterations;
+    a.nostop = nostop;
+    a.b = b;
+    a.x = x;
+    a.dinv = opt->Dinv;
+    int rc;
+    long long ld = 1, ldb = 1, ldx = 1;
+    if ((rc = stg.in(hi->stage[STAGE_CG_B], a.b, ldb, m, 1)) || (rc = stg.in(hi->stage[STAGE_CG_DINV], a.dinv, ld, m, 1, sizeof(float))) || (rc = stg.out(hi->stage[STAGE_CG_X], a.x, ldx, m, 1)))
+        return rc;
+    if (a.x != x && opt->use_x0) HIP_TRY(hipMemcpyAsync(a.x, x, sizeof(double) * m, hipMemcpyHostToDevice, hi->stream));
+    a.wide = wide_ok(a.b, 1, 16) && wide_ok(a.x, 1, 16) && (!a.dinv || wide_ok(a.dinv, 1, 16));
+    a.hist = nullptr;
+    if (hist_entries > 0) {
+        if ((rc = stg.reserve(hi->mix_hist, sizeof(double) * hist_entries))) return rc;
+        a.hist = (double *) hi->mix_hist.p;
+    }
+    return SPMV_HIP_OK;
+}
+
+static int mix_launched(hipError_t e) { return e == hipSuccess ? SPMV_HIP_OK : fail(SPMV_HIP_E_RUNTIME, "cg_mixed: launch: %s", hipGetErrorString(e)); }
+
+// the state zeroed, (q64 = A_high x0,) mix_residual + mix_resume
+static int mix_start(spmv_dev *hi, const MixArgs &a, bool use_x0)
+{
+    int rc;
+    HIP_TRY(hipMemsetAsync(a.state, 0, sizeof(MixState), hi->stream));
+    if (use_x0 && (rc = launch<double>(hi, a.x, a.q64))) return rc;
+    return mix_launched(mix_start_launch(a, use_x0, hi->stream));
+}
+
+// q = A_low p, then cg_dot, cg_update and mix_direction
+static int mix_iteration(spmv_dev *hi, spmv_dev *lo, const MixArgs &a, int k)
+{
+    const int rc = launch<float>(lo, a.p, a.q);
+    return rc ? rc : mix_launched(mix_iteration_launch(a, k, hi->stream));
+}
+
+// behind iteration k: xn = x + y, q64 = A_high xn, mix_residual + mix_resume
+static int mix_update(spmv_dev *hi, const MixArgs &a, int k, int update)
+{
+    int rc;
+    if ((rc = mix_launched(mix_try_launch(a, hi->stream))) || (rc = launch<double>(hi, a.xn, a.q64))) return rc;
+    return mix_launched(mix_update_launch(a, k, update, hi->stream));
+}
+
+extern "C" int spmv_shim_solve_mixed(spmv_dev *hi, spmv_dev *lo, const double *b, double *x, const spmv_hip_cg_mixed_options *opt, spmv_hip_cg_mixed_result *res)
+{
+    if (!hi || !hi->built || !lo || !lo->built) return fail(SPMV_HIP_E_NOSTATE, "cg_mixed: schedule not built");
+    if (!opt || !res) return fail(SPMV_HIP_E_ARG, "cg_mixed: opt or res is NULL");
+    if (const char *why = mix_pair_error(hi, lo)) return fail(SPMV_HIP_E_ARG, "cg_mixed: %s", why);
+    if (hi->m > 0 && (!b || !x)) return fail(SPMV_HIP_E_ARG, "cg_mixed: B or X is NULL");
+    res->status = SPMV_HIP_CG_CONVERGED;
+    res->iterations = res->updates = 0;
+    res->rr = res->bb = 0;
+    if (hi->m == 0) return SPMV_HIP_OK;
+    DeviceGuard guard(hi->device);
+    if (!guard.ok) return fail(SPMV_HIP_E_RUNTIME, "hipSetDevice(%d) failed", hi->device);
+    Stager stg{hi};
+    MixArgs a;
+    int rc = mix_prepare(hi, stg, b, x, opt, opt->history ? (size_t) opt->max_iterations + 1 : 0, 0, a);
+    if (rc || (rc = mix_start(hi, a, opt->use_x0 != 0))) return rc;
+    const int every = opt->check_every > 0 ? opt->check_every : 8;
+    MixState hs;
+    // every look but the last is followed by an applied iteration or by an update
+    for (long long looks = 0;; ++looks) {
+        HIP_TRY(hipMemcpyAsync(&hs, a.state, sizeof hs, hipMemcpyDeviceToHost, hi->stream));
+        HIP_TRY(hipStreamSynchronize(hi->stream));
+        const bool ended = hs.s.end_update || hs.s.end_direction;
+        int k = hs.s.iterations;
+        if ((ended && !hs.segment_end) || (!ended && k >= opt->max_iterations)) break;
+        if (looks > 2ll * opt->max_iterations + 2) return fail(SPMV_HIP_E_RUNTIME, "cg_mixed: the device's state does not advance");
+        if (ended && (rc = mix_update(hi, a, k, hs.updates + 1))) return rc;
+        const int stop = opt->max_iterations - k < every ? opt->max_iterations : k + every;
+        while (k < stop)
+            if ((rc = mix_iteration(hi, lo, a, ++k))) return rc;
+    }
+    const bool ended = hs.s.end_update || hs.s.end_direction;
+    res->status = ended ? hs.s.status : SPMV_HIP_CG_MAX_ITERATIONS;
+    res->iterations = hs.s.iterations;
+    res->updates = hs.updates;
+    res->rr = hs.s.rr;
+    res->bb = hs.s.bb;
+    if (ended && hs.s.status == SPMV_HIP_CG_CONVERGED && hs.s.bb == 0) HIP_TRY(hipMemsetAsync(a.x, 0, sizeof(double) * (size_t) hi->m, hi->stream)); // B = 0: x = 0
+    if (opt->history) HIP_TRY(hipMemcpyAsync(opt->history, a.hist, sizeof(double) * ((size_t) hs.s.iterations + 1), hipMemcpyDeviceToHost, hi->stream));
+    if ((rc = stg.finish())) return rc;
+    HIP_TRY(hipStreamSynchronize(hi->stream)); // the call is synchronous whatever the handle's async setting
+    return SPMV_HIP_OK;
+}
+
+// solve_time for the pair: the stop tests off, an update behind every opt->update_every-th iteration (none when that is 0), so that what is
+// enqueued does not depend on the data; every update is committed
+extern "C" double spmv_shim_time_solve_mixed(spmv_dev *hi, spmv_dev *lo, const double *b, double *x, const spmv_hip_cg_mixed_options *opt, int warmup, int iters, float *ms_out)
+{
+    if (!hi || !hi->built || !lo || !lo->built || !opt || iters <= 0 || warmup < 0 || opt->max_iterations < 1 || hi->m <= 0 || opt->update_every < 0) {
+        fail(SPMV_HIP_E_ARG, "time_cg_mixed: bad arguments");
+        return -1.0;
+    }
+    if (const char *why = mix_pair_error(hi, lo)) { fail(SPMV_HIP_E_ARG, "time_cg_mixed: %s", why); return -1.0; }
+    if (!is_device_ptr(b) || !is_device_ptr(x) || (opt->Dinv && !is_device_ptr(opt->Dinv))) { fail(SPMV_HIP_E_ARG, "time_cg_mixed: B, X and Dinv must be device pointers"); return -1.0; }
+    DeviceGuard guard(hi->device);
+    if (!guard.ok) { fail(SPMV_HIP_E_RUNTIME, "hipSetDevice(%d) failed", hi->device); return -1.0; }
+    Stager stg{hi};
+    MixArgs a;
+    if (mix_prepare(hi, stg, b, x, opt, 0, 1, a)) return -1.0;
+    Events ev(2 * iters);
+    if (!ev.ok) { fail(SPMV_HIP_E_RUNTIME, "hipEventCreate"); return -1.0; }
+    int rc = SPMV_HIP_OK;
+    for (int run = -warmup; run < iters && !rc; ++run) {
+        rc = mix_start(hi, a, opt->use_x0 != 0);
+        if (run >= 0) (void) hipEventRecord(ev[2 * run], hi->stream);
+        for (int it = 1, updates = 0; it <= opt->max_iterations && !rc; ++it) {
+            rc = mix_iteration(hi, lo, a, it);
+            if (!rc && opt->update_every > 0 && it % opt->update_every == 0) rc = mix_update(hi, a, it, ++updates);
+        }
+        if (run >= 0) (void) hipEventRecord(ev[2 * run + 1], hi->stream);
+    }
+    const hipError_t e = hipStreamSynchronize(hi->stream);
+    if (e != hipSuccess) fail(SPMV_HIP_E_RUNTIME, "time_cg_mixed: %s", hipGetErrorString(e));
+    if (rc || e != hipSuccess) return -1.0;
+    double tot = 0;
+    for (int i = 0; i < iters; ++i) {
+        float ms = 0;
+        (void) hipEventElapsedTime(&ms, ev[2 * i], ev[2 * i + 1]);
+        if (ms_out) ms_out[i] = ms;
+        tot += ms;
+    }
+    return tot / iters;
 }

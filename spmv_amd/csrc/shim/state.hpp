@@ -315,6 +315,10 @@ struct spmv_dev {
     void *gmres_ws = nullptr;
     int gmres_restart = 0;
     StageBuf gmres_hist;
+    // spmv_hip_cg_mixed (shim/solve.hpp), on the fp64 handle of the pair: xn, q64 (m doubles each), r, p, q, y (m floats each), six partial
+    // arrays and the state in ONE block of the solver's own, allocated at the first call; its history likewise
+    void *mix_ws = nullptr;
+    StageBuf mix_hist;
     // spmv_hip_spmv_transpose (shim/transpose.hpp): A^T as a matrix of its own (n x m), planned and built like any; perm[p] = our index of its entry p.
     // val_gen counts spmv_shim_update_values calls; A^T's values are gathered again when tr_gen falls behind it.
     spmv_dev *tr = nullptr;

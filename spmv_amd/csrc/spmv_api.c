@@ -1531,3 +1531,35 @@ double spmv_hip_time_cg_columns_iterations(spmv_Handle_t h, int k, const void *B
     if (spmm_columns(h, st, where)) return -1.0;
     return report_time(spmv_shim_time_solve_columns(st->dev, k, B, ldb, X, ldx, opt, warmup, iters, ms_out), where);
 }
+
+/* ---------------------------------------------------------------- mixed-precision conjugate gradients on a pair of handles */
+/* the option rules ahead of the gates, then both gates: the fp64 handle's state in *hi, the fp32 one's in *lo; what a pair must share is the shim's to check */
+static int cg_mixed_pair(spmv_Handle_t high, spmv_Handle_t low, const char *where, const spmv_hip_cg_mixed_options *opt, const void *res, spmv_hip_state **hi, spmv_hip_state **lo)
+{
+    int rc;
+    if (!high || !low) return refuse(SPMV_HIP_E_ARG, where, "handle is NULL");
+    if (!opt || !res) return refuse(SPMV_HIP_E_ARG, where, "opt or res is NULL");
+    if (opt->max_iterations < 0 || opt->check_every < 0) return refuse(SPMV_HIP_E_ARG, where, "need max_iterations >= 0 and check_every >= 0");
+    if (!(opt->rtol >= 0) || !(opt->atol >= 0)) return refuse(SPMV_HIP_E_ARG, where, "rtol and atol must be >= 0 (and not NaN)");
+    if (!(opt->update_drop >= 0) || !(opt->update_drop < 1)) return refuse(SPMV_HIP_E_ARG, where, "need 0 <= update_drop < 1 (0: the default)");
+    if (opt->update_every < 0) return refuse(SPMV_HIP_E_ARG, where, "need update_every >= 0");
+    if ((rc = resident_state(high, where, RESIDENT_NOT_REORDERED, hi)) || (rc = resident_state(low, where, RESIDENT_NOT_REORDERED, lo))) return rc;
+    return SPMV_HIP_OK;
+}
+
+int spmv_hip_cg_mixed(spmv_Handle_t high, spmv_Handle_t low, const double *B, double *X, const spmv_hip_cg_mixed_options *opt, spmv_hip_cg_mixed_result *res)
+{
+    const char *where = "cg_mixed";
+    spmv_hip_state *hi, *lo;
+    const int rc = cg_mixed_pair(high, low, where, opt, res, &hi, &lo);
+    return rc ? rc : report(spmv_shim_solve_mixed(hi->dev, lo->dev, B, X, opt, res), where);
+}
+
+double spmv_hip_time_cg_mixed_iterations(spmv_Handle_t high, spmv_Handle_t low, const double *B, double *X, const spmv_hip_cg_mixed_options *opt, int warmup, int iters,
+                                         float *ms_out)
+{
+    const char *where = "time_cg_mixed_iterations";
+    spmv_hip_state *hi, *lo;
+    if (cg_mixed_pair(high, low, where, opt, opt, &hi, &lo)) return -1.0;
+    return report_time(spmv_shim_time_solve_mixed(hi->dev, lo->dev, B, X, opt, warmup, iters, ms_out), where);
+}

@@ -226,6 +226,11 @@ int spmv_shim_gmres_sqrt(const double *in, double *out, long long n);
 int spmv_shim_solve_columns(spmv_dev *d, int k, const void *b, long long ldb, void *x, long long ldx, const spmv_hip_cg_options *opt, spmv_hip_cg_result *res);
 double spmv_shim_time_solve_columns(spmv_dev *d, int k, const void *b, long long ldb, void *x, long long ldx, const spmv_hip_cg_options *opt, int warmup, int iters,
                                     float *ms_out);
+/* spmv_hip_cg_mixed: fp32 conjugate-gradient iterations on lo's multiply, the solution and the true residual in fp64 through hi's (hi fp64, lo
+ * fp32, the same m = n and nnz, device and stream: SPMV_HIP_E_ARG otherwise).  B and X m doubles, opt->Dinv m floats, host or device pointers.
+ * The workspace is hi's and this solver's own; lo is only multiplied with.  The timer: an update behind every opt->update_every-th iteration */
+int spmv_shim_solve_mixed(spmv_dev *hi, spmv_dev *lo, const double *b, double *x, const spmv_hip_cg_mixed_options *opt, spmv_hip_cg_mixed_result *res);
+double spmv_shim_time_solve_mixed(spmv_dev *hi, spmv_dev *lo, const double *b, double *x, const spmv_hip_cg_mixed_options *opt, int warmup, int iters, float *ms_out);
 
 /* the resident CSR arrays (device pointers; ColIdx may be NULL after spmv_shim_release_columns) */
 void spmv_shim_matrix_arrays(const spmv_dev *d, const int **rowptr, const int **colidx, const void **val);

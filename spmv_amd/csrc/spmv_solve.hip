@@ -4,6 +4,8 @@
 // once; per iteration cg_iteration_launch behind q = A p, or bicg_first_launch behind v = A ph and bicg_second_launch behind t = A sh;
 // spmv_hip_cg_columns: ccg_start_launch, and ccg_iteration_launch behind q = A p for all k columns.  spmv_hip_gmres (kernels/gmres.hpp):
 // gmres_start_launch, gmres_step_launch behind w = A z, and at a cycle's end gmres_apply_launch, then gmres_restart_launch behind w = A x.
+// spmv_hip_cg_mixed (kernels/cg_mixed.hpp): mix_start_launch, mix_iteration_launch behind q = A_low p, and at a segment's end mix_try_launch,
+// then mix_update_launch behind q64 = A_high xn.
 #include <hip/hip_runtime.h>
 
 #include "kernels/common.hpp"
@@ -11,6 +13,7 @@
 #include "kernels/bicgstab.hpp"
 #include "kernels/cg_columns.hpp"
 #include "kernels/gmres.hpp"
+#include "kernels/cg_mixed.hpp"
 
 namespace spmv {
 
@@ -190,5 +193,58 @@ hipError_t gmres_sqrt_launch(const double *in, double *out, long long n, hipStre
     gmres_sqrt_kernel<double><<<(unsigned) ((n + kBlock - 1) / kBlock), kBlock, 0, stream>>>(in, out, n);
     return hipGetLastError();
 }
+
+// ---- spmv_hip_cg_mixed
+template <bool WIDE, bool DINV>
+static void mix_start_t(const MixArgs &a, bool use_x0, hipStream_t stream)
+{
+    const unsigned grid = (unsigned) a.parts;
+    if (use_x0) mix_residual_kernel<WIDE, DINV, 1><<<grid, kBlock, 0, stream>>>(a.m, a.span, 0, a.b, a.x, a.q64, a.dinv, a.r, a.part);
+    else mix_residual_kernel<WIDE, DINV, 0><<<grid, kBlock, 0, stream>>>(a.m, a.span, 0, a.b, a.x, a.q64, a.dinv, a.r, a.part);
+    mix_resume_kernel<WIDE, DINV, true><<<grid, kBlock, 0, stream>>>(a.m, a.span, 0, 0, a.budget, a.xn, a.x, a.r, a.dinv, a.p, a.y, a.part, a.state, a.hist, a.rtol2, a.atol2, a.nostop);
+}
+
+// cg_dot<float> and cg_update<float> are spmv_hip_cg's own, on y in the place of x
+template <bool WIDE, bool DINV>
+static void mix_iteration_t(const MixArgs &a, int k, hipStream_t stream)
+{
+    const unsigned grid = (unsigned) a.parts;
+    cg_dot_kernel<float><<<grid, kBlock, 0, stream>>>(a.m, a.span, a.p, a.q, a.part + (size_t) kCgPartPQ * kCgMaxParts, &a.state->s.end_direction);
+    cg_update_kernel<float, WIDE, DINV><<<grid, kBlock, 0, stream>>>(a.m, a.span, k, a.p, a.q, a.y, a.r, a.dinv, a.part, &a.state->s, a.nostop);
+    mix_direction_kernel<WIDE, DINV><<<grid, kBlock, 0, stream>>>(a.m, a.span, k, a.r, a.dinv, a.p, a.part, a.state, a.hist, a.drop2, a.every, a.budget, a.nostop);
+}
+
+template <bool WIDE, bool DINV>
+static void mix_try_t(const MixArgs &a, hipStream_t stream)
+{
+    mix_try_kernel<WIDE><<<(unsigned) a.parts, kBlock, 0, stream>>>(a.m, a.span, a.x, a.y, a.xn, a.state);
+}
+
+template <bool WIDE, bool DINV>
+static void mix_update_t(const MixArgs &a, int k, int update, hipStream_t stream)
+{
+    const unsigned grid = (unsigned) a.parts;
+    mix_residual_kernel<WIDE, DINV, 2><<<grid, kBlock, 0, stream>>>(a.m, a.span, k, a.b, a.x, a.q64, a.dinv, a.r, a.part);
+    mix_resume_kernel<WIDE, DINV, false><<<grid, kBlock, 0, stream>>>(a.m, a.span, k, update, a.budget, a.xn, a.x, a.r, a.dinv, a.p, a.y, a.part, a.state, a.hist, a.rtol2, a.atol2, a.nostop);
+}
+
+static bool mix_ok(const MixArgs &a)
+{
+    return a.m > 0 && a.parts >= 1 && a.parts <= kCgMaxParts && a.span * a.parts >= a.m && a.b && a.x && a.xn && a.q64 && a.r && a.p && a.q && a.y && a.part && a.state;
+}
+
+// the checked launch of the instantiation of F that a.wide / a.dinv select
+#define MIX_LAUNCH(F, ok, ...)                                                                       \
+    do {                                                                                             \
+        if (!mix_ok(a) || !(ok)) return hipErrorInvalidValue;                                        \
+        if (a.wide) { if (a.dinv) F<true, true>(__VA_ARGS__); else F<true, false>(__VA_ARGS__); }    \
+        else { if (a.dinv) F<false, true>(__VA_ARGS__); else F<false, false>(__VA_ARGS__); }         \
+        return hipGetLastError();                                                                    \
+    } while (0)
+
+hipError_t mix_start_launch(const MixArgs &a, bool use_x0, hipStream_t stream) { MIX_LAUNCH(mix_start_t, true, a, use_x0, stream); }
+hipError_t mix_iteration_launch(const MixArgs &a, int k, hipStream_t stream) { MIX_LAUNCH(mix_iteration_t, k >= 1, a, k, stream); }
+hipError_t mix_try_launch(const MixArgs &a, hipStream_t stream) { MIX_LAUNCH(mix_try_t, true, a, stream); }
+hipError_t mix_update_launch(const MixArgs &a, int k, int update, hipStream_t stream) { MIX_LAUNCH(mix_update_t, k >= 1 && update >= 1, a, k, update, stream); }
 
 } // namespace spmv
