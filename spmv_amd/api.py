@@ -838,12 +838,25 @@ def time_attention_gqa_backward_16_launches(handle, heads, kv_heads, Q, K, V, B,
                            dict(Q=Q, K=K, V=V, B=B, G=G, O=O, L=L, dQ=dQ, dK=dK, dV=dV, dB=dB))
 
 
-def _cg_options(rtol, atol, max_iterations, check_every, x0, dinv, history):
-    """-> (spmv_hip_cg_options, the history array or None)"""
-    hist = np.zeros(int(max_iterations) + 1, dtype=np.float64) if history and max_iterations >= 0 else None
-    opt = spmv_hip_cg_options(float(rtol), float(atol), int(max_iterations), int(check_every), 1 if x0 else 0, _ptr(dinv),
-                              hist.ctypes.data_as(C.POINTER(C.c_double)) if hist is not None else None)
-    return opt, hist
+def _cg_options(rtol, atol, max_iterations, check_every, x0, dinv, history, columns=None, mixed=None):
+    """-> (spmv_hip_cg_options, the history array or None).  mixed = (update_drop, update_every): spmv_hip_cg_mixed_options, which appends the two;
+    columns = k: spmv_hip_cg_columns' history, (max_iterations + 1) x k, NaN where a column wrote nothing"""
+    hist = None
+    if history and max_iterations >= 0:
+        hist = np.zeros(int(max_iterations) + 1, dtype=np.float64) if columns is None else np.full((int(max_iterations) + 1, columns), np.nan, dtype=np.float64)
+    common = (float(rtol), float(atol), int(max_iterations), int(check_every), 1 if x0 else 0, _ptr(dinv), hist.ctypes.data_as(C.POINTER(C.c_double)) if hist is not None else None)
+    return (spmv_hip_cg_mixed_options(*common, float(mixed[0]), int(mixed[1])) if mixed else spmv_hip_cg_options(*common)), hist
+
+
+def _solve_result(res, names, rc=0, hist=None):
+    """a spmv_hip_cg_result or spmv_hip_cg_mixed_result -> the result dict; names: CG_STATUS or CG_MIXED_STATUS"""
+    out = {"status": res.status, "status_name": names[res.status] if 0 <= res.status < len(names) else "?", "iterations": res.iterations}
+    if hasattr(res, "updates"):
+        out["updates"] = res.updates
+    out.update(rr=res.rr, bb=res.bb)
+    if hist is not None:
+        out["history"] = hist[:res.iterations + 1].copy() if rc == 0 else hist[:0].copy()
+    return out
 
 
 def _solve(name, handle, m, RowPtr, ColIdx, Matrix_Val, B, X, rtol, atol, max_iterations, check_every, x0, dinv, history, check, extra=()):
@@ -851,10 +864,7 @@ def _solve(name, handle, m, RowPtr, ColIdx, Matrix_Val, B, X, rtol, atol, max_it
     opt, hist = _cg_options(rtol, atol, max_iterations, check_every, x0, dinv, history)
     res = spmv_hip_cg_result()
     rc = _checked(getattr(load(), name)(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), _ptr(B), _ptr(X), *extra, C.byref(opt), C.byref(res)), name, check)
-    out = {"status": res.status, "status_name": CG_STATUS[res.status] if 0 <= res.status < len(CG_STATUS) else "?", "iterations": res.iterations, "rr": res.rr, "bb": res.bb}
-    if hist is not None:
-        out["history"] = hist[:res.iterations + 1].copy() if rc == 0 else hist[:0].copy()
-    return rc, out
+    return rc, _solve_result(res, CG_STATUS, rc, hist)
 
 
 def _time_solve(name, handle, B, X, iterations, x0, dinv, warmup, iters, extra=()):
@@ -912,14 +922,6 @@ def gmres_device_sqrt(values, out):
     return out
 
 
-def _cg_mixed_options(rtol, atol, max_iterations, check_every, x0, dinv, history, update_drop, update_every):
-    """-> (spmv_hip_cg_mixed_options, the history array or None)"""
-    hist = np.zeros(int(max_iterations) + 1, dtype=np.float64) if history and max_iterations >= 0 else None
-    opt = spmv_hip_cg_mixed_options(float(rtol), float(atol), int(max_iterations), int(check_every), 1 if x0 else 0, _ptr(dinv),
-                                    hist.ctypes.data_as(C.POINTER(C.c_double)) if hist is not None else None, float(update_drop), int(update_every))
-    return opt, hist
-
-
 def cg_mixed(high, low, B, X, rtol=1e-10, atol=0.0, max_iterations=1000, check_every=0, x0=False, dinv=None, history=False, update_drop=0.0,
              update_every=0, check=True):
     """Solve A x = B in fp64 by conjugate gradients with reliable updates (spmv_hip_cg_mixed): the iterations run in fp32 on `low`, an fp32
@@ -927,20 +929,16 @@ def cg_mixed(high, low, B, X, rtol=1e-10, atol=0.0, max_iterations=1000, check_e
     fp32 elements or None, host or device; x0: X holds the initial guess; update_drop (0: the default, 0.01) and update_every (0: no cap) say
     when a segment of fp32 iterations ends.  -> (rc, result dict: status, status_name, iterations, updates, rr (the TRUE one of X), bb[,
     history: rr after iteration 0 .. iterations, the recurrence's but where an update was committed])."""
-    opt, hist = _cg_mixed_options(rtol, atol, max_iterations, check_every, x0, dinv, history, update_drop, update_every)
+    opt, hist = _cg_options(rtol, atol, max_iterations, check_every, x0, dinv, history, mixed=(update_drop, update_every))
     res = spmv_hip_cg_mixed_result()
     rc = _checked(load().spmv_hip_cg_mixed(high, low, _ptr(B), _ptr(X), C.byref(opt), C.byref(res)), "spmv_hip_cg_mixed", check)
-    out = {"status": res.status, "status_name": CG_MIXED_STATUS[res.status] if 0 <= res.status < len(CG_MIXED_STATUS) else "?", "iterations": res.iterations, "updates": res.updates,
-           "rr": res.rr, "bb": res.bb}
-    if hist is not None:
-        out["history"] = hist[:res.iterations + 1].copy() if rc == 0 else hist[:0].copy()
-    return rc, out
+    return rc, _solve_result(res, CG_MIXED_STATUS, rc, hist)
 
 
 def time_cg_mixed_iterations(high, low, B, X, iterations, update_every=0, x0=False, dinv=None, warmup=2, iters=20):
     """-> (mean ms per run, per-run ms array) of `iters` runs of `iterations` mixed iterations each, an fp64 update behind every
     update_every-th one (0: none), stop tests off, on device B / X / dinv (spmv_hip_time_cg_mixed_iterations)."""
-    opt, _ = _cg_mixed_options(0.0, 0.0, iterations, 0, x0, dinv, False, 0.0, update_every)
+    opt, _ = _cg_options(0.0, 0.0, iterations, 0, x0, dinv, False, mixed=(0.0, update_every))
     return _timed("spmv_hip_time_cg_mixed_iterations", (high, low, _ptr(B), _ptr(X), C.byref(opt)), warmup, iters)
 
 
@@ -966,12 +964,10 @@ def cg_columns(handle, m, RowPtr, ColIdx, Matrix_Val, B, X, rtol=1e-8, atol=0.0,
     k, pb, ldb, px, ldx = _cg_columns_blocks(B, X)
     if int(max_iterations) < 0:
         raise ValueError("max_iterations must be >= 0")
-    hist = np.full((int(max_iterations) + 1, k), np.nan, dtype=np.float64) if history else None
-    opt = spmv_hip_cg_options(float(rtol), float(atol), int(max_iterations), int(check_every), 1 if x0 else 0, _ptr(dinv),
-                              hist.ctypes.data_as(C.POINTER(C.c_double)) if hist is not None else None)
+    opt, hist = _cg_options(rtol, atol, max_iterations, check_every, x0, dinv, history, columns=k)
     res = (spmv_hip_cg_result * k)()
     rc = _checked(load().spmv_hip_cg_columns(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), k, pb, ldb, px, ldx, C.byref(opt), res), "spmv_hip_cg_columns", check)
-    out = [{"status": r.status, "status_name": CG_STATUS[r.status] if 0 <= r.status < len(CG_STATUS) else "?", "iterations": r.iterations, "rr": r.rr, "bb": r.bb} for r in res]
+    out = [_solve_result(r, CG_STATUS) for r in res]
     return (rc, out, hist) if history else (rc, out)
 
 

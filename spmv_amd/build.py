@@ -39,7 +39,7 @@ HIP_SOURCES = [("spmv_shim.hip", [], "spmv_shim.hip.o")] + [("spmv_vector.hip", 
               [("spmv_sddmm.hip", [], "spmv_sddmm.hip.o")] + \
               [("spmv_softmax.hip", [], "spmv_softmax.hip.o")] + \
               [(f"spmv_attention{b}.hip", [f"SPMV_ATT_IO={t}"], f"spmv_attention{b}{t}.hip.o") for b in ("", "_backward") for t in range(3)] + \
-              [("spmv_solve.hip", [], "spmv_solve.hip.o")]   # the conjugate-gradient, the BiCGStab and the k-column conjugate-gradient vector kernels (kernels/cg.hpp, kernels/bicgstab.hpp, kernels/cg_columns.hpp); before them: the k-right-hand-side executors (kernels/spmm.hpp), the transpose builder (kernels/transpose.hpp), the sampled product (kernels/sddmm.hpp), the row reductions (kernels/row_softmax.hpp), the fused attention (kernels/attention.hpp) and its backward (kernels/attention_backward.hpp), each compiled three times: a part per element type of Q, K and V (SPMV_ATT_IO, the values of SPMV_HIP_T_*: 0 the handle's float and double, 1 fp16, 2 bf16)
+              [("spmv_solve.hip", [], "spmv_solve.hip.o")]   # the vector kernels of the five device-resident solvers (kernels/cg.hpp, bicgstab.hpp, cg_columns.hpp, gmres.hpp, cg_mixed.hpp); before them: the k-right-hand-side executors (kernels/spmm.hpp), the transpose builder (kernels/transpose.hpp), the sampled product (kernels/sddmm.hpp), the row reductions (kernels/row_softmax.hpp), the fused attention (kernels/attention.hpp) and its backward (kernels/attention_backward.hpp), each compiled three times: a part per element type of Q, K and V (SPMV_ATT_IO, the values of SPMV_HIP_T_*: 0 the handle's float and double, 1 fp16, 2 bf16)
 HIP_FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
              "-ffp-contract=fast"]
 # flags of single sources, behind HIP_FLAGS.  spmv_solve.hip promises the bits of separate multiplies and adds (include/spmv_hip.h, "the arithmetic

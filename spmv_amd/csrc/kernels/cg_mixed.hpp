@@ -49,28 +49,11 @@ struct MixState {
 };
 static_assert(offsetof(MixState, s) == 0, "cg_update_kernel is handed the MixState as its SolveState");
 
-// what one mixed solve's launches need (device pointers)
-struct MixArgs {
-    int m = 0, parts = 0;
-    long long span = 0;
-    const double *b = nullptr;
-    double *x = nullptr, *xn = nullptr, *q64 = nullptr;
-    const float *dinv = nullptr;
-    float *r = nullptr, *p = nullptr, *q = nullptr, *y = nullptr;
-    double *part = nullptr;
-    MixState *state = nullptr;
-    double *hist = nullptr;
-    double rtol2 = 0, atol2 = 0, drop2 = 0; // rtol^2, atol^2, update_drop^2
-    int every = 0, budget = 0;              // update_every, max_iterations
-    int nostop = 0;                         // the timer: no test ends a segment or the loop, every update is committed
-    bool wide = false;                      // b, x and dinv allow 16-byte accesses
-};
-
-// spmv_solve.hip
-hipError_t mix_start_launch(const MixArgs &a, bool use_x0, hipStream_t stream);         // mix_residual + mix_resume of the start; q64 holds A x0 when use_x0
-hipError_t mix_iteration_launch(const MixArgs &a, int k, hipStream_t stream);          // cg_dot + cg_update + mix_direction of iteration k >= 1; q holds A p
-hipError_t mix_try_launch(const MixArgs &a, hipStream_t stream);                        // xn = x + y
-hipError_t mix_update_launch(const MixArgs &a, int k, int update, hipStream_t stream); // mix_residual + mix_resume behind iteration k; q64 holds A xn
+// spmv_solve.hip; the six vectors are SolveArgs::vec[0 .. 5]: the two of doubles, then the four of floats (slot kMixVectors64 + kMixVecR ...)
+hipError_t mix_start_launch(const SolveArgs &a, bool use_x0, hipStream_t stream);         // mix_residual + mix_resume of the start; q64 holds A x0 when use_x0
+hipError_t mix_iteration_launch(const SolveArgs &a, int k, hipStream_t stream);          // cg_dot + cg_update + mix_direction of iteration k >= 1; q holds A p
+hipError_t mix_try_launch(const SolveArgs &a, hipStream_t stream);                        // xn = x + y
+hipError_t mix_update_launch(const SolveArgs &a, int k, int update, hipStream_t stream); // mix_residual + mix_resume behind iteration k; q64 holds A xn
 
 // xn = x + widen(y), an fp64 add
 template <bool WIDE>

@@ -1,5 +1,5 @@
-// solve_common.hpp -- what the vector kernels of the device-resident solvers share (cg.hpp: spmv_hip_cg, bicgstab.hpp: spmv_hip_bicgstab): the
-// state and the arguments of a solve, the 4-element accesses, the sums of a dot, and the two kernels that are the same in both solvers -- the
+// solve_common.hpp -- what the vector kernels of the five device-resident solvers share (cg.hpp, bicgstab.hpp, cg_columns.hpp, gmres.hpp, cg_mixed.hpp): the
+// state and the arguments of a solve, the 4-element accesses, the sums of a dot, and the two kernels that more than one solver launches -- the
 // dot that leaves one array of partials (cg_dot_kernel) and the state of iteration 0 (cg_begin_kernel).
 //
 // Order of a dot over m elements (include/spmv_hip.h "the arithmetic contract"; tests/cg_cases.py restates it in numpy):
@@ -9,7 +9,7 @@
 //   (a0 + a1) + (a2 + a3).  Wave: the adjacent-pair binary tree over 64 lanes (group_sum_dpp: an xor butterfly, the same sums since addition
 //   commutes).  Workgroup: (w0 + w1) + (w2 + w3).  Final sum: the P partials padded with +0.0 to 1024, thread t takes 4t .. 4t + 3 as
 //   (a + b) + (c + d), then the same wave and workgroup trees.
-// Every product and every sum is a separate operation: contraction is off in every function of this file and of the two solvers' files, AND
+// Every product and every sum is a separate operation: contraction is off in every function of this file and of the solvers' files, AND
 // spmv_solve.hip is compiled with -ffp-contract=off (build.py, HIP_SOURCE_FLAGS): under the library's -ffp-contract=fast the back end fuses a
 // multiply and an add whatever the pragma says.  The only fused operations left in the ISA are the five of each kernel's one fp64 division.
 #pragma once
@@ -40,6 +40,8 @@ struct SolveArgs {
     char *base = nullptr;          // spmv_hip_gmres, which has more than six: workspace vector i is base + i * stride
     size_t stride = 0;
     int restart = 0;               // spmv_hip_gmres: steps per cycle
+    double drop2 = 0;              // spmv_hip_cg_mixed: update_drop^2,
+    int every = 0, budget = 0;     // update_every and max_iterations
     void *x = nullptr;
     const void *b = nullptr, *dinv = nullptr;
     double *part = nullptr;        // the solver's partial arrays, kCgMaxParts doubles each

@@ -297,28 +297,11 @@ struct spmv_dev {
     // spmv_hip_attention_gqa_backward_16 with kv_heads < heads and 16-bit dK / dV: the float sums over each group's heads (n x kv_heads * k,
     // n x kv_heads * dv), rounded once into the caller's arrays; allocated at the first such call, grown when a later one needs more
     StageBuf attb_nk, attb_nv;
-    // spmv_hip_cg (shim/solve.hpp): r, p, q (m elements each), the partial arrays and the state in ONE block allocated at the first solve; the
-    // history (doubles, one per iteration + 1) in a block of its own, allocated when a solve wants one and grown when a later one needs more
-    void *cg_ws = nullptr;
-    StageBuf cg_hist;
-    // spmv_hip_bicgstab (shim/solve.hpp): r, rhat, p, v, t, y (m elements each), the partial arrays and the state in ONE block of the solver's
-    // own, allocated at the first BiCGStab solve; its history likewise in a block of its own
-    void *bicg_ws = nullptr;
-    StageBuf bicg_hist;
-    // spmv_hip_cg_columns (shim/solve.hpp): r, p, q (m x cgc_k elements each, compact), 4 cgc_k partial arrays and the per-column state in ONE
-    // block of the solver's own, allocated at the first call and allocated anew when a later call has more columns; its history likewise
-    void *cgc_ws = nullptr;
-    int cgc_k = 0;
-    StageBuf cgc_hist;
-    // spmv_hip_gmres (shim/solve.hpp): w, z and gmres_restart + 1 basis vectors (m elements each), 35 partial arrays and the state in ONE block
-    // of the solver's own, allocated at the first call and allocated anew when a later call has a larger restart; its history likewise
-    void *gmres_ws = nullptr;
-    int gmres_restart = 0;
-    StageBuf gmres_hist;
-    // spmv_hip_cg_mixed (shim/solve.hpp), on the fp64 handle of the pair: xn, q64 (m doubles each), r, p, q, y (m floats each), six partial
-    // arrays and the state in ONE block of the solver's own, allocated at the first call; its history likewise
-    void *mix_ws = nullptr;
-    StageBuf mix_hist;
+    // the device-resident solves (shim/solve.hpp), by solver id: the solver's vectors, partial arrays and state in ONE block of its own, allocated at
+    // its first solve -- n: the columns (spmv_hip_gmres: the restart) it was built for, allocated anew when a later call needs more; the history
+    // (doubles, one per iteration + 1 and column) in a block of its own, allocated when a solve wants one and grown when a later one needs more.
+    // spmv_hip_cg_mixed's is on the fp64 handle of the pair
+    struct SolveWs { void *p = nullptr; int n = 0; StageBuf hist; } solve_ws[SPMV_SHIM_SOLVE_COUNT];
     // spmv_hip_spmv_transpose (shim/transpose.hpp): A^T as a matrix of its own (n x m), planned and built like any; perm[p] = our index of its entry p.
     // val_gen counts spmv_shim_update_values calls; A^T's values are gathered again when tr_gen falls behind it.
     spmv_dev *tr = nullptr;

@@ -1414,81 +1414,98 @@ double spmv_hip_time_attention_gqa_backward_16_launches(spmv_Handle_t h, int hea
     return attention_backward_time(h, "time_attention_gqa_backward_16_launches", ATTENTION_16, &c, warmup, iters, ms_out);
 }
 
-/* ---------------------------------------------------------------- conjugate gradients and BiCGStab (a matrix that need not be symmetric) on the device */
-/* the argument rules ahead of the gate, the same for both: a solve; its timer with m = 1 (B and X are always needed) */
-static int cg_args(spmv_Handle_t h, const char *where, const void *B, const void *X, const spmv_hip_cg_options *opt, const void *res, int m)
+/* ---------------------------------------------------------------- the five solves on the device: one gate, one call struct
+ * conjugate gradients, BiCGStab (a matrix that need not be symmetric), restarted GMRES, conjugate gradients for k right-hand sides and
+ * mixed-precision conjugate gradients on a pair of handles.  An entry point fills a spmv_solve_call and goes through solve_call or solve_time. */
+typedef struct solve_csr { BASIC_INT_TYPE m; const BASIC_INT_TYPE *RowPtr, *ColIdx; const void *Val; } solve_csr; /* the CSR arguments of a solve that takes them */
+
+static spmv_solve_call solve_fill(int solver, int k, int restart, const void *B, long long ldb, void *X, long long ldx, const spmv_hip_cg_options *opt, spmv_hip_cg_result *res)
 {
-    if (!h) return refuse(SPMV_HIP_E_ARG, where, "handle is NULL");
-    if (!opt || !res) return refuse(SPMV_HIP_E_ARG, where, "opt or res is NULL");
-    if (m > 0 && (!B || !X)) return refuse(SPMV_HIP_E_ARG, where, "B or X is NULL");
-    if (opt->max_iterations < 0 || opt->check_every < 0) return refuse(SPMV_HIP_E_ARG, where, "need max_iterations >= 0 and check_every >= 0");
-    if (!(opt->rtol >= 0) || !(opt->atol >= 0)) return refuse(SPMV_HIP_E_ARG, where, "rtol and atol must be >= 0 (and not NaN)");
-    return SPMV_HIP_OK;
+    spmv_solve_call c = {.solver = solver, .k = k, .restart = restart, .b = B, .ldb = ldb, .x = X, .ldx = ldx, .res = res};
+    if (opt) c.opt = *opt;
+    return c;
 }
 
-static int solve_call(spmv_Handle_t handle, const char *where, int solver, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
-                      const void *Matrix_Val, const void *B, void *X, const spmv_hip_cg_options *opt, spmv_hip_cg_result *res)
+/* Every argument rule, once, ahead of the gate (a refusal here is E_ARG whatever the handle's state); then the gate -- spmv_hip_cg_mixed: both
+ * handles', addressed in the caller's order, and c->low filled; the prologue for a solve with the CSR arguments; the plain gate for a timer --
+ * and what needs the state: the square matrix, and the columns of spmv_hip_cg_columns, which with one compact vector is spmv_hip_cg, its
+ * workspace and bits.  given: opt and res are there.  m: the solve's; 1 for a timer (B and X are always needed); 0 for spmv_hip_cg_mixed, whose
+ * m is the resident matrix's: the shim checks its B and X */
+static int solve_gate(const char *where, spmv_Handle_t h, spmv_Handle_t low, int given, spmv_solve_call *c, const solve_csr *csr, int m, spmv_hip_state **st)
 {
-    spmv_hip_state *st;
+    const int mixed = c->solver == SPMV_SHIM_SOLVE_CG_MIXED, kmax = c->solver == SPMV_SHIM_SOLVE_CG_COLUMNS ? SPMV_HIP_CG_COLUMNS_MAX : 1;
+    spmv_hip_state *lo = NULL;
     int rc;
-    if ((rc = cg_args(handle, where, B, X, opt, res, m)) || (rc = resident_prologue(handle, where, 0, m, RowPtr, ColIdx, Matrix_Val, &st))) return rc;
-    if (st->m != st->n) return refuse(SPMV_HIP_E_ARG, where, "the matrix is not square (m != n at create)");
-    return report(spmv_shim_solve(solver, st->dev, B, X, opt, res), where);
+    if (!h || (mixed && !low)) return refuse(SPMV_HIP_E_ARG, where, "handle is NULL");
+    if (!given) return refuse(SPMV_HIP_E_ARG, where, "opt or res is NULL");
+    if (m > 0 && (!c->b || !c->x)) return refuse(SPMV_HIP_E_ARG, where, "B or X is NULL");
+    if (c->opt.max_iterations < 0 || c->opt.check_every < 0) return refuse(SPMV_HIP_E_ARG, where, "need max_iterations >= 0 and check_every >= 0");
+    if (!(c->opt.rtol >= 0) || !(c->opt.atol >= 0)) return refuse(SPMV_HIP_E_ARG, where, "rtol and atol must be >= 0 (and not NaN)");
+    if (c->solver == SPMV_SHIM_SOLVE_GMRES && (c->restart < 1 || c->restart > SPMV_HIP_GMRES_RESTART_MAX))
+        return refuse(SPMV_HIP_E_ARG, where, "need 1 <= restart <= SPMV_HIP_GMRES_RESTART_MAX");
+    if (c->k < 1 || c->k > kmax || c->ldb < c->k || c->ldx < c->k) return refuse(SPMV_HIP_E_ARG, where, "need 1 <= k <= SPMV_HIP_CG_COLUMNS_MAX, ldb >= k and ldx >= k");
+    if (!(c->update_drop >= 0) || !(c->update_drop < 1)) return refuse(SPMV_HIP_E_ARG, where, "need 0 <= update_drop < 1 (0: the default)");
+    if (c->update_every < 0) return refuse(SPMV_HIP_E_ARG, where, "need update_every >= 0");
+    if (mixed) {
+        if ((rc = resident_state(h, where, RESIDENT_NOT_REORDERED, st)) || (rc = resident_state(low, where, RESIDENT_NOT_REORDERED, &lo))) return rc;
+    } else if ((rc = csr ? resident_prologue(h, where, 0, csr->m, csr->RowPtr, csr->ColIdx, csr->Val, st) : resident_state(h, where, 0, st))) return rc;
+    c->low = lo ? lo->dev : NULL;
+    if ((*st)->m != (*st)->n) return refuse(SPMV_HIP_E_ARG, where, "the matrix is not square (m != n at create)");
+    if (c->solver == SPMV_SHIM_SOLVE_CG_COLUMNS && c->k == 1 && c->ldb == 1 && c->ldx == 1) c->solver = SPMV_SHIM_SOLVE_CG;
+    return c->solver == SPMV_SHIM_SOLVE_CG_COLUMNS ? spmm_columns(h, *st, where) : SPMV_HIP_OK;
 }
 
-static double solve_time(spmv_Handle_t h, const char *where, int solver, const void *B, void *X, const spmv_hip_cg_options *opt, int warmup, int iters, float *ms_out)
+static int solve_call(const char *where, spmv_Handle_t h, spmv_Handle_t low, int given, spmv_solve_call *c, const solve_csr *csr)
 {
     spmv_hip_state *st;
-    if (cg_args(h, where, B, X, opt, opt, 1) || resident_state(h, where, 0, &st)) return -1.0;
-    if (st->m != st->n) { (void) refuse(SPMV_HIP_E_ARG, where, "the matrix is not square (m != n at create)"); return -1.0; }
-    return report_time(spmv_shim_time_solve(solver, st->dev, B, X, opt, warmup, iters, ms_out), where);
+    const int rc = solve_gate(where, h, low, given, c, csr, csr ? csr->m : 0, &st);
+    return rc ? rc : report(spmv_shim_solve(st->dev, c), where);
+}
+
+static double solve_time(const char *where, spmv_Handle_t h, spmv_Handle_t low, int given, spmv_solve_call *c, int warmup, int iters, float *ms_out)
+{
+    spmv_hip_state *st;
+    if (solve_gate(where, h, low, given, c, NULL, 1, &st)) return -1.0;
+    return report_time(spmv_shim_time_solve(st->dev, c, warmup, iters, ms_out), where);
 }
 
 int spmv_hip_cg(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
                 const void *Matrix_Val, const void *B, void *X, const spmv_hip_cg_options *opt, spmv_hip_cg_result *res)
 {
-    return solve_call(handle, "cg", SPMV_SHIM_SOLVE_CG, m, RowPtr, ColIdx, Matrix_Val, B, X, opt, res);
+    spmv_solve_call c = solve_fill(SPMV_SHIM_SOLVE_CG, 1, 0, B, 1, X, 1, opt, res);
+    return solve_call("cg", handle, NULL, opt && res, &c, &(solve_csr){m, RowPtr, ColIdx, Matrix_Val});
 }
 
 int spmv_hip_bicgstab(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
                       const void *Matrix_Val, const void *B, void *X, const spmv_hip_cg_options *opt, spmv_hip_cg_result *res)
 {
-    return solve_call(handle, "bicgstab", SPMV_SHIM_SOLVE_BICGSTAB, m, RowPtr, ColIdx, Matrix_Val, B, X, opt, res);
+    spmv_solve_call c = solve_fill(SPMV_SHIM_SOLVE_BICGSTAB, 1, 0, B, 1, X, 1, opt, res);
+    return solve_call("bicgstab", handle, NULL, opt && res, &c, &(solve_csr){m, RowPtr, ColIdx, Matrix_Val});
 }
 
 double spmv_hip_time_cg_iterations(spmv_Handle_t h, const void *B, void *X, const spmv_hip_cg_options *opt, int warmup, int iters, float *ms_out)
 {
-    return solve_time(h, "time_cg_iterations", SPMV_SHIM_SOLVE_CG, B, X, opt, warmup, iters, ms_out);
+    spmv_solve_call c = solve_fill(SPMV_SHIM_SOLVE_CG, 1, 0, B, 1, X, 1, opt, NULL);
+    return solve_time("time_cg_iterations", h, NULL, opt != NULL, &c, warmup, iters, ms_out);
 }
 
 double spmv_hip_time_bicgstab_iterations(spmv_Handle_t h, const void *B, void *X, const spmv_hip_cg_options *opt, int warmup, int iters, float *ms_out)
 {
-    return solve_time(h, "time_bicgstab_iterations", SPMV_SHIM_SOLVE_BICGSTAB, B, X, opt, warmup, iters, ms_out);
+    spmv_solve_call c = solve_fill(SPMV_SHIM_SOLVE_BICGSTAB, 1, 0, B, 1, X, 1, opt, NULL);
+    return solve_time("time_bicgstab_iterations", h, NULL, opt != NULL, &c, warmup, iters, ms_out);
 }
 
-/* ---------------------------------------------------------------- restarted GMRES on the device */
 int spmv_hip_gmres(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx, const void *Matrix_Val, const void *B, void *X, int restart,
                    const spmv_hip_cg_options *opt, spmv_hip_cg_result *res)
 {
-    const char *where = "gmres";
-    spmv_hip_state *st;
-    int rc;
-    if ((rc = cg_args(handle, where, B, X, opt, res, m))) return rc;
-    if (restart < 1 || restart > SPMV_HIP_GMRES_RESTART_MAX) return refuse(SPMV_HIP_E_ARG, where, "need 1 <= restart <= SPMV_HIP_GMRES_RESTART_MAX");
-    if ((rc = resident_prologue(handle, where, 0, m, RowPtr, ColIdx, Matrix_Val, &st))) return rc;
-    if (st->m != st->n) return refuse(SPMV_HIP_E_ARG, where, "the matrix is not square (m != n at create)");
-    return report(spmv_shim_solve_gmres(st->dev, restart, B, X, opt, res), where);
+    spmv_solve_call c = solve_fill(SPMV_SHIM_SOLVE_GMRES, 1, restart, B, 1, X, 1, opt, res);
+    return solve_call("gmres", handle, NULL, opt && res, &c, &(solve_csr){m, RowPtr, ColIdx, Matrix_Val});
 }
 
 double spmv_hip_time_gmres_iterations(spmv_Handle_t h, const void *B, void *X, int restart, const spmv_hip_cg_options *opt, int warmup, int iters, float *ms_out)
 {
-    const char *where = "time_gmres_iterations";
-    spmv_hip_state *st;
-    if (cg_args(h, where, B, X, opt, opt, 1)) return -1.0;
-    if (restart < 1 || restart > SPMV_HIP_GMRES_RESTART_MAX) { (void) refuse(SPMV_HIP_E_ARG, where, "need 1 <= restart <= SPMV_HIP_GMRES_RESTART_MAX"); return -1.0; }
-    if (resident_state(h, where, 0, &st)) return -1.0;
-    if (st->m != st->n) { (void) refuse(SPMV_HIP_E_ARG, where, "the matrix is not square (m != n at create)"); return -1.0; }
-    return report_time(spmv_shim_time_solve_gmres(st->dev, restart, B, X, opt, warmup, iters, ms_out), where);
+    spmv_solve_call c = solve_fill(SPMV_SHIM_SOLVE_GMRES, 1, restart, B, 1, X, 1, opt, NULL);
+    return solve_time("time_gmres_iterations", h, NULL, opt != NULL, &c, warmup, iters, ms_out);
 }
 
 int spmv_hip_gmres_device_sqrt(const double *in, double *out, long long n)
@@ -1496,70 +1513,51 @@ int spmv_hip_gmres_device_sqrt(const double *in, double *out, long long n)
     return report(spmv_shim_gmres_sqrt(in, out, n), "gmres_device_sqrt");
 }
 
-/* ---------------------------------------------------------------- conjugate gradients for k right-hand sides in one pass over A per iteration */
-/* cg_args' rules and the columns' own; the timer with m = 1 */
-static int cg_columns_args(spmv_Handle_t h, const char *where, int k, const void *B, long long ldb, const void *X, long long ldx, const spmv_hip_cg_options *opt, const void *res,
-                           int m)
-{
-    const int rc = cg_args(h, where, B, X, opt, res, m);
-    if (rc) return rc;
-    if (k < 1 || k > SPMV_HIP_CG_COLUMNS_MAX || ldb < k || ldx < k) return refuse(SPMV_HIP_E_ARG, where, "need 1 <= k <= SPMV_HIP_CG_COLUMNS_MAX, ldb >= k and ldx >= k");
-    return SPMV_HIP_OK;
-}
-
 int spmv_hip_cg_columns(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx, const void *Matrix_Val, int k, const void *B,
                         long long ldb, void *X, long long ldx, const spmv_hip_cg_options *opt, spmv_hip_cg_result *res)
 {
-    const char *where = "cg_columns";
-    spmv_hip_state *st;
-    int rc;
-    if ((rc = cg_columns_args(handle, where, k, B, ldb, X, ldx, opt, res, m)) || (rc = resident_prologue(handle, where, 0, m, RowPtr, ColIdx, Matrix_Val, &st))) return rc;
-    if (st->m != st->n) return refuse(SPMV_HIP_E_ARG, where, "the matrix is not square (m != n at create)");
-    if (k == 1 && ldb == 1 && ldx == 1) return report(spmv_shim_solve(SPMV_SHIM_SOLVE_CG, st->dev, B, X, opt, res), where); /* one vector: spmv_hip_cg, its workspace and bits */
-    if ((rc = spmm_columns(handle, st, where))) return rc;
-    return report(spmv_shim_solve_columns(st->dev, k, B, ldb, X, ldx, opt, res), where);
+    spmv_solve_call c = solve_fill(SPMV_SHIM_SOLVE_CG_COLUMNS, k, 0, B, ldb, X, ldx, opt, res);
+    return solve_call("cg_columns", handle, NULL, opt && res, &c, &(solve_csr){m, RowPtr, ColIdx, Matrix_Val});
 }
 
 double spmv_hip_time_cg_columns_iterations(spmv_Handle_t h, int k, const void *B, long long ldb, void *X, long long ldx, const spmv_hip_cg_options *opt, int warmup, int iters,
                                            float *ms_out)
 {
-    const char *where = "time_cg_columns_iterations";
-    spmv_hip_state *st;
-    if (cg_columns_args(h, where, k, B, ldb, X, ldx, opt, opt, 1) || resident_state(h, where, 0, &st)) return -1.0;
-    if (st->m != st->n) { (void) refuse(SPMV_HIP_E_ARG, where, "the matrix is not square (m != n at create)"); return -1.0; }
-    if (k == 1 && ldb == 1 && ldx == 1) return report_time(spmv_shim_time_solve(SPMV_SHIM_SOLVE_CG, st->dev, B, X, opt, warmup, iters, ms_out), where);
-    if (spmm_columns(h, st, where)) return -1.0;
-    return report_time(spmv_shim_time_solve_columns(st->dev, k, B, ldb, X, ldx, opt, warmup, iters, ms_out), where);
+    spmv_solve_call c = solve_fill(SPMV_SHIM_SOLVE_CG_COLUMNS, k, 0, B, ldb, X, ldx, opt, NULL);
+    return solve_time("time_cg_columns_iterations", h, NULL, opt != NULL, &c, warmup, iters, ms_out);
 }
 
-/* ---------------------------------------------------------------- mixed-precision conjugate gradients on a pair of handles */
-/* the option rules ahead of the gates, then both gates: the fp64 handle's state in *hi, the fp32 one's in *lo; what a pair must share is the shim's to check */
-static int cg_mixed_pair(spmv_Handle_t high, spmv_Handle_t low, const char *where, const spmv_hip_cg_mixed_options *opt, const void *res, spmv_hip_state **hi, spmv_hip_state **lo)
+/* the mixed solve's options are a struct of their own: the common fields copied one by one; what a pair must share is the shim's to check */
+static spmv_solve_call mixed_fill(const double *B, double *X, const spmv_hip_cg_mixed_options *opt, spmv_hip_cg_result *res, int *updates)
 {
-    int rc;
-    if (!high || !low) return refuse(SPMV_HIP_E_ARG, where, "handle is NULL");
-    if (!opt || !res) return refuse(SPMV_HIP_E_ARG, where, "opt or res is NULL");
-    if (opt->max_iterations < 0 || opt->check_every < 0) return refuse(SPMV_HIP_E_ARG, where, "need max_iterations >= 0 and check_every >= 0");
-    if (!(opt->rtol >= 0) || !(opt->atol >= 0)) return refuse(SPMV_HIP_E_ARG, where, "rtol and atol must be >= 0 (and not NaN)");
-    if (!(opt->update_drop >= 0) || !(opt->update_drop < 1)) return refuse(SPMV_HIP_E_ARG, where, "need 0 <= update_drop < 1 (0: the default)");
-    if (opt->update_every < 0) return refuse(SPMV_HIP_E_ARG, where, "need update_every >= 0");
-    if ((rc = resident_state(high, where, RESIDENT_NOT_REORDERED, hi)) || (rc = resident_state(low, where, RESIDENT_NOT_REORDERED, lo))) return rc;
-    return SPMV_HIP_OK;
+    spmv_solve_call c = solve_fill(SPMV_SHIM_SOLVE_CG_MIXED, 1, 0, B, 1, X, 1, NULL, res);
+    c.updates = updates;
+    if (!opt) return c;
+    c.opt.rtol = opt->rtol;
+    c.opt.atol = opt->atol;
+    c.opt.max_iterations = opt->max_iterations;
+    c.opt.check_every = opt->check_every;
+    c.opt.use_x0 = opt->use_x0;
+    c.opt.Dinv = opt->Dinv;
+    c.opt.history = opt->history;
+    c.update_drop = opt->update_drop;
+    c.update_every = opt->update_every;
+    return c;
 }
 
 int spmv_hip_cg_mixed(spmv_Handle_t high, spmv_Handle_t low, const double *B, double *X, const spmv_hip_cg_mixed_options *opt, spmv_hip_cg_mixed_result *res)
 {
-    const char *where = "cg_mixed";
-    spmv_hip_state *hi, *lo;
-    const int rc = cg_mixed_pair(high, low, where, opt, res, &hi, &lo);
-    return rc ? rc : report(spmv_shim_solve_mixed(hi->dev, lo->dev, B, X, opt, res), where);
+    spmv_hip_cg_result r = {0};
+    int updates = 0;
+    spmv_solve_call c = mixed_fill(B, X, opt, &r, &updates);
+    const int rc = solve_call("cg_mixed", high, low, opt && res, &c, NULL);
+    if (rc == SPMV_HIP_OK) *res = (spmv_hip_cg_mixed_result){.status = r.status, .iterations = r.iterations, .updates = updates, .rr = r.rr, .bb = r.bb};
+    return rc;
 }
 
 double spmv_hip_time_cg_mixed_iterations(spmv_Handle_t high, spmv_Handle_t low, const double *B, double *X, const spmv_hip_cg_mixed_options *opt, int warmup, int iters,
                                          float *ms_out)
 {
-    const char *where = "time_cg_mixed_iterations";
-    spmv_hip_state *hi, *lo;
-    if (cg_mixed_pair(high, low, where, opt, opt, &hi, &lo)) return -1.0;
-    return report_time(spmv_shim_time_solve_mixed(hi->dev, lo->dev, B, X, opt, warmup, iters, ms_out), where);
+    spmv_solve_call c = mixed_fill(B, X, opt, NULL, NULL);
+    return solve_time("time_cg_mixed_iterations", high, low, opt != NULL, &c, warmup, iters, ms_out);
 }

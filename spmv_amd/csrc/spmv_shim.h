@@ -205,32 +205,41 @@ int spmv_shim_attention_backward(spmv_dev *d, const spmv_attention_backward_call
  * Q, K, V, G and, with stats, O and L must be given. */
 double spmv_shim_time_attention_backward(spmv_dev *d, const spmv_attention_backward_call *c, int warmup, int iters, float *ms_out);
 
-/* ---- the solves on the resident matrix that stay on the device (shim/solve.hpp): preconditioned conjugate gradients (spmv_hip_cg) and
- * right-preconditioned BiCGStab (spmv_hip_bicgstab; the matrix need not be symmetric) ----
- * B, X, opt->Dinv: m elements, host or device pointers each.  The multiply is the built schedule's own launch.  Each solver builds a workspace of its
- * own at its first call.  SPMV_HIP_OK whenever the solve ran (res->status says how it ended); synchronous */
-enum { SPMV_SHIM_SOLVE_CG, SPMV_SHIM_SOLVE_BICGSTAB, SPMV_SHIM_SOLVE_CG_COLUMNS /* spmv_shim_solve_columns alone */, SPMV_SHIM_SOLVE_GMRES /* spmv_shim_solve_gmres alone */ };
-int spmv_shim_solve(int solver, spmv_dev *d, const void *b, void *x, const spmv_hip_cg_options *opt, spmv_hip_cg_result *res);
-/* `iters` runs of opt->max_iterations iterations each, the stop tests off, timed with events on the handle's stream (device B / X / Dinv); mean ms per run, < 0 on failure */
-double spmv_shim_time_solve(int solver, spmv_dev *d, const void *b, void *x, const spmv_hip_cg_options *opt, int warmup, int iters, float *ms_out);
-/* conjugate gradients for k independent right-hand sides (spmv_hip_cg_columns), 1 <= k <= SPMV_HIP_CG_COLUMNS_MAX: B and X m x k, row-major, leading
- * dimensions ldb, ldx >= k, host or device pointers; opt->Dinv one vector of m elements; res k entries; opt->history (max_iterations + 1) * k doubles.
- * The multiply is spmv_shim_spmm's executor on the solver's own compact workspace vectors, one pass over A per iteration: the resident ColIdx
- * is needed (spmv_shim_restore_columns).  The same loop, workspace rules and return value as spmv_shim_solve */
-/* spmv_hip_gmres: restarted GMRES(restart), 1 <= restart <= SPMV_HIP_GMRES_RESTART_MAX, through the same loop; its workspace holds restart + 3 vectors and is
- * allocated anew when a later call has a larger restart.  The timer's iterations include the cycle ends and restarts that fall among them */
-int spmv_shim_solve_gmres(spmv_dev *d, int restart, const void *b, void *x, const spmv_hip_cg_options *opt, spmv_hip_cg_result *res);
-double spmv_shim_time_solve_gmres(spmv_dev *d, int restart, const void *b, void *x, const spmv_hip_cg_options *opt, int warmup, int iters, float *ms_out);
+/* ---- the solves on the resident matrix that stay on the device (shim/solve.hpp): five solvers, one call struct, one loop, one timer ----
+ * spmv_hip_cg, spmv_hip_bicgstab (the matrix need not be symmetric), spmv_hip_cg_columns (k right-hand sides in one pass over A per iteration),
+ * spmv_hip_gmres (restarted GMRES(restart)) and spmv_hip_cg_mixed (fp32 iterations, fp64 solution and true residual).  What every entry point
+ * passes down; one that lacks a field fills it as k = ldb = ldx = 1, restart = 0, low = NULL, update_drop = 0, update_every = 0, updates = NULL:
+ *   - b, x: m x k elements of the handle's value type, row-major, leading dimensions ldb, ldx >= k; opt.Dinv: ONE vector of m elements (floats
+ *     for spmv_hip_cg_mixed, whose handle is fp64); host or device pointers each.  1 <= k <= SPMV_HIP_CG_COLUMNS_MAX for spmv_hip_cg_columns,
+ *     which multiplies with spmv_shim_spmm's executor and needs the resident ColIdx (spmv_shim_restore_columns); k = 1 for the others, whose
+ *     multiply is the built schedule's own launch.
+ *   - restart: 1 <= restart <= SPMV_HIP_GMRES_RESTART_MAX for spmv_hip_gmres.
+ *   - low: spmv_hip_cg_mixed's fp32 handle, only multiplied with; the handle of the call is the fp64 one and owns the workspace.  The pair has
+ *     the same m = n and nnz, device and stream: SPMV_HIP_E_ARG otherwise.
+ *   - res: k entries; opt.history: (max_iterations + 1) * k doubles; updates: spmv_hip_cg_mixed's committed updates.
+ * Each solver builds a workspace of its own on the handle at its first call; spmv_hip_cg_columns' is allocated anew when a later call has more
+ * columns, spmv_hip_gmres's (restart + 3 vectors) when one has a larger restart.  SPMV_HIP_OK whenever the solve ran (res->status says how it
+ * ended); synchronous */
+enum { SPMV_SHIM_SOLVE_CG, SPMV_SHIM_SOLVE_BICGSTAB, SPMV_SHIM_SOLVE_CG_COLUMNS, SPMV_SHIM_SOLVE_GMRES, SPMV_SHIM_SOLVE_CG_MIXED, SPMV_SHIM_SOLVE_COUNT };
+typedef struct spmv_solve_call {
+    int solver;      /* SPMV_SHIM_SOLVE_* */
+    spmv_dev *low;
+    int k, restart;
+    const void *b;   long long ldb;
+    void *x;         long long ldx;
+    spmv_hip_cg_options opt; /* rtol, atol, max_iterations, check_every, use_x0, Dinv, history */
+    double update_drop;      /* spmv_hip_cg_mixed: 0 = SPMV_HIP_CG_MIXED_UPDATE_DROP */
+    int update_every;
+    spmv_hip_cg_result *res;
+    int *updates;            /* NULL: not wanted */
+} spmv_solve_call;
+int spmv_shim_solve(spmv_dev *d, const spmv_solve_call *c);
+/* `iters` runs of opt.max_iterations iterations each, the stop tests off, timed with events on the handle's stream (device B / X / Dinv); mean ms per
+ * run, < 0 on failure.  spmv_hip_gmres: the iterations include the cycle ends and restarts that fall among them; spmv_hip_cg_mixed: an update behind
+ * every update_every-th iteration (none at 0).  res and updates are not looked at */
+double spmv_shim_time_solve(spmv_dev *d, const spmv_solve_call *c, int warmup, int iters, float *ms_out);
 /* out[i] = the fp64 square root of in[i] as spmv_hip_gmres's kernels take it: n doubles each, device pointers; synchronous */
 int spmv_shim_gmres_sqrt(const double *in, double *out, long long n);
-int spmv_shim_solve_columns(spmv_dev *d, int k, const void *b, long long ldb, void *x, long long ldx, const spmv_hip_cg_options *opt, spmv_hip_cg_result *res);
-double spmv_shim_time_solve_columns(spmv_dev *d, int k, const void *b, long long ldb, void *x, long long ldx, const spmv_hip_cg_options *opt, int warmup, int iters,
-                                    float *ms_out);
-/* spmv_hip_cg_mixed: fp32 conjugate-gradient iterations on lo's multiply, the solution and the true residual in fp64 through hi's (hi fp64, lo
- * fp32, the same m = n and nnz, device and stream: SPMV_HIP_E_ARG otherwise).  B and X m doubles, opt->Dinv m floats, host or device pointers.
- * The workspace is hi's and this solver's own; lo is only multiplied with.  The timer: an update behind every opt->update_every-th iteration */
-int spmv_shim_solve_mixed(spmv_dev *hi, spmv_dev *lo, const double *b, double *x, const spmv_hip_cg_mixed_options *opt, spmv_hip_cg_mixed_result *res);
-double spmv_shim_time_solve_mixed(spmv_dev *hi, spmv_dev *lo, const double *b, double *x, const spmv_hip_cg_mixed_options *opt, int warmup, int iters, float *ms_out);
 
 /* the resident CSR arrays (device pointers; ColIdx may be NULL after spmv_shim_release_columns) */
 void spmv_shim_matrix_arrays(const spmv_dev *d, const int **rowptr, const int **colidx, const void **val);

@@ -181,7 +181,8 @@ extern "C" void spmv_shim_matrix_destroy(spmv_dev *d)
     if (d->rowptr) (void) pool_free(d->rowptr);
     if (d->colidx) (void) pool_free(d->colidx);
     if (d->val) (void) pool_free(d->val);
-    for (void *p : {d->scratch8, (void *) d->spmm_split, (void *) d->spmm_longs, (void *) d->att_off, d->att_park, d->attb_p, d->attb_ds, d->attb_nk.p, d->attb_nv.p, d->cg_ws, d->cg_hist.p, d->bicg_ws, d->bicg_hist.p, d->cgc_ws, d->cgc_hist.p, d->gmres_ws, d->gmres_hist.p, d->mix_ws, d->mix_hist.p}) if (p) (void) pool_free(p);
+    for (void *p : {d->scratch8, (void *) d->spmm_split, (void *) d->spmm_longs, (void *) d->att_off, d->att_park, d->attb_p, d->attb_ds, d->attb_nk.p, d->attb_nv.p}) if (p) (void) pool_free(p);
+    for (const spmv_dev::SolveWs &w : d->solve_ws) for (void *p : {w.p, w.hist.p}) if (p) (void) pool_free(p);
     for (StageBuf &b : d->stage) if (b.p) (void) pool_free(b.p);
     delete d;
 }

@@ -1,5 +1,5 @@
-// spmv_solve.hip -- translation unit of the vector kernels of the device-resident solvers (kernels/cg.hpp, kernels/bicgstab.hpp,
-// kernels/cg_columns.hpp, what they share in kernels/solve_common.hpp).  Launches only: the workspace, staging, the multiplies, the host's
+// spmv_solve.hip -- translation unit of the vector kernels of the five device-resident solvers (kernels/cg.hpp, kernels/bicgstab.hpp,
+// kernels/cg_columns.hpp, kernels/gmres.hpp, kernels/cg_mixed.hpp, what they share in kernels/solve_common.hpp).  Launches only: the workspace, staging, the multiplies, the host's
 // looks at the state and the error channel stay in spmv_shim.hip (shim/solve.hpp).  Per solve it calls cg_start_launch or bicg_start_launch
 // once; per iteration cg_iteration_launch behind q = A p, or bicg_first_launch behind v = A ph and bicg_second_launch behind t = A sh;
 // spmv_hip_cg_columns: ccg_start_launch, and ccg_iteration_launch behind q = A p for all k columns.  spmv_hip_gmres (kernels/gmres.hpp):
@@ -78,19 +78,20 @@ static void bicg_second_t(const SolveArgs &a, int k, hipStream_t stream)
 
 static bool args_ok(const SolveArgs &a) { return a.m > 0 && a.parts >= 1 && a.parts <= kCgMaxParts && a.span * a.parts >= a.m; }
 
-// the checked launch of the instantiation of F that a.f64 / a.wide / a.dinv select; `ok`: what the call needs beyond args_ok
-#define SOLVE_LAUNCH(F, ok, ...)                                                                                             \
-    do {                                                                                                                     \
-        if (!args_ok(a) || !(ok)) return hipErrorInvalidValue;                                                               \
-        const bool dinv__ = a.dinv != nullptr;                                                                               \
-        if (a.f64) {                                                                                                         \
-            if (a.wide) { if (dinv__) F<double, true, true>(__VA_ARGS__); else F<double, true, false>(__VA_ARGS__); }        \
-            else { if (dinv__) F<double, false, true>(__VA_ARGS__); else F<double, false, false>(__VA_ARGS__); }             \
-        } else {                                                                                                             \
-            if (a.wide) { if (dinv__) F<float, true, true>(__VA_ARGS__); else F<float, true, false>(__VA_ARGS__); }          \
-            else { if (dinv__) F<float, false, true>(__VA_ARGS__); else F<float, false, false>(__VA_ARGS__); }               \
-        }                                                                                                                    \
-        return hipGetLastError();                                                                                            \
+// the instantiation F<T, WIDE, DINV> that a.wide / a.dinv select
+#define FORM_LAUNCH(F, T, ...)                                                                                       \
+    do {                                                                                                             \
+        if (a.wide) { if (a.dinv) F<T, true, true>(__VA_ARGS__); else F<T, true, false>(__VA_ARGS__); }              \
+        else { if (a.dinv) F<T, false, true>(__VA_ARGS__); else F<T, false, false>(__VA_ARGS__); }                   \
+    } while (0)
+
+// the checked launch of the form of F that a.f64 / a.wide / a.dinv select; `ok`: what the call needs beyond args_ok
+#define SOLVE_LAUNCH(F, ok, ...)                                                                                     \
+    do {                                                                                                             \
+        if (!args_ok(a) || !(ok)) return hipErrorInvalidValue;                                                       \
+        if (a.f64) FORM_LAUNCH(F, double, __VA_ARGS__);                                                              \
+        else FORM_LAUNCH(F, float, __VA_ARGS__);                                                                     \
+        return hipGetLastError();                                                                                    \
     } while (0)
 
 template <typename T, bool WIDE, bool DINV>
@@ -194,57 +195,72 @@ hipError_t gmres_sqrt_launch(const double *in, double *out, long long n, hipStre
     return hipGetLastError();
 }
 
-// ---- spmv_hip_cg_mixed
-template <bool WIDE, bool DINV>
-static void mix_start_t(const MixArgs &a, bool use_x0, hipStream_t stream)
+// ---- spmv_hip_cg_mixed: T is float, the type of the iterations, whatever a.f64 says of the handle
+static MixState *mix_state(const SolveArgs &a) { return reinterpret_cast<MixState *>(a.state); }
+static double *mix_vec64(const SolveArgs &a, int i) { return (double *) a.vec[i]; }
+template <typename T> static T *mix_vec(const SolveArgs &a, int i) { return (T *) a.vec[kMixVectors64 + i]; }
+
+template <typename T, bool WIDE, bool DINV>
+static void mix_start_t(const SolveArgs &a, bool use_x0, hipStream_t stream)
 {
     const unsigned grid = (unsigned) a.parts;
-    if (use_x0) mix_residual_kernel<WIDE, DINV, 1><<<grid, kBlock, 0, stream>>>(a.m, a.span, 0, a.b, a.x, a.q64, a.dinv, a.r, a.part);
-    else mix_residual_kernel<WIDE, DINV, 0><<<grid, kBlock, 0, stream>>>(a.m, a.span, 0, a.b, a.x, a.q64, a.dinv, a.r, a.part);
-    mix_resume_kernel<WIDE, DINV, true><<<grid, kBlock, 0, stream>>>(a.m, a.span, 0, 0, a.budget, a.xn, a.x, a.r, a.dinv, a.p, a.y, a.part, a.state, a.hist, a.rtol2, a.atol2, a.nostop);
+    const double *b = (const double *) a.b;
+    double *x = (double *) a.x, *q64 = mix_vec64(a, kMixVecQ64);
+    const T *dinv = (const T *) a.dinv;
+    T *r = mix_vec<T>(a, kMixVecR);
+    if (use_x0) mix_residual_kernel<WIDE, DINV, 1><<<grid, kBlock, 0, stream>>>(a.m, a.span, 0, b, x, q64, dinv, r, a.part);
+    else mix_residual_kernel<WIDE, DINV, 0><<<grid, kBlock, 0, stream>>>(a.m, a.span, 0, b, x, q64, dinv, r, a.part);
+    mix_resume_kernel<WIDE, DINV, true><<<grid, kBlock, 0, stream>>>(a.m, a.span, 0, 0, a.budget, mix_vec64(a, kMixVecXn), x, r, dinv, mix_vec<T>(a, kMixVecP), mix_vec<T>(a, kMixVecY),
+                                                                     a.part, mix_state(a), a.hist, a.rtol2, a.atol2, a.nostop);
 }
 
 // cg_dot<float> and cg_update<float> are spmv_hip_cg's own, on y in the place of x
-template <bool WIDE, bool DINV>
-static void mix_iteration_t(const MixArgs &a, int k, hipStream_t stream)
+template <typename T, bool WIDE, bool DINV>
+static void mix_iteration_t(const SolveArgs &a, int k, hipStream_t stream)
 {
     const unsigned grid = (unsigned) a.parts;
-    cg_dot_kernel<float><<<grid, kBlock, 0, stream>>>(a.m, a.span, a.p, a.q, a.part + (size_t) kCgPartPQ * kCgMaxParts, &a.state->s.end_direction);
-    cg_update_kernel<float, WIDE, DINV><<<grid, kBlock, 0, stream>>>(a.m, a.span, k, a.p, a.q, a.y, a.r, a.dinv, a.part, &a.state->s, a.nostop);
-    mix_direction_kernel<WIDE, DINV><<<grid, kBlock, 0, stream>>>(a.m, a.span, k, a.r, a.dinv, a.p, a.part, a.state, a.hist, a.drop2, a.every, a.budget, a.nostop);
+    const T *dinv = (const T *) a.dinv;
+    T *r = mix_vec<T>(a, kMixVecR), *p = mix_vec<T>(a, kMixVecP), *q = mix_vec<T>(a, kMixVecQ);
+    cg_dot_kernel<T><<<grid, kBlock, 0, stream>>>(a.m, a.span, p, q, a.part + (size_t) kCgPartPQ * kCgMaxParts, &a.state->end_direction);
+    cg_update_kernel<T, WIDE, DINV><<<grid, kBlock, 0, stream>>>(a.m, a.span, k, p, q, mix_vec<T>(a, kMixVecY), r, dinv, a.part, a.state, a.nostop);
+    mix_direction_kernel<WIDE, DINV><<<grid, kBlock, 0, stream>>>(a.m, a.span, k, r, dinv, p, a.part, mix_state(a), a.hist, a.drop2, a.every, a.budget, a.nostop);
 }
 
-template <bool WIDE, bool DINV>
-static void mix_try_t(const MixArgs &a, hipStream_t stream)
+template <typename T, bool WIDE, bool DINV>
+static void mix_try_t(const SolveArgs &a, hipStream_t stream)
 {
-    mix_try_kernel<WIDE><<<(unsigned) a.parts, kBlock, 0, stream>>>(a.m, a.span, a.x, a.y, a.xn, a.state);
+    mix_try_kernel<WIDE><<<(unsigned) a.parts, kBlock, 0, stream>>>(a.m, a.span, (const double *) a.x, mix_vec<T>(a, kMixVecY), mix_vec64(a, kMixVecXn), mix_state(a));
 }
 
-template <bool WIDE, bool DINV>
-static void mix_update_t(const MixArgs &a, int k, int update, hipStream_t stream)
+template <typename T, bool WIDE, bool DINV>
+static void mix_update_t(const SolveArgs &a, int k, int update, hipStream_t stream)
 {
     const unsigned grid = (unsigned) a.parts;
-    mix_residual_kernel<WIDE, DINV, 2><<<grid, kBlock, 0, stream>>>(a.m, a.span, k, a.b, a.x, a.q64, a.dinv, a.r, a.part);
-    mix_resume_kernel<WIDE, DINV, false><<<grid, kBlock, 0, stream>>>(a.m, a.span, k, update, a.budget, a.xn, a.x, a.r, a.dinv, a.p, a.y, a.part, a.state, a.hist, a.rtol2, a.atol2, a.nostop);
+    double *x = (double *) a.x;
+    const T *dinv = (const T *) a.dinv;
+    T *r = mix_vec<T>(a, kMixVecR);
+    mix_residual_kernel<WIDE, DINV, 2><<<grid, kBlock, 0, stream>>>(a.m, a.span, k, (const double *) a.b, x, mix_vec64(a, kMixVecQ64), dinv, r, a.part);
+    mix_resume_kernel<WIDE, DINV, false><<<grid, kBlock, 0, stream>>>(a.m, a.span, k, update, a.budget, mix_vec64(a, kMixVecXn), x, r, dinv, mix_vec<T>(a, kMixVecP),
+                                                                      mix_vec<T>(a, kMixVecY), a.part, mix_state(a), a.hist, a.rtol2, a.atol2, a.nostop);
 }
 
-static bool mix_ok(const MixArgs &a)
+static bool mix_ok(const SolveArgs &a)
 {
-    return a.m > 0 && a.parts >= 1 && a.parts <= kCgMaxParts && a.span * a.parts >= a.m && a.b && a.x && a.xn && a.q64 && a.r && a.p && a.q && a.y && a.part && a.state;
+    for (void *v : a.vec) if (!v) return false;
+    return a.b && a.x && a.part && a.state;
 }
 
-// the checked launch of the instantiation of F that a.wide / a.dinv select
-#define MIX_LAUNCH(F, ok, ...)                                                                       \
-    do {                                                                                             \
-        if (!mix_ok(a) || !(ok)) return hipErrorInvalidValue;                                        \
-        if (a.wide) { if (a.dinv) F<true, true>(__VA_ARGS__); else F<true, false>(__VA_ARGS__); }    \
-        else { if (a.dinv) F<false, true>(__VA_ARGS__); else F<false, false>(__VA_ARGS__); }         \
-        return hipGetLastError();                                                                    \
+// the checked launch of the float form of F that a.wide / a.dinv select
+#define MIX_LAUNCH(F, ok, ...)                                                     \
+    do {                                                                           \
+        if (!args_ok(a) || !mix_ok(a) || !(ok)) return hipErrorInvalidValue;       \
+        FORM_LAUNCH(F, float, __VA_ARGS__);                                        \
+        return hipGetLastError();                                                  \
     } while (0)
 
-hipError_t mix_start_launch(const MixArgs &a, bool use_x0, hipStream_t stream) { MIX_LAUNCH(mix_start_t, true, a, use_x0, stream); }
-hipError_t mix_iteration_launch(const MixArgs &a, int k, hipStream_t stream) { MIX_LAUNCH(mix_iteration_t, k >= 1, a, k, stream); }
-hipError_t mix_try_launch(const MixArgs &a, hipStream_t stream) { MIX_LAUNCH(mix_try_t, true, a, stream); }
-hipError_t mix_update_launch(const MixArgs &a, int k, int update, hipStream_t stream) { MIX_LAUNCH(mix_update_t, k >= 1 && update >= 1, a, k, update, stream); }
+hipError_t mix_start_launch(const SolveArgs &a, bool use_x0, hipStream_t stream) { MIX_LAUNCH(mix_start_t, true, a, use_x0, stream); }
+hipError_t mix_iteration_launch(const SolveArgs &a, int k, hipStream_t stream) { MIX_LAUNCH(mix_iteration_t, k >= 1, a, k, stream); }
+hipError_t mix_try_launch(const SolveArgs &a, hipStream_t stream) { MIX_LAUNCH(mix_try_t, true, a, stream); }
+hipError_t mix_update_launch(const SolveArgs &a, int k, int update, hipStream_t stream) { MIX_LAUNCH(mix_update_t, k >= 1 && update >= 1, a, k, update, stream); }
 
 } // namespace spmv
