@@ -26,10 +26,11 @@ CONVERGED, MAX_ITERATIONS, BREAKDOWN, NONFINITE, STAGNATED = 0, 1, 2, 3, 4
 UPDATE_DROP = 0.01  # SPMV_HIP_CG_MIXED_UPDATE_DROP
 
 
-def cg_mixed(high, low, b, x0=None, dinv=None, rtol=0.0, atol=0.0, max_iterations=0, update_drop=0.0, update_every=0):
+def cg_mixed(high, low, b, x0=None, dinv=None, rtol=0.0, atol=0.0, max_iterations=0, update_drop=0.0, update_every=0, watch=None):
     """-> dict: x, status, iterations, updates, rr (the TRUE one of x), bb, history, iterates (iterates[k] = committed x + widen(y) after
     iteration k: what an update behind iteration k would try), segments (the test that ended each segment, in order) and end (where and why
-    the solve ended)."""
+    the solve ended).  watch(*values, what=None), when given, sees every vector and every scalar, float or fp64, as it is formed; what="iteration":
+    the call behind cg_update, its last value the recurrence's <r,r>; what="update": the call behind an update's residual, its last value the rr tried."""
     f32, f64 = np.float32, np.float64
     assert b.dtype == f64 and (dinv is None or dinv.dtype == f32)
     m = b.size
@@ -39,6 +40,7 @@ def cg_mixed(high, low, b, x0=None, dinv=None, rtol=0.0, atol=0.0, max_iteration
     drop = update_drop if update_drop > 0 else UPDATE_DROP
     drop2 = drop * drop
     st = dict(k=0, updates=0)
+    see = watch if watch is not None else (lambda *values, what=None: None)
     history, iterates, segments = [], [], []
 
     def out(x, status, rr, bb, end):
@@ -49,9 +51,13 @@ def cg_mixed(high, low, b, x0=None, dinv=None, rtol=0.0, atol=0.0, max_iteration
             x, r64 = np.zeros_like(b), b.copy()
         else:
             x = x0.copy()
-            r64 = b - high(x)
+            ax = high(x)
+            r64 = b - ax
+            see(ax)
         bb, rr = dot(b, b), dot(r64, r64)
+        see(b, x, r64, f64(bb), f64(rr)) if dinv is None else see(b, x, r64, f64(bb), f64(rr), dinv)
         thr = max(rtol * rtol * bb, atol * atol)
+        see(f64(rtol * rtol), f64(rtol * rtol * bb), f64(atol * atol), f64(drop2))
         history.append(rr)
         iterates.append(x.copy())
         if not (fin(bb) and fin(rr)):
@@ -69,6 +75,7 @@ def cg_mixed(high, low, b, x0=None, dinv=None, rtol=0.0, atol=0.0, max_iteration
             y = np.zeros(m, dtype=f32)
             z = dinv * r if dinv is not None else r.copy()
             rz, rs = dot(r, z), dot(r, r)
+            see(r, z, f64(rz), f64(rs))
             seg, n = rs, 0
             if not (fin(rs) and fin(rz)):
                 return out(x, NONFINITE, rr, bb, "segment:nonfinite")
@@ -82,11 +89,13 @@ def cg_mixed(high, low, b, x0=None, dinv=None, rtol=0.0, atol=0.0, max_iteration
             while reason is None:
                 q = low(p)
                 pq = dot(p, q)
+                see(p, q, f64(pq))
                 if not (fin(pq) and fin(rz)):
                     return out(x, NONFINITE, rr, bb, "update:dot_nonfinite")
                 if pq <= 0:
                     return out(x, BREAKDOWN, rr, bb, "update:pq_breakdown")
                 alpha = f32(f64(rz) / f64(pq))           # fp64 quotient, rounded to float once
+                see(f64(rz) / f64(pq), alpha)
                 if not fin(alpha):
                     return out(x, NONFINITE, rr, bb, "update:alpha_nonfinite")
                 ap, aq = alpha * p, alpha * q
@@ -94,6 +103,7 @@ def cg_mixed(high, low, b, x0=None, dinv=None, rtol=0.0, atol=0.0, max_iteration
                 r = r - aq
                 z = dinv * r if dinv is not None else r
                 rzn, rs = dot(r, z), dot(r, r)
+                see(ap, aq, y, r, z, f64(rzn), f64(rs), what="iteration")
                 st["k"] += 1
                 n += 1
                 history.append(rs)
@@ -106,10 +116,12 @@ def cg_mixed(high, low, b, x0=None, dinv=None, rtol=0.0, atol=0.0, max_iteration
                 if rzn <= 0:
                     return out(x, BREAKDOWN, rr, bb, "direction:rz_breakdown")
                 beta = f32(f64(rzn) / f64(rz))
+                see(f64(rzn) / f64(rz), beta)
                 if not fin(beta):
                     return out(x, NONFINITE, rr, bb, "direction:beta_nonfinite")
                 bp = beta * p
                 p = z + bp
+                see(bp, p)
                 rz = rzn
                 if rs <= thr:
                     reason = "estimate"
@@ -121,8 +133,10 @@ def cg_mixed(high, low, b, x0=None, dinv=None, rtol=0.0, atol=0.0, max_iteration
                     reason = "budget"
             segments.append(reason)
             xn = x + y.astype(f64)                        # widen, an fp64 add
-            r64n = b - high(xn)
+            axn = high(xn)
+            r64n = b - axn
             rrn = dot(r64n, r64n)
+            see(axn, xn, r64n, f64(rrn), what="update")
             if not fin(rrn):
                 return out(x, NONFINITE, rr, bb, "resume:nonfinite")
             if reason in ("exact", "estimate", "drop") and rrn >= rr:

@@ -33,26 +33,33 @@ def workspace_bytes(m, itemsize, restart):
     return (restart + 3) * ((m * itemsize + 255) // 256 * 256) + PARTIAL_ARRAYS * 8192 + STATE_ROOM
 
 
-def _apply(T, V, R, g, n, x, dinv):
+def _apply(T, V, R, g, n, x, dinv, see=lambda *values: None):
     """the cycle's end over the n steps applied: R y = g by back substitution in fp64, u = sum T(y_i) v_i, x + Dinv u"""
     f64 = np.float64
     y = [f64(0)] * n
     for i in range(n - 1, -1, -1):
         s = f64(0)
         for c in range(i + 1, n):
-            s = s + R[c][i] * y[c]
+            ry = R[c][i] * y[c]
+            s = s + ry
+            see(ry)
         y[i] = (g[i] - s) / R[i][i]
+        see(s, g[i] - s, y[i], T(y[i]))
     u = None
     for i in range(n):
         yv = T(y[i]) * V[i]
         u = yv if u is None else u + yv
-    return x + (dinv * u if dinv is not None else u)
+        see(yv, u)
+    xn = x + (dinv * u if dinv is not None else u)
+    see(xn) if dinv is None else see(xn, dinv * u)
+    return xn
 
 
-def gmres(multiply, b, restart, x0=None, dinv=None, rtol=0.0, atol=0.0, max_iterations=0):
+def gmres(multiply, b, restart, x0=None, dinv=None, rtol=0.0, atol=0.0, max_iterations=0, watch=None):
     """Right-preconditioned GMRES(restart) as spmv_hip_gmres runs it.  multiply(p) -> A p in b's dtype.  -> dict: x, status, iterations, rr, bb,
     history (the estimate after iteration 0 .. iterations), iterates (x after iteration 0 .. iterations: what a run with a smaller
-    max_iterations returns) and end: the test that ended the loop ("rotate:converged", ...; "budget" when none did)."""
+    max_iterations returns) and end: the test that ended the loop ("rotate:converged", ...; "budget" when none did).  watch(*values), when given, sees every vector and
+    every scalar, of type T or fp64, as it is formed."""
     T = b.dtype.type
     f64 = np.float64
     m = b.size
@@ -60,14 +67,19 @@ def gmres(multiply, b, restart, x0=None, dinv=None, rtol=0.0, atol=0.0, max_iter
     if m == 0:
         return dict(x=b.copy(), status=CONVERGED, iterations=0, rr=0.0, bb=0.0, history=np.zeros(0), iterates=[], end="begin:empty")
     fin = np.isfinite
+    see = watch if watch is not None else (lambda *values: None)
     with np.errstate(all="ignore"):
         if x0 is None:
             x, r = np.zeros_like(b), b.copy()
         else:
             x = x0.copy()
-            r = b - multiply(x)
+            ax = multiply(x)
+            r = b - ax
+            see(ax)
         rr, bb = dot(r, r), dot(b, b)
+        see(b, x, r, f64(rr), f64(bb)) if dinv is None else see(b, x, r, f64(rr), f64(bb), dinv)
         thresh = max(rtol * rtol * bb, atol * atol)
+        see(f64(rtol * rtol), f64(rtol * rtol * bb), f64(atol * atol))
         status, end = None, "budget"
         if not (fin(bb) and fin(rr)):
             status, end = NONFINITE, "begin:nonfinite"
@@ -82,31 +94,40 @@ def gmres(multiply, b, restart, x0=None, dinv=None, rtol=0.0, atol=0.0, max_iter
             beta = np.sqrt(rr_cycle)
             g = [beta]
             V = [r * T(f64(1) / beta)]
+            see(beta, f64(1) / beta, T(f64(1) / beta), V[0])
             R, cs, sn = [], [], []
             n = 0                                             # steps of this cycle that were applied
             while status is None and k < max_iterations and n < restart:
                 j = n + 1
                 z = dinv * V[n] if dinv is not None else V[n]
                 w = multiply(z)
+                see(z, w)
                 a = [T(dot(V[i], w)) for i in range(j)]      # pass 1: all dots of the same w
+                see(*(f64(dot(V[i], w)) for i in range(j)), *a)
                 for i in range(j):
                     av = a[i] * V[i]
                     w = w - av
+                    see(av, w)
                 e = [T(dot(V[i], w)) for i in range(j)]      # pass 2
+                see(*(f64(dot(V[i], w)) for i in range(j)), *e)
                 for i in range(j):
                     ev = e[i] * V[i]
                     w = w - ev
+                    see(ev, w)
                 ww = f64(dot(w, w))
                 hn = np.sqrt(ww)
                 h = [f64(a[i]) + f64(e[i]) for i in range(j)]
+                see(ww, hn, *h)
                 finite = bool(fin(ww)) and all(fin(v) for v in h)
                 for i in range(j - 1):
                     hi, hk = h[i], h[i + 1]
                     t1, t2, t3, t4 = cs[i] * hi, sn[i] * hk, sn[i] * hi, cs[i] * hk
                     h[i], h[i + 1] = t1 + t2, t4 - t3
+                    see(t1, t2, t3, t4, h[i], h[i + 1])
                     finite = finite and bool(fin(h[i])) and bool(fin(h[i + 1]))
                 hj = h[j - 1]
                 d = np.sqrt(hj * hj + hn * hn)
+                see(hj * hj, hn * hn, hj * hj + hn * hn, d)
                 finite = finite and bool(fin(d))
                 if not finite:
                     status, end = NONFINITE, "rotate:nonfinite"
@@ -117,6 +138,7 @@ def gmres(multiply, b, restart, x0=None, dinv=None, rtol=0.0, atol=0.0, max_iter
                 c, s = hj / d, hn / d
                 gn, gc = -(s * g[j - 1]), c * g[j - 1]
                 est = gn * gn
+                see(c, s, s * g[j - 1], gc, est)
                 if not (fin(c) and fin(s) and fin(gc) and fin(est)):
                     status, end = NONFINITE, "rotate:rotation_nonfinite"
                     break
@@ -128,18 +150,21 @@ def gmres(multiply, b, restart, x0=None, dinv=None, rtol=0.0, atol=0.0, max_iter
                 g.append(gn)
                 n, k = j, k + 1
                 history.append(float(est))
-                iterates.append(_apply(T, V, R, g, n, x, dinv))
+                iterates.append(_apply(T, V, R, g, n, x, dinv, see))
                 if est <= thresh:
                     status, end = CONVERGED, "rotate:converged"
                 elif hn == 0:
                     status, end = BREAKDOWN, "rotate:exhausted"
                 else:
                     V.append(w * T(f64(1) / hn))
+                    see(f64(1) / hn, T(f64(1) / hn), V[-1])
             if n > 0:
                 x = iterates[-1].copy()
             if status is None and n == restart:              # the restart behind every full cycle, also when the budget ends on it
-                r = b - multiply(x)
+                ax = multiply(x)
+                r = b - ax
                 rr_cycle = f64(dot(r, r))
+                see(ax, r, rr_cycle)
                 if not fin(rr_cycle):
                     status, end = NONFINITE, "restart:nonfinite"
                 elif rr_cycle == 0:
