@@ -1048,6 +1048,87 @@ typedef struct spmv_hip_cg_mixed_result {
 int spmv_hip_cg_mixed(spmv_Handle_t high, spmv_Handle_t low, const double *B, double *X,
                       const spmv_hip_cg_mixed_options *opt, spmv_hip_cg_mixed_result *res);
 
+/* ---- LSQR on the device: least squares for a matrix of any shape ---------------------------------
+ * LSQR (Paige and Saunders, "LSQR: an algorithm for sparse linear equations and sparse least squares", 1982) minimises
+ * |A x - b|^2 + damp^2 |x|^2 for ANY m x n matrix: an overdetermined fit, the minimum-norm solution of an underdetermined system, a ridge
+ * regression.  Per iteration the handle's own multiply q = A v -- spmv()'s schedule and bits --, the multiply qt = A^T u of the transpose
+ * that spmv_hip_spmv_transpose uses -- its bits -- and four vector kernels.  The bidiagonalisation's alpha and beta, the rotations and the
+ * stop tests are formed on the device; the host enqueues check_every iterations, then looks at a small state once.
+ *   - Returns SPMV_HIP_OK whenever the solve RAN; synchronous, as spmv_hip_cg.  The CSR arguments follow spmv()'s rules, as in spmv_hip_cg.
+ *   - B: m elements, X: n elements, of the handle's type, host or device pointers (host ones are staged through the buffers spmv_hip_cg's B and X
+ *     use); they must not overlap.  use_x0 = 0: the solve starts from x = 0 and X is only written; otherwise X holds x0, the iterations run on
+ *     r0 = B - A x0, and the damping acts on x - x0.  There is no Dinv.
+ *   - The transpose is built at the first call, as by spmv_hip_prepare_transpose, counted in device_bytes and kept in step with
+ *     spmv_hip_update_values and in-place value changes as spmv_hip_spmv_transpose keeps it.
+ *   - Stop: rr <= max(rtol^2 * bb, atol^2) with rr the recurrence's ESTIMATE of |r|^2 + damp^2 |x - x0|^2 (spmv_hip_cg's rule) -> _CONVERGED;
+ *     ar <= ls_tol * (anorm * sqrt(rr)) with ar the estimate of |A^T r - damp^2 (x - x0)| and anorm the running estimate of the Frobenius
+ *     norm of [A; damp I] -> SPMV_HIP_LSQR_LEAST_SQUARES: x is a least-squares solution of a system that need not be consistent.
+ *     _MAX_ITERATIONS and _NONFINITE (a NaN or infinity in a dot, a scalar of the chain or a factor of a vector) keep their meaning;
+ *     _BREAKDOWN is never returned.  rtol = atol = ls_tol = 0 runs max_iterations iterations unless rr or ar reaches 0.
+ *   - m = 0 or bb = 0: X is set to zeros, converged, 0 iterations.  ar and anorm are 0 at every end that comes before alpha is formed.
+ *   - history (a HOST array of max_iterations + 1 doubles, or NULL) receives rr after iteration 0, 1, ..., iterations.
+ *   - Workspace, the solver's own: u, q (m elements each), v, w, qt (n elements each), three arrays of 1024 partial sums and the state in ONE
+ *     block of 2 * up256(m * sizeof(T)) + 3 * up256(n * sizeof(T)) + 3 * 8192 + 256 bytes, allocated at the first call; the history's device
+ *     copy in another; freed and counted as spmv_hip_cg's.  The other solvers' workspaces are neither shared nor grown.
+ *   - Errors (SPMV_HIP_E_ARG, X untouched): NULL opt or res; NULL B when m > 0, NULL X when n > 0; a negative or NaN rtol, atol, ls_tol or
+ *     damp; max_iterations < 0, check_every < 0; multi-GPU handles, host_rows handles, handles created with option "reorder".  A cleared or
+ *     failed handle: SPMV_HIP_E_NOSTATE.
+ *
+ * The arithmetic contract -- bits, not a tolerance; tests/lsqr_cases.py restates it in numpy.  Elements are of the handle's type T; all scalars
+ * are fp64, with every product, sum, quotient and square root a separate operation; the square root is spmv_hip_gmres's, the correctly rounded
+ * one.  dot(a,a) is spmv_hip_cg's dot over a's OWN length: P and L follow from m for B and u, from n for v.  A scalar that multiplies or divides
+ * a vector is rounded to T once; the vector operations are in T, a multiply and then an add or a subtraction, never an fma; a division is a
+ * division (not a multiplication by a reciprocal).  thr = max(rtol^2 * bb, atol^2).
+ *   start:   x = 0 (or X);  u = B (or u = B - A*x through the handle's multiply);  bb = dot(B,B);  uu = dot(u,u)
+ *            nonfinite(bb, uu) -> NONFINITE;  bb == 0 -> X = 0, rr = 0, CONVERGED;  rr = uu = history[0];  rr <= thr -> CONVERGED   (0 iterations)
+ *            beta = sqrt(uu);  u = u / T(beta);  v = A^T*u -- the transpose's own multiply;  vv = dot(v,v);  nonfinite(vv) -> NONFINITE
+ *            alpha = sqrt(vv);  alpha == 0 -> LEAST_SQUARES, ar = 0;  v = v / T(alpha);  w = v
+ *            phibar = beta;  rhobar = alpha;  a2 = alpha*alpha;  psi2 = 0;  ar = alpha*beta;  anorm = sqrt(a2)
+ *            max_iterations == 0 -> MAX_ITERATIONS
+ *   iteration k = 1, 2, ...:
+ *         1. q = A*v                                                            -- the handle's multiply, spmv()'s bits
+ *         2. u = q - T(alpha)*u;  uu = dot(u,u);  nonfinite(uu) -> NONFINITE                                       (iterations = k - 1)
+ *         3. beta = sqrt(uu);  beta > 0: u = u / T(beta)
+ *         4. qt = A^T*u                                                         -- always enqueued
+ *         5. v = qt - T(beta)*v;  vv = dot(v,v);  nonfinite(vv) -> NONFINITE                                       (iterations = k - 1)
+ *         6. alpha = sqrt(vv);  alpha > 0: v = v / T(alpha)
+ *         7. a2 = ((a2 + beta*beta) + alpha*alpha) + damp*damp
+ *         8. rhobar1 = sqrt(rhobar*rhobar + damp*damp);  c1 = rhobar / rhobar1;  s1 = damp / rhobar1
+ *         9. psi = s1*phibar;  phibar = c1*phibar;  psi2 = psi2 + psi*psi
+ *        10. rho = sqrt(rhobar1*rhobar1 + beta*beta);  c = rhobar1 / rho;  s = beta / rho
+ *        11. theta = s*alpha;  rhobar = -(c*alpha);  phi = c*phibar;  phibar = s*phibar (of the phibar of step 9);  tau = s*phi
+ *        12. nonfinite(T(phi / rho)) or nonfinite(T(theta / rho)) -> NONFINITE                                     (iterations = k - 1)
+ *        13. x = x + T(phi / rho)*w                                             -- from here on iterations = k
+ *        14. rr = phibar*phibar + psi2 = history[k];  ar = alpha*|tau|;  anorm = sqrt(a2)
+ *        15. in this order: nonfinite(rr, ar, a2) -> NONFINITE;  rr <= thr -> CONVERGED;  ar <= ls_tol*(sqrt(a2)*sqrt(rr)) -> LEAST_SQUARES
+ *            (beta == 0 and alpha == 0 end here or at the test before it: ar is 0)
+ *        16. otherwise w = v - T(theta / rho)*w
+ *        17. k == max_iterations without a status -> MAX_ITERATIONS
+ *   An end with iterations = k - 1 returns the x, rr, ar, anorm and history of iteration k - 1.
+ *   Consequences: X, status, iterations, rr, ar, anorm and history are bit-identical run to run, for every check_every, for host or device
+ *   pointers and every pointer alignment; a run with max_iterations = k returns the iterate k of a longer run; the handle's method changes the
+ *   bits only as far as it changes spmv()'s and spmv_hip_spmv_transpose's (unless the handle was created with option "deterministic" = 0). */
+enum { SPMV_HIP_LSQR_LEAST_SQUARES = 5 };   /* returned by spmv_hip_lsqr alone */
+typedef struct spmv_hip_lsqr_options {
+    double rtol, atol;        /* stop when rr <= max(rtol^2 * bb, atol^2) */
+    double ls_tol;            /* stop when ar <= ls_tol * (anorm * sqrt(rr)) */
+    double damp;              /* >= 0 */
+    int max_iterations;       /* >= 0 */
+    int check_every;          /* iterations enqueued between two looks at the device's state; 0 = default */
+    int use_x0;               /* 0: start from x = 0 (X is only written); != 0: X holds the initial guess */
+    double *history;          /* NULL, or HOST array of max_iterations + 1 doubles: rr after iteration 0, 1, ... */
+} spmv_hip_lsqr_options;
+typedef struct spmv_hip_lsqr_result {
+    int status;               /* SPMV_HIP_CG_CONVERGED 0, _MAX_ITERATIONS 1, _NONFINITE 3, SPMV_HIP_LSQR_LEAST_SQUARES 5 */
+    int iterations;           /* updates of x that were applied */
+    double rr, bb;            /* the residual estimate of the returned x, and <b,b> */
+    double ar;                /* the estimate of |A^T r - damp^2 x| */
+    double anorm;             /* the running Frobenius estimate sqrt(a2) */
+} spmv_hip_lsqr_result;
+int spmv_hip_lsqr(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx,
+                  const void *Matrix_Val, const void *B, void *X,
+                  const spmv_hip_lsqr_options *opt, spmv_hip_lsqr_result *res);
+
 #endif /* SPMV_HIP_EXT_H */
 
 #if defined(__cplusplus)

@@ -123,6 +123,11 @@ double spmv_hip_time_gmres_iterations(spmv_Handle_t handle, const void *B, void 
 struct spmv_hip_cg_mixed_options;
 double spmv_hip_time_cg_mixed_iterations(spmv_Handle_t high, spmv_Handle_t low, const double *B, double *X, const struct spmv_hip_cg_mixed_options *opt, int warmup, int iters,
                                          float *ms_out);
+/* spmv_hip_lsqr's iterations, timed as spmv_hip_time_cg_iterations times spmv_hip_cg's: an iteration is the multiply, lsqr_u, lsqr_unit_u, the
+   transpose's multiply, lsqr_v, lsqr_step.  B: a DEVICE array of m elements, X: one of n elements; the transpose is built when it is not yet.
+   spmv_hip_lsqr's handle rules; rtol, atol, ls_tol, check_every and history are not used (damp is).  Returns the mean ms per run, < 0 on error. */
+struct spmv_hip_lsqr_options;
+double spmv_hip_time_lsqr_iterations(spmv_Handle_t handle, const void *B, void *X, const struct spmv_hip_lsqr_options *opt, int warmup, int iters, float *ms_out);
 /* out[i] = the fp64 square root of in[i] exactly as spmv_hip_gmres's kernels take it (a kernel of the same translation unit, the same
    compiler flags): n doubles each, DEVICE pointers on the current device; synchronous.  For the test that holds it against a correctly
    rounded square root; SPMV_HIP_E_ARG for n < 0, NULL or host pointers. */

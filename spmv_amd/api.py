@@ -92,8 +92,18 @@ class spmv_hip_cg_mixed_result(C.Structure):  # include/spmv_hip.h
     _fields_ = [("status", C.c_int), ("iterations", C.c_int), ("updates", C.c_int), ("rr", C.c_double), ("bb", C.c_double)]
 
 
+class spmv_hip_lsqr_options(C.Structure):  # include/spmv_hip.h
+    _fields_ = [("rtol", C.c_double), ("atol", C.c_double), ("ls_tol", C.c_double), ("damp", C.c_double), ("max_iterations", C.c_int), ("check_every", C.c_int),
+                ("use_x0", C.c_int), ("history", C.POINTER(C.c_double))]
+
+
+class spmv_hip_lsqr_result(C.Structure):  # include/spmv_hip.h
+    _fields_ = [("status", C.c_int), ("iterations", C.c_int), ("rr", C.c_double), ("bb", C.c_double), ("ar", C.c_double), ("anorm", C.c_double)]
+
+
 CG_STATUS = ("converged", "max_iterations", "breakdown", "nonfinite")  # SPMV_HIP_CG_*
 CG_MIXED_STATUS = CG_STATUS + ("stagnated",)  # spmv_hip_cg_mixed alone has SPMV_HIP_CG_STAGNATED
+LSQR_STATUS = CG_MIXED_STATUS + ("least_squares",)  # spmv_hip_lsqr alone has SPMV_HIP_LSQR_LEAST_SQUARES (5); it never returns 2 or 4
 
 # The fused attention's entry points (include/spmv_hip.h, spmv_hip_tools.h), a row each: the stem, then the size arguments and the operands in
 # the prototype's order.  A size is an int -- scale a double --, an operand a void * followed by its leading dimension or plane stride, a
@@ -199,6 +209,8 @@ FUNCTIONS = {
                                                          C.POINTER(C.c_float)]),
     "spmv_hip_cg_mixed": (C.c_int, [spmv_Handle_t, spmv_Handle_t, _V, _V, C.POINTER(spmv_hip_cg_mixed_options), C.POINTER(spmv_hip_cg_mixed_result)]),
     "spmv_hip_time_cg_mixed_iterations": (C.c_double, [spmv_Handle_t, spmv_Handle_t, _V, _V, C.POINTER(spmv_hip_cg_mixed_options), C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "spmv_hip_lsqr": (C.c_int, [spmv_Handle_t, C.c_int, _V, _V, _V, _V, _V, C.POINTER(spmv_hip_lsqr_options), C.POINTER(spmv_hip_lsqr_result)]),
+    "spmv_hip_time_lsqr_iterations": (C.c_double, [spmv_Handle_t, _V, _V, C.POINTER(spmv_hip_lsqr_options), C.c_int, C.c_int, C.POINTER(C.c_float)]),
     # include/spmv_io.h (host only)
     "spmv_io_read_mtx": (C.c_int, [C.c_char_p, C.c_size_t, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_V)]),
     "spmv_io_cache_path": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t]),
@@ -849,11 +861,13 @@ def _cg_options(rtol, atol, max_iterations, check_every, x0, dinv, history, colu
 
 
 def _solve_result(res, names, rc=0, hist=None):
-    """a spmv_hip_cg_result or spmv_hip_cg_mixed_result -> the result dict; names: CG_STATUS or CG_MIXED_STATUS"""
+    """a spmv_hip_cg_result, spmv_hip_cg_mixed_result or spmv_hip_lsqr_result -> the result dict; names: CG_STATUS, CG_MIXED_STATUS or LSQR_STATUS"""
     out = {"status": res.status, "status_name": names[res.status] if 0 <= res.status < len(names) else "?", "iterations": res.iterations}
     if hasattr(res, "updates"):
         out["updates"] = res.updates
     out.update(rr=res.rr, bb=res.bb)
+    if hasattr(res, "ar"):
+        out.update(ar=res.ar, anorm=res.anorm)
     if hist is not None:
         out["history"] = hist[:res.iterations + 1].copy() if rc == 0 else hist[:0].copy()
     return out
@@ -940,6 +954,31 @@ def time_cg_mixed_iterations(high, low, B, X, iterations, update_every=0, x0=Fal
     update_every-th one (0: none), stop tests off, on device B / X / dinv (spmv_hip_time_cg_mixed_iterations)."""
     opt, _ = _cg_options(0.0, 0.0, iterations, 0, x0, dinv, False, mixed=(0.0, update_every))
     return _timed("spmv_hip_time_cg_mixed_iterations", (high, low, _ptr(B), _ptr(X), C.byref(opt)), warmup, iters)
+
+
+def _lsqr_options(rtol, atol, ls_tol, damp, max_iterations, check_every, x0, history):
+    """-> (spmv_hip_lsqr_options, the history array or None)"""
+    hist = np.zeros(int(max_iterations) + 1, dtype=np.float64) if history and max_iterations >= 0 else None
+    return spmv_hip_lsqr_options(float(rtol), float(atol), float(ls_tol), float(damp), int(max_iterations), int(check_every), 1 if x0 else 0,
+                                 hist.ctypes.data_as(C.POINTER(C.c_double)) if hist is not None else None), hist
+
+
+def lsqr(handle, m, RowPtr, ColIdx, Matrix_Val, B, X, damp=0.0, rtol=1e-8, atol=0.0, ls_tol=1e-8, max_iterations=1000, check_every=0, x0=False, history=False,
+         check=True):
+    """Minimise |A x - B|^2 + damp^2 |x|^2 by LSQR on the device (spmv_hip_lsqr; A of any shape): B of m elements, X of n, host or device; x0: X
+    holds the initial guess.  -> (rc, result dict: status, status_name, iterations, rr, bb, ar, anorm[, history: the residual estimate after
+    iteration 0 .. iterations]); status "least_squares": the normal-equations test ar <= ls_tol * anorm * sqrt(rr) held."""
+    opt, hist = _lsqr_options(rtol, atol, ls_tol, damp, max_iterations, check_every, x0, history)
+    res = spmv_hip_lsqr_result()
+    rc = _checked(load().spmv_hip_lsqr(handle, int(m), _ptr(RowPtr), _ptr(ColIdx), _ptr(Matrix_Val), _ptr(B), _ptr(X), C.byref(opt), C.byref(res)), "spmv_hip_lsqr", check)
+    return rc, _solve_result(res, LSQR_STATUS, rc, hist)
+
+
+def time_lsqr_iterations(handle, B, X, iterations, damp=0.0, x0=False, warmup=2, iters=20):
+    """-> (mean ms per run, per-run ms array) of `iters` runs of `iterations` LSQR iterations each, stop tests off, on device B (m elements) and
+    X (n elements) (spmv_hip_time_lsqr_iterations)."""
+    opt, _ = _lsqr_options(0.0, 0.0, 0.0, damp, iterations, 0, x0, False)
+    return _timed("spmv_hip_time_lsqr_iterations", (handle, _ptr(B), _ptr(X), C.byref(opt)), warmup, iters)
 
 
 CG_COLUMNS_MAX = 16  # SPMV_HIP_CG_COLUMNS_MAX
@@ -1205,6 +1244,24 @@ class Handle:
         def solve(h, m, rp, ci, va, b, x, rtol, atol, max_iterations, check_every, x0, dinv, history):
             return gmres(h, m, rp, ci, va, b, x, restart, rtol, atol, max_iterations, check_every, x0, dinv, history)
         return self._solve(solve, b, x, x0, rtol, atol, max_iterations, check_every, dinv, history)
+
+    def lsqr(self, b, x=None, x0=False, damp=0.0, rtol=1e-8, atol=0.0, ls_tol=1e-8, max_iterations=1000, check_every=0, history=False):
+        """Minimise |A x - b|^2 + damp^2 |x|^2 by LSQR that stays on the device (spmv_hip_lsqr; A of any shape: an overdetermined fit, the
+        minimum-norm solution of an underdetermined system, a ridge regression).  b has m elements; x (n elements) is allocated like b when
+        None (then x0 must be off); x0: x holds the initial guess.  The result's status is "converged" (the residual estimate rr fell to
+        max(rtol^2 bb, atol^2): a consistent system), "least_squares" (ar <= ls_tol * anorm * sqrt(rr): a least-squares solution),
+        "max_iterations" or "nonfinite"; ar estimates |A^T r - damp^2 x|, anorm the Frobenius norm of [A; damp I].  The transpose is built at
+        the first call.  Measured on an MI355X: DESIGN 3.31.
+        -> (x, result dict) or (x, result dict, history) when history is set: rr after iteration 0 .. iterations."""
+        if x is None:
+            if x0:
+                raise ValueError("x0 needs an x that holds the initial guess")
+            x = self._like(b, (self.n,))
+        rp, ci, va = self._keep
+        _, res = lsqr(self.h, self.m, rp, ci, va, b, x, damp, rtol, atol, ls_tol, max_iterations, check_every, x0, history)
+        if history:
+            return x, res, res.pop("history")
+        return x, res
 
     def _attention_out(self, Q, V, heads, kv_heads, out, dtype=None):
         """-> `out`, or when that is None the uninitialised output of an attention forward: (m, heads * dv) like Q -- of `dtype` where one is

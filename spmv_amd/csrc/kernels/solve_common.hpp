@@ -1,4 +1,4 @@
-// solve_common.hpp -- what the vector kernels of the five device-resident solvers share (cg.hpp, bicgstab.hpp, cg_columns.hpp, gmres.hpp, cg_mixed.hpp): the
+// solve_common.hpp -- what the vector kernels of the six device-resident solvers share (cg.hpp, bicgstab.hpp, cg_columns.hpp, gmres.hpp, cg_mixed.hpp, lsqr.hpp): the
 // state and the arguments of a solve, the 4-element accesses, the sums of a dot, and the two kernels that more than one solver launches -- the
 // dot that leaves one array of partials (cg_dot_kernel) and the state of iteration 0 (cg_begin_kernel).
 //
@@ -33,6 +33,9 @@ struct ColsState; // cg_columns.hpp: the per-column state of spmv_hip_cg_columns
 // what one solve's launches need (device pointers)
 struct SolveArgs {
     int m = 0, parts = 0;
+    int n = 0, parts_n = 0;        // spmv_hip_lsqr, whose x, v and w have n elements: that length and its P,
+    long long span_n = 0;          // and its L
+    double ls_tol = 0, damp = 0;   // spmv_hip_lsqr
     int k = 1;                     // right-hand sides: 1 but for spmv_hip_cg_columns, whose workspace vectors are m x k with ld = k
     long long ldb = 1, ldx = 1;    // leading dimensions of b and x
     long long span = 0;            // L

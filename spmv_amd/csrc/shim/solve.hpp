@@ -1,7 +1,7 @@
-// shim/solve.hpp -- part of spmv_shim.hip: the five solves on the RESIDENT matrix that stay on the device and their timer: conjugate gradients
+// shim/solve.hpp -- part of spmv_shim.hip: the six solves on the RESIDENT matrix that stay on the device and their timer: conjugate gradients
 // (spmv_hip_cg), BiCGStab (spmv_hip_bicgstab), conjugate gradients for k right-hand sides at once (spmv_hip_cg_columns), restarted GMRES
-// (spmv_hip_gmres) and mixed-precision conjugate gradients on a pair of handles (spmv_hip_cg_mixed).  The vector kernels are kernels/cg.hpp,
-// bicgstab.hpp, cg_columns.hpp, gmres.hpp and cg_mixed.hpp, launched from their own translation unit (spmv_solve.hip); the multiplies -- q = A p,
+// (spmv_hip_gmres), mixed-precision conjugate gradients on a pair of handles (spmv_hip_cg_mixed) and LSQR for any m x n matrix
+// (spmv_hip_lsqr).  The vector kernels are kernels/cg.hpp, bicgstab.hpp, cg_columns.hpp, gmres.hpp, cg_mixed.hpp and lsqr.hpp, launched from their own translation unit (spmv_solve.hip); the multiplies -- q = A p,
 // or v = A ph and t = A sh -- are launch<T>() on workspace vectors: the launch spmv_shim_run makes, without its staging: the handle's own
 // schedule, spmv()'s bits.  For k columns the multiply is spmm_panels() on the compact workspace vectors: the launches spmv_shim_spmm makes,
 // without its staging: spmv_hip_spmm's bits.
@@ -17,7 +17,9 @@
 // most rows leave empty.  k, ldb and ldx are 1 for the single solves.  spmv_hip_gmres's workspace has `restart` vectors more than its fixed
 // three, and it has a `finish`: the columns of an unfinished cycle are applied to x behind the last look.  spmv_hip_cg_mixed has vectors of
 // two sizes, an `admit` (what its pair of handles must share) and a `resume`: a look that finds a segment ended enqueues the update, and the
-// loop goes on.
+// loop goes on.  spmv_hip_lsqr is the one solver whose matrix need not be square: its vectors have two LENGTHS (b, u and q m elements; x, v,
+// w and qt n), each with its own geometry of the dots, and its second multiply is launch<T>() on the attached transpose: the launch
+// spmv_hip_spmv_transpose makes, without its staging.
 #pragma once
 
 // what the host reads out of a solver's state, per column
@@ -25,7 +27,8 @@ struct SolveLook {
     bool done[kCcgMaxK];
     int status[kCcgMaxK], iterations[kCcgMaxK];
     double rr[kCcgMaxK], bb[kCcgMaxK];
-    int updates; // spmv_hip_cg_mixed: committed updates
+    int updates;      // spmv_hip_cg_mixed: committed updates
+    double ar, anorm; // spmv_hip_lsqr
 };
 
 // one solve or timing: the handle, spmv_hip_cg_mixed's fp32 one (nullptr otherwise), the device operands
@@ -38,6 +41,7 @@ struct Solver {
     int id;                           // SPMV_SHIM_SOLVE_*: the row's index in kSolvers, and of its storage in spmv_dev::solve_ws
     const char *name;                 // in error texts
     int vectors, vectors4;            // workspace vectors of m k elements of the handle's type, and behind them of m k 4-byte elements
+    int vectors_n;                    // spmv_hip_lsqr: behind those, workspace vectors of n elements of the handle's type; != 0: x has n elements and m != n is allowed
     int part_arrays;                  // partial arrays of kCgMaxParts doubles PER COLUMN
     int vectors_per_step;             // spmv_hip_gmres: further vectors per step of a cycle; its workspace is sized by `restart`, not by k (0: by k)
     int max_k;                        // most right-hand sides of a call
@@ -143,6 +147,26 @@ static int gmres_finish(const Solver &s, const SolveRun &r, const void *state)
     return ((const GmresState *) state)->pending > 0 ? solve_launched(s, gmres_apply_launch(r.a, 1, r.d->stream)) : SPMV_HIP_OK;
 }
 
+// (q = A x0,) lsqr_init + lsqr_unit_u, v = A^T u, lsqr_vv + lsqr_step
+static int lsqr_start(const Solver &s, const SolveRun &r, bool use_x0)
+{
+    const SolveArgs &a = r.a;
+    int rc;
+    if (use_x0 && (rc = solve_multiply(r.d, a.x, a.vec[kLsqrVecQ]))) return rc;
+    if ((rc = solve_launched(s, lsqr_init_launch(a, use_x0, r.d->stream))) || (rc = solve_multiply(r.d->tr, a.vec[kLsqrVecU], a.vec[kLsqrVecV]))) return rc;
+    return solve_launched(s, lsqr_first_launch(a, use_x0, r.d->stream));
+}
+
+// q = A v, lsqr_u + lsqr_unit_u, qt = A^T u, lsqr_v + lsqr_step: both multiplies are always enqueued
+static int lsqr_iteration(const Solver &s, const SolveRun &r, int k)
+{
+    const SolveArgs &a = r.a;
+    int rc;
+    if ((rc = solve_multiply(r.d, a.vec[kLsqrVecV], a.vec[kLsqrVecQ])) || (rc = solve_launched(s, lsqr_u_launch(a, k, r.d->stream)))) return rc;
+    if ((rc = solve_multiply(r.d->tr, a.vec[kLsqrVecU], a.vec[kLsqrVecQt]))) return rc;
+    return solve_launched(s, lsqr_v_launch(a, k, r.d->stream));
+}
+
 static void single_look(const void *state, int, SolveLook &l)
 {
     const SolveState &hs = *(const SolveState *) state;
@@ -165,24 +189,43 @@ static void cols_look(const void *state, int k, SolveLook &l)
     }
 }
 
-// bytes of one workspace vector of m x k elements of `elem` bytes
+static void lsqr_look(const void *state, int k, SolveLook &l)
+{
+    single_look(state, k, l);
+    l.ar = ((const LsqrState *) state)->ar;
+    l.anorm = ((const LsqrState *) state)->anorm;
+}
+
+// bytes of one workspace vector of m x k elements of `elem` bytes, and of one of spmv_hip_lsqr's of n elements
 static size_t solve_vec_bytes(const spmv_dev *d, int k, size_t elem) { return (elem * (size_t) d->m * (size_t) k + 255) & ~(size_t) 255; }
+static size_t solve_vecn_bytes(const spmv_dev *d) { return (d->vsize * (size_t) d->n + 255) & ~(size_t) 255; }
+// the elements of a column of x: n for spmv_hip_lsqr, m (= n) for the others
+static size_t solve_x_rows(const Solver &s, const spmv_dev *d) { return (size_t) (s.vectors_n ? d->n : d->m); }
+// P and L of a dot over `len` >= 0 elements (include/spmv_hip.h); one empty workgroup for len = 0
+static void solve_geometry(long long len, int &parts, long long &span)
+{
+    const long long chunks = (len + kCgChunk - 1) / kCgChunk;
+    parts = (int) (chunks < 1 ? 1 : chunks < kCgMaxParts ? chunks : kCgMaxParts);
+    span = (long long) kCgChunk * ((len + (long long) kCgChunk * parts - 1) / ((long long) kCgChunk * parts));
+    if (span < kCgChunk) span = kCgChunk;
+}
 // what a workspace sized by n (k columns; spmv_hip_gmres: restart n) holds: the columns of a vector, the vectors of the handle's type, all the
 // vectors' bytes, the bytes behind them
 static int solve_cols(const Solver &s, int n) { return s.vectors_per_step ? 1 : n; }
 static int solve_vectors(const Solver &s, int n) { return s.vectors + s.vectors_per_step * n; }
 static size_t solve_vectors_bytes(const Solver &s, const spmv_dev *d, int n)
 {
-    return solve_vectors(s, n) * solve_vec_bytes(d, solve_cols(s, n), d->vsize) + s.vectors4 * solve_vec_bytes(d, solve_cols(s, n), 4);
+    return solve_vectors(s, n) * solve_vec_bytes(d, solve_cols(s, n), d->vsize) + s.vectors4 * solve_vec_bytes(d, solve_cols(s, n), 4) + s.vectors_n * solve_vecn_bytes(d);
 }
 static size_t solve_tail_bytes(const Solver &s, int n) { return sizeof(double) * s.part_arrays * (size_t) solve_cols(s, n) * kCgMaxParts + s.state_room; }
 
 // the vectors, the partial arrays (zeroed once: the entries behind the P in use stay +0.0) and the state: allocated at the solver's first solve --
-// s.vectors * solve_vec_bytes(k, vsize) + s.vectors4 * solve_vec_bytes(k, 4) + 8 * s.part_arrays * k * 1024 + s.state_room bytes -- and given
+// s.vectors * solve_vec_bytes(k, vsize) + s.vectors4 * solve_vec_bytes(k, 4) + s.vectors_n * solve_vecn_bytes() + 8 * s.part_arrays * k * 1024 + s.state_room bytes -- and given
 // back and allocated anew when a call has more columns than it holds (spmv_hip_gmres: a larger restart; its vectors are restart + 3 of m elements)
 static int solve_workspace(const Solver &s, spmv_dev *d, int n)
 {
-    static_assert(sizeof(SolveState) <= 256 && sizeof(ColsState) <= 1024 && sizeof(GmresState) <= kGmresStateRoom && sizeof(MixState) <= 256, "the state's room behind the partial arrays");
+    static_assert(sizeof(SolveState) <= 256 && sizeof(ColsState) <= 1024 && sizeof(GmresState) <= kGmresStateRoom && sizeof(MixState) <= 256 && sizeof(LsqrState) <= 256,
+                  "the state's room behind the partial arrays");
     spmv_dev::SolveWs &w = d->solve_ws[s.id];
     if (w.n >= n) return SPMV_HIP_OK;
     if (w.p) {
@@ -202,27 +245,28 @@ static int solve_workspace(const Solver &s, spmv_dev *d, int n)
 // One solve's device operands: the workspace carved up (by the columns it HOLDS, so that a partial array never lies where a vector did), host
 // B / X / Dinv staged (X's copy-back registered with the stager; the initial guess copied in when it is wanted; the single solves share their
 // stage buffers, and all five Dinv's: the calls are synchronous, so they never hold them at the same time), the history block, the geometry
-// of the dots.  m > 0.
+// of the dots (spmv_hip_lsqr: both).  m > 0.
 static int solve_prepare(const Solver &s, spmv_dev *d, Stager &stg, const spmv_solve_call &c, size_t hist_entries, int nostop, SolveArgs &a)
 {
     int rc = solve_workspace(s, d, s.vectors_per_step ? c.restart : c.k);
     if (rc) return rc;
     spmv_dev::SolveWs &w = d->solve_ws[s.id];
     const int cols = solve_cols(s, w.n), vectors = solve_vectors(s, w.n), k = c.k;
-    const size_t vec = solve_vec_bytes(d, cols, d->vsize), vec4 = solve_vec_bytes(d, cols, 4), m = (size_t) d->m;
-    char *ws = (char *) w.p, *ws4 = ws + vectors * vec;
+    const size_t vec = solve_vec_bytes(d, cols, d->vsize), vec4 = solve_vec_bytes(d, cols, 4), vecn = solve_vecn_bytes(d), m = (size_t) d->m, xrows = solve_x_rows(s, d);
+    char *ws = (char *) w.p, *ws4 = ws + vectors * vec, *wsn = ws4 + s.vectors4 * vec4;
     a.m = d->m;
     a.k = k;
     a.restart = c.restart;
     a.base = ws;
     a.stride = vec;
-    const long long chunks = ((long long) d->m + kCgChunk - 1) / kCgChunk;
-    a.parts = (int) (chunks < kCgMaxParts ? chunks : kCgMaxParts);
-    a.span = (long long) kCgChunk * (((long long) d->m + (long long) kCgChunk * a.parts - 1) / ((long long) kCgChunk * a.parts));
+    solve_geometry(d->m, a.parts, a.span);
+    a.n = d->n;
+    solve_geometry(d->n, a.parts_n, a.span_n);
     const int slots = (int) (sizeof(a.vec) / sizeof(a.vec[0]));
     for (int i = 0; i < vectors && i < slots; ++i) a.vec[i] = ws + i * vec;
     for (int i = 0; i < s.vectors4 && vectors + i < slots; ++i) a.vec[vectors + i] = ws4 + i * vec4;
-    a.part = (double *) (ws4 + s.vectors4 * vec4);
+    for (int i = 0; i < s.vectors_n && vectors + s.vectors4 + i < slots; ++i) a.vec[vectors + s.vectors4 + i] = wsn + i * vecn;
+    a.part = (double *) (wsn + s.vectors_n * vecn);
     void *state = a.part + s.part_arrays * (size_t) cols * kCgMaxParts;
     if (s.max_k > 1) a.cols = (ColsState *) state;
     else a.state = (SolveState *) state;
@@ -231,6 +275,8 @@ static int solve_prepare(const Solver &s, spmv_dev *d, Stager &stg, const spmv_s
     const double drop = c.update_drop > 0 ? c.update_drop : SPMV_HIP_CG_MIXED_UPDATE_DROP;
     a.drop2 = drop * drop;
     a.every = c.update_every;
+    a.ls_tol = c.ls_tol;
+    a.damp = c.damp;
     a.budget = c.opt.max_iterations;
     a.nostop = nostop;
     a.f64 = d->vsize == sizeof(double);
@@ -240,9 +286,9 @@ static int solve_prepare(const Solver &s, spmv_dev *d, Stager &stg, const spmv_s
     a.ldb = c.ldb;
     a.ldx = c.ldx;
     long long ld = 1;
-    if ((rc = stg.in(d->stage[s.stage_b], a.b, a.ldb, m, k)) || (rc = stg.in(d->stage[STAGE_CG_DINV], a.dinv, ld, m, 1, s.dinv_size)) || (rc = stg.out(d->stage[s.stage_x], a.x, a.ldx, m, k)))
+    if ((rc = stg.in(d->stage[s.stage_b], a.b, a.ldb, m, k)) || (rc = stg.in(d->stage[STAGE_CG_DINV], a.dinv, ld, m, 1, s.dinv_size)) || (rc = stg.out(d->stage[s.stage_x], a.x, a.ldx, xrows, k)))
         return rc;
-    if (a.x != c.x && c.opt.use_x0) HIP_TRY(stg.copy(a.x, (size_t) k, c.x, (size_t) c.ldx, m, (size_t) k, hipMemcpyHostToDevice, d->vsize));
+    if (a.x != c.x && c.opt.use_x0) HIP_TRY(stg.copy(a.x, (size_t) k, c.x, (size_t) c.ldx, xrows, (size_t) k, hipMemcpyHostToDevice, d->vsize));
     // 16-byte accesses: B and X compact and aligned; the single solves' kernels read Dinv that way too, the k-column ones by element
     a.wide = a.ldb == k && a.ldx == k && wide_ok(a.b, 1, 16) && wide_ok(a.x, 1, 16) && (s.max_k > 1 || !a.dinv || wide_ok(a.dinv, 1, 16));
     a.hist = nullptr;
@@ -270,8 +316,11 @@ static int solve_admit(const Solver &s, const char *pre, const spmv_dev *d, cons
     if (c.k < 1 || c.k > s.max_k || c.ldb < c.k || c.ldx < c.k) return fail(SPMV_HIP_E_ARG, "%s%s: need 1 <= k <= %d, ldb >= k, ldx >= k", pre, s.name, s.max_k);
     if (s.vectors_per_step && (c.restart < 1 || c.restart > kGmresMaxRestart)) return fail(SPMV_HIP_E_ARG, "%s%s: need 1 <= restart <= %d", pre, s.name, kGmresMaxRestart);
     if (c.update_every < 0) return fail(SPMV_HIP_E_ARG, "%s%s: need update_every >= 0", pre, s.name);
-    if (d->m != d->n) return fail(SPMV_HIP_E_ARG, "%s%s: the matrix is %d x %d, not square", pre, s.name, d->m, d->n);
-    if (d->m > 0 && (!c.b || !c.x)) return fail(SPMV_HIP_E_ARG, "%s%s: B or X is NULL", pre, s.name);
+    if (!s.vectors_n && d->m != d->n) return fail(SPMV_HIP_E_ARG, "%s%s: the matrix is %d x %d, not square", pre, s.name, d->m, d->n);
+    if ((d->m > 0 && !c.b) || (solve_x_rows(s, d) > 0 && !c.x)) return fail(SPMV_HIP_E_ARG, "%s%s: B or X is NULL", pre, s.name);
+    if (s.vectors_n && !(c.ls_tol >= 0 && c.damp >= 0)) return fail(SPMV_HIP_E_ARG, "%s%s: ls_tol and damp must be >= 0 (and not NaN)", pre, s.name);
+    if (s.vectors_n && c.opt.Dinv) return fail(SPMV_HIP_E_ARG, "%s%s: there is no Dinv", pre, s.name);
+    if (s.vectors_n && (!d->tr || !d->tr->built || d->tr_gen != d->val_gen)) return fail(SPMV_HIP_E_NOSTATE, "%s%s: the transpose is not attached, not built or not refreshed", pre, s.name);
     if (s.max_k > 1 && d->nnz > 0 && !d->colidx) return fail(SPMV_HIP_E_NOSTATE, "%s%s: the resident column indices were released (spmv_shim_restore_columns first)", pre, s.name);
     return SPMV_HIP_OK;
 }
@@ -291,9 +340,18 @@ static int solve_run(const Solver &s, spmv_dev *d, const spmv_solve_call &c)
         res[j].rr = res[j].bb = 0;
     }
     if (c.updates) *c.updates = 0;
-    if (d->m == 0) return SPMV_HIP_OK;
+    if (c.ar) *c.ar = 0;
+    if (c.anorm) *c.anorm = 0;
+    if (d->m == 0 && solve_x_rows(s, d) == 0) return SPMV_HIP_OK;
     DeviceGuard guard(d->device);
     if (!guard.ok) return fail(SPMV_HIP_E_RUNTIME, "hipSetDevice(%d) failed", d->device);
+    if (d->m == 0) { // spmv_hip_lsqr without rows: B is empty, bb = 0, x = 0
+        if (!is_device_ptr(c.x)) { memset(c.x, 0, d->vsize * (size_t) d->n); return SPMV_HIP_OK; }
+        HIP_TRY(hipMemsetAsync(c.x, 0, d->vsize * (size_t) d->n, d->stream));
+        HIP_TRY(hipStreamSynchronize(d->stream));
+        return SPMV_HIP_OK;
+    }
+    if (s.vectors_n) d->tr->stream = d->stream; // the transpose launches on the parent's stream, as the halves of a split do
     if (s.max_k > 1 && (rc = spmm_plan(d))) return rc;
     Stager stg{d};
     SolveRun r{d, c.low, {}};
@@ -302,7 +360,7 @@ static int solve_run(const Solver &s, spmv_dev *d, const spmv_solve_call &c)
     if (rc || (rc = solve_start(s, r, opt.use_x0 != 0))) return rc;
     const int every = opt.check_every > 0 ? opt.check_every : s.check_every;
     alignas(8) unsigned char hs[sizeof(GmresState) > sizeof(ColsState) ? sizeof(GmresState) : sizeof(ColsState)];
-    static_assert(sizeof(hs) >= sizeof(SolveState) && sizeof(hs) >= sizeof(MixState), "the largest state");
+    static_assert(sizeof(hs) >= sizeof(SolveState) && sizeof(hs) >= sizeof(MixState) && sizeof(hs) >= sizeof(LsqrState), "the largest state");
     SolveLook l = {};
     // every look but the last is followed by an applied iteration or by what a resume enqueued
     int it = 0;
@@ -329,10 +387,12 @@ static int solve_run(const Solver &s, spmv_dev *d, const spmv_solve_call &c)
         if (l.iterations[j] > longest) longest = l.iterations[j];
         if (!(l.done[j] && l.status[j] == SPMV_HIP_CG_CONVERGED && l.bb[j] == 0)) continue;
         // B = 0: x = 0
-        if (k == 1 && a.ldx == 1) HIP_TRY(hipMemsetAsync(a.x, 0, d->vsize * (size_t) d->m, d->stream));
+        if (k == 1 && a.ldx == 1) HIP_TRY(hipMemsetAsync(a.x, 0, d->vsize * solve_x_rows(s, d), d->stream));
         else HIP_TRY(hipMemset2DAsync((char *) a.x + d->vsize * (size_t) j, d->vsize * (size_t) a.ldx, 0, d->vsize, (size_t) d->m, d->stream));
     }
     if (c.updates) *c.updates = l.updates;
+    if (c.ar) *c.ar = l.ar;
+    if (c.anorm) *c.anorm = l.anorm;
     std::vector<double> hist;
     if (opt.history && k == 1) HIP_TRY(hipMemcpyAsync(opt.history, a.hist, sizeof(double) * ((size_t) longest + 1), hipMemcpyDeviceToHost, d->stream));
     if (opt.history && k > 1) {
@@ -358,6 +418,7 @@ static double solve_time(const Solver &s, spmv_dev *d, const spmv_solve_call &c,
     DeviceGuard guard(d->device);
     if (!guard.ok) { fail(SPMV_HIP_E_RUNTIME, "hipSetDevice(%d) failed", d->device); return -1.0; }
     if (s.max_k > 1 && spmm_plan(d)) return -1.0;
+    if (s.vectors_n) d->tr->stream = d->stream;
     Stager stg{d};
     SolveRun r{d, c.low, {}};
     if (solve_prepare(s, d, stg, c, 0, 1, r.a)) return -1.0;
@@ -453,21 +514,23 @@ static bool mix_resume(const Solver &s, const SolveRun &r, const void *state, in
     return !(rc = mix_update(s, r, it, hs.updates + 1));
 }
 
-// ------------------------------------------------------------------------------------ the five rows
+// ------------------------------------------------------------------------------------ the six rows
 // indexed by the solver ids of spmv_shim.h.  check_every: DESIGN 3.26 for CG.  BiCGStab's is from the sweep of tools/bicgstab_bench.py (DESIGN
 // 3.27): a look costs 23-31 us; at 8 an iteration is within 3 % of the best figure of the sweep (32) on the 1e6-row case and within 0.3 % on the
 // 1e7-row band, and what a larger value saves per iteration it loses again behind convergence, where on average check_every - 1 multiplies are wasted.
-// The k-column solve and the mixed one keep CG's 8
+// The k-column solve and the mixed one keep CG's 8; spmv_hip_lsqr's is from the sweep of tools/lsqr_bench.py
 static const Solver kSolvers[SPMV_SHIM_SOLVE_COUNT] = {
-    {SPMV_SHIM_SOLVE_CG, "cg", kCgVectors, 0, kCgPartArrays, 0, 1, 8, sizeof(SolveState), 256, 0, STAGE_CG_B, STAGE_CG_X, cg_start, cg_iteration, single_look, nullptr, nullptr, nullptr},
-    {SPMV_SHIM_SOLVE_BICGSTAB, "bicgstab", kBicgVectors, 0, kBicgPartArrays, 0, 1, 8, sizeof(SolveState), 256, 0, STAGE_CG_B, STAGE_CG_X, bicg_start, bicg_iteration, single_look, nullptr,
+    {SPMV_SHIM_SOLVE_CG, "cg", kCgVectors, 0, 0, kCgPartArrays, 0, 1, 8, sizeof(SolveState), 256, 0, STAGE_CG_B, STAGE_CG_X, cg_start, cg_iteration, single_look, nullptr, nullptr, nullptr},
+    {SPMV_SHIM_SOLVE_BICGSTAB, "bicgstab", kBicgVectors, 0, 0, kBicgPartArrays, 0, 1, 8, sizeof(SolveState), 256, 0, STAGE_CG_B, STAGE_CG_X, bicg_start, bicg_iteration, single_look, nullptr,
      nullptr, nullptr},
-    {SPMV_SHIM_SOLVE_CG_COLUMNS, "cg_columns", kCcgVectors, 0, kCcgPartArrays, 0, kCcgMaxK, 8, sizeof(ColsState), 1024, 0, STAGE_CGC_B, STAGE_CGC_X, ccg_start, ccg_iteration, cols_look,
+    {SPMV_SHIM_SOLVE_CG_COLUMNS, "cg_columns", kCcgVectors, 0, 0, kCcgPartArrays, 0, kCcgMaxK, 8, sizeof(ColsState), 1024, 0, STAGE_CGC_B, STAGE_CGC_X, ccg_start, ccg_iteration, cols_look,
      nullptr, nullptr, nullptr},
-    {SPMV_SHIM_SOLVE_GMRES, "gmres", kGmresVectors, 0, kGmresPartArrays, 1, 1, 8, sizeof(GmresState), kGmresStateRoom, 0, STAGE_CG_B, STAGE_CG_X, gmres_start, gmres_iteration, single_look,
+    {SPMV_SHIM_SOLVE_GMRES, "gmres", kGmresVectors, 0, 0, kGmresPartArrays, 1, 1, 8, sizeof(GmresState), kGmresStateRoom, 0, STAGE_CG_B, STAGE_CG_X, gmres_start, gmres_iteration, single_look,
      gmres_finish, nullptr, nullptr},
-    {SPMV_SHIM_SOLVE_CG_MIXED, "cg_mixed", kMixVectors64, kMixVectors32, kMixPartArrays, 0, 1, 8, sizeof(MixState), 256, sizeof(float), STAGE_CG_B, STAGE_CG_X, mix_start, mix_iteration,
+    {SPMV_SHIM_SOLVE_CG_MIXED, "cg_mixed", kMixVectors64, kMixVectors32, 0, kMixPartArrays, 0, 1, 8, sizeof(MixState), 256, sizeof(float), STAGE_CG_B, STAGE_CG_X, mix_start, mix_iteration,
      mix_look, nullptr, mix_resume, mix_admit},
+    {SPMV_SHIM_SOLVE_LSQR, "lsqr", kLsqrVectorsM, 0, kLsqrVectorsN, kLsqrPartArrays, 0, 1, 8, sizeof(LsqrState), 256, 0, STAGE_CG_B, STAGE_CG_X, lsqr_start, lsqr_iteration, lsqr_look, nullptr,
+     nullptr, nullptr},
 };
 
 static const Solver *solve_row(const spmv_solve_call *c)

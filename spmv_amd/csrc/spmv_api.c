@@ -1414,9 +1414,9 @@ double spmv_hip_time_attention_gqa_backward_16_launches(spmv_Handle_t h, int hea
     return attention_backward_time(h, "time_attention_gqa_backward_16_launches", ATTENTION_16, &c, warmup, iters, ms_out);
 }
 
-/* ---------------------------------------------------------------- the five solves on the device: one gate, one call struct
- * conjugate gradients, BiCGStab (a matrix that need not be symmetric), restarted GMRES, conjugate gradients for k right-hand sides and
- * mixed-precision conjugate gradients on a pair of handles.  An entry point fills a spmv_solve_call and goes through solve_call or solve_time. */
+/* ---------------------------------------------------------------- the six solves on the device: one gate, one call struct
+ * conjugate gradients, BiCGStab (a matrix that need not be symmetric), restarted GMRES, conjugate gradients for k right-hand sides,
+ * mixed-precision conjugate gradients on a pair of handles and LSQR (a matrix that need not be square).  An entry point fills a spmv_solve_call and goes through solve_call or solve_time. */
 typedef struct solve_csr { BASIC_INT_TYPE m; const BASIC_INT_TYPE *RowPtr, *ColIdx; const void *Val; } solve_csr; /* the CSR arguments of a solve that takes them */
 
 static spmv_solve_call solve_fill(int solver, int k, int restart, const void *B, long long ldb, void *X, long long ldx, const spmv_hip_cg_options *opt, spmv_hip_cg_result *res)
@@ -1430,15 +1430,16 @@ static spmv_solve_call solve_fill(int solver, int k, int restart, const void *B,
  * handles', addressed in the caller's order, and c->low filled; the prologue for a solve with the CSR arguments; the plain gate for a timer --
  * and what needs the state: the square matrix, and the columns of spmv_hip_cg_columns, which with one compact vector is spmv_hip_cg, its
  * workspace and bits.  given: opt and res are there.  m: the solve's; 1 for a timer (B and X are always needed); 0 for spmv_hip_cg_mixed, whose
- * m is the resident matrix's: the shim checks its B and X */
+ * m is the resident matrix's: the shim checks its B and X.  spmv_hip_lsqr: X has n elements, known behind the gate; the entries are addressed in the
+ * caller's order (no reordered handle); the transpose is built at the first call and its values are A's as they are now (transpose_ready) */
 static int solve_gate(const char *where, spmv_Handle_t h, spmv_Handle_t low, int given, spmv_solve_call *c, const solve_csr *csr, int m, spmv_hip_state **st)
 {
-    const int mixed = c->solver == SPMV_SHIM_SOLVE_CG_MIXED, kmax = c->solver == SPMV_SHIM_SOLVE_CG_COLUMNS ? SPMV_HIP_CG_COLUMNS_MAX : 1;
+    const int mixed = c->solver == SPMV_SHIM_SOLVE_CG_MIXED, lsqr = c->solver == SPMV_SHIM_SOLVE_LSQR, kmax = c->solver == SPMV_SHIM_SOLVE_CG_COLUMNS ? SPMV_HIP_CG_COLUMNS_MAX : 1;
     spmv_hip_state *lo = NULL;
     int rc;
     if (!h || (mixed && !low)) return refuse(SPMV_HIP_E_ARG, where, "handle is NULL");
     if (!given) return refuse(SPMV_HIP_E_ARG, where, "opt or res is NULL");
-    if (m > 0 && (!c->b || !c->x)) return refuse(SPMV_HIP_E_ARG, where, "B or X is NULL");
+    if (m > 0 && (!c->b || (!lsqr && !c->x))) return refuse(SPMV_HIP_E_ARG, where, "B or X is NULL");
     if (c->opt.max_iterations < 0 || c->opt.check_every < 0) return refuse(SPMV_HIP_E_ARG, where, "need max_iterations >= 0 and check_every >= 0");
     if (!(c->opt.rtol >= 0) || !(c->opt.atol >= 0)) return refuse(SPMV_HIP_E_ARG, where, "rtol and atol must be >= 0 (and not NaN)");
     if (c->solver == SPMV_SHIM_SOLVE_GMRES && (c->restart < 1 || c->restart > SPMV_HIP_GMRES_RESTART_MAX))
@@ -1446,6 +1447,13 @@ static int solve_gate(const char *where, spmv_Handle_t h, spmv_Handle_t low, int
     if (c->k < 1 || c->k > kmax || c->ldb < c->k || c->ldx < c->k) return refuse(SPMV_HIP_E_ARG, where, "need 1 <= k <= SPMV_HIP_CG_COLUMNS_MAX, ldb >= k and ldx >= k");
     if (!(c->update_drop >= 0) || !(c->update_drop < 1)) return refuse(SPMV_HIP_E_ARG, where, "need 0 <= update_drop < 1 (0: the default)");
     if (c->update_every < 0) return refuse(SPMV_HIP_E_ARG, where, "need update_every >= 0");
+    if (lsqr) {
+        if (!(c->ls_tol >= 0) || !(c->damp >= 0)) return refuse(SPMV_HIP_E_ARG, where, "ls_tol and damp must be >= 0 (and not NaN)");
+        if ((rc = resident_state(h, where, RESIDENT_NOT_REORDERED, st))) return rc;
+        if ((*st)->n > 0 && !c->x) return refuse(SPMV_HIP_E_ARG, where, "B or X is NULL");
+        if (csr && (rc = resident_prologue(h, where, RESIDENT_NOT_REORDERED, csr->m, csr->RowPtr, csr->ColIdx, csr->Val, st))) return rc;
+        return transpose_ready(h, *st, where);
+    }
     if (mixed) {
         if ((rc = resident_state(h, where, RESIDENT_NOT_REORDERED, st)) || (rc = resident_state(low, where, RESIDENT_NOT_REORDERED, &lo))) return rc;
     } else if ((rc = csr ? resident_prologue(h, where, 0, csr->m, csr->RowPtr, csr->ColIdx, csr->Val, st) : resident_state(h, where, 0, st))) return rc;
@@ -1560,4 +1568,39 @@ double spmv_hip_time_cg_mixed_iterations(spmv_Handle_t high, spmv_Handle_t low, 
 {
     spmv_solve_call c = mixed_fill(B, X, opt, NULL, NULL);
     return solve_time("time_cg_mixed_iterations", high, low, opt != NULL, &c, warmup, iters, ms_out);
+}
+
+/* LSQR's options and result are structs of their own: the common fields copied one by one; there is no Dinv */
+static spmv_solve_call lsqr_fill(const void *B, void *X, const spmv_hip_lsqr_options *opt, spmv_hip_cg_result *res, double *ar, double *anorm)
+{
+    spmv_solve_call c = solve_fill(SPMV_SHIM_SOLVE_LSQR, 1, 0, B, 1, X, 1, NULL, res);
+    c.ar = ar;
+    c.anorm = anorm;
+    if (!opt) return c;
+    c.opt.rtol = opt->rtol;
+    c.opt.atol = opt->atol;
+    c.opt.max_iterations = opt->max_iterations;
+    c.opt.check_every = opt->check_every;
+    c.opt.use_x0 = opt->use_x0;
+    c.opt.history = opt->history;
+    c.ls_tol = opt->ls_tol;
+    c.damp = opt->damp;
+    return c;
+}
+
+int spmv_hip_lsqr(spmv_Handle_t handle, BASIC_INT_TYPE m, const BASIC_INT_TYPE *RowPtr, const BASIC_INT_TYPE *ColIdx, const void *Matrix_Val, const void *B, void *X,
+                  const spmv_hip_lsqr_options *opt, spmv_hip_lsqr_result *res)
+{
+    spmv_hip_cg_result r = {0};
+    double ar = 0, anorm = 0;
+    spmv_solve_call c = lsqr_fill(B, X, opt, &r, &ar, &anorm);
+    const int rc = solve_call("lsqr", handle, NULL, opt && res, &c, &(solve_csr){m, RowPtr, ColIdx, Matrix_Val});
+    if (rc == SPMV_HIP_OK) *res = (spmv_hip_lsqr_result){.status = r.status, .iterations = r.iterations, .rr = r.rr, .bb = r.bb, .ar = ar, .anorm = anorm};
+    return rc;
+}
+
+double spmv_hip_time_lsqr_iterations(spmv_Handle_t h, const void *B, void *X, const spmv_hip_lsqr_options *opt, int warmup, int iters, float *ms_out)
+{
+    spmv_solve_call c = lsqr_fill(B, X, opt, NULL, NULL, NULL);
+    return solve_time("time_lsqr_iterations", h, NULL, opt != NULL, &c, warmup, iters, ms_out);
 }

@@ -205,10 +205,11 @@ int spmv_shim_attention_backward(spmv_dev *d, const spmv_attention_backward_call
  * Q, K, V, G and, with stats, O and L must be given. */
 double spmv_shim_time_attention_backward(spmv_dev *d, const spmv_attention_backward_call *c, int warmup, int iters, float *ms_out);
 
-/* ---- the solves on the resident matrix that stay on the device (shim/solve.hpp): five solvers, one call struct, one loop, one timer ----
+/* ---- the solves on the resident matrix that stay on the device (shim/solve.hpp): six solvers, one call struct, one loop, one timer ----
  * spmv_hip_cg, spmv_hip_bicgstab (the matrix need not be symmetric), spmv_hip_cg_columns (k right-hand sides in one pass over A per iteration),
- * spmv_hip_gmres (restarted GMRES(restart)) and spmv_hip_cg_mixed (fp32 iterations, fp64 solution and true residual).  What every entry point
- * passes down; one that lacks a field fills it as k = ldb = ldx = 1, restart = 0, low = NULL, update_drop = 0, update_every = 0, updates = NULL:
+ * spmv_hip_gmres (restarted GMRES(restart)), spmv_hip_cg_mixed (fp32 iterations, fp64 solution and true residual) and spmv_hip_lsqr (least
+ * squares for any m x n matrix).  What every entry point passes down; one that lacks a field fills it as k = ldb = ldx = 1, restart = 0,
+ * low = NULL, update_drop = 0, update_every = 0, updates = NULL, ls_tol = damp = 0, ar = anorm = NULL:
  *   - b, x: m x k elements of the handle's value type, row-major, leading dimensions ldb, ldx >= k; opt.Dinv: ONE vector of m elements (floats
  *     for spmv_hip_cg_mixed, whose handle is fp64); host or device pointers each.  1 <= k <= SPMV_HIP_CG_COLUMNS_MAX for spmv_hip_cg_columns,
  *     which multiplies with spmv_shim_spmm's executor and needs the resident ColIdx (spmv_shim_restore_columns); k = 1 for the others, whose
@@ -216,11 +217,15 @@ double spmv_shim_time_attention_backward(spmv_dev *d, const spmv_attention_backw
  *   - restart: 1 <= restart <= SPMV_HIP_GMRES_RESTART_MAX for spmv_hip_gmres.
  *   - low: spmv_hip_cg_mixed's fp32 handle, only multiplied with; the handle of the call is the fp64 one and owns the workspace.  The pair has
  *     the same m = n and nnz, device and stream: SPMV_HIP_E_ARG otherwise.
+ *   - spmv_hip_lsqr: the matrix need not be square; b has m elements and x n; its second multiply is the ATTACHED TRANSPOSE's own launch
+ *     (spmv_shim_attach_transpose, the values refreshed: spmv_shim_transpose_refresh), SPMV_HIP_E_NOSTATE without one.  ls_tol and damp are
+ *     its options, ar and anorm (NULL: not wanted) receive its two further results; opt.Dinv must be NULL.
  *   - res: k entries; opt.history: (max_iterations + 1) * k doubles; updates: spmv_hip_cg_mixed's committed updates.
  * Each solver builds a workspace of its own on the handle at its first call; spmv_hip_cg_columns' is allocated anew when a later call has more
  * columns, spmv_hip_gmres's (restart + 3 vectors) when one has a larger restart.  SPMV_HIP_OK whenever the solve ran (res->status says how it
  * ended); synchronous */
-enum { SPMV_SHIM_SOLVE_CG, SPMV_SHIM_SOLVE_BICGSTAB, SPMV_SHIM_SOLVE_CG_COLUMNS, SPMV_SHIM_SOLVE_GMRES, SPMV_SHIM_SOLVE_CG_MIXED, SPMV_SHIM_SOLVE_COUNT };
+enum { SPMV_SHIM_SOLVE_CG, SPMV_SHIM_SOLVE_BICGSTAB, SPMV_SHIM_SOLVE_CG_COLUMNS, SPMV_SHIM_SOLVE_GMRES, SPMV_SHIM_SOLVE_CG_MIXED, SPMV_SHIM_SOLVE_LSQR,
+       SPMV_SHIM_SOLVE_COUNT };
 typedef struct spmv_solve_call {
     int solver;      /* SPMV_SHIM_SOLVE_* */
     spmv_dev *low;
@@ -232,11 +237,13 @@ typedef struct spmv_solve_call {
     int update_every;
     spmv_hip_cg_result *res;
     int *updates;            /* NULL: not wanted */
+    double ls_tol, damp;     /* spmv_hip_lsqr */
+    double *ar, *anorm;      /* spmv_hip_lsqr's results; NULL: not wanted */
 } spmv_solve_call;
 int spmv_shim_solve(spmv_dev *d, const spmv_solve_call *c);
 /* `iters` runs of opt.max_iterations iterations each, the stop tests off, timed with events on the handle's stream (device B / X / Dinv); mean ms per
  * run, < 0 on failure.  spmv_hip_gmres: the iterations include the cycle ends and restarts that fall among them; spmv_hip_cg_mixed: an update behind
- * every update_every-th iteration (none at 0).  res and updates are not looked at */
+ * every update_every-th iteration (none at 0).  res, updates, ar and anorm are not looked at */
 double spmv_shim_time_solve(spmv_dev *d, const spmv_solve_call *c, int warmup, int iters, float *ms_out);
 /* out[i] = the fp64 square root of in[i] as spmv_hip_gmres's kernels take it: n doubles each, device pointers; synchronous */
 int spmv_shim_gmres_sqrt(const double *in, double *out, long long n);

@@ -46,6 +46,7 @@
 #include "kernels/gmres.hpp"
 #include "kernels/cg_columns.hpp"
 #include "kernels/cg_mixed.hpp"
+#include "kernels/lsqr.hpp"
 
 using namespace spmv;
 

@@ -1,11 +1,12 @@
-// spmv_solve.hip -- translation unit of the vector kernels of the five device-resident solvers (kernels/cg.hpp, kernels/bicgstab.hpp,
-// kernels/cg_columns.hpp, kernels/gmres.hpp, kernels/cg_mixed.hpp, what they share in kernels/solve_common.hpp).  Launches only: the workspace, staging, the multiplies, the host's
+// spmv_solve.hip -- translation unit of the vector kernels of the six device-resident solvers (kernels/cg.hpp, kernels/bicgstab.hpp,
+// kernels/cg_columns.hpp, kernels/gmres.hpp, kernels/cg_mixed.hpp, kernels/lsqr.hpp, what they share in kernels/solve_common.hpp).  Launches only: the workspace, staging, the multiplies, the host's
 // looks at the state and the error channel stay in spmv_shim.hip (shim/solve.hpp).  Per solve it calls cg_start_launch or bicg_start_launch
 // once; per iteration cg_iteration_launch behind q = A p, or bicg_first_launch behind v = A ph and bicg_second_launch behind t = A sh;
 // spmv_hip_cg_columns: ccg_start_launch, and ccg_iteration_launch behind q = A p for all k columns.  spmv_hip_gmres (kernels/gmres.hpp):
 // gmres_start_launch, gmres_step_launch behind w = A z, and at a cycle's end gmres_apply_launch, then gmres_restart_launch behind w = A x.
 // spmv_hip_cg_mixed (kernels/cg_mixed.hpp): mix_start_launch, mix_iteration_launch behind q = A_low p, and at a segment's end mix_try_launch,
-// then mix_update_launch behind q64 = A_high xn.
+// then mix_update_launch behind q64 = A_high xn.  spmv_hip_lsqr (kernels/lsqr.hpp): lsqr_init_launch, lsqr_first_launch behind v = A^T u, and per
+// iteration lsqr_u_launch behind q = A v and lsqr_v_launch behind qt = A^T u.
 #include <hip/hip_runtime.h>
 
 #include "kernels/common.hpp"
@@ -14,6 +15,7 @@
 #include "kernels/cg_columns.hpp"
 #include "kernels/gmres.hpp"
 #include "kernels/cg_mixed.hpp"
+#include "kernels/lsqr.hpp"
 
 namespace spmv {
 
@@ -262,5 +264,59 @@ hipError_t mix_start_launch(const SolveArgs &a, bool use_x0, hipStream_t stream)
 hipError_t mix_iteration_launch(const SolveArgs &a, int k, hipStream_t stream) { MIX_LAUNCH(mix_iteration_t, k >= 1, a, k, stream); }
 hipError_t mix_try_launch(const SolveArgs &a, hipStream_t stream) { MIX_LAUNCH(mix_try_t, true, a, stream); }
 hipError_t mix_update_launch(const SolveArgs &a, int k, int update, hipStream_t stream) { MIX_LAUNCH(mix_update_t, k >= 1 && update >= 1, a, k, update, stream); }
+
+// ---- spmv_hip_lsqr: vectors of two lengths, u and q over a.m (a.parts, a.span), v, w, qt and x over a.n (a.parts_n, a.span_n); no Dinv
+static LsqrState *lsqr_state(const SolveArgs &a) { return reinterpret_cast<LsqrState *>(a.state); }
+
+template <typename T, bool WIDE, bool DINV>
+static void lsqr_init_t(const SolveArgs &a, bool use_x0, hipStream_t stream)
+{
+    const unsigned grid = (unsigned) a.parts;
+    T *u = (T *) a.vec[kLsqrVecU];
+    if (use_x0) lsqr_init_kernel<T, WIDE, true><<<grid, kBlock, 0, stream>>>(a.m, a.span, (const T *) a.b, (const T *) a.vec[kLsqrVecQ], u, a.part);
+    else lsqr_init_kernel<T, WIDE, false><<<grid, kBlock, 0, stream>>>(a.m, a.span, (const T *) a.b, (const T *) a.vec[kLsqrVecQ], u, a.part);
+    lsqr_unit_u_kernel<T, true><<<grid, kBlock, 0, stream>>>(a.m, a.span, u, a.part, lsqr_state(a), a.hist, a.rtol2, a.atol2, a.nostop);
+}
+
+template <typename T, bool WIDE, bool DINV>
+static void lsqr_first_t(const SolveArgs &a, bool use_x0, hipStream_t stream)
+{
+    const unsigned grid = (unsigned) a.parts_n;
+    T *v = (T *) a.vec[kLsqrVecV];
+    if (use_x0) lsqr_vv_kernel<T, WIDE, true><<<grid, kBlock, 0, stream>>>(a.n, a.span_n, v, (T *) a.x, a.part, lsqr_state(a));
+    else lsqr_vv_kernel<T, WIDE, false><<<grid, kBlock, 0, stream>>>(a.n, a.span_n, v, (T *) a.x, a.part, lsqr_state(a));
+    lsqr_step_kernel<T, WIDE, true><<<grid, kBlock, 0, stream>>>(a.n, a.span_n, 0, v, (T *) a.vec[kLsqrVecW], (T *) a.x, a.part, lsqr_state(a), a.hist, a.rtol2, a.atol2, a.ls_tol,
+                                                                 a.damp, a.nostop);
+}
+
+template <typename T, bool WIDE, bool DINV>
+static void lsqr_u_t(const SolveArgs &a, int k, hipStream_t stream)
+{
+    const unsigned grid = (unsigned) a.parts;
+    T *u = (T *) a.vec[kLsqrVecU];
+    lsqr_u_kernel<T><<<grid, kBlock, 0, stream>>>(a.m, a.span, k, (const T *) a.vec[kLsqrVecQ], u, a.part, lsqr_state(a));
+    lsqr_unit_u_kernel<T, false><<<grid, kBlock, 0, stream>>>(a.m, a.span, u, a.part, lsqr_state(a), a.hist, a.rtol2, a.atol2, a.nostop);
+}
+
+template <typename T, bool WIDE, bool DINV>
+static void lsqr_v_t(const SolveArgs &a, int k, hipStream_t stream)
+{
+    const unsigned grid = (unsigned) a.parts_n;
+    T *v = (T *) a.vec[kLsqrVecV];
+    lsqr_v_kernel<T><<<grid, kBlock, 0, stream>>>(a.n, a.span_n, (const T *) a.vec[kLsqrVecQt], v, a.part, lsqr_state(a), a.nostop);
+    lsqr_step_kernel<T, WIDE, false><<<grid, kBlock, 0, stream>>>(a.n, a.span_n, k, v, (T *) a.vec[kLsqrVecW], (T *) a.x, a.part, lsqr_state(a), a.hist, a.rtol2, a.atol2, a.ls_tol,
+                                                                  a.damp, a.nostop);
+}
+
+static bool lsqr_ok(const SolveArgs &a)
+{
+    for (int i = 0; i < kLsqrVectors; ++i) if (!a.vec[i]) return false;
+    return a.n >= 0 && a.parts_n >= 1 && a.parts_n <= kCgMaxParts && a.span_n * a.parts_n >= a.n && a.b && (a.x || a.n == 0) && a.part && a.state && !a.dinv;
+}
+
+hipError_t lsqr_init_launch(const SolveArgs &a, bool use_x0, hipStream_t stream) { SOLVE_LAUNCH(lsqr_init_t, lsqr_ok(a), a, use_x0, stream); }
+hipError_t lsqr_first_launch(const SolveArgs &a, bool use_x0, hipStream_t stream) { SOLVE_LAUNCH(lsqr_first_t, lsqr_ok(a), a, use_x0, stream); }
+hipError_t lsqr_u_launch(const SolveArgs &a, int k, hipStream_t stream) { SOLVE_LAUNCH(lsqr_u_t, lsqr_ok(a) && k >= 1, a, k, stream); }
+hipError_t lsqr_v_launch(const SolveArgs &a, int k, hipStream_t stream) { SOLVE_LAUNCH(lsqr_v_t, lsqr_ok(a) && k >= 1, a, k, stream); }
 
 } // namespace spmv
