@@ -7,23 +7,20 @@ run with the x0, the Dinv, the tolerances and the budget of the call it is compa
 column are compared bit for bit and no tolerance appears anywhere.  The one freedom: a NaN equals a NaN whatever its sign and payload.  The
 columns come from tests/solve_end_cases.py (columns_system: the CG catalogue as the columns of one call), whose every group
 tests/test_cg_column_ends_host.py proves on the CPU first; here every column must also reach the (status, iterations, end) it declares under the
-handle's own multiply -- bits that match a model which ends elsewhere would mean the INPUT is wrong, not the kernel."""
+handle's own multiply -- bits that match a model which ends elsewhere would mean the INPUT is wrong, not the kernel.  The helpers that the
+solvers share are in tests/solve_harness.py."""
 import numpy as np
 import pytest
 
 import cg_cases as cgc
 import cg_columns_cases as ccc
 import solve_end_cases as sec
-from spmv_amd import api, build
-from test_gpu_cg_columns import run_bits
+import solve_harness as sh
+from solve_harness import CANARY, DEV, EVERY, NAMES, ended, handle, run_bits, same
 
 pytestmark = pytest.mark.gpu
 
-M = api.SPMV_METHODS
-DEV = "cuda:0"
-CANARY = -7.25
-NAMES = {np.float32: "f32", np.float64: "f64"}
-EVERY = (1, 2, 3, 0, 64)           # check_every: a column's end falls first, in the middle and last in an enqueued batch
+ROW = sh.ROWS["cg_columns"]
 NOT_REACHED = "the case does not reach its end on this multiply"
 # (shift of B, shift of X in elements, padding of B, padding of X in columns): all but the first run the element-access kernels
 LAYOUTS = ((0, 0, 0, 0), (1, 0, 0, 0), (0, 1, 0, 0), (1, 1, 0, 0), (0, 0, 3, 1), (1, 1, 3, 1))
@@ -31,28 +28,9 @@ LAYOUTS = ((0, 0, 0, 0), (1, 0, 0, 0), (0, 1, 0, 0), (1, 1, 0, 0), (0, 0, 3, 1),
 
 @pytest.fixture(scope="module", autouse=True)
 def _lib():
-    build.build()
-    lib = api.load()
-    assert lib.spmv_hip_device_count() > 0, "GPU tests need a device"
+    lib = sh.library()
     assert hasattr(lib, "spmv_hip_cg_columns")
     return lib
-
-
-def handle(csr, method=M.Method_Parallel):
-    return api.Handle(csr.m, csr.n, csr.rowptr, csr.colidx, csr.val, method)
-
-
-def same(a, b):
-    """the same type, shape and bits; a NaN equals a NaN"""
-    a, b = np.asarray(a), np.asarray(b)
-    if a.dtype != b.dtype or a.shape != b.shape:
-        return False
-    both = np.isnan(a) & np.isnan(b)
-    return np.where(both, 0, a).tobytes() == np.where(both, 0, b).tobytes()
-
-
-def ended(r):
-    return r["status"], r["iterations"], r["end"]
 
 
 def figures(res):
@@ -69,17 +47,15 @@ def same_call(a, b, cols=None):
 
 
 def solve(h, B, X0=None, **kw):
-    """through host pointers, with a canary in X when there is no guess -> (X, list of result dicts, history)"""
-    X = np.full(B.shape, CANARY, dtype=B.dtype) if X0 is None else np.ascontiguousarray(X0).copy()
-    kw.setdefault("rtol", 0.0)
-    return h.cg_columns(np.ascontiguousarray(B), X, x0=X0 is not None, history=True, **kw)
+    """through host pointers, with a canary in X when there is no guess and rtol = 0 unless set -> (X, list of result dicts, history)"""
+    return sh.solve_columns(h, B, X0, **dict(ROW.zero_tols, **kw))
 
 
 def models_of(mul, B, X0=None, dinv=None, **kw):
     return ccc.solve(mul, np.ascontiguousarray(B), None if X0 is None else np.ascontiguousarray(X0), dinv=dinv, **kw)
 
 
-def check(models, got, what=None):
+def check_call(models, got, what=None):
     """a call against model runs with the same arguments, column by column, however each ended"""
     X, res, hist = got
     assert len(res) == X.shape[1] == len(models) and hist.shape == (1 + max(mo["iterations"] for mo in models), len(models)), (what, hist.shape)
@@ -121,9 +97,9 @@ def test_every_end_in_mixed_company_at_every_place_in_a_batch(group, m, dtype):
                     declared(cases, models[budget], budget)
                 what = (run, budget, every)
                 got = solve(h, B, G, dinv=dinv, max_iterations=budget, check_every=every)
-                check(models[budget], got, what)
+                check_call(models[budget], got, what)
                 back = solve(h, B[:, rev], Gr, dinv=dinv, max_iterations=budget, check_every=every)
-                check(models[budget][::-1], back, what + ("reversed",))
+                check_call(models[budget][::-1], back, what + ("reversed",))
                 assert same_call(got, back, rev), what
             reached |= {mo["end"] for mo in models[sec.BUDGET]}
     assert reached == {c.end for c in cases} | {"budget"}
@@ -150,7 +126,7 @@ def test_bits_against_the_model_at_every_k(m, dtype):
                     if X0 is not None:
                         Xw[:, 0] = X0[:, 0]
                     got = h.cg_columns(Bw[:, :1], Xw[:, :1], x0=X0 is not None, rtol=0.0, max_iterations=budget, dinv=dinv, history=True)
-                    check(models_of(mul, b, X0, dinv, max_iterations=budget), got, (X0 is not None, dinv is not None, budget))
+                    check_call(models_of(mul, b, X0, dinv, max_iterations=budget), got, (X0 is not None, dinv is not None, budget))
                     assert (Xw[:, 1] == CANARY).all()
 
 
@@ -166,7 +142,7 @@ def test_frozen_columns_at_every_k(dtype):
             for cols in ([list(range(k))] if k <= n else []) + ([list(range(k - 1)) + [n]] if k >= 2 else []):
                 for every in (0, 1):
                     got = solve(h, B[:, cols], max_iterations=sec.BUDGET, check_every=every)
-                    check([models[j] for j in cols], got, (k, cols, every))
+                    check_call([models[j] for j in cols], got, (k, cols, every))
 
 
 # ----------------------------------------------------------------------------- c. frozen columns in the element-access kernels
@@ -211,11 +187,11 @@ def test_frozen_columns_in_the_element_access_kernels(group, dtype):
             models = models_of(mul, B, X0, Dinv, max_iterations=budget)
             declared(cases, models, budget)
             want = solve(h, B, X0, dinv=Dinv, max_iterations=budget)
-            check(models, want, (budget, "host"))
+            check_call(models, want, (budget, "host"))
             for layout in LAYOUTS:
                 for every in (0, 1):
                     got = device_call(h, B, X0, Dinv, layout, max_iterations=budget, check_every=every)
-                    check(models, got, (budget, layout, every))
+                    check_call(models, got, (budget, layout, every))
                     assert same_call(got, want), (budget, layout, every)
 
 
@@ -231,7 +207,7 @@ def test_one_zero_column_in_a_wider_x(dtype):
         wide = np.full((csr.m, 2), CANARY, dtype=dtype)
         wide[:, 0] = X0[:, 0]
         X, res, hist = h.cg_columns(B[:, :1], wide[:, :1], x0=True, rtol=0.0, max_iterations=sec.BUDGET, history=True)
-        check(models, (X, res, hist), "host")
+        check_call(models, (X, res, hist), "host")
         assert not wide[:, 0].any() and (wide[:, 1] == CANARY).all()
         for shift in (0, 1):
             edge = 16 // np.dtype(dtype).itemsize
@@ -241,7 +217,7 @@ def test_one_zero_column_in_a_wider_x(dtype):
             Bd = torch.from_numpy(B).to(DEV)
             X, res, hist = h.cg_columns(Bd[:, :1], Xd[:, :1], x0=True, rtol=0.0, max_iterations=sec.BUDGET, history=True)
             torch.cuda.synchronize()
-            check(models, (X.cpu().numpy(), res, hist), ("device", shift))
+            check_call(models, (X.cpu().numpy(), res, hist), ("device", shift))
             out = xbuf.cpu().numpy()
             body = out[edge + shift:edge + shift + 2 * csr.m].reshape(csr.m, 2)
             assert not body[:, 0].any() and (body[:, 1] == CANARY).all() and (out[:edge + shift] == CANARY).all() and (out[edge + shift + 2 * csr.m:] == CANARY).all(), shift
@@ -266,7 +242,7 @@ def test_a_call_is_unaffected_by_what_earlier_calls_left(dtype):
         def call(B, X0=None, dinv=None, budget=sec.BUDGET, every=0):
             models = models_of(mul, B, X0, dinv, max_iterations=budget)
             got = device_call(h, B, X0, dinv, LAYOUTS[0], max_iterations=budget, check_every=every)
-            check(models, got, (B.shape[1], every))
+            check_call(models, got, (B.shape[1], every))
             return models, got
 
         def the_ordinary_calls(ks):
@@ -291,9 +267,9 @@ def test_a_call_is_unaffected_by_what_earlier_calls_left(dtype):
         models, _ = call(B, huge, Dinv, budget=16)                      # the first solve of the handle: it allocates the workspace
         assert all(ended(mo) == (cgc.NONFINITE, 0, "begin:nonfinite") for mo in models) and (~np.isfinite(mul(huge[:, 0].copy()))).any()
         held = h.info()["device_bytes"]
-        assert held - before >= ccc.workspace_bytes(m, 11, item)        # ... and the history block
+        assert held - before >= ROW.workspace(m, 11, item)        # ... and the history block
         for k in the_ordinary_calls((3, 15, 2)):
-            assert h.info()["device_bytes"] - held == (0 if k == 3 else ccc.workspace_bytes(m, 15, item) - ccc.workspace_bytes(m, 11, item)), k
+            assert h.info()["device_bytes"] - held == (0 if k == 3 else ROW.workspace(m, 15, item) - ROW.workspace(m, 11, item)), k
         grown = h.info()["device_bytes"]
         the_group("plain")
         the_group("pre")
@@ -325,7 +301,7 @@ def test_atol_decides_with_less_or_equal_column_by_column(dtype):
                         if atol not in seen:
                             seen[atol] = models_of(mul, B, atol=atol, max_iterations=sec.BUDGET)
                             for every in (1, 0):
-                                check(seen[atol], solve(h, B, atol=atol, max_iterations=sec.BUDGET, check_every=every), (m, j, atol, every))
+                                check_call(seen[atol], solve(h, B, atol=atol, max_iterations=sec.BUDGET, check_every=every), (m, j, atol, every))
                         mine = seen[atol][j]
                         assert ((mine["iterations"], mine["end"]) == (its, end)) == there and (not there or mine["status"] == cgc.CONVERGED), (m, j, atol)
     assert places == {"begin:converged", "direction:converged"}, places
@@ -350,7 +326,7 @@ def test_the_timed_launches_do_the_arithmetic_of_the_solve(k, dtype):
         Xw = torch.full((m, ldx), CANARY, dtype=tdt, device=DEV)
         if X0 is not None:
             Xw[:, :k] = torch.from_numpy(X0)
-        mean, runs = api.time_cg_columns_iterations(h.h, Bw[:, :k], Xw[:, :k], budget, x0=X0 is not None, dinv=None if dinv is None else torch.from_numpy(dinv).to(DEV),
+        mean, runs = ROW.timer(h.h, Bw[:, :k], Xw[:, :k], budget, x0=X0 is not None, dinv=None if dinv is None else torch.from_numpy(dinv).to(DEV),
                                                     warmup=warmup, iters=iters)
         torch.cuda.synchronize()
         out = Xw.cpu().numpy()
@@ -363,9 +339,9 @@ def test_the_timed_launches_do_the_arithmetic_of_the_solve(k, dtype):
             assert all(ended(mo) == (cgc.MAX_ITERATIONS, 8, "budget") for mo in models_of(mul, B, None, dinv, max_iterations=8))   # still running at 6
             models = models_of(mul, B, None, dinv, max_iterations=6)
             want = solve(h, B, dinv=dinv, max_iterations=6)
-            check(models, want, "from zero")
+            check_call(models, want, "from zero")
             from_guess = solve(h, B, guess, dinv=dinv, max_iterations=6)
-            check(models_of(mul, B, guess, dinv, max_iterations=6), from_guess, "from the guess")
+            check_call(models_of(mul, B, guess, dinv, max_iterations=6), from_guess, "from the guess")
             half = solve(h, B, guess, dinv=dinv, max_iterations=3)[0]
             again = solve(h, B, half, dinv=dinv, max_iterations=3)[0]       # the solve restarted from its own result: not one run of 6
             assert not same(from_guess[0], want[0]) and not same(again, from_guess[0])
@@ -390,7 +366,7 @@ def test_a_long_row_under_the_column_solver(dtype):
         for X0, dinv in ((None, None), (guess, jac)):
             models = models_of(mul, B, X0, dinv, max_iterations=12)
             assert all(mo["iterations"] == 12 and np.isfinite(mo["x"]).all() for mo in models), [ended(mo) for mo in models]
-            check(models, solve(h, B, X0, dinv=dinv, max_iterations=12), X0 is not None)
+            check_call(models, solve(h, B, X0, dinv=dinv, max_iterations=12), X0 is not None)
 
 
 @pytest.mark.parametrize("dtype", sec.BOTH, ids=NAMES.get)
@@ -404,7 +380,7 @@ def test_three_ends_and_a_running_column_at_two_steps_per_workgroup(dtype):
         models = models_of(mul, B, X0, max_iterations=sec.BUDGET)
         declared(cases, models)
         for every in (1, 0):
-            check(models, solve(h, B, X0, max_iterations=sec.BUDGET, check_every=every), every)
+            check_call(models, solve(h, B, X0, max_iterations=sec.BUDGET, check_every=every), every)
         short = models_of(mul, B, X0, max_iterations=longest - 1)
         declared(cases, short, longest - 1)
-        check(short, solve(h, B, X0, max_iterations=longest - 1), "short")
+        check_call(short, solve(h, B, X0, max_iterations=longest - 1), "short")

@@ -3,7 +3,7 @@
 The yardstick is the per-column host model of tests/cg_columns_cases.py: cg_cases.cg, unchanged, around column 0 of the SAME handle's spmm on a
 two-column probe.  X, status, iterations, rr, bb and the history of every column are compared BIT FOR BIT; no tolerance appears except the
 true-residual bound that tests/test_cg_columns_host.py shows the model alone to meet.  A column's model does not depend on k, so it is computed
-once per matrix and shared by every k and position."""
+once per matrix and shared by every k and position.  The helpers that the solvers share are in tests/solve_harness.py."""
 import ctypes as C
 
 import numpy as np
@@ -11,99 +11,28 @@ import pytest
 
 import cg_cases as cgc
 import cg_columns_cases as ccc
-from spmv_amd import api, build
+import solve_harness as sh
+from solve_harness import CANARY, DEV, DTYPES, E_ARG, METHODS, check_column, check_columns, handle, run_bits, same_bits, same_values
+from solve_harness import solve_columns as solve
+from spmv_amd import api
 
 pytestmark = pytest.mark.gpu
 
-M = api.SPMV_METHODS
-METHODS = [mth for mth in M if mth != M.Method_Total_Size]
-DTYPES = [np.float64, np.float32]
-E_ARG, E_NOSTATE = 3, 5
-DEV = "cuda:0"
-CANARY = -7.25
-SIZES = [1, 3, 4, 5, 1023, 1024, 1025, 2049]     # slot, block and workgroup edges: P = 1, 2 and 3 workgroups
+ROW = sh.ROWS["cg_columns"]
+SIZES = sh.SIZES[:-1]     # slot, block and workgroup edges: P = 1, 2 and 3 workgroups; BIG has a test of its own
 KS = [2, 3, 5, 8, 16]
-BUDGETS = (0, 1, 2, 5)
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _lib():
-    build.build()
-    lib = api.load()
-    assert lib.spmv_hip_device_count() > 0, "GPU tests need a device"
+    lib = sh.library()
     assert hasattr(lib, "spmv_hip_cg_columns")
     return lib
-
-
-def handle(csr, method=M.Method_Parallel, way=api.VECTORIZED_WAY.VECTOR_HIP, **opts):
-    for key, v in opts.items():
-        api.set_thread_option(key, v)
-    try:
-        return api.Handle(csr.m, csr.n, csr.rowptr, csr.colidx, csr.val, method, way=way)
-    finally:
-        api.clear_thread_options()
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
-
-
-def same_values(a, b):
-    """same_bits, but a NaN matches a NaN whatever its payload (the model's NaN is numpy's, the device's is the hardware's)"""
-    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
-    nan = np.isnan(a)
-    return a.shape == b.shape and np.array_equal(nan, np.isnan(b)) and same_bits(np.where(nan, 0.0, a), np.where(nan, 0.0, b))
 
 
 def same_results(a, b):
     """two lists of result dicts, rr and bb by same_values"""
     return len(a) == len(b) and all((p["status"], p["iterations"]) == (q["status"], q["iterations"]) and same_values([p["rr"], p["bb"]], [q["rr"], q["bb"]]) for p, q in zip(a, b))
-
-
-def solve(h, B, X0=None, **kw):
-    """through host pointers -> (X, list of result dicts, history)"""
-    X = np.full(B.shape, CANARY, dtype=B.dtype) if X0 is None else X0.copy()
-    return h.cg_columns(np.ascontiguousarray(B), X, x0=X0 is not None, history=True, **kw)
-
-
-def check_column(model, budget, x, res, hist):
-    """column of a run with max_iterations = budget against its model run with a budget of at least that"""
-    its = min(budget, model["iterations"])
-    ended = model["status"] != cgc.MAX_ITERATIONS and model["iterations"] <= budget
-    assert (res["status"], res["iterations"]) == (model["status"] if ended else cgc.MAX_ITERATIONS, its)
-    assert same_bits(x, model["iterates"][its])
-    assert same_values(res["bb"], model["bb"]) and same_values(res["rr"], model["history"][its])
-    assert same_values(hist[:its + 1], model["history"][:its + 1])
-    assert np.isnan(hist[its + 1:]).all()                  # behind the column's end nothing was written (api.cg_columns fills with NaN)
-
-
-def check_columns(models, budget, X, res, hist):
-    assert len(res) == X.shape[1] == len(models) and hist.shape == (1 + max(r["iterations"] for r in res), len(models))
-    for j, model in enumerate(models):
-        check_column(model, budget, X[:, j], res[j], hist[:, j])
-
-
-def run_bits(csr, dtype, ks, seed):
-    m = csr.m
-    rng = np.random.default_rng(m + seed)
-    kmax = max(ks)
-    B, G = ccc.columns(m, kmax, dtype, seed), rng.uniform(-1, 1, (m, kmax)).astype(dtype)
-    jac = rng.uniform(0.5, 1.5, m).astype(dtype)
-    with handle(csr) as h:
-        mul = ccc.spmm_column(h)
-        for X0 in (None, G):
-            plain = ccc.solve(mul, B, X0, max_iterations=5)
-            pre = ccc.solve(mul, B, X0, dinv=jac, max_iterations=5)
-            for k in ks:
-                Bk, X0k = B[:, :k], None if X0 is None else np.ascontiguousarray(X0[:, :k])
-                for budget in BUDGETS:
-                    X, res, hist = solve(h, Bk, X0k, rtol=0.0, max_iterations=budget)
-                    check_columns(plain[:k], budget, X, res, hist)
-                    X1, res1, hist1 = solve(h, Bk, X0k, rtol=0.0, max_iterations=budget, dinv=np.ones(m, dtype=dtype))
-                    assert same_bits(X1, X) and same_bits(hist1, hist) and res1 == res
-                    X, res, hist = solve(h, Bk, X0k, rtol=0.0, max_iterations=budget, dinv=jac)
-                    check_columns(pre[:k], budget, X, res, hist)
 
 
 # ----------------------------------------------------------------------------- 1. bits against the model
@@ -115,7 +44,7 @@ def test_bits_against_the_model(m, dtype):
 
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_bits_against_the_model_past_one_step(dtype):
-    run_bits(cgc.tri(1024 * 1024 + 1, dtype), dtype, [3], 1)      # P = 1024, L = 2048: two steps, empty workgroups
+    run_bits(cgc.tri(sh.BIG, dtype), dtype, [3], 1)      # P = 1024, L = 2048: two steps, empty workgroups
 
 
 # ----------------------------------------------------------------------------- 2. a column does not know its company
@@ -299,48 +228,21 @@ def test_argument_errors_leave_x_untouched(_lib):
     X = np.full((csr.m, k), CANARY)
     rp, ci, va = csr.rowptr, csr.colidx, csr.val
     results = (api.spmv_hip_cg_result * 16)()
+    call = sh.caller(lib, lambda h, opt, res, B=B, X=X, kk=k, ldb=k, ldx=k: lib.spmv_hip_cg_columns(
+        h, csr.m, api._ptr(rp), api._ptr(ci), api._ptr(va), kk, api._ptr(B), ldb, api._ptr(X), ldx, opt, res))
+    options = sh.options_of(ROW)
 
-    def call(h, opt, res, Bp=B, Xp=X, kk=k, ldb=k, ldx=k):
-        lib.spmv_hip_clear_error()
-        rc = lib.spmv_hip_cg_columns(h, csr.m, api._ptr(rp), api._ptr(ci), api._ptr(va), kk, api._ptr(Bp), ldb, api._ptr(Xp), ldx, opt, res)
-        assert lib.spmv_hip_last_error() == rc
-        lib.spmv_hip_clear_error()
-        return rc
-
-    def options(**kw):
-        base = dict(rtol=1e-8, atol=0.0, max_iterations=10, check_every=0, use_x0=0)
-        base.update(kw)
-        return C.byref(api.spmv_hip_cg_options(**base))
-
-    with handle(csr) as h:
-        assert call(h.h, None, results) == E_ARG and call(h.h, options(), None) == E_ARG
-        assert call(h.h, options(), results, Bp=None) == E_ARG and call(h.h, options(), results, Xp=None) == E_ARG
-        for bad in (dict(max_iterations=-1), dict(check_every=-1), dict(rtol=-1e-3), dict(atol=-1.0), dict(rtol=float("nan")), dict(atol=float("nan"))):
-            assert call(h.h, options(**bad), results) == E_ARG, bad
+    def shapes(h):
         for bad in (dict(kk=0), dict(kk=-1), dict(kk=17, ldb=17, ldx=17), dict(ldb=k - 1), dict(ldx=k - 1), dict(ldb=0), dict(ldx=0)):
             assert call(h.h, options(), results, **bad) == E_ARG, bad
-        assert call(None, options(), results) == E_ARG
-        assert (X == CANARY).all()
-        assert call(h.h, options(), results) == 0 and not (X == CANARY).any()      # the same call with good arguments runs
-    X[:] = CANARY
-    wide = cgc.synth.CSR(csr.m, csr.m + 1, rp, ci, va)                              # m != n at create
-    with handle(wide) as h:
-        assert call(h.h, options(), results) == E_ARG
-    for key, way in (("gpus", api.VECTORIZED_WAY.VECTOR_HIP), ("host_rows", api.VECTORIZED_WAY.VECTOR_NONE)):
-        with handle(csr, M.Method_Serial, way, **{key: 1}) as h:
-            assert call(h.h, options(), results) == E_ARG, key
-    h = handle(csr)
-    api.spmv_clear_handle(h.h)
-    assert call(h.h, options(), results) == E_NOSTATE
-    h.close()
-    assert (X == CANARY).all()
+    sh.common_argument_errors(csr, X, call, options, results, more=shapes)
 
 
 def test_m_zero_is_converged():
-    empty = cgc.synth.CSR(0, 0, np.zeros(1, dtype=np.int32), np.zeros(0, dtype=np.int32), np.zeros(0))
+    empty = sh.empty_csr()
     with handle(empty) as h:
         rc, res = api.cg_columns(h.h, 0, empty.rowptr, empty.colidx, empty.val, np.zeros((0, 3)), np.zeros((0, 3)), max_iterations=5)
-    assert rc == 0 and len(res) == 3 and all((r["status"], r["iterations"], r["rr"], r["bb"]) == (cgc.CONVERGED, 0, 0.0, 0.0) for r in res)
+    assert rc == 0 and len(res) == 3 and all(sh.converged_at_zero(r) for r in res)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -359,25 +261,25 @@ def test_workspace_other_solvers_multiplies_and_timer(dtype):
         Bd = torch.from_numpy(B).to(DEV)
         X3, res3 = h.cg_columns(Bd[:, :3].contiguous(), rtol=1e-6, max_iterations=300)   # device operands: no staging buffer is added
         assert all(r["status"] == cgc.CONVERGED for r in res3) and X3.device.type == "cuda"
-        assert h.info()["device_bytes"] - before == ccc.workspace_bytes(m, 3, item)
+        assert h.info()["device_bytes"] - before == ROW.workspace(m, 3, item)
         h.cg_columns(Bd[:, :2].contiguous(), rtol=1e-6, max_iterations=300)            # fewer columns: the same block
-        assert h.info()["device_bytes"] - before == ccc.workspace_bytes(m, 3, item)
+        assert h.info()["device_bytes"] - before == ROW.workspace(m, 3, item)
         X8, res8 = h.cg_columns(Bd, rtol=1e-6, max_iterations=300)                   # more: allocated anew
-        grown = ccc.workspace_bytes(m, 8, item)
+        grown = ROW.workspace(m, 8, item)
         assert h.info()["device_bytes"] - before == grown
         assert same_bits(X8[:, :3].cpu().numpy(), X3.cpu().numpy()) and res8[:3] == res3
         X3b, res3b = h.cg_columns(Bd[:, :3].contiguous(), rtol=1e-6, max_iterations=300)   # in the larger block: the same bits
         assert h.info()["device_bytes"] - before == grown and same_bits(X3b.cpu().numpy(), X3.cpu().numpy()) and res3b == res3
-        vec = (m * item + 255) // 256 * 256
+        cg_block, bicgstab_block = sh.ROWS["cg"].workspace(m, item), sh.ROWS["bicgstab"].workspace(m, item)
         bd = torch.from_numpy(b).to(DEV)
         h.cg(bd, rtol=1e-6, max_iterations=300)
-        assert h.info()["device_bytes"] - before == grown + 3 * vec + 5 * 1024 * 8 + 256            # spmv_hip_cg's own pinned block
+        assert h.info()["device_bytes"] - before == grown + cg_block            # spmv_hip_cg's own pinned block
         h.bicgstab(bd, rtol=1e-6, max_iterations=300)
-        both = grown + 3 * vec + 5 * 1024 * 8 + 256 + 6 * vec + 8 * 1024 * 8 + 256                  # ... and spmv_hip_bicgstab's
+        both = grown + cg_block + bicgstab_block                  # ... and spmv_hip_bicgstab's
         assert h.info()["device_bytes"] - before == both
         assert same_bits(h.spmv(b, np.empty_like(b)), y0) and same_bits(h.spmm(B), Y0)              # the multiplies compute what they did
         Xt = torch.empty_like(Bd)
-        mean, runs = api.time_cg_columns_iterations(h.h, Bd, Xt, 10, warmup=1, iters=3)
+        mean, runs = ROW.timer(h.h, Bd, Xt, 10, warmup=1, iters=3)
         assert mean > 0 and runs.shape == (3,) and (runs > 0).all() and h.info()["device_bytes"] - before == both
         X8b, res8b = h.cg_columns(Bd, rtol=1e-6, max_iterations=300)
         assert same_bits(X8b.cpu().numpy(), X8.cpu().numpy()) and res8b == res8

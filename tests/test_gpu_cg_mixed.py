@@ -2,8 +2,8 @@
 
 The yardstick is the host model of tests/cg_mixed_cases.py -- a numpy restatement of the header's arithmetic contract -- driven by the two
 handles' OWN spmv(), so X, status, iterations, updates, rr, bb and the history are compared BIT FOR BIT; the only tolerance is the true-residual
-bound ||b - A x|| / ||b|| <= 2 rtol that tests/test_cg_mixed_host.py shows the model alone to meet."""
-import contextlib
+bound ||b - A x|| / ||b|| <= 2 rtol that tests/test_cg_mixed_host.py shows the model alone to meet.  The bodies that the solvers share are in
+tests/solve_harness.py; there a pair (hi, lo) stands where the other solvers have a handle."""
 import ctypes as C
 
 import numpy as np
@@ -11,72 +11,31 @@ import pytest
 
 import cg_cases as cgc
 import cg_mixed_cases as mix
-from spmv_amd import api, build
+import solve_harness as sh
+from solve_harness import CANARY, DEV, E_ARG, E_NOSTATE, M, SIZES, handle, pair, same_bits
+from spmv_amd import api
 
 pytestmark = pytest.mark.gpu
 
-M = api.SPMV_METHODS
-E_ARG, E_NOSTATE = 3, 5
-DEV = "cuda:0"
-CANARY = -7.25
-# test_gpu_cg.py's dot edges: slot, step and workgroup edges, two steps per workgroup and empty workgroups
-SIZES = [1, 3, 4, 5, 1023, 1024, 1025, 2049, 1024 * 1024 + 1]
+ROW = sh.ROWS["cg_mixed"]
 BUDGETS = [0, 1, 2, 5, 9]
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _lib():
-    build.build()
-    lib = api.load()
-    assert lib.spmv_hip_device_count() > 0, "GPU tests need a device"
-    return lib
-
-
-def handle(csr, method=M.Method_Parallel, way=api.VECTORIZED_WAY.VECTOR_HIP, **opts):
-    for key, v in opts.items():
-        api.set_thread_option(key, v)
-    try:
-        return api.Handle(csr.m, csr.n, csr.rowptr, csr.colidx, csr.val, method, way=way)
-    finally:
-        api.clear_thread_options()
-
-
-@contextlib.contextmanager
-def pair(csr, low=None, method=M.Method_Parallel):
-    """the fp64 handle of `csr` and the fp32 handle of `low` (default: csr's float copy)"""
-    with handle(csr, method) as hi, handle(mix.narrowed(csr) if low is None else low, method) as lo:
-        yield hi, lo
-
-
-def multiplies_of(hi, lo):
-    """the model's multiplies: the two handles' spmv() on host vectors"""
-    def high(x):
-        assert x.dtype == np.float64
-        return hi.spmv(np.ascontiguousarray(x), np.empty_like(x))
-
-    def low(x):
-        assert x.dtype == np.float32
-        return lo.spmv(np.ascontiguousarray(x), np.empty_like(x))
-    return high, low
+    return sh.library()
 
 
 def solve(hi, lo, b, x0=None, **kw):
-    """through host pointers -> (x, result dict with history)"""
-    x = np.full(b.size, CANARY) if x0 is None else x0.copy()
-    x, res, hist = hi.cg_mixed(lo, b, x, x0=x0 is not None, history=True, **kw)
-    res["history"] = hist
-    return x, res
+    return sh.solve(ROW, (hi, lo), b, x0, **kw)
 
 
-def same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+def model_of(hi, lo, b, **kw):
+    return ROW.model((hi, lo), b, **kw)
 
 
 def check_against(model, x, res):
-    got = (res["status"], res["iterations"], res["updates"], res["rr"], res["bb"])
-    assert got == (model["status"], model["iterations"], model["updates"], model["rr"], model["bb"]), (got, model["end"], model["segments"])
-    assert same_bits(res["history"], model["history"])
-    assert same_bits(x, model["x"])
+    sh.check_same_end(ROW, model, x, res)
 
 
 # ----------------------------------------------------------------------------- 1. bits against the model, updates inside small budgets
@@ -90,11 +49,10 @@ def test_bits_against_the_model(m, with_x0):
     x0 = guess if with_x0 else None
     kw = dict(rtol=0.0, update_every=2, update_drop=0.5)
     with pair(csr) as (hi, lo):
-        high, low = multiplies_of(hi, lo)
         seen = set()
         for k in BUDGETS:
-            plain = mix.cg_mixed(high, low, b, x0=x0, max_iterations=k, **kw)
-            pre = mix.cg_mixed(high, low, b, x0=x0, dinv=jac, max_iterations=k, **kw)
+            plain = model_of(hi, lo, b, x0=x0, max_iterations=k, **kw)
+            pre = model_of(hi, lo, b, x0=x0, dinv=jac, max_iterations=k, **kw)
             seen.update(plain["segments"])
             x_none, r_none = solve(hi, lo, b, x0, max_iterations=k, **kw)
             check_against(plain, x_none, r_none)
@@ -114,7 +72,7 @@ def full_solve():
     csr = cgc.lap2d(32)
     b = cgc.rhs(csr.m, np.float64)
     with pair(csr) as (hi, lo):
-        model = mix.cg_mixed(*multiplies_of(hi, lo), b, rtol=1e-12, max_iterations=1000)
+        model = model_of(hi, lo, b, rtol=1e-12, max_iterations=1000)
         assert model["status"] == mix.CONVERGED and model["updates"] > 3
         yield csr, b, model, hi, lo
 
@@ -132,7 +90,7 @@ def test_full_solve_has_the_models_bits_and_an_fp64_residual(full_solve):
 def test_check_every_changes_nothing(full_solve):
     csr, b, model, hi, lo = full_solve
     short = model["iterations"] // 2
-    cut = mix.cg_mixed(*multiplies_of(hi, lo), b, rtol=1e-12, max_iterations=short)
+    cut = model_of(hi, lo, b, rtol=1e-12, max_iterations=short)
     assert cut["status"] == mix.MAX_ITERATIONS
     for every in (1, 2, 3, 8, 64):
         # the early exit really exits: nothing is applied behind a segment's end or the solve's, however many iterations were enqueued
@@ -147,37 +105,15 @@ def test_check_every_changes_nothing(full_solve):
 @pytest.mark.parametrize("m", [1025, 70001])
 def test_host_device_and_unaligned_pointers_give_the_same_bits(m):
     import torch
-    csr = cgc.tri(m)
     rng = np.random.default_rng(m + 1)
     b, guess, jac = cgc.rhs(m, np.float64, 4), rng.uniform(-1, 1, m), rng.uniform(0.5, 1.5, m).astype(np.float32)
     kw = dict(rtol=0.0, max_iterations=7, update_every=3)
-    with pair(csr) as (hi, lo):
-        for x0 in (None, guess):
-            want, wres = solve(hi, lo, b, x0, dinv=jac, **kw)
-            assert wres["updates"] >= 2
-            for shift_b, shift_x, shift_d in ((0, 0, 0), (1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 1)):
-                bd = torch.zeros(m + 1, dtype=torch.float64, device=DEV)[shift_b:shift_b + m]
-                bd.copy_(torch.from_numpy(b))
-                jd = torch.zeros(m + 1, dtype=torch.float32, device=DEV)[shift_d:shift_d + m]
-                jd.copy_(torch.from_numpy(jac))
-                buf = torch.full((m + 5,), CANARY, dtype=torch.float64, device=DEV)
-                xd = buf[2 + shift_x:2 + shift_x + m]                  # offset by one element: not 16-byte aligned
-                assert (xd.data_ptr() % 16 != 0) == bool(shift_x) and (bd.data_ptr() % 16 != 0) == bool(shift_b)
-                if x0 is not None:
-                    xd.copy_(torch.from_numpy(x0))
-                got, res, hist = hi.cg_mixed(lo, bd, xd, x0=x0 is not None, dinv=jd, history=True, **kw)
-                torch.cuda.synchronize()
-                assert got is xd and same_bits(xd.cpu().numpy(), want), (shift_b, shift_x, shift_d)
-                assert same_bits(hist, wres["history"]) and (res["rr"], res["updates"]) == (wres["rr"], wres["updates"])
-                out = buf.cpu().numpy()
-                assert (out[:2 + shift_x] == CANARY).all() and (out[2 + shift_x + m:] == CANARY).all(), "written outside X"
-            # mixed: device B, host X, device Dinv; host B, device X, host Dinv
-            xh = np.full(m, CANARY) if x0 is None else x0.copy()
-            hi.cg_mixed(lo, torch.from_numpy(b).to(DEV), xh, x0=x0 is not None, dinv=torch.from_numpy(jac).to(DEV), **kw)
-            assert same_bits(xh, want)
-            xd = torch.full((m,), CANARY, dtype=torch.float64, device=DEV) if x0 is None else torch.from_numpy(x0).to(DEV)
-            hi.cg_mixed(lo, b, xd, x0=x0 is not None, dinv=jac, **kw)
-            assert same_bits(xd.cpu().numpy(), want)
+
+    def host_b_device_x_host_dinv(h, x0, want):
+        xd = torch.full((m,), CANARY, dtype=torch.float64, device=DEV) if x0 is None else torch.from_numpy(x0).to(DEV)
+        h[0].cg_mixed(h[1], b, xd, x0=x0 is not None, dinv=jac, **kw)
+        assert same_bits(xd.cpu().numpy(), want)
+    sh.pointers_give_the_same_bits(ROW, cgc.tri(m), b, guess, kw, lambda res: res["updates"] >= 2, dinv=jac, shift_dinv=True, each=host_b_device_x_host_dinv)
 
 
 # ----------------------------------------------------------------------------- 4. schedules
@@ -187,7 +123,7 @@ def test_schedules_have_the_bits_of_the_model_on_their_own_spmv(method):
     b = cgc.rhs(csr.m, np.float64, 1)
     kw = dict(rtol=1e-12, max_iterations=40, update_every=6)
     with pair(csr, method=method) as (hi, lo):
-        model = mix.cg_mixed(*multiplies_of(hi, lo), b, **kw)
+        model = model_of(hi, lo, b, **kw)
         x, res = solve(hi, lo, b, **kw)
     assert model["updates"] >= 3
     check_against(model, x, res)
@@ -198,7 +134,7 @@ def test_schedules_have_the_bits_of_the_model_on_their_own_spmv(method):
 def test_every_status_and_segment_end(name):
     csr, low_csr, b, kw, status, what = mix.named_cases()[name]
     with pair(csr, low_csr) as (hi, lo):
-        model = mix.cg_mixed(*multiplies_of(hi, lo), b, **kw)
+        model = model_of(hi, lo, b, **kw)
         assert model["status"] == status and (what in model["segments"] or what == model["end"]), (model["end"], model["segments"])
         x, res = solve(hi, lo, b, **kw)
     check_against(model, x, res)
@@ -211,13 +147,11 @@ def test_zero_rhs_and_m_zero(_lib):
     with pair(csr) as (hi, lo):
         for x0 in (None, b):
             x, res = solve(hi, lo, np.zeros_like(b), x0, rtol=1e-6, max_iterations=20)
-            assert (res["status"], res["iterations"], res["updates"], res["rr"], res["bb"]) == (mix.CONVERGED, 0, 0, 0.0, 0.0)
+            assert sh.converged_at_zero(res, "updates")
             assert not x.any() and same_bits(res["history"], np.zeros(1))
-    e64 = cgc.synth.CSR(0, 0, np.zeros(1, dtype=np.int32), np.zeros(0, dtype=np.int32), np.zeros(0))
-    e32 = cgc.synth.CSR(0, 0, np.zeros(1, dtype=np.int32), np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.float32))
-    with handle(e64) as hi, handle(e32) as lo:
+    with handle(sh.empty_csr()) as hi, handle(sh.empty_csr(np.float32)) as lo:
         rc, res = api.cg_mixed(hi.h, lo.h, None, None, max_iterations=5)
-    assert rc == 0 and (res["status"], res["iterations"], res["updates"], res["rr"], res["bb"]) == (mix.CONVERGED, 0, 0, 0.0, 0.0)
+    assert rc == 0 and sh.converged_at_zero(res, "updates")
 
 
 # ----------------------------------------------------------------------------- 6. argument and handle rules
@@ -228,24 +162,13 @@ def test_argument_errors_leave_x_untouched(_lib):
     b = cgc.rhs(csr.m, np.float64)
     x = np.full(csr.m, CANARY)
 
-    def call(hi, lo, opt, res, B=b, X=x):
-        lib.spmv_hip_clear_error()
-        rc = lib.spmv_hip_cg_mixed(hi, lo, api._ptr(B), api._ptr(X), opt, res)
-        assert lib.spmv_hip_last_error() == rc
-        lib.spmv_hip_clear_error()
-        return rc
-
-    def options(**kw):
-        base = dict(rtol=1e-10, atol=0.0, max_iterations=10, check_every=0, use_x0=0, update_drop=0.0, update_every=0)
-        base.update(kw)
-        return C.byref(api.spmv_hip_cg_mixed_options(**base))
-
-    res = C.byref(api.spmv_hip_cg_mixed_result())
+    call = sh.caller(lib, lambda hi, lo, opt, res, B=b, X=x: lib.spmv_hip_cg_mixed(hi, lo, api._ptr(B), api._ptr(X), opt, res))
+    options = sh.options_of(ROW)
+    res = C.byref(ROW.result())
     with pair(csr) as (hi, lo):
         assert call(hi.h, lo.h, None, res) == E_ARG and call(hi.h, lo.h, options(), None) == E_ARG
         assert call(hi.h, lo.h, options(), res, B=None) == E_ARG and call(hi.h, lo.h, options(), res, X=None) == E_ARG
-        for bad in (dict(max_iterations=-1), dict(check_every=-1), dict(rtol=-1e-3), dict(atol=-1.0), dict(rtol=float("nan")), dict(atol=float("nan")),
-                    dict(update_drop=-0.1), dict(update_drop=1.0), dict(update_drop=2.0), dict(update_drop=float("nan")), dict(update_every=-1)):
+        for bad in sh.BAD_OPTIONS + (dict(update_drop=-0.1), dict(update_drop=1.0), dict(update_drop=2.0), dict(update_drop=float("nan")), dict(update_every=-1)):
             assert call(hi.h, lo.h, options(**bad), res) == E_ARG, bad
         assert call(None, lo.h, options(), res) == E_ARG and call(hi.h, None, options(), res) == E_ARG
         # the types: `high` must be fp64 and `low` fp32
@@ -310,13 +233,12 @@ def test_workspace_is_highs_own_and_leaves_the_other_solves_alone():
         xd, res = hi.cg_mixed(lo, bd, rtol=1e-10, max_iterations=500)          # device operands: no staging buffer is added
         assert res["status"] == mix.CONVERGED and xd.device.type == "cuda" and xd.dtype == torch.float64
         grown = hi.info()["device_bytes"] - before_hi
-        up256 = lambda n: (n + 255) // 256 * 256
-        assert grown == 2 * up256(8 * m) + 4 * up256(4 * m) + 6 * 1024 * 8 + 256    # xn, q64; r, p, q, y; six partial arrays; the state
+        assert grown == ROW.workspace(m)
         assert lo.info()["device_bytes"] == before_lo
         x2, res2 = hi.cg_mixed(lo, bd, rtol=1e-10, max_iterations=500)
         assert hi.info()["device_bytes"] == before_hi + grown and lo.info()["device_bytes"] == before_lo
         assert same_bits(x2.cpu().numpy(), xd.cpu().numpy()) and res2 == res
-        mean, runs = api.time_cg_mixed_iterations(hi.h, lo.h, bd, x2, 10, update_every=4, warmup=1, iters=3)
+        mean, runs = ROW.timer(hi.h, lo.h, bd, x2, 10, update_every=4, warmup=1, iters=3)
         assert mean > 0 and runs.shape == (3,) and (runs > 0).all()
         assert hi.info()["device_bytes"] == before_hi + grown and lo.info()["device_bytes"] == before_lo
         # Handle.cg on either handle computes what it did before the mixed solves

@@ -5,8 +5,8 @@ The yardstick is the host model of tests/cg_mixed_cases.py driven by the SAME pa
 history are compared bit for bit and no tolerance appears anywhere.  The one freedom: a NaN equals a NaN whatever its sign and payload.  The
 cases come from tests/cg_mixed_end_cases.py, whose every line tests/test_cg_mixed_ends_host.py proves on the CPU first; here each case must also
 reach the (status, iterations, updates, end, segments) it declares under the pair's own multiplies -- bits that match a model which ends
-elsewhere would mean the INPUT is wrong, not the kernel."""
-import contextlib
+elsewhere would mean the INPUT is wrong, not the kernel.  The bodies that the solvers share are in tests/solve_harness.py."""
+import functools
 
 import numpy as np
 import pytest
@@ -14,17 +14,13 @@ import pytest
 import cg_cases as cgc
 import cg_mixed_cases as mix
 import cg_mixed_end_cases as me
-import packed_cases as pc
 import solve_end_cases as sec
-from spmv_amd import api, build
-from test_gpu_solve_ends import EXECUTORS, LONG_ROW_KERNELS, METHODS, handle, multiply_of, same
+import solve_harness as sh
+from solve_harness import CANARY, DEV, EVERY, EXECUTORS, M, METHODS, multiplies_of, pair, same
 
 pytestmark = pytest.mark.gpu
 
-M = api.SPMV_METHODS
-DEV = "cuda:0"
-CANARY = -7.25
-EVERY = (1, 2, 3, 0, 64)           # check_every: an end or a segment's end falls first, in the middle and last in an enqueued batch
+ROW = sh.ROWS["cg_mixed"]
 # the runs of the atol test (tests/test_cg_mixed_ends_host.py looks first): a segment that ends by the estimate test and a committed rr that converges
 ATOL_CASES = ("m_resume_converged_after_estimate", "m_resume_converged_after_every", "m_resume_converged_after_drop",
               "m_resume_budget_after_estimate")
@@ -32,38 +28,14 @@ ATOL_CASES = ("m_resume_converged_after_estimate", "m_resume_converged_after_eve
 
 @pytest.fixture(scope="module", autouse=True)
 def _lib():
-    build.build()
-    lib = api.load()
-    assert lib.spmv_hip_device_count() > 0, "GPU tests need a device"
-    return lib
+    return sh.library()
 
 
-@contextlib.contextmanager
-def pair(high, low, method=M.Method_Parallel, low_method=None, high_opts=None, low_opts=None):
-    """the fp64 handle of `high` and the fp32 handle of `low`"""
-    with handle(high, method, **(high_opts or {})) as hi, handle(low, method if low_method is None else low_method, **(low_opts or {})) as lo:
-        yield hi, lo
-
-
-def multiplies_of(hi, lo):
-    return multiply_of(hi), multiply_of(lo)
+check = functools.partial(sh.check, ROW)
 
 
 def solve(hi, lo, b, x0=None, **kw):
-    """through host pointers, with a canary in X when there is no guess -> (x, result dict with history)"""
-    x = np.full(b.size, CANARY) if x0 is None else x0.copy()
-    x, res, hist = hi.cg_mixed(lo, b, x, x0=x0 is not None, history=True, **kw)
-    res["history"] = hist
-    return x, res
-
-
-def check(model, x, res, what=None):
-    """a run against a model run with the same arguments, however either ended"""
-    got = (res["status"], res["iterations"], res["updates"])
-    assert got == (model["status"], model["iterations"], model["updates"]), (what, res, model["end"], model["segments"])
-    assert same(x, model["x"]), (what, "x", model["end"])
-    assert same(np.float64(res["rr"]), np.float64(model["rr"])) and same(np.float64(res["bb"]), np.float64(model["bb"])), (what, res, model["rr"], model["bb"])
-    assert same(res["history"], model["history"]), (what, res["history"], model["history"])
+    return sh.solve(ROW, (hi, lo), b, x0, **kw)
 
 
 def signature(r):
@@ -132,35 +104,17 @@ def test_atol_decides_with_less_or_equal():
 
                 def model(atol, watch=None, rtol=0.0):
                     return mix.cg_mixed(mh, ml, b, x0=x0, dinv=dinv, watch=watch, **me.options(case, rtol=rtol, atol=atol))
+
+                def run(atol, rtol=0.0, **kw):
+                    return solve(hi, lo, b, x0, dinv=dinv, **me.options(case, rtol=rtol, atol=atol), **kw)
                 for a, k, where in me.atol_probes(model):
                     what = (case.name, m, a, k, where)
                     places.add(where)
-                    below = float(np.nextafter(a, 0.0))
-                    at, under = model(a), model(below)
-                    assert signature(at) != signature(under) or not same(at["x"], under["x"]) or at["rr"] != under["rr"], what
-                    for every in (1, 0):
-                        x, res = solve(hi, lo, b, x0, dinv=dinv, check_every=every, **me.options(case, rtol=0.0, atol=a))
-                        check(at, x, res, what)
-                        x, res = solve(hi, lo, b, x0, dinv=dinv, check_every=every, **me.options(case, rtol=0.0, atol=below))
-                        check(under, x, res, what + ("below",))
-                    # rtol^2 bb is the smaller: atol still decides, at the same place
-                    small = 2.0 ** -30
-                    while small * small * at["bb"] >= a * a:
-                        small *= 2.0 ** -30
-                    both = model(a, rtol=small)
-                    assert signature(both) == signature(at) and same(both["x"], at["x"]), what
-                    x, res = solve(hi, lo, b, x0, dinv=dinv, **me.options(case, rtol=small, atol=a))
-                    check(both, x, res, what + ("rtol below",))
-                    # ... and the reverse: atol^2 is the smaller and rtol^2 bb is a * a exactly or above: rtol decides where atol alone does not
-                    rtol = 2.0 ** 20
-                    while rtol * rtol * at["bb"] / 4 >= a * a:
-                        rtol /= 2                                                      # the smallest power of two with rtol^2 bb >= a^2
-                    tiny = a * 2.0 ** -10
-                    by_rtol, alone = model(tiny, rtol=rtol), model(tiny)
-                    assert rtol * rtol * at["bb"] >= a * a > tiny * tiny
-                    assert signature(alone) != signature(by_rtol) or not same(alone["x"], by_rtol["x"]), what
-                    x, res = solve(hi, lo, b, x0, dinv=dinv, **me.options(case, rtol=rtol, atol=tiny))
-                    check(by_rtol, x, res, what + ("rtol above",))
+
+                    def before(at, under):
+                        assert signature(at) != signature(under) or not same(at["x"], under["x"]) or at["rr"] != under["rr"], what
+                    sh.atol_ladder(model, run, check, a, k, what, before, same_end=lambda p, q: signature(p) == signature(q) and same(p["x"], q["x"]),
+                                   target=lambda at, a: a * a, converges=False)
     assert places == {"estimate", "resume:converged"}, places
 
 
@@ -247,7 +201,7 @@ def test_the_timed_launches_do_the_arithmetic_of_the_solve():
                 bd, jd = torch.from_numpy(b).to(DEV), None if dinv is None else torch.from_numpy(dinv).to(DEV)
                 xd = torch.full((high.m,), CANARY, dtype=torch.float64, device=DEV) if x0 is None else torch.from_numpy(x0).to(DEV)
                 # one run when it starts from X (a second would start from what the first left), two from x = 0
-                mean, runs = api.time_cg_mixed_iterations(hi.h, lo.h, bd, xd, 3 * e, update_every=e, x0=x0 is not None, dinv=jd, warmup=0 if x0 is not None else 1,
+                mean, runs = ROW.timer(hi.h, lo.h, bd, xd, 3 * e, update_every=e, x0=x0 is not None, dinv=jd, warmup=0 if x0 is not None else 1,
                                                           iters=1 if x0 is not None else 2)
                 torch.cuda.synchronize()
                 assert mean > 0 and (runs > 0).all() and same(xd.cpu().numpy(), want), ("timer", dinv is not None, x0 is not None)
@@ -256,7 +210,7 @@ def test_the_timed_launches_do_the_arithmetic_of_the_solve():
             again, res = solve(hi, lo, b, first, dinv=dinv, rtol=0.0, max_iterations=e, update_every=e, update_drop=1e-30)
             assert res["updates"] == 1 and not same(again, first)
             xd = torch.from_numpy(guess).to(DEV)
-            api.time_cg_mixed_iterations(hi.h, lo.h, bd, xd, e, update_every=e, x0=True, dinv=jd, warmup=1, iters=1)
+            ROW.timer(hi.h, lo.h, bd, xd, e, update_every=e, x0=True, dinv=jd, warmup=1, iters=1)
             torch.cuda.synchronize()
             assert same(xd.cpu().numpy(), again), ("timer, x0 twice", dinv is not None)
 
@@ -282,15 +236,7 @@ def arrow_pair():
 
 
 def check_arrow_executor(h, method):
-    first, long_rows = EXECUTORS[method]
-    info = h.info()
-    names = info["launch_kernels"]
-    assert info["max_row_len"] == 2049 and info["cache_blocked"] == 0 and info["far_nnz"] == 0, info
-    assert first is None or names[0] == first, names
-    if long_rows:
-        assert len(names) == 3 and names[1] in LONG_ROW_KERNELS and names[2] == "csr5_fixup_kernel", names
-    elif first != "csr_scalar_kernel":
-        assert names[-1] == "csr5_fixup_kernel" and names[0] in ("nat_group_kernel",) + LONG_ROW_KERNELS, names   # carries and their fix-up
+    sh.check_executor_layout(h.info(), method)
 
 
 @pytest.mark.parametrize("method", METHODS, ids=lambda mth: mth.name)
@@ -304,22 +250,12 @@ def test_every_executor_under_cg_mixed(method):
     if EXECUTORS[method][0] == "csr_scalar_kernel":
         return
     with pair(high, low, method, high_opts=dict(cache_block=2), low_opts=dict(cache_block=2)) as (hi, lo):
-        for h in (hi, lo):
-            info = h.info()
-            assert info["cache_blocked"] == 1 and info["launch_kernels"] in (["blk_kernel"], ["blk_wide_kernel"]), info
+        sh.check_blocked_layout(hi.info()), sh.check_blocked_layout(lo.info())
         twelve_iterations(hi, lo, high, 2)
 
 
 def check_band_executor(h, csr, pack):
-    info = h.info()
-    names = info["launch_kernels"]
-    assert info["lanes_per_row"] == 8 and info["max_row_len"] == 544, info
-    assert len(names) == 3 and names[0] == pc.TILE_KERNEL and names[1] in LONG_ROW_KERNELS and names[2] == "csr5_fixup_kernel", names
-    if pack:
-        want, flags = pc.model_packed(csr.rowptr, csr.val, 8)
-        assert flags == [True, False, True, True, True] and info["packed_nnz"] == want == info["nnz"] - (255 * 32 + 544) > 0, info
-    else:
-        assert info["packed_nnz"] == 0
+    sh.check_tile_layout(h.info(), csr, pack)
 
 
 @pytest.mark.parametrize("pack", [0, 1])

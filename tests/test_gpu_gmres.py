@@ -2,85 +2,41 @@
 
 The yardstick is the host model of tests/gmres_cases.py -- a numpy restatement of the header's arithmetic contract -- driven by the SAME
 handle's spmv(), so x, rr, bb and the history are compared BIT FOR BIT.  The one tolerance is the bound on true <r,r> / rr that
-tests/test_gmres_host.py measures on the model alone (gmres_cases.RATIO_BOUND)."""
-import ctypes as C
+tests/test_gmres_host.py measures on the model alone (gmres_cases.RATIO_BOUND).  The bodies that the solvers share are in
+tests/solve_harness.py."""
+import functools
 
 import numpy as np
 import pytest
 
 import cg_cases as cgc
 import gmres_cases as gc
-from spmv_amd import api, build
+import solve_harness as sh
+from solve_harness import BIG, CANARY, DEV, DTYPES, E_ARG, METHODS, handle, same_bits
+from spmv_amd import api
 
 pytestmark = pytest.mark.gpu
 
-M = api.SPMV_METHODS
-DTYPES = [np.float64, np.float32]
-E_ARG, E_NOSTATE = 3, 5
-DEV = "cuda:0"
-CANARY = -7.25
+ROW = sh.ROWS["gmres"]
 G = gc.GROUP
-# slot, step and workgroup edges of the dot: P = 1, 2 and 3 workgroups, two steps per workgroup
-SIZES = [1, 3, 4, 5, 1023, 1024, 1025, 2049]
+SIZES = sh.SIZES[:-1]            # the dot's edges; BIG has a test of its own
 # a group boundary of the multi-dot kernel (G, G + 1) and the maximum
 RESTARTS = [1, 2, 3, G, G + 1, gc.RESTART_MAX]
-BIG = 1024 * 1024 + 1            # P = 1024, L = 2048: empty workgroups
+check_same_end = functools.partial(sh.check_same_end, ROW)
+check_against = functools.partial(sh.check_against, ROW)
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _lib():
-    build.build()
-    lib = api.load()
-    assert lib.spmv_hip_device_count() > 0, "GPU tests need a device"
-    return lib
-
-
-def handle(csr, method=M.Method_Parallel, way=api.VECTORIZED_WAY.VECTOR_HIP, **opts):
-    for key, v in opts.items():
-        api.set_thread_option(key, v)
-    try:
-        return api.Handle(csr.m, csr.n, csr.rowptr, csr.colidx, csr.val, method, way=way)
-    finally:
-        api.clear_thread_options()
-
-
-def multiply_of(h):
-    """the model's multiply: this handle's spmv() on host vectors"""
-    def multiply(x):
-        return h.spmv(np.ascontiguousarray(x), np.empty_like(x))
-    return multiply
+    return sh.library()
 
 
 def solve(h, b, restart, x0=None, **kw):
-    """through host pointers -> (x, result dict with history)"""
-    x = np.full(b.size, CANARY, dtype=b.dtype) if x0 is None else x0.copy()
-    x, res, hist = h.gmres(b, x, restart, x0=x0 is not None, history=True, **kw)
-    res["history"] = hist
-    return x, res
+    return sh.solve(ROW, h, b, x0, restart=restart, **kw)
 
 
-def same_bits(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
-
-
-def check_same_end(model, x, res):
-    """a run with the model's own budget, whatever way the model ended"""
-    assert (res["status"], res["iterations"]) == (model["status"], model["iterations"]), model["end"]
-    assert same_bits(x, model["x"]), model["end"]
-    if model["end"] != "begin:nonfinite":
-        assert res["bb"] == model["bb"] and res["rr"] == model["rr"] and same_bits(res["history"], model["history"]), model["end"]
-
-
-def check_against(model, k, x, res):
-    """a run with max_iterations = k against ONE model run with a larger budget, however that ended: iterate k of it while it goes on, its own
-    end from there on"""
-    if k >= model["iterations"]:
-        assert model["status"] != gc.MAX_ITERATIONS or k == model["iterations"]
-        return check_same_end(model, x, res)
-    assert (res["status"], res["iterations"]) == (gc.MAX_ITERATIONS, k)
-    assert same_bits(x, model["iterates"][k])
-    assert res["bb"] == model["bb"] and res["rr"] == model["history"][k] and same_bits(res["history"], model["history"][:k + 1])
+def model_of(h, b, restart, **kw):
+    return ROW.model(h, b, restart, **kw)
 
 
 def budgets(restart):
@@ -122,9 +78,8 @@ def test_bits_against_the_model(m, restart, dtype):
     ones = np.ones(m, dtype=dtype)
     top = 2 * restart + 1
     with handle(csr) as h:
-        mul = multiply_of(h)
-        plain = gc.gmres(mul, b, restart, max_iterations=top)
-        pre = gc.gmres(mul, b, restart, x0=guess, dinv=jac, max_iterations=top)
+        plain = model_of(h, b, restart, max_iterations=top)
+        pre = model_of(h, b, restart, x0=guess, dinv=jac, max_iterations=top)
         for k in budgets(restart):
             x_none, r_none = solve(h, b, restart, rtol=0.0, max_iterations=k)
             check_against(plain, k, x_none, r_none)
@@ -141,7 +96,7 @@ def test_bits_with_empty_workgroups(restart, dtype):
     rng = np.random.default_rng(restart)
     b, guess, jac = gc.rhs(BIG, dtype), rng.uniform(-1, 1, BIG).astype(dtype), rng.uniform(0.5, 1.5, BIG).astype(dtype)
     with handle(csr) as h:
-        pre = gc.gmres(multiply_of(h), b, restart, x0=guess, dinv=jac, max_iterations=restart + 1)
+        pre = model_of(h, b, restart, x0=guess, dinv=jac, max_iterations=restart + 1)
         for k in (0, restart - 1, restart + 1):
             x, res = solve(h, b, restart, guess, rtol=0.0, max_iterations=k, dinv=jac)
             check_against(pre, k, x, res)
@@ -149,14 +104,9 @@ def test_bits_with_empty_workgroups(restart, dtype):
 
 # ----------------------------------------------------------------------------- 2. every method
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("method", [mth for mth in M if mth != M.Method_Total_Size])
+@pytest.mark.parametrize("method", METHODS)
 def test_every_method_has_the_bits_of_the_model_on_its_own_spmv(method, dtype):
-    csr = gc.upwind(32, dtype)
-    b = gc.rhs(csr.m, dtype, 1)
-    with handle(csr, method) as h:
-        model = gc.gmres(multiply_of(h), b, 5, max_iterations=12)
-        x, res = solve(h, b, 5, rtol=0.0, max_iterations=12)
-        check_against(model, 12, x, res)
+    sh.every_method(ROW, method, dtype, restart=5)
 
 
 # ----------------------------------------------------------------------------- 3. convergence
@@ -166,7 +116,7 @@ def test_convergence_with_the_models_iteration_count(name, dtype, rtol, restart)
     csr = gc.upwind(32, dtype) if name == "upwind32" else gc.nonsym_dominant(4096, dtype)
     b = gc.rhs(csr.m, dtype)
     with handle(csr) as h:
-        model = gc.gmres(multiply_of(h), b, restart, rtol=rtol, max_iterations=400)
+        model = model_of(h, b, restart, rtol=rtol, max_iterations=400)
         x, res = solve(h, b, restart, rtol=rtol, max_iterations=400)
     assert model["status"] == gc.CONVERGED
     assert res["status_name"] == "converged"
@@ -195,7 +145,7 @@ def test_check_every_changes_nothing(dtype):
     rtol = 1e-8 if dtype == np.float64 else 1e-4
     restart = 5
     with handle(csr) as h:
-        model = gc.gmres(multiply_of(h), b, restart, rtol=rtol, max_iterations=600)
+        model = model_of(h, b, restart, rtol=rtol, max_iterations=600)
         assert model["status"] == gc.CONVERGED and 2 * restart < model["iterations"] < 600
         for every in (1, 3, restart, 64, 0):
             x, res = solve(h, b, restart, rtol=rtol, max_iterations=600, check_every=every)
@@ -213,7 +163,7 @@ def test_check_every_changes_nothing(dtype):
 def test_every_end(dtype):
     def both(csr, b, restart, x0=None, **kw):
         with handle(csr) as h:
-            model = gc.gmres(multiply_of(h), b, restart, x0=x0, **kw)
+            model = model_of(h, b, restart, x0=x0, **kw)
             for every in (1, 0):
                 x, res = solve(h, b, restart, x0, check_every=every, **kw)
                 check_same_end(model, x, res)
@@ -255,91 +205,25 @@ def test_every_end(dtype):
 
 
 def test_m_zero_is_converged():
-    empty = gc.synth.CSR(0, 0, np.zeros(1, dtype=np.int32), np.zeros(0, dtype=np.int32), np.zeros(0))
-    with handle(empty) as h:
-        rc, res = api.gmres(h.h, 0, empty.rowptr, empty.colidx, empty.val, None, None, 5, max_iterations=5)
-    assert rc == 0 and (res["status"], res["iterations"], res["rr"], res["bb"]) == (gc.CONVERGED, 0, 0.0, 0.0)
+    sh.m_zero_is_converged(ROW, restart=5)
 
 
 # ----------------------------------------------------------------------------- 6. pointers
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("m", [1025, 70001])
 def test_host_device_and_unaligned_pointers_give_the_same_bits(m, dtype):
-    import torch
-    csr = gc.tri_ns(m, dtype)
     rng = np.random.default_rng(m + 1)
     b, guess, jac = gc.rhs(m, dtype, 4), rng.uniform(-1, 1, m).astype(dtype), rng.uniform(0.5, 1.5, m).astype(dtype)
-    pad = 16 // np.dtype(dtype).itemsize                 # canaries of one 16-byte unit each side keep X aligned; + 1 element: not
-    restart, budget = 3, 7
-    with handle(csr) as h:
-        for x0 in (None, guess):
-            want, wres = solve(h, b, restart, x0, rtol=0.0, max_iterations=budget, dinv=jac)
-            assert wres["iterations"] == budget
-            for shift_b, shift_x, shift_d in ((0, 0, 0), (1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 1)):
-                bd = torch.zeros(m + 1, dtype=torch.from_numpy(b).dtype, device=DEV)[shift_b:shift_b + m]
-                bd.copy_(torch.from_numpy(b))
-                jd = torch.zeros(m + 1, dtype=bd.dtype, device=DEV)[shift_d:shift_d + m]
-                jd.copy_(torch.from_numpy(jac))
-                buf = torch.full((m + 2 * pad + 1,), CANARY, dtype=bd.dtype, device=DEV)
-                xd = buf[pad + shift_x:pad + shift_x + m]
-                assert (bd.data_ptr() % 16 != 0) == bool(shift_b) and (xd.data_ptr() % 16 != 0) == bool(shift_x)
-                if x0 is not None:
-                    xd.copy_(torch.from_numpy(x0))
-                got, res, hist = h.gmres(bd, xd, restart, x0=x0 is not None, rtol=0.0, max_iterations=budget, dinv=jd, history=True)
-                torch.cuda.synchronize()
-                assert got is xd and same_bits(xd.cpu().numpy(), want), (shift_b, shift_x, shift_d)
-                assert same_bits(hist, wres["history"]) and res["rr"] == wres["rr"]
-                out = buf.cpu().numpy()
-                assert (out[:pad + shift_x] == CANARY).all() and (out[pad + shift_x + m:] == CANARY).all(), "written outside X"
-            # mixed: device B, host X, device Dinv
-            xh = np.full(m, CANARY, dtype=dtype) if x0 is None else x0.copy()
-            h.gmres(torch.from_numpy(b).to(DEV), xh, restart, x0=x0 is not None, rtol=0.0, max_iterations=budget, dinv=torch.from_numpy(jac).to(DEV))
-            assert same_bits(xh, want)
+    sh.pointers_give_the_same_bits(ROW, gc.tri_ns(m, dtype), b, guess, dict(restart=3, rtol=0.0, max_iterations=7), lambda res: res["iterations"] == 7, dinv=jac,
+                                   shift_dinv=True)
 
 
 # ----------------------------------------------------------------------------- 7. handle rules
 def test_argument_errors_leave_x_untouched(_lib):
-    lib = _lib
-    csr = gc.tri_ns(300)
-    b = gc.rhs(csr.m, np.float64)
-    x = np.full(csr.m, CANARY)
-    rp, ci, va = csr.rowptr, csr.colidx, csr.val
-
-    def call(h, opt, res, B=b, X=x, restart=5):
-        lib.spmv_hip_clear_error()
-        rc = lib.spmv_hip_gmres(h, csr.m, api._ptr(rp), api._ptr(ci), api._ptr(va), api._ptr(B), api._ptr(X), restart, opt, res)
-        assert lib.spmv_hip_last_error() == rc
-        lib.spmv_hip_clear_error()
-        return rc
-
-    def options(**kw):
-        base = dict(rtol=1e-8, atol=0.0, max_iterations=10, check_every=0, use_x0=0)
-        base.update(kw)
-        return C.byref(api.spmv_hip_cg_options(**base))
-
-    res = C.byref(api.spmv_hip_cg_result())
-    with handle(csr) as h:
-        assert call(h.h, None, res) == E_ARG and call(h.h, options(), None) == E_ARG
-        assert call(h.h, options(), res, B=None) == E_ARG and call(h.h, options(), res, X=None) == E_ARG
-        for bad in (dict(max_iterations=-1), dict(check_every=-1), dict(rtol=-1e-3), dict(atol=-1.0), dict(rtol=float("nan")), dict(atol=float("nan"))):
-            assert call(h.h, options(**bad), res) == E_ARG, bad
+    def restarts(call, options, res, h):
         for restart in (0, -1, gc.RESTART_MAX + 1):
             assert call(h.h, options(), res, restart=restart) == E_ARG, restart
-        assert call(None, options(), res) == E_ARG
-        assert (x == CANARY).all()
-        assert call(h.h, options(), res, restart=gc.RESTART_MAX) == 0 and not (x == CANARY).any()      # the same call with good arguments runs
-    x[:] = CANARY
-    wide = gc.synth.CSR(csr.m, csr.m + 1, rp, ci, va)                           # m != n at create
-    with handle(wide) as h:
-        assert call(h.h, options(), res) == E_ARG
-    for key, way in (("gpus", api.VECTORIZED_WAY.VECTOR_HIP), ("host_rows", api.VECTORIZED_WAY.VECTOR_NONE)):
-        with handle(csr, M.Method_Serial, way, **{key: 1}) as h:
-            assert call(h.h, options(), res) == E_ARG, key
-    h = handle(csr)
-    api.spmv_clear_handle(h.h)
-    assert call(h.h, options(), res) == E_NOSTATE
-    h.close()
-    assert (x == CANARY).all()
+    sh.argument_errors(ROW, _lib, gc.tri_ns(300), more=restarts, good=dict(restart=gc.RESTART_MAX))
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -355,22 +239,21 @@ def test_workspace_and_timer(dtype):
         bd = torch.from_numpy(b).to(DEV)
         xd, res = h.gmres(bd, restart=5, rtol=1e-6, max_iterations=300)            # device operands: no staging buffer is added
         assert res["status"] == gc.CONVERGED and xd.device.type == "cuda"
-        small = gc.workspace_bytes(csr.m, item, 5)
+        small = ROW.workspace(csr.m, item, 5)
         assert h.info()["device_bytes"] - before == small
         x2, res2 = h.gmres(bd, restart=3, rtol=1e-6, max_iterations=300)           # a smaller restart runs in the workspace that is there
         assert h.info()["device_bytes"] == before + small and res2["iterations"] > 0
         x3, res3 = h.gmres(bd, restart=9, rtol=1e-6, max_iterations=300)           # a larger one allocates it anew
-        large = gc.workspace_bytes(csr.m, item, 9)
+        large = ROW.workspace(csr.m, item, 9)
         assert h.info()["device_bytes"] == before + large and res3["iterations"] > 0
         x4, res4 = h.gmres(bd, restart=5, rtol=1e-6, max_iterations=300)           # ... and the bits do not depend on the workspace's size
         assert same_bits(x4.cpu().numpy(), xd.cpu().numpy()) and res4 == res
-        mean, runs = api.time_gmres_iterations(h.h, bd, xd, 12, restart=5, warmup=1, iters=3)
+        mean, runs = ROW.timer(h.h, bd, xd, 12, restart=5, warmup=1, iters=3)
         assert mean > 0 and runs.shape == (3,) and (runs > 0).all()
         assert h.info()["device_bytes"] == before + large
         xc = torch.empty_like(bd)
         h.bicgstab(bd, xc, rtol=1e-6, max_iterations=5)                            # the other solvers' workspaces are their own
-        vec = (csr.m * item + 255) // 256 * 256
-        assert h.info()["device_bytes"] == before + large + 6 * vec + 8 * 1024 * 8 + 256
+        assert h.info()["device_bytes"] == before + large + sh.ROWS["bicgstab"].workspace(csr.m, item)
         assert same_bits(h.spmv(b, np.empty_like(b)), y0)                          # spmv() computes what it did before the solves
         # copies of the CSR arrays: spmv() re-inspects, which frees every workspace with everything else on the device (what clear and destroy
         # do as well) and leaves what `before` saw; the next solve allocates the workspace again, for the restart it is called with
@@ -407,16 +290,4 @@ def test_mixed_company(dtype):
 
 
 def test_a_reordered_handle_solves_the_permuted_system():
-    csr = gc.nonsym_dominant(4096, np.float64)
-    b = gc.rhs(csr.m, np.float64, 6)
-    with handle(csr, reorder=1) as h:
-        perm = h.index
-        assert perm is not None and sorted(perm.tolist()) == list(range(csr.m))
-        bp = np.ascontiguousarray(b[perm])                                         # XX[i] = X[index[i]], as for spmv()
-        model = gc.gmres(multiply_of(h), bp, 10, rtol=1e-10, max_iterations=200)
-        xp, res = solve(h, bp, 10, rtol=1e-10, max_iterations=200)
-    assert res["status"] == gc.CONVERGED
-    check_same_end(model, xp, res)
-    x = np.empty_like(xp)
-    x[perm] = xp
-    assert gc.true_residual(csr, b, x) <= 1e-9
+    sh.a_reordered_handle_solves_the_permuted_system(ROW, restart=10)

@@ -6,26 +6,22 @@ compared bit for bit and no tolerance appears anywhere.  The one freedom: a NaN 
 tests/test_gpu_gmres.py, rr, bb and the history are not compared where the solve ends in begin:nonfinite.  The cases come from
 tests/gmres_end_cases.py, whose every line tests/test_gmres_ends_host.py proves on the CPU first; here each case must also reach the (status,
 iterations, end) it declares under the handle's own multiply -- bits that match a model which ends elsewhere would mean the INPUT is wrong,
-not the kernel."""
+not the kernel.  The bodies that the solvers share are in tests/solve_harness.py."""
+import functools
+
 import numpy as np
 import pytest
 
-import cg_cases as cgc
 import gmres_cases as gc
 import gmres_end_cases as ge
-import packed_cases as pc
 import solve_end_cases as sec
-from spmv_amd import api, build
-from test_gpu_solve_ends import EXECUTORS, LONG_ROW_KERNELS, METHODS, handle, multiply_of, same
+import solve_harness as sh
+from solve_harness import CANARY, DEV, EVERY, METHODS, NAMES, ended, handle, multiply_of, run_id, same
 
 pytestmark = pytest.mark.gpu
 
-M = api.SPMV_METHODS
-DEV = "cuda:0"
-CANARY = -7.25
-NAMES = {np.float32: "f32", np.float64: "f64"}
+ROW = sh.ROWS["gmres"]
 G = gc.GROUP
-EVERY = (1, 2, 3, 0, 64)           # check_every: the end falls first, in the middle and last in an enqueued batch; and the case's restart
 RUNS = [(c, d) for c in ge.CASES for d in c.dtypes]
 HISTORY_RUNS = [(c, d) for c in ge.HISTORY_CASES for d in ge.BOTH]
 # the runs of the atol test: exact or not, some estimate on their way is the square of a double (tests/test_gmres_ends_host.py looks first)
@@ -34,43 +30,20 @@ ATOL_CASES = ("g_begin_conv", "g_cyclic_2", "g_restart_zero_64_c2s3", "g_restart
 
 @pytest.fixture(scope="module", autouse=True)
 def _lib():
-    build.build()
-    lib = api.load()
-    assert lib.spmv_hip_device_count() > 0, "GPU tests need a device"
-    return lib
+    return sh.library()
+
+
+check = functools.partial(sh.check, ROW)
 
 
 def solve(h, b, restart, x0=None, **kw):
-    """through host pointers, with a canary in X when there is no guess -> (x, result dict with history)"""
-    x = np.full(b.size, CANARY, dtype=b.dtype) if x0 is None else x0.copy()
-    kw.setdefault("rtol", 0.0)
-    x, res, hist = h.gmres(b, x, restart, x0=x0 is not None, history=True, **kw)
-    res["history"] = hist
-    return x, res
-
-
-def check(model, x, res, what=None):
-    """a run against a model run with the same arguments, however either ended"""
-    assert (res["status"], res["iterations"]) == (model["status"], model["iterations"]), (what, res, model["end"])
-    assert same(x, model["x"]), (what, "x", model["end"])
-    if model["end"] == "begin:nonfinite":
-        return
-    assert same(np.float64(res["rr"]), np.float64(model["rr"])) and same(np.float64(res["bb"]), np.float64(model["bb"])), (what, res, model["rr"], model["bb"])
-    assert same(res["history"], model["history"]), (what, res["history"], model["history"])
-
-
-def ended(r):
-    return r["status"], r["iterations"], r["end"]
-
-
-def run_id(run):
-    return f"{run[0].name}-{NAMES[run[1]]}"
+    return sh.solve0(ROW, h, b, x0, restart=restart, **kw)
 
 
 def model_of(h, case, b, dinv, x0, **kw):
     kw.setdefault("atol", case.atol)
     kw.setdefault("max_iterations", case.budget)
-    return gc.gmres(multiply_of(h), b, case.restart, x0=x0, dinv=dinv, **kw)
+    return ROW.model(h, b, case.restart, x0=x0, dinv=dinv, **kw)
 
 
 # ----------------------------------------------------------------------------- 1. every end, anywhere in a batch, at every budget edge
@@ -87,17 +60,14 @@ def test_every_end_at_every_place_in_a_batch(run):
             for every in EVERY + (R,):
                 x, res = solve(h, b, R, x0, dinv=dinv, atol=case.atol, max_iterations=case.budget, check_every=every)
                 check(model, x, res, what + (every,))
-            for budget in (k - 1, k, k + 1):
-                if budget < 0:
-                    continue
-                short = model_of(h, case, b, dinv, x0, max_iterations=budget)
+
+            def expect(budget, short):
                 if budget < k or (budget == k and ge.found_making_a_step(case)) or case.end == "budget":
                     assert ended(short) == (gc.MAX_ITERATIONS, budget, "budget"), (what, budget)       # found while making step k + 1: not with a budget of k
                 else:
                     assert ended(short) == ended(model), (what, budget)
-                for every in (0, 1):
-                    x, res = solve(h, b, R, x0, dinv=dinv, atol=case.atol, max_iterations=budget, check_every=every)
-                    check(short, x, res, what + (budget, every))
+            sh.budget_edges(k, lambda budget: model_of(h, case, b, dinv, x0, max_iterations=budget),
+                            lambda budget, every: solve(h, b, R, x0, dinv=dinv, atol=case.atol, max_iterations=budget, check_every=every), expect, what, check)
 
 
 @pytest.mark.parametrize("run", HISTORY_RUNS, ids=run_id)
@@ -152,36 +122,17 @@ def test_atol_decides_with_less_or_equal(dtype):
 
                 def model(atol, rtol=0.0):
                     return gc.gmres(mul, b, R, x0=x0, dinv=dinv, rtol=rtol, atol=atol, max_iterations=case.budget)
+
+                def run(**kw):
+                    return solve(h, b, R, x0, dinv=dinv, max_iterations=case.budget, **kw)
                 probes = sec.atol_probes(model)
                 for a, k, end in dict.fromkeys(probes[:2] + probes[-2:]):       # the first two and the last two places
                     what = (case.name, m, a, k, end)
                     places.add((end, "later" if k > R else "first"))
-                    below = float(np.nextafter(a, 0.0))
-                    at, under = model(a), model(below)
-                    assert (at["iterations"], at["end"], at["status"]) == (k, end, gc.CONVERGED) and (under["iterations"], under["end"]) != (k, end), what
-                    for every in (1, 0):
-                        x, res = solve(h, b, R, x0, dinv=dinv, atol=a, max_iterations=case.budget, check_every=every)
-                        check(at, x, res, what)
-                        x, res = solve(h, b, R, x0, dinv=dinv, atol=below, max_iterations=case.budget, check_every=every)
-                        check(under, x, res, what + ("below",))
-                    # rtol^2 bb is the smaller: atol still decides, at the same place
-                    small = 2.0 ** -30
-                    while small * small * at["bb"] >= a * a:
-                        small *= 2.0 ** -30
-                    both = model(a, small)
-                    assert ended(both) == ended(at)
-                    x, res = solve(h, b, R, x0, dinv=dinv, rtol=small, atol=a, max_iterations=case.budget)
-                    check(both, x, res, what + ("rtol below",))
-                    # ... and the reverse: atol^2 is the smaller, rtol decides: the run ends where atol alone does not end it
-                    rtol = 2.0 ** 20
-                    while rtol * rtol * at["bb"] / 4 >= at["rr"]:
-                        rtol /= 2                                                      # the smallest power of two with rtol^2 bb >= rr
-                    low = a * 2.0 ** -10
-                    by_rtol, alone = model(low, rtol), model(low)
-                    assert rtol * rtol * at["bb"] >= at["rr"] > low * low and by_rtol["status"] == gc.CONVERGED and by_rtol["iterations"] <= k
-                    assert ended(alone) != ended(by_rtol), what
-                    x, res = solve(h, b, R, x0, dinv=dinv, rtol=rtol, atol=low, max_iterations=case.budget)
-                    check(by_rtol, x, res, what + ("rtol above",))
+
+                    def before(at, under):
+                        assert (at["iterations"], at["end"], at["status"]) == (k, end, gc.CONVERGED) and (under["iterations"], under["end"]) != (k, end), what
+                    sh.atol_ladder(model, run, check, a, k, what, before)
     assert {p[0] for p in places} == {"begin:converged", "rotate:converged"} and ("rotate:converged", "later") in places, places
 
 
@@ -265,26 +216,26 @@ def test_the_timed_launches_do_the_arithmetic_of_the_solve(dtype):
             assert (res["status"], res["iterations"]) == (gc.MAX_ITERATIONS, 2 * R) and same(want, model["iterates"][2 * R])
             bd, jd = torch.from_numpy(b).to(DEV), None if dinv is None else torch.from_numpy(dinv).to(DEV)
             xd = torch.full((csr.m,), CANARY, dtype=bd.dtype, device=DEV)
-            mean, runs = api.time_gmres_iterations(h.h, bd, xd, 2 * R, restart=R, dinv=jd, warmup=1, iters=2)   # every run starts from x = 0
+            mean, runs = ROW.timer(h.h, bd, xd, 2 * R, restart=R, dinv=jd, warmup=1, iters=2)   # every run starts from x = 0
             torch.cuda.synchronize()
             assert mean > 0 and runs.shape == (2,) and same(xd.cpu().numpy(), want), ("timer", dinv is not None)
             # a budget that is no multiple of R leaves the last finished cycle's x: gmres_finish is not part of the timer
             for budget in (2 * R + 2, 2 * R + 1, R - 1):
                 xd.fill_(CANARY)
-                api.time_gmres_iterations(h.h, bd, xd, budget, restart=R, dinv=jd, warmup=0, iters=1)
+                ROW.timer(h.h, bd, xd, budget, restart=R, dinv=jd, warmup=0, iters=1)
                 torch.cuda.synchronize()
                 assert same(xd.cpu().numpy(), model["iterates"][budget // R * R]) and not same(model["iterates"][budget], model["iterates"][budget // R * R]), ("timer", budget)
             from_guess, res = solve(h, b, R, guess, dinv=dinv, max_iterations=2 * R)
             assert res["iterations"] == 2 * R and not same(from_guess, want)
             xd.copy_(torch.from_numpy(guess))
-            api.time_gmres_iterations(h.h, bd, xd, 2 * R, restart=R, x0=True, dinv=jd, warmup=0, iters=1)       # one run: from the guess in X
+            ROW.timer(h.h, bd, xd, 2 * R, restart=R, x0=True, dinv=jd, warmup=0, iters=1)       # one run: from the guess in X
             torch.cuda.synchronize()
             assert same(xd.cpu().numpy(), from_guess), ("timer, x0", dinv is not None)
             # a second run with use_x0 starts from what the first left in X; for GMRES(R) two runs of R ARE one run of 2 R: the restart forgets
             # everything but x, so the solve from the first run's x is the second cycle
             again, _ = solve(h, b, R, solve(h, b, R, guess, dinv=dinv, max_iterations=R)[0], dinv=dinv, max_iterations=R)
             xd.copy_(torch.from_numpy(guess))
-            api.time_gmres_iterations(h.h, bd, xd, R, restart=R, x0=True, dinv=jd, warmup=1, iters=1)
+            ROW.timer(h.h, bd, xd, R, restart=R, x0=True, dinv=jd, warmup=1, iters=1)
             torch.cuda.synchronize()
             assert same(xd.cpu().numpy(), again) and same(again, from_guess), ("timer, x0 twice", dinv is not None)
 
@@ -293,57 +244,16 @@ def test_the_timed_launches_do_the_arithmetic_of_the_solve(dtype):
 def cycles_and_three(h, csr, dtype, seed):
     """R = G + 1, so that gmres_dots and gmres_sub_dots take their second trip, for 2 R + 3 iterations without and with a guess and Jacobi,
     against the model on this handle's spmv()"""
-    rng = np.random.default_rng(seed)
-    b, guess = gc.rhs(csr.m, dtype, seed), rng.uniform(-1, 1, csr.m).astype(dtype)
-    jac = (1.0 / cgc.diagonal(csr).astype(np.float64)).astype(dtype)
-    mul = multiply_of(h)
-    R = G + 1
-    for x0, dinv in ((None, None), (guess, jac)):
-        model = gc.gmres(mul, b, R, x0=x0, dinv=dinv, max_iterations=2 * R + 3)
-        assert model["iterations"] == 2 * R + 3 and np.isfinite(model["x"]).all(), ended(model)
-        x, res = solve(h, b, R, x0, dinv=dinv, max_iterations=2 * R + 3)
-        check(model, x, res, (x0 is not None,))
+    sh.guess_and_jacobi_iterations(ROW, h, csr, dtype, seed, 2 * (G + 1) + 3, restart=G + 1)
 
 
 @pytest.mark.parametrize("dtype", ge.BOTH, ids=NAMES.get)
 @pytest.mark.parametrize("method", METHODS, ids=lambda mth: mth.name)
 def test_every_executor_under_gmres(method, dtype):
-    """the arrow matrices of tests/test_gpu_solve_ends.py: a row longer than any long-row threshold, a carry across every CSR5 / nnz-split
-    tile boundary.  As built, and on the row-block x column-slab executor (cache_block = 2; CSR-scalar schedules never take it)"""
     csr = sec.arrow(2049, dtype, symmetric=False)
-    first, long_rows = EXECUTORS[method]
-    with handle(csr, method) as h:
-        info = h.info()
-        names = info["launch_kernels"]
-        assert info["max_row_len"] == 2049 and info["cache_blocked"] == 0 and info["far_nnz"] == 0, info
-        assert first is None or names[0] == first, names
-        if long_rows:
-            assert len(names) == 3 and names[1] in LONG_ROW_KERNELS and names[2] == "csr5_fixup_kernel", names
-        elif first != "csr_scalar_kernel":
-            assert names[-1] == "csr5_fixup_kernel" and names[0] in ("nat_group_kernel",) + LONG_ROW_KERNELS, names   # carries and their fix-up
-        cycles_and_three(h, csr, dtype, 1)
-    if first == "csr_scalar_kernel":
-        return
-    with handle(csr, method, cache_block=2) as h:
-        info = h.info()
-        assert info["cache_blocked"] == 1 and info["launch_kernels"] in (["blk_kernel"], ["blk_wide_kernel"]), info
-        cycles_and_three(h, csr, dtype, 2)
+    sh.every_executor(csr, method, lambda h, seed: cycles_and_three(h, csr, dtype, seed))
 
 
 @pytest.mark.parametrize("dtype", ge.BOTH, ids=NAMES.get)
 def test_the_long_row_launch_beside_the_tile_kernel_and_packed_tiles(dtype):
-    """rows of 32 aligned entries at 8 lanes per row run on the CSR-vector TILE kernel; row 300 (544 entries > long_thr = 512) goes to the
-    long-row launch behind it.  fp64 also with pack_values = 1: every tile but row 300's streams 7-byte values"""
-    csr = sec.band32(1280, dtype, long_row=300)
-    for pack in (0, 1) if dtype == np.float64 else (0,):
-        with handle(csr, M.Method_Parallel, lanes_per_row=8, pack_values=pack) as h:
-            info = h.info()
-            names = info["launch_kernels"]
-            assert info["lanes_per_row"] == 8 and info["max_row_len"] == 544, info
-            assert len(names) == 3 and names[0] == pc.TILE_KERNEL and names[1] in LONG_ROW_KERNELS and names[2] == "csr5_fixup_kernel", names
-            if pack:
-                want, flags = pc.model_packed(csr.rowptr, csr.val, 8)
-                assert flags == [True, False, True, True, True] and info["packed_nnz"] == want == info["nnz"] - (255 * 32 + 544) > 0, info
-            else:
-                assert info["packed_nnz"] == 0
-            cycles_and_three(h, csr, dtype, 3 + pack)
+    sh.the_long_row_launch_beside_the_tile_kernel(dtype, lambda h, csr, seed: cycles_and_three(h, csr, dtype, seed))

@@ -1,23 +1,22 @@
 """GPU: spmv_hip_lsqr, the least-squares solve for a matrix of any shape that stays on the device (include/spmv_hip.h).
 
 The yardstick is the host model of tests/lsqr_cases.py -- a numpy restatement of the header's arithmetic contract -- driven by the SAME
-handle's spmv() and spmv_transpose(), so x, rr, bb, ar, anorm and the history are compared BIT FOR BIT.  No tolerance enters."""
-import ctypes as C
+handle's spmv() and spmv_transpose(), so x, rr, bb, ar, anorm and the history are compared BIT FOR BIT.  No tolerance enters.
+The bodies that the solvers share are in tests/solve_harness.py."""
+import functools
 
 import numpy as np
 import pytest
 
 import cg_cases as cgc
 import lsqr_cases as lc
-from spmv_amd import api, build, synth
+import solve_harness as sh
+from solve_harness import CANARY, DEV, DTYPES, E_ARG, M, handle, same_bits
+from spmv_amd import api, synth
 
 pytestmark = pytest.mark.gpu
 
-M = api.SPMV_METHODS
-DTYPES = [np.float64, np.float32]
-E_ARG, E_NOSTATE = 3, 5
-DEV = "cuda:0"
-CANARY = -7.25
+ROW = sh.ROWS["lsqr"]
 # (m, n) -> the model's end without and with (an initial guess and damp = 0.5), under rtol = ls_tol = TOL: a consistent system converges (wide,
 # undamped), an inconsistent one meets the normal-equations test once its Krylov space is exhausted, the largest runs out of budget
 SHAPES = {
@@ -38,67 +37,13 @@ def tol_of(dtype):
 
 @pytest.fixture(scope="module", autouse=True)
 def _lib():
-    build.build()
-    lib = api.load()
-    assert lib.spmv_hip_device_count() > 0, "GPU tests need a device"
-    return lib
+    return sh.library()
 
 
-def handle(csr, method=M.Method_Parallel, way=api.VECTORIZED_WAY.VECTOR_HIP, **opts):
-    for key, v in opts.items():
-        api.set_thread_option(key, v)
-    try:
-        return api.Handle(csr.m, csr.n, csr.rowptr, csr.colidx, csr.val, method, way=way)
-    finally:
-        api.clear_thread_options()
-
-
-def multiplies_of(h):
-    """the model's two multiplies: this handle's spmv() and spmv_transpose() on host vectors"""
-    def multiply(v):
-        return h.spmv(np.ascontiguousarray(v), np.empty(h.m, dtype=v.dtype))
-
-    def multiply_t(u):
-        return h.spmv_transpose(np.ascontiguousarray(u))
-    return multiply, multiply_t
-
-
-def model_of(h, b, **kw):
-    return lc.lsqr(*multiplies_of(h), b, h.n, **kw)
-
-
-def solve(h, b, x0=None, **kw):
-    """through host pointers -> (x, result dict with history)"""
-    x = np.full(h.n, CANARY, dtype=b.dtype) if x0 is None else x0.copy()
-    x, res, hist = h.lsqr(b, x, x0=x0 is not None, history=True, **kw)
-    res["history"] = hist
-    return x, res
-
-
-def same_bits(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
-
-
-def check_same_end(model, x, res):
-    """a run with the model's own budget, whatever way the model ended"""
-    assert (res["status"], res["iterations"]) == (model["status"], model["iterations"]), model["end"]
-    assert same_bits(x, model["x"]), model["end"]
-    assert (res["ar"], res["anorm"]) == (model["ar"], model["anorm"]), model["end"]
-    if model["end"] != "begin:nonfinite":
-        assert res["bb"] == model["bb"] and same_bits(np.float64(res["rr"]), np.float64(model["rr"])) and same_bits(res["history"], model["history"]), model["end"]
-
-
-def check_against(model, k, x, res):
-    """a run with max_iterations = k against ONE model run with a larger budget, however that ended: iterate k of it while it goes on, its own
-    end from there on"""
-    if k >= model["iterations"]:
-        assert model["status"] != lc.MAX_ITERATIONS or k == model["iterations"]
-        return check_same_end(model, x, res)
-    assert (res["status"], res["iterations"]) == (lc.MAX_ITERATIONS, k)
-    assert same_bits(x, model["iterates"][k])
-    assert res["bb"] == model["bb"] and res["rr"] == model["history"][k] and same_bits(res["history"], model["history"][:k + 1])
-    assert (res["ar"], res["anorm"]) == model["estimates"][k]
+model_of = ROW.model
+solve = functools.partial(sh.solve, ROW)
+check_same_end = functools.partial(sh.check_same_end, ROW)
+check_against = functools.partial(sh.check_against, ROW)
 
 
 # ----------------------------------------------------------------------------- 1. bits against the model
@@ -203,14 +148,10 @@ def test_every_end(dtype):
 
 
 def test_no_rows_no_entries():
-    none = synth.CSR(0, 0, np.zeros(1, dtype=np.int32), np.zeros(0, dtype=np.int32), np.zeros(0))
-    with handle(none) as h:
-        rc, res = api.lsqr(h.h, 0, none.rowptr, none.colidx, none.val, None, None, max_iterations=5)
-    assert rc == 0 and (res["status"], res["iterations"], res["rr"], res["bb"]) == (lc.CONVERGED, 0, 0.0, 0.0)
-    m0 = synth.CSR(0, 5, np.zeros(1, np.int32), np.zeros(0, np.int32), np.zeros(0))
-    with handle(m0) as h:
+    sh.m_zero_is_converged(ROW)
+    with handle(sh.empty_csr(n=5)) as h:
         x, res = h.lsqr(np.zeros(0), np.full(5, CANARY), max_iterations=5)
-    assert (res["status"], res["iterations"], res["rr"], res["bb"]) == (lc.CONVERGED, 0, 0.0, 0.0) and not x.any()
+    assert sh.converged_at_zero(res) and not x.any()
     nnz0 = synth.CSR(7, 5, np.zeros(8, np.int32), np.zeros(0, np.int32), np.zeros(0))
     b = lc.rhs(7, np.float64)
     with handle(nnz0) as h:
@@ -225,34 +166,13 @@ def test_no_rows_no_entries():
 def test_host_device_and_unaligned_pointers_give_the_same_bits(dtype):
     import torch
     m, n = 4099, 1030
-    csr = lc.sparse_rect(m, n, dtype, seed=6)
     b, guess = lc.rhs(m, dtype, 6), lc.rhs(n, dtype, 7)
-    pad = 16 // np.dtype(dtype).itemsize                 # canaries of one 16-byte unit each side keep X aligned; + 1 element: not
-    budget = 5
-    with handle(csr) as h:
-        for x0 in (None, guess):
-            want, wres = solve(h, b, x0, damp=0.125, rtol=0.0, ls_tol=0.0, max_iterations=budget)
-            assert wres["iterations"] == budget
-            for shift_b, shift_x in ((0, 0), (1, 0), (0, 1), (1, 1)):
-                bd = torch.zeros(m + 1, dtype=torch.from_numpy(b).dtype, device=DEV)[shift_b:shift_b + m]
-                bd.copy_(torch.from_numpy(b))
-                buf = torch.full((n + 2 * pad + 1,), CANARY, dtype=bd.dtype, device=DEV)
-                xd = buf[pad + shift_x:pad + shift_x + n]
-                assert (bd.data_ptr() % 16 != 0) == bool(shift_b) and (xd.data_ptr() % 16 != 0) == bool(shift_x)
-                if x0 is not None:
-                    xd.copy_(torch.from_numpy(x0))
-                got, res, hist = h.lsqr(bd, xd, x0=x0 is not None, damp=0.125, rtol=0.0, ls_tol=0.0, max_iterations=budget, history=True)
-                torch.cuda.synchronize()
-                assert got is xd and same_bits(xd.cpu().numpy(), want), (shift_b, shift_x)
-                assert same_bits(hist, wres["history"]) and (res["rr"], res["ar"], res["anorm"]) == (wres["rr"], wres["ar"], wres["anorm"])
-                out = buf.cpu().numpy()
-                assert (out[:pad + shift_x] == CANARY).all() and (out[pad + shift_x + n:] == CANARY).all(), "written outside X"
-            # mixed: device B, host X; and x allocated like b
-            xh = np.full(n, CANARY, dtype=dtype) if x0 is None else x0.copy()
-            h.lsqr(torch.from_numpy(b).to(DEV), xh, x0=x0 is not None, damp=0.125, rtol=0.0, ls_tol=0.0, max_iterations=budget)
-            assert same_bits(xh, want)
-        xa, _ = h.lsqr(torch.from_numpy(b).to(DEV), damp=0.125, rtol=0.0, ls_tol=0.0, max_iterations=budget)
+    kw = dict(damp=0.125, rtol=0.0, ls_tol=0.0, max_iterations=5)
+
+    def x_allocated_like_b(h):
+        xa, _ = h.lsqr(torch.from_numpy(b).to(DEV), **kw)
         assert xa.shape == (n,) and xa.device.type == "cuda"
+    sh.pointers_give_the_same_bits(ROW, lc.sparse_rect(m, n, dtype, seed=6), b, guess, kw, lambda res: res["iterations"] == 5, last=x_allocated_like_b)
 
 
 # ----------------------------------------------------------------------------- 6. the values change
@@ -295,50 +215,18 @@ def test_cg_has_the_same_bits_before_and_after_an_lsqr_call(dtype):
 
 # ----------------------------------------------------------------------------- 7. handle rules
 def test_argument_errors_leave_x_untouched(_lib):
-    lib = _lib
-    csr = lc.sparse_rect(300, 40)
-    b = lc.rhs(csr.m, np.float64)
-    x = np.full(csr.n, CANARY)
-    rp, ci, va = csr.rowptr, csr.colidx, csr.val
-
-    def call(h, opt, res, B=b, X=x, mat=csr):
-        lib.spmv_hip_clear_error()
-        rc = lib.spmv_hip_lsqr(h, mat.m, api._ptr(mat.rowptr), api._ptr(mat.colidx), api._ptr(mat.val), api._ptr(B), api._ptr(X), opt, res)
-        assert lib.spmv_hip_last_error() == rc
-        lib.spmv_hip_clear_error()
-        return rc
-
-    def options(**kw):
-        base = dict(rtol=1e-8, atol=0.0, ls_tol=1e-8, damp=0.0, max_iterations=10, check_every=0, use_x0=0)
-        base.update(kw)
-        return C.byref(api.spmv_hip_lsqr_options(**base))
-
-    res = C.byref(api.spmv_hip_lsqr_result())
     nan = float("nan")
-    with handle(csr) as h:
-        assert call(h.h, None, res) == E_ARG and call(h.h, options(), None) == E_ARG
-        assert call(h.h, options(), res, B=None) == E_ARG and call(h.h, options(), res, X=None) == E_ARG
-        for bad in (dict(max_iterations=-1), dict(check_every=-1), dict(rtol=-1e-3), dict(atol=-1.0), dict(ls_tol=-1e-3), dict(damp=-0.5), dict(rtol=nan), dict(atol=nan),
-                    dict(ls_tol=nan), dict(damp=nan)):
-            assert call(h.h, options(**bad), res) == E_ARG, bad
-        assert call(None, options(), res) == E_ARG
-        assert (x == CANARY).all()
-        assert call(h.h, options(), res) == 0 and not (x == CANARY).any()             # the same call with good arguments runs
-    x[:] = CANARY
-    for key, way in (("gpus", api.VECTORIZED_WAY.VECTOR_HIP), ("host_rows", api.VECTORIZED_WAY.VECTOR_NONE)):
-        with handle(csr, M.Method_Serial, way, **{key: 1}) as h:
-            assert call(h.h, options(), res) == E_ARG, key
-    square = cgc.dominant(4096)
-    xs, bs = np.full(square.m, CANARY), cgc.rhs(square.m, np.float64)
-    with handle(square, reorder=1) as h:
-        assert h.index is not None
-        assert call(h.h, options(), res, B=bs, X=xs, mat=square) == E_ARG
-    assert (xs == CANARY).all()
-    h = handle(csr)
-    api.spmv_clear_handle(h.h)
-    assert call(h.h, options(), res) == E_NOSTATE
-    h.close()
-    assert (x == CANARY).all()
+    bad = (dict(max_iterations=-1), dict(check_every=-1), dict(rtol=-1e-3), dict(atol=-1.0), dict(ls_tol=-1e-3), dict(damp=-0.5), dict(rtol=nan), dict(atol=nan),
+           dict(ls_tol=nan), dict(damp=nan))
+
+    def a_reordered_handle(call, options, res):
+        square = cgc.dominant(4096)
+        xs, bs = np.full(square.m, CANARY), cgc.rhs(square.m, np.float64)
+        with handle(square, reorder=1) as h:
+            assert h.index is not None
+            assert call(h.h, options(), res, B=bs, X=xs, mat=square) == E_ARG
+        assert (xs == CANARY).all()
+    sh.argument_errors(ROW, _lib, lc.sparse_rect(300, 40), bad=bad, square=False, after=a_reordered_handle)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -349,7 +237,7 @@ def test_workspace_transpose_and_timer(dtype):
     csr = lc.sparse_rect(4099, 1030, dtype, seed=9)
     b = lc.rhs(csr.m, dtype, 9)
     item = np.dtype(dtype).itemsize
-    ws = lc.workspace_bytes(csr.m, csr.n, item)
+    ws = ROW.workspace(csr.m, csr.n, item)
     bd = torch.from_numpy(b).to(DEV)
     with handle(csr, M.Method_Serial) as h:
         before = h.info()["device_bytes"]
@@ -365,7 +253,7 @@ def test_workspace_transpose_and_timer(dtype):
         assert same_bits(x1.cpu().numpy(), xd.cpu().numpy()) and res1 == res
         x2, res2 = h.lsqr(bd, rtol=0.0, ls_tol=0.0, max_iterations=4)
         assert h.info()["device_bytes"] == before + transpose + ws and same_bits(x2.cpu().numpy(), x1.cpu().numpy())
-        mean, runs = api.time_lsqr_iterations(h.h, bd, x2, 6, warmup=1, iters=3)
+        mean, runs = ROW.timer(h.h, bd, x2, 6, warmup=1, iters=3)
         assert mean > 0 and runs.shape == (3,) and (runs > 0).all()
         assert h.info()["device_bytes"] == before + transpose + ws
         xc = torch.empty(csr.n, dtype=bd.dtype, device=DEV)

@@ -6,72 +6,37 @@ ar, anorm and the history are compared bit for bit and no tolerance appears anyw
 payload; and, as in tests/test_gpu_lsqr.py, rr, bb and the history are not compared where the solve ends in begin:nonfinite.  The cases come from
 tests/lsqr_end_cases.py, whose every line tests/test_lsqr_ends_host.py proves on the CPU first; here each case must also reach the (status,
 iterations, end) it declares under the handle's own multiplies -- bits that match a model which ends elsewhere would mean the INPUT is wrong,
-not the kernel."""
+not the kernel.  The bodies that the solvers share are in tests/solve_harness.py."""
+import functools
+
 import numpy as np
 import pytest
 
 import lsqr_cases as lc
 import lsqr_end_cases as le
-import packed_cases as pc
 import solve_end_cases as sec
-from spmv_amd import api, build
-from test_gpu_solve_ends import EXECUTORS, LONG_ROW_KERNELS, METHODS, handle, same
+import solve_harness as sh
+from solve_harness import CANARY, DEV, EVERY, METHODS, handle, multiplies_with_transpose, same
+from spmv_amd import api
 
 pytestmark = pytest.mark.gpu
 
-M = api.SPMV_METHODS
-DEV = "cuda:0"
-CANARY = -7.25
+ROW = sh.ROWS["lsqr"]
 NAMES, RUNS, run_id, ended, declared = le.NAMES, le.RUNS, le.run_id, le.ended, le.declared
-EVERY = (1, 2, 3, 0, 64)           # check_every: the end falls first, in the middle and last in an enqueued batch
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _lib():
-    build.build()
-    lib = api.load()
-    assert lib.spmv_hip_device_count() > 0, "GPU tests need a device"
-    return lib
+    return sh.library()
 
 
-def multiplies_of(h):
-    """the model's two multiplies: this handle's spmv() and spmv_transpose() on host vectors"""
-    def multiply(v):
-        return h.spmv(np.ascontiguousarray(v), np.empty(h.m, dtype=v.dtype))
-
-    def multiply_t(u):
-        return h.spmv_transpose(np.ascontiguousarray(u))
-    return multiply, multiply_t
+check = functools.partial(sh.check, ROW)
+solve = functools.partial(sh.solve0, ROW)
 
 
 def model_of(h, b, x0=None, **kw):
     kw.pop("check_every", None)
-    return lc.lsqr(*multiplies_of(h), b, h.n, x0=x0, **kw)
-
-
-def solve(h, b, x0=None, **kw):
-    """through host pointers, with a canary in X when there is no guess -> (x, result dict with history)"""
-    x = np.full(h.n, CANARY, dtype=b.dtype) if x0 is None else x0.copy()
-    kw.setdefault("rtol", 0.0)
-    kw.setdefault("ls_tol", 0.0)
-    x, res, hist = h.lsqr(b, x, x0=x0 is not None, history=True, **kw)
-    res["history"] = hist
-    return x, res
-
-
-def f64(v):
-    return np.float64(v)
-
-
-def check(model, x, res, what=None):
-    """a run against a model run with the same arguments, however either ended"""
-    assert (res["status"], res["iterations"]) == (model["status"], model["iterations"]), (what, res, model["end"])
-    assert same(x, model["x"]), (what, "x", model["end"])
-    assert same(f64(res["ar"]), f64(model["ar"])) and same(f64(res["anorm"]), f64(model["anorm"])), (what, res, model["ar"], model["anorm"])
-    if model["end"] == "begin:nonfinite":
-        return
-    assert same(f64(res["rr"]), f64(model["rr"])) and same(f64(res["bb"]), f64(model["bb"])), (what, res, model["rr"], model["bb"])
-    assert same(res["history"], model["history"]), (what, res["history"], model["history"])
+    return ROW.model(h, b, x0=x0, **kw)
 
 
 def budget_edges(h, case, b, x0, model, what, everys=(0, 1), budgets=None):
@@ -79,19 +44,15 @@ def budget_edges(h, case, b, x0, model, what, everys=(0, 1), budgets=None):
     iteration reports (tests/test_gpu_lsqr.py: check_against): the end itself where lsqr_step finds it BEHIND the iteration it applied; where
     it is found while making iteration `iterations` + 1, a budget of `iterations` never sees it"""
     k = case.iterations
-    for budget in (k - 1, k, k + 1) if budgets is None else budgets:
-        if budget < 0:
-            continue
-        kw = le.keywords(case, max_iterations=budget)
-        short = model_of(h, b, x0, **kw)
+
+    def expect(budget, short):
         if budget < k or (budget == k and case.end in le.MAKING) or (budget == k and case.end == "budget"):
             assert ended(short) == (lc.MAX_ITERATIONS, budget, "budget"), (what, budget, ended(short))
             assert same(short["x"], model["iterates"][budget]) and same(short["history"], model["history"][:budget + 1]), (what, budget)
         elif case.end != "budget":
             assert ended(short) == ended(model), (what, budget)
-        for every in everys:
-            x, res = solve(h, b, x0, check_every=every, **kw)
-            check(short, x, res, what + (budget, every))
+    sh.budget_edges(k, lambda budget: model_of(h, b, x0, **le.keywords(case, max_iterations=budget)),
+                    lambda budget, every: solve(h, b, x0, check_every=every, **le.keywords(case, max_iterations=budget)), expect, what, check, everys, budgets)
 
 
 # ----------------------------------------------------------------------------- 1. every end, anywhere in a batch, at every budget edge
@@ -148,6 +109,9 @@ def test_atol_decides_with_less_or_equal(dtype):
         with handle(csr) as h:
             def model(atol, rtol=0.0):
                 return model_of(h, b, damp=damp, rtol=rtol, atol=atol, max_iterations=budget)
+
+            def run(**kw):
+                return solve(h, b, damp=damp, max_iterations=budget, **kw)
             probes = sec.atol_probes(model)
             picks = le.probe_picks(probes, budget)
             print(f"{name} {NAMES[dtype]}: {len(probes)} places where rr is a square: {[k for _, k, _ in probes]}; taken {[k for _, k, _ in picks]}")
@@ -155,32 +119,10 @@ def test_atol_decides_with_less_or_equal(dtype):
             for a, k, end in picks:
                 what = (name, a, k, end)
                 places.add((end, k))
-                below = float(np.nextafter(a, 0.0))
-                at, under = model(a), model(below)
-                assert ended(at) == (lc.CONVERGED, k, end) and at["rr"] == a * a and under["iterations"] > k, (what, ended(at), ended(under))
-                for every in (1, 0):
-                    x, res = solve(h, b, damp=damp, atol=a, max_iterations=budget, check_every=every)
-                    check(at, x, res, what)
-                    x, res = solve(h, b, damp=damp, atol=below, max_iterations=budget, check_every=every)
-                    check(under, x, res, what + ("below",))
-                # rtol^2 bb is the smaller: atol still decides, at the same place
-                small = 2.0 ** -30
-                while small * small * at["bb"] >= a * a:
-                    small *= 2.0 ** -30
-                both = model(a, small)
-                assert ended(both) == ended(at)
-                x, res = solve(h, b, damp=damp, rtol=small, atol=a, max_iterations=budget)
-                check(both, x, res, what + ("rtol below",))
-                # ... and the reverse: atol^2 is the smaller, rtol decides: the run ends where atol alone does not end it
-                rtol = 2.0 ** 20
-                while rtol * rtol * at["bb"] / 4 >= at["rr"]:
-                    rtol /= 2                                                      # the smallest power of two with rtol^2 bb >= rr
-                low = a * 2.0 ** -10
-                by_rtol, alone = model(low, rtol), model(low)
-                assert rtol * rtol * at["bb"] >= at["rr"] > low * low and by_rtol["status"] == lc.CONVERGED and by_rtol["iterations"] <= k
-                assert ended(alone) != ended(by_rtol), what
-                x, res = solve(h, b, damp=damp, rtol=rtol, atol=low, max_iterations=budget)
-                check(by_rtol, x, res, what + ("rtol above",))
+
+                def before(at, under):
+                    assert ended(at) == (lc.CONVERGED, k, end) and at["rr"] == a * a and under["iterations"] > k, (what, ended(at), ended(under))
+                sh.atol_ladder(model, run, check, a, k, what, before)
     assert ("begin:converged", 0) in places and any(end == "step:converged" and k > 1 for end, k in places), places
 
 
@@ -198,7 +140,7 @@ def test_bb_zero_and_begin_ends_with_device_pointers(dtype):
         nan_b = lc.rhs(m, dtype, 16)
         nan_b[m // 2] = np.nan
         with handle(csr) as h:
-            mul, _ = multiplies_of(h)
+            mul, _ = multiplies_with_transpose(h)
             solved = mul(guess)                                                  # B = A x0 in the handle's own bits: u = B - A x0 is exactly 0
             assert solved.any() and guess.all()
             runs = (("zero_b", np.zeros(m, dtype=dtype), None, "begin:bb_zero"), ("zero_b_guess", np.zeros(m, dtype=dtype), guess, "begin:bb_zero"),
@@ -238,7 +180,7 @@ def test_a_solve_is_unaffected_by_what_earlier_solves_left(dtype):
     the model, twice over, in a workspace that never grows"""
     csr, runs = le.state_system(dtype)
     with handle(csr) as h:
-        mul, mul_t = multiplies_of(h)
+        mul, mul_t = multiplies_with_transpose(h)
         assert runs[0][0] == "huge_guess" and (~np.isfinite(mul(runs[0][2]))).sum() > 100           # A x0 overflows
         mul_t(np.zeros(csr.m, dtype=dtype))                     # both of the model's multiplies now own their staging buffers (and the transpose is
                                                                 # built): device_bytes moves no more on their account.  The solver has nothing yet
@@ -268,21 +210,21 @@ def test_the_timed_launches_do_the_arithmetic_of_the_solve(dtype):
                 model = model_of(h, b, damp=damp, max_iterations=k + 1)
                 assert ended(model) == (lc.MAX_ITERATIONS, k + 1, "budget"), what             # still going behind iteration k
                 xd = torch.full((csr.n,), CANARY, dtype=bd.dtype, device=DEV)
-                mean, runs = api.time_lsqr_iterations(h.h, bd, xd, k, damp=damp, warmup=1, iters=2)   # every run starts from x = 0
+                mean, runs = ROW.timer(h.h, bd, xd, k, damp=damp, warmup=1, iters=2)   # every run starts from x = 0
                 torch.cuda.synchronize()
                 assert mean > 0 and runs.shape == (2,) and same(xd.cpu().numpy(), model["iterates"][k]), ("timer",) + what
                 from_guess, res = solve(h, b, guess, damp=damp, max_iterations=k)
                 assert (res["status"], res["iterations"]) == (lc.MAX_ITERATIONS, k) and not same(from_guess, model["iterates"][k])
                 check(model_of(h, b, guess, damp=damp, max_iterations=k), from_guess, res, ("guess",) + what)
                 xd.copy_(torch.from_numpy(guess))
-                api.time_lsqr_iterations(h.h, bd, xd, k, damp=damp, x0=True, warmup=0, iters=1)        # one run: from the guess in X
+                ROW.timer(h.h, bd, xd, k, damp=damp, x0=True, warmup=0, iters=1)        # one run: from the guess in X
                 torch.cuda.synchronize()
                 assert same(xd.cpu().numpy(), from_guess), ("timer, x0",) + what
                 # a second run with use_x0 starts from what the first left in X: two chained solves of k iterations, not one of 2 k
                 again, res = solve(h, b, from_guess, damp=damp, max_iterations=k)
                 assert res["iterations"] == k and not same(again, from_guess)
                 xd.copy_(torch.from_numpy(guess))
-                api.time_lsqr_iterations(h.h, bd, xd, k, damp=damp, x0=True, warmup=1, iters=1)
+                ROW.timer(h.h, bd, xd, k, damp=damp, x0=True, warmup=1, iters=1)
                 torch.cuda.synchronize()
                 assert same(xd.cpu().numpy(), again), ("timer, x0 twice",) + what
 
@@ -313,42 +255,18 @@ def test_every_executor_under_lsqr(method, dtype):
     carry crosses every CSR5 / nnz-split tile boundary.  As built, and on the row-block x column-slab executor (cache_block = 2; CSR-scalar
     schedules never take it)"""
     csr = le.arrow_rect(2049, 1030, dtype)
-    first, long_rows = EXECUTORS[method]
-    with handle(csr, method) as h:
-        info = h.info()
-        names = info["launch_kernels"]
-        assert info["max_row_len"] == 1030 and info["cache_blocked"] == 0 and info["far_nnz"] == 0, info
-        assert first is None or names[0] == first, names
-        if long_rows:
-            assert len(names) == 3 and names[1] in LONG_ROW_KERNELS and names[2] == "csr5_fixup_kernel", names
-        elif first != "csr_scalar_kernel":
-            assert names[-1] == "csr5_fixup_kernel" and names[0] in ("nat_group_kernel",) + LONG_ROW_KERNELS, names   # carries and their fix-up
-        nine_iterations(h, csr, dtype, 1)
+
+    def iterate(h, seed):
+        nine_iterations(h, csr, dtype, seed)
         transpose_of(h, 2049)
-    if first == "csr_scalar_kernel":
-        return
-    with handle(csr, method, cache_block=2) as h:
-        info = h.info()
-        assert info["cache_blocked"] == 1 and info["launch_kernels"] in (["blk_kernel"], ["blk_wide_kernel"]), info
-        nine_iterations(h, csr, dtype, 2)
-        transpose_of(h, 2049)
+    sh.every_executor(csr, method, iterate, longest=1030)
 
 
 @pytest.mark.parametrize("dtype", le.BOTH, ids=NAMES.get)
 def test_the_long_row_launch_beside_the_tile_kernel_and_packed_tiles(dtype):
     """rows of 32 aligned entries at 8 lanes per row run on the CSR-vector TILE kernel; row 300 (544 entries > long_thr = 512) goes to the
     long-row launch behind it.  fp64 also with pack_values = 1: every tile but row 300's streams 7-byte values"""
-    csr = sec.band32(1280, dtype, long_row=300)
-    for pack in (0, 1) if dtype == np.float64 else (0,):
-        with handle(csr, M.Method_Parallel, lanes_per_row=8, pack_values=pack) as h:
-            info = h.info()
-            names = info["launch_kernels"]
-            assert info["lanes_per_row"] == 8 and info["max_row_len"] == 544, info
-            assert len(names) == 3 and names[0] == pc.TILE_KERNEL and names[1] in LONG_ROW_KERNELS and names[2] == "csr5_fixup_kernel", names
-            if pack:
-                want, flags = pc.model_packed(csr.rowptr, csr.val, 8)
-                assert flags == [True, False, True, True, True] and info["packed_nnz"] == want == info["nnz"] - (255 * 32 + 544) > 0, info
-            else:
-                assert info["packed_nnz"] == 0
-            nine_iterations(h, csr, dtype, 3 + pack)
-            transpose_of(h, int(np.bincount(csr.colidx, minlength=csr.n).max()))
+    def iterate(h, csr, seed):
+        nine_iterations(h, csr, dtype, seed)
+        transpose_of(h, int(np.bincount(csr.colidx, minlength=csr.n).max()))
+    sh.the_long_row_launch_beside_the_tile_kernel(dtype, iterate)
